@@ -41,7 +41,7 @@ import time
 ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
 
-HBM_PEAK_GBS = 8000.0  # /opt/skills/guides/MI355X_MICROARCH.md: HBM3E 8.0 TB/s spec
+HBM_PEAK_GBS = 8000.0  # MI355X: HBM3E 8.0 TB/s spec
 
 CONFIGS = {
     # name: (docs, vocab, corpus_seed, nq, terms, limit)
@@ -92,7 +92,33 @@ def parse_args():
                     help="caller threads of the request-coalescer leg (config c2, N = 1; 0: skip the leg)")
     ap.add_argument("--force-dist", action="store_true",
                     help="initialise torch.distributed (RCCL) even for one rank")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the timed path returned in its last step (rank 0) "
+                         "as DIR/<name>.npy, for comparing two builds output for output")
     return ap.parse_args()
+
+
+DUMP_MAX_BYTES = 64 << 20
+RESULT_NAMES = ("doc_ids", "seg_ids", "scores", "counts")  # the arrays slg_batch_fetch fills
+
+
+def dump_outputs(out_dir, arrays):
+    """--dump-outputs: `arrays` (name -> array whose rows are queries) as <name>.npy, floats as float32 and
+    integers as float64 (exact for 32-bit ids and counts).  Above DUMP_MAX_BYTES a fixed, seeded sample of
+    the rows is written; query_rows.npy names the rows written either way."""
+    import numpy as np
+    arrays = {name: np.asarray(a, np.float32 if np.asarray(a).dtype.kind == "f" else np.float64)
+              for name, a in arrays.items()}
+    nq = len(next(iter(arrays.values())))
+    row_bytes = 8 + sum(a[:1].nbytes for a in arrays.values())  # (8: the row's entry in query_rows)
+    budget = DUMP_MAX_BYTES - 1024 * (len(arrays) + 1)  # (room for the .npy headers)
+    rows = np.arange(nq)
+    if nq * row_bytes > budget:
+        rows = np.sort(np.random.default_rng(0).choice(nq, budget // row_bytes, replace=False))
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "query_rows.npy"), rows.astype(np.float64))
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, f"{name}.npy"), a[rows])
 
 
 def spawn_ranks_if_needed(args):
@@ -240,6 +266,9 @@ def main():
         L.slh_error.argtypes = [C.c_void_p]
         L.slh_first_result.restype = C.c_int
         L.slh_first_result.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.slh_keep_step.argtypes = [C.c_void_p, C.c_int64]
+        L.slh_kept_result.restype = C.c_int
+        L.slh_kept_result.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         L.slh_destroy.argtypes = [C.c_void_p]
         L.slh_stats.argtypes = [C.c_void_p, C.c_void_p]
         L.slh_reset_stats.argtypes = [C.c_void_p]
@@ -262,6 +291,7 @@ def main():
         warm = max(warmup, 2 * c4_threads)
         run_steps(warm, 0)
         L.slh_reset_stats(hh)
+        L.slh_keep_step(hh, warm + steps - 1)  # the last timed step's merged result (--dump-outputs)
         index.profile(True)
         group.stats()
         fence()
@@ -280,6 +310,9 @@ def main():
         if not L.slh_first_result(hh, 0, d0.ctypes.data, s0.ctypes.data, sc0.ctypes.data, c0.ctypes.data):
             raise RuntimeError("host harness (sharded): no result for query set 0")
         last_res = [(d0, s0, sc0, c0)]
+        kept = tuple(np.zeros_like(x) for x in last_res[0])
+        if not L.slh_kept_result(hh, *(x.ctypes.data for x in kept)):
+            raise RuntimeError("host harness (sharded): no result for the last timed step")
         L.slh_destroy(hh)
         res = tuple(np.asarray(x).copy() for x in last_res[0])
         last_q = qs[0]  # (the harness keeps the first result of every query set: set 0)
@@ -323,7 +356,7 @@ def main():
                "postings_per_batch_this_rank": int(np.mean([p["n_postings"] for p in postings])),
                "index_postings_this_rank": int(info["n_postings"]), "corpus_build_s": round(t_corpus, 1)}
         out["roofline_this_rank"] = roof
-        return out, res, last_q, (n_docs, vocab, cseed, nq, T, k)
+        return out, res, last_q, dict(zip(RESULT_NAMES, kept))
 
     n_docs, vocab, cseed, nq, T, limit = CONFIGS[args.config]
     n_docs = args.docs or n_docs
@@ -334,7 +367,7 @@ def main():
     out = None
 
     if args.config == "c4":
-        c4, res, last_q, _ = run_sharded("c4", args.steps, args.warmup)
+        c4, res, last_q, last_out = run_sharded("c4", args.steps, args.warmup)
         if rank == 0:
             out = {"metric": "queries/sec at top-10 (batch=1024) + achieved HBM GB/s vs peak",
                    "value": c4["queries_per_s"], "unit": "queries/s", "n_gpus": world, "steps": args.steps,
@@ -358,6 +391,8 @@ def main():
                 if not ok:
                     print(json.dumps(out))
                     raise SystemExit("bench.py: GPU results differ from the oracle")
+            if args.dump_outputs:
+                dump_outputs(args.dump_outputs, last_out)
             print(json.dumps(out), flush=True)
         if use_dist:
             dist.barrier()
@@ -413,6 +448,9 @@ def main():
             L.slh_error.argtypes = [C.c_void_p]
             L.slh_first_result.restype = C.c_int
             L.slh_first_result.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+            L.slh_keep_step.argtypes = [C.c_void_p, C.c_int64]
+            L.slh_kept_result.restype = C.c_int
+            L.slh_kept_result.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
             L.slh_destroy.argtypes = [C.c_void_p]
             L.slh_stats.argtypes = [C.c_void_p, C.c_void_p]
             L.slh_reset_stats.argtypes = [C.c_void_p]
@@ -434,6 +472,14 @@ def main():
             ok = self.L.slh_first_result(self.h, j, d.ctypes.data, s_.ctypes.data, sc.ctypes.data, c.ctypes.data)
             return (d, s_, sc, c) if ok else None
 
+        def kept_result(self):
+            """The result of the step named by slh_keep_step, as name -> host array."""
+            out = (np.zeros((nq, k), np.uint32), np.zeros((nq, k), np.uint32), np.zeros((nq, k), np.float32),
+                   np.zeros(nq, np.uint32))
+            if not self.L.slh_kept_result(self.h, *(a.ctypes.data for a in out)):
+                raise RuntimeError("host harness: no result for the last timed step")
+            return dict(zip(RESULT_NAMES, out))
+
         def stats(self):
             import ctypes as C
             out = (C.c_double * 4)()
@@ -448,7 +494,7 @@ def main():
             self.L.slh_destroy(self.h)
             self.h = None
 
-    value = ms_per_step = value_spread = host_ms = None
+    value = ms_per_step = value_spread = host_ms = last_out = None
     if not rerank and not plans and not args.kernel_leg_only:
         pool = HostPool()
         # untimed: --warmup steps, and at least three batches per caller thread so that every
@@ -460,12 +506,15 @@ def main():
         # (a 20-step region is 2.5 ms: 2.5 steps per caller thread with the pipeline's fill and drain
         # inside) and `value` is the MEDIAN region; the spread is reported beside it
         region_s = []
-        for r in range(max(1, args.regions)):
+        n_regions = max(1, args.regions)
+        pool.L.slh_keep_step(pool.h, host_warm + n_regions * args.steps - 1)  # the last timed step (--dump-outputs)
+        for r in range(n_regions):
             fence()
             t1 = time.perf_counter()
             pool.run(args.steps, host_warm + r * args.steps)
             fence()
             region_s.append(max_over_ranks(time.perf_counter() - t1))
+        last_out = pool.kept_result()
         hp0 = pool.first_result(0)
         if hp0 is not None:
             first_results[0] = hp0
@@ -532,6 +581,13 @@ def main():
     resident_qps = nq * world / (res_elapsed / args.steps)
     if rerank or plans:
         value, ms_per_step = resident_qps, res_elapsed / args.steps * 1e3
+        if args.dump_outputs:  # the last timed step's outputs, before the legs below reuse the buffers
+            j = (turn[0] - 1) % n_sets
+            if rerank:
+                last_out = {name: t.cpu().numpy() for name, t in
+                            zip(("doc_ids", "seg_ids", "scores", "vector_scores", "counts"), r_sets[j % inflight])}
+            else:
+                last_out = dict(zip(RESULT_NAMES, batches[j].fetch()))
 
     # ---- leg 3: the scoring kernel alone (HIP events on its launch stream), batches rotating ----
     for b in batches:
@@ -550,6 +606,8 @@ def main():
     if args.kernel_leg_only:
         value = nq * world / (kern_ms / max(n_launch, 1) * 1e-3)
         ms_per_step = kern_ms / max(n_launch, 1)
+        if args.dump_outputs:  # the last launch of this leg
+            last_out = dict(zip(RESULT_NAMES, batches[-1].fetch()))
     total_postings = sum_over_ranks(float(np.mean([i["n_postings"] for i in infos])))
     touched = np.unique(np.concatenate([np.asarray(q[1]).reshape(-1) for q in qs]))
     working_set_postings = int((seg.term_offsets[touched.astype(np.int64) + 1] - seg.term_offsets[touched.astype(np.int64)]).sum())
@@ -848,6 +906,8 @@ def main():
         if rank == 0:
             out["c4"] = c4
     if rank == 0:
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, last_out)
         print(json.dumps(out), flush=True)
     if use_dist:
         dist.barrier()

@@ -59,6 +59,12 @@ struct Harness {
   std::vector<std::vector<uint32_t>> first_doc, first_seg, first_count;
   std::vector<std::vector<float>> first_score;
   std::vector<char> have_first;
+  // result of the step chosen by slh_keep_step (bench.py --dump-outputs: the last timed step); collect()
+  // swaps the worker's buffers with these, so keeping it costs no copy inside the timed region
+  int64_t keep_step = -1;
+  bool have_kept = false;
+  std::vector<uint32_t> kept_doc, kept_seg, kept_count;
+  std::vector<float> kept_score;
 };
 
 struct Pending {
@@ -84,6 +90,13 @@ void collect(Harness *h, Pending &p, std::vector<uint32_t> &doc, std::vector<uin
       h->first_score[set] = score;
       h->first_count[set] = count;
       h->have_first[set] = 1;
+    }
+    if (rc == SLG_OK && p.step == h->keep_step) {
+      doc.swap(h->kept_doc);
+      seg.swap(h->kept_seg);
+      score.swap(h->kept_score);
+      count.swap(h->kept_count);
+      h->have_kept = true;
     }
     h->done++;
   }
@@ -165,6 +178,11 @@ void *slh_create(slg_index *ix, int device, int n_threads, int n_sets, const uin
   h->first_score.resize(n_sets);
   h->first_count.resize(n_sets);
   h->have_first.assign(n_sets, 0);
+  const size_t n = (size_t)nq * k;  // the sizes of a worker's buffers (worker_main), which these swap with
+  h->kept_doc.resize(n ? n : 1);
+  h->kept_seg.resize(n ? n : 1);
+  h->kept_score.resize(n ? n : 1);
+  h->kept_count.resize(nq ? nq : 1);
   (void)hipSetDevice(device);
   for (int t = 0; t < n_threads; t++) {
     auto *w = new Worker();
@@ -179,8 +197,8 @@ void *slh_create(slg_index *ix, int device, int n_threads, int n_sets, const uin
 // the first slh_run; from then on the step numbers must be 0, 1, 2, ... on every rank.
 void slh_set_group(void *hp, slg_shard_group *group) { static_cast<Harness *>(hp)->group = group; }
 
-// the most recent result of a worker thread is not kept; for parity checks bench.py reads the FIRST
-// result of every query set (slh_first_result)
+// the most recent result of a worker thread is not kept (only the step named by slh_keep_step is); for
+// parity checks bench.py reads the FIRST result of every query set (slh_first_result)
 
 // Runs steps [first, first + n_steps), round-robin over the threads, and returns when every one of
 // them has been fetched.  0 on success, -1 on error (slh_error).
@@ -342,6 +360,27 @@ int slh_first_result(void *hp, int set, uint32_t *doc, uint32_t *seg, float *sco
   std::memcpy(seg, h->first_seg[set].data(), n * 4);
   std::memcpy(score, h->first_score[set].data(), n * 4);
   std::memcpy(count, h->first_count[set].data(), (size_t)h->nq * 4);
+  return 1;
+}
+
+// keep the result of step `step` (-1: none) for slh_kept_result; call it between slh_run calls
+void slh_keep_step(void *hp, int64_t step) {
+  auto *h = static_cast<Harness *>(hp);
+  std::lock_guard<std::mutex> lk(h->done_mu);
+  h->keep_step = step;
+  h->have_kept = false;
+}
+
+// the result of the step named by slh_keep_step; returns 1 if that step has been fetched
+int slh_kept_result(void *hp, uint32_t *doc, uint32_t *seg, float *score, uint32_t *count) {
+  auto *h = static_cast<Harness *>(hp);
+  std::lock_guard<std::mutex> lk(h->done_mu);
+  if (!h->have_kept) return 0;
+  const size_t n = (size_t)h->nq * h->k;
+  std::memcpy(doc, h->kept_doc.data(), n * 4);
+  std::memcpy(seg, h->kept_seg.data(), n * 4);
+  std::memcpy(score, h->kept_score.data(), n * 4);
+  std::memcpy(count, h->kept_count.data(), (size_t)h->nq * 4);
   return 1;
 }
 

@@ -20,7 +20,9 @@
  * (slg_index_add_filter*: accept() = !is_deleted(doc) && filter(doc)); ScorePlan = any tree of Sum /
  * DisMax nodes up to SLG_MAX_PLAN_DEPTH levels above its leaves, each leaf the sum of one or more
  * scored terms (slg_batch_prepare_plans; the default is leaf i == query term i, summed);
- * k = limit + 1 up to 20 001; up to 32 scored terms per query and segment.
+ * k = limit + 1 up to 20 001; up to 32 scored terms per query and segment.  Field sorts (slg_batch_prepare_sorted):
+ * up to SLG_MAX_SORT_PARTS parts of numeric fast fields (i64 / f64) and _score, any order; keyword parts stay
+ * on the CPU.
  */
 #ifndef SEARCHLITE_GPU_H
 #define SEARCHLITE_GPU_H
@@ -292,6 +294,29 @@ int slg_index_add_filter_terms(slg_index *index, const uint32_t *term_ids, uint3
  * batch's index state) and may still run; the id may be handed out again by a later add. */
 int slg_index_remove_filter(slg_index *index, int filter_id);
 
+/* ---- sort fields (query/sort.rs: `sort` on numeric fast fields) -----------------------
+ * A numeric fast field registered once per index and named by id in sorted batches
+ * (slg_batch_prepare_sorted).  Per segment the doc's values as CSR: seg_offsets[s][n_docs + 1] into
+ * seg_values[s] (the reference's i64_values / f64_values, index/fastfields.rs:736-770: several values per
+ * doc allowed); an empty range = Missing; seg_offsets[s] == NULL = every doc of segment s Missing.  The
+ * library picks, on the host, the value the reference sorts by (query/sort.rs:300-345: Asc = min_by, Desc =
+ * max_by under partial_cmp(..).unwrap_or(Equal) — min_by keeps the first of equal elements, max_by the
+ * last; this decides NaN and -0.0 / +0.0) and keeps two device columns (an order-preserving u64 per order)
+ * and a presence bitmap; host arrays are borrowed for the call only.  Lifecycle as filters:
+ * slg_index_update_deleted keeps the columns, slg_index_remove_segment drops that segment's,
+ * slg_index_add_segment gives the new segment none (a sorted batch that names the field then fails with
+ * SLG_ERR_INVALID until it is registered again).  Return the field id (>= 0) or a negative error code;
+ * ids are never handed out again, so a stale id fails instead of naming another field. */
+#define SLG_MAX_SORT_PARTS 4u
+#define SLG_SORT_SCORE (-1) /* the `_score` part */
+enum { SLG_ORDER_ASC = 0, SLG_ORDER_DESC = 1 };
+int slg_index_add_sort_field_i64(slg_index *index, const uint32_t *const *seg_offsets,
+                                 const int64_t *const *seg_values);
+int slg_index_add_sort_field_f64(slg_index *index, const uint32_t *const *seg_offsets,
+                                 const double *const *seg_values);
+/* Batches already prepared with the field keep its columns (they belong to the batch's index state). */
+int slg_index_remove_sort_field(slg_index *index, int sort_field_id);
+
 /* ---- one-shot search (what a searchlite `gpu` shim calls) -------------------------- */
 
 /*
@@ -391,6 +416,34 @@ slg_batch *slg_batch_prepare_plans(slg_index *index, uint32_t nq, const uint32_t
                                    const uint32_t *q_term_ids, const float *q_weights,
                                    const slg_score_plans *plans_or_null, const int32_t *q_filter_or_null,
                                    uint32_t k, int strategy);
+/* Field-sorted batches (SortPlan::from_request with numeric fast fields, query/sort.rs:159-216).  One sort
+ * spec for the whole batch: parts compared in order (field = a sort field id, or SLG_SORT_SCORE; order =
+ * SLG_ORDER_*), a Missing value after every value in both orders, ties after all parts by segment asc, doc
+ * asc (SortKey::cmp, query/sort.rs:80-123).  Rows hold the top k (k = limit + 1 <= SLG_MAX_K) by that key
+ * over all segments, through slg_batch_run / _fetch / _device_results as any batch; out_score is the exact
+ * score (bit-identical to the score path) when a part is `_score`, else 0.0 (ScoreMode::MatchOnly,
+ * api/reader.rs:2936-2940).  Every query shape slg_batch_prepare_plans takes is accepted.  Every matched doc
+ * is scored (candidates mode, no threshold seed, no MaxScore): 8 bytes of device memory per posting of the
+ * batch.  More than SLG_MAX_SORT_PARTS parts or a keyword field: SLG_ERR_UNSUPPORTED (CPU scorer); an
+ * unknown sort field id or one without a column for every segment: SLG_ERR_INVALID. */
+typedef struct {
+  uint32_t n_parts;
+  int32_t field[SLG_MAX_SORT_PARTS]; /* sort field id, or SLG_SORT_SCORE */
+  int32_t order[SLG_MAX_SORT_PARTS]; /* SLG_ORDER_ASC | SLG_ORDER_DESC */
+} slg_sort_spec;
+slg_batch *slg_batch_prepare_sorted(slg_index *index, uint32_t nq, const uint32_t *q_offsets,
+                                    const uint32_t *q_term_ids, const float *q_weights,
+                                    const slg_score_plans *plans_or_null, const int32_t *q_filter_or_null,
+                                    const slg_sort_spec *sort, uint32_t k, int strategy);
+/* Accepted docs per query of a sorted batch's last run (total_matches, api/reader.rs:3026-3028: docs that
+ * pass tombstones, filter and minimum_should_match); waits for the batch.  SLG_ERR_INVALID for a batch
+ * that is not sorted. */
+int slg_batch_matched_counts(slg_batch *batch, uint64_t *out_matched);
+/* One-shot form: slg_search_batch_filtered with score plans and a sort spec; out_matched ([nq]) may be NULL. */
+int slg_search_batch_sorted(slg_index *index, const slg_query *queries, uint32_t nq,
+                            const slg_score_plans *plans_or_null, const int32_t *q_filter_or_null,
+                            const slg_sort_spec *sort, uint32_t k, int strategy, uint32_t *out_doc,
+                            uint32_t *out_seg, float *out_score, uint32_t *out_count, uint64_t *out_matched);
 /* Enqueue the partition / score / merge kernels on the batch's stream (asynchronous). */
 int slg_batch_run(slg_batch *batch);
 /* Run this batch on its own HIP stream instead of the index stream, so several prepared

@@ -40,7 +40,7 @@ let gpu_hits: Option<Vec<RankedHit>> = (|| {
   let folded = crate::gpu::fold_terms(
     qualified_terms.iter().map(|t| (t.key.as_str(), t.weight, t.leaf)),
   );
-  let (score_plan, n_leaves, min_match) = crate::gpu::gpu_eligible(
+  let (score_plan, n_leaves, min_match, sort_parts) = crate::gpu::gpu_eligible(
     req, &sort_plan, &query_plan, needs_score_hook, top_k, folded.len(),
   )?;
   // term keys of the matcher's not-term groups (api/reader.rs:1499-1503): rejected on the device by a filter
@@ -56,11 +56,12 @@ let gpu_hits: Option<Vec<RankedHit>> = (|| {
   };
   match crate::gpu::gpu_top_k(
     gpu, &self.segments, &folded, &score_plan, n_leaves, min_match, req.filter.as_ref(), &not_keys,
-    &req.execution, top_k,
+    &req.execution, top_k, sort_parts.as_deref(),
   ) {
     Ok((rows, scored)) => {
       // total_hits_estimate: the CPU path counts the docs `accept` saw (pruning-dependent under
-      // Wand/Bmw, api/reader.rs:3029-3031); the device reports every distinct doc it scored
+      // Wand/Bmw, api/reader.rs:3029-3031); the device reports every distinct doc it scored — and for a
+      // field sort the docs it accepted, which is the CPU collector path's own count (:3026-3028)
       total_matches = scored;
       Some(
         rows
@@ -88,3 +89,18 @@ if let Some(h) = gpu_hits {
 // for (segment_ord, seg) in self.segments.iter().enumerate() {   // :2670
 //   if skip_cpu_segments { break; }
 //   ...
+//
+// (3) query/sort.rs gains the accessor gpu_eligible reads (SortPlan's fields are private to the module):
+//
+//       #[cfg(feature = "gpu")]
+//       impl SortPlan {
+//         pub(crate) fn gpu_parts(&self) -> Vec<crate::gpu::GpuSortPart> {
+//           use crate::gpu::GpuSortPart as P;
+//           self.fields.iter().map(|f| match &f.field {
+//             SortField::Score => P::Score(f.order),
+//             SortField::I64(name) => P::I64(name.clone(), f.order),
+//             SortField::F64(name) => P::F64(name.clone(), f.order),
+//             SortField::Keyword(_) => P::Keyword,
+//           }).collect()
+//         }
+//       }

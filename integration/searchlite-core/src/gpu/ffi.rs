@@ -44,6 +44,10 @@ pub struct slg_tuning {
     pub q_node_offsets: *const u32, pub node_kind: *const i32, pub node_tie: *const c_float, pub node_parent: *const u32,
     pub q_min_match: *const u32,
 }
+// field sorts (query/sort.rs:159-216): parts = sort field id or SLG_SORT_SCORE, order SLG_ORDER_*
+#[repr(C)] pub struct slg_sort_spec {
+    pub n_parts: u32, pub field: [i32; SLG_MAX_SORT_PARTS], pub order: [i32; SLG_MAX_SORT_PARTS],
+}
 #[repr(C)] pub struct slg_stats { pub scored_docs: u64, pub candidates_examined: u64, pub postings_advanced: u64 }
 #[repr(C)] pub struct slg_query { pub n_terms: u32, pub term_ids: *const u32, pub weights: *const c_float }
 
@@ -111,6 +115,12 @@ extern "C" {
     pub fn slg_index_add_filter_range_i64(index: *mut slg_index, seg_columns: *const *const i64, lo: i64, hi: i64) -> c_int;
     pub fn slg_index_add_filter_range_f64(index: *mut slg_index, seg_columns: *const *const f64, lo: f64, hi: f64) -> c_int;
     pub fn slg_index_remove_filter(index: *mut slg_index, filter_id: c_int) -> c_int;
+    // sort fields: numeric fast fields as CSR of values per doc (query/sort.rs:300-345); ids are never reused
+    pub fn slg_index_add_sort_field_i64(index: *mut slg_index, seg_offsets: *const *const u32,
+        seg_values: *const *const i64) -> c_int;
+    pub fn slg_index_add_sort_field_f64(index: *mut slg_index, seg_offsets: *const *const u32,
+        seg_values: *const *const f64) -> c_int;
+    pub fn slg_index_remove_sort_field(index: *mut slg_index, sort_field_id: c_int) -> c_int;
     // one-shot
     pub fn slg_search_batch(index: *mut slg_index, queries: *const slg_query, nq: u32, k: u32,
         strategy: c_int, out_doc: *mut u32, out_seg: *mut u32, out_score: *mut c_float,
@@ -131,6 +141,14 @@ extern "C" {
     pub fn slg_batch_prepare_plans(index: *mut slg_index, nq: u32, q_offsets: *const u32, q_term_ids: *const u32,
         q_weights: *const c_float, plans_or_null: *const slg_score_plans, q_filter_or_null: *const i32,
         k: u32, strategy: c_int) -> *mut slg_batch;
+    pub fn slg_batch_prepare_sorted(index: *mut slg_index, nq: u32, q_offsets: *const u32, q_term_ids: *const u32,
+        q_weights: *const c_float, plans_or_null: *const slg_score_plans, q_filter_or_null: *const i32,
+        sort: *const slg_sort_spec, k: u32, strategy: c_int) -> *mut slg_batch;
+    pub fn slg_batch_matched_counts(batch: *mut slg_batch, out_matched: *mut u64) -> c_int;
+    pub fn slg_search_batch_sorted(index: *mut slg_index, queries: *const slg_query, nq: u32,
+        plans_or_null: *const slg_score_plans, q_filter_or_null: *const i32, sort: *const slg_sort_spec, k: u32,
+        strategy: c_int, out_doc: *mut u32, out_seg: *mut u32, out_score: *mut c_float, out_count: *mut u32,
+        out_matched: *mut u64) -> c_int;
     pub fn slg_batch_set_stream(batch: *mut slg_batch, hip_stream: *mut c_void) -> c_int;
     pub fn slg_batch_run(batch: *mut slg_batch) -> c_int;
     pub fn slg_batch_sync(batch: *mut slg_batch) -> c_int;
@@ -189,3 +207,7 @@ pub const SLG_PLAN_SUM: i32 = 0;
 pub const SLG_PLAN_DISMAX: i32 = 1;
 pub const SLG_PLAN_LEAF: i32 = 2;
 pub const SLG_MAX_PLAN_DEPTH: usize = 4;
+pub const SLG_MAX_SORT_PARTS: usize = 4;
+pub const SLG_SORT_SCORE: i32 = -1;
+pub const SLG_ORDER_ASC: i32 = 0;
+pub const SLG_ORDER_DESC: i32 = 1;

@@ -35,6 +35,7 @@ use crate::query::filters::passes_filter;
 use crate::query::planner::{QueryMatcher, QueryPlan, ScoreExpr};
 use crate::query::sort::SortPlan;
 use crate::DocId;
+use self::ffi::{slg_index_add_sort_field_f64, slg_index_add_sort_field_i64};
 
 /// SLG_MAX_QUERY_TERMS / SLG_MAX_K of include/searchlite_gpu.h.
 const MAX_QUERY_TERMS: usize = 32;
@@ -63,6 +64,8 @@ pub struct GpuSegments {
   state: std::sync::RwLock<StagedState>,
   /// filters already registered: serialized Filter -> filter id (slg_index_add_filter)
   filters: Mutex<FilterCache>,  // bounded LRU of registered doc filters
+  /// numeric fast fields registered for field sorts: (field, staged segment set) -> sort field id
+  sort_fields: Mutex<SortFieldCache>,
 }
 
 /// (segment id, number of tombstones) per segment ordinal — what `Manifest` says a reader sees.
@@ -230,7 +233,13 @@ impl GpuSegments {
       bail!("slg_coalescer_create failed");
     }
     let state = StagedState { key: manifest_key(segments), generation: 0, dict };
-    Ok(Self { handle, coalescer, state: std::sync::RwLock::new(state), filters: Mutex::new(FilterCache::default()) })
+    Ok(Self {
+      handle,
+      coalescer,
+      state: std::sync::RwLock::new(state),
+      filters: Mutex::new(FilterCache::default()),
+      sort_fields: Mutex::new(SortFieldCache::default()),
+    })
   }
 }
 
@@ -332,6 +341,55 @@ impl GpuSegments {
     self.handle
   }
 
+  /// The sort field id of a numeric fast field over the staged segments (slg_index_add_sort_field_*), registered
+  /// on first use from the segments' own values (index/fastfields.rs:736-770); a field whose columns predate
+  /// the current segment set (slg_index_add_segment gives a new segment none) is registered again.
+  fn sort_field_id(&self, segments: &[SegmentReader], seg_ids: &[String], field: &str, f64_field: bool) -> Result<i32> {
+    let mut cache = self.sort_fields.lock().unwrap();
+    if let Some((ids, id)) = cache.map.get(field) {
+      if ids.as_slice() == seg_ids {
+        return Ok(*id);
+      }
+      unsafe { ffi::slg_index_remove_sort_field(self.handle, *id) };
+      cache.map.remove(field);
+    }
+    let mut offsets: Vec<Vec<u32>> = Vec::with_capacity(segments.len());
+    let (mut ivals, mut fvals): (Vec<Vec<i64>>, Vec<Vec<f64>>) = (Vec::new(), Vec::new());
+    for seg in segments {
+      let n = seg.meta.doc_count;
+      let mut offs = Vec::with_capacity(n as usize + 1);
+      offs.push(0u32);
+      let (mut iv, mut fv) = (Vec::new(), Vec::new());
+      for d in 0..n as DocId {
+        if f64_field {
+          fv.extend(seg.fast_fields().f64_values(field, d));
+          offs.push(fv.len() as u32);
+        } else {
+          iv.extend(seg.fast_fields().i64_values(field, d));
+          offs.push(iv.len() as u32);
+        }
+      }
+      offsets.push(offs);
+      ivals.push(iv);
+      fvals.push(fv);
+    }
+    let optr: Vec<*const u32> = offsets.iter().map(|o| o.as_ptr()).collect();
+    let id = unsafe {
+      if f64_field {
+        let vptr: Vec<*const f64> = fvals.iter().map(|v| v.as_ptr()).collect();
+        slg_index_add_sort_field_f64(self.handle, optr.as_ptr(), vptr.as_ptr())
+      } else {
+        let vptr: Vec<*const i64> = ivals.iter().map(|v| v.as_ptr()).collect();
+        slg_index_add_sort_field_i64(self.handle, optr.as_ptr(), vptr.as_ptr())
+      }
+    };
+    if id < 0 {
+      return Err(last_error());
+    }
+    cache.map.insert(field.to_string(), (seg_ids.to_vec(), id));
+    Ok(id)
+  }
+
   /// `req.filter` as a doc bitmap per segment (accept = !deleted && filter, api/reader.rs:
   /// 3009-3018), evaluated once with the reference's own passes_filter and cached by the filter's
   /// serialized form.
@@ -429,6 +487,22 @@ const MAX_CACHED_FILTERS: usize = 256;
 pub(crate) struct FilterCache {
   map: HashMap<String, (i32, u64)>,
   tick: u64,
+}
+
+/// field -> (segment ids the columns were built for, sort field id).  The library never hands an id out
+/// twice, so an id the cache dropped fails (SLG_ERR_INVALID) instead of naming another field.
+#[derive(Default)]
+pub(crate) struct SortFieldCache {
+  map: HashMap<String, (Vec<String>, i32)>,
+}
+
+/// One part of a request's sort (query/sort.rs:159-216), as SortPlan::gpu_parts reports it
+/// (reader_gpu.patch.rs (3)).
+pub(crate) enum GpuSortPart {
+  Score(SortOrder),
+  I64(String, SortOrder),
+  F64(String, SortOrder),
+  Keyword,
 }
 
 /// One scored term of a request, folded as search_segment does (api/reader.rs:2971-2983):
@@ -605,12 +679,24 @@ pub(crate) fn gpu_eligible(
   needs_score_hook: bool,
   top_k: usize,
   n_folded_terms: usize,
-) -> Option<(GpuScorePlan, u32, u32)> {
+) -> Option<(GpuScorePlan, u32, u32, Option<Vec<GpuSortPart>>)> {
   // score_fast_path (api/reader.rs:2550-2551): sort = _score desc only => ScoreMode::Score and
-  // the scorer is handed rank_limit = top_k (:2702-2703)
+  // the scorer is handed rank_limit = top_k (:2702-2703).  Any other sort of up to SLG_MAX_SORT_PARTS parts
+  // of `_score` and numeric fast fields runs as a sorted batch (slg_batch_prepare_sorted): every matched doc
+  // is scored (the reference's collector path, query/wand.rs:725-729) and the device keeps the top k by
+  // SortKey; keyword parts stay on the CPU
   let score_fast_path =
     sort_plan.is_score_only() && matches!(sort_plan.primary_order(), Some(SortOrder::Desc));
-  if !score_fast_path || !req.return_hits || req.limit == 0 || top_k == 0 || top_k > MAX_K {
+  let sort_parts = if score_fast_path {
+    None
+  } else {
+    let parts = sort_plan.gpu_parts();
+    if parts.is_empty() || parts.len() > ffi::SLG_MAX_SORT_PARTS || parts.iter().any(|p| matches!(p, GpuSortPart::Keyword)) {
+      return None;
+    }
+    Some(parts)
+  };
+  if !req.return_hits || req.limit == 0 || top_k == 0 || top_k > MAX_K {
     return None;
   }
   // no collector: agg_ref stays None only without aggregations (api/reader.rs:2694-2699)
@@ -643,12 +729,13 @@ pub(crate) fn gpu_eligible(
   {
     return None;
   }
-  Some((shape, n_leaves, min_match))
+  Some((shape, n_leaves, min_match, sort_parts))
 }
 
 /// Replaces the per-segment loop + cross-segment sort of IndexReader::search
 /// (api/reader.rs:2670-2778) for ONE eligible request: (segment_ord, doc_id, score) in final order,
-/// at most `top_k` of them, plus the number of distinct docs scored.
+/// at most `top_k` of them, plus the number of distinct docs scored — or, for a field sort (`sort`), the
+/// number of docs accepted (total_matches, api/reader.rs:3026-3028; score 0.0 without a `_score` part).
 pub(crate) fn gpu_top_k(
   gpu: &GpuSegments,
   segments: &[SegmentReader],
@@ -660,6 +747,7 @@ pub(crate) fn gpu_top_k(
   not_keys: &[String],
   execution: &ExecutionStrategy,
   top_k: usize,
+  sort: Option<&[GpuSortPart]>,
 ) -> Result<(Vec<(u32, DocId, f32)>, u64)> {
   let n_segs = segments.len();
   // the reader's manifest snapshot must be what is staged (a commit may have moved the device index
@@ -748,6 +836,49 @@ pub(crate) fn gpu_top_k(
   // reference has no batch API (api/reader.rs:2539) and serves a request per blocking thread
   // (searchlite-http/src/lib.rs:628-652), so concurrent requests share one prepare / run / fetch.
   // (a request with minimum_should_match > 1 is prepared on its own: the coalescer's rows carry no such count)
+  if let Some(parts) = sort {
+    // the sort spec: numeric fast fields registered per staged segment set (ids are never reused)
+    let seg_ids: Vec<String> = st.key.iter().map(|(id, _)| id.clone()).collect();
+    let mut spec = ffi::slg_sort_spec { n_parts: parts.len() as u32, field: [0; ffi::SLG_MAX_SORT_PARTS], order: [0; ffi::SLG_MAX_SORT_PARTS] };
+    for (i, p) in parts.iter().enumerate() {
+      let (field, order) = match p {
+        GpuSortPart::Score(o) => (ffi::SLG_SORT_SCORE, o),
+        GpuSortPart::I64(name, o) => (gpu.sort_field_id(segments, &seg_ids, name, false)?, o),
+        GpuSortPart::F64(name, o) => (gpu.sort_field_id(segments, &seg_ids, name, true)?, o),
+        GpuSortPart::Keyword => bail!("keyword sort parts run on the CPU"),
+      };
+      spec.field[i] = field;
+      spec.order[i] = if matches!(order, SortOrder::Desc) { ffi::SLG_ORDER_DESC } else { ffi::SLG_ORDER_ASC };
+    }
+    let batch = unsafe {
+      ffi::slg_batch_prepare_sorted(
+        gpu.raw(), 1, offsets.as_ptr(), term_ids.as_ptr(), weights.as_ptr(), &plans, &filter_id, &spec, k, strategy,
+      )
+    };
+    drop(st);
+    if batch.is_null() {
+      return Err(last_error());
+    }
+    let (mut doc, mut seg, mut score) = (vec![0u32; top_k], vec![0u32; top_k], vec![0f32; top_k]);
+    let (mut count, mut matched) = (0u32, 0u64);
+    let rc = unsafe {
+      let mut rc = ffi::slg_batch_run(batch);
+      if rc == 0 {
+        rc = ffi::slg_batch_fetch(batch, doc.as_mut_ptr(), seg.as_mut_ptr(), score.as_mut_ptr(), &mut count,
+                                  std::ptr::null_mut());
+      }
+      if rc == 0 {
+        rc = ffi::slg_batch_matched_counts(batch, &mut matched);
+      }
+      ffi::slg_batch_destroy(batch);
+      rc
+    };
+    if rc != 0 {
+      bail!("searchlite_gpu returned {rc}");
+    }
+    let hits = (0..count as usize).map(|i| (seg[i], doc[i] as DocId, score[i])).collect();
+    return Ok((hits, matched));
+  }
   if min_match <= 1 && matches!(score_plan, GpuScorePlan::Sum | GpuScorePlan::DisMax { .. }) {
     let (mut doc, mut seg, mut score) = (vec![0u32; top_k], vec![0u32; top_k], vec![0f32; top_k]);
     let mut count = 0u32;

@@ -22,6 +22,9 @@ OK, ERR_INVALID, ERR_DEVICE, ERR_OOM, ERR_UNSUPPORTED, ERR_INTERNAL = 0, -1, -2,
 STRATEGY_BM25, STRATEGY_WAND, STRATEGY_BMW = 0, 1, 2
 METRIC_COSINE, METRIC_L2 = 0, 1
 PLAN_SUM, PLAN_DISMAX, PLAN_LEAF = 0, 1, 2
+MAX_SORT_PARTS = 4
+SORT_SCORE = -1
+ORDER_ASC, ORDER_DESC = 0, 1
 
 
 class SlgError(RuntimeError):
@@ -74,6 +77,11 @@ class ScorePlans(C.Structure):
                 ("group_plan", C.c_void_p), ("group_tie", C.c_void_p),
                 ("q_node_offsets", C.c_void_p), ("node_kind", C.c_void_p), ("node_tie", C.c_void_p),
                 ("node_parent", C.c_void_p), ("q_min_match", C.c_void_p)]
+
+
+class SortSpec(C.Structure):
+    """slg_sort_spec: the parts of a field sort (sort field id or SORT_SCORE, ORDER_*)."""
+    _fields_ = [("n_parts", C.c_uint32), ("field", C.c_int32 * MAX_SORT_PARTS), ("order", C.c_int32 * MAX_SORT_PARTS)]
 
 
 class Ticket(C.Structure):
@@ -158,6 +166,12 @@ def load():
         "slg_batch_prepare_filtered": (vp, [vp, u32, vp, vp, vp, vp, u32, i32]),
         "slg_batch_prepare_plan": (vp, [vp, u32, vp, vp, vp, vp, vp, vp, vp, vp, u32, i32]),
         "slg_batch_prepare_plans": (vp, [vp, u32, vp, vp, vp, vp, vp, u32, i32]),
+        "slg_index_add_sort_field_i64": (i32, [vp, vp, vp]),
+        "slg_index_add_sort_field_f64": (i32, [vp, vp, vp]),
+        "slg_index_remove_sort_field": (i32, [vp, i32]),
+        "slg_batch_prepare_sorted": (vp, [vp, u32, vp, vp, vp, vp, vp, vp, u32, i32]),
+        "slg_batch_matched_counts": (i32, [vp, vp]),
+        "slg_search_batch_sorted": (i32, [vp, vp, u32, vp, vp, vp, u32, i32, vp, vp, vp, vp, vp]),
         "slg_batch_run": (i32, [vp]),
         "slg_batch_set_stream": (i32, [vp, vp]),
         "slg_batch_sync": (i32, [vp]),

@@ -315,6 +315,16 @@ struct FilterData {
   }
 };
 
+// a registered sort field (slg_index_add_sort_field_*): per segment the u64 key of each order and the
+// presence bitmap; null = the field predates the segment (slg_index_add_segment)
+struct SortColumn {
+  DevBuf key[2];  // SLG_ORDER_ASC, SLG_ORDER_DESC
+  DevBuf present;
+};
+struct SortFieldData {
+  std::vector<std::shared_ptr<SortColumn>> per_seg;
+};
+
 // One immutable state of the index (see "index updates" in searchlite_gpu.h).  Batches hold the state
 // they were prepared on; the index holds the current one.
 struct IndexState {
@@ -327,6 +337,7 @@ struct IndexState {
   std::vector<std::shared_ptr<FilterData>> filters;    // slot = filter id; null = free
   std::vector<const uint32_t *> reject_host;           // flattened [filter * n_segs + seg] device pointers
   DevBuf d_reject_table;                               // the same table on the device
+  std::map<int, std::shared_ptr<SortFieldData>> sort_fields;  // by id (ids are not reused)
   ~IndexState() {
     // kernels of already-destroyed batches, or rerank calls on the index stream, may still read the
     // tables: retiring a state is rare (one per update), so wait for the device once
@@ -360,6 +371,7 @@ struct slg_index {
   std::atomic<uint64_t> generation{0};      // = state->generation, readable without the lock
   std::mutex mu;
   std::mutex update_mu;  // serialises slg_index_update_* / add_filter / add_vector_field (taken before mu)
+  int next_sort_field = 0;  // (under update_mu) sort field ids are never handed out again
   // profiling of the scoring kernel
   bool profile = false;
   std::vector<std::pair<hipEvent_t, hipEvent_t>> prof_events;
@@ -403,6 +415,12 @@ struct slg_batch {
   DevBuf d_q_filter;       // [nq] 0 = none, f + 1 (select_topk_kernel); empty when unfiltered
   bool cand_mode = false;  // uniform kernel, k > 256: candidates + select_topk_kernel
   DevBuf d_cand, d_slice_cbeg, d_slice_ccnt;
+  // field-sorted batch (slg_batch_prepare_sorted): candidates of every matched doc + select_sorted_kernel
+  bool sorted = false;
+  uint32_t score_k = 0;  // k the scoring kernel runs with (a sorted batch: slgplan::planning_k)
+  uint32_t n_sort_parts = 0, sort_score_parts = 0, sort_desc_parts = 0;
+  DevBuf d_sort_cols;  // slg::SortColDev[kSortMaxParts * n_segs]
+  DevBuf d_matched;    // u64[nq] accepted docs
   DevBuf d_out;  // doc | seg | score | count, contiguous
   uint32_t *d_out_doc = nullptr, *d_out_seg = nullptr, *d_out_count = nullptr;
   float *d_out_score = nullptr;
@@ -776,6 +794,7 @@ std::unique_ptr<IndexState> copy_state(const IndexState &cur) {
   n->device = cur.device;
   n->segs = cur.segs;
   n->filters = cur.filters;
+  n->sort_fields = cur.sort_fields;
   for (auto &vf : cur.vfields) {  // the per-state table d_vsegs is rebuilt: own object, shared stores
     auto c = std::make_shared<VecFieldHost>();
     c->dim = vf->dim;
@@ -804,6 +823,9 @@ size_t state_device_bytes(const IndexState &s) {
     if (f)
       for (auto &b : f->per_seg)
         if (b) n += b->bytes;
+  for (auto &sf : s.sort_fields)
+    for (auto &c : sf.second->per_seg)
+      if (c) n += c->key[0].bytes + c->key[1].bytes + c->present.bytes;
   for (auto &vf : s.vfields) {
     n += vf->d_vsegs.bytes;
     for (auto &v : vf->per_seg)
@@ -1148,6 +1170,75 @@ int slg_index_remove_filter(slg_index *ix, int filter_id) {
   });
 }
 
+// ---- sort fields (query/sort.rs:300-345) ---------------------------------------------------
+namespace {
+int add_sort_field_impl(slg_index *ix, int kind, const uint32_t *const *seg_offsets, const void *const *seg_values) {
+  int id = -1;
+  const int rc = guarded([&] {
+    SLG_REQUIRE(ix != nullptr, "index is NULL");
+    SLG_REQUIRE(seg_offsets != nullptr, "seg_offsets is NULL");
+    std::lock_guard<std::mutex> ulk(ix->update_mu);
+    const auto cur = ix->snapshot();
+    DeviceGuard g(ix->device);
+    const size_t n_segs = cur->segs.size();
+    auto fd = std::make_shared<SortFieldData>();
+    fd->per_seg.resize(n_segs);
+    for (size_t s = 0; s < n_segs; s++) {
+      const uint32_t n_docs = cur->segs[s]->n_docs;
+      const uint32_t *offs = seg_offsets[s];
+      SLG_REQUIRE(offs == nullptr || seg_values != nullptr, "seg_values is NULL");
+      if (offs) {
+        for (uint32_t d = 0; d < n_docs; d++)
+          SLG_REQUIRE(offs[d + 1] >= offs[d], "sort field offsets of a segment are not monotone");
+        SLG_REQUIRE(offs[n_docs] == offs[0] || seg_values[s] != nullptr, "sort field values of a segment are NULL");
+      }
+      // the Min / Max selection and the key encoding run on the host (slg_plan.cpp: unit-tested on the CPU)
+      const size_t n = std::max<uint32_t>(n_docs, 1), words = (n + 31) / 32;
+      std::vector<uint64_t> asc(n, 0), desc(n, 0);
+      std::vector<uint32_t> present(words, 0);
+      slgplan::sort_field_keys(kind, n_docs, offs, offs ? seg_values[s] : nullptr, asc.data(), desc.data(),
+                               present.data());
+      auto col = std::make_shared<SortColumn>();
+      col->key[0].alloc(n * 8, &ix->pool);
+      col->key[1].alloc(n * 8, &ix->pool);
+      col->present.alloc(words * 4, &ix->pool);
+      SLG_HIP(hipMemcpy(col->key[0].p, asc.data(), n * 8, hipMemcpyHostToDevice));
+      SLG_HIP(hipMemcpy(col->key[1].p, desc.data(), n * 8, hipMemcpyHostToDevice));
+      SLG_HIP(hipMemcpy(col->present.p, present.data(), words * 4, hipMemcpyHostToDevice));
+      fd->per_seg[s] = std::move(col);
+    }
+    auto ns = copy_state(*cur);
+    ns->generation = cur->generation;  // (as filters: a manifest snapshot sees no change)
+    id = ix->next_sort_field++;
+    ns->sort_fields[id] = std::move(fd);
+    finish_state(ix, *ns);
+    publish(ix, std::move(ns));
+  });
+  return rc == SLG_OK ? id : rc;
+}
+}  // namespace
+
+int slg_index_add_sort_field_i64(slg_index *ix, const uint32_t *const *seg_offsets, const int64_t *const *seg_values) {
+  return add_sort_field_impl(ix, 1, seg_offsets, reinterpret_cast<const void *const *>(seg_values));
+}
+int slg_index_add_sort_field_f64(slg_index *ix, const uint32_t *const *seg_offsets, const double *const *seg_values) {
+  return add_sort_field_impl(ix, 2, seg_offsets, reinterpret_cast<const void *const *>(seg_values));
+}
+int slg_index_remove_sort_field(slg_index *ix, int sort_field_id) {
+  return guarded([&] {
+    SLG_REQUIRE(ix != nullptr, "index is NULL");
+    std::lock_guard<std::mutex> ulk(ix->update_mu);
+    const auto cur = ix->snapshot();
+    DeviceGuard g(ix->device);
+    SLG_REQUIRE(cur->sort_fields.count(sort_field_id) == 1, "unknown sort field id");
+    auto ns = copy_state(*cur);
+    ns->generation = cur->generation;
+    ns->sort_fields.erase(sort_field_id);
+    finish_state(ix, *ns);
+    publish(ix, std::move(ns));
+  });
+}
+
 // ---- index updates (api/writer.rs:106-240) ---------------------------------------------------
 int slg_index_update_deleted(slg_index *ix, uint32_t seg, const uint8_t *deleted, float live_docs) {
   return guarded([&] {
@@ -1204,6 +1295,11 @@ int slg_index_add_segment(slg_index *ix, const slg_segment_desc *seg) {
         nf->per_seg.resize(ns->segs.size());
         f = std::move(nf);
       }
+    for (auto &sf : ns->sort_fields) {  // sort fields too: no column for the new segment
+      auto nf = std::make_shared<SortFieldData>(*sf.second);
+      nf->per_seg.resize(ns->segs.size());
+      sf.second = std::move(nf);
+    }
     for (auto &vf : ns->vfields) vf->per_seg.resize(ns->segs.size());
     finish_state(ix, *ns);
     ord = (int)ns->segs.size() - 1;
@@ -1228,6 +1324,11 @@ int slg_index_remove_segment(slg_index *ix, uint32_t seg) {
         if (seg < nf->per_seg.size()) nf->per_seg.erase(nf->per_seg.begin() + seg);
         f = std::move(nf);
       }
+    for (auto &sf : ns->sort_fields) {
+      auto nf = std::make_shared<SortFieldData>(*sf.second);
+      if (seg < nf->per_seg.size()) nf->per_seg.erase(nf->per_seg.begin() + seg);
+      sf.second = std::move(nf);
+    }
     for (auto &vf : ns->vfields)
       if (seg < vf->per_seg.size()) vf->per_seg.erase(vf->per_seg.begin() + seg);
     finish_state(ix, *ns);
@@ -1274,13 +1375,23 @@ slg_batch *slg_batch_prepare_plan(slg_index *ix, uint32_t nq, const uint32_t *q_
   return slg_batch_prepare_plans(ix, nq, q_offsets, q_term_ids, q_weights, &pl, q_filter, k, strategy);
 }
 
-slg_batch *slg_batch_prepare_plans(slg_index *ix, uint32_t nq, const uint32_t *q_offsets,
-                                   const uint32_t *q_term_ids, const float *q_weights,
-                                   const slg_score_plans *plans, const int32_t *q_filter, uint32_t k,
-                                   int strategy) {
+}  // extern "C"
+
+namespace {
+// slg_batch_prepare_plans, and (sort != nullptr) slg_batch_prepare_sorted
+slg_batch *prepare_impl(slg_index *ix, uint32_t nq, const uint32_t *q_offsets, const uint32_t *q_term_ids,
+                        const float *q_weights, const slg_score_plans *plans, const int32_t *q_filter,
+                        const slg_sort_spec *sort, uint32_t k, int strategy) {
   slg_batch *b = nullptr;
   int rc = guarded([&] {
     SLG_REQUIRE(ix != nullptr, "index is NULL");
+    if (sort) {  // (checked before planning: the planner never sees a sort spec it cannot run)
+      if (sort->n_parts > SLG_MAX_SORT_PARTS)
+        throw SlgError(SLG_ERR_UNSUPPORTED, "more than SLG_MAX_SORT_PARTS sort parts");
+      SLG_REQUIRE(sort->n_parts >= 1, "a sort spec needs at least one part");
+      for (uint32_t i = 0; i < sort->n_parts; i++)
+        SLG_REQUIRE(sort->order[i] == SLG_ORDER_ASC || sort->order[i] == SLG_ORDER_DESC, "unknown sort order");
+    }
     // Planning (slg_plan.cpp: a pure host function) reads only the immutable state the batch binds
     // to, so host threads may prepare batches for one index concurrently, also while an update builds
     // the next state; the index mutex is held just to take the snapshot.
@@ -1308,6 +1419,33 @@ slg_batch *slg_batch_prepare_plans(slg_index *ix, uint32_t nq, const uint32_t *q
     in.strategy = strategy;
     in.filter_live = filter_live.data();
     in.n_filters = filter_live.size();
+    in.sorted = sort != nullptr;
+    // the columns of the sort parts in the batch's state: every part names a field with a column for every
+    // segment (a field registered before slg_index_add_segment has none for the new one)
+    std::vector<slg::SortColDev> sort_cols;
+    uint32_t score_parts = 0, desc_parts = 0;
+    if (sort) {
+      const size_t n_segs = snap->segs.size();
+      sort_cols.assign(slg::kSortMaxParts * std::max<size_t>(n_segs, 1), slg::SortColDev{nullptr, nullptr});
+      for (uint32_t i = 0; i < sort->n_parts; i++) {
+        if (sort->order[i] == SLG_ORDER_DESC) desc_parts |= 1u << i;
+        if (sort->field[i] == SLG_SORT_SCORE) {
+          score_parts |= 1u << i;
+          continue;
+        }
+        const auto it = snap->sort_fields.find(sort->field[i]);
+        SLG_REQUIRE(it != snap->sort_fields.end(), "unknown sort field id in part " + std::to_string(i));
+        const SortFieldData &fd = *it->second;
+        for (size_t s = 0; s < n_segs; s++) {
+          SLG_REQUIRE(s < fd.per_seg.size() && fd.per_seg[s],
+                      "sort field " + std::to_string(sort->field[i]) + " has no column for segment " + std::to_string(s) +
+                          " (added after the field was registered)");
+          const SortColumn &c = *fd.per_seg[s];
+          sort_cols[i * n_segs + s] = slg::SortColDev{c.key[sort->order[i]].as<const unsigned long long>(),
+                                                      c.present.as<const uint32_t>()};
+        }
+      }
+    }
     slgplan::Plan plan;
     slgplan::plan_batch(views, ix->tune, in, plan);
 
@@ -1331,6 +1469,8 @@ slg_batch *slg_batch_prepare_plans(slg_index *ix, uint32_t nq, const uint32_t *q
     b->deep = plan.deep;
     b->pruned = plan.pruned;
     b->cand_mode = plan.cand_mode;
+    b->sorted = sort != nullptr;
+    b->score_k = slgplan::planning_k(in);
     b->n_sq = (uint32_t)plan.sqs.size();
     b->n_terms = (uint32_t)plan.terms.size();
     b->n_slices = (uint32_t)plan.slice_sq.size();
@@ -1391,6 +1531,15 @@ slg_batch *slg_batch_prepare_plans(slg_index *ix, uint32_t nq, const uint32_t *q
       b->d_q_filter.alloc_pooled(&ix->pool, (size_t)nq * 4);
       SLG_HIP(hipMemcpy(b->d_q_filter.p, plan.q_filter.data(), (size_t)nq * 4, hipMemcpyHostToDevice));
     }
+    if (b->sorted) {
+      b->n_sort_parts = sort->n_parts;
+      b->sort_score_parts = score_parts;
+      b->sort_desc_parts = desc_parts;
+      b->d_sort_cols.alloc_pooled(&ix->pool, sort_cols.size() * sizeof(slg::SortColDev));
+      SLG_HIP(hipMemcpy(b->d_sort_cols.p, sort_cols.data(), sort_cols.size() * sizeof(slg::SortColDev),
+                        hipMemcpyHostToDevice));
+      b->d_matched.alloc_pooled(&ix->pool, (size_t)std::max<uint32_t>(nq, 1) * 8);
+    }
     b->d_out.alloc_pooled(&ix->pool, ((size_t)nq * k * 3 + nq + 1) * 4);  // (+ the error word: MergeParams::out_flag)
     b->d_out_doc = b->d_out.as<uint32_t>();
     b->d_out_seg = b->d_out_doc + (size_t)nq * k;
@@ -1410,6 +1559,27 @@ slg_batch *slg_batch_prepare_plans(slg_index *ix, uint32_t nq, const uint32_t *q
     return nullptr;
   }
   return b;
+}
+}  // namespace
+
+extern "C" {
+
+slg_batch *slg_batch_prepare_plans(slg_index *ix, uint32_t nq, const uint32_t *q_offsets,
+                                   const uint32_t *q_term_ids, const float *q_weights,
+                                   const slg_score_plans *plans, const int32_t *q_filter, uint32_t k,
+                                   int strategy) {
+  return prepare_impl(ix, nq, q_offsets, q_term_ids, q_weights, plans, q_filter, nullptr, k, strategy);
+}
+
+slg_batch *slg_batch_prepare_sorted(slg_index *ix, uint32_t nq, const uint32_t *q_offsets,
+                                    const uint32_t *q_term_ids, const float *q_weights,
+                                    const slg_score_plans *plans, const int32_t *q_filter,
+                                    const slg_sort_spec *sort, uint32_t k, int strategy) {
+  if (!sort) {
+    (void)guarded([&] { SLG_REQUIRE(false, "sort spec is NULL"); });
+    return nullptr;
+  }
+  return prepare_impl(ix, nq, q_offsets, q_term_ids, q_weights, plans, q_filter, sort, k, strategy);
 }
 
 #define SLG_REQUIRE_LIVE(b) \
@@ -1455,7 +1625,7 @@ int slg_batch_run(slg_batch *b) {
       uint32_t n_waves = b->n_slices;
       const bool persistent = (score_kind == 6 || score_kind == 7) && ix->tune.score_waves_per_simd != 0;
       if (persistent)
-        n_waves = slg::u4_launch_blocks(kregs_for(b->k), (score_kind & 1) ? 8 : 4, score_kind >= 8, b->n_slices, ix->n_cu,
+        n_waves = slg::u4_launch_blocks(kregs_for(b->score_k), (score_kind & 1) ? 8 : 4, score_kind >= 8, b->n_slices, ix->n_cu,
                                         ix->tune.score_waves_per_simd) *
                   (uint32_t)slg::kU4WavesPerBlock;
       pp.work_ctr = persistent ? b->d_work_ctr.as<uint32_t>() : nullptr;
@@ -1486,7 +1656,7 @@ int slg_batch_run(slg_batch *b) {
       sp.slice_doc = b->d_slice_doc.as<uint32_t>();
       sp.q_scored = b->d_q_scored.as<uint32_t>();
       sp.n_slices = b->n_slices;
-      sp.k = b->k;
+      sp.k = b->score_k;
       sp.block_skip = skipping ? 1u : 0u;
       sp.skip_counts = pp.skip_counts;
       sp.stamps = nullptr;
@@ -1511,7 +1681,33 @@ int slg_batch_run(slg_batch *b) {
       launch_score(sp, score_kind, st);
       if (ev) SLG_HIP(hipEventRecord(ev->second, st));
     }
-    if (b->k > 0 && b->cand_mode && b->n_slices > 0) {
+    if (b->sorted) {  // (also without slices: every row is empty, every matched count 0)
+      slg::SortedSelectParams sp{};
+      sp.queries = b->d_queries;
+      sp.slice_seg = b->d_slice_seg;
+      sp.slice_cbeg = b->d_slice_cbeg.as<uint64_t>();
+      sp.slice_ccnt = b->d_slice_ccnt.as<uint32_t>();
+      sp.cand = b->d_cand.as<uint2>();
+      sp.segs = S.d_segs.as<slg::SegDev>();
+      sp.q_filter = b->d_q_filter.as<uint32_t>();
+      sp.reject_table = S.d_reject_table.as<const uint32_t *>();
+      sp.cols = b->d_sort_cols.as<const slg::SortColDev>();
+      sp.n_segs = (uint32_t)S.segs.size();
+      sp.n_parts = b->n_sort_parts;
+      sp.score_parts = b->sort_score_parts;
+      sp.desc_parts = b->sort_desc_parts;
+      sp.out_doc = b->d_out_doc;
+      sp.out_seg = b->d_out_seg;
+      sp.out_score = b->d_out_score;
+      sp.out_count = b->d_out_count;
+      sp.out_matched = b->d_matched.as<unsigned long long>();
+      sp.nq = b->nq;
+      sp.k = b->k;
+      sp.error_flag = ix->d_error_flag.as<uint32_t>();
+      sp.out_flag = b->d_out_count + b->nq;
+      hipLaunchKernelGGL(slg::select_sorted_kernel, dim3(b->nq), dim3(slg::kSortedThreads), 0, st, sp);
+      SLG_HIP(hipGetLastError());
+    } else if (b->k > 0 && b->cand_mode && b->n_slices > 0) {
       slg::SelectParams sp{};
       sp.queries = b->d_queries;
       sp.slice_seg = b->d_slice_seg;
@@ -1769,6 +1965,59 @@ int slg_search_batch_filtered(slg_index *ix, const slg_query *queries, uint32_t 
   if (!b) return g_last_code;  // slg_batch_prepare set the thread-local error and its code
   rc = slg_batch_run(b);
   if (rc == SLG_OK) rc = slg_batch_fetch(b, out_doc, out_seg, out_score, out_count, stats);
+  const std::string keep = g_last_error;
+  slg_batch_destroy(b);
+  g_last_error = keep;
+  g_last_code = rc;
+  return rc;
+}
+
+int slg_batch_matched_counts(slg_batch *b, uint64_t *out_matched) {
+  return guarded([&] {
+    SLG_REQUIRE_LIVE(b);
+    SLG_REQUIRE(b->sorted, "not a sorted batch (slg_batch_prepare_sorted)");
+    SLG_REQUIRE(b->launched, "the batch has not run");
+    SLG_REQUIRE(b->nq == 0 || out_matched != nullptr, "out_matched is NULL");
+    slg_index *ix = b->idx;
+    DeviceGuard g(ix->device);
+    hipStream_t st;
+    {
+      std::lock_guard<std::mutex> lk(ix->mu);
+      st = batch_stream(b);
+    }
+    SLG_HIP(wait_stream(st));
+    if (b->nq) SLG_HIP(hipMemcpy(out_matched, b->d_matched.p, (size_t)b->nq * 8, hipMemcpyDeviceToHost));
+  });
+}
+
+int slg_search_batch_sorted(slg_index *ix, const slg_query *queries, uint32_t nq, const slg_score_plans *plans,
+                            const int32_t *q_filter, const slg_sort_spec *sort, uint32_t k, int strategy,
+                            uint32_t *out_doc, uint32_t *out_seg, float *out_score, uint32_t *out_count,
+                            uint64_t *out_matched) {
+  int rc = guarded([&] {
+    SLG_REQUIRE(ix != nullptr, "index is NULL");
+    SLG_REQUIRE(nq == 0 || queries != nullptr, "queries is NULL");
+  });
+  if (rc != SLG_OK) return rc;
+  std::vector<uint32_t> offs(nq + 1, 0), tids;
+  std::vector<float> ws;
+  rc = guarded([&] {
+    const size_t n_segs = ix->snapshot()->segs.size();
+    for (uint32_t q = 0; q < nq; q++) {
+      const slg_query &qq = queries[q];
+      SLG_REQUIRE(qq.n_terms == 0 || (qq.term_ids && qq.weights), "query arrays are NULL");
+      offs[q + 1] = offs[q] + qq.n_terms;
+      tids.insert(tids.end(), qq.term_ids, qq.term_ids + (size_t)qq.n_terms * n_segs);
+      ws.insert(ws.end(), qq.weights, qq.weights + qq.n_terms);
+    }
+  });
+  if (rc != SLG_OK) return rc;
+  slg_batch *b = slg_batch_prepare_sorted(ix, nq, offs.data(), tids.data(), ws.data(), plans, q_filter, sort, k,
+                                          strategy);
+  if (!b) return g_last_code;
+  rc = slg_batch_run(b);
+  if (rc == SLG_OK) rc = slg_batch_fetch(b, out_doc, out_seg, out_score, out_count, nullptr);
+  if (rc == SLG_OK && out_matched) rc = slg_batch_matched_counts(b, out_matched);
   const std::string keep = g_last_error;
   slg_batch_destroy(b);
   g_last_error = keep;

@@ -1000,4 +1000,330 @@ select_topk_kernel(SelectParams p) {
   if (tid == 0) p.out_count[q] = nout;
 }
 
+// ---- field-sorted select (slg_batch_prepare_sorted; query/sort.rs:80-123 SortKey::cmp) -------------
+// A sorted batch runs its scoring kernel in candidates mode without a threshold seed, so every matched doc
+// of every sub-query is in the candidate region once with its exact score.  One workgroup per query then
+// takes the k smallest composite keys
+//   part 0 | part 1 | ... | segment | doc        (ascending u32 words, kSortWords of them)
+// where a field part is three words (missing flag, u64 key: the column of its order, complemented for
+// Desc on the host, so ascending is the sort order in both; Missing = flag 1, sorts last in both orders)
+// and a `_score` part is the ordered score (complemented for Desc) in the third word of its three.
+// Parts beyond the spec are zero words.  Keys are regathered from the columns on every sweep (L2), never
+// held per candidate.  Sweep 1 applies accept() (tombstones / filter, counted for `matched`) and finds
+// which key bytes vary over the query's candidates; the byte-wise radix select (as select_topk_kernel's:
+// rank ranges of at most kSortedCap keys, a pass per VARYING byte until the bucket of the range's last
+// key is used up) then walks those bytes only.  A range's keys are gathered into LDS — only their
+// varying words — and bitonic-sorted by index.
+struct SortColDev {
+  const unsigned long long *key;  // [n_docs] u64 key of the part's order (0 for Missing docs)
+  const uint32_t *present;        // presence bitmap (bit d & 31 of word d >> 5)
+};
+
+struct SortedSelectParams {
+  const QueryRef *queries;
+  const uint32_t *slice_seg;
+  const uint64_t *slice_cbeg;
+  const uint32_t *slice_ccnt;
+  uint2 *cand;  // .x ordered score, .y doc (0xFFFFFFFF: dropped)
+  const SegDev *segs;
+  const uint32_t *q_filter;             // [nq] 0 = none, f + 1
+  const uint32_t *const *reject_table;  // [n_filters * n_segs] reject bitmaps
+  const SortColDev *cols;               // [kSortMaxParts * n_segs]: part p of segment s at p * n_segs + s
+  uint32_t n_segs, n_parts;
+  uint32_t score_parts;  // bit p: part p is `_score`
+  uint32_t desc_parts;   // bit p: part p descends (applied here to `_score`; field columns come complemented)
+  uint32_t *out_doc, *out_seg;
+  float *out_score;
+  uint32_t *out_count;
+  unsigned long long *out_matched;  // [nq] accepted docs (total_matches)
+  uint32_t nq, k;
+  const uint32_t *error_flag;  // see MergeParams
+  uint32_t *out_flag;
+};
+
+constexpr uint32_t kSortMaxParts = 4;  // SLG_MAX_SORT_PARTS
+constexpr uint32_t kSortWords = 3 * kSortMaxParts + 2;
+constexpr uint32_t kSortedCap = 1024;  // keys sorted in LDS at a time (their varying words: <= 56 KB)
+constexpr uint32_t kSortedThreads = 512;
+
+__device__ __forceinline__ void sorted_key(const SortedSelectParams &p, uint32_t a, uint32_t seg, uint32_t doc,
+                                           uint32_t (&K)[kSortWords]) {
+#pragma unroll
+  for (uint32_t i = 0; i < kSortMaxParts; i++) {
+    uint32_t w0 = 0, w1 = 0, w2 = 0;
+    if (i < p.n_parts) {
+      if ((p.score_parts >> i) & 1u) {
+        w2 = ((p.desc_parts >> i) & 1u) ? ~a : a;
+      } else {
+        const SortColDev c = p.cols[(size_t)i * p.n_segs + seg];
+        const uint32_t pw = c.present[doc >> 5];
+        const unsigned long long v = c.key[doc];  // (0 for a Missing doc)
+        w0 = ((pw >> (doc & 31u)) & 1u) ^ 1u;
+        w1 = (uint32_t)(v >> 32);
+        w2 = (uint32_t)v;
+      }
+    }
+    K[3 * i] = w0;
+    K[3 * i + 1] = w1;
+    K[3 * i + 2] = w2;
+  }
+  K[kSortWords - 2] = seg;
+  K[kSortWords - 1] = doc;
+}
+
+// lexicographic compare of (K & mask) with a prefix: -1 below, 0 equal, 1 above
+__device__ __forceinline__ int sorted_cmp(const uint32_t (&K)[kSortWords], const uint32_t *pre, const uint32_t *dm) {
+  int c = 0;
+#pragma unroll
+  for (uint32_t w = 0; w < kSortWords; w++) {
+    const uint32_t x = K[w] & dm[w], y = pre[w];
+    if (c == 0) c = x < y ? -1 : (x > y ? 1 : 0);
+  }
+  return c;
+}
+
+// (no amdgpu_waves_per_eu: capped at 128 VGPRs for two workgroups per CU — what its 60 KB of LDS would
+//  allow — it spills 5 VGPRs; uncapped it takes 141 and none, one workgroup per CU)
+static __global__ void __launch_bounds__(kSortedThreads) select_sorted_kernel(SortedSelectParams p) {
+  constexpr uint32_t NT = kSortedThreads, NW = kSortWords, CAP = kSortedCap;
+  __shared__ uint32_t hist[256];
+  __shared__ uint32_t s_and[NW], s_or[NW], s_slot[NW];  // s_slot: LDS row of a varying word, ~0u: constant
+  __shared__ uint32_t s_pre[NW], s_dm[NW], s_qpre[NW], s_qdm[NW];  // prefix (and decided bytes) of this / the previous range
+  __shared__ uint32_t w_key[NW * CAP];
+  __shared__ uint16_t w_idx[CAP];
+  __shared__ uint32_t sh_nvalid, sh_nvary, sh_need, sh_done, sh_taken, sh_nwin;
+  const uint32_t tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const uint32_t q = blockIdx.x;
+  if (q >= p.nq) return;
+  if (q == 0 && tid == 0 && p.out_flag) *p.out_flag = *p.error_flag;
+  const uint32_t k = p.k;
+  const QueryRef qr = p.queries[q];
+  const uint32_t sb = qr.slice_begin, se = qr.slice_end;
+  const uint32_t flt = p.q_filter ? p.q_filter[q] : 0u;
+  if (tid < NW) {
+    s_and[tid] = 0xFFFFFFFFu;
+    s_or[tid] = 0u;
+    s_qpre[tid] = s_qdm[tid] = 0u;
+  }
+  if (tid == 0) sh_nvalid = 0;
+  __syncthreads();
+
+  // visit every live candidate of the query: f(ordered score, segment, doc, slot); a wave per slice
+  auto for_each = [&](auto &&f) {
+    for (uint32_t s = sb + wave; s < se; s += NT / 64) {
+      const uint64_t base = p.slice_cbeg[s];
+      const uint32_t cnt = p.slice_ccnt[s];
+      const uint32_t seg = p.slice_seg[s];
+      for (uint32_t i = lane; i < cnt; i += 64) {
+        const uint2 c = p.cand[base + i];
+        if (c.y != 0xFFFFFFFFu) f(c.x, seg, c.y, base + i);
+      }
+    }
+  };
+
+  // ---- sweep 1: accept() (tombstones / filter), the accepted count, AND / OR of every key word ----
+  {
+    uint32_t t_and[NW], t_or[NW];
+#pragma unroll
+    for (uint32_t w = 0; w < NW; w++) {
+      t_and[w] = 0xFFFFFFFFu;
+      t_or[w] = 0u;
+    }
+    uint32_t nv = 0;
+    for_each([&](uint32_t a, uint32_t seg, uint32_t doc, uint64_t at) {
+      const uint32_t *del = flt ? p.reject_table[(size_t)(flt - 1) * p.n_segs + seg] : p.segs[seg].deleted;
+      if (del && ((del[doc >> 5] >> (doc & 31)) & 1u)) {
+        p.cand[at].y = 0xFFFFFFFFu;
+        return;
+      }
+      uint32_t K[NW];
+      sorted_key(p, a, seg, doc, K);
+#pragma unroll
+      for (uint32_t w = 0; w < NW; w++) {
+        t_and[w] &= K[w];
+        t_or[w] |= K[w];
+      }
+      nv++;
+    });
+#pragma unroll
+    for (uint32_t w = 0; w < NW; w++) {
+      uint32_t x = t_and[w], y = t_or[w];
+      for (int o = 32; o > 0; o >>= 1) {
+        x &= __shfl_xor(x, o, 64);
+        y |= __shfl_xor(y, o, 64);
+      }
+      if (lane == 0) {
+        atomicAnd(&s_and[w], x);
+        atomicOr(&s_or[w], y);
+      }
+    }
+    nv = wave_sum(nv);
+    if (lane == 0) atomicAdd(&sh_nvalid, nv);
+  }
+  __syncthreads();
+  if (tid == 0) {
+    uint32_t n = 0;
+    for (uint32_t w = 0; w < NW; w++) s_slot[w] = s_and[w] != s_or[w] ? n++ : 0xFFFFFFFFu;
+    sh_nvary = n;
+    if (p.out_matched) p.out_matched[q] = sh_nvalid;
+  }
+  __syncthreads();
+  const uint32_t nvalid = sh_nvalid, nvary = sh_nvary;
+  const uint32_t nout = nvalid < k ? nvalid : k;
+
+  uint32_t k_done = 0;
+  bool have_prev = false;
+  while (k_done < nout) {
+    const uint32_t target = nout - k_done > CAP ? k_done + CAP : nout;
+    const bool last = target == nout;
+    // the final range may take more keys than it emits (dropped after the sort) within a sort of the
+    // next power of two above the keys still to emit
+    uint32_t cap_last = 64;
+    while (cap_last < nout - k_done) cap_last <<= 1;
+    cap_last = cap_last < CAP ? cap_last : CAP;
+    const bool all = last && nvalid - k_done <= cap_last;  // everything left fits: no select
+    __syncthreads();
+    if (tid < NW) s_pre[tid] = s_dm[tid] = 0u;
+    if (tid == 0) {
+      sh_need = target;
+      sh_done = all ? 1u : 0u;
+      sh_taken = all ? nvalid : 0u;
+      sh_nwin = 0;
+    }
+    __syncthreads();
+    if (!all) {
+      for (uint32_t lev = 0; lev < NW * 4; lev++) {
+        const uint32_t wd = lev >> 2, shift = 24u - 8u * (lev & 3u), bm = 0xFFu << shift;
+        if (((s_and[wd] ^ s_or[wd]) & bm) == 0u) continue;  // the same byte in every key (uniform)
+        if (tid < 256) hist[tid] = 0;
+        __syncthreads();
+        for_each([&](uint32_t a, uint32_t seg, uint32_t doc, uint64_t) {
+          uint32_t K[NW];
+          sorted_key(p, a, seg, doc, K);
+          if (sorted_cmp(K, s_pre, s_dm) != 0) return;
+          uint32_t wv = 0;
+#pragma unroll
+          for (uint32_t w = 0; w < NW; w++) wv = w == wd ? K[w] : wv;
+          const uint32_t bin = (wv >> shift) & 255u;
+          // (ties are the normal case: lanes of a wave that hold the same bin add their count once)
+          uint64_t todo = __ballot(true);
+          while (todo) {
+            const uint32_t l = (uint32_t)__builtin_ctzll(todo);
+            const uint32_t b = rl(bin, l);
+            const uint64_t same = __ballot(bin == b) & todo;
+            if (lane == l) atomicAdd(&hist[b], (uint32_t)__popcll(same));
+            todo &= ~same;
+          }
+        });
+        __syncthreads();
+        if (wave == 0) {  // lane l owns bins 4l .. 4l+3 (ascending)
+          const uint32_t b0 = 4u * lane;
+          const uint32_t h0 = hist[b0], h1 = hist[b0 + 1], h2 = hist[b0 + 2], h3 = hist[b0 + 3];
+          const uint32_t tot = h0 + h1 + h2 + h3;
+          uint32_t incl = tot;
+          for (int o = 1; o < 64; o <<= 1) {
+            const uint32_t v = __shfl_up(incl, o, 64);
+            if ((int)lane >= o) incl += v;
+          }
+          const uint32_t need = sh_need, excl = incl - tot;
+          if (excl < need && need <= incl) {  // exactly one lane
+            uint32_t cum = excl, b = b0, h = h0;
+            if (cum + h < need) { cum += h; b = b0 + 1; h = h1; }
+            if (cum + h < need) { cum += h; b = b0 + 2; h = h2; }
+            if (cum + h < need) { cum += h; b = b0 + 3; h = h3; }
+            s_pre[wd] |= b << shift;
+            s_dm[wd] |= bm;
+            sh_need = need - cum;                                 // rank of the target key inside the bucket
+            const uint32_t taken = (target - (need - cum)) + h;  // keys with prefix <= the chosen one
+            sh_taken = taken;
+            sh_done = (h == need - cum || (last && taken - k_done <= cap_last)) ? 1u : 0u;
+          }
+        }
+        __syncthreads();
+        if (sh_done) break;
+      }
+    }
+    const uint32_t taken = sh_taken;
+    const uint32_t count = (taken - k_done) < CAP ? (taken - k_done) : CAP;
+    // ---- gather the varying words of this range's keys ----
+    for_each([&](uint32_t a, uint32_t seg, uint32_t doc, uint64_t) {
+      uint32_t K[NW];
+      sorted_key(p, a, seg, doc, K);
+      bool win = all || sorted_cmp(K, s_pre, s_dm) <= 0;
+      if (win && have_prev) win = sorted_cmp(K, s_qpre, s_qdm) > 0;
+      const uint64_t wm = __ballot(win);
+      uint32_t wbase = 0;
+      if (wm != 0ull) {
+        const uint32_t l0 = (uint32_t)__builtin_ctzll(wm);
+        if (lane == l0) wbase = atomicAdd(&sh_nwin, (uint32_t)__popcll(wm));
+        wbase = rl(wbase, l0);
+      }
+      if (win) {
+        const uint32_t at = wbase + (uint32_t)__popcll(wm & ((1ull << lane) - 1ull));
+        if (at < CAP) {
+#pragma unroll
+          for (uint32_t w = 0; w < NW; w++)
+            if (s_slot[w] != 0xFFFFFFFFu) w_key[s_slot[w] * CAP + at] = K[w];
+        }
+      }
+    });
+    __syncthreads();
+    // ---- bitonic sort of the entries' indices, ascending key (indices >= count: padding, last) ----
+    uint32_t n2 = 1;
+    while (n2 < count) n2 <<= 1;
+    for (uint32_t i = tid; i < n2; i += NT) w_idx[i] = (uint16_t)i;
+    __syncthreads();
+    auto less = [&](const uint32_t x, const uint32_t y) {
+      if (x >= count || y >= count) return x < count ? true : (y < count ? false : x < y);
+      for (uint32_t r = 0; r < nvary; r++) {
+        const uint32_t u = w_key[r * CAP + x], v = w_key[r * CAP + y];
+        if (u != v) return u < v;
+      }
+      return false;
+    };
+    for (uint32_t size = 2; size <= n2; size <<= 1) {
+      for (uint32_t stride = size >> 1; stride > 0; stride >>= 1) {
+        for (uint32_t t = tid; t < (n2 >> 1); t += NT) {
+          const uint32_t i = 2 * t - (t & (stride - 1));  // lower index of the pair
+          const uint32_t j = i + stride;
+          const bool up = (i & size) == 0;
+          const uint32_t xi = w_idx[i], xj = w_idx[j];
+          if (up ? less(xj, xi) : less(xi, xj)) {
+            w_idx[i] = (uint16_t)xj;
+            w_idx[j] = (uint16_t)xi;
+          }
+        }
+        __syncthreads();
+      }
+    }
+    // ---- write the range (the final one drops what it took beyond k) ----
+    const uint32_t emit = target - k_done;
+    for (uint32_t i = tid; i < emit; i += NT) {
+      const uint32_t e = w_idx[i];
+      auto word = [&](const uint32_t w) { return s_slot[w] != 0xFFFFFFFFu ? w_key[s_slot[w] * CAP + e] : s_and[w]; };
+      float score = 0.0f;  // (MatchOnly: no `_score` part, the hit's score is 0.0, query/wand.rs match_only_loop)
+      if (p.score_parts) {
+        const uint32_t sp = (uint32_t)__builtin_ctz(p.score_parts);
+        const uint32_t a = word(3 * sp + 2) ^ (((p.desc_parts >> sp) & 1u) ? 0xFFFFFFFFu : 0u);
+        score = key_to_float((int32_t)(a ^ 0x80000000u));
+      }
+      p.out_doc[(size_t)q * k + k_done + i] = word(NW - 1);
+      p.out_seg[(size_t)q * k + k_done + i] = word(NW - 2);
+      p.out_score[(size_t)q * k + k_done + i] = score;
+    }
+    if (tid < NW) {
+      s_qpre[tid] = s_pre[tid];
+      s_qdm[tid] = s_dm[tid];
+    }
+    k_done = target;
+    have_prev = true;
+  }
+  for (uint32_t i = nout + tid; i < k; i += NT) {
+    p.out_doc[(size_t)q * k + i] = 0u;
+    p.out_seg[(size_t)q * k + i] = 0u;
+    p.out_score[(size_t)q * k + i] = 0.0f;
+  }
+  if (tid == 0) p.out_count[q] = nout;
+}
+
 }  // namespace slg

@@ -220,7 +220,7 @@ void plan_queries(const Pass1Ctx &c, const uint32_t q_lo, const uint32_t q_hi, P
   const BatchIn &in = c.in;
   const slg_score_plans &pl = in.plans;
   const uint32_t n_segs = (uint32_t)c.segs.size();
-  const uint32_t k = in.k;
+  const uint32_t k = planning_k(in);
   auto &sqs = o.sqs;
   auto &terms = o.terms;
   sqs.reserve((size_t)(q_hi - q_lo) * n_segs);
@@ -755,7 +755,7 @@ void plan_batch(const std::vector<SegView> &segs, const slg_tuning &tn, const Ba
     Running() { g_plans_running.fetch_add(1, std::memory_order_relaxed); }
     ~Running() { g_plans_running.fetch_sub(1, std::memory_order_relaxed); }
   } running;
-  const uint32_t nq = in.nq, k = in.k;
+  const uint32_t nq = in.nq, k = planning_k(in);
   const uint32_t n_segs = (uint32_t)segs.size();
   const BatchFacts facts = validate_batch(in, n_segs);
   out = Plan();
@@ -911,6 +911,51 @@ void plan_batch(const std::vector<SegView> &segs, const slg_tuning &tn, const Ba
       if (in.q_filter[q] >= 0) out.q_filter[q] = (uint32_t)in.q_filter[q] + 1u;
   }
   out.layout();
+}
+
+// ---- sort keys of numeric fast fields ----------------------------------------------------------
+namespace {
+inline uint64_t i64_key(int64_t v) { return (uint64_t)v ^ 0x8000000000000000ull; }
+inline uint64_t f64_key(double v) {  // f64::total_cmp order: negative values flipped whole, positive ones above them
+  uint64_t b;
+  std::memcpy(&b, &v, 8);
+  return (b >> 63) ? ~b : (b | 0x8000000000000000ull);
+}
+// Some(Greater) of a.partial_cmp(b) (None: a NaN, = Equal for min_by / max_by)
+template <typename T>
+inline bool greater(T a, T b) { return a > b; }
+
+template <typename T>
+void field_keys(uint32_t n_docs, const uint32_t *offsets, const T *values, uint64_t (*enc)(T), uint64_t *asc,
+                uint64_t *desc, uint32_t *present) {
+  for (uint32_t w = 0; w < (n_docs + 31) / 32; w++) present[w] = 0u;
+  for (uint32_t d = 0; d < n_docs; d++) {
+    const uint32_t a = offsets ? offsets[d] : 0u, e = offsets ? offsets[d + 1] : 0u;
+    if (e <= a) {
+      asc[d] = desc[d] = 0ull;
+      continue;
+    }
+    // Iterator::min_by: cmp::min_by(acc, y) = acc unless acc > y; max_by: cmp::max_by(acc, y) = y unless acc > y
+    T mn = values[a], mx = values[a];
+    for (uint32_t i = a + 1; i < e; i++) {
+      if (greater(mn, values[i])) mn = values[i];
+      if (!greater(mx, values[i])) mx = values[i];
+    }
+    asc[d] = enc(mn);
+    desc[d] = ~enc(mx);
+    present[d >> 5] |= 1u << (d & 31u);
+  }
+}
+}  // namespace
+
+void sort_field_keys(int kind, uint32_t n_docs, const uint32_t *offsets, const void *values, uint64_t *asc,
+                     uint64_t *desc, uint32_t *present_words) {
+  if (kind == 1)
+    field_keys<int64_t>(n_docs, offsets, static_cast<const int64_t *>(values), i64_key, asc, desc, present_words);
+  else if (kind == 2)
+    field_keys<double>(n_docs, offsets, static_cast<const double *>(values), f64_key, asc, desc, present_words);
+  else
+    throw SlgError(SLG_ERR_INVALID, "unknown sort field kind");
 }
 
 }  // namespace slgplan

@@ -46,7 +46,25 @@ struct BatchIn {
   int strategy = SLG_STRATEGY_WAND;
   const char *filter_live = nullptr;  // [n_filters] 1 = the filter id is registered
   size_t n_filters = 0;
+  // field-sorted batch (slg_batch_prepare_sorted): every matched doc is a candidate with its exact score,
+  // whatever k is — candidates mode, no threshold seed, no MaxScore classification
+  bool sorted = false;
 };
+
+// k the batch is planned (and its scoring kernel launched) with: a sorted batch runs as a large-k batch
+// (> 1024: candidates mode and no seed), whatever k it returns
+constexpr uint32_t kSortedPlanK = 1025;
+inline uint32_t planning_k(const BatchIn &in) { return in.sorted && in.k < kSortedPlanK ? kSortedPlanK : in.k; }
+
+// ---- sort keys of numeric fast fields (slg_index_add_sort_field_*) ----
+// query/sort.rs:300-345: the value of a field part is min_by (Asc) / max_by (Desc) of the doc's values under
+// partial_cmp(..).unwrap_or(Equal) — min_by keeps the first of "equal" elements, max_by the last — and a doc
+// without values is Missing.  Per doc this writes the value's order-preserving u64 under each order (asc:
+// ascending i64 / f64 total_cmp order; desc: the complement of the same, so ascending u64 order is the sort
+// order in both) and a presence bit (bit d & 31 of word d >> 5; clear = Missing, whose keys are 0).
+// offsets == NULL: every doc is Missing.  kind: 1 i64, 2 f64.
+void sort_field_keys(int kind, uint32_t n_docs, const uint32_t *offsets, const void *values, uint64_t *asc,
+                     uint64_t *desc, uint32_t *present_words);
 
 struct Plan {
   // ---- the descriptor image ----

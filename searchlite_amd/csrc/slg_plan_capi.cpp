@@ -138,4 +138,16 @@ void slgp_copy(const void *plan, int what, void *dst) {
 
 void slgp_free(void *plan) { delete static_cast<slgplan::Plan *>(plan); }
 
+// the host side of slg_index_add_sort_field_i64 / _f64 (kind 1 / 2) for one segment: per doc the ascending
+// and descending u64 keys and the presence bitmap ((n_docs + 31) / 32 words).  0, or a negative error code
+int slgp_sort_keys(int kind, uint32_t n_docs, const uint32_t *offsets, const void *values, uint64_t *asc,
+                   uint64_t *desc, uint32_t *present_words) {
+  try {
+    slgplan::sort_field_keys(kind, n_docs, offsets, values, asc, desc, present_words);
+    return SLG_OK;
+  } catch (const slgplan::SlgError &e) {
+    return e.code;
+  }
+}
+
 }  // extern "C"

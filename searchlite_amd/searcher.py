@@ -199,20 +199,76 @@ class GpuIndex:
     def remove_filter(self, filter_id: int) -> None:
         N.check(self._lib.slg_index_remove_filter(self._h, filter_id))
 
+    # -- sort fields (query/sort.rs: `sort` on numeric fast fields) -----------------------------
+    def add_sort_field(self, per_segment_values, dtype) -> int:
+        """Register a numeric fast field for field-sorted search (slg_index_add_sort_field_i64 / _f64).
+        per_segment_values[s]: the values of segment s's docs, either a list of n_docs arrays (empty = Missing)
+        or a CSR pair (offsets[n_docs + 1], values), or None (every doc Missing).  dtype: np.int64 or
+        np.float64.  Returns the sort field id (ids are never reused)."""
+        dt = np.dtype(dtype)
+        if dt not in (np.dtype(np.int64), np.dtype(np.float64)):
+            raise TypeError("sort fields are int64 or float64")
+        assert len(per_segment_values) == self.n_segs
+        keep = []
+        offs_p, vals_p = [], []
+        for s, v in enumerate(per_segment_values):
+            if v is None:
+                offs_p.append(None)
+                vals_p.append(None)
+                continue
+            if isinstance(v, tuple):
+                offs = np.ascontiguousarray(v[0], dtype=np.uint32)
+                vals = np.ascontiguousarray(v[1], dtype=dt)
+            else:
+                lens = np.array([len(x) for x in v], dtype=np.uint64)
+                offs = np.zeros(len(v) + 1, dtype=np.uint32)
+                offs[1:] = np.cumsum(lens)
+                vals = np.ascontiguousarray(np.concatenate([np.asarray(x, dtype=dt) for x in v]) if len(v) else
+                                            np.zeros(0, dt), dtype=dt)
+            assert len(offs) == int(self.segments[s].n_docs) + 1, "one offset per doc + 1"
+            if vals.size == 0:
+                vals = np.zeros(1, dt)
+            keep += [offs, vals]
+            offs_p.append(offs.ctypes.data)
+            vals_p.append(vals.ctypes.data)
+        po = (C.c_void_p * self.n_segs)(*offs_p)
+        pv = (C.c_void_p * self.n_segs)(*vals_p)
+        fn = self._lib.slg_index_add_sort_field_i64 if dt == np.int64 else self._lib.slg_index_add_sort_field_f64
+        rc = fn(self._h, po, pv)
+        if rc < 0:
+            N.check(rc)
+        return rc
+
+    def remove_sort_field(self, sort_field_id: int) -> None:
+        N.check(self._lib.slg_index_remove_sort_field(self._h, sort_field_id))
+
+    def search_sorted(self, q_offsets, q_terms, q_weights, k: int, sort, strategy: int = Wand, q_filter=None,
+                      **plans):
+        """Field-sorted batch search (slg_batch_prepare_sorted).  sort: [(field, order)], field = a sort field id
+        or "_score", order = "asc" / "desc"; **plans: the score plan arrays of prepare().
+        -> (doc, seg, score, count, matched)."""
+        b = self.prepare(q_offsets, q_terms, q_weights, k, strategy, q_filter, sort=sort, **plans)
+        try:
+            b.run()
+            return b.fetch() + (b.matched_counts(),)
+        finally:
+            b.close()
+
     # -- search ----------------------------------------------------------------------
     def prepare(self, q_offsets, q_terms, q_weights, k: int, strategy: int = Wand,
                 q_filter=None, q_leaf=None, q_plan=None, q_tie=None, q_nleaves=None,
                 q_leaf_offsets=None, leaf_group=None, q_group_offsets=None, group_plan=None,
                 group_tie=None, q_node_offsets=None, node_kind=None, node_tie=None, node_parent=None,
-                q_min_match=None) -> "PreparedBatch":
+                q_min_match=None, sort=None) -> "PreparedBatch":
         """q_leaf / q_plan / q_tie / q_nleaves: score plans; leaf_group / group_plan / group_tie with
         their per-query offsets: two-level plans; q_node_offsets / node_kind / node_tie / node_parent:
         trees of any shape, node by node in pre-order (slg_batch_prepare_plans, slg_score_plans);
-        q_min_match: minimum_should_match per query (leaves that must hold a doc)."""
+        q_min_match: minimum_should_match per query (leaves that must hold a doc); sort: a field sort
+        (search_sorted) -> slg_batch_prepare_sorted."""
         return PreparedBatch(self, q_offsets, q_terms, q_weights, k, strategy, q_filter,
                              q_leaf, q_plan, q_tie, q_nleaves, q_leaf_offsets, leaf_group,
                              q_group_offsets, group_plan, group_tie, q_node_offsets, node_kind, node_tie, node_parent,
-                             q_min_match)
+                             q_min_match, sort)
 
     def search_plan(self, q_offsets, q_terms, q_weights, k: int, q_leaf=None, q_plan=None,
                     q_tie=None, q_nleaves=None, strategy: int = Wand, q_filter=None, **tree):
@@ -463,6 +519,18 @@ class ShardGroup:
         self.close()
 
 
+def sort_spec(sort) -> "N.SortSpec":
+    """[(field, order)] -> slg_sort_spec: field = sort field id or "_score" (N.SORT_SCORE), order = "asc" /
+    "desc" (or N.ORDER_*).  More than N.MAX_SORT_PARTS parts are passed on as given (the library refuses
+    them)."""
+    spec = N.SortSpec()
+    spec.n_parts = len(sort)
+    for i, (field, order) in enumerate(sort[:N.MAX_SORT_PARTS]):
+        spec.field[i] = N.SORT_SCORE if field == "_score" else int(field)
+        spec.order[i] = {"asc": N.ORDER_ASC, "desc": N.ORDER_DESC}.get(order, order)
+    return spec
+
+
 class PreparedBatch:
     """A planned query batch with device-resident descriptors and work buffers."""
 
@@ -470,7 +538,7 @@ class PreparedBatch:
                  q_filter=None, q_leaf=None, q_plan=None, q_tie=None, q_nleaves=None,
                  q_leaf_offsets=None, leaf_group=None, q_group_offsets=None, group_plan=None,
                  group_tie=None, q_node_offsets=None, node_kind=None, node_tie=None, node_parent=None,
-                 q_min_match=None):
+                 q_min_match=None, sort=None):
         self.index = index
         self._lib = index._lib
         q_offsets = np.ascontiguousarray(q_offsets, dtype=np.uint32)
@@ -498,9 +566,16 @@ class PreparedBatch:
         assert qmm is None or len(qmm) == self.nq
         plans = N.ScorePlans(opt(ql), opt(qp), opt(qt), opt(qn), opt(qlo), opt(lg), opt(qgo), opt(gp), opt(gt),
                              opt(qno), opt(nk), opt(ntie), opt(npar), opt(qmm))
-        self._h = self._lib.slg_batch_prepare_plans(
-            index._h, self.nq, _ptr(q_offsets), _ptr(q_terms), _ptr(q_weights), C.addressof(plans),
-            opt(qf), k, strategy)
+        self.sorted = sort is not None
+        if sort is None:
+            self._h = self._lib.slg_batch_prepare_plans(
+                index._h, self.nq, _ptr(q_offsets), _ptr(q_terms), _ptr(q_weights), C.addressof(plans),
+                opt(qf), k, strategy)
+        else:
+            spec = sort_spec(sort)
+            self._h = self._lib.slg_batch_prepare_sorted(
+                index._h, self.nq, _ptr(q_offsets), _ptr(q_terms), _ptr(q_weights), C.addressof(plans),
+                opt(qf), C.addressof(spec), k, strategy)
         if not self._h:
             raise N.SlgError(N.last_error_code() or N.ERR_INVALID, N.last_error())
         index._batches.add(self)
@@ -518,6 +593,12 @@ class PreparedBatch:
 
     def run(self) -> None:
         N.check(self._lib.slg_batch_run(self._h))
+
+    def matched_counts(self) -> np.ndarray:
+        """Accepted docs per query of a sorted batch's last run (total_matches); waits."""
+        out = np.zeros(max(self.nq, 1), dtype=np.uint64)
+        N.check(self._lib.slg_batch_matched_counts(self._h, _ptr(out)))
+        return out[:self.nq]
 
     def run_sharded(self, group: "ShardGroup", fetch: bool = True, seq: Optional[int] = None):
         """slg_batch_run_sharded: this rank's segments, ONE ncclAllGather of the result blocks,

@@ -184,11 +184,11 @@ typedef struct {
                                     index keeps for reuse; auto = a quarter of the HBM free after
                                     staging, within [1 GiB, 24 GiB].  The pool is drained whenever a
                                     device allocation of the library fails (slg_index_trim_pool) */
-  uint32_t uniform_kernel;       /* SLG_UNIFORM_KERNEL (4): form of the few-term scoring kernel: 4 = blocked
-                                    layout, <= 8 lists; 3 = one list per 64-lane slot, <= 8 lists; 2 = the
-                                    round-2 kernel, <= 4 lists (both kept for A/B timing on one device) */
-  uint32_t uniform_sigma_x100;   /* SLG_UNIFORM_SIGMA (0 = 160): the few-term planner keeps a round's
-                                    expected lanes (slots) + this many hundredths of a sigma under 64.3 (8.3) */
+  uint32_t uniform_kernel;       /* SLG_UNIFORM_KERNEL (4): form of the few-term scoring kernel; 4 (blocked
+                                    layout, <= 8 lists) is the only one.  2 and 3, earlier forms, were
+                                    removed: SLG_ERR_UNSUPPORTED; any other value SLG_ERR_INVALID */
+  uint32_t uniform_sigma_x100;   /* SLG_UNIFORM_SIGMA (0 = 320): the few-term planner keeps a round's
+                                    expected lanes + this many hundredths of a sigma under 64.3 */
   int32_t inline_cuts;           /* SLG_INLINE_CUTS (-1 = auto: on): the blocked few-term kernel cuts the lists at
                                     its slice's round boundaries itself instead of reading cut points that
                                     partition_rounds_kernel wrote for the whole batch; 0 off; 1 on */

@@ -469,14 +469,11 @@ template <> void launch_score_kregs<16>(const RoundScoreParams &, int, hipStream
 }  // namespace slg
 namespace {
 
-// kind: 1 few-term kernel (slg_score_uni3.hpp; 5: its 5..8-list form), 2 many-term kernel (slg_score_multi.hpp),
-// 3 many-term kernel with pruning-classified lists, 4 the round-2 few-term kernel (slg_score_uni.hpp)
-// 6 / 7: the few-term kernel in its blocked form (slg_score_uni4.hpp), <= 4 / 5..8 lists; 8 / 9: the same
-// with score plans (flat Sum / DisMax over leaves)
-int uniform_kind(uint32_t form, uint32_t max_terms, bool plans) {
+// kind: 2 many-term kernel (slg_score_multi.hpp), 3 many-term kernel with pruning-classified lists,
+// 6 / 7 the few-term kernel (slg_score_uni4.hpp), <= 4 / 5..8 lists; 8 / 9: the same with score plans
+// (flat Sum / DisMax over leaves)
+int uniform_kind(uint32_t max_terms, bool plans) {
   const bool few = max_terms <= (uint32_t)slg::kUniMaxLists;
-  if (form == 2) return 4;
-  if (form == 3) return few ? 1 : 5;
   if (plans) return few ? 8 : 9;
   return few ? 6 : 7;
 }
@@ -896,14 +893,11 @@ slg_index *slg_index_create_tuned(const slg_segment_desc *segs, uint32_t n_segs,
     } else {
       slg_tuning_default(&tune);
     }
-    // (a zero-initialised struct from a C or Rust caller must not plan for one kernel and launch another)
-    SLG_REQUIRE(tune.uniform_kernel >= 2 && tune.uniform_kernel <= 4, "slg_tuning.uniform_kernel must be 2, 3 or 4");
-#ifndef SLG_LEGACY_KERNELS
-    if (tune.uniform_kernel != 4)
-      throw SlgError(SLG_ERR_UNSUPPORTED, "slg_tuning.uniform_kernel 2 / 3 need a library built with -DSLG_LEGACY_KERNELS");
-#endif
-    tune.uniform_max_terms = std::min<uint32_t>(
-        tune.uniform_max_terms, tune.uniform_kernel == 2 ? slg::kUniMaxLists : slg::kU3MaxLists);
+    // (4 is the only form left; a zero-initialised struct from a C or Rust caller is rejected here)
+    if (tune.uniform_kernel == 2 || tune.uniform_kernel == 3)
+      throw SlgError(SLG_ERR_UNSUPPORTED, "slg_tuning.uniform_kernel 2 / 3: those forms of the few-term kernel were removed");
+    SLG_REQUIRE(tune.uniform_kernel == 4, "slg_tuning.uniform_kernel must be 4");
+    tune.uniform_max_terms = std::min<uint32_t>(tune.uniform_max_terms, slg::kU4MaxLists);
     tune.max_rounds_per_slice = std::min<uint32_t>(tune.max_rounds_per_slice, slg::kMaxRoundsPerSlice);
     tune.slices_per_subquery = std::max<uint32_t>(1, tune.slices_per_subquery);
     for (uint32_t s = 0; s < n_segs; s++) validate_segment(segs[s], s, tune.validate != 0);
@@ -1613,15 +1607,14 @@ int slg_batch_run(slg_batch *b) {
       pp.slice_desc = b->d_slice_desc.as<slg::SliceDesc>();
       pp.nq = b->nq;
       // the blocked few-term kernel can cut its slices itself (slg_tuning.inline_cuts)
-      const bool inline_cuts = b->uniform && ix->tune.uniform_kernel >= 4 &&
-                               (ix->tune.inline_cuts >= 0 ? ix->tune.inline_cuts != 0 : true);
+      const bool inline_cuts = b->uniform && (ix->tune.inline_cuts >= 0 ? ix->tune.inline_cuts != 0 : true);
       pp.n_boundaries = inline_cuts ? 0u : b->n_boundaries;
       pp.n_slices = b->n_slices;
       pp.tpb_shift = b->max_terms <= 4 ? 2u : 3u;
       // few-term kernel: one wave per slice, or (slg_tuning.score_waves_per_simd) persistent waves that
       // pull slices from the batch's work queues (slg_score_uni4.hpp)
       const int score_kind =
-          b->uniform ? uniform_kind(ix->tune.uniform_kernel, b->max_terms, b->plan_batch) : (b->pruned ? 3 : 2);
+          b->uniform ? uniform_kind(b->max_terms, b->plan_batch) : (b->pruned ? 3 : 2);
       uint32_t n_waves = b->n_slices;
       const bool persistent = (score_kind == 6 || score_kind == 7) && ix->tune.score_waves_per_simd != 0;
       if (persistent)

@@ -156,9 +156,8 @@ constexpr int kSpanWords = 512;           // bitmap words per window (many-term 
 constexpr uint32_t kSpan = kSpanWords * 32;  // docs per window
 constexpr int kUniSlots = 8;                 // 64-posting slots per round
 constexpr int kUniCap = kUniSlots * 64;      // postings per round
-constexpr int kUniMaxLists = 4;              // lists per sub-query on the round-2 few-term kernel and
-                                             // on the 4-bit-field form of the current one
-constexpr int kU3MaxLists = 8;               // lists per sub-query on the few-term kernel (8-bit fields)
+constexpr int kUniMaxLists = 4;              // lists per sub-query on the few-term kernel's 4-bit-field form
+constexpr int kU4MaxLists = 8;               // lists per sub-query on the few-term kernel (8-bit fields)
 constexpr int kMultiCap = 512;       // accumulators (= distinct docs) per chunk
 constexpr int kMultiTarget = 448;    // planned postings per round (host; measured optimum 448-480)
 

@@ -490,78 +490,51 @@ void plan_queries(const Pass1Ctx &c, const uint32_t q_lo, const uint32_t q_hi, P
 }
 
 // ---- pass 2: rounds of about one register set of postings, slices of consecutive rounds ----------
-// postings per round of a few-term sub-query.  Slot forms of the kernel (slg_score_uni.hpp, _uni3):
-// every list is padded to a 64-lane slot (half a slot wasted per list on average).  A round that needs more than 8 slots is streamed in chunks at 2-3x
-// the cost, so the target follows the sub-query's own mix of list lengths: the largest R (steps of
-// 16) whose expected slots stay under 8 with 1.6 sigma to spare.  The longest list is cut at exact
-// strides (its count is R * f); every other list's count c is roughly Poisson around R * f:
-// ceil(c / 64) has mean c/64 + 1/2 and variance c/4096 + 1/12.
+// postings per round of a few-term sub-query.  The kernel's blocked layout (slg_score_uni4.hpp):
+// a list is padded to whole lanes of 8 postings, a round has 64 lanes.  A round that needs more
+// lanes is streamed in chunks at 2-3x the cost, so the target follows the sub-query's own mix of
+// list lengths: the largest R whose expected lanes stay under 64 with `sigmas` to spare.  The
+// longest list is cut at exact strides (its count is R * f); every other list's count c is roughly
+// Poisson around R * f: ceil(c / 8) has mean c/8 + 7/16 and variance c/64 + 1/12.
 uint32_t uniform_round_target(const slg::RoundQuery &sq, const slg::TermRef *t, uint64_t P, const slg_tuning &tn) {
   const uint32_t n = sq.n_terms;
   const double Pd = (double)P;
-  // sigmas to spare: blocked form 1.0 / 1.6 / 2.0 / 2.5 / 3.0 / 3.5 / 4.0 / 5.0 -> 0.0874 / 0.0791 / 0.0762 /
+  // sigmas to spare: 1.0 / 1.6 / 2.0 / 2.5 / 3.0 / 3.5 / 4.0 / 5.0 -> 0.0874 / 0.0791 / 0.0762 /
   // 0.0744 / 0.0728 / 0.0727 / 0.0734 / 0.0752 ms on config 2 (an over-full round costs 2-3 rounds)
-  const double sigmas = tn.uniform_sigma_x100 ? tn.uniform_sigma_x100 / 100.0 : (tn.uniform_kernel >= 4 ? 3.2 : 1.6);
-  uint32_t dflt;
-  if (tn.uniform_kernel >= 4) {
-    // blocked layout (slg_score_uni4.hpp): a list is padded to whole lanes of 8 postings, a round
-    // has 64 lanes.  ceil(c / 8) has mean c/8 + 7/16 and variance c/64 + 1/12 (c roughly Poisson)
-    dflt = (uint32_t)slg::kUniCap;
-    if (!tn.uniform_round_target && n > 1) {
-      // lanes a round of R postings is expected to need, plus `sigmas` standard deviations
-      auto lanes_needed = [&](const uint32_t R) {
-        double mu = 0.0, var = 0.0;
-        for (uint32_t j = 0; j < n; j++) {
-          const double c = (double)R * (double)t[j].df / Pd;
-          if (j == sq.longest) {
-            mu += std::ceil(c / 8.0);
-          } else {
-            mu += c / 8.0 + 7.0 / 16.0;
-            var += c / 64.0 + 1.0 / 12.0;
-          }
+  const double sigmas = tn.uniform_sigma_x100 ? tn.uniform_sigma_x100 / 100.0 : 3.2;
+  uint32_t dflt = (uint32_t)slg::kUniCap;
+  if (!tn.uniform_round_target && n > 1) {
+    // lanes a round of R postings is expected to need, plus `sigmas` standard deviations
+    auto lanes_needed = [&](const uint32_t R) {
+      double mu = 0.0, var = 0.0;
+      for (uint32_t j = 0; j < n; j++) {
+        const double c = (double)R * (double)t[j].df / Pd;
+        if (j == sq.longest) {
+          mu += std::ceil(c / 8.0);
+        } else {
+          mu += c / 8.0 + 7.0 / 16.0;
+          var += c / 64.0 + 1.0 / 12.0;
         }
-        return mu + sigmas * std::sqrt(var);
-      };
-      // the largest R (steps of 8) that stays under 64.3 lanes.  With f = the longest list's share of
-      // the postings: mu ~ R/8 + b, var = c R + d (b = 7/16 (n-1) + 1/2, c = (1-f)/64, d = (n-1)/12);
-      // R/8 + b + s sqrt(c R + d) = 64.3 is a quadratic in y = sqrt(c R + d); the root is then
-      // corrected against the exact count (the ceil) in steps of 8 — usually two evaluations (a scan
-      // over all 53 candidates cost 70 ms of planning on config 4's 65 536 sub-queries)
-      const double f = (double)t[sq.longest].df / Pd;
-      const double b = 7.0 / 16.0 * (n - 1) + 0.5, c = (1.0 - f) / 64.0, d = (n - 1) / 12.0;
-      double x = (64.3 - b) * 8.0;
-      if (c > 1e-9) {
-        const double qa = 1.0 / (8.0 * c), qc = b - 64.3 - d / (8.0 * c);
-        const double y = (-sigmas + std::sqrt(sigmas * sigmas - 4.0 * qa * qc)) / (2.0 * qa);
-        x = (y * y - d) / c;
       }
-      uint32_t R = (uint32_t)std::min(std::max(x, 64.0), (double)slg::kUniCap) & ~7u;
-      while (R > 64 && lanes_needed(R) > 64.3) R -= 8;
-      while (R + 8 <= (uint32_t)slg::kUniCap && lanes_needed(R + 8) <= 64.3) R += 8;
-      dflt = R;
+      return mu + sigmas * std::sqrt(var);
+    };
+    // the largest R (steps of 8) that stays under 64.3 lanes.  With f = the longest list's share of
+    // the postings: mu ~ R/8 + b, var = c R + d (b = 7/16 (n-1) + 1/2, c = (1-f)/64, d = (n-1)/12);
+    // R/8 + b + s sqrt(c R + d) = 64.3 is a quadratic in y = sqrt(c R + d); the root is then
+    // corrected against the exact count (the ceil) in steps of 8 — usually two evaluations (a scan
+    // over all 53 candidates cost 70 ms of planning on config 4's 65 536 sub-queries)
+    const double f = (double)t[sq.longest].df / Pd;
+    const double b = 7.0 / 16.0 * (n - 1) + 0.5, c = (1.0 - f) / 64.0, d = (n - 1) / 12.0;
+    double x = (64.3 - b) * 8.0;
+    if (c > 1e-9) {
+      const double qa = 1.0 / (8.0 * c), qc = b - 64.3 - d / (8.0 * c);
+      const double y = (-sigmas + std::sqrt(sigmas * sigmas - 4.0 * qa * qc)) / (2.0 * qa);
+      x = (y * y - d) / c;
     }
-  } else {
-    dflt = 64u * (slg::kUniSlots > (int)n ? slg::kUniSlots - n : 0u) + 64u;
-    if (!tn.uniform_round_target && n > 1) {
-      uint32_t best = 64;
-      for (uint32_t R = 96; R <= (uint32_t)slg::kUniCap; R += 16) {
-        double mu = 0.0, var = 0.0;
-        for (uint32_t j = 0; j < n; j++) {
-          const double c = (double)R * (double)t[j].df / Pd;
-          if (j == sq.longest) {
-            mu += std::ceil(c / 64.0);
-          } else {
-            mu += c / 64.0 + 0.5;
-            var += c / 4096.0 + 1.0 / 12.0;
-          }
-        }
-        // (round-2 kernel, 1.0 / 1.3 / 1.6 / 2.0 / 2.5 sigma: 0.1024 / 0.1011 / 0.1006 / 0.1019 / 0.1039 ms on
-        //  config 2; fixed 384: 0.1042)
-        if (mu + sigmas * std::sqrt(var) > 8.3) break;
-        best = R;
-      }
-      dflt = best;
-    }
+    uint32_t R = (uint32_t)std::min(std::max(x, 64.0), (double)slg::kUniCap) & ~7u;
+    while (R > 64 && lanes_needed(R) > 64.3) R -= 8;
+    while (R + 8 <= (uint32_t)slg::kUniCap && lanes_needed(R + 8) <= 64.3) R += 8;
+    dflt = R;
   }
   return std::max<uint32_t>(48, std::min<uint32_t>(tn.uniform_round_target ? tn.uniform_round_target : dflt,
                                                    (uint32_t)slg::kUniCap));
@@ -624,7 +597,7 @@ void plan_rounds(const std::vector<SegView> &segs, const slg_tuning &tn, uint32_
   // 5..8-list form for large k (config 3, k = 101: 5.03 ms at 16, 5.11 at 8), 6 on that form for
   // k <= 64 (multi-field workload, k = 11: the 15-round slices of the dense sub-queries ran 125 us
   // of a 144-us launch; 0.165 ms at 15, 0.124 at 6, 0.135 at 4)
-  const bool blocked8 = out.uniform && tn.uniform_kernel >= 4 && out.max_terms > (uint32_t)slg::kUniMaxLists;
+  const bool blocked8 = out.uniform && out.max_terms > (uint32_t)slg::kUniMaxLists;
   const uint32_t rps_cap = std::max<uint32_t>(
       max_rps, tn.max_rounds_per_slice ? tn.max_rounds_per_slice
                                        : (out.uniform && !blocked8 ? 8u
@@ -855,11 +828,11 @@ void plan_batch(const std::vector<SegView> &segs, const slg_tuning &tn, const Ba
     out.n_postings_nonessential = 0;
   }
   // which kernel: the few-term kernel (slg_score_uni4.hpp) takes batches of <= 8 lists per sub-query
-  // without non-essential lists — flat sums, and (its plan instantiation, blocked form only) flat score
+  // without non-essential lists — flat sums, and (its plan instantiation) flat score
   // plans: Sum / DisMax over leaves of one or more terms, i.e. every multi-field query string
   // (api/reader.rs:2576-2586: `fields: None` = all text fields).  Two-level plans, more lists and
   // classified batches run on the many-term kernel
-  const bool plans_fit = !any_plan || (tn.uniform_kernel >= 4 && !out.nested && !out.deep && tn.uniform_plans != 0);
+  const bool plans_fit = !any_plan || (!out.nested && !out.deep && tn.uniform_plans != 0);
   out.uniform = out.max_terms <= tn.uniform_max_terms && plans_fit;
   if (facts.min_match && !out.uniform)
     throw SlgError(SLG_ERR_UNSUPPORTED,

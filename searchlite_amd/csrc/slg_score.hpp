@@ -1,8 +1,7 @@
 // slg_score.hpp — shared definitions of the round-scoring kernels: the planning kernel
 // partition_rounds_kernel, RoundScoreParams, wave scans, in-kernel stamps (diagnostic builds).
 // The scoring kernels themselves: slg_score_uni4.hpp (<= 8 lists), slg_score_multi.hpp (9..32
-// lists, score plans beyond the few-term kernel's, MaxScore / block-max pruning); the superseded
-// few-term forms slg_score_uni.hpp / slg_score_uni3.hpp build only with -DSLG_LEGACY_KERNELS.
+// lists, score plans beyond the few-term kernel's, MaxScore / block-max pruning).
 //
 // Restates query/wand.rs:459-566 (brute_force: every posting of every term is scored and
 // summed per doc, in ScorePlan leaf order planner.rs:122-135) and push_top_k

@@ -4,10 +4,6 @@
 #include <hip/hip_runtime.h>
 
 #include "slg_score.hpp"
-#ifdef SLG_LEGACY_KERNELS  // the superseded few-term forms, for A/B timing on one device (tools/ab_uniform.sh)
-#include "slg_score_uni.hpp"
-#include "slg_score_uni3.hpp"
-#endif
 #include "slg_score_uni4.hpp"
 #include "slg_score_multi.hpp"
 
@@ -24,23 +20,6 @@ void launch_score_kregs(const RoundScoreParams &sp, int kind, hipStream_t st);
 // wave: a finished wave frees its wave slot and its LDS at once.
 template <>
 void launch_score_kregs<SLG_INST_KREGS>(const RoundScoreParams &sp, int kind, hipStream_t st) {
-#ifdef SLG_LEGACY_KERNELS
-  if (kind == 1) {  // <= 4 lists (slg_score_uni3.hpp)
-    hipLaunchKernelGGL((score_uniform3_kernel<SLG_INST_KREGS, 4>), dim3(sp.n_slices), dim3(64),
-                       u3_wave_lds(SLG_INST_KREGS, 4), st, sp);
-    return;
-  }
-  if (kind == 5) {  // 5..8 lists: the same kernel with 8 list bits per filter field
-    hipLaunchKernelGGL((score_uniform3_kernel<SLG_INST_KREGS, 8>), dim3(sp.n_slices), dim3(64),
-                       u3_wave_lds(SLG_INST_KREGS, 8), st, sp);
-    return;
-  }
-  if (kind == 4) {  // the round-2 form of the same kernel (slg_tuning.uniform_kernel = 2: A/B timing)
-    hipLaunchKernelGGL((score_uniform_kernel<SLG_INST_KREGS>), dim3(sp.n_slices), dim3(64),
-                       uni_wave_lds(SLG_INST_KREGS), st, sp);
-    return;
-  }
-#endif
   if (kind == 6 || kind == 7) {  // <= 4 / 5..8 lists, blocked layout (slg_score_uni4.hpp)
     // one wave per slice (sp.work_ctr == nullptr), or persistent waves: sp.n_waves / kU4WavesPerBlock
     // workgroups (u4_launch_blocks, slg_api.hip), each wave pulls slices from sp.work_ctr

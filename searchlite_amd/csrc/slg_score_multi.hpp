@@ -1,10 +1,11 @@
 // slg_score_multi.hpp — scoring kernel for queries with many terms (5..32 lists), the shape a
 // multi-field query string produces (one scored term per field and word, api/reader.rs:2971-3005).
 //
-// Same algorithm as slg_score_uni.hpp — exact pre-planned rounds, LDS bitmap + prefix popcount =
-// dense accumulator slot per doc, f32 sums in term order (query/wand.rs:459-566, planner.rs:122-135),
-// buffered top-k — and the same register shape: a 64-lane slot holds postings of ONE list, so a
-// slot's list, weight, count and address are wave-uniform scalars.  What differs: a round's lists
+// Same algorithm as the few-term kernel's earlier slot forms — exact pre-planned rounds,
+// LDS bitmap + prefix popcount = dense accumulator slot per doc, f32 sums in term order
+// (query/wand.rs:459-566, planner.rs:122-135), buffered top-k — and the same register shape: a
+// 64-lane slot holds postings of ONE list, so a slot's list, weight, count and address are
+// wave-uniform scalars.  What differs from those forms: a round's lists
 // need up to 8 + T slots, more than the 8 a wave keeps in registers, so a round is processed in
 // two sweeps over batches of 8 consecutive slots:
 //   sweep A  load each batch, set one bitmap bit per posting (ds_or, no return value);
@@ -141,7 +142,7 @@ __global__ void __launch_bounds__(64, (MODE >= 3 ? 2 : SLG_MULTI_WAVES)) score_m
   btop.init(reinterpret_cast<uint64_t *>(docid + kMultiCap));
   uint32_t ccur = 0;
   uint64_t cbeg = 0;
-  if (!BUF) {  // k > 256: candidate region (see slg_score_uni.hpp)
+  if (!BUF) {  // k > 256: candidate region (as in slg_score_uni4.hpp)
     const uint32_t b0 = lane < T ? gbounds[lane] : 0u;
     cbeg = (((uint64_t)rfl(s.cand_hi) << 32) | rfl(s.cand_lo)) + wave_sum(b0);
   }

@@ -1,13 +1,13 @@
 // slg_score_uni4.hpp — the few-term scoring kernel (<= 8 lists per sub-query; BASELINE configs 2, 3
-// and 5), fourth form: slg_score_uni3.hpp with the round's postings laid out BLOCKED over the wave.
+// and 5), with the round's postings laid out BLOCKED over the wave.
 //
 // Same algorithm — exact pre-planned rounds, FILTER + JOIN accumulate, buffered top-k; restates
 // query/wand.rs:459-566 (every posting scored, per-doc sums in ScorePlan leaf order,
 // planner.rs:122-135) and push_top_k (wand.rs:905-916).  What changed is which posting a lane holds.
-// The earlier forms gave every list whole 64-lane slots (register j of all lanes = 64 consecutive
-// postings of ONE list): a list with 10 postings in the round still cost a slot, so a 5-list round
-// of config 3 carried ~300 postings in its 512 lanes x registers, and the slot's list (posting
-// index, weight, list bit) was a wave-uniform value that had to be fetched per slot.  Here lane l
+// The earlier forms (removed) gave every list whole 64-lane slots (register j of all
+// lanes = 64 consecutive postings of ONE list): a list with 10 postings in the round still cost a
+// slot, so a 5-list round of config 3 carried ~300 postings in its 512 lanes x registers, and the
+// slot's list (posting index, weight, list bit) was a wave-uniform value fetched per slot.  Here lane l
 // holds 8 CONSECUTIVE postings of one list in its 8 registers: the round's lists are laid end to
 // end, each padded to a multiple of 8 postings, and lane l takes positions 8l .. 8l+7.  So
 //   * a list wastes at most 7 lane-registers per round (mean 3.5) instead of half a slot (32): the
@@ -505,7 +505,7 @@ score_uniform4_kernel(RoundScoreParams p_arg) {
       ccur += (uint32_t)__popcll(m);
     }
   };
-  // the per-posting threshold test works on score BITS (slg_score_uni3.hpp): thr_m1 = bits(threshold)
+  // the per-posting threshold test works on score BITS: thr_m1 = bits(threshold)
   // - 1; a threshold that is not positive sends every round through the exact candidate code (hot_all)
   uint32_t thr_m1 = 0;
   bool hot_all = true;
@@ -919,19 +919,6 @@ score_uniform4_kernel(RoundScoreParams p_arg) {
     p.slice_cbeg[slice] = cbeg;
     p.slice_ccnt[slice] = ccur;
   }
-#ifdef SLG_FOLD_PROBE
-  // Experiment (tools/ab_tags.sh, -DSLG_FOLD_PROBE): what folding merge_topk_kernel into the last-arriving
-  // slice of a query would pay per slice BEFORE any merging — an agent-scope release of this slice's
-  // candidate list (the slices of a query run on different XCDs, whose L2s are not coherent with each
-  // other for plain stores) and an arrival ticket on a per-query counter.  q_scored doubles as the counter
-  // (its value is not read in this build).
-  if constexpr (BUF) {
-    __atomic_thread_fence(__ATOMIC_RELEASE);  // (HIP: agent scope) buffer_wbl2 + waits
-    uint32_t prev = 0;
-    if (lane == 0) prev = atomicAdd(&p.q_scored[rfl(sl.q)], 1u);
-    if (rfl(prev) == 0xFFFFFFF0u) __atomic_thread_fence(__ATOMIC_ACQUIRE);  // (the merging wave would acquire here)
-  }
-#endif
   if (p.q_scored && lane == 0 && n_scored) atomicAdd(&p.q_scored[rfl(sl.q)], n_scored);
 #ifdef SLG_STAMPS
   const unsigned long long st_extra = st_ins | (st_queued << 32);

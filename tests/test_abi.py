@@ -169,6 +169,22 @@ def test_tuning_defaults_come_from_the_environment_once(lib, monkeypatch):
     assert b"struct_size" in lib.slg_last_error()
 
 
+@pytest.mark.parametrize("form,code", [(2, "ERR_UNSUPPORTED"), (3, "ERR_UNSUPPORTED"),
+                                       (0, "ERR_INVALID"), (5, "ERR_INVALID")])
+def test_uniform_kernel_other_than_4_is_rejected(lib, form, code):
+    """4 (the blocked form) is the only few-term kernel: 2 and 3, the removed earlier forms, are
+    unsupported; anything else (0: a zero-initialised struct) is invalid.  Checked before any segment
+    or device call."""
+    from searchlite_amd import _native as N
+    keep = []
+    arr = (N.SegmentDesc * 1)(_seg_desc(4, [0, 1], [1], [1], keep))
+    t = N.default_tuning()
+    t.uniform_kernel = form
+    assert lib.slg_index_create_tuned(arr, 1, 0, C.addressof(t)) is None
+    assert b"uniform_kernel" in lib.slg_last_error()
+    assert lib.slg_last_error_code() == getattr(N, code)
+
+
 def test_segfile_library_exports_its_header():
     """include/searchlite_segfile.h (host-only decoder of searchlite's segment files)."""
     from searchlite_amd import index_files as IF

@@ -76,8 +76,7 @@ def test_five_terms_top100_pruned_kernel_small(gpu, oracle, tuning):
     classification because block skipping has nothing to gain), the classified many-term kernel
     score_multi_kernel<2, 1> (pruning: 1), the unclassified one (uniform_max_terms: 4 -> <2, 0> is
     not reached: classification stays on; pruning: 0 with 8 lists -> few-term kernel); inline_cuts: 0 =
-    cut points from partition_rounds_kernel instead of the scoring waves' own.  (The slot forms of the
-    few-term kernel are no longer in the product library: -DSLG_LEGACY_KERNELS, tools/ab_uniform.sh.)"""
+    cut points from partition_rounds_kernel instead of the scoring waves' own."""
     from searchlite_amd import corpus
     seg = corpus.zipf_segment(300_000, 1 << 16, seed=43)
     offs, terms, w = corpus.zipf_queries(192, 5, rank_lo=8, rank_hi=4096, seed=7, vocab=1 << 16)

@@ -220,8 +220,7 @@ def test_kernel_choice_follows_what_block_skipping_can_save(lib):
     """5-term Wand batches are MaxScore-classified, and keep the classification (many-term kernel,
     block skipping) only where skipping is expected to leave >= 15 % of the postings unread: lists of
     similar density (config 3's shape) go to the few-term kernel unclassified; a stop word next to
-    rare terms stays classified.  pruning = 1 / 0 force either way; the slot form of the few-term
-    kernel plans smaller rounds than the blocked form."""
+    rare terms stays classified.  pruning = 1 / 0 force either way."""
     from searchlite_amd import corpus
     seg = corpus.zipf_segment(200_000, 1 << 14, seed=5)
     ch = champions_of(seg)
@@ -231,16 +230,11 @@ def test_kernel_choice_follows_what_block_skipping_can_save(lib):
     sqs, _ = check_structure(p, 101)
     assert p.facts.uniform and not p.facts.pruned and p.facts.n_postings_nonessential == 0
     assert all(int(sq["ess_mask"]) == 31 and int(sq["skip_mask"]) == 0 for sq in sqs)
-    rounds_blocked = p.facts.n_rounds
     p.close()
     forced = Planned(lib, [seg], offs, terms, w, 101, strategy=1, champs=[ch], tuning=default_tuning(pruning=1))
     check_structure(forced, 101)
     assert forced.facts.pruned and forced.facts.multi and forced.facts.n_postings_nonessential > 0
     forced.close()
-    slots = Planned(lib, [seg], offs, terms, w, 101, strategy=1, champs=[ch], tuning=default_tuning(uniform_kernel=3))
-    check_structure(slots, 101)
-    assert slots.facts.uniform and slots.facts.n_rounds > 1.2 * rounds_blocked
-    slots.close()
     # one stop-word-like term (ranks 1..4) among four rare ones
     rng = np.random.default_rng(4)
     t2 = np.stack([np.concatenate([rng.integers(0, 4, 1), rng.choice(np.arange(3000, 12000), 4, replace=False)])

@@ -200,11 +200,9 @@ typedef struct {
                                     of one or more terms) and <= uniform_max_terms lists per sub-query run on the
                                     few-term kernel's plan instantiation; 0: on the many-term kernel, as two-level
                                     plans do (A/B timing) */
-  uint32_t score_waves_per_simd; /* SLG_SCORE_WAVES (0): 0 = the few-term kernel launches one wave per slice, longest
-                                    slices first (the hardware dispatcher hands out the work); n > 0 = persistent
-                                    waves: n_CU x 4 x min(n, what registers and LDS allow) waves that pull slices
-                                    from 64 work queues.  Measured slower on MI355X: kept for
-                                    A/B timing */
+  uint32_t score_waves_per_simd; /* reserved, must be 0: the few-term kernel launches one wave per slice.  Persistent
+                                    scoring waves, which a non-zero value once selected, were removed (slower on
+                                    MI355X): SLG_ERR_UNSUPPORTED */
 } slg_tuning;
 void slg_tuning_default(slg_tuning *out);
 slg_index *slg_index_create_tuned(const slg_segment_desc *segs, uint32_t n_segs, int device,

@@ -358,7 +358,6 @@ struct slg_index {
   slg_tuning tune{};
   std::vector<slg_batch *> live;  // batches prepared on this index and not yet destroyed (under mu)
   int device = 0;
-  uint32_t n_cu = 256;  // compute units of the device (persistent launches fill its wave slots)
   hipStream_t own_stream = nullptr;
   // descriptor uploads of slg_batch_prepare*: non-blocking streams picked by caller thread.  A plain
   // hipMemcpy runs on the legacy default stream and waits for whatever the application has queued
@@ -411,7 +410,6 @@ struct slg_batch {
   const slg::QueryRef *d_queries = nullptr;
   const uint32_t *d_bnd_coarse = nullptr;
   DevBuf d_bounds, d_rdoc, d_slice_tk, d_slice_doc, d_q_scored, d_slice_desc;
-  DevBuf d_work_ctr;       // work counter of the persistent scoring waves (zeroed by partition_rounds_kernel)
   DevBuf d_q_filter;       // [nq] 0 = none, f + 1 (select_topk_kernel); empty when unfiltered
   bool cand_mode = false;  // uniform kernel, k > 256: candidates + select_topk_kernel
   DevBuf d_cand, d_slice_cbeg, d_slice_ccnt;
@@ -874,7 +872,7 @@ void slg_tuning_default(slg_tuning *t) {
   t->inline_cuts = env_i32("SLG_INLINE_CUTS", -1);
   t->updatable = env_i32("SLG_NOT_UPDATABLE", 0) == 0;
   t->uniform_plans = env_i32("SLG_NO_UNIFORM_PLANS", 0) == 0;
-  t->score_waves_per_simd = env_u32("SLG_SCORE_WAVES", 0);
+  t->score_waves_per_simd = 0;  // (reserved: persistent scoring waves were removed)
 }
 
 slg_index *slg_index_create(const slg_segment_desc *segs, uint32_t n_segs, int device) {
@@ -897,6 +895,8 @@ slg_index *slg_index_create_tuned(const slg_segment_desc *segs, uint32_t n_segs,
     if (tune.uniform_kernel == 2 || tune.uniform_kernel == 3)
       throw SlgError(SLG_ERR_UNSUPPORTED, "slg_tuning.uniform_kernel 2 / 3: those forms of the few-term kernel were removed");
     SLG_REQUIRE(tune.uniform_kernel == 4, "slg_tuning.uniform_kernel must be 4");
+    if (tune.score_waves_per_simd != 0)
+      throw SlgError(SLG_ERR_UNSUPPORTED, "slg_tuning.score_waves_per_simd must be 0: persistent scoring waves were removed");
     tune.uniform_max_terms = std::min<uint32_t>(tune.uniform_max_terms, slg::kU4MaxLists);
     tune.max_rounds_per_slice = std::min<uint32_t>(tune.max_rounds_per_slice, slg::kMaxRoundsPerSlice);
     tune.slices_per_subquery = std::max<uint32_t>(1, tune.slices_per_subquery);
@@ -914,7 +914,6 @@ slg_index *slg_index_create_tuned(const slg_segment_desc *segs, uint32_t n_segs,
     if (std::strncmp(prop.gcnArchName, "gfx950", 6) != 0 && !tune.allow_any_arch)
       throw SlgError(SLG_ERR_DEVICE,
                      std::string("device is ") + prop.gcnArchName + ", this library targets gfx950");
-    ix->n_cu = prop.multiProcessorCount > 0 ? (uint32_t)prop.multiProcessorCount : 256u;
     SLG_HIP(hipStreamCreateWithFlags(&ix->own_stream, hipStreamNonBlocking));
     ix->stream = ix->own_stream;
     for (auto &us : ix->upload_streams) SLG_HIP(hipStreamCreateWithFlags(&us, hipStreamNonBlocking));
@@ -952,7 +951,7 @@ namespace {
 // to the runtime (the index and its pool are going away)
 void release_batch_buffers(slg_batch *b, bool to_pool) {
   DevBuf *bufs[] = {&b->d_desc, &b->d_bounds, &b->d_rdoc, &b->d_slice_desc, &b->d_slice_tk, &b->d_slice_doc,
-                    &b->d_q_scored, &b->d_work_ctr, &b->d_q_filter, &b->d_cand, &b->d_slice_cbeg, &b->d_slice_ccnt,
+                    &b->d_q_scored, &b->d_q_filter, &b->d_cand, &b->d_slice_cbeg, &b->d_slice_ccnt,
                     &b->d_out, &b->d_stamps, &b->d_blk_skip, &b->d_gather, &b->d_merged};
   for (DevBuf *d : bufs) {
     if (!to_pool) d->pool = nullptr;
@@ -1517,7 +1516,6 @@ slg_batch *prepare_impl(slg_index *ix, uint32_t nq, const uint32_t *q_offsets, c
       b->d_slice_doc.alloc_pooled(&ix->pool, (size_t)b->n_slices * k * 4);
     }
     b->d_q_scored.alloc_pooled(&ix->pool, (size_t)nq * 4);
-    b->d_work_ctr.alloc_pooled(&ix->pool, (size_t)slg::kWorkQueues * slg::kWorkCtrStride * 4);
     // (from the pool like every per-batch buffer: a raw hipMalloc / hipFree per batch synchronises
     // the device and cost config 4's two-in-flight pipeline 60 %)
     if (b->pruned && !b->uniform && ix->tune.block_max) b->d_blk_skip.alloc_pooled(&ix->pool, ((size_t)nq + 1) * 8);
@@ -1611,18 +1609,8 @@ int slg_batch_run(slg_batch *b) {
       pp.n_boundaries = inline_cuts ? 0u : b->n_boundaries;
       pp.n_slices = b->n_slices;
       pp.tpb_shift = b->max_terms <= 4 ? 2u : 3u;
-      // few-term kernel: one wave per slice, or (slg_tuning.score_waves_per_simd) persistent waves that
-      // pull slices from the batch's work queues (slg_score_uni4.hpp)
       const int score_kind =
           b->uniform ? uniform_kind(b->max_terms, b->plan_batch) : (b->pruned ? 3 : 2);
-      uint32_t n_waves = b->n_slices;
-      const bool persistent = (score_kind == 6 || score_kind == 7) && ix->tune.score_waves_per_simd != 0;
-      if (persistent)
-        n_waves = slg::u4_launch_blocks(kregs_for(b->score_k), (score_kind & 1) ? 8 : 4, score_kind >= 8, b->n_slices, ix->n_cu,
-                                        ix->tune.score_waves_per_simd) *
-                  (uint32_t)slg::kU4WavesPerBlock;
-      pp.work_ctr = persistent ? b->d_work_ctr.as<uint32_t>() : nullptr;
-      pp.n_waves = n_waves;
       const uint64_t pthreads = std::max<uint64_t>(
           std::max<uint64_t>((uint64_t)pp.n_boundaries << pp.tpb_shift, (uint64_t)b->nq + 1), b->n_slices);
       hipLaunchKernelGGL(slg::partition_rounds_kernel, dim3((uint32_t)((pthreads + 255) / 256)),
@@ -1654,8 +1642,6 @@ int slg_batch_run(slg_batch *b) {
       sp.skip_counts = pp.skip_counts;
       sp.stamps = nullptr;
       sp.error_flag = ix->d_error_flag.as<uint32_t>();
-      sp.work_ctr = pp.work_ctr;
-      sp.n_waves = n_waves;
 #ifdef SLG_STAMPS
       b->d_stamps.alloc((size_t)b->n_slices * 96);
       sp.stamps = b->d_stamps.as<unsigned long long>();

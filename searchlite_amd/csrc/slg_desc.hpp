@@ -1,6 +1,6 @@
 // slg_desc.hpp — the descriptors a query batch is planned into (host) and consumed from (device),
 // and the constants both sides share.  Plain C++: included by the HIP translation units through
-// slg_kernels.hpp and by the host-only planner (slg_plan.cpp, built with g++ for the CPU unit tests).
+// slg_wave.hpp and by the host-only planner (slg_plan.cpp, built with g++ for the CPU unit tests).
 #pragma once
 
 #include <stdint.h>
@@ -132,18 +132,6 @@ struct QueryRef {
   uint32_t slice_begin, slice_end;  // all slices of all sub-queries of this query
 };
 
-
-// ---- work queues of the persistent scoring waves (slg_score_uni4.hpp) ---------------------------
-// One returning atomic per slice on ONE counter does not scale: MI355X hands out a ticket of a single
-// address every ~11-16 ns whatever the number of waves asking (tools/micro/atomic_queue.hip: 6144 waves,
-// 195 us for 12 288 tickets; 8 counters 1.8 ns per ticket, 64 counters 0.43 ns) — config 2's 13.4K
-// slices would take longer to hand out than to score.  So the launch order is dealt round-robin over
-// kWorkQueues queues (position p: queue p % kWorkQueues, index p / kWorkQueues — every queue gets the
-// same mix of long and short slices), each with its own counter on its own 256-byte line; wave w pulls
-// from queue w % kWorkQueues and, when that has run dry, tries kWorkSteals other queues before it exits.
-constexpr uint32_t kWorkQueues = 64;
-constexpr uint32_t kWorkCtrStride = 64;  // words between two counters (256 bytes)
-constexpr uint32_t kWorkSteals = 2;      // other queues a wave tries when its own has run dry
 
 // ---- planning constants (the kernels that consume them: slg_score*.hpp) ------------------------
 constexpr int kMaxRoundsPerSlice = 16;  // and (rounds+1)*T <= 64: cut points live in one VGPR

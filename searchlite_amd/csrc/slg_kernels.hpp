@@ -6,287 +6,20 @@
 //   score_rounds    : (slg_score.hpp) query/wand.rs:459-566 + push_top_k :905-916
 //   merge_topk      : query/wand.rs:918-926 + api/reader.rs:2776-2778 (query/sort.rs:80-93)
 //
-// This header: shared descriptors, wave-level helpers, the register top-k, the staging
-// kernel and the merge kernels.  The hot scoring kernel lives in slg_score.hpp.
+// This header: the kernels the host launches around the scoring kernels — staging, the round
+// partition, the merges, doc filters and the large-k / field-sorted selects.  Only slg_api.hip
+// includes it.  Wave-level helpers and the top-k structures: slg_wave.hpp; the scoring kernels:
+// slg_score*.hpp.
 #pragma once
 
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #include "slg_desc.hpp"
+#include "slg_score.hpp"
+#include "slg_wave.hpp"
 
 namespace slg {
-
-// ---- small helpers --------------------------------------------------------------------
-__device__ __forceinline__ int32_t total_key(float x) {
-  // f32::total_cmp key: sign-magnitude bits -> two's complement order
-  int32_t b = __float_as_int(x);
-  return b ^ (int32_t)(((uint32_t)(b >> 31)) >> 1);
-}
-__device__ __forceinline__ float key_to_float(int32_t k) {
-  return __int_as_float(k ^ (int32_t)(((uint32_t)(k >> 31)) >> 1));
-}
-__device__ __forceinline__ uint32_t rfl(uint32_t v) {
-  return (uint32_t)__builtin_amdgcn_readfirstlane((int)v);
-}
-__device__ __forceinline__ uint32_t rl(uint32_t v, uint32_t lane) {
-  return (uint32_t)__builtin_amdgcn_readlane((int)v, (int)lane);
-}
-__device__ __forceinline__ uint32_t wave_sum(uint32_t v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-__device__ __forceinline__ uint32_t wave_min(uint32_t v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    uint32_t u = __shfl_xor(v, o, 64);
-    v = u < v ? u : v;
-  }
-  return v;
-}
-__device__ __forceinline__ uint32_t wave_excl_scan(uint32_t v, uint32_t lane) {
-  uint32_t x = v;
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) {
-    uint32_t u = __shfl_up(x, o, 64);
-    if (lane >= (uint32_t)o) x += u;
-  }
-  return x - v;
-}
-// lane l receives lane l-1's value (lane 0 keeps its own): one DPP move, no LDS traffic
-__device__ __forceinline__ int32_t wave_shr1(int32_t v) {
-  return __builtin_amdgcn_update_dpp(v, v, 0x138 /* wave_shr:1 */, 0xf, 0xf, false);
-}
-// compiler-only ordering point for wave-synchronous LDS traffic (hardware keeps a wave's
-// DS instructions in order; this stops the compiler from moving them across phases)
-__device__ __forceinline__ void wave_fence() { __atomic_signal_fence(__ATOMIC_SEQ_CST); }
-
-// (score key, seg, doc) ordering: larger tk first, then smaller seg, then smaller doc
-// (query/wand.rs:30-37, query/sort.rs:80-93)
-template <bool HAS_SEG>
-__device__ __forceinline__ bool better(int32_t tka, uint32_t sega, uint32_t doca, int32_t tkb,
-                                       uint32_t segb, uint32_t docb) {
-  if (tka != tkb) return tka > tkb;
-  if (HAS_SEG && sega != segb) return sega < segb;
-  return doca < docb;
-}
-
-// ---- wave-wide sorted top-k held in registers -------------------------------------------
-// Position p = lane*KREGS + r (best first).  Capacity 64*KREGS >= k.  All methods are
-// wave-uniform in control flow; candidates are passed as uniform (SGPR) values.
-template <int KREGS, bool HAS_SEG>
-struct WaveTopK {
-  int32_t tk[KREGS];
-  uint32_t doc[KREGS];
-  uint32_t seg[HAS_SEG ? KREGS : 1];
-  int32_t th_tk;  // threshold = entry at position k-1 (uniform), never below the floor
-  uint32_t th_seg, th_doc;
-  uint32_t count;  // real entries held, capped at k (uniform)
-  int32_t floor_tk;  // exact lower bound of the final k-th score known up front (or sentinel)
-
-  __device__ __forceinline__ void init() {
-#pragma unroll
-    for (int r = 0; r < KREGS; r++) {
-      tk[r] = kSentinelTk;
-      doc[r] = 0xFFFFFFFFu;
-      if (HAS_SEG) seg[r] = 0xFFFFFFFFu;
-    }
-    if (!HAS_SEG) seg[0] = 0;
-    th_tk = kSentinelTk;
-    th_seg = 0xFFFFFFFFu;
-    th_doc = 0xFFFFFFFFu;
-    count = 0;
-    floor_tk = kSentinelTk;
-  }
-  // At least k docs are known to score >= f: nothing below f can reach the final top-k.
-  // Candidates equal to f still pass (ties are broken by doc id later).
-  __device__ __forceinline__ void set_floor(float f) {
-    floor_tk = total_key(f);
-    th_tk = floor_tk;
-    th_seg = 0xFFFFFFFFu;
-    th_doc = 0xFFFFFFFFu;
-  }
-  __device__ __forceinline__ bool passes(int32_t ctk, uint32_t cseg, uint32_t cdoc) const {
-    return better<HAS_SEG>(ctk, cseg, cdoc, th_tk, th_seg, th_doc);
-  }
-  // insert a uniform candidate known to pass the threshold
-  __device__ __forceinline__ void insert(int32_t ctk, uint32_t cseg, uint32_t cdoc, uint32_t k,
-                                         uint32_t lane) {
-    uint32_t cnt = 0;
-#pragma unroll
-    for (int r = 0; r < KREGS; r++)
-      cnt += better<HAS_SEG>(tk[r], HAS_SEG ? seg[r] : 0u, doc[r], ctk, cseg, cdoc) ? 1u : 0u;
-    uint64_t full = __ballot(cnt == (uint32_t)KREGS);
-    uint32_t pos_lane = (uint32_t)__popcll(full);  // fully-better lanes form a prefix
-    uint32_t pos_r = pos_lane < 64 ? rl(cnt, pos_lane) : 0u;
-    // value arriving from the previous lane's last register
-    int32_t up_tk = wave_shr1(tk[KREGS - 1]);
-    uint32_t up_doc = (uint32_t)wave_shr1((int32_t)doc[KREGS - 1]);
-    uint32_t up_seg = HAS_SEG ? (uint32_t)wave_shr1((int32_t)seg[KREGS - 1]) : 0u;
-#pragma unroll
-    for (int r = KREGS - 1; r >= 0; r--) {
-      bool shift = lane > pos_lane || (lane == pos_lane && (uint32_t)r > pos_r);
-      bool here = lane == pos_lane && (uint32_t)r == pos_r;
-      int32_t s_tk = r == 0 ? up_tk : tk[r > 0 ? r - 1 : 0];
-      uint32_t s_doc = r == 0 ? up_doc : doc[r > 0 ? r - 1 : 0];
-      uint32_t s_seg = HAS_SEG ? (r == 0 ? up_seg : seg[r > 0 ? r - 1 : 0]) : 0u;
-      tk[r] = here ? ctk : (shift ? s_tk : tk[r]);
-      doc[r] = here ? cdoc : (shift ? s_doc : doc[r]);
-      if (HAS_SEG) seg[r] = here ? cseg : (shift ? s_seg : seg[r]);
-    }
-    if (count < k) count++;
-    // refresh threshold = entry at position k-1
-    uint32_t tl = (k - 1) / KREGS, tr = (k - 1) % KREGS;
-    int32_t v_tk = tk[0];
-    uint32_t v_doc = doc[0], v_seg = HAS_SEG ? seg[0] : 0u;
-#pragma unroll
-    for (int r = 1; r < KREGS; r++) {
-      bool sel = tr == (uint32_t)r;
-      v_tk = sel ? tk[r] : v_tk;
-      v_doc = sel ? doc[r] : v_doc;
-      if (HAS_SEG) v_seg = sel ? seg[r] : v_seg;
-    }
-    th_tk = (int32_t)rl((uint32_t)v_tk, tl);
-    th_doc = rl(v_doc, tl);
-    th_seg = HAS_SEG ? rl(v_seg, tl) : 0u;
-    if (th_tk < floor_tk) {  // fewer than k entries so far: the up-front bound still rules
-      th_tk = floor_tk;
-      th_doc = 0xFFFFFFFFu;
-      th_seg = 0xFFFFFFFFu;
-    }
-  }
-};
-
-// ---- buffered wave top-k (one segment) ------------------------------------------------------
-// push_top_k (query/wand.rs:905-916) without a per-candidate sorted insert: a candidate that
-// beats the current threshold is appended to a per-wave LDS buffer (one ds_write for all passing
-// lanes of a slot); only when the buffer is full, and once at the end, are the entries ranked
-// (every lane counts the entries better than its own) and the k best kept.  The threshold is
-// the k-th best after a ranking, the up-front floor before, so it is always a valid lower bound
-// of the final k-th score: the surviving set is exactly the top-k under (score desc, doc asc).
-//
-// Entries are single 64-bit keys: (order-preserving score bits << 32) | ~doc, so "better" is
-// one unsigned 64-bit compare.
-__device__ __forceinline__ uint32_t ordered_score(float x) {
-  const int32_t b = __float_as_int(x);  // == total_key(x) ^ 0x80000000
-  return (uint32_t)b ^ ((uint32_t)(b >> 31) | 0x80000000u);
-}
-__device__ __forceinline__ uint64_t cand_key(float score, uint32_t doc) {
-  return ((uint64_t)ordered_score(score) << 32) | (uint32_t)~doc;
-}
-
-template <int KREGS>
-struct BufTopK {
-  static constexpr uint32_t kEntries = 64u * (KREGS + 1);  // >= k + 64 for k <= 64 * KREGS: after a
-                                                          // ranking a whole slot of candidates fits
-  static constexpr int E = KREGS + 1;                      // entries per lane while ranking
-  uint64_t *buf;   // LDS [kEntries]
-  uint32_t count;  // uniform: entries held
-  uint64_t th;     // uniform: a candidate passes iff key > th
-
-  __device__ __forceinline__ void init(uint64_t *lds) {
-    buf = lds;
-    count = 0;
-    th = 0;  // any real doc passes (~doc > 0)
-  }
-  // At least k docs score >= f.  Candidates equal to f still pass (doc-id tie break later).
-  __device__ __forceinline__ void set_floor(float f) {
-    th = ((uint64_t)ordered_score(f) << 32) - 1ull;
-  }
-  __device__ __forceinline__ bool passes(uint64_t key) const { return key > th; }
-
-  // drop deleted docs (accept(), query/wand.rs:905), rank the rest, keep the k best sorted at
-  // buf[0..count), refresh the threshold.  Deleted docs are filtered here, before anything is
-  // ranked, so they never influence the threshold.
-  __device__ __forceinline__ void compact(uint32_t k, uint32_t lane, const uint32_t *deleted) {
-    uint64_t e[E];
-    uint32_t rank[E];
-#pragma unroll
-    for (int i = 0; i < E; i++) {
-      const uint32_t idx = lane + 64u * i;
-      e[i] = idx < count ? buf[idx] : 0ull;
-      rank[i] = 0;
-    }
-    if (deleted) {
-#pragma unroll
-      for (int i = 0; i < E; i++) {
-        const uint32_t doc = ~(uint32_t)e[i];
-        if (e[i] != 0ull && ((deleted[doc >> 5] >> (doc & 31)) & 1u)) e[i] = 0ull;
-      }
-    }
-    uint32_t nvalid = 0;
-#pragma unroll
-    for (int i = 0; i < E; i++) {
-      if (64u * i < count) {  // uniform
-        nvalid += (uint32_t)__popcll(__ballot(e[i] != 0ull));
-        const uint32_t n_i = count - 64u * i < 64u ? count - 64u * i : 64u;
-        for (uint32_t l = 0; l < n_i; l++) {
-          const uint64_t c = ((uint64_t)rl((uint32_t)(e[i] >> 32), l) << 32) | rl((uint32_t)e[i], l);
-#pragma unroll
-          for (int j = 0; j < E; j++) rank[j] += c > e[j] ? 1u : 0u;
-        }
-      }
-    }
-    wave_fence();
-#pragma unroll
-    for (int i = 0; i < E; i++)
-      if (e[i] != 0ull && rank[i] < k) buf[rank[i]] = e[i];
-    wave_fence();
-    count = nvalid < k ? nvalid : k;
-    if (nvalid >= k) {
-      const uint64_t kth = buf[k - 1];
-      const uint64_t u = ((uint64_t)rfl((uint32_t)(kth >> 32)) << 32) | rfl((uint32_t)kth);
-      th = u > th ? u : th;
-    }
-  }
-
-  // split-key forms (the hot path keeps 32-bit halves: hi = ordered score, lo = ~doc)
-  __device__ __forceinline__ bool passes(uint32_t hi, uint32_t lo) const {
-    const uint32_t th_hi = (uint32_t)(th >> 32), th_lo = (uint32_t)th;
-    return hi > th_hi || (hi == th_hi && lo > th_lo);
-  }
-  // append the candidates of the lanes with `pass` set (pass implies key > th); the caller
-  // has checked that they fit (count + popcount <= kEntries)
-  __device__ __forceinline__ void append(bool pass, uint32_t hi, uint32_t lo, uint32_t lane) {
-    const uint64_t m = __ballot(pass);
-    if (m == 0ull) return;
-    const uint32_t dest =
-        count + __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
-    uint32_t *b32 = reinterpret_cast<uint32_t *>(buf);
-    if (pass) {
-      b32[2 * dest] = lo;
-      b32[2 * dest + 1] = hi;
-    }
-    count += (uint32_t)__popcll(m);
-  }
-  // same, ranking first when the buffer would overflow (<= 64 candidates always fit after it)
-  __device__ __forceinline__ void append_checked(bool pass, uint32_t hi, uint32_t lo, uint32_t k,
-                                                 uint32_t lane, const uint32_t *deleted) {
-    if (count + (uint32_t)__popcll(__ballot(pass)) > kEntries) {
-      compact(k, lane, deleted);
-      pass = pass && passes(hi, lo);
-    }
-    append(pass, hi, lo, lane);
-  }
-
-  // final candidates of this wave: k entries (int32 total_key, doc), sentinel padded (best
-  // first when they were ranked; the merge does not rely on the order)
-  __device__ __forceinline__ void write_out(int32_t *otk, uint32_t *odoc, uint32_t k, uint32_t lane,
-                                            const uint32_t *deleted) {
-    if (count > k || (deleted && count)) compact(k, lane, deleted);
-    wave_fence();
-#pragma unroll
-    for (int r = 0; r < KREGS; r++) {
-      const uint32_t pos = lane + 64u * r;
-      if (pos < k) {
-        const uint64_t e = pos < count ? buf[pos] : 0ull;
-        otk[pos] = pos < count ? (int32_t)((uint32_t)(e >> 32) ^ 0x80000000u) : kSentinelTk;
-        odoc[pos] = ~(uint32_t)e;
-      }
-    }
-  }
-};
 
 // ---- staging: per-posting impact ---------------------------------------------------------
 // impact = bm25(tf, df, doc_len, avgdl, docs, k1, b) exactly as score_tf computes `base`
@@ -409,6 +142,121 @@ static __global__ void __launch_bounds__(256) stage_champions_kernel(ChampParams
     float *row = p.champ + (size_t)t * kChampions;
     row[lane] = v;
     if (lane < 4) row[kChampSorted + lane] = lane == 0 ? lo[0] : lane == 1 ? lo[1] : lane == 2 ? lo[2] : lo[3];
+  }
+}
+
+// ---- partition: exact per-list cut points of every round --------------------------------------
+struct RoundPartParams {
+  const RoundQuery *sq;
+  const TermRef *terms;
+  const SegDev *segs;
+  const uint32_t *bnd_coarse;  // [ceil(n_boundaries / 32)] sub-query of every 32nd boundary
+  uint32_t n_sq;
+  uint32_t *bounds;
+  uint32_t *rdoc;
+  uint32_t *q_scored;  // [nq] zeroed here (saves a memset node per batch)
+  unsigned long long *skip_counts;  // [1 + nq] zeroed here, or null
+  const uint32_t *slice_sq;     // [n_slices]
+  const uint32_t *slice_order;  // [n_slices] launch position -> slice
+  SliceDesc *slice_desc;        // [n_slices] out, by launch position
+  uint32_t nq;
+  uint32_t n_boundaries;
+  uint32_t n_slices;
+  uint32_t tpb_shift;  // log2(threads per boundary): 2 when no sub-query has more than 4 lists, else 3
+};
+
+// 4 or 8 threads per boundary: thread u handles lists u, u + threads, ...
+// (Measured on config 3, where the kernel takes 1.6 ms: it is bound by the HBM lines it fetches —
+// with a round's postings of a list inside one or two lines, the cut points of all rounds touch
+// every line of every list but the longest, at scattered-access efficiency.  Giving a thread 8
+// consecutive boundaries, each searched behind its predecessor, fetches the same lines and was
+// slower: 2.2 ms.)
+static __global__ void __launch_bounds__(256) partition_rounds_kernel(RoundPartParams p) {
+  const uint32_t gid = blockIdx.x * blockDim.x + threadIdx.x;
+  if (gid < p.nq) p.q_scored[gid] = 0;
+  if (gid <= p.nq && p.skip_counts) p.skip_counts[gid] = 0ull;
+  if (gid < p.n_slices) {  // the slice record of launch position gid
+    const uint32_t slice = p.slice_order[gid];
+    const RoundQuery s = p.sq[p.slice_sq[slice]];
+    const uint32_t r0 = (slice - s.slice_begin) * s.rounds_per_slice;
+    SliceDesc d;
+    d.slice = slice;
+    d.term_begin = s.term_begin;
+    d.bounds_off = s.bounds_begin + r0 * s.n_terms;
+    d.rdoc_off = s.rdoc_begin + r0;
+    d.n_terms = s.n_terms;
+    d.n_rounds = s.n_rounds - r0 < s.rounds_per_slice ? s.n_rounds - r0 : s.rounds_per_slice;
+    d.seg = s.seg;
+    d.filter = s.filter;
+    d.q = s.q;
+    d.theta0 = s.theta0;
+    d.cand_lo = s.cand_lo;
+    d.cand_hi = s.cand_hi;
+    d.first_round = r0;
+    d.sq_rounds = s.n_rounds;
+    d.longest = s.longest;
+    {
+      const TermRef L = p.terms[s.term_begin + s.longest];
+      d.l_df = L.df;
+      d.l_off = L.off;
+    }
+    d.plan = s.plan;
+    d.tie = s.tie;
+    d.max_init = s.max_init;
+    d.n_leaves = s.n_leaves;
+    p.slice_desc[gid] = d;
+  }
+  const uint32_t tpb = 1u << p.tpb_shift;
+  const uint32_t b = gid >> p.tpb_shift, u = gid & (tpb - 1u);
+  if (b >= p.n_boundaries) return;
+  // the sub-query that owns boundary b: the last one whose first boundary is <= b (bnd_begin
+  // ascends).  The host uploads it for every 32nd boundary (a per-boundary table was most of the
+  // descriptor upload); from there a short walk (sub-queries have ~85 boundaries on config 2)
+  uint32_t sqi = p.bnd_coarse[b >> 5];
+  while (sqi + 1 < p.n_sq && p.sq[sqi + 1].bnd_begin <= b) sqi++;
+  const RoundQuery s = p.sq[sqi];
+  const uint32_t j = b - s.bnd_begin;
+  const uint32_t *docs = p.segs[s.seg].docs;
+  const TermRef L = p.terms[s.term_begin + s.longest];
+  const uint32_t stride = (L.df + s.n_rounds - 1) / s.n_rounds;
+  const uint64_t posL = (uint64_t)j * stride;
+  const bool first = j == 0, last = j >= s.n_rounds || posL >= L.df;
+  uint32_t target = 0;
+  if (!first && !last) target = docs[L.off + posL];
+  for (uint32_t t = u; t < s.n_terms; t += tpb) {
+    const TermRef me = p.terms[s.term_begin + t];
+    uint32_t out;
+    if (first) {
+      out = 0;
+    } else if (last) {
+      out = me.df;
+    } else if (t == s.longest) {
+      out = (uint32_t)posL;
+    } else {
+      out = lower_bound_guess(docs + me.off, me.df, target, p.segs[s.seg].n_docs);
+    }
+    p.bounds[s.bounds_begin + j * s.n_terms + t] = out;
+  }
+  if (u == 0) {
+    uint32_t rd;
+    if (first) {  // smallest first doc over the lists
+      rd = 0xFFFFFFFFu;
+      for (uint32_t t = 0; t < s.n_terms; t++) {
+        const TermRef me = p.terms[s.term_begin + t];
+        const uint32_t d0 = docs[me.off];
+        rd = d0 < rd ? d0 : rd;
+      }
+    } else if (last) {  // one past the largest last doc
+      rd = 0;
+      for (uint32_t t = 0; t < s.n_terms; t++) {
+        const TermRef me = p.terms[s.term_begin + t];
+        const uint32_t d1 = docs[me.off + me.df - 1] + 1u;
+        rd = d1 > rd ? d1 : rd;
+      }
+    } else {
+      rd = target;
+    }
+    p.rdoc[s.rdoc_begin + j] = rd;
   }
 }
 

@@ -6,7 +6,7 @@
 //
 // The path is an HBM row gather (one D-float row per candidate, 0.5 flop/byte): each wave
 // streams whole rows with 16-byte lane loads, reduces in-register, and a wave-wide sorted
-// top-k (slg_kernels.hpp) picks the k_out best blended scores.  One clause: rerank_kernel
+// top-k (slg_wave.hpp) picks the k_out best blended scores.  One clause: rerank_kernel
 // (VALU; the contraction is a GEMV).  Several clauses sharing a candidate set:
 // rerank_multi_kernel, whose [candidates x clauses] products run on v_mfma_f32_16x16x4_f32.
 #pragma once
@@ -14,7 +14,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include "slg_kernels.hpp"
+#include "slg_wave.hpp"
 
 namespace slg {
 

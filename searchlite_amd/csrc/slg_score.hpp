@@ -1,5 +1,6 @@
-// slg_score.hpp — shared definitions of the round-scoring kernels: the planning kernel
-// partition_rounds_kernel, RoundScoreParams, wave scans, in-kernel stamps (diagnostic builds).
+// slg_score.hpp — shared definitions of the round-scoring kernels: RoundScoreParams, the cut-point
+// searches (also used by partition_rounds_kernel, slg_kernels.hpp), wave scans, in-kernel stamps
+// (diagnostic builds).
 // The scoring kernels themselves: slg_score_uni4.hpp (<= 8 lists), slg_score_multi.hpp (9..32
 // lists, score plans beyond the few-term kernel's, MaxScore / block-max pruning).
 //
@@ -17,35 +18,12 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include "slg_kernels.hpp"
+#include "slg_wave.hpp"
 
 namespace slg {
 
 // (planning constants: slg_desc.hpp)
 // per-wave LDS: bitmap words, exclusive prefix popcounts, accumulators
-
-// ---- partition: exact per-list cut points of every round --------------------------------------
-struct RoundPartParams {
-  const RoundQuery *sq;
-  const TermRef *terms;
-  const SegDev *segs;
-  const uint32_t *bnd_coarse;  // [ceil(n_boundaries / 32)] sub-query of every 32nd boundary
-  uint32_t n_sq;
-  uint32_t *bounds;
-  uint32_t *rdoc;
-  uint32_t *q_scored;  // [nq] zeroed here (saves a memset node per batch)
-  unsigned long long *skip_counts;  // [1 + nq] zeroed here, or null
-  const uint32_t *slice_sq;     // [n_slices]
-  const uint32_t *slice_order;  // [n_slices] launch position -> slice
-  SliceDesc *slice_desc;        // [n_slices] out, by launch position
-  uint32_t nq;
-  uint32_t n_boundaries;
-  uint32_t n_slices;
-  uint32_t tpb_shift;  // log2(threads per boundary): 2 when no sub-query has more than 4 lists, else 3
-  // work counters of the persistent scoring waves (slg_desc.hpp: kWorkQueues), zeroed here
-  uint32_t *work_ctr;
-  uint32_t n_waves;
-};
 
 // first index of d[0, df) with d[idx] >= target, looked for in the 16 NP postings from `a` on: NP + 1
 // pivots 16 postings apart (independent loads, one latency) bracket it to 16 postings, which are then
@@ -104,102 +82,6 @@ __device__ __forceinline__ uint32_t lower_bound_guess(const DocPtr d, uint32_t d
   return lo;
 }
 
-// 4 or 8 threads per boundary: thread u handles lists u, u + threads, ...
-// (Measured on config 3, where the kernel takes 1.6 ms: it is bound by the HBM lines it fetches —
-// with a round's postings of a list inside one or two lines, the cut points of all rounds touch
-// every line of every list but the longest, at scattered-access efficiency.  Giving a thread 8
-// consecutive boundaries, each searched behind its predecessor, fetches the same lines and was
-// slower: 2.2 ms.)
-static __global__ void __launch_bounds__(256) partition_rounds_kernel(RoundPartParams p) {
-  const uint32_t gid = blockIdx.x * blockDim.x + threadIdx.x;
-  if (gid < p.nq) p.q_scored[gid] = 0;
-  if (gid < kWorkQueues && p.work_ctr) p.work_ctr[gid * kWorkCtrStride] = 0u;
-  if (gid <= p.nq && p.skip_counts) p.skip_counts[gid] = 0ull;
-  if (gid < p.n_slices) {  // the slice record of launch position gid
-    const uint32_t slice = p.slice_order[gid];
-    const RoundQuery s = p.sq[p.slice_sq[slice]];
-    const uint32_t r0 = (slice - s.slice_begin) * s.rounds_per_slice;
-    SliceDesc d;
-    d.slice = slice;
-    d.term_begin = s.term_begin;
-    d.bounds_off = s.bounds_begin + r0 * s.n_terms;
-    d.rdoc_off = s.rdoc_begin + r0;
-    d.n_terms = s.n_terms;
-    d.n_rounds = s.n_rounds - r0 < s.rounds_per_slice ? s.n_rounds - r0 : s.rounds_per_slice;
-    d.seg = s.seg;
-    d.filter = s.filter;
-    d.q = s.q;
-    d.theta0 = s.theta0;
-    d.cand_lo = s.cand_lo;
-    d.cand_hi = s.cand_hi;
-    d.first_round = r0;
-    d.sq_rounds = s.n_rounds;
-    d.longest = s.longest;
-    {
-      const TermRef L = p.terms[s.term_begin + s.longest];
-      d.l_df = L.df;
-      d.l_off = L.off;
-    }
-    d.plan = s.plan;
-    d.tie = s.tie;
-    d.max_init = s.max_init;
-    d.n_leaves = s.n_leaves;
-    p.slice_desc[gid] = d;
-  }
-  const uint32_t tpb = 1u << p.tpb_shift;
-  const uint32_t b = gid >> p.tpb_shift, u = gid & (tpb - 1u);
-  if (b >= p.n_boundaries) return;
-  // the sub-query that owns boundary b: the last one whose first boundary is <= b (bnd_begin
-  // ascends).  The host uploads it for every 32nd boundary (a per-boundary table was most of the
-  // descriptor upload); from there a short walk (sub-queries have ~85 boundaries on config 2)
-  uint32_t sqi = p.bnd_coarse[b >> 5];
-  while (sqi + 1 < p.n_sq && p.sq[sqi + 1].bnd_begin <= b) sqi++;
-  const RoundQuery s = p.sq[sqi];
-  const uint32_t j = b - s.bnd_begin;
-  const uint32_t *docs = p.segs[s.seg].docs;
-  const TermRef L = p.terms[s.term_begin + s.longest];
-  const uint32_t stride = (L.df + s.n_rounds - 1) / s.n_rounds;
-  const uint64_t posL = (uint64_t)j * stride;
-  const bool first = j == 0, last = j >= s.n_rounds || posL >= L.df;
-  uint32_t target = 0;
-  if (!first && !last) target = docs[L.off + posL];
-  for (uint32_t t = u; t < s.n_terms; t += tpb) {
-    const TermRef me = p.terms[s.term_begin + t];
-    uint32_t out;
-    if (first) {
-      out = 0;
-    } else if (last) {
-      out = me.df;
-    } else if (t == s.longest) {
-      out = (uint32_t)posL;
-    } else {
-      out = lower_bound_guess(docs + me.off, me.df, target, p.segs[s.seg].n_docs);
-    }
-    p.bounds[s.bounds_begin + j * s.n_terms + t] = out;
-  }
-  if (u == 0) {
-    uint32_t rd;
-    if (first) {  // smallest first doc over the lists
-      rd = 0xFFFFFFFFu;
-      for (uint32_t t = 0; t < s.n_terms; t++) {
-        const TermRef me = p.terms[s.term_begin + t];
-        const uint32_t d0 = docs[me.off];
-        rd = d0 < rd ? d0 : rd;
-      }
-    } else if (last) {  // one past the largest last doc
-      rd = 0;
-      for (uint32_t t = 0; t < s.n_terms; t++) {
-        const TermRef me = p.terms[s.term_begin + t];
-        const uint32_t d1 = docs[me.off + me.df - 1] + 1u;
-        rd = d1 > rd ? d1 : rd;
-      }
-    } else {
-      rd = target;
-    }
-    p.rdoc[s.rdoc_begin + j] = rd;
-  }
-}
-
 // ---- scoring -----------------------------------------------------------------------------------
 struct RoundScoreParams {
   const RoundQuery *sq;
@@ -231,8 +113,6 @@ struct RoundScoreParams {
   unsigned long long *skip_counts;
   unsigned long long *stamps;  // [n_slices * 8] (SLG_STAMPS builds only)
   uint32_t *error_flag;        // set (non-zero) by a wave that gave up on a round: slg_batch_fetch fails then
-  uint32_t *work_ctr;          // persistent waves: kWorkQueues counters, kWorkCtrStride words apart
-  uint32_t n_waves;            // waves launched (few-term kernel: min(n_slices, wave slots of the device))
 };
 
 // inclusive wave scan (sum) with DPP row shifts + row broadcasts (gfx9 DPP controls)

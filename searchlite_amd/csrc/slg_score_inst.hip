@@ -17,37 +17,24 @@ template <int KREGS>
 void launch_score_kregs(const RoundScoreParams &sp, int kind, hipStream_t st);
 
 // Waves are independent in both kernels (no workgroup barrier anywhere), so workgroups are ONE
-// wave: a finished wave frees its wave slot and its LDS at once.
+// wave: a finished wave frees its wave slot and its LDS at once.  One wave per slice.
+
+// the few-term kernel (slg_score_uni4.hpp): <= 4 (ML 4) or 5..8 (ML 8) lists per sub-query
+// (static: every unit has its own, for its own SLG_INST_KREGS)
+template <int ML, bool PLAN>
+static void launch_uniform4(const RoundScoreParams &sp, hipStream_t st) {
+  hipLaunchKernelGGL((score_uniform4_kernel<SLG_INST_KREGS, ML, PLAN>), dim3(sp.n_slices), dim3(64),
+                     u4_wave_lds(SLG_INST_KREGS, ML, u4_filter_words(ML)), st, sp);
+}
+
 template <>
 void launch_score_kregs<SLG_INST_KREGS>(const RoundScoreParams &sp, int kind, hipStream_t st) {
-  if (kind == 6 || kind == 7) {  // <= 4 / 5..8 lists, blocked layout (slg_score_uni4.hpp)
-    // one wave per slice (sp.work_ctr == nullptr), or persistent waves: sp.n_waves / kU4WavesPerBlock
-    // workgroups (u4_launch_blocks, slg_api.hip), each wave pulls slices from sp.work_ctr
-    const uint32_t blocks = (sp.n_waves + (uint32_t)kU4WavesPerBlock - 1u) / (uint32_t)kU4WavesPerBlock;
-    const dim3 grid(blocks), wg(64 * kU4WavesPerBlock);
-    const size_t lds4 = kU4WavesPerBlock * u4_wave_lds(SLG_INST_KREGS, 4, u4_filter_words(4));
-    const size_t lds8 = kU4WavesPerBlock * u4_wave_lds(SLG_INST_KREGS, 8, u4_filter_words(8));
-    if (sp.work_ctr == nullptr) {
-      if (kind == 6)
-        hipLaunchKernelGGL((score_uniform4_kernel<SLG_INST_KREGS, 4, false, false>), grid, wg, lds4, st, sp);
-      else
-        hipLaunchKernelGGL((score_uniform4_kernel<SLG_INST_KREGS, 8, false, false>), grid, wg, lds8, st, sp);
-    } else {
-      if (kind == 6)
-        hipLaunchKernelGGL((score_uniform4_kernel<SLG_INST_KREGS, 4, false, true>), grid, wg, lds4, st, sp);
-      else
-        hipLaunchKernelGGL((score_uniform4_kernel<SLG_INST_KREGS, 8, false, true>), grid, wg, lds8, st, sp);
-    }
-    return;
-  }
-  if (kind == 8 || kind == 9) {  // the same kernel with score plans (flat Sum / DisMax over multi-term leaves)
-    const uint32_t blocks = (sp.n_waves + (uint32_t)kU4WavesPerBlock - 1u) / (uint32_t)kU4WavesPerBlock;
-    if (kind == 8)
-      hipLaunchKernelGGL((score_uniform4_kernel<SLG_INST_KREGS, 4, true>), dim3(blocks), dim3(64 * kU4WavesPerBlock),
-                         kU4WavesPerBlock * u4_wave_lds(SLG_INST_KREGS, 4, u4_filter_words(4)), st, sp);
+  if (kind >= 6 && kind <= 9) {  // few-term kernel: 6 / 7 <= 4 / 5..8 lists; 8 / 9 the same with score plans
+    const bool ml8 = (kind & 1) != 0, plan = kind >= 8;  // (plans: flat Sum / DisMax over multi-term leaves)
+    if (plan)
+      ml8 ? launch_uniform4<8, true>(sp, st) : launch_uniform4<4, true>(sp, st);
     else
-      hipLaunchKernelGGL((score_uniform4_kernel<SLG_INST_KREGS, 8, true>), dim3(blocks), dim3(64 * kU4WavesPerBlock),
-                         kU4WavesPerBlock * u4_wave_lds(SLG_INST_KREGS, 8, u4_filter_words(8)), st, sp);
+      ml8 ? launch_uniform4<8, false>(sp, st) : launch_uniform4<4, false>(sp, st);
     return;
   }
   // many lists: slots of one list each, 8 at a time (slg_score_multi.hpp)

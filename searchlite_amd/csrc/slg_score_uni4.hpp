@@ -58,20 +58,8 @@ constexpr int u4_wave_lds(int kregs, int ml, int fw) { return u4_tbl_off(kregs, 
 constexpr int kU4JoinPairs = SLG_U4_JOIN_PAIRS;  // queues up to this many entries are joined all-pairs (<= 64: one lane per entry)
 constexpr int u4_filter_words(int ml) { return ml <= 4 ? kJoinWords : SLG_U4_FW8; }
 // (k 129..256: LDS; the plan instantiation's leaf close needs a few registers more than 6 waves leave)
-constexpr int u4_waves(int kregs, int ml, bool plan = false, bool persist = false) {
-  return (ml > 4 || plan || persist) ? SLG_U4_WAVES8 : (kregs >= 4 ? 5 : SLG_U4_WAVES);  // (k > 256: the direct candidates of singles)
-}
-#ifndef SLG_U4_WPB
-#define SLG_U4_WPB 1  // waves per workgroup of the persistent launch (waves never synchronise with each other)
-#endif
-constexpr int kU4WavesPerBlock = SLG_U4_WPB;
-// persistent launch: workgroups to start so that every wave slot the kernel can occupy holds one wave
-// (n_cu compute units x 4 SIMDs x u4_waves), or one wave per slice if the batch has fewer
-inline uint32_t u4_launch_blocks(int kregs, int ml, bool plan, uint32_t n_slices, uint32_t n_cu, uint32_t waves_per_simd = 0) {
-  const uint32_t fit = (uint32_t)u4_waves(kregs, ml, plan, true);
-  const uint32_t slots = n_cu * 4u * (waves_per_simd != 0u && waves_per_simd < fit ? waves_per_simd : fit);
-  const uint32_t waves = n_slices < slots ? n_slices : slots;
-  return (waves + (uint32_t)kU4WavesPerBlock - 1u) / (uint32_t)kU4WavesPerBlock;
+constexpr int u4_waves(int kregs, int ml, bool plan = false) {
+  return (ml > 4 || plan) ? SLG_U4_WAVES8 : (kregs >= 4 ? 5 : SLG_U4_WAVES);  // (k > 256: the direct candidates of singles)
 }
 
 // 16-byte loads at 4-byte alignment (a lane's 8 postings start at any posting)
@@ -95,12 +83,8 @@ __device__ __forceinline__ T load_const(const T *src) {
 // PLAN: the batch has score plans (query/planner.rs:113-153, flat: Sum or DisMax over leaves that sum
 // one or more terms each): the lists arrive sorted by leaf and the join closes a doc's leaves in leaf
 // order.  Its own instantiation: the flat-sum batches (BASELINE configs 2, 3, 5) keep their registers.
-// PERSIST: the persistent-waves form (its own instantiation: the one-wave-per-slice kernel keeps the
-// straight-line code and register allocation it had before the slice loop existed — with the loop
-// compiled in, the default launch measured 5 % slower, 0.0817 against 0.0778 ms on config 2).
-template <int KREGS, int ML, bool PLAN = false, bool PERSIST = false>
-__global__ void __launch_bounds__(64 * kU4WavesPerBlock)
-    __attribute__((amdgpu_waves_per_eu(u4_waves(KREGS, ML, PLAN, PERSIST), u4_waves(KREGS, ML, PLAN, PERSIST))))
+template <int KREGS, int ML, bool PLAN = false>
+__global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(u4_waves(KREGS, ML, PLAN), u4_waves(KREGS, ML, PLAN))))
 score_uniform4_kernel(RoundScoreParams p_arg) {
   constexpr int NS = kUniSlots;            // postings per lane and round
   constexpr int FW = u4_filter_words(ML);  // filter words
@@ -113,66 +97,25 @@ score_uniform4_kernel(RoundScoreParams p_arg) {
   constexpr uint32_t FSM = LB == 4u ? 0x1Cu : 0x18u;
   static_assert(FW == 1024 || FW == 2048, "filter size");
   static_assert(FW * 4 >= kUniCap * 8, "the join queue ({doc, score} per posting) overlays the filter");
-  extern __shared__ __attribute__((aligned(16))) unsigned char smem_wg[];
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   (void)p_arg;
-  // waves are independent (no workgroup barrier anywhere): each wave of the workgroup owns its own
-  // LDS region
-  const uint32_t wave_in_wg = kU4WavesPerBlock > 1 ? rfl(threadIdx.x >> 6) : 0u;  // (uniform: a scalar register)
-  unsigned char *const smem = smem_wg + wave_in_wg * (uint32_t)u4_wave_lds(KREGS, ML, FW);
-  // Two launch forms (RoundScoreParams::work_ctr):
-  //  * one wave per slice (work_ctr == nullptr; the default): wave w of the grid runs launch position w,
-  //    the longest slices first; the hardware dispatcher is the work queue.
-  //  * PERSISTENT WAVES (slg_tuning.score_waves_per_simd): the launch holds that many waves per SIMD and
-  //    every wave pulls launch positions from the batch's work queues (slg_desc.hpp: kWorkQueues) until
-  //    they are empty.  Built because the slice timelines show the wave slots only 63 % / 72 % occupied
-  //    (configs 2 / 3) and measured: it does not pay on MI355X.  One counter hands out a ticket every
-  //    ~11-16 ns (config 2: 0.198 ms); 64 counters with an all-counter scan at the end 0.109 ms (every
-  //    wave reads every counter: same-address reads are served one at a time too); 64 counters with
-  //    bounded stealing 0.0846 ms at 6 waves per SIMD, 0.0876 at 5, 0.0945 at 4 — against 0.0776 ms for
-  //    the dispatcher on the same box; config 3: 5.23 against 5.06 ms.  Instruction counts and HBM
-  //    fetch are identical (profiles/r04_persistent_waves.txt): what the dispatcher does for free — a
-  //    new wave the moment a slot and its LDS are free, no ticket latency in the slice's start-up chain,
-  //    no end-game — costs more as software than the occupancy it recovers.
-  //    Every wave reaches the exit: the grid always drains.
-  const uint32_t wave_id = blockIdx.x * (uint32_t)kU4WavesPerBlock + wave_in_wg;
-  uint32_t wq = wave_id % kWorkQueues;  // the queue this wave pulls from
-  // (in the persistent form EVERY slice is pulled, the first one too: a wave whose workgroup is not
-  //  resident when the launch starts must not own a slice that then waits for a wave slot until the
-  //  other waves have drained the queues)
-  for (uint32_t widx = wave_id, done_slices = 0;; done_slices++) {
-  // (per slice, the launch parameters are read again from the kernel-argument segment: what a slice
-  //  derives from them then lives in registers for that slice only, instead of being hoisted out of
-  //  this loop and held — spilled — across it)
+  // One wave per slice, one wave per workgroup: wave w of the grid runs launch position w, the longest
+  // slices first; the hardware dispatcher is the work queue (waves pulling slices from queues of their
+  // own were measured slower: DESIGN.md §4.2b).
+  const uint32_t widx = blockIdx.x;
+  // (the launch parameters are read through the kernel-argument segment pointer, in the constant
+  //  address space: every field is an invariant scalar load, free to be issued where it is used)
   typedef const __attribute__((address_space(4))) RoundScoreParams *kparams_t;
   kparams_t pk = (kparams_t)__builtin_amdgcn_kernarg_segment_ptr();
-  if constexpr (PERSIST) asm volatile("" : "+s"(pk));
   const __attribute__((address_space(4))) RoundScoreParams &p = *pk;
   const uint32_t lane = threadIdx.x & 63;
-  if constexpr (!PERSIST) {
-    if (done_slices != 0u) break;  // one wave per slice: the loop is gone at compile time
-  } else
-  {
-    // A queue that has run dry is left for another one at most kWorkSteals times, then the wave exits.
-    // (Looking at ALL counters to find the queues that still hold work was measured and is a trap: at
-    //  the end of the launch every wave reads every counter, 6144 reads of each of the 64 lines, and
-    //  reads of one address are served one at a time like the atomics — the tail grew by ~30 us.)
-    const uint32_t n_sl = p.n_slices;
-    for (uint32_t tries = 0;; tries++) {
-      uint32_t c = 0;
-      if (lane == 0) c = atomicAdd(p.work_ctr + wq * kWorkCtrStride, 1u);
-      widx = wq + kWorkQueues * rfl(c);
-      if (widx < n_sl || tries >= kWorkSteals) break;
-      wq = (wq + 21u) % kWorkQueues;
-    }
-  }
-  if (widx >= p.n_slices) break;
+  if (widx >= p.n_slices) return;
   // The slice record, the segment descriptor and the reject-table row are written before this kernel
   // starts and never during it: they are read through the CONSTANT address space, i.e. by scalar
-  // loads (a few hundred cycles from the scalar cache).  Inside this loop the compiler cannot prove
-  // that for a plain global pointer — earlier slices stored to global memory — and would use vector
-  // loads, which put two more HBM-latency steps into every slice's dependent start-up chain
-  // (record -> segment -> term references -> cut-point searches -> first round): measured on config
-  // 2, whose slices are 4 rounds long, 0.111 ms against 0.078 ms for the one-wave-per-slice launch.
+  // loads (a few hundred cycles from the scalar cache).  Through a plain global pointer the compiler
+  // makes a load scalar only where it can prove that no store of the kernel may have changed the
+  // memory; vector loads would put two more HBM-latency steps into the slice's dependent start-up
+  // chain (record -> segment -> term references -> cut-point searches -> first round).
   typedef const __attribute__((address_space(4))) uint64_t *c_u64_t;
   const SliceDesc sl = load_const(p.slice_desc + widx);
   const uint32_t slice = rfl(sl.slice);
@@ -187,8 +130,8 @@ score_uniform4_kernel(RoundScoreParams p_arg) {
 
   const uint32_t T = rfl(sl.n_terms);
   const uint32_t n_r = rfl(sl.n_rounds);
-  // (inside the slice loop the compiler cannot prove these loads invariant — earlier slices stored to
-  //  global memory — so they are vector loads: everything wave-uniform is moved to scalar registers by hand)
+  // (everything wave-uniform is moved to scalar registers by hand: a value the compiler cannot prove
+  //  uniform stays in vector registers)
   auto uni64 = [](const uint64_t v) { return ((uint64_t)rfl((uint32_t)(v >> 32)) << 32) | rfl((uint32_t)v); };
   const uint32_t seg_id = rfl(sl.seg);
   const SegDev sd_v = load_const(p.segs + seg_id);
@@ -930,9 +873,6 @@ score_uniform4_kernel(RoundScoreParams p_arg) {
     p.stamps[(size_t)slice * 12 + 11] = ((unsigned long long)n_r << 32) | (unsigned long long)__builtin_amdgcn_s_getreg((20 << 0) | (0 << 6) | (3 << 11));
   }
 #endif
-  if constexpr (!PERSIST) break;
-  wave_fence();  // (the next slice rewrites the LDS tables this one read)
-  }  // next slice of this wave
 }
 
 }  // namespace slg

@@ -169,20 +169,34 @@ def test_tuning_defaults_come_from_the_environment_once(lib, monkeypatch):
     assert b"struct_size" in lib.slg_last_error()
 
 
+def _tuning_is_rejected(lib, field, value, code):
+    """slg_index_create_tuned refuses a tuning with `field` = value: no index, the field named in the
+    error, error code `code` (checked before any segment or device call)."""
+    from searchlite_amd import _native as N
+    keep = []
+    arr = (N.SegmentDesc * 1)(_seg_desc(4, [0, 1], [1], [1], keep))
+    t = N.default_tuning()
+    setattr(t, field, value)
+    assert lib.slg_index_create_tuned(arr, 1, 0, C.addressof(t)) is None
+    assert field.encode() in lib.slg_last_error()
+    assert lib.slg_last_error_code() == getattr(N, code)
+
+
 @pytest.mark.parametrize("form,code", [(2, "ERR_UNSUPPORTED"), (3, "ERR_UNSUPPORTED"),
                                        (0, "ERR_INVALID"), (5, "ERR_INVALID")])
 def test_uniform_kernel_other_than_4_is_rejected(lib, form, code):
     """4 (the blocked form) is the only few-term kernel: 2 and 3, the removed earlier forms, are
     unsupported; anything else (0: a zero-initialised struct) is invalid.  Checked before any segment
     or device call."""
-    from searchlite_amd import _native as N
-    keep = []
-    arr = (N.SegmentDesc * 1)(_seg_desc(4, [0, 1], [1], [1], keep))
-    t = N.default_tuning()
-    t.uniform_kernel = form
-    assert lib.slg_index_create_tuned(arr, 1, 0, C.addressof(t)) is None
-    assert b"uniform_kernel" in lib.slg_last_error()
-    assert lib.slg_last_error_code() == getattr(N, code)
+    _tuning_is_rejected(lib, "uniform_kernel", form, code)
+
+
+@pytest.mark.parametrize("waves", [1, 6])
+def test_score_waves_per_simd_other_than_0_is_rejected(lib, waves):
+    """score_waves_per_simd is reserved and must be 0 (one wave per slice): the persistent scoring waves
+    a non-zero value selected were removed, so any other value is unsupported.  Checked before any
+    segment or device call."""
+    _tuning_is_rejected(lib, "score_waves_per_simd", waves, "ERR_UNSUPPORTED")
 
 
 def test_segfile_library_exports_its_header():

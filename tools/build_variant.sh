@@ -1,7 +1,7 @@
 #!/bin/bash
 # Build the GPU library of another git revision as searchlite_amd/lib/libsearchlite_gpu_<tag>.so,
 # to time two kernels side by side on ONE box (devices differ by several percent):
-#   bash tools/build_variant.sh <git-ref> <tag> [extra compiler flags, e.g. -DSLG_U4_WPB=2];  SLG_LIB_TAG=<tag> python bench.py ...
+#   bash tools/build_variant.sh <git-ref> <tag> [extra compiler flags, e.g. -DSLG_U4_WAVES=5];  SLG_LIB_TAG=<tag> python bench.py ...
 set -e
 REF=$1; TAG=$2; shift 2; EXTRA="$*"
 ROOT=$(cd "$(dirname "$0")/.." && pwd)

@@ -175,7 +175,8 @@ typedef struct {
   uint32_t rounds_per_slice;     /* SLG_ROUNDS_PER_SLICE (0 = auto) */
   uint32_t max_rounds_per_slice; /* SLG_MAX_ROUNDS_PER_SLICE (0 = auto: 8 few-term kernel, 16 many-term) */
   uint32_t slices_per_subquery;  /* SLG_SLICES_PER_SUBQUERY (16) */
-  int32_t cand_mode;             /* !SLG_NO_CAND_MODE (1): 256 < k <= 1024 via candidates + select */
+  int32_t cand_mode;             /* (1, reserved): k > 256 always runs via candidates + select; any other
+                                    value is SLG_ERR_UNSUPPORTED (the register top-k kernels stop at k = 256) */
   int32_t slice_order;           /* !SLG_NO_SLICE_ORDER (1): longest slices launch first */
   int32_t block_max;             /* !SLG_NO_BLOCK_MAX (1): block skipping — 64-posting blocks of
                                     pruning-classified lists whose doc range holds no candidate doc

@@ -863,7 +863,7 @@ void slg_tuning_default(slg_tuning *t) {
   t->rounds_per_slice = env_u32("SLG_ROUNDS_PER_SLICE", 0);
   t->max_rounds_per_slice = env_u32("SLG_MAX_ROUNDS_PER_SLICE", 0);
   t->slices_per_subquery = env_u32("SLG_SLICES_PER_SUBQUERY", 16);
-  t->cand_mode = env_i32("SLG_NO_CAND_MODE", 0) == 0;
+  t->cand_mode = 1;  // (reserved: k > 256 always runs on candidates + select)
   t->slice_order = env_i32("SLG_NO_SLICE_ORDER", 0) == 0;
   t->block_max = env_i32("SLG_NO_BLOCK_MAX", 0) == 0;
   t->pool_cap_mb = env_u32("SLG_POOL_CAP_MB", 0);
@@ -897,6 +897,8 @@ slg_index *slg_index_create_tuned(const slg_segment_desc *segs, uint32_t n_segs,
     SLG_REQUIRE(tune.uniform_kernel == 4, "slg_tuning.uniform_kernel must be 4");
     if (tune.score_waves_per_simd != 0)
       throw SlgError(SLG_ERR_UNSUPPORTED, "slg_tuning.score_waves_per_simd must be 0: persistent scoring waves were removed");
+    if (tune.cand_mode != 1)
+      throw SlgError(SLG_ERR_UNSUPPORTED, "slg_tuning.cand_mode must be 1: 256 < k <= 1024 has no register top-k path");
     tune.uniform_max_terms = std::min<uint32_t>(tune.uniform_max_terms, slg::kU4MaxLists);
     tune.max_rounds_per_slice = std::min<uint32_t>(tune.max_rounds_per_slice, slg::kMaxRoundsPerSlice);
     tune.slices_per_subquery = std::max<uint32_t>(1, tune.slices_per_subquery);

@@ -847,7 +847,7 @@ void plan_batch(const std::vector<SegView> &segs, const slg_tuning &tn, const Ba
   out.plan_batch = any_plan;
   // large k: per-slice top-k lists would be mostly the slice itself; keep every doc above the
   // seed threshold instead (one candidate slot per posting) and select per query afterwards
-  out.cand_mode = k > 256 && (k > 1024 || tn.cand_mode);
+  out.cand_mode = k > 256;
 
   plan_rounds(segs, tn, k, sq_postings, sq_postings_all, out);
 

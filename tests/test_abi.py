@@ -199,6 +199,14 @@ def test_score_waves_per_simd_other_than_0_is_rejected(lib, waves):
     _tuning_is_rejected(lib, "score_waves_per_simd", waves, "ERR_UNSUPPORTED")
 
 
+@pytest.mark.parametrize("mode", [0, 2])
+def test_cand_mode_other_than_1_is_rejected(lib, mode):
+    """cand_mode is reserved and must be 1: k > 256 always runs on candidates + select.  With 0 the
+    planner would send 256 < k <= 1024 to the register top-k scoring kernels, whose width-8 and -16
+    bodies write candidates the batch never allocates.  Checked before any segment or device call."""
+    _tuning_is_rejected(lib, "cand_mode", mode, "ERR_UNSUPPORTED")
+
+
 def test_segfile_library_exports_its_header():
     """include/searchlite_segfile.h (host-only decoder of searchlite's segment files)."""
     from searchlite_amd import index_files as IF

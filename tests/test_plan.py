@@ -216,6 +216,68 @@ def test_round_and_slice_invariants(lib, T, k, n_segs):
         p.close()
 
 
+def test_large_k_always_runs_on_candidates(lib):
+    """k > 256 plans candidates + select whatever slg_tuning.cand_mode says (the index refuses any value
+    but 1; the planner no longer reads it): no per-slice top-k lists for the register kernels."""
+    rng = np.random.default_rng(13)
+    seg = random_segment(rng, 3000, 40, 15)
+    offs, terms, w = random_queries(rng, 8, 3, 40)
+    for k in (256, 257, 1024):
+        for mode in (1, 0):
+            p = Planned(lib, [seg], offs, terms, w, k, tuning=default_tuning(cand_mode=mode))
+            assert p.h, p.err
+            check_structure(p, k)
+            assert p.facts.cand_mode == (k > 256), (k, mode)
+            p.close()
+
+
+def _family_plans(plans):
+    return _plans(**{n: (a, a.dtype.str) for n, a in plans.items()}) if plans else None
+
+
+@pytest.mark.parametrize("name", ["F1", "F2", "F3", "F4", "F5", "F6", "F7", "F8", "F9"])
+def test_topk_width_families_route_to_their_kernels(lib, name):
+    """tests/test_gpu_topk_widths.py names each batch of tests.util.topk_family after the scoring
+    instantiation it is meant to reach; the planner's facts prove it, at a k of every register width and
+    under both tuning variants of the matrix: few-term kind 6 (<= 4 lists) / 7 (5..8) / 8 (plans, <= 4) /
+    9 (plans, 5..8); many-term MODE 0 (unclassified) / 1 (pruning-classified) / 2 (flat plans) /
+    3 (two-level plans) / 4 (deep trees)."""
+    from searchlite_amd import _native as N
+    from tests.util import TOPK_WIDTH_KS, topk_family, topk_variants
+    fam = topk_family(name)
+    segs = fam["segs"]
+    champs = [champions_of(s) for s in segs]
+    want = {  # uniform, max_terms range, plan_batch, nested (two-level), deep (MODE 4 whatever nested says), pruned
+        "F1": (1, (1, 4), 0, 0, 0, 0), "F2": (1, (5, 8), 0, 0, 0, 0), "F3": (1, (1, 4), 1, 0, 0, 0),
+        "F4": (1, (5, 8), 1, 0, 0, 0), "F5": (0, (9, 32), 0, 0, 0, 0), "F6": (0, (9, 32), 0, 0, 0, 1),
+        "F7": (0, (1, 4), 1, 0, 0, 0), "F8": (0, (5, 32), 1, 1, 0, 0), "F9": (0, (5, 32), 1, 0, 1, 0)}[name]
+    for variant in topk_variants(name).values():
+        tune = default_tuning()
+        for n, v in dict(fam["tuning"], **variant).items():
+            setattr(tune, n, v)
+        for k in TOPK_WIDTH_KS:
+            p = Planned(lib, segs, fam["offs"], fam["terms"], fam["w"], k, strategy=fam["strategy"], tuning=tune,
+                        plans=_family_plans(fam["plans"]), q_filter=fam["q_filter"], filter_live=b"\x01",
+                        champs=champs if tune.champions else None)
+            assert p.h, (name, k, p.err)
+            check_structure(p, k)
+            f = p.facts
+            got = (f.uniform, f.max_terms, f.plan_batch, f.nested, f.deep, f.pruned)
+            assert got[0] == want[0] and f.multi == (not want[0]), (name, variant, k, got)
+            assert want[1][0] <= f.max_terms <= want[1][1], (name, variant, k, got)
+            assert got[2:5] == want[2:5], (name, variant, k, got)
+            # MaxScore classification needs a threshold seed from the champion table.  The one planned with
+            # here is exact; the device's is looser for ranks above 64 and skips deleted docs, so whether
+            # the candidate cells (k > 256) stay classified depends on which table: asserted for the
+            # register widths only
+            if k <= 256:
+                assert f.pruned == want[5], (name, variant, k, got)
+            assert f.cand_mode == (k > 256), (name, k)
+            if variant:   # one round per slice: many slices per query for the merge
+                assert f.n_slices == f.n_rounds > f.n_sq, (name, k, f.n_slices, f.n_rounds, f.n_sq)
+            p.close()
+
+
 def test_kernel_choice_follows_what_block_skipping_can_save(lib):
     """5-term Wand batches are MaxScore-classified, and keep the classification (many-term kernel,
     block skipping) only where skipping is expected to leave >= 15 % of the postings unread: lists of

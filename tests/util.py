@@ -165,3 +165,174 @@ def load_golden(name):
 
 def golden_expected(z):
     return z["exp_doc"], z["exp_seg"], z["exp_score"], z["exp_count"]
+
+
+# ---- top-k width matrix (tests/test_gpu_topk_widths.py, tests/test_plan.py) -------------------------
+# Every scoring and merge kernel is compiled once per top-k register width (KREGS 1 / 2 / 4 / 8 / 16 for
+# k <= 64 / 128 / 256 / 512 / more).  The families below each reach one scoring instantiation; the
+# matrix runs each at k on both sides of every width boundary.
+TOPK_WIDTH_KS = (1, 64, 65, 128, 129, 201, 256, 257, 512, 513, 1024, 1025)
+TOPK_BOUNDARY_DFS = (64, 65, 128, 129, 256, 257, 1024, 1025)
+TOPK_FAMILIES = ("F1", "F2", "F3", "F4", "F5", "F6", "F7", "F8", "F9")
+# tuning variant (b): no threshold seed, so every posting enters the buffered top-k and it ranks many
+# times per slice; one round per slice (rounds_per_slice pins it: max_rounds_per_slice only caps the
+# slices that grow past the default), so the merge sees many slices per query
+TOPK_ROUND_PER_SLICE = {"champions": 0, "rounds_per_slice": 1, "max_rounds_per_slice": 1}
+
+
+def topk_variants(name):
+    """-> {label: tuning overrides} the matrix runs family `name` under.  F6 (MaxScore-classified) keeps
+    its champion table in variant (b): classification needs the threshold seed the table gives, and
+    without it the batch would run unclassified (MODE 0, which F5 covers)."""
+    b = dict(TOPK_ROUND_PER_SLICE)
+    if name == "F6":
+        del b["champions"]
+    return {"a": {}, "b": b}
+
+
+def _append_lists(seg, lists):
+    """seg with extra terms appended after its vocabulary: lists = [(doc ids, tfs)]."""
+    from searchlite_amd.segment import Segment
+    offs = [np.asarray(seg.term_offsets, dtype=np.uint64)]
+    docs, tfs = [seg.doc_ids], [seg.tfs]
+    end = int(seg.term_offsets[-1])
+    for d, t in lists:
+        docs.append(np.asarray(d, dtype=np.uint32))
+        tfs.append(np.asarray(t, dtype=np.uint32))
+        end += len(d)
+        offs.append(np.array([end], dtype=np.uint64))
+    tf = None if seg.term_field is None else np.concatenate(
+        [seg.term_field, np.zeros(len(lists), dtype=seg.term_field.dtype)])
+    return Segment(n_docs=seg.n_docs, term_offsets=np.concatenate(offs), doc_ids=np.concatenate(docs),
+                   tfs=np.concatenate(tfs), field_doc_len=seg.field_doc_len, field_avgdl=seg.field_avgdl,
+                   docs=seg.docs, k1=seg.k1, b=seg.b, term_field=tf)
+
+
+TOPK_FEW_DFS = (40, 100)   # live df of the one list queries 5 and 6 keep
+
+
+def _make_few(terms, q, first, few_term):
+    """Queries 5 and 6: the first term becomes crafted list few_term + (q - 5) of segment 0, every other
+    term of the query is absent (the query keeps its leaves and plan)."""
+    from searchlite_amd.segment import NO_TERM
+    if q not in (5, 6):
+        return
+    for i in range(first, len(terms)):
+        terms[i] = [NO_TERM, NO_TERM]
+    terms[first] = [few_term + q - 5, NO_TERM]
+
+
+def topk_family(name):
+    """One batch of the top-k width matrix (fixed seeds; plain data, no device):
+      F1 few-term, <= 4 lists (T = 3)             F6 many-term, pruning-classified (Wand, pruning 1)
+      F2 few-term, 5..8 lists (T = 7, pruning 0)  F7 flat plans, uniform_plans 0 (many-term kernel)
+      F3 flat Sum / DisMax plans, 2 fields x 2 words  F8 two-level plans
+      F4 flat plans, 4 fields x 2 words           F9 a score tree of four internal levels
+      F5 many-term, unclassified (T = 12, pruning 0)
+    Two segments; every 7th doc deleted and made short (so deleted docs are among the top scorers);
+    integer weights and short docs (scores tie exactly at the k-th place, the doc id decides); queries
+    with no term at all, with far more matches than any k, and two with few: queries 5 and 6 keep one
+    term, a crafted list of segment 0 with TOPK_FEW_DFS live docs (every other term absent).  F1 and F5
+    add single-term queries on crafted lists of segment 0 whose live df is every TOPK_BOUNDARY_DFS value
+    (count == k - 1, k, k + 1 at the width boundaries).  A doc filter (id 0) on every third query.
+    -> dict(segs, offs, terms, w, plans (prepare() keywords), q_filter, masks (filter 0), tuning, strategy)."""
+    from searchlite_amd.segment import NO_TERM
+    fam = int(name[1:])
+    rng = np.random.default_rng(5100 + fam)
+    multifield = fam in (3, 4, 7, 8, 9)
+    n_fields = 4 if fam == 4 else 3 if fam in (8, 9) else 2
+    vocab = 12 if multifield else 40
+    segs = []
+    for s in range(2):
+        n = 2600 + 700 * s
+        if multifield:
+            # (short text where queries span three or four fields: exact ties at the k-th place)
+            sg = random_multifield_segment(rng, n, vocab, n_fields, 3 if n_fields >= 3 else 6)
+        else:
+            sg = random_segment(rng, n, vocab, 5)
+        for dl in sg.field_doc_len:
+            dl[::7] = np.where(dl[::7] > 0, 1.0, 0.0)   # deleted docs score high
+        segs.append(sg)
+    crafted = fam in (1, 5)
+    # lists of live (not deleted) docs of segment 0 after its vocabulary: the boundary dfs (F1, F5), the few
+    base = segs[0].n_terms
+    live = np.array([d for d in range(segs[0].n_docs) if d % 7], dtype=np.uint32)
+    lists = []
+    for df in (TOPK_BOUNDARY_DFS if crafted else ()) + TOPK_FEW_DFS:
+        d = np.sort(rng.choice(live, size=df, replace=False)).astype(np.uint32)
+        lists.append((d, rng.integers(1, 3, size=df)))
+    segs[0] = _append_lists(segs[0], lists)
+    few_term = base + (len(TOPK_BOUNDARY_DFS) if crafted else 0)
+    for sg in segs:
+        sg.set_deleted(range(0, sg.n_docs, 7))
+    nq = 28
+    S, D, L = 0, 1, 2
+    offs, terms, w = [0], [], []
+    leaf, plan, tie, nl = [], [], [], []
+    qlo, lg, qgo, gp, gt = [0], [], [0], [], []
+    nk, nt, npar, qno = [], [], [], [0]
+    T = {1: 3, 2: 7, 5: 12, 6: 12}.get(fam, 0)
+    for q in range(nq):
+        none = q == 3                                    # no term in any segment
+        q_first = len(terms)
+        if fam in (1, 2, 5, 6):
+            if crafted and 8 <= q < 8 + len(TOPK_BOUNDARY_DFS):
+                terms.append([base + q - 8, NO_TERM])
+                w.append(np.float32(1.0))
+            else:
+                n_t = T if q % 4 else max(1, T // 2)     # ragged term counts
+                for t in rng.choice(vocab, size=n_t, replace=False):
+                    terms.append([NO_TERM if none else int(t)] * 2)
+                    w.append(np.float32(1 + q % 2 * (int(t) % 2)))
+            _make_few(terms, q, q_first, few_term)
+            offs.append(len(terms))
+            continue
+        n_words = 2 if fam in (3, 4, 7) else 3
+        words = rng.choice(vocab, size=n_words, replace=False)
+        fields = n_fields if fam != 9 else 3
+        for wi, wd in enumerate(words):
+            for f in range(fields):
+                t = f * vocab + int(wd)
+                terms.append([NO_TERM if none else t] * 2)
+                w.append(np.float32(1 + (f + wi) % 2))
+                leaf.append(wi if fam != 9 else [0, 1, 1, 2, 3, 3, 4, 5, 5][wi * 3 + f])
+        _make_few(terms, q, q_first, few_term)
+        offs.append(len(terms))
+        if fam in (3, 4, 7):     # query string (leaf per word, Sum) or best_fields-like DisMax
+            plan.append(D if q % 2 else S)
+            tie.append(0.5 if q % 2 else 0.0)
+            nl.append(n_words)
+        elif fam == 8:           # root DisMax over two Sum groups, or root Sum over a DisMax group + leaf
+            plan.append(D if q % 2 else S)
+            tie.append(0.25 if q % 2 else 0.0)
+            nl.append(3)
+            lg += [0, 0, 1] if q % 2 else [0, 1, 1]
+            qlo.append(len(lg))
+            gp += [S, S] if q % 2 else [D, S]
+            gt += [0.0, 0.0] if q % 2 else [0.5, 0.0]
+            qgo.append(len(gp))
+        else:                    # four internal levels, a leaf hanging off every level (6 leaves)
+            nk += [D, L, S, L, D, L, S, L, L, L]
+            nt += [.25, 0, 0, 0, .75, 0, 0, 0, 0, 0]
+            npar += [0, 0, 0, 2, 2, 4, 4, 6, 6, 0]
+            qno.append(len(nk))
+    plans = {}
+    if fam in (3, 4, 7, 8):
+        plans = dict(q_leaf=np.array(leaf, np.uint32), q_plan=np.array(plan, np.int32),
+                     q_tie=np.array(tie, np.float32), q_nleaves=np.array(nl, np.uint32))
+    if fam == 8:
+        plans.update(q_leaf_offsets=np.array(qlo, np.uint32), leaf_group=np.array(lg, np.uint32),
+                     q_group_offsets=np.array(qgo, np.uint32), group_plan=np.array(gp, np.int32),
+                     group_tie=np.array(gt, np.float32))
+    if fam == 9:
+        plans = dict(q_leaf=np.array(leaf, np.uint32), q_node_offsets=np.array(qno, np.uint32),
+                     node_kind=np.array(nk, np.int32), node_tie=np.array(nt, np.float32),
+                     node_parent=np.array(npar, np.uint32))
+    q_filter = np.array([0 if q % 3 == 1 and not (crafted and 8 <= q < 16) else -1 for q in range(nq)],
+                        dtype=np.int32)
+    masks = [rng.random(sg.n_docs) < 0.6 for sg in segs]
+    tuning = {2: {"pruning": 0}, 5: {"pruning": 0}, 6: {"pruning": 1, "block_max": 1},
+              7: {"uniform_plans": 0}}.get(fam, {})
+    return dict(segs=segs, offs=np.array(offs, np.uint32), terms=np.array(terms, np.uint32),
+                w=np.array(w, np.float32), plans=plans, q_filter=q_filter, masks=masks, tuning=tuning,
+                strategy=1)   # Wand (pruning-classified where pruning allows it)

@@ -2392,11 +2392,172 @@ int slg_profile_read(slg_index *ix, uint32_t *n_launches, float *total_ms) {
 }
 
 namespace {
-// slg_batch_rerank_device runs the rerank kernels on the batch's stream: the launch sites below take
-// the stream from here when it is set (this thread only, for the duration of that call)
-thread_local bool g_rerank_stream_set = false;
-thread_local hipStream_t g_rerank_stream = nullptr;
-inline hipStream_t rerank_stream(slg_index *ix) { return g_rerank_stream_set ? g_rerank_stream : ix->stream; }
+// dimension / metric / device stores of vector field f (0: the field of the segment descriptors;
+// mixed_metric: its segments may differ in metric — the single-clause kernel reads it per segment —
+// and *metric is the last one's)
+void field_facts(const IndexState &S, uint32_t f, uint32_t *dim, int32_t *metric, const slg::VecSegDev **vsegs,
+                 bool mixed_metric = false) {
+  if (f == 0) {
+    uint32_t d = 0;
+    int32_t m = -1;
+    for (auto &s : S.segs) {
+      if (!s->store->vec_dim) continue;
+      SLG_REQUIRE(d == 0 || d == s->store->vec_dim, "segments disagree on vec_dim");
+      SLG_REQUIRE(mixed_metric || m < 0 || m == s->store->vec_metric, "segments disagree on the vector metric");
+      d = s->store->vec_dim;
+      m = s->store->vec_metric;
+    }
+    if (d == 0) throw SlgError(SLG_ERR_UNSUPPORTED, "index has no vector field");
+    *dim = d;
+    *metric = m;
+    *vsegs = S.d_vsegs.as<slg::VecSegDev>();
+    return;
+  }
+  SLG_REQUIRE(f <= S.vfields.size(), "unknown vector field id");
+  const VecFieldHost &vf = *S.vfields[f - 1];
+  *dim = vf.dim;
+  *metric = vf.metric;
+  *vsegs = vf.d_vsegs.as<slg::VecSegDev>();
+}
+
+enum class RerankShape { One, Multi, Fields };  // rerank_kernel, rerank_multi_kernel, rerank_fields_kernel
+
+// One rerank call, checked against one snapshot of the index.  fp holds the parameters of every
+// shape (the fields kernel's are a superset): base, boost, n_clauses, q_floats = the floats of one
+// query's clause vectors; the per-clause tables are the fields shape's only.
+struct RerankCall {
+  std::shared_ptr<const IndexState> S;  // (a retired state waits for the device before its tables go)
+  RerankShape shape = RerankShape::One;
+  slg::RerankFieldsParams fp{};
+};
+
+// The host-only step of every rerank entry: all checks, in one order for the host and device forms,
+// then the kernel facts of the call's shape.  io's pointers are only tested for NULL (mem names
+// their memory in the message).  false: nq == 0, nothing to do.  Multi-clause entries with one
+// clause and no boost take the single-clause kernel, which has no n_clauses check.
+bool rerank_prepare(slg_index *ix, bool fields, uint32_t n_clauses, const uint32_t *clause_field, const float *boost,
+                    const slg::RerankParams &io, const char *mem, RerankCall *rc) {
+  if (fields)
+    SLG_REQUIRE(ix != nullptr && clause_field != nullptr, "index or clause_field is NULL");
+  else
+    SLG_REQUIRE(ix != nullptr, "index is NULL");
+  rc->shape = fields ? RerankShape::Fields
+                     : (n_clauses == 1 && boost == nullptr ? RerankShape::One : RerankShape::Multi);
+  if (rc->shape != RerankShape::One && (n_clauses < 1 || n_clauses > SLG_MAX_VECTOR_CLAUSES))
+    throw SlgError(SLG_ERR_UNSUPPORTED, "n_clauses outside 1..SLG_MAX_VECTOR_CLAUSES");
+  if (io.k_out > SLG_MAX_RERANK_K) throw SlgError(SLG_ERR_UNSUPPORTED, "k_out > SLG_MAX_RERANK_K");
+  if (io.nq == 0) return false;
+  SLG_REQUIRE(io.qvecs && io.alpha && io.cand_count && io.out_count, std::string(mem) + " arrays are NULL");
+  SLG_REQUIRE(io.max_cand == 0 || (io.cand_doc && io.cand_seg && io.cand_bm25), "candidate arrays are NULL");
+  SLG_REQUIRE(io.k_out == 0 || (io.out_doc && io.out_seg && io.out_score), "output arrays are NULL");
+  rc->S = ix->snapshot();
+  const IndexState &S = *rc->S;
+  slg::RerankFieldsParams &fp = rc->fp;
+  fp.base = io;
+  fp.base.n_segs = (uint32_t)S.segs.size();
+  fp.boost = boost;
+  fp.n_clauses = n_clauses;
+  if (rc->shape == RerankShape::Fields) {
+    for (uint32_t c = 0; c < n_clauses; c++) {
+      field_facts(S, clause_field[c], &fp.cdim[c], &fp.cmetric[c], &fp.cvsegs[c]);
+      fp.coff[c] = fp.q_floats;
+      fp.q_floats += fp.cdim[c];
+    }
+    if (slg::rerank_fields_lds_floats(n_clauses, fp.q_floats, io.max_cand) > slg::kRerankMultiLdsFloats)
+      throw SlgError(SLG_ERR_UNSUPPORTED, "clause vectors + n_clauses * max_cand exceed the LDS budget of the rerank");
+    return true;
+  }
+  int32_t metric;
+  field_facts(S, 0, &fp.base.dim, &metric, &fp.base.vsegs, rc->shape == RerankShape::One);
+  fp.q_floats = n_clauses * fp.base.dim;
+  if (rc->shape == RerankShape::One) {
+    if (io.max_cand > slg::kRerankMaxCand)
+      throw SlgError(SLG_ERR_UNSUPPORTED, "max_cand > " + std::to_string(slg::kRerankMaxCand));
+    return true;
+  }
+  for (auto &s : S.segs)
+    if (!s->store->vec_dim) throw SlgError(SLG_ERR_UNSUPPORTED, "multi-clause rerank needs the vector field in every segment");
+  if (slg::rerank_multi_lds_floats(n_clauses, fp.base.dim, io.max_cand) > slg::kRerankMultiLdsFloats)
+    throw SlgError(SLG_ERR_UNSUPPORTED, "n_clauses * (dim + max_cand) exceeds the LDS budget of the multi-clause rerank");
+  return true;
+}
+
+// The launch step: the kernel of the call's shape on st, with the device pointers of rc.fp (the
+// caller holds ix->mu and the device)
+void rerank_launch(const RerankCall &rc, hipStream_t st) {
+  const slg::RerankFieldsParams &fp = rc.fp;
+  const int kregs = kregs_for(fp.base.k_out ? fp.base.k_out : 1);
+  if (rc.shape == RerankShape::One) {
+    SLG_HIP(slg::launch_rerank(fp.base, kregs, st));
+  } else if (rc.shape == RerankShape::Multi) {
+    const slg::RerankMultiParams mp{fp.base, fp.boost, fp.n_clauses, fp.base.dim + 4};
+    SLG_HIP(slg::launch_rerank_multi(mp, kregs, st));
+  } else {
+    SLG_HIP(slg::launch_rerank_fields(fp, kregs, st));
+  }
+}
+
+// The _device entries: device arrays in and out, asynchronous on the index stream or, b set, on the
+// batch's (read under ix->mu, with the launch)
+void rerank_device(slg_index *ix, const slg_batch *b, bool fields, uint32_t n_clauses, const uint32_t *clause_field,
+                   const float *d_boost, const slg::RerankParams &d) {
+  RerankCall rc;
+  if (!rerank_prepare(ix, fields, n_clauses, clause_field, d_boost, d, "device", &rc)) return;
+  std::lock_guard<std::mutex> lk(ix->mu);
+  DeviceGuard g(ix->device);
+  rerank_launch(rc, b ? batch_stream(b) : ix->stream);
+}
+
+// waits for a stream when it goes out of scope
+struct StreamSync {
+  hipStream_t st;
+  ~StreamSync() { (void)hipStreamSynchronize(st); }
+};
+
+// The host-array entries: checks first, then pooled device buffers, H2D, launch, D2H and a wait, all on
+// the index stream.  Declared after the buffers, `done` waits for the stream on every exit, so no
+// block goes back to the pool while a queued copy or kernel may still use it.
+void rerank_staged(slg_index *ix, bool fields, uint32_t n_clauses, const uint32_t *clause_field, const float *boost,
+                   const slg::RerankParams &h) {
+  RerankCall rc;
+  if (!rerank_prepare(ix, fields, n_clauses, clause_field, boost, h, "host", &rc)) return;
+  const size_t nq = h.nq, nqc = nq * n_clauses, nc = nq * h.max_cand, no = nq * h.k_out;
+  DeviceGuard g(ix->device);
+  const hipStream_t st = ix->stream;
+  DevBuf dq, da, db, dcd, dcs, dcb, dcc, dod, dos, dosc, dov, doc_;
+  StreamSync done{st};
+  const auto up = [&](DevBuf &buf, const void *src, size_t n) -> DevBuf & {
+    buf.alloc_pooled(&ix->pool, n * 4);
+    if (src && n) SLG_HIP(hipMemcpyAsync(buf.p, src, n * 4, hipMemcpyHostToDevice, st));
+    return buf;
+  };
+  slg::RerankParams &d = rc.fp.base;
+  d.qvecs = up(dq, h.qvecs, nq * rc.fp.q_floats).as<float>();
+  d.alpha = up(da, h.alpha, nqc).as<float>();
+  if (boost) rc.fp.boost = up(db, boost, nqc).as<float>();
+  d.cand_doc = up(dcd, h.cand_doc, nc).as<uint32_t>();
+  d.cand_seg = up(dcs, h.cand_seg, nc).as<uint32_t>();
+  d.cand_bm25 = up(dcb, h.cand_bm25, nc).as<float>();
+  d.cand_count = up(dcc, h.cand_count, nq).as<uint32_t>();
+  d.out_doc = up(dod, nullptr, no).as<uint32_t>();
+  d.out_seg = up(dos, nullptr, no).as<uint32_t>();
+  d.out_score = up(dosc, nullptr, no).as<float>();
+  d.out_vec = up(dov, nullptr, no).as<float>();
+  d.out_count = up(doc_, nullptr, nq).as<uint32_t>();
+  {
+    std::lock_guard<std::mutex> lk(ix->mu);
+    rerank_launch(rc, st);
+  }
+  const auto down = [&](void *dst, const void *src, size_t n) {
+    if (dst && n) SLG_HIP(hipMemcpyAsync(dst, src, n * 4, hipMemcpyDeviceToHost, st));
+  };
+  down(h.out_doc, d.out_doc, no);
+  down(h.out_seg, d.out_seg, no);
+  down(h.out_score, d.out_score, no);
+  down(h.out_vec, d.out_vec, no);
+  down(h.out_count, d.out_count, nq);
+  SLG_HIP(hipStreamSynchronize(st));
+}
 }  // namespace
 
 int slg_rerank_batch_device(slg_index *ix, uint32_t nq, const float *d_qvecs, const float *d_alpha,
@@ -2405,45 +2566,9 @@ int slg_rerank_batch_device(slg_index *ix, uint32_t nq, const float *d_qvecs, co
                             uint32_t max_cand, uint32_t k_out, uint32_t *d_out_doc,
                             uint32_t *d_out_seg, float *d_out_score, float *d_out_vec_score,
                             uint32_t *d_out_count) {
-  return guarded([&] {
-    SLG_REQUIRE(ix != nullptr, "index is NULL");
-    if (k_out > SLG_MAX_RERANK_K) throw SlgError(SLG_ERR_UNSUPPORTED, "k_out > SLG_MAX_RERANK_K");
-    if (nq == 0) return;
-    SLG_REQUIRE(d_qvecs && d_alpha && d_cand_count && d_out_count, "device arrays are NULL");
-    SLG_REQUIRE(max_cand == 0 || (d_cand_doc && d_cand_seg && d_cand_bm25), "candidate arrays are NULL");
-    SLG_REQUIRE(k_out == 0 || (d_out_doc && d_out_seg && d_out_score), "output arrays are NULL");
-    const auto S = ix->snapshot();  // (a retired state waits for the device before its tables go)
-    uint32_t dim = 0;
-    for (auto &s : S->segs)
-      if (s->store->vec_dim) {
-        SLG_REQUIRE(dim == 0 || dim == s->store->vec_dim, "segments disagree on vec_dim");
-        dim = s->store->vec_dim;
-      }
-    if (dim == 0) throw SlgError(SLG_ERR_UNSUPPORTED, "index has no vector field");
-    if (max_cand > slg::kRerankMaxCand)
-      throw SlgError(SLG_ERR_UNSUPPORTED, "max_cand > " + std::to_string(slg::kRerankMaxCand));
-    std::lock_guard<std::mutex> lk(ix->mu);
-    DeviceGuard g(ix->device);
-    slg::RerankParams rp{};
-    rp.vsegs = S->d_vsegs.as<slg::VecSegDev>();
-    rp.n_segs = (uint32_t)S->segs.size();
-    rp.dim = dim;
-    rp.qvecs = d_qvecs;
-    rp.alpha = d_alpha;
-    rp.cand_doc = d_cand_doc;
-    rp.cand_seg = d_cand_seg;
-    rp.cand_bm25 = d_cand_bm25;
-    rp.cand_count = d_cand_count;
-    rp.max_cand = max_cand;
-    rp.k_out = k_out;
-    rp.out_doc = d_out_doc;
-    rp.out_seg = d_out_seg;
-    rp.out_score = d_out_score;
-    rp.out_vec = d_out_vec_score;
-    rp.out_count = d_out_count;
-    rp.nq = nq;
-    SLG_HIP(slg::launch_rerank(rp, kregs_for(k_out ? k_out : 1), rerank_stream(ix)));
-  });
+  return slg_rerank_multi_batch_device(ix, nq, 1, d_qvecs, d_alpha, nullptr, d_cand_doc, d_cand_seg, d_cand_bm25,
+                                       d_cand_count, max_cand, k_out, d_out_doc, d_out_seg, d_out_score,
+                                       d_out_vec_score, d_out_count);
 }
 
 int slg_rerank_multi_batch_device(slg_index *ix, uint32_t nq, uint32_t n_clauses, const float *d_qvecs,
@@ -2452,78 +2577,68 @@ int slg_rerank_multi_batch_device(slg_index *ix, uint32_t nq, uint32_t n_clauses
                                   const uint32_t *d_cand_count, uint32_t max_cand, uint32_t k_out,
                                   uint32_t *d_out_doc, uint32_t *d_out_seg, float *d_out_score,
                                   float *d_out_vec_score, uint32_t *d_out_count) {
-  if (n_clauses == 1 && d_boost == nullptr)  // one clause: the GEMV-shaped VALU kernel
-    return slg_rerank_batch_device(ix, nq, d_qvecs, d_alpha, d_cand_doc, d_cand_seg, d_cand_bm25,
-                                   d_cand_count, max_cand, k_out, d_out_doc, d_out_seg, d_out_score,
-                                   d_out_vec_score, d_out_count);
   return guarded([&] {
-    SLG_REQUIRE(ix != nullptr, "index is NULL");
-    if (n_clauses < 1 || n_clauses > SLG_MAX_VECTOR_CLAUSES)
-      throw SlgError(SLG_ERR_UNSUPPORTED, "n_clauses outside 1..SLG_MAX_VECTOR_CLAUSES");
-    if (k_out > SLG_MAX_RERANK_K) throw SlgError(SLG_ERR_UNSUPPORTED, "k_out > SLG_MAX_RERANK_K");
-    if (nq == 0) return;
-    SLG_REQUIRE(d_qvecs && d_alpha && d_cand_count && d_out_count, "device arrays are NULL");
-    SLG_REQUIRE(max_cand == 0 || (d_cand_doc && d_cand_seg && d_cand_bm25), "candidate arrays are NULL");
-    SLG_REQUIRE(k_out == 0 || (d_out_doc && d_out_seg && d_out_score), "output arrays are NULL");
-    const auto S = ix->snapshot();
-    uint32_t dim = 0;
-    int32_t metric = -1;
-    for (auto &s : S->segs) {
-      if (!s->store->vec_dim) continue;
-      SLG_REQUIRE(dim == 0 || dim == s->store->vec_dim, "segments disagree on vec_dim");
-      SLG_REQUIRE(metric < 0 || metric == s->store->vec_metric, "segments disagree on the vector metric");
-      dim = s->store->vec_dim;
-      metric = s->store->vec_metric;
-    }
-    if (dim == 0) throw SlgError(SLG_ERR_UNSUPPORTED, "index has no vector field");
-    for (auto &s : S->segs)
-      if (!s->store->vec_dim) throw SlgError(SLG_ERR_UNSUPPORTED, "multi-clause rerank needs the vector field in every segment");
-    if (slg::rerank_multi_lds_floats(n_clauses, dim, max_cand) > slg::kRerankMultiLdsFloats)
-      throw SlgError(SLG_ERR_UNSUPPORTED, "n_clauses * (dim + max_cand) exceeds the LDS budget of the multi-clause rerank");
-    std::lock_guard<std::mutex> lk(ix->mu);
-    DeviceGuard g(ix->device);
-    slg::RerankMultiParams mp{};
-    slg::RerankParams &rp = mp.base;
-    rp.vsegs = S->d_vsegs.as<slg::VecSegDev>();
-    rp.n_segs = (uint32_t)S->segs.size();
-    rp.dim = dim;
-    rp.qvecs = d_qvecs;
-    rp.alpha = d_alpha;
-    rp.cand_doc = d_cand_doc;
-    rp.cand_seg = d_cand_seg;
-    rp.cand_bm25 = d_cand_bm25;
-    rp.cand_count = d_cand_count;
-    rp.max_cand = max_cand;
-    rp.k_out = k_out;
-    rp.out_doc = d_out_doc;
-    rp.out_seg = d_out_seg;
-    rp.out_score = d_out_score;
-    rp.out_vec = d_out_vec_score;
-    rp.out_count = d_out_count;
-    rp.nq = nq;
-    mp.boost = d_boost;
-    mp.n_clauses = n_clauses;
-    mp.q_stride = dim + 4;
-    SLG_HIP(slg::launch_rerank_multi(mp, kregs_for(k_out ? k_out : 1), rerank_stream(ix)));
+    rerank_device(ix, nullptr, false, n_clauses, nullptr, d_boost,
+                  {nullptr, 0, 0, d_qvecs, d_alpha, d_cand_doc, d_cand_seg, d_cand_bm25, d_cand_count, max_cand,
+                   k_out, d_out_doc, d_out_seg, d_out_score, d_out_vec_score, d_out_count, nq});
   });
 }
 
 int slg_batch_rerank_device(slg_batch *b, uint32_t n_clauses, const float *d_qvecs, const float *d_alpha,
                             const float *d_boost, uint32_t k_out, uint32_t *d_out_doc, uint32_t *d_out_seg,
                             float *d_out_score, float *d_out_vec_score, uint32_t *d_out_count) {
-  int rc = guarded([&] { SLG_REQUIRE_LIVE(b); });
-  if (rc != SLG_OK) return rc;
-  slg_index *ix = b->idx;
-  {
-    std::lock_guard<std::mutex> lk(ix->mu);
-    g_rerank_stream = batch_stream(b);
-  }
-  g_rerank_stream_set = true;
-  rc = slg_rerank_multi_batch_device(ix, b->nq, n_clauses, d_qvecs, d_alpha, d_boost, b->d_out_doc, b->d_out_seg,
-                                     b->d_out_score, b->d_out_count, b->k, k_out, d_out_doc, d_out_seg, d_out_score,
-                                     d_out_vec_score, d_out_count);
-  g_rerank_stream_set = false;
-  return rc;
+  return guarded([&] {
+    SLG_REQUIRE_LIVE(b);
+    rerank_device(b->idx, b, false, n_clauses, nullptr, d_boost,
+                  {nullptr, 0, 0, d_qvecs, d_alpha, b->d_out_doc, b->d_out_seg, b->d_out_score, b->d_out_count,
+                   b->k, k_out, d_out_doc, d_out_seg, d_out_score, d_out_vec_score, d_out_count, b->nq});
+  });
+}
+
+int slg_rerank_fields_batch_device(slg_index *ix, uint32_t nq, uint32_t n_clauses, const uint32_t *clause_field,
+                                   const float *d_qvecs, const float *d_alpha, const float *d_boost,
+                                   const uint32_t *d_cand_doc, const uint32_t *d_cand_seg,
+                                   const float *d_cand_bm25, const uint32_t *d_cand_count, uint32_t max_cand,
+                                   uint32_t k_out, uint32_t *d_out_doc, uint32_t *d_out_seg, float *d_out_score,
+                                   float *d_out_vec_score, uint32_t *d_out_count) {
+  return guarded([&] {
+    rerank_device(ix, nullptr, true, n_clauses, clause_field, d_boost,
+                  {nullptr, 0, 0, d_qvecs, d_alpha, d_cand_doc, d_cand_seg, d_cand_bm25, d_cand_count, max_cand,
+                   k_out, d_out_doc, d_out_seg, d_out_score, d_out_vec_score, d_out_count, nq});
+  });
+}
+
+int slg_rerank_fields_batch(slg_index *ix, uint32_t nq, uint32_t n_clauses, const uint32_t *clause_field,
+                            const float *qvecs, const float *alpha, const float *boost,
+                            const uint32_t *cand_doc, const uint32_t *cand_seg, const float *cand_bm25,
+                            const uint32_t *cand_count, uint32_t max_cand, uint32_t k_out, uint32_t *out_doc,
+                            uint32_t *out_seg, float *out_score, float *out_vec_score, uint32_t *out_count) {
+  return guarded([&] {
+    rerank_staged(ix, true, n_clauses, clause_field, boost,
+                  {nullptr, 0, 0, qvecs, alpha, cand_doc, cand_seg, cand_bm25, cand_count, max_cand, k_out, out_doc,
+                   out_seg, out_score, out_vec_score, out_count, nq});
+  });
+}
+
+int slg_rerank_multi_batch(slg_index *ix, uint32_t nq, uint32_t n_clauses, const float *qvecs,
+                           const float *alpha, const float *boost, const uint32_t *cand_doc,
+                           const uint32_t *cand_seg, const float *cand_bm25, const uint32_t *cand_count,
+                           uint32_t max_cand, uint32_t k_out, uint32_t *out_doc, uint32_t *out_seg,
+                           float *out_score, float *out_vec_score, uint32_t *out_count) {
+  return guarded([&] {
+    rerank_staged(ix, false, n_clauses, nullptr, boost,
+                  {nullptr, 0, 0, qvecs, alpha, cand_doc, cand_seg, cand_bm25, cand_count, max_cand, k_out, out_doc,
+                   out_seg, out_score, out_vec_score, out_count, nq});
+  });
+}
+
+int slg_rerank_batch(slg_index *ix, uint32_t nq, const float *qvecs, const float *alpha,
+                     const uint32_t *cand_doc, const uint32_t *cand_seg, const float *cand_bm25,
+                     const uint32_t *cand_count, uint32_t max_cand, uint32_t k_out,
+                     uint32_t *out_doc, uint32_t *out_seg, float *out_score, float *out_vec_score,
+                     uint32_t *out_count) {
+  return slg_rerank_multi_batch(ix, nq, 1, qvecs, alpha, nullptr, cand_doc, cand_seg, cand_bm25, cand_count,
+                                max_cand, k_out, out_doc, out_seg, out_score, out_vec_score, out_count);
 }
 
 int slg_index_add_vector_field(slg_index *ix, const slg_vector_field_desc *per_segment, uint32_t n_segs) {
@@ -2570,292 +2685,6 @@ int slg_index_add_vector_field(slg_index *ix, const slg_vector_field_desc *per_s
     publish(ix, std::move(ns));
   });
   return rc == SLG_OK ? id : rc;
-}
-
-namespace {
-// dimension / metric / device stores of vector field f (0: the field of the segment descriptors)
-void field_facts(const IndexState &S, uint32_t f, uint32_t *dim, int32_t *metric, const slg::VecSegDev **vsegs) {
-  if (f == 0) {
-    uint32_t d = 0;
-    int32_t m = -1;
-    for (auto &s : S.segs) {
-      if (!s->store->vec_dim) continue;
-      SLG_REQUIRE(d == 0 || d == s->store->vec_dim, "segments disagree on vec_dim");
-      SLG_REQUIRE(m < 0 || m == s->store->vec_metric, "segments disagree on the vector metric");
-      d = s->store->vec_dim;
-      m = s->store->vec_metric;
-    }
-    if (d == 0) throw SlgError(SLG_ERR_UNSUPPORTED, "index has no vector field 0");
-    *dim = d;
-    *metric = m;
-    *vsegs = S.d_vsegs.as<slg::VecSegDev>();
-    return;
-  }
-  SLG_REQUIRE(f <= S.vfields.size(), "unknown vector field id");
-  const VecFieldHost &vf = *S.vfields[f - 1];
-  *dim = vf.dim;
-  *metric = vf.metric;
-  *vsegs = vf.d_vsegs.as<slg::VecSegDev>();
-}
-}  // namespace
-
-int slg_rerank_fields_batch_device(slg_index *ix, uint32_t nq, uint32_t n_clauses, const uint32_t *clause_field,
-                                   const float *d_qvecs, const float *d_alpha, const float *d_boost,
-                                   const uint32_t *d_cand_doc, const uint32_t *d_cand_seg,
-                                   const float *d_cand_bm25, const uint32_t *d_cand_count, uint32_t max_cand,
-                                   uint32_t k_out, uint32_t *d_out_doc, uint32_t *d_out_seg, float *d_out_score,
-                                   float *d_out_vec_score, uint32_t *d_out_count) {
-  return guarded([&] {
-    SLG_REQUIRE(ix != nullptr && clause_field != nullptr, "index or clause_field is NULL");
-    if (n_clauses < 1 || n_clauses > SLG_MAX_VECTOR_CLAUSES)
-      throw SlgError(SLG_ERR_UNSUPPORTED, "n_clauses outside 1..SLG_MAX_VECTOR_CLAUSES");
-    if (k_out > SLG_MAX_RERANK_K) throw SlgError(SLG_ERR_UNSUPPORTED, "k_out > SLG_MAX_RERANK_K");
-    if (nq == 0) return;
-    SLG_REQUIRE(d_qvecs && d_alpha && d_cand_count && d_out_count, "device arrays are NULL");
-    SLG_REQUIRE(max_cand == 0 || (d_cand_doc && d_cand_seg && d_cand_bm25), "candidate arrays are NULL");
-    SLG_REQUIRE(k_out == 0 || (d_out_doc && d_out_seg && d_out_score), "output arrays are NULL");
-    const auto S = ix->snapshot();
-    std::lock_guard<std::mutex> lk(ix->mu);
-    DeviceGuard g(ix->device);
-    slg::RerankFieldsParams fp{};
-    uint32_t qf = 0;
-    for (uint32_t c = 0; c < n_clauses; c++) {
-      field_facts(*S, clause_field[c], &fp.cdim[c], &fp.cmetric[c], &fp.cvsegs[c]);
-      fp.coff[c] = qf;
-      qf += fp.cdim[c];
-    }
-    if (slg::rerank_fields_lds_floats(n_clauses, qf, max_cand) > slg::kRerankMultiLdsFloats)
-      throw SlgError(SLG_ERR_UNSUPPORTED, "clause vectors + n_clauses * max_cand exceed the LDS budget of the rerank");
-    slg::RerankParams &rp = fp.base;
-    rp.vsegs = nullptr;
-    rp.n_segs = (uint32_t)S->segs.size();
-    rp.dim = 0;
-    rp.qvecs = d_qvecs;
-    rp.alpha = d_alpha;
-    rp.cand_doc = d_cand_doc;
-    rp.cand_seg = d_cand_seg;
-    rp.cand_bm25 = d_cand_bm25;
-    rp.cand_count = d_cand_count;
-    rp.max_cand = max_cand;
-    rp.k_out = k_out;
-    rp.out_doc = d_out_doc;
-    rp.out_seg = d_out_seg;
-    rp.out_score = d_out_score;
-    rp.out_vec = d_out_vec_score;
-    rp.out_count = d_out_count;
-    rp.nq = nq;
-    fp.boost = d_boost;
-    fp.n_clauses = n_clauses;
-    fp.q_floats = qf;
-    SLG_HIP(slg::launch_rerank_fields(fp, kregs_for(k_out ? k_out : 1), ix->stream));
-  });
-}
-
-int slg_rerank_fields_batch(slg_index *ix, uint32_t nq, uint32_t n_clauses, const uint32_t *clause_field,
-                            const float *qvecs, const float *alpha, const float *boost,
-                            const uint32_t *cand_doc, const uint32_t *cand_seg, const float *cand_bm25,
-                            const uint32_t *cand_count, uint32_t max_cand, uint32_t k_out, uint32_t *out_doc,
-                            uint32_t *out_seg, float *out_score, float *out_vec_score, uint32_t *out_count) {
-  uint32_t qf = 0;
-  int rc = guarded([&] {
-    SLG_REQUIRE(ix != nullptr && clause_field != nullptr, "index or clause_field is NULL");
-    if (n_clauses < 1 || n_clauses > SLG_MAX_VECTOR_CLAUSES)
-      throw SlgError(SLG_ERR_UNSUPPORTED, "n_clauses outside 1..SLG_MAX_VECTOR_CLAUSES");
-    if (nq == 0) return;
-    SLG_REQUIRE(qvecs && alpha && cand_count && out_count, "host arrays are NULL");
-    SLG_REQUIRE(max_cand == 0 || (cand_doc && cand_seg && cand_bm25), "candidate arrays are NULL");
-    SLG_REQUIRE(k_out == 0 || (out_doc && out_seg && out_score), "output arrays are NULL");
-    const auto S = ix->snapshot();
-    for (uint32_t c = 0; c < n_clauses; c++) {
-      uint32_t d;
-      int32_t m;
-      const slg::VecSegDev *v;
-      field_facts(*S, clause_field[c], &d, &m, &v);
-      qf += d;
-    }
-  });
-  if (rc != SLG_OK || nq == 0) return rc;
-  DevBuf dq, da, db, dcd, dcs, dcb, dcc, dod, dos, dosc, dov, doc_;
-  const size_t nc = (size_t)nq * max_cand, no = (size_t)nq * k_out, nqc = (size_t)nq * n_clauses;
-  rc = guarded([&] {
-    DeviceGuard g(ix->device);
-    hipStream_t st = ix->stream;
-    dq.alloc_pooled(&ix->pool, (size_t)nq * qf * 4);
-    da.alloc_pooled(&ix->pool, nqc * 4);
-    if (boost) db.alloc_pooled(&ix->pool, nqc * 4);
-    dcd.alloc_pooled(&ix->pool, nc * 4);
-    dcs.alloc_pooled(&ix->pool, nc * 4);
-    dcb.alloc_pooled(&ix->pool, nc * 4);
-    dcc.alloc_pooled(&ix->pool, (size_t)nq * 4);
-    dod.alloc_pooled(&ix->pool, no * 4);
-    dos.alloc_pooled(&ix->pool, no * 4);
-    dosc.alloc_pooled(&ix->pool, no * 4);
-    dov.alloc_pooled(&ix->pool, no * 4);
-    doc_.alloc_pooled(&ix->pool, (size_t)nq * 4);
-    SLG_HIP(hipMemcpyAsync(dq.p, qvecs, (size_t)nq * qf * 4, hipMemcpyHostToDevice, st));
-    SLG_HIP(hipMemcpyAsync(da.p, alpha, nqc * 4, hipMemcpyHostToDevice, st));
-    if (boost) SLG_HIP(hipMemcpyAsync(db.p, boost, nqc * 4, hipMemcpyHostToDevice, st));
-    if (nc) {
-      SLG_HIP(hipMemcpyAsync(dcd.p, cand_doc, nc * 4, hipMemcpyHostToDevice, st));
-      SLG_HIP(hipMemcpyAsync(dcs.p, cand_seg, nc * 4, hipMemcpyHostToDevice, st));
-      SLG_HIP(hipMemcpyAsync(dcb.p, cand_bm25, nc * 4, hipMemcpyHostToDevice, st));
-    }
-    SLG_HIP(hipMemcpyAsync(dcc.p, cand_count, (size_t)nq * 4, hipMemcpyHostToDevice, st));
-  });
-  if (rc != SLG_OK) return rc;
-  rc = slg_rerank_fields_batch_device(ix, nq, n_clauses, clause_field, dq.as<float>(), da.as<float>(),
-                                      boost ? db.as<float>() : nullptr, dcd.as<uint32_t>(), dcs.as<uint32_t>(),
-                                      dcb.as<float>(), dcc.as<uint32_t>(), max_cand, k_out, dod.as<uint32_t>(),
-                                      dos.as<uint32_t>(), dosc.as<float>(), dov.as<float>(), doc_.as<uint32_t>());
-  if (rc != SLG_OK) return rc;
-  return guarded([&] {
-    DeviceGuard g(ix->device);
-    hipStream_t st = ix->stream;
-    if (no) {
-      SLG_HIP(hipMemcpyAsync(out_doc, dod.p, no * 4, hipMemcpyDeviceToHost, st));
-      SLG_HIP(hipMemcpyAsync(out_seg, dos.p, no * 4, hipMemcpyDeviceToHost, st));
-      SLG_HIP(hipMemcpyAsync(out_score, dosc.p, no * 4, hipMemcpyDeviceToHost, st));
-      if (out_vec_score) SLG_HIP(hipMemcpyAsync(out_vec_score, dov.p, no * 4, hipMemcpyDeviceToHost, st));
-    }
-    SLG_HIP(hipMemcpyAsync(out_count, doc_.p, (size_t)nq * 4, hipMemcpyDeviceToHost, st));
-    SLG_HIP(hipStreamSynchronize(st));
-  });
-}
-
-int slg_rerank_multi_batch(slg_index *ix, uint32_t nq, uint32_t n_clauses, const float *qvecs,
-                           const float *alpha, const float *boost, const uint32_t *cand_doc,
-                           const uint32_t *cand_seg, const float *cand_bm25, const uint32_t *cand_count,
-                           uint32_t max_cand, uint32_t k_out, uint32_t *out_doc, uint32_t *out_seg,
-                           float *out_score, float *out_vec_score, uint32_t *out_count) {
-  int rc = guarded([&] {
-    SLG_REQUIRE(ix != nullptr, "index is NULL");
-    if (n_clauses < 1 || n_clauses > SLG_MAX_VECTOR_CLAUSES)
-      throw SlgError(SLG_ERR_UNSUPPORTED, "n_clauses outside 1..SLG_MAX_VECTOR_CLAUSES");
-    if (nq == 0) return;
-    SLG_REQUIRE(qvecs && alpha && cand_count && out_count, "host arrays are NULL");
-    SLG_REQUIRE(max_cand == 0 || (cand_doc && cand_seg && cand_bm25), "candidate arrays are NULL");
-    SLG_REQUIRE(k_out == 0 || (out_doc && out_seg && out_score), "output arrays are NULL");
-  });
-  if (rc != SLG_OK || nq == 0) return rc;
-  uint32_t dim = 0;
-  for (auto &s : ix->snapshot()->segs)
-    if (s->store->vec_dim) dim = s->store->vec_dim;
-  if (dim == 0) {
-    g_last_error = "index has no vector field";
-    g_last_code = SLG_ERR_UNSUPPORTED;
-    return SLG_ERR_UNSUPPORTED;
-  }
-  DevBuf dq, da, db, dcd, dcs, dcb, dcc, dod, dos, dosc, dov, doc_;
-  const size_t nc = (size_t)nq * max_cand, no = (size_t)nq * k_out, nqc = (size_t)nq * n_clauses;
-  rc = guarded([&] {
-    DeviceGuard g(ix->device);
-    hipStream_t st = ix->stream;
-    dq.alloc_pooled(&ix->pool, nqc * dim * 4);
-    da.alloc_pooled(&ix->pool, nqc * 4);
-    if (boost) db.alloc_pooled(&ix->pool, nqc * 4);
-    dcd.alloc_pooled(&ix->pool, nc * 4);
-    dcs.alloc_pooled(&ix->pool, nc * 4);
-    dcb.alloc_pooled(&ix->pool, nc * 4);
-    dcc.alloc_pooled(&ix->pool, (size_t)nq * 4);
-    dod.alloc_pooled(&ix->pool, no * 4);
-    dos.alloc_pooled(&ix->pool, no * 4);
-    dosc.alloc_pooled(&ix->pool, no * 4);
-    dov.alloc_pooled(&ix->pool, no * 4);
-    doc_.alloc_pooled(&ix->pool, (size_t)nq * 4);
-    SLG_HIP(hipMemcpyAsync(dq.p, qvecs, nqc * dim * 4, hipMemcpyHostToDevice, st));
-    SLG_HIP(hipMemcpyAsync(da.p, alpha, nqc * 4, hipMemcpyHostToDevice, st));
-    if (boost) SLG_HIP(hipMemcpyAsync(db.p, boost, nqc * 4, hipMemcpyHostToDevice, st));
-    if (nc) {
-      SLG_HIP(hipMemcpyAsync(dcd.p, cand_doc, nc * 4, hipMemcpyHostToDevice, st));
-      SLG_HIP(hipMemcpyAsync(dcs.p, cand_seg, nc * 4, hipMemcpyHostToDevice, st));
-      SLG_HIP(hipMemcpyAsync(dcb.p, cand_bm25, nc * 4, hipMemcpyHostToDevice, st));
-    }
-    SLG_HIP(hipMemcpyAsync(dcc.p, cand_count, (size_t)nq * 4, hipMemcpyHostToDevice, st));
-  });
-  if (rc != SLG_OK) return rc;
-  rc = slg_rerank_multi_batch_device(ix, nq, n_clauses, dq.as<float>(), da.as<float>(),
-                                     boost ? db.as<float>() : nullptr, dcd.as<uint32_t>(), dcs.as<uint32_t>(),
-                                     dcb.as<float>(), dcc.as<uint32_t>(), max_cand, k_out, dod.as<uint32_t>(),
-                                     dos.as<uint32_t>(), dosc.as<float>(), dov.as<float>(), doc_.as<uint32_t>());
-  if (rc != SLG_OK) return rc;
-  return guarded([&] {
-    DeviceGuard g(ix->device);
-    hipStream_t st = ix->stream;
-    if (no) {
-      SLG_HIP(hipMemcpyAsync(out_doc, dod.p, no * 4, hipMemcpyDeviceToHost, st));
-      SLG_HIP(hipMemcpyAsync(out_seg, dos.p, no * 4, hipMemcpyDeviceToHost, st));
-      SLG_HIP(hipMemcpyAsync(out_score, dosc.p, no * 4, hipMemcpyDeviceToHost, st));
-      if (out_vec_score) SLG_HIP(hipMemcpyAsync(out_vec_score, dov.p, no * 4, hipMemcpyDeviceToHost, st));
-    }
-    SLG_HIP(hipMemcpyAsync(out_count, doc_.p, (size_t)nq * 4, hipMemcpyDeviceToHost, st));
-    SLG_HIP(hipStreamSynchronize(st));
-  });
-}
-
-int slg_rerank_batch(slg_index *ix, uint32_t nq, const float *qvecs, const float *alpha,
-                     const uint32_t *cand_doc, const uint32_t *cand_seg, const float *cand_bm25,
-                     const uint32_t *cand_count, uint32_t max_cand, uint32_t k_out,
-                     uint32_t *out_doc, uint32_t *out_seg, float *out_score, float *out_vec_score,
-                     uint32_t *out_count) {
-  int rc = guarded([&] {
-    SLG_REQUIRE(ix != nullptr, "index is NULL");
-    if (nq == 0) return;
-    SLG_REQUIRE(qvecs && alpha && cand_count && out_count, "host arrays are NULL");
-    SLG_REQUIRE(max_cand == 0 || (cand_doc && cand_seg && cand_bm25), "candidate arrays are NULL");
-    SLG_REQUIRE(k_out == 0 || (out_doc && out_seg && out_score), "output arrays are NULL");
-  });
-  if (rc != SLG_OK || nq == 0) return rc;
-  uint32_t dim = 0;
-  for (auto &s : ix->snapshot()->segs)
-    if (s->store->vec_dim) dim = s->store->vec_dim;
-  if (dim == 0) {
-    g_last_error = "index has no vector field";
-    return SLG_ERR_UNSUPPORTED;
-  }
-  DevBuf dq, da, dcd, dcs, dcb, dcc, dod, dos, dosc, dov, doc_;
-  const size_t nc = (size_t)nq * max_cand, no = (size_t)nq * k_out;
-  rc = guarded([&] {
-    DeviceGuard g(ix->device);
-    hipStream_t st = ix->stream;
-    dq.alloc_pooled(&ix->pool, (size_t)nq * dim * 4);
-    da.alloc_pooled(&ix->pool, (size_t)nq * 4);
-    dcd.alloc_pooled(&ix->pool, nc * 4);
-    dcs.alloc_pooled(&ix->pool, nc * 4);
-    dcb.alloc_pooled(&ix->pool, nc * 4);
-    dcc.alloc_pooled(&ix->pool, (size_t)nq * 4);
-    dod.alloc_pooled(&ix->pool, no * 4);
-    dos.alloc_pooled(&ix->pool, no * 4);
-    dosc.alloc_pooled(&ix->pool, no * 4);
-    dov.alloc_pooled(&ix->pool, no * 4);
-    doc_.alloc_pooled(&ix->pool, (size_t)nq * 4);
-    SLG_HIP(hipMemcpyAsync(dq.p, qvecs, (size_t)nq * dim * 4, hipMemcpyHostToDevice, st));
-    SLG_HIP(hipMemcpyAsync(da.p, alpha, (size_t)nq * 4, hipMemcpyHostToDevice, st));
-    if (nc) {
-      SLG_HIP(hipMemcpyAsync(dcd.p, cand_doc, nc * 4, hipMemcpyHostToDevice, st));
-      SLG_HIP(hipMemcpyAsync(dcs.p, cand_seg, nc * 4, hipMemcpyHostToDevice, st));
-      SLG_HIP(hipMemcpyAsync(dcb.p, cand_bm25, nc * 4, hipMemcpyHostToDevice, st));
-    }
-    SLG_HIP(hipMemcpyAsync(dcc.p, cand_count, (size_t)nq * 4, hipMemcpyHostToDevice, st));
-  });
-  if (rc != SLG_OK) return rc;
-  rc = slg_rerank_batch_device(ix, nq, dq.as<float>(), da.as<float>(), dcd.as<uint32_t>(),
-                               dcs.as<uint32_t>(), dcb.as<float>(), dcc.as<uint32_t>(), max_cand,
-                               k_out, dod.as<uint32_t>(), dos.as<uint32_t>(), dosc.as<float>(),
-                               dov.as<float>(), doc_.as<uint32_t>());
-  if (rc != SLG_OK) return rc;
-  return guarded([&] {
-    DeviceGuard g(ix->device);
-    hipStream_t st = ix->stream;
-    if (no) {
-      SLG_HIP(hipMemcpyAsync(out_doc, dod.p, no * 4, hipMemcpyDeviceToHost, st));
-      SLG_HIP(hipMemcpyAsync(out_seg, dos.p, no * 4, hipMemcpyDeviceToHost, st));
-      SLG_HIP(hipMemcpyAsync(out_score, dosc.p, no * 4, hipMemcpyDeviceToHost, st));
-      if (out_vec_score)
-        SLG_HIP(hipMemcpyAsync(out_vec_score, dov.p, no * 4, hipMemcpyDeviceToHost, st));
-    }
-    SLG_HIP(hipMemcpyAsync(out_count, doc_.p, (size_t)nq * 4, hipMemcpyDeviceToHost, st));
-    SLG_HIP(hipStreamSynchronize(st));
-  });
 }
 
 }  // extern "C"

@@ -13,6 +13,7 @@
 
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <type_traits>
 
 #include "slg_wave.hpp"
 
@@ -878,37 +879,32 @@ inline hipError_t launch_with_lds(K kernel, const P &params, uint32_t nq, size_t
   return hipGetLastError();
 }
 
+// launch(std::integral_constant<int, KREGS>{}) for the top-k register width kregs names: every rerank
+// kernel is instantiated for KREGS 1, 2, 4, 8 and 16 here
+template <typename F>
+inline hipError_t with_kregs(int kregs, F &&launch) {
+  switch (kregs) {
+    case 1: return launch(std::integral_constant<int, 1>{});
+    case 2: return launch(std::integral_constant<int, 2>{});
+    case 4: return launch(std::integral_constant<int, 4>{});
+    case 8: return launch(std::integral_constant<int, 8>{});
+    default: return launch(std::integral_constant<int, 16>{});
+  }
+}
+
 inline hipError_t launch_rerank_multi(const RerankMultiParams &mp, int kregs, hipStream_t st) {
   const size_t lds = rerank_multi_lds_floats(mp.n_clauses, mp.base.dim, mp.base.max_cand) * 4 + 16;
-  switch (kregs) {
-    case 1: return launch_with_lds(rerank_multi_kernel<1>, mp, mp.base.nq, lds, st);
-    case 2: return launch_with_lds(rerank_multi_kernel<2>, mp, mp.base.nq, lds, st);
-    case 4: return launch_with_lds(rerank_multi_kernel<4>, mp, mp.base.nq, lds, st);
-    case 8: return launch_with_lds(rerank_multi_kernel<8>, mp, mp.base.nq, lds, st);
-    default: return launch_with_lds(rerank_multi_kernel<16>, mp, mp.base.nq, lds, st);
-  }
+  return with_kregs(kregs, [&](auto K) { return launch_with_lds(rerank_multi_kernel<K>, mp, mp.base.nq, lds, st); });
 }
 
 inline hipError_t launch_rerank_fields(const RerankFieldsParams &fp, int kregs, hipStream_t st) {
   const size_t lds = rerank_fields_lds_floats(fp.n_clauses, fp.q_floats, fp.base.max_cand) * 4 + 16;
-  switch (kregs) {
-    case 1: return launch_with_lds(rerank_fields_kernel<1>, fp, fp.base.nq, lds, st);
-    case 2: return launch_with_lds(rerank_fields_kernel<2>, fp, fp.base.nq, lds, st);
-    case 4: return launch_with_lds(rerank_fields_kernel<4>, fp, fp.base.nq, lds, st);
-    case 8: return launch_with_lds(rerank_fields_kernel<8>, fp, fp.base.nq, lds, st);
-    default: return launch_with_lds(rerank_fields_kernel<16>, fp, fp.base.nq, lds, st);
-  }
+  return with_kregs(kregs, [&](auto K) { return launch_with_lds(rerank_fields_kernel<K>, fp, fp.base.nq, lds, st); });
 }
 
 inline hipError_t launch_rerank(const RerankParams &rp, int kregs, hipStream_t st) {
   const size_t lds = (size_t)rp.max_cand * 8 + 16;
-  switch (kregs) {
-    case 1: return launch_with_lds(rerank_kernel<1>, rp, rp.nq, lds, st);
-    case 2: return launch_with_lds(rerank_kernel<2>, rp, rp.nq, lds, st);
-    case 4: return launch_with_lds(rerank_kernel<4>, rp, rp.nq, lds, st);
-    case 8: return launch_with_lds(rerank_kernel<8>, rp, rp.nq, lds, st);
-    default: return launch_with_lds(rerank_kernel<16>, rp, rp.nq, lds, st);
-  }
+  return with_kregs(kregs, [&](auto K) { return launch_with_lds(rerank_kernel<K>, rp, rp.nq, lds, st); });
 }
 
 }  // namespace slg

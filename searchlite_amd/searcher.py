@@ -24,6 +24,11 @@ def _ptr(a: Optional[np.ndarray]):
     return None if a is None else a.ctypes.data
 
 
+def _f32(a, shape) -> Optional[np.ndarray]:
+    """A contiguous f32 array of `shape` (a scalar or a row broadcasts); None stays None."""
+    return None if a is None else np.ascontiguousarray(np.broadcast_to(np.asarray(a, dtype=np.float32), shape))
+
+
 def device_count() -> int:
     n = N.load().slg_device_count()
     if n < 0:
@@ -352,26 +357,28 @@ class GpuIndex:
         return [(int(s[0, i]), int(d[0, i]), float(sc[0, i])) for i in range(n)]
 
     # -- rerank ----------------------------------------------------------------------
-    def rerank_batch(self, qvecs, alpha, cand_doc, cand_seg, cand_bm25, cand_count, k_out: int):
-        """gpu::rerank slot (gpu/rerank.rs:3): vector similarity + alpha blend + top-k_out."""
-        qvecs = np.ascontiguousarray(qvecs, dtype=np.float32)
-        nq = qvecs.shape[0]
-        alpha = np.ascontiguousarray(np.broadcast_to(np.asarray(alpha, dtype=np.float32), (nq,)))
+    def _rerank(self, entry, nq: int, lead, cand_doc, cand_seg, cand_bm25, cand_count, k_out: int):
+        """One host-array rerank entry: entry(index, nq, *lead, candidates, max_cand, k_out, outputs).
+        -> (out_doc, out_seg, out_score, out_vec, out_count)."""
         cand_doc = np.ascontiguousarray(cand_doc, dtype=np.uint32).reshape(nq, -1)
         max_cand = cand_doc.shape[1]
         cand_seg = np.ascontiguousarray(cand_seg, dtype=np.uint32).reshape(nq, max_cand)
         cand_bm25 = np.ascontiguousarray(cand_bm25, dtype=np.float32).reshape(nq, max_cand)
         cand_count = np.ascontiguousarray(cand_count, dtype=np.uint32)
-        out_doc = np.zeros((nq, k_out), dtype=np.uint32)
-        out_seg = np.zeros((nq, k_out), dtype=np.uint32)
-        out_score = np.zeros((nq, k_out), dtype=np.float32)
-        out_vec = np.zeros((nq, k_out), dtype=np.float32)
-        out_count = np.zeros(nq, dtype=np.uint32)
-        N.check(self._lib.slg_rerank_batch(self._h, nq, _ptr(qvecs), _ptr(alpha), _ptr(cand_doc),
-                                           _ptr(cand_seg), _ptr(cand_bm25), _ptr(cand_count),
-                                           max_cand, k_out, _ptr(out_doc), _ptr(out_seg),
-                                           _ptr(out_score), _ptr(out_vec), _ptr(out_count)))
-        return out_doc, out_seg, out_score, out_vec, out_count
+        out = (np.zeros((nq, k_out), dtype=np.uint32), np.zeros((nq, k_out), dtype=np.uint32),
+               np.zeros((nq, k_out), dtype=np.float32), np.zeros((nq, k_out), dtype=np.float32),
+               np.zeros(nq, dtype=np.uint32))
+        N.check(entry(self._h, nq, *lead, _ptr(cand_doc), _ptr(cand_seg), _ptr(cand_bm25), _ptr(cand_count),
+                      max_cand, k_out, *map(_ptr, out)))
+        return out
+
+    def rerank_batch(self, qvecs, alpha, cand_doc, cand_seg, cand_bm25, cand_count, k_out: int):
+        """gpu::rerank slot (gpu/rerank.rs:3): vector similarity + alpha blend + top-k_out."""
+        qvecs = np.ascontiguousarray(qvecs, dtype=np.float32)
+        nq = qvecs.shape[0]
+        alpha = _f32(alpha, (nq,))
+        return self._rerank(self._lib.slg_rerank_batch, nq, (_ptr(qvecs), _ptr(alpha)),
+                            cand_doc, cand_seg, cand_bm25, cand_count, k_out)
 
     def rerank_multi_batch(self, qvecs, alpha, cand_doc, cand_seg, cand_bm25, cand_count, k_out: int,
                            boost=None):
@@ -379,24 +386,9 @@ class GpuIndex:
         qvecs [nq, n_clauses, dim], alpha / boost [nq, n_clauses]."""
         qvecs = np.ascontiguousarray(qvecs, dtype=np.float32)
         nq, nc = qvecs.shape[0], qvecs.shape[1]
-        alpha = np.ascontiguousarray(np.broadcast_to(np.asarray(alpha, dtype=np.float32), (nq, nc)))
-        bst = None if boost is None else \
-            np.ascontiguousarray(np.broadcast_to(np.asarray(boost, dtype=np.float32), (nq, nc)))
-        cand_doc = np.ascontiguousarray(cand_doc, dtype=np.uint32).reshape(nq, -1)
-        max_cand = cand_doc.shape[1]
-        cand_seg = np.ascontiguousarray(cand_seg, dtype=np.uint32).reshape(nq, max_cand)
-        cand_bm25 = np.ascontiguousarray(cand_bm25, dtype=np.float32).reshape(nq, max_cand)
-        cand_count = np.ascontiguousarray(cand_count, dtype=np.uint32)
-        out_doc = np.zeros((nq, k_out), dtype=np.uint32)
-        out_seg = np.zeros((nq, k_out), dtype=np.uint32)
-        out_score = np.zeros((nq, k_out), dtype=np.float32)
-        out_vec = np.zeros((nq, k_out), dtype=np.float32)
-        out_count = np.zeros(nq, dtype=np.uint32)
-        N.check(self._lib.slg_rerank_multi_batch(
-            self._h, nq, nc, _ptr(qvecs), _ptr(alpha), _ptr(bst), _ptr(cand_doc), _ptr(cand_seg),
-            _ptr(cand_bm25), _ptr(cand_count), max_cand, k_out, _ptr(out_doc), _ptr(out_seg),
-            _ptr(out_score), _ptr(out_vec), _ptr(out_count)))
-        return out_doc, out_seg, out_score, out_vec, out_count
+        alpha, bst = _f32(alpha, (nq, nc)), _f32(boost, (nq, nc))
+        return self._rerank(self._lib.slg_rerank_multi_batch, nq, (nc, _ptr(qvecs), _ptr(alpha), _ptr(bst)),
+                            cand_doc, cand_seg, cand_bm25, cand_count, k_out)
 
     def add_vector_field(self, per_segment) -> int:
         """Stage one more vector field (vectors/mod.rs:10-17: a VectorStore per field).  per_segment[s]
@@ -428,24 +420,10 @@ class GpuIndex:
         nc = len(cf)
         qvecs = np.ascontiguousarray(qvecs, dtype=np.float32)
         nq = qvecs.shape[0]
-        alpha = np.ascontiguousarray(np.broadcast_to(np.asarray(alpha, dtype=np.float32), (nq, nc)))
-        bst = None if boost is None else \
-            np.ascontiguousarray(np.broadcast_to(np.asarray(boost, dtype=np.float32), (nq, nc)))
-        cand_doc = np.ascontiguousarray(cand_doc, dtype=np.uint32).reshape(nq, -1)
-        max_cand = cand_doc.shape[1]
-        cand_seg = np.ascontiguousarray(cand_seg, dtype=np.uint32).reshape(nq, max_cand)
-        cand_bm25 = np.ascontiguousarray(cand_bm25, dtype=np.float32).reshape(nq, max_cand)
-        cand_count = np.ascontiguousarray(cand_count, dtype=np.uint32)
-        out_doc = np.zeros((nq, k_out), dtype=np.uint32)
-        out_seg = np.zeros((nq, k_out), dtype=np.uint32)
-        out_score = np.zeros((nq, k_out), dtype=np.float32)
-        out_vec = np.zeros((nq, k_out), dtype=np.float32)
-        out_count = np.zeros(nq, dtype=np.uint32)
-        N.check(self._lib.slg_rerank_fields_batch(
-            self._h, nq, nc, _ptr(cf), _ptr(qvecs), _ptr(alpha), _ptr(bst), _ptr(cand_doc), _ptr(cand_seg),
-            _ptr(cand_bm25), _ptr(cand_count), max_cand, k_out, _ptr(out_doc), _ptr(out_seg),
-            _ptr(out_score), _ptr(out_vec), _ptr(out_count)))
-        return out_doc, out_seg, out_score, out_vec, out_count
+        alpha, bst = _f32(alpha, (nq, nc)), _f32(boost, (nq, nc))
+        return self._rerank(self._lib.slg_rerank_fields_batch, nq,
+                            (nc, _ptr(cf), _ptr(qvecs), _ptr(alpha), _ptr(bst)),
+                            cand_doc, cand_seg, cand_bm25, cand_count, k_out)
 
     def rerank_batch_device(self, nq, d_qvecs, d_alpha, d_cand_doc, d_cand_seg, d_cand_bm25,
                             d_cand_count, max_cand, k_out, d_out_doc, d_out_seg, d_out_score,

@@ -387,3 +387,58 @@ def test_rerank_multi_limits():
             ix.rerank_multi_batch(np.zeros((1, 9, 8), np.float32), 0.5, c, c, np.zeros((1, 4), np.float32),
                                   np.array([4], np.uint32), 2)
         assert e.value.code == N.ERR_UNSUPPORTED  # > MAX_VECTOR_CLAUSES (api/reader.rs:134)
+
+
+def _host_rerank(ix, entry, q, cand, bm, cnt, k_out):
+    """One clause over vector field 0 through one host entry: the arithmetic of oracle.rerank on each."""
+    z = np.zeros_like(cand)
+    if entry == "slg_rerank_batch":
+        return ix.rerank_batch(q, 0.5, cand, z, bm, cnt, k_out)
+    if entry == "slg_rerank_multi_batch":  # a boost of 1.0 takes the multi-clause kernel
+        return ix.rerank_multi_batch(q[:, None, :], 0.5, cand, z, bm, cnt, k_out,
+                                     boost=np.ones((len(q), 1), np.float32))
+    return ix.rerank_fields_batch([0], q, 0.5, cand, z, bm, cnt, k_out)
+
+
+@pytest.mark.parametrize("entry", ["slg_rerank_batch", "slg_rerank_multi_batch", "slg_rerank_fields_batch"])
+def test_rerank_host_entry_errors(oracle, entry):
+    """A host entry makes its device form's checks before it stages anything: an index without a vector
+    field, and k_out > SLG_MAX_RERANK_K (with nq == 0 too), are SLG_ERR_UNSUPPORTED, and
+    slg_last_error_code() reports that code after a call that failed with another one.  The index
+    reranks correctly afterwards."""
+    import searchlite_amd as sa
+    from searchlite_amd import _native as N
+    from searchlite_amd import corpus
+    from searchlite_amd.segment import SegmentBuilder
+    rng = np.random.default_rng(9)
+    n, dim, ncand, nq, k_out = 600, 64, 120, 3, 10
+    vals = corpus.unit_vectors(n, dim, seed=21)
+    q = corpus.unit_vectors(nq, dim, seed=22)
+    cand = np.stack([rng.choice(n, size=ncand, replace=False) for _ in range(nq)]).astype(np.uint32)
+    bm = (rng.random((nq, ncand)) * 10).astype(np.float32)
+    cnt = np.full(nq, ncand, np.uint32)
+    cf = np.zeros(1, np.uint32)
+    lead = {"slg_rerank_batch": (None, None), "slg_rerank_multi_batch": (1, None, None, None),
+            "slg_rerank_fields_batch": (1, cf.ctypes.data, None, None, None)}[entry]
+
+    def expect_unsupported(call):
+        with pytest.raises(N.SlgError) as e:  # first a call that fails otherwise: unknown field id
+            ix.rerank_fields_batch([7], q, 0.5, cand, cand, bm, cnt, k_out)
+        assert e.value.code == N.ERR_INVALID and N.last_error_code() == N.ERR_INVALID
+        with pytest.raises(N.SlgError) as e:
+            call()
+        assert e.value.code == N.ERR_UNSUPPORTED and N.last_error_code() == N.ERR_UNSUPPORTED
+
+    b = SegmentBuilder(["body"])
+    b.add_document("a", {"body": "rust"})
+    with sa.GpuIndex([b.build()]) as ix:  # no vector field
+        expect_unsupported(lambda: _host_rerank(ix, entry, q, cand, bm, cnt, k_out))
+    with sa.GpuIndex([_segment_with_vectors(n, np.arange(n, dtype=np.uint32), vals, 0)]) as ix:
+        expect_unsupported(lambda: _host_rerank(ix, entry, q, cand, bm, cnt, N.MAX_RERANK_K + 1))
+        # nq == 0: nothing is read past the k_out check
+        expect_unsupported(lambda: N.check(getattr(ix._lib, entry)(
+            ix._h, 0, *lead, None, None, None, None, 0, N.MAX_RERANK_K + 1, None, None, None, None, None)))
+        got = _host_rerank(ix, entry, q, cand, bm, cnt, k_out)
+    want = [oracle.rerank(0, np.arange(n, dtype=np.uint32), vals, q[i], 0.5, cand[i], bm[i], k_out)
+            for i in range(nq)]
+    _check(got, [w[0] for w in want], [w[1] for w in want], [w[2] for w in want], entry)

@@ -735,6 +735,11 @@ void finish_state(slg_index *ix, IndexState &s) {
   s.device = ix->device;
   std::vector<slg::SegDev> sd(n_segs);
   std::vector<slg::VecSegDev> vd(n_segs);
+  // a segment without vectors takes the field's metric (the last one's, as field_facts reports it): its
+  // docs score missing_vector_score of the field's metric, not of the descriptor's unchecked vec_metric
+  int32_t field_metric = 0;
+  for (size_t i = 0; i < n_segs; i++)
+    if (s.segs[i]->store->vec_dim) field_metric = s.segs[i]->store->vec_metric;
   for (size_t i = 0; i < n_segs; i++) {
     const SegHost &sh = *s.segs[i];
     sd[i].docs = sh.store->d_docs.as<uint32_t>();
@@ -748,7 +753,7 @@ void finish_state(slg_index *ix, IndexState &s) {
     vd[i].values = sh.store->d_vec_values.as<float>();
     vd[i].n_docs = sh.n_docs;
     vd[i].dim = sh.store->vec_dim;
-    vd[i].metric = sh.store->vec_metric;
+    vd[i].metric = sh.store->vec_dim ? sh.store->vec_metric : field_metric;
     vd[i].pad = 0;
   }
   s.d_segs.alloc(std::max<size_t>(n_segs, 1) * sizeof(slg::SegDev), &ix->pool);
@@ -2469,6 +2474,7 @@ bool rerank_prepare(slg_index *ix, bool fields, uint32_t n_clauses, const uint32
   }
   int32_t metric;
   field_facts(S, 0, &fp.base.dim, &metric, &fp.base.vsegs, rc->shape == RerankShape::One);
+  fp.base.metric = metric;
   fp.q_floats = n_clauses * fp.base.dim;
   if (rc->shape == RerankShape::One) {
     if (io.max_cand > slg::kRerankMaxCand)

@@ -19,6 +19,9 @@
 
 namespace slg {
 
+// A segment without vectors in the field has dim 0 and the field's metric.  A candidate whose segment
+// is >= n_segs, or whose doc is >= its segment's n_docs, is a candidate without a vector: it scores
+// missing_vector_score of the field's metric (api/reader.rs:217-223).
 struct VecSegDev {
   const uint32_t *offsets;  // [n_docs] row index or 0xFFFFFFFF
   const float *values;      // [rows * dim]
@@ -41,6 +44,7 @@ struct RerankParams {
   float *out_score, *out_vec;
   uint32_t *out_count;
   uint32_t nq;
+  int32_t metric;  // the field's metric: candidates whose segment is >= n_segs (rerank_kernel)
 };
 
 constexpr uint32_t kRerankMaxCand = 8192;  // blended + vec scores staged in LDS
@@ -150,7 +154,7 @@ __device__ __forceinline__ void rerank_finish(const float sum, const bool have_r
       blended = vs;
     else
       blended = alpha * bm + (1.0f - alpha) * vs;
-    s_blend[c] = blended;
+    s_blend[c] = blended == 0.0f ? 0.0f : blended;  // 0.0 + blended (api/reader.rs:232,249): -0.0 -> +0.0, NaN bits kept
     s_vec[c] = vs;
   }
 }
@@ -210,7 +214,7 @@ __device__ __forceinline__ void rerank_scan_rows(const RerankParams &p, const ui
       const gword_t optr = doc_ok ? (gword_t)(vd.offsets + doc) : (gword_t)p.cand_count;  // (any readable word)
       const uint32_t off = *optr;
       haveN[u] = doc_ok && off != 0xFFFFFFFFu;
-      metN[u] = seg_ok ? vd.metric : 0;
+      metN[u] = seg_ok ? vd.metric : p.metric;
       rowN[u] = (grow_t)(haveN[u] ? vd.values + (size_t)off * dim : qv);
     }
   };
@@ -392,7 +396,7 @@ __global__ void __launch_bounds__(256) rerank_kernel(RerankParams p) {
 #pragma unroll
     for (int u = 0; u < U; u++) {
       row[u] = nullptr;
-      metric[u] = 0;
+      metric[u] = p.metric;
       acc[u] = 0.0f;
       const uint32_t c = c0 + u;
       if (c < n) {
@@ -465,7 +469,7 @@ __global__ void __launch_bounds__(256) rerank_kernel(RerankParams p) {
           blended = vs;
         else
           blended = alpha * bm + (1.0f - alpha) * vs;  // vectors/mod.rs:128
-        s_blend[c] = blended;
+        s_blend[c] = blended == 0.0f ? 0.0f : blended;  // (as rerank_finish)
         s_vec[c] = vs;
       }
     }

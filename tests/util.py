@@ -336,3 +336,236 @@ def topk_family(name):
     return dict(segs=segs, offs=np.array(offs, np.uint32), terms=np.array(terms, np.uint32),
                 w=np.array(w, np.float32), plans=plans, q_filter=q_filter, masks=masks, tuning=tuning,
                 strategy=1)   # Wand (pruning-classified where pruning allows it)
+
+
+# ---- rerank reference (tests/test_rerank_bound.py, tests/test_gpu_rerank_widths.py) ---------------------
+# A rerank case: `fields` = [dict(metric, dim, segs=[(offsets u32[n_docs], values f32[rows, dim]) or None
+# per segment])]; a query `q` = dict(cf = field of each clause, qv = [f32[dim] per clause], alpha f32[nc],
+# boost f32[nc] or None, seg / doc u32[n], bm f32[n]).  kind: "one" (rerank_kernel: one clause over
+# field 0, no boost), "multi" (rerank_multi_kernel: clauses over field 0) or "fields"
+# (rerank_fields_kernel).  A candidate has a vector in clause c iff its segment is < n_segs, has the
+# field, and doc < that segment's n_docs with offsets[doc] != NO_VECTOR.
+NO_VECTOR = 0xFFFFFFFF
+F32_MAX = float(np.finfo(np.float32).max)
+F32_MIN = -F32_MAX
+U_F32 = 2.0 ** -24   # unit roundoff of f32
+ETA_F32 = 2.0 ** -149  # absolute error of one f32 operation with a subnormal result
+
+
+def _gamma(n):
+    """gamma_n = n u / (1 - n u) (Higham, Accuracy and Stability, 3.1)."""
+    return n * U_F32 / (1.0 - n * U_F32)
+
+
+def _rnd(lo, hi):
+    """[lo, hi] (float64 arrays) widened by the rounding of one f32 operation whose exact result lies in
+    it: relative u, absolute ETA for subnormals; past F32_MAX the result may round to +-inf."""
+    lo, hi = np.asarray(lo, np.float64), np.asarray(hi, np.float64)
+    with np.errstate(invalid="ignore"):
+        lo2 = np.where(np.isinf(lo), lo, lo - U_F32 * np.abs(lo) - ETA_F32)
+        hi2 = np.where(np.isinf(hi), hi, hi + U_F32 * np.abs(hi) + ETA_F32)
+    lo2 = np.where(lo2 < -F32_MAX, -np.inf, np.minimum(lo2, F32_MAX))
+    hi2 = np.where(hi2 > F32_MAX, np.inf, np.maximum(hi2, -F32_MAX))
+    return lo2, hi2
+
+
+def _mul(a, b):
+    with np.errstate(invalid="ignore", over="ignore"):
+        c = np.stack([a[0] * b[0], a[0] * b[1], a[1] * b[0], a[1] * b[1]])
+    return _rnd(np.fmin.reduce(c), np.fmax.reduce(c))
+
+
+def _add(a, b):
+    with np.errstate(invalid="ignore", over="ignore"):
+        return _rnd(a[0] + b[0], a[1] + b[1])
+
+
+def rerank_row(field, seg, doc):
+    """The row of (seg, doc) in a field, or None (no vector)."""
+    segs = field["segs"]
+    if seg >= len(segs) or segs[seg] is None:
+        return None
+    offs, vals = segs[seg]
+    if doc >= len(offs) or offs[doc] == NO_VECTOR:
+        return None
+    return vals[offs[doc]]
+
+
+def missing_score(metric):
+    return -1.0 if metric == 0 else F32_MIN
+
+
+def similarity_interval(metric, qv, rows, l2_identity=False):
+    """[lo, hi] (float64 arrays over the rows) holding every f32 evaluation of metric_similarity(qv, row)
+    (vectors/mod.rs:98-120), whatever the order of its sums.
+
+    Cosine: an f32 inner product of n terms, in any summation order, differs from the exact sum of the
+    exact products by at most gamma_n * sum |q_i x_i| (Higham 3.1: each product is rounded once, each
+    term takes part in at most n - 1 rounded additions; adding the exact zeros of masked lanes rounds
+    nothing), + n ETA for subnormal results.  A NaN sum scores 0 (vectors/mod.rs:112-116); an infinite
+    one is exact.
+    L2: sum (q_i - x_i)^2: each difference and square is rounded once more, so gamma_{n+2} * sum d_i^2
+    (+ n ETA).  The matrix-core identity (l2_identity: rerank_multi_kernel with >= 3 L2 clauses and
+    dim % 16 == 0) computes |q|^2 + |x|^2 - 2 q.x: three inner products of n terms, one addition and one
+    subtraction, so gamma_{n+2} * (|q|^2 + |x|^2 + 2 sum |q_i x_i|); a near-duplicate pair it recomputes
+    as the plain sum, so both bounds are added.  A sum past F32_MAX may be +inf (with nonnegative terms
+    it is in every order once the exact sum is past it); the square root and the sign are one more
+    rounding (relative u)."""
+    q = np.asarray(qv, dtype=np.float64)
+    x = np.asarray(rows, dtype=np.float64).reshape(-1, len(q))
+    n = len(q)
+    with np.errstate(all="ignore"):
+        if metric == 0:
+            p = x * q
+            s = p.sum(axis=1)
+            e = _gamma(n) * np.abs(p).sum(axis=1) + n * ETA_F32
+            lo = np.where(s - e < -F32_MAX, -np.inf, s - e)
+            hi = np.where(s + e > F32_MAX, np.inf, s + e)
+            exact = np.isinf(s)
+            lo, hi = np.where(exact, s, lo), np.where(exact, s, hi)
+            nan = np.isnan(s)
+            return np.where(nan, 0.0, lo), np.where(nan, 0.0, hi)
+        d = q - x
+        s = (d * d).sum(axis=1)
+        assert not np.isnan(s).any(), "L2 NaN is out of scope"
+        e = _gamma(n + 2) * s + n * ETA_F32
+        if l2_identity:
+            e = e + _gamma(n + 2) * ((q * q).sum() + (x * x).sum(axis=1) + 2 * np.abs(x * q).sum(axis=1))
+        e = np.where(np.isinf(s), 0.0, e)
+        slo, shi = np.maximum(s - e, 0.0), s + e
+        shi = np.where(shi > F32_MAX, np.inf, shi)
+        slo = np.where(slo > F32_MAX, np.inf, slo)
+        return -np.sqrt(shi) * (1 + U_F32), -np.sqrt(slo) * (1 - U_F32)
+
+
+def rerank_exact(fields, q, kind, l2_identity=False):
+    """Per candidate, in float64: the interval of the blended score and of the reported vector score that
+    every f32 evaluation of compute_hybrid_score (api/reader.rs:225-254) lies in.  The similarity carries
+    the bound of similarity_interval; the boost, the blend alpha * bm + (1 - alpha) * vs, the clause sums
+    (in clause order, as the reference and the kernels add them) and the division by the clause count
+    each add one f32 rounding (_rnd) of the interval they produce.  -> (score_lo, score_hi, vec_lo,
+    vec_hi), float64[n] each; an exact value has lo == hi."""
+    n = len(q["doc"])
+    nc = len(q["cf"])
+    alpha = np.asarray(q["alpha"], np.float32).astype(np.float64).reshape(-1)
+    boost = None if q.get("boost") is None else np.asarray(q["boost"], np.float32).astype(np.float64).reshape(-1)
+    bm = np.asarray(q["bm"], np.float32).astype(np.float64)
+    assert not np.isnan(bm).any(), "NaN bm25 values are checked bit for bit, not here"
+    bsum = vsum = None
+    has_any = np.zeros(n, bool)
+    for c in range(nc):
+        f = fields[q["cf"][c]]
+        rows = [rerank_row(f, int(sg), int(d)) for sg, d in zip(q["seg"], q["doc"])]
+        has = np.array([r is not None for r in rows], bool)
+        has_any |= has
+        miss = missing_score(f["metric"])
+        vs = (np.full(n, miss), np.full(n, miss))
+        if has.any():
+            lo, hi = similarity_interval(f["metric"], q["qv"][c], np.stack([r for r in rows if r is not None]),
+                                         l2_identity)
+            if boost is not None:
+                assert boost[c] > 0
+                lo, hi = _mul((lo, hi), (boost[c], boost[c]))
+            vs[0][has], vs[1][has] = lo, hi
+            part = (np.where(has, vs[0], 0.0), np.where(has, vs[1], 0.0))
+            vsum = part if vsum is None else _add(vsum, part)
+        a = alpha[c]
+        if a >= 1.0:
+            bl = (bm, bm)
+        elif a <= 0.0:
+            bl = vs
+        else:
+            w = _rnd(1.0 - a, 1.0 - a)
+            bl = _add(_mul((a, a), (bm, bm)), _mul(w, vs))
+        bsum = bl if bsum is None else _add(bsum, bl)
+    if kind != "one":
+        lo, hi = bsum[0] / nc, bsum[1] / nc
+        bsum = (lo, hi) if nc & (nc - 1) == 0 else _rnd(lo, hi)
+    m0 = missing_score(fields[q["cf"][0]]["metric"])
+    if vsum is None:
+        vsum = (np.zeros(n), np.zeros(n))
+    vlo, vhi = np.where(has_any, vsum[0], m0), np.where(has_any, vsum[1], m0)
+    return np.asarray(bsum[0], np.float64), np.asarray(bsum[1], np.float64), vlo, vhi
+
+
+def _f32_key(x):
+    """f32::total_cmp key of an f32 (as numpy int64)."""
+    b = np.asarray(x, np.float32).view(np.int32).astype(np.int64)
+    return np.where(b < 0, b ^ 0x7FFFFFFF, b)
+
+
+def check_rerank_result(fields, q, kind, k_out, got, l2_identity=False, what=""):
+    """One query's kernel output got = (doc, seg, score, vec, count) (the query's row of each array) against
+    the float64 intervals of rerank_exact: count = min(candidates, k_out); strict (score by total_cmp
+    desc, seg, doc) order; every output a distinct real candidate; every score and vector score inside
+    its interval; and no candidate left out whose interval lies above the k-th output (equal exact
+    scores: the (seg, doc) order decides).  Near-ties need no absolute tolerance."""
+    gd, gs, gsc, gv, gc = got
+    n = len(q["doc"])
+    slo, shi, vlo, vhi = rerank_exact(fields, q, kind, l2_identity)
+    want_n = min(n, k_out)
+    assert int(gc) == want_n, f"{what}: count {int(gc)} != {want_n}"
+    gd, gs = np.asarray(gd[:want_n], np.int64), np.asarray(gs[:want_n], np.int64)
+    gsc, gv = np.asarray(gsc[:want_n], np.float32), np.asarray(gv[:want_n], np.float32)
+    key = _f32_key(gsc)
+    for j in range(1, want_n):
+        assert (key[j - 1], -gs[j - 1], -gd[j - 1]) > (key[j], -gs[j], -gd[j]), f"{what}: order at {j}"
+    index = {}
+    for i in range(n):
+        index.setdefault((int(q["seg"][i]), int(q["doc"][i])), i)
+    used = set()
+    for j in range(want_n):
+        i = index.get((int(gs[j]), int(gd[j])))
+        assert i is not None, f"{what}: output {j} ({gs[j]}, {gd[j]}) is not a candidate"
+        assert i not in used, f"{what}: output {j} ({gs[j]}, {gd[j]}) appears twice"
+        used.add(i)
+        s, v = float(gsc[j]), float(gv[j])
+        assert slo[i] <= s <= shi[i], f"{what}: score of ({gs[j]}, {gd[j]}) {s!r} outside [{slo[i]!r}, {shi[i]!r}]"
+        assert vlo[i] <= v <= vhi[i], f"{what}: vec score of ({gs[j]}, {gd[j]}) {v!r} outside [{vlo[i]!r}, {vhi[i]!r}]"
+    if want_n == 0 or want_n == n:
+        return
+    ks, kseg, kdoc = float(gsc[-1]), int(gs[-1]), int(gd[-1])
+    for i in range(n):
+        if i in used:
+            continue
+        sk = (int(q["seg"][i]), int(q["doc"][i]))
+        assert not (slo[i] > ks or (slo[i] == shi[i] == ks and sk < (kseg, kdoc))), \
+            f"{what}: candidate {sk} (score >= {slo[i]!r}) left out below the k-th output {ks!r}"
+
+
+def oracle_rerank_segments(oracle, fields, q, kind, k_out):
+    """The oracle on candidates from several segments: each field's segments become one store with
+    combined ids seg * N + doc (N above every segment's n_docs and every candidate doc, so the (seg, doc)
+    order is kept); docs past their segment's n_docs, segments >= n_segs and segments without the field
+    map to NO_VECTOR.  -> (doc, seg, score, vec) arrays of the top min(n, k_out)."""
+    doc = np.asarray(q["doc"], np.int64)
+    seg = np.asarray(q["seg"], np.int64)
+    n_segs = len(fields[0]["segs"])
+    N = 1 + max([int(doc.max()) if len(doc) else 0] +
+                [len(s[0]) for f in fields for s in f["segs"] if s is not None])
+    assert (max(n_segs, int(seg.max()) + 1 if len(seg) else 0)) * N < 2 ** 32
+    comb = []
+    for f in fields:
+        offs = np.full(n_segs * N, NO_VECTOR, np.uint32)
+        vals, base = [np.zeros((0, f["dim"]), np.float32)], 0
+        for s, sd in enumerate(f["segs"]):
+            if sd is None:
+                continue
+            o, v = sd
+            offs[s * N:s * N + len(o)] = np.where(o == NO_VECTOR, NO_VECTOR, o.astype(np.int64) + base)
+            vals.append(v)
+            base += len(v)
+        comb.append((f["metric"], offs, np.concatenate(vals)))
+    cid = (seg * N + doc).astype(np.uint32)
+    if kind == "one":
+        m, offs, vals = comb[0]
+        d, s_, v = oracle.rerank(m, offs, vals, q["qv"][0], float(np.float32(q["alpha"][0])), cid, q["bm"], k_out)
+    elif kind == "multi":
+        m, offs, vals = comb[0]
+        d, s_, v = oracle.rerank_multi(m, offs, vals, np.stack(q["qv"]), q["alpha"], cid, q["bm"], k_out,
+                                       boost=q.get("boost"))
+    else:
+        d, s_, v = oracle.rerank_fields(comb, list(q["cf"]), q["qv"], q["alpha"], cid, q["bm"], k_out,
+                                        boost=q.get("boost"))
+    d = np.asarray(d, np.int64)
+    return (d % N).astype(np.uint32), (d // N).astype(np.uint32), s_, v

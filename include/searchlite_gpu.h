@@ -44,6 +44,7 @@ extern "C" {
 #define SLG_MAX_RERANK_K 1024u       /* largest k_out of slg_rerank_*: the reference's own cap on a vector
                                         clause's k (MAX_VECTOR_K, api/reader.rs:136) */
 #define SLG_MAX_VECTOR_CLAUSES 8u    /* MAX_VECTOR_CLAUSES, api/reader.rs:134 */
+#define SLG_MAX_VECTOR_CANDIDATES 10000u  /* MAX_VECTOR_CANDIDATE_SIZE, api/reader.rs:138 */
 #define SLG_BLOCK_SIZE 128u          /* index/postings.rs:11 DEFAULT_BLOCK_SIZE */
 
 /* return codes (searchlite-ffi/src/lib.rs returns NULL / -1..-5 / 0) */
@@ -690,6 +691,37 @@ int slg_rerank_multi_batch_device(slg_index *index, uint32_t nq, uint32_t n_clau
                                   const uint32_t *d_cand_count, uint32_t max_cand, uint32_t k_out,
                                   uint32_t *d_out_doc, uint32_t *d_out_seg, float *d_out_score,
                                   float *d_out_vec_score, uint32_t *d_out_count);
+
+
+/*
+ * Exact vector-only search over every stored vector (search_vector_only, api/reader.rs:2187-2330).
+ * Per query and clause c (field clause_field[c], host array; qvecs[q] = the clause vectors of query q
+ * one after another, cosine vectors normalised by the caller): every doc that has a vector in the
+ * field, is not deleted and passes the query's filter scores metric_similarity * boost[q][c]
+ * (cosine: dot, NaN -> 0; L2: -sqrt(sum (x - y)^2)); the best cand_size by (score desc, segment asc,
+ * doc asc) form the clause's list.  This is collect_vector_maps (:2379-2469) with the per-segment HNSW
+ * search replaced by an exact scan, and with the filter applied before the truncation.  The docs of
+ * any clause's list form the union; each scores compute_hybrid_score at bm25 = 0 (:225-254): a clause
+ * whose list lacks the doc contributes its metric's missing-vector score, also when the doc has a
+ * vector there.  Outputs [nq][k_out]: the top k_out by (final desc, segment asc, doc asc), the vector
+ * score (sum of the clause scores found), out_count[q] = rows filled, out_total[q] = the union size.
+ * alpha / boost [nq][n_clauses] (boost NULL = 1.0); q_filter[q] < 0 or a NULL array = no filter, else
+ * a filter id of slg_index_add_filter*.  n_clauses outside 1..SLG_MAX_VECTOR_CLAUSES, cand_size
+ * outside 1..SLG_MAX_VECTOR_CANDIDATES or k_out > SLG_MAX_K: SLG_ERR_UNSUPPORTED; a NULL or
+ * inconsistent argument: SLG_ERR_INVALID, all before any device work.  The _device form takes device
+ * arrays (clause_field stays on the host) and is asynchronous on the index stream; it cannot check
+ * q_filter ids, and an id that names no filter registered for every segment matches nothing.
+ */
+int slg_vector_search_batch(slg_index *index, uint32_t nq, uint32_t n_clauses, const uint32_t *clause_field,
+                            const float *qvecs, const float *alpha, const float *boost,
+                            const int32_t *q_filter, uint32_t cand_size, uint32_t k_out,
+                            uint32_t *out_doc, uint32_t *out_seg, float *out_score, float *out_vec_score,
+                            uint32_t *out_count, uint64_t *out_total);
+int slg_vector_search_batch_device(slg_index *index, uint32_t nq, uint32_t n_clauses,
+                                   const uint32_t *clause_field, const float *d_qvecs, const float *d_alpha,
+                                   const float *d_boost, const int32_t *d_q_filter, uint32_t cand_size,
+                                   uint32_t k_out, uint32_t *d_out_doc, uint32_t *d_out_seg, float *d_out_score,
+                                   float *d_out_vec_score, uint32_t *d_out_count, uint64_t *d_out_total);
 
 #ifdef __cplusplus
 }

@@ -195,6 +195,14 @@ extern "C" {
         d_alpha: *const c_float, d_boost: *const c_float, d_cand_doc: *const u32, d_cand_seg: *const u32,
         d_cand_bm25: *const c_float, d_cand_count: *const u32, max_cand: u32, k_out: u32, d_out_doc: *mut u32,
         d_out_seg: *mut u32, d_out_score: *mut c_float, d_out_vec_score: *mut c_float, d_out_count: *mut u32) -> c_int;
+    pub fn slg_vector_search_batch(index: *mut slg_index, nq: u32, n_clauses: u32, clause_field: *const u32,
+        qvecs: *const c_float, alpha: *const c_float, boost: *const c_float, q_filter: *const i32, cand_size: u32,
+        k_out: u32, out_doc: *mut u32, out_seg: *mut u32, out_score: *mut c_float, out_vec_score: *mut c_float,
+        out_count: *mut u32, out_total: *mut u64) -> c_int;
+    pub fn slg_vector_search_batch_device(index: *mut slg_index, nq: u32, n_clauses: u32, clause_field: *const u32,
+        d_qvecs: *const c_float, d_alpha: *const c_float, d_boost: *const c_float, d_q_filter: *const i32,
+        cand_size: u32, k_out: u32, d_out_doc: *mut u32, d_out_seg: *mut u32, d_out_score: *mut c_float,
+        d_out_vec_score: *mut c_float, d_out_count: *mut u32, d_out_total: *mut u64) -> c_int;
 }
 pub const SLG_OWN_STREAM: *mut c_void = usize::MAX as *mut c_void;
 pub const SLG_NO_TERM: u32 = 0xFFFF_FFFF;

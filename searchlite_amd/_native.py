@@ -206,6 +206,9 @@ def load():
                                           vp, vp]),
         "slg_rerank_fields_batch_device": (i32, [vp, u32, u32, vp, vp, vp, vp, vp, vp, vp, vp, u32, u32, vp,
                                                  vp, vp, vp, vp]),
+        "slg_vector_search_batch": (i32, [vp, u32, u32, vp, vp, vp, vp, vp, u32, u32, vp, vp, vp, vp, vp, vp]),
+        "slg_vector_search_batch_device": (i32, [vp, u32, u32, vp, vp, vp, vp, vp, u32, u32, vp, vp, vp, vp,
+                                                 vp, vp]),
     }
     for name, (res, args) in sigs.items():
         if os.environ.get("SLG_LIB_TAG") and not hasattr(L, name):

@@ -425,6 +425,37 @@ class GpuIndex:
                             (nc, _ptr(cf), _ptr(qvecs), _ptr(alpha), _ptr(bst)),
                             cand_doc, cand_seg, cand_bm25, cand_count, k_out)
 
+    def vector_search(self, clause_field, qvecs, alpha, cand_size: int, k_out: int, boost=None, q_filter=None):
+        """Exact vector-only search (search_vector_only, api/reader.rs:2187-2330) over every stored
+        vector.  clause_field [n_clauses] field ids; qvecs [nq, sum of the clause dims] (a query's
+        clause vectors one after another); alpha / boost [nq, n_clauses]; q_filter [nq] filter ids
+        (< 0: none).  -> (doc, seg, score, vec_score) [nq, k_out], count [nq], total [nq] (union size)."""
+        cf = np.ascontiguousarray(clause_field, dtype=np.uint32)
+        nc = len(cf)
+        qvecs = np.ascontiguousarray(qvecs, dtype=np.float32)
+        nq = qvecs.shape[0]
+        alpha, bst = _f32(alpha, (nq, nc)), _f32(boost, (nq, nc))
+        flt = None if q_filter is None else np.ascontiguousarray(q_filter, dtype=np.int32)
+        doc = np.zeros((nq, k_out), np.uint32)
+        seg = np.zeros((nq, k_out), np.uint32)
+        score = np.zeros((nq, k_out), np.float32)
+        vec = np.zeros((nq, k_out), np.float32)
+        count = np.zeros(nq, np.uint32)
+        total = np.zeros(nq, np.uint64)
+        N.check(self._lib.slg_vector_search_batch(
+            self._h, nq, nc, _ptr(cf), _ptr(qvecs), _ptr(alpha), _ptr(bst), _ptr(flt), int(cand_size), int(k_out),
+            _ptr(doc), _ptr(seg), _ptr(score), _ptr(vec), _ptr(count), _ptr(total)))
+        return doc, seg, score, vec, count, total
+
+    def vector_search_device(self, nq, clause_field, d_qvecs, d_alpha, d_boost, d_q_filter, cand_size, k_out,
+                             d_out_doc, d_out_seg, d_out_score, d_out_vec, d_out_count, d_out_total) -> None:
+        """Device-pointer form of vector_search (ints; d_boost / d_q_filter may be None; clause_field
+        stays a host array), asynchronous on the index stream."""
+        cf = np.ascontiguousarray(clause_field, dtype=np.uint32)
+        N.check(self._lib.slg_vector_search_batch_device(
+            self._h, nq, len(cf), _ptr(cf), d_qvecs, d_alpha, d_boost, d_q_filter, int(cand_size), int(k_out),
+            d_out_doc, d_out_seg, d_out_score, d_out_vec, d_out_count, d_out_total))
+
     def rerank_batch_device(self, nq, d_qvecs, d_alpha, d_cand_doc, d_cand_seg, d_cand_bm25,
                             d_cand_count, max_cand, k_out, d_out_doc, d_out_seg, d_out_score,
                             d_out_vec, d_out_count) -> None:

@@ -16,13 +16,14 @@
  *
  * Eligibility (the caller keeps every other request shape on searchlite's CPU scorer;
  * SURVEY.md section 8b): ScoreMode::Score, sort = _score desc, no collector/aggs, no
- * score_adjust/explain, no cursor, matcher = pure disjunction; filters as doc bitmaps
+ * score_adjust/explain, matcher = pure disjunction; filters as doc bitmaps
  * (slg_index_add_filter*: accept() = !is_deleted(doc) && filter(doc)); ScorePlan = any tree of Sum /
  * DisMax nodes up to SLG_MAX_PLAN_DEPTH levels above its leaves, each leaf the sum of one or more
  * scored terms (slg_batch_prepare_plans; the default is leaf i == query term i, summed);
  * k = limit + 1 up to 20 001; up to 32 scored terms per query and segment.  Field sorts (slg_batch_prepare_sorted):
  * up to SLG_MAX_SORT_PARTS parts of numeric fast fields (i64 / f64) and _score, any order; keyword parts stay
- * on the CPU.
+ * on the CPU.  A cursor (the next page, slg_batch_prepare_after) in score order or in a device-eligible field
+ * sort; not in sharded runs or the coalescer.
  */
 #ifndef SEARCHLITE_GPU_H
 #define SEARCHLITE_GPU_H
@@ -436,14 +437,57 @@ slg_batch *slg_batch_prepare_sorted(slg_index *index, uint32_t nq, const uint32_
                                     const slg_score_plans *plans_or_null, const int32_t *q_filter_or_null,
                                     const slg_sort_spec *sort, uint32_t k, int strategy);
 /* Accepted docs per query of a sorted batch's last run (total_matches, api/reader.rs:3026-3028: docs that
- * pass tombstones, filter and minimum_should_match); waits for the batch.  SLG_ERR_INVALID for a batch
- * that is not sorted. */
+ * pass tombstones, filter and minimum_should_match; in a cursor batch, of those the ones after the cursor);
+ * waits for the batch.  SLG_ERR_INVALID for a batch that is neither sorted nor a cursor batch. */
 int slg_batch_matched_counts(slg_batch *batch, uint64_t *out_matched);
 /* One-shot form: slg_search_batch_filtered with score plans and a sort spec; out_matched ([nq]) may be NULL. */
 int slg_search_batch_sorted(slg_index *index, const slg_query *queries, uint32_t nq,
                             const slg_score_plans *plans_or_null, const int32_t *q_filter_or_null,
                             const slg_sort_spec *sort, uint32_t k, int strategy, uint32_t *out_doc,
                             uint32_t *out_seg, float *out_score, uint32_t *out_count, uint64_t *out_matched);
+/* Cursor pagination (the next page of a request: api/reader.rs:3009-3036).  The cursor key, decoded by the
+ * caller from the reference's PaginationCursor / SortCursorState (api/reader.rs:613-900): the values the
+ * previous page's last hit was sorted by, then its segment_ord and doc_id.  value_bits[p] of part p: an i64
+ * field's value (two's complement), an f64 field's bits, or a `_score` part's f32 bits in the low 32 bits
+ * (the high 32 zero); a Missing part has its missing_mask bit set (its value_bits are not read).  Parts
+ * beyond the spec (score order: beyond part 0) hold zero.  has_cursor == 0: a first page (nothing else of
+ * the row is read). */
+typedef struct {
+  uint32_t has_cursor;
+  uint32_t segment_ord, doc_id;
+  uint32_t missing_mask;  /* bit p: sort part p is Missing (never a `_score` part) */
+  uint64_t value_bits[SLG_MAX_SORT_PARTS];
+} slg_sort_cursor;
+/* A batch whose rows hold, per query, the top k strictly AFTER the query's cursor in SortKey::cmp order
+ * (query/sort.rs:80-123).  sort_or_null == NULL: score order (score desc by f32 total_cmp, segment asc, doc
+ * asc: the score path's order, score_fast_path); value_bits[0] holds the cursor's score.  Otherwise a field
+ * sort, the specs slg_batch_prepare_sorted takes, one cursor value per part.  Rows come back through
+ * slg_batch_run / _fetch / _device_results; scores are bit-identical to the score path (0.0 in a field sort
+ * without a `_score` part, as slg_batch_prepare_sorted).  Every matched doc is scored (candidates mode, no
+ * threshold seed, no MaxScore: after a cursor the k-th eligible score lies below any champion bound).
+ * slg_batch_matched_counts gives the accepted docs after the cursor (total_matches; the caller adds the
+ * rows it returned before).  Checked on the host before any device work: q_cursor NULL, a Missing bit on a
+ * `_score` part or beyond the spec, non-zero value_bits beyond the spec, or a `_score` value with high bits
+ * set: SLG_ERR_INVALID.  A segment_ord / doc_id that names no doc is not an error (the cursor is stale).
+ * slg_batch_run_sharded[_seq] and slg_batch_fetch_sharded refuse a cursor batch (SLG_ERR_UNSUPPORTED: a
+ * cursor's segment_ord is index-global). */
+slg_batch *slg_batch_prepare_after(slg_index *index, uint32_t nq, const uint32_t *q_offsets,
+                                   const uint32_t *q_term_ids, const float *q_weights,
+                                   const slg_score_plans *plans_or_null, const int32_t *q_filter_or_null,
+                                   const slg_sort_spec *sort_or_null, const slg_sort_cursor *q_cursor,
+                                   uint32_t k, int strategy);
+/* Per query of a cursor batch's last run (waits): 1 when an accepted doc's key equals the cursor key (the
+ * reference's saw_cursor) or the query has no cursor; 0 when the cursor doc was deleted, filtered out, scored
+ * differently or names no doc — the rows are still the window after the key, and the caller decides (the
+ * reference rejects such a cursor, api/reader.rs:2747-2749).  SLG_ERR_INVALID for a batch without cursors. */
+int slg_batch_cursor_seen(slg_batch *batch, uint8_t *out_seen);
+/* One-shot form: slg_search_batch_sorted with a cursor per query; out_matched ([nq], u64) and out_seen ([nq])
+ * may be NULL. */
+int slg_search_batch_after(slg_index *index, const slg_query *queries, uint32_t nq,
+                           const slg_score_plans *plans_or_null, const int32_t *q_filter_or_null,
+                           const slg_sort_spec *sort_or_null, const slg_sort_cursor *q_cursor, uint32_t k,
+                           int strategy, uint32_t *out_doc, uint32_t *out_seg, float *out_score,
+                           uint32_t *out_count, uint64_t *out_matched, uint8_t *out_seen);
 /* Enqueue the partition / score / merge kernels on the batch's stream (asynchronous). */
 int slg_batch_run(slg_batch *batch);
 /* Run this batch on its own HIP stream instead of the index stream, so several prepared

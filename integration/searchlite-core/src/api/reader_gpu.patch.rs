@@ -56,13 +56,16 @@ let gpu_hits: Option<Vec<RankedHit>> = (|| {
   };
   match crate::gpu::gpu_top_k(
     gpu, &self.segments, &folded, &score_plan, n_leaves, min_match, req.filter.as_ref(), &not_keys,
-    &req.execution, top_k, sort_parts.as_deref(),
+    &req.execution, top_k, sort_parts.as_deref(), cursor_state.as_ref().map(|c| &c.key),
   ) {
     Ok((rows, scored)) => {
       // total_hits_estimate: the CPU path counts the docs `accept` saw (pruning-dependent under
       // Wand/Bmw, api/reader.rs:3029-3031); the device reports every distinct doc it scored — and for a
-      // field sort the docs it accepted, which is the CPU collector path's own count (:3026-3028)
+      // field sort or a next page the docs it accepted after the cursor, which is the CPU collector path's own
+      // count (:3026-3028; :2825 adds the cursor's `returned`)
       total_matches = scored;
+      // the device found the cursor's key among the accepted docs (gpu_top_k bails when it did not)
+      saw_cursor = true;
       Some(
         rows
           .into_iter()

@@ -48,6 +48,12 @@ pub struct slg_tuning {
 #[repr(C)] pub struct slg_sort_spec {
     pub n_parts: u32, pub field: [i32; SLG_MAX_SORT_PARTS], pub order: [i32; SLG_MAX_SORT_PARTS],
 }
+// a query's cursor key (slg_batch_prepare_after): the CursorState key's part values (i64 two's complement, f64
+// bits, or f32 bits of a score), Missing parts as bits, then segment_ord and doc_id
+#[repr(C)] #[derive(Clone, Copy, Default)] pub struct slg_sort_cursor {
+    pub has_cursor: u32, pub segment_ord: u32, pub doc_id: u32, pub missing_mask: u32,
+    pub value_bits: [u64; SLG_MAX_SORT_PARTS],
+}
 #[repr(C)] pub struct slg_stats { pub scored_docs: u64, pub candidates_examined: u64, pub postings_advanced: u64 }
 #[repr(C)] pub struct slg_query { pub n_terms: u32, pub term_ids: *const u32, pub weights: *const c_float }
 
@@ -149,6 +155,15 @@ extern "C" {
         plans_or_null: *const slg_score_plans, q_filter_or_null: *const i32, sort: *const slg_sort_spec, k: u32,
         strategy: c_int, out_doc: *mut u32, out_seg: *mut u32, out_score: *mut c_float, out_count: *mut u32,
         out_matched: *mut u64) -> c_int;
+    // cursor pagination: the top k strictly after each query's cursor (sort NULL: score order)
+    pub fn slg_batch_prepare_after(index: *mut slg_index, nq: u32, q_offsets: *const u32, q_term_ids: *const u32,
+        q_weights: *const c_float, plans_or_null: *const slg_score_plans, q_filter_or_null: *const i32,
+        sort_or_null: *const slg_sort_spec, q_cursor: *const slg_sort_cursor, k: u32, strategy: c_int) -> *mut slg_batch;
+    pub fn slg_batch_cursor_seen(batch: *mut slg_batch, out_seen: *mut u8) -> c_int;
+    pub fn slg_search_batch_after(index: *mut slg_index, queries: *const slg_query, nq: u32,
+        plans_or_null: *const slg_score_plans, q_filter_or_null: *const i32, sort_or_null: *const slg_sort_spec,
+        q_cursor: *const slg_sort_cursor, k: u32, strategy: c_int, out_doc: *mut u32, out_seg: *mut u32,
+        out_score: *mut c_float, out_count: *mut u32, out_matched: *mut u64, out_seen: *mut u8) -> c_int;
     pub fn slg_batch_set_stream(batch: *mut slg_batch, hip_stream: *mut c_void) -> c_int;
     pub fn slg_batch_run(batch: *mut slg_batch) -> c_int;
     pub fn slg_batch_sync(batch: *mut slg_batch) -> c_int;

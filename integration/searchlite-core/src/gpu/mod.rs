@@ -33,7 +33,7 @@ use crate::index::fastfields::doc_length_key;
 use crate::index::segment::SegmentReader;
 use crate::query::filters::passes_filter;
 use crate::query::planner::{QueryMatcher, QueryPlan, ScoreExpr};
-use crate::query::sort::SortPlan;
+use crate::query::sort::{SortKey, SortPlan, SortValue};
 use crate::DocId;
 use self::ffi::{slg_index_add_sort_field_f64, slg_index_add_sort_field_i64};
 
@@ -699,8 +699,14 @@ pub(crate) fn gpu_eligible(
   if !req.return_hits || req.limit == 0 || top_k == 0 || top_k > MAX_K {
     return None;
   }
-  // no collector: agg_ref stays None only without aggregations (api/reader.rs:2694-2699)
-  if !req.aggs.is_empty() || req.explain || needs_score_hook || req.cursor.is_some() {
+  // no collector: agg_ref stays None only without aggregations (api/reader.rs:2694-2699).  A cursor (the next
+  // page) runs on the device in score order and in every field sort above (slg_batch_prepare_after); with a
+  // vector query it stays on the CPU
+  if !req.aggs.is_empty() || req.explain || needs_score_hook {
+    return None;
+  }
+  #[cfg(feature = "vectors")]
+  if req.cursor.is_some() && req.vector_query.is_some() {
     return None;
   }
   if req.collapse.is_some() {
@@ -732,10 +738,30 @@ pub(crate) fn gpu_eligible(
   Some((shape, n_leaves, min_match, sort_parts))
 }
 
+/// The reader's decoded cursor key (CursorState.key, api/reader.rs:816-868) as the library's slg_sort_cursor:
+/// one value per sort part (score order: the score), then segment_ord and doc_id.
+fn sort_cursor_of(key: &SortKey) -> Result<ffi::slg_sort_cursor> {
+  if key.parts.len() > ffi::SLG_MAX_SORT_PARTS {
+    bail!("more sort parts than the device takes");
+  }
+  let mut c = ffi::slg_sort_cursor { has_cursor: 1, segment_ord: key.segment_ord, doc_id: key.doc_id, ..Default::default() };
+  for (i, p) in key.parts.iter().enumerate() {
+    match &p.value {
+      SortValue::Score(x) => c.value_bits[i] = x.to_bits() as u64,
+      SortValue::I64(v) => c.value_bits[i] = *v as u64,
+      SortValue::F64(v) => c.value_bits[i] = v.to_bits(),
+      SortValue::Missing => c.missing_mask |= 1 << i,
+      SortValue::Str(_) => bail!("keyword sort parts run on the CPU"),
+    }
+  }
+  Ok(c)
+}
+
 /// Replaces the per-segment loop + cross-segment sort of IndexReader::search
 /// (api/reader.rs:2670-2778) for ONE eligible request: (segment_ord, doc_id, score) in final order,
-/// at most `top_k` of them, plus the number of distinct docs scored — or, for a field sort (`sort`), the
-/// number of docs accepted (total_matches, api/reader.rs:3026-3028; score 0.0 without a `_score` part).
+/// at most `top_k` of them, plus the number of distinct docs scored — or, for a field sort (`sort`) or a next
+/// page (`cursor`), the number of docs accepted (after the cursor: total_matches, api/reader.rs:3026-3028; the
+/// reader adds the hits it returned before; score 0.0 in a field sort without a `_score` part).
 pub(crate) fn gpu_top_k(
   gpu: &GpuSegments,
   segments: &[SegmentReader],
@@ -748,6 +774,7 @@ pub(crate) fn gpu_top_k(
   execution: &ExecutionStrategy,
   top_k: usize,
   sort: Option<&[GpuSortPart]>,
+  cursor: Option<&SortKey>,
 ) -> Result<(Vec<(u32, DocId, f32)>, u64)> {
   let n_segs = segments.len();
   // the reader's manifest snapshot must be what is staged (a commit may have moved the device index
@@ -836,31 +863,48 @@ pub(crate) fn gpu_top_k(
   // reference has no batch API (api/reader.rs:2539) and serves a request per blocking thread
   // (searchlite-http/src/lib.rs:628-652), so concurrent requests share one prepare / run / fetch.
   // (a request with minimum_should_match > 1 is prepared on its own: the coalescer's rows carry no such count)
-  if let Some(parts) = sort {
-    // the sort spec: numeric fast fields registered per staged segment set (ids are never reused)
-    let seg_ids: Vec<String> = st.key.iter().map(|(id, _)| id.clone()).collect();
-    let mut spec = ffi::slg_sort_spec { n_parts: parts.len() as u32, field: [0; ffi::SLG_MAX_SORT_PARTS], order: [0; ffi::SLG_MAX_SORT_PARTS] };
-    for (i, p) in parts.iter().enumerate() {
-      let (field, order) = match p {
-        GpuSortPart::Score(o) => (ffi::SLG_SORT_SCORE, o),
-        GpuSortPart::I64(name, o) => (gpu.sort_field_id(segments, &seg_ids, name, false)?, o),
-        GpuSortPart::F64(name, o) => (gpu.sort_field_id(segments, &seg_ids, name, true)?, o),
-        GpuSortPart::Keyword => bail!("keyword sort parts run on the CPU"),
-      };
-      spec.field[i] = field;
-      spec.order[i] = if matches!(order, SortOrder::Desc) { ffi::SLG_ORDER_DESC } else { ffi::SLG_ORDER_ASC };
+  if sort.is_some() || cursor.is_some() {
+    // the sort spec: numeric fast fields registered per staged segment set (ids are never reused); none for a
+    // next page in score order
+    let mut spec = None;
+    if let Some(parts) = sort {
+      let seg_ids: Vec<String> = st.key.iter().map(|(id, _)| id.clone()).collect();
+      let mut sp = ffi::slg_sort_spec { n_parts: parts.len() as u32, field: [0; ffi::SLG_MAX_SORT_PARTS], order: [0; ffi::SLG_MAX_SORT_PARTS] };
+      for (i, p) in parts.iter().enumerate() {
+        let (field, order) = match p {
+          GpuSortPart::Score(o) => (ffi::SLG_SORT_SCORE, o),
+          GpuSortPart::I64(name, o) => (gpu.sort_field_id(segments, &seg_ids, name, false)?, o),
+          GpuSortPart::F64(name, o) => (gpu.sort_field_id(segments, &seg_ids, name, true)?, o),
+          GpuSortPart::Keyword => bail!("keyword sort parts run on the CPU"),
+        };
+        sp.field[i] = field;
+        sp.order[i] = if matches!(order, SortOrder::Desc) { ffi::SLG_ORDER_DESC } else { ffi::SLG_ORDER_ASC };
+      }
+      spec = Some(sp);
     }
+    let cur = match cursor {
+      Some(key) => Some(sort_cursor_of(key)?),
+      None => None,
+    };
+    let spec_ptr = spec.as_ref().map_or(std::ptr::null(), |s| s as *const ffi::slg_sort_spec);
     let batch = unsafe {
-      ffi::slg_batch_prepare_sorted(
-        gpu.raw(), 1, offsets.as_ptr(), term_ids.as_ptr(), weights.as_ptr(), &plans, &filter_id, &spec, k, strategy,
-      )
+      match &cur {
+        Some(c) => ffi::slg_batch_prepare_after(
+          gpu.raw(), 1, offsets.as_ptr(), term_ids.as_ptr(), weights.as_ptr(), &plans, &filter_id, spec_ptr, c, k,
+          strategy,
+        ),
+        None => ffi::slg_batch_prepare_sorted(
+          gpu.raw(), 1, offsets.as_ptr(), term_ids.as_ptr(), weights.as_ptr(), &plans, &filter_id, spec_ptr, k,
+          strategy,
+        ),
+      }
     };
     drop(st);
     if batch.is_null() {
       return Err(last_error());
     }
     let (mut doc, mut seg, mut score) = (vec![0u32; top_k], vec![0u32; top_k], vec![0f32; top_k]);
-    let (mut count, mut matched) = (0u32, 0u64);
+    let (mut count, mut matched, mut seen) = (0u32, 0u64, 1u8);
     let rc = unsafe {
       let mut rc = ffi::slg_batch_run(batch);
       if rc == 0 {
@@ -870,11 +914,18 @@ pub(crate) fn gpu_top_k(
       if rc == 0 {
         rc = ffi::slg_batch_matched_counts(batch, &mut matched);
       }
+      if rc == 0 && cur.is_some() {
+        rc = ffi::slg_batch_cursor_seen(batch, &mut seen);
+      }
       ffi::slg_batch_destroy(batch);
       rc
     };
     if rc != 0 {
       bail!("searchlite_gpu returned {rc}");
+    }
+    // saw_cursor (api/reader.rs:2747-2749): no accepted doc had the cursor's key
+    if seen == 0 {
+      bail!("stale or invalid cursor for this result set");
     }
     let hits = (0..count as usize).map(|i| (seg[i], doc[i] as DocId, score[i])).collect();
     return Ok((hits, matched));

@@ -84,6 +84,13 @@ class SortSpec(C.Structure):
     _fields_ = [("n_parts", C.c_uint32), ("field", C.c_int32 * MAX_SORT_PARTS), ("order", C.c_int32 * MAX_SORT_PARTS)]
 
 
+class SortCursor(C.Structure):
+    """slg_sort_cursor: a query's cursor key (slg_batch_prepare_after): has_cursor, the last hit's segment and
+    doc, the Missing parts, and per part an i64 value, f64 bits or (low 32 bits) a score's f32 bits."""
+    _fields_ = [("has_cursor", C.c_uint32), ("segment_ord", C.c_uint32), ("doc_id", C.c_uint32),
+                ("missing_mask", C.c_uint32), ("value_bits", C.c_uint64 * MAX_SORT_PARTS)]
+
+
 class Ticket(C.Structure):
     """slg_ticket (slg_coalescer_submit / _wait)."""
     _fields_ = [("batch", C.c_void_p), ("row", C.c_uint32), ("k", C.c_uint32), ("kind", C.c_uint32)]
@@ -172,6 +179,9 @@ def load():
         "slg_batch_prepare_sorted": (vp, [vp, u32, vp, vp, vp, vp, vp, vp, u32, i32]),
         "slg_batch_matched_counts": (i32, [vp, vp]),
         "slg_search_batch_sorted": (i32, [vp, vp, u32, vp, vp, vp, u32, i32, vp, vp, vp, vp, vp]),
+        "slg_batch_prepare_after": (vp, [vp, u32, vp, vp, vp, vp, vp, vp, vp, u32, i32]),
+        "slg_batch_cursor_seen": (i32, [vp, vp]),
+        "slg_search_batch_after": (i32, [vp, vp, u32, vp, vp, vp, vp, u32, i32, vp, vp, vp, vp, vp, vp]),
         "slg_batch_run": (i32, [vp]),
         "slg_batch_set_stream": (i32, [vp, vp]),
         "slg_batch_sync": (i32, [vp]),

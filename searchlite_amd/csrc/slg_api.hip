@@ -323,6 +323,7 @@ struct SortColumn {
   DevBuf present;
 };
 struct SortFieldData {
+  int kind = 0;  // 1 i64, 2 f64 (a cursor's value is encoded by it)
   std::vector<std::shared_ptr<SortColumn>> per_seg;
 };
 
@@ -424,7 +425,12 @@ struct slg_batch {
   uint32_t score_k = 0;  // k the scoring kernel runs with (a sorted batch: slgplan::planning_k)
   uint32_t n_sort_parts = 0, sort_score_parts = 0, sort_desc_parts = 0;
   DevBuf d_sort_cols;  // slg::SortColDev[kSortMaxParts * n_segs]
-  DevBuf d_matched;    // u64[nq] accepted docs
+  DevBuf d_matched;    // u64[nq] accepted docs (sorted and cursor batches)
+  // cursor batch (slg_batch_prepare_after): score order (!sorted: select_topk_kernel<true>) or a field sort
+  // (select_sorted_kernel<true>)
+  bool after = false;
+  DevBuf d_cursor;  // u32[nq * slg::kCursorStride]: has_cursor, then the key words of the select kernel
+  DevBuf d_seen;    // u32[nq] the cursor's key was seen
   DevBuf d_out;  // doc | seg | score | count, contiguous
   uint32_t *d_out_doc = nullptr, *d_out_seg = nullptr, *d_out_count = nullptr;
   float *d_out_score = nullptr;
@@ -1198,6 +1204,7 @@ int add_sort_field_impl(slg_index *ix, int kind, const uint32_t *const *seg_offs
     DeviceGuard g(ix->device);
     const size_t n_segs = cur->segs.size();
     auto fd = std::make_shared<SortFieldData>();
+    fd->kind = kind;
     fd->per_seg.resize(n_segs);
     for (size_t s = 0; s < n_segs; s++) {
       const uint32_t n_docs = cur->segs[s]->n_docs;
@@ -1394,13 +1401,15 @@ slg_batch *slg_batch_prepare_plan(slg_index *ix, uint32_t nq, const uint32_t *q_
 }  // extern "C"
 
 namespace {
-// slg_batch_prepare_plans, and (sort != nullptr) slg_batch_prepare_sorted
+// slg_batch_prepare_plans, (sort != nullptr) slg_batch_prepare_sorted, and (after) slg_batch_prepare_after
 slg_batch *prepare_impl(slg_index *ix, uint32_t nq, const uint32_t *q_offsets, const uint32_t *q_term_ids,
                         const float *q_weights, const slg_score_plans *plans, const int32_t *q_filter,
-                        const slg_sort_spec *sort, uint32_t k, int strategy) {
+                        const slg_sort_spec *sort, uint32_t k, int strategy, bool after = false,
+                        const slg_sort_cursor *q_cursor = nullptr) {
   slg_batch *b = nullptr;
   int rc = guarded([&] {
     SLG_REQUIRE(ix != nullptr, "index is NULL");
+    SLG_REQUIRE(!after || q_cursor != nullptr, "q_cursor is NULL");
     if (sort) {  // (checked before planning: the planner never sees a sort spec it cannot run)
       if (sort->n_parts > SLG_MAX_SORT_PARTS)
         throw SlgError(SLG_ERR_UNSUPPORTED, "more than SLG_MAX_SORT_PARTS sort parts");
@@ -1435,7 +1444,7 @@ slg_batch *prepare_impl(slg_index *ix, uint32_t nq, const uint32_t *q_offsets, c
     in.strategy = strategy;
     in.filter_live = filter_live.data();
     in.n_filters = filter_live.size();
-    in.sorted = sort != nullptr;
+    in.sorted = sort != nullptr || after;
     // the columns of the sort parts in the batch's state: every part names a field with a column for every
     // segment (a field registered before slg_index_add_segment has none for the new one)
     std::vector<slg::SortColDev> sort_cols;
@@ -1459,6 +1468,25 @@ slg_batch *prepare_impl(slg_index *ix, uint32_t nq, const uint32_t *q_offsets, c
           const SortColumn &c = *fd.per_seg[s];
           sort_cols[i * n_segs + s] = slg::SortColDev{c.key[sort->order[i]].as<const unsigned long long>(),
                                                       c.present.as<const uint32_t>()};
+        }
+      }
+    }
+    // the cursors as the key words the select kernel compares (against the same snapshot's field kinds)
+    std::vector<uint32_t> cursor_words;
+    if (after) {
+      int kind[SLG_MAX_SORT_PARTS] = {0, 0, 0, 0};
+      const uint32_t n_parts = sort ? sort->n_parts : 0u;
+      for (uint32_t i = 0; i < n_parts; i++)
+        kind[i] = sort->field[i] == SLG_SORT_SCORE ? 0 : snap->sort_fields.at(sort->field[i])->kind;
+      cursor_words.assign((size_t)std::max<uint32_t>(nq, 1) * slg::kCursorStride, 0u);
+      for (uint32_t q = 0; q < nq; q++) {
+        if (!q_cursor[q].has_cursor) continue;
+        uint32_t *w = &cursor_words[(size_t)q * slg::kCursorStride];
+        w[0] = 1u;
+        try {
+          slgplan::cursor_key(n_parts, kind, sort ? sort->order : nullptr, q_cursor[q], w + 1);
+        } catch (const slgplan::SlgError &e) {
+          throw SlgError(e.code, "query " + std::to_string(q) + ": " + e.what());
         }
       }
     }
@@ -1486,6 +1514,7 @@ slg_batch *prepare_impl(slg_index *ix, uint32_t nq, const uint32_t *q_offsets, c
     b->pruned = plan.pruned;
     b->cand_mode = plan.cand_mode;
     b->sorted = sort != nullptr;
+    b->after = after;
     b->score_k = slgplan::planning_k(in);
     b->n_sq = (uint32_t)plan.sqs.size();
     b->n_terms = (uint32_t)plan.terms.size();
@@ -1553,7 +1582,12 @@ slg_batch *prepare_impl(slg_index *ix, uint32_t nq, const uint32_t *q_offsets, c
       b->d_sort_cols.alloc_pooled(&ix->pool, sort_cols.size() * sizeof(slg::SortColDev));
       SLG_HIP(hipMemcpy(b->d_sort_cols.p, sort_cols.data(), sort_cols.size() * sizeof(slg::SortColDev),
                         hipMemcpyHostToDevice));
-      b->d_matched.alloc_pooled(&ix->pool, (size_t)std::max<uint32_t>(nq, 1) * 8);
+    }
+    if (b->sorted || b->after) b->d_matched.alloc_pooled(&ix->pool, (size_t)std::max<uint32_t>(nq, 1) * 8);
+    if (b->after) {
+      b->d_cursor.alloc_pooled(&ix->pool, cursor_words.size() * 4);
+      SLG_HIP(hipMemcpy(b->d_cursor.p, cursor_words.data(), cursor_words.size() * 4, hipMemcpyHostToDevice));
+      b->d_seen.alloc_pooled(&ix->pool, (size_t)std::max<uint32_t>(nq, 1) * 4);
     }
     b->d_out.alloc_pooled(&ix->pool, ((size_t)nq * k * 3 + nq + 1) * 4);  // (+ the error word: MergeParams::out_flag)
     b->d_out_doc = b->d_out.as<uint32_t>();
@@ -1595,6 +1629,13 @@ slg_batch *slg_batch_prepare_sorted(slg_index *ix, uint32_t nq, const uint32_t *
     return nullptr;
   }
   return prepare_impl(ix, nq, q_offsets, q_term_ids, q_weights, plans, q_filter, sort, k, strategy);
+}
+
+slg_batch *slg_batch_prepare_after(slg_index *ix, uint32_t nq, const uint32_t *q_offsets,
+                                   const uint32_t *q_term_ids, const float *q_weights,
+                                   const slg_score_plans *plans, const int32_t *q_filter, const slg_sort_spec *sort,
+                                   const slg_sort_cursor *q_cursor, uint32_t k, int strategy) {
+  return prepare_impl(ix, nq, q_offsets, q_term_ids, q_weights, plans, q_filter, sort, k, strategy, true, q_cursor);
 }
 
 #define SLG_REQUIRE_LIVE(b) \
@@ -1707,9 +1748,17 @@ int slg_batch_run(slg_batch *b) {
       sp.k = b->k;
       sp.error_flag = ix->d_error_flag.as<uint32_t>();
       sp.out_flag = b->d_out_count + b->nq;
-      hipLaunchKernelGGL(slg::select_sorted_kernel, dim3(b->nq), dim3(slg::kSortedThreads), 0, st, sp);
+      if (b->after) {
+        sp.cursor = b->d_cursor.as<const uint32_t>();
+        sp.out_seen = b->d_seen.as<uint32_t>();
+        hipLaunchKernelGGL(slg::select_sorted_kernel<true>, dim3(b->nq), dim3(slg::kSortedThreads), 0, st, sp);
+      } else {
+        hipLaunchKernelGGL(slg::select_sorted_kernel<false>, dim3(b->nq), dim3(slg::kSortedThreads), 0, st, sp);
+      }
       SLG_HIP(hipGetLastError());
-    } else if (b->k > 0 && b->cand_mode && b->n_slices > 0) {
+    } else if (b->after || (b->k > 0 && b->cand_mode && b->n_slices > 0)) {
+      // (a cursor batch in score order runs the select also without slices or with k = 0: it writes the
+      //  matched counts and seen flags)
       slg::SelectParams sp{};
       sp.queries = b->d_queries;
       sp.slice_seg = b->d_slice_seg;
@@ -1728,7 +1777,14 @@ int slg_batch_run(slg_batch *b) {
       sp.k = b->k;
       sp.error_flag = ix->d_error_flag.as<uint32_t>();
       sp.out_flag = b->d_out_count + b->nq;
-      hipLaunchKernelGGL(slg::select_topk_kernel, dim3(b->nq), dim3(slg::kSelectThreads), 0, st, sp);
+      if (b->after) {
+        sp.cursor = b->d_cursor.as<const uint32_t>();
+        sp.out_matched = b->d_matched.as<unsigned long long>();
+        sp.out_seen = b->d_seen.as<uint32_t>();
+        hipLaunchKernelGGL(slg::select_topk_kernel<true>, dim3(b->nq), dim3(slg::kSelectThreads), 0, st, sp);
+      } else {
+        hipLaunchKernelGGL(slg::select_topk_kernel<false>, dim3(b->nq), dim3(slg::kSelectThreads), 0, st, sp);
+      }
       SLG_HIP(hipGetLastError());
     } else if (b->k > 0) {
       slg::MergeParams mp{};
@@ -1977,7 +2033,7 @@ int slg_search_batch_filtered(slg_index *ix, const slg_query *queries, uint32_t 
 int slg_batch_matched_counts(slg_batch *b, uint64_t *out_matched) {
   return guarded([&] {
     SLG_REQUIRE_LIVE(b);
-    SLG_REQUIRE(b->sorted, "not a sorted batch (slg_batch_prepare_sorted)");
+    SLG_REQUIRE(b->sorted || b->after, "not a sorted or cursor batch (slg_batch_prepare_sorted / _after)");
     SLG_REQUIRE(b->launched, "the batch has not run");
     SLG_REQUIRE(b->nq == 0 || out_matched != nullptr, "out_matched is NULL");
     slg_index *ix = b->idx;
@@ -2020,6 +2076,62 @@ int slg_search_batch_sorted(slg_index *ix, const slg_query *queries, uint32_t nq
   rc = slg_batch_run(b);
   if (rc == SLG_OK) rc = slg_batch_fetch(b, out_doc, out_seg, out_score, out_count, nullptr);
   if (rc == SLG_OK && out_matched) rc = slg_batch_matched_counts(b, out_matched);
+  const std::string keep = g_last_error;
+  slg_batch_destroy(b);
+  g_last_error = keep;
+  g_last_code = rc;
+  return rc;
+}
+
+int slg_batch_cursor_seen(slg_batch *b, uint8_t *out_seen) {
+  return guarded([&] {
+    SLG_REQUIRE_LIVE(b);
+    SLG_REQUIRE(b->after, "not a cursor batch (slg_batch_prepare_after)");
+    SLG_REQUIRE(b->launched, "the batch has not run");
+    SLG_REQUIRE(b->nq == 0 || out_seen != nullptr, "out_seen is NULL");
+    slg_index *ix = b->idx;
+    DeviceGuard g(ix->device);
+    hipStream_t st;
+    {
+      std::lock_guard<std::mutex> lk(ix->mu);
+      st = batch_stream(b);
+    }
+    SLG_HIP(wait_stream(st));
+    std::vector<uint32_t> seen(b->nq);
+    if (b->nq) SLG_HIP(hipMemcpy(seen.data(), b->d_seen.p, (size_t)b->nq * 4, hipMemcpyDeviceToHost));
+    for (uint32_t q = 0; q < b->nq; q++) out_seen[q] = seen[q] ? 1u : 0u;
+  });
+}
+
+int slg_search_batch_after(slg_index *ix, const slg_query *queries, uint32_t nq, const slg_score_plans *plans,
+                           const int32_t *q_filter, const slg_sort_spec *sort, const slg_sort_cursor *q_cursor,
+                           uint32_t k, int strategy, uint32_t *out_doc, uint32_t *out_seg, float *out_score,
+                           uint32_t *out_count, uint64_t *out_matched, uint8_t *out_seen) {
+  int rc = guarded([&] {
+    SLG_REQUIRE(ix != nullptr, "index is NULL");
+    SLG_REQUIRE(nq == 0 || queries != nullptr, "queries is NULL");
+  });
+  if (rc != SLG_OK) return rc;
+  std::vector<uint32_t> offs(nq + 1, 0), tids;
+  std::vector<float> ws;
+  rc = guarded([&] {
+    const size_t n_segs = ix->snapshot()->segs.size();
+    for (uint32_t q = 0; q < nq; q++) {
+      const slg_query &qq = queries[q];
+      SLG_REQUIRE(qq.n_terms == 0 || (qq.term_ids && qq.weights), "query arrays are NULL");
+      offs[q + 1] = offs[q] + qq.n_terms;
+      tids.insert(tids.end(), qq.term_ids, qq.term_ids + (size_t)qq.n_terms * n_segs);
+      ws.insert(ws.end(), qq.weights, qq.weights + qq.n_terms);
+    }
+  });
+  if (rc != SLG_OK) return rc;
+  slg_batch *b = slg_batch_prepare_after(ix, nq, offs.data(), tids.data(), ws.data(), plans, q_filter, sort,
+                                         q_cursor, k, strategy);
+  if (!b) return g_last_code;
+  rc = slg_batch_run(b);
+  if (rc == SLG_OK) rc = slg_batch_fetch(b, out_doc, out_seg, out_score, out_count, nullptr);
+  if (rc == SLG_OK && out_matched) rc = slg_batch_matched_counts(b, out_matched);
+  if (rc == SLG_OK && out_seen) rc = slg_batch_cursor_seen(b, out_seen);
   const std::string keep = g_last_error;
   slg_batch_destroy(b);
   g_last_error = keep;
@@ -2201,6 +2313,8 @@ int run_sharded_impl(slg_batch *b, slg_shard_group *g, bool have_seq, uint64_t s
     SLG_REQUIRE_LIVE(b);
     SLG_REQUIRE(g != nullptr && g->idx == b->idx, "shard group is NULL or belongs to another index");
     SLG_REQUIRE(g->segs_per_rank >= b->snap->segs.size(), "the shard grew beyond the group's segs_per_rank");
+    // (a cursor's segment_ord is index-global; the shard merge does not apply it)
+    if (b->after) throw SlgError(SLG_ERR_UNSUPPORTED, "a cursor batch does not run sharded");
   });
   if (rc != SLG_OK) return rc;
   if (!have_seq) {  // call order = the order on every rank, if one thread issues the runs
@@ -2326,6 +2440,7 @@ int slg_batch_fetch_sharded(slg_batch *b, uint32_t *out_doc, uint32_t *out_seg, 
                             uint32_t *out_count) {
   return guarded([&] {
     SLG_REQUIRE_LIVE(b);
+    if (b->after) throw SlgError(SLG_ERR_UNSUPPORTED, "a cursor batch does not run sharded");
     SLG_REQUIRE(b->nq == 0 || out_count != nullptr, "out_count is NULL");
     SLG_REQUIRE(b->nq == 0 || b->k == 0 || (out_doc && out_seg && out_score), "output array is NULL");
     if (b->nq == 0) return;

@@ -525,6 +525,9 @@ static __global__ void __launch_bounds__(256) bitmap_or_kernel(BitmapOrParams p)
 // histogram (a pass per byte until the bucket that holds the k-th key is exactly used up), a
 // gather of the k winners into LDS and a bitonic sort.  push_top_k / finalize_heap
 // (query/wand.rs:905-926) + the cross-segment sort (api/reader.rs:2776-2778) for large k.
+// The CURSOR instantiation (slg_batch_prepare_after in score order) also drops, in sweep 1, every candidate
+// whose key is at or above the query's cursor key — a hit of an earlier page (api/reader.rs:3009-3036) —
+// the way a deleted one is dropped, counts the rest (out_matched) and raises out_seen on the cursor's own key.
 struct SelectParams {
   const QueryRef *queries;
   const uint32_t *slice_seg;
@@ -541,13 +544,22 @@ struct SelectParams {
   uint32_t nq, k;
   const uint32_t *error_flag;  // see MergeParams
   uint32_t *out_flag;
+  // (CURSOR only)
+  const uint32_t *cursor;            // [nq * kCursorStride]: has_cursor, ordered score, ~segment, ~doc
+  unsigned long long *out_matched;   // [nq] accepted docs after the cursor
+  uint32_t *out_seen;                // [nq] 1: an accepted doc has the cursor's key (or no cursor)
 };
+
+// words per query of a cursor batch's device cursor table: has_cursor, then the key words the select kernel
+// compares (select_topk_kernel: 3; select_sorted_kernel: kSortWords)
+constexpr uint32_t kCursorStride = 16;
 
 constexpr uint32_t kSelectCap = 2048;      // keys sorted in LDS at a time (a rank range of the result)
 constexpr uint32_t kSelectMaxSlices = 512;   // slice table in LDS; more: strided slice loops (34 KB of LDS per workgroup: 4 per CU)
 constexpr uint32_t kSelectThreads = 512;
 
 // (8 waves per SIMD: four 512-thread workgroups per CU, so that the 1024 queries of a batch are all resident at once)
+template <bool CURSOR>
 static __global__ void __launch_bounds__(kSelectThreads) __attribute__((amdgpu_waves_per_eu(8, 8)))
 select_topk_kernel(SelectParams p) {
   constexpr uint32_t NT = kSelectThreads;
@@ -557,6 +569,7 @@ select_topk_kernel(SelectParams p) {
   __shared__ uint32_t t_end[kSelectMaxSlices];   // inclusive prefix of the slice counts
   __shared__ uint32_t t_nseg[kSelectMaxSlices];  // ~segment of the slice
   __shared__ uint64_t t_base[kSelectMaxSlices];  // first candidate slot of the slice
+  __shared__ uint32_t s_cur[4], sh_seen;          // (CURSOR) the query's cursor words; its key was seen
   const uint32_t tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const uint32_t q = blockIdx.x;
   if (q >= p.nq) return;
@@ -577,6 +590,10 @@ select_topk_kernel(SelectParams p) {
     sh_taken = 0;
   }
   if (tid < 256) hist0[tid] = 0;
+  if constexpr (CURSOR) {
+    if (tid < 4) s_cur[tid] = p.cursor[(size_t)q * kCursorStride + tid];
+    if (tid == 0) sh_seen = 0;
+  }
   __syncthreads();
   // slice table: the query's candidates form one flat index space [0, n)
   if (table) {
@@ -599,6 +616,8 @@ select_topk_kernel(SelectParams p) {
   __syncthreads();
   const uint32_t n_flat = table && nsl ? t_end[nsl - 1] : 0u;
   const bool anydel = sh_anydel != 0;
+  const bool cur_on = CURSOR && s_cur[0] != 0u;
+  const uint32_t cur_a = CURSOR ? s_cur[1] : 0u, cur_nseg = CURSOR ? s_cur[2] : 0u, cur_ndoc = CURSOR ? s_cur[3] : 0u;
 
   // visit every live candidate of the query: f(ordered score, ~seg, ~doc, slot)
   auto for_each = [&](auto &&f) {
@@ -665,6 +684,13 @@ select_topk_kernel(SelectParams p) {
       const uint32_t *del = flt ? p.reject_table[(size_t)(flt - 1) * p.n_segs + ~nseg] : p.segs[~nseg].deleted;
       const uint32_t d = ~ndoc;
       if (del && ((del[d >> 5] >> (d & 31)) & 1u)) {
+        p.cand[at].y = 0xFFFFFFFFu;
+        return;
+      }
+    }
+    if constexpr (CURSOR) {  // (descending key: at or above the cursor's = SortKey <= the cursor's)
+      if (cur_on && (a > cur_a || (a == cur_a && (nseg > cur_nseg || (nseg == cur_nseg && ndoc >= cur_ndoc))))) {
+        if (a == cur_a && nseg == cur_nseg && ndoc == cur_ndoc) sh_seen = 1u;
         p.cand[at].y = 0xFFFFFFFFu;
         return;
       }
@@ -846,6 +872,12 @@ select_topk_kernel(SelectParams p) {
     p.out_score[(size_t)q * k + i] = 0.0f;
   }
   if (tid == 0) p.out_count[q] = nout;
+  if constexpr (CURSOR) {
+    if (tid == 0) {
+      p.out_matched[q] = nvalid;
+      p.out_seen[q] = cur_on ? sh_seen : 1u;
+    }
+  }
 }
 
 // ---- field-sorted select (slg_batch_prepare_sorted; query/sort.rs:80-123 SortKey::cmp) -------------
@@ -861,7 +893,10 @@ select_topk_kernel(SelectParams p) {
 // which key bytes vary over the query's candidates; the byte-wise radix select (as select_topk_kernel's:
 // rank ranges of at most kSortedCap keys, a pass per VARYING byte until the bucket of the range's last
 // key is used up) then walks those bytes only.  A range's keys are gathered into LDS — only their
-// varying words — and bitonic-sorted by index.
+// varying words — and bitonic-sorted by index.  The CURSOR instantiation (slg_batch_prepare_after with a
+// sort spec) drops in sweep 1 every accepted candidate whose key is <= the query's cursor key (the words of
+// kSortWords the host encoded from the cursor's values) as it drops a deleted one, so neither `matched` nor
+// the radix levels see it, and raises out_seen on an equal key.
 struct SortColDev {
   const unsigned long long *key;  // [n_docs] u64 key of the part's order (0 for Missing docs)
   const uint32_t *present;        // presence bitmap (bit d & 31 of word d >> 5)
@@ -887,6 +922,9 @@ struct SortedSelectParams {
   uint32_t nq, k;
   const uint32_t *error_flag;  // see MergeParams
   uint32_t *out_flag;
+  // (CURSOR only)
+  const uint32_t *cursor;  // [nq * kCursorStride]: has_cursor, then the kSortWords key words
+  uint32_t *out_seen;      // [nq] 1: an accepted doc has the cursor's key (or no cursor)
 };
 
 constexpr uint32_t kSortMaxParts = 4;  // SLG_MAX_SORT_PARTS
@@ -932,6 +970,7 @@ __device__ __forceinline__ int sorted_cmp(const uint32_t (&K)[kSortWords], const
 
 // (no amdgpu_waves_per_eu: capped at 128 VGPRs for two workgroups per CU — what its 60 KB of LDS would
 //  allow — it spills 5 VGPRs; uncapped it takes 141 and none, one workgroup per CU)
+template <bool CURSOR>
 static __global__ void __launch_bounds__(kSortedThreads) select_sorted_kernel(SortedSelectParams p) {
   constexpr uint32_t NT = kSortedThreads, NW = kSortWords, CAP = kSortedCap;
   __shared__ uint32_t hist[256];
@@ -940,6 +979,7 @@ static __global__ void __launch_bounds__(kSortedThreads) select_sorted_kernel(So
   __shared__ uint32_t w_key[NW * CAP];
   __shared__ uint16_t w_idx[CAP];
   __shared__ uint32_t sh_nvalid, sh_nvary, sh_need, sh_done, sh_taken, sh_nwin;
+  __shared__ uint32_t s_cur[NW + 1], sh_seen;  // (CURSOR) has_cursor + the cursor's key words; its key was seen
   const uint32_t tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const uint32_t q = blockIdx.x;
   if (q >= p.nq) return;
@@ -954,7 +994,12 @@ static __global__ void __launch_bounds__(kSortedThreads) select_sorted_kernel(So
     s_qpre[tid] = s_qdm[tid] = 0u;
   }
   if (tid == 0) sh_nvalid = 0;
+  if constexpr (CURSOR) {
+    if (tid < NW + 1) s_cur[tid] = p.cursor[(size_t)q * kCursorStride + tid];
+    if (tid == 0) sh_seen = 0;
+  }
   __syncthreads();
+  const bool cur_on = CURSOR && s_cur[0] != 0u;
 
   // visit every live candidate of the query: f(ordered score, segment, doc, slot); a wave per slice
   auto for_each = [&](auto &&f) {
@@ -986,6 +1031,21 @@ static __global__ void __launch_bounds__(kSortedThreads) select_sorted_kernel(So
       }
       uint32_t K[NW];
       sorted_key(p, a, seg, doc, K);
+      if constexpr (CURSOR) {
+        if (cur_on) {
+          int c = 0;
+#pragma unroll
+          for (uint32_t w = 0; w < NW; w++) {
+            const uint32_t y = s_cur[1 + w];
+            if (c == 0) c = K[w] < y ? -1 : (K[w] > y ? 1 : 0);
+          }
+          if (c <= 0) {  // on an earlier page
+            if (c == 0) sh_seen = 1u;
+            p.cand[at].y = 0xFFFFFFFFu;
+            return;
+          }
+        }
+      }
 #pragma unroll
       for (uint32_t w = 0; w < NW; w++) {
         t_and[w] &= K[w];
@@ -1172,6 +1232,9 @@ static __global__ void __launch_bounds__(kSortedThreads) select_sorted_kernel(So
     p.out_score[(size_t)q * k + i] = 0.0f;
   }
   if (tid == 0) p.out_count[q] = nout;
+  if constexpr (CURSOR) {
+    if (tid == 0) p.out_seen[q] = cur_on ? sh_seen : 1u;
+  }
 }
 
 }  // namespace slg

@@ -931,4 +931,51 @@ void sort_field_keys(int kind, uint32_t n_docs, const uint32_t *offsets, const v
     throw SlgError(SLG_ERR_INVALID, "unknown sort field kind");
 }
 
+namespace {
+uint32_t ordered_score_bits(uint32_t b) { return b ^ ((uint32_t)((int32_t)b >> 31) | 0x80000000u); }
+}  // namespace
+
+void cursor_key(uint32_t n_parts, const int *kind, const int32_t *order, const slg_sort_cursor &c, uint32_t *out) {
+  const uint32_t parts = n_parts ? n_parts : 1u;  // (score order: part 0 is the score)
+  PLAN_REQUIRE(parts <= SLG_MAX_SORT_PARTS, "more than SLG_MAX_SORT_PARTS sort parts");
+  PLAN_REQUIRE((c.missing_mask >> parts) == 0u, "cursor: Missing bit beyond the sort spec");
+  for (uint32_t i = parts; i < SLG_MAX_SORT_PARTS; i++)
+    PLAN_REQUIRE(c.value_bits[i] == 0u, "cursor: value beyond the sort spec is not zero");
+  auto score_word = [&](uint32_t i) {
+    PLAN_REQUIRE(!((c.missing_mask >> i) & 1u), "cursor: Missing bit on a _score part");
+    PLAN_REQUIRE((c.value_bits[i] >> 32) == 0u, "cursor: _score value has bits above the f32");
+    return ordered_score_bits((uint32_t)c.value_bits[i]);
+  };
+  if (n_parts == 0) {
+    out[0] = score_word(0);
+    out[1] = ~c.segment_ord;
+    out[2] = ~c.doc_id;
+    return;
+  }
+  for (uint32_t i = 0; i < kCursorWords; i++) out[i] = 0u;
+  for (uint32_t i = 0; i < n_parts; i++) {
+    const bool desc = order[i] == SLG_ORDER_DESC;
+    if (kind[i] == 0) {
+      const uint32_t a = score_word(i);
+      out[3 * i + 2] = desc ? ~a : a;
+      continue;
+    }
+    PLAN_REQUIRE(kind[i] == 1 || kind[i] == 2, "unknown sort field kind");
+    if ((c.missing_mask >> i) & 1u) {
+      out[3 * i] = 1u;  // Missing: after every value in both orders, keys 0 (as the columns)
+      continue;
+    }
+    int64_t iv;
+    double dv;
+    std::memcpy(&iv, &c.value_bits[i], 8);
+    std::memcpy(&dv, &c.value_bits[i], 8);
+    uint64_t key = kind[i] == 1 ? i64_key(iv) : f64_key(dv);
+    if (desc) key = ~key;
+    out[3 * i + 1] = (uint32_t)(key >> 32);
+    out[3 * i + 2] = (uint32_t)key;
+  }
+  out[kCursorWords - 2] = c.segment_ord;
+  out[kCursorWords - 1] = c.doc_id;
+}
+
 }  // namespace slgplan

@@ -46,8 +46,10 @@ struct BatchIn {
   int strategy = SLG_STRATEGY_WAND;
   const char *filter_live = nullptr;  // [n_filters] 1 = the filter id is registered
   size_t n_filters = 0;
-  // field-sorted batch (slg_batch_prepare_sorted): every matched doc is a candidate with its exact score,
-  // whatever k is — candidates mode, no threshold seed, no MaxScore classification
+  // field-sorted batch (slg_batch_prepare_sorted) or cursor batch (slg_batch_prepare_after, both orders):
+  // every matched doc is a candidate with its exact score, whatever k is — candidates mode, no threshold
+  // seed, no MaxScore classification (the seed bounds the k-th score over ALL docs; after a cursor the
+  // k-th eligible score is lower, and a seed or a prune would drop docs of the page)
   bool sorted = false;
 };
 
@@ -65,6 +67,18 @@ inline uint32_t planning_k(const BatchIn &in) { return in.sorted && in.k < kSort
 // offsets == NULL: every doc is Missing.  kind: 1 i64, 2 f64.
 void sort_field_keys(int kind, uint32_t n_docs, const uint32_t *offsets, const void *values, uint64_t *asc,
                      uint64_t *desc, uint32_t *present_words);
+
+// ---- cursor keys (slg_batch_prepare_after) ----
+// The cursor's key as the words the select kernels compare.  n_parts == 0: score order -> out[0..2] =
+// (ordered score, ~segment, ~doc), descending as select_topk_kernel's candidate keys.  Otherwise a field sort
+// (kind[p]: 0 `_score`, 1 i64, 2 f64; order[p] SLG_ORDER_*) -> out[0..kCursorWords-1] ascending as
+// select_sorted_kernel's keys: per part (missing flag, u64 key high, low) — the column encoding of
+// sort_field_keys applied to the cursor's value itself (the reference already picked it: no min_by / max_by),
+// complemented for Desc; a `_score` part is (0, 0, ordered score, complemented for Desc) — zero words for
+// parts beyond the spec, then segment, doc.  Throws SlgError(SLG_ERR_INVALID) for a Missing bit on a
+// `_score` part or beyond the spec, non-zero value_bits beyond the spec, or a `_score` value above 32 bits.
+constexpr uint32_t kCursorWords = 3 * SLG_MAX_SORT_PARTS + 2;
+void cursor_key(uint32_t n_parts, const int *kind, const int32_t *order, const slg_sort_cursor &c, uint32_t *out);
 
 struct Plan {
   // ---- the descriptor image ----

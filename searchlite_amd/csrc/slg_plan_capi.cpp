@@ -150,4 +150,18 @@ int slgp_sort_keys(int kind, uint32_t n_docs, const uint32_t *offsets, const voi
   }
 }
 
+// the host side of slg_batch_prepare_after: the select kernels' key words of one cursor (slgplan::cursor_key;
+// n_parts 0 = score order, 3 words; else kind[p] 0 `_score` / 1 i64 / 2 f64, 14 words).  0, or a negative
+// error code
+int slgp_cursor_key(uint32_t n_parts, const int *kind, const int32_t *order, const slg_sort_cursor *cursor,
+                    uint32_t *out_words) {
+  try {
+    if (!cursor || !out_words || (n_parts && (!kind || !order))) return SLG_ERR_INVALID;
+    slgplan::cursor_key(n_parts, kind, order, *cursor, out_words);
+    return SLG_OK;
+  } catch (const slgplan::SlgError &e) {
+    return e.code;
+  }
+}
+
 }  // extern "C"

@@ -9,6 +9,7 @@ No CPU fallback lives here: every search goes through libsearchlite_gpu.so.
 from __future__ import annotations
 
 import ctypes as C
+import struct
 import weakref
 from typing import List, Optional, Sequence, Tuple
 
@@ -259,21 +260,36 @@ class GpuIndex:
         finally:
             b.close()
 
+    def search_after(self, q_offsets, q_terms, q_weights, k: int, cursors, sort=None, strategy: int = Wand,
+                     q_filter=None, **plans):
+        """The next page (slg_batch_prepare_after): per query the top k strictly after its cursor.  cursors: one
+        per query, None (a first page) or (values, segment_ord, doc_id) with values one per sort part (score
+        order: (score,)) — an int for an i64 field, a float for an f64 field or a score, None for Missing; or
+        an N.SortCursor.  sort: None = score order, else as search_sorted.
+        -> (doc, seg, score, count, matched, seen)."""
+        b = self.prepare(q_offsets, q_terms, q_weights, k, strategy, q_filter, sort=sort, cursors=cursors, **plans)
+        try:
+            b.run()
+            return b.fetch() + (b.matched_counts(), b.cursor_seen())
+        finally:
+            b.close()
+
     # -- search ----------------------------------------------------------------------
     def prepare(self, q_offsets, q_terms, q_weights, k: int, strategy: int = Wand,
                 q_filter=None, q_leaf=None, q_plan=None, q_tie=None, q_nleaves=None,
                 q_leaf_offsets=None, leaf_group=None, q_group_offsets=None, group_plan=None,
                 group_tie=None, q_node_offsets=None, node_kind=None, node_tie=None, node_parent=None,
-                q_min_match=None, sort=None) -> "PreparedBatch":
+                q_min_match=None, sort=None, cursors=None) -> "PreparedBatch":
         """q_leaf / q_plan / q_tie / q_nleaves: score plans; leaf_group / group_plan / group_tie with
         their per-query offsets: two-level plans; q_node_offsets / node_kind / node_tie / node_parent:
         trees of any shape, node by node in pre-order (slg_batch_prepare_plans, slg_score_plans);
         q_min_match: minimum_should_match per query (leaves that must hold a doc); sort: a field sort
-        (search_sorted) -> slg_batch_prepare_sorted."""
+        (search_sorted) -> slg_batch_prepare_sorted; cursors: a cursor per query (search_after) ->
+        slg_batch_prepare_after."""
         return PreparedBatch(self, q_offsets, q_terms, q_weights, k, strategy, q_filter,
                              q_leaf, q_plan, q_tie, q_nleaves, q_leaf_offsets, leaf_group,
                              q_group_offsets, group_plan, group_tie, q_node_offsets, node_kind, node_tie, node_parent,
-                             q_min_match, sort)
+                             q_min_match, sort, cursors)
 
     def search_plan(self, q_offsets, q_terms, q_weights, k: int, q_leaf=None, q_plan=None,
                     q_tie=None, q_nleaves=None, strategy: int = Wand, q_filter=None, **tree):
@@ -540,6 +556,30 @@ def sort_spec(sort) -> "N.SortSpec":
     return spec
 
 
+def sort_cursor(cursor, sort=None) -> "N.SortCursor":
+    """None (a first page), an N.SortCursor, or (values, segment_ord, doc_id) -> slg_sort_cursor.  values: one
+    per sort part (score order: one, the score): an int is an i64 value, a float an f64 value (or, on a
+    `_score` part and in score order, an f32 score), None Missing."""
+    c = N.SortCursor()
+    if cursor is None:
+        return c
+    if isinstance(cursor, N.SortCursor):
+        return cursor
+    values, seg, doc = cursor
+    c.has_cursor, c.segment_ord, c.doc_id = 1, int(seg), int(doc)
+    parts = ["_score"] if sort is None else [p for p, _ in sort]
+    for i, v in enumerate(values):
+        if v is None:
+            c.missing_mask |= 1 << i
+        elif i < len(parts) and (parts[i] == "_score" or parts[i] == N.SORT_SCORE):
+            c.value_bits[i] = struct.unpack("<I", struct.pack("<f", float(v)))[0]
+        elif isinstance(v, float):
+            c.value_bits[i] = struct.unpack("<Q", struct.pack("<d", v))[0]
+        else:
+            c.value_bits[i] = int(v) & 0xFFFFFFFFFFFFFFFF
+    return c
+
+
 class PreparedBatch:
     """A planned query batch with device-resident descriptors and work buffers."""
 
@@ -547,7 +587,7 @@ class PreparedBatch:
                  q_filter=None, q_leaf=None, q_plan=None, q_tie=None, q_nleaves=None,
                  q_leaf_offsets=None, leaf_group=None, q_group_offsets=None, group_plan=None,
                  group_tie=None, q_node_offsets=None, node_kind=None, node_tie=None, node_parent=None,
-                 q_min_match=None, sort=None):
+                 q_min_match=None, sort=None, cursors=None):
         self.index = index
         self._lib = index._lib
         q_offsets = np.ascontiguousarray(q_offsets, dtype=np.uint32)
@@ -576,7 +616,15 @@ class PreparedBatch:
         plans = N.ScorePlans(opt(ql), opt(qp), opt(qt), opt(qn), opt(qlo), opt(lg), opt(qgo), opt(gp), opt(gt),
                              opt(qno), opt(nk), opt(ntie), opt(npar), opt(qmm))
         self.sorted = sort is not None
-        if sort is None:
+        self.after = cursors is not None
+        if cursors is not None:
+            assert len(cursors) == self.nq
+            cur = (N.SortCursor * max(self.nq, 1))(*[sort_cursor(c, sort) for c in cursors])
+            spec = None if sort is None else sort_spec(sort)
+            self._h = self._lib.slg_batch_prepare_after(
+                index._h, self.nq, _ptr(q_offsets), _ptr(q_terms), _ptr(q_weights), C.addressof(plans),
+                opt(qf), None if spec is None else C.addressof(spec), C.addressof(cur), k, strategy)
+        elif sort is None:
             self._h = self._lib.slg_batch_prepare_plans(
                 index._h, self.nq, _ptr(q_offsets), _ptr(q_terms), _ptr(q_weights), C.addressof(plans),
                 opt(qf), k, strategy)
@@ -607,6 +655,13 @@ class PreparedBatch:
         """Accepted docs per query of a sorted batch's last run (total_matches); waits."""
         out = np.zeros(max(self.nq, 1), dtype=np.uint64)
         N.check(self._lib.slg_batch_matched_counts(self._h, _ptr(out)))
+        return out[:self.nq]
+
+    def cursor_seen(self) -> np.ndarray:
+        """Per query of a cursor batch's last run: 1 if an accepted doc had the cursor's key (or the query has
+        no cursor), 0 for a stale cursor (saw_cursor); waits."""
+        out = np.zeros(max(self.nq, 1), dtype=np.uint8)
+        N.check(self._lib.slg_batch_cursor_seen(self._h, _ptr(out)))
         return out[:self.nq]
 
     def run_sharded(self, group: "ShardGroup", fetch: bool = True, seq: Optional[int] = None):

@@ -133,6 +133,35 @@ struct QueryRef {
 };
 
 
+// ---- vector stores (slg_rerank.hpp, slg_vsearch.hpp) ----------------------------------------------
+// A segment without vectors in the field has dim 0 and the field's metric.  A candidate whose segment
+// is >= n_segs, or whose doc is >= its segment's n_docs, is a candidate without a vector: it scores
+// missing_vector_score of the field's metric (api/reader.rs:217-223).
+struct VecSegDev {
+  const uint32_t *offsets;  // [n_docs] row index or 0xFFFFFFFF
+  const float *values;      // [rows * dim]
+  uint32_t n_docs;
+  uint32_t dim;
+  int32_t metric;  // 0 cosine, 1 l2
+  uint32_t pad;
+};
+
+// ---- merge of per-shard results gathered over RCCL (merge_shards_kernel, slg_kernels.hpp) ----------
+struct ShardMergeParams {
+  const uint32_t *doc;    // shard sh's rows start at doc + sh * arr_stride ([nq*k] each)
+  const uint32_t *seg;
+  const float *score;
+  const uint32_t *count;  // shard sh's counts start at count + sh * cnt_stride ([nq])
+  uint32_t *out_doc, *out_seg;
+  float *out_score;
+  uint32_t *out_count;
+  uint32_t n_shards, nq, k, seg_stride;
+  // elements between two shards' arrays: nq*k / nq for separate shard-major arrays; (3k+1)*nq for
+  // both when the shards' contiguous result blocks doc|seg|score|count lie one after another, as an
+  // all-gather delivers them
+  uint64_t arr_stride, cnt_stride;
+};
+
 // ---- planning constants (the kernels that consume them: slg_score*.hpp) ------------------------
 constexpr int kMaxRoundsPerSlice = 16;  // and (rounds+1)*T <= 64: cut points live in one VGPR
 constexpr int kDefaultRoundsPerSlice = 8;

@@ -1,0 +1,564 @@
+// slg_host.hpp — what the host translation units of the C ABI share (slg_index.hip, slg_batch.hip,
+// slg_shard.hip, slg_rerank.hip, slg_vsearch.hip): the error plumbing, device memory, the host
+// structures behind the opaque handles and the small helpers several entry points use.  Private: not
+// installed, not part of include/.  No kernel header is included here — each unit includes the one
+// whose kernels it launches (slg_stage.hpp, slg_kernels.hpp, slg_rerank.hpp, slg_vsearch.hpp; the shard
+// unit none), so every kernel is compiled once.
+//
+// Everything in namespace slghost has hidden visibility: shared between the library's objects, never
+// part of its export list.
+#pragma once
+
+#include "../../include/searchlite_gpu.h"
+
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <atomic>
+#include <cstring>
+#include <map>
+#include <memory>
+#include <mutex>
+#include <new>
+#include <stdexcept>
+#include <string>
+#include <utility>
+#include <vector>
+
+#include "slg_desc.hpp"
+#include "slg_plan.hpp"
+
+namespace slghost __attribute__((visibility("hidden"))) {
+
+// the thread's last error (slg_last_error / slg_last_error_code): one thread-local object, in slg_index.hip
+struct LastError {
+  std::string msg;
+  int code = SLG_OK;
+};
+LastError &last_error();
+
+using slgplan::SlgError;  // {code, message}; also what the host planner throws
+
+#define SLG_HIP(expr)                                                                     \
+  do {                                                                                    \
+    hipError_t _e = (expr);                                                               \
+    if (_e != hipSuccess) {                                                               \
+      int _code = (_e == hipErrorOutOfMemory) ? SLG_ERR_OOM : SLG_ERR_DEVICE;             \
+      throw SlgError(_code, std::string(#expr) + ": " + hipGetErrorString(_e));           \
+    }                                                                                     \
+  } while (0)
+
+#define SLG_REQUIRE(cond, msg)                              \
+  do {                                                      \
+    if (!(cond)) throw SlgError(SLG_ERR_INVALID, (msg));    \
+  } while (0)
+
+#define SLG_REQUIRE_LIVE(b) \
+  SLG_REQUIRE((b) != nullptr && (b)->idx != nullptr, "batch is NULL or its index was destroyed")
+
+template <typename F>
+int guarded(F &&f) {
+  LastError &le = last_error();
+  auto fail = [&le](int code, const char *msg) {
+    le.msg = msg;
+    le.code = code;
+  };
+  try {
+    le.msg.clear();
+    le.code = SLG_OK;
+    f();
+  } catch (const SlgError &e) {
+    fail(e.code, e.what());
+  } catch (const std::bad_alloc &) {
+    fail(SLG_ERR_OOM, "host allocation failed");
+  } catch (const std::exception &e) {
+    fail(SLG_ERR_INTERNAL, e.what());
+  } catch (...) {
+    fail(SLG_ERR_INTERNAL, "unknown error");
+  }
+  return le.code;
+}
+
+// Keeps the thread's last error across the clean-up that follows a failure (destroying a batch, an index
+// or a group may reset it): the error at the guard's construction is the last error again when it goes
+struct KeepLastError {
+  const LastError kept = last_error();
+  ~KeepLastError() { last_error() = kept; }
+};
+
+// Freed batch buffers are kept for the next batch: hipMalloc / hipFree cost ~100 us each and
+// hipFree synchronizes the device, which would serialize host threads that serve batches
+// concurrently.  Size classes: powers of two from 4 KiB to 1 MiB, above that eight steps per
+// octave (<= 12.5 % over-allocation).  The pool is bounded (slg_tuning.pool_cap_mb) and is the
+// first thing given back when the device runs out of memory: every allocation of the library that
+// fails with hipErrorOutOfMemory drains it and tries once more, so parked blocks of size classes
+// nobody asks for any more can never starve a new batch, a second index or the application.
+struct BufPool {
+  std::mutex mu;
+  std::multimap<size_t, void *> free_;
+  size_t pooled = 0;
+  // (config 4 on one GPU holds ~1 GB of work buffers per 8192-query batch and keeps three batches
+  //  alive: with a 4 GB cap every batch ended in hipFree + hipMalloc, which synchronise the device)
+  size_t cap = 24ull << 30;
+  // pinned staging images of slg_batch_prepare* (descriptor uploads), owned by the index: taken
+  // for one prepare call, handed back afterwards, released with the index (a thread_local image
+  // would outlive its thread's usefulness and leak when caller threads come and go)
+  std::vector<std::pair<void *, size_t>> images;
+  static size_t size_class(size_t n) {  // powers of two up to 1 MiB, then eighths of an octave
+    size_t c = 4096;
+    while (c < n && c < (1u << 20)) c <<= 1;
+    if (c >= n) return c;
+    while ((c << 1) < n) c <<= 1;  // c <= n < 2c
+    const size_t step = c >> 3;
+    return c + ((n - c + step - 1) / step) * step;
+  }
+  // a free block of class cls, or the next larger one within 25 % (its size goes back in *got)
+  void *get(size_t cls, size_t *got) {
+    std::lock_guard<std::mutex> lk(mu);
+    auto it = free_.lower_bound(cls);
+    if (it == free_.end() || it->first > cls + cls / 4) return nullptr;
+    void *p = it->second;
+    *got = it->first;
+    pooled -= it->first;
+    free_.erase(it);
+    return p;
+  }
+  bool put(void *p, size_t cls) {
+    std::lock_guard<std::mutex> lk(mu);
+    if (pooled + cls > cap) return false;
+    free_.emplace(cls, p);
+    pooled += cls;
+    return true;
+  }
+  // give every parked block back to the runtime (largest first); returns the bytes freed
+  size_t drain() {
+    std::multimap<size_t, void *> take;
+    {
+      std::lock_guard<std::mutex> lk(mu);
+      take.swap(free_);
+      pooled = 0;
+    }
+    size_t freed = 0;
+    for (auto it = take.rbegin(); it != take.rend(); ++it) {
+      (void)hipFree(it->second);
+      freed += it->first;
+    }
+    return freed;
+  }
+  // a pinned host image of at least n bytes (hipHostMallocPortable: usable from any device)
+  void *take_image(size_t n, size_t *got) {
+    {
+      std::lock_guard<std::mutex> lk(mu);
+      for (size_t i = 0; i < images.size(); i++)
+        if (images[i].second >= n) {
+          void *p = images[i].first;
+          *got = images[i].second;
+          images[i] = images.back();
+          images.pop_back();
+          return p;
+        }
+      if (images.size() >= 16) {  // only too-small ones are parked: drop one
+        (void)hipHostFree(images.back().first);
+        images.pop_back();
+      }
+    }
+    const size_t want = std::max<size_t>((n * 5) / 4, 1u << 20);
+    void *p = nullptr;
+    if (hipHostMalloc(&p, want, hipHostMallocPortable) != hipSuccess) return nullptr;
+    *got = want;
+    return p;
+  }
+  void give_image(void *p, size_t bytes) {
+    std::lock_guard<std::mutex> lk(mu);
+    images.emplace_back(p, bytes);
+  }
+  ~BufPool() {
+    for (auto &kv : free_) (void)hipFree(kv.second);
+    for (auto &im : images) (void)hipHostFree(im.first);
+  }
+};
+
+// a pinned staging image of at least n bytes: taken from the pool for one call, handed back when it goes
+struct ImageLease {
+  BufPool &pool;
+  void *p = nullptr;
+  size_t bytes = 0;
+  ImageLease(BufPool &pl, size_t n) : pool(pl) {
+    p = pool.take_image(n, &bytes);
+    if (!p) throw SlgError(SLG_ERR_OOM, "pinned staging image: hipHostMalloc failed");
+  }
+  ~ImageLease() { pool.give_image(p, bytes); }
+  ImageLease(const ImageLease &) = delete;
+  ImageLease &operator=(const ImageLease &) = delete;
+};
+
+// hipMalloc that drains `pool` (may be null) and tries once more when the device is out of memory
+inline void *device_alloc(size_t n, BufPool *pool) {
+  void *p = nullptr;
+  hipError_t e = hipMalloc(&p, n);
+  if (e == hipErrorOutOfMemory && pool && pool->drain() > 0) {
+    (void)hipGetLastError();
+    e = hipMalloc(&p, n);
+  }
+  if (e != hipSuccess) {
+    (void)hipGetLastError();
+    throw SlgError(e == hipErrorOutOfMemory ? SLG_ERR_OOM : SLG_ERR_DEVICE,
+                   std::string("hipMalloc(") + std::to_string(n) + "): " + hipGetErrorString(e));
+  }
+  return p;
+}
+
+// the calling thread on device `dev` for a scope, without error checks (destructors, destroy calls)
+struct DeviceScope {
+  int prev = -1;
+  explicit DeviceScope(int dev) {
+    (void)hipGetDevice(&prev);
+    (void)hipSetDevice(dev);
+  }
+  ~DeviceScope() {
+    if (prev >= 0) (void)hipSetDevice(prev);
+  }
+};
+
+struct DevBuf {
+  void *p = nullptr;
+  size_t bytes = 0;
+  BufPool *pool = nullptr;  // set: bytes is a size class and the block goes back to the pool
+  // relief: a pool to drain if the device is out of memory (the block itself is not pooled)
+  void alloc(size_t n, BufPool *relief = nullptr) {
+    release();
+    if (n == 0) n = 16;
+    p = device_alloc(n, relief);
+    bytes = n;
+  }
+  void alloc_pooled(BufPool *pl, size_t n) {
+    release();
+    size_t cls = BufPool::size_class(n ? n : 16);
+    p = pl->get(cls, &cls);
+    if (!p) p = device_alloc(cls, pl);
+    bytes = cls;
+    pool = pl;
+  }
+  void release() {
+    if (p && !(pool && pool->put(p, bytes))) (void)hipFree(p);
+    p = nullptr;
+    bytes = 0;
+    pool = nullptr;
+  }
+  ~DevBuf() { release(); }
+  DevBuf() = default;
+  DevBuf(const DevBuf &) = delete;
+  DevBuf &operator=(const DevBuf &) = delete;
+  DevBuf(DevBuf &&o) noexcept { swap(o); }
+  DevBuf &operator=(DevBuf &&o) noexcept {
+    if (this != &o) {
+      release();
+      swap(o);
+    }
+    return *this;
+  }
+  void swap(DevBuf &o) noexcept {
+    std::swap(p, o.p);
+    std::swap(bytes, o.bytes);
+    std::swap(pool, o.pool);
+  }
+  template <typename T>
+  T *as() const {
+    return static_cast<T *>(p);
+  }
+};
+
+// What a staged segment keeps for as long as any version of it lives: the posting arrays in the
+// padded device layout, and (slg_tuning.updatable) everything stage_impacts_kernel needs to derive the
+// impacts again when live_docs changes (slg_index_update_deleted).  Immutable after staging.
+struct PostingStore {
+  uint32_t n_docs = 0, n_terms = 0, n_fields = 0;
+  uint64_t n_postings = 0;
+  uint64_t null_idx = 0;               // SegDev::null_idx
+  std::vector<uint64_t> term_offsets;  // as given (unpadded); device position = + kListPad * term
+  std::vector<float> avgdl;            // [n_fields]
+  float k1 = 0.0f, b = 0.0f;
+  bool has_term_field = false;
+  bool updatable = false;
+  DevBuf d_docs;                                        // padded doc ids
+  DevBuf d_offs, d_tfs, d_tfield, d_avgdl, d_lenptrs;   // updatable only (else freed after staging)
+  std::vector<DevBuf> d_lens;                           // updatable only: per-field doc lengths
+  // vectors (field 0)
+  uint32_t vec_dim = 0, vec_rows = 0;
+  int32_t vec_metric = 0;
+  DevBuf d_vec_offsets, d_vec_values;
+  size_t device_bytes() const {
+    size_t n = d_docs.bytes + d_offs.bytes + d_tfs.bytes + d_tfield.bytes + d_avgdl.bytes + d_lenptrs.bytes +
+               d_vec_offsets.bytes + d_vec_values.bytes;
+    for (auto &l : d_lens) n += l.bytes;
+    return n;
+  }
+};
+
+// One VERSION of a staged segment: what depends on live_docs and the tombstones (impacts, champion
+// bounds, the bitmap).  Versions of one segment share its PostingStore.
+struct SegHost {
+  std::shared_ptr<PostingStore> store;
+  uint32_t n_docs = 0, n_terms = 0;
+  uint64_t n_postings = 0;
+  uint64_t null_idx = 0;
+  float docs = 0.0f;         // live_docs this version's idf values were computed with
+  std::vector<float> champ;  // host mirror of d_champ [V * kChampions] (query planning)
+  DevBuf d_imps, d_deleted, d_champ;
+  size_t device_bytes() const { return d_imps.bytes + d_deleted.bytes + d_champ.bytes; }
+};
+
+// a vector field beyond the one in the segment descriptors (slg_index_add_vector_field): per segment
+// shared stores (null: the segment has no vectors in the field)
+struct VecSegStore {
+  DevBuf offsets, values;
+  uint32_t dim = 0;
+};
+struct VecFieldHost {
+  uint32_t dim = 0;
+  int32_t metric = 0;
+  std::vector<std::shared_ptr<VecSegStore>> per_seg;
+  DevBuf d_vsegs;  // slg::VecSegDev[n_segs] of the state this object belongs to
+};
+
+// a registered doc filter: per segment a reject bitmap (deleted | ~filter); null = the filter predates
+// the segment (slg_index_add_segment) and cannot be used until it is registered again
+struct FilterData {
+  std::vector<std::shared_ptr<DevBuf>> per_seg;
+  bool complete() const {
+    for (auto &b : per_seg)
+      if (!b) return false;
+    return true;
+  }
+};
+
+// a registered sort field (slg_index_add_sort_field_*): per segment the u64 key of each order and the
+// presence bitmap; null = the field predates the segment (slg_index_add_segment)
+struct SortColumn {
+  DevBuf key[2];  // SLG_ORDER_ASC, SLG_ORDER_DESC
+  DevBuf present;
+};
+struct SortFieldData {
+  int kind = 0;  // 1 i64, 2 f64 (a cursor's value is encoded by it)
+  std::vector<std::shared_ptr<SortColumn>> per_seg;
+};
+
+// One immutable state of the index (see "index updates" in searchlite_gpu.h).  Batches hold the state
+// they were prepared on; the index holds the current one.
+struct IndexState {
+  uint64_t generation = 0;
+  int device = 0;
+  std::vector<std::shared_ptr<SegHost>> segs;
+  DevBuf d_segs;   // slg::SegDev[n_segs]
+  DevBuf d_vsegs;  // slg::VecSegDev[n_segs]
+  DevBuf d_doc_base;  // u32[n_segs + 1]: first flat doc of each segment (slg_vector_search_batch*)
+  uint64_t total_docs = 0;
+  std::vector<std::shared_ptr<VecFieldHost>> vfields;  // field id f >= 1 is vfields[f - 1]
+  std::vector<std::shared_ptr<FilterData>> filters;    // slot = filter id; null = free
+  std::vector<const uint32_t *> reject_host;           // flattened [filter * n_segs + seg] device pointers
+  DevBuf d_reject_table;                               // the same table on the device
+  std::map<int, std::shared_ptr<SortFieldData>> sort_fields;  // by id (ids are not reused)
+  ~IndexState() {
+    // kernels of already-destroyed batches, or rerank calls on the index stream, may still read the
+    // tables: retiring a state is rare (one per update), so wait for the device once
+    DeviceScope on(device);
+    (void)hipDeviceSynchronize();
+  }
+  // a filter id a query may name: registered, with a bitmap for every segment of this state
+  bool filter_usable(size_t f) const {
+    return f < filters.size() && filters[f] && filters[f]->complete() && filters[f]->per_seg.size() == segs.size();
+  }
+};
+
+}  // namespace slghost
+
+struct slg_index {
+  // work buffers of finished batches.  Shared with the batches (a batch that outlives the index
+  // still returns its buffers somewhere valid); declared first: destroyed last
+  slghost::BufPool pool;
+  slg_tuning tune{};
+  std::vector<slg_batch *> live;  // batches prepared on this index and not yet destroyed (under mu)
+  int device = 0;
+  hipStream_t own_stream = nullptr;
+  // descriptor uploads of slg_batch_prepare*: non-blocking streams picked by caller thread.  A plain
+  // hipMemcpy runs on the legacy default stream and waits for whatever the application has queued
+  // there (config 4: the previous batch's all-gather, shard merge and D2H) — planning would then
+  // serialise with the GPU work it is supposed to overlap
+  static constexpr int kUploadStreams = 8;
+  hipStream_t upload_streams[kUploadStreams] = {};
+  hipStream_t stream = nullptr;
+  std::shared_ptr<const slghost::IndexState> state;  // the current state (under mu)
+  std::atomic<uint64_t> generation{0};               // = state->generation, readable without the lock
+  std::mutex mu;
+  std::mutex update_mu;  // serialises slg_index_update_* / add_filter / add_vector_field (taken before mu)
+  int next_sort_field = 0;  // (under update_mu) sort field ids are never handed out again
+  // profiling of the scoring kernel
+  bool profile = false;
+  std::vector<std::pair<hipEvent_t, hipEvent_t>> prof_events;
+  size_t prof_used = 0;
+  // set by a scoring wave that had to give up on a round (chunk-loop guard): checked at fetch
+  slghost::DevBuf d_error_flag;
+  // work space of slg_vector_search_batch* (under mu; used on `stream` only, so a call that grows it
+  // frees the old block with hipFree, which waits for the device)
+  slghost::DevBuf vs_scratch;
+  std::shared_ptr<const slghost::IndexState> snapshot() {
+    std::lock_guard<std::mutex> lk(mu);
+    return state;
+  }
+};
+
+struct slg_batch {
+  using DevBuf = slghost::DevBuf;
+  slg_index *idx = nullptr;
+  std::shared_ptr<const slghost::IndexState> snap;  // the index state the batch was prepared on
+  uint32_t nq = 0, k = 0;
+  int strategy = 0;
+  uint32_t n_sq = 0, n_slices = 0, n_terms = 0, n_boundaries = 0, max_terms = 0;
+  bool uniform = false;  // every sub-query fits the one-list-per-slot kernel
+  bool plan_batch = false;  // some sub-query has a score plan (multi kernel only)
+  bool nested = false;      // some sub-query has a two-level plan (groups of leaves)
+  bool deep = false;        // some sub-query has a score tree of more than two levels
+  const slg::PlanNode *d_nodes = nullptr;
+  bool pruned = false;      // some sub-query has non-essential lists (MaxScore)
+  bool multi = false;    // many-term form of it (slg_score_multi.hpp); else the packed kernel
+  uint64_t n_postings = 0, n_postings_essential = 0, n_rounds = 0;
+  std::vector<uint64_t> q_postings;  // per query (stats.postings_advanced)
+  bool launched = false;             // slg_batch_run was called at least once
+  bool own_stream_set = false;       // slg_batch_set_stream: run on `stream` instead of the index's
+  hipStream_t stream = nullptr;
+  DevBuf d_desc;                     // packed descriptors
+  const slg::RoundQuery *d_sq = nullptr;
+  const slg::TermRef *d_terms = nullptr;
+  const uint32_t *d_slice_sq = nullptr;
+  const uint32_t *d_slice_seg = nullptr;
+  const uint32_t *d_slice_order = nullptr;
+  const slg::QueryRef *d_queries = nullptr;
+  const uint32_t *d_bnd_coarse = nullptr;
+  DevBuf d_bounds, d_rdoc, d_slice_tk, d_slice_doc, d_q_scored, d_slice_desc;
+  DevBuf d_q_filter;       // [nq] 0 = none, f + 1 (select_topk_kernel); empty when unfiltered
+  bool cand_mode = false;  // uniform kernel, k > 256: candidates + select_topk_kernel
+  DevBuf d_cand, d_slice_cbeg, d_slice_ccnt;
+  // field-sorted batch (slg_batch_prepare_sorted): candidates of every matched doc + select_sorted_kernel
+  bool sorted = false;
+  uint32_t score_k = 0;  // k the scoring kernel runs with (a sorted batch: slgplan::planning_k)
+  uint32_t n_sort_parts = 0, sort_score_parts = 0, sort_desc_parts = 0;
+  DevBuf d_sort_cols;  // slg::SortColDev[kSortMaxParts * n_segs]
+  DevBuf d_matched;    // u64[nq] accepted docs (sorted and cursor batches)
+  // cursor batch (slg_batch_prepare_after): score order (!sorted: select_topk_kernel<true>) or a field sort
+  // (select_sorted_kernel<true>)
+  bool after = false;
+  DevBuf d_cursor;  // u32[nq * slg::kCursorStride]: has_cursor, then the key words of the select kernel
+  DevBuf d_seen;    // u32[nq] the cursor's key was seen
+  DevBuf d_out;  // the result block (slghost::ResultBlock) + the error word
+  uint32_t *d_out_doc = nullptr, *d_out_seg = nullptr, *d_out_count = nullptr;
+  float *d_out_score = nullptr;
+  DevBuf d_stamps;  // SLG_STAMPS diagnostic builds
+  DevBuf d_blk_skip;  // block skipping: postings of non-essential lists that were never loaded (u64)
+  // index-sharded runs (slg_batch_run_sharded): the gathered result blocks of all ranks and the merged
+  // top-k, a result block too
+  DevBuf d_gather, d_merged;
+  slg_shard_group *shard_group = nullptr;  // the group of the last sharded run (timing goes there)
+  hipEvent_t ev_shard[4] = {nullptr, nullptr, nullptr, nullptr};  // start | local kernels done | gathered | merged
+  bool shard_timed = false;
+  uint64_t n_postings_nonessential = 0;  // postings of the pruning-classified (non-essential) lists
+};
+
+namespace slghost __attribute__((visibility("hidden"))) {
+
+struct DeviceGuard {
+  int prev = -1;
+  explicit DeviceGuard(int dev) {
+    SLG_HIP(hipGetDevice(&prev));
+    if (prev != dev) SLG_HIP(hipSetDevice(dev));
+  }
+  ~DeviceGuard() {
+    if (prev >= 0) (void)hipSetDevice(prev);
+  }
+};
+
+inline int kregs_for(uint32_t k) {
+  if (k <= 64) return 1;
+  if (k <= 128) return 2;
+  if (k <= 256) return 4;
+  if (k <= 512) return 8;
+  return 16;
+}
+
+// Waiting for a stream is the blocking hipStreamSynchronize.  (Polling hipStreamQuery first — to spare a
+// small batch the sleep / wake-up of the blocking wait — was built and measured: with 8 caller threads
+// polling, config 2's host-inclusive rate fell from 11M to 2.2M queries/s and fetch + destroy grew from
+// 0.28 to 1.36 ms per batch: the query takes a runtime lock the other threads' launches and copies need.)
+inline hipError_t wait_stream(hipStream_t st) { return hipStreamSynchronize(st); }
+
+// the stream a batch runs on (the caller holds ix->mu) ...
+inline hipStream_t batch_stream(const slg_batch *b) { return b->own_stream_set ? b->stream : b->idx->stream; }
+// ... and the same for a caller that goes on to wait for it: read under the index mutex, which is NOT held
+// while waiting, so other host threads keep launching their batches
+inline hipStream_t locked_stream(const slg_batch *b) {
+  std::lock_guard<std::mutex> lk(b->idx->mu);
+  return batch_stream(b);
+}
+
+// The result block of a batch of nq queries at k: doc[nq*k] | seg[nq*k] | score[nq*k] | count[nq], 32-bit
+// words in one allocation, so that one copy (to the host, or an all-gather between ranks) moves a batch's
+// results.  A batch's own block (slg_batch::d_out) carries one more word behind it: the index's error word
+// as the batch's last kernel saw it (MergeParams::out_flag).
+struct ResultBlock {
+  size_t n, nq;  // n = nq * k entries per array
+  ResultBlock(uint32_t nq_, uint32_t k) : n((size_t)nq_ * k), nq(nq_) {}
+  size_t words() const { return 3 * n + nq; }
+  size_t words_with_flag() const { return words() + 1; }
+  uint32_t *doc(uint32_t *base) const { return base; }
+  uint32_t *seg(uint32_t *base) const { return base + n; }
+  float *score(uint32_t *base) const { return reinterpret_cast<float *>(base + 2 * n); }
+  uint32_t *count(uint32_t *base) const { return base + 3 * n; }
+  uint32_t *flag(uint32_t *base) const { return base + words(); }
+  // a host copy of the block to the caller's arrays
+  void unpack(uint32_t *host_block, uint32_t *out_doc, uint32_t *out_seg, float *out_score,
+              uint32_t *out_count) const {
+    if (n) {
+      std::memcpy(out_doc, doc(host_block), n * 4);
+      std::memcpy(out_seg, seg(host_block), n * 4);
+      std::memcpy(out_score, score(host_block), n * 4);
+    }
+    std::memcpy(out_count, count(host_block), nq * 4);
+  }
+};
+
+// The host arrays of one call staged through pooled device buffers on one stream (the host-array forms
+// of rerank and vector search): up() allocates a buffer of n elements and, src given, queues its upload;
+// down() queues the copy back if the caller wants the array.  The destructor waits for the stream on
+// every exit before the buffers go back to the pool, so no block is reused while a queued copy or kernel
+// may still touch it.
+struct Staging {
+  BufPool *pool;
+  hipStream_t st;
+  std::vector<DevBuf> bufs;
+  Staging(BufPool *pl, hipStream_t s) : pool(pl), st(s) { bufs.reserve(16); }
+  ~Staging() { (void)hipStreamSynchronize(st); }
+  template <typename T>
+  T *up(const T *src, size_t n) {
+    bufs.emplace_back();
+    bufs.back().alloc_pooled(pool, n * sizeof(T));
+    if (src && n) SLG_HIP(hipMemcpyAsync(bufs.back().p, src, n * sizeof(T), hipMemcpyHostToDevice, st));
+    return bufs.back().as<T>();
+  }
+  template <typename T>
+  void down(T *dst, const T *src, size_t n) {
+    if (dst && n) SLG_HIP(hipMemcpyAsync(dst, src, n * sizeof(T), hipMemcpyDeviceToHost, st));
+  }
+};
+
+// ---- defined in one unit, used by others -------------------------------------------------------
+// slg_batch.hip: free everything a batch holds on the device; with `to_pool` false the blocks go straight
+// back to the runtime (the index and its pool are going away)
+void release_batch_buffers(slg_batch *b, bool to_pool);
+// slg_batch.hip: the merge of several ranks' (or shards') rows
+void launch_shard_merge(const slg::ShardMergeParams &mp, hipStream_t st);
+// slg_rerank.hip: dimension / metric / device stores of vector field f (0: the field of the segment
+// descriptors; mixed_metric: its segments may differ in metric — the single-clause kernel reads it per
+// segment — and *metric is the last one's)
+void field_facts(const IndexState &S, uint32_t f, uint32_t *dim, int32_t *metric, const slg::VecSegDev **vsegs,
+                 bool mixed_metric = false);
+
+}  // namespace slghost

@@ -1,0 +1,890 @@
+// slg_index.hip — the index: creation and destruction, tuning, segment staging, the immutable states and
+// their updates (filters, sort fields, vector fields, tombstones, segments), profiling switches.
+//
+// The host units (this one, slg_batch.hip, slg_shard.hip, slg_rerank.hip, slg_vsearch.hip; what they
+// share: slg_host.hpp) are the host side of the C ABI declared in include/searchlite_gpu.h.  They
+// mirror, for the GPU-eligible request shape, what IndexReader::search_segment does before and after
+// the scorer call (searchlite-core/src/api/reader.rs:2971-3000 build the ScoredTerm list; :3075-3099
+// call the scorer; :2776-2778 merge across segments), but for a whole batch of queries at once.  The
+// product path has NO CPU fallback: every entry point either runs the HIP kernels or fails with an
+// error code.
+#include "slg_host.hpp"
+
+#include <cmath>
+#include <cstdlib>
+
+#include "slg_stage.hpp"
+
+slghost::LastError &slghost::last_error() {
+  thread_local LastError le;
+  return le;
+}
+using namespace slghost;
+
+namespace {
+
+// (the environment is read in slg_tuning_default() only)
+uint32_t env_u32(const char *name, uint32_t dflt) {
+  const char *v = std::getenv(name);
+  if (!v || !*v) return dflt;
+  return (uint32_t)std::strtoul(v, nullptr, 10);
+}
+int32_t env_i32(const char *name, int32_t dflt) {
+  const char *v = std::getenv(name);
+  if (!v || !*v) return dflt;
+  return (int32_t)std::strtol(v, nullptr, 10);
+}
+
+void validate_segment(const slg_segment_desc &d, uint32_t si, bool deep) {
+  const std::string pfx = "segment " + std::to_string(si) + ": ";
+  SLG_REQUIRE(d.term_offsets != nullptr, pfx + "term_offsets is NULL");
+  SLG_REQUIRE(d.n_fields >= 1 && d.field_avgdl && d.field_doc_len, pfx + "field arrays missing");
+  SLG_REQUIRE(d.term_offsets[0] == 0, pfx + "term_offsets[0] != 0");
+  const uint64_t P = d.term_offsets[d.n_terms];
+  SLG_REQUIRE(P == 0 || (d.doc_ids && d.tfs), pfx + "doc_ids/tfs missing");
+  for (uint32_t t = 0; t < d.n_terms; t++) {
+    const uint64_t a = d.term_offsets[t], b = d.term_offsets[t + 1];
+    SLG_REQUIRE(b >= a, pfx + "term_offsets not monotone");
+    SLG_REQUIRE(b - a <= 0xFFFFFFFEull, pfx + "posting list too long");
+    if (d.term_field) SLG_REQUIRE(d.term_field[t] < d.n_fields, pfx + "term_field out of range");
+    // The kernels index per-doc bitmaps with the raw doc id and the planner interpolates on
+    // doc / n_docs, so ids must be < n_docs: checked on every posting, or (validate == 0, where
+    // the caller vouches for increasing ids) on the last = largest posting of each list.
+    if (deep) {
+      for (uint64_t i = a; i < b; i++) {
+        SLG_REQUIRE(d.doc_ids[i] < d.n_docs,
+                    pfx + "doc id >= n_docs in term " + std::to_string(t));
+        SLG_REQUIRE(i == a || d.doc_ids[i] > d.doc_ids[i - 1],
+                    pfx + "doc ids not strictly increasing in term " + std::to_string(t));
+      }
+    } else if (b > a) {
+      SLG_REQUIRE(d.doc_ids[b - 1] < d.n_docs, pfx + "doc id >= n_docs in term " + std::to_string(t));
+    }
+  }
+  if (d.vec_dim) {
+    SLG_REQUIRE(d.vec_offsets && (d.vec_values || d.vec_rows == 0), pfx + "vector arrays missing");
+    SLG_REQUIRE(d.vec_metric == SLG_METRIC_COSINE || d.vec_metric == SLG_METRIC_L2,
+                pfx + "bad vec_metric");
+    if (deep)
+      for (uint32_t i = 0; i < d.n_docs; i++)
+        SLG_REQUIRE(d.vec_offsets[i] == SLG_NO_VECTOR || d.vec_offsets[i] < d.vec_rows,
+                    pfx + "vec_offsets out of range");
+  }
+}
+
+// The version of a staged segment for (deleted bitmap, live_docs): impacts (stage_impacts_kernel:
+// query/bm25.rs:1-6 with idf from the host's logf), champion bounds, host mirror.  At creation the
+// kernel also scatters the uploaded doc ids into the padded layout (docs_in != nullptr); for an
+// update it reads them back from there.  Temporaries of a non-updatable store are passed in `tmp`.
+struct StageTemps {
+  const uint32_t *docs_in = nullptr;   // [P] unpadded doc ids as uploaded (creation only)
+};
+void derive_version(slg_index *ix, const std::shared_ptr<PostingStore> &ps, SegHost &sh, const uint8_t *deleted,
+                    float docs, const StageTemps &tmp) {
+  hipStream_t st = ix->stream;
+  sh.store = ps;
+  sh.n_docs = ps->n_docs;
+  sh.n_terms = ps->n_terms;
+  sh.n_postings = ps->n_postings;
+  sh.null_idx = ps->null_idx;
+  sh.docs = docs;
+  const uint64_t P = ps->n_postings;
+  const uint64_t P_pad = P + (uint64_t)slg::kListPad * (uint64_t)ps->n_terms + (uint64_t)slg::kNullRun;
+  sh.d_imps.alloc(P_pad * 4, &ix->pool);
+  SLG_HIP(hipMemsetAsync(sh.d_imps.p, 0, P_pad * 4, st));
+  if (deleted) {
+    const size_t words = ((size_t)ps->n_docs + 31) / 32;
+    std::vector<uint32_t> w(words ? words : 1, 0u);
+    std::memcpy(w.data(), deleted, ((size_t)ps->n_docs + 7) / 8);
+    sh.d_deleted.alloc(w.size() * 4, &ix->pool);
+    SLG_HIP(hipMemcpy(sh.d_deleted.p, w.data(), w.size() * 4, hipMemcpyHostToDevice));
+  }
+  if (P == 0) return;
+  // idf per term: query/bm25.rs:2 with df = postings.len() as f32 (wand.rs:108,471)
+  std::vector<float> idf(ps->n_terms);
+  for (uint32_t t = 0; t < ps->n_terms; t++) {
+    const float df = (float)(uint32_t)(ps->term_offsets[t + 1] - ps->term_offsets[t]);
+    idf[t] = fmaxf(logf((docs - df + 0.5f) / (df + 0.5f)), 0.0f) + 1.0f;
+  }
+  DevBuf d_idf;
+  d_idf.alloc((size_t)ps->n_terms * 4, &ix->pool);
+  SLG_HIP(hipMemcpyAsync(d_idf.p, idf.data(), (size_t)ps->n_terms * 4, hipMemcpyHostToDevice, st));
+  slg::StageParams sp{};
+  sp.n_postings = P;
+  sp.n_terms = ps->n_terms;
+  sp.n_docs = ps->n_docs;
+  sp.term_offsets = ps->d_offs.as<uint64_t>();
+  sp.docs = tmp.docs_in;
+  sp.docs_out = ps->d_docs.as<uint32_t>();
+  sp.tfs = ps->d_tfs.as<uint32_t>();
+  sp.term_idf = d_idf.as<float>();
+  sp.term_field = ps->has_term_field ? ps->d_tfield.as<uint16_t>() : nullptr;
+  sp.field_doc_len = ps->d_lenptrs.as<const float *>();
+  sp.field_avgdl = ps->d_avgdl.as<float>();
+  sp.k1 = ps->k1;
+  sp.b = ps->b;
+  sp.imps = sh.d_imps.as<float>();
+  const uint64_t want = (P + 255) / 256;
+  const uint32_t blocks = (uint32_t)std::min<uint64_t>(want, 256ull * 32);
+  hipLaunchKernelGGL(slg::stage_impacts_kernel, dim3(blocks), dim3(256), 0, st, sp);
+  SLG_HIP(hipGetLastError());
+  if (ix->tune.champions) {
+    sh.d_champ.alloc((size_t)ps->n_terms * slg::kChampions * 4, &ix->pool);
+    slg::ChampParams cp{};
+    cp.term_offsets = ps->d_offs.as<uint64_t>();
+    cp.imps = sh.d_imps.as<float>();
+    cp.docs = ps->d_docs.as<uint32_t>();
+    cp.deleted = sh.d_deleted.as<uint32_t>();
+    cp.champ = sh.d_champ.as<float>();
+    cp.n_terms = ps->n_terms;
+    const uint32_t cblocks = std::min<uint32_t>((ps->n_terms + 3) / 4, 256u * 16);
+    hipLaunchKernelGGL(slg::stage_champions_kernel, dim3(cblocks ? cblocks : 1), dim3(256), 0, st, cp);
+    SLG_HIP(hipGetLastError());
+  }
+  SLG_HIP(hipStreamSynchronize(st));  // d_idf dies here
+  if (sh.d_champ.p) {
+    sh.champ.resize((size_t)ps->n_terms * slg::kChampions);
+    SLG_HIP(hipMemcpy(sh.champ.data(), sh.d_champ.p, sh.champ.size() * 4, hipMemcpyDeviceToHost));
+  }
+}
+
+std::shared_ptr<SegHost> stage_segment(slg_index *ix, const slg_segment_desc &d) {
+  hipStream_t st = ix->stream;
+  auto ps = std::make_shared<PostingStore>();
+  ps->n_docs = d.n_docs;
+  ps->n_terms = d.n_terms;
+  ps->n_fields = d.n_fields;
+  ps->term_offsets.assign(d.term_offsets, d.term_offsets + d.n_terms + 1);
+  ps->avgdl.assign(d.field_avgdl, d.field_avgdl + d.n_fields);
+  ps->k1 = d.k1;
+  ps->b = d.b;
+  ps->has_term_field = d.term_field != nullptr;
+  ps->updatable = ix->tune.updatable != 0;
+  const uint64_t P = ps->term_offsets[d.n_terms];
+  ps->n_postings = P;
+
+  // padded layout (SegDev): every list is followed by kListPad sentinel entries, + a run of kNullRun
+  // at the end (null_idx): the scoring kernels load whole 64-lane slots starting at any posting
+  const uint64_t P_pad = P + (uint64_t)slg::kListPad * (uint64_t)d.n_terms + (uint64_t)slg::kNullRun;
+  ps->null_idx = P + (uint64_t)slg::kListPad * d.n_terms;
+  ps->d_docs.alloc(P_pad * 4, &ix->pool);
+  SLG_HIP(hipMemsetAsync(ps->d_docs.p, 0xFF, P_pad * 4, st));
+  DevBuf d_docs_in;  // the uploaded (unpadded) doc ids: staging only
+  if (P > 0) {
+    d_docs_in.alloc(P * 4, &ix->pool);
+    ps->d_tfs.alloc(P * 4, &ix->pool);
+    SLG_HIP(hipMemcpyAsync(d_docs_in.p, d.doc_ids, P * 4, hipMemcpyHostToDevice, st));
+    SLG_HIP(hipMemcpyAsync(ps->d_tfs.p, d.tfs, P * 4, hipMemcpyHostToDevice, st));
+    ps->d_offs.alloc(((size_t)d.n_terms + 1) * 8, &ix->pool);
+    SLG_HIP(hipMemcpyAsync(ps->d_offs.p, ps->term_offsets.data(), ((size_t)d.n_terms + 1) * 8,
+                           hipMemcpyHostToDevice, st));
+    if (d.term_field) {
+      ps->d_tfield.alloc((size_t)d.n_terms * 2, &ix->pool);
+      SLG_HIP(hipMemcpyAsync(ps->d_tfield.p, d.term_field, (size_t)d.n_terms * 2, hipMemcpyHostToDevice, st));
+    }
+    ps->d_avgdl.alloc((size_t)d.n_fields * 4, &ix->pool);
+    SLG_HIP(hipMemcpyAsync(ps->d_avgdl.p, d.field_avgdl, (size_t)d.n_fields * 4, hipMemcpyHostToDevice, st));
+    ps->d_lens.resize(d.n_fields);
+    std::vector<const float *> lenptrs(d.n_fields, nullptr);
+    for (uint32_t f = 0; f < d.n_fields; f++) {
+      if (d.field_doc_len[f] && d.n_docs) {
+        ps->d_lens[f].alloc((size_t)d.n_docs * 4, &ix->pool);
+        SLG_HIP(hipMemcpyAsync(ps->d_lens[f].p, d.field_doc_len[f], (size_t)d.n_docs * 4, hipMemcpyHostToDevice, st));
+        lenptrs[f] = ps->d_lens[f].as<float>();
+      }
+    }
+    ps->d_lenptrs.alloc((size_t)d.n_fields * sizeof(float *), &ix->pool);
+    SLG_HIP(hipMemcpy(ps->d_lenptrs.p, lenptrs.data(), (size_t)d.n_fields * sizeof(float *), hipMemcpyHostToDevice));
+  }
+  auto sh = std::make_shared<SegHost>();
+  StageTemps tmp;
+  tmp.docs_in = d_docs_in.as<uint32_t>();
+  derive_version(ix, ps, *sh, d.deleted, d.docs, tmp);  // (synchronises the stream when P > 0)
+  if (!ps->updatable) {  // what only an update would read again
+    ps->d_tfs.release();
+    ps->d_offs.release();
+    ps->d_tfield.release();
+    ps->d_avgdl.release();
+    ps->d_lenptrs.release();
+    ps->d_lens.clear();
+  }
+  if (d.vec_dim) {
+    ps->vec_dim = d.vec_dim;
+    ps->vec_rows = d.vec_rows;
+    ps->vec_metric = d.vec_metric;
+    ps->d_vec_offsets.alloc((size_t)d.n_docs * 4, &ix->pool);
+    if (d.n_docs)
+      SLG_HIP(hipMemcpy(ps->d_vec_offsets.p, d.vec_offsets, (size_t)d.n_docs * 4, hipMemcpyHostToDevice));
+    const size_t vb = (size_t)d.vec_rows * d.vec_dim * 4;
+    ps->d_vec_values.alloc(vb, &ix->pool);
+    if (vb) SLG_HIP(hipMemcpy(ps->d_vec_values.p, d.vec_values, vb, hipMemcpyHostToDevice));
+  }
+  SLG_HIP(hipStreamSynchronize(st));
+  return sh;
+}
+
+// the device tables of a state (segment descriptors, vector stores, reject-bitmap pointers): small,
+// rebuilt for every state
+void finish_state(slg_index *ix, IndexState &s) {
+  const size_t n_segs = s.segs.size();
+  s.device = ix->device;
+  std::vector<slg::SegDev> sd(n_segs);
+  std::vector<slg::VecSegDev> vd(n_segs);
+  // a segment without vectors takes the field's metric (the last one's, as field_facts reports it): its
+  // docs score missing_vector_score of the field's metric, not of the descriptor's unchecked vec_metric
+  int32_t field_metric = 0;
+  for (size_t i = 0; i < n_segs; i++)
+    if (s.segs[i]->store->vec_dim) field_metric = s.segs[i]->store->vec_metric;
+  for (size_t i = 0; i < n_segs; i++) {
+    const SegHost &sh = *s.segs[i];
+    sd[i].docs = sh.store->d_docs.as<uint32_t>();
+    sd[i].imps = sh.d_imps.as<float>();
+    sd[i].deleted = sh.d_deleted.as<uint32_t>();
+    sd[i].champ = sh.d_champ.as<float>();
+    sd[i].n_docs = sh.n_docs;
+    sd[i].pad = 0;
+    sd[i].null_idx = sh.null_idx;
+    vd[i].offsets = sh.store->d_vec_offsets.as<uint32_t>();
+    vd[i].values = sh.store->d_vec_values.as<float>();
+    vd[i].n_docs = sh.n_docs;
+    vd[i].dim = sh.store->vec_dim;
+    vd[i].metric = sh.store->vec_dim ? sh.store->vec_metric : field_metric;
+    vd[i].pad = 0;
+  }
+  s.d_segs.alloc(std::max<size_t>(n_segs, 1) * sizeof(slg::SegDev), &ix->pool);
+  s.d_vsegs.alloc(std::max<size_t>(n_segs, 1) * sizeof(slg::VecSegDev), &ix->pool);
+  if (n_segs) {
+    SLG_HIP(hipMemcpy(s.d_segs.p, sd.data(), n_segs * sizeof(slg::SegDev), hipMemcpyHostToDevice));
+    SLG_HIP(hipMemcpy(s.d_vsegs.p, vd.data(), n_segs * sizeof(slg::VecSegDev), hipMemcpyHostToDevice));
+  }
+  for (auto &vfp : s.vfields) {  // (the field objects of a new state are fresh copies: see copy_state)
+    VecFieldHost &vf = *vfp;
+    std::vector<slg::VecSegDev> fv(n_segs);
+    for (size_t i = 0; i < n_segs; i++) {
+      fv[i] = slg::VecSegDev{nullptr, nullptr, s.segs[i]->n_docs, 0u, vf.metric, 0u};
+      if (i < vf.per_seg.size() && vf.per_seg[i]) {
+        fv[i].offsets = vf.per_seg[i]->offsets.as<uint32_t>();
+        fv[i].values = vf.per_seg[i]->values.as<float>();
+        fv[i].dim = vf.per_seg[i]->dim;
+      }
+    }
+    vf.d_vsegs.alloc(std::max<size_t>(n_segs, 1) * sizeof(slg::VecSegDev), &ix->pool);
+    if (n_segs) SLG_HIP(hipMemcpy(vf.d_vsegs.p, fv.data(), n_segs * sizeof(slg::VecSegDev), hipMemcpyHostToDevice));
+  }
+  std::vector<uint32_t> base(n_segs + 1, 0u);
+  uint64_t acc = 0;
+  for (size_t i = 0; i < n_segs; i++) {
+    base[i] = (uint32_t)std::min<uint64_t>(acc, 0xFFFFFFFFull);
+    acc += s.segs[i]->n_docs;
+  }
+  base[n_segs] = (uint32_t)std::min<uint64_t>(acc, 0xFFFFFFFFull);
+  s.total_docs = acc;
+  s.d_doc_base.alloc(base.size() * 4, &ix->pool);
+  SLG_HIP(hipMemcpy(s.d_doc_base.p, base.data(), base.size() * 4, hipMemcpyHostToDevice));
+  s.reject_host.assign(s.filters.size() * n_segs, nullptr);
+  for (size_t f = 0; f < s.filters.size(); f++)
+    if (s.filters[f])
+      for (size_t i = 0; i < n_segs && i < s.filters[f]->per_seg.size(); i++)
+        if (s.filters[f]->per_seg[i]) s.reject_host[f * n_segs + i] = s.filters[f]->per_seg[i]->as<uint32_t>();
+  s.d_reject_table.alloc(std::max<size_t>(s.reject_host.size(), 1) * sizeof(void *), &ix->pool);
+  if (!s.reject_host.empty())
+    SLG_HIP(hipMemcpy(s.d_reject_table.p, s.reject_host.data(), s.reject_host.size() * sizeof(void *),
+                      hipMemcpyHostToDevice));
+}
+
+// the next state: the current one's segments / fields / filters (shared), the device tables not yet built
+std::unique_ptr<IndexState> copy_state(const IndexState &cur) {
+  auto n = std::make_unique<IndexState>();
+  n->generation = cur.generation + 1;
+  n->device = cur.device;
+  n->segs = cur.segs;
+  n->filters = cur.filters;
+  n->sort_fields = cur.sort_fields;
+  for (auto &vf : cur.vfields) {  // the per-state table d_vsegs is rebuilt: own object, shared stores
+    auto c = std::make_shared<VecFieldHost>();
+    c->dim = vf->dim;
+    c->metric = vf->metric;
+    c->per_seg = vf->per_seg;
+    n->vfields.push_back(std::move(c));
+  }
+  return n;
+}
+
+void publish(slg_index *ix, std::unique_ptr<IndexState> ns) {
+  std::shared_ptr<const IndexState> keep;  // (the old state may die here: outside the lock)
+  std::shared_ptr<const IndexState> fresh(std::move(ns));
+  {
+    std::lock_guard<std::mutex> lk(ix->mu);
+    keep.swap(ix->state);
+    ix->state = fresh;
+    ix->generation.store(fresh->generation, std::memory_order_release);
+  }
+}
+
+// One change of the index's state: updates are serialised by update_mu; change(cur, next) turns a copy
+// of the current state into the next one on the index's device (whatever it throws leaves the index as it
+// was), then the device tables are built and the state is published.  Batches prepared on earlier states
+// keep theirs: nobody waits for the device here.  new_generation false: a change no manifest snapshot
+// sees (filters, sort fields, vector fields).
+template <typename F>
+void update_state(slg_index *ix, bool new_generation, F &&change) {
+  std::lock_guard<std::mutex> ulk(ix->update_mu);
+  const auto cur = ix->snapshot();
+  DeviceGuard g(ix->device);
+  auto ns = copy_state(*cur);
+  if (!new_generation) ns->generation = cur->generation;
+  change(*cur, *ns);
+  finish_state(ix, *ns);
+  publish(ix, std::move(ns));
+}
+
+// every per-segment table of a state (filters, sort fields, vector fields) reshaped by op when the
+// segment list changes; filters and sort fields are shared with earlier states: copy on write
+template <typename Op>
+void reshape_per_segment(IndexState &ns, Op op) {
+  for (auto &f : ns.filters)
+    if (f) {
+      auto nf = std::make_shared<FilterData>(*f);
+      op(nf->per_seg);
+      f = std::move(nf);
+    }
+  for (auto &sf : ns.sort_fields) {
+    auto nf = std::make_shared<SortFieldData>(*sf.second);
+    op(nf->per_seg);
+    sf.second = std::move(nf);
+  }
+  for (auto &vf : ns.vfields) op(vf->per_seg);  // (the field objects of a new state are fresh copies)
+}
+
+size_t state_device_bytes(const IndexState &s) {
+  size_t n = s.d_segs.bytes + s.d_vsegs.bytes + s.d_reject_table.bytes + s.d_doc_base.bytes;
+  for (auto &sh : s.segs) n += sh->device_bytes() + sh->store->device_bytes();
+  for (auto &f : s.filters)
+    if (f)
+      for (auto &b : f->per_seg)
+        if (b) n += b->bytes;
+  for (auto &sf : s.sort_fields)
+    for (auto &c : sf.second->per_seg)
+      if (c) n += c->key[0].bytes + c->key[1].bytes + c->present.bytes;
+  for (auto &vf : s.vfields) {
+    n += vf->d_vsegs.bytes;
+    for (auto &v : vf->per_seg)
+      if (v) n += v->offsets.bytes + v->values.bytes;
+  }
+  return n;
+}
+
+}  // namespace
+
+extern "C" {
+
+uint32_t slg_abi_version(void) { return SLG_ABI_VERSION; }
+
+const char *slg_last_error(void) { return last_error().msg.c_str(); }
+int slg_last_error_code(void) { return last_error().code; }
+
+int slg_device_count(void) {
+  int n = 0;
+  hipError_t e = hipGetDeviceCount(&n);
+  if (e != hipSuccess) {
+    last_error().msg = std::string("hipGetDeviceCount: ") + hipGetErrorString(e);
+    return SLG_ERR_DEVICE;
+  }
+  return n;
+}
+
+void slg_tuning_default(slg_tuning *t) {
+  if (!t) return;
+  std::memset(t, 0, sizeof(*t));
+  t->struct_size = (uint32_t)sizeof(slg_tuning);
+  t->validate = env_i32("SLG_VALIDATE", 1) != 0;
+  t->champions = env_i32("SLG_NO_CHAMPIONS", 0) == 0;
+  t->allow_any_arch = env_i32("SLG_ALLOW_ANY_ARCH", 0) != 0;
+  t->pruning = env_i32("SLG_MAXSCORE", -1);
+  t->uniform_max_terms = env_u32("SLG_UNIFORM_MAX_TERMS", 8);
+  t->uniform_round_target = env_u32("SLG_UNIFORM_ROUND_TARGET", 0);
+  t->multi_round_target = env_u32("SLG_MULTI_ROUND_TARGET", slg::kMultiTarget);
+  t->probe_target = env_u32("SLG_PROBE_TARGET", 2048);
+  t->rounds_per_slice = env_u32("SLG_ROUNDS_PER_SLICE", 0);
+  t->max_rounds_per_slice = env_u32("SLG_MAX_ROUNDS_PER_SLICE", 0);
+  t->slices_per_subquery = env_u32("SLG_SLICES_PER_SUBQUERY", 16);
+  t->cand_mode = 1;  // (reserved: k > 256 always runs on candidates + select)
+  t->slice_order = env_i32("SLG_NO_SLICE_ORDER", 0) == 0;
+  t->block_max = env_i32("SLG_NO_BLOCK_MAX", 0) == 0;
+  t->pool_cap_mb = env_u32("SLG_POOL_CAP_MB", 0);
+  t->uniform_kernel = env_u32("SLG_UNIFORM_KERNEL", 4);
+  t->uniform_sigma_x100 = env_u32("SLG_UNIFORM_SIGMA", 0);
+  t->inline_cuts = env_i32("SLG_INLINE_CUTS", -1);
+  t->updatable = env_i32("SLG_NOT_UPDATABLE", 0) == 0;
+  t->uniform_plans = env_i32("SLG_NO_UNIFORM_PLANS", 0) == 0;
+  t->score_waves_per_simd = 0;  // (reserved: persistent scoring waves were removed)
+}
+
+slg_index *slg_index_create(const slg_segment_desc *segs, uint32_t n_segs, int device) {
+  return slg_index_create_tuned(segs, n_segs, device, nullptr);
+}
+
+slg_index *slg_index_create_tuned(const slg_segment_desc *segs, uint32_t n_segs, int device,
+                                  const slg_tuning *tuning) {
+  slg_index *ix = nullptr;
+  int rc = guarded([&] {
+    SLG_REQUIRE(segs != nullptr && n_segs >= 1, "segs is NULL or n_segs == 0");
+    slg_tuning tune;
+    if (tuning) {
+      SLG_REQUIRE(tuning->struct_size == sizeof(slg_tuning), "slg_tuning.struct_size mismatch");
+      tune = *tuning;
+    } else {
+      slg_tuning_default(&tune);
+    }
+    // (4 is the only form left; a zero-initialised struct from a C or Rust caller is rejected here)
+    if (tune.uniform_kernel == 2 || tune.uniform_kernel == 3)
+      throw SlgError(SLG_ERR_UNSUPPORTED, "slg_tuning.uniform_kernel 2 / 3: those forms of the few-term kernel were removed");
+    SLG_REQUIRE(tune.uniform_kernel == 4, "slg_tuning.uniform_kernel must be 4");
+    if (tune.score_waves_per_simd != 0)
+      throw SlgError(SLG_ERR_UNSUPPORTED, "slg_tuning.score_waves_per_simd must be 0: persistent scoring waves were removed");
+    if (tune.cand_mode != 1)
+      throw SlgError(SLG_ERR_UNSUPPORTED, "slg_tuning.cand_mode must be 1: 256 < k <= 1024 has no register top-k path");
+    tune.uniform_max_terms = std::min<uint32_t>(tune.uniform_max_terms, slg::kU4MaxLists);
+    tune.max_rounds_per_slice = std::min<uint32_t>(tune.max_rounds_per_slice, slg::kMaxRoundsPerSlice);
+    tune.slices_per_subquery = std::max<uint32_t>(1, tune.slices_per_subquery);
+    for (uint32_t s = 0; s < n_segs; s++) validate_segment(segs[s], s, tune.validate != 0);
+    int ndev = 0;
+    SLG_HIP(hipGetDeviceCount(&ndev));
+    if (device < 0 || device >= ndev)
+      throw SlgError(SLG_ERR_DEVICE, "no such HIP device " + std::to_string(device));
+    ix = new slg_index();
+    ix->tune = tune;
+    ix->device = device;
+    DeviceGuard g(device);
+    hipDeviceProp_t prop;
+    SLG_HIP(hipGetDeviceProperties(&prop, device));
+    if (std::strncmp(prop.gcnArchName, "gfx950", 6) != 0 && !tune.allow_any_arch)
+      throw SlgError(SLG_ERR_DEVICE,
+                     std::string("device is ") + prop.gcnArchName + ", this library targets gfx950");
+    SLG_HIP(hipStreamCreateWithFlags(&ix->own_stream, hipStreamNonBlocking));
+    ix->stream = ix->own_stream;
+    for (auto &us : ix->upload_streams) SLG_HIP(hipStreamCreateWithFlags(&us, hipStreamNonBlocking));
+    auto st0 = std::make_unique<IndexState>();
+    st0->generation = 0;
+    st0->device = device;
+    for (uint32_t s = 0; s < n_segs; s++) st0->segs.push_back(stage_segment(ix, segs[s]));
+    {  // bound of the work-buffer pool (BufPool): a quarter of what staging left free
+      size_t cap = (size_t)tune.pool_cap_mb << 20;
+      if (tune.pool_cap_mb == 0) {
+        size_t free_b = 0, total_b = 0;
+        SLG_HIP(hipMemGetInfo(&free_b, &total_b));
+        cap = std::min<size_t>(24ull << 30, std::max<size_t>(1ull << 30, free_b / 4));
+        ix->tune.pool_cap_mb = (uint32_t)(cap >> 20);
+      }
+      ix->pool.cap = cap;
+    }
+    ix->d_error_flag.alloc(16, &ix->pool);
+    SLG_HIP(hipMemset(ix->d_error_flag.p, 0, 16));
+    finish_state(ix, *st0);
+    publish(ix, std::move(st0));
+  });
+  if (rc != SLG_OK) {
+    KeepLastError keep;
+    if (ix) slg_index_destroy(ix);
+    return nullptr;
+  }
+  return ix;
+}
+
+void slg_index_destroy(slg_index *ix) {
+  if (!ix) return;
+  DeviceScope on(ix->device);
+  (void)hipDeviceSynchronize();  // batches may run on streams of their own
+  {
+    // batches that outlive the index are detached: buffers freed, handle stays valid for
+    // slg_batch_destroy, every other call on it fails with SLG_ERR_INVALID
+    std::lock_guard<std::mutex> lk(ix->mu);
+    for (slg_batch *b : ix->live) {
+      release_batch_buffers(b, false);
+      b->snap.reset();
+      b->idx = nullptr;
+    }
+    ix->live.clear();
+  }
+  for (auto &pr : ix->prof_events) {
+    (void)hipEventDestroy(pr.first);
+    (void)hipEventDestroy(pr.second);
+  }
+  {
+    std::shared_ptr<const IndexState> last;
+    std::lock_guard<std::mutex> lk(ix->mu);
+    last.swap(ix->state);
+  }  // (the state's device memory goes here unless a detached batch handle still holds a snapshot)
+  ix->d_error_flag.release();
+  if (ix->own_stream) (void)hipStreamDestroy(ix->own_stream);
+  for (auto us : ix->upload_streams)
+    if (us) (void)hipStreamDestroy(us);
+  delete ix;
+}
+
+int slg_index_get_tuning(const slg_index *ix, slg_tuning *out) {
+  return guarded([&] {
+    SLG_REQUIRE(ix != nullptr && out != nullptr, "index or out is NULL");
+    *out = ix->tune;
+  });
+}
+
+int slg_index_trim_pool(slg_index *ix, uint64_t *freed_bytes) {
+  return guarded([&] {
+    SLG_REQUIRE(ix != nullptr, "index is NULL");
+    DeviceGuard g(ix->device);
+    const size_t freed = ix->pool.drain();
+    if (freed_bytes) *freed_bytes = freed;
+  });
+}
+
+int slg_index_info(const slg_index *ix, uint32_t *n_segs, uint64_t *n_postings,
+                   uint64_t *device_bytes) {
+  return guarded([&] {
+    SLG_REQUIRE(ix != nullptr, "index is NULL");
+    const auto st = const_cast<slg_index *>(ix)->snapshot();
+    uint64_t P = 0;
+    for (auto &s : st->segs) P += s->n_postings;
+    if (n_segs) *n_segs = (uint32_t)st->segs.size();
+    if (n_postings) *n_postings = P;
+    if (device_bytes) *device_bytes = state_device_bytes(*st);
+  });
+}
+
+int slg_index_set_stream(slg_index *ix, void *hip_stream) {
+  return guarded([&] {
+    SLG_REQUIRE(ix != nullptr, "index is NULL");
+    std::lock_guard<std::mutex> lk(ix->mu);
+    DeviceGuard g(ix->device);
+    SLG_HIP(hipStreamSynchronize(ix->stream));
+    ix->stream = hip_stream == SLG_OWN_STREAM ? ix->own_stream : (hipStream_t)hip_stream;
+  });
+}
+
+
+// ---- doc filters -------------------------------------------------------------
+namespace {
+int add_filter_impl(slg_index *ix, const uint8_t *const *seg_bitmaps, const void *const *seg_columns,
+                    int column_kind, long long lo_i, long long hi_i, double lo_f, double hi_f,
+                    const uint32_t *term_ids = nullptr, uint32_t n_terms = 0, int pass_if_absent = 0) {
+  int id = -1;
+  int rc = guarded([&] {
+    SLG_REQUIRE(ix != nullptr, "index is NULL");
+    update_state(ix, false, [&](const IndexState &cur, IndexState &ns) {
+      hipStream_t st = ix->stream;
+      const size_t n_segs = cur.segs.size();
+      auto fd = std::make_shared<FilterData>();
+      fd->per_seg.resize(n_segs);
+      std::vector<DevBuf> tmp(n_segs);  // uploaded pass bitmaps / columns (freed on return)
+      std::vector<DevBuf> marked(n_segs);  // docs that hold one of the terms (slg_index_add_filter_terms)
+      SLG_REQUIRE(n_terms == 0 || term_ids != nullptr, "term_ids is NULL");
+      for (size_t s = 0; s < n_segs; s++) {
+        const SegHost &sh = *cur.segs[s];
+        const size_t words = ((size_t)sh.n_docs + 31) / 32;
+        fd->per_seg[s] = std::make_shared<DevBuf>();
+        fd->per_seg[s]->alloc((words ? words : 1) * 4, &ix->pool);
+        slg::FilterBuildParams fp{};
+        fp.deleted = sh.d_deleted.as<uint32_t>();
+        fp.n_docs = sh.n_docs;
+        fp.reject = fd->per_seg[s]->as<uint32_t>();
+        fp.column_kind = 0;
+        if (column_kind) {
+          SLG_REQUIRE(seg_columns && seg_columns[s], "filter column of a segment is NULL");
+          tmp[s].alloc((size_t)std::max<uint32_t>(sh.n_docs, 1) * 8, &ix->pool);
+          SLG_HIP(hipMemcpyAsync(tmp[s].p, seg_columns[s], (size_t)sh.n_docs * 8, hipMemcpyHostToDevice, st));
+          fp.column = tmp[s].p;
+          fp.column_kind = column_kind;
+          fp.lo_i = lo_i;
+          fp.hi_i = hi_i;
+          fp.lo_f = lo_f;
+          fp.hi_f = hi_f;
+        } else if (seg_bitmaps && seg_bitmaps[s]) {
+          std::vector<uint32_t> w(words ? words : 1, 0u);
+          std::memcpy(w.data(), seg_bitmaps[s], ((size_t)sh.n_docs + 7) / 8);
+          tmp[s].alloc(w.size() * 4, &ix->pool);
+          SLG_HIP(hipMemcpy(tmp[s].p, w.data(), w.size() * 4, hipMemcpyHostToDevice));
+          fp.pass = tmp[s].as<uint32_t>();
+        }
+        if (term_ids) {
+          // the docs of the given posting lists, marked on the device (the lists are resident: nothing is
+          // uploaded but a bitmap's worth of zeros); a caller's bitmap, if any, is AND-ed as a second pass set
+          const PostingStore &ps = *sh.store;
+          marked[s].alloc((words ? words : 1) * 4, &ix->pool);
+          SLG_HIP(hipMemsetAsync(marked[s].p, 0, (words ? words : 1) * 4, st));
+          for (uint32_t t = 0; t < n_terms; t++) {
+            const uint32_t id = term_ids[(size_t)t * n_segs + s];
+            if (id == SLG_NO_TERM) continue;
+            SLG_REQUIRE(id < ps.n_terms, "term id out of range");
+            const uint64_t a = ps.term_offsets[id], b = ps.term_offsets[(size_t)id + 1];
+            if (b == a || sh.n_docs == 0) continue;
+            slg::PostingMarkParams mp{};
+            mp.docs = ps.d_docs.as<uint32_t>() + a + (uint64_t)slg::kListPad * id;
+            mp.df = (uint32_t)(b - a);
+            mp.n_docs = sh.n_docs;
+            mp.bitmap = marked[s].as<uint32_t>();
+            hipLaunchKernelGGL(slg::posting_mark_kernel, dim3((mp.df + 255) / 256), dim3(256), 0, st, mp);
+            SLG_HIP(hipGetLastError());
+          }
+          fp.pass2 = fp.pass;  // (the caller's bitmap, or nullptr)
+          fp.pass = marked[s].as<uint32_t>();
+          fp.invert_pass = pass_if_absent ? 1 : 0;
+        }
+        if (sh.n_docs) {
+          hipLaunchKernelGGL(slg::filter_build_kernel, dim3((sh.n_docs + 255) / 256), dim3(256), 0, st, fp);
+          SLG_HIP(hipGetLastError());
+        }
+      }
+      SLG_HIP(hipStreamSynchronize(st));
+      // the filter takes the lowest free id (ids of removed filters are reused, so the pointer table stays
+      // as small as the number of filters alive at once)
+      size_t slot = 0;
+      while (slot < ns.filters.size() && ns.filters[slot]) slot++;
+      if (slot == ns.filters.size()) ns.filters.emplace_back();
+      ns.filters[slot] = std::move(fd);
+      id = (int)slot;
+    });
+  });
+  return rc == SLG_OK ? id : rc;
+}
+}  // namespace
+
+int slg_index_add_filter(slg_index *ix, const uint8_t *const *seg_bitmaps) {
+  return add_filter_impl(ix, seg_bitmaps, nullptr, 0, 0, 0, 0.0, 0.0);
+}
+int slg_index_add_filter_range_i64(slg_index *ix, const int64_t *const *seg_columns, int64_t lo, int64_t hi) {
+  return add_filter_impl(ix, nullptr, reinterpret_cast<const void *const *>(seg_columns), 1, lo, hi, 0.0, 0.0);
+}
+int slg_index_add_filter_range_f64(slg_index *ix, const double *const *seg_columns, double lo, double hi) {
+  return add_filter_impl(ix, nullptr, reinterpret_cast<const void *const *>(seg_columns), 2, 0, 0, lo, hi);
+}
+int slg_index_add_filter_terms(slg_index *ix, const uint32_t *term_ids, uint32_t n_terms, int pass_if_absent,
+                               const uint8_t *const *and_bitmaps_or_null) {
+  if (!term_ids && n_terms) {
+    return guarded([&] { SLG_REQUIRE(false, "term_ids is NULL"); });
+  }
+  static const uint32_t none = SLG_NO_TERM;
+  return add_filter_impl(ix, and_bitmaps_or_null, nullptr, 0, 0, 0, 0.0, 0.0, term_ids ? term_ids : &none, n_terms,
+                         pass_if_absent);
+}
+int slg_index_remove_filter(slg_index *ix, int filter_id) {
+  return guarded([&] {
+    SLG_REQUIRE(ix != nullptr, "index is NULL");
+    update_state(ix, false, [&](const IndexState &cur, IndexState &ns) {
+      SLG_REQUIRE(filter_id >= 0 && (size_t)filter_id < cur.filters.size() && cur.filters[filter_id],
+                  "unknown filter id");
+      // batches prepared with the filter hold the state that owns its bitmaps and its table row: they
+      // may still run.  The slot is free for the next add
+      ns.filters[filter_id].reset();
+      while (!ns.filters.empty() && !ns.filters.back()) ns.filters.pop_back();
+    });
+  });
+}
+
+// ---- sort fields (query/sort.rs:300-345) ---------------------------------------------------
+namespace {
+int add_sort_field_impl(slg_index *ix, int kind, const uint32_t *const *seg_offsets, const void *const *seg_values) {
+  int id = -1;
+  const int rc = guarded([&] {
+    SLG_REQUIRE(ix != nullptr, "index is NULL");
+    SLG_REQUIRE(seg_offsets != nullptr, "seg_offsets is NULL");
+    update_state(ix, false, [&](const IndexState &cur, IndexState &ns) {
+      const size_t n_segs = cur.segs.size();
+      auto fd = std::make_shared<SortFieldData>();
+      fd->kind = kind;
+      fd->per_seg.resize(n_segs);
+      for (size_t s = 0; s < n_segs; s++) {
+        const uint32_t n_docs = cur.segs[s]->n_docs;
+        const uint32_t *offs = seg_offsets[s];
+        SLG_REQUIRE(offs == nullptr || seg_values != nullptr, "seg_values is NULL");
+        if (offs) {
+          for (uint32_t d = 0; d < n_docs; d++)
+            SLG_REQUIRE(offs[d + 1] >= offs[d], "sort field offsets of a segment are not monotone");
+          SLG_REQUIRE(offs[n_docs] == offs[0] || seg_values[s] != nullptr, "sort field values of a segment are NULL");
+        }
+        // the Min / Max selection and the key encoding run on the host (slg_plan.cpp: unit-tested on the CPU)
+        const size_t n = std::max<uint32_t>(n_docs, 1), words = (n + 31) / 32;
+        std::vector<uint64_t> asc(n, 0), desc(n, 0);
+        std::vector<uint32_t> present(words, 0);
+        slgplan::sort_field_keys(kind, n_docs, offs, offs ? seg_values[s] : nullptr, asc.data(), desc.data(),
+                                 present.data());
+        auto col = std::make_shared<SortColumn>();
+        col->key[0].alloc(n * 8, &ix->pool);
+        col->key[1].alloc(n * 8, &ix->pool);
+        col->present.alloc(words * 4, &ix->pool);
+        SLG_HIP(hipMemcpy(col->key[0].p, asc.data(), n * 8, hipMemcpyHostToDevice));
+        SLG_HIP(hipMemcpy(col->key[1].p, desc.data(), n * 8, hipMemcpyHostToDevice));
+        SLG_HIP(hipMemcpy(col->present.p, present.data(), words * 4, hipMemcpyHostToDevice));
+        fd->per_seg[s] = std::move(col);
+      }
+      id = ix->next_sort_field++;
+      ns.sort_fields.emplace(id, std::move(fd));
+    });
+  });
+  return rc == SLG_OK ? id : rc;
+}
+}  // namespace
+
+int slg_index_add_sort_field_i64(slg_index *ix, const uint32_t *const *seg_offsets, const int64_t *const *seg_values) {
+  return add_sort_field_impl(ix, 1, seg_offsets, reinterpret_cast<const void *const *>(seg_values));
+}
+int slg_index_add_sort_field_f64(slg_index *ix, const uint32_t *const *seg_offsets, const double *const *seg_values) {
+  return add_sort_field_impl(ix, 2, seg_offsets, reinterpret_cast<const void *const *>(seg_values));
+}
+int slg_index_remove_sort_field(slg_index *ix, int sort_field_id) {
+  return guarded([&] {
+    SLG_REQUIRE(ix != nullptr, "index is NULL");
+    update_state(ix, false, [&](const IndexState &cur, IndexState &ns) {
+      SLG_REQUIRE(cur.sort_fields.count(sort_field_id) == 1, "unknown sort field id");
+      ns.sort_fields.erase(sort_field_id);
+    });
+  });
+}
+
+// ---- index updates (api/writer.rs:106-240) ---------------------------------------------------
+int slg_index_update_deleted(slg_index *ix, uint32_t seg, const uint8_t *deleted, float live_docs) {
+  return guarded([&] {
+    SLG_REQUIRE(ix != nullptr, "index is NULL");
+    update_state(ix, true, [&](const IndexState &cur, IndexState &ns) {
+      SLG_REQUIRE(seg < cur.segs.size(), "no such segment");
+      SLG_REQUIRE(live_docs >= 0.0f && live_docs <= (float)cur.segs[seg]->n_docs, "live_docs outside [0, n_docs]");
+      const std::shared_ptr<PostingStore> &ps = cur.segs[seg]->store;
+      if (!ps->updatable)
+        throw SlgError(SLG_ERR_UNSUPPORTED, "index was created with slg_tuning.updatable = 0");
+      auto sh = std::make_shared<SegHost>();
+      derive_version(ix, ps, *sh, deleted, live_docs, StageTemps{});
+      ns.segs[seg] = sh;
+      // registered filters: reject = deleted | ~filter, so this segment's bitmaps take the new tombstones
+      const size_t words = std::max<size_t>(((size_t)ps->n_docs + 31) / 32, 1);
+      for (auto &f : ns.filters) {
+        if (!f || seg >= f->per_seg.size() || !f->per_seg[seg]) continue;
+        auto nf = std::make_shared<FilterData>(*f);
+        auto nb = std::make_shared<DevBuf>();
+        nb->alloc(words * 4, &ix->pool);
+        slg::BitmapOrParams bp{};
+        bp.a = f->per_seg[seg]->as<uint32_t>();
+        bp.b = sh->d_deleted.as<uint32_t>();
+        bp.out = nb->as<uint32_t>();
+        bp.n_words = (uint32_t)words;
+        hipLaunchKernelGGL(slg::bitmap_or_kernel, dim3((uint32_t)((words + 255) / 256)), dim3(256), 0, ix->stream, bp);
+        SLG_HIP(hipGetLastError());
+        nf->per_seg[seg] = std::move(nb);
+        f = std::move(nf);
+      }
+      SLG_HIP(hipStreamSynchronize(ix->stream));
+    });
+  });
+}
+
+int slg_index_add_segment(slg_index *ix, const slg_segment_desc *seg) {
+  int ord = -1;
+  const int rc = guarded([&] {
+    SLG_REQUIRE(ix != nullptr && seg != nullptr, "index or segment descriptor is NULL");
+    validate_segment(*seg, 0, ix->tune.validate != 0);
+    update_state(ix, true, [&](const IndexState &, IndexState &ns) {
+      ns.segs.push_back(stage_segment(ix, *seg));
+      // no bitmap / column / store for the new segment: a filter or sort field registered before is
+      // unusable until it is registered again
+      const size_t n_segs = ns.segs.size();
+      reshape_per_segment(ns, [n_segs](auto &per_seg) { per_seg.resize(n_segs); });
+      ord = (int)n_segs - 1;
+    });
+  });
+  return rc == SLG_OK ? ord : rc;
+}
+
+int slg_index_remove_segment(slg_index *ix, uint32_t seg) {
+  return guarded([&] {
+    SLG_REQUIRE(ix != nullptr, "index is NULL");
+    update_state(ix, true, [&](const IndexState &cur, IndexState &ns) {
+      SLG_REQUIRE(seg < cur.segs.size(), "no such segment");
+      SLG_REQUIRE(cur.segs.size() > 1, "the last segment of an index cannot be removed (add the replacement first)");
+      ns.segs.erase(ns.segs.begin() + seg);
+      reshape_per_segment(ns, [seg](auto &per_seg) {
+        if (seg < per_seg.size()) per_seg.erase(per_seg.begin() + seg);
+      });
+    });
+  });
+}
+
+int slg_index_device(const slg_index *ix) {
+  if (!ix) {
+    last_error().msg = "index is NULL";
+    last_error().code = SLG_ERR_INVALID;
+    return SLG_ERR_INVALID;
+  }
+  return ix->device;
+}
+
+uint64_t slg_index_generation(const slg_index *ix) {
+  return ix ? ix->generation.load(std::memory_order_acquire) : 0;  // (no lock: callers poll it per request)
+}
+
+int slg_profile_enable(slg_index *ix, int on) {
+  return guarded([&] {
+    SLG_REQUIRE(ix != nullptr, "index is NULL");
+    std::lock_guard<std::mutex> lk(ix->mu);
+    ix->profile = on != 0;
+  });
+}
+
+int slg_profile_read(slg_index *ix, uint32_t *n_launches, float *total_ms) {
+  return guarded([&] {
+    SLG_REQUIRE(ix != nullptr, "index is NULL");
+    std::lock_guard<std::mutex> lk(ix->mu);
+    DeviceGuard g(ix->device);
+    float sum = 0.0f;
+    for (size_t i = 0; i < ix->prof_used; i++) {
+      SLG_HIP(hipEventSynchronize(ix->prof_events[i].second));
+      float ms = 0.0f;
+      SLG_HIP(hipEventElapsedTime(&ms, ix->prof_events[i].first, ix->prof_events[i].second));
+      sum += ms;
+    }
+    if (n_launches) *n_launches = (uint32_t)ix->prof_used;
+    if (total_ms) *total_ms = sum;
+    ix->prof_used = 0;
+  });
+}
+
+int slg_index_add_vector_field(slg_index *ix, const slg_vector_field_desc *per_segment, uint32_t n_segs) {
+  int id = 0;
+  const int rc = guarded([&] {
+    SLG_REQUIRE(ix != nullptr && per_segment != nullptr, "index or descriptors are NULL");
+    update_state(ix, false, [&](const IndexState &cur, IndexState &ns) {
+      SLG_REQUIRE(n_segs == cur.segs.size(), "one descriptor per segment of the index is required");
+      auto vf = std::make_shared<VecFieldHost>();
+      for (uint32_t s = 0; s < n_segs; s++) {
+        const slg_vector_field_desc &d = per_segment[s];
+        if (!d.vec_dim) continue;
+        SLG_REQUIRE(d.vec_offsets != nullptr && (d.vec_rows == 0 || d.vec_values != nullptr), "vector arrays are NULL");
+        SLG_REQUIRE(d.vec_metric == SLG_METRIC_COSINE || d.vec_metric == SLG_METRIC_L2, "unknown vector metric");
+        SLG_REQUIRE(vf->dim == 0 || (vf->dim == d.vec_dim && vf->metric == d.vec_metric),
+                    "segments disagree on the field's dimension or metric");
+        vf->dim = d.vec_dim;
+        vf->metric = d.vec_metric;
+        const uint32_t nd = cur.segs[s]->n_docs;
+        for (uint32_t i = 0; i < nd; i++)
+          SLG_REQUIRE(d.vec_offsets[i] == SLG_NO_VECTOR || d.vec_offsets[i] < d.vec_rows,
+                      "vector offset past vec_rows");
+      }
+      SLG_REQUIRE(vf->dim != 0, "no segment has vectors in this field");
+      vf->per_seg.resize(n_segs);
+      for (uint32_t s = 0; s < n_segs; s++) {
+        const slg_vector_field_desc &d = per_segment[s];
+        if (!d.vec_dim) continue;
+        auto vs = std::make_shared<VecSegStore>();
+        const size_t ob = (size_t)cur.segs[s]->n_docs * 4, vb = (size_t)d.vec_rows * d.vec_dim * 4;
+        vs->offsets.alloc(ob, &ix->pool);
+        if (ob) SLG_HIP(hipMemcpy(vs->offsets.p, d.vec_offsets, ob, hipMemcpyHostToDevice));
+        vs->values.alloc(vb, &ix->pool);
+        if (vb) SLG_HIP(hipMemcpy(vs->values.p, d.vec_values, vb, hipMemcpyHostToDevice));
+        vs->dim = d.vec_dim;
+        vf->per_seg[s] = std::move(vs);
+      }
+      ns.vfields.push_back(std::move(vf));
+      id = (int)ns.vfields.size();
+    });
+  });
+  return rc == SLG_OK ? id : rc;
+}
+
+}  // extern "C"

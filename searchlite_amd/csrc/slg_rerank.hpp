@@ -19,17 +19,7 @@
 
 namespace slg {
 
-// A segment without vectors in the field has dim 0 and the field's metric.  A candidate whose segment
-// is >= n_segs, or whose doc is >= its segment's n_docs, is a candidate without a vector: it scores
-// missing_vector_score of the field's metric (api/reader.rs:217-223).
-struct VecSegDev {
-  const uint32_t *offsets;  // [n_docs] row index or 0xFFFFFFFF
-  const float *values;      // [rows * dim]
-  uint32_t n_docs;
-  uint32_t dim;
-  int32_t metric;  // 0 cosine, 1 l2
-  uint32_t pad;
-};
+// (VecSegDev, the per-segment vector store the kernels read: slg_desc.hpp)
 
 struct RerankParams {
   const VecSegDev *vsegs;
@@ -500,7 +490,7 @@ struct RerankMultiParams {
   uint32_t q_stride;       // padded LDS row of one clause vector (floats): dim + 4
 };
 
-typedef float f32x4_t __attribute__((ext_vector_type(4)));
+// (f32x4_t: slg_wave.hpp)
 
 constexpr uint32_t kRerankMultiLdsFloats = 36 * 1024;  // clause vectors + per-clause scores + blends
 

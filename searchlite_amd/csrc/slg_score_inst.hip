@@ -1,5 +1,5 @@
 // slg_score_inst.hip — one translation unit per top-k register width (SLG_INST_KREGS), so the
-// scoring-kernel instantiations compile in parallel.  slg_api.hip calls
+// scoring-kernel instantiations compile in parallel.  slg_batch.hip calls
 // slg::launch_score_kregs<N>() declared below.
 #include <hip/hip_runtime.h>
 

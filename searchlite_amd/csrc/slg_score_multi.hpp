@@ -20,7 +20,7 @@
 //
 // MaxScore pruning (strategies Wand / Bmw; query/wand.rs:659-903 reaches the same top-k by
 // skipping): the host marks as NON-ESSENTIAL the lists whose summed maximum contributions stay
-// below the seed threshold (slg_api.hip) — a doc found only in them cannot reach the top-k.  Such
+// below the seed threshold (slg_batch.hip) — a doc found only in them cannot reach the top-k.  Such
 // lists set no bitmap bits in sweep A; in sweep C their postings are only probed against the
 // bitmap of the essential lists and added (in list order) where the doc is present.
 // Block skipping (wand.rs:205-265 advance_to / skip_to_block: postings between candidate docs are

@@ -21,7 +21,6 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include "slg_rerank.hpp"
 #include "slg_wave.hpp"
 
 namespace slg {

@@ -11,6 +11,8 @@
 
 namespace slg {
 
+typedef float f32x4_t __attribute__((ext_vector_type(4)));  // 16-byte lane loads, MFMA accumulators
+
 // ---- small helpers --------------------------------------------------------------------
 __device__ __forceinline__ int32_t total_key(float x) {
   // f32::total_cmp key: sign-magnitude bits -> two's complement order

@@ -14,11 +14,15 @@ for kr in 1 2 4 8 16; do
   /opt/rocm/bin/hipcc $FLAGS -DSLG_INST_KREGS=$kr -c slg_score_inst.hip -o k$kr.o &
   OBJS="$OBJS k$kr.o"
 done
-/opt/rocm/bin/hipcc $FLAGS -c slg_api.hip -o api.o &
-PLAN=""
-if [ -f slg_plan.cpp ]; then /opt/rocm/bin/hipcc $FLAGS -x c++ -c slg_plan.cpp -o plan.o & PLAN="plan.o"; fi
-if [ -f slg_coalesce.hip ]; then /opt/rocm/bin/hipcc $FLAGS -c slg_coalesce.hip -o coalesce.o & PLAN="$PLAN coalesce.o"; fi
+# the host units of the revision: every .hip but the score instantiations (one slg_api.hip in older
+# revisions, one unit per concern since)
+for src in *.hip; do
+  [ "$src" = slg_score_inst.hip ] && continue
+  /opt/rocm/bin/hipcc $FLAGS -c "$src" -o "${src%.hip}.o" &
+  OBJS="$OBJS ${src%.hip}.o"
+done
+if [ -f slg_plan.cpp ]; then /opt/rocm/bin/hipcc $FLAGS -x c++ -c slg_plan.cpp -o plan.o & OBJS="$OBJS plan.o"; fi
 wait
-/opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC -o "$ROOT/searchlite_amd/lib/libsearchlite_gpu_$TAG.so" api.o $PLAN $OBJS
+/opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC -o "$ROOT/searchlite_amd/lib/libsearchlite_gpu_$TAG.so" $OBJS
 rm -rf "$TMP"
 echo "$ROOT/searchlite_amd/lib/libsearchlite_gpu_$TAG.so"

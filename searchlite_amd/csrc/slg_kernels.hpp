@@ -8,8 +8,11 @@
 // This header: the kernels a batch runs around the scoring kernels — the round partition, the merges
 // and the large-k / field-sorted selects.  Only slg_batch.hip includes it (a static kernel is compiled
 // into every unit that includes its header); the staging and filter kernels of the index are in
-// slg_stage.hpp.  Wave-level helpers and the top-k structures: slg_wave.hpp; the scoring kernels:
-// slg_score*.hpp.
+// slg_stage.hpp.  Wave-level helpers (one LDS atomic per wave and bin / per wave and compaction), the
+// register top-k with its stream-and-insert loop and its result row: slg_wave.hpp; the scoring kernels:
+// slg_score*.hpp.  What the merges and the two selects share beyond that — the error word, the zero fill
+// of a short result row, the size of a select's last rank range — is defined once below, ahead of the
+// merge kernels.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -136,6 +139,30 @@ static __global__ void __launch_bounds__(256) partition_rounds_kernel(RoundPartP
   }
 }
 
+// ---- pieces shared by the merge and select kernels ------------------------------------------------
+// The index's error word is copied behind the result block (MergeParams::error_flag) by one thread of the grid.
+template <typename P>
+__device__ __forceinline__ void copy_error_flag(const P &p, const bool first_thread) {
+  if (first_thread && p.out_flag) *p.out_flag = *p.error_flag;
+}
+// zero the entries [from, k) of query q's result row; thread t of nt
+__device__ __forceinline__ void zero_rows(uint32_t *out_doc, uint32_t *out_seg, float *out_score, const uint32_t q,
+                                          const uint32_t k, const uint32_t from, const uint32_t t, const uint32_t nt) {
+  for (uint32_t i = from + t; i < k; i += nt) {
+    out_doc[(size_t)q * k + i] = 0u;
+    out_seg[(size_t)q * k + i] = 0u;
+    out_score[(size_t)q * k + i] = 0.0f;
+  }
+}
+// The final rank range of a select may take more keys than it emits (dropped after the sort) as long as
+// they fit the sort, whose size is the next power of two: no more than that of the `left` keys still to
+// emit (k = 1001: a 1024-key sort; up to 2048 keys were 66 stages x 2 passes against 55 x 1), at most cap.
+__device__ __forceinline__ uint32_t last_range_cap(const uint32_t left, const uint32_t cap) {
+  uint32_t cap_last = 64;
+  while (cap_last < left) cap_last <<= 1;
+  return cap_last < cap ? cap_last : cap;
+}
+
 // ---- merge: per query, all slice candidate lists -> final top-k ---------------------------
 struct MergeParams {
   const QueryRef *queries;
@@ -162,7 +189,7 @@ __global__ void __launch_bounds__(256) merge_topk_kernel(MergeParams p) {
   const uint32_t lane = threadIdx.x & 63;
   const uint32_t q = rfl(blockIdx.x * kWavesPerBlock + (threadIdx.x >> 6));
   if (q >= p.nq) return;
-  if (q == 0 && lane == 0 && p.out_flag) *p.out_flag = *p.error_flag;
+  copy_error_flag(p, q == 0 && lane == 0);
   const uint32_t k = p.k;
   const QueryRef qr = p.queries[q];
   WaveTopK<KREGS, true> top;
@@ -194,6 +221,8 @@ __global__ void __launch_bounds__(256) merge_topk_kernel(MergeParams p) {
       const int32_t ctk = gtk[u];
       const uint32_t cdoc = gdoc[u], cseg = gseg[u];
       const bool valid = !(ctk == kSentinelTk && cdoc == 0xFFFFFFFFu);
+      // (WaveTopK::offer written out: through the member the KREGS = 16 instantiation takes 101 VGPRs, with
+      //  this copy 70; the parent commit's took 100)
       uint64_t m = __ballot(valid && top.passes(ctk, cseg, cdoc));
       while (m) {
         const uint32_t l = (uint32_t)__builtin_ctzll(m);
@@ -203,17 +232,7 @@ __global__ void __launch_bounds__(256) merge_topk_kernel(MergeParams p) {
       }
     }
   }
-#pragma unroll
-  for (int r = 0; r < KREGS; r++) {
-    const uint32_t pos = lane * KREGS + r;
-    if (pos < k) {
-      const bool real = pos < top.count;
-      p.out_doc[(size_t)q * k + pos] = real ? top.doc[r] : 0u;
-      p.out_seg[(size_t)q * k + pos] = real ? top.seg[r] : 0u;
-      p.out_score[(size_t)q * k + pos] = real ? key_to_float(top.tk[r]) : 0.0f;
-    }
-  }
-  if (lane == 0) p.out_count[q] = top.count;
+  top.store_row(p.out_doc, p.out_seg, p.out_score, p.out_count, q, k, lane);
 }
 
 // ---- merge of per-shard results gathered over RCCL (api/reader.rs:2776-2778 across shards) --
@@ -239,6 +258,10 @@ __global__ void __launch_bounds__(256) merge_shards_kernel(ShardMergeParams p) {
         cdoc = p.doc[row + i];
         cseg = sh * p.seg_stride + p.seg[row + i];
       }
+      // (not WaveTopK::offer: a shard's row is sorted, so the row is left at the first 64 entries that add
+      //  nothing, and only the chosen lane is re-tested — the lanes behind it are worse and fall out one
+      //  scalar compare each, without a wave-wide ballot per insert.  No single-card workload times this
+      //  kernel, so its loop is kept as it was measured.)
       uint64_t m = __ballot(i < cnt && top.passes(ctk, cseg, cdoc));
       if (m == 0) break;
       while (m) {
@@ -251,19 +274,8 @@ __global__ void __launch_bounds__(256) merge_shards_kernel(ShardMergeParams p) {
       }
     }
   }
-#pragma unroll
-  for (int r = 0; r < KREGS; r++) {
-    const uint32_t pos = lane * KREGS + r;
-    if (pos < k) {
-      const bool real = pos < top.count;
-      p.out_doc[(size_t)q * k + pos] = real ? top.doc[r] : 0u;
-      p.out_seg[(size_t)q * k + pos] = real ? top.seg[r] : 0u;
-      p.out_score[(size_t)q * k + pos] = real ? key_to_float(top.tk[r]) : 0.0f;
-    }
-  }
-  if (lane == 0) p.out_count[q] = top.count;
+  top.store_row(p.out_doc, p.out_seg, p.out_score, p.out_count, q, k, lane);
 }
-
 
 // ---- the same merge for k beyond the register top-k (k up to 20 001, api/reader.rs:2615-2619) --
 // Every shard's row is already sorted by (score desc, segment asc, doc asc) and keys are unique,
@@ -307,11 +319,7 @@ static __global__ void __launch_bounds__(256) merge_shards_large_kernel(ShardMer
       p.out_score[(size_t)q * k + rank] = p.score[row + i];
     }
   }
-  for (uint32_t i = nout + threadIdx.x; i < k; i += blockDim.x) {
-    p.out_doc[(size_t)q * k + i] = 0u;
-    p.out_seg[(size_t)q * k + i] = 0u;
-    p.out_score[(size_t)q * k + i] = 0.0f;
-  }
+  zero_rows(p.out_doc, p.out_seg, p.out_score, q, k, nout, threadIdx.x, blockDim.x);
   if (threadIdx.x == 0) p.out_count[q] = nout;
 }
 
@@ -372,7 +380,7 @@ select_topk_kernel(SelectParams p) {
   const uint32_t tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const uint32_t q = blockIdx.x;
   if (q >= p.nq) return;
-  if (q == 0 && tid == 0 && p.out_flag) *p.out_flag = *p.error_flag;
+  copy_error_flag(p, q == 0 && tid == 0);
   const uint32_t k = p.k;
   const QueryRef qr = p.queries[q];
   const uint32_t sb = qr.slice_begin, se = qr.slice_end, nsl = se - sb;
@@ -497,15 +505,7 @@ select_topk_kernel(SelectParams p) {
     // (scores of one query share their exponent: nearly all candidates fall into one or two bins, and LDS
     //  atomics on one address are served one at a time — 2K of them were 27 us of this kernel.  The
     //  lanes of a wave that hold the same bin add their count once.)
-    uint64_t todo = __ballot(true);  // the lanes that are here
-    const uint32_t bin = a >> 24;
-    while (todo) {
-      const uint32_t l = (uint32_t)__builtin_ctzll(todo);
-      const uint32_t b = rl(bin, l);
-      const uint64_t same = __ballot(bin == b) & todo;
-      if (lane == l) atomicAdd(&hist0[b], (uint32_t)__popcll(same));
-      todo &= ~same;
-    }
+    hist_add_by_bin(hist0, a >> 24, lane);
   });
   __syncthreads();
   if (wave == 0) {  // (one wave adds the 256 bins: a single thread walking them was ~10 us of this kernel)
@@ -539,12 +539,7 @@ select_topk_kernel(SelectParams p) {
   while (k_done < nout) {
     const uint32_t target = nout - k_done > kSelectCap ? k_done + kSelectCap : nout;
     const bool last = target == nout;
-    // the final range may take more keys than it emits (dropped after the sort) as long as they fit the
-    // sort — whose size is the next power of two: no more than that of the keys still to emit (k = 1001:
-    // a 1024-key sort; up to 2048 keys were 66 stages x 2 passes against 55 x 1)
-    uint32_t cap_last = 64;
-    while (cap_last < nout - k_done) cap_last <<= 1;
-    cap_last = cap_last < kSelectCap ? cap_last : kSelectCap;
+    uint32_t cap_last = last_range_cap(nout - k_done, kSelectCap);
     if (n_flat > 16u * NT) cap_last = kSelectCap;  // (many candidates: a further select level costs more than the larger sort)
     const bool all = last && nvalid - k_done <= cap_last;  // everything left fits: no select
     __syncthreads();
@@ -576,6 +571,8 @@ select_topk_kernel(SelectParams p) {
         }
         if (wave == 0) {
           // lane l owns bins 255-4l .. 252-4l (descending); inclusive prefix of the lane sums
+          // (select_sorted_kernel has the ascending twin of this pick: folded into one helper templated on the
+          //  direction, in two forms, it cost that kernel 4 to 6 VGPRs above its 141)
           const uint32_t b0 = 255u - 4u * lane;
           const uint32_t h0 = hist[b0], h1 = hist[b0 - 1], h2 = hist[b0 - 2], h3 = hist[b0 - 3];
           const uint32_t tot = h0 + h1 + h2 + h3;
@@ -602,30 +599,21 @@ select_topk_kernel(SelectParams p) {
         if (sh_done) break;
       }
     }
-      const uint32_t p0 = sh_pre[0], p1 = sh_pre[1], p2 = sh_pre[2];
+    const uint32_t p0 = sh_pre[0], p1 = sh_pre[1], p2 = sh_pre[2];
     const uint32_t count = (sh_taken - k_done) < kSelectCap ? (sh_taken - k_done) : kSelectCap;
     // ---- gather the keys of this range ----
     for_each([&](uint32_t a, uint32_t b, uint32_t c, uint64_t) {
       bool win = all || at_or_above(a, b, c, p0, p1, p2, level);
       if (win && have_prev) win = !at_or_above(a, b, c, q0, q1, q2, q_level);
-      const uint64_t wm = __ballot(win);  // (one add per wave: see the histogram above)
-      uint32_t wbase = 0;
-      if (wm != 0ull) {
-        const uint32_t l0 = (uint32_t)__builtin_ctzll(wm);
-        if (lane == l0) wbase = atomicAdd(&sh_nwin, (uint32_t)__popcll(wm));
-        wbase = rl(wbase, l0);
-      }
-      if (win) {
-        const uint32_t at = wbase + (uint32_t)__popcll(wm & ((1ull << lane) - 1ull));
-        if (at < kSelectCap) {
-          w_ok[at] = a;
-          w_sg[at] = b;
-          w_dc[at] = c;
-        }
+      const uint32_t at = wave_compact_slot(&sh_nwin, win, lane);  // (one add per wave: see the histogram above)
+      if (win && at < kSelectCap) {
+        w_ok[at] = a;
+        w_sg[at] = b;
+        w_dc[at] = c;
       }
     });
     __syncthreads();
-      // ---- bitonic sort, descending 96-bit key ----
+    // ---- bitonic sort, descending 96-bit key ----
     uint32_t n2 = 1;
     while (n2 < count) n2 <<= 1;
     for (uint32_t i = count + tid; i < n2; i += NT) {
@@ -651,7 +639,7 @@ select_topk_kernel(SelectParams p) {
         __syncthreads();
       }
     }
-      const uint32_t emit = target - k_done;  // (the final range drops what it took beyond k)
+    const uint32_t emit = target - k_done;  // (the final range drops what it took beyond k)
     for (uint32_t i = tid; i < emit; i += NT) {
       const int32_t tk = (int32_t)(w_ok[i] ^ 0x80000000u);
       p.out_doc[(size_t)q * k + k_done + i] = ~w_dc[i];
@@ -665,11 +653,7 @@ select_topk_kernel(SelectParams p) {
     q2 = p2;
     q_level = level;
   }
-  for (uint32_t i = nout + tid; i < k; i += NT) {
-    p.out_doc[(size_t)q * k + i] = 0u;
-    p.out_seg[(size_t)q * k + i] = 0u;
-    p.out_score[(size_t)q * k + i] = 0.0f;
-  }
+  zero_rows(p.out_doc, p.out_seg, p.out_score, q, k, nout, tid, NT);
   if (tid == 0) p.out_count[q] = nout;
   if constexpr (CURSOR) {
     if (tid == 0) {
@@ -782,7 +766,7 @@ static __global__ void __launch_bounds__(kSortedThreads) select_sorted_kernel(So
   const uint32_t tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const uint32_t q = blockIdx.x;
   if (q >= p.nq) return;
-  if (q == 0 && tid == 0 && p.out_flag) *p.out_flag = *p.error_flag;
+  copy_error_flag(p, q == 0 && tid == 0);
   const uint32_t k = p.k;
   const QueryRef qr = p.queries[q];
   const uint32_t sb = qr.slice_begin, se = qr.slice_end;
@@ -883,11 +867,7 @@ static __global__ void __launch_bounds__(kSortedThreads) select_sorted_kernel(So
   while (k_done < nout) {
     const uint32_t target = nout - k_done > CAP ? k_done + CAP : nout;
     const bool last = target == nout;
-    // the final range may take more keys than it emits (dropped after the sort) within a sort of the
-    // next power of two above the keys still to emit
-    uint32_t cap_last = 64;
-    while (cap_last < nout - k_done) cap_last <<= 1;
-    cap_last = cap_last < CAP ? cap_last : CAP;
+    const uint32_t cap_last = last_range_cap(nout - k_done, CAP);
     const bool all = last && nvalid - k_done <= cap_last;  // everything left fits: no select
     __syncthreads();
     if (tid < NW) s_pre[tid] = s_dm[tid] = 0u;
@@ -911,19 +891,10 @@ static __global__ void __launch_bounds__(kSortedThreads) select_sorted_kernel(So
           uint32_t wv = 0;
 #pragma unroll
           for (uint32_t w = 0; w < NW; w++) wv = w == wd ? K[w] : wv;
-          const uint32_t bin = (wv >> shift) & 255u;
-          // (ties are the normal case: lanes of a wave that hold the same bin add their count once)
-          uint64_t todo = __ballot(true);
-          while (todo) {
-            const uint32_t l = (uint32_t)__builtin_ctzll(todo);
-            const uint32_t b = rl(bin, l);
-            const uint64_t same = __ballot(bin == b) & todo;
-            if (lane == l) atomicAdd(&hist[b], (uint32_t)__popcll(same));
-            todo &= ~same;
-          }
+          hist_add_by_bin(hist, (wv >> shift) & 255u, lane);  // (ties are the normal case here)
         });
         __syncthreads();
-        if (wave == 0) {  // lane l owns bins 4l .. 4l+3 (ascending)
+        if (wave == 0) {  // lane l owns bins 4l .. 4l+3 (ascending; the twin of select_topk_kernel's pick)
           const uint32_t b0 = 4u * lane;
           const uint32_t h0 = hist[b0], h1 = hist[b0 + 1], h2 = hist[b0 + 2], h3 = hist[b0 + 3];
           const uint32_t tot = h0 + h1 + h2 + h3;
@@ -958,20 +929,11 @@ static __global__ void __launch_bounds__(kSortedThreads) select_sorted_kernel(So
       sorted_key(p, a, seg, doc, K);
       bool win = all || sorted_cmp(K, s_pre, s_dm) <= 0;
       if (win && have_prev) win = sorted_cmp(K, s_qpre, s_qdm) > 0;
-      const uint64_t wm = __ballot(win);
-      uint32_t wbase = 0;
-      if (wm != 0ull) {
-        const uint32_t l0 = (uint32_t)__builtin_ctzll(wm);
-        if (lane == l0) wbase = atomicAdd(&sh_nwin, (uint32_t)__popcll(wm));
-        wbase = rl(wbase, l0);
-      }
-      if (win) {
-        const uint32_t at = wbase + (uint32_t)__popcll(wm & ((1ull << lane) - 1ull));
-        if (at < CAP) {
+      const uint32_t at = wave_compact_slot(&sh_nwin, win, lane);
+      if (win && at < CAP) {
 #pragma unroll
-          for (uint32_t w = 0; w < NW; w++)
-            if (s_slot[w] != 0xFFFFFFFFu) w_key[s_slot[w] * CAP + at] = K[w];
-        }
+        for (uint32_t w = 0; w < NW; w++)
+          if (s_slot[w] != 0xFFFFFFFFu) w_key[s_slot[w] * CAP + at] = K[w];
       }
     });
     __syncthreads();
@@ -1025,11 +987,7 @@ static __global__ void __launch_bounds__(kSortedThreads) select_sorted_kernel(So
     k_done = target;
     have_prev = true;
   }
-  for (uint32_t i = nout + tid; i < k; i += NT) {
-    p.out_doc[(size_t)q * k + i] = 0u;
-    p.out_seg[(size_t)q * k + i] = 0u;
-    p.out_score[(size_t)q * k + i] = 0.0f;
-  }
+  zero_rows(p.out_doc, p.out_seg, p.out_score, q, k, nout, tid, NT);
   if (tid == 0) p.out_count[q] = nout;
   if constexpr (CURSOR) {
     if (tid == 0) p.out_seen[q] = cur_on ? sh_seen : 1u;

@@ -78,24 +78,9 @@ __device__ __forceinline__ void rerank_emit_topk(const RerankParams &p, const ui
       d = cdoc[i];
       sg = cseg[i];
     }
-    uint64_t m = __ballot(i < n && top.passes(ctk, sg, d));
-    while (m) {
-      const uint32_t l = (uint32_t)__builtin_ctzll(m);
-      top.insert((int32_t)rl((uint32_t)ctk, l), rl(sg, l), rl(d, l), k, lane);
-      m &= m - 1;
-      m &= __ballot(top.passes(ctk, sg, d));
-    }
+    top.offer(i < n, ctk, sg, d, k, lane);
   }
-#pragma unroll
-  for (int r = 0; r < KREGS; r++) {
-    const uint32_t pos = lane * KREGS + r;
-    if (pos < k) {
-      const bool real = pos < top.count;
-      p.out_doc[(size_t)q * k + pos] = real ? top.doc[r] : 0u;
-      p.out_seg[(size_t)q * k + pos] = real ? top.seg[r] : 0u;
-      p.out_score[(size_t)q * k + pos] = real ? key_to_float(top.tk[r]) : 0.0f;
-    }
-  }
+  top.store_row(p.out_doc, p.out_seg, p.out_score, p.out_count, q, k, lane);
   if (p.out_vec) {
     // vector score of each winner: all lanes scan the candidate list for its (seg, doc)
     const uint32_t nout = top.count < k ? top.count : k;
@@ -121,32 +106,82 @@ __device__ __forceinline__ void rerank_emit_topk(const RerankParams &p, const ui
     }
     for (uint32_t pos = nout + lane; pos < k; pos += 64) p.out_vec[(size_t)q * k + pos] = 0.0f;
   }
-  if (lane == 0) p.out_count[q] = top.count;
 }
 
 // vector score + blend of candidate c (lane 0 stores): api/reader.rs:217-223, :240-246,
-// vectors/mod.rs:112-118, :128
+// vectors/mod.rs:112-118, :128 (missing_vector_score, similarity_from_sum, blend: slg_wave.hpp)
 __device__ __forceinline__ void rerank_finish(const float sum, const bool have_row, const int32_t metric,
                                               const float alpha, const float bm, float *s_blend,
                                               float *s_vec, const uint32_t c, const bool store) {
-  float vs;
-  if (!have_row)
-    vs = metric == 0 ? -1.0f : -3.40282347e+38f;
-  else if (metric == 0)
-    vs = (sum != sum) ? 0.0f : sum;
-  else
-    vs = -sqrtf(sum);
+  const float vs = have_row ? similarity_from_sum(metric, sum) : missing_vector_score(metric);
   if (store) {
-    float blended;
-    if (alpha >= 1.0f)
-      blended = bm;
-    else if (alpha <= 0.0f)
-      blended = vs;
-    else
-      blended = alpha * bm + (1.0f - alpha) * vs;
+    const float blended = blend(alpha, bm, vs);
     s_blend[c] = blended == 0.0f ? 0.0f : blended;  // 0.0 + blended (api/reader.rs:232,249): -0.0 -> +0.0, NaN bits kept
     s_vec[c] = vs;
   }
+}
+
+// Row of (seg, doc) in a vector field's per-segment stores (VectorStore::vector, vectors/mod.rs:63-71), or
+// nullptr: segment out of range, a store of another dimension, doc beyond the store, no vector.
+__device__ __forceinline__ const float *vec_row(const VecSegDev *vsegs, const uint32_t n_segs, const uint32_t dim,
+                                                const uint32_t seg, const uint32_t doc) {
+  if (seg >= n_segs) return nullptr;
+  const VecSegDev vd = vsegs[seg];
+  if (vd.dim != dim || doc >= vd.n_docs) return nullptr;
+  const uint32_t off = vd.offsets[doc];
+  return off == 0xFFFFFFFFu ? nullptr : vd.values + (size_t)off * dim;
+}
+
+// acc += this lane's four terms of the dot (metric 0) or of the squared distance, one add after the other
+// in x, y, z, w order: the sum order is part of the result's bits
+template <typename V>
+__device__ __forceinline__ void accumulate4(const int32_t metric, const V &a, const V &b, float &acc) {
+  if (metric == 0) {
+    acc += a.x * b.x;
+    acc += a.y * b.y;
+    acc += a.z * b.z;
+    acc += a.w * b.w;
+  } else {
+    const float d0 = a.x - b.x, d1 = a.y - b.y, d2 = a.z - b.z, d3 = a.w - b.w;
+    acc += d0 * d0;
+    acc += d1 * d1;
+    acc += d2 * d2;
+    acc += d3 * d3;
+  }
+}
+
+// f(std::integral_constant<int, CH>{}) for the whole-row scans' chunk count: dim <= 256 * CH, CH = 1, 2, 3
+template <typename F>
+__device__ __forceinline__ void with_row_chunks(const uint32_t dim, F &&f) {
+  if (dim <= 256u)
+    f(std::integral_constant<int, 1>{});
+  else if (dim <= 512u)
+    f(std::integral_constant<int, 2>{});
+  else
+    f(std::integral_constant<int, 3>{});
+}
+
+// compute_hybrid_score (api/reader.rs:225-254) of one candidate, clauses in order: bit cc of `has` says
+// that clause cc found a vector, whose similarity is vs[cc * vs_stride]; a clause without one takes the
+// missing-vector score of ITS metric, metric_of(cc) (:217-223).  Returns the mean of the clause blends;
+// vsum = the sum of the boosted similarities found (:236-238), or the missing score of clause 0's metric.
+template <typename MetricOf>
+__device__ __forceinline__ float hybrid_score(const uint32_t NC, const uint32_t has, const float bm,
+                                              const float *alpha, const float *boost, const float *vs,
+                                              const uint32_t vs_stride, MetricOf &&metric_of, float &vsum) {
+  float blended_sum = 0.0f, vector_sum = 0.0f;
+  for (uint32_t cc = 0; cc < NC; cc++) {
+    float v;
+    if ((has >> cc) & 1u) {
+      v = vs[cc * vs_stride] * (boost ? boost[cc] : 1.0f);  // api/reader.rs:2421
+      vector_sum += v;
+    } else {
+      v = missing_vector_score(metric_of(cc));
+    }
+    blended_sum += blend(alpha[cc], bm, v);
+  }
+  vsum = has ? vector_sum : missing_vector_score(metric_of(0));
+  return blended_sum / (float)NC;
 }
 
 // Whole-row scan for dim <= 256 * CH, dim % 4 == 0 (config 5: 768 = 3 chunks).  A wave takes 4
@@ -231,18 +266,7 @@ __device__ __forceinline__ void rerank_scan_rows(const RerankParams &p, const ui
 #pragma unroll
       for (int ch = 0; ch < CH; ch++) {
         const fvec4 bb = valid[ch] ? b[u][ch] : a[ch];  // masked lanes: a = 0 and a - a = 0
-        if (met[u] == 0) {
-          acc += a[ch].x * bb.x;
-          acc += a[ch].y * bb.y;
-          acc += a[ch].z * bb.z;
-          acc += a[ch].w * bb.w;
-        } else {
-          const float d0 = a[ch].x - bb.x, d1 = a[ch].y - bb.y, d2 = a[ch].z - bb.z, d3 = a[ch].w - bb.w;
-          acc += d0 * d0;
-          acc += d1 * d1;
-          acc += d2 * d2;
-          acc += d3 * d3;
-        }
+        accumulate4(met[u], a[ch], bb, acc);
       }
       const uint32_t c = c0 + u;
       const float sum = wave_sum_f(acc);
@@ -321,23 +345,12 @@ __device__ __forceinline__ void rerank_scan_clauses(const VecSegDev *vsegs, cons
 #pragma unroll
         for (int ch = 0; ch < CH; ch++) {
           const fvec4 bb = valid[ch] ? b[u][ch] : a[ch];  // masked lanes: a = 0 and a - a = 0
-          if (metric == 0) {
-            acc += a[ch].x * bb.x;
-            acc += a[ch].y * bb.y;
-            acc += a[ch].z * bb.z;
-            acc += a[ch].w * bb.w;
-          } else {
-            const float d0 = a[ch].x - bb.x, d1 = a[ch].y - bb.y, d2 = a[ch].z - bb.z, d3 = a[ch].w - bb.w;
-            acc += d0 * d0;
-            acc += d1 * d1;
-            acc += d2 * d2;
-            acc += d3 * d3;
-          }
+          accumulate4(metric, a[ch], bb, acc);
         }
         const float sum = wave_sum_f(acc);
         const uint32_t c = c0 + u;
         if (lane == 0 && c < n && have[u])
-          s_vs[cc * vs_stride + c] = metric == 0 ? (sum != sum ? 0.0f : sum) : -sqrtf(sum);
+          s_vs[cc * vs_stride + c] = similarity_from_sum(metric, sum);
       }
     }
     if (s_has && lane == 0) {
@@ -371,14 +384,8 @@ __global__ void __launch_bounds__(256) rerank_kernel(RerankParams p) {
   const float *cbm = p.cand_bm25 + (size_t)q * p.max_cand;
   constexpr int U = 8;
   const bool whole_rows = (dim & 3u) == 0 && dim <= 768u;
-  if (whole_rows) {
-    if (dim <= 256u)
-      rerank_scan_rows<1>(p, q, n, alpha, s_blend, s_vec, lane, wave);
-    else if (dim <= 512u)
-      rerank_scan_rows<2>(p, q, n, alpha, s_blend, s_vec, lane, wave);
-    else
-      rerank_scan_rows<3>(p, q, n, alpha, s_blend, s_vec, lane, wave);
-  }
+  if (whole_rows)
+    with_row_chunks(dim, [&](auto CH) { rerank_scan_rows<CH>(p, q, n, alpha, s_blend, s_vec, lane, wave); });
   for (uint32_t c0 = whole_rows ? n : wave * U; c0 < n; c0 += 4 * U) {
     const float *row[U];
     int32_t metric[U];
@@ -390,15 +397,9 @@ __global__ void __launch_bounds__(256) rerank_kernel(RerankParams p) {
       acc[u] = 0.0f;
       const uint32_t c = c0 + u;
       if (c < n) {
-        const uint32_t doc = cdoc[c], seg = cseg[c];
-        if (seg < p.n_segs) {
-          const VecSegDev vd = p.vsegs[seg];
-          metric[u] = vd.metric;
-          if (vd.dim == dim && doc < vd.n_docs) {
-            const uint32_t off = vd.offsets[doc];
-            if (off != 0xFFFFFFFFu) row[u] = vd.values + (size_t)off * dim;
-          }
-        }
+        const uint32_t seg = cseg[c];
+        if (seg < p.n_segs) metric[u] = p.vsegs[seg].metric;
+        row[u] = vec_row(p.vsegs, p.n_segs, dim, seg, cdoc[c]);
       }
     }
     if ((dim & 3u) == 0) {
@@ -410,6 +411,8 @@ __global__ void __launch_bounds__(256) rerank_kernel(RerankParams p) {
           b[u] = row[u] ? *reinterpret_cast<const float4 *>(row[u] + i) : make_float4(0.f, 0.f, 0.f, 0.f);
 #pragma unroll
         for (int u = 0; u < U; u++) {
+          // (accumulate4 written out: through the helper this kernel takes 94 VGPRs by value, 115 by
+          //  reference, against 92 — this loop holds 8 rows' pieces at once)
           if (metric[u] == 0) {
             acc[u] += a.x * b[u].x;
             acc[u] += a.y * b[u].y;
@@ -443,25 +446,8 @@ __global__ void __launch_bounds__(256) rerank_kernel(RerankParams p) {
     for (int u = 0; u < U; u++) {
       const uint32_t c = c0 + u;
       const float sum = wave_sum_f(acc[u]);
-      float vs;
-      if (row[u] == nullptr)
-        vs = metric[u] == 0 ? -1.0f : -3.40282347e+38f;  // api/reader.rs:217-223
-      else if (metric[u] == 0)
-        vs = (sum != sum) ? 0.0f : sum;  // vectors/mod.rs:112-116 NaN -> 0
-      else
-        vs = -sqrtf(sum);  // vectors/mod.rs:118
-      if (lane == 0 && c < n) {
-        const float bm = cbm[c];
-        float blended;  // api/reader.rs:240-246
-        if (alpha >= 1.0f)
-          blended = bm;
-        else if (alpha <= 0.0f)
-          blended = vs;
-        else
-          blended = alpha * bm + (1.0f - alpha) * vs;  // vectors/mod.rs:128
-        s_blend[c] = blended == 0.0f ? 0.0f : blended;  // (as rerank_finish)
-        s_vec[c] = vs;
-      }
+      const bool store = lane == 0 && c < n;
+      rerank_finish(sum, row[u] != nullptr, metric[u], alpha, store ? cbm[c] : 0.0f, s_blend, s_vec, c, store);
     }
   }
   __syncthreads();
@@ -518,13 +504,7 @@ __global__ void __launch_bounds__(256) rerank_multi_kernel(RerankMultiParams mp)
 
   // row of candidate c, or nullptr (missing vector / out of range)
   auto row_of = [&](const uint32_t c) -> const float * {
-    if (c >= n) return nullptr;
-    const uint32_t doc = cdoc[c], seg = cseg[c];
-    if (seg >= p.n_segs) return nullptr;
-    const VecSegDev vd = p.vsegs[seg];
-    if (vd.dim != dim || doc >= vd.n_docs) return nullptr;
-    const uint32_t off = vd.offsets[doc];
-    return off == 0xFFFFFFFFu ? nullptr : vd.values + (size_t)off * dim;
+    return c < n ? vec_row(p.vsegs, p.n_segs, dim, cseg[c], cdoc[c]) : nullptr;
   };
 
   // L2 with >= 3 clauses also runs its products on the matrix cores: |q - x|^2 = |q|^2 + |x|^2 - 2 q.x
@@ -593,7 +573,7 @@ __global__ void __launch_bounds__(256) rerank_multi_kernel(RerankMultiParams mp)
           for (int r = 0; r < 4; r++) {
             const uint32_t c = t0 + 4 * g + r;
             const float d = acc[r];
-            if (c < n) s_vs[cl * p.max_cand + c] = d != d ? 0.0f : d;  // vectors/mod.rs:112-116 NaN -> 0
+            if (c < n) s_vs[cl * p.max_cand + c] = similarity_from_sum(0, d);
           }
         }
       } else {
@@ -638,15 +618,10 @@ __global__ void __launch_bounds__(256) rerank_multi_kernel(RerankMultiParams mp)
     //      per wave and step with their whole rows in flight, every clause against the rows held ----
     const float *readable = p.qvecs + (size_t)q * NC * dim;
     const uint32_t wv = (uint32_t)__builtin_amdgcn_readfirstlane((int)wave);
-    if (dim <= 256u)
-      rerank_scan_clauses<1>(p.vsegs, p.n_segs, dim, metric, s_q, qs, NC, cdoc, cseg, n, readable, s_vs, p.max_cand,
-                             nullptr, 0u, lane, wv);
-    else if (dim <= 512u)
-      rerank_scan_clauses<2>(p.vsegs, p.n_segs, dim, metric, s_q, qs, NC, cdoc, cseg, n, readable, s_vs, p.max_cand,
-                             nullptr, 0u, lane, wv);
-    else
-      rerank_scan_clauses<3>(p.vsegs, p.n_segs, dim, metric, s_q, qs, NC, cdoc, cseg, n, readable, s_vs, p.max_cand,
-                             nullptr, 0u, lane, wv);
+    with_row_chunks(dim, [&](auto CH) {
+      rerank_scan_clauses<CH>(p.vsegs, p.n_segs, dim, metric, s_q, qs, NC, cdoc, cseg, n, readable, s_vs, p.max_cand,
+                              nullptr, 0u, lane, wv);
+    });
   } else {
     // ---- other dimensions: one candidate per wave at a time; its row is read ONCE into registers
     //      (dim <= 1024) and every clause runs against it ----
@@ -691,37 +666,16 @@ __global__ void __launch_bounds__(256) rerank_multi_kernel(RerankMultiParams mp)
           }
         }
         const float sum = wave_sum_f(acc);
-        if (lane == 0) s_vs[cc * p.max_cand + c] = metric == 0 ? (sum != sum ? 0.0f : sum) : -sqrtf(sum);
+        if (lane == 0) s_vs[cc * p.max_cand + c] = similarity_from_sum(metric, sum);
       }
     }
   }
   __syncthreads();
-  // ---- compute_hybrid_score (api/reader.rs:225-254) per candidate, clauses in order ----
-  for (uint32_t c = threadIdx.x; c < n; c += 256) {
-    const bool has = row_of(c) != nullptr;
-    const float bm = cbm[c];
-    float blended_sum = 0.0f, vector_sum = 0.0f;
-    for (uint32_t cc = 0; cc < NC; cc++) {
-      const float alpha = p.alpha[(size_t)q * NC + cc];
-      float vs;
-      if (has) {
-        vs = s_vs[cc * p.max_cand + c] * (mp.boost ? mp.boost[(size_t)q * NC + cc] : 1.0f);
-        vector_sum += vs;
-      } else {
-        vs = metric == 0 ? -1.0f : -3.40282347e+38f;  // missing_vector_score
-      }
-      float blended;
-      if (alpha >= 1.0f)
-        blended = bm;
-      else if (alpha <= 0.0f)
-        blended = vs;
-      else
-        blended = alpha * bm + (1.0f - alpha) * vs;
-      blended_sum += blended;
-    }
-    s_blend[c] = blended_sum / (float)NC;
-    s_vsum[c] = has ? vector_sum : (metric == 0 ? -1.0f : -3.40282347e+38f);
-  }
+  // ---- compute_hybrid_score per candidate: one field, so a candidate has a vector for every clause or none ----
+  for (uint32_t c = threadIdx.x; c < n; c += 256)
+    s_blend[c] = hybrid_score(NC, row_of(c) != nullptr ? 0xFFFFFFFFu : 0u, cbm[c], p.alpha + (size_t)q * NC,
+                              mp.boost ? mp.boost + (size_t)q * NC : nullptr, s_vs + c, p.max_cand,
+                              [&](uint32_t) { return metric; }, s_vsum[c]);
   __syncthreads();
   if (wave != 0) return;
 
@@ -778,15 +732,10 @@ __global__ void __launch_bounds__(256) rerank_fields_kernel(RerankFieldsParams f
       continue;
     }
     const float *readable = p.qvecs + (size_t)q * fp.q_floats + fp.coff[cc];
-    if (dim <= 256u)
-      rerank_scan_clauses<1>(fp.cvsegs[cc], p.n_segs, dim, fp.cmetric[cc], s_q + fp.coff[cc], 0u, 1u, cdoc, cseg, n,
-                             readable, s_vs + cc * p.max_cand, p.max_cand, s_has, 1u << cc, lane, wave);
-    else if (dim <= 512u)
-      rerank_scan_clauses<2>(fp.cvsegs[cc], p.n_segs, dim, fp.cmetric[cc], s_q + fp.coff[cc], 0u, 1u, cdoc, cseg, n,
-                             readable, s_vs + cc * p.max_cand, p.max_cand, s_has, 1u << cc, lane, wave);
-    else
-      rerank_scan_clauses<3>(fp.cvsegs[cc], p.n_segs, dim, fp.cmetric[cc], s_q + fp.coff[cc], 0u, 1u, cdoc, cseg, n,
-                             readable, s_vs + cc * p.max_cand, p.max_cand, s_has, 1u << cc, lane, wave);
+    with_row_chunks(dim, [&](auto CH) {
+      rerank_scan_clauses<CH>(fp.cvsegs[cc], p.n_segs, dim, fp.cmetric[cc], s_q + fp.coff[cc], 0u, 1u, cdoc, cseg, n,
+                              readable, s_vs + cc * p.max_cand, p.max_cand, s_has, 1u << cc, lane, wave);
+    });
   }
   __syncthreads();  // (the two loops spread the candidates over the waves differently: s_has is shared)
   for (uint32_t c = wave; slow_clauses != 0u && c < n; c += 4) {
@@ -796,14 +745,7 @@ __global__ void __launch_bounds__(256) rerank_fields_kernel(RerankFieldsParams f
       if (!((slow_clauses >> cc) & 1u)) continue;
       const uint32_t dim = fp.cdim[cc];
       const int32_t metric = fp.cmetric[cc];
-      const float *row = nullptr;
-      if (seg < p.n_segs) {
-        const VecSegDev vd = fp.cvsegs[cc][seg];
-        if (vd.dim == dim && doc < vd.n_docs) {
-          const uint32_t off = vd.offsets[doc];
-          if (off != 0xFFFFFFFFu) row = vd.values + (size_t)off * dim;
-        }
-      }
+      const float *row = vec_row(fp.cvsegs[cc], p.n_segs, dim, seg, doc);
       if (row == nullptr) continue;
       const float *qc = s_q + fp.coff[cc];
       float acc = 0.0f;
@@ -817,38 +759,17 @@ __global__ void __launch_bounds__(256) rerank_fields_kernel(RerankFieldsParams f
         }
       }
       const float sum = wave_sum_f(acc);
-      if (lane == 0) s_vs[cc * p.max_cand + c] = metric == 0 ? (sum != sum ? 0.0f : sum) : -sqrtf(sum);
+      if (lane == 0) s_vs[cc * p.max_cand + c] = similarity_from_sum(metric, sum);
       has |= 1u << cc;
     }
     if (lane == 0) s_has[c] |= has;
   }
   __syncthreads();
-  // ---- compute_hybrid_score (api/reader.rs:225-254) per candidate, clauses in order ----
-  for (uint32_t c = threadIdx.x; c < n; c += 256) {
-    const uint32_t has = s_has[c];
-    const float bm = cbm[c];
-    float blended_sum = 0.0f, vector_sum = 0.0f;
-    for (uint32_t cc = 0; cc < NC; cc++) {
-      const float alpha = p.alpha[(size_t)q * NC + cc];
-      float vs;
-      if ((has >> cc) & 1u) {
-        vs = s_vs[cc * p.max_cand + c] * (fp.boost ? fp.boost[(size_t)q * NC + cc] : 1.0f);
-        vector_sum += vs;
-      } else {
-        vs = fp.cmetric[cc] == 0 ? -1.0f : -3.40282347e+38f;  // missing_vector_score of THIS clause
-      }
-      float blended;
-      if (alpha >= 1.0f)
-        blended = bm;
-      else if (alpha <= 0.0f)
-        blended = vs;
-      else
-        blended = alpha * bm + (1.0f - alpha) * vs;
-      blended_sum += blended;
-    }
-    s_blend[c] = blended_sum / (float)NC;
-    s_vsum[c] = has ? vector_sum : (fp.cmetric[0] == 0 ? -1.0f : -3.40282347e+38f);
-  }
+  // ---- compute_hybrid_score per candidate: every clause has its own field, so its own has-bit and metric ----
+  for (uint32_t c = threadIdx.x; c < n; c += 256)
+    s_blend[c] = hybrid_score(NC, s_has[c], cbm[c], p.alpha + (size_t)q * NC,
+                              fp.boost ? fp.boost + (size_t)q * NC : nullptr, s_vs + c, p.max_cand,
+                              [&](uint32_t cc) { return fp.cmetric[cc]; }, s_vsum[c]);
   __syncthreads();
   if (wave != 0) return;
   rerank_emit_topk<KREGS>(p, q, n, s_blend, s_vsum, cdoc, cseg, lane);

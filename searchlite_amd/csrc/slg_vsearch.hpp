@@ -428,16 +428,8 @@ __global__ void __launch_bounds__(kVsSortThreads) vs_blend_kernel(VsBlendParams 
       if (lookup(cc, flat, &vs))
         vector_sum += vs;
       else
-        vs = p.metric[cc] == 0 ? -1.0f : -3.40282347e+38f;  // missing_vector_score (:217-223)
-      const float alpha = p.alpha[(size_t)q * NC + cc];
-      float blended;
-      if (alpha >= 1.0f)
-        blended = bm;
-      else if (alpha <= 0.0f)
-        blended = vs;
-      else
-        blended = alpha * bm + (1.0f - alpha) * vs;  // vectors/mod.rs:128
-      blended_sum += blended;
+        vs = missing_vector_score(p.metric[cc]);  // (:217-223)
+      blended_sum += blend(p.alpha[(size_t)q * NC + cc], bm, vs);
     }
     *vsum = vector_sum;
     return blended_sum / (float)NC;

@@ -1,5 +1,8 @@
 // slg_wave.hpp — device-side building blocks shared by every kernel of the library: small wave
-// helpers (readlanes, scans, fences), the register top-k WaveTopK and the buffered top-k BufTopK.
+// helpers (readlanes, scans, fences, one LDS atomic per wave: hist_add_by_bin, wave_compact_slot), the
+// register top-k WaveTopK (insert, the stream-and-insert loop `offer`, the result row `store_row`), the
+// buffered top-k BufTopK, and the three scalar rules of a vector score (missing_vector_score,
+// similarity_from_sum, blend) that the rerank and the vector-search kernels restate from the reference.
 // Device code only, no kernels: the scoring units (slg_score_inst.hip) include it without
 // compiling a copy of the host-launched kernels of slg_kernels.hpp.
 #pragma once
@@ -57,6 +60,31 @@ __device__ __forceinline__ int32_t wave_shr1(int32_t v) {
 // compiler-only ordering point for wave-synchronous LDS traffic (hardware keeps a wave's
 // DS instructions in order; this stops the compiler from moving them across phases)
 __device__ __forceinline__ void wave_fence() { __atomic_signal_fence(__ATOMIC_SEQ_CST); }
+
+// hist[bin] += 1 for every lane that is here, one LDS atomic per DISTINCT bin of the wave: LDS atomics
+// on one address are served one at a time, and the lanes of a wave mostly hold the same one or two bins
+__device__ __forceinline__ void hist_add_by_bin(uint32_t *hist, const uint32_t bin, const uint32_t lane) {
+  uint64_t todo = __ballot(true);  // the lanes that are here
+  while (todo) {
+    const uint32_t l = (uint32_t)__builtin_ctzll(todo);
+    const uint32_t b = rl(bin, l);
+    const uint64_t same = __ballot(bin == b) & todo;
+    if (lane == l) atomicAdd(&hist[b], (uint32_t)__popcll(same));
+    todo &= ~same;
+  }
+}
+// compaction slot of every lane with `win` set: one atomicAdd on *counter per wave (by its first winning
+// lane), then the lane's rank among the winners.  Lanes without `win` get a value they must not use.
+__device__ __forceinline__ uint32_t wave_compact_slot(uint32_t *counter, const bool win, const uint32_t lane) {
+  const uint64_t wm = __ballot(win);
+  uint32_t wbase = 0;
+  if (wm != 0ull) {
+    const uint32_t l0 = (uint32_t)__builtin_ctzll(wm);
+    if (lane == l0) wbase = atomicAdd(counter, (uint32_t)__popcll(wm));
+    wbase = rl(wbase, l0);
+  }
+  return wbase + (uint32_t)__popcll(wm & ((1ull << lane) - 1ull));
+}
 
 // (score key, seg, doc) ordering: larger tk first, then smaller seg, then smaller doc
 // (query/wand.rs:30-37, query/sort.rs:80-93)
@@ -152,6 +180,33 @@ struct WaveTopK {
       th_seg = 0xFFFFFFFFu;
     }
   }
+  // one candidate per lane (`valid`: the lane holds one): the passing lanes are taken lowest first, each
+  // inserted through readlanes, and the rest re-balloted against the threshold the insert raised
+  __device__ __forceinline__ void offer(bool valid, int32_t ctk, uint32_t cseg, uint32_t cdoc, uint32_t k,
+                                        uint32_t lane) {
+    uint64_t m = __ballot(valid && passes(ctk, cseg, cdoc));
+    while (m) {
+      const uint32_t l = (uint32_t)__builtin_ctzll(m);
+      insert((int32_t)rl((uint32_t)ctk, l), rl(cseg, l), rl(cdoc, l), k, lane);
+      m &= m - 1;
+      m &= __ballot(passes(ctk, cseg, cdoc));
+    }
+  }
+  // the result row of query q: k entries best first, zeros behind the real ones, and their count
+  __device__ __forceinline__ void store_row(uint32_t *out_doc, uint32_t *out_seg, float *out_score,
+                                            uint32_t *out_count, uint32_t q, uint32_t k, uint32_t lane) const {
+#pragma unroll
+    for (int r = 0; r < KREGS; r++) {
+      const uint32_t pos = lane * KREGS + r;
+      if (pos < k) {
+        const bool real = pos < count;
+        out_doc[(size_t)q * k + pos] = real ? doc[r] : 0u;
+        out_seg[(size_t)q * k + pos] = real ? seg[r] : 0u;
+        out_score[(size_t)q * k + pos] = real ? key_to_float(tk[r]) : 0.0f;
+      }
+    }
+    if (lane == 0) out_count[q] = count;
+  }
 };
 
 // ---- buffered wave top-k (one segment) ------------------------------------------------------
@@ -170,6 +225,23 @@ __device__ __forceinline__ uint32_t ordered_score(float x) {
 }
 __device__ __forceinline__ uint64_t cand_key(float score, uint32_t doc) {
   return ((uint64_t)ordered_score(score) << 32) | (uint32_t)~doc;
+}
+
+// ---- the scalar rules of a vector score (rerank and vector-only search) -------------------------
+// api/reader.rs:217-223: what a doc without a vector scores, by the field's metric (0 cosine, else L2)
+__device__ __forceinline__ float missing_vector_score(const int32_t metric) {
+  return metric == 0 ? -1.0f : -3.40282347e+38f;
+}
+// metric_similarity (vectors/mod.rs:107-120) from the finished sum: cosine = the dot, NaN -> 0 (:112-116);
+// L2 = -sqrt of the sum of squared differences (:118)
+__device__ __forceinline__ float similarity_from_sum(const int32_t metric, const float sum) {
+  return metric == 0 ? ((sum != sum) ? 0.0f : sum) : -sqrtf(sum);
+}
+// blend_scores of one clause (api/reader.rs:240-246, vectors/mod.rs:122-129)
+__device__ __forceinline__ float blend(const float alpha, const float bm, const float vs) {
+  if (alpha >= 1.0f) return bm;
+  if (alpha <= 0.0f) return vs;
+  return alpha * bm + (1.0f - alpha) * vs;  // vectors/mod.rs:128
 }
 
 template <int KREGS>

@@ -767,6 +767,61 @@ int slg_vector_search_batch_device(slg_index *index, uint32_t nq, uint32_t n_cla
                                    uint32_t k_out, uint32_t *d_out_doc, uint32_t *d_out_seg, float *d_out_score,
                                    float *d_out_vec_score, uint32_t *d_out_count, uint64_t *d_out_total);
 
+/*
+ * Hybrid text + vector search: one request with a text query and vector clauses (api/reader.rs:2754-2775:
+ * collect_vector_maps with require_text_match = true, then merge_vector_hits, :2474-2537).  Per query:
+ *   1. the matched set M = every doc the text query matches that is not deleted and passes q_filter (and
+ *      minimum_should_match, where the batch shape supports it);
+ *   2. the BM25 hits = the top k of M by (score desc, segment asc, doc asc): the batch's own rows, bit for bit
+ *      those of slg_batch_prepare_plans for the same queries at the same k;
+ *   3. per clause c (field clause_field[c], as in slg_vector_search_batch) every doc of M with a vector in the
+ *      field scores metric_similarity * boost[q][c]; the best cand_size by (score desc, segment asc, doc asc)
+ *      form the clause's list.  Exact where the reference searches an HNSW graph, every predicate applied
+ *      before the truncation: recall is never below the reference's;
+ *   4. union = BM25 hits + all clause lists; a union doc's bm25 is its score among the BM25 hits, else 0.0
+ *      (:2496-2500, also though it matches the text); each clause blends as compute_hybrid_score (:225-254),
+ *      a clause whose list lacks the doc with its metric's missing-vector score; final = sum / n_clauses; when
+ *      every alpha <= 0 a union doc found in no clause list is dropped (:2494,2504);
+ *   5. rows [nq][k_out] = the top by (final desc under f32::total_cmp, segment asc, doc asc); out_vec_score =
+ *      the sum of the clause scores found, and for a row no clause list holds (the reference's None) the
+ *      missing-vector score of clause 0's metric (-1.0 / f32::MIN), as slg_rerank_fields_batch writes it;
+ *      out_count[q] = rows filled, out_total[q] = the union size after the drop.
+ *
+ * slg_batch_prepare_hybrid plans the text side as slg_batch_prepare_sorted does (every matched doc becomes a
+ * candidate with its exact score: no threshold seed, no MaxScore) and accepts every query shape that call
+ * accepts; slg_batch_run leaves the BM25 top k in the batch's rows (slg_batch_fetch, slg_batch_device_results)
+ * and keeps the candidates.  slg_batch_hybrid_device then runs steps 3-5 asynchronously on the batch's stream
+ * (no host round trip after slg_batch_run; device arrays, clause_field on the host; qvecs / alpha / boost as in
+ * slg_vector_search_batch).  It may be called again on the same batch with other clauses.  The gathered keys
+ * take 8 bytes x matched docs x clauses; the queries of a batch are processed in ranges whose keys fit a
+ * quarter of the buffer pool's cap (at most 1 GiB), and a single query that does not fit fails with
+ * SLG_ERR_OOM: never a partial result.  slg_search_batch_hybrid is the one-call form with host arrays.
+ * k = 0 is allowed: there are no BM25 hits, the union is the clause lists alone and every bm25 is 0.0 (no
+ * select kernel runs; the gather drops deleted and filtered docs itself, by the same bitmaps).
+ *
+ * n_clauses outside 1..SLG_MAX_VECTOR_CLAUSES, cand_size outside 1..SLG_MAX_VECTOR_CANDIDATES, k or k_out above
+ * SLG_MAX_K, or clause vectors of more than 36 Ki floats per query: SLG_ERR_UNSUPPORTED; a NULL or inconsistent
+ * argument, a batch that has not run or was not made by slg_batch_prepare_hybrid: SLG_ERR_INVALID; all before
+ * any device work.  slg_batch_run_sharded*, slg_batch_fetch_sharded, slg_batch_matched_counts and
+ * slg_batch_cursor_seen refuse a hybrid batch with SLG_ERR_UNSUPPORTED; the coalescer builds its own batches
+ * and has no hybrid request kind.
+ */
+slg_batch *slg_batch_prepare_hybrid(slg_index *index, uint32_t nq, const uint32_t *q_offsets,
+                                    const uint32_t *q_term_ids, const float *q_weights,
+                                    const slg_score_plans *plans_or_null, const int32_t *q_filter_or_null,
+                                    uint32_t k, int strategy);
+int slg_batch_hybrid_device(slg_batch *batch, uint32_t n_clauses, const uint32_t *clause_field,
+                            const float *d_qvecs, const float *d_alpha, const float *d_boost, uint32_t cand_size,
+                            uint32_t k_out, uint32_t *d_out_doc, uint32_t *d_out_seg, float *d_out_score,
+                            float *d_out_vec_score, uint32_t *d_out_count, uint64_t *d_out_total);
+int slg_search_batch_hybrid(slg_index *index, uint32_t nq, const uint32_t *q_offsets, const uint32_t *q_term_ids,
+                            const float *q_weights, const slg_score_plans *plans_or_null,
+                            const int32_t *q_filter_or_null, uint32_t k, int strategy, uint32_t n_clauses,
+                            const uint32_t *clause_field, const float *qvecs, const float *alpha,
+                            const float *boost, uint32_t cand_size, uint32_t k_out, uint32_t *out_doc,
+                            uint32_t *out_seg, float *out_score, float *out_vec_score, uint32_t *out_count,
+                            uint64_t *out_total);
+
 #ifdef __cplusplus
 }
 #endif

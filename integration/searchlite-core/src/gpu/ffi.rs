@@ -218,6 +218,19 @@ extern "C" {
         d_qvecs: *const c_float, d_alpha: *const c_float, d_boost: *const c_float, d_q_filter: *const i32,
         cand_size: u32, k_out: u32, d_out_doc: *mut u32, d_out_seg: *mut u32, d_out_score: *mut c_float,
         d_out_vec_score: *mut c_float, d_out_count: *mut u32, d_out_total: *mut u64) -> c_int;
+    // hybrid text + vector search (merge_vector_hits): prepare, run (slg_batch_run), then the vector side
+    pub fn slg_batch_prepare_hybrid(index: *mut slg_index, nq: u32, q_offsets: *const u32, q_term_ids: *const u32,
+        q_weights: *const c_float, plans: *const slg_score_plans, q_filter: *const i32, k: u32,
+        strategy: c_int) -> *mut slg_batch;
+    pub fn slg_batch_hybrid_device(batch: *mut slg_batch, n_clauses: u32, clause_field: *const u32,
+        d_qvecs: *const c_float, d_alpha: *const c_float, d_boost: *const c_float, cand_size: u32, k_out: u32,
+        d_out_doc: *mut u32, d_out_seg: *mut u32, d_out_score: *mut c_float, d_out_vec_score: *mut c_float,
+        d_out_count: *mut u32, d_out_total: *mut u64) -> c_int;
+    pub fn slg_search_batch_hybrid(index: *mut slg_index, nq: u32, q_offsets: *const u32, q_term_ids: *const u32,
+        q_weights: *const c_float, plans: *const slg_score_plans, q_filter: *const i32, k: u32, strategy: c_int,
+        n_clauses: u32, clause_field: *const u32, qvecs: *const c_float, alpha: *const c_float,
+        boost: *const c_float, cand_size: u32, k_out: u32, out_doc: *mut u32, out_seg: *mut u32,
+        out_score: *mut c_float, out_vec_score: *mut c_float, out_count: *mut u32, out_total: *mut u64) -> c_int;
 }
 pub const SLG_OWN_STREAM: *mut c_void = usize::MAX as *mut c_void;
 pub const SLG_NO_TERM: u32 = 0xFFFF_FFFF;

@@ -19,6 +19,12 @@
 //! Everything that is not eligible (below) keeps running on the CPU scorer; a non-zero return code
 //! of the library also falls back to it — the GPU path never substitutes results silently.
 
+// Routing note (unverified source, as the rest of this shim): hybrid requests — a text query with `vector`
+// clauses, api/reader.rs:2754-2775 — are not routed here yet.  The device path is
+// ffi::slg_batch_prepare_hybrid (k = top_k) -> ffi::slg_batch_run -> ffi::slg_batch_hybrid_device
+// (cand_size = candidate_size, k_out = heap_limit), or ffi::slg_search_batch_hybrid in one call; its clause
+// lists are exact where collect_vector_maps searches HNSW.
+
 pub mod ffi;
 pub mod rerank;
 

@@ -16,6 +16,7 @@ MAX_QUERY_TERMS = 32
 MAX_K = 20001
 MAX_RERANK_K = 1024
 MAX_VECTOR_CLAUSES = 8
+MAX_VECTOR_CANDIDATES = 10000
 SHARD_UNIQUE_ID_BYTES = 128
 
 OK, ERR_INVALID, ERR_DEVICE, ERR_OOM, ERR_UNSUPPORTED, ERR_INTERNAL = 0, -1, -2, -3, -4, -5
@@ -219,6 +220,10 @@ def load():
         "slg_vector_search_batch": (i32, [vp, u32, u32, vp, vp, vp, vp, vp, u32, u32, vp, vp, vp, vp, vp, vp]),
         "slg_vector_search_batch_device": (i32, [vp, u32, u32, vp, vp, vp, vp, vp, u32, u32, vp, vp, vp, vp,
                                                  vp, vp]),
+        "slg_batch_prepare_hybrid": (vp, [vp, u32, vp, vp, vp, vp, vp, u32, i32]),
+        "slg_batch_hybrid_device": (i32, [vp, u32, vp, vp, vp, vp, u32, u32, vp, vp, vp, vp, vp, vp]),
+        "slg_search_batch_hybrid": (i32, [vp, u32, vp, vp, vp, vp, vp, u32, i32, u32, vp, vp, vp, vp, u32, u32,
+                                          vp, vp, vp, vp, vp, vp]),
     }
     for name, (res, args) in sigs.items():
         if os.environ.get("SLG_LIB_TAG") and not hasattr(L, name):

@@ -123,7 +123,8 @@ void slghost::launch_shard_merge(const slg::ShardMergeParams &mp, hipStream_t st
 void slghost::release_batch_buffers(slg_batch *b, bool to_pool) {
   DevBuf *bufs[] = {&b->d_desc, &b->d_bounds, &b->d_rdoc, &b->d_slice_desc, &b->d_slice_tk, &b->d_slice_doc,
                     &b->d_q_scored, &b->d_q_filter, &b->d_cand, &b->d_slice_cbeg, &b->d_slice_ccnt,
-                    &b->d_out, &b->d_stamps, &b->d_blk_skip, &b->d_gather, &b->d_merged};
+                    &b->d_out, &b->d_stamps, &b->d_blk_skip, &b->d_gather, &b->d_merged, &b->d_q_cand,
+                    &b->d_hy_keys, &b->d_hy_work};
   for (DevBuf *d : bufs) {
     if (!to_pool) d->pool = nullptr;
     d->release();
@@ -161,11 +162,12 @@ slg_batch *slg_batch_prepare_plan(slg_index *ix, uint32_t nq, const uint32_t *q_
 }  // extern "C"
 
 namespace {
-// slg_batch_prepare_plans, (sort != nullptr) slg_batch_prepare_sorted, and (after) slg_batch_prepare_after
+// slg_batch_prepare_plans, (sort != nullptr) slg_batch_prepare_sorted, (after) slg_batch_prepare_after, and
+// (hybrid) slg_batch_prepare_hybrid
 slg_batch *prepare_impl(slg_index *ix, uint32_t nq, const uint32_t *q_offsets, const uint32_t *q_term_ids,
                         const float *q_weights, const slg_score_plans *plans, const int32_t *q_filter,
                         const slg_sort_spec *sort, uint32_t k, int strategy, bool after = false,
-                        const slg_sort_cursor *q_cursor = nullptr) {
+                        const slg_sort_cursor *q_cursor = nullptr, bool hybrid = false) {
   slg_batch *b = nullptr;
   int rc = guarded([&] {
     SLG_REQUIRE(ix != nullptr, "index is NULL");
@@ -203,7 +205,7 @@ slg_batch *prepare_impl(slg_index *ix, uint32_t nq, const uint32_t *q_offsets, c
     in.strategy = strategy;
     in.filter_live = filter_live.data();
     in.n_filters = filter_live.size();
-    in.sorted = sort != nullptr || after;
+    in.sorted = sort != nullptr || after || hybrid;
     // the columns of the sort parts in the batch's state: every part names a field with a column for every
     // segment (a field registered before slg_index_add_segment has none for the new one)
     std::vector<slg::SortColDev> sort_cols;
@@ -274,6 +276,7 @@ slg_batch *prepare_impl(slg_index *ix, uint32_t nq, const uint32_t *q_offsets, c
     b->cand_mode = plan.cand_mode;
     b->sorted = sort != nullptr;
     b->after = after;
+    b->hybrid = hybrid;
     b->score_k = slgplan::planning_k(in);
     b->n_sq = (uint32_t)plan.sqs.size();
     b->n_terms = (uint32_t)plan.terms.size();
@@ -339,6 +342,22 @@ slg_batch *prepare_impl(slg_index *ix, uint32_t nq, const uint32_t *q_offsets, c
       SLG_HIP(hipMemcpy(b->d_cursor.p, cursor_words.data(), cursor_words.size() * 4, hipMemcpyHostToDevice));
       b->d_seen.alloc_pooled(&ix->pool, (size_t)std::max<uint32_t>(nq, 1) * 4);
     }
+    if (b->hybrid) {  // where each query's candidates start: its sub-queries' regions lie one after another
+      b->q_cand.assign((size_t)nq + 1, UINT64_MAX);
+      b->q_cand[nq] = plan.cand_total;
+      uint64_t prev = 0;
+      for (const slg::RoundQuery &sq : plan.sqs) {
+        const uint64_t base = ((uint64_t)sq.cand_hi << 32) | sq.cand_lo;
+        // (hy_gather_kernel searches the slices' regions by slot: they must lie in sub-query, so query, order)
+        if (base < prev || sq.q >= nq) throw SlgError(SLG_ERR_INTERNAL, "candidate regions are not in query order");
+        prev = base;
+        b->q_cand[sq.q] = std::min(b->q_cand[sq.q], base);
+      }
+      for (uint32_t q = nq; q-- > 0;)
+        if (b->q_cand[q] == UINT64_MAX) b->q_cand[q] = b->q_cand[q + 1];
+      b->d_q_cand.alloc_pooled(&ix->pool, b->q_cand.size() * 8);
+      SLG_HIP(hipMemcpy(b->d_q_cand.p, b->q_cand.data(), b->q_cand.size() * 8, hipMemcpyHostToDevice));
+    }
     const ResultBlock R(nq, k);
     b->d_out.alloc_pooled(&ix->pool, R.words_with_flag() * 4);
     b->d_out_doc = R.doc(b->d_out.as<uint32_t>());
@@ -358,6 +377,14 @@ slg_batch *prepare_impl(slg_index *ix, uint32_t nq, const uint32_t *q_offsets, c
   return b;
 }
 }  // namespace
+
+slg_batch *slghost::prepare_hybrid_batch(slg_index *ix, uint32_t nq, const uint32_t *q_offsets,
+                                         const uint32_t *q_term_ids, const float *q_weights,
+                                         const slg_score_plans *plans, const int32_t *q_filter, uint32_t k,
+                                         int strategy) {
+  return prepare_impl(ix, nq, q_offsets, q_term_ids, q_weights, plans, q_filter, nullptr, k, strategy, false, nullptr,
+                      true);
+}
 
 extern "C" {
 
@@ -733,6 +760,7 @@ int slg_search_batch_filtered(slg_index *ix, const slg_query *queries, uint32_t 
 int slg_batch_matched_counts(slg_batch *b, uint64_t *out_matched) {
   return guarded([&] {
     SLG_REQUIRE_LIVE(b);
+    if (b->hybrid) throw SlgError(SLG_ERR_UNSUPPORTED, "a hybrid batch has no matched counts");
     SLG_REQUIRE(b->sorted || b->after, "not a sorted or cursor batch (slg_batch_prepare_sorted / _after)");
     SLG_REQUIRE(b->launched, "the batch has not run");
     SLG_REQUIRE(b->nq == 0 || out_matched != nullptr, "out_matched is NULL");
@@ -757,6 +785,7 @@ int slg_search_batch_sorted(slg_index *ix, const slg_query *queries, uint32_t nq
 int slg_batch_cursor_seen(slg_batch *b, uint8_t *out_seen) {
   return guarded([&] {
     SLG_REQUIRE_LIVE(b);
+    if (b->hybrid) throw SlgError(SLG_ERR_UNSUPPORTED, "a hybrid batch takes no cursor");
     SLG_REQUIRE(b->after, "not a cursor batch (slg_batch_prepare_after)");
     SLG_REQUIRE(b->launched, "the batch has not run");
     SLG_REQUIRE(b->nq == 0 || out_seen != nullptr, "out_seen is NULL");

@@ -1,8 +1,8 @@
 // slg_host.hpp — what the host translation units of the C ABI share (slg_index.hip, slg_batch.hip,
-// slg_shard.hip, slg_rerank.hip, slg_vsearch.hip): the error plumbing, device memory, the host
+// slg_shard.hip, slg_rerank.hip, slg_vsearch.hip, slg_hybrid.hip): the error plumbing, device memory, the host
 // structures behind the opaque handles and the small helpers several entry points use.  Private: not
 // installed, not part of include/.  No kernel header is included here — each unit includes the one
-// whose kernels it launches (slg_stage.hpp, slg_kernels.hpp, slg_rerank.hpp, slg_vsearch.hpp; the shard
+// whose kernels it launches (slg_stage.hpp, slg_kernels.hpp, slg_rerank.hpp, slg_vsearch.hpp, slg_hybrid.hpp; the shard
 // unit none), so every kernel is compiled once.
 //
 // Everything in namespace slghost has hidden visibility: shared between the library's objects, never
@@ -461,6 +461,12 @@ struct slg_batch {
   hipEvent_t ev_shard[4] = {nullptr, nullptr, nullptr, nullptr};  // start | local kernels done | gathered | merged
   bool shard_timed = false;
   uint64_t n_postings_nonessential = 0;  // postings of the pruning-classified (non-essential) lists
+  // hybrid text + vector batch (slg_batch_prepare_hybrid): planned as a sorted batch (candidates of every
+  // matched doc), run as a score page without a cursor; slg_batch_hybrid_device then reads the candidates
+  bool hybrid = false;
+  std::vector<uint64_t> q_cand;  // [nq + 1] first candidate slot of each query
+  DevBuf d_q_cand;               // the same on the device
+  DevBuf d_hy_keys, d_hy_work;   // the gathered keys of a range of queries; clause lists, counts, sort space
 };
 
 namespace slghost __attribute__((visibility("hidden"))) {
@@ -555,6 +561,64 @@ struct Staging {
 void release_batch_buffers(slg_batch *b, bool to_pool);
 // slg_batch.hip: the merge of several ranks' (or shards') rows
 void launch_shard_merge(const slg::ShardMergeParams &mp, hipStream_t st);
+// slg_batch.hip: slg_batch_prepare_hybrid (the planning of slg_batch_prepare_plans with BatchIn::sorted)
+slg_batch *prepare_hybrid_batch(slg_index *ix, uint32_t nq, const uint32_t *q_offsets, const uint32_t *q_term_ids,
+                                const float *q_weights, const slg_score_plans *plans, const int32_t *q_filter,
+                                uint32_t k, int strategy);
+
+// slg_vsearch.hip: one vector search or hybrid call, checked against one state of the index ...
+struct VsCall {
+  std::shared_ptr<const IndexState> S;
+  uint32_t nq = 0, n_clauses = 0, cand = 0, k_out = 0;
+  uint32_t dim[SLG_MAX_VECTOR_CLAUSES] = {}, coff[SLG_MAX_VECTOR_CLAUSES] = {};
+  int32_t metric[SLG_MAX_VECTOR_CLAUSES] = {};
+  const slg::VecSegDev *vsegs[SLG_MAX_VECTOR_CLAUSES] = {};
+  uint32_t q_floats = 0;
+};
+// ... and its arrays (host or device memory, as the entry says)
+struct VsArgs {
+  const float *qvecs, *alpha, *boost;
+  const int32_t *q_filter;
+  uint32_t *out_doc, *out_seg;
+  float *out_score, *out_vec;
+  uint32_t *out_count;
+  uint64_t *out_total;
+};
+// every check of such a call, before any device work.  false: nq == 0, nothing to do.  host_filter: q_filter is
+// host memory and its ids are checked here.  state: the one to check against (null: the index's current one)
+bool vs_prepare(slg_index *ix, uint32_t nq, uint32_t n_clauses, const uint32_t *clause_field, uint32_t cand_size,
+                uint32_t k_out, const VsArgs &a, bool host_filter, VsCall *vc,
+                std::shared_ptr<const IndexState> state = nullptr);
+// slg_vsearch.hip: the steps a hybrid call (slg_hybrid.hip) shares with the vector search, whose kernels they
+// run.  HyWork: the clause lists and sort space of one call, laid out over one block (base null: the size only);
+// cnt = run_cnt [clause][nq] then key_cnt [clause][nq], zeroed by the caller
+struct HyWork {
+  uint64_t *run, *dlist, *ukeys, *bkeys;
+  uint32_t *cnt;
+  uint32_t P, Pb;
+};
+size_t hy_work_layout(const VsCall &vc, uint32_t bm_k, void *base, HyWork *w);
+// the keys hy_gather_kernel appended for queries q_lo .. q_hi - 1: clause c's at keys + c * stride, query q's
+// from q_cand[q] - slot_lo on; max_cap = the most slots a query of the range has
+struct HyKeys {
+  const uint64_t *keys;
+  uint64_t stride, slot_lo, max_cap;
+  const uint64_t *q_cand;
+  uint32_t q_lo, q_hi;
+};
+void hy_fold(const VsCall &vc, const HyWork &w, const HyKeys &k, hipStream_t st);
+// union with the BM25 rows [nq][bm_k], blend, top k_out
+void hy_blend(const VsCall &vc, const VsArgs &a, const HyWork &w, const uint32_t *bm_doc, const uint32_t *bm_seg,
+              const float *bm_score, const uint32_t *bm_count, uint32_t bm_k, hipStream_t st);
+template <typename K, typename P>
+void launch_kernel_lds(K kernel, const P &params, dim3 grid, uint32_t threads, size_t lds, hipStream_t st) {
+  if (lds > 48 * 1024)
+    SLG_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                (int)lds));
+  hipLaunchKernelGGL(kernel, grid, dim3(threads), lds, st, params);
+  SLG_HIP(hipGetLastError());
+}
+
 // slg_rerank.hip: dimension / metric / device stores of vector field f (0: the field of the segment
 // descriptors; mixed_metric: its segments may differ in metric — the single-clause kernel reads it per
 // segment — and *metric is the last one's)

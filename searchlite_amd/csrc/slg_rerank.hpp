@@ -39,21 +39,7 @@ struct RerankParams {
 
 constexpr uint32_t kRerankMaxCand = 8192;  // blended + vec scores staged in LDS
 
-// wave-wide f32 sum with DPP row shifts / broadcasts (no LDS round trips); result in lane 63
-__device__ __forceinline__ float wave_sum_f(float v) {
-  int x = __float_as_int(v);
-#define SLG_DPP_ADD(ctrl, rmask)                                                                \
-  x = __float_as_int(__int_as_float(x) +                                                        \
-                     __int_as_float(__builtin_amdgcn_update_dpp(0, x, ctrl, rmask, 0xf, true)))
-  SLG_DPP_ADD(0x111, 0xf);  // row_shr:1
-  SLG_DPP_ADD(0x112, 0xf);  // row_shr:2
-  SLG_DPP_ADD(0x114, 0xf);  // row_shr:4
-  SLG_DPP_ADD(0x118, 0xf);  // row_shr:8
-  SLG_DPP_ADD(0x142, 0xa);  // row_bcast:15
-  SLG_DPP_ADD(0x143, 0xc);  // row_bcast:31
-#undef SLG_DPP_ADD
-  return __int_as_float(__builtin_amdgcn_readlane(x, 63));
-}
+// (wave_sum_f, the wave-wide f32 sum of the row scans: slg_wave.hpp)
 
 // The k_out best blended scores of query q by (blended desc, segment asc, doc asc), their vector
 // scores, the count: wave 0 of the workgroup, after the blends are in LDS.

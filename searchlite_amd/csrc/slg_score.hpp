@@ -102,6 +102,10 @@ struct RoundScoreParams {
   const PlanNode *plan_nodes;  // canonical node tables of the deep trees (RoundQuery::node_begin)
   // large-k mode of the uniform kernel (k > 256): candidates instead of per-slice top-k lists
   uint2 *cand;            // {ordered score, doc}; sub-query region + posting offset of the slice
+  // INVARIANT (hy_gather_kernel, slg_hybrid.hpp, searches this array): every scoring wave writes its slice's
+  // slice_cbeg and slice_ccnt, also when it kept no candidate, and slice_cbeg is non-decreasing in the slice
+  // index over the whole batch (slices lie per sub-query in query order; cbeg = the sub-query's base + the
+  // postings before the slice).  A kernel that leaves early must still store both.
   uint64_t *slice_cbeg;   // [n_slices] first candidate slot of the slice
   uint32_t *slice_ccnt;   // [n_slices] candidates written
   uint32_t n_slices;

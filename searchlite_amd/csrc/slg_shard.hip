@@ -142,6 +142,7 @@ int run_sharded_impl(slg_batch *b, slg_shard_group *g, bool have_seq, uint64_t s
     SLG_REQUIRE(g->segs_per_rank >= b->snap->segs.size(), "the shard grew beyond the group's segs_per_rank");
     // (a cursor's segment_ord is index-global; the shard merge does not apply it)
     if (b->after) throw SlgError(SLG_ERR_UNSUPPORTED, "a cursor batch does not run sharded");
+    if (b->hybrid) throw SlgError(SLG_ERR_UNSUPPORTED, "a hybrid batch does not run sharded");
   });
   if (rc != SLG_OK) return rc;
   if (!have_seq) {  // call order = the order on every rank, if one thread issues the runs
@@ -269,6 +270,7 @@ int slg_batch_fetch_sharded(slg_batch *b, uint32_t *out_doc, uint32_t *out_seg, 
   return guarded([&] {
     SLG_REQUIRE_LIVE(b);
     if (b->after) throw SlgError(SLG_ERR_UNSUPPORTED, "a cursor batch does not run sharded");
+    if (b->hybrid) throw SlgError(SLG_ERR_UNSUPPORTED, "a hybrid batch does not run sharded");
     SLG_REQUIRE(b->nq == 0 || out_count != nullptr, "out_count is NULL");
     SLG_REQUIRE(b->nq == 0 || b->k == 0 || (out_doc && out_seg && out_score), "output array is NULL");
     if (b->nq == 0) return;

@@ -5,31 +5,9 @@
 
 using namespace slghost;
 
-namespace {
-
-// One call, checked against one snapshot of the index: every check runs before any device work
-struct VsCall {
-  std::shared_ptr<const IndexState> S;
-  uint32_t nq = 0, n_clauses = 0, cand = 0, k_out = 0;
-  uint32_t dim[SLG_MAX_VECTOR_CLAUSES] = {}, coff[SLG_MAX_VECTOR_CLAUSES] = {};
-  int32_t metric[SLG_MAX_VECTOR_CLAUSES] = {};
-  const slg::VecSegDev *vsegs[SLG_MAX_VECTOR_CLAUSES] = {};
-  uint32_t q_floats = 0;
-};
-
-// The arrays of one call (host or device memory, as the entry says)
-struct VsArgs {
-  const float *qvecs, *alpha, *boost;
-  const int32_t *q_filter;
-  uint32_t *out_doc, *out_seg;
-  float *out_score, *out_vec;
-  uint32_t *out_count;
-  uint64_t *out_total;
-};
-
-// false: nq == 0, nothing to do.  host_filter: q_filter is host memory and its ids are checked here
-bool vs_prepare(slg_index *ix, uint32_t nq, uint32_t n_clauses, const uint32_t *clause_field, uint32_t cand_size,
-                uint32_t k_out, const VsArgs &a, bool host_filter, VsCall *vc) {
+bool slghost::vs_prepare(slg_index *ix, uint32_t nq, uint32_t n_clauses, const uint32_t *clause_field,
+                         uint32_t cand_size, uint32_t k_out, const VsArgs &a, bool host_filter, VsCall *vc,
+                         std::shared_ptr<const IndexState> state) {
   SLG_REQUIRE(ix != nullptr && clause_field != nullptr, "index or clause_field is NULL");
   if (n_clauses < 1 || n_clauses > SLG_MAX_VECTOR_CLAUSES)
     throw SlgError(SLG_ERR_UNSUPPORTED, "n_clauses outside 1..SLG_MAX_VECTOR_CLAUSES");
@@ -39,7 +17,7 @@ bool vs_prepare(slg_index *ix, uint32_t nq, uint32_t n_clauses, const uint32_t *
   if (nq == 0) return false;
   SLG_REQUIRE(a.qvecs && a.alpha && a.out_count && a.out_total, "query or count arrays are NULL");
   SLG_REQUIRE(k_out == 0 || (a.out_doc && a.out_seg && a.out_score), "output arrays are NULL");
-  vc->S = ix->snapshot();
+  vc->S = state ? state : ix->snapshot();
   const IndexState &S = *vc->S;
   SLG_REQUIRE(S.total_docs < 0xFFFFFFFFull, "more than 2^32 - 2 docs in the index");
   vc->nq = nq;
@@ -60,14 +38,7 @@ bool vs_prepare(slg_index *ix, uint32_t nq, uint32_t n_clauses, const uint32_t *
   return true;
 }
 
-template <typename K, typename P>
-void vs_launch_kernel(K kernel, const P &params, dim3 grid, uint32_t threads, size_t lds, hipStream_t st) {
-  if (lds > 48 * 1024)
-    SLG_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                (int)lds));
-  hipLaunchKernelGGL(kernel, grid, dim3(threads), lds, st, params);
-  SLG_HIP(hipGetLastError());
-}
+namespace {
 
 // the kernels of one call on st, device arrays in a (the caller holds ix->mu and the device)
 void vs_run(slg_index *ix, const VsCall &vc, const VsArgs &a, hipStream_t st) {
@@ -127,11 +98,11 @@ void vs_run(slg_index *ix, const VsCall &vc, const VsArgs &a, hipStream_t st) {
     sp.qvec4 = (vc.q_floats % 4 == 0 && vc.coff[c] % 4 == 0 && ((uintptr_t)a.qvecs & 15) == 0) ? 1u : 0u;
     const size_t lds = slg::vs_scan_lds_bytes(topk, sp.cap);
     if (vc.metric[c] == 0)
-      topk ? vs_launch_kernel(slg::vs_scan_kernel<0, true>, sp, grid, 256, lds, st)
-           : vs_launch_kernel(slg::vs_scan_kernel<0, false>, sp, grid, 256, lds, st);
+      topk ? launch_kernel_lds(slg::vs_scan_kernel<0, true>, sp, grid, 256, lds, st)
+           : launch_kernel_lds(slg::vs_scan_kernel<0, false>, sp, grid, 256, lds, st);
     else
-      topk ? vs_launch_kernel(slg::vs_scan_kernel<1, true>, sp, grid, 256, lds, st)
-           : vs_launch_kernel(slg::vs_scan_kernel<1, false>, sp, grid, 256, lds, st);
+      topk ? launch_kernel_lds(slg::vs_scan_kernel<1, true>, sp, grid, 256, lds, st)
+           : launch_kernel_lds(slg::vs_scan_kernel<1, false>, sp, grid, 256, lds, st);
   };
   slg::VsSelectParams sel{};
   sel.run = run;
@@ -146,7 +117,7 @@ void vs_run(slg_index *ix, const VsCall &vc, const VsArgs &a, hipStream_t st) {
     sel.in_stride = stride;
     sel.final_ = final_ ? 1u : 0u;
     const size_t lds = (size_t)slg::vs_pow2(K + n_in_q) * 8;
-    vs_launch_kernel(slg::vs_select_kernel, sel, dim3(nq, n_cl), slg::kVsSortThreads, lds, st);
+    launch_kernel_lds(slg::vs_select_kernel, sel, dim3(nq, n_cl), slg::kVsSortThreads, lds, st);
   };
   if (small) {
     sp.tile_begin = 0;
@@ -193,7 +164,7 @@ void vs_run(slg_index *ix, const VsCall &vc, const VsArgs &a, hipStream_t st) {
   bp.out_vec = a.out_vec;
   bp.out_count = a.out_count;
   bp.out_total = a.out_total;
-  vs_launch_kernel(slg::vs_blend_kernel, bp, dim3(nq), slg::kVsSortThreads,
+  launch_kernel_lds(slg::vs_blend_kernel<false>, bp, dim3(nq), slg::kVsSortThreads,
                    P > slg::kVsSortCap ? 0 : (size_t)P * 8, st);
 }
 
@@ -240,6 +211,85 @@ void vs_staged(slg_index *ix, uint32_t nq, uint32_t n_clauses, const uint32_t *c
   SLG_HIP(hipStreamSynchronize(st));
 }
 }  // namespace
+
+size_t slghost::hy_work_layout(const VsCall &vc, uint32_t bm_k, void *base, HyWork *w) {
+  const size_t n_run = (size_t)vc.n_clauses * vc.nq * vc.cand, n_cnt = (size_t)vc.n_clauses * vc.nq;
+  const uint32_t P = slg::vs_pow2(vc.n_clauses * vc.cand + bm_k), Pb = slg::vs_pow2(std::max<uint32_t>(bm_k, 1u));
+  // the union keys sort in LDS while they fit, and the BM25 hits behind them while both do
+  const size_t n_u = P > slg::kVsSortCap ? (size_t)vc.nq * P : 0;
+  const size_t n_b = P + Pb > slg::kVsSortCap ? (size_t)vc.nq * Pb : 0;
+  if (w) {
+    uint64_t *p = static_cast<uint64_t *>(base);
+    w->run = p;
+    w->dlist = w->run + n_run;
+    w->ukeys = w->dlist + n_run;
+    w->bkeys = w->ukeys + n_u;
+    w->cnt = reinterpret_cast<uint32_t *>(w->bkeys + n_b);
+    w->P = P;
+    w->Pb = Pb;
+  }
+  return (2 * n_run + n_u + n_b) * 8 + 2 * n_cnt * 4 + 256;
+}
+
+void slghost::hy_fold(const VsCall &vc, const HyWork &w, const HyKeys &k, hipStream_t st) {
+  const uint32_t K = vc.cand, NC = vc.n_clauses;
+  const uint32_t fold_n = slg::kVsSortCap - K;  // keys of a pass: with the running list they sort in LDS
+  slg::VsSelectParams sel{};
+  sel.run = w.run;
+  sel.run_cnt = w.cnt;
+  sel.dlist = w.dlist;
+  sel.nq = vc.nq;
+  sel.k = K;
+  sel.in = k.keys;
+  sel.in_stride = (uint32_t)k.stride;
+  sel.in_off = k.q_cand;
+  sel.in_cnt = w.cnt + (size_t)NC * vc.nq;
+  sel.in_base = k.slot_lo;
+  sel.q0 = k.q_lo;
+  sel.n_in = fold_n;
+  const uint64_t passes = std::max<uint64_t>((k.max_cap + fold_n - 1) / fold_n, 1);
+  const size_t lds = (size_t)slg::vs_pow2((uint32_t)std::min<uint64_t>(K + k.max_cap, slg::kVsSortCap)) * 8;
+  for (uint64_t t = 0; t < passes; t++) {
+    sel.in_skip = (uint32_t)(t * fold_n);
+    sel.final_ = t + 1 == passes ? 1u : 0u;
+    launch_kernel_lds(slg::vs_select_kernel, sel, dim3(k.q_hi - k.q_lo, NC), slg::kVsSortThreads, lds, st);
+  }
+}
+
+void slghost::hy_blend(const VsCall &vc, const VsArgs &a, const HyWork &w, const uint32_t *bm_doc,
+                       const uint32_t *bm_seg, const float *bm_score, const uint32_t *bm_count, uint32_t bm_k,
+                       hipStream_t st) {
+  const IndexState &S = *vc.S;
+  slg::VsBlendParams bp{};
+  bp.dlist = w.dlist;
+  bp.run_cnt = w.cnt;
+  bp.nq = vc.nq;
+  bp.k = vc.cand;
+  bp.n_clauses = vc.n_clauses;
+  bp.alpha = a.alpha;
+  for (uint32_t c = 0; c < vc.n_clauses; c++) bp.metric[c] = vc.metric[c];
+  bp.doc_base = S.d_doc_base.as<uint32_t>();
+  bp.n_segs = (uint32_t)S.segs.size();
+  bp.ukeys = w.ukeys;
+  bp.P = w.P;
+  bp.k_out = vc.k_out;
+  bp.out_doc = a.out_doc;
+  bp.out_seg = a.out_seg;
+  bp.out_score = a.out_score;
+  bp.out_vec = a.out_vec;
+  bp.out_count = a.out_count;
+  bp.out_total = a.out_total;
+  bp.bm_doc = bm_doc;
+  bp.bm_seg = bm_seg;
+  bp.bm_score = bm_score;
+  bp.bm_count = bm_count;
+  bp.bkeys = w.bkeys;
+  bp.bm_k = bm_k;
+  bp.Pb = w.Pb;
+  bp.bm_lds = w.P + w.Pb <= slg::kVsSortCap ? 1u : 0u;
+  const size_t lds = ((w.P > slg::kVsSortCap ? 0 : (size_t)w.P) + (bp.bm_lds ? w.Pb : 0)) * 8;
+  launch_kernel_lds(slg::vs_blend_kernel<true>, bp, dim3(vc.nq), slg::kVsSortThreads, lds, st);
+}
 
 extern "C" {
 

@@ -16,6 +16,8 @@
 //     into each query's running top-cand_size (bitonic sort in LDS), chunk after chunk.
 // vs_select_kernel's last step also leaves every clause list sorted by doc; vs_blend_kernel forms the
 // union of the clause lists, applies compute_hybrid_score at bm25 = 0 (:225-254) and sorts the union.
+// Hybrid text + vector search (slg_hybrid.hpp) gathers its keys from a batch's matched docs and shares the
+// last two steps: vs_select_kernel folds them, vs_blend_kernel<true> adds the BM25 hits to the union.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -336,22 +338,36 @@ struct VsSelectParams {
   uint32_t *run_cnt;   // [clause][q]
   uint64_t *dlist;     // [clause][q][k]
   uint32_t nq, k, c0, final_;
+  // hybrid search (slg_hybrid.hpp: the keys hy_gather_kernel appended): the workgroups are queries q0 + x;
+  // query q's keys of clause c0 + y start at in + y * in_stride + (in_off[q] - in_base), in_cnt[clause][q] of
+  // them, and this pass folds those from in_skip on, at most n_in.  in_off == nullptr: the layout above
+  const uint64_t *in_off;
+  const uint32_t *in_cnt;
+  uint64_t in_base;
+  uint32_t in_skip, q0;
 };
 
 __global__ void __launch_bounds__(kVsSortThreads) vs_select_kernel(VsSelectParams p) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   uint64_t *s = reinterpret_cast<uint64_t *>(smem);
   __shared__ uint32_t s_n;
-  const uint32_t q = blockIdx.x, c = p.c0 + blockIdx.y;
+  const uint32_t q = p.q0 + blockIdx.x, c = p.c0 + blockIdx.y;
   const size_t qc = (size_t)c * p.nq + q;
+  const uint64_t *in = p.in + ((size_t)blockIdx.y * p.nq + q) * p.in_stride;
+  uint32_t n_in = p.n_in;
+  if (p.in_off) {
+    const uint32_t have = p.in_cnt[qc];
+    n_in = have > p.in_skip ? (have - p.in_skip < n_in ? have - p.in_skip : n_in) : 0u;
+    in = p.in + (size_t)blockIdx.y * p.in_stride + (p.in_off[q] - p.in_base) + p.in_skip;
+    if (n_in == 0 && !p.final_) return;  // (nothing of this query in this pass)
+  }
   uint64_t *run = p.run + qc * p.k;
   const uint32_t cnt = p.run_cnt[qc];
   const uint64_t th = cnt >= p.k ? run[p.k - 1] : 0ull;
   for (uint32_t i = threadIdx.x; i < cnt; i += blockDim.x) s[i] = run[i];
   if (threadIdx.x == 0) s_n = cnt;
   __syncthreads();
-  const uint64_t *in = p.in + ((size_t)blockIdx.y * p.nq + q) * p.in_stride;
-  for (uint32_t i = threadIdx.x; i < p.n_in; i += blockDim.x) {
+  for (uint32_t i = threadIdx.x; i < n_in; i += blockDim.x) {
     const uint64_t key = in[i];
     if (key > th) s[atomicAdd(&s_n, 1u)] = key;
   }
@@ -392,13 +408,65 @@ struct VsBlendParams {
   float *out_score, *out_vec;
   uint32_t *out_count;
   uint64_t *out_total;
+  // (HYBRID) the BM25 hits of the batch: rows [nq][bm_k], bm_count[q] of them filled; Pb = vs_pow2(bm_k) keys
+  // of work space per query: behind the union keys in LDS (bm_lds), else at bkeys
+  const uint32_t *bm_doc, *bm_seg;
+  const float *bm_score;
+  const uint32_t *bm_count;
+  uint64_t *bkeys;
+  uint32_t bm_k, Pb, bm_lds;
 };
 
+// HYBRID (merge_vector_hits, api/reader.rs:2474-2537): the union also holds the query's BM25 hits, a union
+// doc's bm25 is its score among those hits or 0.0 (:2496-2500), and when every alpha is <= 0 a doc that no
+// clause list holds is dropped (all_vector_only, :2494,2504); such a row's vector score, the reference's None,
+// is the missing-vector score of clause 0's metric, as the rerank kernels write it.
+template <bool HYBRID>
 __global__ void __launch_bounds__(kVsSortThreads) vs_blend_kernel(VsBlendParams p) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   __shared__ uint32_t s_n;
   const uint32_t q = blockIdx.x, NC = p.n_clauses;
   uint64_t *u = p.P > kVsSortCap ? p.ukeys + (size_t)q * p.P : reinterpret_cast<uint64_t *>(smem);
+  // (HYBRID) the BM25 hits as (flat << 32 | score bits), descending, so by flat doc for the binary search
+  const uint64_t *bl = nullptr;
+  uint32_t nb = 0;
+  bool vec_only = false;
+  if constexpr (HYBRID) {
+    uint64_t *b = p.bm_lds ? reinterpret_cast<uint64_t *>(smem) + p.P : p.bkeys + (size_t)q * p.Pb;
+    nb = p.bm_count[q] < p.bm_k ? p.bm_count[q] : p.bm_k;
+    for (uint32_t i = threadIdx.x; i < p.Pb; i += blockDim.x) {
+      uint64_t key = 0ull;
+      if (i < nb) {
+        const size_t o = (size_t)q * p.bm_k + i;
+        const uint32_t sg = p.bm_seg[o] < p.n_segs ? p.bm_seg[o] : 0u;
+        key = ((uint64_t)(p.doc_base[sg] + p.bm_doc[o]) << 32) | (uint32_t)__float_as_int(p.bm_score[o]);
+      }
+      b[i] = key;
+    }
+    __syncthreads();
+    vs_bitonic_desc(b, p.Pb);
+    __syncthreads();
+    bl = b;
+    vec_only = true;
+    for (uint32_t cc = 0; cc < NC; cc++) vec_only = vec_only && p.alpha[(size_t)q * NC + cc] <= 0.0f;
+  }
+  // (HYBRID) the BM25 score of flat, if it is a BM25 hit
+  auto bm_lookup = [&](uint32_t flat, float *bm) -> bool {
+    uint32_t lo = 0, hi = nb;
+    while (lo < hi) {
+      const uint32_t mid = (lo + hi) >> 1;
+      const uint32_t f = (uint32_t)(bl[mid] >> 32);
+      if (f == flat) {
+        *bm = __int_as_float((int32_t)(uint32_t)bl[mid]);
+        return true;
+      }
+      if (f > flat)
+        lo = mid + 1;
+      else
+        hi = mid;
+    }
+    return false;
+  };
   auto list = [&](uint32_t c) { return p.dlist + ((size_t)c * p.nq + q) * p.k; };
   auto count = [&](uint32_t c) { return p.run_cnt[(size_t)c * p.nq + q]; };
   // the score of flat in clause c's list, if it is there
@@ -420,22 +488,37 @@ __global__ void __launch_bounds__(kVsSortThreads) vs_blend_kernel(VsBlendParams 
     return false;
   };
   // compute_hybrid_score, clauses in order: the final score and the vector sum
-  auto hybrid = [&](uint32_t flat, float *vsum) -> float {
-    const float bm = 0.0f;
+  auto hybrid = [&](uint32_t flat, float *vsum, bool *has) -> float {
+    float bm = 0.0f;
+    if constexpr (HYBRID) (void)bm_lookup(flat, &bm);
     float blended_sum = 0.0f, vector_sum = 0.0f;
+    bool found = false;
     for (uint32_t cc = 0; cc < NC; cc++) {
       float vs;
-      if (lookup(cc, flat, &vs))
+      if (lookup(cc, flat, &vs)) {
         vector_sum += vs;
-      else
+        found = true;
+      } else {
         vs = missing_vector_score(p.metric[cc]);  // (:217-223)
+      }
       blended_sum += blend(p.alpha[(size_t)q * NC + cc], bm, vs);
     }
     *vsum = vector_sum;
+    *has = found;
     return blended_sum / (float)NC;
   };
   if (threadIdx.x == 0) s_n = 0;
   __syncthreads();
+  if constexpr (HYBRID) {
+    for (uint32_t i = threadIdx.x; i < nb; i += blockDim.x) {
+      const uint32_t flat = (uint32_t)(bl[i] >> 32);
+      float vsum;
+      bool has;
+      const float fin = hybrid(flat, &vsum, &has);
+      if (vec_only && !has) continue;
+      u[atomicAdd(&s_n, 1u)] = ((uint64_t)ordered_score(fin) << 32) | (uint32_t)~flat;
+    }
+  }
   for (uint32_t c = 0; c < NC; c++) {
     const uint64_t *l = list(c);
     const uint32_t n = count(c);
@@ -443,10 +526,12 @@ __global__ void __launch_bounds__(kVsSortThreads) vs_blend_kernel(VsBlendParams 
       const uint32_t flat = (uint32_t)(l[i] >> 32);
       bool seen = false;  // a doc belongs to the first clause whose list holds it
       float dummy;
+      if constexpr (HYBRID) seen = bm_lookup(flat, &dummy);  // (or to the BM25 hits)
       for (uint32_t cc = 0; cc < c && !seen; cc++) seen = lookup(cc, flat, &dummy);
       if (seen) continue;
       float vsum;
-      const float fin = hybrid(flat, &vsum);
+      bool has;
+      const float fin = hybrid(flat, &vsum, &has);
       u[atomicAdd(&s_n, 1u)] = ((uint64_t)ordered_score(fin) << 32) | (uint32_t)~flat;
     }
   }
@@ -462,11 +547,12 @@ __global__ void __launch_bounds__(kVsSortThreads) vs_blend_kernel(VsBlendParams 
       const uint32_t flat = ~(uint32_t)key;
       const uint32_t seg = vs_seg_of(p.doc_base, p.n_segs, flat);
       float vsum;
-      (void)hybrid(flat, &vsum);
+      bool has;
+      (void)hybrid(flat, &vsum, &has);
       p.out_doc[o] = flat - p.doc_base[seg];
       p.out_seg[o] = seg;
       p.out_score[o] = vs_key_score(key);
-      if (p.out_vec) p.out_vec[o] = vsum;
+      if (p.out_vec) p.out_vec[o] = HYBRID && !has ? missing_vector_score(p.metric[0]) : vsum;
     } else {
       p.out_doc[o] = 0u;
       p.out_seg[o] = 0u;

@@ -57,6 +57,22 @@ __device__ __forceinline__ uint32_t wave_excl_scan(uint32_t v, uint32_t lane) {
 __device__ __forceinline__ int32_t wave_shr1(int32_t v) {
   return __builtin_amdgcn_update_dpp(v, v, 0x138 /* wave_shr:1 */, 0xf, 0xf, false);
 }
+// wave-wide f32 sum with DPP row shifts / broadcasts (no LDS round trips); result in lane 63
+__device__ __forceinline__ float wave_sum_f(float v) {
+  int x = __float_as_int(v);
+#define SLG_DPP_ADD(ctrl, rmask)                                                                \
+  x = __float_as_int(__int_as_float(x) +                                                        \
+                     __int_as_float(__builtin_amdgcn_update_dpp(0, x, ctrl, rmask, 0xf, true)))
+  SLG_DPP_ADD(0x111, 0xf);  // row_shr:1
+  SLG_DPP_ADD(0x112, 0xf);  // row_shr:2
+  SLG_DPP_ADD(0x114, 0xf);  // row_shr:4
+  SLG_DPP_ADD(0x118, 0xf);  // row_shr:8
+  SLG_DPP_ADD(0x142, 0xa);  // row_bcast:15
+  SLG_DPP_ADD(0x143, 0xc);  // row_bcast:31
+#undef SLG_DPP_ADD
+  return __int_as_float(__builtin_amdgcn_readlane(x, 63));
+}
+
 // compiler-only ordering point for wave-synchronous LDS traffic (hardware keeps a wave's
 // DS instructions in order; this stops the compiler from moving them across phases)
 __device__ __forceinline__ void wave_fence() { __atomic_signal_fence(__ATOMIC_SEQ_CST); }

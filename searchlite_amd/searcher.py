@@ -279,17 +279,18 @@ class GpuIndex:
                 q_filter=None, q_leaf=None, q_plan=None, q_tie=None, q_nleaves=None,
                 q_leaf_offsets=None, leaf_group=None, q_group_offsets=None, group_plan=None,
                 group_tie=None, q_node_offsets=None, node_kind=None, node_tie=None, node_parent=None,
-                q_min_match=None, sort=None, cursors=None) -> "PreparedBatch":
+                q_min_match=None, sort=None, cursors=None, hybrid=False) -> "PreparedBatch":
         """q_leaf / q_plan / q_tie / q_nleaves: score plans; leaf_group / group_plan / group_tie with
         their per-query offsets: two-level plans; q_node_offsets / node_kind / node_tie / node_parent:
         trees of any shape, node by node in pre-order (slg_batch_prepare_plans, slg_score_plans);
         q_min_match: minimum_should_match per query (leaves that must hold a doc); sort: a field sort
         (search_sorted) -> slg_batch_prepare_sorted; cursors: a cursor per query (search_after) ->
-        slg_batch_prepare_after."""
+        slg_batch_prepare_after; hybrid: the text side of a hybrid text + vector search ->
+        slg_batch_prepare_hybrid (PreparedBatch.hybrid_device)."""
         return PreparedBatch(self, q_offsets, q_terms, q_weights, k, strategy, q_filter,
                              q_leaf, q_plan, q_tie, q_nleaves, q_leaf_offsets, leaf_group,
                              q_group_offsets, group_plan, group_tie, q_node_offsets, node_kind, node_tie, node_parent,
-                             q_min_match, sort, cursors)
+                             q_min_match, sort, cursors, hybrid)
 
     def search_plan(self, q_offsets, q_terms, q_weights, k: int, q_leaf=None, q_plan=None,
                     q_tie=None, q_nleaves=None, strategy: int = Wand, q_filter=None, **tree):
@@ -463,6 +464,36 @@ class GpuIndex:
             _ptr(doc), _ptr(seg), _ptr(score), _ptr(vec), _ptr(count), _ptr(total)))
         return doc, seg, score, vec, count, total
 
+    def search_hybrid(self, q_offsets, q_terms, q_weights, k: int, clause_field, qvecs, alpha, cand_size: int,
+                      k_out: int, boost=None, strategy: int = Wand, q_filter=None, **plans):
+        """Hybrid text + vector search (merge_vector_hits, api/reader.rs:2474-2537) in one call: the BM25 top k
+        of the text query's matched docs, per clause the best cand_size vector scores among the matched docs,
+        their union blended as compute_hybrid_score.  Queries as prepare(); clause arrays as vector_search().
+        -> (doc, seg, score, vec_score) [nq, k_out], count [nq], total [nq] (union size)."""
+        if plans:  # (score plans: the prepared form builds slg_score_plans)
+            with self.prepare(q_offsets, q_terms, q_weights, k, strategy, q_filter, hybrid=True, **plans) as b:
+                return b.hybrid(clause_field, qvecs, alpha, cand_size, k_out, boost)
+        q_offsets = np.ascontiguousarray(q_offsets, dtype=np.uint32)
+        q_terms = np.ascontiguousarray(q_terms, dtype=np.uint32)
+        q_weights = np.ascontiguousarray(q_weights, dtype=np.float32)
+        nq = len(q_offsets) - 1
+        cf = np.ascontiguousarray(clause_field, dtype=np.uint32)
+        nc = len(cf)
+        qvecs = np.ascontiguousarray(qvecs, dtype=np.float32)
+        alpha, bst = _f32(alpha, (nq, nc)), _f32(boost, (nq, nc))
+        flt = None if q_filter is None else np.ascontiguousarray(q_filter, dtype=np.int32)
+        doc = np.zeros((nq, k_out), np.uint32)
+        seg = np.zeros((nq, k_out), np.uint32)
+        score = np.zeros((nq, k_out), np.float32)
+        vec = np.zeros((nq, k_out), np.float32)
+        count = np.zeros(nq, np.uint32)
+        total = np.zeros(nq, np.uint64)
+        N.check(self._lib.slg_search_batch_hybrid(
+            self._h, nq, _ptr(q_offsets), _ptr(q_terms), _ptr(q_weights), None, _ptr(flt), int(k), int(strategy),
+            nc, _ptr(cf), _ptr(qvecs), _ptr(alpha), _ptr(bst), int(cand_size), int(k_out),
+            _ptr(doc), _ptr(seg), _ptr(score), _ptr(vec), _ptr(count), _ptr(total)))
+        return doc, seg, score, vec, count, total
+
     def vector_search_device(self, nq, clause_field, d_qvecs, d_alpha, d_boost, d_q_filter, cand_size, k_out,
                              d_out_doc, d_out_seg, d_out_score, d_out_vec, d_out_count, d_out_total) -> None:
         """Device-pointer form of vector_search (ints; d_boost / d_q_filter may be None; clause_field
@@ -587,7 +618,7 @@ class PreparedBatch:
                  q_filter=None, q_leaf=None, q_plan=None, q_tie=None, q_nleaves=None,
                  q_leaf_offsets=None, leaf_group=None, q_group_offsets=None, group_plan=None,
                  group_tie=None, q_node_offsets=None, node_kind=None, node_tie=None, node_parent=None,
-                 q_min_match=None, sort=None, cursors=None):
+                 q_min_match=None, sort=None, cursors=None, hybrid=False):
         self.index = index
         self._lib = index._lib
         q_offsets = np.ascontiguousarray(q_offsets, dtype=np.uint32)
@@ -617,7 +648,13 @@ class PreparedBatch:
                              opt(qno), opt(nk), opt(ntie), opt(npar), opt(qmm))
         self.sorted = sort is not None
         self.after = cursors is not None
-        if cursors is not None:
+        self.is_hybrid = bool(hybrid)
+        assert not (hybrid and (sort is not None or cursors is not None)), "a hybrid batch takes no sort or cursor"
+        if hybrid:
+            self._h = self._lib.slg_batch_prepare_hybrid(
+                index._h, self.nq, _ptr(q_offsets), _ptr(q_terms), _ptr(q_weights), C.addressof(plans),
+                opt(qf), k, strategy)
+        elif cursors is not None:
             assert len(cursors) == self.nq
             cur = (N.SortCursor * max(self.nq, 1))(*[sort_cursor(c, sort) for c in cursors])
             spec = None if sort is None else sort_spec(sort)
@@ -712,6 +749,46 @@ class PreparedBatch:
         """slg_batch_rerank_device: rerank this batch's own device results on the batch's stream."""
         N.check(self._lib.slg_batch_rerank_device(self._h, n_clauses, d_qvecs, d_alpha, d_boost, k_out, d_out_doc,
                                                   d_out_seg, d_out_score, d_out_vec, d_out_count))
+
+    def hybrid_device(self, clause_field, d_qvecs, d_alpha, d_boost, cand_size, k_out, d_out_doc, d_out_seg,
+                      d_out_score, d_out_vec, d_out_count, d_out_total) -> None:
+        """slg_batch_hybrid_device: the vector side of a hybrid batch (prepare(..., hybrid=True)) after run(),
+        on the batch's stream; device addresses (ints), clause_field a host array, d_boost may be None."""
+        cf = np.ascontiguousarray(clause_field, dtype=np.uint32)
+        N.check(self._lib.slg_batch_hybrid_device(self._h, len(cf), _ptr(cf), d_qvecs, d_alpha, d_boost,
+                                                  int(cand_size), int(k_out), d_out_doc, d_out_seg, d_out_score,
+                                                  d_out_vec, d_out_count, d_out_total))
+
+    def hybrid(self, clause_field, qvecs, alpha, cand_size: int, k_out: int, boost=None):
+        """run() + hybrid_device() with host arrays (staged through torch tensors on the index's device);
+        waits.  -> (doc, seg, score, vec_score) [nq, k_out], count [nq], total [nq]."""
+        import torch
+        nq, nc = self.nq, len(clause_field)
+        dev = torch.device("cuda", self.index.device)
+        up = lambda a: None if a is None else torch.from_numpy(np.array(a, order="C")).to(dev)  # (a writable copy)
+        t_q = up(np.ascontiguousarray(qvecs, dtype=np.float32).reshape(nq, -1))
+        t_a, t_b = up(_f32(alpha, (nq, nc))), up(_f32(boost, (nq, nc)))
+        o_doc = torch.zeros((nq, k_out), dtype=torch.int32, device=dev)
+        o_seg = torch.zeros_like(o_doc)
+        o_score = torch.zeros((nq, k_out), dtype=torch.float32, device=dev)
+        o_vec = torch.zeros_like(o_score)
+        o_cnt = torch.zeros(max(nq, 1), dtype=torch.int32, device=dev)
+        o_tot = torch.zeros(max(nq, 1), dtype=torch.int64, device=dev)
+        torch.cuda.synchronize(dev)
+        self.run()
+        ptr = lambda t: None if t is None else t.data_ptr()
+        self.hybrid_device(clause_field, ptr(t_q), ptr(t_a), ptr(t_b), cand_size, k_out, ptr(o_doc), ptr(o_seg),
+                           ptr(o_score), ptr(o_vec), ptr(o_cnt), ptr(o_tot))
+        self.sync()
+        return (o_doc.cpu().numpy().view(np.uint32), o_seg.cpu().numpy().view(np.uint32), o_score.cpu().numpy(),
+                o_vec.cpu().numpy(), o_cnt.cpu().numpy().view(np.uint32)[:nq],
+                o_tot.cpu().numpy().view(np.uint64)[:nq])
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
 
     def sync(self) -> None:
         N.check(self._lib.slg_batch_sync(self._h))

@@ -23,7 +23,9 @@
  * k = limit + 1 up to 20 001; up to 32 scored terms per query and segment.  Field sorts (slg_batch_prepare_sorted):
  * up to SLG_MAX_SORT_PARTS parts of numeric fast fields (i64 / f64) and _score, any order; keyword parts stay
  * on the CPU.  A cursor (the next page, slg_batch_prepare_after) in score order or in a device-eligible field
- * sort; not in sharded runs or the coalescer.
+ * sort; not in sharded runs or the coalescer.  Aggregations (slg_batch_prepare_aggs): terms, histogram, range and
+ * stats over registered columns, two levels, in score order or a field sort; not with a cursor, not on hybrid,
+ * vector-only, sharded or coalesced batches.
  */
 #ifndef SEARCHLITE_GPU_H
 #define SEARCHLITE_GPU_H
@@ -519,6 +521,133 @@ int slg_batch_info(const slg_batch *batch, uint64_t *n_postings, uint32_t *n_sli
  * slg_tuning.block_max is off.  Waits for the batch. */
 int slg_batch_skip_counts(slg_batch *batch, uint64_t *probed_postings, uint64_t *skipped_postings);
 void slg_batch_destroy(slg_batch *batch);
+
+/* ---- aggregations (query/aggs/mod.rs: `aggs` with terms, histogram, range and stats) ----------------
+ * A request with `aggs` makes the reference visit every matched doc (a collector sets the WAND threshold to
+ * -inf, query/wand.rs:725-729) and upsert a hash map per aggregation and doc (aggs/mod.rs:894-930,
+ * 1166-1204).  On the device an aggregation batch is planned like a sorted batch — every matched doc is a
+ * candidate, once, with its exact score — and one more kernel walks the candidates and fills dense bucket
+ * tables.  The aggregated set of a query is exactly the docs slg_batch_matched_counts counts: those that
+ * pass tombstones, the doc filter and minimum_should_match (api/reader.rs:3009-3036), over all segments,
+ * whatever k is.  The rows of an aggregation batch are bit-identical to the same batch without aggregations.
+ *
+ * Columns are registered once per index and named by id, with the lifecycle and id policy of sort fields:
+ * per segment a CSR (seg_offsets[s][n_docs + 1] into seg_values[s]; an empty range = the doc has no value;
+ * seg_offsets[s] == NULL = no doc of segment s has one); slg_index_update_deleted keeps the columns,
+ * slg_index_remove_segment drops that segment's, slg_index_add_segment gives the new segment none (a batch
+ * that names the field then fails with SLG_ERR_INVALID until it is registered again); ids are never handed
+ * out again.  Numeric columns hold f64 (an i64 field arrives as `v as f64`, index/fastfields.rs:772-800, the
+ * conversion done here on the host); registration records the column's finite minimum and maximum and
+ * whether it holds a non-finite value.  The reference's behaviour on NaN / +-inf is an accident of `as i64`
+ * saturation and f64::min: a batch that names such a column fails with SLG_ERR_UNSUPPORTED (CPU path).
+ * A keyword column holds u32 ordinals into ONE caller-owned dictionary of n_ords keys: the caller maps each
+ * segment's own dictionary (index/fastfields.rs:711-734) to global ordinals; an ordinal >= n_ords is
+ * SLG_ERR_INVALID.  Return the field id (>= 0) or a negative error code. */
+#define SLG_MAX_AGGS 8u          /* nodes of one spec, roots and children together */
+#define SLG_MAX_AGG_RANGES 16u   /* ranges of one SLG_AGG_RANGE node */
+#define SLG_MAX_AGG_CELLS 65536u /* count cells + stats cells of one query */
+#define SLG_AGG_LDS_BYTES 32768u /* tables of 4 B per count cell + 32 B per stats cell up to this size are
+                                    filled in LDS, larger ones in device memory (same results) */
+enum { SLG_AGG_TERMS = 0, SLG_AGG_HISTOGRAM = 1, SLG_AGG_RANGE = 2, SLG_AGG_STATS = 3 };
+int slg_index_add_agg_field_f64(slg_index *index, const uint32_t *const *seg_offsets,
+                                const double *const *seg_values);
+int slg_index_add_agg_field_i64(slg_index *index, const uint32_t *const *seg_offsets,
+                                const int64_t *const *seg_values);
+int slg_index_add_agg_field_ord(slg_index *index, const uint32_t *const *seg_offsets,
+                                const uint32_t *const *seg_ords, uint32_t n_ords);
+/* Batches already prepared with the field keep its columns (they belong to the batch's index state). */
+int slg_index_remove_agg_field(slg_index *index, int agg_field_id);
+
+/* One aggregation node.  A node is a root (parent == -1) or the child of an EARLIER bucket root (terms,
+ * histogram or range); children have no children.  A child under a bucket collects the doc once per parent
+ * bucket the doc was counted in (aggs/mod.rs:905-908, 1026-1028, 1200-1202).
+ *   SLG_AGG_TERMS      keyword column.  A doc counts once in every DISTINCT ordinal it holds (:898-909); a
+ *                      doc without a value counts in row missing_ord if has_missing (:914-929).  missing_ord
+ *                      in [0, n_ords]: n_ords = a key of its own (one more row), a smaller value = the missing
+ *                      key equals that real key (the reference puts both into one bucket).
+ *   SLG_AGG_HISTOGRAM  numeric column.  Bucket id = floor((val - offset) / interval) in IEEE f64 (:1162-1164);
+ *                      a doc counts once per DISTINCT id (:1174-1184); with has_hard_bounds values with
+ *                      val < hard_min || val > hard_max are skipped (:1176-1180); a doc without a value has the
+ *                      one value `missing` if has_missing (:597-610).  interval > 0 and finite, offset finite.
+ *   SLG_AGG_RANGE      numeric column, n_ranges <= SLG_MAX_AGG_RANGES.  A doc counts once in EVERY range for
+ *                      which ANY of its values has from <= val && val <= to (:1019-1030: `to` is inclusive);
+ *                      an absent bound is -/+infinity; `missing` as above.
+ *   SLG_AGG_STATS      numeric column: count, min, max, sum over EVERY value of every collected doc (:1426-1441);
+ *                      `missing` as above.  value_count, min, max, sum and avg follow on the host; extended_stats
+ *                      (m2) is not built.
+ * Everything after the tables is the caller's: ordering terms buckets (count desc, key string asc), size,
+ * min_doc_count, extended_bounds, histogram keys id * interval + offset, pipeline aggregations.
+ *
+ * ONE DELIBERATE DEVIATION: the reference truncates terms buckets to shard_size / size and applies
+ * min_doc_count PER SEGMENT before it merges (:932-944, 1230-1232, 2368-2393), so its multi-segment counts can
+ * be too low.  The device counts over all segments and is exact; it equals the reference whenever no segment
+ * truncates or drops a bucket.
+ *
+ * Determinism: counts, min and max are exact and identical from run to run.  sum is accumulated with f64
+ * atomic adds in an order the hardware picks: its last bits may differ between runs when the values are not
+ * exactly summable. */
+typedef struct {
+  int32_t kind;             /* SLG_AGG_* */
+  int32_t field;            /* agg field id */
+  int32_t parent;           /* -1, or the index of an earlier bucket root */
+  uint32_t has_missing;
+  double missing;           /* numeric kinds */
+  uint32_t missing_ord;     /* SLG_AGG_TERMS */
+  uint32_t has_hard_bounds; /* SLG_AGG_HISTOGRAM */
+  double interval, offset, hard_min, hard_max;
+  uint32_t n_ranges;        /* SLG_AGG_RANGE */
+  double from[SLG_MAX_AGG_RANGES], to[SLG_MAX_AGG_RANGES];
+} slg_agg_node;
+typedef struct {
+  uint32_t n_nodes; /* 1 .. SLG_MAX_AGGS */
+  slg_agg_node nodes[SLG_MAX_AGGS];
+} slg_agg_spec;
+/* A node's table is parent_rows x rows, parent-major (parent_rows = 1 for a root, else the parent's rows).
+ * rows: terms n_ords (+ 1 when missing_ord == n_ords); histogram the dense id range that the column's finite
+ * minimum and maximum, `missing` and the hard bounds allow (the bucket formula is monotone), row i = id
+ * first_id + i; range n_ranges; stats 1.  offset: the table's first cell in the query's count table (bucket
+ * kinds) or stats table (is_stats). */
+typedef struct {
+  uint32_t parent_rows, rows;
+  int64_t first_id; /* histogram: the id of row 0; else 0 */
+  uint32_t is_stats;
+  uint64_t offset;
+} slg_agg_layout;
+typedef struct {
+  uint64_t count;
+  double min, max, sum; /* all zero when count == 0 (StatsState::default) */
+} slg_agg_stats;
+/* slg_batch_prepare_plans (sort_or_null == NULL: score order) or slg_batch_prepare_sorted with one
+ * aggregation spec for the whole batch.  Every query shape those two take is accepted; the batch runs through
+ * slg_batch_run / _fetch / _matched_counts as any sorted batch.  Checked before anything else, without an
+ * index: aggs NULL, n_nodes == 0, an unknown kind, a parent that is not an earlier bucket root, a
+ * non-positive or non-finite interval, a non-finite offset / missing, a NaN bound, n_ranges == 0:
+ * SLG_ERR_INVALID; n_nodes > SLG_MAX_AGGS or n_ranges > SLG_MAX_AGG_RANGES: SLG_ERR_UNSUPPORTED.  Against
+ * the index: an unknown field id, a field without a column for every segment, a field of the wrong kind
+ * for its node, missing_ord > n_ords: SLG_ERR_INVALID; a numeric column with a non-finite value, or more than
+ * SLG_MAX_AGG_CELLS cells per query: SLG_ERR_UNSUPPORTED.  Aggregations are not built on cursor, hybrid,
+ * vector-only, sharded or coalesced batches (slg_batch_run_sharded* refuses an aggregation batch:
+ * SLG_ERR_UNSUPPORTED). */
+slg_batch *slg_batch_prepare_aggs(slg_index *index, uint32_t nq, const uint32_t *q_offsets,
+                                  const uint32_t *q_term_ids, const float *q_weights,
+                                  const slg_score_plans *plans_or_null, const int32_t *q_filter_or_null,
+                                  const slg_sort_spec *sort_or_null, const slg_agg_spec *aggs, uint32_t k,
+                                  int strategy);
+/* The layout of every node's table (out: n_nodes entries).  The cells of one query's count table
+ * (count_cells) and stats table (stats_cells) are the sums of parent_rows * rows over the bucket nodes and
+ * over the stats nodes; tables lie in node order. */
+int slg_batch_agg_layout(const slg_batch *batch, slg_agg_layout *out);
+/* The tables of the batch's last run: counts [nq x count_cells], stats [nq x stats_cells] (either may be
+ * NULL when it has no cells); waits for the batch. */
+int slg_batch_fetch_aggs(slg_batch *batch, uint64_t *counts, slg_agg_stats *stats);
+/* One-shot form: slg_search_batch_sorted with an aggregation spec (sort_or_null == NULL: score order);
+ * counts / stats are sized by the caller from the spec (a prepared batch tells through
+ * slg_batch_agg_layout); out_matched ([nq]) may be NULL. */
+int slg_search_batch_aggs(slg_index *index, const slg_query *queries, uint32_t nq,
+                          const slg_score_plans *plans_or_null, const int32_t *q_filter_or_null,
+                          const slg_sort_spec *sort_or_null, const slg_agg_spec *aggs, uint32_t k, int strategy,
+                          uint32_t *out_doc, uint32_t *out_seg, float *out_score, uint32_t *out_count,
+                          uint64_t *out_matched, uint64_t *counts, slg_agg_stats *stats);
 
 /* ---- request coalescer ------------------------------------------------------------------------------
  * searchlite has no batch API: IndexReader::search takes one request (api/reader.rs:2539) and the HTTP

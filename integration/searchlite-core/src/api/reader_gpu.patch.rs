@@ -107,3 +107,16 @@ if let Some(h) = gpu_hits {
 //           }).collect()
 //         }
 //       }
+
+// ---- aggregations ---------------------------------------------------------------------------------------
+// A request with `aggs` that gpu_eligible accepts (terms / histogram / range / stats, two levels, no sampling,
+// no cursor) goes through slg_batch_prepare_aggs instead of slg_batch_prepare_plans / _sorted: the same
+// arrays plus one slg_agg_spec (roots in the BTreeMap's name order, each followed by its children).  Staging
+// registers every fast field an aggregation may name: numeric fields with slg_index_add_agg_field_i64 / _f64
+// (CSR per segment, as the sort fields), keyword fields with slg_index_add_agg_field_ord after mapping each
+// segment's own dictionary (index/fastfields.rs:711-734) to the sorted union of all segments' keys.  After
+// slg_batch_fetch the shim reads slg_batch_agg_layout + slg_batch_fetch_aggs and builds the
+// AggregationResponse map on the host (terms_bucket_cmp order, size, min_doc_count, extended_bounds,
+// histogram keys, keyed ranges, pipeline aggregations over the shaped buckets): `agg_ref` stays None, no
+// collector runs.  SLG_ERR_UNSUPPORTED (a column with a non-finite value, more than SLG_MAX_AGG_CELLS cells)
+// falls back to the CPU collectors like every other library error.  Unverified, as all of the shim.

@@ -54,6 +54,24 @@ pub struct slg_tuning {
     pub has_cursor: u32, pub segment_ord: u32, pub doc_id: u32, pub missing_mask: u32,
     pub value_bits: [u64; SLG_MAX_SORT_PARTS],
 }
+// aggregations (query/aggs/mod.rs): the nodes of a batch's spec, the layout of a node's dense table, a stats cell
+pub const SLG_MAX_AGGS: usize = 8;
+pub const SLG_MAX_AGG_RANGES: usize = 16;
+pub const SLG_MAX_AGG_CELLS: u32 = 65536;
+pub const SLG_AGG_TERMS: i32 = 0;
+pub const SLG_AGG_HISTOGRAM: i32 = 1;
+pub const SLG_AGG_RANGE: i32 = 2;
+pub const SLG_AGG_STATS: i32 = 3;
+#[repr(C)] #[derive(Clone, Copy)] pub struct slg_agg_node {
+    pub kind: i32, pub field: i32, pub parent: i32, pub has_missing: u32, pub missing: f64, pub missing_ord: u32,
+    pub has_hard_bounds: u32, pub interval: f64, pub offset: f64, pub hard_min: f64, pub hard_max: f64,
+    pub n_ranges: u32, pub from: [f64; SLG_MAX_AGG_RANGES], pub to: [f64; SLG_MAX_AGG_RANGES],
+}
+#[repr(C)] #[derive(Clone, Copy)] pub struct slg_agg_spec { pub n_nodes: u32, pub nodes: [slg_agg_node; SLG_MAX_AGGS] }
+#[repr(C)] #[derive(Clone, Copy, Default)] pub struct slg_agg_layout {
+    pub parent_rows: u32, pub rows: u32, pub first_id: i64, pub is_stats: u32, pub offset: u64,
+}
+#[repr(C)] #[derive(Clone, Copy, Default)] pub struct slg_agg_stats { pub count: u64, pub min: f64, pub max: f64, pub sum: f64 }
 #[repr(C)] pub struct slg_stats { pub scored_docs: u64, pub candidates_examined: u64, pub postings_advanced: u64 }
 #[repr(C)] pub struct slg_query { pub n_terms: u32, pub term_ids: *const u32, pub weights: *const c_float }
 
@@ -150,6 +168,24 @@ extern "C" {
     pub fn slg_batch_prepare_sorted(index: *mut slg_index, nq: u32, q_offsets: *const u32, q_term_ids: *const u32,
         q_weights: *const c_float, plans_or_null: *const slg_score_plans, q_filter_or_null: *const i32,
         sort: *const slg_sort_spec, k: u32, strategy: c_int) -> *mut slg_batch;
+    // aggregation columns (ids and lifecycle as sort fields) and aggregation batches (sort NULL: score order)
+    pub fn slg_index_add_agg_field_f64(index: *mut slg_index, seg_offsets: *const *const u32,
+        seg_values: *const *const f64) -> c_int;
+    pub fn slg_index_add_agg_field_i64(index: *mut slg_index, seg_offsets: *const *const u32,
+        seg_values: *const *const i64) -> c_int;
+    pub fn slg_index_add_agg_field_ord(index: *mut slg_index, seg_offsets: *const *const u32,
+        seg_ords: *const *const u32, n_ords: u32) -> c_int;
+    pub fn slg_index_remove_agg_field(index: *mut slg_index, agg_field_id: c_int) -> c_int;
+    pub fn slg_batch_prepare_aggs(index: *mut slg_index, nq: u32, q_offsets: *const u32, q_term_ids: *const u32,
+        q_weights: *const c_float, plans_or_null: *const slg_score_plans, q_filter_or_null: *const i32,
+        sort_or_null: *const slg_sort_spec, aggs: *const slg_agg_spec, k: u32, strategy: c_int) -> *mut slg_batch;
+    pub fn slg_batch_agg_layout(batch: *const slg_batch, out: *mut slg_agg_layout) -> c_int;
+    pub fn slg_batch_fetch_aggs(batch: *mut slg_batch, counts: *mut u64, stats: *mut slg_agg_stats) -> c_int;
+    pub fn slg_search_batch_aggs(index: *mut slg_index, queries: *const slg_query, nq: u32,
+        plans_or_null: *const slg_score_plans, q_filter_or_null: *const i32, sort_or_null: *const slg_sort_spec,
+        aggs: *const slg_agg_spec, k: u32, strategy: c_int, out_doc: *mut u32, out_seg: *mut u32,
+        out_score: *mut c_float, out_count: *mut u32, out_matched: *mut u64, counts: *mut u64,
+        stats: *mut slg_agg_stats) -> c_int;
     pub fn slg_batch_matched_counts(batch: *mut slg_batch, out_matched: *mut u64) -> c_int;
     pub fn slg_search_batch_sorted(index: *mut slg_index, queries: *const slg_query, nq: u32,
         plans_or_null: *const slg_score_plans, q_filter_or_null: *const i32, sort: *const slg_sort_spec, k: u32,

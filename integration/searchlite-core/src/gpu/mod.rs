@@ -676,6 +676,39 @@ fn min_should_match(m: &QueryMatcher) -> Option<u32> {
   }
 }
 
+/// The aggregation trees slg_batch_prepare_aggs takes (include/searchlite_gpu.h, "aggregations"): four kinds,
+/// two levels, at most SLG_MAX_AGGS nodes, no sampling.  Unverified, as all of this shim.
+fn aggs_fit_device(aggs: &std::collections::BTreeMap<String, crate::api::types::Aggregation>) -> bool {
+  use crate::api::types::Aggregation as A;
+  fn leaf_ok(a: &A) -> bool {
+    match a {
+      A::Terms(t) => t.sampling.is_none() && t.aggs.is_empty(),
+      A::Histogram(h) => h.sampling.is_none() && h.aggs.is_empty(),
+      A::Range(r) => r.sampling.is_none() && r.aggs.is_empty() && r.ranges.len() <= ffi::SLG_MAX_AGG_RANGES,
+      A::Stats(_) => true,
+      _ => false,
+    }
+  }
+  let mut nodes = 0usize;
+  for a in aggs.values() {
+    let children = match a {
+      A::Terms(t) if t.sampling.is_none() => &t.aggs,
+      A::Histogram(h) if h.sampling.is_none() => &h.aggs,
+      A::Range(r) if r.sampling.is_none() && r.ranges.len() <= ffi::SLG_MAX_AGG_RANGES => &r.aggs,
+      A::Stats(_) => {
+        nodes += 1;
+        continue;
+      }
+      _ => return false,
+    };
+    if !children.values().all(leaf_ok) {
+      return false;
+    }
+    nodes += 1 + children.len();
+  }
+  nodes <= ffi::SLG_MAX_AGGS
+}
+
 /// is this request one the GPU scorer reproduces exactly?
 /// `needs_score_hook` = has_custom_scoring(&compiled_score) (api/reader.rs:376-387, :2628).
 pub(crate) fn gpu_eligible(
@@ -708,7 +741,23 @@ pub(crate) fn gpu_eligible(
   // no collector: agg_ref stays None only without aggregations (api/reader.rs:2694-2699).  A cursor (the next
   // page) runs on the device in score order and in every field sort above (slg_batch_prepare_after); with a
   // vector query it stays on the CPU
-  if !req.aggs.is_empty() || req.explain || needs_score_hook {
+  if req.explain || needs_score_hook {
+    return None;
+  }
+  // Aggregations run on the device (slg_batch_prepare_aggs) when the tree fits what is built there: terms,
+  // histogram, range and stats over registered columns, a root or the child of a bucket root (two levels), at
+  // most ffi::SLG_MAX_AGGS nodes, no `sampling`; anything else (significant_terms, rare_terms, date_*,
+  // composite, filter, percentiles, cardinality, top_hits, pipeline aggregations as NODES — they are applied on
+  // the host to the shaped buckets —, deeper trees) keeps the request on the CPU collectors.  Not with a cursor:
+  // cursor batches take no aggregations.  The caller maps every segment's keyword dictionary
+  // (index/fastfields.rs:711-734) to ONE dictionary per field at staging time (sorted union of the segments'
+  // keys; a segment's local ordinal -> the global one) and registers the columns with
+  // slg_index_add_agg_field_{ord,i64,f64}; the response is shaped on the host from the dense tables
+  // (slg_batch_agg_layout / slg_batch_fetch_aggs) exactly as finish() / finalize do (aggs/mod.rs:932-944,
+  // 1207-1245, 2469-2478): terms by count desc then key string asc, size, min_doc_count, extended_bounds zero
+  // buckets, histogram keys id * interval + offset, keyed ranges, pipeline aggregations.  One deviation: the
+  // device counts terms buckets over all segments (exact), the reference truncates them per segment first.
+  if !req.aggs.is_empty() && (req.cursor.is_some() || !aggs_fit_device(&req.aggs)) {
     return None;
   }
   #[cfg(feature = "vectors")]

@@ -26,6 +26,11 @@ PLAN_SUM, PLAN_DISMAX, PLAN_LEAF = 0, 1, 2
 MAX_SORT_PARTS = 4
 SORT_SCORE = -1
 ORDER_ASC, ORDER_DESC = 0, 1
+MAX_AGGS = 8
+MAX_AGG_RANGES = 16
+MAX_AGG_CELLS = 65536
+AGG_LDS_BYTES = 32768
+AGG_TERMS, AGG_HISTOGRAM, AGG_RANGE, AGG_STATS = 0, 1, 2, 3
 
 
 class SlgError(RuntimeError):
@@ -90,6 +95,30 @@ class SortCursor(C.Structure):
     doc, the Missing parts, and per part an i64 value, f64 bits or (low 32 bits) a score's f32 bits."""
     _fields_ = [("has_cursor", C.c_uint32), ("segment_ord", C.c_uint32), ("doc_id", C.c_uint32),
                 ("missing_mask", C.c_uint32), ("value_bits", C.c_uint64 * MAX_SORT_PARTS)]
+
+
+class AggNode(C.Structure):
+    """slg_agg_node: one aggregation node (AGG_* kind, agg field id, parent = -1 or an earlier bucket root)."""
+    _fields_ = [("kind", C.c_int32), ("field", C.c_int32), ("parent", C.c_int32), ("has_missing", C.c_uint32),
+                ("missing", C.c_double), ("missing_ord", C.c_uint32), ("has_hard_bounds", C.c_uint32),
+                ("interval", C.c_double), ("offset", C.c_double), ("hard_min", C.c_double), ("hard_max", C.c_double),
+                ("n_ranges", C.c_uint32), ("from_", C.c_double * MAX_AGG_RANGES), ("to", C.c_double * MAX_AGG_RANGES)]
+
+
+class AggSpec(C.Structure):
+    """slg_agg_spec: the nodes of a batch's aggregations, roots and children together."""
+    _fields_ = [("n_nodes", C.c_uint32), ("nodes", AggNode * MAX_AGGS)]
+
+
+class AggLayout(C.Structure):
+    """slg_agg_layout: a node's table is parent_rows x rows at `offset` of the count or the stats table."""
+    _fields_ = [("parent_rows", C.c_uint32), ("rows", C.c_uint32), ("first_id", C.c_int64),
+                ("is_stats", C.c_uint32), ("offset", C.c_uint64)]
+
+
+class AggStats(C.Structure):
+    """slg_agg_stats: one stats cell."""
+    _fields_ = [("count", C.c_uint64), ("min", C.c_double), ("max", C.c_double), ("sum", C.c_double)]
 
 
 class Ticket(C.Structure):
@@ -183,6 +212,14 @@ def load():
         "slg_batch_prepare_after": (vp, [vp, u32, vp, vp, vp, vp, vp, vp, vp, u32, i32]),
         "slg_batch_cursor_seen": (i32, [vp, vp]),
         "slg_search_batch_after": (i32, [vp, vp, u32, vp, vp, vp, vp, u32, i32, vp, vp, vp, vp, vp, vp]),
+        "slg_index_add_agg_field_f64": (i32, [vp, vp, vp]),
+        "slg_index_add_agg_field_i64": (i32, [vp, vp, vp]),
+        "slg_index_add_agg_field_ord": (i32, [vp, vp, vp, u32]),
+        "slg_index_remove_agg_field": (i32, [vp, i32]),
+        "slg_batch_prepare_aggs": (vp, [vp, u32, vp, vp, vp, vp, vp, vp, vp, u32, i32]),
+        "slg_batch_agg_layout": (i32, [vp, vp]),
+        "slg_batch_fetch_aggs": (i32, [vp, vp, vp]),
+        "slg_search_batch_aggs": (i32, [vp, vp, u32, vp, vp, vp, vp, u32, i32, vp, vp, vp, vp, vp, vp, vp]),
         "slg_batch_run": (i32, [vp]),
         "slg_batch_set_stream": (i32, [vp, vp]),
         "slg_batch_sync": (i32, [vp]),

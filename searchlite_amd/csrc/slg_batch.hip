@@ -124,7 +124,7 @@ void slghost::release_batch_buffers(slg_batch *b, bool to_pool) {
   DevBuf *bufs[] = {&b->d_desc, &b->d_bounds, &b->d_rdoc, &b->d_slice_desc, &b->d_slice_tk, &b->d_slice_doc,
                     &b->d_q_scored, &b->d_q_filter, &b->d_cand, &b->d_slice_cbeg, &b->d_slice_ccnt,
                     &b->d_out, &b->d_stamps, &b->d_blk_skip, &b->d_gather, &b->d_merged, &b->d_q_cand,
-                    &b->d_hy_keys, &b->d_hy_work};
+                    &b->d_hy_keys, &b->d_hy_work, &b->d_agg_desc, &b->d_agg_counts, &b->d_agg_stats};
   for (DevBuf *d : bufs) {
     if (!to_pool) d->pool = nullptr;
     d->release();
@@ -163,13 +163,15 @@ slg_batch *slg_batch_prepare_plan(slg_index *ix, uint32_t nq, const uint32_t *q_
 
 namespace {
 // slg_batch_prepare_plans, (sort != nullptr) slg_batch_prepare_sorted, (after) slg_batch_prepare_after, and
-// (hybrid) slg_batch_prepare_hybrid
+// (hybrid) slg_batch_prepare_hybrid, (aggs != nullptr) slg_batch_prepare_aggs
 slg_batch *prepare_impl(slg_index *ix, uint32_t nq, const uint32_t *q_offsets, const uint32_t *q_term_ids,
                         const float *q_weights, const slg_score_plans *plans, const int32_t *q_filter,
                         const slg_sort_spec *sort, uint32_t k, int strategy, bool after = false,
-                        const slg_sort_cursor *q_cursor = nullptr, bool hybrid = false) {
+                        const slg_sort_cursor *q_cursor = nullptr, bool hybrid = false,
+                        const slg_agg_spec *aggs = nullptr, bool want_aggs = false) {
   slg_batch *b = nullptr;
   int rc = guarded([&] {
+    if (want_aggs) agg_check_spec(aggs);  // (what needs no index comes first, as every argument check)
     SLG_REQUIRE(ix != nullptr, "index is NULL");
     SLG_REQUIRE(!after || q_cursor != nullptr, "q_cursor is NULL");
     if (sort) {  // (checked before planning: the planner never sees a sort spec it cannot run)
@@ -205,7 +207,7 @@ slg_batch *prepare_impl(slg_index *ix, uint32_t nq, const uint32_t *q_offsets, c
     in.strategy = strategy;
     in.filter_live = filter_live.data();
     in.n_filters = filter_live.size();
-    in.sorted = sort != nullptr || after || hybrid;
+    in.sorted = sort != nullptr || after || hybrid || aggs != nullptr;
     // the columns of the sort parts in the batch's state: every part names a field with a column for every
     // segment (a field registered before slg_index_add_segment has none for the new one)
     std::vector<slg::SortColDev> sort_cols;
@@ -336,7 +338,7 @@ slg_batch *prepare_impl(slg_index *ix, uint32_t nq, const uint32_t *q_offsets, c
       SLG_HIP(hipMemcpy(b->d_sort_cols.p, sort_cols.data(), sort_cols.size() * sizeof(slg::SortColDev),
                         hipMemcpyHostToDevice));
     }
-    if (b->sorted || b->after) b->d_matched.alloc_pooled(&ix->pool, (size_t)std::max<uint32_t>(nq, 1) * 8);
+    if (b->sorted || b->after || aggs) b->d_matched.alloc_pooled(&ix->pool, (size_t)std::max<uint32_t>(nq, 1) * 8);
     if (b->after) {
       b->d_cursor.alloc_pooled(&ix->pool, cursor_words.size() * 4);
       SLG_HIP(hipMemcpy(b->d_cursor.p, cursor_words.data(), cursor_words.size() * 4, hipMemcpyHostToDevice));
@@ -364,6 +366,7 @@ slg_batch *prepare_impl(slg_index *ix, uint32_t nq, const uint32_t *q_offsets, c
     b->d_out_seg = R.seg(b->d_out.as<uint32_t>());
     b->d_out_score = R.score(b->d_out.as<uint32_t>());
     b->d_out_count = R.count(b->d_out.as<uint32_t>());
+    if (aggs) agg_attach(b, *aggs);
     {
       std::lock_guard<std::mutex> lk(ix->mu);
       ix->live.push_back(b);
@@ -384,6 +387,14 @@ slg_batch *slghost::prepare_hybrid_batch(slg_index *ix, uint32_t nq, const uint3
                                          int strategy) {
   return prepare_impl(ix, nq, q_offsets, q_term_ids, q_weights, plans, q_filter, nullptr, k, strategy, false, nullptr,
                       true);
+}
+
+slg_batch *slghost::prepare_agg_batch(slg_index *ix, uint32_t nq, const uint32_t *q_offsets,
+                                      const uint32_t *q_term_ids, const float *q_weights,
+                                      const slg_score_plans *plans, const int32_t *q_filter, const slg_sort_spec *sort,
+                                      const slg_agg_spec *aggs, uint32_t k, int strategy) {
+  return prepare_impl(ix, nq, q_offsets, q_term_ids, q_weights, plans, q_filter, sort, k, strategy, false, nullptr,
+                      false, aggs, true);
 }
 
 extern "C" {
@@ -532,6 +543,7 @@ int slg_batch_run(slg_batch *b) {
     } else {
       SLG_HIP(hipMemsetAsync(b->d_out_count, 0, ((size_t)b->nq + 1) * 4, st));  // (k = 0: nothing was scored)
     }
+    if (b->aggs) agg_launch(b, st);  // (after the select: the tables of every accepted candidate)
   });
 }
 
@@ -724,11 +736,13 @@ int flatten_queries(slg_index *ix, const slg_query *queries, uint32_t nq, FlatQu
 // A prepared batch (null: prepare failed and set the thread's error) run to the caller's host arrays, with
 // the matched counts and seen flags the caller asks for, and destroyed: the first error is the one reported
 int run_to_host(slg_batch *b, uint32_t *out_doc, uint32_t *out_seg, float *out_score, uint32_t *out_count,
-                slg_stats *stats, uint64_t *out_matched, uint8_t *out_seen) {
+                slg_stats *stats, uint64_t *out_matched, uint8_t *out_seen, uint64_t *agg_counts = nullptr,
+                slg_agg_stats *agg_stats = nullptr) {
   if (!b) return last_error().code;
   int rc = slg_batch_run(b);
   if (rc == SLG_OK) rc = slg_batch_fetch(b, out_doc, out_seg, out_score, out_count, stats);
   if (rc == SLG_OK && out_matched) rc = slg_batch_matched_counts(b, out_matched);
+  if (rc == SLG_OK && b->aggs) rc = slg_batch_fetch_aggs(b, agg_counts, agg_stats);
   if (rc == SLG_OK && out_seen) rc = slg_batch_cursor_seen(b, out_seen);
   KeepLastError keep;
   slg_batch_destroy(b);
@@ -761,7 +775,8 @@ int slg_batch_matched_counts(slg_batch *b, uint64_t *out_matched) {
   return guarded([&] {
     SLG_REQUIRE_LIVE(b);
     if (b->hybrid) throw SlgError(SLG_ERR_UNSUPPORTED, "a hybrid batch has no matched counts");
-    SLG_REQUIRE(b->sorted || b->after, "not a sorted or cursor batch (slg_batch_prepare_sorted / _after)");
+    SLG_REQUIRE(b->sorted || b->after || b->aggs,
+                "not a sorted, cursor or aggregation batch (slg_batch_prepare_sorted / _after / _aggs)");
     SLG_REQUIRE(b->launched, "the batch has not run");
     SLG_REQUIRE(b->nq == 0 || out_matched != nullptr, "out_matched is NULL");
     DeviceGuard g(b->idx->device);
@@ -780,6 +795,24 @@ int slg_search_batch_sorted(slg_index *ix, const slg_query *queries, uint32_t nq
   return run_to_host(slg_batch_prepare_sorted(ix, nq, fq.offs.data(), fq.tids.data(), fq.ws.data(), plans, q_filter,
                                               sort, k, strategy),
                      out_doc, out_seg, out_score, out_count, nullptr, out_matched, nullptr);
+}
+
+slg_batch *slg_batch_prepare_aggs(slg_index *ix, uint32_t nq, const uint32_t *q_offsets, const uint32_t *q_term_ids,
+                                  const float *q_weights, const slg_score_plans *plans, const int32_t *q_filter,
+                                  const slg_sort_spec *sort, const slg_agg_spec *aggs, uint32_t k, int strategy) {
+  return prepare_agg_batch(ix, nq, q_offsets, q_term_ids, q_weights, plans, q_filter, sort, aggs, k, strategy);
+}
+
+int slg_search_batch_aggs(slg_index *ix, const slg_query *queries, uint32_t nq, const slg_score_plans *plans,
+                          const int32_t *q_filter, const slg_sort_spec *sort, const slg_agg_spec *aggs, uint32_t k,
+                          int strategy, uint32_t *out_doc, uint32_t *out_seg, float *out_score, uint32_t *out_count,
+                          uint64_t *out_matched, uint64_t *counts, slg_agg_stats *stats) {
+  FlatQueries fq;
+  const int rc = flatten_queries(ix, queries, nq, &fq);
+  if (rc != SLG_OK) return rc;
+  return run_to_host(slg_batch_prepare_aggs(ix, nq, fq.offs.data(), fq.tids.data(), fq.ws.data(), plans, q_filter,
+                                            sort, aggs, k, strategy),
+                     out_doc, out_seg, out_score, out_count, nullptr, out_matched, nullptr, counts, stats);
 }
 
 int slg_batch_cursor_seen(slg_batch *b, uint8_t *out_seen) {

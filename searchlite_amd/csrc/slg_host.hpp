@@ -343,6 +343,20 @@ struct SortFieldData {
   std::vector<std::shared_ptr<SortColumn>> per_seg;
 };
 
+// a registered aggregation column (slg_index_add_agg_field_*): per segment the CSR on the device; null = the
+// field predates the segment (slg_index_add_segment).  Registration scans the values once: the finite
+// minimum and maximum (a histogram's dense id range follows from them) and whether a non-finite one exists
+struct AggColumn {
+  DevBuf offs, vals;   // offs empty: every doc of the segment has exactly one value (vals[doc])
+};
+struct AggFieldData {
+  int kind = 0;  // 1 numeric (f64 values), 2 keyword (u32 ordinals)
+  uint32_t n_ords = 0;
+  bool any_value = false, non_finite = false;
+  double vmin = 0.0, vmax = 0.0;  // over the finite values, when any_value
+  std::vector<std::shared_ptr<AggColumn>> per_seg;
+};
+
 // One immutable state of the index (see "index updates" in searchlite_gpu.h).  Batches hold the state
 // they were prepared on; the index holds the current one.
 struct IndexState {
@@ -358,6 +372,7 @@ struct IndexState {
   std::vector<const uint32_t *> reject_host;           // flattened [filter * n_segs + seg] device pointers
   DevBuf d_reject_table;                               // the same table on the device
   std::map<int, std::shared_ptr<SortFieldData>> sort_fields;  // by id (ids are not reused)
+  std::map<int, std::shared_ptr<AggFieldData>> agg_fields;    // by id (ids are not reused)
   ~IndexState() {
     // kernels of already-destroyed batches, or rerank calls on the index stream, may still read the
     // tables: retiring a state is rare (one per update), so wait for the device once
@@ -392,6 +407,7 @@ struct slg_index {
   std::mutex mu;
   std::mutex update_mu;  // serialises slg_index_update_* / add_filter / add_vector_field (taken before mu)
   int next_sort_field = 0;  // (under update_mu) sort field ids are never handed out again
+  int next_agg_field = 0;   // (under update_mu) the same for aggregation fields
   // profiling of the scoring kernel
   bool profile = false;
   std::vector<std::pair<hipEvent_t, hipEvent_t>> prof_events;
@@ -467,6 +483,15 @@ struct slg_batch {
   std::vector<uint64_t> q_cand;  // [nq + 1] first candidate slot of each query
   DevBuf d_q_cand;               // the same on the device
   DevBuf d_hy_keys, d_hy_work;   // the gathered keys of a range of queries; clause lists, counts, sort space
+  // aggregation batch (slg_batch_prepare_aggs): planned as a sorted batch, run in score order or under its
+  // sort spec; agg_kernel then fills the tables from the candidates (slg_aggs.hip)
+  bool aggs = false;
+  slg_agg_spec agg_spec{};
+  std::vector<slg_agg_layout> agg_layout;  // [n_nodes]
+  uint32_t agg_count_cells = 0, agg_stats_cells = 0;
+  bool agg_lds = false;              // the tables fit SLG_AGG_LDS_BYTES
+  DevBuf d_agg_desc;                 // slg::AggNodeDev[n_nodes], then slg::AggColDev[n_nodes * n_segs]
+  DevBuf d_agg_counts, d_agg_stats;  // u32[nq * count_cells], slg::AggStatDev[nq * stats_cells]
 };
 
 namespace slghost __attribute__((visibility("hidden"))) {
@@ -565,6 +590,17 @@ void launch_shard_merge(const slg::ShardMergeParams &mp, hipStream_t st);
 slg_batch *prepare_hybrid_batch(slg_index *ix, uint32_t nq, const uint32_t *q_offsets, const uint32_t *q_term_ids,
                                 const float *q_weights, const slg_score_plans *plans, const int32_t *q_filter,
                                 uint32_t k, int strategy);
+
+// slg_batch.hip: slg_batch_prepare_aggs (the planning of slg_batch_prepare_plans / _sorted with BatchIn::sorted)
+slg_batch *prepare_agg_batch(slg_index *ix, uint32_t nq, const uint32_t *q_offsets, const uint32_t *q_term_ids,
+                             const float *q_weights, const slg_score_plans *plans, const int32_t *q_filter,
+                             const slg_sort_spec *sort, const slg_agg_spec *aggs, uint32_t k, int strategy);
+// slg_aggs.hip: the checks of a spec that need no index (throws); the spec against the batch's state, the
+// tables' layout and the device buffers (throws; the batch is otherwise prepared); the launch behind the
+// batch's select kernel
+void agg_check_spec(const slg_agg_spec *aggs);
+void agg_attach(slg_batch *b, const slg_agg_spec &aggs);
+void agg_launch(slg_batch *b, hipStream_t st);
 
 // slg_vsearch.hip: one vector search or hybrid call, checked against one state of the index ...
 struct VsCall {

@@ -300,6 +300,7 @@ std::unique_ptr<IndexState> copy_state(const IndexState &cur) {
   n->segs = cur.segs;
   n->filters = cur.filters;
   n->sort_fields = cur.sort_fields;
+  n->agg_fields = cur.agg_fields;
   for (auto &vf : cur.vfields) {  // the per-state table d_vsegs is rebuilt: own object, shared stores
     auto c = std::make_shared<VecFieldHost>();
     c->dim = vf->dim;
@@ -353,6 +354,11 @@ void reshape_per_segment(IndexState &ns, Op op) {
     op(nf->per_seg);
     sf.second = std::move(nf);
   }
+  for (auto &af : ns.agg_fields) {
+    auto nf = std::make_shared<AggFieldData>(*af.second);
+    op(nf->per_seg);
+    af.second = std::move(nf);
+  }
   for (auto &vf : ns.vfields) op(vf->per_seg);  // (the field objects of a new state are fresh copies)
 }
 
@@ -366,6 +372,9 @@ size_t state_device_bytes(const IndexState &s) {
   for (auto &sf : s.sort_fields)
     for (auto &c : sf.second->per_seg)
       if (c) n += c->key[0].bytes + c->key[1].bytes + c->present.bytes;
+  for (auto &af : s.agg_fields)
+    for (auto &c : af.second->per_seg)
+      if (c) n += c->offs.bytes + c->vals.bytes;
   for (auto &vf : s.vfields) {
     n += vf->d_vsegs.bytes;
     for (auto &v : vf->per_seg)
@@ -736,6 +745,102 @@ int slg_index_remove_sort_field(slg_index *ix, int sort_field_id) {
     update_state(ix, false, [&](const IndexState &cur, IndexState &ns) {
       SLG_REQUIRE(cur.sort_fields.count(sort_field_id) == 1, "unknown sort field id");
       ns.sort_fields.erase(sort_field_id);
+    });
+  });
+}
+
+// ---- aggregation fields (query/aggs/mod.rs; index/fastfields.rs:711-800) -----------------------
+namespace {
+// kind: 1 f64 values, 2 i64 values (converted `as f64` here, as the reference does), 3 u32 ordinals
+int add_agg_field_impl(slg_index *ix, int kind, const uint32_t *const *seg_offsets, const void *const *seg_values,
+                       uint32_t n_ords) {
+  int id = -1;
+  const int rc = guarded([&] {
+    SLG_REQUIRE(ix != nullptr, "index is NULL");
+    SLG_REQUIRE(seg_offsets != nullptr, "seg_offsets is NULL");
+    update_state(ix, false, [&](const IndexState &cur, IndexState &ns) {
+      const size_t n_segs = cur.segs.size();
+      auto fd = std::make_shared<AggFieldData>();
+      fd->kind = kind == 3 ? 2 : 1;
+      fd->n_ords = n_ords;
+      fd->per_seg.resize(n_segs);
+      for (size_t s = 0; s < n_segs; s++) {
+        const uint32_t n_docs = cur.segs[s]->n_docs;
+        const uint32_t *offs = seg_offsets[s];
+        SLG_REQUIRE(offs == nullptr || seg_values != nullptr, "seg_values is NULL");
+        bool dense = offs != nullptr && n_docs > 0;
+        if (offs) {
+          for (uint32_t d = 0; d < n_docs; d++) {
+            SLG_REQUIRE(offs[d + 1] >= offs[d], "agg field offsets of a segment are not monotone");
+            dense = dense && offs[d] == offs[0] + d;
+          }
+          dense = dense && offs[n_docs] == offs[0] + n_docs;
+          SLG_REQUIRE(offs[n_docs] == offs[0] || seg_values[s] != nullptr, "agg field values of a segment are NULL");
+        }
+        const uint32_t first = offs ? offs[0] : 0u;
+        const size_t nv = offs ? (size_t)offs[n_docs] - first : 0;
+        auto col = std::make_shared<AggColumn>();
+        if (kind == 3) {
+          const uint32_t *v = nv ? static_cast<const uint32_t *>(seg_values[s]) + first : nullptr;
+          for (size_t i = 0; i < nv; i++) SLG_REQUIRE(v[i] < n_ords, "keyword ordinal >= n_ords");
+          col->vals.alloc(std::max<size_t>(nv, 1) * 4, &ix->pool);
+          if (nv) SLG_HIP(hipMemcpy(col->vals.p, v, nv * 4, hipMemcpyHostToDevice));
+        } else {
+          std::vector<double> conv;
+          const double *v = nullptr;
+          if (nv && kind == 2) {  // fastfields.rs:772-800: i64 values reach the collectors `as f64`
+            const int64_t *iv = static_cast<const int64_t *>(seg_values[s]) + first;
+            conv.resize(nv);
+            for (size_t i = 0; i < nv; i++) conv[i] = (double)iv[i];
+            v = conv.data();
+          } else if (nv) {
+            v = static_cast<const double *>(seg_values[s]) + first;
+          }
+          for (size_t i = 0; i < nv; i++) {
+            if (!std::isfinite(v[i])) {
+              fd->non_finite = true;
+              continue;
+            }
+            fd->vmin = fd->any_value ? std::min(fd->vmin, v[i]) : v[i];
+            fd->vmax = fd->any_value ? std::max(fd->vmax, v[i]) : v[i];
+            fd->any_value = true;
+          }
+          col->vals.alloc(std::max<size_t>(nv, 1) * 8, &ix->pool);
+          if (nv) SLG_HIP(hipMemcpy(col->vals.p, v, nv * 8, hipMemcpyHostToDevice));
+        }
+        if (!dense) {  // the offsets, rebased to the copied values (NULL: no doc has a value)
+          std::vector<uint32_t> o((size_t)n_docs + 1, 0u);
+          if (offs)
+            for (uint32_t d = 0; d <= n_docs; d++) o[d] = offs[d] - first;
+          col->offs.alloc(o.size() * 4, &ix->pool);
+          SLG_HIP(hipMemcpy(col->offs.p, o.data(), o.size() * 4, hipMemcpyHostToDevice));
+        }
+        fd->per_seg[s] = std::move(col);
+      }
+      id = ix->next_agg_field++;
+      ns.agg_fields.emplace(id, std::move(fd));
+    });
+  });
+  return rc == SLG_OK ? id : rc;
+}
+}  // namespace
+
+int slg_index_add_agg_field_f64(slg_index *ix, const uint32_t *const *seg_offsets, const double *const *seg_values) {
+  return add_agg_field_impl(ix, 1, seg_offsets, reinterpret_cast<const void *const *>(seg_values), 0);
+}
+int slg_index_add_agg_field_i64(slg_index *ix, const uint32_t *const *seg_offsets, const int64_t *const *seg_values) {
+  return add_agg_field_impl(ix, 2, seg_offsets, reinterpret_cast<const void *const *>(seg_values), 0);
+}
+int slg_index_add_agg_field_ord(slg_index *ix, const uint32_t *const *seg_offsets, const uint32_t *const *seg_ords,
+                                uint32_t n_ords) {
+  return add_agg_field_impl(ix, 3, seg_offsets, reinterpret_cast<const void *const *>(seg_ords), n_ords);
+}
+int slg_index_remove_agg_field(slg_index *ix, int agg_field_id) {
+  return guarded([&] {
+    SLG_REQUIRE(ix != nullptr, "index is NULL");
+    update_state(ix, false, [&](const IndexState &cur, IndexState &ns) {
+      SLG_REQUIRE(cur.agg_fields.count(agg_field_id) == 1, "unknown agg field id");
+      ns.agg_fields.erase(agg_field_id);
     });
   });
 }

@@ -248,6 +248,73 @@ class GpuIndex:
     def remove_sort_field(self, sort_field_id: int) -> None:
         N.check(self._lib.slg_index_remove_sort_field(self._h, sort_field_id))
 
+    # -- aggregation fields (query/aggs/mod.rs; lifecycle and ids as sort fields) ----------------
+    def _csr_ptrs(self, per_segment, dt, keep):
+        """per_segment[s]: a list of n_docs arrays, a CSR pair (offsets[n_docs + 1], values) or None ->
+        the two pointer arrays of slg_index_add_*_field_*."""
+        assert len(per_segment) == self.n_segs
+        offs_p, vals_p = [], []
+        for s, v in enumerate(per_segment):
+            if v is None:
+                offs_p.append(None)
+                vals_p.append(None)
+                continue
+            if isinstance(v, tuple):
+                offs = np.ascontiguousarray(v[0], dtype=np.uint32)
+                vals = np.ascontiguousarray(v[1], dtype=dt)
+            else:
+                offs = np.zeros(len(v) + 1, dtype=np.uint32)
+                offs[1:] = np.cumsum(np.array([len(x) for x in v], dtype=np.uint64))
+                vals = np.ascontiguousarray(np.concatenate([np.asarray(x, dtype=dt) for x in v]) if len(v) else
+                                            np.zeros(0, dt), dtype=dt)
+            assert len(offs) == int(self.segments[s].n_docs) + 1, "one offset per doc + 1"
+            if vals.size == 0:
+                vals = np.zeros(1, dt)
+            keep += [offs, vals]
+            offs_p.append(offs.ctypes.data)
+            vals_p.append(vals.ctypes.data)
+        return (C.c_void_p * self.n_segs)(*offs_p), (C.c_void_p * self.n_segs)(*vals_p)
+
+    def add_agg_field(self, per_segment, dtype) -> int:
+        """Register a numeric column for aggregations (slg_index_add_agg_field_i64 / _f64); per_segment as
+        add_sort_field.  Returns the agg field id (ids are never reused)."""
+        dt = np.dtype(dtype)
+        if dt not in (np.dtype(np.int64), np.dtype(np.float64)):
+            raise TypeError("numeric agg fields are int64 or float64")
+        keep: list = []
+        po, pv = self._csr_ptrs(per_segment, dt, keep)
+        fn = self._lib.slg_index_add_agg_field_i64 if dt == np.int64 else self._lib.slg_index_add_agg_field_f64
+        rc = fn(self._h, po, pv)
+        if rc < 0:
+            N.check(rc)
+        return rc
+
+    def add_agg_keyword_field(self, per_segment_ords, n_ords: int) -> int:
+        """Register a keyword column (slg_index_add_agg_field_ord): per segment the docs' ordinals into ONE
+        dictionary of n_ords keys, the caller's."""
+        keep: list = []
+        po, pv = self._csr_ptrs(per_segment_ords, np.dtype(np.uint32), keep)
+        rc = self._lib.slg_index_add_agg_field_ord(self._h, po, pv, int(n_ords))
+        if rc < 0:
+            N.check(rc)
+        return rc
+
+    def remove_agg_field(self, agg_field_id: int) -> None:
+        N.check(self._lib.slg_index_remove_agg_field(self._h, agg_field_id))
+
+    def search_aggs(self, q_offsets, q_terms, q_weights, k: int, aggs, sort=None, strategy: int = Wand,
+                    q_filter=None, **plans):
+        """Batch search with aggregations (slg_batch_prepare_aggs).  aggs: an N.AggSpec or an aggs.AggPlan;
+        sort: None = score order, else as search_sorted.
+        -> (doc, seg, score, count, matched, tables, layout): tables[i] [nq, parent_rows, rows] of node i
+        (PreparedBatch.aggs), layout as PreparedBatch.agg_layout."""
+        b = self.prepare(q_offsets, q_terms, q_weights, k, strategy, q_filter, sort=sort, aggs=aggs, **plans)
+        try:
+            b.run()
+            return b.fetch() + (b.matched_counts(), b.aggs(), b.agg_layout())
+        finally:
+            b.close()
+
     def search_sorted(self, q_offsets, q_terms, q_weights, k: int, sort, strategy: int = Wand, q_filter=None,
                       **plans):
         """Field-sorted batch search (slg_batch_prepare_sorted).  sort: [(field, order)], field = a sort field id
@@ -279,18 +346,19 @@ class GpuIndex:
                 q_filter=None, q_leaf=None, q_plan=None, q_tie=None, q_nleaves=None,
                 q_leaf_offsets=None, leaf_group=None, q_group_offsets=None, group_plan=None,
                 group_tie=None, q_node_offsets=None, node_kind=None, node_tie=None, node_parent=None,
-                q_min_match=None, sort=None, cursors=None, hybrid=False) -> "PreparedBatch":
+                q_min_match=None, sort=None, cursors=None, hybrid=False, aggs=None) -> "PreparedBatch":
         """q_leaf / q_plan / q_tie / q_nleaves: score plans; leaf_group / group_plan / group_tie with
         their per-query offsets: two-level plans; q_node_offsets / node_kind / node_tie / node_parent:
         trees of any shape, node by node in pre-order (slg_batch_prepare_plans, slg_score_plans);
         q_min_match: minimum_should_match per query (leaves that must hold a doc); sort: a field sort
         (search_sorted) -> slg_batch_prepare_sorted; cursors: a cursor per query (search_after) ->
         slg_batch_prepare_after; hybrid: the text side of a hybrid text + vector search ->
-        slg_batch_prepare_hybrid (PreparedBatch.hybrid_device)."""
+        slg_batch_prepare_hybrid (PreparedBatch.hybrid_device); aggs: an N.AggSpec or aggs.AggPlan ->
+        slg_batch_prepare_aggs (PreparedBatch.aggs)."""
         return PreparedBatch(self, q_offsets, q_terms, q_weights, k, strategy, q_filter,
                              q_leaf, q_plan, q_tie, q_nleaves, q_leaf_offsets, leaf_group,
                              q_group_offsets, group_plan, group_tie, q_node_offsets, node_kind, node_tie, node_parent,
-                             q_min_match, sort, cursors, hybrid)
+                             q_min_match, sort, cursors, hybrid, aggs)
 
     def search_plan(self, q_offsets, q_terms, q_weights, k: int, q_leaf=None, q_plan=None,
                     q_tie=None, q_nleaves=None, strategy: int = Wand, q_filter=None, **tree):
@@ -618,7 +686,7 @@ class PreparedBatch:
                  q_filter=None, q_leaf=None, q_plan=None, q_tie=None, q_nleaves=None,
                  q_leaf_offsets=None, leaf_group=None, q_group_offsets=None, group_plan=None,
                  group_tie=None, q_node_offsets=None, node_kind=None, node_tie=None, node_parent=None,
-                 q_min_match=None, sort=None, cursors=None, hybrid=False):
+                 q_min_match=None, sort=None, cursors=None, hybrid=False, aggs=None):
         self.index = index
         self._lib = index._lib
         q_offsets = np.ascontiguousarray(q_offsets, dtype=np.uint32)
@@ -650,7 +718,17 @@ class PreparedBatch:
         self.after = cursors is not None
         self.is_hybrid = bool(hybrid)
         assert not (hybrid and (sort is not None or cursors is not None)), "a hybrid batch takes no sort or cursor"
-        if hybrid:
+        self.agg_spec = getattr(aggs, "spec", aggs)  # (an aggs.AggPlan carries its N.AggSpec)
+        if aggs is not None:
+            # (cursor and hybrid batches take no aggregations: the library's prepare calls for them have no
+            #  spec argument, so the refusal is made here with the library's code)
+            if hybrid or cursors is not None:
+                raise N.SlgError(N.ERR_UNSUPPORTED, "aggregations are not built on cursor or hybrid batches")
+            spec = None if sort is None else sort_spec(sort)
+            self._h = self._lib.slg_batch_prepare_aggs(
+                index._h, self.nq, _ptr(q_offsets), _ptr(q_terms), _ptr(q_weights), C.addressof(plans),
+                opt(qf), None if spec is None else C.addressof(spec), C.addressof(self.agg_spec), k, strategy)
+        elif hybrid:
             self._h = self._lib.slg_batch_prepare_hybrid(
                 index._h, self.nq, _ptr(q_offsets), _ptr(q_terms), _ptr(q_weights), C.addressof(plans),
                 opt(qf), k, strategy)
@@ -693,6 +771,33 @@ class PreparedBatch:
         out = np.zeros(max(self.nq, 1), dtype=np.uint64)
         N.check(self._lib.slg_batch_matched_counts(self._h, _ptr(out)))
         return out[:self.nq]
+
+    def agg_layout(self) -> list:
+        """slg_batch_agg_layout: per node dict(parent_rows, rows, first_id, is_stats, offset)."""
+        n = int(self.agg_spec.n_nodes)
+        lay = (N.AggLayout * n)()
+        N.check(self._lib.slg_batch_agg_layout(self._h, lay))
+        return [dict(parent_rows=int(x.parent_rows), rows=int(x.rows), first_id=int(x.first_id),
+                     is_stats=bool(x.is_stats), offset=int(x.offset)) for x in lay]
+
+    def aggs(self) -> list:
+        """The tables of the last run (slg_batch_fetch_aggs; waits): per node an array [nq, parent_rows, rows],
+        uint64 counts for a bucket node, aggs.STATS_DTYPE records (count, min, max, sum) for a stats node."""
+        from .aggs import STATS_DTYPE
+        lay = self.agg_layout()
+        cc = sum(x["parent_rows"] * x["rows"] for x in lay if not x["is_stats"])
+        sc = sum(x["parent_rows"] * x["rows"] for x in lay if x["is_stats"])
+        counts = np.zeros((max(self.nq, 1), max(cc, 1)), dtype=np.uint64)
+        stats = np.zeros((max(self.nq, 1), max(sc, 1)), dtype=STATS_DTYPE)
+        N.check(self._lib.slg_batch_fetch_aggs(self._h, _ptr(counts.reshape(-1)[:self.nq * cc]) if cc else None,
+                                               _ptr(stats.reshape(-1)[:self.nq * sc]) if sc else None))
+        out = []
+        for x in lay:
+            src, cells = (stats, sc) if x["is_stats"] else (counts, cc)
+            flat = src.reshape(-1)[:self.nq * cells].reshape(self.nq, cells)
+            n = x["parent_rows"] * x["rows"]
+            out.append(flat[:, x["offset"]:x["offset"] + n].reshape(self.nq, x["parent_rows"], x["rows"]).copy())
+        return out
 
     def cursor_seen(self) -> np.ndarray:
         """Per query of a cursor batch's last run: 1 if an accepted doc had the cursor's key (or the query has

@@ -25,7 +25,9 @@
  * on the CPU.  A cursor (the next page, slg_batch_prepare_after) in score order or in a device-eligible field
  * sort; not in sharded runs or the coalescer.  Aggregations (slg_batch_prepare_aggs): terms, histogram, range and
  * stats over registered columns, two levels, in score order or a field sort; not with a cursor, not on hybrid,
- * vector-only, sharded or coalesced batches.
+ * vector-only, sharded or coalesced batches.  Query rescore (slg_batch_prepare_rescore): a second BM25 query with
+ * a flat Sum / DisMax plan over a window of up to SLG_MAX_RESCORE_WINDOW first-pass rows, every score_mode; in
+ * score order only, not on sorted, cursor, hybrid, vector-only, aggregation, sharded or coalesced batches.
  */
 #ifndef SEARCHLITE_GPU_H
 #define SEARCHLITE_GPU_H
@@ -950,6 +952,78 @@ int slg_search_batch_hybrid(slg_index *index, uint32_t nq, const uint32_t *q_off
                             const float *boost, uint32_t cand_size, uint32_t k_out, uint32_t *out_doc,
                             uint32_t *out_seg, float *out_score, float *out_vec_score, uint32_t *out_count,
                             uint64_t *out_total);
+
+/*
+ * Query rescore: SearchRequest::rescore { window_size, query, score_mode } (api/types.rs:523-545), carried out by
+ * rescore_hits (api/reader.rs:3238-3398) and combine_rescore_scores (:3623-3629).  Per query, after the first
+ * pass has left its rows (count <= k, by score desc, segment asc, doc asc):
+ *   1. w = min(q_window[q], count).  w == 0, or a rescore query without a term: the rows stay as they are.
+ *   2. A row (segment s, doc d, score o) of the first w is MATCHED if at least max(q_min_match[q], 1) leaves of
+ *      the rescore query have a term whose list in segment s holds d.  A row that is not matched keeps its
+ *      score untouched: it is neither multiplied by 0 nor removed (:3319-3321).
+ *   3. For a matched row every rescore term t whose list in segment s holds d adds impact * weight_t to its
+ *      leaf (impact = the BM25 score of the posting at weight 1, score_tf's base; one f32 product, one f32
+ *      add, never fused), the terms of a leaf IN QUERY-TERM ORDER; the leaves are combined as the first pass
+ *      combines a flat plan (slg_batch_prepare_plan): SLG_PLAN_SUM, or SLG_PLAN_DISMAX with a tie breaker in
+ *      [0, 1], leaves in leaf order, a DisMax leaf without a posting counting as 0.0.  That is the rescore
+ *      score r.  (The reference accumulates a row's term scores by walking a HashMap, :3290-3300, so its own
+ *      summation order is not defined; this library fixes it, as its first pass does.)
+ *   4. new score = o + r (SLG_RESCORE_TOTAL, _SUM), o * r (_MULTIPLY), max(o, r) (_MAX), min(o, r) (_MIN; max
+ *      and min as f32::max / f32::min: a NaN operand yields the other one): plain f32 operations.
+ *   5. The first w rows are sorted again by (score desc under f32::total_cmp, segment asc, doc asc).  Rows
+ *      from w on keep their place and score, also where a window row now scores below them: the reference
+ *      sorts hits[..window] only (:3393-3396).  out_count does not change.
+ * The rescore applies no tombstone or filter test of its own: first-pass rows are live and filtered.
+ *
+ * The rescore queries come in the CSR form of the first pass (q_offsets [nq + 1], q_term_ids [total x n_segs],
+ * q_weights [total]) with the flat plan arrays of slg_batch_prepare_plan (each may be NULL, same defaults),
+ * q_min_match [nq] or NULL, q_window [nq], and q_mode [nq] or NULL (total).  Rescore queries whose score tree
+ * has more than one level of Sum / DisMax over the leaves, function scores and phrases are not accepted by
+ * this form: the caller keeps such requests on the CPU scorer.
+ *
+ * slg_batch_prepare_rescore is slg_batch_prepare_plans plus the spec; the batch goes through slg_batch_run /
+ * _fetch / _device_results / _set_stream as any batch.  slg_batch_run enqueues the rescore kernel behind the
+ * first pass on the batch's stream, so several batches stay in flight and the rows a caller sees are the
+ * rescored ones; running a batch again scores from scratch.  The rescore terms are resolved against the index
+ * state the batch was prepared on.  slg_batch_fetch_rescore waits for the batch and copies [nq * k] arrays
+ * parallel to the rows (each may be NULL): the first-pass score, r (0.0 where the row was not rescored), and
+ * 1 where the row was rescored.  slg_search_batch_rescore is the one-call form with host arrays.
+ *
+ * Before any device work: a NULL spec, inconsistent offsets, a mode or plan out of range, a tie outside [0, 1]
+ * or not finite, a weight that is not finite, a term id out of range, or more than SLG_MAX_QUERY_TERMS rescore
+ * terms in a query: SLG_ERR_INVALID.  A window that, capped at k (a window never reaches past the k rows), is
+ * above SLG_MAX_RESCORE_WINDOW (= SLG_MAX_RERANK_K, the widest register top-k the library has), or a rescore
+ * query whose terms x segments exceed 2048 table entries: SLG_ERR_UNSUPPORTED (CPU scorer).  slg_batch_fetch_rescore on a batch without rescore, or one that has not
+ * run: SLG_ERR_INVALID.  slg_batch_run_sharded* and slg_batch_fetch_sharded refuse a rescore batch with
+ * SLG_ERR_UNSUPPORTED.  Not built: rescore on sorted, cursor, hybrid, vector-only and aggregation batches,
+ * and in the coalescer (none of their prepare calls takes a rescore spec).
+ */
+enum { SLG_RESCORE_TOTAL = 0, SLG_RESCORE_MULTIPLY = 1, SLG_RESCORE_SUM = 2, SLG_RESCORE_MAX = 3, SLG_RESCORE_MIN = 4 };
+#define SLG_MAX_RESCORE_WINDOW 1024u
+typedef struct slg_rescore_spec {
+  const uint32_t *q_offsets;   /* [nq + 1] rescore terms of every query */
+  const uint32_t *q_term_ids;  /* [total x n_segs] per-segment term ids, SLG_NO_TERM where absent */
+  const float *q_weights;      /* [total] */
+  const uint32_t *q_leaf;      /* [total] leaf of every rescore term; NULL: term i of a query is leaf i */
+  const int32_t *q_plan;       /* [nq] SLG_PLAN_SUM | SLG_PLAN_DISMAX over the leaves; NULL: Sum */
+  const float *q_tie;          /* [nq] DisMax tie breaker in [0, 1]; NULL: 0 */
+  const uint32_t *q_nleaves;   /* [nq] leaves of the plan; NULL: 1 + the largest leaf named */
+  const uint32_t *q_min_match; /* [nq] leaves that must hold a row's doc; NULL, 0 and 1: any */
+  const uint32_t *q_window;    /* [nq] window_size; min(window, k) <= SLG_MAX_RESCORE_WINDOW */
+  const int32_t *q_mode;       /* [nq] SLG_RESCORE_*; NULL: total */
+} slg_rescore_spec;
+slg_batch *slg_batch_prepare_rescore(slg_index *index, uint32_t nq, const uint32_t *q_offsets,
+                                     const uint32_t *q_term_ids, const float *q_weights,
+                                     const slg_score_plans *plans_or_null, const int32_t *q_filter_or_null,
+                                     const slg_rescore_spec *rescore, uint32_t k, int strategy);
+int slg_batch_fetch_rescore(slg_batch *batch, float *out_first_score, float *out_rescore_score,
+                            uint32_t *out_rescored);
+int slg_search_batch_rescore(slg_index *index, uint32_t nq, const uint32_t *q_offsets, const uint32_t *q_term_ids,
+                             const float *q_weights, const slg_score_plans *plans_or_null,
+                             const int32_t *q_filter_or_null, const slg_rescore_spec *rescore, uint32_t k,
+                             int strategy, uint32_t *out_doc, uint32_t *out_seg, float *out_score,
+                             uint32_t *out_count, float *out_first_score, float *out_rescore_score,
+                             uint32_t *out_rescored);
 
 #ifdef __cplusplus
 }

@@ -72,6 +72,11 @@ pub const SLG_AGG_STATS: i32 = 3;
     pub parent_rows: u32, pub rows: u32, pub first_id: i64, pub is_stats: u32, pub offset: u64,
 }
 #[repr(C)] #[derive(Clone, Copy, Default)] pub struct slg_agg_stats { pub count: u64, pub min: f64, pub max: f64, pub sum: f64 }
+#[repr(C)] pub struct slg_rescore_spec {
+    pub q_offsets: *const u32, pub q_term_ids: *const u32, pub q_weights: *const c_float, pub q_leaf: *const u32,
+    pub q_plan: *const i32, pub q_tie: *const c_float, pub q_nleaves: *const u32, pub q_min_match: *const u32,
+    pub q_window: *const u32, pub q_mode: *const i32,
+}
 #[repr(C)] pub struct slg_stats { pub scored_docs: u64, pub candidates_examined: u64, pub postings_advanced: u64 }
 #[repr(C)] pub struct slg_query { pub n_terms: u32, pub term_ids: *const u32, pub weights: *const c_float }
 
@@ -267,7 +272,24 @@ extern "C" {
         n_clauses: u32, clause_field: *const u32, qvecs: *const c_float, alpha: *const c_float,
         boost: *const c_float, cand_size: u32, k_out: u32, out_doc: *mut u32, out_seg: *mut u32,
         out_score: *mut c_float, out_vec_score: *mut c_float, out_count: *mut u32, out_total: *mut u64) -> c_int;
+    // query rescore (SearchRequest::rescore): slg_batch_prepare_plans plus the spec; the rows are the rescored ones
+    pub fn slg_batch_prepare_rescore(index: *mut slg_index, nq: u32, q_offsets: *const u32, q_term_ids: *const u32,
+        q_weights: *const c_float, plans: *const slg_score_plans, q_filter: *const i32,
+        rescore: *const slg_rescore_spec, k: u32, strategy: c_int) -> *mut slg_batch;
+    pub fn slg_batch_fetch_rescore(batch: *mut slg_batch, out_first_score: *mut c_float,
+        out_rescore_score: *mut c_float, out_rescored: *mut u32) -> c_int;
+    pub fn slg_search_batch_rescore(index: *mut slg_index, nq: u32, q_offsets: *const u32, q_term_ids: *const u32,
+        q_weights: *const c_float, plans: *const slg_score_plans, q_filter: *const i32,
+        rescore: *const slg_rescore_spec, k: u32, strategy: c_int, out_doc: *mut u32, out_seg: *mut u32,
+        out_score: *mut c_float, out_count: *mut u32, out_first_score: *mut c_float,
+        out_rescore_score: *mut c_float, out_rescored: *mut u32) -> c_int;
 }
+pub const SLG_RESCORE_TOTAL: i32 = 0;
+pub const SLG_RESCORE_MULTIPLY: i32 = 1;
+pub const SLG_RESCORE_SUM: i32 = 2;
+pub const SLG_RESCORE_MAX: i32 = 3;
+pub const SLG_RESCORE_MIN: i32 = 4;
+pub const SLG_MAX_RESCORE_WINDOW: u32 = 1024;
 pub const SLG_OWN_STREAM: *mut c_void = usize::MAX as *mut c_void;
 pub const SLG_NO_TERM: u32 = 0xFFFF_FFFF;
 pub const SLG_METRIC_COSINE: i32 = 0;

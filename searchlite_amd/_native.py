@@ -31,6 +31,8 @@ MAX_AGG_RANGES = 16
 MAX_AGG_CELLS = 65536
 AGG_LDS_BYTES = 32768
 AGG_TERMS, AGG_HISTOGRAM, AGG_RANGE, AGG_STATS = 0, 1, 2, 3
+RESCORE_TOTAL, RESCORE_MULTIPLY, RESCORE_SUM, RESCORE_MAX, RESCORE_MIN = 0, 1, 2, 3, 4
+MAX_RESCORE_WINDOW = 1024
 
 
 class SlgError(RuntimeError):
@@ -119,6 +121,13 @@ class AggLayout(C.Structure):
 class AggStats(C.Structure):
     """slg_agg_stats: one stats cell."""
     _fields_ = [("count", C.c_uint64), ("min", C.c_double), ("max", C.c_double), ("sum", C.c_double)]
+
+
+class RescoreSpec(C.Structure):
+    """slg_rescore_spec: the rescore queries (CSR, flat plan arrays), their windows and score modes."""
+    _fields_ = [("q_offsets", C.c_void_p), ("q_term_ids", C.c_void_p), ("q_weights", C.c_void_p),
+                ("q_leaf", C.c_void_p), ("q_plan", C.c_void_p), ("q_tie", C.c_void_p), ("q_nleaves", C.c_void_p),
+                ("q_min_match", C.c_void_p), ("q_window", C.c_void_p), ("q_mode", C.c_void_p)]
 
 
 class Ticket(C.Structure):
@@ -261,6 +270,9 @@ def load():
         "slg_batch_hybrid_device": (i32, [vp, u32, vp, vp, vp, vp, u32, u32, vp, vp, vp, vp, vp, vp]),
         "slg_search_batch_hybrid": (i32, [vp, u32, vp, vp, vp, vp, vp, u32, i32, u32, vp, vp, vp, vp, u32, u32,
                                           vp, vp, vp, vp, vp, vp]),
+        "slg_batch_prepare_rescore": (vp, [vp, u32, vp, vp, vp, vp, vp, vp, u32, i32]),
+        "slg_batch_fetch_rescore": (i32, [vp, vp, vp, vp]),
+        "slg_search_batch_rescore": (i32, [vp, u32, vp, vp, vp, vp, vp, vp, u32, i32, vp, vp, vp, vp, vp, vp, vp]),
     }
     for name, (res, args) in sigs.items():
         if os.environ.get("SLG_LIB_TAG") and not hasattr(L, name):

@@ -124,7 +124,8 @@ void slghost::release_batch_buffers(slg_batch *b, bool to_pool) {
   DevBuf *bufs[] = {&b->d_desc, &b->d_bounds, &b->d_rdoc, &b->d_slice_desc, &b->d_slice_tk, &b->d_slice_doc,
                     &b->d_q_scored, &b->d_q_filter, &b->d_cand, &b->d_slice_cbeg, &b->d_slice_ccnt,
                     &b->d_out, &b->d_stamps, &b->d_blk_skip, &b->d_gather, &b->d_merged, &b->d_q_cand,
-                    &b->d_hy_keys, &b->d_hy_work, &b->d_agg_desc, &b->d_agg_counts, &b->d_agg_stats};
+                    &b->d_hy_keys, &b->d_hy_work, &b->d_agg_desc, &b->d_agg_counts, &b->d_agg_stats,
+                    &b->d_rs_desc, &b->d_rs_side};
   for (DevBuf *d : bufs) {
     if (!to_pool) d->pool = nullptr;
     d->release();
@@ -163,15 +164,17 @@ slg_batch *slg_batch_prepare_plan(slg_index *ix, uint32_t nq, const uint32_t *q_
 
 namespace {
 // slg_batch_prepare_plans, (sort != nullptr) slg_batch_prepare_sorted, (after) slg_batch_prepare_after, and
-// (hybrid) slg_batch_prepare_hybrid, (aggs != nullptr) slg_batch_prepare_aggs
+// (hybrid) slg_batch_prepare_hybrid, (want_aggs) slg_batch_prepare_aggs, (want_rescore) slg_batch_prepare_rescore
 slg_batch *prepare_impl(slg_index *ix, uint32_t nq, const uint32_t *q_offsets, const uint32_t *q_term_ids,
                         const float *q_weights, const slg_score_plans *plans, const int32_t *q_filter,
                         const slg_sort_spec *sort, uint32_t k, int strategy, bool after = false,
                         const slg_sort_cursor *q_cursor = nullptr, bool hybrid = false,
-                        const slg_agg_spec *aggs = nullptr, bool want_aggs = false) {
+                        const slg_agg_spec *aggs = nullptr, bool want_aggs = false,
+                        const slg_rescore_spec *rescore = nullptr, bool want_rescore = false) {
   slg_batch *b = nullptr;
   int rc = guarded([&] {
     if (want_aggs) agg_check_spec(aggs);  // (what needs no index comes first, as every argument check)
+    if (want_rescore) slgplan::check_rescore(rescore, nq, k);
     SLG_REQUIRE(ix != nullptr, "index is NULL");
     SLG_REQUIRE(!after || q_cursor != nullptr, "q_cursor is NULL");
     if (sort) {  // (checked before planning: the planner never sees a sort spec it cannot run)
@@ -255,6 +258,8 @@ slg_batch *prepare_impl(slg_index *ix, uint32_t nq, const uint32_t *q_offsets, c
     }
     slgplan::Plan plan;
     slgplan::plan_batch(views, ix->tune, in, plan);
+    slgplan::RescorePlan rescore_plan;  // (against the same snapshot, before any device work)
+    if (want_rescore) slgplan::plan_rescore(views, nq, k, *rescore, rescore_plan);
 
     DeviceGuard g(ix->device);
     b = new slg_batch();
@@ -367,6 +372,7 @@ slg_batch *prepare_impl(slg_index *ix, uint32_t nq, const uint32_t *q_offsets, c
     b->d_out_score = R.score(b->d_out.as<uint32_t>());
     b->d_out_count = R.count(b->d_out.as<uint32_t>());
     if (aggs) agg_attach(b, *aggs);
+    if (want_rescore) rescore_attach(b, rescore_plan);
     {
       std::lock_guard<std::mutex> lk(ix->mu);
       ix->live.push_back(b);
@@ -544,6 +550,7 @@ int slg_batch_run(slg_batch *b) {
       SLG_HIP(hipMemsetAsync(b->d_out_count, 0, ((size_t)b->nq + 1) * 4, st));  // (k = 0: nothing was scored)
     }
     if (b->aggs) agg_launch(b, st);  // (after the select: the tables of every accepted candidate)
+    if (b->rescore) rescore_launch(b, st);  // (behind the rows: the first w of every query are scored again)
   });
 }
 
@@ -813,6 +820,29 @@ int slg_search_batch_aggs(slg_index *ix, const slg_query *queries, uint32_t nq, 
   return run_to_host(slg_batch_prepare_aggs(ix, nq, fq.offs.data(), fq.tids.data(), fq.ws.data(), plans, q_filter,
                                             sort, aggs, k, strategy),
                      out_doc, out_seg, out_score, out_count, nullptr, out_matched, nullptr, counts, stats);
+}
+
+slg_batch *slg_batch_prepare_rescore(slg_index *ix, uint32_t nq, const uint32_t *q_offsets, const uint32_t *q_term_ids,
+                                     const float *q_weights, const slg_score_plans *plans, const int32_t *q_filter,
+                                     const slg_rescore_spec *rescore, uint32_t k, int strategy) {
+  return prepare_impl(ix, nq, q_offsets, q_term_ids, q_weights, plans, q_filter, nullptr, k, strategy, false, nullptr,
+                      false, nullptr, false, rescore, true);
+}
+
+int slg_search_batch_rescore(slg_index *ix, uint32_t nq, const uint32_t *q_offsets, const uint32_t *q_term_ids,
+                             const float *q_weights, const slg_score_plans *plans, const int32_t *q_filter,
+                             const slg_rescore_spec *rescore, uint32_t k, int strategy, uint32_t *out_doc,
+                             uint32_t *out_seg, float *out_score, uint32_t *out_count, float *out_first_score,
+                             float *out_rescore_score, uint32_t *out_rescored) {
+  slg_batch *b = slg_batch_prepare_rescore(ix, nq, q_offsets, q_term_ids, q_weights, plans, q_filter, rescore, k,
+                                           strategy);
+  if (!b) return last_error().code;
+  int rc = slg_batch_run(b);
+  if (rc == SLG_OK) rc = slg_batch_fetch(b, out_doc, out_seg, out_score, out_count, nullptr);
+  if (rc == SLG_OK) rc = slg_batch_fetch_rescore(b, out_first_score, out_rescore_score, out_rescored);
+  KeepLastError keep;
+  slg_batch_destroy(b);
+  return rc;
 }
 
 int slg_batch_cursor_seen(slg_batch *b, uint8_t *out_seen) {

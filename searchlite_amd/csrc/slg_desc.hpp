@@ -146,6 +146,29 @@ struct VecSegDev {
   uint32_t pad;
 };
 
+// ---- query rescore (slg_batch_prepare_rescore; kernel: slg_rescore.hpp, planner: slg_plan.cpp) -------
+// The rescore terms of query q are terms[(term_begin + i) * n_segs + s], i = 0 .. n_terms - 1, for
+// segment s: sorted by leaf (stable, so a leaf's terms keep the query's term order); a term absent
+// from a segment (SLG_NO_TERM or an empty list) has df 0.
+struct RescoreTerm {
+  uint64_t off;  // posting offset inside the segment arrays (padded layout, as TermRef::off)
+  uint32_t df;   // list length; 0: the segment has no posting of the term
+  float weight;
+  uint32_t leaf;
+  uint32_t pad;
+};
+struct RescoreQuery {
+  uint32_t term_begin, n_terms;
+  uint32_t window;     // rows offered to the rescore (the kernel caps it at the query's row count)
+  uint32_t mode;       // SLG_RESCORE_*
+  uint32_t plan;       // 0 Sum, 1 DisMax over the leaves
+  float tie;
+  uint32_t n_leaves;   // leaves of the plan (a DisMax counts every one, those without a posting as 0.0)
+  uint32_t min_match;  // leaves that must hold a row's doc (already >= 1)
+};
+constexpr uint32_t kRescoreMaxWindow = 1024;  // = SLG_MAX_RESCORE_WINDOW: the widest WaveTopK
+constexpr uint32_t kRescoreMaxTable = 2048;   // RescoreTerm entries of one query (terms x segments) in LDS: 48 KB
+
 // ---- merge of per-shard results gathered over RCCL (merge_shards_kernel, slg_kernels.hpp) ----------
 struct ShardMergeParams {
   const uint32_t *doc;    // shard sh's rows start at doc + sh * arr_stride ([nq*k] each)

@@ -1,5 +1,5 @@
 // slg_host.hpp — what the host translation units of the C ABI share (slg_index.hip, slg_batch.hip,
-// slg_shard.hip, slg_rerank.hip, slg_vsearch.hip, slg_hybrid.hip): the error plumbing, device memory, the host
+// slg_shard.hip, slg_rerank.hip, slg_vsearch.hip, slg_hybrid.hip, slg_aggs.hip, slg_rescore.hip): the error plumbing, device memory, the host
 // structures behind the opaque handles and the small helpers several entry points use.  Private: not
 // installed, not part of include/.  No kernel header is included here — each unit includes the one
 // whose kernels it launches (slg_stage.hpp, slg_kernels.hpp, slg_rerank.hpp, slg_vsearch.hpp, slg_hybrid.hpp; the shard
@@ -492,6 +492,12 @@ struct slg_batch {
   bool agg_lds = false;              // the tables fit SLG_AGG_LDS_BYTES
   DevBuf d_agg_desc;                 // slg::AggNodeDev[n_nodes], then slg::AggColDev[n_nodes * n_segs]
   DevBuf d_agg_counts, d_agg_stats;  // u32[nq * count_cells], slg::AggStatDev[nq * stats_cells]
+  // rescore batch (slg_batch_prepare_rescore): rescore_kernel runs behind the first pass's last kernel and
+  // rewrites the first rows of every query in place (slg_rescore.hip)
+  bool rescore = false;
+  uint32_t rs_lds_rows = 0, rs_max_table = 0;  // LDS rows (>= every window, even) and table entries of the launch
+  DevBuf d_rs_desc;  // slg::RescoreQuery[nq], then slg::RescoreTerm[total x n_segs]
+  DevBuf d_rs_side;  // first-pass score | rescore score | rescored flag, [nq * k] each
 };
 
 namespace slghost __attribute__((visibility("hidden"))) {
@@ -601,6 +607,10 @@ slg_batch *prepare_agg_batch(slg_index *ix, uint32_t nq, const uint32_t *q_offse
 void agg_check_spec(const slg_agg_spec *aggs);
 void agg_attach(slg_batch *b, const slg_agg_spec &aggs);
 void agg_launch(slg_batch *b, hipStream_t st);
+// slg_rescore.hip: the planned rescore table onto the device with the batch's detail arrays (throws; the batch
+// is otherwise prepared); the launch behind the batch's last first-pass kernel
+void rescore_attach(slg_batch *b, const slgplan::RescorePlan &rp);
+void rescore_launch(slg_batch *b, hipStream_t st);
 
 // slg_vsearch.hip: one vector search or hybrid call, checked against one state of the index ...
 struct VsCall {

@@ -886,6 +886,90 @@ void plan_batch(const std::vector<SegView> &segs, const slg_tuning &tn, const Ba
   out.layout();
 }
 
+// ---- query rescore ---------------------------------------------------------------------------------
+static_assert(slg::kRescoreMaxWindow == SLG_MAX_RESCORE_WINDOW, "the kernel's rows per lane and the ABI's window limit");
+
+void check_rescore(const slg_rescore_spec *spec, uint32_t nq, uint32_t k) {
+  PLAN_REQUIRE(spec != nullptr, "rescore spec is NULL");
+  if (nq == 0) return;
+  PLAN_REQUIRE(spec->q_offsets != nullptr, "rescore q_offsets is NULL");
+  PLAN_REQUIRE(spec->q_window != nullptr, "rescore q_window is NULL");
+  const uint32_t total = spec->q_offsets[nq];
+  PLAN_REQUIRE(total == 0 || (spec->q_term_ids && spec->q_weights), "rescore q_term_ids/q_weights is NULL");
+  for (uint32_t q = 0; q < nq; q++) {
+    const std::string in_q = " in rescore query " + std::to_string(q);
+    PLAN_REQUIRE(spec->q_offsets[q + 1] >= spec->q_offsets[q] && spec->q_offsets[q + 1] <= total,
+                 "rescore q_offsets not monotone");
+    const uint32_t t0 = spec->q_offsets[q], nt = spec->q_offsets[q + 1] - t0;
+    PLAN_REQUIRE(nt <= SLG_MAX_QUERY_TERMS, "more than " + std::to_string(SLG_MAX_QUERY_TERMS) + " terms" + in_q);
+    const int32_t mode = spec->q_mode ? spec->q_mode[q] : SLG_RESCORE_TOTAL;
+    PLAN_REQUIRE(mode >= SLG_RESCORE_TOTAL && mode <= SLG_RESCORE_MIN, "unknown score mode" + in_q);
+    const int32_t plan = spec->q_plan ? spec->q_plan[q] : SLG_PLAN_SUM;
+    PLAN_REQUIRE(plan == SLG_PLAN_SUM || plan == SLG_PLAN_DISMAX, "unknown score plan" + in_q);
+    const float tie = spec->q_tie ? spec->q_tie[q] : 0.0f;
+    PLAN_REQUIRE(tie >= 0.0f && tie <= 1.0f, "tie breaker outside [0, 1]" + in_q);  // (also: NaN)
+    for (uint32_t i = 0; i < nt; i++) {
+      PLAN_REQUIRE(std::isfinite(spec->q_weights[t0 + i]), "non-finite weight" + in_q);
+      PLAN_REQUIRE(!spec->q_leaf || spec->q_leaf[t0 + i] < 0x80000000u, "leaf index >= 2^31" + in_q);
+    }
+  }
+  for (uint32_t q = 0; q < nq; q++)
+    if (std::min(spec->q_window[q], k) > SLG_MAX_RESCORE_WINDOW)  // (a window never reaches past the k rows)
+      throw SlgError(SLG_ERR_UNSUPPORTED, "rescore window of query " + std::to_string(q) + " > SLG_MAX_RESCORE_WINDOW");
+}
+
+void plan_rescore(const std::vector<SegView> &segs, uint32_t nq, uint32_t k, const slg_rescore_spec &spec,
+                  RescorePlan &out) {
+  const uint32_t n_segs = (uint32_t)segs.size();
+  out.queries.assign(nq, slg::RescoreQuery{});
+  out.terms.clear();
+  out.terms.reserve((size_t)(nq ? spec.q_offsets[nq] : 0) * n_segs);
+  for (uint32_t q = 0; q < nq; q++) {
+    const uint32_t t0 = spec.q_offsets[q], nt = spec.q_offsets[q + 1] - t0;
+    slg::RescoreQuery &rq = out.queries[q];
+    rq.term_begin = t0;
+    rq.n_terms = nt;
+    rq.window = spec.q_window[q];
+    rq.mode = spec.q_mode ? (uint32_t)spec.q_mode[q] : (uint32_t)SLG_RESCORE_TOTAL;
+    rq.plan = spec.q_plan && spec.q_plan[q] == SLG_PLAN_DISMAX ? 1u : 0u;
+    rq.tie = spec.q_tie ? spec.q_tie[q] : 0.0f;
+    rq.n_leaves = spec.q_nleaves ? spec.q_nleaves[q] : 0u;
+    rq.min_match = std::max(spec.q_min_match ? spec.q_min_match[q] : 0u, 1u);
+    if ((uint64_t)nt * n_segs > slg::kRescoreMaxTable)
+      throw SlgError(SLG_ERR_UNSUPPORTED, "rescore query " + std::to_string(q) + ": terms x segments exceed " +
+                                              std::to_string(slg::kRescoreMaxTable) + " table entries");
+    // the query's terms by leaf (stable: a leaf's terms keep the term order their scores are added in)
+    uint32_t order[SLG_MAX_QUERY_TERMS];
+    for (uint32_t i = 0; i < nt; i++) {
+      order[i] = i;
+      rq.n_leaves = std::max(rq.n_leaves, (spec.q_leaf ? spec.q_leaf[t0 + i] : i) + 1u);
+    }
+    if (spec.q_leaf)
+      std::stable_sort(order, order + nt,
+                       [&](uint32_t a, uint32_t b) { return spec.q_leaf[t0 + a] < spec.q_leaf[t0 + b]; });
+    for (uint32_t j = 0; j < nt; j++) {
+      const uint32_t i = order[j];
+      for (uint32_t s = 0; s < n_segs; s++) {
+        const SegView &sh = segs[s];
+        slg::RescoreTerm rt{};
+        rt.weight = spec.q_weights[t0 + i];
+        rt.leaf = spec.q_leaf ? spec.q_leaf[t0 + i] : i;
+        const uint32_t tid = spec.q_term_ids[(size_t)(t0 + i) * n_segs + s];
+        if (tid != SLG_NO_TERM) {
+          PLAN_REQUIRE(tid < sh.n_terms, "term id out of range in rescore query " + std::to_string(q));
+          rt.df = (uint32_t)(sh.term_offsets[tid + 1] - sh.term_offsets[tid]);
+          rt.off = sh.term_offsets[tid] + (uint64_t)slg::kListPad * tid;  // padded layout (SegDev)
+        }
+        out.terms.push_back(rt);
+      }
+    }
+    if (nt) {
+      out.max_window = std::max(out.max_window, std::min(rq.window, k));
+      out.max_table = std::max(out.max_table, nt * n_segs);
+    }
+  }
+}
+
 // ---- sort keys of numeric fast fields ----------------------------------------------------------
 namespace {
 inline uint64_t i64_key(int64_t v) { return (uint64_t)v ^ 0x8000000000000000ull; }

@@ -108,6 +108,23 @@ struct Plan {
   void pack(unsigned char *dst) const;  // dst: image_bytes bytes
 };
 
+// ---- query rescore (slg_batch_prepare_rescore) ----
+// The checks of a rescore spec that need no index (throws SlgError): NULL spec or arrays, offsets, term
+// counts, modes, plans, ties, weights (SLG_ERR_INVALID), windows that, capped at k, exceed the limit
+// (SLG_ERR_UNSUPPORTED).
+void check_rescore(const slg_rescore_spec *spec, uint32_t nq, uint32_t k);
+// The per-(query, segment) term table of a checked spec against the segments (slg::RescoreQuery /
+// RescoreTerm: slg_desc.hpp).  Throws SLG_ERR_INVALID for a term id out of range, SLG_ERR_UNSUPPORTED
+// for a query whose table exceeds slg::kRescoreMaxTable entries.
+struct RescorePlan {
+  std::vector<slg::RescoreQuery> queries;  // [nq]
+  std::vector<slg::RescoreTerm> terms;     // [total x n_segs]
+  uint32_t max_window = 0;                 // the largest min(window, k) of a query with terms
+  uint32_t max_table = 0;                  // the most table entries (terms x segments) of a query
+};
+void plan_rescore(const std::vector<SegView> &segs, uint32_t nq, uint32_t k, const slg_rescore_spec &spec,
+                  RescorePlan &out);
+
 // Throws SlgError (SLG_ERR_INVALID / SLG_ERR_UNSUPPORTED) on malformed input.
 void plan_batch(const std::vector<SegView> &segs, const slg_tuning &tune, const BatchIn &in, Plan &out);
 

@@ -769,29 +769,7 @@ inline size_t rerank_multi_lds_floats(uint32_t n_clauses, uint32_t dim, uint32_t
   return (size_t)n_clauses * (dim + 4) + (size_t)n_clauses * max_cand + 2 * (size_t)max_cand + 8;  // (+ clause norms)
 }
 
-template <typename K, typename P>
-inline hipError_t launch_with_lds(K kernel, const P &params, uint32_t nq, size_t lds, hipStream_t st) {
-  if (lds > 48 * 1024) {  // above the default dynamic-LDS limit: opt in (up to the CU's 160 KiB)
-    const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kernel),
-                                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return e;
-  }
-  hipLaunchKernelGGL(kernel, dim3(nq), dim3(256), lds, st, params);
-  return hipGetLastError();
-}
-
-// launch(std::integral_constant<int, KREGS>{}) for the top-k register width kregs names: every rerank
-// kernel is instantiated for KREGS 1, 2, 4, 8 and 16 here
-template <typename F>
-inline hipError_t with_kregs(int kregs, F &&launch) {
-  switch (kregs) {
-    case 1: return launch(std::integral_constant<int, 1>{});
-    case 2: return launch(std::integral_constant<int, 2>{});
-    case 4: return launch(std::integral_constant<int, 4>{});
-    case 8: return launch(std::integral_constant<int, 8>{});
-    default: return launch(std::integral_constant<int, 16>{});
-  }
-}
+// (launch_with_lds, with_kregs: slg_wave.hpp)
 
 inline hipError_t launch_rerank_multi(const RerankMultiParams &mp, int kregs, hipStream_t st) {
   const size_t lds = rerank_multi_lds_floats(mp.n_clauses, mp.base.dim, mp.base.max_cand) * 4 + 16;

@@ -3,12 +3,13 @@
 // register top-k WaveTopK (insert, the stream-and-insert loop `offer`, the result row `store_row`), the
 // buffered top-k BufTopK, and the three scalar rules of a vector score (missing_vector_score,
 // similarity_from_sum, blend) that the rerank and the vector-search kernels restate from the reference.
-// Device code only, no kernels: the scoring units (slg_score_inst.hip) include it without
-// compiling a copy of the host-launched kernels of slg_kernels.hpp.
+// Device code and two launch helpers (launch_with_lds, with_kregs), no kernels: the scoring units
+// (slg_score_inst.hip) include it without compiling a copy of the host-launched kernels of slg_kernels.hpp.
 #pragma once
 
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <type_traits>
 
 #include "slg_desc.hpp"
 
@@ -371,5 +372,30 @@ struct BufTopK {
     }
   }
 };
+
+// ---- launch helpers of the one-workgroup-per-query kernels (rerank, rescore) ------------------------
+template <typename K, typename P>
+inline hipError_t launch_with_lds(K kernel, const P &params, uint32_t nq, size_t lds, hipStream_t st) {
+  if (lds > 48 * 1024) {  // above the default dynamic-LDS limit: opt in (up to the CU's 160 KiB)
+    const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kernel),
+                                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    if (e != hipSuccess) return e;
+  }
+  hipLaunchKernelGGL(kernel, dim3(nq), dim3(256), lds, st, params);
+  return hipGetLastError();
+}
+
+// launch(std::integral_constant<int, KREGS>{}) for the top-k register width kregs names: a kernel launched
+// through it is instantiated for KREGS 1, 2, 4, 8 and 16
+template <typename F>
+inline hipError_t with_kregs(int kregs, F &&launch) {
+  switch (kregs) {
+    case 1: return launch(std::integral_constant<int, 1>{});
+    case 2: return launch(std::integral_constant<int, 2>{});
+    case 4: return launch(std::integral_constant<int, 4>{});
+    case 8: return launch(std::integral_constant<int, 8>{});
+    default: return launch(std::integral_constant<int, 16>{});
+  }
+}
 
 }  // namespace slg

@@ -315,6 +315,19 @@ class GpuIndex:
         finally:
             b.close()
 
+    def search_rescore(self, q_offsets, q_terms, q_weights, k: int, rescore, strategy: int = Wand, q_filter=None,
+                       **plans):
+        """Batch search with a query rescore (slg_batch_prepare_rescore).  rescore: a dict with q_offsets, q_terms
+        ([total, n_segs]), q_weights, window (a number or one per query) and optionally mode (RESCORE_*, a number
+        or one per query), q_leaf, q_plan, q_tie, q_nleaves, q_min_match; **plans: the first pass's score plan
+        arrays of prepare().  -> (doc, seg, score, count, first_score, rescore_score, rescored)."""
+        b = self.prepare(q_offsets, q_terms, q_weights, k, strategy, q_filter, rescore=rescore, **plans)
+        try:
+            b.run()
+            return b.fetch() + b.rescore_details()
+        finally:
+            b.close()
+
     def search_sorted(self, q_offsets, q_terms, q_weights, k: int, sort, strategy: int = Wand, q_filter=None,
                       **plans):
         """Field-sorted batch search (slg_batch_prepare_sorted).  sort: [(field, order)], field = a sort field id
@@ -346,7 +359,8 @@ class GpuIndex:
                 q_filter=None, q_leaf=None, q_plan=None, q_tie=None, q_nleaves=None,
                 q_leaf_offsets=None, leaf_group=None, q_group_offsets=None, group_plan=None,
                 group_tie=None, q_node_offsets=None, node_kind=None, node_tie=None, node_parent=None,
-                q_min_match=None, sort=None, cursors=None, hybrid=False, aggs=None) -> "PreparedBatch":
+                q_min_match=None, sort=None, cursors=None, hybrid=False, aggs=None,
+                rescore=None) -> "PreparedBatch":
         """q_leaf / q_plan / q_tie / q_nleaves: score plans; leaf_group / group_plan / group_tie with
         their per-query offsets: two-level plans; q_node_offsets / node_kind / node_tie / node_parent:
         trees of any shape, node by node in pre-order (slg_batch_prepare_plans, slg_score_plans);
@@ -354,11 +368,12 @@ class GpuIndex:
         (search_sorted) -> slg_batch_prepare_sorted; cursors: a cursor per query (search_after) ->
         slg_batch_prepare_after; hybrid: the text side of a hybrid text + vector search ->
         slg_batch_prepare_hybrid (PreparedBatch.hybrid_device); aggs: an N.AggSpec or aggs.AggPlan ->
-        slg_batch_prepare_aggs (PreparedBatch.aggs)."""
+        slg_batch_prepare_aggs (PreparedBatch.aggs); rescore: the dict of search_rescore ->
+        slg_batch_prepare_rescore (PreparedBatch.rescore_details)."""
         return PreparedBatch(self, q_offsets, q_terms, q_weights, k, strategy, q_filter,
                              q_leaf, q_plan, q_tie, q_nleaves, q_leaf_offsets, leaf_group,
                              q_group_offsets, group_plan, group_tie, q_node_offsets, node_kind, node_tie, node_parent,
-                             q_min_match, sort, cursors, hybrid, aggs)
+                             q_min_match, sort, cursors, hybrid, aggs, rescore)
 
     def search_plan(self, q_offsets, q_terms, q_weights, k: int, q_leaf=None, q_plan=None,
                     q_tie=None, q_nleaves=None, strategy: int = Wand, q_filter=None, **tree):
@@ -655,6 +670,25 @@ def sort_spec(sort) -> "N.SortSpec":
     return spec
 
 
+def rescore_spec(rescore: dict, nq: int):
+    """The dict of GpuIndex.search_rescore as (N.RescoreSpec, the arrays it points into)."""
+    def arr(name, dtype, per_query=False):
+        a = rescore.get(name)
+        if a is None:
+            return None
+        a = np.asarray(a, dtype=dtype)
+        if per_query and a.ndim == 0:
+            a = np.full(nq, a, dtype=dtype)
+        return np.ascontiguousarray(a)
+    keep = [arr("q_offsets", np.uint32), arr("q_terms", np.uint32), arr("q_weights", np.float32),
+            arr("q_leaf", np.uint32), arr("q_plan", np.int32, True), arr("q_tie", np.float32, True),
+            arr("q_nleaves", np.uint32, True), arr("q_min_match", np.uint32, True),
+            arr("window", np.uint32, True), arr("mode", np.int32, True)]
+    assert keep[0] is not None and len(keep[0]) == nq + 1 and keep[8] is not None
+    assert all(a is None or len(a) == nq for a in keep[4:])
+    return N.RescoreSpec(*[_ptr(a) for a in keep]), keep
+
+
 def sort_cursor(cursor, sort=None) -> "N.SortCursor":
     """None (a first page), an N.SortCursor, or (values, segment_ord, doc_id) -> slg_sort_cursor.  values: one
     per sort part (score order: one, the score): an int is an i64 value, a float an f64 value (or, on a
@@ -686,7 +720,7 @@ class PreparedBatch:
                  q_filter=None, q_leaf=None, q_plan=None, q_tie=None, q_nleaves=None,
                  q_leaf_offsets=None, leaf_group=None, q_group_offsets=None, group_plan=None,
                  group_tie=None, q_node_offsets=None, node_kind=None, node_tie=None, node_parent=None,
-                 q_min_match=None, sort=None, cursors=None, hybrid=False, aggs=None):
+                 q_min_match=None, sort=None, cursors=None, hybrid=False, aggs=None, rescore=None):
         self.index = index
         self._lib = index._lib
         q_offsets = np.ascontiguousarray(q_offsets, dtype=np.uint32)
@@ -719,7 +753,16 @@ class PreparedBatch:
         self.is_hybrid = bool(hybrid)
         assert not (hybrid and (sort is not None or cursors is not None)), "a hybrid batch takes no sort or cursor"
         self.agg_spec = getattr(aggs, "spec", aggs)  # (an aggs.AggPlan carries its N.AggSpec)
-        if aggs is not None:
+        self.is_rescore = rescore is not None
+        if rescore is not None:
+            # (the library's other prepare calls take no rescore spec: the refusal is made here with its code)
+            if hybrid or cursors is not None or sort is not None or aggs is not None:
+                raise N.SlgError(N.ERR_UNSUPPORTED, "rescore is not built on sorted, cursor, hybrid or aggregation batches")
+            spec, self._rescore_keep = rescore_spec(rescore, self.nq)
+            self._h = self._lib.slg_batch_prepare_rescore(
+                index._h, self.nq, _ptr(q_offsets), _ptr(q_terms), _ptr(q_weights), C.addressof(plans),
+                opt(qf), C.addressof(spec), k, strategy)
+        elif aggs is not None:
             # (cursor and hybrid batches take no aggregations: the library's prepare calls for them have no
             #  spec argument, so the refusal is made here with the library's code)
             if hybrid or cursors is not None:
@@ -798,6 +841,16 @@ class PreparedBatch:
             n = x["parent_rows"] * x["rows"]
             out.append(flat[:, x["offset"]:x["offset"] + n].reshape(self.nq, x["parent_rows"], x["rows"]).copy())
         return out
+
+    def rescore_details(self):
+        """Per row of a rescore batch's last run (slg_batch_fetch_rescore; waits): (first_score [nq, k], the
+        first-pass score; rescore_score [nq, k], 0.0 where the row was not rescored; rescored [nq, k], 1 where
+        it was)."""
+        first = np.zeros((self.nq, self.k), dtype=np.float32)
+        rsc = np.zeros((self.nq, self.k), dtype=np.float32)
+        flag = np.zeros((self.nq, self.k), dtype=np.uint32)
+        N.check(self._lib.slg_batch_fetch_rescore(self._h, _ptr(first), _ptr(rsc), _ptr(flag)))
+        return first, rsc, flag
 
     def cursor_seen(self) -> np.ndarray:
         """Per query of a cursor batch's last run: 1 if an accepted doc had the cursor's key (or the query has

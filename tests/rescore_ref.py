@@ -2,15 +2,19 @@
 combine_rescore_scores) over the oracle, f32 operation by operation.
 
   1. First-pass rows = oracle.search_batch / search_batch_filtered / search_batch_min_match at k.
-  2. The rescore score r and the matcher = the oracle's exhaustive run of the rescore query (k = the docs of
-     all segments): a doc in that result is matched and its score is r; a doc absent from it is not matched.
+  2. The rescore score r and the matcher = the oracle's exhaustive (brute-force) run of the rescore query (k =
+     the docs of all segments): a doc in that result is matched and its score is r; a doc absent from it is not matched.
      The oracle adds a doc's term scores per leaf in term order and the leaves in leaf order, which is the
      order the library fixes.  (The exhaustive run leaves out deleted docs; first-pass rows are live.)
   3. w = min(window, count); a matched row of the first w scores combine(mode, first, r) in f32, the others
      keep their score; the first w rows are sorted by (score desc under total_cmp, segment asc, doc asc); rows
      from w on keep their place.
 
-apply_rescore() is pure (tests/test_rescore_ref.py checks it by hand-derived cases)."""
+direct_maps() is step 2 without the oracle's top-k: r of every doc from the oracle's per-posting impacts
+(score_tf at weight 1), combined as include/searchlite_gpu.h states it (slg_batch_prepare_rescore, step 3).
+It is the reference where an exhaustive top-k run is no fit: negative weights, products that overflow, NaN.
+
+apply_rescore() and direct_maps() are checked by hand-derived cases in tests/test_rescore_ref.py."""
 import numpy as np
 
 from tests.util import _f32_key
@@ -76,12 +80,79 @@ def rescore_maps(oracle, segs, rescore):
     mm = rescore.get("q_min_match")
     if mm is not None and np.ndim(mm) == 0:
         mm = np.full(nq, mm)
+    # the brute-force scorer: it adds a leaf's terms in query-term order (the WAND scorer adds them in the order
+    # of its cursors, which shows once a leaf has three terms)
     args = (segs, offs, rescore["q_terms"], rescore["q_weights"], k_all)
     if mm is not None and int(np.max(mm, initial=0)) > 1:
-        d, s, sc, c = oracle.search_batch_min_match(*args, np.asarray(mm, np.uint32), **plans)
+        d, s, sc, c = oracle.search_batch_min_match(*args, np.asarray(mm, np.uint32), strategy=oracle.BM25, **plans)
     else:
-        d, s, sc, c = oracle.search_batch(*args, **plans)
+        d, s, sc, c = oracle.search_batch(*args, strategy=oracle.BM25, **plans)
     return [{(int(s[q, i]), int(d[q, i])): F32(sc[q, i]) for i in range(int(c[q]))} for q in range(nq)]
+
+
+_impacts = {}
+
+
+def impacts(oracle, seg, term):
+    """(doc ids, f32 impact of every posting of `term` at weight 1): score_tf over the list, df = its length"""
+    key = (id(seg), int(term))
+    if key not in _impacts:
+        a, b = int(seg.term_offsets[term]), int(seg.term_offsets[term + 1])
+        f = 0 if seg.term_field is None else int(seg.term_field[term])
+        dl, avg = seg.field_doc_len[f], float(seg.field_avgdl[f])
+        docs = np.asarray(seg.doc_ids[a:b], np.int64)
+        imp = np.array([oracle.score_tf(float(tf), float(b - a), 0.0 if dl is None else float(dl[d]), avg,
+                                        float(seg.docs), float(seg.k1), float(seg.b), 1.0)
+                        for d, tf in zip(docs, seg.tfs[a:b])], F32)
+        _impacts[key] = (seg, docs, imp)  # (the segment is kept: its id stays its own)
+    return _impacts[key][1:]
+
+
+def direct_maps(oracle, segs, rescore):
+    """per query {(seg, doc): r} as rescore_maps, from the impacts: a doc's leaf sums start at 0.0 and take
+    impact * weight of the leaf's terms in query-term order; a Sum starts at -0.0 and adds the leaves that hold
+    the doc in leaf order; a DisMax is m + tie * (sum - m), sum from 0.0, m = the max (f32::max from -inf) of the
+    leaves that hold the doc, and of 0.0 if fewer than n_leaves do; matched = at least max(min_match, 1) leaves
+    hold the doc.  Every step is one f32 operation."""
+    offs = np.asarray(rescore["q_offsets"], np.uint32)
+    nq = len(offs) - 1
+    terms = np.asarray(rescore["q_terms"], np.uint32).reshape(-1, len(segs))
+    weights = np.asarray(rescore["q_weights"], F32)
+    leaf_of = rescore.get("q_leaf")
+    plan, tie = per_query(rescore.get("q_plan"), nq, 0), per_query(rescore.get("q_tie"), nq, 0.0).astype(F32)
+    nleaves, mm = per_query(rescore.get("q_nleaves"), nq, 0), per_query(rescore.get("q_min_match"), nq, 0)
+    out = []
+    with np.errstate(over="ignore", invalid="ignore"):
+        for q in range(nq):
+            t0, t1 = int(offs[q]), int(offs[q + 1])
+            leaves = np.arange(t1 - t0) if leaf_of is None else np.asarray(leaf_of, np.int64)[t0:t1]
+            n_leaves = max(int(nleaves[q]), int(leaves.max()) + 1 if len(leaves) else 0)
+            rmap = {}
+            for s, seg in enumerate(segs):
+                n = int(seg.n_docs)
+                acc = np.full(n, -0.0 if int(plan[q]) == 0 else 0.0, F32)
+                mx, nhit = np.full(n, -np.inf, F32), np.zeros(n, np.int64)
+                for lf in np.unique(leaves):
+                    leafv, hit = np.zeros(n, F32), np.zeros(n, bool)
+                    for i in np.nonzero(leaves == lf)[0]:
+                        t = int(terms[t0 + i, s])
+                        if t == 0xFFFFFFFF:
+                            continue
+                        docs, imp = impacts(oracle, seg, t)
+                        leafv[docs] = leafv[docs] + imp * weights[t0 + i]
+                        hit[docs] = True
+                    acc[hit] = acc[hit] + leafv[hit]
+                    mx[hit] = np.fmax(mx[hit], leafv[hit])
+                    nhit += hit
+                r = acc
+                if int(plan[q]) != 0:
+                    m = np.where(nhit < n_leaves, np.fmax(mx, F32(0.0)), mx).astype(F32)
+                    r = m + tie[q] * (acc - m)
+                assert r.dtype == F32
+                for d in np.nonzero(nhit >= max(int(mm[q]), 1))[0]:
+                    rmap[(s, int(d))] = F32(r[d])
+            out.append(rmap)
+    return out
 
 
 def per_query(x, nq, default):

@@ -98,12 +98,14 @@ def world(gpu, oracle):
 _expected = {}
 
 
-def expected(request, cols, docs, plan, key=None):
-    """agg_ref's tables of every query, computed once per (request, doc sets) and shared"""
+def expected(request, cols, docs, plan, key=None, keys_of=None):
+    """agg_ref's tables of every query, computed once per (request, doc sets) and shared; keys_of: the keyword
+    dictionaries of `cols` (KEYS_OF when not given)"""
     if key is not None and key in _expected:
         return _expected[key]
-    layout = R.ref_layout(plan.nodes, cols, KEYS_OF)
-    per_q = [R.dense(plan.nodes, layout, R.run(request, cols, d), KEYS_OF) for d in docs]
+    keys_of = KEYS_OF if keys_of is None else keys_of
+    layout = R.ref_layout(plan.nodes, cols, keys_of)
+    per_q = [R.dense(plan.nodes, layout, R.run(request, cols, d), keys_of) for d in docs]
     out = layout, [np.stack([t[i] for t in per_q]) for i in range(len(plan.nodes))]
     if key is not None:
         _expected[key] = out
@@ -136,7 +138,7 @@ def run_check(W, request, sort=None, k=11, docs=None, key=None, what="", **kw):
     ix = W["ix"]
     plan = A.agg_spec(request, W["fields"])
     docs = W["docs"] if docs is None else docs
-    want_layout, want_tables = expected(request, W["cols"], docs, plan, key)
+    want_layout, want_tables = expected(request, W["cols"], docs, plan, key, W.get("keys_of"))
     got = ix.search_aggs(W["offs"], W["terms"], W["w"], k, plan, sort=sort, **kw)
     doc, seg, score, count, matched, tables, layout = got
     if sort is None:

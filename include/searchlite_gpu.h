@@ -28,6 +28,9 @@
  * vector-only, sharded or coalesced batches.  Query rescore (slg_batch_prepare_rescore): a second BM25 query with
  * a flat Sum / DisMax plan over a window of up to SLG_MAX_RESCORE_WINDOW first-pass rows, every score_mode; in
  * score order only, not on sorted, cursor, hybrid, vector-only, aggregation, sharded or coalesced batches.
+ * Boolean queries (slg_batch_prepare_bool): must / should / must_not groups of terms and minimum_should_match
+ * over up to SLG_MAX_BOOL_GROUPS groups, in score order or a field sort; not nested, no phrases, not on
+ * cursor, hybrid, aggregation, rescore, sharded or coalesced batches.
  */
 #ifndef SEARCHLITE_GPU_H
 #define SEARCHLITE_GPU_H
@@ -1024,6 +1027,79 @@ int slg_search_batch_rescore(slg_index *index, uint32_t nq, const uint32_t *q_of
                              int strategy, uint32_t *out_doc, uint32_t *out_seg, float *out_score,
                              uint32_t *out_count, float *out_first_score, float *out_rescore_score,
                              uint32_t *out_rescored);
+
+/* ---------------------------------------------------------------------------------------------------------
+ * Boolean queries: `bool { must, should, must_not, minimum_should_match }` over term clauses and the query
+ * string's `+a -b` form.  The reference walks the union of the scored lists and asks accept(doc) for each doc;
+ * accept evaluates QueryEvaluator::matches_node (api/reader.rs:1485-1565), whose term-group test is a binary
+ * search of the doc in the group's posting lists (term_group_matches, :1571-1580).  Here, in flat form:
+ *
+ * A query has a clause table of GROUPS.  A group is one or more terms (one query word over its fields) and
+ * HOLDS a doc of segment s if any of its terms has a posting of the doc in s.  Every group has a kind
+ * (SLG_BOOL_MUST / _SHOULD / _MUST_NOT) and the query a q_min_should.  A candidate — a doc of a scored list —
+ * is accepted iff every MUST group holds it, no MUST_NOT group holds it, and at least q_min_should SHOULD groups
+ * hold it (0: no should requirement; more than the query has SHOULD groups: nothing matches).  Tombstones and
+ * q_filter apply as in every batch.  `Bool` with Term children (:1527-1563): the caller passes the reference's
+ * minimum_should_match, its default rule (:1553-1561) applied.  A query string (:1490-1518): term groups are
+ * SHOULD groups with q_min_should = minimum_should_match.unwrap_or(1), not-terms are MUST_NOT groups.
+ *
+ * Clause terms are independent of the scored terms (a must / should term is normally scored too, a must_not
+ * term never is).  Only docs of the scored lists are candidates, as in the reference: a query whose scored
+ * lists are all empty returns nothing.  A clause term that is SLG_NO_TERM in a segment has no posting there: a
+ * MUST group whose terms are all absent from a segment rejects every candidate of that segment, an absent
+ * MUST_NOT term rejects nothing.  A query without a group is untouched (its q_min_should is not looked at);
+ * queries with and without groups mix in one batch.
+ *
+ * Scores are untouched: an accepted doc has the exact score of the first pass, under any score plan.  The
+ * plans' q_min_match must be NULL, 0 or 1 (SLG_ERR_INVALID otherwise): the clause table is the one place that
+ * states it — which also lifts its limits (more than 8 scored lists, nested plans).
+ *
+ * The clause terms of query q are rows c_offsets[q] .. c_offsets[q + 1] - 1 of c_term_ids (one id per segment,
+ * as q_term_ids) and c_group; c_group[i] is the term's group inside its query: non-decreasing from 0 without
+ * gaps, so every group g_offsets[q] .. g_offsets[q + 1] - 1 of g_kind has a term.
+ *
+ * slg_batch_prepare_bool is slg_batch_prepare_plans (sort NULL: score order) or slg_batch_prepare_sorted (a field
+ * sort) plus the spec.  The batch is planned as a sorted batch is — every doc of the scored lists is scored,
+ * no threshold seed, no MaxScore — and slg_batch_run enqueues one kernel between the scoring kernel and the
+ * select that drops the candidates the clause table rejects.  slg_batch_run / _fetch / _device_results / _sync /
+ * _set_stream as for any batch; slg_batch_matched_counts for the sorted form: it counts accepted docs.
+ * slg_stats.scored_docs = the count of a batch without clauses (see slg_stats) minus the docs the clause table
+ * rejected.  The clause terms are resolved against the index state the batch was prepared on.
+ * slg_search_batch_bool is the one-call form with host arrays; stats may be NULL; out_matched may be NULL and
+ * must be NULL without a sort spec.
+ *
+ * Errors, all before any device work.  SLG_ERR_INVALID: a NULL spec or array, offsets that decrease, a c_group
+ * that decreases, skips a number or names a group the query does not have, a group without a term, an unknown
+ * kind, a term id out of range, q_min_match > 1 in the plans.  SLG_ERR_UNSUPPORTED (CPU scorer): more than
+ * SLG_MAX_BOOL_GROUPS groups or SLG_MAX_BOOL_TERMS clause terms in a query.  slg_batch_run_sharded* and
+ * slg_batch_fetch_sharded refuse a bool batch with SLG_ERR_UNSUPPORTED.  Not built (CPU scorer): nested matchers
+ * (a bool or dis_max as a child of bool), phrases, bool.filter other than through q_filter, and clause tables
+ * on cursor, hybrid, aggregation, rescore, sharded and coalesced batches (none of their prepare calls takes a
+ * bool spec).
+ * --------------------------------------------------------------------------------------------------------- */
+#define SLG_BOOL_MUST 0
+#define SLG_BOOL_SHOULD 1
+#define SLG_BOOL_MUST_NOT 2
+#define SLG_MAX_BOOL_GROUPS 32u   /* groups of one query (one bit each in the kernel's masks) */
+#define SLG_MAX_BOOL_TERMS 64u    /* clause terms of one query */
+typedef struct slg_bool_spec {
+  const uint32_t *c_offsets;    /* [nq + 1] into c_term_ids rows / c_group */
+  const uint32_t *c_term_ids;   /* [n_clause_terms x n_segs], rows as q_term_ids, SLG_NO_TERM where absent */
+  const uint32_t *c_group;      /* [n_clause_terms] group of the term inside its query, non-decreasing, from 0, no gaps */
+  const uint32_t *g_offsets;    /* [nq + 1] into g_kind */
+  const int32_t *g_kind;        /* [n_groups] SLG_BOOL_* */
+  const uint32_t *q_min_should; /* [nq] or NULL (= 0) */
+} slg_bool_spec;
+slg_batch *slg_batch_prepare_bool(slg_index *index, uint32_t nq, const uint32_t *q_offsets, const uint32_t *q_term_ids,
+                                  const float *q_weights, const slg_score_plans *plans_or_null,
+                                  const int32_t *q_filter_or_null, const slg_sort_spec *sort_or_null,
+                                  const slg_bool_spec *spec, uint32_t k, int strategy);
+int slg_search_batch_bool(slg_index *index, uint32_t nq, const uint32_t *q_offsets, const uint32_t *q_term_ids,
+                          const float *q_weights, const slg_score_plans *plans_or_null,
+                          const int32_t *q_filter_or_null, const slg_sort_spec *sort_or_null,
+                          const slg_bool_spec *spec, uint32_t k, int strategy, uint32_t *out_doc, uint32_t *out_seg,
+                          float *out_score, uint32_t *out_count, slg_stats *stats_or_null,
+                          uint64_t *out_matched_or_null);
 
 #ifdef __cplusplus
 }

@@ -72,6 +72,10 @@ pub const SLG_AGG_STATS: i32 = 3;
     pub parent_rows: u32, pub rows: u32, pub first_id: i64, pub is_stats: u32, pub offset: u64,
 }
 #[repr(C)] #[derive(Clone, Copy, Default)] pub struct slg_agg_stats { pub count: u64, pub min: f64, pub max: f64, pub sum: f64 }
+#[repr(C)] pub struct slg_bool_spec {
+    pub c_offsets: *const u32, pub c_term_ids: *const u32, pub c_group: *const u32, pub g_offsets: *const u32,
+    pub g_kind: *const i32, pub q_min_should: *const u32,
+}
 #[repr(C)] pub struct slg_rescore_spec {
     pub q_offsets: *const u32, pub q_term_ids: *const u32, pub q_weights: *const c_float, pub q_leaf: *const u32,
     pub q_plan: *const i32, pub q_tie: *const c_float, pub q_nleaves: *const u32, pub q_min_match: *const u32,
@@ -283,7 +287,21 @@ extern "C" {
         rescore: *const slg_rescore_spec, k: u32, strategy: c_int, out_doc: *mut u32, out_seg: *mut u32,
         out_score: *mut c_float, out_count: *mut u32, out_first_score: *mut c_float,
         out_rescore_score: *mut c_float, out_rescored: *mut u32) -> c_int;
+    // boolean queries (must / should / must_not groups of terms): slg_batch_prepare_plans or _sorted plus the spec
+    pub fn slg_batch_prepare_bool(index: *mut slg_index, nq: u32, q_offsets: *const u32, q_term_ids: *const u32,
+        q_weights: *const c_float, plans: *const slg_score_plans, q_filter: *const i32,
+        sort: *const slg_sort_spec, spec: *const slg_bool_spec, k: u32, strategy: c_int) -> *mut slg_batch;
+    pub fn slg_search_batch_bool(index: *mut slg_index, nq: u32, q_offsets: *const u32, q_term_ids: *const u32,
+        q_weights: *const c_float, plans: *const slg_score_plans, q_filter: *const i32,
+        sort: *const slg_sort_spec, spec: *const slg_bool_spec, k: u32, strategy: c_int, out_doc: *mut u32,
+        out_seg: *mut u32, out_score: *mut c_float, out_count: *mut u32, stats: *mut slg_stats,
+        out_matched: *mut u64) -> c_int;
 }
+pub const SLG_BOOL_MUST: i32 = 0;
+pub const SLG_BOOL_SHOULD: i32 = 1;
+pub const SLG_BOOL_MUST_NOT: i32 = 2;
+pub const SLG_MAX_BOOL_GROUPS: u32 = 32;
+pub const SLG_MAX_BOOL_TERMS: u32 = 64;
 pub const SLG_RESCORE_TOTAL: i32 = 0;
 pub const SLG_RESCORE_MULTIPLY: i32 = 1;
 pub const SLG_RESCORE_SUM: i32 = 2;

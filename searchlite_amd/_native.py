@@ -33,6 +33,9 @@ AGG_LDS_BYTES = 32768
 AGG_TERMS, AGG_HISTOGRAM, AGG_RANGE, AGG_STATS = 0, 1, 2, 3
 RESCORE_TOTAL, RESCORE_MULTIPLY, RESCORE_SUM, RESCORE_MAX, RESCORE_MIN = 0, 1, 2, 3, 4
 MAX_RESCORE_WINDOW = 1024
+BOOL_MUST, BOOL_SHOULD, BOOL_MUST_NOT = 0, 1, 2
+MAX_BOOL_GROUPS = 32
+MAX_BOOL_TERMS = 64
 
 
 class SlgError(RuntimeError):
@@ -128,6 +131,13 @@ class RescoreSpec(C.Structure):
     _fields_ = [("q_offsets", C.c_void_p), ("q_term_ids", C.c_void_p), ("q_weights", C.c_void_p),
                 ("q_leaf", C.c_void_p), ("q_plan", C.c_void_p), ("q_tie", C.c_void_p), ("q_nleaves", C.c_void_p),
                 ("q_min_match", C.c_void_p), ("q_window", C.c_void_p), ("q_mode", C.c_void_p)]
+
+
+class BoolSpec(C.Structure):
+    """slg_bool_spec: the clause tables of a bool batch (CSR clause terms with their groups, group kinds,
+    minimum_should_match per query)."""
+    _fields_ = [("c_offsets", C.c_void_p), ("c_term_ids", C.c_void_p), ("c_group", C.c_void_p),
+                ("g_offsets", C.c_void_p), ("g_kind", C.c_void_p), ("q_min_should", C.c_void_p)]
 
 
 class Ticket(C.Structure):
@@ -273,6 +283,8 @@ def load():
         "slg_batch_prepare_rescore": (vp, [vp, u32, vp, vp, vp, vp, vp, vp, u32, i32]),
         "slg_batch_fetch_rescore": (i32, [vp, vp, vp, vp]),
         "slg_search_batch_rescore": (i32, [vp, u32, vp, vp, vp, vp, vp, vp, u32, i32, vp, vp, vp, vp, vp, vp, vp]),
+        "slg_batch_prepare_bool": (vp, [vp, u32, vp, vp, vp, vp, vp, vp, vp, u32, i32]),
+        "slg_search_batch_bool": (i32, [vp, u32, vp, vp, vp, vp, vp, vp, vp, u32, i32, vp, vp, vp, vp, vp, vp]),
     }
     for name, (res, args) in sigs.items():
         if os.environ.get("SLG_LIB_TAG") and not hasattr(L, name):

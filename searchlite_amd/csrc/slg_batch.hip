@@ -125,7 +125,7 @@ void slghost::release_batch_buffers(slg_batch *b, bool to_pool) {
                     &b->d_q_scored, &b->d_q_filter, &b->d_cand, &b->d_slice_cbeg, &b->d_slice_ccnt,
                     &b->d_out, &b->d_stamps, &b->d_blk_skip, &b->d_gather, &b->d_merged, &b->d_q_cand,
                     &b->d_hy_keys, &b->d_hy_work, &b->d_agg_desc, &b->d_agg_counts, &b->d_agg_stats,
-                    &b->d_rs_desc, &b->d_rs_side};
+                    &b->d_rs_desc, &b->d_rs_side, &b->d_bool_desc};
   for (DevBuf *d : bufs) {
     if (!to_pool) d->pool = nullptr;
     d->release();
@@ -164,17 +164,20 @@ slg_batch *slg_batch_prepare_plan(slg_index *ix, uint32_t nq, const uint32_t *q_
 
 namespace {
 // slg_batch_prepare_plans, (sort != nullptr) slg_batch_prepare_sorted, (after) slg_batch_prepare_after, and
-// (hybrid) slg_batch_prepare_hybrid, (want_aggs) slg_batch_prepare_aggs, (want_rescore) slg_batch_prepare_rescore
+// (hybrid) slg_batch_prepare_hybrid, (want_aggs) slg_batch_prepare_aggs, (want_rescore) slg_batch_prepare_rescore,
+// (want_bool) slg_batch_prepare_bool
 slg_batch *prepare_impl(slg_index *ix, uint32_t nq, const uint32_t *q_offsets, const uint32_t *q_term_ids,
                         const float *q_weights, const slg_score_plans *plans, const int32_t *q_filter,
                         const slg_sort_spec *sort, uint32_t k, int strategy, bool after = false,
                         const slg_sort_cursor *q_cursor = nullptr, bool hybrid = false,
                         const slg_agg_spec *aggs = nullptr, bool want_aggs = false,
-                        const slg_rescore_spec *rescore = nullptr, bool want_rescore = false) {
+                        const slg_rescore_spec *rescore = nullptr, bool want_rescore = false,
+                        const slg_bool_spec *boolean = nullptr, bool want_bool = false) {
   slg_batch *b = nullptr;
   int rc = guarded([&] {
     if (want_aggs) agg_check_spec(aggs);  // (what needs no index comes first, as every argument check)
     if (want_rescore) slgplan::check_rescore(rescore, nq, k);
+    if (want_bool) slgplan::check_bool(boolean, nq, plans);
     SLG_REQUIRE(ix != nullptr, "index is NULL");
     SLG_REQUIRE(!after || q_cursor != nullptr, "q_cursor is NULL");
     if (sort) {  // (checked before planning: the planner never sees a sort spec it cannot run)
@@ -210,7 +213,7 @@ slg_batch *prepare_impl(slg_index *ix, uint32_t nq, const uint32_t *q_offsets, c
     in.strategy = strategy;
     in.filter_live = filter_live.data();
     in.n_filters = filter_live.size();
-    in.sorted = sort != nullptr || after || hybrid || aggs != nullptr;
+    in.sorted = sort != nullptr || after || hybrid || aggs != nullptr || want_bool;
     // the columns of the sort parts in the batch's state: every part names a field with a column for every
     // segment (a field registered before slg_index_add_segment has none for the new one)
     std::vector<slg::SortColDev> sort_cols;
@@ -260,6 +263,8 @@ slg_batch *prepare_impl(slg_index *ix, uint32_t nq, const uint32_t *q_offsets, c
     slgplan::plan_batch(views, ix->tune, in, plan);
     slgplan::RescorePlan rescore_plan;  // (against the same snapshot, before any device work)
     if (want_rescore) slgplan::plan_rescore(views, nq, k, *rescore, rescore_plan);
+    slgplan::BoolPlan bool_plan;
+    if (want_bool) slgplan::plan_bool(views, nq, *boolean, bool_plan);
 
     DeviceGuard g(ix->device);
     b = new slg_batch();
@@ -373,6 +378,7 @@ slg_batch *prepare_impl(slg_index *ix, uint32_t nq, const uint32_t *q_offsets, c
     b->d_out_count = R.count(b->d_out.as<uint32_t>());
     if (aggs) agg_attach(b, *aggs);
     if (want_rescore) rescore_attach(b, rescore_plan);
+    if (want_bool) bool_attach(b, bool_plan);
     {
       std::lock_guard<std::mutex> lk(ix->mu);
       ix->live.push_back(b);
@@ -516,6 +522,7 @@ int slg_batch_run(slg_batch *b) {
       launch_score(sp, score_kind, st);
       if (ev) SLG_HIP(hipEventRecord(ev->second, st));
     }
+    if (b->boolean) bool_launch(b, st);  // (in front of the select: the regions hold accepted candidates only)
     if (b->sorted) {  // (also without slices: every row is empty, every matched count 0)
       slg::SortedSelectParams sp{};
       fill_select(sp, b);
@@ -843,6 +850,23 @@ int slg_search_batch_rescore(slg_index *ix, uint32_t nq, const uint32_t *q_offse
   KeepLastError keep;
   slg_batch_destroy(b);
   return rc;
+}
+
+slg_batch *slg_batch_prepare_bool(slg_index *ix, uint32_t nq, const uint32_t *q_offsets, const uint32_t *q_term_ids,
+                                  const float *q_weights, const slg_score_plans *plans, const int32_t *q_filter,
+                                  const slg_sort_spec *sort, const slg_bool_spec *spec, uint32_t k, int strategy) {
+  return prepare_impl(ix, nq, q_offsets, q_term_ids, q_weights, plans, q_filter, sort, k, strategy, false, nullptr,
+                      false, nullptr, false, nullptr, false, spec, true);
+}
+
+int slg_search_batch_bool(slg_index *ix, uint32_t nq, const uint32_t *q_offsets, const uint32_t *q_term_ids,
+                          const float *q_weights, const slg_score_plans *plans, const int32_t *q_filter,
+                          const slg_sort_spec *sort, const slg_bool_spec *spec, uint32_t k, int strategy,
+                          uint32_t *out_doc, uint32_t *out_seg, float *out_score, uint32_t *out_count,
+                          slg_stats *stats, uint64_t *out_matched) {
+  return run_to_host(slg_batch_prepare_bool(ix, nq, q_offsets, q_term_ids, q_weights, plans, q_filter, sort, spec, k,
+                                            strategy),
+                     out_doc, out_seg, out_score, out_count, stats, out_matched, nullptr);
 }
 
 int slg_batch_cursor_seen(slg_batch *b, uint8_t *out_seen) {

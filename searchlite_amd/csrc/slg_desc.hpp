@@ -169,6 +169,26 @@ struct RescoreQuery {
 constexpr uint32_t kRescoreMaxWindow = 1024;  // = SLG_MAX_RESCORE_WINDOW: the widest WaveTopK
 constexpr uint32_t kRescoreMaxTable = 2048;   // RescoreTerm entries of one query (terms x segments) in LDS: 48 KB
 
+// ---- boolean queries (slg_batch_prepare_bool; kernel: slg_bool.hpp, planner: slg_plan.cpp) -----------
+// The clause terms of query q in segment s are terms[term_begin * n_segs + s * n_terms + i], i = 0 ..
+// n_terms - 1: one contiguous row per (query, segment), which is what a wave of bool_filter_kernel reads.
+// Inside a row the terms lie MUST first, MUST_NOT second, SHOULD last (stable: a kind's terms keep the
+// caller's order), so the kernel's early outs see the clauses that reject first; a term absent from a
+// segment (SLG_NO_TERM or an empty list) has df 0.
+struct BoolTerm {
+  uint64_t off;    // posting offset inside the segment arrays (padded layout, as TermRef::off)
+  uint32_t df;     // list length; 0: the segment has no posting of the term
+  uint32_t group;  // the term's group inside its query (< kBoolMaxGroups: a bit of the masks)
+};
+struct BoolQuery {
+  uint32_t term_begin, n_terms;  // n_terms 0: the query has no clause table and is left as it is
+  uint32_t must_mask, must_not_mask, should_mask;  // bit g: group g is of that kind
+  uint32_t min_should;
+  uint32_t n_must, n_must_not;   // terms of MUST groups (the row's first), of MUST_NOT groups (behind them)
+};
+constexpr uint32_t kBoolMaxGroups = 32;  // = SLG_MAX_BOOL_GROUPS
+constexpr uint32_t kBoolMaxTerms = 64;   // = SLG_MAX_BOOL_TERMS
+
 // ---- merge of per-shard results gathered over RCCL (merge_shards_kernel, slg_kernels.hpp) ----------
 struct ShardMergeParams {
   const uint32_t *doc;    // shard sh's rows start at doc + sh * arr_stride ([nq*k] each)

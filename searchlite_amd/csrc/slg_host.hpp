@@ -1,5 +1,5 @@
 // slg_host.hpp — what the host translation units of the C ABI share (slg_index.hip, slg_batch.hip,
-// slg_shard.hip, slg_rerank.hip, slg_vsearch.hip, slg_hybrid.hip, slg_aggs.hip, slg_rescore.hip): the error plumbing, device memory, the host
+// slg_shard.hip, slg_rerank.hip, slg_vsearch.hip, slg_hybrid.hip, slg_aggs.hip, slg_rescore.hip, slg_bool.hip): the error plumbing, device memory, the host
 // structures behind the opaque handles and the small helpers several entry points use.  Private: not
 // installed, not part of include/.  No kernel header is included here — each unit includes the one
 // whose kernels it launches (slg_stage.hpp, slg_kernels.hpp, slg_rerank.hpp, slg_vsearch.hpp, slg_hybrid.hpp; the shard
@@ -498,6 +498,12 @@ struct slg_batch {
   uint32_t rs_lds_rows = 0, rs_max_table = 0;  // LDS rows (>= every window, even) and table entries of the launch
   DevBuf d_rs_desc;  // slg::RescoreQuery[nq], then slg::RescoreTerm[total x n_segs]
   DevBuf d_rs_side;  // first-pass score | rescore score | rescored flag, [nq * k] each
+  // bool batch (slg_batch_prepare_bool): planned as a sorted batch, run in score order or under its sort spec;
+  // bool_filter_kernel runs between the scoring kernel and the select and drops the candidates the clause
+  // tables reject (slg_bool.hip)
+  bool boolean = false;
+  uint32_t bool_groups = 0;  // groups of all queries (0: no query has a clause table, nothing is launched)
+  DevBuf d_bool_desc;        // slg::BoolQuery[nq], then slg::BoolTerm rows per (query, segment)
 };
 
 namespace slghost __attribute__((visibility("hidden"))) {
@@ -611,6 +617,10 @@ void agg_launch(slg_batch *b, hipStream_t st);
 // is otherwise prepared); the launch behind the batch's last first-pass kernel
 void rescore_attach(slg_batch *b, const slgplan::RescorePlan &rp);
 void rescore_launch(slg_batch *b, hipStream_t st);
+// slg_bool.hip: the planned clause tables onto the device (throws; the batch is otherwise prepared); the launch
+// behind the batch's scoring kernel, in front of its select
+void bool_attach(slg_batch *b, const slgplan::BoolPlan &bp);
+void bool_launch(slg_batch *b, hipStream_t st);
 
 // slg_vsearch.hip: one vector search or hybrid call, checked against one state of the index ...
 struct VsCall {

@@ -970,6 +970,96 @@ void plan_rescore(const std::vector<SegView> &segs, uint32_t nq, uint32_t k, con
   }
 }
 
+// ---- boolean queries -------------------------------------------------------------------------------
+static_assert(slg::kBoolMaxGroups == SLG_MAX_BOOL_GROUPS && slg::kBoolMaxTerms == SLG_MAX_BOOL_TERMS,
+              "the kernel's group masks and the ABI's limits");
+
+void check_bool(const slg_bool_spec *spec, uint32_t nq, const slg_score_plans *plans) {
+  PLAN_REQUIRE(spec != nullptr, "bool spec is NULL");
+  if (nq == 0) return;
+  PLAN_REQUIRE(spec->c_offsets != nullptr, "bool c_offsets is NULL");
+  PLAN_REQUIRE(spec->g_offsets != nullptr, "bool g_offsets is NULL");
+  for (uint32_t q = 0; q < nq; q++) {
+    PLAN_REQUIRE(spec->c_offsets[q + 1] >= spec->c_offsets[q], "bool c_offsets not monotone");
+    PLAN_REQUIRE(spec->g_offsets[q + 1] >= spec->g_offsets[q], "bool g_offsets not monotone");
+  }
+  PLAN_REQUIRE(spec->c_offsets[nq] == spec->c_offsets[0] || (spec->c_term_ids && spec->c_group),
+               "bool c_term_ids/c_group is NULL");
+  PLAN_REQUIRE(spec->g_offsets[nq] == spec->g_offsets[0] || spec->g_kind, "bool g_kind is NULL");
+  for (uint32_t q = 0; q < nq; q++) {
+    const std::string in_q = " in bool query " + std::to_string(q);
+    const uint32_t t0 = spec->c_offsets[q], nt = spec->c_offsets[q + 1] - t0;
+    const uint32_t g0 = spec->g_offsets[q], ng = spec->g_offsets[q + 1] - g0;
+    uint32_t next = 0;  // the group a new group's first term must name
+    for (uint32_t i = 0; i < nt; i++) {
+      const uint32_t g = spec->c_group[t0 + i];
+      PLAN_REQUIRE(g < ng, "c_group names a group the query does not have" + in_q);
+      PLAN_REQUIRE(g == next || (next > 0 && g == next - 1), "c_group decreases or skips a group" + in_q);
+      if (g == next) next++;
+    }
+    PLAN_REQUIRE(next == ng, "a group without a term" + in_q);
+    for (uint32_t g = 0; g < ng; g++) {
+      const int32_t kind = spec->g_kind[g0 + g];
+      PLAN_REQUIRE(kind == SLG_BOOL_MUST || kind == SLG_BOOL_SHOULD || kind == SLG_BOOL_MUST_NOT,
+                   "unknown clause kind" + in_q);
+    }
+    PLAN_REQUIRE(!plans || !plans->q_min_match || plans->q_min_match[q] <= 1u,
+                 "q_min_match > 1 in the score plans of a bool batch (q_min_should states it)" + in_q);
+  }
+  for (uint32_t q = 0; q < nq; q++) {
+    if (spec->g_offsets[q + 1] - spec->g_offsets[q] > SLG_MAX_BOOL_GROUPS)
+      throw SlgError(SLG_ERR_UNSUPPORTED, "bool query " + std::to_string(q) + " has more than SLG_MAX_BOOL_GROUPS groups");
+    if (spec->c_offsets[q + 1] - spec->c_offsets[q] > SLG_MAX_BOOL_TERMS)
+      throw SlgError(SLG_ERR_UNSUPPORTED, "bool query " + std::to_string(q) + " has more than SLG_MAX_BOOL_TERMS clause terms");
+  }
+}
+
+void plan_bool(const std::vector<SegView> &segs, uint32_t nq, const slg_bool_spec &spec, BoolPlan &out) {
+  const uint32_t n_segs = (uint32_t)segs.size();
+  out.queries.assign(nq, slg::BoolQuery{});
+  out.terms.clear();
+  out.n_groups = 0;
+  if (nq == 0) return;
+  const uint32_t c_base = spec.c_offsets[0];
+  out.terms.reserve((size_t)(spec.c_offsets[nq] - c_base) * n_segs);
+  for (uint32_t q = 0; q < nq; q++) {
+    const uint32_t t0 = spec.c_offsets[q], nt = spec.c_offsets[q + 1] - t0;
+    const uint32_t g0 = spec.g_offsets[q], ng = spec.g_offsets[q + 1] - g0;
+    slg::BoolQuery &bq = out.queries[q];
+    bq.term_begin = t0 - c_base;
+    bq.n_terms = nt;
+    bq.min_should = ng && spec.q_min_should ? spec.q_min_should[q] : 0u;
+    out.n_groups += ng;
+    for (uint32_t g = 0; g < ng; g++) {
+      const int32_t kind = spec.g_kind[g0 + g];
+      (kind == SLG_BOOL_MUST ? bq.must_mask : kind == SLG_BOOL_MUST_NOT ? bq.must_not_mask : bq.should_mask) |= 1u << g;
+    }
+    // the row's order: MUST, MUST_NOT, SHOULD (stable inside a kind)
+    uint32_t order[SLG_MAX_BOOL_TERMS], n = 0;
+    for (const int32_t kind : {SLG_BOOL_MUST, SLG_BOOL_MUST_NOT, SLG_BOOL_SHOULD}) {
+      for (uint32_t i = 0; i < nt; i++)
+        if (spec.g_kind[g0 + spec.c_group[t0 + i]] == kind) order[n++] = i;
+      if (kind == SLG_BOOL_MUST) bq.n_must = n;
+      if (kind == SLG_BOOL_MUST_NOT) bq.n_must_not = n - bq.n_must;
+    }
+    for (uint32_t s = 0; s < n_segs; s++) {
+      const SegView &sh = segs[s];
+      for (uint32_t j = 0; j < nt; j++) {
+        const uint32_t i = order[j];
+        slg::BoolTerm bt{};
+        bt.group = spec.c_group[t0 + i];
+        const uint32_t tid = spec.c_term_ids[(size_t)(t0 + i) * n_segs + s];
+        if (tid != SLG_NO_TERM) {
+          PLAN_REQUIRE(tid < sh.n_terms, "term id out of range in bool query " + std::to_string(q));
+          bt.df = (uint32_t)(sh.term_offsets[tid + 1] - sh.term_offsets[tid]);
+          bt.off = sh.term_offsets[tid] + (uint64_t)slg::kListPad * tid;  // padded layout (SegDev)
+        }
+        out.terms.push_back(bt);
+      }
+    }
+  }
+}
+
 // ---- sort keys of numeric fast fields ----------------------------------------------------------
 namespace {
 inline uint64_t i64_key(int64_t v) { return (uint64_t)v ^ 0x8000000000000000ull; }

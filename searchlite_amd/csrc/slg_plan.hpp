@@ -125,6 +125,21 @@ struct RescorePlan {
 void plan_rescore(const std::vector<SegView> &segs, uint32_t nq, uint32_t k, const slg_rescore_spec &spec,
                   RescorePlan &out);
 
+// ---- boolean queries (slg_batch_prepare_bool) ----
+// The checks of a bool spec that need no index (throws SlgError): a NULL spec or array, offsets that decrease,
+// a c_group that decreases, skips a number or names a group the query does not have, a group without a term,
+// an unknown kind, q_min_match > 1 in the batch's score plans (SLG_ERR_INVALID, reported first); more than
+// SLG_MAX_BOOL_GROUPS groups or SLG_MAX_BOOL_TERMS clause terms in a query (SLG_ERR_UNSUPPORTED).
+void check_bool(const slg_bool_spec *spec, uint32_t nq, const slg_score_plans *plans);
+// The clause tables of a checked spec against the segments (slg::BoolQuery / BoolTerm: slg_desc.hpp).
+// Throws SLG_ERR_INVALID for a term id out of range.
+struct BoolPlan {
+  std::vector<slg::BoolQuery> queries;  // [nq]
+  std::vector<slg::BoolTerm> terms;     // [total x n_segs], a row per (query, segment)
+  uint32_t n_groups = 0;                // groups of the whole batch (0: no query has a clause table)
+};
+void plan_bool(const std::vector<SegView> &segs, uint32_t nq, const slg_bool_spec &spec, BoolPlan &out);
+
 // Throws SlgError (SLG_ERR_INVALID / SLG_ERR_UNSUPPORTED) on malformed input.
 void plan_batch(const std::vector<SegView> &segs, const slg_tuning &tune, const BatchIn &in, Plan &out);
 

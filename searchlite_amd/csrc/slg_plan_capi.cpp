@@ -164,4 +164,35 @@ int slgp_cursor_key(uint32_t n_parts, const int *kind, const int32_t *order, con
   }
 }
 
+// the host side of slg_batch_prepare_bool: check_bool, then plan_bool against the segments.  queries: nq x 8
+// words (slg::BoolQuery); terms: room for terms_cap entries of 4 words (slg::BoolTerm: off low, off high, df,
+// group), filled when the tables fit; *n_terms: the entries the tables have.  0, or a negative error code (err filled)
+int slgp_plan_bool(const slgp_segment *segs, uint32_t n_segs, uint32_t nq, const slg_bool_spec *spec,
+                   const slg_score_plans *plans, uint32_t *queries, uint32_t *terms, uint32_t terms_cap,
+                   uint32_t *n_terms, char *err, uint32_t err_len) {
+  try {
+    slgplan::check_bool(spec, nq, plans);
+    std::vector<slgplan::SegView> views(n_segs);
+    for (uint32_t s = 0; s < n_segs; s++) {
+      views[s].n_docs = segs[s].n_docs;
+      views[s].n_terms = segs[s].n_terms;
+      views[s].term_offsets = segs[s].term_offsets;
+    }
+    slgplan::BoolPlan bp;
+    slgplan::plan_bool(views, nq, *spec, bp);
+    static_assert(sizeof(slg::BoolQuery) == 32 && sizeof(slg::BoolTerm) == 16, "the words the caller reads");
+    if (queries && nq) std::memcpy(queries, bp.queries.data(), (size_t)nq * sizeof(slg::BoolQuery));
+    if (n_terms) *n_terms = (uint32_t)bp.terms.size();
+    if (terms && bp.terms.size() <= terms_cap && !bp.terms.empty())
+      std::memcpy(terms, bp.terms.data(), bp.terms.size() * sizeof(slg::BoolTerm));
+    return SLG_OK;
+  } catch (const slgplan::SlgError &e) {
+    if (err && err_len) {
+      std::strncpy(err, e.what(), err_len - 1);
+      err[err_len - 1] = 0;
+    }
+    return e.code;
+  }
+}
+
 }  // extern "C"

@@ -328,6 +328,20 @@ class GpuIndex:
         finally:
             b.close()
 
+    def search_batch_bool(self, q_offsets, q_terms, q_weights, k: int, clauses, sort=None, strategy: int = Wand,
+                          q_filter=None, want_stats: bool = False, **plans):
+        """Batch search with boolean clauses (slg_batch_prepare_bool).  clauses: a dict with c_offsets [nq + 1],
+        c_terms ([total, n_segs]), c_group [total], g_offsets [nq + 1], g_kind (BOOL_MUST / _SHOULD / _MUST_NOT per
+        group) and optionally q_min_should (a number or one per query); sort: None = score order, else as
+        search_sorted; **plans: the score plan arrays of prepare().
+        -> (doc, seg, score, count[, stats]) in score order, (doc, seg, score, count[, stats], matched) sorted."""
+        b = self.prepare(q_offsets, q_terms, q_weights, k, strategy, q_filter, sort=sort, clauses=clauses, **plans)
+        try:
+            b.run()
+            return b.fetch(want_stats) + ((b.matched_counts(),) if sort is not None else ())
+        finally:
+            b.close()
+
     def search_sorted(self, q_offsets, q_terms, q_weights, k: int, sort, strategy: int = Wand, q_filter=None,
                       **plans):
         """Field-sorted batch search (slg_batch_prepare_sorted).  sort: [(field, order)], field = a sort field id
@@ -360,7 +374,7 @@ class GpuIndex:
                 q_leaf_offsets=None, leaf_group=None, q_group_offsets=None, group_plan=None,
                 group_tie=None, q_node_offsets=None, node_kind=None, node_tie=None, node_parent=None,
                 q_min_match=None, sort=None, cursors=None, hybrid=False, aggs=None,
-                rescore=None) -> "PreparedBatch":
+                rescore=None, clauses=None) -> "PreparedBatch":
         """q_leaf / q_plan / q_tie / q_nleaves: score plans; leaf_group / group_plan / group_tie with
         their per-query offsets: two-level plans; q_node_offsets / node_kind / node_tie / node_parent:
         trees of any shape, node by node in pre-order (slg_batch_prepare_plans, slg_score_plans);
@@ -369,11 +383,12 @@ class GpuIndex:
         slg_batch_prepare_after; hybrid: the text side of a hybrid text + vector search ->
         slg_batch_prepare_hybrid (PreparedBatch.hybrid_device); aggs: an N.AggSpec or aggs.AggPlan ->
         slg_batch_prepare_aggs (PreparedBatch.aggs); rescore: the dict of search_rescore ->
-        slg_batch_prepare_rescore (PreparedBatch.rescore_details)."""
+        slg_batch_prepare_rescore (PreparedBatch.rescore_details); clauses: the dict of search_batch_bool ->
+        slg_batch_prepare_bool (score order, or with sort)."""
         return PreparedBatch(self, q_offsets, q_terms, q_weights, k, strategy, q_filter,
                              q_leaf, q_plan, q_tie, q_nleaves, q_leaf_offsets, leaf_group,
                              q_group_offsets, group_plan, group_tie, q_node_offsets, node_kind, node_tie, node_parent,
-                             q_min_match, sort, cursors, hybrid, aggs, rescore)
+                             q_min_match, sort, cursors, hybrid, aggs, rescore, clauses)
 
     def search_plan(self, q_offsets, q_terms, q_weights, k: int, q_leaf=None, q_plan=None,
                     q_tie=None, q_nleaves=None, strategy: int = Wand, q_filter=None, **tree):
@@ -689,6 +704,23 @@ def rescore_spec(rescore: dict, nq: int):
     return N.RescoreSpec(*[_ptr(a) for a in keep]), keep
 
 
+def bool_spec(clauses: dict, nq: int):
+    """The dict of GpuIndex.search_batch_bool as (N.BoolSpec, the arrays it points into)."""
+    def arr(name, dtype, per_query=False):
+        a = clauses.get(name)
+        if a is None:
+            return None
+        a = np.asarray(a, dtype=dtype)
+        if per_query and a.ndim == 0:
+            a = np.full(nq, a, dtype=dtype)
+        return np.ascontiguousarray(a)
+    keep = [arr("c_offsets", np.uint32), arr("c_terms", np.uint32), arr("c_group", np.uint32),
+            arr("g_offsets", np.uint32), arr("g_kind", np.int32), arr("q_min_should", np.uint32, True)]
+    assert keep[0] is not None and len(keep[0]) == nq + 1 and keep[3] is not None and len(keep[3]) == nq + 1
+    assert keep[5] is None or len(keep[5]) == nq
+    return N.BoolSpec(*[_ptr(a) for a in keep]), keep
+
+
 def sort_cursor(cursor, sort=None) -> "N.SortCursor":
     """None (a first page), an N.SortCursor, or (values, segment_ord, doc_id) -> slg_sort_cursor.  values: one
     per sort part (score order: one, the score): an int is an i64 value, a float an f64 value (or, on a
@@ -720,7 +752,7 @@ class PreparedBatch:
                  q_filter=None, q_leaf=None, q_plan=None, q_tie=None, q_nleaves=None,
                  q_leaf_offsets=None, leaf_group=None, q_group_offsets=None, group_plan=None,
                  group_tie=None, q_node_offsets=None, node_kind=None, node_tie=None, node_parent=None,
-                 q_min_match=None, sort=None, cursors=None, hybrid=False, aggs=None, rescore=None):
+                 q_min_match=None, sort=None, cursors=None, hybrid=False, aggs=None, rescore=None, clauses=None):
         self.index = index
         self._lib = index._lib
         q_offsets = np.ascontiguousarray(q_offsets, dtype=np.uint32)
@@ -754,7 +786,17 @@ class PreparedBatch:
         assert not (hybrid and (sort is not None or cursors is not None)), "a hybrid batch takes no sort or cursor"
         self.agg_spec = getattr(aggs, "spec", aggs)  # (an aggs.AggPlan carries its N.AggSpec)
         self.is_rescore = rescore is not None
-        if rescore is not None:
+        self.is_bool = clauses is not None
+        if clauses is not None:
+            # (the library's other prepare calls take no bool spec: the refusal is made here with its code)
+            if hybrid or cursors is not None or aggs is not None or rescore is not None:
+                raise N.SlgError(N.ERR_UNSUPPORTED, "boolean clauses are not built on cursor, hybrid, aggregation or rescore batches")
+            bspec, self._bool_keep = bool_spec(clauses, self.nq)
+            spec = None if sort is None else sort_spec(sort)
+            self._h = self._lib.slg_batch_prepare_bool(
+                index._h, self.nq, _ptr(q_offsets), _ptr(q_terms), _ptr(q_weights), C.addressof(plans),
+                opt(qf), None if spec is None else C.addressof(spec), C.addressof(bspec), k, strategy)
+        elif rescore is not None:
             # (the library's other prepare calls take no rescore spec: the refusal is made here with its code)
             if hybrid or cursors is not None or sort is not None or aggs is not None:
                 raise N.SlgError(N.ERR_UNSUPPORTED, "rescore is not built on sorted, cursor, hybrid or aggregation batches")

@@ -29,8 +29,11 @@
  * a flat Sum / DisMax plan over a window of up to SLG_MAX_RESCORE_WINDOW first-pass rows, every score_mode; in
  * score order only, not on sorted, cursor, hybrid, vector-only, aggregation, sharded or coalesced batches.
  * Boolean queries (slg_batch_prepare_bool): must / should / must_not groups of terms and minimum_should_match
- * over up to SLG_MAX_BOOL_GROUPS groups, in score order or a field sort; not nested, no phrases, not on
- * cursor, hybrid, aggregation, rescore, sharded or coalesced batches.
+ * over up to SLG_MAX_BOOL_GROUPS groups, in score order or a field sort; not nested, not on
+ * cursor, hybrid, aggregation, rescore, sharded or coalesced batches.  Phrase queries
+ * (slg_index_set_positions, slg_batch_prepare_phrase): phrase groups with a slop and per-field variants beside
+ * the term groups of a bool batch, under the same limits; one term per phrase position (no position
+ * alternatives), not in rescore queries.
  */
 #ifndef SEARCHLITE_GPU_H
 #define SEARCHLITE_GPU_H
@@ -981,8 +984,9 @@ int slg_search_batch_hybrid(slg_index *index, uint32_t nq, const uint32_t *q_off
  * The rescore queries come in the CSR form of the first pass (q_offsets [nq + 1], q_term_ids [total x n_segs],
  * q_weights [total]) with the flat plan arrays of slg_batch_prepare_plan (each may be NULL, same defaults),
  * q_min_match [nq] or NULL, q_window [nq], and q_mode [nq] or NULL (total).  Rescore queries whose score tree
- * has more than one level of Sum / DisMax over the leaves, function scores and phrases are not accepted by
- * this form: the caller keeps such requests on the CPU scorer.
+ * has more than one level of Sum / DisMax over the leaves, function scores and phrases (a rescore query takes no
+ * phrase spec; phrases of the first pass: slg_batch_prepare_phrase) are not accepted by this form: the caller
+ * keeps such requests on the CPU scorer.
  *
  * slg_batch_prepare_rescore is slg_batch_prepare_plans plus the spec; the batch goes through slg_batch_run /
  * _fetch / _device_results / _set_stream as any batch.  slg_batch_run enqueues the rescore kernel behind the
@@ -1073,9 +1077,9 @@ int slg_search_batch_rescore(slg_index *index, uint32_t nq, const uint32_t *q_of
  * kind, a term id out of range, q_min_match > 1 in the plans.  SLG_ERR_UNSUPPORTED (CPU scorer): more than
  * SLG_MAX_BOOL_GROUPS groups or SLG_MAX_BOOL_TERMS clause terms in a query.  slg_batch_run_sharded* and
  * slg_batch_fetch_sharded refuse a bool batch with SLG_ERR_UNSUPPORTED.  Not built (CPU scorer): nested matchers
- * (a bool or dis_max as a child of bool), phrases, bool.filter other than through q_filter, and clause tables
+ * (a bool or dis_max as a child of bool), bool.filter other than through q_filter, and clause tables
  * on cursor, hybrid, aggregation, rescore, sharded and coalesced batches (none of their prepare calls takes a
- * bool spec).
+ * bool spec).  Phrase children of a bool and the query string's quoted phrases: slg_batch_prepare_phrase below.
  * --------------------------------------------------------------------------------------------------------- */
 #define SLG_BOOL_MUST 0
 #define SLG_BOOL_SHOULD 1
@@ -1100,6 +1104,98 @@ int slg_search_batch_bool(slg_index *index, uint32_t nq, const uint32_t *q_offse
                           const slg_bool_spec *spec, uint32_t k, int strategy, uint32_t *out_doc, uint32_t *out_seg,
                           float *out_score, uint32_t *out_count, slg_stats *stats_or_null,
                           uint64_t *out_matched_or_null);
+
+/* ---------------------------------------------------------------------------------------------------------
+ * Phrase queries: `"olive oil" pasta`, match_phrase with a slop, and Phrase children of a bool.  The reference
+ * treats a phrase as a pure filter: QueryNode::Phrase scores nothing (query/planner.rs:622-635) and a query
+ * string's phrase_groups are required, unscored groups (api/reader.rs:1502-1506).  So a phrase batch is a bool
+ * batch (above) whose clause table has one more kind of group.
+ *
+ * POSITIONS.  slg_index_set_positions attaches the positions of segment seg's postings: pos_offsets is
+ * uint64_t[P + 1] over the segment's P postings in the order of doc_ids / tfs (unpadded), positions is
+ * uint32_t[pos_offsets[P]]; posting i has positions[pos_offsets[i] .. pos_offsets[i + 1]).  Host arrays are
+ * borrowed for the call only.  The call builds the next index state, as every update call does; batches already
+ * prepared keep the state — and the positions — they were prepared on.  slg_index_update_deleted keeps a
+ * segment's positions, slg_index_remove_segment drops that segment's, slg_index_add_segment gives the new
+ * segment none, and NULL, NULL removes them.  A segment without positions behaves as the reference's
+ * keep_positions = false: every posting has an empty position list, so no phrase holds any doc there (not an
+ * error).  Checked on the host before any device work.  SLG_ERR_INVALID: no such segment, one array NULL and
+ * the other not, pos_offsets[0] != 0, offsets that decrease, positions that decrease inside a posting, a
+ * position >= 2^31 (the reference does its gap arithmetic in i32).  SLG_ERR_UNSUPPORTED: more than 2^32 - 1
+ * positions in the segment (told from the offsets, before a position is read).
+ *
+ * PHRASE GROUPS AND VARIANTS (build_phrase_runtimes, phrase_matches, api/reader.rs:1584-1720).  A phrase group
+ * has a slop and zero or more VARIANTS, one per field the phrase is looked up in.  A variant is an ordered row
+ * of n >= 1 terms, one per phrase position.  (More than one alternative term per position — synonym analyzers —
+ * is not built: the caller keeps such requests on the CPU.)  In segment s a variant is DROPPED if any of its
+ * terms is SLG_NO_TERM there or has df 0.  A group holds a doc iff any surviving variant matches it; a group
+ * with no surviving variant holds nothing.
+ *
+ * matches_phrase (query/phrase.rs:4-48).  Every term of the variant must have a posting of the doc, and that
+ * posting must have at least one position: a posting with an empty position list fails the variant, also for
+ * n = 1.  For n = 1 that is all.  For n >= 2 the variant matches iff positions p0 < p1 < ... < p(n-1) exist,
+ * p_i taken from term i's position list of the doc, with sum(p_i - p_(i-1) - 1) <= slop.  The sum telescopes:
+ * p(n-1) - p0 <= slop + n - 1 over strictly increasing chains.  The same list may appear twice ("a a");
+ * strictness then demands two different positions.  Positions of one posting are non-decreasing.
+ *
+ * WHERE THE GROUP GOES.  Into the clause table of a bool batch, with the same three kinds and the same formula:
+ * a candidate — a doc of a scored list — is accepted iff every MUST group (term or phrase) holds it, no
+ * MUST_NOT group holds it, and at least q_min_should SHOULD groups (term or phrase) hold it.  A query string
+ * (reader.rs:1490-1518): phrases are MUST phrase groups, words are SHOULD term groups with q_min_should =
+ * minimum_should_match.unwrap_or(1), not-terms are MUST_NOT term groups.  Bool with Term / Phrase children
+ * (:1527-1563): as a bool batch, plus phrase groups of the child's kind.  Only docs of the scored lists are
+ * candidates: a request without scored terms stays on the CPU.  Scores are the first pass's, bit for bit.  A
+ * query without any group is untouched; such queries mix with others in a batch.
+ *
+ * THE SPEC is CSR, three levels deep.  The phrases of query q are p_offsets[q] .. p_offsets[q + 1] - 1 of p_kind
+ * (SLG_BOOL_*) and p_slop; the variants of phrase p are v_offsets[p] .. v_offsets[p + 1] - 1; the terms of
+ * variant v are rows t_offsets[v] .. t_offsets[v + 1] - 1 of t_term_ids (one id per segment, as q_term_ids), in
+ * phrase order.  The term groups come in the bool spec, or bool_or_null is NULL: none.  In a query's clause
+ * table the phrase groups are numbered after its term groups; term groups plus phrase groups <=
+ * SLG_MAX_BOOL_GROUPS.  q_min_should [nq] or NULL (= 0) counts over both; when both specs are given the bool
+ * spec's q_min_should must be NULL — one place states it, as with q_min_match, which must be NULL, 0 or 1.
+ *
+ * slg_batch_prepare_phrase is slg_batch_prepare_bool with the phrase spec: planned exactly as a bool batch,
+ * run / fetch / matched counts / set_stream as one, the stats contract (scored_docs counts accepted docs) is
+ * the bool batch's.  slg_batch_run enqueues ONE kernel between the scoring kernel and the select; it evaluates
+ * the whole table, term groups and phrase groups.  Terms and positions are resolved against the index state
+ * the batch was prepared on.  slg_search_batch_phrase is the one-call form.
+ *
+ * Errors, all before an index state is looked at.  SLG_ERR_INVALID: a NULL phrase spec or array, whatever a
+ * bool batch refuses in the bool spec, a q_min_should in the bool spec, offsets that decrease, a variant
+ * without a term, an unknown kind, a term id out of range, q_min_match > 1.  SLG_ERR_UNSUPPORTED (CPU scorer):
+ * more than SLG_MAX_PHRASE_TERMS terms in a variant, SLG_MAX_PHRASE_VARIANTS variants in a phrase,
+ * SLG_MAX_PHRASE_QUERY_TERMS variant terms in a query, a slop above SLG_MAX_PHRASE_SLOP, too many groups.
+ * slg_batch_run_sharded* and slg_batch_fetch_sharded refuse a phrase batch with SLG_ERR_UNSUPPORTED.  Not built
+ * (CPU scorer): phrases in rescore queries, position alternatives, nested matchers, and phrase batches on
+ * cursor, hybrid, aggregation, rescore, sharded and coalesced paths.
+ * --------------------------------------------------------------------------------------------------------- */
+int slg_index_set_positions(slg_index *index, uint32_t seg, const uint64_t *pos_offsets, const uint32_t *positions);
+
+#define SLG_MAX_PHRASE_TERMS 8u         /* terms of one variant */
+#define SLG_MAX_PHRASE_VARIANTS 8u      /* variants of one phrase */
+#define SLG_MAX_PHRASE_QUERY_TERMS 64u  /* variant terms of one query */
+#define SLG_MAX_PHRASE_SLOP (2147483647u - 8u)
+typedef struct slg_phrase_spec {
+  const uint32_t *p_offsets;    /* [nq + 1] into p_kind / p_slop */
+  const int32_t *p_kind;        /* [n_phrases] SLG_BOOL_* */
+  const uint32_t *p_slop;       /* [n_phrases] */
+  const uint32_t *v_offsets;    /* [n_phrases + 1] into the variants */
+  const uint32_t *t_offsets;    /* [n_variants + 1] into the rows of t_term_ids */
+  const uint32_t *t_term_ids;   /* [n_variant_terms x n_segs], rows as q_term_ids, SLG_NO_TERM where absent */
+  const uint32_t *q_min_should; /* [nq] or NULL (= 0), over term and phrase SHOULD groups */
+} slg_phrase_spec;
+slg_batch *slg_batch_prepare_phrase(slg_index *index, uint32_t nq, const uint32_t *q_offsets,
+                                    const uint32_t *q_term_ids, const float *q_weights,
+                                    const slg_score_plans *plans_or_null, const int32_t *q_filter_or_null,
+                                    const slg_sort_spec *sort_or_null, const slg_bool_spec *bool_or_null,
+                                    const slg_phrase_spec *phrases, uint32_t k, int strategy);
+int slg_search_batch_phrase(slg_index *index, uint32_t nq, const uint32_t *q_offsets, const uint32_t *q_term_ids,
+                            const float *q_weights, const slg_score_plans *plans_or_null,
+                            const int32_t *q_filter_or_null, const slg_sort_spec *sort_or_null,
+                            const slg_bool_spec *bool_or_null, const slg_phrase_spec *phrases, uint32_t k,
+                            int strategy, uint32_t *out_doc, uint32_t *out_seg, float *out_score,
+                            uint32_t *out_count, slg_stats *stats_or_null, uint64_t *out_matched_or_null);
 
 #ifdef __cplusplus
 }

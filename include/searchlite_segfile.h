@@ -56,6 +56,18 @@ int slf_postings_decode(const uint8_t *post, size_t n_bytes, const uint64_t *off
                         uint64_t *blk_offsets, uint32_t *blk_max_doc, float *blk_max_tf,
                         uint32_t *blk_size, float *max_tf);
 
+/*
+ * The positions pass 2 skips (index/postings.rs:176-183: per posting a count, then the deltas of its positions,
+ * the first from 0), for phrase queries: pos_offsets[total_postings + 1] is a CSR over the postings in the order
+ * of doc_ids / tfs, positions[pos_offsets[total_postings]] the absolute positions.  A list written without
+ * positions gives empty position lists.  Call it once with positions NULL (pos_offsets may be NULL too) for
+ * *total_positions, then with arrays of that size; positions_cap is the room in positions (SLF_ERR_INVALID if
+ * it is too small).  SLF_ERR_FORMAT when a posting's positions run past 2^32 - 1.
+ */
+int slf_postings_decode_positions(const uint8_t *post, size_t n_bytes, const uint64_t *offsets, uint32_t n_terms,
+                                  uint64_t *pos_offsets, uint32_t *positions, uint64_t positions_cap,
+                                  uint64_t *total_positions);
+
 /* util/varint.rs:5-16 / :31-48 — exposed for the tests of the reference's own roundtrip values.
  * slf_varint_write returns the bytes written (<= 10); slf_varint_read_u32 returns the bytes
  * consumed or a negative error ("varint too long" past 5 bytes, as read_u32_var). */

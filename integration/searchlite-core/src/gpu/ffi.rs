@@ -76,6 +76,10 @@ pub const SLG_AGG_STATS: i32 = 3;
     pub c_offsets: *const u32, pub c_term_ids: *const u32, pub c_group: *const u32, pub g_offsets: *const u32,
     pub g_kind: *const i32, pub q_min_should: *const u32,
 }
+#[repr(C)] pub struct slg_phrase_spec {
+    pub p_offsets: *const u32, pub p_kind: *const i32, pub p_slop: *const u32, pub v_offsets: *const u32,
+    pub t_offsets: *const u32, pub t_term_ids: *const u32, pub q_min_should: *const u32,
+}
 #[repr(C)] pub struct slg_rescore_spec {
     pub q_offsets: *const u32, pub q_term_ids: *const u32, pub q_weights: *const c_float, pub q_leaf: *const u32,
     pub q_plan: *const i32, pub q_tie: *const c_float, pub q_nleaves: *const u32, pub q_min_match: *const u32,
@@ -296,7 +300,22 @@ extern "C" {
         sort: *const slg_sort_spec, spec: *const slg_bool_spec, k: u32, strategy: c_int, out_doc: *mut u32,
         out_seg: *mut u32, out_score: *mut c_float, out_count: *mut u32, stats: *mut slg_stats,
         out_matched: *mut u64) -> c_int;
+    // phrase queries: positions per segment, then slg_batch_prepare_bool plus the phrase spec (bool_spec may be null)
+    pub fn slg_index_set_positions(index: *mut slg_index, seg: u32, pos_offsets: *const u64, positions: *const u32) -> c_int;
+    pub fn slg_batch_prepare_phrase(index: *mut slg_index, nq: u32, q_offsets: *const u32, q_term_ids: *const u32,
+        q_weights: *const c_float, plans: *const slg_score_plans, q_filter: *const i32,
+        sort: *const slg_sort_spec, bool_spec: *const slg_bool_spec, phrases: *const slg_phrase_spec, k: u32,
+        strategy: c_int) -> *mut slg_batch;
+    pub fn slg_search_batch_phrase(index: *mut slg_index, nq: u32, q_offsets: *const u32, q_term_ids: *const u32,
+        q_weights: *const c_float, plans: *const slg_score_plans, q_filter: *const i32,
+        sort: *const slg_sort_spec, bool_spec: *const slg_bool_spec, phrases: *const slg_phrase_spec, k: u32,
+        strategy: c_int, out_doc: *mut u32, out_seg: *mut u32, out_score: *mut c_float, out_count: *mut u32,
+        stats: *mut slg_stats, out_matched: *mut u64) -> c_int;
 }
+pub const SLG_MAX_PHRASE_TERMS: u32 = 8;
+pub const SLG_MAX_PHRASE_VARIANTS: u32 = 8;
+pub const SLG_MAX_PHRASE_QUERY_TERMS: u32 = 64;
+pub const SLG_MAX_PHRASE_SLOP: u32 = 2147483639;
 pub const SLG_BOOL_MUST: i32 = 0;
 pub const SLG_BOOL_SHOULD: i32 = 1;
 pub const SLG_BOOL_MUST_NOT: i32 = 2;

@@ -36,6 +36,10 @@ MAX_RESCORE_WINDOW = 1024
 BOOL_MUST, BOOL_SHOULD, BOOL_MUST_NOT = 0, 1, 2
 MAX_BOOL_GROUPS = 32
 MAX_BOOL_TERMS = 64
+MAX_PHRASE_TERMS = 8
+MAX_PHRASE_VARIANTS = 8
+MAX_PHRASE_QUERY_TERMS = 64
+MAX_PHRASE_SLOP = 2147483647 - 8
 
 
 class SlgError(RuntimeError):
@@ -138,6 +142,13 @@ class BoolSpec(C.Structure):
     minimum_should_match per query)."""
     _fields_ = [("c_offsets", C.c_void_p), ("c_term_ids", C.c_void_p), ("c_group", C.c_void_p),
                 ("g_offsets", C.c_void_p), ("g_kind", C.c_void_p), ("q_min_should", C.c_void_p)]
+
+
+class PhraseSpec(C.Structure):
+    """slg_phrase_spec: the phrase groups of a phrase batch (CSR: phrases per query, variants per phrase, term
+    rows per variant; minimum_should_match per query over term and phrase groups)."""
+    _fields_ = [("p_offsets", C.c_void_p), ("p_kind", C.c_void_p), ("p_slop", C.c_void_p), ("v_offsets", C.c_void_p),
+                ("t_offsets", C.c_void_p), ("t_term_ids", C.c_void_p), ("q_min_should", C.c_void_p)]
 
 
 class Ticket(C.Structure):
@@ -285,6 +296,9 @@ def load():
         "slg_search_batch_rescore": (i32, [vp, u32, vp, vp, vp, vp, vp, vp, u32, i32, vp, vp, vp, vp, vp, vp, vp]),
         "slg_batch_prepare_bool": (vp, [vp, u32, vp, vp, vp, vp, vp, vp, vp, u32, i32]),
         "slg_search_batch_bool": (i32, [vp, u32, vp, vp, vp, vp, vp, vp, vp, u32, i32, vp, vp, vp, vp, vp, vp]),
+        "slg_index_set_positions": (i32, [vp, u32, vp, vp]),
+        "slg_batch_prepare_phrase": (vp, [vp, u32, vp, vp, vp, vp, vp, vp, vp, vp, u32, i32]),
+        "slg_search_batch_phrase": (i32, [vp, u32, vp, vp, vp, vp, vp, vp, vp, vp, u32, i32, vp, vp, vp, vp, vp, vp]),
     }
     for name, (res, args) in sigs.items():
         if os.environ.get("SLG_LIB_TAG") and not hasattr(L, name):

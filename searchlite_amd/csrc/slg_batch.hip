@@ -125,7 +125,7 @@ void slghost::release_batch_buffers(slg_batch *b, bool to_pool) {
                     &b->d_q_scored, &b->d_q_filter, &b->d_cand, &b->d_slice_cbeg, &b->d_slice_ccnt,
                     &b->d_out, &b->d_stamps, &b->d_blk_skip, &b->d_gather, &b->d_merged, &b->d_q_cand,
                     &b->d_hy_keys, &b->d_hy_work, &b->d_agg_desc, &b->d_agg_counts, &b->d_agg_stats,
-                    &b->d_rs_desc, &b->d_rs_side, &b->d_bool_desc};
+                    &b->d_rs_desc, &b->d_rs_side, &b->d_bool_desc, &b->d_phrase_desc};
   for (DevBuf *d : bufs) {
     if (!to_pool) d->pool = nullptr;
     d->release();
@@ -165,19 +165,21 @@ slg_batch *slg_batch_prepare_plan(slg_index *ix, uint32_t nq, const uint32_t *q_
 namespace {
 // slg_batch_prepare_plans, (sort != nullptr) slg_batch_prepare_sorted, (after) slg_batch_prepare_after, and
 // (hybrid) slg_batch_prepare_hybrid, (want_aggs) slg_batch_prepare_aggs, (want_rescore) slg_batch_prepare_rescore,
-// (want_bool) slg_batch_prepare_bool
+// (want_bool) slg_batch_prepare_bool, (phrases) slg_batch_prepare_phrase: want_bool with a bool spec or nullptr
 slg_batch *prepare_impl(slg_index *ix, uint32_t nq, const uint32_t *q_offsets, const uint32_t *q_term_ids,
                         const float *q_weights, const slg_score_plans *plans, const int32_t *q_filter,
                         const slg_sort_spec *sort, uint32_t k, int strategy, bool after = false,
                         const slg_sort_cursor *q_cursor = nullptr, bool hybrid = false,
                         const slg_agg_spec *aggs = nullptr, bool want_aggs = false,
                         const slg_rescore_spec *rescore = nullptr, bool want_rescore = false,
-                        const slg_bool_spec *boolean = nullptr, bool want_bool = false) {
+                        const slg_bool_spec *boolean = nullptr, bool want_bool = false,
+                        const slg_phrase_spec *phrases = nullptr, bool want_phrase = false) {
   slg_batch *b = nullptr;
   int rc = guarded([&] {
     if (want_aggs) agg_check_spec(aggs);  // (what needs no index comes first, as every argument check)
     if (want_rescore) slgplan::check_rescore(rescore, nq, k);
-    if (want_bool) slgplan::check_bool(boolean, nq, plans);
+    if (want_phrase) slgplan::check_phrase(boolean, phrases, nq, plans);
+    else if (want_bool) slgplan::check_bool(boolean, nq, plans);
     SLG_REQUIRE(ix != nullptr, "index is NULL");
     SLG_REQUIRE(!after || q_cursor != nullptr, "q_cursor is NULL");
     if (sort) {  // (checked before planning: the planner never sees a sort spec it cannot run)
@@ -201,6 +203,7 @@ slg_batch *prepare_impl(slg_index *ix, uint32_t nq, const uint32_t *q_offsets, c
       views[s].n_terms = sh.n_terms;
       views[s].term_offsets = sh.store->term_offsets.data();
       views[s].champ = sh.champ.empty() ? nullptr : sh.champ.data();
+      views[s].has_positions = s < snap->positions.size() && snap->positions[s] != nullptr;
     }
     slgplan::BatchIn in;
     in.nq = nq;
@@ -264,7 +267,9 @@ slg_batch *prepare_impl(slg_index *ix, uint32_t nq, const uint32_t *q_offsets, c
     slgplan::RescorePlan rescore_plan;  // (against the same snapshot, before any device work)
     if (want_rescore) slgplan::plan_rescore(views, nq, k, *rescore, rescore_plan);
     slgplan::BoolPlan bool_plan;
-    if (want_bool) slgplan::plan_bool(views, nq, *boolean, bool_plan);
+    slgplan::PhrasePlan phrase_plan;
+    if (want_phrase) slgplan::plan_phrase(views, nq, boolean, *phrases, phrase_plan);
+    else if (want_bool) slgplan::plan_bool(views, nq, *boolean, bool_plan);
 
     DeviceGuard g(ix->device);
     b = new slg_batch();
@@ -378,7 +383,12 @@ slg_batch *prepare_impl(slg_index *ix, uint32_t nq, const uint32_t *q_offsets, c
     b->d_out_count = R.count(b->d_out.as<uint32_t>());
     if (aggs) agg_attach(b, *aggs);
     if (want_rescore) rescore_attach(b, rescore_plan);
-    if (want_bool) bool_attach(b, bool_plan);
+    if (want_phrase) {
+      bool_attach(b, phrase_plan.bools);
+      phrase_attach(b, phrase_plan);
+    } else if (want_bool) {
+      bool_attach(b, bool_plan);
+    }
     {
       std::lock_guard<std::mutex> lk(ix->mu);
       ix->live.push_back(b);
@@ -522,7 +532,10 @@ int slg_batch_run(slg_batch *b) {
       launch_score(sp, score_kind, st);
       if (ev) SLG_HIP(hipEventRecord(ev->second, st));
     }
-    if (b->boolean) bool_launch(b, st);  // (in front of the select: the regions hold accepted candidates only)
+    // (in front of the select: the regions hold accepted candidates only; a phrase batch launches its own
+    //  kernel alone, which evaluates the term groups too)
+    if (b->phrase) phrase_launch(b, st);
+    else if (b->boolean) bool_launch(b, st);
     if (b->sorted) {  // (also without slices: every row is empty, every matched count 0)
       slg::SortedSelectParams sp{};
       fill_select(sp, b);
@@ -866,6 +879,24 @@ int slg_search_batch_bool(slg_index *ix, uint32_t nq, const uint32_t *q_offsets,
                           slg_stats *stats, uint64_t *out_matched) {
   return run_to_host(slg_batch_prepare_bool(ix, nq, q_offsets, q_term_ids, q_weights, plans, q_filter, sort, spec, k,
                                             strategy),
+                     out_doc, out_seg, out_score, out_count, stats, out_matched, nullptr);
+}
+
+slg_batch *slg_batch_prepare_phrase(slg_index *ix, uint32_t nq, const uint32_t *q_offsets, const uint32_t *q_term_ids,
+                                    const float *q_weights, const slg_score_plans *plans, const int32_t *q_filter,
+                                    const slg_sort_spec *sort, const slg_bool_spec *boolean,
+                                    const slg_phrase_spec *phrases, uint32_t k, int strategy) {
+  return prepare_impl(ix, nq, q_offsets, q_term_ids, q_weights, plans, q_filter, sort, k, strategy, false, nullptr,
+                      false, nullptr, false, nullptr, false, boolean, true, phrases, true);
+}
+
+int slg_search_batch_phrase(slg_index *ix, uint32_t nq, const uint32_t *q_offsets, const uint32_t *q_term_ids,
+                            const float *q_weights, const slg_score_plans *plans, const int32_t *q_filter,
+                            const slg_sort_spec *sort, const slg_bool_spec *boolean, const slg_phrase_spec *phrases,
+                            uint32_t k, int strategy, uint32_t *out_doc, uint32_t *out_seg, float *out_score,
+                            uint32_t *out_count, slg_stats *stats, uint64_t *out_matched) {
+  return run_to_host(slg_batch_prepare_phrase(ix, nq, q_offsets, q_term_ids, q_weights, plans, q_filter, sort,
+                                              boolean, phrases, k, strategy),
                      out_doc, out_seg, out_score, out_count, stats, out_matched, nullptr);
 }
 

@@ -189,6 +189,43 @@ struct BoolQuery {
 constexpr uint32_t kBoolMaxGroups = 32;  // = SLG_MAX_BOOL_GROUPS
 constexpr uint32_t kBoolMaxTerms = 64;   // = SLG_MAX_BOOL_TERMS
 
+// ---- phrase queries (slg_batch_prepare_phrase; kernel: slg_phrase.hpp, planner: slg_plan.cpp) --------
+// A phrase batch carries the bool tables above for its term groups (BoolQuery's masks and min_should cover
+// the phrase groups too: they are numbered behind the query's term groups) and three tables of its own.
+// The variants of query q are vars[var_begin .. var_begin + n_vars), the same for every segment, ordered
+// MUST groups first, MUST_NOT second, SHOULD last (stable) with a group's variants side by side.  The
+// variant terms of query q in segment s are pterms[term_begin * n_segs + s * n_terms + i]: one contiguous
+// row per (query, segment) in the spec's order; a variant's terms are row[t_begin .. t_begin + n).  A
+// variant that is DROPPED in a segment (a term absent or with df 0 there, or the segment has no positions)
+// has df 0 in every one of its terms of that segment's row, so its first term tells.
+struct PosSegDev {          // per segment of an index state (slg_index_set_positions)
+  const uint32_t *offs;     // [P + 1] first position of each posting, in the UNPADDED posting order; or nullptr
+  const uint32_t *pos;      // [offs[P]] positions, non-decreasing inside a posting
+};
+struct PhraseTerm {
+  uint64_t off;    // posting offset inside the segment arrays (padded layout, as BoolTerm::off)
+  uint64_t ubase;  // the list's first posting in the unpadded order (= term_offsets[term]): PosSegDev::offs index
+  uint32_t df;     // list length; 0: the variant is dropped in this segment
+  uint32_t pad;
+};
+struct PhraseVar {
+  uint32_t t_begin;  // first term of the variant inside the (query, segment) row
+  uint32_t n_last;   // bits 0-7: terms (1 .. kPhraseMaxTerms); bit 8: the last variant of its group
+  uint32_t group;    // the phrase's group inside its query (a bit of BoolQuery's masks)
+  uint32_t slop;
+};
+struct PhraseQuery {
+  uint32_t var_begin, n_vars;
+  uint32_t term_begin, n_terms;
+  uint32_t n_term_groups;  // groups 0 .. n_term_groups - 1 are term groups (BoolTerm rows), the rest phrases
+  uint32_t pad[3];
+};
+constexpr uint32_t kPhraseMaxTerms = 8;        // = SLG_MAX_PHRASE_TERMS (the kernel's unrolled cursors)
+constexpr uint32_t kPhraseMaxVariants = 8;     // = SLG_MAX_PHRASE_VARIANTS
+constexpr uint32_t kPhraseMaxQueryTerms = 64;  // = SLG_MAX_PHRASE_QUERY_TERMS
+constexpr uint32_t kPhraseMaxSlop = 0x7FFFFFFFu - kPhraseMaxTerms;  // = SLG_MAX_PHRASE_SLOP
+constexpr uint32_t kPositionEnd = 0x80000000u;  // positions are below it (the reference's gaps are i32)
+
 // ---- merge of per-shard results gathered over RCCL (merge_shards_kernel, slg_kernels.hpp) ----------
 struct ShardMergeParams {
   const uint32_t *doc;    // shard sh's rows start at doc + sh * arr_stride ([nq*k] each)

@@ -1,5 +1,5 @@
 // slg_host.hpp — what the host translation units of the C ABI share (slg_index.hip, slg_batch.hip,
-// slg_shard.hip, slg_rerank.hip, slg_vsearch.hip, slg_hybrid.hip, slg_aggs.hip, slg_rescore.hip, slg_bool.hip): the error plumbing, device memory, the host
+// slg_shard.hip, slg_rerank.hip, slg_vsearch.hip, slg_hybrid.hip, slg_aggs.hip, slg_rescore.hip, slg_bool.hip, slg_phrase.hip): the error plumbing, device memory, the host
 // structures behind the opaque handles and the small helpers several entry points use.  Private: not
 // installed, not part of include/.  No kernel header is included here — each unit includes the one
 // whose kernels it launches (slg_stage.hpp, slg_kernels.hpp, slg_rerank.hpp, slg_vsearch.hpp, slg_hybrid.hpp; the shard
@@ -357,6 +357,12 @@ struct AggFieldData {
   std::vector<std::shared_ptr<AggColumn>> per_seg;
 };
 
+// the positions of a segment's postings (slg_index_set_positions): shared by the states that hold them
+struct PosStore {
+  DevBuf offs;  // u32[P + 1] in the unpadded posting order
+  DevBuf pos;   // u32[offs[P]]
+};
+
 // One immutable state of the index (see "index updates" in searchlite_gpu.h).  Batches hold the state
 // they were prepared on; the index holds the current one.
 struct IndexState {
@@ -373,6 +379,8 @@ struct IndexState {
   DevBuf d_reject_table;                               // the same table on the device
   std::map<int, std::shared_ptr<SortFieldData>> sort_fields;  // by id (ids are not reused)
   std::map<int, std::shared_ptr<AggFieldData>> agg_fields;    // by id (ids are not reused)
+  std::vector<std::shared_ptr<PosStore>> positions;           // [n_segs]; null = the segment has none
+  DevBuf d_pos_segs;                                          // slg::PosSegDev[n_segs]
   ~IndexState() {
     // kernels of already-destroyed batches, or rerank calls on the index stream, may still read the
     // tables: retiring a state is rare (one per update), so wait for the device once
@@ -504,6 +512,12 @@ struct slg_batch {
   bool boolean = false;
   uint32_t bool_groups = 0;  // groups of all queries (0: no query has a clause table, nothing is launched)
   DevBuf d_bool_desc;        // slg::BoolQuery[nq], then slg::BoolTerm rows per (query, segment)
+  // phrase batch (slg_batch_prepare_phrase): a bool batch (boolean is set, d_bool_desc holds the term groups'
+  // tables) whose clause tables also have phrase groups; phrase_filter_kernel runs in bool_filter_kernel's
+  // place (slg_phrase.hip)
+  bool phrase = false;
+  uint32_t phrase_vars = 0, phrase_terms = 0;  // entries of the two tables behind the PhraseQuery records
+  DevBuf d_phrase_desc;      // slg::PhraseQuery[nq], slg::PhraseVar[phrase_vars], slg::PhraseTerm[phrase_terms]
 };
 
 namespace slghost __attribute__((visibility("hidden"))) {
@@ -621,6 +635,9 @@ void rescore_launch(slg_batch *b, hipStream_t st);
 // behind the batch's scoring kernel, in front of its select
 void bool_attach(slg_batch *b, const slgplan::BoolPlan &bp);
 void bool_launch(slg_batch *b, hipStream_t st);
+// slg_phrase.hip: the same for a phrase batch, behind bool_attach; the launch in bool_launch's place
+void phrase_attach(slg_batch *b, const slgplan::PhrasePlan &pp);
+void phrase_launch(slg_batch *b, hipStream_t st);
 
 // slg_vsearch.hip: one vector search or hybrid call, checked against one state of the index ...
 struct VsCall {

@@ -271,6 +271,12 @@ void finish_state(slg_index *ix, IndexState &s) {
     vf.d_vsegs.alloc(std::max<size_t>(n_segs, 1) * sizeof(slg::VecSegDev), &ix->pool);
     if (n_segs) SLG_HIP(hipMemcpy(vf.d_vsegs.p, fv.data(), n_segs * sizeof(slg::VecSegDev), hipMemcpyHostToDevice));
   }
+  s.positions.resize(n_segs);  // (a new state of a new segment list: no positions where none were set)
+  std::vector<slg::PosSegDev> pd(n_segs);
+  for (size_t i = 0; i < n_segs; i++)
+    if (s.positions[i]) pd[i] = slg::PosSegDev{s.positions[i]->offs.as<uint32_t>(), s.positions[i]->pos.as<uint32_t>()};
+  s.d_pos_segs.alloc(std::max<size_t>(n_segs, 1) * sizeof(slg::PosSegDev), &ix->pool);
+  if (n_segs) SLG_HIP(hipMemcpy(s.d_pos_segs.p, pd.data(), n_segs * sizeof(slg::PosSegDev), hipMemcpyHostToDevice));
   std::vector<uint32_t> base(n_segs + 1, 0u);
   uint64_t acc = 0;
   for (size_t i = 0; i < n_segs; i++) {
@@ -301,6 +307,7 @@ std::unique_ptr<IndexState> copy_state(const IndexState &cur) {
   n->filters = cur.filters;
   n->sort_fields = cur.sort_fields;
   n->agg_fields = cur.agg_fields;
+  n->positions = cur.positions;
   for (auto &vf : cur.vfields) {  // the per-state table d_vsegs is rebuilt: own object, shared stores
     auto c = std::make_shared<VecFieldHost>();
     c->dim = vf->dim;
@@ -360,10 +367,13 @@ void reshape_per_segment(IndexState &ns, Op op) {
     af.second = std::move(nf);
   }
   for (auto &vf : ns.vfields) op(vf->per_seg);  // (the field objects of a new state are fresh copies)
+  op(ns.positions);  // (the state's own vector; the stores are shared)
 }
 
 size_t state_device_bytes(const IndexState &s) {
-  size_t n = s.d_segs.bytes + s.d_vsegs.bytes + s.d_reject_table.bytes + s.d_doc_base.bytes;
+  size_t n = s.d_segs.bytes + s.d_vsegs.bytes + s.d_reject_table.bytes + s.d_doc_base.bytes + s.d_pos_segs.bytes;
+  for (auto &ps : s.positions)
+    if (ps) n += ps->offs.bytes + ps->pos.bytes;
   for (auto &sh : s.segs) n += sh->device_bytes() + sh->store->device_bytes();
   for (auto &f : s.filters)
     if (f)
@@ -745,6 +755,32 @@ int slg_index_remove_sort_field(slg_index *ix, int sort_field_id) {
     update_state(ix, false, [&](const IndexState &cur, IndexState &ns) {
       SLG_REQUIRE(cur.sort_fields.count(sort_field_id) == 1, "unknown sort field id");
       ns.sort_fields.erase(sort_field_id);
+    });
+  });
+}
+
+// ---- positions of a segment's postings (phrase queries; index/postings.rs:176-183) ---------------
+int slg_index_set_positions(slg_index *ix, uint32_t seg, const uint64_t *pos_offsets, const uint32_t *positions) {
+  return guarded([&] {
+    SLG_REQUIRE(ix != nullptr, "index is NULL");
+    update_state(ix, false, [&](const IndexState &cur, IndexState &ns) {
+      SLG_REQUIRE(seg < cur.segs.size(), "no such segment");
+      ns.positions.resize(cur.segs.size());
+      if (!pos_offsets && !positions) {  // the segment is back to keep_positions = false
+        ns.positions[seg].reset();
+        return;
+      }
+      const uint64_t P = cur.segs[seg]->n_postings;
+      slgplan::check_positions(P, pos_offsets, positions);  // (host only, before any device work)
+      const uint64_t total = pos_offsets[P];
+      std::vector<uint32_t> offs(P + 1);
+      for (uint64_t i = 0; i <= P; i++) offs[i] = (uint32_t)pos_offsets[i];
+      auto store = std::make_shared<PosStore>();
+      store->offs.alloc((P + 1) * 4, &ix->pool);
+      store->pos.alloc(std::max<uint64_t>(total, 1) * 4, &ix->pool);
+      SLG_HIP(hipMemcpy(store->offs.p, offs.data(), (P + 1) * 4, hipMemcpyHostToDevice));
+      if (total) SLG_HIP(hipMemcpy(store->pos.p, positions, total * 4, hipMemcpyHostToDevice));
+      ns.positions[seg] = std::move(store);
     });
   });
 }

@@ -1060,6 +1060,169 @@ void plan_bool(const std::vector<SegView> &segs, uint32_t nq, const slg_bool_spe
   }
 }
 
+// ---- phrase queries ---------------------------------------------------------------------------------
+static_assert(slg::kPhraseMaxTerms == SLG_MAX_PHRASE_TERMS && slg::kPhraseMaxVariants == SLG_MAX_PHRASE_VARIANTS &&
+                  slg::kPhraseMaxQueryTerms == SLG_MAX_PHRASE_QUERY_TERMS && slg::kPhraseMaxSlop == SLG_MAX_PHRASE_SLOP,
+              "the kernel's unrolled cursors and span arithmetic and the ABI's limits");
+
+void check_positions(uint64_t n_postings, const uint64_t *pos_offsets, const uint32_t *positions) {
+  PLAN_REQUIRE(pos_offsets != nullptr, "pos_offsets is NULL");
+  PLAN_REQUIRE(pos_offsets[0] == 0, "pos_offsets does not start at 0");
+  for (uint64_t i = 0; i < n_postings; i++)
+    PLAN_REQUIRE(pos_offsets[i + 1] >= pos_offsets[i], "pos_offsets not monotone");
+  const uint64_t total = pos_offsets[n_postings];
+  if (total > 0xFFFFFFFFull)
+    throw SlgError(SLG_ERR_UNSUPPORTED, "more than 2^32 - 1 positions in a segment");
+  PLAN_REQUIRE(total == 0 || positions != nullptr, "positions is NULL");
+  for (uint64_t i = 0; i < n_postings; i++) {
+    uint32_t prev = 0;
+    for (uint64_t j = pos_offsets[i]; j < pos_offsets[i + 1]; j++) {
+      const uint32_t v = positions[j];
+      PLAN_REQUIRE(v < slg::kPositionEnd, "a position is >= 2^31 (posting " + std::to_string(i) + ")");
+      PLAN_REQUIRE(v >= prev, "positions decrease inside posting " + std::to_string(i));
+      prev = v;
+    }
+  }
+}
+
+void check_phrase(const slg_bool_spec *boolean, const slg_phrase_spec *spec, uint32_t nq, const slg_score_plans *plans) {
+  PLAN_REQUIRE(spec != nullptr, "phrase spec is NULL");
+  PLAN_REQUIRE(!boolean || boolean->q_min_should == nullptr,
+               "bool q_min_should beside a phrase spec (the phrase spec's q_min_should states it)");
+  if (nq != 0) {
+    PLAN_REQUIRE(spec->p_offsets != nullptr, "phrase p_offsets is NULL");
+    for (uint32_t q = 0; q < nq; q++)
+      PLAN_REQUIRE(spec->p_offsets[q + 1] >= spec->p_offsets[q], "phrase p_offsets not monotone");
+    const uint32_t p0 = spec->p_offsets[0], p1 = spec->p_offsets[nq];
+    if (p1 > p0) {
+      PLAN_REQUIRE(spec->p_kind && spec->p_slop, "phrase p_kind/p_slop is NULL");
+      PLAN_REQUIRE(spec->v_offsets != nullptr, "phrase v_offsets is NULL");
+      for (uint32_t p = p0; p < p1; p++)
+        PLAN_REQUIRE(spec->v_offsets[p + 1] >= spec->v_offsets[p], "phrase v_offsets not monotone");
+      const uint32_t v0 = spec->v_offsets[p0], v1 = spec->v_offsets[p1];
+      if (v1 > v0) {
+        PLAN_REQUIRE(spec->t_offsets != nullptr, "phrase t_offsets is NULL");
+        for (uint32_t v = v0; v < v1; v++) {
+          PLAN_REQUIRE(spec->t_offsets[v + 1] >= spec->t_offsets[v], "phrase t_offsets not monotone");
+          PLAN_REQUIRE(spec->t_offsets[v + 1] > spec->t_offsets[v], "a phrase variant without a term");
+        }
+        PLAN_REQUIRE(spec->t_term_ids != nullptr, "phrase t_term_ids is NULL");
+      }
+      for (uint32_t p = p0; p < p1; p++) {
+        const int32_t kind = spec->p_kind[p];
+        PLAN_REQUIRE(kind == SLG_BOOL_MUST || kind == SLG_BOOL_SHOULD || kind == SLG_BOOL_MUST_NOT,
+                     "unknown phrase kind (phrase " + std::to_string(p) + ")");
+      }
+    }
+    for (uint32_t q = 0; q < nq; q++)
+      PLAN_REQUIRE(!plans || !plans->q_min_match || plans->q_min_match[q] <= 1u,
+                   "q_min_match > 1 in the score plans of a phrase batch (q_min_should states it) in query " +
+                       std::to_string(q));
+  }
+  if (boolean) check_bool(boolean, nq, plans);
+  for (uint32_t q = 0; q < nq; q++) {
+    const std::string in_q = "phrase query " + std::to_string(q);
+    const uint32_t p0 = spec->p_offsets[q], p1 = spec->p_offsets[q + 1];
+    uint64_t q_terms = 0;
+    for (uint32_t p = p0; p < p1; p++) {
+      const uint32_t v0 = spec->v_offsets[p], v1 = spec->v_offsets[p + 1];
+      if (v1 - v0 > SLG_MAX_PHRASE_VARIANTS)
+        throw SlgError(SLG_ERR_UNSUPPORTED, in_q + " has a phrase of more than SLG_MAX_PHRASE_VARIANTS variants");
+      for (uint32_t v = v0; v < v1; v++) {
+        const uint32_t n = spec->t_offsets[v + 1] - spec->t_offsets[v];
+        if (n > SLG_MAX_PHRASE_TERMS)
+          throw SlgError(SLG_ERR_UNSUPPORTED, in_q + " has a variant of more than SLG_MAX_PHRASE_TERMS terms");
+        q_terms += n;
+      }
+      if (spec->p_slop[p] > SLG_MAX_PHRASE_SLOP)
+        throw SlgError(SLG_ERR_UNSUPPORTED, in_q + " has a slop above SLG_MAX_PHRASE_SLOP");
+    }
+    if (q_terms > SLG_MAX_PHRASE_QUERY_TERMS)
+      throw SlgError(SLG_ERR_UNSUPPORTED, in_q + " has more than SLG_MAX_PHRASE_QUERY_TERMS variant terms");
+    const uint32_t n_tg = boolean ? boolean->g_offsets[q + 1] - boolean->g_offsets[q] : 0u;
+    if ((uint64_t)n_tg + (p1 - p0) > SLG_MAX_BOOL_GROUPS)
+      throw SlgError(SLG_ERR_UNSUPPORTED, in_q + " has more than SLG_MAX_BOOL_GROUPS term and phrase groups");
+  }
+}
+
+void plan_phrase(const std::vector<SegView> &segs, uint32_t nq, const slg_bool_spec *boolean, const slg_phrase_spec &spec,
+                 PhrasePlan &out) {
+  const uint32_t n_segs = (uint32_t)segs.size();
+  if (boolean) {
+    plan_bool(segs, nq, *boolean, out.bools);
+  } else {
+    out.bools.queries.assign(nq, slg::BoolQuery{});
+    out.bools.terms.clear();
+    out.bools.n_groups = 0;
+  }
+  out.queries.assign(nq, slg::PhraseQuery{});
+  out.vars.clear();
+  out.terms.clear();
+  uint32_t term_begin = 0;
+  for (uint32_t q = 0; q < nq; q++) {
+    const uint32_t p0 = spec.p_offsets[q], np = spec.p_offsets[q + 1] - p0;
+    const uint32_t n_tg = boolean ? boolean->g_offsets[q + 1] - boolean->g_offsets[q] : 0u;
+    slg::BoolQuery &bq = out.bools.queries[q];
+    slg::PhraseQuery &pq = out.queries[q];
+    bq.min_should = (n_tg + np) && spec.q_min_should ? spec.q_min_should[q] : 0u;
+    out.bools.n_groups += np;
+    pq.n_term_groups = n_tg;
+    pq.var_begin = (uint32_t)out.vars.size();
+    pq.term_begin = term_begin;
+    // where each variant's terms start in the row (the spec's order), then the variants by kind
+    uint32_t t_begin[SLG_MAX_BOOL_GROUPS][SLG_MAX_PHRASE_VARIANTS], n_terms = 0;
+    for (uint32_t pi = 0; pi < np; pi++)
+      for (uint32_t v = spec.v_offsets[p0 + pi]; v < spec.v_offsets[p0 + pi + 1]; v++) {
+        t_begin[pi][v - spec.v_offsets[p0 + pi]] = n_terms;
+        n_terms += spec.t_offsets[v + 1] - spec.t_offsets[v];
+      }
+    pq.n_terms = n_terms;
+    for (const int32_t kind : {SLG_BOOL_MUST, SLG_BOOL_MUST_NOT, SLG_BOOL_SHOULD})
+      for (uint32_t pi = 0; pi < np; pi++) {
+        if (spec.p_kind[p0 + pi] != kind) continue;
+        const uint32_t g = n_tg + pi;
+        (kind == SLG_BOOL_MUST ? bq.must_mask : kind == SLG_BOOL_MUST_NOT ? bq.must_not_mask : bq.should_mask) |= 1u << g;
+        const uint32_t v0 = spec.v_offsets[p0 + pi], v1 = spec.v_offsets[p0 + pi + 1];
+        for (uint32_t v = v0; v < v1; v++) {
+          slg::PhraseVar pv{};
+          pv.t_begin = t_begin[pi][v - v0];
+          pv.n_last = (spec.t_offsets[v + 1] - spec.t_offsets[v]) | (v + 1 == v1 ? 0x100u : 0u);
+          pv.group = g;
+          pv.slop = spec.p_slop[p0 + pi];
+          out.vars.push_back(pv);
+        }
+      }
+    pq.n_vars = (uint32_t)out.vars.size() - pq.var_begin;
+    for (uint32_t s = 0; s < n_segs; s++) {
+      const SegView &sh = segs[s];
+      for (uint32_t pi = 0; pi < np; pi++)
+        for (uint32_t v = spec.v_offsets[p0 + pi]; v < spec.v_offsets[p0 + pi + 1]; v++) {
+          const uint32_t t0 = spec.t_offsets[v], n = spec.t_offsets[v + 1] - t0;
+          bool survives = sh.has_positions;  // (no positions: every posting's position list is empty)
+          slg::PhraseTerm row[SLG_MAX_PHRASE_TERMS];
+          for (uint32_t i = 0; i < n; i++) {
+            row[i] = slg::PhraseTerm{};
+            const uint32_t tid = spec.t_term_ids[(size_t)(t0 + i) * n_segs + s];
+            if (tid == SLG_NO_TERM) {
+              survives = false;
+              continue;
+            }
+            PLAN_REQUIRE(tid < sh.n_terms, "term id out of range in phrase query " + std::to_string(q));
+            row[i].ubase = sh.term_offsets[tid];
+            row[i].off = sh.term_offsets[tid] + (uint64_t)slg::kListPad * tid;  // padded layout (SegDev)
+            row[i].df = (uint32_t)(sh.term_offsets[tid + 1] - sh.term_offsets[tid]);
+            survives = survives && row[i].df != 0;
+          }
+          for (uint32_t i = 0; i < n; i++) {
+            if (!survives) row[i].df = 0;  // dropped in this segment: the kernel reads the first term's df
+            out.terms.push_back(row[i]);
+          }
+        }
+    }
+    term_begin += n_terms;
+  }
+}
+
 // ---- sort keys of numeric fast fields ----------------------------------------------------------
 namespace {
 inline uint64_t i64_key(int64_t v) { return (uint64_t)v ^ 0x8000000000000000ull; }

@@ -32,6 +32,7 @@ struct SegView {
   uint32_t n_docs = 0, n_terms = 0;
   const uint64_t *term_offsets = nullptr;  // [n_terms + 1] as given (unpadded)
   const float *champ = nullptr;            // [n_terms * kChampions] or nullptr (champions off)
+  bool has_positions = false;              // slg_index_set_positions was called for it (phrase batches)
 };
 
 // the caller's arrays (slg_batch_prepare_plans)
@@ -139,6 +140,31 @@ struct BoolPlan {
   uint32_t n_groups = 0;                // groups of the whole batch (0: no query has a clause table)
 };
 void plan_bool(const std::vector<SegView> &segs, uint32_t nq, const slg_bool_spec &spec, BoolPlan &out);
+
+// ---- phrase queries (slg_index_set_positions, slg_batch_prepare_phrase) ----
+// The checks of a segment's positions (throws SlgError): NULL arrays, a first offset other than 0, offsets that
+// decrease (SLG_ERR_INVALID); more than 2^32 - 1 positions (SLG_ERR_UNSUPPORTED; from the offsets alone, before a
+// position is read); positions that decrease inside a posting, a position >= 2^31 (SLG_ERR_INVALID).
+void check_positions(uint64_t n_postings, const uint64_t *pos_offsets, const uint32_t *positions);
+// The checks of a phrase spec (and the bool spec beside it, or nullptr) that need no index (throws SlgError).
+// SLG_ERR_INVALID, reported first: whatever check_bool refuses in the bool spec, a q_min_should in the bool spec
+// (the phrase spec states it), a NULL phrase spec or array, offsets that decrease, a variant without a term, an
+// unknown kind, q_min_match > 1 in the batch's score plans.  SLG_ERR_UNSUPPORTED: more than SLG_MAX_PHRASE_TERMS
+// terms in a variant, SLG_MAX_PHRASE_VARIANTS variants in a phrase, SLG_MAX_PHRASE_QUERY_TERMS variant terms in
+// a query, a slop above SLG_MAX_PHRASE_SLOP, term groups plus phrase groups above SLG_MAX_BOOL_GROUPS.
+void check_phrase(const slg_bool_spec *bool_or_null, const slg_phrase_spec *spec, uint32_t nq,
+                  const slg_score_plans *plans);
+// The tables of a checked pair of specs against the segments (slg_desc.hpp).  bools: plan_bool's tables of the
+// term groups, with the phrase groups' bits in the masks and the phrase spec's min_should.  Throws
+// SLG_ERR_INVALID for a term id out of range.
+struct PhrasePlan {
+  BoolPlan bools;
+  std::vector<slg::PhraseQuery> queries;  // [nq]
+  std::vector<slg::PhraseVar> vars;       // per query, MUST / MUST_NOT / SHOULD groups in that order
+  std::vector<slg::PhraseTerm> terms;     // [total x n_segs], a row per (query, segment)
+};
+void plan_phrase(const std::vector<SegView> &segs, uint32_t nq, const slg_bool_spec *bool_or_null,
+                 const slg_phrase_spec &spec, PhrasePlan &out);
 
 // Throws SlgError (SLG_ERR_INVALID / SLG_ERR_UNSUPPORTED) on malformed input.
 void plan_batch(const std::vector<SegView> &segs, const slg_tuning &tune, const BatchIn &in, Plan &out);

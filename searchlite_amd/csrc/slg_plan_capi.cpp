@@ -195,4 +195,66 @@ int slgp_plan_bool(const slgp_segment *segs, uint32_t n_segs, uint32_t nq, const
   }
 }
 
+// the host side of slg_batch_prepare_phrase: check_phrase, then plan_phrase against the segments.  seg_has_pos:
+// one byte per segment, 0 = no positions were set for it (NULL: every segment has positions).  queries: nq x 8
+// words (slg::BoolQuery); pqueries: nq x 8 words (slg::PhraseQuery); vars: entries of 4 words (slg::PhraseVar);
+// terms: entries of 6 words (slg::PhraseTerm: off low, off high, ubase low, ubase high, df, pad); bterms: entries
+// of 4 words (slg::BoolTerm).  Each table is filled when it fits its cap; counts: its entries (vars, terms,
+// bterms).  0, or a negative error code (err filled)
+int slgp_plan_phrase(const slgp_segment *segs, const uint8_t *seg_has_pos, uint32_t n_segs, uint32_t nq,
+                     const slg_bool_spec *boolean, const slg_phrase_spec *spec, const slg_score_plans *plans,
+                     uint32_t *queries, uint32_t *pqueries, uint32_t *vars, uint32_t vars_cap, uint32_t *terms,
+                     uint32_t terms_cap, uint32_t *bterms, uint32_t bterms_cap, uint32_t *counts, char *err,
+                     uint32_t err_len) {
+  try {
+    slgplan::check_phrase(boolean, spec, nq, plans);
+    std::vector<slgplan::SegView> views(n_segs);
+    for (uint32_t s = 0; s < n_segs; s++) {
+      views[s].n_docs = segs[s].n_docs;
+      views[s].n_terms = segs[s].n_terms;
+      views[s].term_offsets = segs[s].term_offsets;
+      views[s].has_positions = seg_has_pos ? seg_has_pos[s] != 0 : true;
+    }
+    slgplan::PhrasePlan pp;
+    slgplan::plan_phrase(views, nq, boolean, *spec, pp);
+    static_assert(sizeof(slg::PhraseQuery) == 32 && sizeof(slg::PhraseVar) == 16 && sizeof(slg::PhraseTerm) == 24,
+                  "the words the caller reads");
+    if (queries && nq) std::memcpy(queries, pp.bools.queries.data(), (size_t)nq * sizeof(slg::BoolQuery));
+    if (pqueries && nq) std::memcpy(pqueries, pp.queries.data(), (size_t)nq * sizeof(slg::PhraseQuery));
+    if (vars && pp.vars.size() <= vars_cap && !pp.vars.empty())
+      std::memcpy(vars, pp.vars.data(), pp.vars.size() * sizeof(slg::PhraseVar));
+    if (terms && pp.terms.size() <= terms_cap && !pp.terms.empty())
+      std::memcpy(terms, pp.terms.data(), pp.terms.size() * sizeof(slg::PhraseTerm));
+    if (bterms && pp.bools.terms.size() <= bterms_cap && !pp.bools.terms.empty())
+      std::memcpy(bterms, pp.bools.terms.data(), pp.bools.terms.size() * sizeof(slg::BoolTerm));
+    if (counts) {
+      counts[0] = (uint32_t)pp.vars.size();
+      counts[1] = (uint32_t)pp.terms.size();
+      counts[2] = (uint32_t)pp.bools.terms.size();
+    }
+    return SLG_OK;
+  } catch (const slgplan::SlgError &e) {
+    if (err && err_len) {
+      std::strncpy(err, e.what(), err_len - 1);
+      err[err_len - 1] = 0;
+    }
+    return e.code;
+  }
+}
+
+// the host checks of slg_index_set_positions over a segment of n_postings postings.  0, or a negative error code
+int slgp_check_positions(uint64_t n_postings, const uint64_t *pos_offsets, const uint32_t *positions, char *err,
+                         uint32_t err_len) {
+  try {
+    slgplan::check_positions(n_postings, pos_offsets, positions);
+    return SLG_OK;
+  } catch (const slgplan::SlgError &e) {
+    if (err && err_len) {
+      std::strncpy(err, e.what(), err_len - 1);
+      err[err_len - 1] = 0;
+    }
+    return e.code;
+  }
+}
+
 }  // extern "C"

@@ -160,7 +160,7 @@ int slf_postings_decode(const uint8_t *post, size_t n_bytes, const uint64_t *off
       int rc = c.var32(d);
       if (rc == SLF_OK) rc = c.var32(tf);
       if (rc != SLF_OK) return fail(rc, "bad varint in posting " + std::to_string(i) + where);
-      if (h.has_pos) {  // postings.rs:176-183: count, then deltas — skipped
+      if (h.has_pos) {  // postings.rs:176-183: count, then deltas — skipped (slf_postings_decode_positions reads them)
         uint32_t cnt, x;
         if ((rc = c.var32(cnt)) != SLF_OK) return fail(rc, "bad position count" + where);
         for (uint32_t j = 0; j < cnt; j++)
@@ -193,6 +193,52 @@ int slf_postings_decode(const uint8_t *post, size_t n_bytes, const uint64_t *off
     term_offsets[t + 1] = P;
     if (blk_offsets) blk_offsets[t + 1] = B;
   }
+  return SLF_OK;
+}
+
+int slf_postings_decode_positions(const uint8_t *post, size_t n_bytes, const uint64_t *offsets, uint32_t n_terms,
+                                  uint64_t *pos_offsets, uint32_t *positions, uint64_t positions_cap,
+                                  uint64_t *total_positions) {
+  if (!post || (n_terms && !offsets)) return fail(SLF_ERR_INVALID, "NULL argument");
+  uint64_t P = 0, N = 0;
+  if (pos_offsets) pos_offsets[0] = 0;
+  for (uint32_t t = 0; t < n_terms; t++) {
+    const std::string where = " (term " + std::to_string(t) + ")";
+    if (offsets[t] >= n_bytes) return fail(SLF_ERR_TRUNCATED, "posting offset outside the file" + where);
+    Cursor c{post, n_bytes, (size_t)offsets[t]};
+    Header h;
+    if (read_header(c, h) != SLF_OK) return fail(SLF_ERR_TRUNCATED, "truncated posting header" + where);
+    if (h.has_meta && h.block_count > 0) {  // the block-max arrays of slf_postings_decode
+      uint32_t bs;
+      if (!c.u32(bs)) return fail(SLF_ERR_TRUNCATED, "truncated block size" + where);
+      if (c.at + (size_t)h.block_count * 8 > n_bytes) return fail(SLF_ERR_TRUNCATED, "truncated block-max arrays" + where);
+      c.at += (size_t)h.block_count * 8;
+    }
+    for (uint32_t i = 0; i < h.df; i++) {
+      uint32_t d, tf;
+      int rc = c.var32(d);
+      if (rc == SLF_OK) rc = c.var32(tf);
+      if (rc != SLF_OK) return fail(rc, "bad varint in posting " + std::to_string(i) + where);
+      if (h.has_pos) {
+        uint32_t cnt, x;
+        if ((rc = c.var32(cnt)) != SLF_OK) return fail(rc, "bad position count" + where);
+        uint64_t at = 0;
+        for (uint32_t j = 0; j < cnt; j++) {
+          if ((rc = c.var32(x)) != SLF_OK) return fail(rc, "bad position delta" + where);
+          at += x;
+          if (at > 0xFFFFFFFFull) return fail(SLF_ERR_FORMAT, "positions run past 2^32 - 1" + where);
+          if (positions) {
+            if (N >= positions_cap) return fail(SLF_ERR_INVALID, "positions_cap is too small");
+            positions[N] = (uint32_t)at;
+          }
+          N++;
+        }
+      }
+      P++;
+      if (pos_offsets) pos_offsets[P] = N;
+    }
+  }
+  if (total_positions) *total_positions = N;
   return SLF_OK;
 }
 

@@ -52,6 +52,8 @@ def _load():
         L.slf_postings_scan.argtypes = [vp, C.c_size_t, vp, u32, vp, vp, u64p, u64p]
         L.slf_postings_decode.restype = C.c_int
         L.slf_postings_decode.argtypes = [vp, C.c_size_t, vp, u32, vp, vp, vp, vp, vp, vp, vp, vp]
+        L.slf_postings_decode_positions.restype = C.c_int
+        L.slf_postings_decode_positions.argtypes = [vp, C.c_size_t, vp, u32, vp, vp, C.c_uint64, vp]
         L.slf_varint_write.restype = C.c_int
         L.slf_varint_write.argtypes = [C.c_uint64, vp]
         L.slf_varint_read_u32.restype = C.c_int
@@ -121,6 +123,27 @@ def decode_postings(post: bytes, offsets: np.ndarray):
                                  out["blk_max_doc"].ctypes.data, out["blk_max_tf"].ctypes.data,
                                  out["blk_size"].ctypes.data, out["max_tf"].ctypes.data))
     return out
+
+
+def decode_positions(post: bytes, offsets: np.ndarray):
+    """The positions of all posting lists of one seg_<id>.post image (slf_postings_decode_positions) ->
+    (pos_offsets u64[P + 1] over the postings in decode_postings' order, positions u32).  Lists written without
+    positions give empty position lists."""
+    L = _load()
+    offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
+    V = len(offsets)
+    img = np.frombuffer(post, dtype=np.uint8)
+    df = np.zeros(V, dtype=np.uint32)
+    P, total = C.c_uint64(0), C.c_uint64(0)
+    _check(L.slf_postings_scan(img.ctypes.data, len(img), offsets.ctypes.data, V, df.ctypes.data, None,
+                               C.addressof(P), None))
+    _check(L.slf_postings_decode_positions(img.ctypes.data, len(img), offsets.ctypes.data, V, None, None, 0,
+                                           C.addressof(total)))
+    pos_offsets = np.zeros(P.value + 1, dtype=np.uint64)
+    positions = np.zeros(total.value, dtype=np.uint32)
+    _check(L.slf_postings_decode_positions(img.ctypes.data, len(img), offsets.ctypes.data, V, pos_offsets.ctypes.data,
+                                           positions.ctypes.data, total.value, None))
+    return pos_offsets, positions
 
 
 # index/fastfields.rs:27-56 column type tags
@@ -247,9 +270,11 @@ class LoadedIndex:
 
 
 def load_index(path: str, k1: float = 0.9, b: float = 0.4, vector_field: Optional[str] = None,
-               verify_checksums: bool = True) -> LoadedIndex:
+               verify_checksums: bool = True, positions: bool = False) -> LoadedIndex:
     """Open a searchlite index directory as Index::open + SegmentReader::open do
-    (index/segment.rs:1239-1318), in manifest (= segment_ord, api/reader.rs:2670) order."""
+    (index/segment.rs:1239-1318), in manifest (= segment_ord, api/reader.rs:2670) order.  positions: also decode
+    the postings' positions into Segment.pos_offsets / .positions (the reader's keep_positions; a segment
+    written without positions gets empty lists)."""
     with open(os.path.join(path, "MANIFEST.json"), "rb") as f:
         manifest = json.loads(f.read())
     schema = manifest.get("schema", {})
@@ -275,7 +300,8 @@ def load_index(path: str, k1: float = 0.9, b: float = 0.4, vector_field: Optiona
         seg_meta = json.loads(blob("meta", "meta"))
         n_docs = int(meta["doc_count"])
         keys, offs = read_terms(blob("terms", "terms"))
-        dec = decode_postings(blob("postings", "post"), offs)
+        post_blob = blob("postings", "post")
+        dec = decode_postings(post_blob, offs)
         for k in keys:  # fields that only occur as term prefixes (nested paths ...)
             f = k.split(":", 1)[0]
             if f not in fidx:
@@ -305,6 +331,8 @@ def load_index(path: str, k1: float = 0.9, b: float = 0.4, vector_field: Optiona
                       docs=float(max(0, n_docs - len(dels))),  # live_docs, index/segment.rs:1362-1367
                       k1=k1, b=b, term_field=term_field, deleted=deleted, fields=list(fields),
                       term_dict={k: i for i, k in enumerate(keys)}, ext_ids=list(seg_meta.get("doc_ids", [])))
+        if positions:
+            seg.pos_offsets, seg.positions = decode_positions(post_blob, offs)
         vfields = seg_meta.get("vector_fields", {})
         vname = vector_field or (sorted(vfields)[0] if vfields else None)
         if vname is not None and vname in vfields:

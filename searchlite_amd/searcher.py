@@ -96,6 +96,15 @@ class GpuIndex:
         N.check(self._lib.slg_index_remove_segment(self._h, seg))
         del self.segments[seg]
 
+    def set_positions(self, seg: int, pos_offsets=None, positions=None) -> None:
+        """The positions of segment `seg`'s postings (slg_index_set_positions): pos_offsets u64[P + 1] over the
+        postings in the order of doc_ids / tfs, positions u32[pos_offsets[P]]; None, None removes them.  Phrase
+        batches prepared afterwards see them; the mirrored Segment object follows."""
+        po = None if pos_offsets is None else np.ascontiguousarray(pos_offsets, dtype=np.uint64)
+        ps = None if positions is None else np.ascontiguousarray(positions, dtype=np.uint32)
+        N.check(self._lib.slg_index_set_positions(self._h, seg, _ptr(po), _ptr(ps)))
+        self.segments[seg].pos_offsets, self.segments[seg].positions = po, ps
+
     @property
     def generation(self) -> int:
         return int(self._lib.slg_index_generation(self._h))
@@ -342,6 +351,21 @@ class GpuIndex:
         finally:
             b.close()
 
+    def search_batch_phrase(self, q_offsets, q_terms, q_weights, k: int, phrases, clauses=None, sort=None,
+                            strategy: int = Wand, q_filter=None, want_stats: bool = False, **plans):
+        """Batch search with phrase groups (slg_batch_prepare_phrase).  phrases: a dict with p_offsets [nq + 1],
+        p_kind (BOOL_MUST / _SHOULD / _MUST_NOT per phrase), p_slop, v_offsets [n_phrases + 1], t_offsets
+        [n_variants + 1], t_terms ([total, n_segs]) and optionally q_min_should (a number or one per query, over
+        term and phrase groups); clauses: the term groups, the dict of search_batch_bool without q_min_should, or
+        None; the segments' positions: set_positions.  Returns what search_batch_bool returns."""
+        b = self.prepare(q_offsets, q_terms, q_weights, k, strategy, q_filter, sort=sort, clauses=clauses,
+                         phrases=phrases, **plans)
+        try:
+            b.run()
+            return b.fetch(want_stats) + ((b.matched_counts(),) if sort is not None else ())
+        finally:
+            b.close()
+
     def search_sorted(self, q_offsets, q_terms, q_weights, k: int, sort, strategy: int = Wand, q_filter=None,
                       **plans):
         """Field-sorted batch search (slg_batch_prepare_sorted).  sort: [(field, order)], field = a sort field id
@@ -374,7 +398,7 @@ class GpuIndex:
                 q_leaf_offsets=None, leaf_group=None, q_group_offsets=None, group_plan=None,
                 group_tie=None, q_node_offsets=None, node_kind=None, node_tie=None, node_parent=None,
                 q_min_match=None, sort=None, cursors=None, hybrid=False, aggs=None,
-                rescore=None, clauses=None) -> "PreparedBatch":
+                rescore=None, clauses=None, phrases=None) -> "PreparedBatch":
         """q_leaf / q_plan / q_tie / q_nleaves: score plans; leaf_group / group_plan / group_tie with
         their per-query offsets: two-level plans; q_node_offsets / node_kind / node_tie / node_parent:
         trees of any shape, node by node in pre-order (slg_batch_prepare_plans, slg_score_plans);
@@ -384,11 +408,12 @@ class GpuIndex:
         slg_batch_prepare_hybrid (PreparedBatch.hybrid_device); aggs: an N.AggSpec or aggs.AggPlan ->
         slg_batch_prepare_aggs (PreparedBatch.aggs); rescore: the dict of search_rescore ->
         slg_batch_prepare_rescore (PreparedBatch.rescore_details); clauses: the dict of search_batch_bool ->
-        slg_batch_prepare_bool (score order, or with sort)."""
+        slg_batch_prepare_bool (score order, or with sort); phrases: the dict of search_batch_phrase ->
+        slg_batch_prepare_phrase (with clauses as its term groups, or without)."""
         return PreparedBatch(self, q_offsets, q_terms, q_weights, k, strategy, q_filter,
                              q_leaf, q_plan, q_tie, q_nleaves, q_leaf_offsets, leaf_group,
                              q_group_offsets, group_plan, group_tie, q_node_offsets, node_kind, node_tie, node_parent,
-                             q_min_match, sort, cursors, hybrid, aggs, rescore, clauses)
+                             q_min_match, sort, cursors, hybrid, aggs, rescore, clauses, phrases)
 
     def search_plan(self, q_offsets, q_terms, q_weights, k: int, q_leaf=None, q_plan=None,
                     q_tie=None, q_nleaves=None, strategy: int = Wand, q_filter=None, **tree):
@@ -721,6 +746,23 @@ def bool_spec(clauses: dict, nq: int):
     return N.BoolSpec(*[_ptr(a) for a in keep]), keep
 
 
+def phrase_spec(phrases: dict, nq: int):
+    """The dict of GpuIndex.search_batch_phrase as (N.PhraseSpec, the arrays it points into)."""
+    def arr(name, dtype, per_query=False):
+        a = phrases.get(name)
+        if a is None:
+            return None
+        a = np.asarray(a, dtype=dtype)
+        if per_query and a.ndim == 0:
+            a = np.full(nq, a, dtype=dtype)
+        return np.ascontiguousarray(a)
+    keep = [arr("p_offsets", np.uint32), arr("p_kind", np.int32), arr("p_slop", np.uint32), arr("v_offsets", np.uint32),
+            arr("t_offsets", np.uint32), arr("t_terms", np.uint32), arr("q_min_should", np.uint32, True)]
+    assert keep[0] is not None and len(keep[0]) == nq + 1
+    assert keep[6] is None or len(keep[6]) == nq
+    return N.PhraseSpec(*[_ptr(a) for a in keep]), keep
+
+
 def sort_cursor(cursor, sort=None) -> "N.SortCursor":
     """None (a first page), an N.SortCursor, or (values, segment_ord, doc_id) -> slg_sort_cursor.  values: one
     per sort part (score order: one, the score): an int is an i64 value, a float an f64 value (or, on a
@@ -752,7 +794,8 @@ class PreparedBatch:
                  q_filter=None, q_leaf=None, q_plan=None, q_tie=None, q_nleaves=None,
                  q_leaf_offsets=None, leaf_group=None, q_group_offsets=None, group_plan=None,
                  group_tie=None, q_node_offsets=None, node_kind=None, node_tie=None, node_parent=None,
-                 q_min_match=None, sort=None, cursors=None, hybrid=False, aggs=None, rescore=None, clauses=None):
+                 q_min_match=None, sort=None, cursors=None, hybrid=False, aggs=None, rescore=None, clauses=None,
+                 phrases=None):
         self.index = index
         self._lib = index._lib
         q_offsets = np.ascontiguousarray(q_offsets, dtype=np.uint32)
@@ -786,8 +829,22 @@ class PreparedBatch:
         assert not (hybrid and (sort is not None or cursors is not None)), "a hybrid batch takes no sort or cursor"
         self.agg_spec = getattr(aggs, "spec", aggs)  # (an aggs.AggPlan carries its N.AggSpec)
         self.is_rescore = rescore is not None
-        self.is_bool = clauses is not None
-        if clauses is not None:
+        self.is_bool = clauses is not None or phrases is not None
+        self.is_phrase = phrases is not None
+        if phrases is not None:
+            # (the library's other prepare calls take no phrase spec: the refusal is made here with its code)
+            if hybrid or cursors is not None or aggs is not None or rescore is not None:
+                raise N.SlgError(N.ERR_UNSUPPORTED, "phrases are not built on cursor, hybrid, aggregation or rescore batches")
+            pspec, self._phrase_keep = phrase_spec(phrases, self.nq)
+            bspec = None
+            if clauses is not None:
+                bspec, self._bool_keep = bool_spec(clauses, self.nq)
+            spec = None if sort is None else sort_spec(sort)
+            self._h = self._lib.slg_batch_prepare_phrase(
+                index._h, self.nq, _ptr(q_offsets), _ptr(q_terms), _ptr(q_weights), C.addressof(plans),
+                opt(qf), None if spec is None else C.addressof(spec), None if bspec is None else C.addressof(bspec),
+                C.addressof(pspec), k, strategy)
+        elif clauses is not None:
             # (the library's other prepare calls take no bool spec: the refusal is made here with its code)
             if hybrid or cursors is not None or aggs is not None or rescore is not None:
                 raise N.SlgError(N.ERR_UNSUPPORTED, "boolean clauses are not built on cursor, hybrid, aggregation or rescore batches")

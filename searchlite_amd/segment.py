@@ -43,6 +43,9 @@ class Segment:
     fields: List[str] = field(default_factory=lambda: ["body"])
     term_dict: Optional[Dict[str, int]] = None  # "field:term" -> term id
     ext_ids: Optional[List[str]] = None
+    # positions of the postings (phrase queries; GpuIndex.set_positions): CSR over doc_ids / tfs
+    pos_offsets: Optional[np.ndarray] = None    # u64[P+1]
+    positions: Optional[np.ndarray] = None      # u32[pos_offsets[P]]
 
     def __post_init__(self):
         self.term_offsets = np.ascontiguousarray(self.term_offsets, dtype=np.uint64)
@@ -59,6 +62,10 @@ class Segment:
             self.vec_offsets = np.ascontiguousarray(self.vec_offsets, dtype=np.uint32)
         if self.vec_values is not None:
             self.vec_values = np.ascontiguousarray(self.vec_values, dtype=np.float32)
+        if self.pos_offsets is not None:
+            self.pos_offsets = np.ascontiguousarray(self.pos_offsets, dtype=np.uint64)
+        if self.positions is not None:
+            self.positions = np.ascontiguousarray(self.positions, dtype=np.uint32)
 
     @property
     def n_terms(self) -> int:
@@ -74,6 +81,13 @@ class Segment:
     def postings(self, term_id: int) -> Tuple[np.ndarray, np.ndarray]:
         a, b = int(self.term_offsets[term_id]), int(self.term_offsets[term_id + 1])
         return self.doc_ids[a:b], self.tfs[a:b]
+
+    def posting_positions(self, term_id: int, i: int) -> np.ndarray:
+        """the positions of posting i of the term's list (empty without positions)"""
+        if self.pos_offsets is None:
+            return np.zeros(0, np.uint32)
+        at = int(self.term_offsets[term_id]) + i
+        return self.positions[int(self.pos_offsets[at]):int(self.pos_offsets[at + 1])]
 
     def term_id(self, key: str) -> int:
         if self.term_dict is None:
@@ -109,7 +123,14 @@ def default_tokenize(text: str) -> List[str]:
 
 
 class SegmentBuilder:
-    """Builds one segment the way SegmentWriter::write_segment does for text fields."""
+    """Builds one segment the way SegmentWriter::write_segment does for text fields.
+
+    Positions (index/segment.rs:664-692): a token's position is its index inside its value (the default tokenizer
+    numbers the tokens of one text 0, 1, ...) plus the field's running position_offset, which starts at 0 for each
+    (doc, field) and grows by max position + 1 after each value — by 1 after a value without tokens.  So the values
+    of a multi-valued field run on without a gap: the last token of one value and the first of the next are
+    adjacent, and a slop-0 phrase can match across them; only an empty value leaves a gap of one.  A posting's
+    positions are recorded in token order, so they are strictly increasing."""
 
     def __init__(self, fields: Sequence[str], k1: float = 0.9, b: float = 0.4):
         self.fields = list(fields)
@@ -132,7 +153,7 @@ class SegmentBuilder:
         lens = [np.zeros(n, dtype=np.float32) for _ in range(F)]
         present = [False] * F
         totals = [0] * F
-        post: Dict[str, List[List[int]]] = {}
+        post: Dict[str, List[list]] = {}  # key -> [[doc, tf, [positions]]]
         for ord_, eid in enumerate(ext_ids):
             doc = self._docs[eid]
             for fi, f in enumerate(self.fields):
@@ -140,28 +161,35 @@ class SegmentBuilder:
                     continue
                 present[fi] = True
                 dl = 0
+                position_offset = 0
                 for text in doc[f]:
                     toks = default_tokenize(text)
                     dl += len(toks)
-                    for t in toks:
+                    for ti, t in enumerate(toks):
                         key = f"{f}:{t}"
                         lst = post.setdefault(key, [])
                         if lst and lst[-1][0] == ord_:
                             lst[-1][1] += 1   # index/postings.rs:33-41
+                            lst[-1][2].append(position_offset + ti)
                         else:
-                            lst.append([ord_, 1])
+                            lst.append([ord_, 1, [position_offset + ti]])
+                    position_offset += len(toks) if toks else 1   # index/segment.rs:686-691
                 totals[fi] += dl
                 lens[fi][ord_] = dl           # "_len:<field>" fast column
         keys = sorted(post.keys())            # index/postings.rs:56-60
         offs = np.zeros(len(keys) + 1, dtype=np.uint64)
         docs_l: List[int] = []
         tfs_l: List[int] = []
+        pos_l: List[int] = []
+        pos_offs: List[int] = [0]
         tfield = np.zeros(len(keys), dtype=np.uint16)
         fidx = {f: i for i, f in enumerate(self.fields)}
         for i, k in enumerate(keys):
-            for d, tf in post[k]:
+            for d, tf, ps in post[k]:
                 docs_l.append(d)
                 tfs_l.append(tf)
+                pos_l.extend(ps)
+                pos_offs.append(len(pos_l))
             offs[i + 1] = len(docs_l)
             tfield[i] = fidx[k.split(":", 1)[0]]
         avg = np.array([np.float32(totals[i]) / np.float32(n) if n else np.float32(0)
@@ -172,15 +200,16 @@ class SegmentBuilder:
                        field_doc_len=[lens[i] if present[i] else None for i in range(F)],
                        field_avgdl=avg, docs=float(n), k1=self.k1, b=self.b,
                        term_field=tfield, fields=list(self.fields),
-                       term_dict={k: i for i, k in enumerate(keys)}, ext_ids=ext_ids)
+                       term_dict={k: i for i, k in enumerate(keys)}, ext_ids=ext_ids,
+                       pos_offsets=np.array(pos_offs, dtype=np.uint64), positions=np.array(pos_l, dtype=np.uint32))
 
 
 def parse_query_terms(query: str, default_field: str) -> List[Tuple[str, float]]:
     """Plain-term subset of api/query.rs:20-98 + query-time analysis (api/reader.rs:1037-1046):
-    whitespace split, optional `field:` prefix, default tokenizer.  Phrases / -terms are outside
-    the GPU eligibility predicate and raise."""
+    whitespace split, optional `field:` prefix, default tokenizer.  Phrases / -terms are not plain
+    terms and raise here: parse_query_string splits them out (they run as bool / phrase batches)."""
     if '"' in query:
-        raise ValueError("phrase queries are not GPU-eligible")
+        raise ValueError("a quoted phrase is not a plain term: parse_query_string splits phrases out")
     out: List[Tuple[str, float]] = []
     for raw in query.split():
         if raw.startswith("-"):
@@ -192,6 +221,43 @@ def parse_query_terms(query: str, default_field: str) -> List[Tuple[str, float]]
         for tok in default_tokenize(rest):
             out.append((f"{f}:{tok}", 1.0))
     return out
+
+
+def parse_query_string(query: str, default_field: str):
+    """api/query.rs:20-98 in full: -> (words, not_terms, phrases).  words / not_terms: [(field, raw term)] in
+    query order (`-` marks a not-term, `field:` a field, else default_field); phrases: [(field, [raw terms])] for
+    every closed "..." with at least one term, `field:` in front of the body taken only when it is alphanumeric
+    or `_`; an unclosed quote drops the rest of the string.  The raw terms still go through the field's analyzer
+    (default_tokenize) before they are looked up."""
+    def split(chunk):
+        for raw in chunk.split():
+            neg = raw.startswith("-")
+            tok = raw.lstrip("-")
+            f, term = tok.split(":", 1) if ":" in tok else (default_field, tok)
+            (not_terms if neg else words).append((f, term))
+    words, not_terms, phrases = [], [], []
+    rest = query.strip()
+    while '"' in rest:
+        start = rest.index('"')
+        if rest[:start].strip():
+            split(rest[:start])
+        after = rest[start + 1:]
+        end = after.find('"')
+        if end < 0:
+            rest = ""
+            break
+        body, f = after[:end], default_field
+        if ":" in body:
+            head = body[:body.index(":")]
+            if all(ch.isalnum() or ch == "_" for ch in head):
+                f, body = head, body[body.index(":") + 1:]
+        terms = body.split()
+        if terms:
+            phrases.append((f, terms))
+        rest = after[end + 1:]
+    if rest.strip():
+        split(rest)
+    return words, not_terms, phrases
 
 
 def fold_terms(keys_weights: Sequence[Tuple[str, float]]) -> List[Tuple[str, float]]:

@@ -152,12 +152,7 @@ void slghost::agg_attach(slg_batch *b, const slg_agg_spec &aggs) {
   b->agg_count_cells = (uint32_t)count_cells;
   b->agg_stats_cells = (uint32_t)stats_cells;
   b->agg_lds = 4 * count_cells + sizeof(slg::AggStatDev) * stats_cells <= slg::kAggLdsBytes;
-  const size_t node_bytes = nodes.size() * sizeof(slg::AggNodeDev), col_bytes = cols.size() * sizeof(slg::AggColDev);
-  std::vector<unsigned char> image(node_bytes + col_bytes);
-  std::memcpy(image.data(), nodes.data(), node_bytes);
-  std::memcpy(image.data() + node_bytes, cols.data(), col_bytes);
-  b->d_agg_desc.alloc_pooled(&ix->pool, image.size());
-  SLG_HIP(hipMemcpy(b->d_agg_desc.p, image.data(), image.size(), hipMemcpyHostToDevice));
+  upload_image(b->d_agg_desc, &ix->pool, {image_part(nodes), image_part(cols)});
   const size_t nq = std::max<uint32_t>(b->nq, 1);
   b->d_agg_counts.alloc_pooled(&ix->pool, nq * std::max<size_t>(count_cells, 1) * 4);
   b->d_agg_stats.alloc_pooled(&ix->pool, nq * std::max<size_t>(stats_cells, 1) * sizeof(slg::AggStatDev));

@@ -162,24 +162,21 @@ slg_batch *slg_batch_prepare_plan(slg_index *ix, uint32_t nq, const uint32_t *q_
 
 }  // extern "C"
 
-namespace {
-// slg_batch_prepare_plans, (sort != nullptr) slg_batch_prepare_sorted, (after) slg_batch_prepare_after, and
-// (hybrid) slg_batch_prepare_hybrid, (want_aggs) slg_batch_prepare_aggs, (want_rescore) slg_batch_prepare_rescore,
-// (want_bool) slg_batch_prepare_bool, (phrases) slg_batch_prepare_phrase: want_bool with a bool spec or nullptr
-slg_batch *prepare_impl(slg_index *ix, uint32_t nq, const uint32_t *q_offsets, const uint32_t *q_term_ids,
-                        const float *q_weights, const slg_score_plans *plans, const int32_t *q_filter,
-                        const slg_sort_spec *sort, uint32_t k, int strategy, bool after = false,
-                        const slg_sort_cursor *q_cursor = nullptr, bool hybrid = false,
-                        const slg_agg_spec *aggs = nullptr, bool want_aggs = false,
-                        const slg_rescore_spec *rescore = nullptr, bool want_rescore = false,
-                        const slg_bool_spec *boolean = nullptr, bool want_bool = false,
-                        const slg_phrase_spec *phrases = nullptr, bool want_phrase = false) {
+// every slg_batch_prepare*: the kinds the request asks for decide what is checked, planned and attached
+slg_batch *slghost::prepare_impl(const PrepareRequest &r) {
+  slg_index *const ix = r.ix;
+  const uint32_t nq = r.nq, k = r.k;
+  const slg_score_plans *const plans = r.plans;
+  const slg_sort_spec *const sort = r.sort.spec;
+  const slg_sort_cursor *const q_cursor = r.cursor.spec;
+  const bool after = r.cursor.on, hybrid = r.hybrid;
   slg_batch *b = nullptr;
   int rc = guarded([&] {
-    if (want_aggs) agg_check_spec(aggs);  // (what needs no index comes first, as every argument check)
-    if (want_rescore) slgplan::check_rescore(rescore, nq, k);
-    if (want_phrase) slgplan::check_phrase(boolean, phrases, nq, plans);
-    else if (want_bool) slgplan::check_bool(boolean, nq, plans);
+    SLG_REQUIRE(!r.sort.on || sort != nullptr, "sort spec is NULL");
+    if (r.aggs.on) agg_check_spec(r.aggs.spec);  // (what needs no index comes first, as every argument check)
+    if (r.rescore.on) slgplan::check_rescore(r.rescore.spec, nq, k);
+    if (r.phrase.on) slgplan::check_phrase(r.boolean.spec, r.phrase.spec, nq, plans);
+    else if (r.boolean.on) slgplan::check_bool(r.boolean.spec, nq, plans);
     SLG_REQUIRE(ix != nullptr, "index is NULL");
     SLG_REQUIRE(!after || q_cursor != nullptr, "q_cursor is NULL");
     if (sort) {  // (checked before planning: the planner never sees a sort spec it cannot run)
@@ -207,16 +204,16 @@ slg_batch *prepare_impl(slg_index *ix, uint32_t nq, const uint32_t *q_offsets, c
     }
     slgplan::BatchIn in;
     in.nq = nq;
-    in.q_offsets = q_offsets;
-    in.q_term_ids = q_term_ids;
-    in.q_weights = q_weights;
+    in.q_offsets = r.q_offsets;
+    in.q_term_ids = r.q_term_ids;
+    in.q_weights = r.q_weights;
     if (plans) in.plans = *plans;
-    in.q_filter = q_filter;
+    in.q_filter = r.q_filter;
     in.k = k;
-    in.strategy = strategy;
+    in.strategy = r.strategy;
     in.filter_live = filter_live.data();
     in.n_filters = filter_live.size();
-    in.sorted = sort != nullptr || after || hybrid || aggs != nullptr || want_bool;
+    in.sorted = sort != nullptr || after || hybrid || r.aggs.on || r.boolean.on;
     // the columns of the sort parts in the batch's state: every part names a field with a column for every
     // segment (a field registered before slg_index_add_segment has none for the new one)
     std::vector<slg::SortColDev> sort_cols;
@@ -265,11 +262,11 @@ slg_batch *prepare_impl(slg_index *ix, uint32_t nq, const uint32_t *q_offsets, c
     slgplan::Plan plan;
     slgplan::plan_batch(views, ix->tune, in, plan);
     slgplan::RescorePlan rescore_plan;  // (against the same snapshot, before any device work)
-    if (want_rescore) slgplan::plan_rescore(views, nq, k, *rescore, rescore_plan);
+    if (r.rescore.on) slgplan::plan_rescore(views, nq, k, *r.rescore.spec, rescore_plan);
     slgplan::BoolPlan bool_plan;
     slgplan::PhrasePlan phrase_plan;
-    if (want_phrase) slgplan::plan_phrase(views, nq, boolean, *phrases, phrase_plan);
-    else if (want_bool) slgplan::plan_bool(views, nq, *boolean, bool_plan);
+    if (r.phrase.on) slgplan::plan_phrase(views, nq, r.boolean.spec, *r.phrase.spec, phrase_plan);
+    else if (r.boolean.on) slgplan::plan_bool(views, nq, *r.boolean.spec, bool_plan);
 
     DeviceGuard g(ix->device);
     b = new slg_batch();
@@ -277,7 +274,7 @@ slg_batch *prepare_impl(slg_index *ix, uint32_t nq, const uint32_t *q_offsets, c
     b->snap = snap;
     b->nq = nq;
     b->k = k;
-    b->strategy = strategy;
+    b->strategy = r.strategy;
     b->q_postings.swap(plan.q_postings);
     b->n_postings = plan.n_postings;
     b->n_postings_essential = plan.n_postings_essential;
@@ -353,7 +350,7 @@ slg_batch *prepare_impl(slg_index *ix, uint32_t nq, const uint32_t *q_offsets, c
       SLG_HIP(hipMemcpy(b->d_sort_cols.p, sort_cols.data(), sort_cols.size() * sizeof(slg::SortColDev),
                         hipMemcpyHostToDevice));
     }
-    if (b->sorted || b->after || aggs) b->d_matched.alloc_pooled(&ix->pool, (size_t)std::max<uint32_t>(nq, 1) * 8);
+    if (b->sorted || b->after || r.aggs.on) b->d_matched.alloc_pooled(&ix->pool, (size_t)std::max<uint32_t>(nq, 1) * 8);
     if (b->after) {
       b->d_cursor.alloc_pooled(&ix->pool, cursor_words.size() * 4);
       SLG_HIP(hipMemcpy(b->d_cursor.p, cursor_words.data(), cursor_words.size() * 4, hipMemcpyHostToDevice));
@@ -381,12 +378,12 @@ slg_batch *prepare_impl(slg_index *ix, uint32_t nq, const uint32_t *q_offsets, c
     b->d_out_seg = R.seg(b->d_out.as<uint32_t>());
     b->d_out_score = R.score(b->d_out.as<uint32_t>());
     b->d_out_count = R.count(b->d_out.as<uint32_t>());
-    if (aggs) agg_attach(b, *aggs);
-    if (want_rescore) rescore_attach(b, rescore_plan);
-    if (want_phrase) {
+    if (r.aggs.on) agg_attach(b, *r.aggs.spec);
+    if (r.rescore.on) rescore_attach(b, rescore_plan);
+    if (r.phrase.on) {
       bool_attach(b, phrase_plan.bools);
       phrase_attach(b, phrase_plan);
-    } else if (want_bool) {
+    } else if (r.boolean.on) {
       bool_attach(b, bool_plan);
     }
     {
@@ -401,23 +398,6 @@ slg_batch *prepare_impl(slg_index *ix, uint32_t nq, const uint32_t *q_offsets, c
   }
   return b;
 }
-}  // namespace
-
-slg_batch *slghost::prepare_hybrid_batch(slg_index *ix, uint32_t nq, const uint32_t *q_offsets,
-                                         const uint32_t *q_term_ids, const float *q_weights,
-                                         const slg_score_plans *plans, const int32_t *q_filter, uint32_t k,
-                                         int strategy) {
-  return prepare_impl(ix, nq, q_offsets, q_term_ids, q_weights, plans, q_filter, nullptr, k, strategy, false, nullptr,
-                      true);
-}
-
-slg_batch *slghost::prepare_agg_batch(slg_index *ix, uint32_t nq, const uint32_t *q_offsets,
-                                      const uint32_t *q_term_ids, const float *q_weights,
-                                      const slg_score_plans *plans, const int32_t *q_filter, const slg_sort_spec *sort,
-                                      const slg_agg_spec *aggs, uint32_t k, int strategy) {
-  return prepare_impl(ix, nq, q_offsets, q_term_ids, q_weights, plans, q_filter, sort, k, strategy, false, nullptr,
-                      false, aggs, true);
-}
 
 extern "C" {
 
@@ -425,29 +405,27 @@ slg_batch *slg_batch_prepare_plans(slg_index *ix, uint32_t nq, const uint32_t *q
                                    const uint32_t *q_term_ids, const float *q_weights,
                                    const slg_score_plans *plans, const int32_t *q_filter, uint32_t k,
                                    int strategy) {
-  return prepare_impl(ix, nq, q_offsets, q_term_ids, q_weights, plans, q_filter, nullptr, k, strategy);
+  return prepare_impl(PrepareRequest{ix, nq, q_offsets, q_term_ids, q_weights, plans, q_filter, k, strategy});
 }
 
 slg_batch *slg_batch_prepare_sorted(slg_index *ix, uint32_t nq, const uint32_t *q_offsets,
                                     const uint32_t *q_term_ids, const float *q_weights,
                                     const slg_score_plans *plans, const int32_t *q_filter,
                                     const slg_sort_spec *sort, uint32_t k, int strategy) {
-  if (!sort) {
-    (void)guarded([&] { SLG_REQUIRE(false, "sort spec is NULL"); });
-    return nullptr;
-  }
-  return prepare_impl(ix, nq, q_offsets, q_term_ids, q_weights, plans, q_filter, sort, k, strategy);
+  PrepareRequest r{ix, nq, q_offsets, q_term_ids, q_weights, plans, q_filter, k, strategy};
+  r.sort = {true, sort};
+  return prepare_impl(r);
 }
 
 slg_batch *slg_batch_prepare_after(slg_index *ix, uint32_t nq, const uint32_t *q_offsets,
                                    const uint32_t *q_term_ids, const float *q_weights,
                                    const slg_score_plans *plans, const int32_t *q_filter, const slg_sort_spec *sort,
                                    const slg_sort_cursor *q_cursor, uint32_t k, int strategy) {
-  return prepare_impl(ix, nq, q_offsets, q_term_ids, q_weights, plans, q_filter, sort, k, strategy, true, q_cursor);
+  PrepareRequest r{ix, nq, q_offsets, q_term_ids, q_weights, plans, q_filter, k, strategy};
+  r.sort = if_given(sort);
+  r.cursor = {true, q_cursor};
+  return prepare_impl(r);
 }
-
-#define SLG_REQUIRE_LIVE(b) \
-  SLG_REQUIRE((b) != nullptr && (b)->idx != nullptr, "batch is NULL or its index was destroyed")
 
 int slg_batch_run(slg_batch *b) {
   return guarded([&] {
@@ -760,17 +738,29 @@ int flatten_queries(slg_index *ix, const slg_query *queries, uint32_t nq, FlatQu
   });
 }
 
-// A prepared batch (null: prepare failed and set the thread's error) run to the caller's host arrays, with
-// the matched counts and seen flags the caller asks for, and destroyed: the first error is the one reported
-int run_to_host(slg_batch *b, uint32_t *out_doc, uint32_t *out_seg, float *out_score, uint32_t *out_count,
-                slg_stats *stats, uint64_t *out_matched, uint8_t *out_seen, uint64_t *agg_counts = nullptr,
-                slg_agg_stats *agg_stats = nullptr) {
+// the host arrays of a one-call search: the rows, and what the batch's kind adds to them (null: not asked for)
+struct HostOut {
+  uint32_t *doc, *seg;
+  float *score;
+  uint32_t *count;
+  slg_stats *stats = nullptr;
+  uint64_t *matched = nullptr;
+  uint8_t *seen = nullptr;
+  uint64_t *agg_counts = nullptr;  // (an aggregation batch)
+  slg_agg_stats *agg_stats = nullptr;
+  float *first_score = nullptr, *rescore_score = nullptr;  // (a rescore batch)
+  uint32_t *rescored = nullptr;
+};
+// A prepared batch (null: prepare failed and set the thread's error) run to the caller's host arrays and
+// destroyed: the first error is the one reported
+int run_to_host(slg_batch *b, const HostOut &o) {
   if (!b) return last_error().code;
   int rc = slg_batch_run(b);
-  if (rc == SLG_OK) rc = slg_batch_fetch(b, out_doc, out_seg, out_score, out_count, stats);
-  if (rc == SLG_OK && out_matched) rc = slg_batch_matched_counts(b, out_matched);
-  if (rc == SLG_OK && b->aggs) rc = slg_batch_fetch_aggs(b, agg_counts, agg_stats);
-  if (rc == SLG_OK && out_seen) rc = slg_batch_cursor_seen(b, out_seen);
+  if (rc == SLG_OK) rc = slg_batch_fetch(b, o.doc, o.seg, o.score, o.count, o.stats);
+  if (rc == SLG_OK && o.matched) rc = slg_batch_matched_counts(b, o.matched);
+  if (rc == SLG_OK && b->aggs) rc = slg_batch_fetch_aggs(b, o.agg_counts, o.agg_stats);
+  if (rc == SLG_OK && b->rescore) rc = slg_batch_fetch_rescore(b, o.first_score, o.rescore_score, o.rescored);
+  if (rc == SLG_OK && o.seen) rc = slg_batch_cursor_seen(b, o.seen);
   KeepLastError keep;
   slg_batch_destroy(b);
   return rc;
@@ -795,7 +785,7 @@ int slg_search_batch_filtered(slg_index *ix, const slg_query *queries, uint32_t 
   if (rc != SLG_OK) return rc;
   return run_to_host(slg_batch_prepare_filtered(ix, nq, fq.offs.data(), fq.tids.data(), fq.ws.data(), q_filter, k,
                                                 strategy),
-                     out_doc, out_seg, out_score, out_count, stats, nullptr, nullptr);
+                     HostOut{out_doc, out_seg, out_score, out_count, stats});
 }
 
 int slg_batch_matched_counts(slg_batch *b, uint64_t *out_matched) {
@@ -821,13 +811,16 @@ int slg_search_batch_sorted(slg_index *ix, const slg_query *queries, uint32_t nq
   if (rc != SLG_OK) return rc;
   return run_to_host(slg_batch_prepare_sorted(ix, nq, fq.offs.data(), fq.tids.data(), fq.ws.data(), plans, q_filter,
                                               sort, k, strategy),
-                     out_doc, out_seg, out_score, out_count, nullptr, out_matched, nullptr);
+                     HostOut{out_doc, out_seg, out_score, out_count, nullptr, out_matched});
 }
 
 slg_batch *slg_batch_prepare_aggs(slg_index *ix, uint32_t nq, const uint32_t *q_offsets, const uint32_t *q_term_ids,
                                   const float *q_weights, const slg_score_plans *plans, const int32_t *q_filter,
                                   const slg_sort_spec *sort, const slg_agg_spec *aggs, uint32_t k, int strategy) {
-  return prepare_agg_batch(ix, nq, q_offsets, q_term_ids, q_weights, plans, q_filter, sort, aggs, k, strategy);
+  PrepareRequest r{ix, nq, q_offsets, q_term_ids, q_weights, plans, q_filter, k, strategy};
+  r.sort = if_given(sort);
+  r.aggs = {true, aggs};
+  return prepare_impl(r);
 }
 
 int slg_search_batch_aggs(slg_index *ix, const slg_query *queries, uint32_t nq, const slg_score_plans *plans,
@@ -839,14 +832,15 @@ int slg_search_batch_aggs(slg_index *ix, const slg_query *queries, uint32_t nq, 
   if (rc != SLG_OK) return rc;
   return run_to_host(slg_batch_prepare_aggs(ix, nq, fq.offs.data(), fq.tids.data(), fq.ws.data(), plans, q_filter,
                                             sort, aggs, k, strategy),
-                     out_doc, out_seg, out_score, out_count, nullptr, out_matched, nullptr, counts, stats);
+                     HostOut{out_doc, out_seg, out_score, out_count, nullptr, out_matched, nullptr, counts, stats});
 }
 
 slg_batch *slg_batch_prepare_rescore(slg_index *ix, uint32_t nq, const uint32_t *q_offsets, const uint32_t *q_term_ids,
                                      const float *q_weights, const slg_score_plans *plans, const int32_t *q_filter,
                                      const slg_rescore_spec *rescore, uint32_t k, int strategy) {
-  return prepare_impl(ix, nq, q_offsets, q_term_ids, q_weights, plans, q_filter, nullptr, k, strategy, false, nullptr,
-                      false, nullptr, false, rescore, true);
+  PrepareRequest r{ix, nq, q_offsets, q_term_ids, q_weights, plans, q_filter, k, strategy};
+  r.rescore = {true, rescore};
+  return prepare_impl(r);
 }
 
 int slg_search_batch_rescore(slg_index *ix, uint32_t nq, const uint32_t *q_offsets, const uint32_t *q_term_ids,
@@ -854,22 +848,22 @@ int slg_search_batch_rescore(slg_index *ix, uint32_t nq, const uint32_t *q_offse
                              const slg_rescore_spec *rescore, uint32_t k, int strategy, uint32_t *out_doc,
                              uint32_t *out_seg, float *out_score, uint32_t *out_count, float *out_first_score,
                              float *out_rescore_score, uint32_t *out_rescored) {
-  slg_batch *b = slg_batch_prepare_rescore(ix, nq, q_offsets, q_term_ids, q_weights, plans, q_filter, rescore, k,
-                                           strategy);
-  if (!b) return last_error().code;
-  int rc = slg_batch_run(b);
-  if (rc == SLG_OK) rc = slg_batch_fetch(b, out_doc, out_seg, out_score, out_count, nullptr);
-  if (rc == SLG_OK) rc = slg_batch_fetch_rescore(b, out_first_score, out_rescore_score, out_rescored);
-  KeepLastError keep;
-  slg_batch_destroy(b);
-  return rc;
+  HostOut o{out_doc, out_seg, out_score, out_count};
+  o.first_score = out_first_score;
+  o.rescore_score = out_rescore_score;
+  o.rescored = out_rescored;
+  return run_to_host(slg_batch_prepare_rescore(ix, nq, q_offsets, q_term_ids, q_weights, plans, q_filter, rescore, k,
+                                               strategy),
+                     o);
 }
 
 slg_batch *slg_batch_prepare_bool(slg_index *ix, uint32_t nq, const uint32_t *q_offsets, const uint32_t *q_term_ids,
                                   const float *q_weights, const slg_score_plans *plans, const int32_t *q_filter,
                                   const slg_sort_spec *sort, const slg_bool_spec *spec, uint32_t k, int strategy) {
-  return prepare_impl(ix, nq, q_offsets, q_term_ids, q_weights, plans, q_filter, sort, k, strategy, false, nullptr,
-                      false, nullptr, false, nullptr, false, spec, true);
+  PrepareRequest r{ix, nq, q_offsets, q_term_ids, q_weights, plans, q_filter, k, strategy};
+  r.sort = if_given(sort);
+  r.boolean = {true, spec};
+  return prepare_impl(r);
 }
 
 int slg_search_batch_bool(slg_index *ix, uint32_t nq, const uint32_t *q_offsets, const uint32_t *q_term_ids,
@@ -879,15 +873,18 @@ int slg_search_batch_bool(slg_index *ix, uint32_t nq, const uint32_t *q_offsets,
                           slg_stats *stats, uint64_t *out_matched) {
   return run_to_host(slg_batch_prepare_bool(ix, nq, q_offsets, q_term_ids, q_weights, plans, q_filter, sort, spec, k,
                                             strategy),
-                     out_doc, out_seg, out_score, out_count, stats, out_matched, nullptr);
+                     HostOut{out_doc, out_seg, out_score, out_count, stats, out_matched});
 }
 
 slg_batch *slg_batch_prepare_phrase(slg_index *ix, uint32_t nq, const uint32_t *q_offsets, const uint32_t *q_term_ids,
                                     const float *q_weights, const slg_score_plans *plans, const int32_t *q_filter,
                                     const slg_sort_spec *sort, const slg_bool_spec *boolean,
                                     const slg_phrase_spec *phrases, uint32_t k, int strategy) {
-  return prepare_impl(ix, nq, q_offsets, q_term_ids, q_weights, plans, q_filter, sort, k, strategy, false, nullptr,
-                      false, nullptr, false, nullptr, false, boolean, true, phrases, true);
+  PrepareRequest r{ix, nq, q_offsets, q_term_ids, q_weights, plans, q_filter, k, strategy};
+  r.sort = if_given(sort);
+  r.boolean = {true, boolean};  // (NULL: the batch has no term groups)
+  r.phrase = {true, phrases};
+  return prepare_impl(r);
 }
 
 int slg_search_batch_phrase(slg_index *ix, uint32_t nq, const uint32_t *q_offsets, const uint32_t *q_term_ids,
@@ -897,7 +894,7 @@ int slg_search_batch_phrase(slg_index *ix, uint32_t nq, const uint32_t *q_offset
                             uint32_t *out_count, slg_stats *stats, uint64_t *out_matched) {
   return run_to_host(slg_batch_prepare_phrase(ix, nq, q_offsets, q_term_ids, q_weights, plans, q_filter, sort,
                                               boolean, phrases, k, strategy),
-                     out_doc, out_seg, out_score, out_count, stats, out_matched, nullptr);
+                     HostOut{out_doc, out_seg, out_score, out_count, stats, out_matched});
 }
 
 int slg_batch_cursor_seen(slg_batch *b, uint8_t *out_seen) {
@@ -924,7 +921,7 @@ int slg_search_batch_after(slg_index *ix, const slg_query *queries, uint32_t nq,
   if (rc != SLG_OK) return rc;
   return run_to_host(slg_batch_prepare_after(ix, nq, fq.offs.data(), fq.tids.data(), fq.ws.data(), plans, q_filter,
                                              sort, q_cursor, k, strategy),
-                     out_doc, out_seg, out_score, out_count, nullptr, out_matched, out_seen);
+                     HostOut{out_doc, out_seg, out_score, out_count, nullptr, out_matched, out_seen});
 }
 
 int slg_merge_shards_device(slg_index *ix, uint32_t n_shards, uint32_t nq, uint32_t k,

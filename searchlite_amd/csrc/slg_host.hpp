@@ -612,15 +612,73 @@ struct Staging {
 void release_batch_buffers(slg_batch *b, bool to_pool);
 // slg_batch.hip: the merge of several ranks' (or shards') rows
 void launch_shard_merge(const slg::ShardMergeParams &mp, hipStream_t st);
-// slg_batch.hip: slg_batch_prepare_hybrid (the planning of slg_batch_prepare_plans with BatchIn::sorted)
-slg_batch *prepare_hybrid_batch(slg_index *ix, uint32_t nq, const uint32_t *q_offsets, const uint32_t *q_term_ids,
-                                const float *q_weights, const slg_score_plans *plans, const int32_t *q_filter,
-                                uint32_t k, int strategy);
+// slg_batch.hip: every slg_batch_prepare* is one PrepareRequest.  The query arrays, and one member per batch
+// kind; a kind that was asked for and its spec travel together, so a kind asked for with a NULL spec still
+// reaches its check.  (hybrid and aggs plan as slg_batch_prepare_plans / _sorted with BatchIn::sorted)
+template <typename T>
+struct Asked {
+  bool on = false;
+  const T *spec = nullptr;
+};
+struct PrepareRequest {
+  slg_index *ix;
+  uint32_t nq;
+  const uint32_t *q_offsets, *q_term_ids;
+  const float *q_weights;
+  const slg_score_plans *plans;
+  const int32_t *q_filter;
+  uint32_t k;
+  int strategy;
+  Asked<slg_sort_spec> sort;      // off: score order
+  Asked<slg_sort_cursor> cursor;  // slg_batch_prepare_after
+  bool hybrid = false;            // slg_batch_prepare_hybrid
+  Asked<slg_agg_spec> aggs;
+  Asked<slg_rescore_spec> rescore;
+  Asked<slg_bool_spec> boolean;   // a phrase batch: on, its spec may be NULL (no term groups)
+  Asked<slg_phrase_spec> phrase;
+};
+// a spec that is a kind of its own only when it is given (the sort of a bool, phrase, cursor or agg batch)
+template <typename T>
+Asked<T> if_given(const T *spec) {
+  return Asked<T>{spec != nullptr, spec};
+}
+slg_batch *prepare_impl(const PrepareRequest &r);
 
-// slg_batch.hip: slg_batch_prepare_aggs (the planning of slg_batch_prepare_plans / _sorted with BatchIn::sorted)
-slg_batch *prepare_agg_batch(slg_index *ix, uint32_t nq, const uint32_t *q_offsets, const uint32_t *q_term_ids,
-                             const float *q_weights, const slg_score_plans *plans, const int32_t *q_filter,
-                             const slg_sort_spec *sort, const slg_agg_spec *aggs, uint32_t k, int strategy);
+// the tables of a batch kind: host arrays back to back as one image in a pooled device buffer, one copy
+struct ImagePart {
+  const void *p;
+  size_t bytes;
+};
+template <typename T>
+ImagePart image_part(const std::vector<T> &v) {
+  return ImagePart{v.data(), v.size() * sizeof(T)};
+}
+inline void upload_image(DevBuf &dst, BufPool *pool, std::initializer_list<ImagePart> parts) {
+  std::vector<unsigned char> image;
+  for (const ImagePart &pt : parts)
+    image.insert(image.end(), static_cast<const unsigned char *>(pt.p), static_cast<const unsigned char *>(pt.p) + pt.bytes);
+  dst.alloc_pooled(pool, image.size());
+  if (!image.empty()) SLG_HIP(hipMemcpy(dst.p, image.data(), image.size(), hipMemcpyHostToDevice));
+}
+
+// what the launches of the two clause-filter kernels share (P: slg::BoolFilterParams, slg_clause.hpp): the
+// slices, the candidates and the term groups' tables of a bool or phrase batch
+template <typename P>
+void fill_clause_filter(P &p, const slg_batch *b) {
+  p.segs = b->snap->d_segs.template as<slg::SegDev>();
+  p.sq = b->d_sq;
+  p.slice_sq = b->d_slice_sq;
+  p.queries = b->d_bool_desc.as<const slg::BoolQuery>();
+  p.terms = reinterpret_cast<const slg::BoolTerm *>(b->d_bool_desc.as<unsigned char>() +
+                                                    (size_t)b->nq * sizeof(slg::BoolQuery));
+  p.cand = b->d_cand.as<uint2>();
+  p.slice_cbeg = b->d_slice_cbeg.as<uint64_t>();
+  p.slice_ccnt = b->d_slice_ccnt.as<uint32_t>();
+  p.q_scored = b->d_q_scored.as<uint32_t>();
+  p.n_slices = b->n_slices;
+  p.n_segs = (uint32_t)b->snap->segs.size();
+}
+
 // slg_aggs.hip: the checks of a spec that need no index (throws); the spec against the batch's state, the
 // tables' layout and the device buffers (throws; the batch is otherwise prepared); the launch behind the
 // batch's select kernel

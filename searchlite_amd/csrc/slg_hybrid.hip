@@ -121,7 +121,9 @@ slg_batch *slg_batch_prepare_hybrid(slg_index *ix, uint32_t nq, const uint32_t *
                                     const uint32_t *q_term_ids, const float *q_weights,
                                     const slg_score_plans *plans, const int32_t *q_filter, uint32_t k,
                                     int strategy) {
-  return prepare_hybrid_batch(ix, nq, q_offsets, q_term_ids, q_weights, plans, q_filter, k, strategy);
+  PrepareRequest r{ix, nq, q_offsets, q_term_ids, q_weights, plans, q_filter, k, strategy};
+  r.hybrid = true;
+  return prepare_impl(r);
 }
 
 int slg_batch_hybrid_device(slg_batch *b, uint32_t n_clauses, const uint32_t *clause_field, const float *d_qvecs,

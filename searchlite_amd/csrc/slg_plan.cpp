@@ -918,6 +918,29 @@ void check_rescore(const slg_rescore_spec *spec, uint32_t nq, uint32_t k) {
       throw SlgError(SLG_ERR_UNSUPPORTED, "rescore window of query " + std::to_string(q) + " > SLG_MAX_RESCORE_WINDOW");
 }
 
+namespace {
+// The list of term `tid` in a segment: off in the padded layout (SegDev), ubase its first posting in the
+// unpadded order, df its length.  false (nothing written): SLG_NO_TERM, the segment has no such term.
+// what: "rescore" / "bool" / "phrase", for the message of an id out of range
+bool resolve_term(const SegView &sh, uint32_t tid, const char *what, uint32_t q, uint64_t &off, uint64_t &ubase,
+                  uint32_t &df) {
+  if (tid == SLG_NO_TERM) return false;
+  PLAN_REQUIRE(tid < sh.n_terms, std::string("term id out of range in ") + what + " query " + std::to_string(q));
+  ubase = sh.term_offsets[tid];
+  off = ubase + (uint64_t)slg::kListPad * tid;
+  df = (uint32_t)(sh.term_offsets[tid + 1] - ubase);
+  return true;
+}
+bool clause_kind_known(int32_t kind) {
+  return kind == SLG_BOOL_MUST || kind == SLG_BOOL_SHOULD || kind == SLG_BOOL_MUST_NOT;
+}
+// a bool or phrase batch states its minimum in q_min_should: the score plans must not state one too
+void require_no_min_match(const slg_score_plans *plans, uint32_t q, const char *what, const std::string &in_q) {
+  PLAN_REQUIRE(!plans || !plans->q_min_match || plans->q_min_match[q] <= 1u,
+               std::string("q_min_match > 1 in the score plans of a ") + what + " batch (q_min_should states it)" + in_q);
+}
+}  // namespace
+
 void plan_rescore(const std::vector<SegView> &segs, uint32_t nq, uint32_t k, const slg_rescore_spec &spec,
                   RescorePlan &out) {
   const uint32_t n_segs = (uint32_t)segs.size();
@@ -950,16 +973,11 @@ void plan_rescore(const std::vector<SegView> &segs, uint32_t nq, uint32_t k, con
     for (uint32_t j = 0; j < nt; j++) {
       const uint32_t i = order[j];
       for (uint32_t s = 0; s < n_segs; s++) {
-        const SegView &sh = segs[s];
         slg::RescoreTerm rt{};
         rt.weight = spec.q_weights[t0 + i];
         rt.leaf = spec.q_leaf ? spec.q_leaf[t0 + i] : i;
-        const uint32_t tid = spec.q_term_ids[(size_t)(t0 + i) * n_segs + s];
-        if (tid != SLG_NO_TERM) {
-          PLAN_REQUIRE(tid < sh.n_terms, "term id out of range in rescore query " + std::to_string(q));
-          rt.df = (uint32_t)(sh.term_offsets[tid + 1] - sh.term_offsets[tid]);
-          rt.off = sh.term_offsets[tid] + (uint64_t)slg::kListPad * tid;  // padded layout (SegDev)
-        }
+        uint64_t ubase;
+        resolve_term(segs[s], spec.q_term_ids[(size_t)(t0 + i) * n_segs + s], "rescore", q, rt.off, ubase, rt.df);
         out.terms.push_back(rt);
       }
     }
@@ -1000,11 +1018,9 @@ void check_bool(const slg_bool_spec *spec, uint32_t nq, const slg_score_plans *p
     PLAN_REQUIRE(next == ng, "a group without a term" + in_q);
     for (uint32_t g = 0; g < ng; g++) {
       const int32_t kind = spec->g_kind[g0 + g];
-      PLAN_REQUIRE(kind == SLG_BOOL_MUST || kind == SLG_BOOL_SHOULD || kind == SLG_BOOL_MUST_NOT,
-                   "unknown clause kind" + in_q);
+      PLAN_REQUIRE(clause_kind_known(kind), "unknown clause kind" + in_q);
     }
-    PLAN_REQUIRE(!plans || !plans->q_min_match || plans->q_min_match[q] <= 1u,
-                 "q_min_match > 1 in the score plans of a bool batch (q_min_should states it)" + in_q);
+    require_no_min_match(plans, q, "bool", in_q);
   }
   for (uint32_t q = 0; q < nq; q++) {
     if (spec->g_offsets[q + 1] - spec->g_offsets[q] > SLG_MAX_BOOL_GROUPS)
@@ -1043,17 +1059,12 @@ void plan_bool(const std::vector<SegView> &segs, uint32_t nq, const slg_bool_spe
       if (kind == SLG_BOOL_MUST_NOT) bq.n_must_not = n - bq.n_must;
     }
     for (uint32_t s = 0; s < n_segs; s++) {
-      const SegView &sh = segs[s];
       for (uint32_t j = 0; j < nt; j++) {
         const uint32_t i = order[j];
         slg::BoolTerm bt{};
         bt.group = spec.c_group[t0 + i];
-        const uint32_t tid = spec.c_term_ids[(size_t)(t0 + i) * n_segs + s];
-        if (tid != SLG_NO_TERM) {
-          PLAN_REQUIRE(tid < sh.n_terms, "term id out of range in bool query " + std::to_string(q));
-          bt.df = (uint32_t)(sh.term_offsets[tid + 1] - sh.term_offsets[tid]);
-          bt.off = sh.term_offsets[tid] + (uint64_t)slg::kListPad * tid;  // padded layout (SegDev)
-        }
+        uint64_t ubase;
+        resolve_term(segs[s], spec.c_term_ids[(size_t)(t0 + i) * n_segs + s], "bool", q, bt.off, ubase, bt.df);
         out.terms.push_back(bt);
       }
     }
@@ -1110,14 +1121,10 @@ void check_phrase(const slg_bool_spec *boolean, const slg_phrase_spec *spec, uin
       }
       for (uint32_t p = p0; p < p1; p++) {
         const int32_t kind = spec->p_kind[p];
-        PLAN_REQUIRE(kind == SLG_BOOL_MUST || kind == SLG_BOOL_SHOULD || kind == SLG_BOOL_MUST_NOT,
-                     "unknown phrase kind (phrase " + std::to_string(p) + ")");
+        PLAN_REQUIRE(clause_kind_known(kind), "unknown phrase kind (phrase " + std::to_string(p) + ")");
       }
     }
-    for (uint32_t q = 0; q < nq; q++)
-      PLAN_REQUIRE(!plans || !plans->q_min_match || plans->q_min_match[q] <= 1u,
-                   "q_min_match > 1 in the score plans of a phrase batch (q_min_should states it) in query " +
-                       std::to_string(q));
+    for (uint32_t q = 0; q < nq; q++) require_no_min_match(plans, q, "phrase", " in query " + std::to_string(q));
   }
   if (boolean) check_bool(boolean, nq, plans);
   for (uint32_t q = 0; q < nq; q++) {
@@ -1202,16 +1209,9 @@ void plan_phrase(const std::vector<SegView> &segs, uint32_t nq, const slg_bool_s
           slg::PhraseTerm row[SLG_MAX_PHRASE_TERMS];
           for (uint32_t i = 0; i < n; i++) {
             row[i] = slg::PhraseTerm{};
-            const uint32_t tid = spec.t_term_ids[(size_t)(t0 + i) * n_segs + s];
-            if (tid == SLG_NO_TERM) {
-              survives = false;
-              continue;
-            }
-            PLAN_REQUIRE(tid < sh.n_terms, "term id out of range in phrase query " + std::to_string(q));
-            row[i].ubase = sh.term_offsets[tid];
-            row[i].off = sh.term_offsets[tid] + (uint64_t)slg::kListPad * tid;  // padded layout (SegDev)
-            row[i].df = (uint32_t)(sh.term_offsets[tid + 1] - sh.term_offsets[tid]);
-            survives = survives && row[i].df != 0;
+            survives = resolve_term(sh, spec.t_term_ids[(size_t)(t0 + i) * n_segs + s], "phrase", q, row[i].off,
+                                    row[i].ubase, row[i].df) &&
+                       survives && row[i].df != 0;
           }
           for (uint32_t i = 0; i < n; i++) {
             if (!survives) row[i].df = 0;  // dropped in this segment: the kernel reads the first term's df

@@ -14,12 +14,7 @@ void slghost::rescore_attach(slg_batch *b, const slgplan::RescorePlan &rp) {
   b->rescore = true;
   b->rs_lds_rows = (std::max(rp.max_window, 2u) + 1u) & ~1u;  // even: the table behind the rows stays 8-byte aligned
   b->rs_max_table = rp.max_table;
-  const size_t q_bytes = rp.queries.size() * sizeof(slg::RescoreQuery), t_bytes = rp.terms.size() * sizeof(slg::RescoreTerm);
-  std::vector<unsigned char> image(q_bytes + t_bytes);
-  if (q_bytes) std::memcpy(image.data(), rp.queries.data(), q_bytes);
-  if (t_bytes) std::memcpy(image.data() + q_bytes, rp.terms.data(), t_bytes);
-  b->d_rs_desc.alloc_pooled(&ix->pool, image.size());
-  if (!image.empty()) SLG_HIP(hipMemcpy(b->d_rs_desc.p, image.data(), image.size(), hipMemcpyHostToDevice));
+  upload_image(b->d_rs_desc, &ix->pool, {image_part(rp.queries), image_part(rp.terms)});
   b->d_rs_side.alloc_pooled(&ix->pool, 3 * (size_t)b->nq * b->k * 4);
 }
 

@@ -66,20 +66,6 @@ constexpr int u4_waves(int kregs, int ml, bool plan = false) {
 typedef uint32_t u32x4_t __attribute__((ext_vector_type(4)));
 typedef u32x4_t U4x4 __attribute__((aligned(4)));
 
-// *src read through the constant address space (scalar loads when the address is wave-uniform): for
-// data written before the kernel starts and never during it
-template <typename T>
-__device__ __forceinline__ T load_const(const T *src) {
-  static_assert(sizeof(T) % 4 == 0, "whole words");
-  typedef const __attribute__((address_space(4))) uint32_t *c_u32_t;
-  const c_u32_t w = (c_u32_t)(uintptr_t)src;
-  T out;
-  uint32_t *dst = reinterpret_cast<uint32_t *>(&out);
-#pragma unroll
-  for (unsigned i = 0; i < sizeof(T) / 4; i++) dst[i] = w[i];
-  return out;
-}
-
 // PLAN: the batch has score plans (query/planner.rs:113-153, flat: Sum or DisMax over leaves that sum
 // one or more terms each): the lists arrive sorted by leaf and the join closes a doc's leaves in leaf
 // order.  Its own instantiation: the flat-sum batches (BASELINE configs 2, 3, 5) keep their registers.

@@ -32,6 +32,22 @@ __device__ __forceinline__ uint32_t rfl(uint32_t v) {
 __device__ __forceinline__ uint32_t rl(uint32_t v, uint32_t lane) {
   return (uint32_t)__builtin_amdgcn_readlane((int)v, (int)lane);
 }
+__device__ __forceinline__ uint64_t uniform64(uint64_t v) {
+  return ((uint64_t)rfl((uint32_t)(v >> 32)) << 32) | rfl((uint32_t)v);
+}
+// *src read through the constant address space (scalar loads when the address is wave-uniform): for
+// data written before the kernel starts and never during it
+template <typename T>
+__device__ __forceinline__ T load_const(const T *src) {
+  static_assert(sizeof(T) % 4 == 0, "whole words");
+  typedef const __attribute__((address_space(4))) uint32_t *c_u32_t;
+  const c_u32_t w = (c_u32_t)(uintptr_t)src;
+  T out;
+  uint32_t *dst = reinterpret_cast<uint32_t *>(&out);
+#pragma unroll
+  for (unsigned i = 0; i < sizeof(T) / 4; i++) dst[i] = w[i];
+  return out;
+}
 __device__ __forceinline__ uint32_t wave_sum(uint32_t v) {
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);

@@ -177,6 +177,42 @@ def test_many_slices(T):
         assert got[3].tolist()[:2] == [0, k] and got[3][2] > 0 and got[3][3] > 0
 
 
+def test_term_groups_alone_equal_the_bool_batch(T):
+    """A clause table of term groups only, once as a bool batch and once as a phrase batch whose spec gives no
+    query a phrase (q_min_should moves to it): the phrase kernel's term pass may then accept early, as the bool
+    kernel's does, and both batches return the same rows, counts, scored_docs and matched counts, bit for bit.
+    Rows of 1, 4, 5 and 9 clause terms (a full step, a step with one live list, three steps) over lists of df 0
+    (an absent term), 1, 63, 64, 65 and 129, against regions of 1, 63, 64, 65 and 129 candidates."""
+    W, tok = T, T.tok
+    mix = [(MUST, [ALL, tok["c1"]]), (MUST, [tok["c129"], tok["c65"]]), (MUST_NOT, [tok["k64"]]),  # MUST_NOT: the 5th term
+           (SHOULD, [tok["c63"]]), (SHOULD, [tok["c64"], NO_TERM]), (SHOULD, [tok["k65"]])]
+    table = [("c129", [(MUST, [tok["k63"]])], 0),                                                  # MUST only, 1 term
+             ("c63", [(MUST_NOT, [tok["c1"], NO_TERM]), (MUST_NOT, [tok["c64"], tok["none"]])], 0),  # MUST_NOT only, 4
+             ("c64", [(SHOULD, [tok["c63"], tok["c65"]]), (SHOULD, [tok["c129"]]), (SHOULD, [ALL, NO_TERM])], 2),  # 5
+             ("c65", mix, 1), ("c129", mix, 1),                                                    # 9 terms
+             ("c1", [(MUST, [tok["c1"]])], 0), ("c129", [(SHOULD, [tok["k65"]]), (SHOULD, [NO_TERM])], 2)]
+    assert [sum(len(t) for _, t in groups) for _, groups, _ in table] == [1, 4, 5, 9, 9, 1, 2]
+    qs = one_term_queries([tok[nm] for nm, _, _ in table])
+    as_bool = B.clauses_of([(groups, ms) for _, groups, ms in table], 1)
+    cl, ph = specs_of([(groups, [], ms) for _, groups, ms in table], 1)
+    assert "q_min_should" not in cl and ph["p_offsets"].tolist() == [0] * (len(table) + 1)
+    left = B.scored_docs(W.segs, qs[0], qs[1], as_bool).tolist()
+    assert left[0] == 63 and left[5] == 1 and left[6] == 0 and 0 < left[1] < 63 and 0 < left[2] < 64
+    score_order = [("_score", "desc")]  # (a sort spec: the batch has matched counts)
+    for k in (1, 11):
+        for sort in (None, score_order):
+            what = f"term groups alone k={k} sort={sort}"
+            a = W.ix.search_batch_bool(*qs, k, as_bool, sort=sort, want_stats=True)
+            b = W.ix.search_batch_phrase(*qs, k, ph, clauses=cl, sort=sort, want_stats=True)
+            same(b[:4], a[:4], what)
+            for q in range(len(table)):
+                assert int(b[4][q].scored_docs) == int(a[4][q].scored_docs) == left[q], f"{what}: scored_docs of query {q}"
+                assert int(b[4][q].candidates_examined) == int(a[4][q].candidates_examined)
+            assert a[3].tolist() == [min(x, k) for x in left], what
+            if sort is not None:
+                assert np.array_equal(np.asarray(b[5]), np.asarray(a[5])) and np.asarray(a[5]).tolist() == left, what
+
+
 # ---- world S: crafted docs for the phrase shapes; every doc starts with term 0 (the scored term) ----
 S_DOCS = [
     [0, 1, 2, 3, 4, 5, 6, 7, 8],          # 0: the 8-term phrase 1..8

@@ -22,6 +22,53 @@ inline uint32_t full_mask(uint32_t n) { return n >= 32 ? 0xFFFFFFFFu : ((1u << n
 static_assert(slg::kMaxPlanDepth == SLG_MAX_PLAN_DEPTH, "the kernels' level arrays and the ABI's depth limit");
 constexpr uint32_t kMaxPlanNodes = 255;  // leaves / groups of a two-level plan (8-bit fields of TermRef::gmeta)
 
+// ---- score trees given node by node (slg_score_plans::q_node_offsets) ---------------------------
+struct TreeShape {
+  uint32_t n_leaf = 0, deepest = 0;  // leaves, depth of the deepest one (the root: 0)
+};
+
+// The one walk over a query's tree (pre-order): depth of every node, leaves, deepest leaf.
+// kCheck = validate_batch's walk: it refuses a malformed tree before anything indexes through it;
+// resolve_tree walks the trees that passed.
+template <bool kCheck>
+TreeShape walk_tree(const slg_score_plans &pl, uint32_t q, uint32_t *depth_of) {
+  const uint32_t n0 = pl.q_node_offsets[q], nn = pl.q_node_offsets[q + 1] - n0;
+  const int32_t *kind = pl.node_kind + n0;
+  const uint32_t *par = pl.node_parent + n0;
+  [[maybe_unused]] uint32_t kids[2 * kMaxPlanNodes + 1];
+  TreeShape t;
+  for (uint32_t i = 0; i < nn; i++) {
+    const int kd = kind[i];
+    if constexpr (kCheck) {
+      PLAN_REQUIRE(kd == SLG_PLAN_SUM || kd == SLG_PLAN_DISMAX || kd == SLG_PLAN_LEAF, "unknown node kind in query " + std::to_string(q));
+      kids[i] = 0;
+      if (i != 0) {
+        PLAN_REQUIRE(par[i] < i, "node_parent must name an earlier node (pre-order) in query " + std::to_string(q));
+        PLAN_REQUIRE(kind[par[i]] != SLG_PLAN_LEAF, "a leaf node has a child in query " + std::to_string(q));
+      }
+    }
+    depth_of[i] = i == 0 ? 0u : depth_of[par[i]] + 1u;
+    if constexpr (kCheck)
+      if (i != 0) {
+        // pre-order: the parent is the last node before i whose depth is smaller
+        PLAN_REQUIRE(par[i] == i - 1 || depth_of[i - 1] >= depth_of[i], "nodes are not in pre-order in query " + std::to_string(q));
+        kids[par[i]]++;
+      }
+    if (kd == SLG_PLAN_LEAF) {
+      t.n_leaf++;
+      t.deepest = std::max(t.deepest, depth_of[i]);
+    } else if (kCheck && kd == SLG_PLAN_DISMAX) {
+      const float tie = pl.node_tie[n0 + i];
+      PLAN_REQUIRE(tie >= 0.0f && tie <= 1.0f, "tie breaker outside [0, 1] in query " + std::to_string(q));
+    }
+  }
+  if constexpr (kCheck)
+    for (uint32_t i = 0; i < nn; i++)
+      if (kind[i] != SLG_PLAN_LEAF && kids[i] == 0)
+        throw SlgError(SLG_ERR_UNSUPPORTED, "a Sum / DisMax node without children in query " + std::to_string(q));
+  return t;
+}
+
 // ---- validation of the caller's arrays (cheap, before anything indexes through them) ------------
 struct BatchFacts {
   uint32_t total_terms = 0;
@@ -31,14 +78,13 @@ struct BatchFacts {
   bool nested_requested = false; // some query names groups of leaves
 };
 
-BatchFacts validate_batch(const BatchIn &in, uint32_t n_segs) {
+BatchFacts validate_batch(const BatchIn &in) {
   BatchFacts f;
   PLAN_REQUIRE(in.nq == 0 || in.q_offsets != nullptr, "q_offsets is NULL");
   PLAN_REQUIRE(in.strategy == SLG_STRATEGY_BM25 || in.strategy == SLG_STRATEGY_WAND ||
                    in.strategy == SLG_STRATEGY_BMW,
                "unknown strategy");
   if (in.k > SLG_MAX_K) throw SlgError(SLG_ERR_UNSUPPORTED, "k > SLG_MAX_K (" + std::to_string(SLG_MAX_K) + ")");
-  (void)n_segs;
   f.total_terms = in.nq ? in.q_offsets[in.nq] : 0;
   PLAN_REQUIRE(f.total_terms == 0 || (in.q_term_ids && in.q_weights), "q_term_ids/q_weights is NULL");
   for (uint32_t q = 0; q < in.nq; q++) {
@@ -63,46 +109,20 @@ BatchFacts validate_batch(const BatchIn &in, uint32_t n_segs) {
   if (trees) {
     for (uint32_t q = 0; q < in.nq; q++) {
       PLAN_REQUIRE(pl.q_node_offsets[q + 1] >= pl.q_node_offsets[q], "q_node_offsets not monotone");
-      const uint32_t n0 = pl.q_node_offsets[q], nn = pl.q_node_offsets[q + 1] - n0;
+      const uint32_t nn = pl.q_node_offsets[q + 1] - pl.q_node_offsets[q];
       PLAN_REQUIRE(nn >= 1, "a score tree has no node in query " + std::to_string(q));
       if (nn > 2 * kMaxPlanNodes)
         throw SlgError(SLG_ERR_UNSUPPORTED, "score tree of query " + std::to_string(q) + " has too many nodes");
-      uint32_t depth_of[2 * kMaxPlanNodes + 1], kids[2 * kMaxPlanNodes + 1];
-      uint32_t n_leaf = 0, deepest = 0;
-      for (uint32_t i = 0; i < nn; i++) {
-        const int kd = pl.node_kind[n0 + i];
-        PLAN_REQUIRE(kd == SLG_PLAN_SUM || kd == SLG_PLAN_DISMAX || kd == SLG_PLAN_LEAF, "unknown node kind in query " + std::to_string(q));
-        kids[i] = 0;
-        if (i == 0) {
-          depth_of[0] = 0;
-        } else {
-          const uint32_t pa = pl.node_parent[n0 + i];
-          PLAN_REQUIRE(pa < i, "node_parent must name an earlier node (pre-order) in query " + std::to_string(q));
-          PLAN_REQUIRE(pl.node_kind[n0 + pa] != SLG_PLAN_LEAF, "a leaf node has a child in query " + std::to_string(q));
-          // pre-order: the parent is the last node before i whose depth is smaller
-          depth_of[i] = depth_of[pa] + 1;
-          PLAN_REQUIRE(pa == i - 1 || depth_of[i - 1] >= depth_of[i], "nodes are not in pre-order in query " + std::to_string(q));
-          kids[pa]++;
-        }
-        if (kd == SLG_PLAN_LEAF) {
-          n_leaf++;
-          deepest = std::max(deepest, depth_of[i]);
-        } else if (kd == SLG_PLAN_DISMAX) {
-          const float t = pl.node_tie[n0 + i];
-          PLAN_REQUIRE(t >= 0.0f && t <= 1.0f, "tie breaker outside [0, 1] in query " + std::to_string(q));
-        }
-      }
-      for (uint32_t i = 0; i < nn; i++)
-        if (pl.node_kind[n0 + i] != SLG_PLAN_LEAF && kids[i] == 0)
-          throw SlgError(SLG_ERR_UNSUPPORTED, "a Sum / DisMax node without children in query " + std::to_string(q));
-      if (n_leaf > kMaxPlanNodes) throw SlgError(SLG_ERR_UNSUPPORTED, "score tree of query " + std::to_string(q) + " has too many leaves");
-      if (deepest > SLG_MAX_PLAN_DEPTH)
+      uint32_t depth_of[2 * kMaxPlanNodes + 1];
+      const TreeShape tree = walk_tree<true>(pl, q, depth_of);
+      if (tree.n_leaf > kMaxPlanNodes) throw SlgError(SLG_ERR_UNSUPPORTED, "score tree of query " + std::to_string(q) + " has too many leaves");
+      if (tree.deepest > SLG_MAX_PLAN_DEPTH)
         throw SlgError(SLG_ERR_UNSUPPORTED, "score tree of query " + std::to_string(q) + " is deeper than SLG_MAX_PLAN_DEPTH");
       const uint32_t t0 = in.q_offsets[q], nt = in.q_offsets[q + 1] - t0;
       for (uint32_t i = 0; i < nt; i++)
-        PLAN_REQUIRE((pl.q_leaf ? pl.q_leaf[t0 + i] : i) < n_leaf, "a term names a leaf the tree does not have in query " + std::to_string(q));
+        PLAN_REQUIRE((pl.q_leaf ? pl.q_leaf[t0 + i] : i) < tree.n_leaf, "a term names a leaf the tree does not have in query " + std::to_string(q));
       f.plans_requested = true;  // (resolved per query: a one-level tree of single-term leaves still is the flat sum)
-      if (deepest >= 2) f.nested_requested = true;
+      if (tree.deepest >= 2) f.nested_requested = true;
     }
     return f;
   }
@@ -159,17 +179,146 @@ BatchFacts validate_batch(const BatchIn &in, uint32_t n_segs) {
 }
 
 // ---- pass 1: sub-queries (query x segment) and their terms ---------------------------------------
+// Per query (plan_queries): resolve_plan -> per segment: build_subquery -> seed_and_classify.
+
+// Score plan of one query (query/planner.rs:113-153), resolved from whichever form the caller used: root
+// over leaves (q_plan / q_leaf), root over groups of leaves (leaf_group / group_plan), or a tree given node
+// by node, which becomes one of the first two when it has one or two levels and a canonical node table
+// otherwise.  One object serves every query of a plan_queries call: resolve_plan assigns the scalars and
+// pointers per query, the arrays are scratch that only the queries needing them write.
+struct QueryPlan {
+  int kind;  // the root: SLG_PLAN_SUM | SLG_PLAN_DISMAX
+  float tie;
+  uint32_t min_match, n_leaves;
+  // two-level plan: group of every leaf, leaves per group (nested: it is not the flat plan in disguise)
+  bool groups, nested;
+  uint32_t n_groups;
+  const uint32_t *lgroup;  // (these three: the caller's arrays, or tree_* below)
+  const int32_t *gplan;
+  const float *gtie;
+  uint32_t leaves_in_group[kMaxPlanNodes + 1];  // (zeroed only for queries with groups: 1 KB per query otherwise)
+  // deep tree: levels of internal nodes (0: none), first canonical node, canonical node every leaf hangs off
+  uint32_t depth, node_begin;
+  uint32_t leaf_node[kMaxPlanNodes + 1];
+  // the group view of a two-level tree; depth of every node of the tree
+  uint32_t tree_lgroup[kMaxPlanNodes + 1];
+  int32_t tree_gplan[kMaxPlanNodes + 1];
+  float tree_gtie[kMaxPlanNodes + 1];
+  uint32_t depth_of[2 * kMaxPlanNodes + 1];
+};
+
+// deep tree: canonical node table — the internal nodes in pre-order, and under every leaf that
+// hangs above the deepest level a chain of one-child Sum nodes down to it
+void build_node_table(const slg_score_plans &pl, uint32_t q, std::vector<slg::PlanNode> &nodes, QueryPlan &p) {
+  const uint32_t n0 = pl.q_node_offsets[q], nn = pl.q_node_offsets[q + 1] - n0;
+  const int32_t *kind = pl.node_kind + n0;
+  const float *ntie = pl.node_tie + n0;
+  const uint32_t *par = pl.node_parent + n0;
+  p.node_begin = (uint32_t)nodes.size();
+  uint32_t canon[2 * kMaxPlanNodes + 1];  // original internal node -> canonical index
+  uint32_t lf = 0;
+  for (uint32_t i = 0; i < nn; i++) {
+    if (kind[i] != SLG_PLAN_LEAF) {
+      const bool dismax = kind[i] == SLG_PLAN_DISMAX;
+      canon[i] = (uint32_t)nodes.size() - p.node_begin;
+      nodes.push_back(slg::PlanNode{i == 0 ? 0u : canon[par[i]], 0u, dismax ? 1u : 0u, dismax ? ntie[i] : 0.0f});
+      if (i != 0) nodes[p.node_begin + canon[par[i]]].n_children++;
+    } else {
+      uint32_t above = canon[par[i]];
+      nodes[p.node_begin + above].n_children++;
+      for (uint32_t d = p.depth_of[i]; d < p.depth; d++) {  // pad: Sum of one child
+        nodes.push_back(slg::PlanNode{above, 1u, 0u, 0.0f});
+        above = (uint32_t)nodes.size() - 1u - p.node_begin;
+      }
+      p.leaf_node[lf++] = above;
+    }
+  }
+}
+
+// a tree given node by node (validate_batch has walked it): root, leaves, and the group view or node table
+void resolve_tree(const slg_score_plans &pl, uint32_t q, std::vector<slg::PlanNode> &nodes, QueryPlan &p) {
+  const uint32_t n0 = pl.q_node_offsets[q], nn = pl.q_node_offsets[q + 1] - n0;
+  const int32_t *kind = pl.node_kind + n0;
+  const float *ntie = pl.node_tie + n0;
+  const TreeShape tree = walk_tree<false>(pl, q, p.depth_of);
+  p.n_leaves = tree.n_leaf;
+  p.kind = kind[0] == SLG_PLAN_LEAF ? SLG_PLAN_SUM : kind[0];  // (the plan is one leaf: Sum of one leaf)
+  p.tie = kind[0] == SLG_PLAN_DISMAX ? ntie[0] : 0.0f;
+  if (tree.deepest > 2) {
+    p.depth = tree.deepest;
+    build_node_table(pl, q, nodes, p);
+  } else if (tree.deepest == 2) {  // root over groups (one level: root over leaves, nothing to add)
+    p.groups = true;
+    p.n_groups = 0;
+    uint32_t lf = 0;
+    for (uint32_t i = 1; i < nn; i++) {
+      if (p.depth_of[i] == 1) {  // a child of the root: a group (a bare leaf = a Sum group of one leaf)
+        p.tree_gplan[p.n_groups] = kind[i] == SLG_PLAN_DISMAX ? SLG_PLAN_DISMAX : SLG_PLAN_SUM;
+        p.tree_gtie[p.n_groups] = kind[i] == SLG_PLAN_DISMAX ? ntie[i] : 0.0f;
+        p.n_groups++;
+      }
+      if (kind[i] == SLG_PLAN_LEAF) p.tree_lgroup[lf++] = p.n_groups - 1u;
+    }
+    p.lgroup = p.tree_lgroup;
+    p.gplan = p.tree_gplan;
+    p.gtie = p.tree_gtie;
+  }
+}
+
+// step 1: the score plan of query q.  nodes: where a deep tree's canonical node table is appended
+void resolve_plan(const BatchIn &in, uint32_t q, std::vector<slg::PlanNode> &nodes, QueryPlan &p) {
+  const slg_score_plans &pl = in.plans;
+  p.kind = pl.q_plan ? pl.q_plan[q] : SLG_PLAN_SUM;
+  p.tie = pl.q_tie ? pl.q_tie[q] : 0.0f;
+  p.min_match = pl.q_min_match ? pl.q_min_match[q] : 0u;
+  p.n_leaves = pl.q_nleaves ? pl.q_nleaves[q] : 0;
+  p.groups = pl.leaf_group != nullptr && pl.q_node_offsets == nullptr;
+  p.lgroup = p.groups ? pl.leaf_group + pl.q_leaf_offsets[q] : nullptr;
+  p.n_groups = p.groups ? pl.q_group_offsets[q + 1] - pl.q_group_offsets[q] : 0u;
+  p.gplan = p.groups ? pl.group_plan + pl.q_group_offsets[q] : nullptr;
+  p.gtie = p.groups ? pl.group_tie + pl.q_group_offsets[q] : nullptr;
+  p.depth = p.node_begin = 0;
+  if (pl.q_node_offsets) {
+    resolve_tree(pl, q, nodes, p);
+  } else {
+    PLAN_REQUIRE(p.kind == SLG_PLAN_SUM || p.kind == SLG_PLAN_DISMAX,
+                 "unknown score plan in query " + std::to_string(q));
+    // validate_tie_breaker (query/planner.rs:850-856); the threshold seed and the pruning bounds
+    // also rely on it: with tie in [0, 1] a DisMax is >= each of its non-negative leaves
+    PLAN_REQUIRE(p.tie >= 0.0f && p.tie <= 1.0f, "tie breaker outside [0, 1] in query " + std::to_string(q));
+  }
+  const uint32_t t0 = in.q_offsets[q], nt = in.q_offsets[q + 1] - t0;
+  for (uint32_t i = 0; i < nt; i++) {
+    const uint32_t lf = pl.q_leaf ? pl.q_leaf[t0 + i] : i;
+    PLAN_REQUIRE(lf < 0x80000000u, "leaf index >= 2^31 in query " + std::to_string(q));
+    p.n_leaves = std::max(p.n_leaves, lf + 1u);
+  }
+  p.nested = false;
+  if (p.groups) {
+    std::memset(p.leaves_in_group, 0, sizeof(p.leaves_in_group));
+    if (!pl.q_node_offsets)
+      PLAN_REQUIRE(p.n_leaves == pl.q_nleaves[q], "a term names a leaf beyond q_nleaves in query " + std::to_string(q));
+    for (uint32_t l = 0; l < p.n_leaves; l++) p.leaves_in_group[p.lgroup[l]]++;
+    for (uint32_t g = 0; g < p.n_groups; g++)
+      if (p.leaves_in_group[g] != 1 || p.gplan[g] == SLG_PLAN_DISMAX) p.nested = true;
+  }
+}
+
+// what pass 2 and the accounting need of a sub-query beside its RoundQuery
+struct SqCount {
+  uint64_t ess, all;     // postings of the essential lists (what the round planner cuts), of all lists
+  uint32_t longest_all;  // longest list of the sub-query, classification aside
+};
+
 struct Pass1Out {
   std::vector<slg::RoundQuery> sqs;
   std::vector<slg::TermRef> terms;
-  std::vector<uint64_t> sq_postings, sq_postings_all;
-  std::vector<uint32_t> sq_longest_all;  // longest list of the sub-query, classification aside
-  double skip_est = 0.0;                 // postings block skipping is expected to leave unread
-  uint64_t n_postings = 0, n_ess = 0, n_noness = 0;
+  std::vector<SqCount> counts;  // [sqs.size()]
+  double skip_est = 0.0;        // postings block skipping is expected to leave unread
+  uint64_t n_postings = 0, n_ess = 0;
   uint32_t max_terms = 0;
   bool any_plan = false, any_filter = false, any_nested = false, any_deep = false;
   std::vector<slg::PlanNode> nodes;  // canonical node tables of this part's deep trees
-  std::exception_ptr err;
 };
 
 struct Pass1Ctx {
@@ -178,7 +327,6 @@ struct Pass1Ctx {
   const BatchIn &in;
   const BatchFacts &facts;
   bool maxscore_on;
-  std::vector<uint32_t> &q_sq_begin;
   std::vector<uint64_t> &q_postings;
 };
 
@@ -216,18 +364,127 @@ uint32_t classify_essential(const SegView &sh, const slg::TermRef *t, uint32_t n
   return ess_mask;
 }
 
-void plan_queries(const Pass1Ctx &c, const uint32_t q_lo, const uint32_t q_hi, Pass1Out &o) {
+// step 2: the term list of (query q, segment sq.seg), appended to `terms` and sorted by leaf, and the
+// plan fields of sq.  false: no term of the query has a posting in the segment (no sub-query)
+bool build_subquery(const Pass1Ctx &c, const QueryPlan &p, uint32_t q, std::vector<slg::TermRef> &terms,
+                    slg::RoundQuery &sq) {
   const BatchIn &in = c.in;
   const slg_score_plans &pl = in.plans;
   const uint32_t n_segs = (uint32_t)c.segs.size();
+  const SegView &sh = c.segs[sq.seg];
+  const uint32_t t0 = in.q_offsets[q], nt = in.q_offsets[q + 1] - t0;
+  sq.term_begin = (uint32_t)terms.size();
+  for (uint32_t i = 0; i < nt; i++) {
+    const uint32_t tid = in.q_term_ids[(size_t)(t0 + i) * n_segs + sq.seg];
+    if (tid == SLG_NO_TERM) continue;
+    PLAN_REQUIRE(tid < sh.n_terms, "term id out of range in query " + std::to_string(q));
+    const uint32_t df = (uint32_t)(sh.term_offsets[tid + 1] - sh.term_offsets[tid]);
+    if (df == 0) continue;  // wand.rs:441 filter(postings.len() > 0)
+    const float w = in.q_weights[t0 + i];
+    PLAN_REQUIRE(std::isfinite(w), "non-finite weight in query " + std::to_string(q));
+    slg::TermRef tr{};
+    tr.off = sh.term_offsets[tid] + (uint64_t)slg::kListPad * tid;  // padded layout (SegDev)
+    tr.df = df;
+    tr.weight = w;
+    tr.term = tid;
+    tr.leaf = pl.q_leaf ? pl.q_leaf[t0 + i] : i;
+    if (p.depth) {
+      tr.gmeta = p.leaf_node[tr.leaf];  // the canonical node the leaf hangs off
+    } else if (p.nested) {
+      const uint32_t g = p.lgroup[tr.leaf];
+      tr.gmeta = g | (p.leaves_in_group[g] << 8) | ((p.gplan[g] == SLG_PLAN_DISMAX ? 1u : 0u) << 16);
+      tr.gtie = p.gtie[g];
+    }
+    terms.push_back(tr);
+  }
+  sq.n_terms = (uint32_t)terms.size() - sq.term_begin;
+  if (sq.n_terms == 0) return false;
+  slg::TermRef *first = terms.data() + sq.term_begin;
+  // Lists go to the device sorted by leaf (stable: a leaf's terms keep the term order in
+  // which the reference adds them, wand.rs:488-497; a group's leaves are consecutive, so the
+  // lists are sorted by group too).  plan 0 = the flat term-order sum, which is what Sum
+  // gives when no leaf holds two terms.
+  if (pl.q_leaf)  // (without leaves given, leaf = term position: already in order)
+    std::stable_sort(first, first + sq.n_terms,
+                     [](const slg::TermRef &a, const slg::TermRef &b) { return a.leaf < b.leaf; });
+  bool shared = false;
+  uint32_t present = 0;
+  for (uint32_t i = 0; i < sq.n_terms; i++) {
+    const bool fresh = i == 0 || first[i].leaf != first[i - 1].leaf;
+    present += fresh ? 1u : 0u;
+    shared = shared || !fresh;
+  }
+  sq.plan = p.kind == SLG_PLAN_DISMAX ? 2u : ((shared || p.nested || p.depth) ? 1u : 0u);
+  if (p.min_match > 1u) {  // leaves are counted in the plan kernel's leaf close: Sum of leaves, bits 8.. = the count asked for
+    if (sq.plan == 0u) sq.plan = 1u;
+    sq.plan |= p.min_match << 8;
+  }
+  sq.tie = p.tie;
+  sq.max_init = present < p.n_leaves ? 0.0f : -INFINITY;
+  sq.n_leaves = p.n_leaves;
+  sq.n_groups = p.nested ? p.n_groups : 0u;
+  sq.depth = p.depth;
+  sq.node_begin = p.node_begin;
+  return true;
+}
+
+// step 3: seed and classify the sub-query whose lists are t[0 .. sq.n_terms): theta0, ess_mask, longest,
+// skip_mask (its expected saving is added to skip_est, list by list); returns its posting counts
+SqCount seed_and_classify(const Pass1Ctx &c, const slg::TermRef *t, uint32_t k, uint32_t min_match,
+                          slg::RoundQuery &sq, double &skip_est) {
+  const SegView &sh = c.segs[sq.seg];
+  // (minimum_should_match > 1: the champions behind the seed are single postings — docs the matcher may reject)
+  sq.theta0 = min_match > 1u ? 0.0f : threshold_seed(sh, t, sq.n_terms, k, sq.filter);
+  // MaxScore: by default for batches with a query of >= 5 terms (plan_batch drops the
+  // classification again when block skipping has nothing to gain);
+  // slg_tuning.pruning = 1 / 0 forces it on / off.  Never with score plans in the batch (the
+  // plan kernels have no classified path).
+  uint32_t ess_mask = full_mask(sq.n_terms);
+  if (c.in.strategy != SLG_STRATEGY_BM25 && sq.theta0 > 0.0f && !c.facts.plans_requested && sq.n_terms > 1 &&
+      c.maxscore_on)
+    ess_mask = classify_essential(sh, t, sq.n_terms, sq.theta0);
+  sq.ess_mask = ess_mask;
+  // the round planner works on the essential lists only
+  SqCount n{0, 0, 0};
+  uint32_t longest = 0, longest_df = 0, longest_all_df = 0;
+  for (uint32_t i = 0; i < sq.n_terms; i++) {
+    const uint32_t df = t[i].df;
+    n.all += df;
+    if (df > longest_all_df) {
+      longest_all_df = df;
+      n.longest_all = i;
+    }
+    if (!((ess_mask >> i) & 1u)) continue;
+    n.ess += df;
+    if (df > longest_df) {
+      longest_df = df;
+      longest = i;
+    }
+  }
+  sq.longest = longest;
+  // block skipping pays where a 64-posting block of a non-essential list usually holds no
+  // candidate doc: a block spans 64 * N / df docs, which hold 64 * P / df essential postings
+  // on average; blocks are tested only below 2 (>= e^-2 = 13 % of them can be skipped).
+  // Config 3's lists are all of similar density (>= 64 per block): no test, no cost.
+  sq.skip_mask = 0;
+  if (c.tn.block_max)
+    for (uint32_t i = 0; i < sq.n_terms && i < 32; i++) {
+      const uint64_t df = t[i].df;
+      if (!((ess_mask >> i) & 1u) && 64ull * n.ess < 2ull * df) {
+        sq.skip_mask |= 1u << i;
+        skip_est += (double)df * std::exp(-64.0 * (double)n.ess / (double)df);  // blocks without a candidate doc
+      }
+    }
+  return n;
+}
+
+void plan_queries(const Pass1Ctx &c, const uint32_t q_lo, const uint32_t q_hi, Pass1Out &o) {
+  const BatchIn &in = c.in;
+  const uint32_t n_segs = (uint32_t)c.segs.size();
   const uint32_t k = planning_k(in);
-  auto &sqs = o.sqs;
-  auto &terms = o.terms;
-  sqs.reserve((size_t)(q_hi - q_lo) * n_segs);
-  terms.reserve((size_t)(in.q_offsets[q_hi] - in.q_offsets[q_lo]) * n_segs);
-  o.sq_postings.reserve(sqs.capacity());
-  o.sq_postings_all.reserve(sqs.capacity());
-  o.sq_longest_all.reserve(sqs.capacity());
+  o.sqs.reserve((size_t)(q_hi - q_lo) * n_segs);
+  o.terms.reserve((size_t)(in.q_offsets[q_hi] - in.q_offsets[q_lo]) * n_segs);
+  o.counts.reserve(o.sqs.capacity());
   // the champion table is tens of MB (config 2: 71 MB) and a query touches one line of it per term
   // (cold for queries that were not planned just before): the lines of the query 8 ahead are
   // requested while this one is planned
@@ -245,11 +502,10 @@ void plan_queries(const Pass1Ctx &c, const uint32_t q_lo, const uint32_t q_hi, P
         }
       }
   };
+  QueryPlan plan;  // (one for the whole call: see QueryPlan)
   for (uint32_t q = q_lo; q < std::min(q_hi, q_lo + 8u); q++) prefetch_query(q);
   for (uint32_t q = q_lo; q < q_hi; q++) {
     if (q + 8u < q_hi) prefetch_query(q + 8u);
-    c.q_sq_begin[q] = (uint32_t)sqs.size();
-    const uint32_t t0 = in.q_offsets[q], nt = in.q_offsets[q + 1] - t0;
     uint32_t fq = 0;  // doc filter of the query (0 none, id + 1)
     if (in.q_filter && in.q_filter[q] >= 0) {
       PLAN_REQUIRE((size_t)in.q_filter[q] < in.n_filters && in.filter_live[in.q_filter[q]],
@@ -257,234 +513,24 @@ void plan_queries(const Pass1Ctx &c, const uint32_t q_lo, const uint32_t q_hi, P
       fq = (uint32_t)in.q_filter[q] + 1u;
       o.any_filter = true;
     }
-    // score plan of the query (query/planner.rs:113-153): root over leaves, root over groups of leaves,
-    // or (slg_score_plans::q_node_offsets) a tree given node by node, which is resolved here into one
-    // of the first two when it has one or two levels, and into a canonical node table otherwise
-    int plan_kind = pl.q_plan ? pl.q_plan[q] : SLG_PLAN_SUM;
-    float tie = pl.q_tie ? pl.q_tie[q] : 0.0f;
-    const uint32_t min_match = pl.q_min_match ? pl.q_min_match[q] : 0u;
-    uint32_t n_leaves = pl.q_nleaves ? pl.q_nleaves[q] : 0;
-    bool groups = pl.leaf_group != nullptr && pl.q_node_offsets == nullptr;
-    const uint32_t *lgroup = groups ? pl.leaf_group + pl.q_leaf_offsets[q] : nullptr;
-    uint32_t n_groups = groups ? pl.q_group_offsets[q + 1] - pl.q_group_offsets[q] : 0u;
-    const int32_t *gplan = groups ? pl.group_plan + pl.q_group_offsets[q] : nullptr;
-    const float *gtie = groups ? pl.group_tie + pl.q_group_offsets[q] : nullptr;
-    uint32_t tree_lgroup[kMaxPlanNodes + 1];
-    int32_t tree_gplan[kMaxPlanNodes + 1];
-    float tree_gtie[kMaxPlanNodes + 1];
-    uint32_t depth = 0, node_begin = 0;        // deep tree: levels of internal nodes, first canonical node
-    uint32_t leaf_node[kMaxPlanNodes + 1];     // deep tree: canonical node every leaf hangs off
-    if (pl.q_node_offsets) {
-      const uint32_t n0 = pl.q_node_offsets[q], nn = pl.q_node_offsets[q + 1] - n0;
-      const int32_t *kind = pl.node_kind + n0;
-      const float *ntie = pl.node_tie + n0;
-      const uint32_t *par = pl.node_parent + n0;
-      uint32_t dep[2 * kMaxPlanNodes + 1];
-      uint32_t deepest = 0;
-      n_leaves = 0;
-      for (uint32_t i = 0; i < nn; i++) {
-        dep[i] = i == 0 ? 0u : dep[par[i]] + 1u;
-        if (kind[i] == SLG_PLAN_LEAF) {
-          n_leaves++;
-          deepest = std::max(deepest, dep[i]);
-        }
-      }
-      if (kind[0] == SLG_PLAN_LEAF) {  // the plan is one leaf: Sum of one leaf
-        plan_kind = SLG_PLAN_SUM;
-        tie = 0.0f;
-      } else if (deepest <= 2) {  // root over leaves, or root over groups: the forms above
-        plan_kind = kind[0];
-        tie = kind[0] == SLG_PLAN_DISMAX ? ntie[0] : 0.0f;
-        if (deepest == 2) {
-          groups = true;
-          n_groups = 0;
-          uint32_t lf = 0;
-          for (uint32_t i = 1; i < nn; i++) {
-            if (dep[i] == 1) {  // a child of the root: a group (a bare leaf = a Sum group of one leaf)
-              tree_gplan[n_groups] = kind[i] == SLG_PLAN_DISMAX ? SLG_PLAN_DISMAX : SLG_PLAN_SUM;
-              tree_gtie[n_groups] = kind[i] == SLG_PLAN_DISMAX ? ntie[i] : 0.0f;
-              n_groups++;
-            }
-            if (kind[i] == SLG_PLAN_LEAF) tree_lgroup[lf++] = n_groups - 1u;
-          }
-          lgroup = tree_lgroup;
-          gplan = tree_gplan;
-          gtie = tree_gtie;
-        }
-      } else {
-        // deep tree: canonical node table — the internal nodes in pre-order, and under every leaf that
-        // hangs above the deepest level a chain of one-child Sum nodes down to it
-        depth = deepest;
-        plan_kind = kind[0];
-        tie = kind[0] == SLG_PLAN_DISMAX ? ntie[0] : 0.0f;
-        node_begin = (uint32_t)o.nodes.size();
-        uint32_t canon[2 * kMaxPlanNodes + 1];  // original internal node -> canonical index
-        uint32_t lf = 0;
-        for (uint32_t i = 0; i < nn; i++) {
-          if (kind[i] != SLG_PLAN_LEAF) {
-            canon[i] = (uint32_t)o.nodes.size() - node_begin;
-            slg::PlanNode pn{};
-            pn.parent = i == 0 ? 0u : canon[par[i]];
-            pn.n_children = 0;
-            pn.kind = kind[i] == SLG_PLAN_DISMAX ? 1u : 0u;
-            pn.tie = kind[i] == SLG_PLAN_DISMAX ? ntie[i] : 0.0f;
-            o.nodes.push_back(pn);
-            if (i != 0) o.nodes[node_begin + canon[par[i]]].n_children++;
-          } else {
-            uint32_t above = canon[par[i]];
-            o.nodes[node_begin + above].n_children++;
-            for (uint32_t d = dep[i]; d < deepest; d++) {  // pad: Sum of one child
-              slg::PlanNode pn{};
-              pn.parent = above;
-              pn.n_children = 1;
-              pn.kind = 0u;
-              pn.tie = 0.0f;
-              above = (uint32_t)o.nodes.size() - node_begin;
-              o.nodes.push_back(pn);
-            }
-            leaf_node[lf++] = above;
-          }
-        }
-      }
-    } else {
-      PLAN_REQUIRE(plan_kind == SLG_PLAN_SUM || plan_kind == SLG_PLAN_DISMAX,
-                   "unknown score plan in query " + std::to_string(q));
-      // validate_tie_breaker (query/planner.rs:850-856); the threshold seed and the pruning bounds
-      // also rely on it: with tie in [0, 1] a DisMax is >= each of its non-negative leaves
-      PLAN_REQUIRE(tie >= 0.0f && tie <= 1.0f, "tie breaker outside [0, 1] in query " + std::to_string(q));
-    }
-    for (uint32_t i = 0; i < nt; i++) {
-      const uint32_t lf = pl.q_leaf ? pl.q_leaf[t0 + i] : i;
-      PLAN_REQUIRE(lf < 0x80000000u, "leaf index >= 2^31 in query " + std::to_string(q));
-      n_leaves = std::max(n_leaves, lf + 1u);
-    }
-    // two-level plan: group of every leaf, leaves per group
-    uint32_t leaves_in_group[kMaxPlanNodes + 1];  // (zeroed only for queries with groups: 1 KB per query otherwise)
-    bool nested = false;
-    if (groups) {
-      std::memset(leaves_in_group, 0, sizeof(leaves_in_group));
-      if (!pl.q_node_offsets)
-        PLAN_REQUIRE(n_leaves == pl.q_nleaves[q], "a term names a leaf beyond q_nleaves in query " + std::to_string(q));
-      for (uint32_t l = 0; l < n_leaves; l++) leaves_in_group[lgroup[l]]++;
-      for (uint32_t g = 0; g < n_groups; g++)
-        if (leaves_in_group[g] != 1 || gplan[g] == SLG_PLAN_DISMAX) nested = true;
-    }
+    resolve_plan(in, q, o.nodes, plan);
     if (k == 0) continue;  // wand.rs:413-416: k == 0 and no collector => no work
     for (uint32_t s = 0; s < n_segs; s++) {
-      const SegView &sh = c.segs[s];
       slg::RoundQuery sq{};
       sq.q = q;
       sq.seg = s;
       sq.filter = fq;
-      sq.term_begin = (uint32_t)terms.size();
-      for (uint32_t i = 0; i < nt; i++) {
-        const uint32_t tid = in.q_term_ids[(size_t)(t0 + i) * n_segs + s];
-        if (tid == SLG_NO_TERM) continue;
-        PLAN_REQUIRE(tid < sh.n_terms, "term id out of range in query " + std::to_string(q));
-        const uint32_t df = (uint32_t)(sh.term_offsets[tid + 1] - sh.term_offsets[tid]);
-        if (df == 0) continue;  // wand.rs:441 filter(postings.len() > 0)
-        const uint64_t off = sh.term_offsets[tid] + (uint64_t)slg::kListPad * tid;  // padded layout (SegDev)
-        const float w = in.q_weights[t0 + i];
-        PLAN_REQUIRE(std::isfinite(w), "non-finite weight in query " + std::to_string(q));
-        slg::TermRef tr{};
-        tr.off = off;
-        tr.df = df;
-        tr.weight = w;
-        tr.term = tid;
-        tr.leaf = pl.q_leaf ? pl.q_leaf[t0 + i] : i;
-        if (depth) {
-          tr.gmeta = leaf_node[tr.leaf];  // the canonical node the leaf hangs off
-        } else if (nested) {
-          const uint32_t g = lgroup[tr.leaf];
-          tr.gmeta = g | (leaves_in_group[g] << 8) | ((gplan[g] == SLG_PLAN_DISMAX ? 1u : 0u) << 16);
-          tr.gtie = gtie[g];
-        }
-        terms.push_back(tr);
-      }
-      sq.n_terms = (uint32_t)terms.size() - sq.term_begin;
-      if (sq.n_terms == 0) continue;
-      slg::TermRef *first = terms.data() + sq.term_begin;
-      {
-        // Lists go to the device sorted by leaf (stable: a leaf's terms keep the term order in
-        // which the reference adds them, wand.rs:488-497; a group's leaves are consecutive, so the
-        // lists are sorted by group too).  plan 0 = the flat term-order sum, which is what Sum
-        // gives when no leaf holds two terms.
-        if (pl.q_leaf)  // (without leaves given, leaf = term position: already in order)
-          std::stable_sort(first, first + sq.n_terms,
-                           [](const slg::TermRef &a, const slg::TermRef &b) { return a.leaf < b.leaf; });
-        bool shared = false;
-        uint32_t present = 0;
-        for (uint32_t i = 0; i < sq.n_terms; i++) {
-          const bool fresh = i == 0 || first[i].leaf != first[i - 1].leaf;
-          present += fresh ? 1u : 0u;
-          shared = shared || !fresh;
-        }
-        sq.plan = plan_kind == SLG_PLAN_DISMAX ? 2u : ((shared || nested || depth) ? 1u : 0u);
-        if (min_match > 1u) {  // leaves are counted in the plan kernel's leaf close: Sum of leaves, bits 8.. = the count asked for
-          if (sq.plan == 0u) sq.plan = 1u;
-          sq.plan |= min_match << 8;
-        }
-        sq.tie = tie;
-        sq.max_init = present < n_leaves ? 0.0f : -INFINITY;
-        sq.n_leaves = n_leaves;
-        sq.n_groups = nested ? n_groups : 0u;
-        sq.depth = depth;
-        sq.node_begin = node_begin;
-        if (sq.plan) o.any_plan = true;
-        if (nested) o.any_nested = true;
-        if (depth) o.any_deep = true;
-      }
-      // (minimum_should_match > 1: the champions behind the seed are single postings — docs the matcher may reject)
-      sq.theta0 = min_match > 1u ? 0.0f : threshold_seed(sh, first, sq.n_terms, k, fq);
-      // MaxScore: by default for batches with a query of >= 5 terms (plan_batch drops the
-      // classification again when block skipping has nothing to gain);
-      // slg_tuning.pruning = 1 / 0 forces it on / off.  Never with score plans in the batch (the
-      // plan kernels have no classified path).
-      uint32_t ess_mask = full_mask(sq.n_terms);
-      if (in.strategy != SLG_STRATEGY_BM25 && sq.theta0 > 0.0f && !c.facts.plans_requested && sq.n_terms > 1 &&
-          c.maxscore_on)
-        ess_mask = classify_essential(sh, first, sq.n_terms, sq.theta0);
-      sq.ess_mask = ess_mask;
-      // the round planner works on the essential lists only
-      uint64_t P = 0, P_all = 0;
-      uint32_t longest = 0, longest_df = 0, longest_all = 0, longest_all_df = 0;
-      for (uint32_t i = 0; i < sq.n_terms; i++) {
-        const uint32_t df = first[i].df;
-        P_all += df;
-        if (df > longest_all_df) {
-          longest_all_df = df;
-          longest_all = i;
-        }
-        if (!((ess_mask >> i) & 1u)) continue;
-        P += df;
-        if (df > longest_df) {
-          longest_df = df;
-          longest = i;
-        }
-      }
-      // block skipping pays where a 64-posting block of a non-essential list usually holds no
-      // candidate doc: a block spans 64 * N / df docs, which hold 64 * P / df essential postings
-      // on average; blocks are tested only below 2 (>= e^-2 = 13 % of them can be skipped).
-      // Config 3's lists are all of similar density (>= 64 per block): no test, no cost.
-      sq.skip_mask = 0;
-      if (c.tn.block_max)
-        for (uint32_t i = 0; i < sq.n_terms && i < 32; i++) {
-          const uint64_t df = first[i].df;
-          if (!((ess_mask >> i) & 1u) && 64ull * P < 2ull * df) {
-            sq.skip_mask |= 1u << i;
-            o.skip_est += (double)df * std::exp(-64.0 * (double)P / (double)df);  // blocks without a candidate doc
-          }
-        }
-      o.n_noness += P_all - P;
-      c.q_postings[q] += P_all;
-      o.n_postings += P_all;
-      o.n_ess += P;
-      sq.longest = longest;
+      if (!build_subquery(c, plan, q, o.terms, sq)) continue;
+      if (sq.plan) o.any_plan = true;
+      if (plan.nested) o.any_nested = true;
+      if (plan.depth) o.any_deep = true;
+      const SqCount n = seed_and_classify(c, o.terms.data() + sq.term_begin, k, plan.min_match, sq, o.skip_est);
+      c.q_postings[q] += n.all;
+      o.n_postings += n.all;
+      o.n_ess += n.ess;
       o.max_terms = std::max(o.max_terms, sq.n_terms);
-      sqs.push_back(sq);
-      o.sq_postings.push_back(P);
-      o.sq_postings_all.push_back(P_all);
-      o.sq_longest_all.push_back(longest_all);
+      o.sqs.push_back(sq);
+      o.counts.push_back(n);
     }
   }
 }
@@ -569,6 +615,27 @@ uint32_t planner_threads() {
   return std::max<uint32_t>(1, std::min<uint32_t>(8, cpu_budget() / (uint32_t)running));
 }
 
+// fn(t, lo, hi) for each of n_thr contiguous ranges [lo, hi) of [0, n), t = the range's number: every range
+// on a thread of its own, a single one on the caller's.  A range that throws ends alone; once all have
+// ended the exception of the lowest range is rethrown
+template <typename Fn>
+void fan_out(size_t n, size_t n_thr, Fn fn) {
+  if (n_thr <= 1) return fn((size_t)0, (size_t)0, n);
+  std::vector<std::exception_ptr> errs(n_thr);
+  std::vector<std::thread> pool;
+  for (size_t t = 0; t < n_thr; t++)
+    pool.emplace_back([&, t] {
+      try {
+        fn(t, n * t / n_thr, n * (t + 1) / n_thr);
+      } catch (...) {
+        errs[t] = std::current_exception();
+      }
+    });
+  for (auto &th : pool) th.join();
+  for (auto &e : errs)
+    if (e) std::rethrow_exception(e);
+}
+
 uint32_t multi_round_target(uint64_t P, uint32_t n_docs, const slg_tuning &tn) {
   uint32_t target = std::max<uint32_t>(64, std::min<uint32_t>(tn.multi_round_target, (uint32_t)slg::kMultiCap));
   const double dens = (double)P / (double)std::max<uint32_t>(1u, n_docs);
@@ -579,7 +646,7 @@ uint32_t multi_round_target(uint64_t P, uint32_t n_docs, const slg_tuning &tn) {
 }
 
 void plan_rounds(const std::vector<SegView> &segs, const slg_tuning &tn, uint32_t k,
-                 const std::vector<uint64_t> &sq_postings, const std::vector<uint64_t> &sq_postings_all, Plan &out) {
+                 const std::vector<SqCount> &counts, Plan &out) {
   auto &sqs = out.sqs;
   const uint32_t probe_target = std::max<uint32_t>((uint32_t)slg::kMultiCap, tn.probe_target);
   // rounds per slice: short slices pack the tail of the launch better (one wave per slice).  The
@@ -607,25 +674,14 @@ void plan_rounds(const std::vector<SegView> &segs, const slg_tuning &tn, uint32_
   // the round targets are independent per sub-query: large batches (config 4: 65 536 sub-queries)
   // compute them on several threads; the offsets below are a serial prefix
   std::vector<uint32_t> targets(sqs.size());
-  {
-    auto fill = [&](size_t a, size_t b) {
-      for (size_t i = a; i < b; i++) {
-        const slg::RoundQuery &sq = sqs[i];
-        const slg::TermRef *t = out.terms.data() + sq.term_begin;
-        targets[i] = out.uniform ? uniform_round_target(sq, t, sq_postings[i], tn)
-                                 : multi_round_target(sq_postings[i], segs[sq.seg].n_docs, tn);
-      }
-    };
-    const size_t n_thr = sqs.size() >= 8192 ? planner_threads() : 1;
-    if (n_thr <= 1) {
-      fill(0, sqs.size());
-    } else {
-      std::vector<std::thread> pool;
-      for (size_t th = 0; th < n_thr; th++)
-        pool.emplace_back(fill, sqs.size() * th / n_thr, sqs.size() * (th + 1) / n_thr);
-      for (auto &th : pool) th.join();
+  fan_out(sqs.size(), sqs.size() >= 8192 ? planner_threads() : 1, [&](size_t, size_t a, size_t b) {
+    for (size_t i = a; i < b; i++) {
+      const slg::RoundQuery &sq = sqs[i];
+      const slg::TermRef *t = out.terms.data() + sq.term_begin;
+      targets[i] = out.uniform ? uniform_round_target(sq, t, counts[i].ess, tn)
+                               : multi_round_target(counts[i].ess, segs[sq.seg].n_docs, tn);
     }
-  }
+  });
   for (size_t i = 0; i < sqs.size(); i++) {
     slg::RoundQuery &sq = sqs[i];
     const slg::TermRef *t = out.terms.data() + sq.term_begin;
@@ -634,8 +690,8 @@ void plan_rounds(const std::vector<SegView> &segs, const slg_tuning &tn, uint32_
     // a round holds <= ~round_target postings of the essential lists (register slots) and
     // <= ~probe_target postings overall (non-essential lists are streamed per round), so
     // slices stay balanced whatever the mix
-    uint64_t nr = (sq_postings[i] + round_target - 1) / round_target;
-    nr = std::max<uint64_t>(nr, (sq_postings_all[i] + probe_target - 1) / probe_target);
+    uint64_t nr = (counts[i].ess + round_target - 1) / round_target;
+    nr = std::max<uint64_t>(nr, (counts[i].all + probe_target - 1) / probe_target);
     nr = std::max<uint64_t>(1, std::min<uint64_t>(nr, dfL));
     // sub-queries with many rounds get longer slices (fewer candidate lists for the merge,
     // whose time is set by the heaviest query); they are launched first (slice_order below)
@@ -689,6 +745,15 @@ void order_slices(const slg_tuning &tn, Plan &out) {
     out.slice_order[lpt ? hist[slg::kMaxRoundsPerSlice - nrounds[sidx]]++ : sidx] = (uint32_t)sidx;
 }
 
+// stitching: dst += src, which is spent (the first part is taken whole: one part = no copy)
+template <typename T>
+void append(std::vector<T> &dst, std::vector<T> &src) {
+  if (dst.empty())
+    dst.swap(src);
+  else
+    dst.insert(dst.end(), src.begin(), src.end());
+}
+
 template <typename T>
 size_t place(size_t &cursor, size_t count) {
   cursor = (cursor + 15) & ~(size_t)15;
@@ -730,76 +795,40 @@ void plan_batch(const std::vector<SegView> &segs, const slg_tuning &tn, const Ba
   } running;
   const uint32_t nq = in.nq, k = planning_k(in);
   const uint32_t n_segs = (uint32_t)segs.size();
-  const BatchFacts facts = validate_batch(in, n_segs);
+  const BatchFacts facts = validate_batch(in);
   out = Plan();
   out.q_postings.assign(nq, 0);
-  std::vector<uint32_t> q_sq_begin(nq + 1, 0);
   // MaxScore classification: on request, or (auto) for batches with a query of more than 4 terms
   const bool maxscore_on =
       tn.pruning >= 0 ? tn.pruning != 0 : facts.max_nt > std::min<uint32_t>(tn.uniform_max_terms, slg::kUniMaxLists);
-  Pass1Ctx ctx{segs, tn, in, facts, maxscore_on, q_sq_begin, out.q_postings};
+  Pass1Ctx ctx{segs, tn, in, facts, maxscore_on, out.q_postings};
 
   // Pass 1 is per query: large batches (config 4: 8192 queries x 8 segments = 65K sub-queries,
   // 15 ms on one thread, mostly cache misses in the champion tables) are planned by several
   // threads, each into its own vectors, stitched together in query order afterwards.
-  std::vector<uint64_t> sq_postings, sq_postings_all;
-  std::vector<uint32_t> sq_longest_all;
+  std::vector<SqCount> counts;
   double skip_est = 0.0;
   bool any_plan = false, any_filter = false;
   {
-    const uint64_t work = (uint64_t)nq * n_segs;
     uint32_t n_thr = 1;
-    if (work >= 8192)
-      n_thr = (uint32_t)std::min<uint64_t>(planner_threads(), nq / 512);
-    n_thr = std::max(1u, n_thr);
+    if ((uint64_t)nq * n_segs >= 8192) n_thr = std::max<uint32_t>(1, std::min<uint32_t>(planner_threads(), nq / 512));
     std::vector<Pass1Out> parts(n_thr);
-    auto lo_of = [&](uint32_t t) { return n_thr == 1 ? 0u : (uint32_t)((uint64_t)nq * t / n_thr); };
-    if (n_thr == 1) {
-      plan_queries(ctx, 0, nq, parts[0]);
-    } else {
-      std::vector<std::thread> pool;
-      for (uint32_t t = 0; t < n_thr; t++)
-        pool.emplace_back([&, t] {
-          try {
-            plan_queries(ctx, lo_of(t), t + 1 == n_thr ? nq : lo_of(t + 1), parts[t]);
-          } catch (...) {
-            parts[t].err = std::current_exception();
-          }
-        });
-      for (auto &th : pool) th.join();
-      for (auto &pt : parts)
-        if (pt.err) std::rethrow_exception(pt.err);
-    }
-    for (uint32_t t = 0; t < n_thr; t++) {
-      Pass1Out &pt = parts[t];
-      const uint32_t sq_base = (uint32_t)out.sqs.size(), term_base = (uint32_t)out.terms.size();
-      const uint32_t q_lo = lo_of(t), q_hi = t + 1 == n_thr ? nq : lo_of(t + 1);
-      for (uint32_t q = q_lo; q < q_hi; q++) q_sq_begin[q] += sq_base;
-      {
-        const uint32_t node_base = (uint32_t)out.nodes.size();
-        if (node_base)
-          for (auto &sq : pt.sqs)
-            if (sq.depth) sq.node_begin += node_base;
-        out.nodes.insert(out.nodes.end(), pt.nodes.begin(), pt.nodes.end());
-      }
-      if (n_thr == 1) {
-        out.sqs.swap(pt.sqs);
-        out.terms.swap(pt.terms);
-        sq_postings.swap(pt.sq_postings);
-        sq_postings_all.swap(pt.sq_postings_all);
-        sq_longest_all.swap(pt.sq_longest_all);
-      } else {
-        for (auto &sq : pt.sqs) sq.term_begin += term_base;
-        out.sqs.insert(out.sqs.end(), pt.sqs.begin(), pt.sqs.end());
-        out.terms.insert(out.terms.end(), pt.terms.begin(), pt.terms.end());
-        sq_postings.insert(sq_postings.end(), pt.sq_postings.begin(), pt.sq_postings.end());
-        sq_postings_all.insert(sq_postings_all.end(), pt.sq_postings_all.begin(), pt.sq_postings_all.end());
-        sq_longest_all.insert(sq_longest_all.end(), pt.sq_longest_all.begin(), pt.sq_longest_all.end());
-      }
+    fan_out(nq, n_thr, [&](size_t t, size_t lo, size_t hi) { plan_queries(ctx, (uint32_t)lo, (uint32_t)hi, parts[t]); });
+    for (Pass1Out &pt : parts) {
+      const uint32_t term_base = (uint32_t)out.terms.size(), node_base = (uint32_t)out.nodes.size();
+      if (term_base || node_base)
+        for (auto &sq : pt.sqs) {
+          sq.term_begin += term_base;
+          if (sq.depth) sq.node_begin += node_base;
+        }
+      append(out.sqs, pt.sqs);
+      append(out.terms, pt.terms);
+      append(counts, pt.counts);
+      append(out.nodes, pt.nodes);
       skip_est += pt.skip_est;
       out.n_postings += pt.n_postings;
       out.n_postings_essential += pt.n_ess;
-      out.n_postings_nonessential += pt.n_noness;
+      out.n_postings_nonessential += pt.n_postings - pt.n_ess;
       out.max_terms = std::max(out.max_terms, pt.max_terms);
       any_plan = any_plan || pt.any_plan;
       any_filter = any_filter || pt.any_filter;
@@ -807,7 +836,6 @@ void plan_batch(const std::vector<SegView> &segs, const slg_tuning &tn, const Ba
       out.deep = out.deep || pt.any_deep;
     }
   }
-  q_sq_begin[nq] = (uint32_t)out.sqs.size();
 
   // Classified lists only pay through block skipping (the many-term kernel loads a non-essential
   // list as it loads any other; what it saves is the blocks without a candidate doc).  A batch the
@@ -821,8 +849,8 @@ void plan_batch(const std::vector<SegView> &segs, const slg_tuning &tn, const Ba
       slg::RoundQuery &sq = out.sqs[i];
       sq.ess_mask = full_mask(sq.n_terms);
       sq.skip_mask = 0;
-      sq.longest = sq_longest_all[i];
-      sq_postings[i] = sq_postings_all[i];
+      sq.longest = counts[i].longest_all;
+      counts[i].ess = counts[i].all;
     }
     out.n_postings_essential = out.n_postings;
     out.n_postings_nonessential = 0;
@@ -849,23 +877,19 @@ void plan_batch(const std::vector<SegView> &segs, const slg_tuning &tn, const Ba
   // seed threshold instead (one candidate slot per posting) and select per query afterwards
   out.cand_mode = k > 256;
 
-  plan_rounds(segs, tn, k, sq_postings, sq_postings_all, out);
+  plan_rounds(segs, tn, k, counts, out);
 
   if (out.cand_mode)
     for (size_t i = 0; i < out.sqs.size(); i++) {
       out.sqs[i].cand_lo = (uint32_t)out.cand_total;
       out.sqs[i].cand_hi = (uint32_t)(out.cand_total >> 32);
-      out.cand_total += sq_postings_all[i];
+      out.cand_total += counts[i].all;
     }
-  out.qrefs.resize(nq);
-  for (uint32_t q = 0; q < nq; q++) {
-    const uint32_t a = q_sq_begin[q], e = q_sq_begin[q + 1];
-    if (a == e) {
-      out.qrefs[q] = slg::QueryRef{0, 0};
-    } else {
-      out.qrefs[q].slice_begin = out.sqs[a].slice_begin;
-      out.qrefs[q].slice_end = out.sqs[e - 1].slice_begin + out.sqs[e - 1].n_slices;
-    }
+  out.qrefs.assign(nq, slg::QueryRef{0, 0});
+  for (const slg::RoundQuery &sq : out.sqs) {  // (in query order; every sub-query has a slice)
+    slg::QueryRef &qr = out.qrefs[sq.q];
+    if (qr.slice_end == 0) qr.slice_begin = sq.slice_begin;
+    qr.slice_end = sq.slice_begin + sq.n_slices;
   }
   order_slices(tn, out);
   // sub-query of every 32nd round boundary (partition_rounds_kernel walks from there)

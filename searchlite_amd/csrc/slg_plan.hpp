@@ -2,7 +2,9 @@
 // the index's tuning and the caller's query arrays -> the descriptor image the kernels consume
 // (sub-queries, term references, slices, launch order).  No HIP in here: the translation unit
 // builds with g++ and is unit-tested and sanitized on a box without a GPU
-// (tests/test_plan.py, tools/sanitize_cpu.sh); slg_batch.hip uploads what it returns.
+// (tests/test_plan.py, tools/sanitize_cpu.sh; tools/plan_digest.cpp beside this file is a stand-alone
+// driver that digests everything plan_batch returns over a fixed list of batches: two builds of the
+// planner are compared, or one is run under a sanitizer, with it); slg_batch.hip uploads what it returns.
 //
 // What it mirrors: IndexReader::search_segment's preparation of the scorer call
 // (searchlite-core/src/api/reader.rs:2971-3005: ScoredTerm list per segment, terms with empty

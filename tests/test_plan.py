@@ -579,3 +579,121 @@ def test_large_batches_plan_identically_on_several_threads(lib):
     assert tr_w.tobytes() == a.array(1, TR).tobytes() + b.array(1, TR).tobytes()
     for p in (whole, a, b):
         p.close()
+
+
+# score trees of 4 leaves each (kinds, ties, parents; 0 Sum, 1 DisMax, 2 leaf): one level, two levels (groups),
+# three levels with a leaf at every level, four levels
+_TREE_FLAT = ([1, 2, 2, 2, 2], [.3, 0, 0, 0, 0], [0, 0, 0, 0, 0])
+_TREE_GROUPS = ([0, 1, 2, 2, 2, 1, 2], [0, .5, 0, 0, 0, 1.0, 0], [0, 0, 1, 1, 0, 0, 5])
+_TREE_DEEP3 = ([0, 2, 1, 2, 0, 2, 2], [0, 0, .25, 0, 0, 0, 0], [0, 0, 0, 2, 2, 4, 4])
+_TREE_DEEP4 = ([1, 0, 0, 0, 2, 2, 2, 2], [.5, 0, 0, 0, 0, 0, 0, 0], [0, 0, 1, 2, 3, 3, 1, 0])
+
+
+def _tree_plans(trees, leaf):
+    qno = np.cumsum([0] + [len(t[0]) for t in trees])
+    return _plans(q_leaf=(leaf, "<u4"), q_node_offsets=(qno, "<u4"), node_kind=(sum((t[0] for t in trees), []), "<i4"),
+                  node_tie=(sum((t[1] for t in trees), []), "<f4"), node_parent=(sum((t[2] for t in trees), []), "<u4"))
+
+
+def test_large_batches_of_deep_trees_stitch_their_node_tables(lib):
+    """Several threads, deep score trees, a doc filter on some queries: every part builds the node tables of
+    its own queries, and the stitching rebases node_begin by the nodes of the parts before it.  Compared with
+    the same queries planned in two halves: node bytes concatenate, the second half's node_begin values are
+    offset by the first half's node count."""
+    rng = np.random.default_rng(14)
+    segs = [random_segment(rng, 800, 30, 10) for _ in range(4)]
+    champs = [champions_of(s) for s in segs]
+    nq, T = 2304, 3
+    offs, terms, w = random_queries(rng, nq, T, 30, n_segs=4)
+    shapes = (_TREE_DEEP3, _TREE_GROUPS, _TREE_DEEP4, _TREE_FLAT)
+    trees = [shapes[q % 4] for q in range(nq)]
+    leaf = np.tile(np.array([0, 2, 3], dtype=np.uint32), nq)
+    qf = np.where(np.arange(nq) % 5 == 0, 0, -1).astype(np.int32)
+
+    def plan(a, b):
+        return Planned(lib, segs, offs[a:b + 1] - offs[a], terms[T * a:T * b], w[T * a:T * b], 11, champs=champs,
+                       plans=_tree_plans(trees[a:b], leaf[T * a:T * b]), q_filter=qf[a:b], filter_live=b"\x01")
+    h = nq // 2
+    whole, a, b = plan(0, nq), plan(0, h), plan(h, nq)
+    assert whole.h and a.h and b.h, (whole.err, a.err, b.err)
+    assert whole.facts.n_sq >= 8192 and whole.facts.deep and whole.facts.nested
+    sq_w, tr_w = check_structure(whole, 11)
+    sq_a, sq_b = a.array(0, RQ), b.array(0, RQ)
+    assert len(sq_w) == len(sq_a) + len(sq_b)
+    for name in ("seg", "n_terms", "n_rounds", "rounds_per_slice", "n_slices", "longest", "ess_mask", "theta0", "filter",
+                 "plan", "tie", "max_init", "n_leaves", "n_groups", "depth"):
+        assert np.array_equal(sq_w[name], np.concatenate([sq_a[name], sq_b[name]])), name
+    assert np.array_equal(sq_w["q"], np.concatenate([sq_a["q"], sq_b["q"] + h]))
+    assert tr_w.tobytes() == a.array(1, TR).tobytes() + b.array(1, TR).tobytes()
+    nodes_a, nodes_b = a.array(9, PN), b.array(9, PN)
+    assert len(nodes_a) > 0 and len(nodes_b) > 0
+    assert whole.array(9, PN).tobytes() == nodes_a.tobytes() + nodes_b.tobytes()
+    want_begin = np.concatenate([sq_a["node_begin"], np.where(sq_b["depth"] > 0, sq_b["node_begin"] + len(nodes_a), 0)])
+    assert np.array_equal(sq_w["node_begin"], want_begin)
+    assert set(sq_w["depth"].tolist()) == {0, 3, 4} and (sq_w["filter"] == 1).any() and (sq_w["filter"] == 0).any()
+    for p in (whole, a, b):
+        p.close()
+
+
+def test_a_large_batch_reports_the_error_of_the_earliest_query(lib):
+    """Several threads plan their ranges of queries at once; of two malformed queries the earlier one is named,
+    whichever thread met its own first."""
+    rng = np.random.default_rng(15)
+    segs = [random_segment(rng, 800, 30, 10) for _ in range(4)]
+    nq = 2304
+    offs, terms, w = random_queries(rng, nq, 3, 30, n_segs=4)
+    t2 = terms.copy().reshape(nq * 3, 4)
+    t2[7 * 3 + 1, 2] = 4000        # query 7
+    t2[2290 * 3, 0] = 4000         # query 2290
+    p = Planned(lib, segs, offs, t2.reshape(-1), w, 11)
+    assert not p.h and p.code == -1 and p.err == "term id out of range in query 7", p.err
+    t3 = terms.copy().reshape(nq * 3, 4)
+    t3[2290 * 3, 0] = 4000
+    p = Planned(lib, segs, offs, t3.reshape(-1), w, 11)
+    assert not p.h and p.code == -1 and p.err == "term id out of range in query 2290", p.err
+
+
+def test_a_two_level_plan_on_one_query_leaves_the_others_as_planned_alone(lib):
+    """Pass 1 resolves every query's score plan into the same scratch object; what a query with groups of
+    leaves leaves behind there must not show in the queries after it: they plan exactly as they do alone."""
+    rng = np.random.default_rng(16)
+    seg = random_segment(rng, 2000, 40, 15)
+    ch = champions_of(seg)
+    nq, T = 6, 6
+    offs, terms, w = random_queries(rng, nq, T, 40)
+    leaf = np.tile(np.array([0, 0, 1, 2, 2, 3], dtype=np.uint32), nq)
+    trees = [_TREE_FLAT, _TREE_GROUPS, _TREE_FLAT, _TREE_DEEP3, ([2], [0], [0]), _TREE_FLAT]
+    leaf[4 * T:5 * T] = 0          # (query 4's tree is a single leaf)
+    batch = Planned(lib, [seg], offs, terms, w, 11, champs=[ch], plans=_tree_plans(trees, leaf))
+    assert batch.h, batch.err
+    sqs, tr = check_structure(batch, 11)
+    assert len(sqs) == nq and [int(x) for x in sqs["n_groups"]] == [0, 3, 0, 0, 0, 0]
+    # what pass 1 decides per sub-query (the rounds and slices follow the kernel, which is chosen per batch)
+    pass1 = ("n_terms", "longest", "ess_mask", "skip_mask", "plan", "tie", "max_init", "n_leaves", "n_groups", "theta0",
+             "depth", "filter")
+    rounds = ("n_rounds", "rounds_per_slice", "n_slices")
+
+    def same(x, y, names):
+        return all(x[n] == y[n] or (np.isinf(x[n]) and np.isinf(y[n])) for n in names)
+    for q in range(nq):
+        alone = Planned(lib, [seg], offs[q:q + 2] - offs[q], terms[T * q:T * (q + 1)], w[T * q:T * (q + 1)], 11, champs=[ch],
+                        plans=_tree_plans(trees[q:q + 1], leaf[T * q:T * (q + 1)]))
+        assert alone.h, alone.err
+        sq1, tr1 = alone.array(0, RQ), alone.array(1, TR)
+        assert len(sq1) == 1 and same(sqs[q], sq1[0], pass1), (q, sqs[q], sq1[0])
+        t0 = int(sqs[q]["term_begin"])
+        assert tr[t0:t0 + int(sqs[q]["n_terms"])].tobytes() == tr1.tobytes(), q
+        alone.close()
+    # and, rounds and slices included, as in the same batch (same kernel: query 3's deep tree) without query 1
+    keep = [0, 2, 3, 4, 5]
+    rows = np.concatenate([np.arange(T * q, T * (q + 1)) for q in keep])
+    rest = Planned(lib, [seg], np.arange(len(keep) + 1, dtype=np.uint32) * T, terms[rows], w[rows], 11, champs=[ch],
+                   plans=_tree_plans([trees[q] for q in keep], leaf[rows]))
+    assert rest.h, rest.err
+    sq_r, tr_r = rest.array(0, RQ), rest.array(1, TR)
+    assert len(sq_r) == len(keep)
+    for i, q in enumerate(keep):
+        assert same(sqs[q], sq_r[i], pass1 + rounds), (q, sqs[q], sq_r[i])
+    assert tr_r.tobytes() == np.concatenate([tr[:T], tr[2 * T:]]).tobytes()
+    rest.close()
+    batch.close()

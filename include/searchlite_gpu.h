@@ -1197,6 +1197,109 @@ int slg_search_batch_phrase(slg_index *index, uint32_t nq, const uint32_t *q_off
                             int strategy, uint32_t *out_doc, uint32_t *out_seg, float *out_score,
                             uint32_t *out_count, slg_stats *stats_or_null, uint64_t *out_matched_or_null);
 
+/* ---------------------------------------------------------------------------------------------------------
+ * function_score at the root of the score tree, with the batch's scored query as its inner query: boost by a
+ * column (field_value_factor), by closeness to an origin (decay), by a constant under a filter (weight), and
+ * min_score.  The reference visits every accepted doc, computes the node's score from the doc's base score
+ * and fast-field values, drops the doc when that gives None and ranks by the computed score
+ * (evaluate_compiled_score, api/reader.rs:491-548 and :3166-3187; query/score_functions.rs).  Every candidate
+ * passes matches_subquery, because the inner query is the scored one.
+ *
+ * FUNCTIONS.  Query q has functions q_fn_offsets[q] .. q_fn_offsets[q + 1] - 1 (at most SLG_MAX_FSCORE_FUNCS),
+ * evaluated in that order.  Each gives the doc a VALUE (f32) or none.  f_filter is a filter id of
+ * slg_index_add_filter* or -1: a function whose filter rejects the doc gives none.
+ *   SLG_FSCORE_WEIGHT               the value is f_weight.
+ *   SLG_FSCORE_FIELD_VALUE_FACTOR   raw = the FIRST value of the doc in column f_field, or f_missing when the doc
+ *                                   has none; scaled = raw * (double)f_weight (the factor); non-finite: no value;
+ *                                   m = modifier(scaled); non-finite: no value; the value is (float)m.  Modifiers:
+ *                                   NONE x; LOG x <= 0 ? 0 : ln x; LOG1P x <= -1 ? 0 : ln(1 + x) (log1p);
+ *                                   LOG2P x <= -1 ? 0 : log2(x + 1); SQRT x < 0 ? 0 : sqrt x;
+ *                                   RECIPROCAL x == 0 ? 0 : 1 / x.
+ *   SLG_FSCORE_DECAY                a doc without a value in f_field: no value.  distance = |v - f_origin| -
+ *                                   f_offset, norm = max(distance, 0) / f_scale; EXP pow(f_decay, norm), GAUSS
+ *                                   pow(f_decay, norm * norm), LINEAR max((1 - norm) * (1 - f_decay) + f_decay, 0);
+ *                                   non-finite: no value; the value is (float) of it.
+ * All of this is f64 arithmetic, operation by operation (no contraction).  Columns are the numeric columns of
+ * slg_index_add_agg_field_f64 / _i64 (an i64 value counts `as f64`); a function_score batch only reads them.
+ *
+ * COMBINE, in f32, operation by operation.  fs = the present values folded left to right by q_score_mode: SUM,
+ * MULTIPLY, MAX, MIN (fmaxf / fminf: a NaN operand loses, as Rust's f32::max / min), AVG (the sum divided by the
+ * number of present values).  base = the doc's first-pass score; eff = base, but 1.0 when |base| <= FLT_EPSILON
+ * and a value is present.  combined = eff when no value is present, else by q_boost_mode: MULTIPLY eff * fs,
+ * SUM eff + fs, REPLACE fs, MAX fmaxf(eff, fs), MIN fminf(eff, fs).  Then, in this order: with
+ * SLG_FSCORE_HAS_MAX_BOOST combined = fminf(combined, q_max_boost); with SLG_FSCORE_HAS_MIN_SCORE the doc is
+ * DROPPED when combined < q_min_score; combined *= q_boost.  A query without functions still applies the three.
+ * A dropped doc is not ranked and not counted: slg_stats.scored_docs = the count of the same batch without the
+ * spec minus the dropped docs (the bool batch's rule), and a sorted batch's matched counts see survivors only.
+ * A query with no function, neither flag and q_boost == 1 is untouched, bit for bit; such queries mix with
+ * others in a batch.  (A NaN score has the sign the device's arithmetic gives it.)
+ *
+ * slg_batch_prepare_fscore is slg_batch_prepare_plans (sort NULL: rows in order of the new score) or
+ * slg_batch_prepare_sorted (a field sort; `_score` parts read the new score) plus the spec.  The batch is planned
+ * as a sorted batch is — every doc of the scored lists is a candidate with its exact score, no threshold seed,
+ * no MaxScore, whatever k is — and slg_batch_run enqueues ONE kernel between the scoring kernel and the select
+ * that rewrites every candidate's score and drops those below min_score.  A batch in which no query has work
+ * launches nothing.  The kernel has two instantiations, chosen per batch: a lean one for batches whose
+ * functions need no ln / log1p / log2 / pow (weight, NONE / SQRT / RECIPROCAL, LINEAR), and a full one;
+ * slg_batch_fscore_info tells which (0: nothing is launched, 1 lean, 2 full) and how many queries have work.
+ * run / fetch / device_results / sync / set_stream as for any batch; slg_batch_matched_counts for the sorted
+ * form.  Columns and filters are those of the index state the batch was prepared on.  slg_search_batch_fscore
+ * is the one-call form; stats may be NULL; out_matched may be NULL and must be NULL without a sort spec.
+ *
+ * Errors, the spec's own before an index state is looked at.  SLG_ERR_INVALID: a NULL spec or array, offsets
+ * that decrease, an unknown kind, mode, modifier or decay function, a non-finite weight or factor, a non-finite
+ * scale or scale <= 0, f_decay outside (0, 1]; then against the state: an unknown field or filter id, a keyword
+ * column, a field without a column for a segment.  SLG_ERR_UNSUPPORTED (CPU scorer): more than
+ * SLG_MAX_FSCORE_FUNCS functions in a query, a column that holds a non-finite value (the rule of aggregations).
+ * slg_batch_run_sharded* and slg_batch_fetch_sharded refuse a function_score batch with SLG_ERR_UNSUPPORTED.
+ * Not built (CPU scorer): function_score below the root or over another inner query, rank_feature,
+ * script_score, constant_score, explain, function filters other than registered filter ids, and specs on bool,
+ * phrase, cursor, hybrid, aggregation, rescore, sharded and coalesced batches (none of their prepare calls
+ * takes the spec).
+ * --------------------------------------------------------------------------------------------------------- */
+#define SLG_MAX_FSCORE_FUNCS 8u /* functions of one query */
+enum { SLG_FSCORE_WEIGHT = 0, SLG_FSCORE_FIELD_VALUE_FACTOR = 1, SLG_FSCORE_DECAY = 2 };
+enum { SLG_FSCORE_MOD_NONE = 0, SLG_FSCORE_MOD_LOG = 1, SLG_FSCORE_MOD_LOG1P = 2, SLG_FSCORE_MOD_LOG2P = 3,
+       SLG_FSCORE_MOD_SQRT = 4, SLG_FSCORE_MOD_RECIPROCAL = 5 };
+enum { SLG_FSCORE_DECAY_EXP = 0, SLG_FSCORE_DECAY_GAUSS = 1, SLG_FSCORE_DECAY_LINEAR = 2 };
+enum { SLG_FSCORE_MODE_SUM = 0, SLG_FSCORE_MODE_MULTIPLY = 1, SLG_FSCORE_MODE_MAX = 2, SLG_FSCORE_MODE_MIN = 3,
+       SLG_FSCORE_MODE_AVG = 4 };
+enum { SLG_FSCORE_BOOST_MULTIPLY = 0, SLG_FSCORE_BOOST_SUM = 1, SLG_FSCORE_BOOST_REPLACE = 2,
+       SLG_FSCORE_BOOST_MAX = 3, SLG_FSCORE_BOOST_MIN = 4 };
+#define SLG_FSCORE_HAS_MAX_BOOST 1u
+#define SLG_FSCORE_HAS_MIN_SCORE 2u
+typedef struct slg_fscore_spec {
+  const uint32_t *q_fn_offsets; /* [nq + 1] into the f_ arrays */
+  const int32_t *q_score_mode;  /* [nq] SLG_FSCORE_MODE_* */
+  const int32_t *q_boost_mode;  /* [nq] SLG_FSCORE_BOOST_* */
+  const uint32_t *q_flags;      /* [nq] SLG_FSCORE_HAS_* */
+  const float *q_max_boost;     /* [nq] read with SLG_FSCORE_HAS_MAX_BOOST */
+  const float *q_min_score;     /* [nq] read with SLG_FSCORE_HAS_MIN_SCORE */
+  const float *q_boost;         /* [nq] */
+  const int32_t *f_kind;        /* [n_functions] SLG_FSCORE_WEIGHT / _FIELD_VALUE_FACTOR / _DECAY */
+  const int32_t *f_field;       /* [n_functions] agg field id (numeric); not read for a weight */
+  const int32_t *f_filter;      /* [n_functions] filter id or -1 */
+  const float *f_weight;        /* [n_functions] the weight, or field_value_factor's factor */
+  const int32_t *f_modifier;    /* [n_functions] SLG_FSCORE_MOD_* (field_value_factor) */
+  const int32_t *f_decay_fn;    /* [n_functions] SLG_FSCORE_DECAY_* (decay) */
+  const double *f_missing;      /* [n_functions] field_value_factor: the value of a doc without one */
+  const double *f_origin;       /* [n_functions] decay */
+  const double *f_scale;        /* [n_functions] decay: finite, > 0 */
+  const double *f_offset;       /* [n_functions] decay */
+  const double *f_decay;        /* [n_functions] decay: in (0, 1] */
+} slg_fscore_spec;
+slg_batch *slg_batch_prepare_fscore(slg_index *index, uint32_t nq, const uint32_t *q_offsets, const uint32_t *q_term_ids,
+                                    const float *q_weights, const slg_score_plans *plans_or_null,
+                                    const int32_t *q_filter_or_null, const slg_sort_spec *sort_or_null,
+                                    const slg_fscore_spec *spec, uint32_t k, int strategy);
+int slg_batch_fscore_info(const slg_batch *batch, uint32_t *out_variant, uint32_t *out_queries_with_work);
+int slg_search_batch_fscore(slg_index *index, uint32_t nq, const uint32_t *q_offsets, const uint32_t *q_term_ids,
+                            const float *q_weights, const slg_score_plans *plans_or_null,
+                            const int32_t *q_filter_or_null, const slg_sort_spec *sort_or_null,
+                            const slg_fscore_spec *spec, uint32_t k, int strategy, uint32_t *out_doc, uint32_t *out_seg,
+                            float *out_score, uint32_t *out_count, slg_stats *stats_or_null,
+                            uint64_t *out_matched_or_null);
+
 #ifdef __cplusplus
 }
 #endif

@@ -76,6 +76,13 @@ pub const SLG_AGG_STATS: i32 = 3;
     pub c_offsets: *const u32, pub c_term_ids: *const u32, pub c_group: *const u32, pub g_offsets: *const u32,
     pub g_kind: *const i32, pub q_min_should: *const u32,
 }
+#[repr(C)] pub struct slg_fscore_spec {
+    pub q_fn_offsets: *const u32, pub q_score_mode: *const i32, pub q_boost_mode: *const i32, pub q_flags: *const u32,
+    pub q_max_boost: *const c_float, pub q_min_score: *const c_float, pub q_boost: *const c_float,
+    pub f_kind: *const i32, pub f_field: *const i32, pub f_filter: *const i32, pub f_weight: *const c_float,
+    pub f_modifier: *const i32, pub f_decay_fn: *const i32, pub f_missing: *const f64, pub f_origin: *const f64,
+    pub f_scale: *const f64, pub f_offset: *const f64, pub f_decay: *const f64,
+}
 #[repr(C)] pub struct slg_phrase_spec {
     pub p_offsets: *const u32, pub p_kind: *const i32, pub p_slop: *const u32, pub v_offsets: *const u32,
     pub t_offsets: *const u32, pub t_term_ids: *const u32, pub q_min_should: *const u32,
@@ -311,6 +318,17 @@ extern "C" {
         sort: *const slg_sort_spec, bool_spec: *const slg_bool_spec, phrases: *const slg_phrase_spec, k: u32,
         strategy: c_int, out_doc: *mut u32, out_seg: *mut u32, out_score: *mut c_float, out_count: *mut u32,
         stats: *mut slg_stats, out_matched: *mut u64) -> c_int;
+    // function_score at the root (weight, field_value_factor, decay, min_score): slg_batch_prepare_plans or _sorted
+    // plus the spec; columns are those of slg_index_add_agg_field_f64 / _i64
+    pub fn slg_batch_prepare_fscore(index: *mut slg_index, nq: u32, q_offsets: *const u32, q_term_ids: *const u32,
+        q_weights: *const c_float, plans: *const slg_score_plans, q_filter: *const i32,
+        sort: *const slg_sort_spec, spec: *const slg_fscore_spec, k: u32, strategy: c_int) -> *mut slg_batch;
+    pub fn slg_batch_fscore_info(batch: *const slg_batch, out_variant: *mut u32, out_queries_with_work: *mut u32) -> c_int;
+    pub fn slg_search_batch_fscore(index: *mut slg_index, nq: u32, q_offsets: *const u32, q_term_ids: *const u32,
+        q_weights: *const c_float, plans: *const slg_score_plans, q_filter: *const i32,
+        sort: *const slg_sort_spec, spec: *const slg_fscore_spec, k: u32, strategy: c_int, out_doc: *mut u32,
+        out_seg: *mut u32, out_score: *mut c_float, out_count: *mut u32, stats: *mut slg_stats,
+        out_matched: *mut u64) -> c_int;
 }
 pub const SLG_MAX_PHRASE_TERMS: u32 = 8;
 pub const SLG_MAX_PHRASE_VARIANTS: u32 = 8;
@@ -321,6 +339,31 @@ pub const SLG_BOOL_SHOULD: i32 = 1;
 pub const SLG_BOOL_MUST_NOT: i32 = 2;
 pub const SLG_MAX_BOOL_GROUPS: u32 = 32;
 pub const SLG_MAX_BOOL_TERMS: u32 = 64;
+pub const SLG_MAX_FSCORE_FUNCS: u32 = 8;
+pub const SLG_FSCORE_WEIGHT: i32 = 0;
+pub const SLG_FSCORE_FIELD_VALUE_FACTOR: i32 = 1;
+pub const SLG_FSCORE_DECAY: i32 = 2;
+pub const SLG_FSCORE_MOD_NONE: i32 = 0;
+pub const SLG_FSCORE_MOD_LOG: i32 = 1;
+pub const SLG_FSCORE_MOD_LOG1P: i32 = 2;
+pub const SLG_FSCORE_MOD_LOG2P: i32 = 3;
+pub const SLG_FSCORE_MOD_SQRT: i32 = 4;
+pub const SLG_FSCORE_MOD_RECIPROCAL: i32 = 5;
+pub const SLG_FSCORE_DECAY_EXP: i32 = 0;
+pub const SLG_FSCORE_DECAY_GAUSS: i32 = 1;
+pub const SLG_FSCORE_DECAY_LINEAR: i32 = 2;
+pub const SLG_FSCORE_MODE_SUM: i32 = 0;
+pub const SLG_FSCORE_MODE_MULTIPLY: i32 = 1;
+pub const SLG_FSCORE_MODE_MAX: i32 = 2;
+pub const SLG_FSCORE_MODE_MIN: i32 = 3;
+pub const SLG_FSCORE_MODE_AVG: i32 = 4;
+pub const SLG_FSCORE_BOOST_MULTIPLY: i32 = 0;
+pub const SLG_FSCORE_BOOST_SUM: i32 = 1;
+pub const SLG_FSCORE_BOOST_REPLACE: i32 = 2;
+pub const SLG_FSCORE_BOOST_MAX: i32 = 3;
+pub const SLG_FSCORE_BOOST_MIN: i32 = 4;
+pub const SLG_FSCORE_HAS_MAX_BOOST: u32 = 1;
+pub const SLG_FSCORE_HAS_MIN_SCORE: u32 = 2;
 pub const SLG_RESCORE_TOTAL: i32 = 0;
 pub const SLG_RESCORE_MULTIPLY: i32 = 1;
 pub const SLG_RESCORE_SUM: i32 = 2;

@@ -40,6 +40,13 @@ MAX_PHRASE_TERMS = 8
 MAX_PHRASE_VARIANTS = 8
 MAX_PHRASE_QUERY_TERMS = 64
 MAX_PHRASE_SLOP = 2147483647 - 8
+MAX_FSCORE_FUNCS = 8
+FSCORE_WEIGHT, FSCORE_FIELD_VALUE_FACTOR, FSCORE_DECAY = 0, 1, 2
+FSCORE_MOD_NONE, FSCORE_MOD_LOG, FSCORE_MOD_LOG1P, FSCORE_MOD_LOG2P, FSCORE_MOD_SQRT, FSCORE_MOD_RECIPROCAL = 0, 1, 2, 3, 4, 5
+FSCORE_DECAY_EXP, FSCORE_DECAY_GAUSS, FSCORE_DECAY_LINEAR = 0, 1, 2
+FSCORE_MODE_SUM, FSCORE_MODE_MULTIPLY, FSCORE_MODE_MAX, FSCORE_MODE_MIN, FSCORE_MODE_AVG = 0, 1, 2, 3, 4
+FSCORE_BOOST_MULTIPLY, FSCORE_BOOST_SUM, FSCORE_BOOST_REPLACE, FSCORE_BOOST_MAX, FSCORE_BOOST_MIN = 0, 1, 2, 3, 4
+FSCORE_HAS_MAX_BOOST, FSCORE_HAS_MIN_SCORE = 1, 2
 
 
 class SlgError(RuntimeError):
@@ -149,6 +156,17 @@ class PhraseSpec(C.Structure):
     rows per variant; minimum_should_match per query over term and phrase groups)."""
     _fields_ = [("p_offsets", C.c_void_p), ("p_kind", C.c_void_p), ("p_slop", C.c_void_p), ("v_offsets", C.c_void_p),
                 ("t_offsets", C.c_void_p), ("t_term_ids", C.c_void_p), ("q_min_should", C.c_void_p)]
+
+
+class FscoreSpec(C.Structure):
+    """slg_fscore_spec: the function_score of every query of a batch (CSR functions; score mode, boost mode,
+    max_boost / min_score behind their flags, and boost per query)."""
+    _fields_ = [("q_fn_offsets", C.c_void_p), ("q_score_mode", C.c_void_p), ("q_boost_mode", C.c_void_p),
+                ("q_flags", C.c_void_p), ("q_max_boost", C.c_void_p), ("q_min_score", C.c_void_p),
+                ("q_boost", C.c_void_p), ("f_kind", C.c_void_p), ("f_field", C.c_void_p), ("f_filter", C.c_void_p),
+                ("f_weight", C.c_void_p), ("f_modifier", C.c_void_p), ("f_decay_fn", C.c_void_p),
+                ("f_missing", C.c_void_p), ("f_origin", C.c_void_p), ("f_scale", C.c_void_p),
+                ("f_offset", C.c_void_p), ("f_decay", C.c_void_p)]
 
 
 class Ticket(C.Structure):
@@ -299,6 +317,9 @@ def load():
         "slg_index_set_positions": (i32, [vp, u32, vp, vp]),
         "slg_batch_prepare_phrase": (vp, [vp, u32, vp, vp, vp, vp, vp, vp, vp, vp, u32, i32]),
         "slg_search_batch_phrase": (i32, [vp, u32, vp, vp, vp, vp, vp, vp, vp, vp, u32, i32, vp, vp, vp, vp, vp, vp]),
+        "slg_batch_prepare_fscore": (vp, [vp, u32, vp, vp, vp, vp, vp, vp, vp, u32, i32]),
+        "slg_batch_fscore_info": (i32, [vp, vp, vp]),
+        "slg_search_batch_fscore": (i32, [vp, u32, vp, vp, vp, vp, vp, vp, vp, u32, i32, vp, vp, vp, vp, vp, vp]),
     }
     for name, (res, args) in sigs.items():
         if os.environ.get("SLG_LIB_TAG") and not hasattr(L, name):

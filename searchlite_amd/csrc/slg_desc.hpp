@@ -226,6 +226,30 @@ constexpr uint32_t kPhraseMaxQueryTerms = 64;  // = SLG_MAX_PHRASE_QUERY_TERMS
 constexpr uint32_t kPhraseMaxSlop = 0x7FFFFFFFu - kPhraseMaxTerms;  // = SLG_MAX_PHRASE_SLOP
 constexpr uint32_t kPositionEnd = 0x80000000u;  // positions are below it (the reference's gaps are i32)
 
+// ---- function_score (slg_batch_prepare_fscore; kernel: slg_fscore.hpp, planner: slg_plan.cpp) --------
+// The functions of query q are fns[fn_begin .. fn_begin + n_fns), in request order, the same for every segment.
+// A function's column is cols[col * n_segs + seg], its filter's reject bitmap filters[(filter - 1) * n_segs + seg].
+struct FscoreQuery {
+  uint32_t fn_begin, n_fns;
+  uint32_t modes;      // bits 0-7 score mode, 8-15 boost mode, 16-23 SLG_FSCORE_HAS_* flags
+  uint32_t work;       // 0: no function, no max_boost, no min_score, boost 1 — the query is left as it is
+  float max_boost, min_score, boost;
+  uint32_t pad;
+};
+struct FscoreFn {
+  uint32_t kinds;      // bits 0-7 SLG_FSCORE_* kind, 8-15 modifier, 16-23 decay function
+  uint32_t col;        // the function's row of the column table (weight: unused)
+  uint32_t filter;     // 0: none; r + 1: row r of the batch's filter table
+  float weight;        // weight, or field_value_factor's factor
+  double missing, origin, scale, offset, decay;
+  uint32_t pad[2];
+};
+struct FscoreColDev {
+  const uint32_t *offs;  // [n_docs + 1] into vals, or nullptr: every doc has exactly one value, vals[doc]
+  const double *vals;
+};
+constexpr uint32_t kFscoreMaxFuncs = 8;  // = SLG_MAX_FSCORE_FUNCS
+
 // ---- merge of per-shard results gathered over RCCL (merge_shards_kernel, slg_kernels.hpp) ----------
 struct ShardMergeParams {
   const uint32_t *doc;    // shard sh's rows start at doc + sh * arr_stride ([nq*k] each)

@@ -1,5 +1,5 @@
 // slg_host.hpp — what the host translation units of the C ABI share (slg_index.hip, slg_batch.hip,
-// slg_shard.hip, slg_rerank.hip, slg_vsearch.hip, slg_hybrid.hip, slg_aggs.hip, slg_rescore.hip, slg_bool.hip, slg_phrase.hip): the error plumbing, device memory, the host
+// slg_shard.hip, slg_rerank.hip, slg_vsearch.hip, slg_hybrid.hip, slg_aggs.hip, slg_rescore.hip, slg_bool.hip, slg_phrase.hip, slg_fscore.hip): the error plumbing, device memory, the host
 // structures behind the opaque handles and the small helpers several entry points use.  Private: not
 // installed, not part of include/.  No kernel header is included here — each unit includes the one
 // whose kernels it launches (slg_stage.hpp, slg_kernels.hpp, slg_rerank.hpp, slg_vsearch.hpp, slg_hybrid.hpp; the shard
@@ -518,6 +518,14 @@ struct slg_batch {
   bool phrase = false;
   uint32_t phrase_vars = 0, phrase_terms = 0;  // entries of the two tables behind the PhraseQuery records
   DevBuf d_phrase_desc;      // slg::PhraseQuery[nq], slg::PhraseVar[phrase_vars], slg::PhraseTerm[phrase_terms]
+  // function_score batch (slg_batch_prepare_fscore): planned as a sorted batch, run in score order or under its
+  // sort spec; fscore_kernel runs between the scoring kernel and the select, rewrites every candidate's score and
+  // drops the candidates below min_score (slg_fscore.hip)
+  bool fscore = false;
+  uint32_t fscore_work = 0;  // queries with work (0: nothing is launched)
+  bool fscore_full = false;  // some function needs ln / log1p / log2 / pow: the full instantiation
+  uint32_t fscore_fns = 0, fscore_cols = 0;  // entries of the two tables behind the FscoreQuery records
+  DevBuf d_fscore_desc;      // slg::FscoreQuery[nq], FscoreFn[fscore_fns], FscoreColDev[fscore_cols], bitmap addresses
 };
 
 namespace slghost __attribute__((visibility("hidden"))) {
@@ -636,6 +644,7 @@ struct PrepareRequest {
   Asked<slg_rescore_spec> rescore;
   Asked<slg_bool_spec> boolean;   // a phrase batch: on, its spec may be NULL (no term groups)
   Asked<slg_phrase_spec> phrase;
+  Asked<slg_fscore_spec> fscore;
 };
 // a spec that is a kind of its own only when it is given (the sort of a bool, phrase, cursor or agg batch)
 template <typename T>
@@ -696,6 +705,12 @@ void bool_launch(slg_batch *b, hipStream_t st);
 // slg_phrase.hip: the same for a phrase batch, behind bool_attach; the launch in bool_launch's place
 void phrase_attach(slg_batch *b, const slgplan::PhrasePlan &pp);
 void phrase_launch(slg_batch *b, hipStream_t st);
+// slg_fscore.hip: an index state's aggregation columns as plan_fscore reads them; the planned tables onto the
+// device (throws; the batch is otherwise prepared); the launch behind the batch's scoring kernel, in front of
+// its select
+std::vector<slgplan::FscoreFieldView> fscore_field_views(const IndexState &S);
+void fscore_attach(slg_batch *b, const slgplan::FscorePlan &fp);
+void fscore_launch(slg_batch *b, hipStream_t st);
 
 // slg_vsearch.hip: one vector search or hybrid call, checked against one state of the index ...
 struct VsCall {

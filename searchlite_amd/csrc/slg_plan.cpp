@@ -1247,6 +1247,136 @@ void plan_phrase(const std::vector<SegView> &segs, uint32_t nq, const slg_bool_s
   }
 }
 
+// ---- function_score ------------------------------------------------------------------------------------
+static_assert(slg::kFscoreMaxFuncs == SLG_MAX_FSCORE_FUNCS, "the kernel's limit and the ABI's");
+static_assert(sizeof(slg::FscoreQuery) == 32 && sizeof(slg::FscoreFn) == 64, "records the kernel reads in whole words");
+
+void check_fscore(const slg_fscore_spec *spec, uint32_t nq) {
+  PLAN_REQUIRE(spec != nullptr, "fscore spec is NULL");
+  if (nq == 0) return;
+  PLAN_REQUIRE(spec->q_fn_offsets != nullptr, "fscore q_fn_offsets is NULL");
+  PLAN_REQUIRE(spec->q_score_mode && spec->q_boost_mode, "fscore q_score_mode/q_boost_mode is NULL");
+  PLAN_REQUIRE(spec->q_flags != nullptr, "fscore q_flags is NULL");
+  PLAN_REQUIRE(spec->q_boost != nullptr, "fscore q_boost is NULL");
+  for (uint32_t q = 0; q < nq; q++)
+    PLAN_REQUIRE(spec->q_fn_offsets[q + 1] >= spec->q_fn_offsets[q], "fscore q_fn_offsets not monotone");
+  const uint32_t f_lo = spec->q_fn_offsets[0], f_hi = spec->q_fn_offsets[nq];
+  PLAN_REQUIRE(f_hi == f_lo || (spec->f_kind && spec->f_field && spec->f_filter && spec->f_weight && spec->f_modifier &&
+                                spec->f_decay_fn && spec->f_missing && spec->f_origin && spec->f_scale && spec->f_offset &&
+                                spec->f_decay),
+               "an fscore f_ array is NULL");
+  for (uint32_t q = 0; q < nq; q++) {
+    const std::string in_q = " in fscore query " + std::to_string(q);
+    const int32_t sm = spec->q_score_mode[q], bm = spec->q_boost_mode[q];
+    PLAN_REQUIRE(sm >= SLG_FSCORE_MODE_SUM && sm <= SLG_FSCORE_MODE_AVG, "unknown score mode" + in_q);
+    PLAN_REQUIRE(bm >= SLG_FSCORE_BOOST_MULTIPLY && bm <= SLG_FSCORE_BOOST_MIN, "unknown boost mode" + in_q);
+    const uint32_t flags = spec->q_flags[q];
+    PLAN_REQUIRE((flags & ~(SLG_FSCORE_HAS_MAX_BOOST | SLG_FSCORE_HAS_MIN_SCORE)) == 0u, "unknown flag" + in_q);
+    PLAN_REQUIRE(!(flags & SLG_FSCORE_HAS_MAX_BOOST) || spec->q_max_boost, "fscore q_max_boost is NULL");
+    PLAN_REQUIRE(!(flags & SLG_FSCORE_HAS_MIN_SCORE) || spec->q_min_score, "fscore q_min_score is NULL");
+    for (uint32_t f = spec->q_fn_offsets[q]; f < spec->q_fn_offsets[q + 1]; f++) {
+      const int32_t kind = spec->f_kind[f];
+      PLAN_REQUIRE(kind >= SLG_FSCORE_WEIGHT && kind <= SLG_FSCORE_DECAY, "unknown function kind" + in_q);
+      PLAN_REQUIRE(spec->f_filter[f] >= -1, "negative filter id other than -1" + in_q);
+      if (kind != SLG_FSCORE_DECAY)
+        PLAN_REQUIRE(std::isfinite(spec->f_weight[f]),
+                     (kind == SLG_FSCORE_WEIGHT ? "non-finite weight" : "non-finite factor") + in_q);
+      if (kind == SLG_FSCORE_FIELD_VALUE_FACTOR) {
+        const int32_t m = spec->f_modifier[f];
+        PLAN_REQUIRE(m >= SLG_FSCORE_MOD_NONE && m <= SLG_FSCORE_MOD_RECIPROCAL, "unknown modifier" + in_q);
+      }
+      if (kind == SLG_FSCORE_DECAY) {
+        const int32_t d = spec->f_decay_fn[f];
+        PLAN_REQUIRE(d >= SLG_FSCORE_DECAY_EXP && d <= SLG_FSCORE_DECAY_LINEAR, "unknown decay function" + in_q);
+        PLAN_REQUIRE(std::isfinite(spec->f_scale[f]), "decay scale must be finite" + in_q);
+        PLAN_REQUIRE(spec->f_scale[f] > 0.0, "decay scale must be > 0" + in_q);
+        PLAN_REQUIRE(spec->f_decay[f] > 0.0 && spec->f_decay[f] <= 1.0, "decay factor outside (0, 1]" + in_q);  // (also: NaN)
+      }
+    }
+  }
+  for (uint32_t q = 0; q < nq; q++)
+    if (spec->q_fn_offsets[q + 1] - spec->q_fn_offsets[q] > SLG_MAX_FSCORE_FUNCS)
+      throw SlgError(SLG_ERR_UNSUPPORTED, "fscore query " + std::to_string(q) + " has more than SLG_MAX_FSCORE_FUNCS functions");
+}
+
+void plan_fscore(const std::vector<FscoreFieldView> &fields, const uint32_t *const *reject, const char *filter_live,
+                 size_t n_filters, uint32_t n_segs, uint32_t nq, const slg_fscore_spec &spec, FscorePlan &out) {
+  out = FscorePlan{};
+  out.queries.assign(nq, slg::FscoreQuery{});
+  if (nq == 0) return;
+  const uint32_t f_base = spec.q_fn_offsets[0];
+  std::vector<int32_t> used_fields, used_filters;  // the rows of the two tables, in order of first use
+  std::string unsupported;                         // (reported behind every invalid argument)
+  auto row_of = [](std::vector<int32_t> &rows, int32_t id) {
+    const auto it = std::find(rows.begin(), rows.end(), id);
+    if (it != rows.end()) return (uint32_t)(it - rows.begin());
+    rows.push_back(id);
+    return (uint32_t)rows.size() - 1u;
+  };
+  for (uint32_t q = 0; q < nq; q++) {
+    const std::string in_q = " in fscore query " + std::to_string(q);
+    const uint32_t f0 = spec.q_fn_offsets[q], nf = spec.q_fn_offsets[q + 1] - f0;
+    slg::FscoreQuery &fq = out.queries[q];
+    const uint32_t flags = spec.q_flags[q];
+    fq.fn_begin = f0 - f_base;
+    fq.n_fns = nf;
+    fq.modes = (uint32_t)spec.q_score_mode[q] | ((uint32_t)spec.q_boost_mode[q] << 8) | (flags << 16);
+    fq.max_boost = (flags & SLG_FSCORE_HAS_MAX_BOOST) ? spec.q_max_boost[q] : 0.0f;
+    fq.min_score = (flags & SLG_FSCORE_HAS_MIN_SCORE) ? spec.q_min_score[q] : 0.0f;
+    fq.boost = spec.q_boost[q];
+    fq.work = (nf != 0u || flags != 0u || !(fq.boost == 1.0f)) ? 1u : 0u;
+    out.n_work += fq.work;
+    for (uint32_t f = f0; f < f0 + nf; f++) {
+      slg::FscoreFn fn{};
+      const int32_t kind = spec.f_kind[f];
+      fn.kinds = (uint32_t)kind;
+      fn.weight = spec.f_weight[f];
+      if (spec.f_filter[f] >= 0) {
+        PLAN_REQUIRE((size_t)spec.f_filter[f] < n_filters && filter_live[spec.f_filter[f]],
+                     "unknown filter id " + std::to_string(spec.f_filter[f]) + in_q);
+        fn.filter = row_of(used_filters, spec.f_filter[f]) + 1u;
+      }
+      if (kind != SLG_FSCORE_WEIGHT) {
+        const int32_t id = spec.f_field[f];
+        const auto it = std::find_if(fields.begin(), fields.end(), [id](const FscoreFieldView &v) { return v.id == id; });
+        PLAN_REQUIRE(it != fields.end(), "unknown agg field id " + std::to_string(id) + in_q);
+        PLAN_REQUIRE(!it->keyword, "agg field " + std::to_string(id) + " is a keyword field" + in_q);
+        for (uint32_t s = 0; s < n_segs; s++)
+          PLAN_REQUIRE(s < it->per_seg.size() && it->per_seg[s].vals != nullptr,
+                       "agg field " + std::to_string(id) + " has no column for segment " + std::to_string(s) +
+                           " (added after the field was registered)");
+        if (it->non_finite && unsupported.empty())
+          unsupported = "agg field " + std::to_string(id) + " holds a non-finite value (CPU path)" + in_q;
+        fn.col = row_of(used_fields, id);
+      }
+      if (kind == SLG_FSCORE_FIELD_VALUE_FACTOR) {
+        const int32_t m = spec.f_modifier[f];
+        fn.kinds |= (uint32_t)m << 8;
+        fn.missing = spec.f_missing[f];
+        out.full = out.full || m == SLG_FSCORE_MOD_LOG || m == SLG_FSCORE_MOD_LOG1P || m == SLG_FSCORE_MOD_LOG2P;
+      } else if (kind == SLG_FSCORE_DECAY) {
+        const int32_t d = spec.f_decay_fn[f];
+        fn.kinds |= (uint32_t)d << 16;
+        fn.origin = spec.f_origin[f];
+        fn.scale = spec.f_scale[f];
+        fn.offset = spec.f_offset[f];
+        fn.decay = spec.f_decay[f];
+        out.full = out.full || d != SLG_FSCORE_DECAY_LINEAR;
+      }
+      out.fns.push_back(fn);
+    }
+  }
+  if (!unsupported.empty()) throw SlgError(SLG_ERR_UNSUPPORTED, unsupported);
+  out.cols.reserve(used_fields.size() * n_segs);
+  for (const int32_t id : used_fields) {
+    const auto it = std::find_if(fields.begin(), fields.end(), [id](const FscoreFieldView &v) { return v.id == id; });
+    out.cols.insert(out.cols.end(), it->per_seg.begin(), it->per_seg.begin() + n_segs);
+  }
+  out.filters.reserve(used_filters.size() * n_segs);
+  for (const int32_t f : used_filters)
+    for (uint32_t s = 0; s < n_segs; s++) out.filters.push_back(reject[(size_t)f * n_segs + s]);
+}
+
 // ---- sort keys of numeric fast fields ----------------------------------------------------------
 namespace {
 inline uint64_t i64_key(int64_t v) { return (uint64_t)v ^ 0x8000000000000000ull; }

@@ -168,6 +168,34 @@ struct PhrasePlan {
 void plan_phrase(const std::vector<SegView> &segs, uint32_t nq, const slg_bool_spec *bool_or_null,
                  const slg_phrase_spec &spec, PhrasePlan &out);
 
+// ---- function_score (slg_batch_prepare_fscore) ----
+// The checks of a spec that need no index (throws SlgError).  SLG_ERR_INVALID, reported first: a NULL spec or
+// array, offsets that decrease, an unknown kind, mode, modifier or decay function, a non-finite weight or factor,
+// a non-finite scale or scale <= 0, decay outside (0, 1].  SLG_ERR_UNSUPPORTED: more than SLG_MAX_FSCORE_FUNCS
+// functions in a query.
+void check_fscore(const slg_fscore_spec *spec, uint32_t nq);
+// What plan_fscore sees of a registered aggregation column: per segment its two device arrays, as opaque
+// addresses (vals null: the field has no column for that segment)
+struct FscoreFieldView {
+  int32_t id = 0;
+  bool keyword = false, non_finite = false;
+  std::vector<slg::FscoreColDev> per_seg;  // [n_segs]
+};
+// The tables of a checked spec against an index state's fields and filters.  reject: the state's flattened
+// [filter * n_segs + seg] reject bitmaps (device addresses), filter_live [n_filters] as BatchIn's.  Throws
+// SLG_ERR_INVALID for an unknown field or filter id, a keyword column, a field without a column for a segment;
+// SLG_ERR_UNSUPPORTED for a column that holds a non-finite value.
+struct FscorePlan {
+  std::vector<slg::FscoreQuery> queries;   // [nq]
+  std::vector<slg::FscoreFn> fns;          // the spec's functions, in its order
+  std::vector<slg::FscoreColDev> cols;     // [fields the batch names][n_segs]
+  std::vector<const uint32_t *> filters;   // [filters the batch names][n_segs]
+  uint32_t n_work = 0;                     // queries with work (0: nothing is launched)
+  bool full = false;                       // some function needs ln / log1p / log2 / pow
+};
+void plan_fscore(const std::vector<FscoreFieldView> &fields, const uint32_t *const *reject, const char *filter_live,
+                 size_t n_filters, uint32_t n_segs, uint32_t nq, const slg_fscore_spec &spec, FscorePlan &out);
+
 // Throws SlgError (SLG_ERR_INVALID / SLG_ERR_UNSUPPORTED) on malformed input.
 void plan_batch(const std::vector<SegView> &segs, const slg_tuning &tune, const BatchIn &in, Plan &out);
 

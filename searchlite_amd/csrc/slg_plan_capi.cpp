@@ -242,6 +242,71 @@ int slgp_plan_phrase(const slgp_segment *segs, const uint8_t *seg_has_pos, uint3
   }
 }
 
+// the host side of slg_batch_prepare_fscore: check_fscore, then plan_fscore against registered fields and filters
+// that exist as descriptions only.  A field's column of segment s: seg_has[s] 0 = none; seg_dense[s] 1 = stored
+// without offsets.  The tables carry addresses that are never read and name what they stand for: a column's values
+// (id + 1) << 32 | s << 8 | 1, its offsets the same | 2 (0 when dense), the reject bitmap of filter f in segment s
+// (f + 1) << 32 | s << 8 | 3.  queries: nq x 8 words (slg::FscoreQuery); fns: entries of 16 words (slg::FscoreFn);
+// cols: entries of two addresses (offsets, values); filters: addresses.  Each table is filled when it fits its cap;
+// counts: entries of fns, cols, filters, then the queries with work and 1 for the full kernel.  0, or a negative
+// error code (err filled)
+struct slgp_fscore_field {
+  int32_t id;
+  uint32_t keyword, non_finite;
+  const uint8_t *seg_has, *seg_dense;
+};
+int slgp_plan_fscore(const slgp_fscore_field *fields, uint32_t n_fields, const char *filter_live, uint32_t n_filters,
+                     uint32_t n_segs, uint32_t nq, const slg_fscore_spec *spec, uint32_t *queries, uint32_t *fns,
+                     uint32_t fns_cap, uint64_t *cols, uint32_t cols_cap, uint64_t *filters, uint32_t filters_cap,
+                     uint32_t *counts, char *err, uint32_t err_len) {
+  try {
+    slgplan::check_fscore(spec, nq);
+    std::vector<slgplan::FscoreFieldView> views(n_fields);
+    for (uint32_t i = 0; i < n_fields; i++) {
+      views[i].id = fields[i].id;
+      views[i].keyword = fields[i].keyword != 0;
+      views[i].non_finite = fields[i].non_finite != 0;
+      views[i].per_seg.assign(n_segs, slg::FscoreColDev{nullptr, nullptr});
+      for (uint32_t s = 0; s < n_segs; s++) {
+        if (!fields[i].seg_has[s]) continue;
+        const uint64_t a = ((uint64_t)(fields[i].id + 1) << 32) | ((uint64_t)s << 8);
+        views[i].per_seg[s].vals = reinterpret_cast<const double *>((uintptr_t)(a | 1u));
+        if (!fields[i].seg_dense[s]) views[i].per_seg[s].offs = reinterpret_cast<const uint32_t *>((uintptr_t)(a | 2u));
+      }
+    }
+    std::vector<const uint32_t *> reject((size_t)n_filters * n_segs);
+    for (uint32_t f = 0; f < n_filters; f++)
+      for (uint32_t s = 0; s < n_segs; s++)
+        reject[(size_t)f * n_segs + s] =
+            reinterpret_cast<const uint32_t *>((uintptr_t)(((uint64_t)(f + 1) << 32) | ((uint64_t)s << 8) | 3u));
+    slgplan::FscorePlan fp;
+    slgplan::plan_fscore(views, reject.data(), filter_live, n_filters, n_segs, nq, *spec, fp);
+    static_assert(sizeof(slg::FscoreQuery) == 32 && sizeof(slg::FscoreFn) == 64 && sizeof(slg::FscoreColDev) == 16,
+                  "the words the caller reads");
+    if (queries && nq) std::memcpy(queries, fp.queries.data(), (size_t)nq * sizeof(slg::FscoreQuery));
+    if (fns && fp.fns.size() <= fns_cap && !fp.fns.empty())
+      std::memcpy(fns, fp.fns.data(), fp.fns.size() * sizeof(slg::FscoreFn));
+    if (cols && fp.cols.size() <= cols_cap && !fp.cols.empty())
+      std::memcpy(cols, fp.cols.data(), fp.cols.size() * sizeof(slg::FscoreColDev));
+    if (filters && fp.filters.size() <= filters_cap && !fp.filters.empty())
+      std::memcpy(filters, fp.filters.data(), fp.filters.size() * sizeof(void *));
+    if (counts) {
+      counts[0] = (uint32_t)fp.fns.size();
+      counts[1] = (uint32_t)fp.cols.size();
+      counts[2] = (uint32_t)fp.filters.size();
+      counts[3] = fp.n_work;
+      counts[4] = fp.full ? 1u : 0u;
+    }
+    return SLG_OK;
+  } catch (const slgplan::SlgError &e) {
+    if (err && err_len) {
+      std::strncpy(err, e.what(), err_len - 1);
+      err[err_len - 1] = 0;
+    }
+    return e.code;
+  }
+}
+
 // the host checks of slg_index_set_positions over a segment of n_postings postings.  0, or a negative error code
 int slgp_check_positions(uint64_t n_postings, const uint64_t *pos_offsets, const uint32_t *positions, char *err,
                          uint32_t err_len) {

@@ -366,6 +366,20 @@ class GpuIndex:
         finally:
             b.close()
 
+    def search_batch_fscore(self, q_offsets, q_terms, q_weights, k: int, functions, sort=None, strategy: int = Wand,
+                            q_filter=None, want_stats: bool = False, **plans):
+        """Batch search under a function_score per query (slg_batch_prepare_fscore).  functions: the list of
+        fscore_spec(), one entry per query (None: the query is left as it is); columns are agg field ids
+        (add_agg_field), function filters are filter ids (add_filter*); sort: None = order of the new score, else
+        as search_sorted; **plans: the score plan arrays of prepare().
+        -> (doc, seg, score, count[, stats]) in score order, (doc, seg, score, count[, stats], matched) sorted."""
+        b = self.prepare(q_offsets, q_terms, q_weights, k, strategy, q_filter, sort=sort, fscore=functions, **plans)
+        try:
+            b.run()
+            return b.fetch(want_stats) + ((b.matched_counts(),) if sort is not None else ())
+        finally:
+            b.close()
+
     def search_sorted(self, q_offsets, q_terms, q_weights, k: int, sort, strategy: int = Wand, q_filter=None,
                       **plans):
         """Field-sorted batch search (slg_batch_prepare_sorted).  sort: [(field, order)], field = a sort field id
@@ -398,7 +412,7 @@ class GpuIndex:
                 q_leaf_offsets=None, leaf_group=None, q_group_offsets=None, group_plan=None,
                 group_tie=None, q_node_offsets=None, node_kind=None, node_tie=None, node_parent=None,
                 q_min_match=None, sort=None, cursors=None, hybrid=False, aggs=None,
-                rescore=None, clauses=None, phrases=None) -> "PreparedBatch":
+                rescore=None, clauses=None, phrases=None, fscore=None) -> "PreparedBatch":
         """q_leaf / q_plan / q_tie / q_nleaves: score plans; leaf_group / group_plan / group_tie with
         their per-query offsets: two-level plans; q_node_offsets / node_kind / node_tie / node_parent:
         trees of any shape, node by node in pre-order (slg_batch_prepare_plans, slg_score_plans);
@@ -409,11 +423,12 @@ class GpuIndex:
         slg_batch_prepare_aggs (PreparedBatch.aggs); rescore: the dict of search_rescore ->
         slg_batch_prepare_rescore (PreparedBatch.rescore_details); clauses: the dict of search_batch_bool ->
         slg_batch_prepare_bool (score order, or with sort); phrases: the dict of search_batch_phrase ->
-        slg_batch_prepare_phrase (with clauses as its term groups, or without)."""
+        slg_batch_prepare_phrase (with clauses as its term groups, or without); fscore: one function_score per
+        query, the list of fscore_spec() (or its result) -> slg_batch_prepare_fscore (score order, or with sort)."""
         return PreparedBatch(self, q_offsets, q_terms, q_weights, k, strategy, q_filter,
                              q_leaf, q_plan, q_tie, q_nleaves, q_leaf_offsets, leaf_group,
                              q_group_offsets, group_plan, group_tie, q_node_offsets, node_kind, node_tie, node_parent,
-                             q_min_match, sort, cursors, hybrid, aggs, rescore, clauses, phrases)
+                             q_min_match, sort, cursors, hybrid, aggs, rescore, clauses, phrases, fscore)
 
     def search_plan(self, q_offsets, q_terms, q_weights, k: int, q_leaf=None, q_plan=None,
                     q_tie=None, q_nleaves=None, strategy: int = Wand, q_filter=None, **tree):
@@ -763,6 +778,60 @@ def phrase_spec(phrases: dict, nq: int):
     return N.PhraseSpec(*[_ptr(a) for a in keep]), keep
 
 
+FSCORE_KINDS = {"weight": N.FSCORE_WEIGHT, "field_value_factor": N.FSCORE_FIELD_VALUE_FACTOR, "decay": N.FSCORE_DECAY}
+FSCORE_MODIFIERS = {"none": N.FSCORE_MOD_NONE, "log": N.FSCORE_MOD_LOG, "log1p": N.FSCORE_MOD_LOG1P,
+                    "log2p": N.FSCORE_MOD_LOG2P, "sqrt": N.FSCORE_MOD_SQRT, "reciprocal": N.FSCORE_MOD_RECIPROCAL}
+FSCORE_DECAYS = {"exp": N.FSCORE_DECAY_EXP, "gauss": N.FSCORE_DECAY_GAUSS, "linear": N.FSCORE_DECAY_LINEAR}
+FSCORE_MODES = {"sum": N.FSCORE_MODE_SUM, "multiply": N.FSCORE_MODE_MULTIPLY, "max": N.FSCORE_MODE_MAX,
+                "min": N.FSCORE_MODE_MIN, "avg": N.FSCORE_MODE_AVG}
+FSCORE_BOOSTS = {"multiply": N.FSCORE_BOOST_MULTIPLY, "sum": N.FSCORE_BOOST_SUM, "replace": N.FSCORE_BOOST_REPLACE,
+                 "max": N.FSCORE_BOOST_MAX, "min": N.FSCORE_BOOST_MIN}
+
+
+def fscore_spec(functions, nq: int):
+    """One function_score per query as (N.FscoreSpec, the arrays it points into).  functions[q]: None (the query
+    is left as it is) or a dict with `functions` (a list, in request order), `score_mode` ("multiply"), `boost_mode`
+    ("multiply"), `max_boost` (None), `min_score` (None) and `boost` (1.0) — the request's defaults.  A function
+    is a dict with `kind` ("weight" / "field_value_factor" / "decay") and `filter` (a filter id, default -1), plus
+    weight: `weight`; field_value_factor: `field` (agg field id), `factor` (1.0), `modifier` ("none"), `missing`
+    (0.0); decay: `field`, `origin`, `scale`, `offset` (0.0), `decay` (0.5), `function` ("exp").  Names may also be
+    the numbers of N.FSCORE_*."""
+    assert len(functions) == nq
+    num = lambda table, v: table.get(v, v) if isinstance(v, str) else int(v)
+    q = dict(off=[0], sm=[], bm=[], flags=[], maxb=[], mins=[], boost=[])
+    f = dict(kind=[], field=[], filt=[], w=[], mod=[], dfn=[], missing=[], origin=[], scale=[], offset=[], decay=[])
+    for fsq in functions:
+        fsq = fsq or {}
+        for fn in fsq.get("functions", ()):
+            kind = num(FSCORE_KINDS, fn["kind"])
+            f["kind"].append(kind)
+            f["field"].append(int(fn.get("field", -1)))
+            f["filt"].append(int(fn.get("filter", -1)))
+            f["w"].append(fn["weight"] if kind == N.FSCORE_WEIGHT else fn.get("factor", 1.0))
+            f["mod"].append(num(FSCORE_MODIFIERS, fn.get("modifier", "none")))
+            f["dfn"].append(num(FSCORE_DECAYS, fn.get("function", "exp")))
+            f["missing"].append(fn.get("missing", 0.0))
+            f["origin"].append(fn.get("origin", 0.0))
+            f["scale"].append(fn.get("scale", 1.0))
+            f["offset"].append(fn.get("offset", 0.0))
+            f["decay"].append(fn.get("decay", 0.5))
+        q["off"].append(len(f["kind"]))
+        q["sm"].append(num(FSCORE_MODES, fsq.get("score_mode", "multiply")))
+        q["bm"].append(num(FSCORE_BOOSTS, fsq.get("boost_mode", "multiply")))
+        maxb, mins = fsq.get("max_boost"), fsq.get("min_score")
+        q["flags"].append((N.FSCORE_HAS_MAX_BOOST if maxb is not None else 0) | (N.FSCORE_HAS_MIN_SCORE if mins is not None else 0))
+        q["maxb"].append(0.0 if maxb is None else maxb)
+        q["mins"].append(0.0 if mins is None else mins)
+        q["boost"].append(fsq.get("boost", 1.0))
+    pad = lambda a, dt: np.ascontiguousarray(a if len(a) else [0], dtype=dt)  # (never NULL: an empty array is read nowhere)
+    keep = [pad(q["off"], np.uint32), pad(q["sm"], np.int32), pad(q["bm"], np.int32), pad(q["flags"], np.uint32),
+            pad(q["maxb"], np.float32), pad(q["mins"], np.float32), pad(q["boost"], np.float32),
+            pad(f["kind"], np.int32), pad(f["field"], np.int32), pad(f["filt"], np.int32), pad(f["w"], np.float32),
+            pad(f["mod"], np.int32), pad(f["dfn"], np.int32), pad(f["missing"], np.float64), pad(f["origin"], np.float64),
+            pad(f["scale"], np.float64), pad(f["offset"], np.float64), pad(f["decay"], np.float64)]
+    return N.FscoreSpec(*[_ptr(a) for a in keep]), keep
+
+
 def sort_cursor(cursor, sort=None) -> "N.SortCursor":
     """None (a first page), an N.SortCursor, or (values, segment_ord, doc_id) -> slg_sort_cursor.  values: one
     per sort part (score order: one, the score): an int is an i64 value, a float an f64 value (or, on a
@@ -795,7 +864,7 @@ class PreparedBatch:
                  q_leaf_offsets=None, leaf_group=None, q_group_offsets=None, group_plan=None,
                  group_tie=None, q_node_offsets=None, node_kind=None, node_tie=None, node_parent=None,
                  q_min_match=None, sort=None, cursors=None, hybrid=False, aggs=None, rescore=None, clauses=None,
-                 phrases=None):
+                 phrases=None, fscore=None):
         self.index = index
         self._lib = index._lib
         q_offsets = np.ascontiguousarray(q_offsets, dtype=np.uint32)
@@ -831,7 +900,19 @@ class PreparedBatch:
         self.is_rescore = rescore is not None
         self.is_bool = clauses is not None or phrases is not None
         self.is_phrase = phrases is not None
-        if phrases is not None:
+        self.is_fscore = fscore is not None
+        if fscore is not None:
+            # (the library's other prepare calls take no fscore spec: the refusal is made here with its code)
+            if hybrid or cursors is not None or aggs is not None or rescore is not None or clauses is not None or \
+                    phrases is not None:
+                raise N.SlgError(N.ERR_UNSUPPORTED, "function_score is not built on cursor, hybrid, aggregation, "
+                                                    "rescore, bool or phrase batches")
+            fspec, self._fscore_keep = fscore if isinstance(fscore, tuple) else fscore_spec(fscore, self.nq)
+            spec = None if sort is None else sort_spec(sort)
+            self._h = self._lib.slg_batch_prepare_fscore(
+                index._h, self.nq, _ptr(q_offsets), _ptr(q_terms), _ptr(q_weights), C.addressof(plans),
+                opt(qf), None if spec is None else C.addressof(spec), C.addressof(fspec), k, strategy)
+        elif phrases is not None:
             # (the library's other prepare calls take no phrase spec: the refusal is made here with its code)
             if hybrid or cursors is not None or aggs is not None or rescore is not None:
                 raise N.SlgError(N.ERR_UNSUPPORTED, "phrases are not built on cursor, hybrid, aggregation or rescore batches")
@@ -1054,8 +1135,13 @@ class PreparedBatch:
         npost, nsl, nbytes = C.c_uint64(), C.c_uint32(), C.c_uint64()
         N.check(self._lib.slg_batch_info(self._h, C.addressof(npost), C.addressof(nsl),
                                          C.addressof(nbytes)))
-        return {"n_postings": npost.value, "n_slices": nsl.value,
-                "algorithmic_bytes": nbytes.value}
+        out = {"n_postings": npost.value, "n_slices": nsl.value, "algorithmic_bytes": nbytes.value}
+        if getattr(self, "is_fscore", False):  # which fscore_kernel runs: None (nothing is launched), "lean", "full"
+            variant, work = C.c_uint32(), C.c_uint32()
+            N.check(self._lib.slg_batch_fscore_info(self._h, C.addressof(variant), C.addressof(work)))
+            out["fscore_kernel"] = (None, "lean", "full")[variant.value]
+            out["fscore_queries"] = work.value
+        return out
 
     def skip_counts(self):
         """-> (postings of pruning-classified lists the plan covered, those never loaded) of the

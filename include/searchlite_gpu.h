@@ -305,6 +305,69 @@ int slg_index_add_filter_terms(slg_index *index, const uint32_t *term_ids, uint3
  * batch's index state) and may still run; the id may be handed out again by a later add. */
 int slg_index_remove_filter(slg_index *index, int filter_id);
 
+/* ---- filter trees built on the device (query/filters.rs:84-149; index/fastfields.rs:490-640) ----
+ * A filter tree (api/types.rs: KeywordEq, KeywordIn, I64Range, F64Range, And, Or, Not) over the columns
+ * registered with slg_index_add_agg_field_* is evaluated on the device, doc by doc, into the reject bitmap every
+ * batch kind reads.  A tree is a POSTFIX program: a leaf pushes one value, AND / OR replace the `arity` values on
+ * top of the stack by one, NOT replaces the top; the program ends with exactly one value.
+ *   KEYWORD_IN  field: a keyword column.  Passes iff ANY ordinal of the doc is in ords[ord_begin .. ord_begin +
+ *               n_ords_in) of the tree (repeats allowed; an empty set passes nothing).  The caller resolves
+ *               KeywordEq / KeywordIn strings to ordinals with the reference's case_insensitive_equals: several
+ *               dictionary keys may fold to one value.  An ordinal >= the field's n_ords: SLG_ERR_INVALID.
+ *   RANGE_F64   field: a numeric column.  Passes iff any value v of the doc has lo_f <= v && v <= hi_f in IEEE
+ *               f64: a NaN value never passes, infinite bounds are allowed, a NaN bound is SLG_ERR_INVALID.  A
+ *               column that holds non-finite values is accepted (the comparison is well defined).
+ *   RANGE_I64   field: a numeric column registered with slg_index_add_agg_field_i64 (on an _f64 column:
+ *               SLG_ERR_INVALID).  The column holds `v as f64`: one whose finite minimum or maximum lies outside
+ *               +-2^53 is refused with SLG_ERR_UNSUPPORTED (those values were rounded at registration);
+ *               otherwise lo_i / hi_i are clamped into +-2^53 and compared in f64, which is exact (a lo_i above
+ *               2^53 or a hi_i below -2^53 passes nothing: it is compared as the infinity, not as the clamped value,
+ *               which a stored +-2^53 would equal).
+ *   FILTER_ID   filter_id: a registered filter of any kind.  Passes iff its reject bit is clear.  That bitmap
+ *               already holds the tombstones, so NOT over this leaf passes deleted docs inside the tree; the
+ *               final bitmap ORs the tombstones in again, so the result is right all the same.  This leaf is how
+ *               Nested sub-filters, not-term filters and any host-made bitmap compose with the rest.
+ *   AND / OR    arity children (0 and up): AND of none is true (passes_filters_at on an empty list), OR of none
+ *               is false.  NOT: exactly one child.
+ * A doc without a value fails every leaf over that column (NOT of the leaf then passes it); so does every doc of
+ * a segment registered with seg_offsets[s] == NULL.  Final bitmap of every segment: reject = deleted | ~tree;
+ * bits past n_docs are set. */
+enum { SLG_FILTER_KEYWORD_IN = 0, SLG_FILTER_RANGE_F64 = 1, SLG_FILTER_RANGE_I64 = 2, SLG_FILTER_ID = 3,
+       SLG_FILTER_AND = 4, SLG_FILTER_OR = 5, SLG_FILTER_NOT = 6 };
+#define SLG_MAX_FILTER_NODES 64u   /* nodes of one tree */
+#define SLG_MAX_FILTER_DEPTH 16u   /* deepest evaluation stack */
+#define SLG_MAX_FILTER_TREES 64u   /* trees of one call */
+typedef struct slg_filter_node {
+  int32_t kind;        /* SLG_FILTER_* */
+  int32_t field;       /* agg field id (KEYWORD_IN, RANGE_*) */
+  int32_t filter_id;   /* FILTER_ID */
+  uint32_t arity;      /* AND / OR */
+  double lo_f, hi_f;   /* RANGE_F64 */
+  int64_t lo_i, hi_i;  /* RANGE_I64 */
+  uint32_t ord_begin, n_ords_in;  /* KEYWORD_IN: a range of the tree's ords */
+} slg_filter_node;
+typedef struct slg_filter_tree {
+  uint32_t n_nodes;
+  const slg_filter_node *nodes;
+  uint32_t n_ords;
+  const uint32_t *ords;
+} slg_filter_tree;
+/* Registers n_trees filters in ONE update of the index's state (a retired state costs a device synchronise: n
+ * filters must not cost n updates); out_ids[t] is the filter id of trees[t], handed out as by slg_index_add_filter
+ * (lowest free ids).  All or nothing: on an error no id is handed out and the index is as it was.  Afterwards the
+ * filters are ordinary filters (slg_index_remove_filter, slg_index_update_deleted, slg_index_add_segment and
+ * slg_index_remove_segment treat them like any other).  Errors, in this order: SLG_ERR_INVALID before the index
+ * is looked at (NULL arrays; n_trees == 0 or n_nodes == 0; an unknown kind; a program that underflows the stack or
+ * does not end with exactly one value; an arity larger than the stack; a NaN bound; ord_begin + n_ords_in >
+ * n_ords), then SLG_ERR_UNSUPPORTED (more than SLG_MAX_FILTER_NODES nodes, a stack deeper than
+ * SLG_MAX_FILTER_DEPTH, more than SLG_MAX_FILTER_TREES trees), then against the index SLG_ERR_INVALID (an unknown
+ * field or filter id; a field or filter without data for every segment; the wrong column kind; an ordinal out of
+ * range), then SLG_ERR_UNSUPPORTED for the 2^53 rule.  Returns 0 or an error code. */
+int slg_index_add_filter_trees(slg_index *index, const slg_filter_tree *trees, uint32_t n_trees, int32_t *out_ids);
+/* The PASS bits (~reject: the doc is alive and passes) of segment seg of any registered filter, whichever call
+ * made it: ceil(n_docs / 8) bytes, bit d & 7 of byte d >> 3. */
+int slg_index_fetch_filter(slg_index *index, int filter_id, uint32_t seg, uint8_t *out_pass);
+
 /* ---- sort fields (query/sort.rs: `sort` on numeric fast fields) -----------------------
  * A numeric fast field registered once per index and named by id in sorted batches
  * (slg_batch_prepare_sorted).  Per segment the doc's values as CSR: seg_offsets[s][n_docs + 1] into

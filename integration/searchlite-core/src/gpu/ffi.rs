@@ -83,6 +83,13 @@ pub const SLG_AGG_STATS: i32 = 3;
     pub f_modifier: *const i32, pub f_decay_fn: *const i32, pub f_missing: *const f64, pub f_origin: *const f64,
     pub f_scale: *const f64, pub f_offset: *const f64, pub f_decay: *const f64,
 }
+#[repr(C)] pub struct slg_filter_node {
+    pub kind: i32, pub field: i32, pub filter_id: i32, pub arity: u32, pub lo_f: f64, pub hi_f: f64,
+    pub lo_i: i64, pub hi_i: i64, pub ord_begin: u32, pub n_ords_in: u32,
+}
+#[repr(C)] pub struct slg_filter_tree {
+    pub n_nodes: u32, pub nodes: *const slg_filter_node, pub n_ords: u32, pub ords: *const u32,
+}
 #[repr(C)] pub struct slg_phrase_spec {
     pub p_offsets: *const u32, pub p_kind: *const i32, pub p_slop: *const u32, pub v_offsets: *const u32,
     pub t_offsets: *const u32, pub t_term_ids: *const u32, pub q_min_should: *const u32,
@@ -323,6 +330,9 @@ extern "C" {
     pub fn slg_batch_prepare_fscore(index: *mut slg_index, nq: u32, q_offsets: *const u32, q_term_ids: *const u32,
         q_weights: *const c_float, plans: *const slg_score_plans, q_filter: *const i32,
         sort: *const slg_sort_spec, spec: *const slg_fscore_spec, k: u32, strategy: c_int) -> *mut slg_batch;
+    pub fn slg_index_add_filter_trees(index: *mut slg_index, trees: *const slg_filter_tree, n_trees: u32,
+        out_ids: *mut i32) -> c_int;
+    pub fn slg_index_fetch_filter(index: *mut slg_index, filter_id: c_int, seg: u32, out_pass: *mut u8) -> c_int;
     pub fn slg_batch_fscore_info(batch: *const slg_batch, out_variant: *mut u32, out_queries_with_work: *mut u32) -> c_int;
     pub fn slg_search_batch_fscore(index: *mut slg_index, nq: u32, q_offsets: *const u32, q_term_ids: *const u32,
         q_weights: *const c_float, plans: *const slg_score_plans, q_filter: *const i32,
@@ -364,6 +374,16 @@ pub const SLG_FSCORE_BOOST_MAX: i32 = 3;
 pub const SLG_FSCORE_BOOST_MIN: i32 = 4;
 pub const SLG_FSCORE_HAS_MAX_BOOST: u32 = 1;
 pub const SLG_FSCORE_HAS_MIN_SCORE: u32 = 2;
+pub const SLG_FILTER_KEYWORD_IN: i32 = 0;
+pub const SLG_FILTER_RANGE_F64: i32 = 1;
+pub const SLG_FILTER_RANGE_I64: i32 = 2;
+pub const SLG_FILTER_ID: i32 = 3;
+pub const SLG_FILTER_AND: i32 = 4;
+pub const SLG_FILTER_OR: i32 = 5;
+pub const SLG_FILTER_NOT: i32 = 6;
+pub const SLG_MAX_FILTER_NODES: u32 = 64;
+pub const SLG_MAX_FILTER_DEPTH: u32 = 16;
+pub const SLG_MAX_FILTER_TREES: u32 = 64;
 pub const SLG_RESCORE_TOTAL: i32 = 0;
 pub const SLG_RESCORE_MULTIPLY: i32 = 1;
 pub const SLG_RESCORE_SUM: i32 = 2;

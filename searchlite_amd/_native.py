@@ -47,6 +47,8 @@ FSCORE_DECAY_EXP, FSCORE_DECAY_GAUSS, FSCORE_DECAY_LINEAR = 0, 1, 2
 FSCORE_MODE_SUM, FSCORE_MODE_MULTIPLY, FSCORE_MODE_MAX, FSCORE_MODE_MIN, FSCORE_MODE_AVG = 0, 1, 2, 3, 4
 FSCORE_BOOST_MULTIPLY, FSCORE_BOOST_SUM, FSCORE_BOOST_REPLACE, FSCORE_BOOST_MAX, FSCORE_BOOST_MIN = 0, 1, 2, 3, 4
 FSCORE_HAS_MAX_BOOST, FSCORE_HAS_MIN_SCORE = 1, 2
+FILTER_KEYWORD_IN, FILTER_RANGE_F64, FILTER_RANGE_I64, FILTER_ID, FILTER_AND, FILTER_OR, FILTER_NOT = 0, 1, 2, 3, 4, 5, 6
+MAX_FILTER_NODES, MAX_FILTER_DEPTH, MAX_FILTER_TREES = 64, 16, 64
 
 
 class SlgError(RuntimeError):
@@ -167,6 +169,18 @@ class FscoreSpec(C.Structure):
                 ("f_weight", C.c_void_p), ("f_modifier", C.c_void_p), ("f_decay_fn", C.c_void_p),
                 ("f_missing", C.c_void_p), ("f_origin", C.c_void_p), ("f_scale", C.c_void_p),
                 ("f_offset", C.c_void_p), ("f_decay", C.c_void_p)]
+
+
+class FilterNode(C.Structure):
+    """slg_filter_node: one node of a filter tree's postfix program (slg_index_add_filter_trees)."""
+    _fields_ = [("kind", C.c_int32), ("field", C.c_int32), ("filter_id", C.c_int32), ("arity", C.c_uint32),
+                ("lo_f", C.c_double), ("hi_f", C.c_double), ("lo_i", C.c_int64), ("hi_i", C.c_int64),
+                ("ord_begin", C.c_uint32), ("n_ords_in", C.c_uint32)]
+
+
+class FilterTree(C.Structure):
+    """slg_filter_tree: the nodes of one tree and the ordinals its KEYWORD_IN nodes point into."""
+    _fields_ = [("n_nodes", C.c_uint32), ("nodes", C.c_void_p), ("n_ords", C.c_uint32), ("ords", C.c_void_p)]
 
 
 class Ticket(C.Structure):
@@ -319,6 +333,8 @@ def load():
         "slg_search_batch_phrase": (i32, [vp, u32, vp, vp, vp, vp, vp, vp, vp, vp, u32, i32, vp, vp, vp, vp, vp, vp]),
         "slg_batch_prepare_fscore": (vp, [vp, u32, vp, vp, vp, vp, vp, vp, vp, u32, i32]),
         "slg_batch_fscore_info": (i32, [vp, vp, vp]),
+        "slg_index_add_filter_trees": (i32, [vp, vp, u32, vp]),
+        "slg_index_fetch_filter": (i32, [vp, i32, u32, vp]),
         "slg_search_batch_fscore": (i32, [vp, u32, vp, vp, vp, vp, vp, vp, vp, u32, i32, vp, vp, vp, vp, vp, vp]),
     }
     for name, (res, args) in sigs.items():

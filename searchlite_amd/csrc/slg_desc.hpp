@@ -250,6 +250,24 @@ struct FscoreColDev {
 };
 constexpr uint32_t kFscoreMaxFuncs = 8;  // = SLG_MAX_FSCORE_FUNCS
 
+// ---- filter trees (slg_index_add_filter_trees; kernel: slg_filter.hpp, planner: slg_plan.cpp) --------
+// The image of one call: trees[n_trees], nodes (every tree's, in postfix order), the column table, the filter
+// table, the words of the ordinal bit sets.  A leaf's column is cols[row * n_segs + seg] (FscoreColDev; a keyword
+// column's vals are u32 ordinals), a FILTER_ID leaf's reject bitmap filters[row * n_segs + seg].
+struct FilterTreeDev {
+  uint32_t node_begin, n_nodes;
+};
+struct FilterNodeDev {
+  uint32_t kind;   // SLG_FILTER_*
+  uint32_t arity;  // AND / OR
+  uint32_t row;    // a leaf's row of the column table, or of the filter table (FILTER_ID)
+  uint32_t bits;   // KEYWORD_IN: first word of the node's ordinal bit set (ceil(n_ords / 32) words)
+  double lo, hi;   // RANGE_F64 as given; RANGE_I64 clamped into +-2^53 (or the infinity: nothing passes)
+};
+constexpr uint32_t kFilterMaxNodes = 64, kFilterMaxDepth = 16, kFilterMaxTrees = 64;  // = SLG_MAX_FILTER_*
+constexpr uint32_t kFilterKeywordIn = 0, kFilterRangeF64 = 1, kFilterRangeI64 = 2, kFilterId = 3, kFilterAnd = 4,
+                   kFilterOr = 5, kFilterNot = 6;
+
 // ---- merge of per-shard results gathered over RCCL (merge_shards_kernel, slg_kernels.hpp) ----------
 struct ShardMergeParams {
   const uint32_t *doc;    // shard sh's rows start at doc + sh * arr_stride ([nq*k] each)

@@ -35,6 +35,12 @@ std::vector<slgplan::FscoreFieldView> slghost::fscore_field_views(const IndexSta
     v.id = kv.first;
     v.keyword = kv.second->kind == 2;
     v.non_finite = kv.second->non_finite;
+    v.n_ords = kv.second->n_ords;
+    v.from_i64 = kv.second->from_i64;
+    v.i64_rounded = kv.second->i64_rounded;
+    v.any_value = kv.second->any_value;
+    v.vmin = kv.second->vmin;
+    v.vmax = kv.second->vmax;
     v.per_seg.assign(S.segs.size(), slg::FscoreColDev{nullptr, nullptr});
     for (size_t s = 0; s < S.segs.size() && s < kv.second->per_seg.size(); s++)
       if (const auto &c = kv.second->per_seg[s])

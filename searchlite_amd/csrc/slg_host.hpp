@@ -354,6 +354,9 @@ struct AggFieldData {
   uint32_t n_ords = 0;
   bool any_value = false, non_finite = false;
   double vmin = 0.0, vmax = 0.0;  // over the finite values, when any_value
+  // the numeric column came from slg_index_add_agg_field_i64 (a RANGE_I64 filter leaf asks for it); some value of
+  // it lay beyond +-2^53 and was rounded by `as f64`
+  bool from_i64 = false, i64_rounded = false;
   std::vector<std::shared_ptr<AggColumn>> per_seg;
 };
 

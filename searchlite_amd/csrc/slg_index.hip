@@ -1,5 +1,5 @@
 // slg_index.hip — the index: creation and destruction, tuning, segment staging, the immutable states and
-// their updates (filters, sort fields, vector fields, tombstones, segments), profiling switches.
+// their updates (filters, filter trees, sort fields, vector fields, tombstones, segments), profiling switches.
 //
 // The host units (this one, slg_batch.hip, slg_shard.hip, slg_rerank.hip, slg_vsearch.hip; what they
 // share: slg_host.hpp) are the host side of the C ABI declared in include/searchlite_gpu.h.  They
@@ -13,6 +13,7 @@
 #include <cmath>
 #include <cstdlib>
 
+#include "slg_filter.hpp"
 #include "slg_stage.hpp"
 
 slghost::LastError &slghost::last_error() {
@@ -699,6 +700,95 @@ int slg_index_remove_filter(slg_index *ix, int filter_id) {
   });
 }
 
+// ---- filter trees built on the device (slg_filter.hpp; the checks and the image: slg_plan.cpp) ----
+int slg_index_add_filter_trees(slg_index *ix, const slg_filter_tree *trees, uint32_t n_trees, int32_t *out_ids) {
+  return guarded([&] {
+    slgplan::check_filter_trees(trees, n_trees);  // (host only, before the index is looked at)
+    SLG_REQUIRE(out_ids != nullptr, "out_ids is NULL");
+    SLG_REQUIRE(ix != nullptr, "index is NULL");
+    std::vector<int32_t> ids(n_trees, -1);  // (handed out only once the state is published: all or nothing)
+    update_state(ix, false, [&](const IndexState &cur, IndexState &ns) {
+      hipStream_t st = ix->stream;
+      const size_t n_segs = cur.segs.size();
+      std::vector<char> live(cur.filters.size());
+      for (size_t f = 0; f < live.size(); f++) live[f] = cur.filter_usable(f) ? 1 : 0;
+      slgplan::FilterTreePlan fp;
+      slgplan::plan_filter_trees(fscore_field_views(cur), cur.reject_host.data(), live.data(), live.size(),
+                                 (uint32_t)n_segs, trees, n_trees, fp);
+      // the new filters' bitmaps, and their addresses as the image's last table
+      std::vector<std::shared_ptr<FilterData>> made(n_trees);
+      std::vector<uint32_t *> outs((size_t)n_trees * n_segs);
+      for (uint32_t t = 0; t < n_trees; t++) {
+        made[t] = std::make_shared<FilterData>();
+        made[t]->per_seg.resize(n_segs);
+        for (size_t s = 0; s < n_segs; s++) {
+          const size_t words = ((size_t)cur.segs[s]->n_docs + 31) / 32;
+          made[t]->per_seg[s] = std::make_shared<DevBuf>();
+          made[t]->per_seg[s]->alloc((words ? words : 1) * 4, &ix->pool);
+          outs[(size_t)t * n_segs + s] = made[t]->per_seg[s]->as<uint32_t>();
+        }
+      }
+      DevBuf image;  // one pooled upload (freed on return: the stream is synchronised below)
+      upload_image(image, &ix->pool, {image_part(fp.trees), image_part(fp.nodes), image_part(fp.cols),
+                                      image_part(fp.filters), image_part(outs), image_part(fp.words)});
+      slg::FilterTreeParams p{};
+      unsigned char *base = image.as<unsigned char>();
+      p.trees = reinterpret_cast<const slg::FilterTreeDev *>(base);
+      base += fp.trees.size() * sizeof(slg::FilterTreeDev);
+      p.nodes = reinterpret_cast<const slg::FilterNodeDev *>(base);
+      base += fp.nodes.size() * sizeof(slg::FilterNodeDev);
+      p.cols = reinterpret_cast<const slg::FscoreColDev *>(base);
+      base += fp.cols.size() * sizeof(slg::FscoreColDev);
+      p.filters = reinterpret_cast<const uint32_t *const *>(base);
+      base += fp.filters.size() * sizeof(void *);
+      p.out = reinterpret_cast<uint32_t *const *>(base);
+      base += outs.size() * sizeof(void *);
+      p.words = reinterpret_cast<const uint32_t *>(base);
+      p.n_segs = (uint32_t)n_segs;
+      for (size_t s = 0; s < n_segs; s++) {
+        const SegHost &sh = *cur.segs[s];
+        if (sh.n_docs == 0) continue;
+        p.deleted = sh.d_deleted.as<uint32_t>();
+        p.n_docs = sh.n_docs;
+        p.seg = (uint32_t)s;
+        hipLaunchKernelGGL(slg::filter_tree_kernel, dim3((sh.n_docs + slg::kFilterThreads - 1) / slg::kFilterThreads, n_trees),
+                           dim3(slg::kFilterThreads), 0, st, p);
+        SLG_HIP(hipGetLastError());
+      }
+      SLG_HIP(hipStreamSynchronize(st));
+      // every filter takes the lowest free id, in the order of the trees (add_filter_impl's policy)
+      size_t slot = 0;
+      for (uint32_t t = 0; t < n_trees; t++) {
+        while (slot < ns.filters.size() && ns.filters[slot]) slot++;
+        if (slot == ns.filters.size()) ns.filters.emplace_back();
+        ns.filters[slot] = std::move(made[t]);
+        ids[t] = (int32_t)slot;
+      }
+    });
+    std::copy(ids.begin(), ids.end(), out_ids);
+  });
+}
+
+int slg_index_fetch_filter(slg_index *ix, int filter_id, uint32_t seg, uint8_t *out_pass) {
+  return guarded([&] {
+    SLG_REQUIRE(ix != nullptr, "index is NULL");
+    SLG_REQUIRE(out_pass != nullptr, "out_pass is NULL");
+    const auto st = ix->snapshot();
+    SLG_REQUIRE(filter_id >= 0 && (size_t)filter_id < st->filters.size() && st->filters[filter_id], "unknown filter id");
+    SLG_REQUIRE(seg < st->segs.size(), "no such segment");
+    const FilterData &fd = *st->filters[filter_id];
+    SLG_REQUIRE(seg < fd.per_seg.size() && fd.per_seg[seg], "the filter has no bitmap for this segment (added after it was registered)");
+    const uint32_t n_docs = st->segs[seg]->n_docs;
+    const size_t words = ((size_t)n_docs + 31) / 32;
+    if (words == 0) return;
+    DeviceGuard g(ix->device);
+    std::vector<uint32_t> w(words);
+    SLG_HIP(hipMemcpy(w.data(), fd.per_seg[seg]->p, words * 4, hipMemcpyDeviceToHost));
+    for (auto &x : w) x = ~x;  // (bits past n_docs are set in the reject bitmap: clear here)
+    std::memcpy(out_pass, w.data(), ((size_t)n_docs + 7) / 8);
+  });
+}
+
 // ---- sort fields (query/sort.rs:300-345) ---------------------------------------------------
 namespace {
 int add_sort_field_impl(slg_index *ix, int kind, const uint32_t *const *seg_offsets, const void *const *seg_values) {
@@ -799,6 +889,7 @@ int add_agg_field_impl(slg_index *ix, int kind, const uint32_t *const *seg_offse
       auto fd = std::make_shared<AggFieldData>();
       fd->kind = kind == 3 ? 2 : 1;
       fd->n_ords = n_ords;
+      fd->from_i64 = kind == 2;
       fd->per_seg.resize(n_segs);
       for (size_t s = 0; s < n_segs; s++) {
         const uint32_t n_docs = cur.segs[s]->n_docs;
@@ -827,7 +918,11 @@ int add_agg_field_impl(slg_index *ix, int kind, const uint32_t *const *seg_offse
           if (nv && kind == 2) {  // fastfields.rs:772-800: i64 values reach the collectors `as f64`
             const int64_t *iv = static_cast<const int64_t *>(seg_values[s]) + first;
             conv.resize(nv);
-            for (size_t i = 0; i < nv; i++) conv[i] = (double)iv[i];
+            constexpr int64_t i2p53 = (int64_t)1 << 53;
+            for (size_t i = 0; i < nv; i++) {
+              conv[i] = (double)iv[i];
+              fd->i64_rounded = fd->i64_rounded || iv[i] > i2p53 || iv[i] < -i2p53;
+            }
             v = conv.data();
           } else if (nv) {
             v = static_cast<const double *>(seg_values[s]) + first;

@@ -1377,6 +1377,134 @@ void plan_fscore(const std::vector<FscoreFieldView> &fields, const uint32_t *con
     for (uint32_t s = 0; s < n_segs; s++) out.filters.push_back(reject[(size_t)f * n_segs + s]);
 }
 
+// ---- filter trees --------------------------------------------------------------------------------------
+static_assert(slg::kFilterMaxNodes == SLG_MAX_FILTER_NODES && slg::kFilterMaxDepth == SLG_MAX_FILTER_DEPTH &&
+                  slg::kFilterMaxTrees == SLG_MAX_FILTER_TREES, "the kernel's limits and the ABI's");
+static_assert(slg::kFilterKeywordIn == SLG_FILTER_KEYWORD_IN && slg::kFilterRangeF64 == SLG_FILTER_RANGE_F64 &&
+                  slg::kFilterRangeI64 == SLG_FILTER_RANGE_I64 && slg::kFilterId == SLG_FILTER_ID &&
+                  slg::kFilterAnd == SLG_FILTER_AND && slg::kFilterOr == SLG_FILTER_OR &&
+                  slg::kFilterNot == SLG_FILTER_NOT, "header kinds");
+static_assert(sizeof(slg::FilterTreeDev) == 8 && sizeof(slg::FilterNodeDev) == 32, "records the kernel reads in whole words");
+
+void check_filter_trees(const slg_filter_tree *trees, uint32_t n_trees) {
+  PLAN_REQUIRE(trees != nullptr, "filter trees is NULL");
+  PLAN_REQUIRE(n_trees != 0u, "n_trees is 0");
+  std::string unsupported;  // (reported behind every invalid argument)
+  for (uint32_t t = 0; t < n_trees; t++) {
+    const slg_filter_tree &tr = trees[t];
+    const std::string in_t = " in filter tree " + std::to_string(t);
+    PLAN_REQUIRE(tr.n_nodes != 0u, "n_nodes is 0" + in_t);
+    PLAN_REQUIRE(tr.nodes != nullptr, "nodes is NULL" + in_t);
+    PLAN_REQUIRE(tr.n_ords == 0u || tr.ords != nullptr, "ords is NULL" + in_t);
+    uint64_t depth = 0, deepest = 0;  // the evaluation stack of the postfix program
+    for (uint32_t i = 0; i < tr.n_nodes; i++) {
+      const slg_filter_node &n = tr.nodes[i];
+      const std::string at = " (node " + std::to_string(i) + ")" + in_t;
+      PLAN_REQUIRE(n.kind >= SLG_FILTER_KEYWORD_IN && n.kind <= SLG_FILTER_NOT, "unknown filter node kind" + at);
+      if (n.kind == SLG_FILTER_NOT) {
+        PLAN_REQUIRE(depth >= 1u, "NOT underflows the stack" + at);
+      } else if (n.kind == SLG_FILTER_AND || n.kind == SLG_FILTER_OR) {
+        PLAN_REQUIRE((uint64_t)n.arity <= depth, "arity larger than the stack" + at);
+        depth = depth - n.arity + 1u;
+      } else {
+        if (n.kind == SLG_FILTER_RANGE_F64)
+          PLAN_REQUIRE(!std::isnan(n.lo_f) && !std::isnan(n.hi_f), "NaN bound" + at);
+        if (n.kind == SLG_FILTER_KEYWORD_IN)
+          PLAN_REQUIRE((uint64_t)n.ord_begin + n.n_ords_in <= tr.n_ords, "ord_begin + n_ords_in > n_ords" + at);
+        depth++;
+      }
+      deepest = std::max(deepest, depth);
+    }
+    PLAN_REQUIRE(depth == 1u, "the program does not end with exactly one value" + in_t);
+    if (unsupported.empty() && tr.n_nodes > SLG_MAX_FILTER_NODES)
+      unsupported = "more than SLG_MAX_FILTER_NODES nodes" + in_t;
+    if (unsupported.empty() && deepest > SLG_MAX_FILTER_DEPTH)
+      unsupported = "evaluation stack deeper than SLG_MAX_FILTER_DEPTH" + in_t;
+  }
+  if (unsupported.empty() && n_trees > SLG_MAX_FILTER_TREES) unsupported = "more than SLG_MAX_FILTER_TREES trees in one call";
+  if (!unsupported.empty()) throw SlgError(SLG_ERR_UNSUPPORTED, unsupported);
+}
+
+void plan_filter_trees(const std::vector<FscoreFieldView> &fields, const uint32_t *const *reject,
+                       const char *filter_live, size_t n_filters, uint32_t n_segs, const slg_filter_tree *trees,
+                       uint32_t n_trees, FilterTreePlan &out) {
+  out = FilterTreePlan{};
+  out.trees.reserve(n_trees);
+  std::vector<int32_t> used_fields, used_filters;  // the rows of the two tables, in order of first use
+  std::string unsupported;                         // (reported behind every invalid argument)
+  auto row_of = [](std::vector<int32_t> &rows, int32_t id) {
+    const auto it = std::find(rows.begin(), rows.end(), id);
+    if (it != rows.end()) return (uint32_t)(it - rows.begin());
+    rows.push_back(id);
+    return (uint32_t)rows.size() - 1u;
+  };
+  constexpr double k2p53 = 9007199254740992.0;
+  constexpr int64_t i2p53 = (int64_t)1 << 53;
+  for (uint32_t t = 0; t < n_trees; t++) {
+    const slg_filter_tree &tr = trees[t];
+    const std::string in_t = " in filter tree " + std::to_string(t);
+    out.trees.push_back(slg::FilterTreeDev{(uint32_t)out.nodes.size(), tr.n_nodes});
+    for (uint32_t i = 0; i < tr.n_nodes; i++) {
+      const slg_filter_node &n = tr.nodes[i];
+      slg::FilterNodeDev nd{};
+      nd.kind = (uint32_t)n.kind;
+      if (n.kind == SLG_FILTER_AND || n.kind == SLG_FILTER_OR) {
+        nd.arity = n.arity;
+      } else if (n.kind == SLG_FILTER_ID) {
+        const int32_t f = n.filter_id;
+        PLAN_REQUIRE(f >= 0 && (size_t)f < n_filters && filter_live[f],
+                     "unknown filter id " + std::to_string(f) + " (or one without a bitmap for every segment)" + in_t);
+        nd.row = row_of(used_filters, f);
+      } else if (n.kind != SLG_FILTER_NOT) {
+        const int32_t id = n.field;
+        const auto it = std::find_if(fields.begin(), fields.end(), [id](const FscoreFieldView &v) { return v.id == id; });
+        PLAN_REQUIRE(it != fields.end(), "unknown agg field id " + std::to_string(id) + in_t);
+        for (uint32_t s = 0; s < n_segs; s++)
+          PLAN_REQUIRE(s < it->per_seg.size() && it->per_seg[s].vals != nullptr,
+                       "agg field " + std::to_string(id) + " has no column for segment " + std::to_string(s) +
+                           " (added after the field was registered)" + in_t);
+        nd.row = row_of(used_fields, id);
+        if (n.kind == SLG_FILTER_KEYWORD_IN) {
+          PLAN_REQUIRE(it->keyword, "agg field " + std::to_string(id) + " is not a keyword field" + in_t);
+          nd.bits = (uint32_t)out.words.size();
+          out.words.resize(out.words.size() + ((size_t)it->n_ords + 31u) / 32u, 0u);
+          for (uint32_t j = 0; j < n.n_ords_in; j++) {
+            const uint32_t o = tr.ords[n.ord_begin + j];
+            PLAN_REQUIRE(o < it->n_ords, "ordinal " + std::to_string(o) + " >= n_ords of agg field " +
+                                             std::to_string(id) + in_t);
+            out.words[nd.bits + (o >> 5)] |= 1u << (o & 31u);
+          }
+        } else {
+          PLAN_REQUIRE(!it->keyword, "agg field " + std::to_string(id) + " is a keyword field" + in_t);
+          if (n.kind == SLG_FILTER_RANGE_F64) {
+            nd.lo = n.lo_f;
+            nd.hi = n.hi_f;
+          } else {
+            PLAN_REQUIRE(it->from_i64, "agg field " + std::to_string(id) + " was not registered from i64 values" + in_t);
+            if (unsupported.empty() && (it->i64_rounded || (it->any_value && (it->vmin < -k2p53 || it->vmax > k2p53))))
+              unsupported = "agg field " + std::to_string(id) + " holds an i64 value beyond +-2^53 (CPU path)" + in_t;
+            // every stored value is an integer within +-2^53: a bound on the far side of it selects what the
+            // clamped one does; a lower bound above 2^53 (an upper one below -2^53) selects nothing, which the
+            // clamped bound would not say of a value of exactly +-2^53, so it becomes the infinity
+            nd.lo = n.lo_i > i2p53 ? HUGE_VAL : (double)std::max<int64_t>(n.lo_i, -i2p53);
+            nd.hi = n.hi_i < -i2p53 ? -HUGE_VAL : (double)std::min<int64_t>(n.hi_i, i2p53);
+          }
+        }
+      }
+      out.nodes.push_back(nd);
+    }
+  }
+  if (!unsupported.empty()) throw SlgError(SLG_ERR_UNSUPPORTED, unsupported);
+  out.cols.reserve(used_fields.size() * n_segs);
+  for (const int32_t id : used_fields) {
+    const auto it = std::find_if(fields.begin(), fields.end(), [id](const FscoreFieldView &v) { return v.id == id; });
+    out.cols.insert(out.cols.end(), it->per_seg.begin(), it->per_seg.begin() + n_segs);
+  }
+  out.filters.reserve(used_filters.size() * n_segs);
+  for (const int32_t f : used_filters)
+    for (uint32_t s = 0; s < n_segs; s++) out.filters.push_back(reject[(size_t)f * n_segs + s]);
+}
+
 // ---- sort keys of numeric fast fields ----------------------------------------------------------
 namespace {
 inline uint64_t i64_key(int64_t v) { return (uint64_t)v ^ 0x8000000000000000ull; }

@@ -180,6 +180,12 @@ struct FscoreFieldView {
   int32_t id = 0;
   bool keyword = false, non_finite = false;
   std::vector<slg::FscoreColDev> per_seg;  // [n_segs]
+  // what only plan_filter_trees reads: the keyword dictionary's size; whether the numeric column was registered
+  // from i64 values, the finite minimum and maximum recorded then (when any_value), and whether an i64 value beyond
+  // +-2^53 was seen (2^53 + 1 is stored as 2^53: the minimum and maximum alone do not show it)
+  uint32_t n_ords = 0;
+  bool from_i64 = false, any_value = false, i64_rounded = false;
+  double vmin = 0.0, vmax = 0.0;
 };
 // The tables of a checked spec against an index state's fields and filters.  reject: the state's flattened
 // [filter * n_segs + seg] reject bitmaps (device addresses), filter_live [n_filters] as BatchIn's.  Throws
@@ -195,6 +201,28 @@ struct FscorePlan {
 };
 void plan_fscore(const std::vector<FscoreFieldView> &fields, const uint32_t *const *reject, const char *filter_live,
                  size_t n_filters, uint32_t n_segs, uint32_t nq, const slg_fscore_spec &spec, FscorePlan &out);
+
+// ---- filter trees (slg_index_add_filter_trees) ----
+// The checks of the trees that need no index (throws SlgError).  SLG_ERR_INVALID, reported first: NULL arrays,
+// n_trees == 0, n_nodes == 0, an unknown kind, a program that underflows the stack or does not end with exactly
+// one value, an arity larger than the stack, a NaN bound, ord_begin + n_ords_in > n_ords.  Then
+// SLG_ERR_UNSUPPORTED: more than SLG_MAX_FILTER_NODES nodes, a stack deeper than SLG_MAX_FILTER_DEPTH, more than
+// SLG_MAX_FILTER_TREES trees.
+void check_filter_trees(const slg_filter_tree *trees, uint32_t n_trees);
+// The device image of checked trees against an index state's fields and filters (reject, filter_live, n_filters
+// as plan_fscore's; a filter without a bitmap for some segment has nullptr there).  Throws SLG_ERR_INVALID for an
+// unknown field or filter id, a field or filter without data for every segment, the wrong column kind, an ordinal
+// >= the field's n_ords; behind those SLG_ERR_UNSUPPORTED for an i64 column beyond +-2^53.
+struct FilterTreePlan {
+  std::vector<slg::FilterTreeDev> trees;   // [n_trees]
+  std::vector<slg::FilterNodeDev> nodes;   // every tree's nodes, in its order
+  std::vector<slg::FscoreColDev> cols;     // [fields the trees name][n_segs]
+  std::vector<const uint32_t *> filters;   // [filters the trees name][n_segs]
+  std::vector<uint32_t> words;             // one bit set of ceil(n_ords / 32) words per KEYWORD_IN node
+};
+void plan_filter_trees(const std::vector<FscoreFieldView> &fields, const uint32_t *const *reject,
+                       const char *filter_live, size_t n_filters, uint32_t n_segs, const slg_filter_tree *trees,
+                       uint32_t n_trees, FilterTreePlan &out);
 
 // Throws SlgError (SLG_ERR_INVALID / SLG_ERR_UNSUPPORTED) on malformed input.
 void plan_batch(const std::vector<SegView> &segs, const slg_tuning &tune, const BatchIn &in, Plan &out);

@@ -307,6 +307,74 @@ int slgp_plan_fscore(const slgp_fscore_field *fields, uint32_t n_fields, const c
   }
 }
 
+// the host side of slg_index_add_filter_trees: check_filter_trees, then plan_filter_trees against registered fields
+// and filters that exist as descriptions only (columns and reject bitmaps: the addresses slgp_plan_fscore makes
+// up; a filter with filter_live 0 has none).  tree_rows: n_trees x 2 words (slg::FilterTreeDev); nodes: entries of
+// 8 words (slg::FilterNodeDev); cols: entries of two addresses (offsets, values); filters: addresses; words: the
+// ordinal bit sets.  Each table is filled when it fits its cap; counts: entries of nodes, cols, filters, words.
+// 0, or a negative error code (err filled)
+struct slgp_filter_field {
+  int32_t id;
+  uint32_t keyword, n_ords, from_i64, any_value;
+  double vmin, vmax;
+  const uint8_t *seg_has, *seg_dense;
+};
+int slgp_plan_filter_trees(const slgp_filter_field *fields, uint32_t n_fields, const char *filter_live,
+                           uint32_t n_filters, uint32_t n_segs, const slg_filter_tree *trees, uint32_t n_trees,
+                           uint32_t *tree_rows, uint32_t *nodes, uint32_t nodes_cap, uint64_t *cols, uint32_t cols_cap,
+                           uint64_t *filters, uint32_t filters_cap, uint32_t *words, uint32_t words_cap,
+                           uint32_t *counts, char *err, uint32_t err_len) {
+  try {
+    slgplan::check_filter_trees(trees, n_trees);
+    std::vector<slgplan::FscoreFieldView> views(n_fields);
+    for (uint32_t i = 0; i < n_fields; i++) {
+      views[i].id = fields[i].id;
+      views[i].keyword = fields[i].keyword != 0;
+      views[i].n_ords = fields[i].n_ords;
+      views[i].from_i64 = fields[i].from_i64 != 0;
+      views[i].any_value = fields[i].any_value != 0;
+      views[i].vmin = fields[i].vmin;
+      views[i].vmax = fields[i].vmax;
+      views[i].per_seg.assign(n_segs, slg::FscoreColDev{nullptr, nullptr});
+      for (uint32_t s = 0; s < n_segs; s++) {
+        if (!fields[i].seg_has[s]) continue;
+        const uint64_t a = ((uint64_t)(fields[i].id + 1) << 32) | ((uint64_t)s << 8);
+        views[i].per_seg[s].vals = reinterpret_cast<const double *>((uintptr_t)(a | 1u));
+        if (!fields[i].seg_dense[s]) views[i].per_seg[s].offs = reinterpret_cast<const uint32_t *>((uintptr_t)(a | 2u));
+      }
+    }
+    std::vector<const uint32_t *> reject((size_t)n_filters * n_segs, nullptr);
+    for (uint32_t f = 0; f < n_filters; f++)
+      for (uint32_t s = 0; s < n_segs && filter_live[f]; s++)
+        reject[(size_t)f * n_segs + s] =
+            reinterpret_cast<const uint32_t *>((uintptr_t)(((uint64_t)(f + 1) << 32) | ((uint64_t)s << 8) | 3u));
+    slgplan::FilterTreePlan fp;
+    slgplan::plan_filter_trees(views, reject.data(), filter_live, n_filters, n_segs, trees, n_trees, fp);
+    static_assert(sizeof(slg::FilterTreeDev) == 8 && sizeof(slg::FilterNodeDev) == 32, "the words the caller reads");
+    if (tree_rows) std::memcpy(tree_rows, fp.trees.data(), fp.trees.size() * sizeof(slg::FilterTreeDev));
+    if (nodes && fp.nodes.size() <= nodes_cap) std::memcpy(nodes, fp.nodes.data(), fp.nodes.size() * sizeof(slg::FilterNodeDev));
+    if (cols && fp.cols.size() <= cols_cap && !fp.cols.empty())
+      std::memcpy(cols, fp.cols.data(), fp.cols.size() * sizeof(slg::FscoreColDev));
+    if (filters && fp.filters.size() <= filters_cap && !fp.filters.empty())
+      std::memcpy(filters, fp.filters.data(), fp.filters.size() * sizeof(void *));
+    if (words && fp.words.size() <= words_cap && !fp.words.empty())
+      std::memcpy(words, fp.words.data(), fp.words.size() * 4);
+    if (counts) {
+      counts[0] = (uint32_t)fp.nodes.size();
+      counts[1] = (uint32_t)fp.cols.size();
+      counts[2] = (uint32_t)fp.filters.size();
+      counts[3] = (uint32_t)fp.words.size();
+    }
+    return SLG_OK;
+  } catch (const slgplan::SlgError &e) {
+    if (err && err_len) {
+      std::strncpy(err, e.what(), err_len - 1);
+      err[err_len - 1] = 0;
+    }
+    return e.code;
+  }
+}
+
 // the host checks of slg_index_set_positions over a segment of n_postings postings.  0, or a negative error code
 int slgp_check_positions(uint64_t n_postings, const uint64_t *pos_offsets, const uint32_t *positions, char *err,
                          uint32_t err_len) {

@@ -214,6 +214,30 @@ class GpuIndex:
     def remove_filter(self, filter_id: int) -> None:
         N.check(self._lib.slg_index_remove_filter(self._h, filter_id))
 
+    def add_filter_trees(self, trees) -> List[int]:
+        """Filters built on the device from filter trees over the registered agg fields, all in one update of
+        the index (slg_index_add_filter_trees).  trees: filters.FilterProgram objects (filters.compile_filter) or
+        (nodes, ords) pairs, nodes being dicts of slg_filter_node fields in postfix order.  -> the filter ids,
+        one per tree; on an error none is registered."""
+        from .filters import tree_array
+        trees = list(trees)
+        arr, keep = tree_array(trees)
+        ids = np.full(max(len(trees), 1), -1, dtype=np.int32)
+        N.check(self._lib.slg_index_add_filter_trees(self._h, arr, len(trees), ids.ctypes.data))
+        del keep
+        return [int(i) for i in ids[:len(trees)]]
+
+    def fetch_filter(self, filter_id: int) -> List[np.ndarray]:
+        """The docs that are alive and pass a registered filter of any kind (slg_index_fetch_filter): one
+        boolean array per segment."""
+        out = []
+        for s, seg in enumerate(self.segments):
+            n = int(seg.n_docs)
+            buf = np.zeros(max((n + 7) // 8, 1), dtype=np.uint8)
+            N.check(self._lib.slg_index_fetch_filter(self._h, int(filter_id), s, buf.ctypes.data))
+            out.append(np.unpackbits(buf, bitorder="little")[:n].astype(bool))
+        return out
+
     # -- sort fields (query/sort.rs: `sort` on numeric fast fields) -----------------------------
     def add_sort_field(self, per_segment_values, dtype) -> int:
         """Register a numeric fast field for field-sorted search (slg_index_add_sort_field_i64 / _f64).

@@ -63,6 +63,35 @@ def _clause_scores(oracle, field, qv, bst, live):
     return ents
 
 
+def blend_rows(maps, metrics, clause_field, alpha_q, k_out):
+    """the union of one query's clause lists ({(seg, doc): score} each), compute_hybrid_score at bm25 = 0, sorted:
+    (rows [(seg, doc, final, vec)] of the top k_out, the union size)"""
+    nc = len(maps)
+    old = np.seterr(over="ignore", invalid="ignore")
+    union = set().union(*[m.keys() for m in maps])
+    rows = []
+    for key in union:
+        bsum, vsum = F32(0.0), F32(0.0)
+        for c in range(nc):
+            if key in maps[c]:
+                vs = maps[c][key]
+                vsum = F32(vsum + vs)
+            else:
+                vs = F32(-1.0) if metrics[clause_field[c]] == 0 else F32(np.finfo(F32).min)
+            a = F32(alpha_q[c])
+            if a >= 1:
+                bl = F32(0.0)
+            elif a <= 0:
+                bl = vs
+            else:
+                bl = F32(F32(a * F32(0.0)) + F32(F32(F32(1.0) - a) * vs))
+            bsum = F32(bsum + bl)
+        rows.append((key[0], key[1], F32(bsum / F32(nc)), vsum))
+    rows.sort(key=lambda r: (-_tkey(r[2]), r[0], r[1]))
+    np.seterr(**old)
+    return rows[:k_out], len(union)
+
+
 def reference(oracle, fields, metrics, clause_field, qvecs, alpha, boost, cand, k_out, live=None):
     """Per query: rows [(seg, doc, final, vec)] of the top k_out, the union size, the clause lists."""
     nq, nc = alpha.shape
@@ -76,27 +105,8 @@ def reference(oracle, fields, metrics, clause_field, qvecs, alpha, boost, cand, 
         for c, f in enumerate(clause_field):
             ents = _clause_scores(oracle, fields[f], qvecs[q, offs[c]:offs[c + 1]], boost[q, c], lv)[:cand]
             maps.append({(s, d): v for v, s, d in ents})
-        union = set().union(*[m.keys() for m in maps])
-        rows = []
-        for key in union:
-            bsum, vsum = F32(0.0), F32(0.0)
-            for c in range(nc):
-                if key in maps[c]:
-                    vs = maps[c][key]
-                    vsum = F32(vsum + vs)
-                else:
-                    vs = F32(-1.0) if metrics[clause_field[c]] == 0 else F32(np.finfo(F32).min)
-                a = F32(alpha[q, c])
-                if a >= 1:
-                    bl = F32(0.0)
-                elif a <= 0:
-                    bl = vs
-                else:
-                    bl = F32(F32(a * F32(0.0)) + F32(F32(F32(1.0) - a) * vs))
-                bsum = F32(bsum + bl)
-            rows.append((key[0], key[1], F32(bsum / F32(nc)), vsum))
-        rows.sort(key=lambda r: (-_tkey(r[2]), r[0], r[1]))
-        out.append((rows[:k_out], len(union), maps))
+        rows, total = blend_rows(maps, metrics, clause_field, alpha[q], k_out)
+        out.append((rows, total, maps))
     np.seterr(**old)
     return out
 
@@ -117,7 +127,8 @@ def _close(a, b, tol=TOL):
     return a == b or abs(float(a) - float(b)) <= tol
 
 
-def check(got, want, k_out, what, exact_order=False):
+def check(got, want, k_out, what, exact_order=False, vec_tol=TOL):
+    """vec_tol: the bound on the summed vector score (TOL unless a caller states why its sums need more)"""
     doc, seg, score, vec, count, total = got
     for q, (rows, tot, _) in enumerate(want):
         assert int(total[q]) == tot, f"{what} q{q}: total {total[q]} != {tot}"
@@ -132,7 +143,7 @@ def check(got, want, k_out, what, exact_order=False):
             elif key != (rows[i][0], rows[i][1]):
                 assert key in wmap and _close(wmap[key][2], rows[i][2], 2 * TOL), f"{what} q{q} row {i}: order"
             if key in wmap:
-                assert _close(vec[q, i], wmap[key][3]), f"{what} q{q} row {i}: vec {vec[q, i]} != {wmap[key][3]}"
+                assert _close(vec[q, i], wmap[key][3], vec_tol), f"{what} q{q} row {i}: vec {vec[q, i]} != {wmap[key][3]}"
         assert np.all(doc[q, n:] == 0) and np.all(score[q, n:] == 0)
 
 

@@ -33,7 +33,10 @@
  * cursor, hybrid, aggregation, rescore, sharded or coalesced batches.  Phrase queries
  * (slg_index_set_positions, slg_batch_prepare_phrase): phrase groups with a slop and per-field variants beside
  * the term groups of a bool batch, under the same limits; one term per phrase position (no position
- * alternatives), not in rescore queries.
+ * alternatives), not in rescore queries.  Field collapsing (slg_batch_prepare_collapse): one hit per ordinal of a
+ * keyword column over the k <= SLG_MAX_COLLAPSE_ROWS rows of a plain, sorted or cursor batch, with up to
+ * SLG_MAX_INNER_HITS inner hits per group; not with aggregations, rescore, bool, phrase, function_score, hybrid or
+ * vector-only batches, sharded or coalesced.
  */
 #ifndef SEARCHLITE_GPU_H
 #define SEARCHLITE_GPU_H
@@ -1362,6 +1365,77 @@ int slg_search_batch_fscore(slg_index *index, uint32_t nq, const uint32_t *q_off
                             const slg_fscore_spec *spec, uint32_t k, int strategy, uint32_t *out_doc, uint32_t *out_seg,
                             float *out_score, uint32_t *out_count, slg_stats *stats_or_null,
                             uint64_t *out_matched_or_null);
+
+/* ---- field collapsing (SearchRequest::collapse, api/reader.rs:2826-2835, 3499-3595) --------------------
+ * The reference collapses the top_k = candidate_size + 1 hits it already holds, in their SortKey order
+ * (collapse_hits): a hit without a value of the collapse field is dropped (it is in no group and nobody's
+ * inner hit), a hit with more than one value fails the request, every other hit joins the group of its value;
+ * groups are ordered by first appearance, a group's first hit is its representative and the rest are its
+ * members; total_groups counts the groups over those hits, the caller truncates the representatives to
+ * `limit` and takes next_cursor from the limit-th.  With inner_hits the members (never the representative)
+ * are put in the inner sort's order when that differs from the request's — a full SortKey, so ties after all
+ * parts go to segment asc, doc asc — then the first `from` are dropped and at most `size` kept.
+ *
+ * A collapse batch is slg_batch_prepare_plans (sort_or_null == NULL and q_cursor_or_null == NULL),
+ * slg_batch_prepare_sorted (a sort) or slg_batch_prepare_after (a cursor) with one collapse spec for the
+ * whole batch; its rows (slg_batch_fetch, slg_batch_device_results) are bit-identical to the same batch
+ * without the spec.  One more kernel behind the batch's last one collapses each query's rows on the device
+ * into side arrays that slg_batch_fetch_collapse copies out; running the batch again computes them again.
+ * The group keys are the global ordinals of a keyword column (slg_index_add_agg_field_ord).
+ *
+ * Per query q with n = out_count[q] rows: total_groups[q] = groups over the n rows; n_groups[q] =
+ * min(total_groups[q], group_limit); for g < n_groups[q] (arrays [nq x group_limit]): group_row = the
+ * representative's index among the query's rows, group_doc / group_seg / group_score = that row, group_ord =
+ * its ordinal, group_size = rows of the group, the representative included, inner_count = kept members =
+ * min(inner_size, max(0, group_size - 1 - inner_from)); inner_row / inner_doc / inner_seg / inner_score
+ * ([nq x group_limit x inner_size]) = the kept members in inner order, inner_row indexing the query's rows.
+ * status[q] = 1 if one of the n rows has more than one value in the column (the caller fails that request,
+ * as the reference does), else 0.  Everything past a count is zero; for a query with status 1 every other
+ * output is zero.  Every output pointer may be NULL.
+ *
+ * inner_sort: NULL = the batch's own order (members stay in row order); else up to SLG_MAX_SORT_PARTS parts
+ * as in slg_sort_spec (n_parts == 0 = `_score` desc, what the reference resolves an empty inner sort to,
+ * query/sort.rs:159-167).  A `_score` part reads the row's score: 0.0 in a field sort without a `_score`
+ * part (ScoreMode::MatchOnly, api/reader.rs:2936-2940).
+ *
+ * Checked before any device work.  SLG_ERR_INVALID: collapse NULL; group_limit == 0 or > k; an inner sort
+ * part with an unknown order or a negative field other than SLG_SORT_SCORE; against the index: an unknown
+ * field id, a numeric agg field, a field without a column for every segment, an unknown inner sort field.
+ * SLG_ERR_UNSUPPORTED (CPU path): k > SLG_MAX_COLLAPSE_ROWS; inner_size > 0 and inner_from + inner_size >
+ * SLG_MAX_INNER_HITS; more than SLG_MAX_SORT_PARTS inner parts.  slg_batch_fetch_collapse on another kind
+ * of batch or before the batch has run: SLG_ERR_INVALID.  NOT BUILT: collapse together with aggregations,
+ * rescore, bool, phrase, function_score, hybrid or vector-only batches, in the coalescer or sharded
+ * (slg_batch_run_sharded* and slg_batch_fetch_sharded refuse a collapse batch: SLG_ERR_UNSUPPORTED);
+ * k > SLG_MAX_COLLAPSE_ROWS; inner_hits beyond SLG_MAX_INNER_HITS (an unlimited inner size included). */
+#define SLG_MAX_COLLAPSE_ROWS 4096u /* k of a collapse batch: the rows of a query are collapsed in LDS */
+#define SLG_MAX_INNER_HITS 64u      /* inner_from + inner_size: one member per lane of a wave */
+typedef struct slg_collapse_spec {
+  int32_t field;        /* id of a KEYWORD column (slg_index_add_agg_field_ord): global ordinals = group keys */
+  uint32_t group_limit; /* groups reported per query (the request's limit), 1 .. k */
+  uint32_t inner_from;
+  uint32_t inner_size;  /* 0 = no inner hits */
+  const slg_sort_spec *inner_sort; /* NULL: the batch's own order */
+} slg_collapse_spec;
+slg_batch *slg_batch_prepare_collapse(slg_index *index, uint32_t nq, const uint32_t *q_offsets,
+                                      const uint32_t *q_term_ids, const float *q_weights,
+                                      const slg_score_plans *plans_or_null, const int32_t *q_filter_or_null,
+                                      const slg_sort_spec *sort_or_null, const slg_sort_cursor *q_cursor_or_null,
+                                      const slg_collapse_spec *collapse, uint32_t k, int strategy);
+/* The collapse arrays of the batch's last run; waits for the batch. */
+int slg_batch_fetch_collapse(slg_batch *batch, uint32_t *n_groups, uint32_t *total_groups, uint32_t *status,
+                             uint32_t *group_row, uint32_t *group_ord, uint32_t *group_size, uint32_t *group_doc,
+                             uint32_t *group_seg, float *group_score, uint32_t *inner_count, uint32_t *inner_row,
+                             uint32_t *inner_doc, uint32_t *inner_seg, float *inner_score);
+/* One-call form with host arrays: the rows as slg_batch_fetch, then the arrays of slg_batch_fetch_collapse. */
+int slg_search_batch_collapse(slg_index *index, uint32_t nq, const uint32_t *q_offsets, const uint32_t *q_term_ids,
+                              const float *q_weights, const slg_score_plans *plans_or_null,
+                              const int32_t *q_filter_or_null, const slg_sort_spec *sort_or_null,
+                              const slg_sort_cursor *q_cursor_or_null, const slg_collapse_spec *collapse, uint32_t k,
+                              int strategy, uint32_t *out_doc, uint32_t *out_seg, float *out_score,
+                              uint32_t *out_count, uint32_t *n_groups, uint32_t *total_groups, uint32_t *status,
+                              uint32_t *group_row, uint32_t *group_ord, uint32_t *group_size, uint32_t *group_doc,
+                              uint32_t *group_seg, float *group_score, uint32_t *inner_count, uint32_t *inner_row,
+                              uint32_t *inner_doc, uint32_t *inner_seg, float *inner_score);
 
 #ifdef __cplusplus
 }

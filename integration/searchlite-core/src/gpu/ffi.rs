@@ -99,6 +99,12 @@ pub const SLG_AGG_STATS: i32 = 3;
     pub q_plan: *const i32, pub q_tie: *const c_float, pub q_nleaves: *const u32, pub q_min_match: *const u32,
     pub q_window: *const u32, pub q_mode: *const i32,
 }
+// field collapsing (SearchRequest::collapse): the keyword column whose global ordinals are the group keys, the
+// groups reported per query, the inner hits' from / size (0: none) and sort (null: the batch's own order)
+#[repr(C)] pub struct slg_collapse_spec {
+    pub field: i32, pub group_limit: u32, pub inner_from: u32, pub inner_size: u32,
+    pub inner_sort: *const slg_sort_spec,
+}
 #[repr(C)] pub struct slg_stats { pub scored_docs: u64, pub candidates_examined: u64, pub postings_advanced: u64 }
 #[repr(C)] pub struct slg_query { pub n_terms: u32, pub term_ids: *const u32, pub weights: *const c_float }
 
@@ -339,7 +345,27 @@ extern "C" {
         sort: *const slg_sort_spec, spec: *const slg_fscore_spec, k: u32, strategy: c_int, out_doc: *mut u32,
         out_seg: *mut u32, out_score: *mut c_float, out_count: *mut u32, stats: *mut slg_stats,
         out_matched: *mut u64) -> c_int;
+    // field collapsing: slg_batch_prepare_plans, _sorted or _after plus the spec; the rows stay as they are, the
+    // groups and inner hits of each query's rows come from slg_batch_fetch_collapse
+    pub fn slg_batch_prepare_collapse(index: *mut slg_index, nq: u32, q_offsets: *const u32, q_term_ids: *const u32,
+        q_weights: *const c_float, plans: *const slg_score_plans, q_filter: *const i32,
+        sort: *const slg_sort_spec, q_cursor: *const slg_sort_cursor, collapse: *const slg_collapse_spec, k: u32,
+        strategy: c_int) -> *mut slg_batch;
+    pub fn slg_batch_fetch_collapse(batch: *mut slg_batch, n_groups: *mut u32, total_groups: *mut u32,
+        status: *mut u32, group_row: *mut u32, group_ord: *mut u32, group_size: *mut u32, group_doc: *mut u32,
+        group_seg: *mut u32, group_score: *mut c_float, inner_count: *mut u32, inner_row: *mut u32,
+        inner_doc: *mut u32, inner_seg: *mut u32, inner_score: *mut c_float) -> c_int;
+    pub fn slg_search_batch_collapse(index: *mut slg_index, nq: u32, q_offsets: *const u32, q_term_ids: *const u32,
+        q_weights: *const c_float, plans: *const slg_score_plans, q_filter: *const i32,
+        sort: *const slg_sort_spec, q_cursor: *const slg_sort_cursor, collapse: *const slg_collapse_spec, k: u32,
+        strategy: c_int, out_doc: *mut u32, out_seg: *mut u32, out_score: *mut c_float, out_count: *mut u32,
+        n_groups: *mut u32, total_groups: *mut u32, status: *mut u32, group_row: *mut u32, group_ord: *mut u32,
+        group_size: *mut u32, group_doc: *mut u32, group_seg: *mut u32, group_score: *mut c_float,
+        inner_count: *mut u32, inner_row: *mut u32, inner_doc: *mut u32, inner_seg: *mut u32,
+        inner_score: *mut c_float) -> c_int;
 }
+pub const SLG_MAX_COLLAPSE_ROWS: u32 = 4096;
+pub const SLG_MAX_INNER_HITS: u32 = 64;
 pub const SLG_MAX_PHRASE_TERMS: u32 = 8;
 pub const SLG_MAX_PHRASE_VARIANTS: u32 = 8;
 pub const SLG_MAX_PHRASE_QUERY_TERMS: u32 = 64;

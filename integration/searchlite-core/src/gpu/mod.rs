@@ -765,7 +765,11 @@ pub(crate) fn gpu_eligible(
     return None;
   }
   if req.collapse.is_some() {
-    return None; // collapse needs every hit of a group, not just the top k
+    // Not routed yet.  collapse_hits (api/reader.rs:2826-2835, 3499-3562) collapses the top_k = candidate_size + 1
+    // hits the request already holds, in SortKey order: slg_batch_prepare_collapse does that on the device over the
+    // batch's own rows (group keys = global ordinals of the keyword column, k = candidate_size + 1,
+    // group_limit = limit, status 1 -> bail, next_cursor from row group_row[limit - 1]); INTEGRATION.md, "Collapse".
+    return None;
   }
   if n_folded_terms == 0 || n_folded_terms > MAX_QUERY_TERMS {
     return None;

@@ -49,6 +49,8 @@ FSCORE_BOOST_MULTIPLY, FSCORE_BOOST_SUM, FSCORE_BOOST_REPLACE, FSCORE_BOOST_MAX,
 FSCORE_HAS_MAX_BOOST, FSCORE_HAS_MIN_SCORE = 1, 2
 FILTER_KEYWORD_IN, FILTER_RANGE_F64, FILTER_RANGE_I64, FILTER_ID, FILTER_AND, FILTER_OR, FILTER_NOT = 0, 1, 2, 3, 4, 5, 6
 MAX_FILTER_NODES, MAX_FILTER_DEPTH, MAX_FILTER_TREES = 64, 16, 64
+MAX_COLLAPSE_ROWS = 4096
+MAX_INNER_HITS = 64
 
 
 class SlgError(RuntimeError):
@@ -169,6 +171,13 @@ class FscoreSpec(C.Structure):
                 ("f_weight", C.c_void_p), ("f_modifier", C.c_void_p), ("f_decay_fn", C.c_void_p),
                 ("f_missing", C.c_void_p), ("f_origin", C.c_void_p), ("f_scale", C.c_void_p),
                 ("f_offset", C.c_void_p), ("f_decay", C.c_void_p)]
+
+
+class CollapseSpec(C.Structure):
+    """slg_collapse_spec: the keyword column whose ordinals are the group keys, the groups reported per query, the
+    inner hits' from / size (size 0: none) and their sort (NULL: the batch's own order)."""
+    _fields_ = [("field", C.c_int32), ("group_limit", C.c_uint32), ("inner_from", C.c_uint32),
+                ("inner_size", C.c_uint32), ("inner_sort", C.c_void_p)]
 
 
 class FilterNode(C.Structure):
@@ -336,6 +345,9 @@ def load():
         "slg_index_add_filter_trees": (i32, [vp, vp, u32, vp]),
         "slg_index_fetch_filter": (i32, [vp, i32, u32, vp]),
         "slg_search_batch_fscore": (i32, [vp, u32, vp, vp, vp, vp, vp, vp, vp, u32, i32, vp, vp, vp, vp, vp, vp]),
+        "slg_batch_prepare_collapse": (vp, [vp, u32, vp, vp, vp, vp, vp, vp, vp, vp, u32, i32]),
+        "slg_batch_fetch_collapse": (i32, [vp] * 15),
+        "slg_search_batch_collapse": (i32, [vp, u32, vp, vp, vp, vp, vp, vp, vp, vp, u32, i32] + [vp] * 18),
     }
     for name, (res, args) in sigs.items():
         if os.environ.get("SLG_LIB_TAG") and not hasattr(L, name):

@@ -125,7 +125,8 @@ void slghost::release_batch_buffers(slg_batch *b, bool to_pool) {
                     &b->d_q_scored, &b->d_q_filter, &b->d_cand, &b->d_slice_cbeg, &b->d_slice_ccnt,
                     &b->d_out, &b->d_stamps, &b->d_blk_skip, &b->d_gather, &b->d_merged, &b->d_q_cand,
                     &b->d_hy_keys, &b->d_hy_work, &b->d_agg_desc, &b->d_agg_counts, &b->d_agg_stats,
-                    &b->d_rs_desc, &b->d_rs_side, &b->d_bool_desc, &b->d_phrase_desc, &b->d_fscore_desc};
+                    &b->d_rs_desc, &b->d_rs_side, &b->d_bool_desc, &b->d_phrase_desc, &b->d_fscore_desc,
+                    &b->d_cl_desc, &b->d_cl_side};
   for (DevBuf *d : bufs) {
     if (!to_pool) d->pool = nullptr;
     d->release();
@@ -178,6 +179,7 @@ slg_batch *slghost::prepare_impl(const PrepareRequest &r) {
     if (r.phrase.on) slgplan::check_phrase(r.boolean.spec, r.phrase.spec, nq, plans);
     else if (r.boolean.on) slgplan::check_bool(r.boolean.spec, nq, plans);
     if (r.fscore.on) slgplan::check_fscore(r.fscore.spec, nq);
+    if (r.collapse.on) slgplan::check_collapse(r.collapse.spec, k);
     SLG_REQUIRE(ix != nullptr, "index is NULL");
     SLG_REQUIRE(!after || q_cursor != nullptr, "q_cursor is NULL");
     if (sort) {  // (checked before planning: the planner never sees a sort spec it cannot run)
@@ -392,6 +394,7 @@ slg_batch *slghost::prepare_impl(const PrepareRequest &r) {
       bool_attach(b, bool_plan);
     }
     if (r.fscore.on) fscore_attach(b, fscore_plan);
+    if (r.collapse.on) collapse_attach(b, *r.collapse.spec, sort);
     {
       std::lock_guard<std::mutex> lk(ix->mu);
       ix->live.push_back(b);
@@ -556,6 +559,7 @@ int slg_batch_run(slg_batch *b) {
     }
     if (b->aggs) agg_launch(b, st);  // (after the select: the tables of every accepted candidate)
     if (b->rescore) rescore_launch(b, st);  // (behind the rows: the first w of every query are scored again)
+    if (b->collapse) collapse_launch(b, st);  // (behind the rows: they are read, never written)
   });
 }
 
@@ -757,6 +761,7 @@ struct HostOut {
   slg_agg_stats *agg_stats = nullptr;
   float *first_score = nullptr, *rescore_score = nullptr;  // (a rescore batch)
   uint32_t *rescored = nullptr;
+  void *const *collapse = nullptr;  // (a collapse batch) the 14 arrays of slg_batch_fetch_collapse, in its order
 };
 // A prepared batch (null: prepare failed and set the thread's error) run to the caller's host arrays and
 // destroyed: the first error is the one reported
@@ -768,6 +773,12 @@ int run_to_host(slg_batch *b, const HostOut &o) {
   if (rc == SLG_OK && b->aggs) rc = slg_batch_fetch_aggs(b, o.agg_counts, o.agg_stats);
   if (rc == SLG_OK && b->rescore) rc = slg_batch_fetch_rescore(b, o.first_score, o.rescore_score, o.rescored);
   if (rc == SLG_OK && o.seen) rc = slg_batch_cursor_seen(b, o.seen);
+  if (rc == SLG_OK && b->collapse) {
+    void *const *c = o.collapse;
+    auto u = [c](int i) { return static_cast<uint32_t *>(c[i]); };
+    rc = slg_batch_fetch_collapse(b, u(0), u(1), u(2), u(3), u(4), u(5), u(6), u(7), static_cast<float *>(c[8]), u(9),
+                                  u(10), u(11), u(12), static_cast<float *>(c[13]));
+  }
   KeepLastError keep;
   slg_batch_destroy(b);
   return rc;
@@ -921,6 +932,35 @@ int slg_search_batch_fscore(slg_index *ix, uint32_t nq, const uint32_t *q_offset
   return run_to_host(slg_batch_prepare_fscore(ix, nq, q_offsets, q_term_ids, q_weights, plans, q_filter, sort, spec, k,
                                               strategy),
                      HostOut{out_doc, out_seg, out_score, out_count, stats, out_matched});
+}
+
+slg_batch *slg_batch_prepare_collapse(slg_index *ix, uint32_t nq, const uint32_t *q_offsets, const uint32_t *q_term_ids,
+                                      const float *q_weights, const slg_score_plans *plans, const int32_t *q_filter,
+                                      const slg_sort_spec *sort, const slg_sort_cursor *q_cursor,
+                                      const slg_collapse_spec *collapse, uint32_t k, int strategy) {
+  PrepareRequest r{ix, nq, q_offsets, q_term_ids, q_weights, plans, q_filter, k, strategy};
+  r.sort = if_given(sort);
+  r.cursor = if_given(q_cursor);
+  r.collapse = {true, collapse};
+  return prepare_impl(r);
+}
+
+int slg_search_batch_collapse(slg_index *ix, uint32_t nq, const uint32_t *q_offsets, const uint32_t *q_term_ids,
+                              const float *q_weights, const slg_score_plans *plans, const int32_t *q_filter,
+                              const slg_sort_spec *sort, const slg_sort_cursor *q_cursor,
+                              const slg_collapse_spec *collapse, uint32_t k, int strategy, uint32_t *out_doc,
+                              uint32_t *out_seg, float *out_score, uint32_t *out_count, uint32_t *n_groups,
+                              uint32_t *total_groups, uint32_t *status, uint32_t *group_row, uint32_t *group_ord,
+                              uint32_t *group_size, uint32_t *group_doc, uint32_t *group_seg, float *group_score,
+                              uint32_t *inner_count, uint32_t *inner_row, uint32_t *inner_doc, uint32_t *inner_seg,
+                              float *inner_score) {
+  void *const arrays[14] = {n_groups,  total_groups, status,      group_row, group_ord, group_size, group_doc,
+                            group_seg, group_score,  inner_count, inner_row, inner_doc, inner_seg,  inner_score};
+  HostOut o{out_doc, out_seg, out_score, out_count};
+  o.collapse = arrays;
+  return run_to_host(slg_batch_prepare_collapse(ix, nq, q_offsets, q_term_ids, q_weights, plans, q_filter, sort,
+                                                q_cursor, collapse, k, strategy),
+                     o);
 }
 
 int slg_batch_cursor_seen(slg_batch *b, uint8_t *out_seen) {

@@ -1,5 +1,5 @@
 // slg_host.hpp — what the host translation units of the C ABI share (slg_index.hip, slg_batch.hip,
-// slg_shard.hip, slg_rerank.hip, slg_vsearch.hip, slg_hybrid.hip, slg_aggs.hip, slg_rescore.hip, slg_bool.hip, slg_phrase.hip, slg_fscore.hip): the error plumbing, device memory, the host
+// slg_shard.hip, slg_rerank.hip, slg_vsearch.hip, slg_hybrid.hip, slg_aggs.hip, slg_rescore.hip, slg_bool.hip, slg_phrase.hip, slg_fscore.hip, slg_collapse.hip): the error plumbing, device memory, the host
 // structures behind the opaque handles and the small helpers several entry points use.  Private: not
 // installed, not part of include/.  No kernel header is included here — each unit includes the one
 // whose kernels it launches (slg_stage.hpp, slg_kernels.hpp, slg_rerank.hpp, slg_vsearch.hpp, slg_hybrid.hpp; the shard
@@ -529,6 +529,14 @@ struct slg_batch {
   bool fscore_full = false;  // some function needs ln / log1p / log2 / pow: the full instantiation
   uint32_t fscore_fns = 0, fscore_cols = 0;  // entries of the two tables behind the FscoreQuery records
   DevBuf d_fscore_desc;      // slg::FscoreQuery[nq], FscoreFn[fscore_fns], FscoreColDev[fscore_cols], bitmap addresses
+  // collapse batch (slg_batch_prepare_collapse): a plain, sorted or cursor batch; collapse_kernel runs behind its
+  // last kernel and fills the side arrays from each query's rows, which it leaves as they are (slg_collapse.hip)
+  bool collapse = false;
+  uint32_t cl_groups = 0, cl_from = 0, cl_size = 0;  // group_limit, inner_from, inner_size
+  uint32_t cl_lds_rows = 0;                          // rows the kernel's LDS arrays hold: a power of two >= k
+  uint32_t cl_parts = 0, cl_score_parts = 0, cl_desc_parts = 0;  // the inner sort (0 parts: the batch's own order)
+  DevBuf d_cl_desc;  // slg::AggColDev[n_segs], then slg::SortColDev[kSortMaxParts * n_segs] of the inner sort
+  DevBuf d_cl_side;  // the arrays of slg_batch_fetch_collapse, back to back in its argument order
 };
 
 namespace slghost __attribute__((visibility("hidden"))) {
@@ -648,6 +656,7 @@ struct PrepareRequest {
   Asked<slg_bool_spec> boolean;   // a phrase batch: on, its spec may be NULL (no term groups)
   Asked<slg_phrase_spec> phrase;
   Asked<slg_fscore_spec> fscore;
+  Asked<slg_collapse_spec> collapse;
 };
 // a spec that is a kind of its own only when it is given (the sort of a bool, phrase, cursor or agg batch)
 template <typename T>
@@ -714,6 +723,10 @@ void phrase_launch(slg_batch *b, hipStream_t st);
 std::vector<slgplan::FscoreFieldView> fscore_field_views(const IndexState &S);
 void fscore_attach(slg_batch *b, const slgplan::FscorePlan &fp);
 void fscore_launch(slg_batch *b, hipStream_t st);
+// slg_collapse.hip: the spec against the batch's state (its keyword column, the inner sort's columns), the tables
+// and side arrays onto the device (throws; the batch is otherwise prepared); the launch behind the batch's rows
+void collapse_attach(slg_batch *b, const slg_collapse_spec &spec, const slg_sort_spec *batch_sort);
+void collapse_launch(slg_batch *b, hipStream_t st);
 
 // slg_vsearch.hip: one vector search or hybrid call, checked against one state of the index ...
 struct VsCall {

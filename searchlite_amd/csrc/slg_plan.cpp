@@ -1251,6 +1251,26 @@ void plan_phrase(const std::vector<SegView> &segs, uint32_t nq, const slg_bool_s
 static_assert(slg::kFscoreMaxFuncs == SLG_MAX_FSCORE_FUNCS, "the kernel's limit and the ABI's");
 static_assert(sizeof(slg::FscoreQuery) == 32 && sizeof(slg::FscoreFn) == 64, "records the kernel reads in whole words");
 
+// ---- field collapsing ------------------------------------------------------------------------------
+void check_collapse(const slg_collapse_spec *spec, uint32_t k) {
+  PLAN_REQUIRE(spec != nullptr, "collapse spec is NULL");
+  PLAN_REQUIRE(spec->group_limit >= 1, "collapse group_limit is 0");
+  PLAN_REQUIRE(spec->group_limit <= k, "collapse group_limit > k");
+  if (const slg_sort_spec *in = spec->inner_sort) {
+    for (uint32_t i = 0; i < std::min<uint32_t>(in->n_parts, SLG_MAX_SORT_PARTS); i++) {
+      PLAN_REQUIRE(in->order[i] == SLG_ORDER_ASC || in->order[i] == SLG_ORDER_DESC,
+                   "unknown sort order in inner sort part " + std::to_string(i));
+      PLAN_REQUIRE(in->field[i] >= 0 || in->field[i] == SLG_SORT_SCORE,
+                   "unknown sort field id in inner sort part " + std::to_string(i));
+    }
+  }
+  if (k > SLG_MAX_COLLAPSE_ROWS) throw SlgError(SLG_ERR_UNSUPPORTED, "collapse batch with k > SLG_MAX_COLLAPSE_ROWS");
+  if (spec->inner_size > 0 && (uint64_t)spec->inner_from + spec->inner_size > SLG_MAX_INNER_HITS)
+    throw SlgError(SLG_ERR_UNSUPPORTED, "collapse inner_from + inner_size > SLG_MAX_INNER_HITS");
+  if (spec->inner_sort && spec->inner_sort->n_parts > SLG_MAX_SORT_PARTS)
+    throw SlgError(SLG_ERR_UNSUPPORTED, "more than SLG_MAX_SORT_PARTS inner sort parts");
+}
+
 void check_fscore(const slg_fscore_spec *spec, uint32_t nq) {
   PLAN_REQUIRE(spec != nullptr, "fscore spec is NULL");
   if (nq == 0) return;

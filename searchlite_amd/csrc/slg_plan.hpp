@@ -128,6 +128,13 @@ struct RescorePlan {
 void plan_rescore(const std::vector<SegView> &segs, uint32_t nq, uint32_t k, const slg_rescore_spec &spec,
                   RescorePlan &out);
 
+// ---- field collapsing (slg_batch_prepare_collapse) ----
+// The checks of a collapse spec that need no index (throws SlgError): a NULL spec, group_limit outside 1 .. k,
+// an inner sort part with an unknown order or a negative field other than SLG_SORT_SCORE (SLG_ERR_INVALID,
+// reported first); k > SLG_MAX_COLLAPSE_ROWS, inner_from + inner_size > SLG_MAX_INNER_HITS with inner hits
+// asked for, more than SLG_MAX_SORT_PARTS inner parts (SLG_ERR_UNSUPPORTED).
+void check_collapse(const slg_collapse_spec *spec, uint32_t k);
+
 // ---- boolean queries (slg_batch_prepare_bool) ----
 // The checks of a bool spec that need no index (throws SlgError): a NULL spec or array, offsets that decrease,
 // a c_group that decreases, skips a number or names a group the query does not have, a group without a term,

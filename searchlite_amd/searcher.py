@@ -436,7 +436,7 @@ class GpuIndex:
                 q_leaf_offsets=None, leaf_group=None, q_group_offsets=None, group_plan=None,
                 group_tie=None, q_node_offsets=None, node_kind=None, node_tie=None, node_parent=None,
                 q_min_match=None, sort=None, cursors=None, hybrid=False, aggs=None,
-                rescore=None, clauses=None, phrases=None, fscore=None) -> "PreparedBatch":
+                rescore=None, clauses=None, phrases=None, fscore=None, collapse=None) -> "PreparedBatch":
         """q_leaf / q_plan / q_tie / q_nleaves: score plans; leaf_group / group_plan / group_tie with
         their per-query offsets: two-level plans; q_node_offsets / node_kind / node_tie / node_parent:
         trees of any shape, node by node in pre-order (slg_batch_prepare_plans, slg_score_plans);
@@ -448,11 +448,28 @@ class GpuIndex:
         slg_batch_prepare_rescore (PreparedBatch.rescore_details); clauses: the dict of search_batch_bool ->
         slg_batch_prepare_bool (score order, or with sort); phrases: the dict of search_batch_phrase ->
         slg_batch_prepare_phrase (with clauses as its term groups, or without); fscore: one function_score per
-        query, the list of fscore_spec() (or its result) -> slg_batch_prepare_fscore (score order, or with sort)."""
+        query, the list of fscore_spec() (or its result) -> slg_batch_prepare_fscore (score order, or with sort);
+        collapse: the dict of search_collapse -> slg_batch_prepare_collapse (score order, with sort and / or cursors;
+        PreparedBatch.collapse_groups)."""
         return PreparedBatch(self, q_offsets, q_terms, q_weights, k, strategy, q_filter,
                              q_leaf, q_plan, q_tie, q_nleaves, q_leaf_offsets, leaf_group,
                              q_group_offsets, group_plan, group_tie, q_node_offsets, node_kind, node_tie, node_parent,
-                             q_min_match, sort, cursors, hybrid, aggs, rescore, clauses, phrases, fscore)
+                             q_min_match, sort, cursors, hybrid, aggs, rescore, clauses, phrases, fscore, collapse)
+
+    def search_collapse(self, q_offsets, q_terms, q_weights, k: int, collapse, sort=None, cursors=None,
+                        strategy: int = Wand, q_filter=None, **plans):
+        """Batch search with field collapsing (slg_batch_prepare_collapse).  collapse: a dict with field (the id of
+        a keyword column, add_agg_keyword_field), group_limit (the request's limit) and optionally inner_from (0),
+        inner_size (0: no inner hits) and inner_sort (None: the batch's own order, else as search_sorted's sort;
+        [] is `_score` desc); sort / cursors as search_sorted / search_after; k = candidate_size + 1.
+        -> (doc, seg, score, count, groups): the rows, and the dict of PreparedBatch.collapse_groups."""
+        b = self.prepare(q_offsets, q_terms, q_weights, k, strategy, q_filter, sort=sort, cursors=cursors,
+                         collapse=collapse, **plans)
+        try:
+            b.run()
+            return b.fetch() + (b.collapse_groups(),)
+        finally:
+            b.close()
 
     def search_plan(self, q_offsets, q_terms, q_weights, k: int, q_leaf=None, q_plan=None,
                     q_tie=None, q_nleaves=None, strategy: int = Wand, q_filter=None, **tree):
@@ -749,6 +766,15 @@ def sort_spec(sort) -> "N.SortSpec":
     return spec
 
 
+def collapse_spec(collapse: dict):
+    """The dict of GpuIndex.search_collapse as (N.CollapseSpec, the inner sort spec it points to or None)."""
+    inner = collapse.get("inner_sort")
+    keep = None if inner is None else (inner if isinstance(inner, N.SortSpec) else sort_spec(inner))
+    spec = N.CollapseSpec(int(collapse["field"]), int(collapse["group_limit"]), int(collapse.get("inner_from", 0)),
+                          int(collapse.get("inner_size", 0)), None if keep is None else C.addressof(keep))
+    return spec, keep
+
+
 def rescore_spec(rescore: dict, nq: int):
     """The dict of GpuIndex.search_rescore as (N.RescoreSpec, the arrays it points into)."""
     def arr(name, dtype, per_query=False):
@@ -888,7 +914,7 @@ class PreparedBatch:
                  q_leaf_offsets=None, leaf_group=None, q_group_offsets=None, group_plan=None,
                  group_tie=None, q_node_offsets=None, node_kind=None, node_tie=None, node_parent=None,
                  q_min_match=None, sort=None, cursors=None, hybrid=False, aggs=None, rescore=None, clauses=None,
-                 phrases=None, fscore=None):
+                 phrases=None, fscore=None, collapse=None):
         self.index = index
         self._lib = index._lib
         q_offsets = np.ascontiguousarray(q_offsets, dtype=np.uint32)
@@ -925,7 +951,25 @@ class PreparedBatch:
         self.is_bool = clauses is not None or phrases is not None
         self.is_phrase = phrases is not None
         self.is_fscore = fscore is not None
-        if fscore is not None:
+        self.is_collapse = collapse is not None
+        if collapse is not None:
+            # (the library's other prepare calls take no collapse spec: the refusal is made here with its code)
+            if hybrid or aggs is not None or rescore is not None or clauses is not None or phrases is not None or \
+                    fscore is not None:
+                raise N.SlgError(N.ERR_UNSUPPORTED, "collapse is not built on hybrid, aggregation, rescore, bool, "
+                                                    "phrase or function_score batches")
+            cspec, self._collapse_keep = collapse if isinstance(collapse, tuple) else collapse_spec(collapse)
+            self.collapse_shape = (int(cspec.group_limit), int(cspec.inner_size))
+            spec = None if sort is None else sort_spec(sort)
+            cur = None
+            if cursors is not None:
+                assert len(cursors) == self.nq
+                cur = (N.SortCursor * max(self.nq, 1))(*[sort_cursor(c, sort) for c in cursors])
+            self._h = self._lib.slg_batch_prepare_collapse(
+                index._h, self.nq, _ptr(q_offsets), _ptr(q_terms), _ptr(q_weights), C.addressof(plans), opt(qf),
+                None if spec is None else C.addressof(spec), None if cur is None else C.addressof(cur),
+                C.addressof(cspec), k, strategy)
+        elif fscore is not None:
             # (the library's other prepare calls take no fscore spec: the refusal is made here with its code)
             if hybrid or cursors is not None or aggs is not None or rescore is not None or clauses is not None or \
                     phrases is not None:
@@ -1055,6 +1099,21 @@ class PreparedBatch:
         flag = np.zeros((self.nq, self.k), dtype=np.uint32)
         N.check(self._lib.slg_batch_fetch_rescore(self._h, _ptr(first), _ptr(rsc), _ptr(flag)))
         return first, rsc, flag
+
+    def collapse_groups(self) -> dict:
+        """The collapse arrays of a collapse batch's last run (slg_batch_fetch_collapse; waits): n_groups,
+        total_groups, status [nq]; group_row, group_ord, group_size, group_doc, group_seg, group_score, inner_count
+        [nq, G]; inner_row, inner_doc, inner_seg, inner_score [nq, G, S] (G = group_limit, S = inner_size).  Zeros
+        past the counts; a query with status 1 (a row with several values: the request fails) has zeros only."""
+        G, S = self.collapse_shape
+        names = [("n_groups", ()), ("total_groups", ()), ("status", ()), ("group_row", (G,)), ("group_ord", (G,)),
+                 ("group_size", (G,)), ("group_doc", (G,)), ("group_seg", (G,)), ("group_score", (G,)),
+                 ("inner_count", (G,)), ("inner_row", (G, S)), ("inner_doc", (G, S)), ("inner_seg", (G, S)),
+                 ("inner_score", (G, S))]
+        out = {n: np.zeros((self.nq,) + shape, dtype=np.float32 if n.endswith("score") else np.uint32)
+               for n, shape in names}
+        N.check(self._lib.slg_batch_fetch_collapse(self._h, *[_ptr(out[n]) if out[n].size else None for n, _ in names]))
+        return out
 
     def cursor_seen(self) -> np.ndarray:
         """Per query of a cursor batch's last run: 1 if an accepted doc had the cursor's key (or the query has

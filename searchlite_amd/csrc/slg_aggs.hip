@@ -60,25 +60,18 @@ void slghost::agg_attach(slg_batch *b, const slg_agg_spec &aggs) {
   const size_t n_segs = S.segs.size();
   const uint32_t nn = aggs.n_nodes;
   std::vector<slg::AggNodeDev> nodes(nn);
-  std::vector<slg::AggColDev> cols((size_t)nn * std::max<size_t>(n_segs, 1), slg::AggColDev{nullptr, nullptr});
+  std::vector<slg::ColumnDev> cols((size_t)nn * std::max<size_t>(n_segs, 1), slg::ColumnDev{nullptr, nullptr});
+  const std::vector<slgplan::FscoreFieldView> fields = fscore_field_views(S);
   b->agg_layout.assign(nn, slg_agg_layout{});
   uint64_t count_cells = 0, stats_cells = 0;
   for (uint32_t i = 0; i < nn; i++) {
     const slg_agg_node &n = aggs.nodes[i];
-    const auto it = S.agg_fields.find(n.field);
-    SLG_REQUIRE(it != S.agg_fields.end(), node_name(i) + ": unknown agg field id " + std::to_string(n.field));
-    const AggFieldData &fd = *it->second;
-    SLG_REQUIRE((n.kind == SLG_AGG_TERMS) == (fd.kind == 2),
+    const slgplan::FscoreFieldView &fd = slgplan::agg_field(fields, n.field, node_name(i) + ": ", "");
+    SLG_REQUIRE((n.kind == SLG_AGG_TERMS) == fd.keyword,
                 node_name(i) + ": field " + std::to_string(n.field) +
-                    (fd.kind == 2 ? " is a keyword field (terms only)" : " is a numeric field (not for terms)"));
-    for (size_t s = 0; s < n_segs; s++) {
-      SLG_REQUIRE(s < fd.per_seg.size() && fd.per_seg[s],
-                  "agg field " + std::to_string(n.field) + " has no column for segment " + std::to_string(s) +
-                      " (added after the field was registered)");
-      const AggColumn &c = *fd.per_seg[s];
-      cols[(size_t)i * n_segs + s] = slg::AggColDev{c.offs.as<const uint32_t>(), c.vals.p};
-    }
-    if (fd.kind == 1 && fd.non_finite)
+                    (fd.keyword ? " is a keyword field (terms only)" : " is a numeric field (not for terms)"));
+    std::copy_n(slgplan::agg_field_rows(fd, (uint32_t)n_segs, "", ""), n_segs, cols.begin() + (size_t)i * n_segs);
+    if (!fd.keyword && fd.non_finite)
       throw SlgError(SLG_ERR_UNSUPPORTED,
                      node_name(i) + ": agg field " + std::to_string(n.field) + " holds a non-finite value (CPU path)");
     slg::AggNodeDev &d = nodes[i];
@@ -159,21 +152,12 @@ void slghost::agg_attach(slg_batch *b, const slg_agg_spec &aggs) {
 }
 
 void slghost::agg_launch(slg_batch *b, hipStream_t st) {
-  const IndexState &S = *b->snap;
   if (b->nq == 0) return;
   slg::AggParams p{};
-  p.queries = b->d_queries;
-  p.slice_seg = b->d_slice_seg;
-  p.slice_cbeg = b->d_slice_cbeg.as<uint64_t>();
-  p.slice_ccnt = b->d_slice_ccnt.as<uint32_t>();
-  p.cand = b->d_cand.as<uint2>();
-  p.segs = S.d_segs.as<slg::SegDev>();
-  p.q_filter = b->d_q_filter.as<uint32_t>();
-  p.reject_table = S.d_reject_table.as<const uint32_t *>();
+  fill_candidates(p, b);
   p.nodes = b->d_agg_desc.as<const slg::AggNodeDev>();
-  p.cols = reinterpret_cast<const slg::AggColDev *>(b->d_agg_desc.as<unsigned char>() +
-                                                    (size_t)b->agg_spec.n_nodes * sizeof(slg::AggNodeDev));
-  p.n_segs = (uint32_t)S.segs.size();
+  p.cols = reinterpret_cast<const slg::ColumnDev *>(b->d_agg_desc.as<unsigned char>() +
+                                                   (size_t)b->agg_spec.n_nodes * sizeof(slg::AggNodeDev));
   p.n_nodes = b->agg_spec.n_nodes;
   p.nq = b->nq;
   p.count_cells = b->agg_count_cells;

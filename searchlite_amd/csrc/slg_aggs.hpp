@@ -28,12 +28,6 @@ constexpr uint32_t kAggLdsBytes = 32768;  // SLG_AGG_LDS_BYTES: five workgroups 
 constexpr uint32_t kAggMaxRanges = 16;    // SLG_MAX_AGG_RANGES
 enum : int32_t { kAggTerms = 0, kAggHistogram = 1, kAggRange = 2, kAggStats = 3 };
 
-// one column of one segment: CSR over the docs, or (offs == nullptr) exactly one value per doc
-struct AggColDev {
-  const uint32_t *offs;  // [n_docs + 1]
-  const void *vals;      // double[] (numeric) or uint32_t[] (ordinals)
-};
-
 // min and max as u64 keys under atomicMax, so that an all-zero cell is the empty one: max_key = the value's
 // order-preserving key, min_key = its complement (keys of finite values are neither 0 nor ~0)
 struct AggStatDev {
@@ -63,7 +57,7 @@ struct AggParams {
   const uint32_t *q_filter;             // [nq] 0 = none, f + 1
   const uint32_t *const *reject_table;  // [n_filters * n_segs] reject bitmaps
   const AggNodeDev *nodes;              // [n_nodes]
-  const AggColDev *cols;                // [n_nodes * n_segs]
+  const ColumnDev *cols;                // [n_nodes * n_segs]
   uint32_t n_segs, n_nodes, nq;
   uint32_t count_cells, stats_cells;
   uint32_t *counts;                 // [nq * count_cells]
@@ -82,14 +76,11 @@ template <typename F>
 __device__ __forceinline__ void agg_collect(const AggParams &p, const AggNodeDev &n, const uint32_t seg,
                                             const uint32_t doc, const uint32_t cell, uint32_t *cnt, AggStatDev *st,
                                             F &&child) {
-  const AggColDev col = p.cols[(size_t)n.col * p.n_segs + seg];
-  uint32_t a = doc, e = doc + 1;
-  if (col.offs) {
-    a = col.offs[doc];
-    e = col.offs[doc + 1];
-  }
+  const ColumnDev col = p.cols[(size_t)n.col * p.n_segs + seg];
+  uint32_t a, e;
+  column_range(col, doc, a, e);
   if (n.kind == kAggTerms) {
-    const uint32_t *v = static_cast<const uint32_t *>(col.vals);
+    const uint32_t *v = col.ords();
     if (e == a) {
       if (n.has_missing && n.missing_ord < n.rows) {
         atomicAdd(&cnt[cell + n.missing_ord], 1u);
@@ -108,7 +99,7 @@ __device__ __forceinline__ void agg_collect(const AggParams &p, const AggNodeDev
     }
     return;
   }
-  const double *v = static_cast<const double *>(col.vals);
+  const double *v = col.f64();
   const bool miss = e == a;
   if (miss && !n.has_missing) return;
   const uint32_t nv = miss ? 1u : e - a;

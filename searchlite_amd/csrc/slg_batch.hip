@@ -2,7 +2,6 @@
 // run, waiting, fetching and destroying, the one-call searches, and the merge of shard results.
 #include "slg_host.hpp"
 
-#include <optional>
 #include <thread>
 
 #include "slg_kernels.hpp"
@@ -63,19 +62,12 @@ void fill_final(P &p, const slg_batch *b) {
   p.error_flag = b->idx->d_error_flag.as<uint32_t>();
   p.out_flag = ResultBlock(b->nq, b->k).flag(b->d_out.as<uint32_t>());
 }
-// ... and what the two selects share beyond that: the candidates, the filters of the batch's state, and
-// the matched counts, cursor keys and seen flags of the batches that have them (null otherwise)
+// ... and what the two selects share beyond that: the candidate regions (fill_candidates), and the matched
+// counts, cursor keys and seen flags of the batches that have them (null otherwise)
 template <typename P>
 void fill_select(P &p, const slg_batch *b) {
-  const IndexState &S = *b->snap;
   fill_final(p, b);
-  p.slice_cbeg = b->d_slice_cbeg.as<uint64_t>();
-  p.slice_ccnt = b->d_slice_ccnt.as<uint32_t>();
-  p.cand = b->d_cand.as<uint2>();
-  p.segs = S.d_segs.as<slg::SegDev>();
-  p.q_filter = b->d_q_filter.as<uint32_t>();
-  p.reject_table = S.d_reject_table.as<const uint32_t *>();
-  p.n_segs = (uint32_t)S.segs.size();
+  fill_candidates(p, b);
   p.out_matched = b->d_matched.as<unsigned long long>();
   p.cursor = b->d_cursor.as<const uint32_t>();
   p.out_seen = b->d_seen.as<uint32_t>();
@@ -118,6 +110,34 @@ void slghost::launch_shard_merge(const slg::ShardMergeParams &mp, hipStream_t st
     default: launch_shard_merge_t<16>(mp, st); break;
   }
   SLG_HIP(hipGetLastError());
+}
+
+// every part names `_score` or a field with a column for every segment (a field registered before
+// slg_index_add_segment has none for the new one)
+SortBinding slghost::bind_sort(const IndexState &S, const slg_sort_spec &spec, const std::string &prefix,
+                               const std::string &part) {
+  const size_t n_segs = S.segs.size();
+  SortBinding sb;
+  sb.cols.assign(slg::kSortMaxParts * std::max<size_t>(n_segs, 1), slg::SortColDev{nullptr, nullptr});
+  for (uint32_t i = 0; i < spec.n_parts; i++) {
+    if (spec.order[i] == SLG_ORDER_DESC) sb.desc_parts |= 1u << i;
+    if (spec.field[i] == SLG_SORT_SCORE) {
+      sb.score_parts |= 1u << i;
+      continue;
+    }
+    const auto it = S.sort_fields.find(spec.field[i]);
+    SLG_REQUIRE(it != S.sort_fields.end(), prefix + "unknown sort field id in " + part + std::to_string(i));
+    const SortFieldData &fd = *it->second;
+    for (size_t s = 0; s < n_segs; s++) {
+      SLG_REQUIRE(s < fd.per_seg.size() && fd.per_seg[s],
+                  prefix + "sort field " + std::to_string(spec.field[i]) + " has no column for segment " +
+                      std::to_string(s) + " (added after the field was registered)");
+      const SortColumn &c = *fd.per_seg[s];
+      sb.cols[i * n_segs + s] = slg::SortColDev{c.key[spec.order[i]].as<const unsigned long long>(),
+                                                c.present.as<const uint32_t>()};
+    }
+  }
+  return sb;
 }
 
 void slghost::release_batch_buffers(slg_batch *b, bool to_pool) {
@@ -217,32 +237,8 @@ slg_batch *slghost::prepare_impl(const PrepareRequest &r) {
     in.filter_live = filter_live.data();
     in.n_filters = filter_live.size();
     in.sorted = sort != nullptr || after || hybrid || r.aggs.on || r.boolean.on || r.fscore.on;
-    // the columns of the sort parts in the batch's state: every part names a field with a column for every
-    // segment (a field registered before slg_index_add_segment has none for the new one)
-    std::vector<slg::SortColDev> sort_cols;
-    uint32_t score_parts = 0, desc_parts = 0;
-    if (sort) {
-      const size_t n_segs = snap->segs.size();
-      sort_cols.assign(slg::kSortMaxParts * std::max<size_t>(n_segs, 1), slg::SortColDev{nullptr, nullptr});
-      for (uint32_t i = 0; i < sort->n_parts; i++) {
-        if (sort->order[i] == SLG_ORDER_DESC) desc_parts |= 1u << i;
-        if (sort->field[i] == SLG_SORT_SCORE) {
-          score_parts |= 1u << i;
-          continue;
-        }
-        const auto it = snap->sort_fields.find(sort->field[i]);
-        SLG_REQUIRE(it != snap->sort_fields.end(), "unknown sort field id in part " + std::to_string(i));
-        const SortFieldData &fd = *it->second;
-        for (size_t s = 0; s < n_segs; s++) {
-          SLG_REQUIRE(s < fd.per_seg.size() && fd.per_seg[s],
-                      "sort field " + std::to_string(sort->field[i]) + " has no column for segment " + std::to_string(s) +
-                          " (added after the field was registered)");
-          const SortColumn &c = *fd.per_seg[s];
-          sort_cols[i * n_segs + s] = slg::SortColDev{c.key[sort->order[i]].as<const unsigned long long>(),
-                                                      c.present.as<const uint32_t>()};
-        }
-      }
-    }
+    SortBinding sorting;  // the columns of the sort parts in the batch's state
+    if (sort) sorting = bind_sort(*snap, *sort, "", "part ");
     // the cursors as the key words the select kernel compares (against the same snapshot's field kinds)
     std::vector<uint32_t> cursor_words;
     if (after) {
@@ -351,10 +347,10 @@ slg_batch *slghost::prepare_impl(const PrepareRequest &r) {
     }
     if (b->sorted) {
       b->n_sort_parts = sort->n_parts;
-      b->sort_score_parts = score_parts;
-      b->sort_desc_parts = desc_parts;
-      b->d_sort_cols.alloc_pooled(&ix->pool, sort_cols.size() * sizeof(slg::SortColDev));
-      SLG_HIP(hipMemcpy(b->d_sort_cols.p, sort_cols.data(), sort_cols.size() * sizeof(slg::SortColDev),
+      b->sort_score_parts = sorting.score_parts;
+      b->sort_desc_parts = sorting.desc_parts;
+      b->d_sort_cols.alloc_pooled(&ix->pool, sorting.cols.size() * sizeof(slg::SortColDev));
+      SLG_HIP(hipMemcpy(b->d_sort_cols.p, sorting.cols.data(), sorting.cols.size() * sizeof(slg::SortColDev),
                         hipMemcpyHostToDevice));
     }
     if (b->sorted || b->after || r.aggs.on) b->d_matched.alloc_pooled(&ix->pool, (size_t)std::max<uint32_t>(nq, 1) * 8);
@@ -527,7 +523,7 @@ int slg_batch_run(slg_batch *b) {
     if (b->sorted) {  // (also without slices: every row is empty, every matched count 0)
       slg::SortedSelectParams sp{};
       fill_select(sp, b);
-      sp.cols = b->d_sort_cols.as<const slg::SortColDev>();
+      sp.sort_cols = b->d_sort_cols.as<const slg::SortColDev>();
       sp.n_parts = b->n_sort_parts;
       sp.score_parts = b->sort_score_parts;
       sp.desc_parts = b->sort_desc_parts;
@@ -571,9 +567,6 @@ int slg_batch_sync(slg_batch *b) {
   });
 }
 
-// result blocks up to this size are fetched into pageable memory (see slg_batch_fetch)
-static constexpr size_t kPageableFetchBytes = 256u << 10;
-
 int slg_batch_fetch(slg_batch *b, uint32_t *out_doc, uint32_t *out_seg, float *out_score,
                     uint32_t *out_count, slg_stats *stats) {
   return guarded([&] {
@@ -596,16 +589,8 @@ int slg_batch_fetch(slg_batch *b, uint32_t *out_doc, uint32_t *out_seg, float *o
       // 4-byte copy of the error word).
       const size_t words = R.words_with_flag();
       const size_t extra = stats ? (size_t)b->nq + ((b->d_blk_skip.p && b->launched) ? 2 * ((size_t)b->nq + 1) : 0) : 0;
-      std::optional<ImageLease> lease;
-      std::vector<uint32_t> pageable;
-      uint32_t *blk = nullptr;
-      if ((words + extra) * 4 <= kPageableFetchBytes) {
-        pageable.resize(words + extra);
-        blk = pageable.data();
-      } else {
-        lease.emplace(ix->pool, (words + extra) * 4);
-        blk = static_cast<uint32_t *>(lease->p);
-      }
+      FetchBlock host(ix->pool, words + extra);
+      uint32_t *const blk = host.p;
       SLG_HIP(hipMemcpyAsync(blk, b->d_out.p, words * 4, hipMemcpyDeviceToHost, st));
       uint32_t *flagw = R.flag(blk);  // the index's error word as the batch's last kernel saw it
       uint32_t *const sblk = blk + words;

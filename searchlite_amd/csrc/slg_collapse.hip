@@ -3,14 +3,12 @@
 // slg_batch_fetch_collapse.  (The checks of a spec that need no index: slg_plan.cpp, check_collapse.)
 #include "slg_host.hpp"
 
-#include <optional>
-
 #include "slg_collapse.hpp"
 
 using namespace slghost;
 
 static_assert(slg::kCollapseMaxRows == SLG_MAX_COLLAPSE_ROWS, "the kernel's LDS rows and the ABI's limit on k");
-static_assert(slg::kCollapseSortParts == SLG_MAX_SORT_PARTS, "the inner sort's parts");
+static_assert(slg::kSortMaxParts == SLG_MAX_SORT_PARTS, "the inner sort's parts");
 static_assert(SLG_MAX_INNER_HITS == 64u, "one kept member per lane of a wave");
 
 namespace {
@@ -22,18 +20,11 @@ void slghost::collapse_attach(slg_batch *b, const slg_collapse_spec &spec, const
   const IndexState &S = *b->snap;
   slg_index *ix = b->idx;
   const size_t n_segs = S.segs.size();
-  const auto it = S.agg_fields.find(spec.field);
-  SLG_REQUIRE(it != S.agg_fields.end(), "collapse: unknown agg field id " + std::to_string(spec.field));
-  const AggFieldData &fd = *it->second;
-  SLG_REQUIRE(fd.kind == 2, "collapse: field " + std::to_string(spec.field) + " is a numeric field (keyword columns only)");
-  std::vector<slg::CollapseColDev> cols(std::max<size_t>(n_segs, 1), slg::CollapseColDev{nullptr, nullptr});
-  for (size_t s = 0; s < n_segs; s++) {
-    SLG_REQUIRE(s < fd.per_seg.size() && fd.per_seg[s],
-                "collapse: agg field " + std::to_string(spec.field) + " has no column for segment " + std::to_string(s) +
-                    " (added after the field was registered)");
-    const AggColumn &c = *fd.per_seg[s];
-    cols[s] = slg::CollapseColDev{c.offs.as<const uint32_t>(), c.vals.as<const uint32_t>()};
-  }
+  const std::vector<slgplan::FscoreFieldView> fields = fscore_field_views(S);
+  const slgplan::FscoreFieldView &fd = slgplan::agg_field(fields, spec.field, "collapse: ", "");
+  SLG_REQUIRE(fd.keyword, "collapse: field " + std::to_string(spec.field) + " is a numeric field (keyword columns only)");
+  std::vector<slg::ColumnDev> cols(std::max<size_t>(n_segs, 1), slg::ColumnDev{nullptr, nullptr});
+  std::copy_n(slgplan::agg_field_rows(fd, (uint32_t)n_segs, "collapse: ", ""), n_segs, cols.begin());
   // the inner sort: none, or one that equals the batch's own order (score order: `_score` desc), leaves the
   // members in row order; an empty one is `_score` desc (query/sort.rs:159-167)
   slg_sort_spec inner{}, own{};
@@ -49,33 +40,17 @@ void slghost::collapse_attach(slg_batch *b, const slg_collapse_spec &spec, const
       same = inner.field[i] == own.field[i] && inner.order[i] == own.order[i];
     resort = !same;
   }
-  std::vector<slg::CollapseSortColDev> scols(slg::kCollapseSortParts * std::max<size_t>(n_segs, 1),
-                                             slg::CollapseSortColDev{nullptr, nullptr});
-  b->cl_parts = b->cl_score_parts = b->cl_desc_parts = 0;
-  for (uint32_t i = 0; resort && i < inner.n_parts; i++) {
-    if (inner.order[i] == SLG_ORDER_DESC) b->cl_desc_parts |= 1u << i;
-    if (inner.field[i] == SLG_SORT_SCORE) {
-      b->cl_score_parts |= 1u << i;
-      continue;
-    }
-    const auto sf = S.sort_fields.find(inner.field[i]);
-    SLG_REQUIRE(sf != S.sort_fields.end(), "collapse: unknown sort field id in inner sort part " + std::to_string(i));
-    for (size_t s = 0; s < n_segs; s++) {
-      SLG_REQUIRE(s < sf->second->per_seg.size() && sf->second->per_seg[s],
-                  "collapse: sort field " + std::to_string(inner.field[i]) + " has no column for segment " +
-                      std::to_string(s) + " (added after the field was registered)");
-      const SortColumn &c = *sf->second->per_seg[s];
-      scols[i * n_segs + s] = slg::CollapseSortColDev{c.key[inner.order[i]].as<const unsigned long long>(),
-                                                      c.present.as<const uint32_t>()};
-    }
-  }
-  if (resort) b->cl_parts = inner.n_parts;
+  if (!resort) inner = slg_sort_spec{};  // (no part: an all-null table, the members stay in row order)
+  const SortBinding sorting = bind_sort(S, inner, "collapse: ", "inner sort part ");
+  b->cl_parts = inner.n_parts;
+  b->cl_score_parts = sorting.score_parts;
+  b->cl_desc_parts = sorting.desc_parts;
   b->collapse = true;
   b->cl_groups = spec.group_limit;
   b->cl_from = spec.inner_from;
   b->cl_size = spec.inner_size;
   b->cl_lds_rows = slg::collapse_lds_rows(b->k);
-  upload_image(b->d_cl_desc, &ix->pool, {image_part(cols), image_part(scols)});
+  upload_image(b->d_cl_desc, &ix->pool, {image_part(cols), image_part(sorting.cols)});
   b->d_cl_side.alloc_pooled(&ix->pool, (side_off(b, slg::kClArrays) + 1) * 4);  // (+ the error word)
 }
 
@@ -84,8 +59,8 @@ void slghost::collapse_launch(slg_batch *b, hipStream_t st) {
   const IndexState &S = *b->snap;
   const size_t n_segs = S.segs.size();
   slg::CollapseParams p{};
-  p.cols = b->d_cl_desc.as<const slg::CollapseColDev>();
-  p.scols = reinterpret_cast<const slg::CollapseSortColDev *>(p.cols + std::max<size_t>(n_segs, 1));
+  p.cols = b->d_cl_desc.as<const slg::ColumnDev>();
+  p.sort_cols = reinterpret_cast<const slg::SortColDev *>(p.cols + std::max<size_t>(n_segs, 1));
   p.n_segs = (uint32_t)n_segs;
   p.n_parts = b->cl_parts;
   p.score_parts = b->cl_score_parts;
@@ -118,19 +93,10 @@ int slg_batch_fetch_collapse(slg_batch *b, uint32_t *n_groups, uint32_t *total_g
     DeviceGuard g(b->idx->device);
     const hipStream_t st = locked_stream(b);
     if (b->nq == 0) return;
-    // the arrays and the error word behind them are one block: ONE D2H copy, small blocks into pageable memory,
-    // large ones into a pinned image of the index's pool (as slg_batch_fetch)
+    // the arrays and the error word behind them are one block: ONE D2H copy (as slg_batch_fetch)
     const size_t words = side_off(b, slg::kClArrays) + 1;
-    std::optional<ImageLease> lease;
-    std::vector<uint32_t> pageable;
-    uint32_t *blk = nullptr;
-    if (words * 4 <= (256u << 10)) {
-      pageable.resize(words);
-      blk = pageable.data();
-    } else {
-      lease.emplace(b->idx->pool, words * 4);
-      blk = static_cast<uint32_t *>(lease->p);
-    }
+    FetchBlock host(b->idx->pool, words);
+    uint32_t *const blk = host.p;
     SLG_HIP(hipMemcpyAsync(blk, b->d_cl_side.p, words * 4, hipMemcpyDeviceToHost, st));
     SLG_HIP(wait_stream(st));
     if (blk[words - 1] != 0u)  // rows a scoring wave gave up on are not collapsed into an answer

@@ -20,7 +20,7 @@
 //   4. (group << 12 | row) of every row with a value, bitonic-sorted over the table's first half: each group
 //      is a run in row order with its representative first; the run starts give the sizes
 //   5. inner hits in row order are slices of the runs; under an inner sort one wave per reported group keeps
-//      the best from + size <= 64 members sorted one per lane (a member's key: select_sorted_kernel's words),
+//      the best from + size <= 64 members sorted one per lane (a member's key: sorted_key's words),
 //      reading the run 64 members at a time and inserting those that beat the list's last by ballot + shuffle
 // Nothing depends on scheduling: the table's final content, the scan, the sort of distinct keys and the
 // per-wave insertion are all functions of the rows.  Every element of every side array is written on every
@@ -39,25 +39,12 @@ constexpr uint32_t kCollapseMaxRows = 4096;  // SLG_MAX_COLLAPSE_ROWS
 constexpr uint32_t kCollapseRowBits = 12;    // a row index in the sort key
 constexpr uint32_t kCollapseRowsPerThread = kCollapseMaxRows / kCollapseThreads;
 constexpr uint32_t kCollapseNone = 0xFFFFFFFFu;  // a row without a value; an empty slot; a pad key
-constexpr uint32_t kCollapseSortParts = 4;       // SLG_MAX_SORT_PARTS
-constexpr uint32_t kCollapseWords = 3 * kCollapseSortParts + 2;  // the select's kSortWords
 constexpr uint32_t kCollapseMisc = 16;           // words behind the arrays: status, valid rows, wave sums
 static_assert((1u << kCollapseRowBits) == kCollapseMaxRows, "row bits of the sort key");
 
-// the keyword column of one segment (the layout of an aggregation column: slg_aggs.hpp AggColDev)
-struct CollapseColDev {
-  const uint32_t *offs;  // [n_docs + 1], or nullptr: one value per doc
-  const uint32_t *ords;  // nullptr: the segment has no column, no doc has a value
-};
-// one part of the inner sort in one segment (slg_kernels.hpp SortColDev)
-struct CollapseSortColDev {
-  const unsigned long long *key;  // [n_docs] u64 key of the part's order (0 for Missing docs)
-  const uint32_t *present;        // presence bitmap
-};
-
 struct CollapseParams {
-  const CollapseColDev *cols;       // [n_segs]
-  const CollapseSortColDev *scols;  // [kCollapseSortParts * n_segs]: part p of segment s at p * n_segs + s
+  const ColumnDev *cols;        // [n_segs] the keyword column (vals nullptr: no doc of the segment has a value)
+  const SortColDev *sort_cols;  // [kSortMaxParts * n_segs] the inner sort: part p of segment s at p * n_segs + s
   uint32_t n_segs;
   uint32_t n_parts;  // of the inner sort; 0: members stay in row order
   uint32_t score_parts, desc_parts;  // bit p: part p is `_score` / descends (as SortedSelectParams)
@@ -93,38 +80,11 @@ inline uint32_t collapse_lds_rows(uint32_t k) {
 }
 inline size_t collapse_lds_bytes(uint32_t lds_rows) { return ((size_t)lds_rows * 3 + kCollapseMisc) * 4; }
 
-// a row's inner sort key: sorted_key's layout (slg_kernels.hpp), the `_score` part from the row's score
-__device__ __forceinline__ void collapse_key(const CollapseParams &p, const float score, const uint32_t seg,
-                                             const uint32_t doc, uint32_t (&K)[kCollapseWords]) {
-  const uint32_t a = ordered_score(score);
-#pragma unroll
-  for (uint32_t i = 0; i < kCollapseSortParts; i++) {
-    uint32_t w0 = 0, w1 = 0, w2 = 0;
-    if (i < p.n_parts) {
-      if ((p.score_parts >> i) & 1u) {
-        w2 = ((p.desc_parts >> i) & 1u) ? ~a : a;
-      } else {
-        const CollapseSortColDev c = p.scols[(size_t)i * p.n_segs + seg];
-        const uint32_t pw = c.present[doc >> 5];
-        const unsigned long long v = c.key[doc];
-        w0 = ((pw >> (doc & 31u)) & 1u) ^ 1u;
-        w1 = (uint32_t)(v >> 32);
-        w2 = (uint32_t)v;
-      }
-    }
-    K[3 * i] = w0;
-    K[3 * i + 1] = w1;
-    K[3 * i + 2] = w2;
-  }
-  K[kCollapseWords - 2] = seg;
-  K[kCollapseWords - 1] = doc;
-}
-
 // x < y, word by word
-__device__ __forceinline__ bool collapse_less(const uint32_t (&x)[kCollapseWords], const uint32_t (&y)[kCollapseWords]) {
+__device__ __forceinline__ bool collapse_less(const uint32_t (&x)[kSortWords], const uint32_t (&y)[kSortWords]) {
   int c = 0;
 #pragma unroll
-  for (uint32_t w = 0; w < kCollapseWords; w++)
+  for (uint32_t w = 0; w < kSortWords; w++)
     if (c == 0) c = x[w] < y[w] ? -1 : (x[w] > y[w] ? 1 : 0);
   return c < 0;
 }
@@ -165,14 +125,11 @@ static __global__ void __launch_bounds__(kCollapseThreads) collapse_kernel(Colla
       const uint32_t seg = oseg[i], doc = odoc[i];
       uint32_t o = NONE;
       if (seg < p.n_segs) {
-        const CollapseColDev col = p.cols[seg];
-        if (col.ords) {
-          uint32_t a = doc, e = doc + 1u;
-          if (col.offs) {
-            a = col.offs[doc];
-            e = col.offs[doc + 1u];
-          }
-          if (e - a == 1u) o = col.ords[a];
+        const ColumnDev col = p.cols[seg];
+        if (col.vals) {
+          uint32_t a, e;
+          column_range(col, doc, a, e);
+          if (e - a == 1u) o = col.ords()[a];
           multi = multi || (e > a && e - a > 1u);
         }
       }
@@ -340,7 +297,7 @@ static __global__ void __launch_bounds__(kCollapseThreads) collapse_kernel(Colla
   }
   // under the inner sort: a wave per group, lane l holds the l-th best member seen so far (all-ones: none; no
   // row's key is all-ones, its doc word is a doc id)
-  constexpr uint32_t NW = kCollapseWords;
+  constexpr uint32_t NW = kSortWords;
   const uint32_t L = from + S;  // <= 64
   for (uint32_t g = wave; g < G; g += NT / 64u) {
     uint32_t K[NW], krow = 0;
@@ -355,7 +312,7 @@ static __global__ void __launch_bounds__(kCollapseThreads) collapse_kernel(Colla
       uint32_t C[NW], W[NW];
 #pragma unroll
       for (uint32_t w = 0; w < NW; w++) C[w] = 0xFFFFFFFFu;
-      if (has) collapse_key(p, oscore[row], oseg[row], odoc[row], C);
+      if (has) sorted_key(p, ordered_score(oscore[row]), oseg[row], odoc[row], C);
 #pragma unroll
       for (uint32_t w = 0; w < NW; w++) W[w] = (uint32_t)__shfl((int)K[w], (int)(L - 1u), 64);
       // (the list's last as it is now: it only gets better, so a member that does not beat it never enters)

@@ -226,6 +226,23 @@ constexpr uint32_t kPhraseMaxQueryTerms = 64;  // = SLG_MAX_PHRASE_QUERY_TERMS
 constexpr uint32_t kPhraseMaxSlop = 0x7FFFFFFFu - kPhraseMaxTerms;  // = SLG_MAX_PHRASE_SLOP
 constexpr uint32_t kPositionEnd = 0x80000000u;  // positions are below it (the reference's gaps are i32)
 
+// ---- registered columns of one segment, as every batch kind's tables hold them ------------------------
+// (the device code that reads them: slg_wave.hpp column_range, sorted_key)
+// An aggregation column (slg_index_add_agg_field_*): aggregations, function_score, filter trees, collapse
+struct ColumnDev {
+  const uint32_t *offs;  // [n_docs + 1] into vals, or nullptr: every doc has exactly one value, vals[doc]
+  const void *vals;      // double[] (numeric) or uint32_t[] (keyword ordinals); nullptr: the segment has no column
+  SLG_HD const double *f64() const { return static_cast<const double *>(vals); }
+  SLG_HD const uint32_t *ords() const { return static_cast<const uint32_t *>(vals); }
+};
+// One part of a sort (slg_index_add_sort_field_*): the sorted select, the inner sort of collapse
+struct SortColDev {
+  const unsigned long long *key;  // [n_docs] u64 key of the part's order (0 for Missing docs)
+  const uint32_t *present;        // presence bitmap (bit d & 31 of word d >> 5)
+};
+constexpr uint32_t kSortMaxParts = 4;  // SLG_MAX_SORT_PARTS
+constexpr uint32_t kSortWords = 3 * kSortMaxParts + 2;  // of a sort key: three per part, segment, doc
+
 // ---- function_score (slg_batch_prepare_fscore; kernel: slg_fscore.hpp, planner: slg_plan.cpp) --------
 // The functions of query q are fns[fn_begin .. fn_begin + n_fns), in request order, the same for every segment.
 // A function's column is cols[col * n_segs + seg], its filter's reject bitmap filters[(filter - 1) * n_segs + seg].
@@ -244,15 +261,11 @@ struct FscoreFn {
   double missing, origin, scale, offset, decay;
   uint32_t pad[2];
 };
-struct FscoreColDev {
-  const uint32_t *offs;  // [n_docs + 1] into vals, or nullptr: every doc has exactly one value, vals[doc]
-  const double *vals;
-};
 constexpr uint32_t kFscoreMaxFuncs = 8;  // = SLG_MAX_FSCORE_FUNCS
 
 // ---- filter trees (slg_index_add_filter_trees; kernel: slg_filter.hpp, planner: slg_plan.cpp) --------
 // The image of one call: trees[n_trees], nodes (every tree's, in postfix order), the column table, the filter
-// table, the words of the ordinal bit sets.  A leaf's column is cols[row * n_segs + seg] (FscoreColDev; a keyword
+// table, the words of the ordinal bit sets.  A leaf's column is cols[row * n_segs + seg] (ColumnDev; a keyword
 // column's vals are u32 ordinals), a FILTER_ID leaf's reject bitmap filters[row * n_segs + seg].
 struct FilterTreeDev {
   uint32_t node_begin, n_nodes;

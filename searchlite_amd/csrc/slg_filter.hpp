@@ -20,7 +20,7 @@ namespace slg {
 struct FilterTreeParams {
   const FilterTreeDev *trees;            // [gridDim.y]
   const FilterNodeDev *nodes;
-  const FscoreColDev *cols;              // [column rows][n_segs]
+  const ColumnDev *cols;                 // [column rows][n_segs]
   const uint32_t *const *filters;        // [filter rows][n_segs] reject bitmaps of FILTER_ID leaves
   const uint32_t *words;                 // the ordinal bit sets
   uint32_t *const *out;                  // [gridDim.y][n_segs] the reject bitmaps to write
@@ -42,15 +42,16 @@ static __global__ void __launch_bounds__(kFilterThreads) filter_tree_kernel(Filt
     if (n.kind <= kFilterRangeI64) {
       // a leaf over a column: the doc's values are vals[a .. b) (no offsets: exactly vals[d]); a lane past
       // n_docs has none.  The walk ends when no lane of the wave has a value left; a lane that passed stops
-      const FscoreColDev c = load_const(p.cols + (size_t)n.row * p.n_segs + at);
+      const ColumnDev c = load_const(p.cols + (size_t)n.row * p.n_segs + at);
       uint32_t a = 0, b = 0;
+      // (column_range written out: through the helper the kernel takes 18 VGPRs, not 16)
       if (in) {
         a = c.offs ? c.offs[d] : d;
         b = c.offs ? c.offs[d + 1] : d + 1u;
       }
       bool pass = false;
       if (n.kind == kFilterKeywordIn) {
-        const uint32_t *ords = reinterpret_cast<const uint32_t *>(c.vals);
+        const uint32_t *ords = c.ords();
         const uint32_t *set = p.words + n.bits;
         while (__ballot(a < b) != 0ull) {
           if (a < b) {
@@ -62,7 +63,7 @@ static __global__ void __launch_bounds__(kFilterThreads) filter_tree_kernel(Filt
       } else {
         while (__ballot(a < b) != 0ull) {
           if (a < b) {
-            const double v = c.vals[a];
+            const double v = c.f64()[a];
             pass = n.lo <= v && v <= n.hi;  // (a NaN never passes)
             a = pass ? b : a + 1u;
           }

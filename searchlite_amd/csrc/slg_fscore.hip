@@ -7,7 +7,7 @@
 
 using namespace slghost;
 
-static_assert(sizeof(slg::FscoreQuery) == 32 && sizeof(slg::FscoreFn) == 64 && sizeof(slg::FscoreColDev) == 16,
+static_assert(sizeof(slg::FscoreQuery) == 32 && sizeof(slg::FscoreFn) == 64 && sizeof(slg::ColumnDev) == 16,
               "the tables are read in whole words, functions and columns 8-byte aligned");
 static_assert(slg::kFsWeight == SLG_FSCORE_WEIGHT && slg::kFsFieldValue == SLG_FSCORE_FIELD_VALUE_FACTOR &&
                   slg::kFsDecay == SLG_FSCORE_DECAY, "header kinds");
@@ -41,10 +41,10 @@ std::vector<slgplan::FscoreFieldView> slghost::fscore_field_views(const IndexSta
     v.any_value = kv.second->any_value;
     v.vmin = kv.second->vmin;
     v.vmax = kv.second->vmax;
-    v.per_seg.assign(S.segs.size(), slg::FscoreColDev{nullptr, nullptr});
+    v.per_seg.assign(S.segs.size(), slg::ColumnDev{nullptr, nullptr});
     for (size_t s = 0; s < S.segs.size() && s < kv.second->per_seg.size(); s++)
       if (const auto &c = kv.second->per_seg[s])
-        v.per_seg[s] = slg::FscoreColDev{c->offs.as<const uint32_t>(), c->vals.as<const double>()};
+        v.per_seg[s] = slg::ColumnDev{c->offs.as<const uint32_t>(), c->vals.p};
     views.push_back(std::move(v));
   }
   return views;
@@ -78,8 +78,8 @@ void slghost::fscore_launch(slg_batch *b, hipStream_t st) {
   base += (size_t)b->nq * sizeof(slg::FscoreQuery);
   p.fns = reinterpret_cast<const slg::FscoreFn *>(base);
   base += (size_t)b->fscore_fns * sizeof(slg::FscoreFn);
-  p.cols = reinterpret_cast<const slg::FscoreColDev *>(base);
-  base += (size_t)b->fscore_cols * sizeof(slg::FscoreColDev);
+  p.cols = reinterpret_cast<const slg::ColumnDev *>(base);
+  base += (size_t)b->fscore_cols * sizeof(slg::ColumnDev);
   p.filters = reinterpret_cast<const uint32_t *const *>(base);
   constexpr uint32_t per_block = slg::kFscoreThreads / 64;
   const dim3 grid((b->n_slices + per_block - 1) / per_block), block(slg::kFscoreThreads);

@@ -46,7 +46,7 @@ struct FscoreParams {
   BoolFilterParams c;            // the slices, the candidates and q_scored (queries and terms: unused, null)
   const FscoreQuery *queries;    // [nq]
   const FscoreFn *fns;           // the functions of all queries
-  const FscoreColDev *cols;      // [fields of the batch][n_segs]
+  const ColumnDev *cols;         // [fields of the batch][n_segs]
   const uint32_t *const *filters;  // [filters of the batch][n_segs] reject bitmaps (bit set: the filter rejects)
 };
 
@@ -111,7 +111,7 @@ static __global__ void __launch_bounds__(kFscoreThreads) fscore_kernel(FscorePar
       if (kind != kFsWeight) {  // the doc's first value of the column
         typedef const __attribute__((address_space(1))) uint32_t *gu32_t;
         typedef const __attribute__((address_space(1))) double *gf64_t;
-        const FscoreColDev col = load_const(p.cols + ((size_t)rfl(fn.col) * p.c.n_segs + sl.seg));
+        const ColumnDev col = load_const(p.cols + ((size_t)rfl(fn.col) * p.c.n_segs + sl.seg));
         const uint64_t offs = uniform64((uint64_t)(uintptr_t)col.offs), vals = uniform64((uint64_t)(uintptr_t)col.vals);
         uint32_t first = doc, end = doc + 1u;
         if (offs != 0ull && has) {

@@ -20,6 +20,7 @@
 #include <memory>
 #include <mutex>
 #include <new>
+#include <optional>
 #include <stdexcept>
 #include <string>
 #include <utility>
@@ -501,7 +502,7 @@ struct slg_batch {
   std::vector<slg_agg_layout> agg_layout;  // [n_nodes]
   uint32_t agg_count_cells = 0, agg_stats_cells = 0;
   bool agg_lds = false;              // the tables fit SLG_AGG_LDS_BYTES
-  DevBuf d_agg_desc;                 // slg::AggNodeDev[n_nodes], then slg::AggColDev[n_nodes * n_segs]
+  DevBuf d_agg_desc;                 // slg::AggNodeDev[n_nodes], then slg::ColumnDev[n_nodes * n_segs]
   DevBuf d_agg_counts, d_agg_stats;  // u32[nq * count_cells], slg::AggStatDev[nq * stats_cells]
   // rescore batch (slg_batch_prepare_rescore): rescore_kernel runs behind the first pass's last kernel and
   // rewrites the first rows of every query in place (slg_rescore.hip)
@@ -528,14 +529,14 @@ struct slg_batch {
   uint32_t fscore_work = 0;  // queries with work (0: nothing is launched)
   bool fscore_full = false;  // some function needs ln / log1p / log2 / pow: the full instantiation
   uint32_t fscore_fns = 0, fscore_cols = 0;  // entries of the two tables behind the FscoreQuery records
-  DevBuf d_fscore_desc;      // slg::FscoreQuery[nq], FscoreFn[fscore_fns], FscoreColDev[fscore_cols], bitmap addresses
+  DevBuf d_fscore_desc;      // slg::FscoreQuery[nq], FscoreFn[fscore_fns], ColumnDev[fscore_cols], bitmap addresses
   // collapse batch (slg_batch_prepare_collapse): a plain, sorted or cursor batch; collapse_kernel runs behind its
   // last kernel and fills the side arrays from each query's rows, which it leaves as they are (slg_collapse.hip)
   bool collapse = false;
   uint32_t cl_groups = 0, cl_from = 0, cl_size = 0;  // group_limit, inner_from, inner_size
   uint32_t cl_lds_rows = 0;                          // rows the kernel's LDS arrays hold: a power of two >= k
   uint32_t cl_parts = 0, cl_score_parts = 0, cl_desc_parts = 0;  // the inner sort (0 parts: the batch's own order)
-  DevBuf d_cl_desc;  // slg::AggColDev[n_segs], then slg::SortColDev[kSortMaxParts * n_segs] of the inner sort
+  DevBuf d_cl_desc;  // slg::ColumnDev[n_segs], then slg::SortColDev[kSortMaxParts * n_segs] of the inner sort
   DevBuf d_cl_side;  // the arrays of slg_batch_fetch_collapse, back to back in its argument order
 };
 
@@ -681,6 +682,50 @@ inline void upload_image(DevBuf &dst, BufPool *pool, std::initializer_list<Image
   dst.alloc_pooled(pool, image.size());
   if (!image.empty()) SLG_HIP(hipMemcpy(dst.p, image.data(), image.size(), hipMemcpyHostToDevice));
 }
+
+// One host block of `words` 32-bit words for ONE D2H copy of a batch's results: a small block is pageable memory,
+// a large one a pinned image of the index's pool (why, with the measurement: slg_batch_fetch)
+constexpr size_t kPageableFetchBytes = 256u << 10;
+struct FetchBlock {
+  std::vector<uint32_t> pageable;
+  std::optional<ImageLease> lease;
+  uint32_t *p;
+  FetchBlock(BufPool &pool, size_t words) {
+    if (words * 4 <= kPageableFetchBytes) {
+      pageable.resize(words);
+      p = pageable.data();
+    } else {
+      lease.emplace(pool, words * 4);
+      p = static_cast<uint32_t *>(lease->p);
+    }
+  }
+};
+
+// what the kernels that walk a query's candidate regions share (the two selects, agg_kernel): the slices of each
+// query, their regions, and the tombstones and filters of the batch's state
+template <typename P>
+void fill_candidates(P &p, const slg_batch *b) {
+  const IndexState &S = *b->snap;
+  p.queries = b->d_queries;
+  p.slice_seg = b->d_slice_seg;
+  p.slice_cbeg = b->d_slice_cbeg.as<uint64_t>();
+  p.slice_ccnt = b->d_slice_ccnt.as<uint32_t>();
+  p.cand = b->d_cand.as<uint2>();
+  p.segs = S.d_segs.as<slg::SegDev>();
+  p.q_filter = b->d_q_filter.as<uint32_t>();
+  p.reject_table = S.d_reject_table.as<const uint32_t *>();
+  p.n_segs = (uint32_t)S.segs.size();
+}
+
+// slg_batch.hip: a sort spec against an index state: the column table [kSortMaxParts * n_segs] (part p of segment
+// s at p * n_segs + s; null rows for `_score` parts and beyond the spec) and the bits of the `_score` and the
+// descending parts.  Throws SLG_ERR_INVALID "<prefix>unknown sort field id in <part>I" and "<prefix>sort field N
+// has no column for segment S (added after the field was registered)"
+struct SortBinding {
+  std::vector<slg::SortColDev> cols;
+  uint32_t score_parts = 0, desc_parts = 0;
+};
+SortBinding bind_sort(const IndexState &S, const slg_sort_spec &spec, const std::string &prefix, const std::string &part);
 
 // what the launches of the two clause-filter kernels share (P: slg::BoolFilterParams, slg_clause.hpp): the
 // slices, the candidates and the term groups' tables of a bool or phrase batch

@@ -737,8 +737,8 @@ int slg_index_add_filter_trees(slg_index *ix, const slg_filter_tree *trees, uint
       base += fp.trees.size() * sizeof(slg::FilterTreeDev);
       p.nodes = reinterpret_cast<const slg::FilterNodeDev *>(base);
       base += fp.nodes.size() * sizeof(slg::FilterNodeDev);
-      p.cols = reinterpret_cast<const slg::FscoreColDev *>(base);
-      base += fp.cols.size() * sizeof(slg::FscoreColDev);
+      p.cols = reinterpret_cast<const slg::ColumnDev *>(base);
+      base += fp.cols.size() * sizeof(slg::ColumnDev);
       p.filters = reinterpret_cast<const uint32_t *const *>(base);
       base += fp.filters.size() * sizeof(void *);
       p.out = reinterpret_cast<uint32_t *const *>(base);

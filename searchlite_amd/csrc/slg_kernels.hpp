@@ -679,12 +679,8 @@ select_topk_kernel(SelectParams p) {
 // varying words — and bitonic-sorted by index.  The CURSOR instantiation (slg_batch_prepare_after with a
 // sort spec) drops in sweep 1 every accepted candidate whose key is <= the query's cursor key (the words of
 // kSortWords the host encoded from the cursor's values) as it drops a deleted one, so neither `matched` nor
-// the radix levels see it, and raises out_seen on an equal key.
-struct SortColDev {
-  const unsigned long long *key;  // [n_docs] u64 key of the part's order (0 for Missing docs)
-  const uint32_t *present;        // presence bitmap (bit d & 31 of word d >> 5)
-};
-
+// the radix levels see it, and raises out_seen on an equal key.  (SortColDev, kSortMaxParts, kSortWords:
+// slg_desc.hpp; the key itself: slg_wave.hpp sorted_key)
 struct SortedSelectParams {
   const QueryRef *queries;
   const uint32_t *slice_seg;
@@ -694,7 +690,7 @@ struct SortedSelectParams {
   const SegDev *segs;
   const uint32_t *q_filter;             // [nq] 0 = none, f + 1
   const uint32_t *const *reject_table;  // [n_filters * n_segs] reject bitmaps
-  const SortColDev *cols;               // [kSortMaxParts * n_segs]: part p of segment s at p * n_segs + s
+  const SortColDev *sort_cols;          // [kSortMaxParts * n_segs]: part p of segment s at p * n_segs + s
   uint32_t n_segs, n_parts;
   uint32_t score_parts;  // bit p: part p is `_score`
   uint32_t desc_parts;   // bit p: part p descends (applied here to `_score`; field columns come complemented)
@@ -710,35 +706,8 @@ struct SortedSelectParams {
   uint32_t *out_seen;      // [nq] 1: an accepted doc has the cursor's key (or no cursor)
 };
 
-constexpr uint32_t kSortMaxParts = 4;  // SLG_MAX_SORT_PARTS
-constexpr uint32_t kSortWords = 3 * kSortMaxParts + 2;
 constexpr uint32_t kSortedCap = 1024;  // keys sorted in LDS at a time (their varying words: <= 56 KB)
 constexpr uint32_t kSortedThreads = 512;
-
-__device__ __forceinline__ void sorted_key(const SortedSelectParams &p, uint32_t a, uint32_t seg, uint32_t doc,
-                                           uint32_t (&K)[kSortWords]) {
-#pragma unroll
-  for (uint32_t i = 0; i < kSortMaxParts; i++) {
-    uint32_t w0 = 0, w1 = 0, w2 = 0;
-    if (i < p.n_parts) {
-      if ((p.score_parts >> i) & 1u) {
-        w2 = ((p.desc_parts >> i) & 1u) ? ~a : a;
-      } else {
-        const SortColDev c = p.cols[(size_t)i * p.n_segs + seg];
-        const uint32_t pw = c.present[doc >> 5];
-        const unsigned long long v = c.key[doc];  // (0 for a Missing doc)
-        w0 = ((pw >> (doc & 31u)) & 1u) ^ 1u;
-        w1 = (uint32_t)(v >> 32);
-        w2 = (uint32_t)v;
-      }
-    }
-    K[3 * i] = w0;
-    K[3 * i + 1] = w1;
-    K[3 * i + 2] = w2;
-  }
-  K[kSortWords - 2] = seg;
-  K[kSortWords - 1] = doc;
-}
 
 // lexicographic compare of (K & mask) with a prefix: -1 below, 0 equal, 1 above
 __device__ __forceinline__ int sorted_cmp(const uint32_t (&K)[kSortWords], const uint32_t *pre, const uint32_t *dm) {

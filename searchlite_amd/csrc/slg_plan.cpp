@@ -1319,6 +1319,42 @@ void check_fscore(const slg_fscore_spec *spec, uint32_t nq) {
       throw SlgError(SLG_ERR_UNSUPPORTED, "fscore query " + std::to_string(q) + " has more than SLG_MAX_FSCORE_FUNCS functions");
 }
 
+// ---- registered aggregation fields (function_score, filter trees; aggregations and collapse on the device side) ----
+const FscoreFieldView &agg_field(const std::vector<FscoreFieldView> &fields, int32_t id, const std::string &before,
+                                 const std::string &after) {
+  const auto it = std::find_if(fields.begin(), fields.end(), [id](const FscoreFieldView &v) { return v.id == id; });
+  PLAN_REQUIRE(it != fields.end(), before + "unknown agg field id " + std::to_string(id) + after);
+  return *it;
+}
+const slg::ColumnDev *agg_field_rows(const FscoreFieldView &field, uint32_t n_segs, const std::string &before,
+                                     const std::string &after) {
+  for (uint32_t s = 0; s < n_segs; s++)
+    PLAN_REQUIRE(s < field.per_seg.size() && field.per_seg[s].vals != nullptr,
+                 before + "agg field " + std::to_string(field.id) + " has no column for segment " + std::to_string(s) +
+                     " (added after the field was registered)" + after);
+  return field.per_seg.data();
+}
+
+namespace {
+// the row of `id` in a table whose rows are numbered in order of first use
+uint32_t row_of(std::vector<int32_t> &rows, int32_t id) {
+  const auto it = std::find(rows.begin(), rows.end(), id);
+  if (it != rows.end()) return (uint32_t)(it - rows.begin());
+  rows.push_back(id);
+  return (uint32_t)rows.size() - 1u;
+}
+// the two tables of such rows: the columns of the (checked) fields and the reject bitmaps of the filters, [row][n_segs]
+void fill_tables(const std::vector<FscoreFieldView> &fields, const std::vector<int32_t> &used_fields,
+                 const uint32_t *const *reject, const std::vector<int32_t> &used_filters, uint32_t n_segs,
+                 std::vector<slg::ColumnDev> &cols, std::vector<const uint32_t *> &filters) {
+  for (const int32_t id : used_fields) {
+    const slg::ColumnDev *rows = agg_field_rows(agg_field(fields, id, "", ""), n_segs, "", "");
+    cols.insert(cols.end(), rows, rows + n_segs);
+  }
+  for (const int32_t f : used_filters) filters.insert(filters.end(), reject + (size_t)f * n_segs, reject + ((size_t)f + 1) * n_segs);
+}
+}  // namespace
+
 void plan_fscore(const std::vector<FscoreFieldView> &fields, const uint32_t *const *reject, const char *filter_live,
                  size_t n_filters, uint32_t n_segs, uint32_t nq, const slg_fscore_spec &spec, FscorePlan &out) {
   out = FscorePlan{};
@@ -1327,12 +1363,6 @@ void plan_fscore(const std::vector<FscoreFieldView> &fields, const uint32_t *con
   const uint32_t f_base = spec.q_fn_offsets[0];
   std::vector<int32_t> used_fields, used_filters;  // the rows of the two tables, in order of first use
   std::string unsupported;                         // (reported behind every invalid argument)
-  auto row_of = [](std::vector<int32_t> &rows, int32_t id) {
-    const auto it = std::find(rows.begin(), rows.end(), id);
-    if (it != rows.end()) return (uint32_t)(it - rows.begin());
-    rows.push_back(id);
-    return (uint32_t)rows.size() - 1u;
-  };
   for (uint32_t q = 0; q < nq; q++) {
     const std::string in_q = " in fscore query " + std::to_string(q);
     const uint32_t f0 = spec.q_fn_offsets[q], nf = spec.q_fn_offsets[q + 1] - f0;
@@ -1358,14 +1388,10 @@ void plan_fscore(const std::vector<FscoreFieldView> &fields, const uint32_t *con
       }
       if (kind != SLG_FSCORE_WEIGHT) {
         const int32_t id = spec.f_field[f];
-        const auto it = std::find_if(fields.begin(), fields.end(), [id](const FscoreFieldView &v) { return v.id == id; });
-        PLAN_REQUIRE(it != fields.end(), "unknown agg field id " + std::to_string(id) + in_q);
-        PLAN_REQUIRE(!it->keyword, "agg field " + std::to_string(id) + " is a keyword field" + in_q);
-        for (uint32_t s = 0; s < n_segs; s++)
-          PLAN_REQUIRE(s < it->per_seg.size() && it->per_seg[s].vals != nullptr,
-                       "agg field " + std::to_string(id) + " has no column for segment " + std::to_string(s) +
-                           " (added after the field was registered)");
-        if (it->non_finite && unsupported.empty())
+        const FscoreFieldView &fv = agg_field(fields, id, "", in_q);
+        PLAN_REQUIRE(!fv.keyword, "agg field " + std::to_string(id) + " is a keyword field" + in_q);
+        agg_field_rows(fv, n_segs, "", "");
+        if (fv.non_finite && unsupported.empty())
           unsupported = "agg field " + std::to_string(id) + " holds a non-finite value (CPU path)" + in_q;
         fn.col = row_of(used_fields, id);
       }
@@ -1387,14 +1413,7 @@ void plan_fscore(const std::vector<FscoreFieldView> &fields, const uint32_t *con
     }
   }
   if (!unsupported.empty()) throw SlgError(SLG_ERR_UNSUPPORTED, unsupported);
-  out.cols.reserve(used_fields.size() * n_segs);
-  for (const int32_t id : used_fields) {
-    const auto it = std::find_if(fields.begin(), fields.end(), [id](const FscoreFieldView &v) { return v.id == id; });
-    out.cols.insert(out.cols.end(), it->per_seg.begin(), it->per_seg.begin() + n_segs);
-  }
-  out.filters.reserve(used_filters.size() * n_segs);
-  for (const int32_t f : used_filters)
-    for (uint32_t s = 0; s < n_segs; s++) out.filters.push_back(reject[(size_t)f * n_segs + s]);
+  fill_tables(fields, used_fields, reject, used_filters, n_segs, out.cols, out.filters);
 }
 
 // ---- filter trees --------------------------------------------------------------------------------------
@@ -1452,12 +1471,6 @@ void plan_filter_trees(const std::vector<FscoreFieldView> &fields, const uint32_
   out.trees.reserve(n_trees);
   std::vector<int32_t> used_fields, used_filters;  // the rows of the two tables, in order of first use
   std::string unsupported;                         // (reported behind every invalid argument)
-  auto row_of = [](std::vector<int32_t> &rows, int32_t id) {
-    const auto it = std::find(rows.begin(), rows.end(), id);
-    if (it != rows.end()) return (uint32_t)(it - rows.begin());
-    rows.push_back(id);
-    return (uint32_t)rows.size() - 1u;
-  };
   constexpr double k2p53 = 9007199254740992.0;
   constexpr int64_t i2p53 = (int64_t)1 << 53;
   for (uint32_t t = 0; t < n_trees; t++) {
@@ -1477,31 +1490,27 @@ void plan_filter_trees(const std::vector<FscoreFieldView> &fields, const uint32_
         nd.row = row_of(used_filters, f);
       } else if (n.kind != SLG_FILTER_NOT) {
         const int32_t id = n.field;
-        const auto it = std::find_if(fields.begin(), fields.end(), [id](const FscoreFieldView &v) { return v.id == id; });
-        PLAN_REQUIRE(it != fields.end(), "unknown agg field id " + std::to_string(id) + in_t);
-        for (uint32_t s = 0; s < n_segs; s++)
-          PLAN_REQUIRE(s < it->per_seg.size() && it->per_seg[s].vals != nullptr,
-                       "agg field " + std::to_string(id) + " has no column for segment " + std::to_string(s) +
-                           " (added after the field was registered)" + in_t);
+        const FscoreFieldView &fv = agg_field(fields, id, "", in_t);
+        agg_field_rows(fv, n_segs, "", in_t);
         nd.row = row_of(used_fields, id);
         if (n.kind == SLG_FILTER_KEYWORD_IN) {
-          PLAN_REQUIRE(it->keyword, "agg field " + std::to_string(id) + " is not a keyword field" + in_t);
+          PLAN_REQUIRE(fv.keyword, "agg field " + std::to_string(id) + " is not a keyword field" + in_t);
           nd.bits = (uint32_t)out.words.size();
-          out.words.resize(out.words.size() + ((size_t)it->n_ords + 31u) / 32u, 0u);
+          out.words.resize(out.words.size() + ((size_t)fv.n_ords + 31u) / 32u, 0u);
           for (uint32_t j = 0; j < n.n_ords_in; j++) {
             const uint32_t o = tr.ords[n.ord_begin + j];
-            PLAN_REQUIRE(o < it->n_ords, "ordinal " + std::to_string(o) + " >= n_ords of agg field " +
+            PLAN_REQUIRE(o < fv.n_ords, "ordinal " + std::to_string(o) + " >= n_ords of agg field " +
                                              std::to_string(id) + in_t);
             out.words[nd.bits + (o >> 5)] |= 1u << (o & 31u);
           }
         } else {
-          PLAN_REQUIRE(!it->keyword, "agg field " + std::to_string(id) + " is a keyword field" + in_t);
+          PLAN_REQUIRE(!fv.keyword, "agg field " + std::to_string(id) + " is a keyword field" + in_t);
           if (n.kind == SLG_FILTER_RANGE_F64) {
             nd.lo = n.lo_f;
             nd.hi = n.hi_f;
           } else {
-            PLAN_REQUIRE(it->from_i64, "agg field " + std::to_string(id) + " was not registered from i64 values" + in_t);
-            if (unsupported.empty() && (it->i64_rounded || (it->any_value && (it->vmin < -k2p53 || it->vmax > k2p53))))
+            PLAN_REQUIRE(fv.from_i64, "agg field " + std::to_string(id) + " was not registered from i64 values" + in_t);
+            if (unsupported.empty() && (fv.i64_rounded || (fv.any_value && (fv.vmin < -k2p53 || fv.vmax > k2p53))))
               unsupported = "agg field " + std::to_string(id) + " holds an i64 value beyond +-2^53 (CPU path)" + in_t;
             // every stored value is an integer within +-2^53: a bound on the far side of it selects what the
             // clamped one does; a lower bound above 2^53 (an upper one below -2^53) selects nothing, which the
@@ -1515,14 +1524,7 @@ void plan_filter_trees(const std::vector<FscoreFieldView> &fields, const uint32_
     }
   }
   if (!unsupported.empty()) throw SlgError(SLG_ERR_UNSUPPORTED, unsupported);
-  out.cols.reserve(used_fields.size() * n_segs);
-  for (const int32_t id : used_fields) {
-    const auto it = std::find_if(fields.begin(), fields.end(), [id](const FscoreFieldView &v) { return v.id == id; });
-    out.cols.insert(out.cols.end(), it->per_seg.begin(), it->per_seg.begin() + n_segs);
-  }
-  out.filters.reserve(used_filters.size() * n_segs);
-  for (const int32_t f : used_filters)
-    for (uint32_t s = 0; s < n_segs; s++) out.filters.push_back(reject[(size_t)f * n_segs + s]);
+  fill_tables(fields, used_fields, reject, used_filters, n_segs, out.cols, out.filters);
 }
 
 // ---- sort keys of numeric fast fields ----------------------------------------------------------

@@ -186,7 +186,7 @@ void check_fscore(const slg_fscore_spec *spec, uint32_t nq);
 struct FscoreFieldView {
   int32_t id = 0;
   bool keyword = false, non_finite = false;
-  std::vector<slg::FscoreColDev> per_seg;  // [n_segs]
+  std::vector<slg::ColumnDev> per_seg;     // [n_segs]
   // what only plan_filter_trees reads: the keyword dictionary's size; whether the numeric column was registered
   // from i64 values, the finite minimum and maximum recorded then (when any_value), and whether an i64 value beyond
   // +-2^53 was seen (2^53 + 1 is stored as 2^53: the minimum and maximum alone do not show it)
@@ -194,6 +194,14 @@ struct FscoreFieldView {
   bool from_i64 = false, any_value = false, i64_rounded = false;
   double vmin = 0.0, vmax = 0.0;
 };
+// The lookup of every batch kind that reads a registered aggregation column, in the two steps between which a
+// kind checks the field's type.  agg_field: the view of field `id`, or SLG_ERR_INVALID "<before>unknown agg field
+// id N<after>".  agg_field_rows: its columns of segments 0 .. n_segs - 1, or SLG_ERR_INVALID "<before>agg field N
+// has no column for segment S (added after the field was registered)<after>" for the first segment without one.
+const FscoreFieldView &agg_field(const std::vector<FscoreFieldView> &fields, int32_t id, const std::string &before,
+                                 const std::string &after);
+const slg::ColumnDev *agg_field_rows(const FscoreFieldView &field, uint32_t n_segs, const std::string &before,
+                                     const std::string &after);
 // The tables of a checked spec against an index state's fields and filters.  reject: the state's flattened
 // [filter * n_segs + seg] reject bitmaps (device addresses), filter_live [n_filters] as BatchIn's.  Throws
 // SLG_ERR_INVALID for an unknown field or filter id, a keyword column, a field without a column for a segment;
@@ -201,7 +209,7 @@ struct FscoreFieldView {
 struct FscorePlan {
   std::vector<slg::FscoreQuery> queries;   // [nq]
   std::vector<slg::FscoreFn> fns;          // the spec's functions, in its order
-  std::vector<slg::FscoreColDev> cols;     // [fields the batch names][n_segs]
+  std::vector<slg::ColumnDev> cols;        // [fields the batch names][n_segs]
   std::vector<const uint32_t *> filters;   // [filters the batch names][n_segs]
   uint32_t n_work = 0;                     // queries with work (0: nothing is launched)
   bool full = false;                       // some function needs ln / log1p / log2 / pow
@@ -223,7 +231,7 @@ void check_filter_trees(const slg_filter_tree *trees, uint32_t n_trees);
 struct FilterTreePlan {
   std::vector<slg::FilterTreeDev> trees;   // [n_trees]
   std::vector<slg::FilterNodeDev> nodes;   // every tree's nodes, in its order
-  std::vector<slg::FscoreColDev> cols;     // [fields the trees name][n_segs]
+  std::vector<slg::ColumnDev> cols;        // [fields the trees name][n_segs]
   std::vector<const uint32_t *> filters;   // [filters the trees name][n_segs]
   std::vector<uint32_t> words;             // one bit set of ceil(n_ords / 32) words per KEYWORD_IN node
 };

@@ -255,6 +255,23 @@ struct slgp_fscore_field {
   uint32_t keyword, non_finite;
   const uint8_t *seg_has, *seg_dense;
 };
+}  // extern "C"
+// the view of a described field (slgp_fscore_field, slgp_filter_field): its id, kind and made-up column addresses
+template <typename F>
+static slgplan::FscoreFieldView described_field(const F &f, uint32_t n_segs) {
+  slgplan::FscoreFieldView v;
+  v.id = f.id;
+  v.keyword = f.keyword != 0;
+  v.per_seg.assign(n_segs, slg::ColumnDev{nullptr, nullptr});
+  for (uint32_t s = 0; s < n_segs; s++) {
+    if (!f.seg_has[s]) continue;
+    const uint64_t a = ((uint64_t)(f.id + 1) << 32) | ((uint64_t)s << 8);
+    v.per_seg[s].vals = reinterpret_cast<const void *>((uintptr_t)(a | 1u));
+    if (!f.seg_dense[s]) v.per_seg[s].offs = reinterpret_cast<const uint32_t *>((uintptr_t)(a | 2u));
+  }
+  return v;
+}
+extern "C" {
 int slgp_plan_fscore(const slgp_fscore_field *fields, uint32_t n_fields, const char *filter_live, uint32_t n_filters,
                      uint32_t n_segs, uint32_t nq, const slg_fscore_spec *spec, uint32_t *queries, uint32_t *fns,
                      uint32_t fns_cap, uint64_t *cols, uint32_t cols_cap, uint64_t *filters, uint32_t filters_cap,
@@ -263,16 +280,8 @@ int slgp_plan_fscore(const slgp_fscore_field *fields, uint32_t n_fields, const c
     slgplan::check_fscore(spec, nq);
     std::vector<slgplan::FscoreFieldView> views(n_fields);
     for (uint32_t i = 0; i < n_fields; i++) {
-      views[i].id = fields[i].id;
-      views[i].keyword = fields[i].keyword != 0;
+      views[i] = described_field(fields[i], n_segs);
       views[i].non_finite = fields[i].non_finite != 0;
-      views[i].per_seg.assign(n_segs, slg::FscoreColDev{nullptr, nullptr});
-      for (uint32_t s = 0; s < n_segs; s++) {
-        if (!fields[i].seg_has[s]) continue;
-        const uint64_t a = ((uint64_t)(fields[i].id + 1) << 32) | ((uint64_t)s << 8);
-        views[i].per_seg[s].vals = reinterpret_cast<const double *>((uintptr_t)(a | 1u));
-        if (!fields[i].seg_dense[s]) views[i].per_seg[s].offs = reinterpret_cast<const uint32_t *>((uintptr_t)(a | 2u));
-      }
     }
     std::vector<const uint32_t *> reject((size_t)n_filters * n_segs);
     for (uint32_t f = 0; f < n_filters; f++)
@@ -281,13 +290,13 @@ int slgp_plan_fscore(const slgp_fscore_field *fields, uint32_t n_fields, const c
             reinterpret_cast<const uint32_t *>((uintptr_t)(((uint64_t)(f + 1) << 32) | ((uint64_t)s << 8) | 3u));
     slgplan::FscorePlan fp;
     slgplan::plan_fscore(views, reject.data(), filter_live, n_filters, n_segs, nq, *spec, fp);
-    static_assert(sizeof(slg::FscoreQuery) == 32 && sizeof(slg::FscoreFn) == 64 && sizeof(slg::FscoreColDev) == 16,
+    static_assert(sizeof(slg::FscoreQuery) == 32 && sizeof(slg::FscoreFn) == 64 && sizeof(slg::ColumnDev) == 16,
                   "the words the caller reads");
     if (queries && nq) std::memcpy(queries, fp.queries.data(), (size_t)nq * sizeof(slg::FscoreQuery));
     if (fns && fp.fns.size() <= fns_cap && !fp.fns.empty())
       std::memcpy(fns, fp.fns.data(), fp.fns.size() * sizeof(slg::FscoreFn));
     if (cols && fp.cols.size() <= cols_cap && !fp.cols.empty())
-      std::memcpy(cols, fp.cols.data(), fp.cols.size() * sizeof(slg::FscoreColDev));
+      std::memcpy(cols, fp.cols.data(), fp.cols.size() * sizeof(slg::ColumnDev));
     if (filters && fp.filters.size() <= filters_cap && !fp.filters.empty())
       std::memcpy(filters, fp.filters.data(), fp.filters.size() * sizeof(void *));
     if (counts) {
@@ -328,20 +337,12 @@ int slgp_plan_filter_trees(const slgp_filter_field *fields, uint32_t n_fields, c
     slgplan::check_filter_trees(trees, n_trees);
     std::vector<slgplan::FscoreFieldView> views(n_fields);
     for (uint32_t i = 0; i < n_fields; i++) {
-      views[i].id = fields[i].id;
-      views[i].keyword = fields[i].keyword != 0;
+      views[i] = described_field(fields[i], n_segs);
       views[i].n_ords = fields[i].n_ords;
       views[i].from_i64 = fields[i].from_i64 != 0;
       views[i].any_value = fields[i].any_value != 0;
       views[i].vmin = fields[i].vmin;
       views[i].vmax = fields[i].vmax;
-      views[i].per_seg.assign(n_segs, slg::FscoreColDev{nullptr, nullptr});
-      for (uint32_t s = 0; s < n_segs; s++) {
-        if (!fields[i].seg_has[s]) continue;
-        const uint64_t a = ((uint64_t)(fields[i].id + 1) << 32) | ((uint64_t)s << 8);
-        views[i].per_seg[s].vals = reinterpret_cast<const double *>((uintptr_t)(a | 1u));
-        if (!fields[i].seg_dense[s]) views[i].per_seg[s].offs = reinterpret_cast<const uint32_t *>((uintptr_t)(a | 2u));
-      }
     }
     std::vector<const uint32_t *> reject((size_t)n_filters * n_segs, nullptr);
     for (uint32_t f = 0; f < n_filters; f++)
@@ -354,7 +355,7 @@ int slgp_plan_filter_trees(const slgp_filter_field *fields, uint32_t n_fields, c
     if (tree_rows) std::memcpy(tree_rows, fp.trees.data(), fp.trees.size() * sizeof(slg::FilterTreeDev));
     if (nodes && fp.nodes.size() <= nodes_cap) std::memcpy(nodes, fp.nodes.data(), fp.nodes.size() * sizeof(slg::FilterNodeDev));
     if (cols && fp.cols.size() <= cols_cap && !fp.cols.empty())
-      std::memcpy(cols, fp.cols.data(), fp.cols.size() * sizeof(slg::FscoreColDev));
+      std::memcpy(cols, fp.cols.data(), fp.cols.size() * sizeof(slg::ColumnDev));
     if (filters && fp.filters.size() <= filters_cap && !fp.filters.empty())
       std::memcpy(filters, fp.filters.data(), fp.filters.size() * sizeof(void *));
     if (words && fp.words.size() <= words_cap && !fp.words.empty())

@@ -1,8 +1,9 @@
 // slg_wave.hpp — device-side building blocks shared by every kernel of the library: small wave
 // helpers (readlanes, scans, fences, one LDS atomic per wave: hist_add_by_bin, wave_compact_slot), the
 // register top-k WaveTopK (insert, the stream-and-insert loop `offer`, the result row `store_row`), the
-// buffered top-k BufTopK, and the three scalar rules of a vector score (missing_vector_score,
-// similarity_from_sum, blend) that the rerank and the vector-search kernels restate from the reference.
+// buffered top-k BufTopK, the readers of a registered column (column_range, sorted_key), and the three scalar
+// rules of a vector score (missing_vector_score, similarity_from_sum, blend) that the rerank and the
+// vector-search kernels restate from the reference.
 // Device code and two launch helpers (launch_with_lds, with_kregs), no kernels: the scoring units
 // (slg_score_inst.hip) include it without compiling a copy of the host-launched kernels of slg_kernels.hpp.
 #pragma once
@@ -258,6 +259,41 @@ __device__ __forceinline__ uint32_t ordered_score(float x) {
 }
 __device__ __forceinline__ uint64_t cand_key(float score, uint32_t doc) {
   return ((uint64_t)ordered_score(score) << 32) | (uint32_t)~doc;
+}
+
+// ---- registered columns (slg_desc.hpp: ColumnDev, SortColDev) -------------------------------------
+// the values of `doc` in a column are vals[a .. e)
+__device__ __forceinline__ void column_range(const ColumnDev &c, const uint32_t doc, uint32_t &a, uint32_t &e) {
+  a = c.offs ? c.offs[doc] : doc;
+  e = c.offs ? c.offs[doc + 1u] : doc + 1u;
+}
+// The sort key of (seg, doc) under the sort that p describes (its layout: slg_kernels.hpp, the field-sorted
+// select): p.sort_cols[part * p.n_segs + seg], p.n_parts, and bit i of p.score_parts / p.desc_parts for part i.
+// a: the doc's ordered score, what a `_score` part holds
+template <typename P>
+__device__ __forceinline__ void sorted_key(const P &p, const uint32_t a, const uint32_t seg, const uint32_t doc,
+                                           uint32_t (&K)[kSortWords]) {
+#pragma unroll
+  for (uint32_t i = 0; i < kSortMaxParts; i++) {
+    uint32_t w0 = 0, w1 = 0, w2 = 0;
+    if (i < p.n_parts) {
+      if ((p.score_parts >> i) & 1u) {
+        w2 = ((p.desc_parts >> i) & 1u) ? ~a : a;
+      } else {
+        const SortColDev c = p.sort_cols[(size_t)i * p.n_segs + seg];
+        const uint32_t pw = c.present[doc >> 5];
+        const unsigned long long v = c.key[doc];  // (0 for a Missing doc)
+        w0 = ((pw >> (doc & 31u)) & 1u) ^ 1u;
+        w1 = (uint32_t)(v >> 32);
+        w2 = (uint32_t)v;
+      }
+    }
+    K[3 * i] = w0;
+    K[3 * i + 1] = w1;
+    K[3 * i + 2] = w2;
+  }
+  K[kSortWords - 2] = seg;
+  K[kSortWords - 1] = doc;
 }
 
 // ---- the scalar rules of a vector score (rerank and vector-only search) -------------------------

@@ -286,6 +286,33 @@ def test_lifecycle_and_errors(gpu, oracle, W):
             assert np.array_equal(got[name], want[name]), name
 
 
+def test_inner_sort_field_predates_the_added_segment(gpu, W):
+    """the world of the added-segment case above (the three segments, then one of 50 docs that holds no query term),
+    queries 0 .. 3: an inner sort over a sort field registered before the fourth segment is refused, as the column
+    is; over the field registered again the arrays are the reference's for the rows, which all lie in the first three
+    segments"""
+    from searchlite_amd import _native as N
+    nq, k = 4, 65
+    offs = W["offs"][:nq + 1]
+    terms4 = np.concatenate([W["terms"], np.full_like(W["terms"][:, :1], CW.NO_TERM)], axis=1)
+    q = (offs, np.ascontiguousarray(terms4[:offs[nq]]), W["w"][:offs[nq]])
+    col, n_ords = W["columns"]["seven"]
+    low = W["fields"]["low"][0]
+    want = R.expected_arrays(*CW.as_arrays(all_rows(W, None)[:nq], k), col, 5, 0, 2, [("low", "asc")], None, W["fields"])
+    with gpu.GpuIndex([copy.copy(s) for s in W["segs"]]) as ix:
+        before = ix.add_sort_field(low, np.int64)
+        ix.add_segment(random_segment(np.random.default_rng(5), 50, 40, 25, k1=0.9, b=0.4))
+        spec = dict(field=ix.add_agg_keyword_field(col + [None], n_ords), group_limit=5, inner_from=0, inner_size=2)
+        with pytest.raises(N.SlgError) as ei:
+            ix.prepare(*q, k, collapse=dict(spec, inner_sort=[(before, "asc")]))
+        assert ei.value.code == N.ERR_INVALID, ei.value.msg
+        assert "collapse: sort field" in ei.value.msg and "no column for segment" in ei.value.msg, ei.value.msg
+        again = ix.add_sort_field(low + [[[0]] * 50], np.int64)
+        with ix.prepare(*q, k, collapse=dict(spec, inner_sort=[(again, "asc")])) as b:
+            b.run()
+            R.assert_same_arrays(b.collapse_groups(), want, "inner sort over the field registered again")
+
+
 def test_recipes_collapse_quick_by_cuisine(gpu, oracle):
     """recipes/queries/collapse-quick-by-cuisine.json as far as this library goes: the golden queries of
     recipes.npz under `total_time_minutes` asc, collapsed on `cuisine` (28 keys, every doc single-valued), limit 5

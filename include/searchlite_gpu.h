@@ -36,7 +36,11 @@
  * alternatives), not in rescore queries.  Field collapsing (slg_batch_prepare_collapse): one hit per ordinal of a
  * keyword column over the k <= SLG_MAX_COLLAPSE_ROWS rows of a plain, sorted or cursor batch, with up to
  * SLG_MAX_INNER_HITS inner hits per group; not with aggregations, rescore, bool, phrase, function_score, hybrid or
- * vector-only batches, sharded or coalesced.
+ * vector-only batches, sharded or coalesced.  Term expansion (slg_index_set_terms, slg_expand_batch): the fuzzy
+ * option of a request and Prefix / Wildcard nodes are expanded against the segments' term dictionaries on the
+ * device into ordinary slg_query terms, keys in the reference's order; terms or patterns of up to
+ * SLG_MAX_EXPAND_CHARS chars, max_expansions up to SLG_MAX_EXPANSIONS.  Regex nodes, unscored groups, a query that
+ * folds to more than SLG_MAX_QUERY_TERMS terms, and expansion inside sharded or coalesced paths stay on the CPU.
  */
 #ifndef SEARCHLITE_GPU_H
 #define SEARCHLITE_GPU_H
@@ -1436,6 +1440,89 @@ int slg_search_batch_collapse(slg_index *index, uint32_t nq, const uint32_t *q_o
                               uint32_t *group_row, uint32_t *group_ord, uint32_t *group_size, uint32_t *group_doc,
                               uint32_t *group_seg, float *group_score, uint32_t *inner_count, uint32_t *inner_row,
                               uint32_t *inner_doc, uint32_t *inner_seg, float *inner_score);
+
+/* ---- term expansion: fuzzy, prefix and wildcard (api/reader.rs:1119-1283, 1394-1465) -----------------
+ * A request whose terms must be expanded against the term dictionary (SearchRequest.fuzzy, QueryNode::Prefix,
+ * QueryNode::Wildcard) becomes a plain batch once its terms are known: slg_expand_batch returns, per source term,
+ * the keys the reference's expansion yields, in its order, as rows of per-segment term ids with their edit
+ * distance; the caller weights them (fuzzy: boost * 1 / (distance + 1) in f32, distance_weight, :977-979; prefix
+ * and wildcard: boost), folds equal keys of a query by summing (:2971-2983), gives all expansions of a source term
+ * that term's plan leaf and prepares an ordinary batch.  Scoring is untouched.
+ *
+ * DICTIONARIES.  slg_index_set_terms attaches segment seg's dictionary: key_offsets is uint32_t[n_terms + 1] over
+ * key_bytes, key i the UTF-8 "field:term" key of term id i of the segment's CSR (n_terms = slg_segment_desc.n_terms).
+ * The arrays are borrowed for the call.  The library sorts the keys by bytes (the identity for files written by
+ * searchlite, whose dictionary is a BTreeMap, util/fst.rs:25-33), keeps the sorted position -> term id map and a
+ * host copy, and stages sorted bytes, offsets, map and a char count per key (u8, saturating) on the device.  It
+ * builds the next index state as slg_index_set_positions does: prepared batches keep theirs;
+ * slg_index_update_deleted keeps the dictionaries; a segment added later has none until it is set;
+ * slg_index_remove_segment drops its dictionary.  SLG_ERR_INVALID: NULL arrays, seg out of range, decreasing
+ * offsets, duplicate keys, a key without ':', invalid UTF-8.
+ *
+ * REQUESTS.  field and term are UTF-8 with byte lengths (an embedded NUL is a byte like any other: the structs
+ * carry lengths, nothing is NUL-terminated); term is already analysed by the caller, as expand_term_groups hands
+ * it on (:1020-1099).  Lengths, prefixes and edits are counted in Unicode scalar values, never bytes.  "The
+ * range of P" below is terms_with_prefix("field:" + P): the segment's keys that start with it, in byte order; the
+ * key "field:" itself is always skipped (:1187, :1257, :1431).
+ *
+ * FUZZY (:1394-1465).  Key 0 is the exact key "field:term" at distance 0, also when no segment holds it (a row
+ * of SLG_NO_TERM).  A term of fewer than min_length chars, max_expansions == 0, or max_edits == 0 (:1140-1143):
+ * that is all.  max_edits is clamped to 2.  Then, segment by segment and over the range of the term's first
+ * min(prefix_length, chars of the term) chars: skip a candidate equal to the term, one whose char count differs
+ * from the term's by more than max_edits, one whose Levenshtein distance (bounded_levenshtein, :981-1018: unit
+ * insert / delete / substitute, a transposition is 2) exceeds max_edits, and a key already seen; anything else is
+ * a new expansion with its distance.  The cap is GLOBAL: everything stops at max_expansions new keys.
+ *
+ * PREFIX (:1164-1210) and WILDCARD (:1212-1283).  Every key of the range of the prefix (wildcard: of the
+ * pattern's literal prefix, the chars before its first '*' or '?') whose term matches (prefix: always; wildcard:
+ * the whole term against the pattern, '*' = any run of chars, '?' = one char, neither matches U+000A because
+ * the reference compiles them to the regex '.', every other char is literal) and that no EARLIER segment
+ * yielded is an expansion at distance 0.  The cap is PER SEGMENT and counts only such new keys: a key past the cap
+ * in segment 0 can still enter through segment 1.  max_expansions == 0: no keys.
+ *
+ * OUTPUT.  out_offsets [n_reqs + 1]: request r's keys are rows out_offsets[r] .. out_offsets[r + 1] - 1 of
+ * out_term_ids ([rows x n_segs], laid out as q_term_ids: SLG_NO_TERM where the segment lacks the key) and
+ * out_distance ([rows] u8).  key_capacity = the rows the two arrays hold.  Size query: out_term_ids and
+ * out_distance both NULL fills out_offsets only.  The call is synchronous (as slg_search_batch) and its answer
+ * is the same from run to run: the device's rows come from ballots and prefix counts in dictionary order.
+ *
+ * The device scans (slg_expand.hpp: per request and segment the first R keys of the range that pass the
+ * request's predicate, in dictionary order, with their distance); the host runs the reference's sequential loop
+ * over those rows (seen set, caps, term-id rows).  R = max_expansions for fuzzy and (seg + 1) * max_expansions
+ * for prefix / wildcard is all the reference can consume in a segment.
+ *
+ * SLG_ERR_INVALID: index, reqs (n_reqs > 0) or out_offsets NULL; a struct_size other than
+ * sizeof(slg_expand_req); an unknown kind; field or term NULL with a non-zero length; field or term not valid
+ * UTF-8; a segment without a dictionary; out_term_ids or out_distance NULL but not both; key_capacity too small.
+ * SLG_ERR_UNSUPPORTED (CPU path): a term or pattern of more than SLG_MAX_EXPAND_CHARS chars; max_expansions above
+ * SLG_MAX_EXPANSIONS.  NOT BUILT: QueryNode::Regex; unscored (score == false) groups; a query whose folded list
+ * exceeds SLG_MAX_QUERY_TERMS (the scoring kernels' cap is untouched); expansion inside sharded or coalesced
+ * paths (expand first, then submit the plain query). */
+enum { SLG_EXPAND_FUZZY = 0, SLG_EXPAND_PREFIX = 1, SLG_EXPAND_WILDCARD = 2 };
+#define SLG_MAX_EXPAND_CHARS 128u  /* chars of a term or pattern: they sit in LDS beside the scan */
+#define SLG_MAX_EXPANSIONS 1024u   /* max_expansions of a request */
+/* the scan's geometry (the boundaries its tests sit on): lanes of a wave = candidate keys looked at together,
+ * threads of a workgroup, keys of a range one workgroup scans */
+#define SLG_EXPAND_WAVE 64u
+#define SLG_EXPAND_WORKGROUP 256u
+#define SLG_EXPAND_CHUNK 1024u
+typedef struct slg_expand_req {
+  uint32_t struct_size;    /* sizeof(slg_expand_req) */
+  int32_t kind;            /* SLG_EXPAND_* */
+  const char *field;       /* UTF-8, field_len bytes */
+  const char *term;        /* UTF-8, term_len bytes: the analysed term, the prefix or the wildcard pattern */
+  uint32_t field_len, term_len;
+  uint32_t max_expansions;
+  uint32_t max_edits, prefix_length, min_length; /* fuzzy only (FuzzyOptions) */
+} slg_expand_req;
+int slg_index_set_terms(slg_index *index, uint32_t seg, const char *key_bytes, const uint32_t *key_offsets);
+int slg_expand_batch(slg_index *index, const slg_expand_req *reqs, uint32_t n_reqs, uint32_t *out_offsets,
+                     uint32_t key_capacity, uint32_t *out_term_ids, uint8_t *out_distance);
+/* DIAGNOSTIC ONLY, not part of the product path (tools/expand_time.py reads it; a caller has no use for it):
+ * where the calling thread's last slg_expand_batch spent its time, in ms, by the host clock: the device scan
+ * (uploads, both kernels, the copy back, the wait) and the host merge.  The figures are per thread, not per index:
+ * `index` is only checked for NULL.  Either pointer may be NULL. */
+int slg_expand_phase_ms(slg_index *index, double *scan_ms, double *merge_ms);
 
 #ifdef __cplusplus
 }

@@ -105,6 +105,16 @@ pub const SLG_AGG_STATS: i32 = 3;
     pub field: i32, pub group_limit: u32, pub inner_from: u32, pub inner_size: u32,
     pub inner_sort: *const slg_sort_spec,
 }
+// term expansion (SearchRequest::fuzzy, QueryNode::Prefix / ::Wildcard): one source term, prefix or pattern;
+// field and term are UTF-8 with byte lengths, max_edits / prefix_length / min_length are FuzzyOptions
+#[repr(C)] pub struct slg_expand_req {
+    pub struct_size: u32, pub kind: i32, pub field: *const c_char, pub term: *const c_char,
+    pub field_len: u32, pub term_len: u32, pub max_expansions: u32,
+    pub max_edits: u32, pub prefix_length: u32, pub min_length: u32,
+}
+pub const SLG_EXPAND_FUZZY: i32 = 0;
+pub const SLG_EXPAND_PREFIX: i32 = 1;
+pub const SLG_EXPAND_WILDCARD: i32 = 2;
 #[repr(C)] pub struct slg_stats { pub scored_docs: u64, pub candidates_examined: u64, pub postings_advanced: u64 }
 #[repr(C)] pub struct slg_query { pub n_terms: u32, pub term_ids: *const u32, pub weights: *const c_float }
 
@@ -322,6 +332,12 @@ extern "C" {
         out_matched: *mut u64) -> c_int;
     // phrase queries: positions per segment, then slg_batch_prepare_bool plus the phrase spec (bool_spec may be null)
     pub fn slg_index_set_positions(index: *mut slg_index, seg: u32, pos_offsets: *const u64, positions: *const u32) -> c_int;
+    // term expansion: a dictionary per segment, then fuzzy / prefix / wildcard requests -> rows of term ids
+    pub fn slg_index_set_terms(index: *mut slg_index, seg: u32, key_bytes: *const c_char, key_offsets: *const u32) -> c_int;
+    pub fn slg_expand_batch(index: *mut slg_index, reqs: *const slg_expand_req, n_reqs: u32, out_offsets: *mut u32,
+        key_capacity: u32, out_term_ids: *mut u32, out_distance: *mut u8) -> c_int;
+    // diagnostic only (the timing tool's split of the last call on this thread into scan and merge): not routed
+    pub fn slg_expand_phase_ms(index: *mut slg_index, scan_ms: *mut f64, merge_ms: *mut f64) -> c_int;
     pub fn slg_batch_prepare_phrase(index: *mut slg_index, nq: u32, q_offsets: *const u32, q_term_ids: *const u32,
         q_weights: *const c_float, plans: *const slg_score_plans, q_filter: *const i32,
         sort: *const slg_sort_spec, bool_spec: *const slg_bool_spec, phrases: *const slg_phrase_spec, k: u32,

@@ -51,6 +51,10 @@ FILTER_KEYWORD_IN, FILTER_RANGE_F64, FILTER_RANGE_I64, FILTER_ID, FILTER_AND, FI
 MAX_FILTER_NODES, MAX_FILTER_DEPTH, MAX_FILTER_TREES = 64, 16, 64
 MAX_COLLAPSE_ROWS = 4096
 MAX_INNER_HITS = 64
+EXPAND_FUZZY, EXPAND_PREFIX, EXPAND_WILDCARD = 0, 1, 2
+MAX_EXPAND_CHARS = 128
+MAX_EXPANSIONS = 1024
+EXPAND_WAVE, EXPAND_WORKGROUP, EXPAND_CHUNK = 64, 256, 1024  # the scan's geometry (SLG_EXPAND_*)
 
 
 class SlgError(RuntimeError):
@@ -190,6 +194,13 @@ class FilterNode(C.Structure):
 class FilterTree(C.Structure):
     """slg_filter_tree: the nodes of one tree and the ordinals its KEYWORD_IN nodes point into."""
     _fields_ = [("n_nodes", C.c_uint32), ("nodes", C.c_void_p), ("n_ords", C.c_uint32), ("ords", C.c_void_p)]
+
+
+class ExpandReq(C.Structure):
+    """slg_expand_req: one term / prefix / wildcard pattern to expand (slg_expand_batch)."""
+    _fields_ = [("struct_size", C.c_uint32), ("kind", C.c_int32), ("field", C.c_char_p), ("term", C.c_char_p),
+                ("field_len", C.c_uint32), ("term_len", C.c_uint32), ("max_expansions", C.c_uint32),
+                ("max_edits", C.c_uint32), ("prefix_length", C.c_uint32), ("min_length", C.c_uint32)]
 
 
 class Ticket(C.Structure):
@@ -348,6 +359,9 @@ def load():
         "slg_batch_prepare_collapse": (vp, [vp, u32, vp, vp, vp, vp, vp, vp, vp, vp, u32, i32]),
         "slg_batch_fetch_collapse": (i32, [vp] * 15),
         "slg_search_batch_collapse": (i32, [vp, u32, vp, vp, vp, vp, vp, vp, vp, vp, u32, i32] + [vp] * 18),
+        "slg_index_set_terms": (i32, [vp, u32, vp, vp]),
+        "slg_expand_batch": (i32, [vp, vp, u32, vp, u32, vp, vp]),
+        "slg_expand_phase_ms": (i32, [vp, vp, vp]),
     }
     for name, (res, args) in sigs.items():
         if os.environ.get("SLG_LIB_TAG") and not hasattr(L, name):

@@ -202,6 +202,11 @@ struct PosSegDev {          // per segment of an index state (slg_index_set_posi
   const uint32_t *offs;     // [P + 1] first position of each posting, in the UNPADDED posting order; or nullptr
   const uint32_t *pos;      // [offs[P]] positions, non-decreasing inside a posting
 };
+struct ExpandSegDev {           // per segment of an index state (slg_index_set_terms): its dictionary in byte order
+  const unsigned char *bytes;   // the sorted keys back to back; or nullptr
+  const uint32_t *offs;         // [n + 1]
+  const uint8_t *nchars;        // [n] chars of each key; 255: 255 or more
+};
 struct PhraseTerm {
   uint64_t off;    // posting offset inside the segment arrays (padded layout, as BoolTerm::off)
   uint64_t ubase;  // the list's first posting in the unpadded order (= term_offsets[term]): PosSegDev::offs index

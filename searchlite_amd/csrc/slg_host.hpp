@@ -27,6 +27,7 @@
 #include <vector>
 
 #include "slg_desc.hpp"
+#include "slg_expand_merge.hpp"
 #include "slg_plan.hpp"
 
 namespace slghost __attribute__((visibility("hidden"))) {
@@ -367,6 +368,14 @@ struct PosStore {
   DevBuf pos;   // u32[offs[P]]
 };
 
+// the term dictionary of a segment (slg_index_set_terms): the host copy the merge of slg_expand_batch reads and
+// what the scan reads on the device; shared by the states that hold it
+struct TermStore {
+  slgexpand::Dict dict;
+  DevBuf bytes, offs, map, nchars;  // sorted key bytes | u32[n + 1] | u32[n] sorted position -> term id | u8[n]
+  size_t device_bytes() const { return bytes.bytes + offs.bytes + map.bytes + nchars.bytes; }
+};
+
 // One immutable state of the index (see "index updates" in searchlite_gpu.h).  Batches hold the state
 // they were prepared on; the index holds the current one.
 struct IndexState {
@@ -385,6 +394,8 @@ struct IndexState {
   std::map<int, std::shared_ptr<AggFieldData>> agg_fields;    // by id (ids are not reused)
   std::vector<std::shared_ptr<PosStore>> positions;           // [n_segs]; null = the segment has none
   DevBuf d_pos_segs;                                          // slg::PosSegDev[n_segs]
+  std::vector<std::shared_ptr<TermStore>> terms;              // [n_segs]; null = the segment has no dictionary
+  DevBuf d_term_segs;                                         // slg::ExpandSegDev[n_segs]
   ~IndexState() {
     // kernels of already-destroyed batches, or rerank calls on the index stream, may still read the
     // tables: retiring a state is rare (one per update), so wait for the device once

@@ -278,6 +278,12 @@ void finish_state(slg_index *ix, IndexState &s) {
     if (s.positions[i]) pd[i] = slg::PosSegDev{s.positions[i]->offs.as<uint32_t>(), s.positions[i]->pos.as<uint32_t>()};
   s.d_pos_segs.alloc(std::max<size_t>(n_segs, 1) * sizeof(slg::PosSegDev), &ix->pool);
   if (n_segs) SLG_HIP(hipMemcpy(s.d_pos_segs.p, pd.data(), n_segs * sizeof(slg::PosSegDev), hipMemcpyHostToDevice));
+  s.terms.resize(n_segs);  // (the same for the dictionaries)
+  std::vector<slg::ExpandSegDev> td(n_segs, slg::ExpandSegDev{nullptr, nullptr, nullptr});
+  for (size_t i = 0; i < n_segs; i++)
+    if (s.terms[i]) td[i] = slg::ExpandSegDev{s.terms[i]->bytes.as<unsigned char>(), s.terms[i]->offs.as<uint32_t>(), s.terms[i]->nchars.as<uint8_t>()};
+  s.d_term_segs.alloc(std::max<size_t>(n_segs, 1) * sizeof(slg::ExpandSegDev), &ix->pool);
+  if (n_segs) SLG_HIP(hipMemcpy(s.d_term_segs.p, td.data(), n_segs * sizeof(slg::ExpandSegDev), hipMemcpyHostToDevice));
   std::vector<uint32_t> base(n_segs + 1, 0u);
   uint64_t acc = 0;
   for (size_t i = 0; i < n_segs; i++) {
@@ -309,6 +315,7 @@ std::unique_ptr<IndexState> copy_state(const IndexState &cur) {
   n->sort_fields = cur.sort_fields;
   n->agg_fields = cur.agg_fields;
   n->positions = cur.positions;
+  n->terms = cur.terms;
   for (auto &vf : cur.vfields) {  // the per-state table d_vsegs is rebuilt: own object, shared stores
     auto c = std::make_shared<VecFieldHost>();
     c->dim = vf->dim;
@@ -369,12 +376,16 @@ void reshape_per_segment(IndexState &ns, Op op) {
   }
   for (auto &vf : ns.vfields) op(vf->per_seg);  // (the field objects of a new state are fresh copies)
   op(ns.positions);  // (the state's own vector; the stores are shared)
+  op(ns.terms);
 }
 
 size_t state_device_bytes(const IndexState &s) {
   size_t n = s.d_segs.bytes + s.d_vsegs.bytes + s.d_reject_table.bytes + s.d_doc_base.bytes + s.d_pos_segs.bytes;
   for (auto &ps : s.positions)
     if (ps) n += ps->offs.bytes + ps->pos.bytes;
+  n += s.d_term_segs.bytes;
+  for (auto &ts : s.terms)
+    if (ts) n += ts->device_bytes();
   for (auto &sh : s.segs) n += sh->device_bytes() + sh->store->device_bytes();
   for (auto &f : s.filters)
     if (f)
@@ -871,6 +882,30 @@ int slg_index_set_positions(slg_index *ix, uint32_t seg, const uint64_t *pos_off
       SLG_HIP(hipMemcpy(store->offs.p, offs.data(), (P + 1) * 4, hipMemcpyHostToDevice));
       if (total) SLG_HIP(hipMemcpy(store->pos.p, positions, total * 4, hipMemcpyHostToDevice));
       ns.positions[seg] = std::move(store);
+    });
+  });
+}
+
+// ---- the term dictionary of a segment (term expansion; util/fst.rs:25-33) ------------------------
+int slg_index_set_terms(slg_index *ix, uint32_t seg, const char *key_bytes, const uint32_t *key_offsets) {
+  return guarded([&] {
+    SLG_REQUIRE(ix != nullptr, "index is NULL");
+    update_state(ix, false, [&](const IndexState &cur, IndexState &ns) {
+      SLG_REQUIRE(seg < cur.segs.size(), "no such segment");
+      SLG_REQUIRE(key_bytes != nullptr, "set_terms: key_bytes is NULL");
+      ns.terms.resize(cur.segs.size());
+      auto store = std::make_shared<TermStore>();
+      slgexpand::build_dict(cur.segs[seg]->n_terms, key_bytes, key_offsets, store->dict);  // (host only, before any device work)
+      const slgexpand::Dict &d = store->dict;
+      const auto stage = [&](DevBuf &b, const void *src, size_t bytes) {
+        b.alloc(std::max<size_t>(bytes, 4), &ix->pool);
+        if (bytes) SLG_HIP(hipMemcpy(b.p, src, bytes, hipMemcpyHostToDevice));
+      };
+      stage(store->bytes, d.bytes.data(), d.bytes.size());
+      stage(store->offs, d.offs.data(), d.offs.size() * 4);
+      stage(store->map, d.map.data(), d.map.size() * 4);
+      stage(store->nchars, d.nchars.data(), d.nchars.size());
+      ns.terms[seg] = std::move(store);
     });
   });
 }

@@ -105,6 +105,99 @@ class GpuIndex:
         N.check(self._lib.slg_index_set_positions(self._h, seg, _ptr(po), _ptr(ps)))
         self.segments[seg].pos_offsets, self.segments[seg].positions = po, ps
 
+    def set_terms(self, seg: int, keys: Sequence[str]) -> None:
+        """The term dictionary of segment `seg` (slg_index_set_terms): keys[i] is the "field:term" key of term id
+        i.  expand() needs one for every segment."""
+        raw = [k.encode("utf-8") if isinstance(k, str) else bytes(k) for k in keys]
+        offs = np.zeros(len(raw) + 1, dtype=np.uint32)
+        np.cumsum([len(r) for r in raw], out=offs[1:])
+        blob = np.frombuffer(b"".join(raw) + b"\0", dtype=np.uint8)  # (one spare byte: never an empty array)
+        N.check(self._lib.slg_index_set_terms(self._h, seg, _ptr(blob), _ptr(offs)))
+
+    def set_terms_from_segments(self) -> None:
+        """set_terms for every segment from its host dictionary (Segment.term_dict)."""
+        for i, s in enumerate(self.segments):
+            if s.term_dict is None:
+                raise KeyError(f"segment {i} has no term dictionary")
+            keys = [None] * s.n_terms
+            for k, t in s.term_dict.items():
+                keys[t] = k
+            self.set_terms(i, keys)
+
+    @classmethod
+    def from_directory(cls, path: str, device: int = 0, tuning: Optional[dict] = None, **load) -> "GpuIndex":
+        """The segments of a searchlite index directory (index_files.load_index(path, **load)), staged with their
+        term dictionaries."""
+        from .index_files import load_index
+        ix = cls(load_index(path, **load).segments, device=device, tuning=tuning)
+        try:
+            ix.set_terms_from_segments()
+        except Exception:
+            ix.close()
+            raise
+        return ix
+
+    def expand(self, requests) -> List[Tuple[np.ndarray, np.ndarray]]:
+        """slg_expand_batch: requests = expand_request() dicts (or anything with their keys) -> per request
+        (term_id_rows u32[n_keys, n_segs], distances u8[n_keys]), keys in the reference's order."""
+        n = len(requests)
+        reqs = (N.ExpandReq * max(n, 1))()
+        keep = []
+        for i, r in enumerate(requests):
+            f = r["field"].encode("utf-8") if isinstance(r["field"], str) else bytes(r["field"])
+            t = r["term"].encode("utf-8") if isinstance(r["term"], str) else bytes(r["term"])
+            keep += [f, t]
+            reqs[i] = N.ExpandReq(C.sizeof(N.ExpandReq), int(r["kind"]), f, t, len(f), len(t),
+                                  int(r["max_expansions"]), int(r.get("max_edits", 0)),
+                                  int(r.get("prefix_length", 0)), int(r.get("min_length", 0)))
+        offs = np.zeros(n + 1, dtype=np.uint32)
+        # the most keys the requests can yield: one call if that is a small array, else the size query first
+        cap = max(sum(1 + r.max_expansions if r.kind == N.EXPAND_FUZZY else self.n_segs * r.max_expansions
+                      for r in reqs[:n]), 1)
+        if cap * self.n_segs > (1 << 24):
+            N.check(self._lib.slg_expand_batch(self._h, reqs, n, _ptr(offs), 0, None, None))
+            cap = max(int(offs[n]), 1)
+        ids = np.zeros((cap, self.n_segs), dtype=np.uint32)
+        dist = np.zeros(cap, dtype=np.uint8)
+        N.check(self._lib.slg_expand_batch(self._h, reqs, n, _ptr(offs), cap, _ptr(ids), _ptr(dist)))
+        return [(ids[int(offs[i]):int(offs[i + 1])].copy(), dist[int(offs[i]):int(offs[i + 1])].copy())
+                for i in range(n)]
+
+    def expand_phase_ms(self) -> Tuple[float, float]:
+        """Diagnostic only (tools/expand_time.py): (device scan, host merge) of this thread's last expand(), in ms
+        (slg_expand_phase_ms)."""
+        a, b = C.c_double(0), C.c_double(0)
+        N.check(self._lib.slg_expand_phase_ms(self._h, C.addressof(a), C.addressof(b)))
+        return a.value, b.value
+
+    def expanded_queries(self, queries: Sequence[str], default_field: str, fuzzy: Optional[dict] = None,
+                         boost: float = 1.0):
+        """The fuzzy expansion of a batch of query strings, folded into the arrays of a plain batch with plans.
+        Every analysed term of a query is one source term and one plan leaf (summed); its expansions
+        (expand(), FuzzyOptions `fuzzy`: max_edits 1, prefix_length 1, max_expansions 50, min_length 3 by default)
+        weigh boost * the term's own boost * 1 / (distance + 1) in f32 (distance_weight, api/reader.rs:977-979) and go
+        to its leaf; equal
+        keys inside a query fold by summing and keep their first leaf (:2971-2983).  A query that folds to more
+        than SLG_MAX_QUERY_TERMS terms raises SlgError(ERR_UNSUPPORTED).
+        -> (q_offsets, q_terms[n, n_segs], q_weights, plans) with plans the q_leaf / q_plan / q_tie / q_nleaves
+        keywords of search_plan()."""
+        fz = dict(max_edits=1, prefix_length=1, max_expansions=50, min_length=3)
+        fz.update(fuzzy or {})
+        sources = []  # (query, "field:term", the term's own boost)
+        for qi, q in enumerate(queries):
+            sources += [(qi, key, tb) for key, tb in parse_query_terms(q, default_field)]
+        reqs = [expand_request(N.EXPAND_FUZZY, key.split(":", 1)[0], key.split(":", 1)[1], **fz) for _, key, _ in sources]
+        rows = self.expand(reqs) if reqs else []
+        return fold_expansions(len(queries), [qi for qi, _, _ in sources], [key for _, key, _ in sources], rows,
+                               self.n_segs, [np.float32(boost) * np.float32(tb) for _, _, tb in sources], queries)
+
+    def search_fuzzy(self, queries: Sequence[str], default_field: str, k: int, fuzzy: Optional[dict] = None,
+                     strategy: int = Wand, boost: float = 1.0):
+        """A batch of query strings under SearchRequest.fuzzy: expanded_queries(), then the ordinary batch with
+        plans -> (doc, seg, score, count)."""
+        offs, terms, w, plans = self.expanded_queries(queries, default_field, fuzzy, boost)
+        return self.search_plan(offs, terms, w, k, strategy=strategy, **plans)
+
     @property
     def generation(self) -> int:
         return int(self._lib.slg_index_generation(self._h))
@@ -704,6 +797,61 @@ class GpuIndex:
         N.check(self._lib.slg_merge_shards_device(self._h, n_shards, nq, k, d_doc, d_seg, d_score,
                                                   d_count, seg_stride, d_out_doc, d_out_seg,
                                                   d_out_score, d_out_count))
+
+
+def expand_request(kind: int, field: str, term: str, max_expansions: int, max_edits: int = 0, prefix_length: int = 0,
+                   min_length: int = 0) -> dict:
+    """One request of GpuIndex.expand(): kind N.EXPAND_FUZZY (term: the analysed term; the FuzzyOptions),
+    N.EXPAND_PREFIX (term: the prefix) or N.EXPAND_WILDCARD (term: the pattern)."""
+    return dict(kind=kind, field=field, term=term, max_expansions=max_expansions, max_edits=max_edits,
+                prefix_length=prefix_length, min_length=min_length)
+
+
+def fold_expansions(nq: int, source_query, source_key, rows, n_segs: int, boost=1.0, names=None):
+    """Expansions into the arrays of a plain batch with plans.  Source term i belongs to query source_query[i]
+    (ascending), has the exact key source_key[i] and expanded to rows[i] = (term_id_rows, distances); it is one leaf
+    of its query.  A key's weight is boost * 1 / (distance + 1) in f32 (boost: one for all, or one per source term);
+    equal keys of a query fold by summing and
+    keep their first leaf (api/reader.rs:2971-2983); leaves a fold left without a term are dropped.
+    -> (q_offsets, q_terms, q_weights, plans dict for search_plan)."""
+    offs = [0]
+    terms, weights, leaves, nleaves = [], [], [], []
+    boosts = np.broadcast_to(np.asarray(boost, dtype=np.float32), (len(source_query),))
+    i = 0
+    for q in range(nq):
+        slot = {}   # key identity -> index into this query's lists
+        q_rows, q_w, q_leaf = [], [], []
+        leaf = 0
+        while i < len(source_query) and source_query[i] == q:
+            ids, dist = rows[i]
+            for r in range(len(dist)):
+                present = bool((ids[r] != N.NO_TERM).any())
+                # a key no segment holds can only be the source's own exact key (row 0)
+                ident = ids[r].tobytes() if present else ("absent", source_key[i])
+                w = boosts[i] * (np.float32(1.0) / (np.float32(int(dist[r])) + np.float32(1.0)))
+                if ident in slot:
+                    q_w[slot[ident]] = np.float32(q_w[slot[ident]] + w)
+                else:
+                    slot[ident] = len(q_rows)
+                    q_rows.append(ids[r])
+                    q_w.append(np.float32(w))
+                    q_leaf.append(leaf)
+            leaf += 1
+            i += 1
+        if len(q_rows) > N.MAX_QUERY_TERMS:
+            name = f" ({names[q]!r})" if names is not None else ""
+            raise N.SlgError(N.ERR_UNSUPPORTED, f"query {q}{name} folds to {len(q_rows)} terms, more than "
+                                                f"SLG_MAX_QUERY_TERMS = {N.MAX_QUERY_TERMS}: CPU path")
+        dense = {l: j for j, l in enumerate(sorted(set(q_leaf)))}
+        terms += q_rows
+        weights += q_w
+        leaves += [dense[l] for l in q_leaf]
+        nleaves.append(len(dense))
+        offs.append(len(terms))
+    q_terms = np.array(terms, dtype=np.uint32).reshape(-1, n_segs)
+    plans = dict(q_leaf=np.array(leaves, dtype=np.uint32), q_plan=np.full(nq, N.PLAN_SUM, dtype=np.uint32),
+                 q_tie=np.zeros(nq, dtype=np.float32), q_nleaves=np.array(nleaves, dtype=np.uint32))
+    return np.array(offs, dtype=np.uint32), q_terms, np.array(weights, dtype=np.float32), plans
 
 
 def shard_unique_id() -> bytes:

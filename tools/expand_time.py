@@ -1,0 +1,171 @@
+"""Time of term expansion (slg_expand_batch) at config 2's scale: a Zipf-like vocabulary of 2^18 words generated
+here (word of rank r = term id r of the 1M-doc Zipf segment), one segment, and a batch of 1024 three-term queries
+under the default FuzzyOptions (1 edit, prefix 1, 50 expansions, min length 3), then the same with prefix_length 0.
+Per batch, mean of `reps` calls after two warm-up calls, `rounds` times over so the spread shows:
+  * slg_expand_batch: the whole call by the host clock (the call ends in a stream synchronise), and its own split
+    into the device scan (uploads, both kernels, the copy back, the wait) and the host merge (slg_expand_phase_ms);
+  * the same expansions by the C++ restatement of the reference's loop (csrc/slg_expand_capi.cpp,
+    slgx_reference_expand: what a caller without the scan runs) on this box, at 1 and 16 threads; the 1-thread
+    prefix-0 figure is timed on every 8th request and multiplied by 8 (stated in the line);
+  * for context the plain scoring batch that follows (the source terms as a plain batch, k = 11): HIP events around
+    slg_batch_run, and search_fuzzy (8 expansions per term, so that every query stays under the scoring kernels' 32-term
+    cap) end to end through the Python layer, whose folding loop is most of that figure.
+The device's answer is compared with the restatement's before anything is timed.
+usage (GPU box): python tools/expand_time.py [reps] [rounds]"""
+import ctypes as C
+import json
+import os
+import sys
+import time
+
+import numpy as np
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import torch  # noqa: E402
+
+from searchlite_amd import build, corpus, searcher, _native as N  # noqa: E402
+
+reps = int(sys.argv[1]) if len(sys.argv) > 1 else 5
+rounds = int(sys.argv[2]) if len(sys.argv) > 2 else 3
+n_docs, vocab, nq, T = 1_000_000, 1 << 18, 1024, 3
+
+
+def make_vocabulary(n, seed=17):
+    """n distinct lowercase words, rank order: frequent words are short (2 .. 4 letters up to rank ~1000), rare
+    ones longer (up to 12), letters drawn with English-like weights"""
+    rng = np.random.default_rng(seed)
+    letters = np.array(list("etaoinshrdlcumwfgypbvkjxqz"))
+    p = np.array([12.7, 9.1, 8.2, 7.5, 7.0, 6.7, 6.3, 6.1, 6.0, 4.3, 4.0, 2.8, 2.8, 2.4, 2.4, 2.2, 2.0, 2.0, 1.9, 1.5, 1.0,
+                  0.8, 0.15, 0.15, 0.1, 0.07])
+    p /= p.sum()
+    m = 2 * n
+    mat, extra = rng.choice(26, size=(m, 12), p=p), rng.integers(0, 4, size=m)
+    words, seen = [], set()
+    for i in range(m):
+        if len(words) == n:
+            break
+        length = int(min(12, max(2, np.log2(len(words) + 4) * 0.55 + extra[i])))
+        w = "".join(letters[mat[i, :length]])
+        if w not in seen:
+            seen.add(w)
+            words.append(w)
+    assert len(words) == n
+    return words
+
+
+t0 = time.time()
+words = make_vocabulary(vocab)
+keys = ["body:" + w for w in words]
+seg = corpus.zipf_segment(n_docs, vocab, seed=42, n_threads=16)
+offs, terms, w = corpus.zipf_queries(nq, T, seed=7, vocab=vocab)
+ix = searcher.GpuIndex([seg])
+ix.set_stream(torch.cuda.current_stream().cuda_stream)
+ix.set_terms(0, keys)
+lens = np.array([len(x) for x in words])
+first = np.array([x[0] for x in words])
+print(json.dumps(dict(vocabulary=len(words), mean_chars=round(float(lens.mean()), 2), segments=1, docs=n_docs,
+                      queries=nq, terms_per_query=T,
+                      largest_prefix1_range=int(max((first == c).sum() for c in set(first.tolist()))),
+                      setup_s=round(time.time() - t0, 1))), flush=True)
+
+# the host restatement over the library's own host dictionary
+L = C.CDLL(build.build_plan_lib())
+L.slgx_dict_build.restype = C.c_void_p
+L.slgx_dict_build.argtypes = [C.c_uint32, C.c_void_p, C.c_void_p, C.c_char_p, C.c_uint32, C.c_void_p]
+L.slgx_reference_expand.restype = C.c_int
+L.slgx_reference_expand.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint32,
+                                    C.c_void_p, C.c_void_p, C.c_char_p, C.c_uint32]
+raw = [k.encode() for k in keys]
+koffs = np.zeros(len(raw) + 1, dtype=np.uint32)
+np.cumsum([len(r) for r in raw], out=koffs[1:])
+blob = np.frombuffer(b"".join(raw), dtype=np.uint8)
+err = C.create_string_buffer(256)
+hd = L.slgx_dict_build(len(raw), blob.ctypes.data, koffs.ctypes.data, err, 256, None)
+assert hd, err.value
+dicts = (C.c_void_p * 1)(hd)
+
+
+def c_reqs(reqs):
+    keep = []
+    arr = (N.ExpandReq * len(reqs))()
+    for i, r in enumerate(reqs):
+        f, t = r["field"].encode(), r["term"].encode()
+        keep += [f, t]
+        arr[i] = N.ExpandReq(C.sizeof(N.ExpandReq), r["kind"], f, t, len(f), len(t), r["max_expansions"], r["max_edits"],
+                             r["prefix_length"], r["min_length"])
+    return arr, keep
+
+
+def host_loop(reqs, n_threads, want_rows=False):
+    arr, keep = c_reqs(reqs)
+    o = np.zeros(len(reqs) + 1, dtype=np.uint32)
+    cap = len(reqs) * 51
+    ids = np.zeros((cap, 1), np.uint32) if want_rows else None
+    dist = np.zeros(cap, np.uint8) if want_rows else None
+    t = time.perf_counter()
+    rc = L.slgx_reference_expand(dicts, 1, arr, len(reqs), n_threads, o.ctypes.data, cap,
+                                 None if ids is None else ids.ctypes.data, None if dist is None else dist.ctypes.data, err, 256)
+    ms = (time.perf_counter() - t) * 1e3
+    assert rc == 0, err.value
+    return ms, o, ids, dist
+
+
+def scoring_context():
+    b = ix.prepare(offs, terms, w, 11, searcher.Wand)
+    try:
+        for _ in range(2):
+            b.run()
+        torch.cuda.synchronize()
+        a, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record()
+        for _ in range(10):
+            b.run()
+        e.record()
+        torch.cuda.synchronize()
+        return round(a.elapsed_time(e) / 10, 4)
+    finally:
+        b.close()
+
+
+for prefix_length in (1, 0):
+    fz = dict(max_edits=1, prefix_length=prefix_length, max_expansions=50, min_length=3)
+    reqs = [searcher.expand_request(N.EXPAND_FUZZY, "body", words[int(t)], **fz) for t in terms.reshape(-1)]
+    arr, keep = c_reqs(reqs)
+    o, out_ids, out_dist = np.zeros(len(reqs) + 1, np.uint32), np.zeros((len(reqs) * 51, 1), np.uint32), np.zeros(len(reqs) * 51, np.uint8)
+
+    def one_call():
+        N.check(ix._lib.slg_expand_batch(ix._h, arr, len(reqs), o.ctypes.data, len(out_dist), out_ids.ctypes.data,
+                                         out_dist.ctypes.data))
+    got = ix.expand(reqs)                                   # (also the first warm-up call)
+    _, ro, rids, rdist = host_loop(reqs, 16, want_rows=True)
+    for i, (ids, dist) in enumerate(got):                   # the same answer before any timing
+        assert ids[:, 0].tolist() == rids[ro[i]:ro[i + 1], 0].tolist() and dist.tolist() == rdist[ro[i]:ro[i + 1]].tolist(), i
+    n_keys = int(ro[-1])
+    one_call()
+    assert o.tolist() == ro.tolist()
+    for rnd in range(rounds):
+        call, scan, merge = [], [], []
+        for _ in range(reps):
+            t = time.perf_counter()
+            one_call()
+            call.append((time.perf_counter() - t) * 1e3)
+            s, m = ix.expand_phase_ms()
+            scan.append(s)
+            merge.append(m)
+        sub = reqs[::8] if prefix_length == 0 else reqs
+        cpu1 = host_loop(sub, 1)[0] * (len(reqs) / len(sub))
+        cpu16 = host_loop(reqs, 16)[0]
+        print(json.dumps(dict(round=rnd, prefix_length=prefix_length, requests=len(reqs), keys=n_keys,
+                              expand_call_ms=round(float(np.mean(call)), 3),
+                              device_scan_ms=round(float(np.mean(scan)), 3), host_merge_ms=round(float(np.mean(merge)), 3),
+                              cpu_loop_1_thread_ms=round(cpu1, 1), cpu_1_thread_timed_on="every 8th request, x8" if len(sub) != len(reqs) else "all requests",
+                              cpu_loop_16_threads_ms=round(cpu16, 1))), flush=True)
+
+plain_ms = scoring_context()
+queries = [" ".join(words[int(t)] for t in terms.reshape(-1)[q * T:(q + 1) * T]) for q in range(nq)]
+fz8 = dict(max_edits=1, prefix_length=1, max_expansions=8, min_length=3)   # (3 x 9 keys stay under the 32-term cap)
+ix.search_fuzzy(queries[:64], "body", 11, fz8)
+t = time.perf_counter()
+ix.search_fuzzy(queries, "body", 11, fz8)
+fuzzy_ms = round((time.perf_counter() - t) * 1e3, 1)
+print(json.dumps(dict(plain_scoring_batch_ms=plain_ms, search_fuzzy_8_expansions_python_host_ms=fuzzy_ms)), flush=True)

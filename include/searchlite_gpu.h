@@ -238,6 +238,15 @@ int slg_index_trim_pool(slg_index *index, uint64_t *freed_bytes_or_null);
 int slg_index_info(const slg_index *index, uint32_t *n_segs, uint64_t *n_postings,
                    uint64_t *device_bytes);
 
+/* The champion table of segment `seg` in the index's current state, as the query planner reads it (its host copy
+ * of what the staging kernel wrote; nothing is launched): out[n_terms * 68], one row of 68 floats per term, built
+ * over the term's live postings.  Entries 0..63: exact-rank lower bounds, descending: at least r + 1 live postings
+ * have an impact (weight 1) >= row[r]; row[0] is the list's exact maximum, the upper bound MaxScore classifies by;
+ * 0 where the list is shorter.  Entries 64..67: lower bounds of the impacts at ranks 128, 256, 512 and 1024 (0
+ * where no bound is known).  A segment without postings has an all-zero table.  SLG_ERR_INVALID for a NULL index,
+ * a NULL out or an unknown segment; SLG_ERR_UNSUPPORTED when the index was created with slg_tuning.champions = 0. */
+int slg_index_fetch_champions(const slg_index *index, uint32_t seg, float *out);
+
 /* ---- index updates (the reference's commit: api/writer.rs:106-240) -------------------------------
  * searchlite opens a fresh IndexReader per request (searchlite-http/src/lib.rs:640-643 ->
  * index/mod.rs:98-100 -> api/reader.rs:1887-1913), so a staged index must outlive readers and follow

@@ -355,6 +355,8 @@ extern "C" {
     pub fn slg_index_add_filter_trees(index: *mut slg_index, trees: *const slg_filter_tree, n_trees: u32,
         out_ids: *mut i32) -> c_int;
     pub fn slg_index_fetch_filter(index: *mut slg_index, filter_id: c_int, seg: u32, out_pass: *mut u8) -> c_int;
+    // diagnostic only (the planner's champion table of a segment, [n_terms * 68]): not routed
+    pub fn slg_index_fetch_champions(index: *const slg_index, seg: u32, out: *mut c_float) -> c_int;
     pub fn slg_batch_fscore_info(batch: *const slg_batch, out_variant: *mut u32, out_queries_with_work: *mut u32) -> c_int;
     pub fn slg_search_batch_fscore(index: *mut slg_index, nq: u32, q_offsets: *const u32, q_term_ids: *const u32,
         q_weights: *const c_float, plans: *const slg_score_plans, q_filter: *const i32,

@@ -257,6 +257,7 @@ def load():
         "slg_index_create": (vp, [vp, u32, i32]),
         "slg_index_destroy": (None, [vp]),
         "slg_index_info": (i32, [vp, vp, vp, vp]),
+        "slg_index_fetch_champions": (i32, [vp, u32, vp]),
         "slg_index_trim_pool": (i32, [vp, vp]),
         "slg_index_set_stream": (i32, [vp, vp]),
         "slg_index_update_deleted": (i32, [vp, u32, vp, f32]),

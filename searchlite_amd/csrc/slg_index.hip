@@ -582,6 +582,23 @@ int slg_index_info(const slg_index *ix, uint32_t *n_segs, uint64_t *n_postings,
   });
 }
 
+int slg_index_fetch_champions(const slg_index *ix, uint32_t seg, float *out) {
+  return guarded([&] {
+    SLG_REQUIRE(ix != nullptr, "index is NULL");
+    SLG_REQUIRE(out != nullptr, "out is NULL");
+    const auto st = const_cast<slg_index *>(ix)->snapshot();
+    SLG_REQUIRE(seg < st->segs.size(), "no such segment");
+    if (!ix->tune.champions)
+      throw SlgError(SLG_ERR_UNSUPPORTED, "index was created with slg_tuning.champions = 0");
+    const SegHost &sh = *st->segs[seg];
+    const size_t n = (size_t)sh.n_terms * slg::kChampions;
+    if (sh.champ.size() == n)
+      std::memcpy(out, sh.champ.data(), n * sizeof(float));
+    else  // (a segment without postings stages no table)
+      std::fill(out, out + n, 0.0f);
+  });
+}
+
 int slg_index_set_stream(slg_index *ix, void *hip_stream) {
   return guarded([&] {
     SLG_REQUIRE(ix != nullptr, "index is NULL");

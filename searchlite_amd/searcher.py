@@ -237,6 +237,14 @@ class GpuIndex:
                                          C.addressof(nbytes)))
         return {"n_segs": ns.value, "n_postings": npost.value, "device_bytes": nbytes.value}
 
+    def champions(self, seg: int) -> np.ndarray:
+        """The champion table of segment `seg` as the planner reads it (slg_index_fetch_champions):
+        f32[n_terms, 68]; row[0..63] exact-rank lower bounds (row[0] the exact maximum), row[64..67] lower
+        bounds of ranks 128, 256, 512 and 1024, over the live postings."""
+        out = np.zeros((int(self.segments[seg].n_terms), 68), dtype=np.float32)
+        N.check(self._lib.slg_index_fetch_champions(self._h, int(seg), out.ctypes.data))
+        return out
+
     def trim_pool(self) -> int:
         """Give the pooled work buffers of finished batches back to the runtime -> bytes freed."""
         freed = C.c_uint64()

@@ -80,6 +80,15 @@ def test_null_arguments_fail_cleanly(lib):
     lib.slg_batch_destroy(None)
 
 
+def test_fetch_champions_null_arguments(lib):
+    from searchlite_amd import _native as N
+    out = (C.c_float * 68)()
+    assert lib.slg_index_fetch_champions(None, 0, out) == N.ERR_INVALID
+    assert b"index is NULL" in lib.slg_last_error()
+    assert lib.slg_index_fetch_champions(None, 0, None) == N.ERR_INVALID
+    assert len(lib.slg_index_fetch_champions.argtypes) == 3
+
+
 def test_malformed_segment_is_rejected_before_touching_a_device(lib):
     import numpy as np
     from searchlite_amd import _native as N

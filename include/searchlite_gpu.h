@@ -120,8 +120,8 @@ typedef struct {
 /* query/wand.rs:45-50 QueryStats, per query, with brute_force's accounting (wand.rs:472,500-503)
  * applied to the work the device did:
  *   scored_docs = candidates_examined = distinct docs that got a score.  SLG_STRATEGY_BM25: every
- *     doc holding a query term (tombstoned docs included: accept() runs at top-k insertion) — the
- *     count brute_force reports.  SLG_STRATEGY_WAND / _BMW: the same when the batch runs unclassified
+ *     doc holding a query term (tombstoned docs included, and docs a doc filter or minimum_should_match
+ *     refuses: accept() runs at top-k insertion) — the count brute_force reports.  SLG_STRATEGY_WAND / _BMW: the same when the batch runs unclassified
  *     (slg_tuning.pruning: the default for queries of <= 8 terms unless block skipping pays); with the
  *     MaxScore classification kept, docs of the ESSENTIAL lists only (a doc found in non-essential
  *     lists alone is never scored);

@@ -588,6 +588,7 @@ score_uniform4_kernel(RoundScoreParams p_arg) {
       const uint2 me = have ? queue[lane] : make_uint2(kDocEnd, 0u);
       float acc = 0.0f;
       uint32_t first = 64u;
+      bool refused = false;  // min_match: the doc is scored (and counted) but not accepted
       auto sender = [&](const uint32_t at, float &sum) {
         const uint2 sq = queue[at];
         const uint32_t diff = sq.x ^ me.x;
@@ -644,15 +645,18 @@ score_uniform4_kernel(RoundScoreParams p_arg) {
           lo = hi;
         }
         acc = plan == 2u ? mx + plan_tie * (tot - mx) : tot;
-        if (need_many && present < min_match) first = 64u;  // not accepted: nobody owns it
+        refused = need_many && present < min_match;
       } else {
         for (uint32_t g = 0; g < n; g += 8) {
 #pragma unroll
           for (uint32_t l = 0; l < 8; l++) sender(g + l, acc);
         }
       }
-      const bool own = have && first == lane;
-      n_scored += (uint32_t)__popcll(__ballot(own));
+      // (slg_stats.scored_docs counts a doc the matcher refuses, like one a doc filter refuses: accept() runs at the
+      //  top-k insertion)
+      const bool owner = have && first == lane;
+      n_scored += (uint32_t)__popcll(__ballot(owner));
+      const bool own = owner && !refused;
       if (__ballot(own && acc >= threshold_score()) != 0ull) {
         touched = true;
         take_checked(own, acc, me.x);
@@ -733,8 +737,9 @@ score_uniform4_kernel(RoundScoreParams p_arg) {
           acc = plan == 2u ? mx + plan_tie * (tot - mx) : tot;
           present += leaf_hit ? 1u : 0u;
         }
-        const bool own = have && !lower && !(need_many && present < min_match);
-        n_scored += (uint32_t)__popcll(__ballot(own));
+        const bool owner = have && !lower;
+        n_scored += (uint32_t)__popcll(__ballot(owner));
+        const bool own = owner && !(need_many && present < min_match);
         if (__ballot(own && acc >= threshold_score()) != 0ull) {
           touched = true;
           take_checked(own, acc, me.x);

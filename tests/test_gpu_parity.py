@@ -566,7 +566,8 @@ def _skewed_segment(n_docs, lists):
 
 def test_clustered_list_makes_overfull_rounds(gpu, oracle):
     """The round planner cuts at strides of the longest list; a shorter list that is packed into
-    a narrow doc range then lands > 512 postings in one round (the streaming path)."""
+    a narrow doc range then lands more postings in one round than its 64 lanes of 8 hold, each list
+    padded to whole lanes (the streaming path)."""
     n = 400_000
     rng = np.random.default_rng(12)
     long_list = np.sort(rng.choice(n, size=60_000, replace=False))

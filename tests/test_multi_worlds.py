@@ -45,13 +45,15 @@ def lane_champions(seg):
 
 
 class WorldPlan:
-    """A world planned at (k, strategy): the planner's arrays, the model's trace over them, the counters it predicts."""
+    """A world planned at (k, strategy): the planner's arrays, the model's trace over them, the counters it predicts.
+    q_filter / filter_live: a doc filter per query, as Planned takes it; multi_trace False: the arrays alone (the worlds
+    of the few-term kernel, which tests/fewterm_model.py traces)."""
 
-    def __init__(self, lib, W, k, strategy, tuning=None, champs=None):
+    def __init__(self, lib, W, k, strategy, tuning=None, champs=None, q_filter=None, filter_live=b"", multi_trace=True):
         tune = tuning if tuning is not None else default_tuning(**W.tuning)
         champs = champs if champs is not None else [lane_champions(s) for s in W.segs]
         p = Planned(lib, W.segs, W.offs, W.terms, W.w, k, strategy=strategy, tuning=tune,
-                    plans=_family_plans(W.plans), champs=champs)
+                    plans=_family_plans(W.plans), champs=champs, q_filter=q_filter, filter_live=filter_live)
         assert p.h, (W.name, p.err)
         self.W, self.k, self.strategy = W, k, strategy
         self.facts = p.facts
@@ -60,6 +62,8 @@ class WorldPlan:
         p.close()
         self.nq = len(W.offs) - 1
         self.block_skip = bool(self.facts.pruned and self.facts.multi and tune.block_max)
+        if not multi_trace:
+            return
         self.traced = M.trace(W.segs, self.sqs, self.terms, self.block_skip)
         self.scored, self.skipped = M.counters(self.sqs, self.traced, self.nq)
 

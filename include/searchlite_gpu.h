@@ -29,8 +29,11 @@
  * a flat Sum / DisMax plan over a window of up to SLG_MAX_RESCORE_WINDOW first-pass rows, every score_mode; in
  * score order only, not on sorted, cursor, hybrid, vector-only, aggregation, sharded or coalesced batches.
  * Boolean queries (slg_batch_prepare_bool): must / should / must_not groups of terms and minimum_should_match
- * over up to SLG_MAX_BOOL_GROUPS groups, in score order or a field sort; not nested, not on
- * cursor, hybrid, aggregation, rescore, sharded or coalesced batches.  Phrase queries
+ * over up to SLG_MAX_BOOL_GROUPS groups, in score order or a field sort; not on
+ * cursor, hybrid, aggregation, rescore, sharded or coalesced batches.  Nested boolean matchers
+ * (slg_batch_prepare_bool_tree): a tree of bool / dis_max / query string / match_all nodes over term groups and
+ * registered filters (a bool's own filter list), up to SLG_MAX_BOOL_TREE_LEAVES leaves and
+ * SLG_MAX_BOOL_TREE_NODES nodes, where a bool batch runs; phrase leaves in a tree stay on the CPU.  Phrase queries
  * (slg_index_set_positions, slg_batch_prepare_phrase): phrase groups with a slop and per-field variants beside
  * the term groups of a bool batch, under the same limits; one term per phrase position (no position
  * alternatives), not in rescore queries.  Field collapsing (slg_batch_prepare_collapse): one hit per ordinal of a
@@ -1155,10 +1158,11 @@ int slg_search_batch_rescore(slg_index *index, uint32_t nq, const uint32_t *q_of
  * that decreases, skips a number or names a group the query does not have, a group without a term, an unknown
  * kind, a term id out of range, q_min_match > 1 in the plans.  SLG_ERR_UNSUPPORTED (CPU scorer): more than
  * SLG_MAX_BOOL_GROUPS groups or SLG_MAX_BOOL_TERMS clause terms in a query.  slg_batch_run_sharded* and
- * slg_batch_fetch_sharded refuse a bool batch with SLG_ERR_UNSUPPORTED.  Not built (CPU scorer): nested matchers
- * (a bool or dis_max as a child of bool), bool.filter other than through q_filter, and clause tables
- * on cursor, hybrid, aggregation, rescore, sharded and coalesced batches (none of their prepare calls takes a
- * bool spec).  Phrase children of a bool and the query string's quoted phrases: slg_batch_prepare_phrase below.
+ * slg_batch_fetch_sharded refuse a bool batch with SLG_ERR_UNSUPPORTED.  Nested matchers (a bool, dis_max or
+ * query string as a child of bool) and a bool's own filter list: slg_batch_prepare_bool_tree below.  Not built
+ * (CPU scorer): clause tables on cursor, hybrid, aggregation, rescore, sharded and coalesced batches (none of
+ * their prepare calls takes a bool spec).  Phrase children of a bool and the query string's quoted phrases:
+ * slg_batch_prepare_phrase below.
  * --------------------------------------------------------------------------------------------------------- */
 #define SLG_BOOL_MUST 0
 #define SLG_BOOL_SHOULD 1
@@ -1183,6 +1187,97 @@ int slg_search_batch_bool(slg_index *index, uint32_t nq, const uint32_t *q_offse
                           const slg_bool_spec *spec, uint32_t k, int strategy, uint32_t *out_doc, uint32_t *out_seg,
                           float *out_score, uint32_t *out_count, slg_stats *stats_or_null,
                           uint64_t *out_matched_or_null);
+
+/* ---------------------------------------------------------------------------------------------------------
+ * Nested boolean matchers: the matcher TREE of QueryEvaluator::matches_node (api/reader.rs:1485-1565), in which
+ * a `Bool` may hold `Bool`, `DisMax`, `QueryString` and `MatchAll` children and carries a `filter` list of its
+ * own — `bool{must:[..], should:[bool{..}, dis_max{..}]}`, a multi_match under a must, a negated sub-query.
+ *
+ * A query's matcher is a table of LEAVES and a table of NODES.
+ *
+ * Leaves.  A TERM GROUP is one or more clause terms and HOLDS a doc of segment s iff one of its terms has a
+ * posting of the doc in s (the bool batch's rule, term_group_matches); a term that is SLG_NO_TERM in a segment, or
+ * has df 0 there, has no posting there.  A FILTER LEAF is a registered filter id (slg_index_add_filter*,
+ * slg_index_add_filter_trees) and holds the doc iff the doc passes that filter in its segment; a filter with no
+ * bitmap for a segment (one added after the filter was registered) passes every doc there.  A registered bitmap
+ * carries its segment's tombstones, so a tombstoned doc passes no filter leaf: no row changes (tombstones apply
+ * on top anyway), only slg_stats.scored_docs sees it.  A query's leaves are numbered term groups first, filter
+ * leaves behind them.
+ *
+ * Nodes.  A node is a list of (child, kind) pairs, kind SLG_BOOL_MUST / _SHOULD / _MUST_NOT, and a min_should.
+ * Its value is
+ *     every MUST child true  &&  no MUST_NOT child true  &&  count(true SHOULD children) >= min_should.
+ * A child is a leaf or an EARLIER node: the node table is in post-order, a child's index is below its parent's,
+ * the last node is the root, and the root's value is the candidate's verdict.  Tombstones and q_filter apply on
+ * top, as in every batch.
+ *
+ * Every node kind of the reference folds into this form (the caller folds; searchlite_amd/booltree.py does it):
+ *   Bool         its must / should / must_not children with their kinds, its `filter` list as MUST filter leaves,
+ *                min_should = minimum_should_match with the default rule (:1553-1561) applied: 0 without should
+ *                children, 1 when must and filter are both empty, else 0.
+ *   DisMax       all children SHOULD, min_should 1 (an empty DisMax: no children, min_should 1 — never true).
+ *   QueryString  not-groups MUST_NOT, term groups SHOULD, min_should = minimum_should_match.unwrap_or(1) when it
+ *                has term groups, else 0; no groups at all: no children, min_should 1 — never true (:1491-1496).
+ *   MatchAll     no children, min_should 0.
+ *   a matcher that is one Term: one node with that leaf as a MUST child.
+ *   Phrase leaves are not built in a tree: the caller refuses them (SLG_ERR_UNSUPPORTED).
+ *
+ * Everything else is the bool batch's, unchanged.  Clause terms are independent of the scored terms; only docs of
+ * the scored lists are candidates; an accepted doc has the exact score of the first pass, bit for bit, under any
+ * score plan and either scoring kernel; a query without a node is left as it is, and such queries mix with others
+ * in a batch; slg_stats.scored_docs = the count of the batch without a matcher minus the docs the matcher
+ * rejected; a sorted batch's matched counts see survivors only; the plans' q_min_match must be NULL, 0 or 1; the
+ * batch is planned as a bool batch is (candidates mode, no threshold seed, no MaxScore); clause terms and filter
+ * ids are resolved against the index state the batch was prepared on.
+ *
+ * The spec.  Term groups: c_offsets / c_term_ids / c_group / g_offsets as in slg_bool_spec, without kinds
+ * (g_offsets[q + 1] - g_offsets[q] = the query's term groups).  Filter leaves: f_filter[f_offsets[q] ..
+ * f_offsets[q + 1]).  Nodes: node j of query q is entry n = n_offsets[q] + j of n_min_should, its children
+ * e_child / e_kind [e_offsets[n] .. e_offsets[n + 1]).  A child index below the query's leaf count names a leaf;
+ * otherwise it is leaf count + the index of an earlier node of the same query.
+ *
+ * slg_batch_prepare_bool_tree / slg_search_batch_bool_tree have the argument shape and the life cycle of the two
+ * bool calls.  slg_batch_run enqueues ONE kernel between the scoring kernel and the select; a batch without
+ * slices, or whose queries have no node, launches nothing.  One candidate's state is a 64-bit mask — bits 0-31
+ * the leaves, bits 32-63 the nodes — hence the limits.
+ *
+ * Errors, all before any device work.  SLG_ERR_INVALID: a NULL spec or array, offsets that decrease, a c_group
+ * that decreases, skips a number or names a group the query does not have, a group without a term, an unknown
+ * kind, a child index that is not below its node, a leaf — or a node other than the root — that no node
+ * references, a query with leaves but no node, a term id out of range, an unknown filter id, q_min_match > 1 in
+ * the plans.  SLG_ERR_UNSUPPORTED (CPU scorer): more than SLG_MAX_BOOL_TREE_LEAVES leaves, SLG_MAX_BOOL_TREE_NODES
+ * nodes or SLG_MAX_BOOL_TERMS clause terms in a query; the same child twice in one node (the reference would
+ * count it twice, a mask cannot).  slg_batch_run_sharded* and slg_batch_fetch_sharded refuse the batch with
+ * SLG_ERR_UNSUPPORTED.  Not built (CPU scorer): phrase leaves in a tree, and trees on cursor, hybrid,
+ * aggregation, rescore, collapse, function_score, sharded and coalesced batches (none of their prepare calls
+ * takes a tree spec).
+ * --------------------------------------------------------------------------------------------------------- */
+#define SLG_MAX_BOOL_TREE_LEAVES 32u  /* term groups + filter leaves of one query (bits 0-31 of the kernel's masks) */
+#define SLG_MAX_BOOL_TREE_NODES 32u   /* nodes of one query (bits 32-63) */
+typedef struct slg_bool_tree_spec {
+  const uint32_t *c_offsets;    /* [nq + 1] into c_term_ids rows / c_group */
+  const uint32_t *c_term_ids;   /* [n_clause_terms x n_segs], rows as q_term_ids, SLG_NO_TERM where absent */
+  const uint32_t *c_group;      /* [n_clause_terms] term group of the term inside its query, non-decreasing, from 0, no gaps */
+  const uint32_t *g_offsets;    /* [nq + 1]: query q has g_offsets[q + 1] - g_offsets[q] term groups */
+  const uint32_t *f_offsets;    /* [nq + 1] into f_filter */
+  const int32_t *f_filter;      /* [n_filter_leaves] filter ids */
+  const uint32_t *n_offsets;    /* [nq + 1] into n_min_should / e_offsets */
+  const uint32_t *n_min_should; /* [n_nodes] */
+  const uint32_t *e_offsets;    /* [n_nodes + 1] into e_child / e_kind */
+  const uint32_t *e_child;      /* [n_edges] a leaf, or leaf count + an earlier node of the query */
+  const int32_t *e_kind;        /* [n_edges] SLG_BOOL_* */
+} slg_bool_tree_spec;
+slg_batch *slg_batch_prepare_bool_tree(slg_index *index, uint32_t nq, const uint32_t *q_offsets,
+                                       const uint32_t *q_term_ids, const float *q_weights,
+                                       const slg_score_plans *plans_or_null, const int32_t *q_filter_or_null,
+                                       const slg_sort_spec *sort_or_null, const slg_bool_tree_spec *spec, uint32_t k,
+                                       int strategy);
+int slg_search_batch_bool_tree(slg_index *index, uint32_t nq, const uint32_t *q_offsets, const uint32_t *q_term_ids,
+                               const float *q_weights, const slg_score_plans *plans_or_null,
+                               const int32_t *q_filter_or_null, const slg_sort_spec *sort_or_null,
+                               const slg_bool_tree_spec *spec, uint32_t k, int strategy, uint32_t *out_doc,
+                               uint32_t *out_seg, float *out_score, uint32_t *out_count, slg_stats *stats_or_null,
+                               uint64_t *out_matched_or_null);
 
 /* ---------------------------------------------------------------------------------------------------------
  * Phrase queries: `"olive oil" pasta`, match_phrase with a slop, and Phrase children of a bool.  The reference

@@ -76,6 +76,11 @@ pub const SLG_AGG_STATS: i32 = 3;
     pub c_offsets: *const u32, pub c_term_ids: *const u32, pub c_group: *const u32, pub g_offsets: *const u32,
     pub g_kind: *const i32, pub q_min_should: *const u32,
 }
+#[repr(C)] pub struct slg_bool_tree_spec {
+    pub c_offsets: *const u32, pub c_term_ids: *const u32, pub c_group: *const u32, pub g_offsets: *const u32,
+    pub f_offsets: *const u32, pub f_filter: *const i32, pub n_offsets: *const u32, pub n_min_should: *const u32,
+    pub e_offsets: *const u32, pub e_child: *const u32, pub e_kind: *const i32,
+}
 #[repr(C)] pub struct slg_fscore_spec {
     pub q_fn_offsets: *const u32, pub q_score_mode: *const i32, pub q_boost_mode: *const i32, pub q_flags: *const u32,
     pub q_max_boost: *const c_float, pub q_min_score: *const c_float, pub q_boost: *const c_float,
@@ -330,6 +335,16 @@ extern "C" {
         sort: *const slg_sort_spec, spec: *const slg_bool_spec, k: u32, strategy: c_int, out_doc: *mut u32,
         out_seg: *mut u32, out_score: *mut c_float, out_count: *mut u32, stats: *mut slg_stats,
         out_matched: *mut u64) -> c_int;
+    // nested boolean matchers (a tree of bool / dis_max / query string nodes over term groups and filter ids):
+    // the argument shape of the two bool calls.  The shim does not route requests to them yet.
+    pub fn slg_batch_prepare_bool_tree(index: *mut slg_index, nq: u32, q_offsets: *const u32, q_term_ids: *const u32,
+        q_weights: *const c_float, plans: *const slg_score_plans, q_filter: *const i32,
+        sort: *const slg_sort_spec, spec: *const slg_bool_tree_spec, k: u32, strategy: c_int) -> *mut slg_batch;
+    pub fn slg_search_batch_bool_tree(index: *mut slg_index, nq: u32, q_offsets: *const u32, q_term_ids: *const u32,
+        q_weights: *const c_float, plans: *const slg_score_plans, q_filter: *const i32,
+        sort: *const slg_sort_spec, spec: *const slg_bool_tree_spec, k: u32, strategy: c_int, out_doc: *mut u32,
+        out_seg: *mut u32, out_score: *mut c_float, out_count: *mut u32, stats: *mut slg_stats,
+        out_matched: *mut u64) -> c_int;
     // phrase queries: positions per segment, then slg_batch_prepare_bool plus the phrase spec (bool_spec may be null)
     pub fn slg_index_set_positions(index: *mut slg_index, seg: u32, pos_offsets: *const u64, positions: *const u32) -> c_int;
     // term expansion: a dictionary per segment, then fuzzy / prefix / wildcard requests -> rows of term ids
@@ -393,6 +408,8 @@ pub const SLG_BOOL_SHOULD: i32 = 1;
 pub const SLG_BOOL_MUST_NOT: i32 = 2;
 pub const SLG_MAX_BOOL_GROUPS: u32 = 32;
 pub const SLG_MAX_BOOL_TERMS: u32 = 64;
+pub const SLG_MAX_BOOL_TREE_LEAVES: u32 = 32;
+pub const SLG_MAX_BOOL_TREE_NODES: u32 = 32;
 pub const SLG_MAX_FSCORE_FUNCS: u32 = 8;
 pub const SLG_FSCORE_WEIGHT: i32 = 0;
 pub const SLG_FSCORE_FIELD_VALUE_FACTOR: i32 = 1;

@@ -36,6 +36,8 @@ MAX_RESCORE_WINDOW = 1024
 BOOL_MUST, BOOL_SHOULD, BOOL_MUST_NOT = 0, 1, 2
 MAX_BOOL_GROUPS = 32
 MAX_BOOL_TERMS = 64
+MAX_BOOL_TREE_LEAVES = 32
+MAX_BOOL_TREE_NODES = 32
 MAX_PHRASE_TERMS = 8
 MAX_PHRASE_VARIANTS = 8
 MAX_PHRASE_QUERY_TERMS = 64
@@ -157,6 +159,15 @@ class BoolSpec(C.Structure):
     minimum_should_match per query)."""
     _fields_ = [("c_offsets", C.c_void_p), ("c_term_ids", C.c_void_p), ("c_group", C.c_void_p),
                 ("g_offsets", C.c_void_p), ("g_kind", C.c_void_p), ("q_min_should", C.c_void_p)]
+
+
+class BoolTreeSpec(C.Structure):
+    """slg_bool_tree_spec: the matcher trees of a tree batch (CSR clause terms with their term groups, filter leaves,
+    and per query a post-order node table of (child, kind) edges with a min_should per node)."""
+    _fields_ = [("c_offsets", C.c_void_p), ("c_term_ids", C.c_void_p), ("c_group", C.c_void_p),
+                ("g_offsets", C.c_void_p), ("f_offsets", C.c_void_p), ("f_filter", C.c_void_p),
+                ("n_offsets", C.c_void_p), ("n_min_should", C.c_void_p), ("e_offsets", C.c_void_p),
+                ("e_child", C.c_void_p), ("e_kind", C.c_void_p)]
 
 
 class PhraseSpec(C.Structure):
@@ -349,6 +360,8 @@ def load():
         "slg_search_batch_rescore": (i32, [vp, u32, vp, vp, vp, vp, vp, vp, u32, i32, vp, vp, vp, vp, vp, vp, vp]),
         "slg_batch_prepare_bool": (vp, [vp, u32, vp, vp, vp, vp, vp, vp, vp, u32, i32]),
         "slg_search_batch_bool": (i32, [vp, u32, vp, vp, vp, vp, vp, vp, vp, u32, i32, vp, vp, vp, vp, vp, vp]),
+        "slg_batch_prepare_bool_tree": (vp, [vp, u32, vp, vp, vp, vp, vp, vp, vp, u32, i32]),
+        "slg_search_batch_bool_tree": (i32, [vp, u32, vp, vp, vp, vp, vp, vp, vp, u32, i32, vp, vp, vp, vp, vp, vp]),
         "slg_index_set_positions": (i32, [vp, u32, vp, vp]),
         "slg_batch_prepare_phrase": (vp, [vp, u32, vp, vp, vp, vp, vp, vp, vp, vp, u32, i32]),
         "slg_search_batch_phrase": (i32, [vp, u32, vp, vp, vp, vp, vp, vp, vp, vp, u32, i32, vp, vp, vp, vp, vp, vp]),

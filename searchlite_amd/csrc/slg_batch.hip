@@ -145,7 +145,7 @@ void slghost::release_batch_buffers(slg_batch *b, bool to_pool) {
                     &b->d_q_scored, &b->d_q_filter, &b->d_cand, &b->d_slice_cbeg, &b->d_slice_ccnt,
                     &b->d_out, &b->d_stamps, &b->d_blk_skip, &b->d_gather, &b->d_merged, &b->d_q_cand,
                     &b->d_hy_keys, &b->d_hy_work, &b->d_agg_desc, &b->d_agg_counts, &b->d_agg_stats,
-                    &b->d_rs_desc, &b->d_rs_side, &b->d_bool_desc, &b->d_phrase_desc, &b->d_fscore_desc,
+                    &b->d_rs_desc, &b->d_rs_side, &b->d_bool_desc, &b->d_phrase_desc, &b->d_booltree_desc, &b->d_fscore_desc,
                     &b->d_cl_desc, &b->d_cl_side};
   for (DevBuf *d : bufs) {
     if (!to_pool) d->pool = nullptr;
@@ -198,6 +198,7 @@ slg_batch *slghost::prepare_impl(const PrepareRequest &r) {
     if (r.rescore.on) slgplan::check_rescore(r.rescore.spec, nq, k);
     if (r.phrase.on) slgplan::check_phrase(r.boolean.spec, r.phrase.spec, nq, plans);
     else if (r.boolean.on) slgplan::check_bool(r.boolean.spec, nq, plans);
+    if (r.booltree.on) slgplan::check_bool_tree(r.booltree.spec, nq, plans);
     if (r.fscore.on) slgplan::check_fscore(r.fscore.spec, nq);
     if (r.collapse.on) slgplan::check_collapse(r.collapse.spec, k);
     SLG_REQUIRE(ix != nullptr, "index is NULL");
@@ -236,7 +237,7 @@ slg_batch *slghost::prepare_impl(const PrepareRequest &r) {
     in.strategy = r.strategy;
     in.filter_live = filter_live.data();
     in.n_filters = filter_live.size();
-    in.sorted = sort != nullptr || after || hybrid || r.aggs.on || r.boolean.on || r.fscore.on;
+    in.sorted = sort != nullptr || after || hybrid || r.aggs.on || r.boolean.on || r.booltree.on || r.fscore.on;
     SortBinding sorting;  // the columns of the sort parts in the batch's state
     if (sort) sorting = bind_sort(*snap, *sort, "", "part ");
     // the cursors as the key words the select kernel compares (against the same snapshot's field kinds)
@@ -266,6 +267,10 @@ slg_batch *slghost::prepare_impl(const PrepareRequest &r) {
     slgplan::PhrasePlan phrase_plan;
     if (r.phrase.on) slgplan::plan_phrase(views, nq, r.boolean.spec, *r.phrase.spec, phrase_plan);
     else if (r.boolean.on) slgplan::plan_bool(views, nq, *r.boolean.spec, bool_plan);
+    slgplan::BoolTreePlan booltree_plan;
+    if (r.booltree.on)
+      slgplan::plan_bool_tree(views, snap->reject_host.data(), filter_live.data(), filter_live.size(), nq,
+                              *r.booltree.spec, booltree_plan);
     slgplan::FscorePlan fscore_plan;
     if (r.fscore.on)
       slgplan::plan_fscore(fscore_field_views(*snap), snap->reject_host.data(), filter_live.data(), filter_live.size(),
@@ -389,6 +394,7 @@ slg_batch *slghost::prepare_impl(const PrepareRequest &r) {
     } else if (r.boolean.on) {
       bool_attach(b, bool_plan);
     }
+    if (r.booltree.on) booltree_attach(b, booltree_plan);
     if (r.fscore.on) fscore_attach(b, fscore_plan);
     if (r.collapse.on) collapse_attach(b, *r.collapse.spec, sort);
     {
@@ -519,6 +525,7 @@ int slg_batch_run(slg_batch *b) {
     //  kernel alone, which evaluates the term groups too)
     if (b->phrase) phrase_launch(b, st);
     else if (b->boolean) bool_launch(b, st);
+    else if (b->booltree) booltree_launch(b, st);
     if (b->fscore) fscore_launch(b, st);  // (the candidates' scores rewritten, those below min_score dropped)
     if (b->sorted) {  // (also without slices: every row is empty, every matched count 0)
       slg::SortedSelectParams sp{};
@@ -876,6 +883,27 @@ int slg_search_batch_bool(slg_index *ix, uint32_t nq, const uint32_t *q_offsets,
                           slg_stats *stats, uint64_t *out_matched) {
   return run_to_host(slg_batch_prepare_bool(ix, nq, q_offsets, q_term_ids, q_weights, plans, q_filter, sort, spec, k,
                                             strategy),
+                     HostOut{out_doc, out_seg, out_score, out_count, stats, out_matched});
+}
+
+slg_batch *slg_batch_prepare_bool_tree(slg_index *ix, uint32_t nq, const uint32_t *q_offsets,
+                                       const uint32_t *q_term_ids, const float *q_weights,
+                                       const slg_score_plans *plans, const int32_t *q_filter,
+                                       const slg_sort_spec *sort, const slg_bool_tree_spec *spec, uint32_t k,
+                                       int strategy) {
+  PrepareRequest r{ix, nq, q_offsets, q_term_ids, q_weights, plans, q_filter, k, strategy};
+  r.sort = if_given(sort);
+  r.booltree = {true, spec};
+  return prepare_impl(r);
+}
+
+int slg_search_batch_bool_tree(slg_index *ix, uint32_t nq, const uint32_t *q_offsets, const uint32_t *q_term_ids,
+                               const float *q_weights, const slg_score_plans *plans, const int32_t *q_filter,
+                               const slg_sort_spec *sort, const slg_bool_tree_spec *spec, uint32_t k, int strategy,
+                               uint32_t *out_doc, uint32_t *out_seg, float *out_score, uint32_t *out_count,
+                               slg_stats *stats, uint64_t *out_matched) {
+  return run_to_host(slg_batch_prepare_bool_tree(ix, nq, q_offsets, q_term_ids, q_weights, plans, q_filter, sort, spec,
+                                                 k, strategy),
                      HostOut{out_doc, out_seg, out_score, out_count, stats, out_matched});
 }
 

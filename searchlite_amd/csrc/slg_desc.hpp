@@ -189,6 +189,55 @@ struct BoolQuery {
 constexpr uint32_t kBoolMaxGroups = 32;  // = SLG_MAX_BOOL_GROUPS
 constexpr uint32_t kBoolMaxTerms = 64;   // = SLG_MAX_BOOL_TERMS
 
+// ---- nested boolean matchers (slg_batch_prepare_bool_tree; kernel: slg_booltree.hpp, planner: slg_plan.cpp) ----
+// One candidate's state is a pair of 64-bit masks over the query's VALUES: bit l < 32 is leaf l (the term groups,
+// then the filter leaves), bit 32 + i is node i.  The nodes of query q are nodes[node_begin .. node_begin +
+// n_nodes) in post-order (a node child lies below its parent), the last one the root.  The clause terms are
+// BoolTerm rows as above, one per (query, segment); BoolTerm::group holds the term's leaf in bits 0-4 and
+// kBoolTreeLeafEnd where the term is the last of its leaf.  Inside a row the terms of the leaves that reach the
+// root over MUST / MUST_NOT edges only come first (they alone can reject on their own), then the others, each
+// class in the caller's order, a leaf's terms side by side.  Filter leaf i of the query (leaf n_leaves -
+// n_filters + i) passes where filters[filt_rows[filt_begin + i] * n_segs + seg] has the doc's bit clear or is null.
+struct BoolTreeQuery {
+  uint32_t term_begin, n_terms;
+  uint32_t node_begin, n_nodes;  // n_nodes 0: the query has no matcher and is left as it is
+  uint32_t n_leaves;             // term groups + filter leaves
+  uint32_t filt_begin, n_filters;
+  uint32_t pad;
+};
+struct BoolTreeNode {
+  uint64_t must, must_not, should;  // the node's children of each kind, as value bits
+  uint32_t min_should;
+  uint32_t pad;
+};
+constexpr uint32_t kBoolTreeMaxLeaves = 32;   // = SLG_MAX_BOOL_TREE_LEAVES
+constexpr uint32_t kBoolTreeMaxNodes = 32;    // = SLG_MAX_BOOL_TREE_NODES
+constexpr uint32_t kBoolTreeLeafEnd = 0x100;  // in BoolTerm::group: the last term of its leaf
+
+// The three-valued pass over a query's nodes.  t: the values known to be true, f: the values known to be false
+// (disjoint; a value in neither is open).  Walks the nodes in order — children first — and puts every node that
+// is decided by what is known into t or f.  node_at(i) -> BoolTreeNode i of the query.
+//   sure true:  every MUST child true, every MUST_NOT child false, at least min_should SHOULD children true;
+//   sure false: a MUST child false, a MUST_NOT child true, or fewer than min_should SHOULD children not false.
+// Sound because a node's value is MONOTONE in what is known: learning an open value moves bits INTO t or f and
+// never out, (t & must) == must and popc(t & should) only grow with t, popc(should & ~f) only shrinks with f —
+// so a node that is sure stays sure, and equals its value under every completion of the open leaves.  With every
+// leaf known every node is decided (by induction over the order: all of a node's children are in t | f, so
+// either all three tests of `sure true` hold or one of `sure false` does).
+template <typename NodeAt>
+SLG_HD inline void booltree_eval(NodeAt node_at, uint32_t n_nodes, uint64_t &t, uint64_t &f) {
+  for (uint32_t i = 0; i < n_nodes; i++) {
+    const BoolTreeNode n = node_at(i);
+    const bool yes = (t & n.must) == n.must && (f & n.must_not) == n.must_not &&
+                     (uint32_t)__builtin_popcountll(t & n.should) >= n.min_should;
+    const bool no = (f & n.must) != 0ull || (t & n.must_not) != 0ull ||
+                    (uint32_t)__builtin_popcountll(n.should & ~f) < n.min_should;
+    const uint64_t bit = 1ull << (32u + i);
+    if (yes) t |= bit;
+    if (no) f |= bit;
+  }
+}
+
 // ---- phrase queries (slg_batch_prepare_phrase; kernel: slg_phrase.hpp, planner: slg_plan.cpp) --------
 // A phrase batch carries the bool tables above for its term groups (BoolQuery's masks and min_should cover
 // the phrase groups too: they are numbered behind the query's term groups) and three tables of its own.

@@ -1,5 +1,5 @@
 // slg_host.hpp — what the host translation units of the C ABI share (slg_index.hip, slg_batch.hip,
-// slg_shard.hip, slg_rerank.hip, slg_vsearch.hip, slg_hybrid.hip, slg_aggs.hip, slg_rescore.hip, slg_bool.hip, slg_phrase.hip, slg_fscore.hip, slg_collapse.hip): the error plumbing, device memory, the host
+// slg_shard.hip, slg_rerank.hip, slg_vsearch.hip, slg_hybrid.hip, slg_aggs.hip, slg_rescore.hip, slg_bool.hip, slg_booltree.hip, slg_phrase.hip, slg_fscore.hip, slg_collapse.hip): the error plumbing, device memory, the host
 // structures behind the opaque handles and the small helpers several entry points use.  Private: not
 // installed, not part of include/.  No kernel header is included here — each unit includes the one
 // whose kernels it launches (slg_stage.hpp, slg_kernels.hpp, slg_rerank.hpp, slg_vsearch.hpp, slg_hybrid.hpp; the shard
@@ -533,6 +533,12 @@ struct slg_batch {
   bool phrase = false;
   uint32_t phrase_vars = 0, phrase_terms = 0;  // entries of the two tables behind the PhraseQuery records
   DevBuf d_phrase_desc;      // slg::PhraseQuery[nq], slg::PhraseVar[phrase_vars], slg::PhraseTerm[phrase_terms]
+  // tree batch (slg_batch_prepare_bool_tree): planned and run as a bool batch; booltree_filter_kernel runs in
+  // bool_filter_kernel's place and drops the candidates the query's matcher tree rejects (slg_booltree.hip)
+  bool booltree = false;
+  uint32_t bt_nodes = 0, bt_terms = 0, bt_filters = 0;  // entries of the tables (bt_nodes 0: nothing is launched)
+  DevBuf d_booltree_desc;    // slg::BoolTreeQuery[nq], BoolTreeNode[bt_nodes], BoolTerm[bt_terms], bitmap addresses
+                             // [bt_filters], then the filter rows
   // function_score batch (slg_batch_prepare_fscore): planned as a sorted batch, run in score order or under its
   // sort spec; fscore_kernel runs between the scoring kernel and the select, rewrites every candidate's score and
   // drops the candidates below min_score (slg_fscore.hip)
@@ -667,6 +673,7 @@ struct PrepareRequest {
   Asked<slg_rescore_spec> rescore;
   Asked<slg_bool_spec> boolean;   // a phrase batch: on, its spec may be NULL (no term groups)
   Asked<slg_phrase_spec> phrase;
+  Asked<slg_bool_tree_spec> booltree;
   Asked<slg_fscore_spec> fscore;
   Asked<slg_collapse_spec> collapse;
 };
@@ -773,6 +780,9 @@ void bool_launch(slg_batch *b, hipStream_t st);
 // slg_phrase.hip: the same for a phrase batch, behind bool_attach; the launch in bool_launch's place
 void phrase_attach(slg_batch *b, const slgplan::PhrasePlan &pp);
 void phrase_launch(slg_batch *b, hipStream_t st);
+// slg_booltree.hip: the planned tables of a tree batch onto the device; the launch in bool_launch's place
+void booltree_attach(slg_batch *b, const slgplan::BoolTreePlan &tp);
+void booltree_launch(slg_batch *b, hipStream_t st);
 // slg_fscore.hip: an index state's aggregation columns as plan_fscore reads them; the planned tables onto the
 // device (throws; the batch is otherwise prepared); the launch behind the batch's scoring kernel, in front of
 // its select

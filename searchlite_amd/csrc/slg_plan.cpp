@@ -1416,6 +1416,147 @@ void plan_fscore(const std::vector<FscoreFieldView> &fields, const uint32_t *con
   fill_tables(fields, used_fields, reject, used_filters, n_segs, out.cols, out.filters);
 }
 
+// ---- nested boolean matchers ------------------------------------------------------------------------------
+static_assert(slg::kBoolTreeMaxLeaves == SLG_MAX_BOOL_TREE_LEAVES && slg::kBoolTreeMaxNodes == SLG_MAX_BOOL_TREE_NODES &&
+                  slg::kBoolTreeMaxLeaves == 32 && slg::kBoolTreeMaxNodes == 32,
+              "the kernel's value masks (bits 0-31 leaves, 32-63 nodes) and the ABI's limits");
+static_assert(sizeof(slg::BoolTreeQuery) == 32 && sizeof(slg::BoolTreeNode) == 32, "records the kernel reads in whole words");
+
+void check_bool_tree(const slg_bool_tree_spec *spec, uint32_t nq, const slg_score_plans *plans) {
+  PLAN_REQUIRE(spec != nullptr, "bool tree spec is NULL");
+  if (nq == 0) return;
+  PLAN_REQUIRE(spec->c_offsets != nullptr, "bool tree c_offsets is NULL");
+  PLAN_REQUIRE(spec->g_offsets != nullptr, "bool tree g_offsets is NULL");
+  PLAN_REQUIRE(spec->f_offsets != nullptr, "bool tree f_offsets is NULL");
+  PLAN_REQUIRE(spec->n_offsets != nullptr, "bool tree n_offsets is NULL");
+  for (uint32_t q = 0; q < nq; q++) {
+    PLAN_REQUIRE(spec->c_offsets[q + 1] >= spec->c_offsets[q], "bool tree c_offsets not monotone");
+    PLAN_REQUIRE(spec->g_offsets[q + 1] >= spec->g_offsets[q], "bool tree g_offsets not monotone");
+    PLAN_REQUIRE(spec->f_offsets[q + 1] >= spec->f_offsets[q], "bool tree f_offsets not monotone");
+    PLAN_REQUIRE(spec->n_offsets[q + 1] >= spec->n_offsets[q], "bool tree n_offsets not monotone");
+  }
+  PLAN_REQUIRE(spec->c_offsets[nq] == spec->c_offsets[0] || (spec->c_term_ids && spec->c_group),
+               "bool tree c_term_ids/c_group is NULL");
+  PLAN_REQUIRE(spec->f_offsets[nq] == spec->f_offsets[0] || spec->f_filter, "bool tree f_filter is NULL");
+  const uint32_t n0 = spec->n_offsets[0], n1 = spec->n_offsets[nq];
+  if (n1 != n0) {
+    PLAN_REQUIRE(spec->n_min_should && spec->e_offsets, "bool tree n_min_should/e_offsets is NULL");
+    for (uint32_t n = n0; n < n1; n++)
+      PLAN_REQUIRE(spec->e_offsets[n + 1] >= spec->e_offsets[n], "bool tree e_offsets not monotone");
+    PLAN_REQUIRE(spec->e_offsets[n1] == spec->e_offsets[n0] || (spec->e_child && spec->e_kind),
+                 "bool tree e_child/e_kind is NULL");
+  }
+  std::string unsupported;  // (reported behind every invalid argument)
+  for (uint32_t q = 0; q < nq; q++) {
+    const std::string in_q = " in bool tree query " + std::to_string(q);
+    const uint32_t t0 = spec->c_offsets[q], nt = spec->c_offsets[q + 1] - t0;
+    const uint32_t ng = spec->g_offsets[q + 1] - spec->g_offsets[q];
+    const uint32_t f0 = spec->f_offsets[q], nf = spec->f_offsets[q + 1] - f0;
+    const uint32_t nb = spec->n_offsets[q], nn = spec->n_offsets[q + 1] - nb;
+    uint32_t next = 0;  // the group a new group's first term must name
+    for (uint32_t i = 0; i < nt; i++) {
+      const uint32_t g = spec->c_group[t0 + i];
+      PLAN_REQUIRE(g < ng, "c_group names a group the query does not have" + in_q);
+      PLAN_REQUIRE(g == next || (next > 0 && g == next - 1), "c_group decreases or skips a group" + in_q);
+      if (g == next) next++;
+    }
+    PLAN_REQUIRE(next == ng, "a group without a term" + in_q);
+    for (uint32_t f = f0; f < f0 + nf; f++)
+      PLAN_REQUIRE(spec->f_filter[f] >= 0, "unknown filter id " + std::to_string(spec->f_filter[f]) + in_q);
+    const uint64_t nl = (uint64_t)ng + nf;  // leaves
+    PLAN_REQUIRE(nl == 0 || nn != 0, "leaves but no node" + in_q);
+    std::vector<uint32_t> refs((size_t)(nl + nn), 0u);  // how often each value is some node's child
+    bool twice = false;
+    for (uint32_t j = 0; j < nn; j++) {
+      std::vector<uint32_t> mine;
+      for (uint32_t e = spec->e_offsets[nb + j]; e < spec->e_offsets[nb + j + 1]; e++) {
+        PLAN_REQUIRE(clause_kind_known(spec->e_kind[e]), "unknown child kind" + in_q);
+        const uint32_t c = spec->e_child[e];
+        PLAN_REQUIRE((uint64_t)c < nl + j, "a child index that is not below its node" + in_q);
+        twice = twice || std::find(mine.begin(), mine.end(), c) != mine.end();
+        mine.push_back(c);
+        refs[c]++;
+      }
+    }
+    for (uint64_t v = 0; v + 1 < nl + nn; v++)  // (every value but the root)
+      PLAN_REQUIRE(refs[v] != 0u, std::string(v < nl ? "a leaf" : "a node other than the root") + " that no node references" + in_q);
+    require_no_min_match(plans, q, "bool tree", in_q);
+    if (!unsupported.empty()) continue;
+    if (nl > SLG_MAX_BOOL_TREE_LEAVES) unsupported = "more than SLG_MAX_BOOL_TREE_LEAVES leaves" + in_q;
+    else if (nn > SLG_MAX_BOOL_TREE_NODES) unsupported = "more than SLG_MAX_BOOL_TREE_NODES nodes" + in_q;
+    else if (nt > SLG_MAX_BOOL_TERMS) unsupported = "more than SLG_MAX_BOOL_TERMS clause terms" + in_q;
+    else if (twice) unsupported = "the same child twice in one node" + in_q;
+  }
+  if (!unsupported.empty()) throw SlgError(SLG_ERR_UNSUPPORTED, unsupported);
+}
+
+void plan_bool_tree(const std::vector<SegView> &segs, const uint32_t *const *reject, const char *filter_live,
+                    size_t n_filters, uint32_t nq, const slg_bool_tree_spec &spec, BoolTreePlan &out) {
+  const uint32_t n_segs = (uint32_t)segs.size();
+  out = BoolTreePlan{};
+  out.queries.assign(nq, slg::BoolTreeQuery{});
+  if (nq == 0) return;
+  const uint32_t c_base = spec.c_offsets[0];
+  out.terms.reserve((size_t)(spec.c_offsets[nq] - c_base) * n_segs);
+  std::vector<int32_t> used_filters;  // the rows of the filter table, in order of first use
+  for (uint32_t q = 0; q < nq; q++) {
+    const std::string in_q = " in bool tree query " + std::to_string(q);
+    const uint32_t t0 = spec.c_offsets[q], nt = spec.c_offsets[q + 1] - t0;
+    const uint32_t ng = spec.g_offsets[q + 1] - spec.g_offsets[q];
+    const uint32_t f0 = spec.f_offsets[q], nf = spec.f_offsets[q + 1] - f0;
+    const uint32_t nb = spec.n_offsets[q], nn = spec.n_offsets[q + 1] - nb;
+    const uint32_t nl = ng + nf;
+    slg::BoolTreeQuery &tq = out.queries[q];
+    tq.term_begin = t0 - c_base;
+    tq.n_terms = nt;
+    tq.node_begin = (uint32_t)out.nodes.size();
+    tq.n_nodes = nn;
+    tq.n_leaves = nl;
+    tq.filt_begin = (uint32_t)out.filt_rows.size();
+    tq.n_filters = nf;
+    for (uint32_t f = f0; f < f0 + nf; f++) {
+      PLAN_REQUIRE((size_t)spec.f_filter[f] < n_filters && filter_live[spec.f_filter[f]],
+                   "unknown filter id " + std::to_string(spec.f_filter[f]) + in_q);
+      out.filt_rows.push_back(row_of(used_filters, spec.f_filter[f]));
+    }
+    // a child as a value bit: a leaf its own number, node j bit 32 + j
+    const auto value_bit = [nl](uint32_t c) { return 1ull << (c < nl ? c : 32u + (c - nl)); };
+    for (uint32_t j = 0; j < nn; j++) {
+      slg::BoolTreeNode nd{};
+      nd.min_should = spec.n_min_should[nb + j];
+      for (uint32_t e = spec.e_offsets[nb + j]; e < spec.e_offsets[nb + j + 1]; e++) {
+        const int32_t kind = spec.e_kind[e];
+        (kind == SLG_BOOL_MUST ? nd.must : kind == SLG_BOOL_MUST_NOT ? nd.must_not : nd.should) |= value_bit(spec.e_child[e]);
+      }
+      out.nodes.push_back(nd);
+    }
+    // the values that reach the root over MUST / MUST_NOT edges only, from the root down (a parent lies above
+    // its children): the leaves among them can reject on their own and go first in the row
+    uint64_t direct = nn ? 1ull << (31u + nn) : 0ull;
+    for (uint32_t j = nn; j-- > 0;) {
+      const slg::BoolTreeNode &nd = out.nodes[tq.node_begin + j];
+      if (direct & (1ull << (32u + j))) direct |= nd.must | nd.must_not;
+    }
+    uint32_t order[SLG_MAX_BOOL_TERMS], n = 0;
+    for (const bool first : {true, false})
+      for (uint32_t i = 0; i < nt; i++)
+        if ((((direct >> spec.c_group[t0 + i]) & 1ull) != 0ull) == first) order[n++] = i;
+    for (uint32_t s = 0; s < n_segs; s++) {
+      for (uint32_t j = 0; j < nt; j++) {
+        const uint32_t i = order[j];
+        slg::BoolTerm bt{};
+        bt.group = spec.c_group[t0 + i];
+        if (i + 1 == nt || spec.c_group[t0 + i + 1] != bt.group) bt.group |= slg::kBoolTreeLeafEnd;
+        uint64_t ubase;
+        resolve_term(segs[s], spec.c_term_ids[(size_t)(t0 + i) * n_segs + s], "bool tree", q, bt.off, ubase, bt.df);
+        out.terms.push_back(bt);
+      }
+    }
+  }
+  for (const int32_t f : used_filters)
+    out.filters.insert(out.filters.end(), reject + (size_t)f * n_segs, reject + ((size_t)f + 1) * n_segs);
+}
+
 // ---- filter trees --------------------------------------------------------------------------------------
 static_assert(slg::kFilterMaxNodes == SLG_MAX_FILTER_NODES && slg::kFilterMaxDepth == SLG_MAX_FILTER_DEPTH &&
                   slg::kFilterMaxTrees == SLG_MAX_FILTER_TREES, "the kernel's limits and the ABI's");

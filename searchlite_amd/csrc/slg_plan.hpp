@@ -150,6 +150,27 @@ struct BoolPlan {
 };
 void plan_bool(const std::vector<SegView> &segs, uint32_t nq, const slg_bool_spec &spec, BoolPlan &out);
 
+// ---- nested boolean matchers (slg_batch_prepare_bool_tree) ----
+// The checks of a tree spec that need no index (throws SlgError).  SLG_ERR_INVALID, reported first: a NULL spec or
+// array, offsets that decrease, check_bool's c_group rules, an unknown kind, a child index that is not below its
+// node, a leaf or a node other than the root that no node references, a query with leaves but no node, a negative
+// filter id, q_min_match > 1 in the batch's score plans.  SLG_ERR_UNSUPPORTED: more than SLG_MAX_BOOL_TREE_LEAVES
+// leaves, SLG_MAX_BOOL_TREE_NODES nodes or SLG_MAX_BOOL_TERMS clause terms in a query, the same child twice in a node.
+void check_bool_tree(const slg_bool_tree_spec *spec, uint32_t nq, const slg_score_plans *plans);
+// The tables of a checked spec against the segments and the registered filters (slg_desc.hpp: BoolTreeQuery,
+// BoolTreeNode, BoolTerm rows, the filter rows and the batch's filter table [row * n_segs + seg]; reject,
+// filter_live and n_filters as plan_fscore's).  Throws SLG_ERR_INVALID for a term id out of range or an unknown
+// filter id.
+struct BoolTreePlan {
+  std::vector<slg::BoolTreeQuery> queries;  // [nq]
+  std::vector<slg::BoolTreeNode> nodes;     // the nodes of all queries (0: no query has a matcher)
+  std::vector<slg::BoolTerm> terms;         // [total x n_segs], a row per (query, segment)
+  std::vector<const uint32_t *> filters;    // [filters of the batch x n_segs]
+  std::vector<uint32_t> filt_rows;          // the filter leaves of all queries: their rows of `filters`
+};
+void plan_bool_tree(const std::vector<SegView> &segs, const uint32_t *const *reject, const char *filter_live,
+                    size_t n_filters, uint32_t nq, const slg_bool_tree_spec &spec, BoolTreePlan &out);
+
 // ---- phrase queries (slg_index_set_positions, slg_batch_prepare_phrase) ----
 // The checks of a segment's positions (throws SlgError): NULL arrays, a first offset other than 0, offsets that
 // decrease (SLG_ERR_INVALID); more than 2^32 - 1 positions (SLG_ERR_UNSUPPORTED; from the offsets alone, before a

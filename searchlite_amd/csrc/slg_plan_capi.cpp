@@ -195,6 +195,71 @@ int slgp_plan_bool(const slgp_segment *segs, uint32_t n_segs, uint32_t nq, const
   }
 }
 
+// the host side of slg_batch_prepare_bool_tree: check_bool_tree, then plan_bool_tree against the segments and
+// filters that exist as descriptions only (reject bitmaps: the addresses slgp_plan_fscore makes up, (f + 1) << 32 |
+// s << 8 | 3).  queries: nq x 8 words (slg::BoolTreeQuery); nodes: entries of 8 words (slg::BoolTreeNode: must,
+// must_not, should as low / high words, min_should, pad); terms: entries of 4 words (slg::BoolTerm); filters:
+// addresses; filt_rows: words.  Each table is filled when it fits its cap; counts: entries of nodes, terms,
+// filters, filt_rows.  0, or a negative error code (err filled)
+int slgp_plan_bool_tree(const slgp_segment *segs, uint32_t n_segs, const char *filter_live, uint32_t n_filters,
+                        uint32_t nq, const slg_bool_tree_spec *spec, const slg_score_plans *plans, uint32_t *queries,
+                        uint32_t *nodes, uint32_t nodes_cap, uint32_t *terms, uint32_t terms_cap, uint64_t *filters,
+                        uint32_t filters_cap, uint32_t *filt_rows, uint32_t filt_rows_cap, uint32_t *counts,
+                        char *err, uint32_t err_len) {
+  try {
+    slgplan::check_bool_tree(spec, nq, plans);
+    std::vector<slgplan::SegView> views(n_segs);
+    for (uint32_t s = 0; s < n_segs; s++) {
+      views[s].n_docs = segs[s].n_docs;
+      views[s].n_terms = segs[s].n_terms;
+      views[s].term_offsets = segs[s].term_offsets;
+    }
+    std::vector<const uint32_t *> reject((size_t)n_filters * n_segs);
+    for (uint32_t f = 0; f < n_filters; f++)
+      for (uint32_t s = 0; s < n_segs; s++)
+        reject[(size_t)f * n_segs + s] =
+            reinterpret_cast<const uint32_t *>((uintptr_t)(((uint64_t)(f + 1) << 32) | ((uint64_t)s << 8) | 3u));
+    slgplan::BoolTreePlan tp;
+    slgplan::plan_bool_tree(views, reject.data(), filter_live, n_filters, nq, *spec, tp);
+    static_assert(sizeof(slg::BoolTreeQuery) == 32 && sizeof(slg::BoolTreeNode) == 32 && sizeof(slg::BoolTerm) == 16,
+                  "the words the caller reads");
+    if (queries && nq) std::memcpy(queries, tp.queries.data(), (size_t)nq * sizeof(slg::BoolTreeQuery));
+    if (nodes && tp.nodes.size() <= nodes_cap && !tp.nodes.empty())
+      std::memcpy(nodes, tp.nodes.data(), tp.nodes.size() * sizeof(slg::BoolTreeNode));
+    if (terms && tp.terms.size() <= terms_cap && !tp.terms.empty())
+      std::memcpy(terms, tp.terms.data(), tp.terms.size() * sizeof(slg::BoolTerm));
+    if (filters && tp.filters.size() <= filters_cap && !tp.filters.empty())
+      std::memcpy(filters, tp.filters.data(), tp.filters.size() * sizeof(void *));
+    if (filt_rows && tp.filt_rows.size() <= filt_rows_cap && !tp.filt_rows.empty())
+      std::memcpy(filt_rows, tp.filt_rows.data(), tp.filt_rows.size() * 4);
+    if (counts) {
+      counts[0] = (uint32_t)tp.nodes.size();
+      counts[1] = (uint32_t)tp.terms.size();
+      counts[2] = (uint32_t)tp.filters.size();
+      counts[3] = (uint32_t)tp.filt_rows.size();
+    }
+    return SLG_OK;
+  } catch (const slgplan::SlgError &e) {
+    if (err && err_len) {
+      std::strncpy(err, e.what(), err_len - 1);
+      err[err_len - 1] = 0;
+    }
+    return e.code;
+  }
+}
+
+// the three-valued pass booltree_filter_kernel runs after every step of a row (slg::booltree_eval, slg_desc.hpp):
+// nodes: n_nodes entries of 8 words as slgp_plan_bool_tree writes them; *t / *f: the values known to be true /
+// false going in (leaf bits), with the decided nodes' bits added coming out
+void slgp_booltree_eval(const uint32_t *nodes, uint32_t n_nodes, uint64_t *t, uint64_t *f) {
+  const auto node_at = [nodes](uint32_t i) {
+    slg::BoolTreeNode n;
+    std::memcpy(&n, nodes + (size_t)i * 8, sizeof n);
+    return n;
+  };
+  slg::booltree_eval(node_at, n_nodes, *t, *f);
+}
+
 // the host side of slg_batch_prepare_phrase: check_phrase, then plan_phrase against the segments.  seg_has_pos:
 // one byte per segment, 0 = no positions were set for it (NULL: every segment has positions).  queries: nq x 8
 // words (slg::BoolQuery); pqueries: nq x 8 words (slg::PhraseQuery); vars: entries of 4 words (slg::PhraseVar);

@@ -147,6 +147,7 @@ int run_sharded_impl(slg_batch *b, slg_shard_group *g, bool have_seq, uint64_t s
     if (b->rescore) throw SlgError(SLG_ERR_UNSUPPORTED, "a rescore batch does not run sharded");
     if (b->phrase) throw SlgError(SLG_ERR_UNSUPPORTED, "a phrase batch does not run sharded");
     if (b->boolean) throw SlgError(SLG_ERR_UNSUPPORTED, "a bool batch does not run sharded");
+    if (b->booltree) throw SlgError(SLG_ERR_UNSUPPORTED, "a tree batch does not run sharded");
     if (b->fscore) throw SlgError(SLG_ERR_UNSUPPORTED, "a function_score batch does not run sharded");
     if (b->collapse) throw SlgError(SLG_ERR_UNSUPPORTED, "a collapse batch does not run sharded");
   });
@@ -281,6 +282,7 @@ int slg_batch_fetch_sharded(slg_batch *b, uint32_t *out_doc, uint32_t *out_seg, 
     if (b->rescore) throw SlgError(SLG_ERR_UNSUPPORTED, "a rescore batch does not run sharded");
     if (b->phrase) throw SlgError(SLG_ERR_UNSUPPORTED, "a phrase batch does not run sharded");
     if (b->boolean) throw SlgError(SLG_ERR_UNSUPPORTED, "a bool batch does not run sharded");
+    if (b->booltree) throw SlgError(SLG_ERR_UNSUPPORTED, "a tree batch does not run sharded");
     if (b->fscore) throw SlgError(SLG_ERR_UNSUPPORTED, "a function_score batch does not run sharded");
     if (b->collapse) throw SlgError(SLG_ERR_UNSUPPORTED, "a collapse batch does not run sharded");
     SLG_REQUIRE(b->nq == 0 || out_count != nullptr, "out_count is NULL");

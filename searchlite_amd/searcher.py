@@ -476,6 +476,20 @@ class GpuIndex:
         finally:
             b.close()
 
+    def search_batch_bool_tree(self, q_offsets, q_terms, q_weights, k: int, clause_tree, sort=None,
+                               strategy: int = Wand, q_filter=None, want_stats: bool = False, **plans):
+        """Batch search with a nested boolean matcher per query (slg_batch_prepare_bool_tree).  clause_tree: the dict
+        of booltree.compile_matchers (term groups, filter leaves and a post-order node table per query); sort: None =
+        score order, else as search_sorted; **plans: the score plan arrays of prepare().
+        Returns what search_batch_bool returns."""
+        b = self.prepare(q_offsets, q_terms, q_weights, k, strategy, q_filter, sort=sort, clause_tree=clause_tree,
+                         **plans)
+        try:
+            b.run()
+            return b.fetch(want_stats) + ((b.matched_counts(),) if sort is not None else ())
+        finally:
+            b.close()
+
     def search_batch_phrase(self, q_offsets, q_terms, q_weights, k: int, phrases, clauses=None, sort=None,
                             strategy: int = Wand, q_filter=None, want_stats: bool = False, **plans):
         """Batch search with phrase groups (slg_batch_prepare_phrase).  phrases: a dict with p_offsets [nq + 1],
@@ -537,7 +551,8 @@ class GpuIndex:
                 q_leaf_offsets=None, leaf_group=None, q_group_offsets=None, group_plan=None,
                 group_tie=None, q_node_offsets=None, node_kind=None, node_tie=None, node_parent=None,
                 q_min_match=None, sort=None, cursors=None, hybrid=False, aggs=None,
-                rescore=None, clauses=None, phrases=None, fscore=None, collapse=None) -> "PreparedBatch":
+                rescore=None, clauses=None, phrases=None, fscore=None, collapse=None,
+                clause_tree=None) -> "PreparedBatch":
         """q_leaf / q_plan / q_tie / q_nleaves: score plans; leaf_group / group_plan / group_tie with
         their per-query offsets: two-level plans; q_node_offsets / node_kind / node_tie / node_parent:
         trees of any shape, node by node in pre-order (slg_batch_prepare_plans, slg_score_plans);
@@ -551,11 +566,13 @@ class GpuIndex:
         slg_batch_prepare_phrase (with clauses as its term groups, or without); fscore: one function_score per
         query, the list of fscore_spec() (or its result) -> slg_batch_prepare_fscore (score order, or with sort);
         collapse: the dict of search_collapse -> slg_batch_prepare_collapse (score order, with sort and / or cursors;
-        PreparedBatch.collapse_groups)."""
+        PreparedBatch.collapse_groups); clause_tree: the dict of search_batch_bool_tree ->
+        slg_batch_prepare_bool_tree (score order, or with sort)."""
         return PreparedBatch(self, q_offsets, q_terms, q_weights, k, strategy, q_filter,
                              q_leaf, q_plan, q_tie, q_nleaves, q_leaf_offsets, leaf_group,
                              q_group_offsets, group_plan, group_tie, q_node_offsets, node_kind, node_tie, node_parent,
-                             q_min_match, sort, cursors, hybrid, aggs, rescore, clauses, phrases, fscore, collapse)
+                             q_min_match, sort, cursors, hybrid, aggs, rescore, clauses, phrases, fscore, collapse,
+                             clause_tree)
 
     def search_collapse(self, q_offsets, q_terms, q_weights, k: int, collapse, sort=None, cursors=None,
                         strategy: int = Wand, q_filter=None, **plans):
@@ -967,6 +984,20 @@ def bool_spec(clauses: dict, nq: int):
     return N.BoolSpec(*[_ptr(a) for a in keep]), keep
 
 
+def bool_tree_spec(tree: dict, nq: int):
+    """The dict of GpuIndex.search_batch_bool_tree (booltree.compile_matchers) as (N.BoolTreeSpec, the arrays it
+    points into)."""
+    def arr(name, dtype):
+        a = tree.get(name)
+        return None if a is None else np.ascontiguousarray(np.asarray(a, dtype=dtype))
+    keep = [arr("c_offsets", np.uint32), arr("c_terms", np.uint32), arr("c_group", np.uint32),
+            arr("g_offsets", np.uint32), arr("f_offsets", np.uint32), arr("f_filter", np.int32),
+            arr("n_offsets", np.uint32), arr("n_min_should", np.uint32), arr("e_offsets", np.uint32),
+            arr("e_child", np.uint32), arr("e_kind", np.int32)]
+    assert all(a is None or len(a) == nq + 1 for a in (keep[0], keep[3], keep[4], keep[6]))
+    return N.BoolTreeSpec(*[_ptr(a) for a in keep]), keep
+
+
 def phrase_spec(phrases: dict, nq: int):
     """The dict of GpuIndex.search_batch_phrase as (N.PhraseSpec, the arrays it points into)."""
     def arr(name, dtype, per_query=False):
@@ -1070,7 +1101,7 @@ class PreparedBatch:
                  q_leaf_offsets=None, leaf_group=None, q_group_offsets=None, group_plan=None,
                  group_tie=None, q_node_offsets=None, node_kind=None, node_tie=None, node_parent=None,
                  q_min_match=None, sort=None, cursors=None, hybrid=False, aggs=None, rescore=None, clauses=None,
-                 phrases=None, fscore=None, collapse=None):
+                 phrases=None, fscore=None, collapse=None, clause_tree=None):
         self.index = index
         self._lib = index._lib
         q_offsets = np.ascontiguousarray(q_offsets, dtype=np.uint32)
@@ -1108,7 +1139,19 @@ class PreparedBatch:
         self.is_phrase = phrases is not None
         self.is_fscore = fscore is not None
         self.is_collapse = collapse is not None
-        if collapse is not None:
+        self.is_bool_tree = clause_tree is not None
+        if clause_tree is not None:
+            # (the library's other prepare calls take no tree spec: the refusal is made here with its code)
+            if hybrid or cursors is not None or aggs is not None or rescore is not None or clauses is not None or \
+                    phrases is not None or fscore is not None or collapse is not None:
+                raise N.SlgError(N.ERR_UNSUPPORTED, "a matcher tree is not built on cursor, hybrid, aggregation, rescore, "
+                                                    "bool, phrase, function_score or collapse batches")
+            tspec, self._tree_keep = bool_tree_spec(clause_tree, self.nq)
+            spec = None if sort is None else sort_spec(sort)
+            self._h = self._lib.slg_batch_prepare_bool_tree(
+                index._h, self.nq, _ptr(q_offsets), _ptr(q_terms), _ptr(q_weights), C.addressof(plans),
+                opt(qf), None if spec is None else C.addressof(spec), C.addressof(tspec), k, strategy)
+        elif collapse is not None:
             # (the library's other prepare calls take no collapse spec: the refusal is made here with its code)
             if hybrid or aggs is not None or rescore is not None or clauses is not None or phrases is not None or \
                     fscore is not None:

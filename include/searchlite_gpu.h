@@ -23,8 +23,8 @@
  * k = limit + 1 up to 20 001; up to 32 scored terms per query and segment.  Field sorts (slg_batch_prepare_sorted):
  * up to SLG_MAX_SORT_PARTS parts of numeric fast fields (i64 / f64) and _score, any order; keyword parts stay
  * on the CPU.  A cursor (the next page, slg_batch_prepare_after) in score order or in a device-eligible field
- * sort; not in sharded runs or the coalescer.  Aggregations (slg_batch_prepare_aggs): terms, histogram, range and
- * stats over registered columns, two levels, in score order or a field sort; not with a cursor, not on hybrid,
+ * sort; not in sharded runs or the coalescer.  Aggregations (slg_batch_prepare_aggs): terms, histogram, range,
+ * stats, cardinality, percentiles and percentile_ranks over registered columns, two levels, in score order or a field sort; not with a cursor, not on hybrid,
  * vector-only, sharded or coalesced batches.  Query rescore (slg_batch_prepare_rescore): a second BM25 query with
  * a flat Sum / DisMax plan over a window of up to SLG_MAX_RESCORE_WINDOW first-pass rows, every score_mode; in
  * score order only, not on sorted, cursor, hybrid, vector-only, aggregation, sharded or coalesced batches.
@@ -612,7 +612,8 @@ int slg_batch_info(const slg_batch *batch, uint64_t *n_postings, uint32_t *n_sli
 int slg_batch_skip_counts(slg_batch *batch, uint64_t *probed_postings, uint64_t *skipped_postings);
 void slg_batch_destroy(slg_batch *batch);
 
-/* ---- aggregations (query/aggs/mod.rs: `aggs` with terms, histogram, range and stats) ----------------
+/* ---- aggregations (query/aggs/mod.rs: `aggs` with terms, histogram, range, stats, cardinality, percentiles
+ * and percentile_ranks) -----------------------------------------------------------------------------
  * A request with `aggs` makes the reference visit every matched doc (a collector sets the WAND threshold to
  * -inf, query/wand.rs:725-729) and upsert a hash map per aggregation and doc (aggs/mod.rs:894-930,
  * 1166-1204).  On the device an aggregation batch is planned like a sorted batch — every matched doc is a
@@ -638,7 +639,13 @@ void slg_batch_destroy(slg_batch *batch);
 #define SLG_MAX_AGG_CELLS 65536u /* count cells + stats cells of one query */
 #define SLG_AGG_LDS_BYTES 32768u /* tables of 4 B per count cell + 32 B per stats cell up to this size are
                                     filled in LDS, larger ones in device memory (same results) */
-enum { SLG_AGG_TERMS = 0, SLG_AGG_HISTOGRAM = 1, SLG_AGG_RANGE = 2, SLG_AGG_STATS = 3 };
+#define SLG_MAX_AGG_SCRATCH_WORDS (1u << 19) /* u32 words of one query's value-node scratch (2 MB): the cardinality
+                                               bitmaps plus the fine tables of the percentiles nodes */
+#define SLG_AGG_PCT_LDS_BYTES 16384u /* of SLG_AGG_LDS_BYTES, held back by a spec with a percentiles node: its
+                                        coarse histogram, then its fine tables when they fit */
+#define SLG_MAX_AGG_RANKS (1u << 24) /* distinct values of a ranked column (slg_index_rank_agg_field) */
+enum { SLG_AGG_TERMS = 0, SLG_AGG_HISTOGRAM = 1, SLG_AGG_RANGE = 2, SLG_AGG_STATS = 3,
+       SLG_AGG_CARDINALITY = 4, SLG_AGG_PERCENTILES = 5, SLG_AGG_PERCENTILE_RANKS = 6 };
 int slg_index_add_agg_field_f64(slg_index *index, const uint32_t *const *seg_offsets,
                                 const double *const *seg_values);
 int slg_index_add_agg_field_i64(slg_index *index, const uint32_t *const *seg_offsets,
@@ -647,6 +654,18 @@ int slg_index_add_agg_field_ord(slg_index *index, const uint32_t *const *seg_off
                                 const uint32_t *const *seg_ords, uint32_t n_ords);
 /* Batches already prepared with the field keep its columns (they belong to the batch's index state). */
 int slg_index_remove_agg_field(slg_index *index, int agg_field_id);
+/* The value ranks of a registered column, what SLG_AGG_CARDINALITY and SLG_AGG_PERCENTILES need of a numeric
+ * field.  Builds the field's value dictionary — the sorted distinct values over all segments, ordered and told
+ * apart by the order-preserving u64 key of their bits (so -0.0 and 0.0 are two entries, as the reference hashes
+ * to_bits(), aggs/mod.rs:1549) — and, beside each segment's values, a u32 rank array with the same indexing.
+ * Returns the distinct count R (>= 0) or a negative error code; a second call returns R and does nothing else; a
+ * keyword field returns n_ords (its ordinals are its ranks).  Cost on the device: 4 B per value + 8 B per distinct
+ * value; the dictionary is kept on the host too (prepare looks `missing` up in it).  The values are sorted on the
+ * host: registration is not the hot path.  A new index state, as every update: slg_index_update_deleted keeps the
+ * ranks, slg_index_remove_segment drops that segment's and keeps the dictionary (then a superset: harmless).
+ * SLG_ERR_UNSUPPORTED: a column with a non-finite value; an _i64 column with a value beyond +-2^53 (two i64 values
+ * the reference counts apart became one f64); R > SLG_MAX_AGG_RANKS. */
+int64_t slg_index_rank_agg_field(slg_index *index, int agg_field_id);
 
 /* One aggregation node.  A node is a root (parent == -1) or the child of an EARLIER bucket root (terms,
  * histogram or range); children have no children.  A child under a bucket collects the doc once per parent
@@ -665,6 +684,28 @@ int slg_index_remove_agg_field(slg_index *index, int agg_field_id);
  *   SLG_AGG_STATS      numeric column: count, min, max, sum over EVERY value of every collected doc (:1426-1441);
  *                      `missing` as above.  value_count, min, max, sum and avg follow on the host; extended_stats
  *                      (m2) is not built.
+ * Value nodes: order and identity questions over the values of the collected docs, answered from the value ranks
+ * of the column (slg_index_rank_agg_field) into a table of 8-byte cells (slg_batch_fetch_agg_values):
+ *   SLG_AGG_CARDINALITY      keyword or RANKED numeric column: the number of distinct values over every value of
+ *                      every collected doc (:1508-1556; exact, a HashSet — precision_threshold is carried but
+ *                      never used, :2688-2692).  A doc without a value contributes `missing` if has_missing: the
+ *                      key missing_ord of a keyword column as for terms, the f64 `missing` of a numeric one
+ *                      (its rank when the dictionary holds it, one rank beyond R otherwise).  Root, or child of a
+ *                      bucket root: one set per parent bucket the doc was counted in.  Table: parent_rows x 1.
+ *   SLG_AGG_PERCENTILES      RANKED numeric column, ROOT ONLY (as a child: SLG_ERR_UNSUPPORTED).  percents in
+ *                      from[0 .. n_ranges), 1 <= n_ranges <= SLG_MAX_AGG_RANGES.  Over the sorted multiset vals of
+ *                      every value (`missing` as above) with n elements: rank = (clamp(p, 0, 100) / 100) * (n - 1)
+ *                      in IEEE f64, low = floor, high = ceil (:529-532).  Table: 1 x (1 + 2 * n_ranges): n, then
+ *                      per percent the bits of vals[low] and vals[high].  The host returns vals[low] when low ==
+ *                      high, else vals[low] * (1 - w) + vals[high] * w with w = rank - low (:533-537); 0.0 when
+ *                      n == 0 (:523-525).  A `missing` the dictionary does not hold takes a virtual rank at its
+ *                      lower bound (the ranks at or above it shift by one): no dictionary is rebuilt per batch.
+ *   SLG_AGG_PERCENTILE_RANKS numeric column (ranks not needed), targets in from[0 .. n_ranges).  Table:
+ *                      parent_rows x (1 + n_ranges): n, then per target the count of values <= target (:552).
+ *                      The host returns count / max(n, 1) * 100, 0.0 when n == 0 (:548-553).  Root or child.
+ * ANOTHER DELIBERATE DEVIATION: the reference's quantiles are exact up to PERCENTILE_EXACT_LIMIT = 256 values
+ * and a t-digest estimate beyond (:472-545).  The device is exact at any n: it equals the reference where the
+ * reference is exact and is never further from the truth elsewhere.
  * Everything after the tables is the caller's: ordering terms buckets (count desc, key string asc), size,
  * min_doc_count, extended_bounds, histogram keys id * interval + offset, pipeline aggregations.
  *
@@ -685,8 +726,8 @@ typedef struct {
   uint32_t missing_ord;     /* SLG_AGG_TERMS */
   uint32_t has_hard_bounds; /* SLG_AGG_HISTOGRAM */
   double interval, offset, hard_min, hard_max;
-  uint32_t n_ranges;        /* SLG_AGG_RANGE */
-  double from[SLG_MAX_AGG_RANGES], to[SLG_MAX_AGG_RANGES];
+  uint32_t n_ranges;        /* SLG_AGG_RANGE; the percents / targets of SLG_AGG_PERCENTILES / _PERCENTILE_RANKS */
+  double from[SLG_MAX_AGG_RANGES], to[SLG_MAX_AGG_RANGES]; /* (percents and targets: from[]) */
 } slg_agg_node;
 typedef struct {
   uint32_t n_nodes; /* 1 .. SLG_MAX_AGGS */
@@ -695,12 +736,13 @@ typedef struct {
 /* A node's table is parent_rows x rows, parent-major (parent_rows = 1 for a root, else the parent's rows).
  * rows: terms n_ords (+ 1 when missing_ord == n_ords); histogram the dense id range that the column's finite
  * minimum and maximum, `missing` and the hard bounds allow (the bucket formula is monotone), row i = id
- * first_id + i; range n_ranges; stats 1.  offset: the table's first cell in the query's count table (bucket
- * kinds) or stats table (is_stats). */
+ * first_id + i; range n_ranges; stats 1; cardinality 1; percentile_ranks 1 + n_ranges; percentiles
+ * 1 + 2 * n_ranges.  offset: the table's first cell in the query's count table (bucket kinds), stats table
+ * (is_stats == 1) or value table (is_stats == 2). */
 typedef struct {
   uint32_t parent_rows, rows;
   int64_t first_id; /* histogram: the id of row 0; else 0 */
-  uint32_t is_stats;
+  uint32_t is_stats; /* 0 count table, 1 stats table, 2 value table */
   uint64_t offset;
 } slg_agg_layout;
 typedef struct {
@@ -711,11 +753,16 @@ typedef struct {
  * aggregation spec for the whole batch.  Every query shape those two take is accepted; the batch runs through
  * slg_batch_run / _fetch / _matched_counts as any sorted batch.  Checked before anything else, without an
  * index: aggs NULL, n_nodes == 0, an unknown kind, a parent that is not an earlier bucket root, a
- * non-positive or non-finite interval, a non-finite offset / missing, a NaN bound, n_ranges == 0:
- * SLG_ERR_INVALID; n_nodes > SLG_MAX_AGGS or n_ranges > SLG_MAX_AGG_RANGES: SLG_ERR_UNSUPPORTED.  Against
+ * non-positive or non-finite interval, a non-finite offset / missing, a NaN bound, percent or target,
+ * n_ranges == 0 (range, percentiles, percentile_ranks): SLG_ERR_INVALID; n_nodes > SLG_MAX_AGGS, n_ranges >
+ * SLG_MAX_AGG_RANGES or a percentiles node with a parent: SLG_ERR_UNSUPPORTED.  Against
  * the index: an unknown field id, a field without a column for every segment, a field of the wrong kind
- * for its node, missing_ord > n_ords: SLG_ERR_INVALID; a numeric column with a non-finite value, or more than
- * SLG_MAX_AGG_CELLS cells per query: SLG_ERR_UNSUPPORTED.  Aggregations are not built on cursor, hybrid,
+ * for its node, missing_ord > n_ords, a numeric field without ranks under a cardinality or percentiles node
+ * (slg_index_rank_agg_field): SLG_ERR_INVALID; a numeric column with a non-finite value, more than
+ * SLG_MAX_AGG_CELLS cells per query (value cells count too), or more than SLG_MAX_AGG_SCRATCH_WORDS words of
+ * value-node scratch per query (parent_rows x ceil(ranks / 32) per cardinality node, plus the fine tables of a
+ * percentiles node: min(32, 2 * n_ranges) << max(0, ceil_log2(ranks) - 12) when that shift is > 0):
+ * SLG_ERR_UNSUPPORTED.  Aggregations are not built on cursor, hybrid,
  * vector-only, sharded or coalesced batches (slg_batch_run_sharded* refuses an aggregation batch:
  * SLG_ERR_UNSUPPORTED). */
 slg_batch *slg_batch_prepare_aggs(slg_index *index, uint32_t nq, const uint32_t *q_offsets,
@@ -730,6 +777,10 @@ int slg_batch_agg_layout(const slg_batch *batch, slg_agg_layout *out);
 /* The tables of the batch's last run: counts [nq x count_cells], stats [nq x stats_cells] (either may be
  * NULL when it has no cells); waits for the batch. */
 int slg_batch_fetch_aggs(slg_batch *batch, uint64_t *counts, slg_agg_stats *stats);
+/* The value tables of the batch's last run: values [nq x value_cells], value_cells = the sum of parent_rows * rows
+ * over the value nodes (is_stats == 2), in node order; waits for the batch.  Counts, n and the percentile cells
+ * (bits of an f64) are exact and identical from run to run: nothing here depends on an order. */
+int slg_batch_fetch_agg_values(slg_batch *batch, uint64_t *values);
 /* One-shot form: slg_search_batch_sorted with an aggregation spec (sort_or_null == NULL: score order);
  * counts / stats are sized by the caller from the spec (a prepared batch tells through
  * slg_batch_agg_layout); out_matched ([nq]) may be NULL. */
@@ -738,6 +789,14 @@ int slg_search_batch_aggs(slg_index *index, const slg_query *queries, uint32_t n
                           const slg_sort_spec *sort_or_null, const slg_agg_spec *aggs, uint32_t k, int strategy,
                           uint32_t *out_doc, uint32_t *out_seg, float *out_score, uint32_t *out_count,
                           uint64_t *out_matched, uint64_t *counts, slg_agg_stats *stats);
+/* slg_search_batch_aggs with the value tables (values: [nq x value_cells], may be NULL without value nodes).
+ * slg_search_batch_aggs itself refuses a spec with value nodes (SLG_ERR_INVALID): it has nowhere to put them. */
+int slg_search_batch_agg_values(slg_index *index, const slg_query *queries, uint32_t nq,
+                                const slg_score_plans *plans_or_null, const int32_t *q_filter_or_null,
+                                const slg_sort_spec *sort_or_null, const slg_agg_spec *aggs, uint32_t k,
+                                int strategy, uint32_t *out_doc, uint32_t *out_seg, float *out_score,
+                                uint32_t *out_count, uint64_t *out_matched, uint64_t *counts, slg_agg_stats *stats,
+                                uint64_t *values);
 
 /* ---- request coalescer ------------------------------------------------------------------------------
  * searchlite has no batch API: IndexReader::search takes one request (api/reader.rs:2539) and the HTTP

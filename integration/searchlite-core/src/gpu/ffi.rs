@@ -62,6 +62,11 @@ pub const SLG_AGG_TERMS: i32 = 0;
 pub const SLG_AGG_HISTOGRAM: i32 = 1;
 pub const SLG_AGG_RANGE: i32 = 2;
 pub const SLG_AGG_STATS: i32 = 3;
+pub const SLG_AGG_CARDINALITY: i32 = 4;
+pub const SLG_AGG_PERCENTILES: i32 = 5;
+pub const SLG_AGG_PERCENTILE_RANKS: i32 = 6;
+pub const SLG_MAX_AGG_SCRATCH_WORDS: u32 = 1 << 19;
+pub const SLG_MAX_AGG_RANKS: u32 = 1 << 24;
 #[repr(C)] #[derive(Clone, Copy)] pub struct slg_agg_node {
     pub kind: i32, pub field: i32, pub parent: i32, pub has_missing: u32, pub missing: f64, pub missing_ord: u32,
     pub has_hard_bounds: u32, pub interval: f64, pub offset: f64, pub hard_min: f64, pub hard_max: f64,
@@ -224,6 +229,8 @@ extern "C" {
     pub fn slg_index_add_agg_field_ord(index: *mut slg_index, seg_offsets: *const *const u32,
         seg_ords: *const *const u32, n_ords: u32) -> c_int;
     pub fn slg_index_remove_agg_field(index: *mut slg_index, agg_field_id: c_int) -> c_int;
+    // the value ranks of a column (cardinality and percentiles nodes over a numeric field): the distinct count or < 0
+    pub fn slg_index_rank_agg_field(index: *mut slg_index, agg_field_id: c_int) -> i64;
     pub fn slg_batch_prepare_aggs(index: *mut slg_index, nq: u32, q_offsets: *const u32, q_term_ids: *const u32,
         q_weights: *const c_float, plans_or_null: *const slg_score_plans, q_filter_or_null: *const i32,
         sort_or_null: *const slg_sort_spec, aggs: *const slg_agg_spec, k: u32, strategy: c_int) -> *mut slg_batch;
@@ -234,6 +241,13 @@ extern "C" {
         aggs: *const slg_agg_spec, k: u32, strategy: c_int, out_doc: *mut u32, out_seg: *mut u32,
         out_score: *mut c_float, out_count: *mut u32, out_matched: *mut u64, counts: *mut u64,
         stats: *mut slg_agg_stats) -> c_int;
+    // the value tables (slg_agg_layout.is_stats == 2) of cardinality, percentiles and percentile_ranks nodes
+    pub fn slg_batch_fetch_agg_values(batch: *mut slg_batch, values: *mut u64) -> c_int;
+    pub fn slg_search_batch_agg_values(index: *mut slg_index, queries: *const slg_query, nq: u32,
+        plans_or_null: *const slg_score_plans, q_filter_or_null: *const i32, sort_or_null: *const slg_sort_spec,
+        aggs: *const slg_agg_spec, k: u32, strategy: c_int, out_doc: *mut u32, out_seg: *mut u32,
+        out_score: *mut c_float, out_count: *mut u32, out_matched: *mut u64, counts: *mut u64,
+        stats: *mut slg_agg_stats, values: *mut u64) -> c_int;
     pub fn slg_batch_matched_counts(batch: *mut slg_batch, out_matched: *mut u64) -> c_int;
     pub fn slg_search_batch_sorted(index: *mut slg_index, queries: *const slg_query, nq: u32,
         plans_or_null: *const slg_score_plans, q_filter_or_null: *const i32, sort: *const slg_sort_spec, k: u32,

@@ -676,8 +676,12 @@ fn min_should_match(m: &QueryMatcher) -> Option<u32> {
   }
 }
 
-/// The aggregation trees slg_batch_prepare_aggs takes (include/searchlite_gpu.h, "aggregations"): four kinds,
-/// two levels, at most SLG_MAX_AGGS nodes, no sampling.  Unverified, as all of this shim.
+/// The aggregation trees slg_batch_prepare_aggs takes (include/searchlite_gpu.h, "aggregations"): terms,
+/// histogram, range, stats and the value kinds cardinality, percentiles (a root only) and percentile_ranks (at
+/// most SLG_MAX_AGG_RANGES percents / targets), two levels, at most SLG_MAX_AGGS nodes, no sampling.  The caller
+/// ranks the numeric column of a cardinality or percentiles node once (slg_index_rank_agg_field) and reads the
+/// value tables with slg_batch_fetch_agg_values.  Percentiles over more than 256 values are exact on the device
+/// where the reference estimates with a t-digest.  Unverified, as all of this shim.
 fn aggs_fit_device(aggs: &std::collections::BTreeMap<String, crate::api::types::Aggregation>) -> bool {
   use crate::api::types::Aggregation as A;
   fn leaf_ok(a: &A) -> bool {
@@ -685,8 +689,9 @@ fn aggs_fit_device(aggs: &std::collections::BTreeMap<String, crate::api::types::
       A::Terms(t) => t.sampling.is_none() && t.aggs.is_empty(),
       A::Histogram(h) => h.sampling.is_none() && h.aggs.is_empty(),
       A::Range(r) => r.sampling.is_none() && r.aggs.is_empty() && r.ranges.len() <= ffi::SLG_MAX_AGG_RANGES,
-      A::Stats(_) => true,
-      _ => false,
+      A::Stats(_) | A::Cardinality(_) => true,
+      A::PercentileRanks(p) => !p.values.is_empty() && p.values.len() <= ffi::SLG_MAX_AGG_RANGES,
+      _ => false,  // (percentiles is a root only)
     }
   }
   let mut nodes = 0usize;
@@ -695,7 +700,15 @@ fn aggs_fit_device(aggs: &std::collections::BTreeMap<String, crate::api::types::
       A::Terms(t) if t.sampling.is_none() => &t.aggs,
       A::Histogram(h) if h.sampling.is_none() => &h.aggs,
       A::Range(r) if r.sampling.is_none() && r.ranges.len() <= ffi::SLG_MAX_AGG_RANGES => &r.aggs,
-      A::Stats(_) => {
+      A::Stats(_) | A::Cardinality(_) => {
+        nodes += 1;
+        continue;
+      }
+      A::Percentiles(p) if p.percents.as_ref().map_or(true, |v| !v.is_empty() && v.len() <= ffi::SLG_MAX_AGG_RANGES) => {
+        nodes += 1;
+        continue;
+      }
+      A::PercentileRanks(p) if !p.values.is_empty() && p.values.len() <= ffi::SLG_MAX_AGG_RANGES => {
         nodes += 1;
         continue;
       }
@@ -745,9 +758,10 @@ pub(crate) fn gpu_eligible(
     return None;
   }
   // Aggregations run on the device (slg_batch_prepare_aggs) when the tree fits what is built there: terms,
-  // histogram, range and stats over registered columns, a root or the child of a bucket root (two levels), at
+  // histogram, range, stats, cardinality, percentiles (root only) and percentile_ranks over registered columns, a
+  // root or the child of a bucket root (two levels), at
   // most ffi::SLG_MAX_AGGS nodes, no `sampling`; anything else (significant_terms, rare_terms, date_*,
-  // composite, filter, percentiles, cardinality, top_hits, pipeline aggregations as NODES — they are applied on
+  // composite, filter, extended_stats, top_hits, pipeline aggregations as NODES — they are applied on
   // the host to the shaped buckets —, deeper trees) keeps the request on the CPU collectors.  Not with a cursor:
   // cursor batches take no aggregations.  The caller maps every segment's keyword dictionary
   // (index/fastfields.rs:711-734) to ONE dictionary per field at staging time (sorted union of the segments'

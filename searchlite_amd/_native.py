@@ -31,6 +31,10 @@ MAX_AGG_RANGES = 16
 MAX_AGG_CELLS = 65536
 AGG_LDS_BYTES = 32768
 AGG_TERMS, AGG_HISTOGRAM, AGG_RANGE, AGG_STATS = 0, 1, 2, 3
+AGG_CARDINALITY, AGG_PERCENTILES, AGG_PERCENTILE_RANKS = 4, 5, 6
+MAX_AGG_SCRATCH_WORDS = 1 << 19
+AGG_PCT_LDS_BYTES = 16384
+MAX_AGG_RANKS = 1 << 24
 RESCORE_TOTAL, RESCORE_MULTIPLY, RESCORE_SUM, RESCORE_MAX, RESCORE_MIN = 0, 1, 2, 3, 4
 MAX_RESCORE_WINDOW = 1024
 BOOL_MUST, BOOL_SHOULD, BOOL_MUST_NOT = 0, 1, 2
@@ -137,7 +141,8 @@ class AggSpec(C.Structure):
 
 
 class AggLayout(C.Structure):
-    """slg_agg_layout: a node's table is parent_rows x rows at `offset` of the count or the stats table."""
+    """slg_agg_layout: a node's table is parent_rows x rows at `offset` of the count (is_stats 0), the stats (1) or
+    the value table (2)."""
     _fields_ = [("parent_rows", C.c_uint32), ("rows", C.c_uint32), ("first_id", C.c_int64),
                 ("is_stats", C.c_uint32), ("offset", C.c_uint64)]
 
@@ -310,9 +315,12 @@ def load():
         "slg_index_add_agg_field_i64": (i32, [vp, vp, vp]),
         "slg_index_add_agg_field_ord": (i32, [vp, vp, vp, u32]),
         "slg_index_remove_agg_field": (i32, [vp, i32]),
+        "slg_index_rank_agg_field": (C.c_int64, [vp, i32]),
         "slg_batch_prepare_aggs": (vp, [vp, u32, vp, vp, vp, vp, vp, vp, vp, u32, i32]),
         "slg_batch_agg_layout": (i32, [vp, vp]),
         "slg_batch_fetch_aggs": (i32, [vp, vp, vp]),
+        "slg_batch_fetch_agg_values": (i32, [vp, vp]),
+        "slg_search_batch_agg_values": (i32, [vp, vp, u32, vp, vp, vp, vp, u32, i32, vp, vp, vp, vp, vp, vp, vp, vp]),
         "slg_search_batch_aggs": (i32, [vp, vp, u32, vp, vp, vp, vp, u32, i32, vp, vp, vp, vp, vp, vp, vp]),
         "slg_batch_run": (i32, [vp]),
         "slg_batch_set_stream": (i32, [vp, vp]),

@@ -5,10 +5,13 @@ work and lives here, a restatement of the reference's finish / finalize steps (q
 terms buckets ordered by count descending, then key STRING ascending (terms_bucket_cmp, :2469-2478), `size`
 and `min_doc_count` (default 1); histogram keys id * interval + offset, `min_doc_count` (default 0 with
 bounds, else 1), zero buckets over extended_bounds (or hard_bounds), ascending; range buckets in request order
-with their key string or {"from", "to"}; stats with avg = sum / count (0.0 when empty).
+with their key string or {"from", "to"}; stats with avg = sum / count (0.0 when empty); cardinality {"value": n};
+percentiles and percentile_ranks {"values": {key: f64}} keyed by the percent / target as Rust's `format!("{p}")`
+prints an f64 (:3245-3262), percentiles interpolated as QuantileState::percentile does (:529-537) — over ALL
+values: the device is exact at any n, where the reference switches to a t-digest estimate above 256 values.
 
-A request is the reference's `aggs` map: name -> {"type": "terms" | "histogram" | "range" | "stats",
-"field": ..., ..., "aggs": {...children...}}.  Maps are walked in name order, as the reference's BTreeMaps.
+A request is the reference's `aggs` map: name -> {"type": "terms" | "histogram" | "range" | "stats" | "cardinality"
+| "percentiles" | "percentile_ranks", "field": ..., ..., "aggs": {...children...}}.  Maps are walked in name order, as the reference's BTreeMaps.
 """
 from __future__ import annotations
 
@@ -20,7 +23,48 @@ import numpy as np
 
 from . import _native as N
 
-KINDS = {"terms": N.AGG_TERMS, "histogram": N.AGG_HISTOGRAM, "range": N.AGG_RANGE, "stats": N.AGG_STATS}
+KINDS = {"terms": N.AGG_TERMS, "histogram": N.AGG_HISTOGRAM, "range": N.AGG_RANGE, "stats": N.AGG_STATS,
+         "cardinality": N.AGG_CARDINALITY, "percentiles": N.AGG_PERCENTILES, "percentile_ranks": N.AGG_PERCENTILE_RANKS}
+BUCKET_TYPES = ("terms", "histogram", "range")
+DEFAULT_PERCENTS = [1.0, 5.0, 25.0, 50.0, 75.0, 95.0, 99.0]  # default_percentiles_list (:3376-3378)
+
+
+def rust_f64(x: float) -> str:
+    """format!("{x}") of an f64: the shortest digits that round-trip, never an exponent, and no ".0" on a whole
+    number (50.0 -> "50", 99.9 -> "99.9", 1e21 -> "1000000000000000000000", -0.0 -> "-0")."""
+    x = float(x)
+    if math.isnan(x):
+        return "NaN"
+    if math.isinf(x):
+        return "inf" if x > 0 else "-inf"
+    r = repr(x)
+    if "e" in r or "E" in r:
+        from decimal import Decimal
+        r = format(Decimal(r), "f")
+    if r.endswith(".0"):
+        r = r[:-2]
+    return r
+
+
+def node_percents(body: dict) -> List[float]:
+    """the percents of a percentiles body (default list when absent) / the targets of a percentile_ranks body"""
+    if body["type"] == "percentiles":
+        return [float(p) for p in (body["percents"] if body.get("percents") is not None else DEFAULT_PERCENTS)]
+    return [float(v) for v in body["values"]]
+
+
+def percentile_of(n: int, low_bits: int, high_bits: int, pct: float) -> float:
+    """QuantileState::percentile (:522-537) from the device's cells: n, the bits of vals[low] and vals[high]"""
+    if n == 0:
+        return 0.0
+    lo = float(np.uint64(low_bits).view(np.float64))
+    hi = float(np.uint64(high_bits).view(np.float64))
+    rank = max((min(max(float(pct), 0.0), 100.0) / 100.0) * (float(n) - 1.0), 0.0)
+    low, high = math.floor(rank), math.ceil(rank)
+    if low == high:
+        return lo
+    w = rank - float(low)
+    return lo * (1.0 - w) + hi * w
 STATS_DTYPE = np.dtype([("count", np.uint64), ("min", np.float64), ("max", np.float64), ("sum", np.float64)])
 
 
@@ -51,7 +95,7 @@ def agg_spec(aggs: Dict[str, dict], fields: Dict[str, dict]) -> AggPlan:
         nodes.append(dict(name=name, type=typ, body=body, parent=parent, keys=fields[body["field"]].get("keys")))
         me = len(nodes) - 1
         children = body.get("aggs") or {}
-        if children and (parent >= 0 or typ == "stats"):
+        if children and (parent >= 0 or typ not in BUCKET_TYPES):
             raise ValueError(f"aggregation {name!r}: only two levels under a bucket aggregation are built")
         for cname in sorted(children):
             add(cname, children[cname], me)
@@ -64,13 +108,18 @@ def agg_spec(aggs: Dict[str, dict], fields: Dict[str, dict]) -> AggPlan:
         body, n = nd["body"], spec.nodes[i]
         n.kind, n.field, n.parent = KINDS[nd["type"]], int(fields[body["field"]]["id"]), nd["parent"]
         missing = body.get("missing")
-        if nd["type"] == "terms":
+        if nd["type"] == "terms" or (nd["type"] == "cardinality" and nd["keys"] is not None):
             if missing is not None:
                 keys = list(nd["keys"] or [])
                 n.has_missing = 1
                 n.missing_ord = keys.index(str(missing)) if str(missing) in keys else len(keys)
         elif missing is not None:
             n.has_missing, n.missing = 1, float(missing)
+        if nd["type"] in ("percentiles", "percentile_ranks"):
+            xs = node_percents(body)
+            n.n_ranges = len(xs)
+            for r, x in enumerate(xs[:N.MAX_AGG_RANGES]):
+                n.from_[r] = x
         if nd["type"] == "histogram":
             n.interval, n.offset = float(body["interval"]), float(body.get("offset") or 0.0)
             hb = body.get("hard_bounds")
@@ -104,6 +153,18 @@ def shape(plan: AggPlan, layout: List[dict], tables: List[np.ndarray], q: int) -
         nd, body, tab = plan.nodes[i], plan.nodes[i]["body"], tables[i][q, prow]
         if nd["type"] == "stats":
             return _stats(tab[0])
+        if nd["type"] == "cardinality":  # :2688-2692
+            return {"type": "cardinality", "value": int(tab[0])}
+        if nd["type"] == "percentiles":  # :3245-3251 (a BTreeMap: a repeated key keeps its last value)
+            n = int(tab[0])
+            return {"type": "percentiles",
+                    "values": {rust_f64(p): percentile_of(n, int(tab[1 + 2 * j]), int(tab[2 + 2 * j]), p)
+                               for j, p in enumerate(node_percents(body))}}
+        if nd["type"] == "percentile_ranks":  # :547-553, :3253-3262
+            n = int(tab[0])
+            return {"type": "percentile_ranks",
+                    "values": {rust_f64(t): (float(int(tab[1 + j])) / float(max(n, 1))) * 100.0 if n else 0.0
+                               for j, t in enumerate(node_percents(body))}}
         children = [c for c in range(len(plan.nodes)) if plan.nodes[c]["parent"] == i]
 
         def bucket(key, row: Optional[int], count: int) -> dict:

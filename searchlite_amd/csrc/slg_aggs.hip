@@ -1,5 +1,6 @@
 // slg_aggs.hip — aggregation batches (slg_batch_prepare_aggs): the checks of a spec, the layout of its
-// tables, the launch of agg_kernel behind the batch's select kernel, and slg_batch_agg_layout / _fetch_aggs.
+// tables, the launch of agg_kernel (and, for a spec with value nodes, agg_values_kernel) behind the batch's select
+// kernel, and slg_batch_agg_layout / _fetch_aggs / _fetch_agg_values.
 #include "slg_host.hpp"
 
 #include <cmath>
@@ -11,10 +12,26 @@ using namespace slghost;
 static_assert(slg::kAggLdsBytes == SLG_AGG_LDS_BYTES && slg::kAggMaxRanges == SLG_MAX_AGG_RANGES, "header constants");
 static_assert(slg::kAggTerms == SLG_AGG_TERMS && slg::kAggHistogram == SLG_AGG_HISTOGRAM &&
                   slg::kAggRange == SLG_AGG_RANGE && slg::kAggStats == SLG_AGG_STATS, "header kinds");
+static_assert(slg::kAggCardinality == SLG_AGG_CARDINALITY && slg::kAggPercentiles == SLG_AGG_PERCENTILES &&
+                  slg::kAggPercentileRanks == SLG_AGG_PERCENTILE_RANKS && slg::kAggPctLdsBytes == SLG_AGG_PCT_LDS_BYTES,
+              "header value kinds");
 static_assert(sizeof(slg::AggStatDev) == 32 && sizeof(slg_agg_stats) == 32, "stats cells are 32 bytes");
 
 namespace {
 bool is_bucket(int32_t kind) { return kind == SLG_AGG_TERMS || kind == SLG_AGG_HISTOGRAM || kind == SLG_AGG_RANGE; }
+bool is_value(int32_t kind) {
+  return kind == SLG_AGG_CARDINALITY || kind == SLG_AGG_PERCENTILES || kind == SLG_AGG_PERCENTILE_RANKS;
+}
+uint64_t f64_key(double x) {  // = slg::agg_f64_key
+  uint64_t b;
+  std::memcpy(&b, &x, 8);
+  return (b >> 63) ? ~b : (b | 0x8000000000000000ull);
+}
+uint32_t ceil_log2(uint32_t n) {
+  uint32_t l = 0;
+  while (l < 32 && (1ull << l) < n) l++;
+  return l;
+}
 std::string node_name(uint32_t i) { return "agg node " + std::to_string(i); }
 
 // floor((val - offset) / interval), the reference's bucket_key (aggs/mod.rs:1162-1164) in IEEE f64 (host
@@ -28,15 +45,26 @@ void slghost::agg_check_spec(const slg_agg_spec *aggs) {
   if (aggs->n_nodes > SLG_MAX_AGGS) throw SlgError(SLG_ERR_UNSUPPORTED, "more than SLG_MAX_AGGS aggregation nodes");
   for (uint32_t i = 0; i < aggs->n_nodes; i++) {
     const slg_agg_node &n = aggs->nodes[i];
-    SLG_REQUIRE(n.kind == SLG_AGG_STATS || is_bucket(n.kind), node_name(i) + ": unknown kind");
+    SLG_REQUIRE(n.kind == SLG_AGG_STATS || is_bucket(n.kind) || is_value(n.kind), node_name(i) + ": unknown kind");
     if (n.parent != -1) {
       SLG_REQUIRE(n.parent >= 0 && (uint32_t)n.parent < i, node_name(i) + ": parent is not an earlier node");
       const slg_agg_node &pn = aggs->nodes[n.parent];
       SLG_REQUIRE(is_bucket(pn.kind), node_name(i) + ": parent is not a bucket node (terms, histogram, range)");
       SLG_REQUIRE(pn.parent == -1, node_name(i) + ": parent is not a root (two levels)");
     }
-    if (n.kind != SLG_AGG_TERMS && n.has_missing)
+    // (a cardinality node's `missing` is read for a numeric field only: checked against the index)
+    if (n.kind != SLG_AGG_TERMS && n.kind != SLG_AGG_CARDINALITY && n.has_missing)
       SLG_REQUIRE(std::isfinite(n.missing), node_name(i) + ": missing is not finite");
+    if (n.kind == SLG_AGG_PERCENTILES || n.kind == SLG_AGG_PERCENTILE_RANKS) {
+      const char *what = n.kind == SLG_AGG_PERCENTILES ? "percent" : "target";
+      SLG_REQUIRE(n.n_ranges >= 1, node_name(i) + ": needs at least one " + what);
+      if (n.n_ranges > SLG_MAX_AGG_RANGES)
+        throw SlgError(SLG_ERR_UNSUPPORTED, node_name(i) + ": more than SLG_MAX_AGG_RANGES " + what + "s");
+      for (uint32_t r = 0; r < n.n_ranges; r++)
+        SLG_REQUIRE(!std::isnan(n.from[r]), node_name(i) + ": " + what + " is NaN");
+      if (n.kind == SLG_AGG_PERCENTILES && n.parent != -1)
+        throw SlgError(SLG_ERR_UNSUPPORTED, node_name(i) + ": a percentiles node is a root (not built as a child)");
+    }
     if (n.kind == SLG_AGG_HISTOGRAM) {
       SLG_REQUIRE(std::isfinite(n.interval) && n.interval > 0.0, node_name(i) + ": interval must be positive and finite");
       SLG_REQUIRE(std::isfinite(n.offset), node_name(i) + ": offset is not finite");
@@ -63,13 +91,16 @@ void slghost::agg_attach(slg_batch *b, const slg_agg_spec &aggs) {
   std::vector<slg::ColumnDev> cols((size_t)nn * std::max<size_t>(n_segs, 1), slg::ColumnDev{nullptr, nullptr});
   const std::vector<slgplan::FscoreFieldView> fields = fscore_field_views(S);
   b->agg_layout.assign(nn, slg_agg_layout{});
-  uint64_t count_cells = 0, stats_cells = 0;
+  std::vector<const uint32_t *> rank_cols((size_t)nn * std::max<size_t>(n_segs, 1), nullptr);
+  uint64_t count_cells = 0, stats_cells = 0, value_cells = 0, card_words = 0, fine_words = 0, fine_total = 0;
+  uint32_t n_value = 0, n_pct = 0, n_walk1 = 0;
   for (uint32_t i = 0; i < nn; i++) {
     const slg_agg_node &n = aggs.nodes[i];
     const slgplan::FscoreFieldView &fd = slgplan::agg_field(fields, n.field, node_name(i) + ": ", "");
-    SLG_REQUIRE((n.kind == SLG_AGG_TERMS) == fd.keyword,
+    SLG_REQUIRE((n.kind == SLG_AGG_TERMS || (n.kind == SLG_AGG_CARDINALITY && fd.keyword)) == fd.keyword,
                 node_name(i) + ": field " + std::to_string(n.field) +
-                    (fd.keyword ? " is a keyword field (terms only)" : " is a numeric field (not for terms)"));
+                    (fd.keyword ? " is a keyword field (terms and cardinality only)"
+                                : " is a numeric field (not for terms)"));
     std::copy_n(slgplan::agg_field_rows(fd, (uint32_t)n_segs, "", ""), n_segs, cols.begin() + (size_t)i * n_segs);
     if (!fd.keyword && fd.non_finite)
       throw SlgError(SLG_ERR_UNSUPPORTED,
@@ -125,9 +156,73 @@ void slghost::agg_attach(slg_batch *b, const slg_agg_spec &aggs) {
     }
     if (rows == 0) rows = 1;  // (a keyword field without keys and without a missing row: one cell, never counted)
     const uint64_t parent_rows = n.parent < 0 ? 1u : b->agg_layout[n.parent].rows;
-    uint64_t &cells = n.kind == SLG_AGG_STATS ? stats_cells : count_cells;
+    if (is_value(n.kind)) {
+      n_value++;
+      d.n_ranges = n.n_ranges;
+      std::copy_n(n.from, SLG_MAX_AGG_RANGES, d.from);
+      d.shift_from = slg::kAggNoRank;
+      const AggFieldData &F = *S.agg_fields.at(n.field);
+      uint64_t R = fd.n_ords;
+      if (fd.keyword) {  // (cardinality) the ordinals are the ranks
+        if (n.has_missing) SLG_REQUIRE(n.missing_ord <= fd.n_ords, node_name(i) + ": missing_ord > n_ords");
+        d.miss_rank = n.missing_ord;
+        d.n_ranks = fd.n_ords + ((n.has_missing && n.missing_ord == fd.n_ords) ? 1u : 0u);
+        for (size_t s = 0; s < n_segs; s++) rank_cols[(size_t)i * n_segs + s] = cols[(size_t)i * n_segs + s].ords();
+      } else if (n.kind != SLG_AGG_PERCENTILE_RANKS) {
+        if (n.has_missing) SLG_REQUIRE(std::isfinite(n.missing), node_name(i) + ": missing is not finite");
+        SLG_REQUIRE(F.dict != nullptr, node_name(i) + ": agg field " + std::to_string(n.field) +
+                                           " has no value ranks (slg_index_rank_agg_field)");
+        for (size_t s = 0; s < n_segs; s++) {
+          SLG_REQUIRE(s < F.ranks.size() && F.ranks[s], node_name(i) + ": agg field " + std::to_string(n.field) +
+                                                            " has no value ranks for segment " + std::to_string(s));
+          rank_cols[(size_t)i * n_segs + s] = F.ranks[s]->as<const uint32_t>();
+        }
+        R = F.dict->keys.size();
+        d.n_ranks = (uint32_t)R;
+        d.dict = F.dict->vals.as<const double>();
+        if (n.has_missing) {
+          const uint64_t key = f64_key(n.missing);
+          const size_t lb = std::lower_bound(F.dict->keys.begin(), F.dict->keys.end(), key) - F.dict->keys.begin();
+          d.miss_rank = (uint32_t)lb;
+          if (lb == R || F.dict->keys[lb] != key) {  // not a value of the column: one more rank
+            d.n_ranks = (uint32_t)R + 1u;
+            // cardinality: beyond R; percentiles: a virtual rank at the lower bound, the ranks from there shift
+            if (n.kind == SLG_AGG_CARDINALITY) d.miss_rank = (uint32_t)R;
+            else d.shift_from = (uint32_t)lb;
+          }
+        }
+      }
+      d.n_ranks = std::max(d.n_ranks, 1u);
+      if (n.kind == SLG_AGG_CARDINALITY) {
+        n_walk1++;
+        d.wpr = (d.n_ranks + 31u) / 32u;
+        d.bm_off = (uint32_t)card_words;
+        card_words += parent_rows * d.wpr;
+      } else if (n.kind == SLG_AGG_PERCENTILE_RANKS) {
+        n_walk1++;
+        rows = 1u + n.n_ranges;
+      } else {
+        n_pct++;
+        rows = 1u + 2u * n.n_ranges;
+        const uint32_t lg = ceil_log2(d.n_ranks);
+        d.shift = lg > slg::kAggCoarseBits ? lg - slg::kAggCoarseBits : 0u;
+        if (d.shift) {  // the fine tables: in the LDS the coarse bins leave behind, or in the scratch slice
+          const uint64_t words = (uint64_t)std::min(32u, 2u * n.n_ranges) << d.shift;
+          fine_total += words;
+          d.fine_lds = words * 4 <= slg::kAggPctLdsBytes ? 1u : 0u;
+          if (!d.fine_lds) {
+            d.fine_off = (uint32_t)fine_words;  // (behind the bitmaps when those are global too: see below)
+            fine_words += words;
+          }
+        }
+      }
+      if (card_words + fine_total > SLG_MAX_AGG_SCRATCH_WORDS)
+        throw SlgError(SLG_ERR_UNSUPPORTED, "more than SLG_MAX_AGG_SCRATCH_WORDS words of value scratch per query (at " +
+                                                node_name(i) + ")");
+    }
+    uint64_t &cells = is_value(n.kind) ? value_cells : n.kind == SLG_AGG_STATS ? stats_cells : count_cells;
     if (rows > SLG_MAX_AGG_CELLS || parent_rows * rows > SLG_MAX_AGG_CELLS ||
-        count_cells + stats_cells + parent_rows * rows > SLG_MAX_AGG_CELLS)
+        count_cells + stats_cells + value_cells + parent_rows * rows > SLG_MAX_AGG_CELLS)
       throw SlgError(SLG_ERR_UNSUPPORTED, "more than SLG_MAX_AGG_CELLS aggregation cells per query (at " + node_name(i) + ")");
     d.rows = (uint32_t)rows;
     d.first_id = first_id;
@@ -136,7 +231,7 @@ void slghost::agg_attach(slg_batch *b, const slg_agg_spec &aggs) {
     lay.parent_rows = (uint32_t)parent_rows;
     lay.rows = (uint32_t)rows;
     lay.first_id = first_id;
-    lay.is_stats = n.kind == SLG_AGG_STATS ? 1u : 0u;
+    lay.is_stats = is_value(n.kind) ? 2u : n.kind == SLG_AGG_STATS ? 1u : 0u;
     lay.offset = cells;
     cells += parent_rows * rows;
   }
@@ -145,8 +240,23 @@ void slghost::agg_attach(slg_batch *b, const slg_agg_spec &aggs) {
   b->agg_count_cells = (uint32_t)count_cells;
   b->agg_stats_cells = (uint32_t)stats_cells;
   b->agg_lds = 4 * count_cells + sizeof(slg::AggStatDev) * stats_cells <= slg::kAggLdsBytes;
-  upload_image(b->d_agg_desc, &ix->pool, {image_part(nodes), image_part(cols)});
+  // the value nodes' homes (slg_aggs.hpp): value cells and bitmaps in LDS beside the percentiles region, or global
+  b->agg_value_nodes = n_value;
+  b->agg_value_cells = (uint32_t)value_cells;
+  b->agg_card_words = (uint32_t)card_words;
+  b->agg_walk1 = n_walk1 > 0;
+  b->agg_pct_lds = n_pct ? slg::kAggPctLdsBytes : 0u;
+  b->agg_x_lds = 8 * value_cells + 4 * card_words + b->agg_pct_lds <= slg::kAggLdsBytes;
+  if (!b->agg_x_lds)
+    for (slg::AggNodeDev &d : nodes)
+      if (d.kind == SLG_AGG_PERCENTILES && d.shift && !d.fine_lds) d.fine_off += (uint32_t)card_words;
+  b->agg_scratch_words = (uint32_t)((b->agg_x_lds ? 0u : card_words) + fine_words);
+  upload_image(b->d_agg_desc, &ix->pool, {image_part(nodes), image_part(cols), image_part(rank_cols)});
   const size_t nq = std::max<uint32_t>(b->nq, 1);
+  if (n_value) {
+    b->d_agg_values.alloc_pooled(&ix->pool, nq * std::max<size_t>(value_cells, 1) * 8);
+    b->d_agg_scratch.alloc_pooled(&ix->pool, nq * std::max<size_t>(b->agg_scratch_words, 1) * 4);
+  }
   b->d_agg_counts.alloc_pooled(&ix->pool, nq * std::max<size_t>(count_cells, 1) * 4);
   b->d_agg_stats.alloc_pooled(&ix->pool, nq * std::max<size_t>(stats_cells, 1) * sizeof(slg::AggStatDev));
 }
@@ -166,7 +276,9 @@ void slghost::agg_launch(slg_batch *b, hipStream_t st) {
   p.stats = b->d_agg_stats.as<slg::AggStatDev>();
   // a sorted batch's select counted the accepted docs; in score order this kernel does
   p.out_matched = b->sorted ? nullptr : b->d_matched.as<unsigned long long>();
-  if (b->agg_lds) {
+  if (b->agg_value_nodes == p.n_nodes && !p.out_matched) {
+    // (nothing but value nodes, and nobody to count for)
+  } else if (b->agg_lds) {
     const size_t lds = (size_t)p.stats_cells * sizeof(slg::AggStatDev) + (size_t)p.count_cells * 4;
     launch_kernel_lds(slg::agg_kernel<true>, p, dim3(b->nq), slg::kAggThreads, lds, st);
   } else {
@@ -174,6 +286,29 @@ void slghost::agg_launch(slg_batch *b, hipStream_t st) {
     SLG_HIP(hipMemsetAsync(b->d_agg_stats.p, 0,
                            (size_t)b->nq * std::max<size_t>(p.stats_cells, 1) * sizeof(slg::AggStatDev), st));
     launch_kernel_lds(slg::agg_kernel<false>, p, dim3(b->nq), slg::kAggThreads, 0, st);
+  }
+  if (b->agg_value_nodes == 0) return;
+  slg::AggValueParams v{};
+  fill_candidates(v, b);
+  v.nodes = p.nodes;
+  v.cols = p.cols;
+  v.rank_cols = reinterpret_cast<const uint32_t *const *>(p.cols + (size_t)p.n_nodes * std::max<size_t>(v.n_segs, 1));
+  v.n_nodes = p.n_nodes;
+  v.nq = b->nq;
+  v.value_cells = b->agg_value_cells;
+  v.card_words = b->agg_card_words;
+  v.pct_words = b->agg_pct_lds / 4;
+  v.scratch_words = b->agg_scratch_words;
+  v.walk1 = b->agg_walk1 ? 1u : 0u;
+  v.values = b->d_agg_values.as<unsigned long long>();
+  v.scratch = b->d_agg_scratch.as<uint32_t>();
+  if (v.scratch_words) SLG_HIP(hipMemsetAsync(v.scratch, 0, (size_t)b->nq * v.scratch_words * 4, st));
+  if (b->agg_x_lds) {
+    const size_t lds = (size_t)b->agg_pct_lds + 8 * (size_t)v.value_cells + 4 * (size_t)v.card_words;
+    launch_kernel_lds(slg::agg_values_kernel<true>, v, dim3(b->nq), slg::kAggThreads, lds, st);
+  } else {
+    SLG_HIP(hipMemsetAsync(v.values, 0, (size_t)b->nq * std::max<size_t>(v.value_cells, 1) * 8, st));
+    launch_kernel_lds(slg::agg_values_kernel<false>, v, dim3(b->nq), slg::kAggThreads, b->agg_pct_lds, st);
   }
 }
 
@@ -185,6 +320,22 @@ int slg_batch_agg_layout(const slg_batch *b, slg_agg_layout *out) {
     SLG_REQUIRE(b->aggs, "not an aggregation batch (slg_batch_prepare_aggs)");
     SLG_REQUIRE(out != nullptr, "out is NULL");
     std::copy(b->agg_layout.begin(), b->agg_layout.end(), out);
+  });
+}
+
+int slg_batch_fetch_agg_values(slg_batch *b, uint64_t *values) {
+  return guarded([&] {
+    SLG_REQUIRE_LIVE(b);
+    SLG_REQUIRE(b->aggs, "not an aggregation batch (slg_batch_prepare_aggs)");
+    SLG_REQUIRE(b->launched, "the batch has not run");
+    const size_t nv = (size_t)b->nq * b->agg_value_cells;
+    SLG_REQUIRE(nv == 0 || values != nullptr, "values is NULL");
+    if (nv == 0) return;
+    DeviceGuard g(b->idx->device);
+    const hipStream_t st = locked_stream(b);
+    static_assert(sizeof(uint64_t) == sizeof(unsigned long long), "value cells are 8 bytes");
+    SLG_HIP(hipMemcpyAsync(values, b->d_agg_values.p, nv * 8, hipMemcpyDeviceToHost, st));
+    SLG_HIP(wait_stream(st));
   });
 }
 

@@ -145,6 +145,7 @@ void slghost::release_batch_buffers(slg_batch *b, bool to_pool) {
                     &b->d_q_scored, &b->d_q_filter, &b->d_cand, &b->d_slice_cbeg, &b->d_slice_ccnt,
                     &b->d_out, &b->d_stamps, &b->d_blk_skip, &b->d_gather, &b->d_merged, &b->d_q_cand,
                     &b->d_hy_keys, &b->d_hy_work, &b->d_agg_desc, &b->d_agg_counts, &b->d_agg_stats,
+                    &b->d_agg_values, &b->d_agg_scratch,
                     &b->d_rs_desc, &b->d_rs_side, &b->d_bool_desc, &b->d_phrase_desc, &b->d_booltree_desc, &b->d_fscore_desc,
                     &b->d_cl_desc, &b->d_cl_side};
   for (DevBuf *d : bufs) {
@@ -751,6 +752,7 @@ struct HostOut {
   uint8_t *seen = nullptr;
   uint64_t *agg_counts = nullptr;  // (an aggregation batch)
   slg_agg_stats *agg_stats = nullptr;
+  uint64_t *agg_values = nullptr;
   float *first_score = nullptr, *rescore_score = nullptr;  // (a rescore batch)
   uint32_t *rescored = nullptr;
   void *const *collapse = nullptr;  // (a collapse batch) the 14 arrays of slg_batch_fetch_collapse, in its order
@@ -763,6 +765,7 @@ int run_to_host(slg_batch *b, const HostOut &o) {
   if (rc == SLG_OK) rc = slg_batch_fetch(b, o.doc, o.seg, o.score, o.count, o.stats);
   if (rc == SLG_OK && o.matched) rc = slg_batch_matched_counts(b, o.matched);
   if (rc == SLG_OK && b->aggs) rc = slg_batch_fetch_aggs(b, o.agg_counts, o.agg_stats);
+  if (rc == SLG_OK && b->aggs && b->agg_value_nodes) rc = slg_batch_fetch_agg_values(b, o.agg_values);
   if (rc == SLG_OK && b->rescore) rc = slg_batch_fetch_rescore(b, o.first_score, o.rescore_score, o.rescored);
   if (rc == SLG_OK && o.seen) rc = slg_batch_cursor_seen(b, o.seen);
   if (rc == SLG_OK && b->collapse) {
@@ -833,16 +836,34 @@ slg_batch *slg_batch_prepare_aggs(slg_index *ix, uint32_t nq, const uint32_t *q_
   return prepare_impl(r);
 }
 
+int slg_search_batch_agg_values(slg_index *ix, const slg_query *queries, uint32_t nq, const slg_score_plans *plans,
+                                const int32_t *q_filter, const slg_sort_spec *sort, const slg_agg_spec *aggs, uint32_t k,
+                                int strategy, uint32_t *out_doc, uint32_t *out_seg, float *out_score,
+                                uint32_t *out_count, uint64_t *out_matched, uint64_t *counts, slg_agg_stats *stats,
+                                uint64_t *values) {
+  FlatQueries fq;
+  const int rc = flatten_queries(ix, queries, nq, &fq);
+  if (rc != SLG_OK) return rc;
+  HostOut o{out_doc, out_seg, out_score, out_count, nullptr, out_matched, nullptr, counts, stats};
+  o.agg_values = values;
+  return run_to_host(slg_batch_prepare_aggs(ix, nq, fq.offs.data(), fq.tids.data(), fq.ws.data(), plans, q_filter,
+                                            sort, aggs, k, strategy),
+                     o);
+}
+
 int slg_search_batch_aggs(slg_index *ix, const slg_query *queries, uint32_t nq, const slg_score_plans *plans,
                           const int32_t *q_filter, const slg_sort_spec *sort, const slg_agg_spec *aggs, uint32_t k,
                           int strategy, uint32_t *out_doc, uint32_t *out_seg, float *out_score, uint32_t *out_count,
                           uint64_t *out_matched, uint64_t *counts, slg_agg_stats *stats) {
-  FlatQueries fq;
-  const int rc = flatten_queries(ix, queries, nq, &fq);
+  // this form has nowhere to put a value table: it refuses the spec and drops nothing silently
+  const int rc = guarded([&] {
+    for (uint32_t i = 0; aggs && i < aggs->n_nodes && i < SLG_MAX_AGGS; i++)
+      SLG_REQUIRE(aggs->nodes[i].kind < SLG_AGG_CARDINALITY || aggs->nodes[i].kind > SLG_AGG_PERCENTILE_RANKS,
+                  "agg node " + std::to_string(i) + " has a value table: use slg_search_batch_agg_values");
+  });
   if (rc != SLG_OK) return rc;
-  return run_to_host(slg_batch_prepare_aggs(ix, nq, fq.offs.data(), fq.tids.data(), fq.ws.data(), plans, q_filter,
-                                            sort, aggs, k, strategy),
-                     HostOut{out_doc, out_seg, out_score, out_count, nullptr, out_matched, nullptr, counts, stats});
+  return slg_search_batch_agg_values(ix, queries, nq, plans, q_filter, sort, aggs, k, strategy, out_doc, out_seg,
+                                     out_score, out_count, out_matched, counts, stats, nullptr);
 }
 
 slg_batch *slg_batch_prepare_rescore(slg_index *ix, uint32_t nq, const uint32_t *q_offsets, const uint32_t *q_term_ids,

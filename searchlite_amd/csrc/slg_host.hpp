@@ -350,6 +350,13 @@ struct SortFieldData {
 // minimum and maximum (a histogram's dense id range follows from them) and whether a non-finite one exists
 struct AggColumn {
   DevBuf offs, vals;   // offs empty: every doc of the segment has exactly one value (vals[doc])
+  size_t n_vals = 0;   // values in vals
+};
+// the value ranks of a numeric field (slg_index_rank_agg_field): the dictionary of its distinct values, shared by
+// the states that hold the field
+struct AggRankDict {
+  std::vector<uint64_t> keys;  // sorted order-preserving keys of the distinct values (agg_f64_key)
+  DevBuf vals;                 // f64[keys.size()]: the values, in the same order
 };
 struct AggFieldData {
   int kind = 0;  // 1 numeric (f64 values), 2 keyword (u32 ordinals)
@@ -360,6 +367,9 @@ struct AggFieldData {
   // it lay beyond +-2^53 and was rounded by `as f64`
   bool from_i64 = false, i64_rounded = false;
   std::vector<std::shared_ptr<AggColumn>> per_seg;
+  // set by slg_index_rank_agg_field (numeric fields): the dictionary, and per segment u32[n_vals] beside vals
+  std::shared_ptr<AggRankDict> dict;
+  std::vector<std::shared_ptr<DevBuf>> ranks;  // [per_seg.size()]; null = no ranks for that segment
 };
 
 // the positions of a segment's postings (slg_index_set_positions): shared by the states that hold them
@@ -513,8 +523,12 @@ struct slg_batch {
   std::vector<slg_agg_layout> agg_layout;  // [n_nodes]
   uint32_t agg_count_cells = 0, agg_stats_cells = 0;
   bool agg_lds = false;              // the tables fit SLG_AGG_LDS_BYTES
-  DevBuf d_agg_desc;                 // slg::AggNodeDev[n_nodes], then slg::ColumnDev[n_nodes * n_segs]
+  DevBuf d_agg_desc;                 // slg::AggNodeDev[n_nodes], slg::ColumnDev[n_nodes * n_segs], then the rank columns
   DevBuf d_agg_counts, d_agg_stats;  // u32[nq * count_cells], slg::AggStatDev[nq * stats_cells]
+  // value nodes (cardinality, percentiles, percentile_ranks): agg_values_kernel behind agg_kernel
+  uint32_t agg_value_nodes = 0, agg_value_cells = 0, agg_card_words = 0, agg_scratch_words = 0, agg_pct_lds = 0;
+  bool agg_walk1 = false, agg_x_lds = false;  // a cardinality / percentile_ranks node; cells and bitmaps fit LDS
+  DevBuf d_agg_values, d_agg_scratch;         // u64[nq * value_cells], u32[nq * scratch_words]
   // rescore batch (slg_batch_prepare_rescore): rescore_kernel runs behind the first pass's last kernel and
   // rewrites the first rows of every query in place (slg_rescore.hip)
   bool rescore = false;

@@ -372,6 +372,7 @@ void reshape_per_segment(IndexState &ns, Op op) {
   for (auto &af : ns.agg_fields) {
     auto nf = std::make_shared<AggFieldData>(*af.second);
     op(nf->per_seg);
+    op(nf->ranks);
     af.second = std::move(nf);
   }
   for (auto &vf : ns.vfields) op(vf->per_seg);  // (the field objects of a new state are fresh copies)
@@ -394,9 +395,13 @@ size_t state_device_bytes(const IndexState &s) {
   for (auto &sf : s.sort_fields)
     for (auto &c : sf.second->per_seg)
       if (c) n += c->key[0].bytes + c->key[1].bytes + c->present.bytes;
-  for (auto &af : s.agg_fields)
+  for (auto &af : s.agg_fields) {
     for (auto &c : af.second->per_seg)
       if (c) n += c->offs.bytes + c->vals.bytes;
+    for (auto &r : af.second->ranks)
+      if (r) n += r->bytes;
+    if (af.second->dict) n += af.second->dict->vals.bytes;
+  }
   for (auto &vf : s.vfields) {
     n += vf->d_vsegs.bytes;
     for (auto &v : vf->per_seg)
@@ -943,6 +948,7 @@ int add_agg_field_impl(slg_index *ix, int kind, const uint32_t *const *seg_offse
       fd->n_ords = n_ords;
       fd->from_i64 = kind == 2;
       fd->per_seg.resize(n_segs);
+      fd->ranks.resize(n_segs);
       for (size_t s = 0; s < n_segs; s++) {
         const uint32_t n_docs = cur.segs[s]->n_docs;
         const uint32_t *offs = seg_offsets[s];
@@ -959,6 +965,7 @@ int add_agg_field_impl(slg_index *ix, int kind, const uint32_t *const *seg_offse
         const uint32_t first = offs ? offs[0] : 0u;
         const size_t nv = offs ? (size_t)offs[n_docs] - first : 0;
         auto col = std::make_shared<AggColumn>();
+        col->n_vals = nv;
         if (kind == 3) {
           const uint32_t *v = nv ? static_cast<const uint32_t *>(seg_values[s]) + first : nullptr;
           for (size_t i = 0; i < nv; i++) SLG_REQUIRE(v[i] < n_ords, "keyword ordinal >= n_ords");
@@ -1017,6 +1024,77 @@ int slg_index_add_agg_field_i64(slg_index *ix, const uint32_t *const *seg_offset
 int slg_index_add_agg_field_ord(slg_index *ix, const uint32_t *const *seg_offsets, const uint32_t *const *seg_ords,
                                 uint32_t n_ords) {
   return add_agg_field_impl(ix, 3, seg_offsets, reinterpret_cast<const void *const *>(seg_ords), n_ords);
+}
+int64_t slg_index_rank_agg_field(slg_index *ix, int agg_field_id) {
+  int64_t n_ranks = 0;
+  const int rc = guarded([&] {
+    SLG_REQUIRE(ix != nullptr, "index is NULL");
+    // a keyword field's ordinals are its ranks; a ranked field stays as it is: no new state for either
+    auto known = [&](const IndexState &S) {
+      const auto it = S.agg_fields.find(agg_field_id);
+      SLG_REQUIRE(it != S.agg_fields.end(), "unknown agg field id");
+      if (it->second->kind == 2) n_ranks = it->second->n_ords;
+      if (it->second->dict) n_ranks = (int64_t)it->second->dict->keys.size();
+      return it->second->kind == 2 || it->second->dict != nullptr;
+    };
+    if (known(*ix->snapshot())) return;
+    update_state(ix, false, [&](const IndexState &cur, IndexState &ns) {
+      if (known(cur)) return;  // (ranked by another thread in between)
+      const AggFieldData &fd = *cur.agg_fields.find(agg_field_id)->second;
+      if (fd.non_finite)
+        throw SlgError(SLG_ERR_UNSUPPORTED, "agg field " + std::to_string(agg_field_id) + " holds a non-finite value");
+      if (fd.i64_rounded)
+        throw SlgError(SLG_ERR_UNSUPPORTED, "agg field " + std::to_string(agg_field_id) +
+                                                " holds an i64 value beyond +-2^53: distinct values became one f64");
+      auto key_of = [](double x) {  // = slg::agg_f64_key
+        uint64_t b;
+        std::memcpy(&b, &x, 8);
+        return (b >> 63) ? ~b : (b | 0x8000000000000000ull);
+      };
+      // the values come back from the device (registration kept no host copy); one sort over all of them
+      std::vector<std::vector<uint64_t>> keys(fd.per_seg.size());
+      auto dict = std::make_shared<AggRankDict>();
+      for (size_t s = 0; s < fd.per_seg.size(); s++) {
+        const auto &col = fd.per_seg[s];
+        if (!col || col->n_vals == 0) continue;
+        std::vector<double> v(col->n_vals);
+        SLG_HIP(hipMemcpy(v.data(), col->vals.p, v.size() * 8, hipMemcpyDeviceToHost));
+        keys[s].resize(v.size());
+        for (size_t i = 0; i < v.size(); i++) keys[s][i] = key_of(v[i]);
+        dict->keys.insert(dict->keys.end(), keys[s].begin(), keys[s].end());
+      }
+      std::sort(dict->keys.begin(), dict->keys.end());
+      dict->keys.erase(std::unique(dict->keys.begin(), dict->keys.end()), dict->keys.end());
+      dict->keys.shrink_to_fit();
+      if (dict->keys.size() > SLG_MAX_AGG_RANKS)
+        throw SlgError(SLG_ERR_UNSUPPORTED, "agg field " + std::to_string(agg_field_id) +
+                                                " holds more than SLG_MAX_AGG_RANKS distinct values");
+      auto nf = std::make_shared<AggFieldData>(fd);
+      nf->ranks.assign(fd.per_seg.size(), nullptr);
+      std::vector<uint32_t> r;
+      for (size_t s = 0; s < fd.per_seg.size(); s++) {
+        if (!fd.per_seg[s]) continue;
+        r.resize(keys[s].size());
+        for (size_t i = 0; i < r.size(); i++)
+          r[i] = (uint32_t)(std::lower_bound(dict->keys.begin(), dict->keys.end(), keys[s][i]) - dict->keys.begin());
+        auto buf = std::make_shared<DevBuf>();
+        buf->alloc(std::max<size_t>(r.size(), 1) * 4, &ix->pool);
+        if (!r.empty()) SLG_HIP(hipMemcpy(buf->p, r.data(), r.size() * 4, hipMemcpyHostToDevice));
+        nf->ranks[s] = std::move(buf);
+      }
+      std::vector<double> vals(dict->keys.size());
+      for (size_t i = 0; i < vals.size(); i++) {
+        const uint64_t k = dict->keys[i], b = (k >> 63) ? (k & 0x7FFFFFFFFFFFFFFFull) : ~k;
+        std::memcpy(&vals[i], &b, 8);
+      }
+      dict->vals.alloc(std::max<size_t>(vals.size(), 1) * 8, &ix->pool);
+      if (!vals.empty()) SLG_HIP(hipMemcpy(dict->vals.p, vals.data(), vals.size() * 8, hipMemcpyHostToDevice));
+      n_ranks = (int64_t)dict->keys.size();
+      nf->dict = std::move(dict);
+      ns.agg_fields[agg_field_id] = std::move(nf);
+    });
+  });
+  return rc == SLG_OK ? n_ranks : rc;
 }
 int slg_index_remove_agg_field(slg_index *ix, int agg_field_id) {
   return guarded([&] {

@@ -436,6 +436,15 @@ class GpuIndex:
     def remove_agg_field(self, agg_field_id: int) -> None:
         N.check(self._lib.slg_index_remove_agg_field(self._h, agg_field_id))
 
+    def rank_agg_field(self, agg_field_id: int) -> int:
+        """Build the value ranks of a registered column (slg_index_rank_agg_field), what cardinality and percentiles
+        nodes need of a numeric field.  Returns the number of distinct values (n_ords for a keyword field); a
+        second call only returns it."""
+        rc = int(self._lib.slg_index_rank_agg_field(self._h, agg_field_id))
+        if rc < 0:
+            N.check(rc)
+        return rc
+
     def search_aggs(self, q_offsets, q_terms, q_weights, k: int, aggs, sort=None, strategy: int = Wand,
                     q_filter=None, **plans):
         """Batch search with aggregations (slg_batch_prepare_aggs).  aggs: an N.AggSpec or an aggs.AggPlan;
@@ -1268,23 +1277,28 @@ class PreparedBatch:
         lay = (N.AggLayout * n)()
         N.check(self._lib.slg_batch_agg_layout(self._h, lay))
         return [dict(parent_rows=int(x.parent_rows), rows=int(x.rows), first_id=int(x.first_id),
-                     is_stats=bool(x.is_stats), offset=int(x.offset)) for x in lay]
+                     is_stats=int(x.is_stats) == 1, is_values=int(x.is_stats) == 2, offset=int(x.offset)) for x in lay]
 
     def aggs(self) -> list:
-        """The tables of the last run (slg_batch_fetch_aggs; waits): per node an array [nq, parent_rows, rows],
-        uint64 counts for a bucket node, aggs.STATS_DTYPE records (count, min, max, sum) for a stats node."""
+        """The tables of the last run (slg_batch_fetch_aggs / _fetch_agg_values; waits): per node an array
+        [nq, parent_rows, rows], uint64 counts for a bucket node, aggs.STATS_DTYPE records (count, min, max, sum)
+        for a stats node, uint64 value cells for a cardinality, percentiles or percentile_ranks node."""
         from .aggs import STATS_DTYPE
         lay = self.agg_layout()
-        cc = sum(x["parent_rows"] * x["rows"] for x in lay if not x["is_stats"])
-        sc = sum(x["parent_rows"] * x["rows"] for x in lay if x["is_stats"])
+        cells = lambda pick: sum(x["parent_rows"] * x["rows"] for x in lay if pick(x))
+        cc = cells(lambda x: not x["is_stats"] and not x["is_values"])
+        sc, vc = cells(lambda x: x["is_stats"]), cells(lambda x: x["is_values"])
         counts = np.zeros((max(self.nq, 1), max(cc, 1)), dtype=np.uint64)
         stats = np.zeros((max(self.nq, 1), max(sc, 1)), dtype=STATS_DTYPE)
+        values = np.zeros((max(self.nq, 1), max(vc, 1)), dtype=np.uint64)
         N.check(self._lib.slg_batch_fetch_aggs(self._h, _ptr(counts.reshape(-1)[:self.nq * cc]) if cc else None,
                                                _ptr(stats.reshape(-1)[:self.nq * sc]) if sc else None))
+        if vc:
+            N.check(self._lib.slg_batch_fetch_agg_values(self._h, _ptr(values.reshape(-1)[:self.nq * vc])))
         out = []
         for x in lay:
-            src, cells = (stats, sc) if x["is_stats"] else (counts, cc)
-            flat = src.reshape(-1)[:self.nq * cells].reshape(self.nq, cells)
+            src, n_cells = (stats, sc) if x["is_stats"] else (values, vc) if x["is_values"] else (counts, cc)
+            flat = src.reshape(-1)[:self.nq * n_cells].reshape(self.nq, n_cells)
             n = x["parent_rows"] * x["rows"]
             out.append(flat[:, x["offset"]:x["offset"] + n].reshape(self.nq, x["parent_rows"], x["rows"]).copy())
         return out

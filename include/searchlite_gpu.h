@@ -807,7 +807,27 @@ int slg_search_batch_agg_values(slg_index *index, const slg_query *queries, uint
  * batch already collects, and every caller returns with its own row — bit-identical to the same query in
  * slg_search_batch.  A batch closes when it holds max_batch queries, or max_wait_us after its first
  * query arrived; a query that finds the coalescer idle (nothing in flight) does not wait at all.
- * Thread-safe; out_doc / out_seg / out_score hold k entries, out_count one. */
+ * Thread-safe; out_doc / out_seg / out_score hold k entries, out_count one.
+ *
+ * A request is checked when it is submitted, before it joins a batch: whatever slg_batch_prepare_plan refuses
+ * about one query — an unknown strategy or plan, k > SLG_MAX_K or more than SLG_MAX_QUERY_TERMS terms
+ * (SLG_ERR_UNSUPPORTED), a tie outside [0, 1] or NaN, a leaf >= 2^31, a term id that is neither SLG_NO_TERM nor
+ * below its segment's term count, a non-finite weight, a filter id that is not registered for every segment —
+ * fails that request alone (SLG_ERR_INVALID unless noted), with its text in slg_coalescer_last_error, and costs
+ * the callers that would have shared its batch nothing.  Two rules are stricter than the batch API's: a
+ * non-finite weight is refused even where its term has no posting, and a negative filter id other than -1 is
+ * refused.  A failure of the batch as a whole (the device, memory) goes to every caller of that batch.
+ *
+ * Up to 8 combinations of (k, strategy, segment count) collect at the same time.  A combination whose requests
+ * have all been waited for gives its place to a new one, so any number of combinations may be used over the
+ * coalescer's life; a request that meets 8 others with requests in flight at that moment fails with
+ * SLG_ERR_UNSUPPORTED and may be sent again.
+ *
+ * Index updates need a quiesced coalescer: slg_index_add_segment / _remove_segment, and the removal of a filter
+ * that requests name, must not run between a request's submit and its wait (a row is written at the width, and
+ * checked against the segments and filters, of the index as it was at submit; the batch is planned on the index
+ * as it is when the batch closes).  A request in flight across slg_index_update_deleted is answered from the
+ * state before or after it.  Requests submitted after an update returns see the new index. */
 typedef struct slg_coalescer slg_coalescer;
 slg_coalescer *slg_coalescer_create(slg_index *index, uint32_t max_batch, uint32_t max_wait_us);
 /* No caller may be inside slg_coalescer_search any more. */
@@ -817,7 +837,7 @@ int slg_coalescer_search(slg_coalescer *coalescer, const slg_query *query, uint3
                          slg_stats *stats_or_null);
 /* The same for a query with a flat score plan (slg_batch_prepare_plan: leaf[i] = leaf of query term i or
  * NULL, plan = SLG_PLAN_SUM | SLG_PLAN_DISMAX over the leaves, tie in [0, 1], n_leaves = leaves of the
- * plan or 0 = 1 + the largest leaf named) and / or a registered doc filter (filter_id, < 0: none): what
+ * plan or 0 = 1 + the largest leaf named) and / or a registered doc filter (filter_id, -1: none): what
  * an unmodified request over the default fields is (api/reader.rs:2576-2586).  Rows with and without
  * plans or filters share batches.  Two-level plans go through slg_batch_prepare_plans directly. */
 int slg_coalescer_search_plan(slg_coalescer *coalescer, const slg_query *query, const uint32_t *leaf, int plan,
@@ -829,7 +849,11 @@ int slg_coalescer_search_plan(slg_coalescer *coalescer, const slg_query *query, 
  * batch and returns at once with a ticket; slg_coalescer_wait blocks until that batch's results are in,
  * copies the ticket's row out and gives the row back (every ticket must be waited for exactly once, by any
  * thread; the ticket is cleared).  slg_coalescer_poll: 1 if slg_coalescer_wait would not block, else 0.
- * The query's arrays may be reused as soon as submit returns.  A thread-per-request caller pays a sleep and
+ * The query's arrays may be reused as soon as submit returns.  A submit that fails took no ticket: there is
+ * nothing to wait for.  want_stats != 0 asks for the request's slg_stats: slg_coalescer_wait writes
+ * *stats_or_null — the slg_stats slg_batch_fetch reports for the same query — only for such a ticket and only when
+ * it returns SLG_OK; for a ticket submitted with want_stats == 0, or on failure, *stats_or_null is left as it was.
+ * A thread-per-request caller pays a sleep and
  * a wake-up per query — what bounds slg_coalescer_search on a host with few cores; with D tickets per
  * thread a thread sleeps at most once per D queries. */
 typedef struct slg_ticket {
@@ -842,7 +866,8 @@ int slg_coalescer_submit(slg_coalescer *coalescer, const slg_query *query, const
 int slg_coalescer_poll(const slg_coalescer *coalescer, const slg_ticket *ticket);
 int slg_coalescer_wait(slg_coalescer *coalescer, slg_ticket *ticket, uint32_t *out_doc, uint32_t *out_seg,
                        float *out_score, uint32_t *out_count, slg_stats *stats_or_null);
-/* Thread-local text of the last failure of slg_coalescer_search on this thread. */
+/* Thread-local text of the last failure of slg_coalescer_search / _search_plan / _submit / _wait on this thread
+ * (empty after a call that succeeded). */
 const char *slg_coalescer_last_error(void);
 /* Mean time (ms) a batch's leader spent collecting / in slg_batch_prepare / in set_stream + run / in
  * fetch + destroy, over the batches run so far. */

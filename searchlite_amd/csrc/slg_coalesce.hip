@@ -20,11 +20,50 @@
 // followers — was built first: with a dozen leaders inside the HIP runtime at once, prepare took 0.24 ms
 // and fetch 0.41 ms for 23-query batches whose kernels take ~40 us; polling the stream instead of the
 // blocking wait made it worse.)  Batches of different kinds — (k, strategy, segment count) — collect
-// side by side.  Batch objects are recycled per kind, so a caller that still holds the pointer of a
-// batch that has been closed and reopened meanwhile joins a batch of its own kind or bounces.
+// side by side, kMaxKinds of them at once.
 //
-// Host code on top of the public ABI (no kernels here; HIP only for the leaders' streams); part of
-// libsearchlite_gpu.so.
+// Stale pointers.  A caller reads a kind's `cur` pointer and then takes its ticket, with no lock between
+// the two, so it may take the ticket on a batch that has been closed, waited for and handed out again
+// meanwhile.  What keeps that harmless:
+//   * a batch object keeps its (k, strategy, segment count) from the day it is made to the day the coalescer
+//     is destroyed, and no object is freed before then.  A caller compares the object's key with its own
+//     before it touches the ticket counter, so whatever has happened to the object since, the caller either
+//     joins a batch of its own kind (open: a row like any other) or bounces (closed or full) and looks its
+//     kind up again;
+//   * a kind slot whose batches are all idle — the collecting batch holds no ticket, every other object
+//     of the kind lies on the spare list, i.e. none is closed and not yet fully waited for — is RECLAIMED
+//     (find_kind, under c->mu) when a new combination finds no free slot.  The collecting batch is closed by
+//     a compare-and-swap of its ticket counter from 0 (a caller's fetch_add either came first, then the kind
+//     is not idle, or comes later and bounces), the slot's key is cleared, and the kind's objects go to the
+//     coalescer's `retired` list: closed, their row storage freed, their key kept.  They come back only to a
+//     slot that is registered for the SAME key, so a caller that still holds one can never end up in a batch
+//     of another k, strategy or row width.  A slot that every caller is still using — more than kMaxKinds
+//     combinations with requests in flight at the same moment — is not reclaimed: that request is refused;
+//   * the submitter reads a slot's `cur` and then that batch's ticket counter under close_mu, which no
+//     reclaim takes, so its pointer can be stale in the same way: slot i reclaimed and given to another
+//     kind, the object retired, handed to the slot its key is registered in again, opened there and joined.
+//     Once the submitter has seen the batch open with a row, the batch cannot move any more (a reclaim needs
+//     a ticket counter of 0, and only the holder of close_mu closes), so it compares the batch's slot
+//     (CoBatch::kind, written while the object is closed and unowned, before it is opened) with the slot it
+//     is looking at and leaves the batch to that slot's turn if they differ.  Without this it would close
+//     the batch as slot i's: slot i's real collecting batch would be replaced and never launched, and the
+//     batch's own slot would keep a closed `cur` for good.
+//
+// Cost of reclaiming, by design: a retired object is a few hundred bytes (its row storage is freed) and stays
+// until its key is registered again or the coalescer is destroyed, so the list grows with the number of
+// distinct combinations ever used; the lowest idle slot is taken, so a caller that rotates over more than
+// kMaxKinds combinations one after the other frees and allocates a slot's row storage at every change.
+//
+// A row is checked before it takes its ticket (check_row): everything slg_batch_prepare_plan would refuse
+// about ONE query is refused in slg_coalescer_submit, to that caller alone.  What is left to fail in
+// launch_batch is the batch as a whole (the device, memory, an index update or a filter removal that raced
+// the collection), and that is published to every caller of the batch.
+//
+// Host code on top of the C ABI and the index's host structures (slg_host.hpp: the per-segment term counts
+// and the registered filters that check_row reads); no kernels here, HIP only for the leaders' streams;
+// part of libsearchlite_gpu.so.
+#include "slg_host.hpp"
+
 #include <hip/hip_runtime.h>
 #include <linux/futex.h>
 #include <sys/syscall.h>
@@ -32,6 +71,7 @@
 
 #include <atomic>
 #include <climits>
+#include <cmath>
 #include <cstdlib>
 #include <chrono>
 #include <condition_variable>
@@ -50,6 +90,12 @@ namespace {
 constexpr uint32_t kClosed = 0x80000000u;  // ticket counter: top bit = the batch takes no more rows
 constexpr int kMaxKinds = 8;               // (k, strategy, segment count) combinations collecting at once
 using Clock = std::chrono::steady_clock;
+
+// A kind's key as one word, 0 = a free slot (k <= SLG_MAX_K and a known strategy: check_row comes first).
+inline uint64_t kind_key(uint32_t k, int strategy, uint32_t n_segs) {
+  static_assert(SLG_MAX_K < (1u << 24), "k takes the key's low 24 bits");
+  return (1ull << 63) | ((uint64_t)(n_segs & 0x7FFFFFFFu) << 32) | ((uint64_t)(uint32_t)strategy << 24) | k;
+}
 
 // Callers sleep on the batch's `done` word itself (futex): waking a batch's callers is one system call
 // and none of them takes a lock on the way out.  (A condition variable was built first: notify_all
@@ -72,10 +118,16 @@ inline void cpu_relax() {
 // One collecting / running batch (see the header comment).  Fixed-size slots: SLG_MAX_QUERY_TERMS x
 // n_segs term ids per row (a megabyte for an 8-segment index: objects are recycled, per kind).
 struct CoBatch {
-  uint32_t k = 0;
-  int strategy = 0;
-  uint32_t n_segs = 0, slot_terms = 0, cap = 0;
-  std::atomic<uint32_t> tickets{kClosed};  // rows handed out; >= kClosed: closed
+  // the kind's key: fixed when the object is made (see "Stale pointers" in the header comment)
+  const uint64_t key;
+  const uint32_t k;
+  const int strategy;
+  const uint32_t n_segs;
+  CoBatch(uint32_t k_, int strategy_, uint32_t n_segs_)
+      : key(kind_key(k_, strategy_, n_segs_)), k(k_), strategy(strategy_), n_segs(n_segs_) {}
+  uint32_t slot_terms = 0, cap = 0;
+  // (a cache line of its own from here: every caller's fetch_add lands on it, and a caller reads `key` first)
+  alignas(64) std::atomic<uint32_t> tickets{kClosed};  // rows handed out; >= kClosed: closed
   uint32_t nq = 0;                         // rows of the closed batch (set by the submitter)
   std::atomic<uint32_t> ready{0};          // rows written
   std::atomic<uint32_t> leaving{0};        // callers that have copied their result out
@@ -87,6 +139,7 @@ struct CoBatch {
   std::vector<uint32_t> slot_leaf, slot_nleaves;
   std::vector<int32_t> slot_plan, slot_filter;
   std::vector<float> slot_tie;
+  std::vector<uint8_t> slot_want;  // the row asked for its slg_stats (want_stats of slg_coalescer_submit)
   std::atomic<bool> want_stats{false}, any_plan{false}, any_filter{false};
   // the closed batch as CSR (built by the submitter), and its results
   std::vector<uint32_t> offs, term_ids, leaves;
@@ -97,17 +150,19 @@ struct CoBatch {
   int rc = SLG_OK;
   std::string error;
   std::atomic<uint32_t> done{0};  // 1: results are in (callers sleep on this word: futex)
-  int kind = 0;
+  int kind = 0;                   // the slot the object belongs to (set while it is closed and on no list)
 };
 
 struct Kind {
-  std::atomic<bool> used{false};
-  uint32_t k = 0, n_segs = 0;
+  std::atomic<uint64_t> key{0};  // kind_key of the slot's (k, strategy, n_segs); 0: free
+  uint32_t k = 0, n_segs = 0;    // (written under c->mu before `key` is published)
   int strategy = 0;
-  std::atomic<CoBatch *> cur{nullptr};  // the batch that is collecting (never null once the kind is used)
-  std::mutex mu;                        // spare list
+  std::atomic<CoBatch *> cur{nullptr};  // the batch that is collecting (never null once the slot was used)
+  std::mutex mu;                        // spare list, all
   std::vector<CoBatch *> spare;
-  std::vector<CoBatch *> all;           // every batch object of the kind (destroy)
+  // every batch object of the kind: the collecting one, the spare ones, and those that are closed and not
+  // yet fully waited for — the kind is idle when spare.size() + 1 == all.size() and `cur` holds no ticket
+  std::vector<CoBatch *> all;
 };
 
 struct Flight {  // a launched batch on its way to the collector
@@ -123,8 +178,10 @@ struct slg_coalescer {
   slg_index *index = nullptr;
   uint32_t max_batch = 1024, max_wait_us = 50;
   int device = 0;
+  uint64_t id = 0;  // never handed out twice in a process (the callers' per-thread view of the index names it)
   Kind kinds[kMaxKinds];
-  std::mutex mu;  // kind registration, stream free list
+  std::mutex mu;  // kind registration and reclaiming, the retired list, stream free list
+  std::vector<CoBatch *> retired;  // the objects of reclaimed kinds: closed, storage freed, key kept
   std::vector<void *> free_streams;
   std::atomic<uint32_t> in_flight{0};     // batches launched and not yet fetched
   std::atomic<uint32_t> rows_waiting{0};  // rows in collecting batches
@@ -136,9 +193,6 @@ struct slg_coalescer {
   std::mutex q_mu;     // submitter -> collector
   std::condition_variable q_cv;
   std::deque<Flight> flights;
-  // the index's segment count, cached per generation (slg_index_info takes the index mutex)
-  std::atomic<uint64_t> seen_generation{~0ull};
-  std::atomic<uint32_t> seen_n_segs{0};
   // accounting (slg_coalescer_stats / _phase_ms)
   std::atomic<uint64_t> n_batches{0}, n_queries{0};
   std::atomic<uint64_t> ns_collect{0}, ns_prepare{0}, ns_run{0}, ns_fetch{0};
@@ -181,13 +235,10 @@ CoBatch *fresh_batch(slg_coalescer *c, Kind &kd) {
       b = kd.spare.back();
       kd.spare.pop_back();
     } else {
-      b = new CoBatch();
+      b = new CoBatch(kd.k, kd.strategy, kd.n_segs);
       kd.all.push_back(b);
     }
   }
-  b->k = kd.k;
-  b->strategy = kd.strategy;
-  b->n_segs = kd.n_segs;
   b->kind = (int)(&kd - c->kinds);
   if (b->cap != c->max_batch || b->slot_terms != SLG_MAX_QUERY_TERMS * kd.n_segs) {
     b->cap = c->max_batch;
@@ -200,11 +251,13 @@ CoBatch *fresh_batch(slg_coalescer *c, Kind &kd) {
     b->slot_plan.resize(b->cap);
     b->slot_filter.resize(b->cap);
     b->slot_tie.resize(b->cap);
+    b->slot_want.resize(b->cap);
   }
   b->nq = 0;
   b->ready.store(0);
   b->leaving.store(0);
   b->seen = false;
+  if (b->want_stats.load()) std::fill(b->slot_want.begin(), b->slot_want.end(), uint8_t{0});
   b->want_stats.store(false);
   b->any_plan.store(false);
   b->any_filter.store(false);
@@ -214,30 +267,137 @@ CoBatch *fresh_batch(slg_coalescer *c, Kind &kd) {
   return b;
 }
 
+template <typename T, typename... More>
+void drop_storage(std::vector<T> &v, More &...more) {
+  std::vector<T>().swap(v);
+  if constexpr (sizeof...(more) != 0) drop_storage(more...);
+}
+
+// Frees an idle slot (under c->mu; see "Stale pointers" in the header comment).  false: the kind has a row
+// collecting, or a batch that is closed and not yet fully waited for.
+bool reclaim_kind(slg_coalescer *c, Kind &kd) {
+  std::lock_guard<std::mutex> lk(kd.mu);
+  if (kd.spare.size() + 1 != kd.all.size()) return false;
+  CoBatch *cur = kd.cur.load(std::memory_order_acquire);
+  uint32_t none = 0;
+  if (!cur->tickets.compare_exchange_strong(none, kClosed, std::memory_order_acq_rel)) return false;
+  kd.key.store(0, std::memory_order_release);  // (cur keeps pointing at the closed batch: late callers bounce off it)
+  for (CoBatch *b : kd.all) {  // all of them closed and on no caller's ticket: only `tickets` is still looked at
+    drop_storage(b->slot_ids, b->slot_nt, b->slot_leaf, b->slot_nleaves, b->offs, b->term_ids, b->leaves, b->doc,
+                 b->seg, b->count);
+    drop_storage(b->slot_w, b->slot_tie, b->weights, b->score);
+    drop_storage(b->slot_plan, b->slot_filter);
+    drop_storage(b->slot_want);
+    drop_storage(b->stats);
+    b->cap = b->slot_terms = 0;
+    c->retired.push_back(b);
+  }
+  kd.all.clear();
+  kd.spare.clear();
+  return true;
+}
+
+// The slot that collects (k, strategy, n_segs): the one that has it, a free one, or one whose kind is idle.
+// nullptr: kMaxKinds other combinations have requests in flight right now.
 Kind *find_kind(slg_coalescer *c, uint32_t k, int strategy, uint32_t n_segs) {
-  for (int i = 0; i < kMaxKinds; i++) {
-    Kind &kd = c->kinds[i];
-    if (kd.used.load(std::memory_order_acquire) && kd.k == k && kd.strategy == strategy && kd.n_segs == n_segs) return &kd;
-  }
+  const uint64_t key = kind_key(k, strategy, n_segs);
+  for (int i = 0; i < kMaxKinds; i++)
+    if (c->kinds[i].key.load(std::memory_order_acquire) == key) return &c->kinds[i];
   std::lock_guard<std::mutex> lk(c->mu);
+  Kind *slot = nullptr;
   for (int i = 0; i < kMaxKinds; i++) {
     Kind &kd = c->kinds[i];
-    if (kd.used.load() && kd.k == k && kd.strategy == strategy && kd.n_segs == n_segs) return &kd;
+    const uint64_t has = kd.key.load(std::memory_order_acquire);
+    if (has == key) return &kd;
+    if (has == 0 && !slot) slot = &kd;
   }
-  for (int i = 0; i < kMaxKinds; i++) {
-    Kind &kd = c->kinds[i];
-    if (!kd.used.load()) {
-      kd.k = k;
-      kd.strategy = strategy;
-      kd.n_segs = n_segs;
-      CoBatch *nb = fresh_batch(c, kd);
-      nb->tickets.store(0, std::memory_order_release);  // open
-      kd.cur.store(nb, std::memory_order_release);
-      kd.used.store(true, std::memory_order_release);
-      return &kd;
+  for (int i = 0; i < kMaxKinds && !slot; i++)
+    if (reclaim_kind(c, c->kinds[i])) slot = &c->kinds[i];
+  if (!slot) return nullptr;
+  Kind &kd = *slot;
+  kd.k = k;
+  kd.strategy = strategy;
+  kd.n_segs = n_segs;
+  {  // the objects this key had when it was reclaimed (a caller may still hold one of them: they open for it only)
+    std::lock_guard<std::mutex> lk2(kd.mu);
+    size_t keep = 0;
+    for (CoBatch *b : c->retired)
+      if (b->key == key) {
+        kd.all.push_back(b);
+        kd.spare.push_back(b);
+      } else {
+        c->retired[keep++] = b;
+      }
+    c->retired.resize(keep);
+  }
+  CoBatch *nb = fresh_batch(c, kd);
+  nb->tickets.store(0, std::memory_order_release);  // open
+  kd.cur.store(nb, std::memory_order_release);
+  kd.key.store(key, std::memory_order_release);
+  return &kd;
+}
+
+// ---- a row's checks -------------------------------------------------------------------------------
+// What check_row needs of the index, per caller thread and index generation (a new segment list is a new
+// generation; slg_index::snapshot takes the index mutex, which a request must not do every time).
+struct IndexView {
+  uint64_t owner = 0, generation = 0;  // slg_coalescer::id it was read through
+  std::vector<uint32_t> n_terms;       // per segment
+};
+thread_local IndexView g_view;
+
+const IndexView &index_view(slg_coalescer *c) {
+  const uint64_t gen = slg_index_generation(c->index);
+  if (g_view.owner != c->id || g_view.generation != gen) {
+    const std::shared_ptr<const slghost::IndexState> snap = c->index->snapshot();
+    g_view.n_terms.resize(snap->segs.size());
+    for (size_t s = 0; s < snap->segs.size(); s++) g_view.n_terms[s] = snap->segs[s]->n_terms;
+    g_view.generation = snap->generation;
+    g_view.owner = c->id;
+  }
+  return g_view;
+}
+
+// Everything the planner refuses about one query of slg_batch_prepare_plan (slg_plan.cpp: validate_batch,
+// plan_queries, resolve_plan, build_subquery — they throw from the middle of planning a whole batch, which is
+// why they are restated here and not called; a note beside each of them there points here, and
+// tests/test_gpu_coalescer_edges.py holds the two to the same verdicts).  Two rules are stricter than the planner's: a non-finite weight is refused whether or not its
+// term has postings in some segment, and a negative filter id other than -1 is refused (the planner reads
+// every negative id as "no filter").  SLG_OK, or the code with the text in *err.
+int check_row(slg_coalescer *c, const IndexView &v, const slg_query *query, const uint32_t *leaf, int plan, float tie,
+              int32_t filter_id, uint32_t k, int strategy, std::string *err) {
+  auto fail = [&](int rc, const char *msg) {
+    *err = msg;
+    return rc;
+  };
+  if (strategy != SLG_STRATEGY_BM25 && strategy != SLG_STRATEGY_WAND && strategy != SLG_STRATEGY_BMW)
+    return fail(SLG_ERR_INVALID, "unknown strategy");
+  if (k > SLG_MAX_K) return fail(SLG_ERR_UNSUPPORTED, "k > SLG_MAX_K");
+  if (query->n_terms > SLG_MAX_QUERY_TERMS)
+    return fail(SLG_ERR_UNSUPPORTED, "query has more than SLG_MAX_QUERY_TERMS terms");
+  if (filter_id < -1) return fail(SLG_ERR_INVALID, "filter id is negative and not -1 (no filter)");
+  // Filters are registered and removed without a new generation (the shim registers them while requests run),
+  // so nothing a caller could cache tells it that the set has changed: a FILTERED request takes the index
+  // mutex for one shared_ptr copy here, which rows without a filter never do.  That is contention among
+  // filtered callers that has not been measured; a filter epoch on the index, readable without the lock as
+  // its generation is, would let IndexView cache the live filters too.
+  if (filter_id >= 0 && !c->index->snapshot()->filter_usable((size_t)filter_id))
+    return fail(SLG_ERR_INVALID, "unknown filter id");
+  if (plan != SLG_PLAN_SUM && plan != SLG_PLAN_DISMAX) return fail(SLG_ERR_INVALID, "unknown score plan");
+  if (!(tie >= 0.0f && tie <= 1.0f)) return fail(SLG_ERR_INVALID, "tie breaker outside [0, 1]");  // (also: NaN)
+  const uint32_t nt = query->n_terms, ns = (uint32_t)v.n_terms.size();
+  if (leaf)
+    for (uint32_t i = 0; i < nt; i++)
+      if (leaf[i] >= 0x80000000u) return fail(SLG_ERR_INVALID, "leaf index >= 2^31");
+  if (k == 0) return SLG_OK;  // (the planner looks at no term of a k == 0 batch)
+  for (uint32_t i = 0; i < nt; i++) {
+    for (uint32_t s = 0; s < ns; s++) {
+      const uint32_t tid = query->term_ids[(size_t)i * ns + s];
+      if (tid != SLG_NO_TERM && tid >= v.n_terms[s]) return fail(SLG_ERR_INVALID, "term id out of range");
     }
+    if (!std::isfinite(query->weights[i])) return fail(SLG_ERR_INVALID, "non-finite weight");
   }
-  return nullptr;
+  return SLG_OK;
 }
 
 void publish(CoBatch &b, int rc, const char *err) {
@@ -320,10 +480,15 @@ void submitter_main(slg_coalescer *c) {
         const auto now = Clock::now();
         for (int i = 0; i < kMaxKinds && !closed; i++) {
           Kind &kd = c->kinds[i];
-          if (!kd.used.load(std::memory_order_acquire)) continue;
+          if (kd.key.load(std::memory_order_acquire) == 0) continue;
           CoBatch *b = kd.cur.load(std::memory_order_acquire);
           const uint32_t t = b->tickets.load(std::memory_order_acquire);
           if (t == 0u || (t & kClosed)) continue;
+          // b is pinned from here on: it is open with a row, so no reclaim can take it (that needs a ticket
+          // counter of 0) and nobody else closes (close_mu).  But between the two loads above slot i may have
+          // been reclaimed and b handed to the slot its key was registered in again: only that slot's turn of
+          // this loop may close it (see "Stale pointers" in the header comment)
+          if (b->kind != i) continue;
           if (!b->seen) {
             b->seen = true;
             b->first_seen = now;
@@ -388,7 +553,9 @@ slg_coalescer *slg_coalescer_create(slg_index *index, uint32_t max_batch, uint32
   if (!index) return nullptr;
   const int dev = slg_index_device(index);
   if (dev < 0) return nullptr;
+  static std::atomic<uint64_t> next_id{1};
   auto *c = new slg_coalescer();
+  c->id = next_id.fetch_add(1);
   c->index = index;
   c->device = dev;
   c->max_batch = max_batch ? (max_batch < kClosed / 2 ? max_batch : 1024u) : 1024u;
@@ -415,6 +582,7 @@ void slg_coalescer_destroy(slg_coalescer *c) {
   for (void *s : c->free_streams) (void)hipStreamDestroy((hipStream_t)s);
   for (Kind &kd : c->kinds)
     for (CoBatch *b : kd.all) delete b;
+  for (CoBatch *b : c->retired) delete b;
   delete c;
 }
 
@@ -465,42 +633,37 @@ int slg_coalescer_submit(slg_coalescer *c, const slg_query *query, const uint32_
     g_co_error = "coalescer, query or ticket is NULL";
     return SLG_ERR_INVALID;
   }
-  if (query->n_terms > SLG_MAX_QUERY_TERMS) {
-    g_co_error = "query has more than SLG_MAX_QUERY_TERMS terms";
-    return SLG_ERR_UNSUPPORTED;
-  }
-  // the index's segment count (the width of the query's term-id rows), cached per index generation
-  const uint64_t gen = slg_index_generation(c->index);
-  uint32_t n_segs = c->seen_n_segs.load(std::memory_order_acquire);
-  if (c->seen_generation.load(std::memory_order_acquire) != gen) {
-    if (slg_index_info(c->index, &n_segs, nullptr, nullptr) != SLG_OK) {
-      g_co_error = slg_last_error();
-      return SLG_ERR_INVALID;
-    }
-    c->seen_n_segs.store(n_segs, std::memory_order_release);
-    c->seen_generation.store(gen, std::memory_order_release);
-  }
-  Kind *kd = find_kind(c, k, strategy, n_segs);
-  if (!kd) {
-    g_co_error = "too many (k, strategy) combinations collecting at once";
-    return SLG_ERR_UNSUPPORTED;
-  }
+  // the index's segments (their count is the width of the query's term-id rows), then the row's own checks:
+  // a request the planner would refuse fails here, alone, and takes neither a kind nor a ticket
+  const IndexView &view = index_view(c);
+  const uint32_t n_segs = (uint32_t)view.n_terms.size();
+  if (const int bad = check_row(c, view, query, leaf, plan, tie, filter_id, k, strategy, &g_co_error)) return bad;
+  const uint64_t key = kind_key(k, strategy, n_segs);
   // ---- a row: one fetch_add on the collecting batch's ticket counter ----
+  Kind *kd = nullptr;
   CoBatch *b = nullptr;
   uint32_t row = 0;
   for (;;) {
+    kd = find_kind(c, k, strategy, n_segs);
+    if (!kd) {
+      g_co_error = "too many (k, strategy) combinations collecting at once";
+      return SLG_ERR_UNSUPPORTED;
+    }
     b = kd->cur.load(std::memory_order_acquire);
+    if (b->key != key) continue;  // the slot went to another kind since find_kind looked (see "Stale pointers")
     const uint32_t t = b->tickets.fetch_add(1, std::memory_order_acq_rel);
     if (t < c->max_batch) {  // (closed: t >= kClosed; full: t >= max_batch)
       row = t;
       break;
     }
-    // closed or full: the submitter swaps the next batch in within microseconds
+    // closed or full: the submitter swaps the next batch in within microseconds; a reclaimed kind is looked up again
     if (c->stop.load(std::memory_order_acquire)) {
       g_co_error = "coalescer is being destroyed";
       return SLG_ERR_INVALID;
     }
-    while (kd->cur.load(std::memory_order_acquire) == b && !c->stop.load(std::memory_order_relaxed)) cpu_relax();
+    while (kd->key.load(std::memory_order_acquire) == key && kd->cur.load(std::memory_order_acquire) == b &&
+           b->tickets.load(std::memory_order_acquire) >= c->max_batch && !c->stop.load(std::memory_order_relaxed))
+      cpu_relax();
   }
   // ---- my row ----
   b->slot_nt[row] = query->n_terms;
@@ -522,7 +685,10 @@ int slg_coalescer_submit(slg_coalescer *c, const slg_query *query, const uint32_
   b->slot_filter[row] = filter_id;
   if (planned) b->any_plan.store(true);
   if (filter_id >= 0) b->any_filter.store(true);
-  if (want_stats) b->want_stats.store(true);
+  if (want_stats) {  // (slot_want is cleared when the object is handed out: rows that do not ask write nothing)
+    b->slot_want[row] = 1;
+    b->want_stats.store(true);
+  }
   b->ready.fetch_add(1, std::memory_order_release);
   if (c->rows_waiting.fetch_add(1, std::memory_order_acq_rel) == 0) {  // the first waiting row wakes the submitter
     {
@@ -533,7 +699,7 @@ int slg_coalescer_submit(slg_coalescer *c, const slg_query *query, const uint32_
   ticket->batch = b;
   ticket->row = row;
   ticket->k = k;
-  ticket->kind = (uint32_t)(kd - c->kinds);
+  ticket->kind = (uint32_t)b->kind;  // (the batch's slot: a late caller's `kd` may be another slot by now)
   return SLG_OK;
 }
 
@@ -551,7 +717,7 @@ int slg_coalescer_wait(slg_coalescer *c, slg_ticket *ticket, uint32_t *out_doc, 
   }
   CoBatch *b = static_cast<CoBatch *>(ticket->batch);
   const uint32_t row = ticket->row, k = ticket->k;
-  Kind *kd = &c->kinds[ticket->kind];
+  Kind *kd = &c->kinds[b->kind];  // (stays the batch's slot until its last row is given back)
   // ---- wait (asleep: hundreds of callers spinning would take the cores the two dispatcher threads and
   //      the callers that are being woken need) ----
   while (b->done.load(std::memory_order_acquire) == 0u) futex_wait(&b->done, 0u);
@@ -567,12 +733,15 @@ int slg_coalescer_wait(slg_coalescer *c, slg_ticket *ticket, uint32_t *out_doc, 
       std::memcpy(out_seg, b->seg.data() + (size_t)row * k, (size_t)k * 4);
       std::memcpy(out_score, b->score.data() + (size_t)row * k, (size_t)k * 4);
     }
-    if (stats_or_null && !b->stats.empty()) *stats_or_null = b->stats[row];
+    // only a row that asked for them: the vector may hold another row's request, or an earlier batch's numbers
+    if (stats_or_null && b->slot_want[row]) *stats_or_null = b->stats[row];
   }
   const bool args_ok = rc != SLG_OK || (out_count && (!k || (out_doc && out_seg && out_score)));
-  // the last caller to leave hands the batch object back to its kind (b->nq is final: done was seen)
+  // the last caller to leave hands the batch object back to its kind (b->nq is final: done was seen; read
+  // before this row is given back — after that the object may be collecting again)
   ticket->batch = nullptr;
-  if (b->leaving.fetch_add(1) + 1 == b->nq) {
+  const uint32_t nq = b->nq;
+  if (b->leaving.fetch_add(1) + 1 == nq) {
     std::lock_guard<std::mutex> lk(kd->mu);
     kd->spare.push_back(b);
   }

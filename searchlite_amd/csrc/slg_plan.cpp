@@ -81,6 +81,7 @@ struct BatchFacts {
 BatchFacts validate_batch(const BatchIn &in) {
   BatchFacts f;
   PLAN_REQUIRE(in.nq == 0 || in.q_offsets != nullptr, "q_offsets is NULL");
+  // (strategy, k and the term count per query: also made per request by slg_coalesce.hip check_row)
   PLAN_REQUIRE(in.strategy == SLG_STRATEGY_BM25 || in.strategy == SLG_STRATEGY_WAND ||
                    in.strategy == SLG_STRATEGY_BMW,
                "unknown strategy");
@@ -281,6 +282,7 @@ void resolve_plan(const BatchIn &in, uint32_t q, std::vector<slg::PlanNode> &nod
   if (pl.q_node_offsets) {
     resolve_tree(pl, q, nodes, p);
   } else {
+    // (plan, tie and leaf: checks on ONE query that slg_coalesce.hip check_row also makes per request — keep the two together)
     PLAN_REQUIRE(p.kind == SLG_PLAN_SUM || p.kind == SLG_PLAN_DISMAX,
                  "unknown score plan in query " + std::to_string(q));
     // validate_tie_breaker (query/planner.rs:850-856); the threshold seed and the pruning bounds
@@ -377,6 +379,7 @@ bool build_subquery(const Pass1Ctx &c, const QueryPlan &p, uint32_t q, std::vect
   for (uint32_t i = 0; i < nt; i++) {
     const uint32_t tid = in.q_term_ids[(size_t)(t0 + i) * n_segs + sq.seg];
     if (tid == SLG_NO_TERM) continue;
+    // (this and the weight check below: checks on ONE query that slg_coalesce.hip check_row also makes per request — keep the two together)
     PLAN_REQUIRE(tid < sh.n_terms, "term id out of range in query " + std::to_string(q));
     const uint32_t df = (uint32_t)(sh.term_offsets[tid + 1] - sh.term_offsets[tid]);
     if (df == 0) continue;  // wand.rs:441 filter(postings.len() > 0)
@@ -508,6 +511,7 @@ void plan_queries(const Pass1Ctx &c, const uint32_t q_lo, const uint32_t q_hi, P
     if (q + 8u < q_hi) prefetch_query(q + 8u);
     uint32_t fq = 0;  // doc filter of the query (0 none, id + 1)
     if (in.q_filter && in.q_filter[q] >= 0) {
+      // (a check on ONE query that slg_coalesce.hip check_row also makes per request — keep the two together)
       PLAN_REQUIRE((size_t)in.q_filter[q] < in.n_filters && in.filter_live[in.q_filter[q]],
                    "unknown filter id in query " + std::to_string(q));
       fq = (uint32_t)in.q_filter[q] + 1u;

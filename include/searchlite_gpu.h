@@ -1510,10 +1510,11 @@ int slg_search_batch_phrase(slg_index *index, uint32_t nq, const uint32_t *q_off
  * column, a field without a column for a segment.  SLG_ERR_UNSUPPORTED (CPU scorer): more than
  * SLG_MAX_FSCORE_FUNCS functions in a query, a column that holds a non-finite value (the rule of aggregations).
  * slg_batch_run_sharded* and slg_batch_fetch_sharded refuse a function_score batch with SLG_ERR_UNSUPPORTED.
- * Not built (CPU scorer): function_score below the root or over another inner query, rank_feature,
- * script_score, constant_score, explain, function filters other than registered filter ids, and specs on bool,
- * phrase, cursor, hybrid, aggregation, rescore, sharded and coalesced batches (none of their prepare calls
- * takes the spec).
+ * Built beside it: script_score at the root, and the two nodes nested one inside the other
+ * (slg_batch_prepare_script, below).  Not built (CPU scorer): function_score below the root or over any other
+ * inner query, deeper nesting, rank_feature, constant_score, explain, function filters other than registered
+ * filter ids, and specs on bool, phrase, cursor, hybrid, aggregation, rescore, sharded and coalesced batches
+ * (none of their prepare calls takes the spec).
  * --------------------------------------------------------------------------------------------------------- */
 #define SLG_MAX_FSCORE_FUNCS 8u /* functions of one query */
 enum { SLG_FSCORE_WEIGHT = 0, SLG_FSCORE_FIELD_VALUE_FACTOR = 1, SLG_FSCORE_DECAY = 2 };
@@ -1557,6 +1558,85 @@ int slg_search_batch_fscore(slg_index *index, uint32_t nq, const uint32_t *q_off
                             const slg_fscore_spec *spec, uint32_t k, int strategy, uint32_t *out_doc, uint32_t *out_seg,
                             float *out_score, uint32_t *out_count, slg_stats *stats_or_null,
                             uint64_t *out_matched_or_null);
+
+/* ---------------------------------------------------------------------------------------------------------
+ * script_score at the root of the score tree, with the batch's scored query as its inner query: an arithmetic
+ * script over the doc's base score, constants and numeric fast fields (query/script.rs; the node:
+ * evaluate_compiled_score, api/reader.rs:577-612; planner.rs:776-791 builds matcher and scorer from the inner
+ * node, so every candidate passes matches_subquery).  Optionally chained with a function_score stage: the two
+ * nodes nested one inside the other.
+ *
+ * PROGRAM.  Query q has instructions p_offsets[q] .. p_offsets[q + 1] - 1 (at most SLG_MAX_SCRIPT_INSTRS): the
+ * script in reverse Polish order, as CompiledScript holds it, evaluated in f64 on a stack (script.rs:69-146), one
+ * correctly rounded operation at a time.
+ *   SLG_SCRIPT_PUSH_CONST  push consts[i_arg] (number literals and params: both are constants here)
+ *   SLG_SCRIPT_PUSH_FIELD  push the doc's FIRST value of agg column i_arg (slg_index_add_agg_field_f64 / _i64, an
+ *                          i64 value `as f64`), or 0.0 when the doc has none (script.rs:80-87)
+ *   SLG_SCRIPT_PUSH_SCORE  push the doc's base score `as f64`
+ *   SLG_SCRIPT_ADD / _SUB / _MUL   pop b, pop a, push a op b; a non-finite result: NONE
+ *   SLG_SCRIPT_DIV         pop b, pop a; b == 0.0 (also -0.0): NONE, before dividing; push a / b; non-finite: NONE
+ *   SLG_SCRIPT_NEG         pop a, push -a
+ * AFTER THE PROGRAM.  v = (float)top, non-finite: NONE (reader.rs:596); score = v * q_boost in f32, non-finite:
+ * NONE (:599-602).  NONE DROPS the doc: it is not ranked and not counted — slg_stats.scored_docs and a sorted
+ * batch's matched counts follow the rule of function_score's min_score drops.  A query with no instruction is
+ * untouched, bit for bit (its q_boost is checked, not applied); such queries mix with scripted ones in a batch.
+ *
+ * BOOSTS.  The reference hands a node's incoming boost B on to its inner node and gives the node itself
+ * B * node_boost (planner.rs:783-790; function_score the same, :746-755).  The ABI takes FINAL values per stage: the
+ * caller folds B into q_weights as for any query, passes q_boost = B * node_boost of the script_score node here and
+ * q_boost = B * node_boost of the function_score node in its spec.
+ *
+ * slg_batch_prepare_script is slg_batch_prepare_fscore with the script spec: planned as a sorted batch is (every doc
+ * of the scored lists is a candidate with its exact score), in score order or under a sort spec whose `_score` parts
+ * read the new score.  fscore NULL: the script stage alone (`order` must still be one of the two values).  With an
+ * fscore spec the batch has two stages, enqueued behind the scoring kernel and in front of the select in this order:
+ *   SLG_SCRIPT_OUTER  function_score first, the script reads its score and the docs it dropped stay dropped:
+ *                     script_score{query: function_score{query: Q}}
+ *   SLG_SCRIPT_INNER  the script first, function_score reads its score: function_score{query: script_score{query: Q}}
+ * (evaluate_compiled_score evaluates a node's `base` with `?`: an inner None drops the doc, else the outer node
+ * reads the inner score.)  A stage in which no query has work launches nothing.  slg_batch_script_info: the
+ * queries with a program and the deepest stack of the batch's programs (0 without work).  slg_batch_fscore_info
+ * answers for the fscore stage when there is one.  slg_search_batch_script is the one-call form; stats may be NULL;
+ * out_matched may be NULL and must be NULL without a sort spec.
+ *
+ * Errors, the spec's own before an index state is looked at.  SLG_ERR_INVALID: a NULL spec or array, offsets that
+ * decrease, an unknown op, a const index >= n_consts, a non-finite q_boost, an unknown order;
+ * then against the state: an unknown field id, a keyword column, a field without a column for a segment.
+ * SLG_ERR_UNSUPPORTED (CPU scorer), behind every invalid argument: a program of more than SLG_MAX_SCRIPT_INSTRS
+ * instructions, a stack deeper than SLG_MAX_SCRIPT_DEPTH, more than SLG_MAX_SCRIPT_FIELDS distinct fields in a
+ * query, a non-finite constant (the reference compiles a 310-digit literal to inf and returns None for every doc),
+ * an ill-formed program — a stack underflow or a final depth other than 1, which the reference accepts and answers
+ * with no hit (e.g. "1 2") — and a column that holds a non-finite value (the rule of aggregations).
+ * slg_batch_run_sharded* and slg_batch_fetch_sharded refuse a script batch with SLG_ERR_UNSUPPORTED.
+ * Not built (CPU scorer): script_score below the root or over any other inner query, more than the two stages,
+ * rank_feature, constant_score, explain, and specs on any other batch kind.
+ * --------------------------------------------------------------------------------------------------------- */
+#define SLG_MAX_SCRIPT_INSTRS 64u /* instructions of one query */
+#define SLG_MAX_SCRIPT_DEPTH 8u   /* stack slots */
+#define SLG_MAX_SCRIPT_FIELDS 8u  /* distinct fields of one query */
+enum { SLG_SCRIPT_PUSH_CONST = 0, SLG_SCRIPT_PUSH_FIELD = 1, SLG_SCRIPT_PUSH_SCORE = 2, SLG_SCRIPT_ADD = 3,
+       SLG_SCRIPT_SUB = 4, SLG_SCRIPT_MUL = 5, SLG_SCRIPT_DIV = 6, SLG_SCRIPT_NEG = 7 };
+enum { SLG_SCRIPT_OUTER = 0, SLG_SCRIPT_INNER = 1 };
+typedef struct slg_script_spec {
+  const uint32_t *p_offsets; /* [nq + 1] into the i_ arrays */
+  const int32_t *i_op;       /* [n_instructions] SLG_SCRIPT_* */
+  const int32_t *i_arg;      /* [n_instructions] PUSH_FIELD: agg field id (numeric); PUSH_CONST: index into consts */
+  const double *consts;      /* [n_consts] */
+  uint32_t n_consts;
+  const float *q_boost;      /* [nq] */
+} slg_script_spec;
+slg_batch *slg_batch_prepare_script(slg_index *index, uint32_t nq, const uint32_t *q_offsets, const uint32_t *q_term_ids,
+                                    const float *q_weights, const slg_score_plans *plans_or_null,
+                                    const int32_t *q_filter_or_null, const slg_sort_spec *sort_or_null,
+                                    const slg_script_spec *script, const slg_fscore_spec *fscore_or_null, int order,
+                                    uint32_t k, int strategy);
+int slg_batch_script_info(const slg_batch *batch, uint32_t *out_queries_with_work, uint32_t *out_max_depth);
+int slg_search_batch_script(slg_index *index, uint32_t nq, const uint32_t *q_offsets, const uint32_t *q_term_ids,
+                            const float *q_weights, const slg_score_plans *plans_or_null,
+                            const int32_t *q_filter_or_null, const slg_sort_spec *sort_or_null,
+                            const slg_script_spec *script, const slg_fscore_spec *fscore_or_null, int order, uint32_t k,
+                            int strategy, uint32_t *out_doc, uint32_t *out_seg, float *out_score, uint32_t *out_count,
+                            slg_stats *stats_or_null, uint64_t *out_matched_or_null);
 
 /* ---- field collapsing (SearchRequest::collapse, api/reader.rs:2826-2835, 3499-3595) --------------------
  * The reference collapses the top_k = candidate_size + 1 hits it already holds, in their SortKey order

@@ -93,6 +93,10 @@ pub const SLG_MAX_AGG_RANKS: u32 = 1 << 24;
     pub f_modifier: *const i32, pub f_decay_fn: *const i32, pub f_missing: *const f64, pub f_origin: *const f64,
     pub f_scale: *const f64, pub f_offset: *const f64, pub f_decay: *const f64,
 }
+#[repr(C)] pub struct slg_script_spec {
+    pub p_offsets: *const u32, pub i_op: *const i32, pub i_arg: *const i32, pub consts: *const f64,
+    pub n_consts: u32, pub q_boost: *const c_float,
+}
 #[repr(C)] pub struct slg_filter_node {
     pub kind: i32, pub field: i32, pub filter_id: i32, pub arity: u32, pub lo_f: f64, pub hi_f: f64,
     pub lo_i: i64, pub hi_i: i64, pub ord_begin: u32, pub n_ords_in: u32,
@@ -381,6 +385,18 @@ extern "C" {
     pub fn slg_batch_prepare_fscore(index: *mut slg_index, nq: u32, q_offsets: *const u32, q_term_ids: *const u32,
         q_weights: *const c_float, plans: *const slg_score_plans, q_filter: *const i32,
         sort: *const slg_sort_spec, spec: *const slg_fscore_spec, k: u32, strategy: c_int) -> *mut slg_batch;
+    // script_score at the root (arithmetic over _score, constants and numeric columns), alone or chained with a
+    // function_score stage (order: SLG_SCRIPT_OUTER = script_score{function_score}, _INNER = the other nesting)
+    pub fn slg_batch_prepare_script(index: *mut slg_index, nq: u32, q_offsets: *const u32, q_term_ids: *const u32,
+        q_weights: *const c_float, plans: *const slg_score_plans, q_filter: *const i32,
+        sort: *const slg_sort_spec, script: *const slg_script_spec, fscore: *const slg_fscore_spec, order: c_int,
+        k: u32, strategy: c_int) -> *mut slg_batch;
+    pub fn slg_batch_script_info(batch: *const slg_batch, out_queries_with_work: *mut u32, out_max_depth: *mut u32) -> c_int;
+    pub fn slg_search_batch_script(index: *mut slg_index, nq: u32, q_offsets: *const u32, q_term_ids: *const u32,
+        q_weights: *const c_float, plans: *const slg_score_plans, q_filter: *const i32,
+        sort: *const slg_sort_spec, script: *const slg_script_spec, fscore: *const slg_fscore_spec, order: c_int,
+        k: u32, strategy: c_int, out_doc: *mut u32, out_seg: *mut u32, out_score: *mut c_float, out_count: *mut u32,
+        stats: *mut slg_stats, out_matched: *mut u64) -> c_int;
     pub fn slg_index_add_filter_trees(index: *mut slg_index, trees: *const slg_filter_tree, n_trees: u32,
         out_ids: *mut i32) -> c_int;
     pub fn slg_index_fetch_filter(index: *mut slg_index, filter_id: c_int, seg: u32, out_pass: *mut u8) -> c_int;
@@ -449,6 +465,19 @@ pub const SLG_FSCORE_BOOST_MAX: i32 = 3;
 pub const SLG_FSCORE_BOOST_MIN: i32 = 4;
 pub const SLG_FSCORE_HAS_MAX_BOOST: u32 = 1;
 pub const SLG_FSCORE_HAS_MIN_SCORE: u32 = 2;
+pub const SLG_MAX_SCRIPT_INSTRS: u32 = 64;
+pub const SLG_MAX_SCRIPT_DEPTH: u32 = 8;
+pub const SLG_MAX_SCRIPT_FIELDS: u32 = 8;
+pub const SLG_SCRIPT_PUSH_CONST: i32 = 0;
+pub const SLG_SCRIPT_PUSH_FIELD: i32 = 1;
+pub const SLG_SCRIPT_PUSH_SCORE: i32 = 2;
+pub const SLG_SCRIPT_ADD: i32 = 3;
+pub const SLG_SCRIPT_SUB: i32 = 4;
+pub const SLG_SCRIPT_MUL: i32 = 5;
+pub const SLG_SCRIPT_DIV: i32 = 6;
+pub const SLG_SCRIPT_NEG: i32 = 7;
+pub const SLG_SCRIPT_OUTER: i32 = 0;
+pub const SLG_SCRIPT_INNER: i32 = 1;
 pub const SLG_FILTER_KEYWORD_IN: i32 = 0;
 pub const SLG_FILTER_RANGE_F64: i32 = 1;
 pub const SLG_FILTER_RANGE_I64: i32 = 2;

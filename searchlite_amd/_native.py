@@ -53,6 +53,9 @@ FSCORE_DECAY_EXP, FSCORE_DECAY_GAUSS, FSCORE_DECAY_LINEAR = 0, 1, 2
 FSCORE_MODE_SUM, FSCORE_MODE_MULTIPLY, FSCORE_MODE_MAX, FSCORE_MODE_MIN, FSCORE_MODE_AVG = 0, 1, 2, 3, 4
 FSCORE_BOOST_MULTIPLY, FSCORE_BOOST_SUM, FSCORE_BOOST_REPLACE, FSCORE_BOOST_MAX, FSCORE_BOOST_MIN = 0, 1, 2, 3, 4
 FSCORE_HAS_MAX_BOOST, FSCORE_HAS_MIN_SCORE = 1, 2
+MAX_SCRIPT_INSTRS, MAX_SCRIPT_DEPTH, MAX_SCRIPT_FIELDS = 64, 8, 8
+SCRIPT_PUSH_CONST, SCRIPT_PUSH_FIELD, SCRIPT_PUSH_SCORE, SCRIPT_ADD, SCRIPT_SUB, SCRIPT_MUL, SCRIPT_DIV, SCRIPT_NEG = range(8)
+SCRIPT_OUTER, SCRIPT_INNER = 0, 1
 FILTER_KEYWORD_IN, FILTER_RANGE_F64, FILTER_RANGE_I64, FILTER_ID, FILTER_AND, FILTER_OR, FILTER_NOT = 0, 1, 2, 3, 4, 5, 6
 MAX_FILTER_NODES, MAX_FILTER_DEPTH, MAX_FILTER_TREES = 64, 16, 64
 MAX_COLLAPSE_ROWS = 4096
@@ -191,6 +194,13 @@ class FscoreSpec(C.Structure):
                 ("f_weight", C.c_void_p), ("f_modifier", C.c_void_p), ("f_decay_fn", C.c_void_p),
                 ("f_missing", C.c_void_p), ("f_origin", C.c_void_p), ("f_scale", C.c_void_p),
                 ("f_offset", C.c_void_p), ("f_decay", C.c_void_p)]
+
+
+class ScriptSpec(C.Structure):
+    """slg_script_spec: the script_score program of every query of a batch (CSR instructions in reverse Polish
+    order, their constants, and boost per query)."""
+    _fields_ = [("p_offsets", C.c_void_p), ("i_op", C.c_void_p), ("i_arg", C.c_void_p), ("consts", C.c_void_p),
+                ("n_consts", C.c_uint32), ("q_boost", C.c_void_p)]
 
 
 class CollapseSpec(C.Structure):
@@ -375,6 +385,9 @@ def load():
         "slg_search_batch_phrase": (i32, [vp, u32, vp, vp, vp, vp, vp, vp, vp, vp, u32, i32, vp, vp, vp, vp, vp, vp]),
         "slg_batch_prepare_fscore": (vp, [vp, u32, vp, vp, vp, vp, vp, vp, vp, u32, i32]),
         "slg_batch_fscore_info": (i32, [vp, vp, vp]),
+        "slg_batch_prepare_script": (vp, [vp, u32, vp, vp, vp, vp, vp, vp, vp, vp, i32, u32, i32]),
+        "slg_batch_script_info": (i32, [vp, vp, vp]),
+        "slg_search_batch_script": (i32, [vp, u32, vp, vp, vp, vp, vp, vp, vp, vp, i32, u32, i32, vp, vp, vp, vp, vp, vp]),
         "slg_index_add_filter_trees": (i32, [vp, vp, u32, vp]),
         "slg_index_fetch_filter": (i32, [vp, i32, u32, vp]),
         "slg_search_batch_fscore": (i32, [vp, u32, vp, vp, vp, vp, vp, vp, vp, u32, i32, vp, vp, vp, vp, vp, vp]),

@@ -146,7 +146,7 @@ void slghost::release_batch_buffers(slg_batch *b, bool to_pool) {
                     &b->d_out, &b->d_stamps, &b->d_blk_skip, &b->d_gather, &b->d_merged, &b->d_q_cand,
                     &b->d_hy_keys, &b->d_hy_work, &b->d_agg_desc, &b->d_agg_counts, &b->d_agg_stats,
                     &b->d_agg_values, &b->d_agg_scratch,
-                    &b->d_rs_desc, &b->d_rs_side, &b->d_bool_desc, &b->d_phrase_desc, &b->d_booltree_desc, &b->d_fscore_desc,
+                    &b->d_rs_desc, &b->d_rs_side, &b->d_bool_desc, &b->d_phrase_desc, &b->d_booltree_desc, &b->d_fscore_desc, &b->d_script_desc,
                     &b->d_cl_desc, &b->d_cl_side};
   for (DevBuf *d : bufs) {
     if (!to_pool) d->pool = nullptr;
@@ -201,6 +201,11 @@ slg_batch *slghost::prepare_impl(const PrepareRequest &r) {
     else if (r.boolean.on) slgplan::check_bool(r.boolean.spec, nq, plans);
     if (r.booltree.on) slgplan::check_bool_tree(r.booltree.spec, nq, plans);
     if (r.fscore.on) slgplan::check_fscore(r.fscore.spec, nq);
+    slgplan::ScriptShape script_shape;
+    if (r.script.on) {
+      slgplan::check_script_order(r.script_order);  // (an invalid argument comes before an unsupported program)
+      slgplan::check_script(r.script.spec, nq, script_shape);
+    }
     if (r.collapse.on) slgplan::check_collapse(r.collapse.spec, k);
     SLG_REQUIRE(ix != nullptr, "index is NULL");
     SLG_REQUIRE(!after || q_cursor != nullptr, "q_cursor is NULL");
@@ -238,7 +243,7 @@ slg_batch *slghost::prepare_impl(const PrepareRequest &r) {
     in.strategy = r.strategy;
     in.filter_live = filter_live.data();
     in.n_filters = filter_live.size();
-    in.sorted = sort != nullptr || after || hybrid || r.aggs.on || r.boolean.on || r.booltree.on || r.fscore.on;
+    in.sorted = sort != nullptr || after || hybrid || r.aggs.on || r.boolean.on || r.booltree.on || r.fscore.on || r.script.on;
     SortBinding sorting;  // the columns of the sort parts in the batch's state
     if (sort) sorting = bind_sort(*snap, *sort, "", "part ");
     // the cursors as the key words the select kernel compares (against the same snapshot's field kinds)
@@ -276,6 +281,10 @@ slg_batch *slghost::prepare_impl(const PrepareRequest &r) {
     if (r.fscore.on)
       slgplan::plan_fscore(fscore_field_views(*snap), snap->reject_host.data(), filter_live.data(), filter_live.size(),
                            (uint32_t)snap->segs.size(), nq, *r.fscore.spec, fscore_plan);
+    slgplan::ScriptPlan script_plan;
+    if (r.script.on)
+      slgplan::plan_script(fscore_field_views(*snap), (uint32_t)snap->segs.size(), nq, *r.script.spec, script_shape,
+                           script_plan);
 
     DeviceGuard g(ix->device);
     b = new slg_batch();
@@ -397,6 +406,7 @@ slg_batch *slghost::prepare_impl(const PrepareRequest &r) {
     }
     if (r.booltree.on) booltree_attach(b, booltree_plan);
     if (r.fscore.on) fscore_attach(b, fscore_plan);
+    if (r.script.on) script_attach(b, script_plan, r.fscore.on && r.script_order == SLG_SCRIPT_INNER);
     if (r.collapse.on) collapse_attach(b, *r.collapse.spec, sort);
     {
       std::lock_guard<std::mutex> lk(ix->mu);
@@ -527,7 +537,10 @@ int slg_batch_run(slg_batch *b) {
     if (b->phrase) phrase_launch(b, st);
     else if (b->boolean) bool_launch(b, st);
     else if (b->booltree) booltree_launch(b, st);
+    // (a script batch: the stage of the inner node first, the outer node reads the score it left)
+    if (b->script && b->script_first) script_launch(b, st);
     if (b->fscore) fscore_launch(b, st);  // (the candidates' scores rewritten, those below min_score dropped)
+    if (b->script && !b->script_first) script_launch(b, st);
     if (b->sorted) {  // (also without slices: every row is empty, every matched count 0)
       slg::SortedSelectParams sp{};
       fill_select(sp, b);
@@ -965,6 +978,28 @@ int slg_search_batch_fscore(slg_index *ix, uint32_t nq, const uint32_t *q_offset
                             slg_stats *stats, uint64_t *out_matched) {
   return run_to_host(slg_batch_prepare_fscore(ix, nq, q_offsets, q_term_ids, q_weights, plans, q_filter, sort, spec, k,
                                               strategy),
+                     HostOut{out_doc, out_seg, out_score, out_count, stats, out_matched});
+}
+
+slg_batch *slg_batch_prepare_script(slg_index *ix, uint32_t nq, const uint32_t *q_offsets, const uint32_t *q_term_ids,
+                                    const float *q_weights, const slg_score_plans *plans, const int32_t *q_filter,
+                                    const slg_sort_spec *sort, const slg_script_spec *script,
+                                    const slg_fscore_spec *fscore, int order, uint32_t k, int strategy) {
+  PrepareRequest r{ix, nq, q_offsets, q_term_ids, q_weights, plans, q_filter, k, strategy};
+  r.sort = if_given(sort);
+  r.fscore = if_given(fscore);
+  r.script = {true, script};
+  r.script_order = order;
+  return prepare_impl(r);
+}
+
+int slg_search_batch_script(slg_index *ix, uint32_t nq, const uint32_t *q_offsets, const uint32_t *q_term_ids,
+                            const float *q_weights, const slg_score_plans *plans, const int32_t *q_filter,
+                            const slg_sort_spec *sort, const slg_script_spec *script, const slg_fscore_spec *fscore,
+                            int order, uint32_t k, int strategy, uint32_t *out_doc, uint32_t *out_seg,
+                            float *out_score, uint32_t *out_count, slg_stats *stats, uint64_t *out_matched) {
+  return run_to_host(slg_batch_prepare_script(ix, nq, q_offsets, q_term_ids, q_weights, plans, q_filter, sort, script,
+                                              fscore, order, k, strategy),
                      HostOut{out_doc, out_seg, out_score, out_count, stats, out_matched});
 }
 

@@ -317,6 +317,28 @@ struct FscoreFn {
 };
 constexpr uint32_t kFscoreMaxFuncs = 8;  // = SLG_MAX_FSCORE_FUNCS
 
+// ---- script_score (slg_batch_prepare_script; kernel: slg_script.hpp, planner: slg_plan.cpp) --------
+// The program of query q is instrs[instr_begin .. instr_begin + n_instrs), in reverse Polish order, the same for
+// every segment.  The stack positions of such a program are static: the planner records with every instruction
+// the slot it works at, and the kernel never tracks a stack pointer.  The query's distinct fields are numbered in
+// order of first use; field f's column is cols[col[f] * n_segs + seg].
+constexpr uint32_t kScriptMaxInstrs = 64, kScriptMaxDepth = 8, kScriptMaxFields = 8;  // = SLG_MAX_SCRIPT_*
+struct ScriptQuery {
+  uint32_t instr_begin, n_instrs;   // n_instrs 0: the query is left as it is
+  uint32_t n_fields;
+  float boost;
+  uint32_t max_depth;               // the deepest stack of the program
+  uint32_t pad[3];
+  uint32_t col[kScriptMaxFields];   // the fields' rows of the column table
+};
+struct ScriptInstr {
+  uint32_t code;   // bits 0-7 SLG_SCRIPT_* op; 8-15 `at`: the slot the result is written to — a push: the depth
+                   // before it; ADD / SUB / MUL / DIV: a = slot at, b = slot at + 1; NEG: slot at; 16-23 PUSH_FIELD:
+                   // the field's number in the query
+  uint32_t pad;
+  double value;    // PUSH_CONST
+};
+
 // ---- filter trees (slg_index_add_filter_trees; kernel: slg_filter.hpp, planner: slg_plan.cpp) --------
 // The image of one call: trees[n_trees], nodes (every tree's, in postfix order), the column table, the filter
 // table, the words of the ordinal bit sets.  A leaf's column is cols[row * n_segs + seg] (ColumnDev; a keyword

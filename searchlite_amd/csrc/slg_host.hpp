@@ -1,5 +1,5 @@
 // slg_host.hpp — what the host translation units of the C ABI share (slg_index.hip, slg_batch.hip,
-// slg_shard.hip, slg_rerank.hip, slg_vsearch.hip, slg_hybrid.hip, slg_aggs.hip, slg_rescore.hip, slg_bool.hip, slg_booltree.hip, slg_phrase.hip, slg_fscore.hip, slg_collapse.hip): the error plumbing, device memory, the host
+// slg_shard.hip, slg_rerank.hip, slg_vsearch.hip, slg_hybrid.hip, slg_aggs.hip, slg_rescore.hip, slg_bool.hip, slg_booltree.hip, slg_phrase.hip, slg_fscore.hip, slg_script.hip, slg_collapse.hip): the error plumbing, device memory, the host
 // structures behind the opaque handles and the small helpers several entry points use.  Private: not
 // installed, not part of include/.  No kernel header is included here — each unit includes the one
 // whose kernels it launches (slg_stage.hpp, slg_kernels.hpp, slg_rerank.hpp, slg_vsearch.hpp, slg_hybrid.hpp; the shard
@@ -561,6 +561,14 @@ struct slg_batch {
   bool fscore_full = false;  // some function needs ln / log1p / log2 / pow: the full instantiation
   uint32_t fscore_fns = 0, fscore_cols = 0;  // entries of the two tables behind the FscoreQuery records
   DevBuf d_fscore_desc;      // slg::FscoreQuery[nq], FscoreFn[fscore_fns], ColumnDev[fscore_cols], bitmap addresses
+  // script_score batch (slg_batch_prepare_script): planned as a function_score batch is; script_kernel runs between
+  // the scoring kernel and the select — alone, in front of the fscore stage (script_first) or behind it — rewrites
+  // every candidate's score and drops the candidates whose script gives none (slg_script.hip)
+  bool script = false, script_first = false;
+  uint32_t script_work = 0;       // queries with a program (0: nothing is launched)
+  uint32_t script_max_depth = 0;  // the deepest stack of the batch's programs
+  uint32_t script_instrs = 0;     // entries of the instruction table behind the ScriptQuery records
+  DevBuf d_script_desc;           // slg::ScriptQuery[nq], ScriptInstr[script_instrs], ColumnDev[fields][n_segs]
   // collapse batch (slg_batch_prepare_collapse): a plain, sorted or cursor batch; collapse_kernel runs behind its
   // last kernel and fills the side arrays from each query's rows, which it leaves as they are (slg_collapse.hip)
   bool collapse = false;
@@ -689,6 +697,8 @@ struct PrepareRequest {
   Asked<slg_phrase_spec> phrase;
   Asked<slg_bool_tree_spec> booltree;
   Asked<slg_fscore_spec> fscore;
+  Asked<slg_script_spec> script;  // slg_batch_prepare_script (with fscore: the two stages, in script_order)
+  int script_order = 0;           // SLG_SCRIPT_OUTER / _INNER
   Asked<slg_collapse_spec> collapse;
 };
 // a spec that is a kind of its own only when it is given (the sort of a bool, phrase, cursor or agg batch)
@@ -803,6 +813,9 @@ void booltree_launch(slg_batch *b, hipStream_t st);
 std::vector<slgplan::FscoreFieldView> fscore_field_views(const IndexState &S);
 void fscore_attach(slg_batch *b, const slgplan::FscorePlan &fp);
 void fscore_launch(slg_batch *b, hipStream_t st);
+// slg_script.hip: the same for the script stage of a script batch
+void script_attach(slg_batch *b, const slgplan::ScriptPlan &sp, bool first);
+void script_launch(slg_batch *b, hipStream_t st);
 // slg_collapse.hip: the spec against the batch's state (its keyword column, the inner sort's columns), the tables
 // and side arrays onto the device (throws; the batch is otherwise prepared); the launch behind the batch's rows
 void collapse_attach(slg_batch *b, const slg_collapse_spec &spec, const slg_sort_spec *batch_sort);

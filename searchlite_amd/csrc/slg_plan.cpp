@@ -1420,6 +1420,113 @@ void plan_fscore(const std::vector<FscoreFieldView> &fields, const uint32_t *con
   fill_tables(fields, used_fields, reject, used_filters, n_segs, out.cols, out.filters);
 }
 
+// ---- script_score ------------------------------------------------------------------------------------------
+static_assert(slg::kScriptMaxInstrs == SLG_MAX_SCRIPT_INSTRS && slg::kScriptMaxDepth == SLG_MAX_SCRIPT_DEPTH &&
+                  slg::kScriptMaxFields == SLG_MAX_SCRIPT_FIELDS, "the kernel's limits and the ABI's");
+static_assert(sizeof(slg::ScriptQuery) == 64 && sizeof(slg::ScriptInstr) == 16, "records the kernel reads in whole words");
+
+void check_script_order(int order) {
+  PLAN_REQUIRE(order == SLG_SCRIPT_OUTER || order == SLG_SCRIPT_INNER, "unknown script order");
+}
+
+void check_script(const slg_script_spec *spec, uint32_t nq, ScriptShape &shape) {
+  shape = ScriptShape{};
+  PLAN_REQUIRE(spec != nullptr, "script spec is NULL");
+  shape.max_depth.assign(nq, 0u);
+  if (nq == 0) return;
+  PLAN_REQUIRE(spec->p_offsets != nullptr, "script p_offsets is NULL");
+  PLAN_REQUIRE(spec->q_boost != nullptr, "script q_boost is NULL");
+  for (uint32_t q = 0; q < nq; q++)
+    PLAN_REQUIRE(spec->p_offsets[q + 1] >= spec->p_offsets[q], "script p_offsets not monotone");
+  const uint32_t i_lo = spec->p_offsets[0], i_hi = spec->p_offsets[nq];
+  PLAN_REQUIRE(i_hi == i_lo || (spec->i_op && spec->i_arg), "script i_op/i_arg is NULL");
+  shape.at.assign(i_hi - i_lo, 0u);
+  std::string unsupported;  // (reported behind every invalid argument)
+  const auto refuse = [&](const std::string &what) {
+    if (unsupported.empty()) unsupported = what;
+  };
+  for (uint32_t q = 0; q < nq; q++) {
+    const std::string in_q = " in script query " + std::to_string(q);
+    PLAN_REQUIRE(std::isfinite(spec->q_boost[q]), "non-finite q_boost" + in_q);
+    const uint32_t i0 = spec->p_offsets[q], n = spec->p_offsets[q + 1] - i0;
+    if (n > SLG_MAX_SCRIPT_INSTRS) refuse("more than SLG_MAX_SCRIPT_INSTRS instructions" + in_q);
+    uint32_t depth = 0, deepest = 0;
+    bool underflow = false;
+    std::vector<int32_t> seen;  // the distinct fields
+    for (uint32_t i = i0; i < i0 + n; i++) {
+      const int32_t op = spec->i_op[i];
+      PLAN_REQUIRE(op >= SLG_SCRIPT_PUSH_CONST && op <= SLG_SCRIPT_NEG, "unknown script op" + in_q);
+      const uint32_t pops = op <= SLG_SCRIPT_PUSH_SCORE ? 0u : (op == SLG_SCRIPT_NEG ? 1u : 2u);
+      if (op == SLG_SCRIPT_PUSH_CONST) {
+        PLAN_REQUIRE(spec->i_arg[i] >= 0 && (uint32_t)spec->i_arg[i] < spec->n_consts, "const index >= n_consts" + in_q);
+        PLAN_REQUIRE(spec->consts != nullptr, "script consts is NULL");
+        if (!std::isfinite(spec->consts[spec->i_arg[i]])) refuse("non-finite constant (CPU path)" + in_q);
+      } else if (op == SLG_SCRIPT_PUSH_FIELD) {
+        row_of(seen, spec->i_arg[i]);
+      }
+      if (depth < pops) {  // (the walk goes on for the invalid arguments behind it)
+        underflow = true;
+        depth = pops;
+      }
+      depth -= pops;
+      shape.at[i - i_lo] = (uint8_t)std::min<uint32_t>(depth, 255u);
+      depth++;
+      deepest = std::max(deepest, depth);
+    }
+    if (n != 0 && (underflow || depth != 1)) refuse("ill-formed program: the reference returns no hit (CPU path)" + in_q);
+    if (deepest > SLG_MAX_SCRIPT_DEPTH) refuse("stack deeper than SLG_MAX_SCRIPT_DEPTH" + in_q);
+    if (seen.size() > SLG_MAX_SCRIPT_FIELDS) refuse("more than SLG_MAX_SCRIPT_FIELDS distinct fields" + in_q);
+    shape.max_depth[q] = deepest;
+    shape.batch_max_depth = std::max(shape.batch_max_depth, deepest);
+  }
+  if (!unsupported.empty()) throw SlgError(SLG_ERR_UNSUPPORTED, unsupported);
+}
+
+void plan_script(const std::vector<FscoreFieldView> &fields, uint32_t n_segs, uint32_t nq, const slg_script_spec &spec,
+                 const ScriptShape &shape, ScriptPlan &out) {
+  out = ScriptPlan{};
+  out.queries.assign(nq, slg::ScriptQuery{});
+  if (nq == 0) return;
+  const uint32_t i_base = spec.p_offsets[0];
+  std::vector<int32_t> used_fields;  // the rows of the column table, in order of first use
+  std::string unsupported;           // (reported behind every invalid argument)
+  for (uint32_t q = 0; q < nq; q++) {
+    const std::string in_q = " in script query " + std::to_string(q);
+    const uint32_t i0 = spec.p_offsets[q], n = spec.p_offsets[q + 1] - i0;
+    slg::ScriptQuery &sq = out.queries[q];
+    sq.instr_begin = i0 - i_base;
+    sq.n_instrs = n;
+    sq.boost = spec.q_boost[q];
+    sq.max_depth = shape.max_depth[q];
+    out.n_work += n != 0u ? 1u : 0u;
+    std::vector<int32_t> mine;  // the query's distinct fields, in order of first use
+    for (uint32_t i = i0; i < i0 + n; i++) {
+      slg::ScriptInstr in{};
+      const int32_t op = spec.i_op[i];
+      in.code = (uint32_t)op | ((uint32_t)shape.at[i - i_base] << 8);
+      if (op == SLG_SCRIPT_PUSH_CONST) {
+        in.value = spec.consts[spec.i_arg[i]];
+      } else if (op == SLG_SCRIPT_PUSH_FIELD) {
+        const int32_t id = spec.i_arg[i];
+        const FscoreFieldView &fv = agg_field(fields, id, "", in_q);
+        PLAN_REQUIRE(!fv.keyword, "agg field " + std::to_string(id) + " is a keyword field" + in_q);
+        agg_field_rows(fv, n_segs, "", "");
+        if (fv.non_finite && unsupported.empty())
+          unsupported = "agg field " + std::to_string(id) + " holds a non-finite value (CPU path)" + in_q;
+        const uint32_t f = row_of(mine, id);
+        sq.col[f] = row_of(used_fields, id);  // (f < SLG_MAX_SCRIPT_FIELDS: check_script)
+        in.code |= f << 16;
+      }
+      out.instrs.push_back(in);
+    }
+    sq.n_fields = (uint32_t)mine.size();
+  }
+  if (!unsupported.empty()) throw SlgError(SLG_ERR_UNSUPPORTED, unsupported);
+  out.max_depth = shape.batch_max_depth;
+  std::vector<const uint32_t *> no_filters;
+  fill_tables(fields, used_fields, nullptr, {}, n_segs, out.cols, no_filters);
+}
+
 // ---- nested boolean matchers ------------------------------------------------------------------------------
 static_assert(slg::kBoolTreeMaxLeaves == SLG_MAX_BOOL_TREE_LEAVES && slg::kBoolTreeMaxNodes == SLG_MAX_BOOL_TREE_NODES &&
                   slg::kBoolTreeMaxLeaves == 32 && slg::kBoolTreeMaxNodes == 32,

@@ -238,6 +238,33 @@ struct FscorePlan {
 void plan_fscore(const std::vector<FscoreFieldView> &fields, const uint32_t *const *reject, const char *filter_live,
                  size_t n_filters, uint32_t n_segs, uint32_t nq, const slg_fscore_spec &spec, FscorePlan &out);
 
+// ---- script_score (slg_batch_prepare_script) ----
+// The checks of a spec that need no index (throws SlgError), in ONE walk over each program, which also records the
+// static stack positions (ScriptShape).  SLG_ERR_INVALID, reported first: a NULL spec or array, offsets that
+// decrease, an unknown op, a const index >= n_consts, a non-finite q_boost.  Behind every invalid argument
+// SLG_ERR_UNSUPPORTED: more than SLG_MAX_SCRIPT_INSTRS instructions, a non-finite constant, a stack underflow or a
+// final depth other than 1, a stack deeper than SLG_MAX_SCRIPT_DEPTH, more than SLG_MAX_SCRIPT_FIELDS distinct
+// fields in a query.  check_script_order: SLG_ERR_INVALID for an order that is neither SLG_SCRIPT_OUTER nor _INNER.
+struct ScriptShape {
+  std::vector<uint8_t> at;          // per instruction of the spec (from p_offsets[0] on): ScriptInstr's `at`
+  std::vector<uint32_t> max_depth;  // [nq] the deepest stack of each program (0: no program)
+  uint32_t batch_max_depth = 0;
+};
+void check_script(const slg_script_spec *spec, uint32_t nq, ScriptShape &shape);
+void check_script_order(int order);
+// The tables of a checked spec against an index state's fields.  Throws SLG_ERR_INVALID for an unknown field id,
+// a keyword column, a field without a column for a segment; behind those SLG_ERR_UNSUPPORTED for a column that
+// holds a non-finite value.
+struct ScriptPlan {
+  std::vector<slg::ScriptQuery> queries;  // [nq]
+  std::vector<slg::ScriptInstr> instrs;   // the spec's instructions, in its order
+  std::vector<slg::ColumnDev> cols;       // [fields the batch names][n_segs]
+  uint32_t n_work = 0;                    // queries with a program (0: nothing is launched)
+  uint32_t max_depth = 0;                 // the deepest stack of the batch's programs
+};
+void plan_script(const std::vector<FscoreFieldView> &fields, uint32_t n_segs, uint32_t nq, const slg_script_spec &spec,
+                 const ScriptShape &shape, ScriptPlan &out);
+
 // ---- filter trees (slg_index_add_filter_trees) ----
 // The checks of the trees that need no index (throws SlgError).  SLG_ERR_INVALID, reported first: NULL arrays,
 // n_trees == 0, n_nodes == 0, an unknown kind, a program that underflows the stack or does not end with exactly

@@ -381,6 +381,48 @@ int slgp_plan_fscore(const slgp_fscore_field *fields, uint32_t n_fields, const c
   }
 }
 
+// the host side of slg_batch_prepare_script: check_script_order and check_script, then plan_script against
+// registered fields that exist as descriptions only (slgp_fscore_field, the made-up addresses of slgp_plan_fscore).
+// queries: nq x 16 words (slg::ScriptQuery); instrs: entries of 4 words (slg::ScriptInstr); cols: entries of two
+// addresses (offsets, values).  Each table is filled when it fits its cap; counts: entries of instrs and cols, then
+// the queries with a program and the batch's deepest stack.  0, or a negative error code (err filled)
+int slgp_plan_script(const slgp_fscore_field *fields, uint32_t n_fields, uint32_t n_segs, uint32_t nq,
+                     const slg_script_spec *spec, int order, uint32_t *queries, uint32_t *instrs, uint32_t instrs_cap,
+                     uint64_t *cols, uint32_t cols_cap, uint32_t *counts, char *err, uint32_t err_len) {
+  try {
+    slgplan::ScriptShape shape;
+    slgplan::check_script_order(order);  // (an invalid argument comes before an unsupported program)
+    slgplan::check_script(spec, nq, shape);
+    std::vector<slgplan::FscoreFieldView> views(n_fields);
+    for (uint32_t i = 0; i < n_fields; i++) {
+      views[i] = described_field(fields[i], n_segs);
+      views[i].non_finite = fields[i].non_finite != 0;
+    }
+    slgplan::ScriptPlan sp;
+    slgplan::plan_script(views, n_segs, nq, *spec, shape, sp);
+    static_assert(sizeof(slg::ScriptQuery) == 64 && sizeof(slg::ScriptInstr) == 16 && sizeof(slg::ColumnDev) == 16,
+                  "the words the caller reads");
+    if (queries && nq) std::memcpy(queries, sp.queries.data(), (size_t)nq * sizeof(slg::ScriptQuery));
+    if (instrs && sp.instrs.size() <= instrs_cap && !sp.instrs.empty())
+      std::memcpy(instrs, sp.instrs.data(), sp.instrs.size() * sizeof(slg::ScriptInstr));
+    if (cols && sp.cols.size() <= cols_cap && !sp.cols.empty())
+      std::memcpy(cols, sp.cols.data(), sp.cols.size() * sizeof(slg::ColumnDev));
+    if (counts) {
+      counts[0] = (uint32_t)sp.instrs.size();
+      counts[1] = (uint32_t)sp.cols.size();
+      counts[2] = sp.n_work;
+      counts[3] = sp.max_depth;
+    }
+    return SLG_OK;
+  } catch (const slgplan::SlgError &e) {
+    if (err && err_len) {
+      std::strncpy(err, e.what(), err_len - 1);
+      err[err_len - 1] = 0;
+    }
+    return e.code;
+  }
+}
+
 // the host side of slg_index_add_filter_trees: check_filter_trees, then plan_filter_trees against registered fields
 // and filters that exist as descriptions only (columns and reject bitmaps: the addresses slgp_plan_fscore makes
 // up; a filter with filter_live 0 has none).  tree_rows: n_trees x 2 words (slg::FilterTreeDev); nodes: entries of

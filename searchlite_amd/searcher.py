@@ -528,6 +528,22 @@ class GpuIndex:
         finally:
             b.close()
 
+    def search_batch_script(self, q_offsets, q_terms, q_weights, k: int, scripts, fscore=None, script_order="outer",
+                            sort=None, strategy: int = Wand, q_filter=None, want_stats: bool = False, **plans):
+        """Batch search under a script_score per query (slg_batch_prepare_script).  scripts: the list of
+        script.script_spec(), one entry per query (None: the query is left as it is); fields are agg field ids
+        (add_agg_field); fscore: a function_score stage beside it (the list of fscore_spec()), script_order "outer"
+        = script_score{query: function_score}, "inner" = function_score{query: script_score}; sort: None = order
+        of the new score, else as search_sorted; **plans: the score plan arrays of prepare().
+        -> (doc, seg, score, count[, stats]) in score order, (doc, seg, score, count[, stats], matched) sorted."""
+        b = self.prepare(q_offsets, q_terms, q_weights, k, strategy, q_filter, sort=sort, fscore=fscore, script=scripts,
+                         script_order=script_order, **plans)
+        try:
+            b.run()
+            return b.fetch(want_stats) + ((b.matched_counts(),) if sort is not None else ())
+        finally:
+            b.close()
+
     def search_sorted(self, q_offsets, q_terms, q_weights, k: int, sort, strategy: int = Wand, q_filter=None,
                       **plans):
         """Field-sorted batch search (slg_batch_prepare_sorted).  sort: [(field, order)], field = a sort field id
@@ -561,7 +577,7 @@ class GpuIndex:
                 group_tie=None, q_node_offsets=None, node_kind=None, node_tie=None, node_parent=None,
                 q_min_match=None, sort=None, cursors=None, hybrid=False, aggs=None,
                 rescore=None, clauses=None, phrases=None, fscore=None, collapse=None,
-                clause_tree=None) -> "PreparedBatch":
+                clause_tree=None, script=None, script_order="outer") -> "PreparedBatch":
         """q_leaf / q_plan / q_tie / q_nleaves: score plans; leaf_group / group_plan / group_tie with
         their per-query offsets: two-level plans; q_node_offsets / node_kind / node_tie / node_parent:
         trees of any shape, node by node in pre-order (slg_batch_prepare_plans, slg_score_plans);
@@ -576,12 +592,15 @@ class GpuIndex:
         query, the list of fscore_spec() (or its result) -> slg_batch_prepare_fscore (score order, or with sort);
         collapse: the dict of search_collapse -> slg_batch_prepare_collapse (score order, with sort and / or cursors;
         PreparedBatch.collapse_groups); clause_tree: the dict of search_batch_bool_tree ->
-        slg_batch_prepare_bool_tree (score order, or with sort)."""
+        slg_batch_prepare_bool_tree (score order, or with sort); script: one script_score per query, the list of
+        script.script_spec() (or its result) -> slg_batch_prepare_script (score order, or with sort), alone or with
+        fscore as its second stage: script_order "outer" is script_score{query: function_score}, "inner" is
+        function_score{query: script_score}."""
         return PreparedBatch(self, q_offsets, q_terms, q_weights, k, strategy, q_filter,
                              q_leaf, q_plan, q_tie, q_nleaves, q_leaf_offsets, leaf_group,
                              q_group_offsets, group_plan, group_tie, q_node_offsets, node_kind, node_tie, node_parent,
                              q_min_match, sort, cursors, hybrid, aggs, rescore, clauses, phrases, fscore, collapse,
-                             clause_tree)
+                             clause_tree, script, script_order)
 
     def search_collapse(self, q_offsets, q_terms, q_weights, k: int, collapse, sort=None, cursors=None,
                         strategy: int = Wand, q_filter=None, **plans):
@@ -1110,7 +1129,7 @@ class PreparedBatch:
                  q_leaf_offsets=None, leaf_group=None, q_group_offsets=None, group_plan=None,
                  group_tie=None, q_node_offsets=None, node_kind=None, node_tie=None, node_parent=None,
                  q_min_match=None, sort=None, cursors=None, hybrid=False, aggs=None, rescore=None, clauses=None,
-                 phrases=None, fscore=None, collapse=None, clause_tree=None):
+                 phrases=None, fscore=None, collapse=None, clause_tree=None, script=None, script_order="outer"):
         self.index = index
         self._lib = index._lib
         q_offsets = np.ascontiguousarray(q_offsets, dtype=np.uint32)
@@ -1149,7 +1168,25 @@ class PreparedBatch:
         self.is_fscore = fscore is not None
         self.is_collapse = collapse is not None
         self.is_bool_tree = clause_tree is not None
-        if clause_tree is not None:
+        self.is_script = script is not None
+        if script is not None:
+            # (the library's other prepare calls take no script spec: the refusal is made here with its code)
+            if hybrid or cursors is not None or aggs is not None or rescore is not None or clauses is not None or \
+                    phrases is not None or collapse is not None or clause_tree is not None:
+                raise N.SlgError(N.ERR_UNSUPPORTED, "script_score is not built on cursor, hybrid, aggregation, rescore, "
+                                                    "bool, phrase, collapse or matcher tree batches")
+            from .script import script_spec
+            sspec, self._script_keep = script if isinstance(script, tuple) else script_spec(script, self.nq)
+            fspec = None
+            if fscore is not None:
+                fspec, self._fscore_keep = fscore if isinstance(fscore, tuple) else fscore_spec(fscore, self.nq)
+            order = {"outer": N.SCRIPT_OUTER, "inner": N.SCRIPT_INNER}.get(script_order, script_order)
+            spec = None if sort is None else sort_spec(sort)
+            self._h = self._lib.slg_batch_prepare_script(
+                index._h, self.nq, _ptr(q_offsets), _ptr(q_terms), _ptr(q_weights), C.addressof(plans),
+                opt(qf), None if spec is None else C.addressof(spec), C.addressof(sspec),
+                None if fspec is None else C.addressof(fspec), int(order), k, strategy)
+        elif clause_tree is not None:
             # (the library's other prepare calls take no tree spec: the refusal is made here with its code)
             if hybrid or cursors is not None or aggs is not None or rescore is not None or clauses is not None or \
                     phrases is not None or fscore is not None or collapse is not None:
@@ -1437,6 +1474,11 @@ class PreparedBatch:
             N.check(self._lib.slg_batch_fscore_info(self._h, C.addressof(variant), C.addressof(work)))
             out["fscore_kernel"] = (None, "lean", "full")[variant.value]
             out["fscore_queries"] = work.value
+        if getattr(self, "is_script", False):
+            work, depth = C.c_uint32(), C.c_uint32()
+            N.check(self._lib.slg_batch_script_info(self._h, C.addressof(work), C.addressof(depth)))
+            out["script_queries"] = work.value
+            out["script_max_depth"] = depth.value
         return out
 
     def skip_counts(self):

@@ -1512,7 +1512,8 @@ int slg_search_batch_phrase(slg_index *index, uint32_t nq, const uint32_t *q_off
  * slg_batch_run_sharded* and slg_batch_fetch_sharded refuse a function_score batch with SLG_ERR_UNSUPPORTED.
  * Built beside it: script_score at the root, and the two nodes nested one inside the other
  * (slg_batch_prepare_script, below).  Not built (CPU scorer): function_score below the root or over any other
- * inner query, deeper nesting, rank_feature, constant_score, explain, function filters other than registered
+ * inner query (rank_feature and constant_score at the root are scan batches, below), deeper nesting, explain,
+ * function filters other than registered
  * filter ids, and specs on bool, phrase, cursor, hybrid, aggregation, rescore, sharded and coalesced batches
  * (none of their prepare calls takes the spec).
  * --------------------------------------------------------------------------------------------------------- */
@@ -1609,7 +1610,7 @@ int slg_search_batch_fscore(slg_index *index, uint32_t nq, const uint32_t *q_off
  * with no hit (e.g. "1 2") — and a column that holds a non-finite value (the rule of aggregations).
  * slg_batch_run_sharded* and slg_batch_fetch_sharded refuse a script batch with SLG_ERR_UNSUPPORTED.
  * Not built (CPU scorer): script_score below the root or over any other inner query, more than the two stages,
- * rank_feature, constant_score, explain, and specs on any other batch kind.
+ * explain, and specs on any other batch kind (rank_feature and constant_score at the root are scan batches, below).
  * --------------------------------------------------------------------------------------------------------- */
 #define SLG_MAX_SCRIPT_INSTRS 64u /* instructions of one query */
 #define SLG_MAX_SCRIPT_DEPTH 8u   /* stack slots */
@@ -1637,6 +1638,76 @@ int slg_search_batch_script(slg_index *index, uint32_t nq, const uint32_t *q_off
                             const slg_script_spec *script, const slg_fscore_spec *fscore_or_null, int order, uint32_t k,
                             int strategy, uint32_t *out_doc, uint32_t *out_seg, float *out_score, uint32_t *out_count,
                             slg_stats *stats_or_null, uint64_t *out_matched_or_null);
+
+/* ---------------------------------------------------------------------------------------------------------
+ * Scan batches: match_all, constant_score and rank_feature at the root — requests WITHOUT a scored term.  They
+ * bring no posting list, so their candidates come from a scan over every doc of every segment, the reference's
+ * scan_segment (api/reader.rs:3131-3236).  Every stage behind the candidates is the one every batch kind runs.
+ *
+ * MATCH.  A doc matches when it is not deleted, the node's own filter (q_filter of the spec: constant_score.filter,
+ * a filter id of slg_index_add_filter* or -1) passes and the batch's root filter (q_filter of the call) passes;
+ * docs 0 .. n_docs - 1 of every segment are looked at (:3154-3164).
+ * SCORE.
+ *   SLG_SCAN_MATCH_ALL     1.0 (:428, :3151).
+ *   SLG_SCAN_CONSTANT      q_score: boost * node_boost, multiplied by the caller (:484-490); finite.
+ *   SLG_SCAN_RANK_FEATURE  raw = the FIRST value of the doc in column q_field `as f64`, or (double)q_missing when
+ *                          the doc has none (:176-181); m = modifier(raw): NONE raw; LOG raw <= 0 ? 0 : ln raw;
+ *                          LOG1P raw <= -1 ? 0 : ln(1 + raw) (ln_1p); SQRT raw < 0 ? 0 : sqrt raw; RECIPROCAL
+ *                          raw == 0 ? 0 : 1 / raw (:183-215); a non-finite m DROPS the doc; s = (float)m * q_boost
+ *                          in f32; a non-finite s DROPS the doc (:549-576).  f64 arithmetic, operation by operation.
+ * A dropped doc is neither ranked, counted nor aggregated (the `continue` at :3176-3179 comes before the counter
+ * and the collector).
+ * ORDER.  Rows as in every batch: in score order (score desc by total_cmp, segment asc, doc asc); under a sort
+ * spec the SortKey order of slg_batch_prepare_sorted.  slg_batch_matched_counts gives total_matches for EVERY scan
+ * batch — score-ordered ones and k == 0 included; slg_stats.scored_docs and candidates_examined are the same
+ * number (postings_advanced is 0).
+ * ONE KNOWN DEVIATION.  Under a sort spec without a `_score` part the reference still reports the computed score
+ * of a CONSTANT or RANK_FEATURE hit; the sorted select writes 0.0 there, as for every sorted batch, and a scan batch
+ * returns 0.0.  (MATCH_ALL is 0.0 there in the reference too, :3151.)
+ *
+ * slg_batch_prepare_scan: sort_or_null and aggs_or_null mean what they mean in slg_batch_prepare_aggs (all seven
+ * aggregation kinds); k == 0 is legal, k <= SLG_MAX_K.  slg_batch_run enqueues scan_kernel — no partition kernel
+ * and no scoring kernel — then the select of the batch's order and, with a spec, the aggregation kernels; a batch
+ * with k == 0 and no aggregation launches the scan alone.  The kernel has two instantiations, chosen per batch: a
+ * lean one (MATCH_ALL, CONSTANT, the modifiers NONE / SQRT / RECIPROCAL) and a full one with the f64 ln / log1p;
+ * slg_batch_scan_info tells which (0: the batch has no slice, 1 lean, 2 full), the batch's slices and the docs per
+ * slice the planner cuts at.  run / fetch / device_results / matched_counts / agg_layout / fetch_aggs /
+ * fetch_agg_values / set_stream / sync as for any batch.  slg_search_batch_scan is the one-call form with the
+ * outputs of slg_search_batch_agg_values; the aggregation outputs may be NULL without a spec, out_matched may be
+ * NULL.
+ * MEMORY.  A query whose kind is MATCH_ALL or CONSTANT, in a batch without sort spec and without aggregations, keeps
+ * min(slice docs, k) candidates per slice (all its scores are equal: a doc of the top k is among the first k
+ * passing docs of its slice) and counts the rest.  Every other query keeps 8 bytes per doc of every segment; a
+ * batch too large for the device fails with SLG_ERR_OOM as any candidates-mode batch does.
+ *
+ * Errors, all on the host before any device work.  SLG_ERR_INVALID: a NULL spec or array, an unknown kind or
+ * modifier, a non-finite q_score (CONSTANT), q_missing or q_boost (RANK_FEATURE), an unknown or incomplete filter
+ * id, an unknown field id, a keyword column, a field without a column for every segment, an invalid sort spec or
+ * aggregation spec.  SLG_ERR_UNSUPPORTED: a column recorded as holding a non-finite value (the rule of
+ * aggregations), k > SLG_MAX_K; slg_batch_run_sharded* and slg_batch_fetch_sharded refuse a scan batch.
+ * Not built (CPU path): scan batches with cursor, collapse, rescore, hybrid, function_score or script_score over
+ * them, scan requests in the coalescer, and scan queries mixed with scored queries in one batch.
+ * --------------------------------------------------------------------------------------------------------- */
+enum { SLG_SCAN_MATCH_ALL = 0, SLG_SCAN_CONSTANT = 1, SLG_SCAN_RANK_FEATURE = 2 };
+enum { SLG_SCAN_MOD_NONE = 0, SLG_SCAN_MOD_LOG = 1, SLG_SCAN_MOD_LOG1P = 2, SLG_SCAN_MOD_SQRT = 3,
+       SLG_SCAN_MOD_RECIPROCAL = 4 };
+typedef struct slg_scan_spec {
+  const int32_t *q_kind;     /* [nq] SLG_SCAN_* */
+  const int32_t *q_filter;   /* [nq] the node's own filter id, or -1 */
+  const float *q_score;      /* [nq] CONSTANT: boost * node_boost */
+  const int32_t *q_field;    /* [nq] RANK_FEATURE: agg field id (numeric) */
+  const int32_t *q_modifier; /* [nq] RANK_FEATURE: SLG_SCAN_MOD_* */
+  const float *q_missing;    /* [nq] RANK_FEATURE */
+  const float *q_boost;      /* [nq] RANK_FEATURE */
+} slg_scan_spec;
+slg_batch *slg_batch_prepare_scan(slg_index *index, uint32_t nq, const slg_scan_spec *spec,
+                                  const int32_t *q_filter_or_null, const slg_sort_spec *sort_or_null,
+                                  const slg_agg_spec *aggs_or_null, uint32_t k);
+int slg_batch_scan_info(const slg_batch *batch, uint32_t *out_variant, uint32_t *out_slices, uint32_t *out_slice_docs);
+int slg_search_batch_scan(slg_index *index, uint32_t nq, const slg_scan_spec *spec, const int32_t *q_filter_or_null,
+                          const slg_sort_spec *sort_or_null, const slg_agg_spec *aggs_or_null, uint32_t k,
+                          uint32_t *out_doc, uint32_t *out_seg, float *out_score, uint32_t *out_count,
+                          uint64_t *out_matched_or_null, uint64_t *counts, slg_agg_stats *stats, uint64_t *values);
 
 /* ---- field collapsing (SearchRequest::collapse, api/reader.rs:2826-2835, 3499-3595) --------------------
  * The reference collapses the top_k = candidate_size + 1 hits it already holds, in their SortKey order

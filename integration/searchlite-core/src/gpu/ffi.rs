@@ -97,6 +97,19 @@ pub const SLG_MAX_AGG_RANKS: u32 = 1 << 24;
     pub p_offsets: *const u32, pub i_op: *const i32, pub i_arg: *const i32, pub consts: *const f64,
     pub n_consts: u32, pub q_boost: *const c_float,
 }
+// scan batches: match_all, constant_score and rank_feature at the root (requests without a scored term)
+pub const SLG_SCAN_MATCH_ALL: i32 = 0;
+pub const SLG_SCAN_CONSTANT: i32 = 1;
+pub const SLG_SCAN_RANK_FEATURE: i32 = 2;
+pub const SLG_SCAN_MOD_NONE: i32 = 0;
+pub const SLG_SCAN_MOD_LOG: i32 = 1;
+pub const SLG_SCAN_MOD_LOG1P: i32 = 2;
+pub const SLG_SCAN_MOD_SQRT: i32 = 3;
+pub const SLG_SCAN_MOD_RECIPROCAL: i32 = 4;
+#[repr(C)] pub struct slg_scan_spec {
+    pub q_kind: *const i32, pub q_filter: *const i32, pub q_score: *const c_float, pub q_field: *const i32,
+    pub q_modifier: *const i32, pub q_missing: *const c_float, pub q_boost: *const c_float,
+}
 #[repr(C)] pub struct slg_filter_node {
     pub kind: i32, pub field: i32, pub filter_id: i32, pub arity: u32, pub lo_f: f64, pub hi_f: f64,
     pub lo_i: i64, pub hi_i: i64, pub ord_begin: u32, pub n_ords_in: u32,
@@ -408,6 +421,17 @@ extern "C" {
         sort: *const slg_sort_spec, spec: *const slg_fscore_spec, k: u32, strategy: c_int, out_doc: *mut u32,
         out_seg: *mut u32, out_score: *mut c_float, out_count: *mut u32, stats: *mut slg_stats,
         out_matched: *mut u64) -> c_int;
+    // scan batches (match_all, constant_score, rank_feature at the root): no query arrays; sort and aggs as in
+    // slg_batch_prepare_aggs, both may be null; run / fetch / matched counts / aggregation tables as for any batch.
+    // Bound, not routed: reader_gpu.patch.rs sends no request here yet
+    pub fn slg_batch_prepare_scan(index: *mut slg_index, nq: u32, spec: *const slg_scan_spec, q_filter: *const i32,
+        sort: *const slg_sort_spec, aggs: *const slg_agg_spec, k: u32) -> *mut slg_batch;
+    pub fn slg_batch_scan_info(batch: *const slg_batch, out_variant: *mut u32, out_slices: *mut u32,
+        out_slice_docs: *mut u32) -> c_int;
+    pub fn slg_search_batch_scan(index: *mut slg_index, nq: u32, spec: *const slg_scan_spec, q_filter: *const i32,
+        sort: *const slg_sort_spec, aggs: *const slg_agg_spec, k: u32, out_doc: *mut u32, out_seg: *mut u32,
+        out_score: *mut c_float, out_count: *mut u32, out_matched: *mut u64, counts: *mut u64,
+        stats: *mut slg_agg_stats, values: *mut u64) -> c_int;
     // field collapsing: slg_batch_prepare_plans, _sorted or _after plus the spec; the rows stay as they are, the
     // groups and inner hits of each query's rows come from slg_batch_fetch_collapse
     pub fn slg_batch_prepare_collapse(index: *mut slg_index, nq: u32, q_offsets: *const u32, q_term_ids: *const u32,

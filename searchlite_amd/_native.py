@@ -56,6 +56,8 @@ FSCORE_HAS_MAX_BOOST, FSCORE_HAS_MIN_SCORE = 1, 2
 MAX_SCRIPT_INSTRS, MAX_SCRIPT_DEPTH, MAX_SCRIPT_FIELDS = 64, 8, 8
 SCRIPT_PUSH_CONST, SCRIPT_PUSH_FIELD, SCRIPT_PUSH_SCORE, SCRIPT_ADD, SCRIPT_SUB, SCRIPT_MUL, SCRIPT_DIV, SCRIPT_NEG = range(8)
 SCRIPT_OUTER, SCRIPT_INNER = 0, 1
+SCAN_MATCH_ALL, SCAN_CONSTANT, SCAN_RANK_FEATURE = 0, 1, 2
+SCAN_MOD_NONE, SCAN_MOD_LOG, SCAN_MOD_LOG1P, SCAN_MOD_SQRT, SCAN_MOD_RECIPROCAL = 0, 1, 2, 3, 4
 FILTER_KEYWORD_IN, FILTER_RANGE_F64, FILTER_RANGE_I64, FILTER_ID, FILTER_AND, FILTER_OR, FILTER_NOT = 0, 1, 2, 3, 4, 5, 6
 MAX_FILTER_NODES, MAX_FILTER_DEPTH, MAX_FILTER_TREES = 64, 16, 64
 MAX_COLLAPSE_ROWS = 4096
@@ -201,6 +203,13 @@ class ScriptSpec(C.Structure):
     order, their constants, and boost per query)."""
     _fields_ = [("p_offsets", C.c_void_p), ("i_op", C.c_void_p), ("i_arg", C.c_void_p), ("consts", C.c_void_p),
                 ("n_consts", C.c_uint32), ("q_boost", C.c_void_p)]
+
+
+class ScanSpec(C.Structure):
+    """slg_scan_spec: the unscored root node of every query of a scan batch (match_all, constant_score,
+    rank_feature): kind, the node's own filter, and the arguments of its kind, per query."""
+    _fields_ = [("q_kind", C.c_void_p), ("q_filter", C.c_void_p), ("q_score", C.c_void_p), ("q_field", C.c_void_p),
+                ("q_modifier", C.c_void_p), ("q_missing", C.c_void_p), ("q_boost", C.c_void_p)]
 
 
 class CollapseSpec(C.Structure):
@@ -391,6 +400,9 @@ def load():
         "slg_index_add_filter_trees": (i32, [vp, vp, u32, vp]),
         "slg_index_fetch_filter": (i32, [vp, i32, u32, vp]),
         "slg_search_batch_fscore": (i32, [vp, u32, vp, vp, vp, vp, vp, vp, vp, u32, i32, vp, vp, vp, vp, vp, vp]),
+        "slg_batch_prepare_scan": (vp, [vp, u32, vp, vp, vp, vp, u32]),
+        "slg_batch_scan_info": (i32, [vp, vp, vp, vp]),
+        "slg_search_batch_scan": (i32, [vp, u32, vp, vp, vp, vp, u32, vp, vp, vp, vp, vp, vp, vp, vp]),
         "slg_batch_prepare_collapse": (vp, [vp, u32, vp, vp, vp, vp, vp, vp, vp, vp, u32, i32]),
         "slg_batch_fetch_collapse": (i32, [vp] * 15),
         "slg_search_batch_collapse": (i32, [vp, u32, vp, vp, vp, vp, vp, vp, vp, vp, u32, i32] + [vp] * 18),

@@ -459,8 +459,11 @@ int slg_batch_run(slg_batch *b) {
     hipStream_t st = batch_stream(b);
     b->launched = true;
     if (b->nq == 0) return;
-    if (b->n_slices == 0) SLG_HIP(hipMemsetAsync(b->d_q_scored.p, 0, (size_t)b->nq * 4, st));
-    if (b->n_slices > 0) {
+    if (b->scan) {
+      scan_launch(b, st);  // (no scored term: the candidates come from a scan over the segments' docs)
+    } else if (b->n_slices == 0) {
+      SLG_HIP(hipMemsetAsync(b->d_q_scored.p, 0, (size_t)b->nq * 4, st));
+    } else {
       slg::RoundPartParams pp{};
       pp.sq = b->d_sq;
       pp.terms = b->d_terms;
@@ -565,14 +568,16 @@ int slg_batch_run(slg_batch *b) {
         hipLaunchKernelGGL(slg::select_topk_kernel<false>, dim3(b->nq), dim3(slg::kSelectThreads), 0, st, sp);
       }
       SLG_HIP(hipGetLastError());
-    } else if (b->k > 0) {
+    } else if (b->k > 0 && !b->scan) {
+      // (a scan batch comes here only without a slice — no segment has a doc — and has no per-slice top-k lists to
+      //  merge: scan_launch zeroed its rows, the counts follow below)
       slg::MergeParams mp{};
       fill_final(mp, b);
       mp.slice_tk = b->d_slice_tk.as<int32_t>();
       mp.slice_doc = b->d_slice_doc.as<uint32_t>();
       launch_merge(mp, st);
     } else {
-      SLG_HIP(hipMemsetAsync(b->d_out_count, 0, ((size_t)b->nq + 1) * 4, st));  // (k = 0: nothing was scored)
+      SLG_HIP(hipMemsetAsync(b->d_out_count, 0, ((size_t)b->nq + 1) * 4, st));  // (k = 0, or a scan without a slice: no row)
     }
     if (b->aggs) agg_launch(b, st);  // (after the select: the tables of every accepted candidate)
     if (b->rescore) rescore_launch(b, st);  // (behind the rows: the first w of every query are scored again)
@@ -818,8 +823,8 @@ int slg_batch_matched_counts(slg_batch *b, uint64_t *out_matched) {
   return guarded([&] {
     SLG_REQUIRE_LIVE(b);
     if (b->hybrid) throw SlgError(SLG_ERR_UNSUPPORTED, "a hybrid batch has no matched counts");
-    SLG_REQUIRE(b->sorted || b->after || b->aggs,
-                "not a sorted, cursor or aggregation batch (slg_batch_prepare_sorted / _after / _aggs)");
+    SLG_REQUIRE(b->sorted || b->after || b->aggs || b->scan,
+                "not a sorted, cursor, aggregation or scan batch (slg_batch_prepare_sorted / _after / _aggs / _scan)");
     SLG_REQUIRE(b->launched, "the batch has not run");
     SLG_REQUIRE(b->nq == 0 || out_matched != nullptr, "out_matched is NULL");
     DeviceGuard g(b->idx->device);

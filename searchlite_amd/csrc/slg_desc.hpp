@@ -357,6 +357,38 @@ constexpr uint32_t kFilterMaxNodes = 64, kFilterMaxDepth = 16, kFilterMaxTrees =
 constexpr uint32_t kFilterKeywordIn = 0, kFilterRangeF64 = 1, kFilterRangeI64 = 2, kFilterId = 3, kFilterAnd = 4,
                    kFilterOr = 5, kFilterNot = 6;
 
+// ---- scan batches (slg_batch_prepare_scan; kernel: slg_scan.hpp, planner: slg_plan.cpp) --------------
+// A query without a scored term has no posting list: its candidates are the docs of every segment that pass the
+// bitmaps.  A (query, segment) pair is cut into slices of kScanSliceDocs consecutive docs — a multiple of 2048, so
+// that a slice starts at a bitmap word and a wave's step of 64 words never straddles two slices.  A slice's region
+// of the candidate buffer starts at slice_cbeg[s] and holds `cap` entries: the slice's doc count (full form), or
+// min(doc count, k) (truncated form: every score of the query is equal, no sort, no aggregation — the first k
+// passing docs of a slice are the only ones the select can take from it; the rest are counted, not stored).
+#ifndef SLG_SCAN_SLICE_DOCS
+#define SLG_SCAN_SLICE_DOCS 16384
+#endif
+constexpr uint32_t kScanSliceDocs = SLG_SCAN_SLICE_DOCS;
+static_assert(kScanSliceDocs % 2048 == 0 && kScanSliceDocs != 0, "64 lanes x one bitmap word");
+constexpr uint32_t kScanMatchAll = 0, kScanConstant = 1, kScanRankFeature = 2;  // = SLG_SCAN_*
+constexpr uint32_t kScanModNone = 0, kScanModLog = 1, kScanModLog1p = 2, kScanModSqrt = 3, kScanModReciprocal = 4;
+struct ScanQuery {
+  uint32_t kind;      // SLG_SCAN_*
+  uint32_t modifier;  // SLG_SCAN_MOD_* (rank_feature)
+  uint32_t filter;    // the node's own filter: 0 none, f + 1 (a row of the state's reject table)
+  uint32_t col;       // rank_feature: the field's row of the batch's column table
+  float score;        // constant_score: boost * node_boost (match_all: 1.0)
+  float missing;      // rank_feature: the value of a doc without one
+  float boost;        // rank_feature
+  uint32_t pad;
+};
+struct ScanSlice {
+  uint32_t q, seg;
+  uint32_t first_doc;  // a multiple of kScanSliceDocs
+  uint32_t n_docs;     // 1 .. kScanSliceDocs
+  uint32_t cap;        // entries of the slice's region (n_docs, or min(n_docs, k) in the truncated form)
+  uint32_t pad[3];
+};
+
 // ---- merge of per-shard results gathered over RCCL (merge_shards_kernel, slg_kernels.hpp) ----------
 struct ShardMergeParams {
   const uint32_t *doc;    // shard sh's rows start at doc + sh * arr_stride ([nq*k] each)

@@ -1,5 +1,5 @@
 // slg_host.hpp — what the host translation units of the C ABI share (slg_index.hip, slg_batch.hip,
-// slg_shard.hip, slg_rerank.hip, slg_vsearch.hip, slg_hybrid.hip, slg_aggs.hip, slg_rescore.hip, slg_bool.hip, slg_booltree.hip, slg_phrase.hip, slg_fscore.hip, slg_script.hip, slg_collapse.hip): the error plumbing, device memory, the host
+// slg_shard.hip, slg_rerank.hip, slg_vsearch.hip, slg_hybrid.hip, slg_aggs.hip, slg_rescore.hip, slg_bool.hip, slg_booltree.hip, slg_phrase.hip, slg_fscore.hip, slg_script.hip, slg_scan.hip, slg_collapse.hip): the error plumbing, device memory, the host
 // structures behind the opaque handles and the small helpers several entry points use.  Private: not
 // installed, not part of include/.  No kernel header is included here — each unit includes the one
 // whose kernels it launches (slg_stage.hpp, slg_kernels.hpp, slg_rerank.hpp, slg_vsearch.hpp, slg_hybrid.hpp; the shard
@@ -569,6 +569,12 @@ struct slg_batch {
   uint32_t script_max_depth = 0;  // the deepest stack of the batch's programs
   uint32_t script_instrs = 0;     // entries of the instruction table behind the ScriptQuery records
   DevBuf d_script_desc;           // slg::ScriptQuery[nq], ScriptInstr[script_instrs], ColumnDev[fields][n_segs]
+  // scan batch (slg_batch_prepare_scan): no scored term, so no sub-queries, terms or rounds; scan_kernel fills the
+  // candidate regions in the place of the partition and scoring kernels and counts d_q_scored and d_matched
+  // (slg_scan.hip).  d_desc holds slg::ScanSlice[n_slices], ScanQuery[nq], ColumnDev[fields][n_segs], then the
+  // query and slice-segment tables every batch has
+  bool scan = false;
+  bool scan_full = false;  // some query needs ln / log1p: the full instantiation
   // collapse batch (slg_batch_prepare_collapse): a plain, sorted or cursor batch; collapse_kernel runs behind its
   // last kernel and fills the side arrays from each query's rows, which it leaves as they are (slg_collapse.hip)
   bool collapse = false;
@@ -816,6 +822,8 @@ void fscore_launch(slg_batch *b, hipStream_t st);
 // slg_script.hip: the same for the script stage of a script batch
 void script_attach(slg_batch *b, const slgplan::ScriptPlan &sp, bool first);
 void script_launch(slg_batch *b, hipStream_t st);
+// slg_scan.hip: the launch of a scan batch's candidate source, in the place of the partition and scoring kernels
+void scan_launch(slg_batch *b, hipStream_t st);
 // slg_collapse.hip: the spec against the batch's state (its keyword column, the inner sort's columns), the tables
 // and side arrays onto the device (throws; the batch is otherwise prepared); the launch behind the batch's rows
 void collapse_attach(slg_batch *b, const slg_collapse_spec &spec, const slg_sort_spec *batch_sort);

@@ -1420,6 +1420,114 @@ void plan_fscore(const std::vector<FscoreFieldView> &fields, const uint32_t *con
   fill_tables(fields, used_fields, reject, used_filters, n_segs, out.cols, out.filters);
 }
 
+// ---- scan batches ------------------------------------------------------------------------------------------
+static_assert(slg::kScanMatchAll == SLG_SCAN_MATCH_ALL && slg::kScanConstant == SLG_SCAN_CONSTANT &&
+                  slg::kScanRankFeature == SLG_SCAN_RANK_FEATURE, "header kinds");
+static_assert(slg::kScanModNone == SLG_SCAN_MOD_NONE && slg::kScanModLog == SLG_SCAN_MOD_LOG &&
+                  slg::kScanModLog1p == SLG_SCAN_MOD_LOG1P && slg::kScanModSqrt == SLG_SCAN_MOD_SQRT &&
+                  slg::kScanModReciprocal == SLG_SCAN_MOD_RECIPROCAL, "header modifiers");
+static_assert(sizeof(slg::ScanQuery) == 32 && sizeof(slg::ScanSlice) == 32, "records the kernel reads in whole words");
+
+void check_scan(const slg_scan_spec *spec, uint32_t nq, uint32_t k) {
+  PLAN_REQUIRE(spec != nullptr, "scan spec is NULL");
+  if (nq != 0) {
+    PLAN_REQUIRE(spec->q_kind != nullptr, "scan q_kind is NULL");
+    PLAN_REQUIRE(spec->q_filter != nullptr, "scan q_filter is NULL");
+    PLAN_REQUIRE(spec->q_score != nullptr, "scan q_score is NULL");
+    PLAN_REQUIRE(spec->q_field && spec->q_modifier && spec->q_missing && spec->q_boost,
+                 "scan q_field/q_modifier/q_missing/q_boost is NULL");
+  }
+  for (uint32_t q = 0; q < nq; q++) {
+    const std::string in_q = " in scan query " + std::to_string(q);
+    const int32_t kind = spec->q_kind[q];
+    PLAN_REQUIRE(kind >= SLG_SCAN_MATCH_ALL && kind <= SLG_SCAN_RANK_FEATURE, "unknown scan kind" + in_q);
+    PLAN_REQUIRE(spec->q_filter[q] >= -1, "negative filter id other than -1" + in_q);
+    if (kind == SLG_SCAN_CONSTANT) PLAN_REQUIRE(std::isfinite(spec->q_score[q]), "non-finite score" + in_q);
+    if (kind == SLG_SCAN_RANK_FEATURE) {
+      const int32_t m = spec->q_modifier[q];
+      PLAN_REQUIRE(m >= SLG_SCAN_MOD_NONE && m <= SLG_SCAN_MOD_RECIPROCAL, "unknown modifier" + in_q);
+      PLAN_REQUIRE(std::isfinite(spec->q_missing[q]), "non-finite missing" + in_q);
+      PLAN_REQUIRE(std::isfinite(spec->q_boost[q]), "non-finite boost" + in_q);
+    }
+  }
+  if (k > SLG_MAX_K) throw SlgError(SLG_ERR_UNSUPPORTED, "k > SLG_MAX_K");
+}
+
+void plan_scan(const std::vector<uint32_t> &seg_docs, const std::vector<FscoreFieldView> &fields,
+               const char *filter_live, size_t n_filters, uint32_t nq, const slg_scan_spec &spec,
+               const int32_t *q_filter, bool full_regions, uint32_t k, ScanPlan &out) {
+  out = ScanPlan{};
+  const uint32_t n_segs = (uint32_t)seg_docs.size();
+  out.queries.assign(nq, slg::ScanQuery{});
+  out.qrefs.assign(nq, slg::QueryRef{0, 0});
+  std::vector<int32_t> used_fields;  // the rows of the column table, in order of first use
+  std::string unsupported;           // (reported behind every invalid argument)
+  bool any_root = false;
+  for (uint32_t q = 0; q < nq; q++) {
+    const std::string in_q = " in scan query " + std::to_string(q);
+    slg::ScanQuery &sq = out.queries[q];
+    sq.kind = (uint32_t)spec.q_kind[q];
+    sq.score = 1.0f;
+    if (q_filter && q_filter[q] != -1) {
+      PLAN_REQUIRE(q_filter[q] >= 0 && (size_t)q_filter[q] < n_filters && filter_live[q_filter[q]],
+                   "unknown filter id " + std::to_string(q_filter[q]) + " in q_filter of query " + std::to_string(q));
+      any_root = true;
+    }
+    if (spec.q_filter[q] >= 0) {
+      PLAN_REQUIRE((size_t)spec.q_filter[q] < n_filters && filter_live[spec.q_filter[q]],
+                   "unknown filter id " + std::to_string(spec.q_filter[q]) + in_q);
+      sq.filter = (uint32_t)spec.q_filter[q] + 1u;
+    }
+    if (sq.kind == slg::kScanConstant) sq.score = spec.q_score[q];
+    if (sq.kind == slg::kScanRankFeature) {
+      const int32_t id = spec.q_field[q];
+      const FscoreFieldView &fv = agg_field(fields, id, "", in_q);
+      PLAN_REQUIRE(!fv.keyword, "agg field " + std::to_string(id) + " is a keyword field" + in_q);
+      agg_field_rows(fv, n_segs, "", in_q);
+      if (fv.non_finite && unsupported.empty())
+        unsupported = "agg field " + std::to_string(id) + " holds a non-finite value (CPU path)" + in_q;
+      sq.col = row_of(used_fields, id);
+      sq.modifier = (uint32_t)spec.q_modifier[q];
+      sq.missing = spec.q_missing[q];
+      sq.boost = spec.q_boost[q];
+      out.full = out.full || sq.modifier == slg::kScanModLog || sq.modifier == slg::kScanModLog1p;
+    }
+  }
+  if (!unsupported.empty()) throw SlgError(SLG_ERR_UNSUPPORTED, unsupported);
+  for (const int32_t id : used_fields) {
+    const slg::ColumnDev *rows = agg_field_rows(agg_field(fields, id, "", ""), n_segs, "", "");
+    out.cols.insert(out.cols.end(), rows, rows + n_segs);
+  }
+  if (any_root) {
+    out.q_filter.assign(nq, 0u);
+    for (uint32_t q = 0; q < nq; q++)
+      if (q_filter[q] >= 0) out.q_filter[q] = (uint32_t)q_filter[q] + 1u;
+  }
+  // the slices: per query, per segment with docs, kScanSliceDocs docs each; the regions lie in slice order
+  uint64_t per_query = 0;
+  for (const uint32_t n : seg_docs) per_query += ((uint64_t)n + slg::kScanSliceDocs - 1) / slg::kScanSliceDocs;
+  if (per_query * nq > 0xFFFFFFF0ull) throw SlgError(SLG_ERR_UNSUPPORTED, "a scan batch of more than 2^32 slices");
+  out.slices.reserve((size_t)(per_query * nq));
+  for (uint32_t q = 0; q < nq; q++) {
+    const bool truncated = !full_regions && out.queries[q].kind != slg::kScanRankFeature;
+    out.qrefs[q].slice_begin = (uint32_t)out.slices.size();
+    for (uint32_t s = 0; s < n_segs; s++)
+      for (uint64_t first = 0; first < seg_docs[s]; first += slg::kScanSliceDocs) {
+        slg::ScanSlice sl{};
+        sl.q = q;
+        sl.seg = s;
+        sl.first_doc = (uint32_t)first;
+        sl.n_docs = (uint32_t)std::min<uint64_t>(slg::kScanSliceDocs, seg_docs[s] - first);
+        sl.cap = truncated ? std::min(sl.n_docs, k) : sl.n_docs;
+        out.slices.push_back(sl);
+        out.slice_seg.push_back(s);
+        out.slice_cbeg.push_back(out.cand_total);
+        out.cand_total += sl.cap;
+      }
+    out.qrefs[q].slice_end = (uint32_t)out.slices.size();
+  }
+}
+
 // ---- script_score ------------------------------------------------------------------------------------------
 static_assert(slg::kScriptMaxInstrs == SLG_MAX_SCRIPT_INSTRS && slg::kScriptMaxDepth == SLG_MAX_SCRIPT_DEPTH &&
                   slg::kScriptMaxFields == SLG_MAX_SCRIPT_FIELDS, "the kernel's limits and the ABI's");

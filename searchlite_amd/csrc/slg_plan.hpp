@@ -238,6 +238,33 @@ struct FscorePlan {
 void plan_fscore(const std::vector<FscoreFieldView> &fields, const uint32_t *const *reject, const char *filter_live,
                  size_t n_filters, uint32_t n_segs, uint32_t nq, const slg_fscore_spec &spec, FscorePlan &out);
 
+// ---- scan batches (slg_batch_prepare_scan) ----
+// The checks of a spec that need no index (throws SlgError).  SLG_ERR_INVALID: a NULL spec or array, an unknown kind
+// or modifier, a node filter id below -1, a non-finite q_score of a CONSTANT query, a non-finite q_missing or q_boost
+// of a RANK_FEATURE query.  SLG_ERR_UNSUPPORTED, behind those: k > SLG_MAX_K.
+void check_scan(const slg_scan_spec *spec, uint32_t nq, uint32_t k);
+// The slice tables of a checked spec against an index state's segments, fields and filters: what the selects and
+// the aggregation kernels read of any batch (qrefs, slice_seg, the regions' bases in slice_cbeg, cand_total) and
+// what scan_kernel reads (queries, slices, cols).  seg_docs: the doc count of every segment; q_filter: the batch's
+// root filters or nullptr; full_regions: the batch has a sort spec or aggregations (no query is truncated).
+// Throws SLG_ERR_INVALID for an unknown or incomplete filter id (root or node), an unknown field id, a keyword
+// column, a field without a column for a segment; SLG_ERR_UNSUPPORTED, behind those, for a column that holds a
+// non-finite value.
+struct ScanPlan {
+  std::vector<slg::ScanQuery> queries;   // [nq]
+  std::vector<slg::ScanSlice> slices;    // per query, per segment with docs, ascending first_doc
+  std::vector<slg::QueryRef> qrefs;      // [nq]
+  std::vector<uint32_t> slice_seg;       // [slices]
+  std::vector<uint64_t> slice_cbeg;      // [slices] first entry of the slice's region
+  std::vector<slg::ColumnDev> cols;      // [fields the batch names][n_segs]
+  std::vector<uint32_t> q_filter;        // [nq] 0 = none, f + 1 (empty when no query has a root filter)
+  uint64_t cand_total = 0;               // entries of all regions
+  bool full = false;                     // some query needs ln / log1p: the full instantiation
+};
+void plan_scan(const std::vector<uint32_t> &seg_docs, const std::vector<FscoreFieldView> &fields,
+               const char *filter_live, size_t n_filters, uint32_t nq, const slg_scan_spec &spec,
+               const int32_t *q_filter, bool full_regions, uint32_t k, ScanPlan &out);
+
 // ---- script_score (slg_batch_prepare_script) ----
 // The checks of a spec that need no index (throws SlgError), in ONE walk over each program, which also records the
 // static stack positions (ScriptShape).  SLG_ERR_INVALID, reported first: a NULL spec or array, offsets that

@@ -381,6 +381,62 @@ int slgp_plan_fscore(const slgp_fscore_field *fields, uint32_t n_fields, const c
   }
 }
 
+// the host side of slg_batch_prepare_scan: check_scan, then plan_scan against segments of seg_docs[s] docs and
+// registered fields and filters that exist as descriptions only (slgp_fscore_field, the made-up addresses of
+// slgp_plan_fscore).  full_regions: the batch has a sort spec or aggregations.  queries: nq x 8 words
+// (slg::ScanQuery); qrefs: nq x 2 words; slices: entries of 8 words (slg::ScanSlice: q, seg, first_doc, n_docs, cap,
+// pad); cbeg: the regions' first entries; cols: entries of two addresses (offsets, values); root: nq words (0 = none,
+// f + 1; zeros when no query has a root filter).  slices, cbeg and cols are filled when they fit their cap; counts:
+// entries of slices and cols, 1 for the full kernel, then cand_total's low and high word.  0, or a negative error
+// code (err filled).  slgp_scan_slice_docs: the docs per slice the planner cuts at
+uint32_t slgp_scan_slice_docs(void) { return slg::kScanSliceDocs; }
+int slgp_plan_scan(const uint32_t *seg_docs, uint32_t n_segs, const slgp_fscore_field *fields, uint32_t n_fields,
+                   const char *filter_live, uint32_t n_filters, uint32_t nq, const slg_scan_spec *spec,
+                   const int32_t *q_filter, uint32_t full_regions, uint32_t k, uint32_t *queries, uint32_t *qrefs,
+                   uint32_t *slices, uint64_t *cbeg, uint32_t slices_cap, uint64_t *cols, uint32_t cols_cap,
+                   uint32_t *root, uint32_t *counts, char *err, uint32_t err_len) {
+  try {
+    slgplan::check_scan(spec, nq, k);
+    if (n_segs && !seg_docs) throw slgplan::SlgError(SLG_ERR_INVALID, "seg_docs is NULL");
+    std::vector<slgplan::FscoreFieldView> views(n_fields);
+    for (uint32_t i = 0; i < n_fields; i++) {
+      views[i] = described_field(fields[i], n_segs);
+      views[i].non_finite = fields[i].non_finite != 0;
+    }
+    slgplan::ScanPlan sp;
+    slgplan::plan_scan(std::vector<uint32_t>(seg_docs, seg_docs + n_segs), views, filter_live, n_filters, nq, *spec,
+                       q_filter, full_regions != 0, k, sp);
+    static_assert(sizeof(slg::ScanQuery) == 32 && sizeof(slg::ScanSlice) == 32 && sizeof(slg::QueryRef) == 8,
+                  "the words the caller reads");
+    if (queries && nq) std::memcpy(queries, sp.queries.data(), (size_t)nq * sizeof(slg::ScanQuery));
+    if (qrefs && nq) std::memcpy(qrefs, sp.qrefs.data(), (size_t)nq * sizeof(slg::QueryRef));
+    if (sp.slices.size() <= slices_cap && !sp.slices.empty()) {
+      if (slices) std::memcpy(slices, sp.slices.data(), sp.slices.size() * sizeof(slg::ScanSlice));
+      if (cbeg) std::memcpy(cbeg, sp.slice_cbeg.data(), sp.slice_cbeg.size() * 8);
+    }
+    if (cols && sp.cols.size() <= cols_cap && !sp.cols.empty())
+      std::memcpy(cols, sp.cols.data(), sp.cols.size() * sizeof(slg::ColumnDev));
+    if (root && nq) {
+      std::memset(root, 0, (size_t)nq * 4);
+      if (!sp.q_filter.empty()) std::memcpy(root, sp.q_filter.data(), (size_t)nq * 4);
+    }
+    if (counts) {
+      counts[0] = (uint32_t)sp.slices.size();
+      counts[1] = (uint32_t)sp.cols.size();
+      counts[2] = sp.full ? 1u : 0u;
+      counts[3] = (uint32_t)sp.cand_total;
+      counts[4] = (uint32_t)(sp.cand_total >> 32);
+    }
+    return SLG_OK;
+  } catch (const slgplan::SlgError &e) {
+    if (err && err_len) {
+      std::strncpy(err, e.what(), err_len - 1);
+      err[err_len - 1] = 0;
+    }
+    return e.code;
+  }
+}
+
 // the host side of slg_batch_prepare_script: check_script_order and check_script, then plan_script against
 // registered fields that exist as descriptions only (slgp_fscore_field, the made-up addresses of slgp_plan_fscore).
 // queries: nq x 16 words (slg::ScriptQuery); instrs: entries of 4 words (slg::ScriptInstr); cols: entries of two

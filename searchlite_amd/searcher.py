@@ -544,6 +544,24 @@ class GpuIndex:
         finally:
             b.close()
 
+    def prepare_scan(self, queries, k: int, sort=None, aggs=None, q_filter=None) -> "ScanBatch":
+        """A batch of unscored root queries (slg_batch_prepare_scan).  queries: one dictionary per query, as
+        scan.scan_spec takes them (match_all, constant_score, rank_feature), or its (spec, keep) pair; sort: None =
+        score order, else as search_sorted; aggs: an N.AggSpec or an aggs.AggPlan, or None; q_filter: the root
+        filter id per query, or None; k may be 0."""
+        return ScanBatch(self, queries, k, sort=sort, aggs=aggs, q_filter=q_filter)
+
+    def search_scan(self, queries, k: int, sort=None, aggs=None, q_filter=None, want_stats: bool = False):
+        """prepare_scan, one run and the results: -> (doc, seg, score, count[, stats], matched), and with aggs also
+        (tables, layout) as search_aggs returns them.  matched is total_matches, in every order and for k = 0."""
+        b = self.prepare_scan(queries, k, sort=sort, aggs=aggs, q_filter=q_filter)
+        try:
+            b.run()
+            out = b.fetch(want_stats) + (b.matched_counts(),)
+            return out + ((b.aggs(), b.agg_layout()) if aggs is not None else ())
+        finally:
+            b.close()
+
     def search_sorted(self, q_offsets, q_terms, q_weights, k: int, sort, strategy: int = Wand, q_filter=None,
                       **plans):
         """Field-sorted batch search (slg_batch_prepare_sorted).  sort: [(field, order)], field = a sort field id
@@ -1513,3 +1531,40 @@ class PreparedBatch:
         if want_stats:
             return out_doc, out_seg, out_score, out_count, stats
         return out_doc, out_seg, out_score, out_count
+
+
+class ScanBatch(PreparedBatch):
+    """A planned batch of unscored root queries — match_all, constant_score, rank_feature — whose candidates come
+    from a scan over the segments' docs (slg_batch_prepare_scan).  Everything behind prepare is PreparedBatch's:
+    run, fetch, matched_counts (every scan batch has them), agg_layout, aggs, device_results, set_stream, sync."""
+
+    def __init__(self, index: GpuIndex, queries, k: int, sort=None, aggs=None, q_filter=None):
+        from .scan import scan_spec
+        self.index = index
+        self._lib = index._lib
+        sspec, self._scan_keep = queries if isinstance(queries, tuple) else scan_spec(queries)
+        self.nq = len(self._scan_keep["q_kind"])
+        self.k = k
+        qf = None if q_filter is None else np.ascontiguousarray(q_filter, dtype=np.int32)
+        assert qf is None or len(qf) == self.nq
+        self.sorted = sort is not None
+        self.after = False
+        self.is_hybrid = False
+        self.is_scan = True
+        self.agg_spec = getattr(aggs, "spec", aggs)  # (an aggs.AggPlan carries its N.AggSpec)
+        spec = None if sort is None else sort_spec(sort)
+        self._h = self._lib.slg_batch_prepare_scan(
+            index._h, self.nq, C.addressof(sspec), _ptr(qf), None if spec is None else C.addressof(spec),
+            None if self.agg_spec is None else C.addressof(self.agg_spec), k)
+        if not self._h:
+            raise N.SlgError(N.last_error_code() or N.ERR_INVALID, N.last_error())
+        index._batches.add(self)
+
+    def info(self):
+        out = super().info()
+        variant, slices, docs = C.c_uint32(), C.c_uint32(), C.c_uint32()
+        N.check(self._lib.slg_batch_scan_info(self._h, C.addressof(variant), C.addressof(slices), C.addressof(docs)))
+        out["scan_kernel"] = (None, "lean", "full")[variant.value]  # None: the batch has no slice
+        out["n_slices"] = slices.value
+        out["scan_slice_docs"] = docs.value
+        return out

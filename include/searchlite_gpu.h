@@ -628,9 +628,11 @@ void slg_batch_destroy(slg_batch *batch);
  * slg_index_remove_segment drops that segment's, slg_index_add_segment gives the new segment none (a batch
  * that names the field then fails with SLG_ERR_INVALID until it is registered again); ids are never handed
  * out again.  Numeric columns hold f64 (an i64 field arrives as `v as f64`, index/fastfields.rs:772-800, the
- * conversion done here on the host); registration records the column's finite minimum and maximum and
- * whether it holds a non-finite value.  The reference's behaviour on NaN / +-inf is an accident of `as i64`
- * saturation and f64::min: a batch that names such a column fails with SLG_ERR_UNSUPPORTED (CPU path).
+ * conversion done here on the host); registration records, per segment, the finite minimum and maximum and
+ * whether it holds a non-finite value: the column's own are those of the segments it holds, so after
+ * slg_index_remove_segment a histogram's dense id range is what a fresh registration over the segments left
+ * gives.  The reference's behaviour on NaN / +-inf is an accident of `as i64` saturation and f64::min: a batch
+ * that names such a column fails with SLG_ERR_UNSUPPORTED (CPU path).
  * A keyword column holds u32 ordinals into ONE caller-owned dictionary of n_ords keys: the caller maps each
  * segment's own dictionary (index/fastfields.rs:711-734) to global ordinals; an ordinal >= n_ords is
  * SLG_ERR_INVALID.  Return the field id (>= 0) or a negative error code. */
@@ -1282,11 +1284,12 @@ int slg_search_batch_bool(slg_index *index, uint32_t nq, const uint32_t *q_offse
  * Leaves.  A TERM GROUP is one or more clause terms and HOLDS a doc of segment s iff one of its terms has a
  * posting of the doc in s (the bool batch's rule, term_group_matches); a term that is SLG_NO_TERM in a segment, or
  * has df 0 there, has no posting there.  A FILTER LEAF is a registered filter id (slg_index_add_filter*,
- * slg_index_add_filter_trees) and holds the doc iff the doc passes that filter in its segment; a filter with no
- * bitmap for a segment (one added after the filter was registered) passes every doc there.  A registered bitmap
- * carries its segment's tombstones, so a tombstoned doc passes no filter leaf: no row changes (tombstones apply
- * on top anyway), only slg_stats.scored_docs sees it.  A query's leaves are numbered term groups first, filter
- * leaves behind them.
+ * slg_index_add_filter_trees) and holds the doc iff the doc passes that filter in its segment; a segment
+ * given no mask when the filter was registered passes every live doc, and a filter that predates a segment
+ * (slg_index_add_segment) is refused here as it is in q_filter: SLG_ERR_INVALID, "unknown filter id", until it is
+ * registered again.  A registered bitmap carries its segment's tombstones, so a tombstoned doc passes no filter
+ * leaf: no row changes (tombstones apply on top anyway), only slg_stats.scored_docs sees it.  A query's leaves are
+ * numbered term groups first, filter leaves behind them.
  *
  * Nodes.  A node is a list of (child, kind) pairs, kind SLG_BOOL_MUST / _SHOULD / _MUST_NOT, and a min_should.
  * Its value is

@@ -351,6 +351,10 @@ struct SortFieldData {
 struct AggColumn {
   DevBuf offs, vals;   // offs empty: every doc of the segment has exactly one value (vals[doc])
   size_t n_vals = 0;   // values in vals
+  // what registration saw in this segment's values (numeric columns); the field's own facts are these folded over
+  // the segments it holds (AggFieldData::refold), so that they follow slg_index_remove_segment
+  bool any_value = false, non_finite = false, i64_rounded = false;
+  double vmin = 0.0, vmax = 0.0;
 };
 // the value ranks of a numeric field (slg_index_rank_agg_field): the dictionary of its distinct values, shared by
 // the states that hold the field
@@ -370,6 +374,21 @@ struct AggFieldData {
   // set by slg_index_rank_agg_field (numeric fields): the dictionary, and per segment u32[n_vals] beside vals
   std::shared_ptr<AggRankDict> dict;
   std::vector<std::shared_ptr<DevBuf>> ranks;  // [per_seg.size()]; null = no ranks for that segment
+  // any_value / vmin / vmax / non_finite / i64_rounded from the columns of the segments held now: what a
+  // registration over exactly these segments would have recorded
+  void refold() {
+    any_value = non_finite = i64_rounded = false;
+    vmin = vmax = 0.0;
+    for (const auto &c : per_seg) {
+      if (!c) continue;
+      non_finite = non_finite || c->non_finite;
+      i64_rounded = i64_rounded || c->i64_rounded;
+      if (!c->any_value) continue;
+      vmin = any_value ? std::min(vmin, c->vmin) : c->vmin;
+      vmax = any_value ? std::max(vmax, c->vmax) : c->vmax;
+      any_value = true;
+    }
+  }
 };
 
 // the positions of a segment's postings (slg_index_set_positions): shared by the states that hold them

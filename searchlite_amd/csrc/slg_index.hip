@@ -373,6 +373,7 @@ void reshape_per_segment(IndexState &ns, Op op) {
     auto nf = std::make_shared<AggFieldData>(*af.second);
     op(nf->per_seg);
     op(nf->ranks);
+    nf->refold();  // (a histogram's dense id range follows the minimum and maximum of the segments left)
     af.second = std::move(nf);
   }
   for (auto &vf : ns.vfields) op(vf->per_seg);  // (the field objects of a new state are fresh copies)
@@ -980,7 +981,7 @@ int add_agg_field_impl(slg_index *ix, int kind, const uint32_t *const *seg_offse
             constexpr int64_t i2p53 = (int64_t)1 << 53;
             for (size_t i = 0; i < nv; i++) {
               conv[i] = (double)iv[i];
-              fd->i64_rounded = fd->i64_rounded || iv[i] > i2p53 || iv[i] < -i2p53;
+              col->i64_rounded = col->i64_rounded || iv[i] > i2p53 || iv[i] < -i2p53;
             }
             v = conv.data();
           } else if (nv) {
@@ -988,12 +989,12 @@ int add_agg_field_impl(slg_index *ix, int kind, const uint32_t *const *seg_offse
           }
           for (size_t i = 0; i < nv; i++) {
             if (!std::isfinite(v[i])) {
-              fd->non_finite = true;
+              col->non_finite = true;
               continue;
             }
-            fd->vmin = fd->any_value ? std::min(fd->vmin, v[i]) : v[i];
-            fd->vmax = fd->any_value ? std::max(fd->vmax, v[i]) : v[i];
-            fd->any_value = true;
+            col->vmin = col->any_value ? std::min(col->vmin, v[i]) : v[i];
+            col->vmax = col->any_value ? std::max(col->vmax, v[i]) : v[i];
+            col->any_value = true;
           }
           col->vals.alloc(std::max<size_t>(nv, 1) * 8, &ix->pool);
           if (nv) SLG_HIP(hipMemcpy(col->vals.p, v, nv * 8, hipMemcpyHostToDevice));
@@ -1007,6 +1008,7 @@ int add_agg_field_impl(slg_index *ix, int kind, const uint32_t *const *seg_offse
         }
         fd->per_seg[s] = std::move(col);
       }
+      fd->refold();
       id = ix->next_agg_field++;
       ns.agg_fields.emplace(id, std::move(fd));
     });

@@ -647,7 +647,12 @@ void slg_batch_destroy(slg_batch *batch);
                                         coarse histogram, then its fine tables when they fit */
 #define SLG_MAX_AGG_RANKS (1u << 24) /* distinct values of a ranked column (slg_index_rank_agg_field) */
 enum { SLG_AGG_TERMS = 0, SLG_AGG_HISTOGRAM = 1, SLG_AGG_RANGE = 2, SLG_AGG_STATS = 3,
-       SLG_AGG_CARDINALITY = 4, SLG_AGG_PERCENTILES = 5, SLG_AGG_PERCENTILE_RANKS = 6 };
+       SLG_AGG_CARDINALITY = 4, SLG_AGG_PERCENTILES = 5, SLG_AGG_PERCENTILE_RANKS = 6,
+       /* (7 is not a kind) */
+       SLG_AGG_DATE_HISTOGRAM = 8, SLG_AGG_FILTER = 9 };
+/* slg_agg_node.calendar_unit */
+enum { SLG_DATE_FIXED = 0, SLG_DATE_DAY = 1, SLG_DATE_WEEK = 2, SLG_DATE_MONTH = 3, SLG_DATE_QUARTER = 4,
+       SLG_DATE_YEAR = 5 };
 int slg_index_add_agg_field_f64(slg_index *index, const uint32_t *const *seg_offsets,
                                 const double *const *seg_values);
 int slg_index_add_agg_field_i64(slg_index *index, const uint32_t *const *seg_offsets,
@@ -670,7 +675,7 @@ int slg_index_remove_agg_field(slg_index *index, int agg_field_id);
 int64_t slg_index_rank_agg_field(slg_index *index, int agg_field_id);
 
 /* One aggregation node.  A node is a root (parent == -1) or the child of an EARLIER bucket root (terms,
- * histogram or range); children have no children.  A child under a bucket collects the doc once per parent
+ * histogram, range, date_histogram or filter); children have no children.  A child under a bucket collects the doc once per parent
  * bucket the doc was counted in (aggs/mod.rs:905-908, 1026-1028, 1200-1202).
  *   SLG_AGG_TERMS      keyword column.  A doc counts once in every DISTINCT ordinal it holds (:898-909); a
  *                      doc without a value counts in row missing_ord if has_missing (:914-929).  missing_ord
@@ -686,6 +691,27 @@ int64_t slg_index_rank_agg_field(slg_index *index, int agg_field_id);
  *   SLG_AGG_STATS      numeric column: count, min, max, sum over EVERY value of every collected doc (:1426-1441);
  *                      `missing` as above.  value_count, min, max, sum and avg follow on the host; extended_stats
  *                      (m2) is not built.
+ *   SLG_AGG_DATE_HISTOGRAM numeric column; a bucket root like the three above (root, or child of a bucket root;
+ *                      parent of every kind that can be a child).  The doc's values (`missing` as above) are
+ *                      taken `as i64`, which truncates an f64 toward zero (-0.5 -> 0, -1.5 -> -1) (:1320-1328);
+ *                      with has_hard_bounds a value with val < date_hard_min || val > date_hard_max (i64, both
+ *                      ends inclusive) is skipped (:1334-1338); a doc counts once per DISTINCT bucket and its
+ *                      children collect once per bucket it was counted in (:1343-1360).  All times are i64
+ *                      milliseconds.  calendar_unit SLG_DATE_FIXED: id = ceil((val - date_offset) as f64 /
+ *                      date_step as f64), ONE IEEE f64 division, then ceil (bucket_start, :3391-3396) — ceil, not
+ *                      floor: a value on a boundary is its own bucket, any other goes to the NEXT boundary; key =
+ *                      id * date_step + date_offset.  SLG_DATE_DAY .. _YEAR: t = val - date_offset lies in a UTC
+ *                      proleptic-Gregorian day / ISO week (from Monday) / month / quarter / year
+ *                      (truncate_calendar, :3410-3429); id = the unit's index since 1970 with floor semantics
+ *                      (t = -1 is 1969-12-31): day floor(t / 86 400 000), week floor((day + 3) / 7), month
+ *                      (y - 1970) * 12 + (m - 1), quarter floor(month / 3), year y - 1970; key = the unit's start
+ *                      in ms + date_offset.  date_step is read for SLG_DATE_FIXED only.  The ids are dense: row i
+ *                      of the table is id first_id + i.
+ *   SLG_AGG_FILTER     no column (field is not read): ONE bucket that counts every collected doc whose bit in the
+ *                      reject bitmap of the registered filter `filter` is clear (FilterCollector::collect,
+ *                      :1664-1674; a filter without a bitmap for a segment rejects nothing there); a bucket root
+ *                      like date_histogram: its children collect the docs that pass.  Any registered filter id
+ *                      serves: bitmaps, ranges, term filters and filter trees alike.
  * Value nodes: order and identity questions over the values of the collected docs, answered from the value ranks
  * of the column (slg_index_rank_agg_field) into a table of 8-byte cells (slg_batch_fetch_agg_values):
  *   SLG_AGG_CARDINALITY      keyword or RANKED numeric column: the number of distinct values over every value of
@@ -730,6 +756,11 @@ typedef struct {
   double interval, offset, hard_min, hard_max;
   uint32_t n_ranges;        /* SLG_AGG_RANGE; the percents / targets of SLG_AGG_PERCENTILES / _PERCENTILE_RANKS */
   double from[SLG_MAX_AGG_RANGES], to[SLG_MAX_AGG_RANGES]; /* (percents and targets: from[]) */
+  uint32_t calendar_unit;   /* SLG_AGG_DATE_HISTOGRAM: SLG_DATE_* */
+  int32_t filter;           /* SLG_AGG_FILTER: a registered filter id */
+  /* SLG_AGG_DATE_HISTOGRAM, i64 milliseconds (`missing` stays the f64 member above: the reference hands it to
+   * numeric_values as an f64 and takes it `as i64` again; has_hard_bounds says whether the two bounds are read) */
+  int64_t date_step, date_offset, date_hard_min, date_hard_max;
 } slg_agg_node;
 typedef struct {
   uint32_t n_nodes; /* 1 .. SLG_MAX_AGGS */
@@ -738,12 +769,13 @@ typedef struct {
 /* A node's table is parent_rows x rows, parent-major (parent_rows = 1 for a root, else the parent's rows).
  * rows: terms n_ords (+ 1 when missing_ord == n_ords); histogram the dense id range that the column's finite
  * minimum and maximum, `missing` and the hard bounds allow (the bucket formula is monotone), row i = id
- * first_id + i; range n_ranges; stats 1; cardinality 1; percentile_ranks 1 + n_ranges; percentiles
+ * first_id + i; date_histogram the same over its ids (an empty range: one row that is never counted); filter 1;
+ * range n_ranges; stats 1; cardinality 1; percentile_ranks 1 + n_ranges; percentiles
  * 1 + 2 * n_ranges.  offset: the table's first cell in the query's count table (bucket kinds), stats table
  * (is_stats == 1) or value table (is_stats == 2). */
 typedef struct {
   uint32_t parent_rows, rows;
-  int64_t first_id; /* histogram: the id of row 0; else 0 */
+  int64_t first_id; /* histogram, date_histogram: the id of row 0; else 0 */
   uint32_t is_stats; /* 0 count table, 1 stats table, 2 value table */
   uint64_t offset;
 } slg_agg_layout;
@@ -757,9 +789,15 @@ typedef struct {
  * index: aggs NULL, n_nodes == 0, an unknown kind, a parent that is not an earlier bucket root, a
  * non-positive or non-finite interval, a non-finite offset / missing, a NaN bound, percent or target,
  * n_ranges == 0 (range, percentiles, percentile_ranks): SLG_ERR_INVALID; n_nodes > SLG_MAX_AGGS, n_ranges >
- * SLG_MAX_AGG_RANGES or a percentiles node with a parent: SLG_ERR_UNSUPPORTED.  Against
- * the index: an unknown field id, a field without a column for every segment, a field of the wrong kind
- * for its node, missing_ord > n_ords, a numeric field without ranks under a cardinality or percentiles node
+ * SLG_MAX_AGG_RANGES or a percentiles node with a parent: SLG_ERR_UNSUPPORTED.  A date_histogram node:
+ * calendar_unit > SLG_DATE_YEAR or a fixed date_step < 1: SLG_ERR_INVALID; |date_offset|, |missing| or a hard bound
+ * beyond 2^53: SLG_ERR_UNSUPPORTED.  A filter node with filter < 0: SLG_ERR_INVALID.  Against
+ * the index: a date_histogram node on a keyword column, or a filter id that is not registered in the batch's index
+ * state (never registered, or removed): SLG_ERR_INVALID; a date_histogram column that holds a value beyond +-2^53, or,
+ * under a calendar unit, a collectable val - date_offset outside 0001-01-01T00:00:00Z .. 9999-12-31T23:59:59.999Z
+ * (-62 135 596 800 000 .. 253 402 300 799 999 ms): SLG_ERR_UNSUPPORTED (CPU path; within these limits `as i64`,
+ * `as f64` and val - offset are exact and cannot overflow).  For every kind: an unknown field id, a field
+ * without a column for every segment, a field of the wrong kind for its node, missing_ord > n_ords, a numeric field without ranks under a cardinality or percentiles node
  * (slg_index_rank_agg_field): SLG_ERR_INVALID; a numeric column with a non-finite value, more than
  * SLG_MAX_AGG_CELLS cells per query (value cells count too), or more than SLG_MAX_AGG_SCRATCH_WORDS words of
  * value-node scratch per query (parent_rows x ceil(ranks / 32) per cardinality node, plus the fine tables of a

@@ -65,12 +65,23 @@ pub const SLG_AGG_STATS: i32 = 3;
 pub const SLG_AGG_CARDINALITY: i32 = 4;
 pub const SLG_AGG_PERCENTILES: i32 = 5;
 pub const SLG_AGG_PERCENTILE_RANKS: i32 = 6;
+pub const SLG_AGG_DATE_HISTOGRAM: i32 = 8; // (7 is not a kind)
+pub const SLG_AGG_FILTER: i32 = 9;
+pub const SLG_DATE_FIXED: u32 = 0;
+pub const SLG_DATE_DAY: u32 = 1;
+pub const SLG_DATE_WEEK: u32 = 2;
+pub const SLG_DATE_MONTH: u32 = 3;
+pub const SLG_DATE_QUARTER: u32 = 4;
+pub const SLG_DATE_YEAR: u32 = 5;
 pub const SLG_MAX_AGG_SCRATCH_WORDS: u32 = 1 << 19;
 pub const SLG_MAX_AGG_RANKS: u32 = 1 << 24;
 #[repr(C)] #[derive(Clone, Copy)] pub struct slg_agg_node {
     pub kind: i32, pub field: i32, pub parent: i32, pub has_missing: u32, pub missing: f64, pub missing_ord: u32,
     pub has_hard_bounds: u32, pub interval: f64, pub offset: f64, pub hard_min: f64, pub hard_max: f64,
     pub n_ranges: u32, pub from: [f64; SLG_MAX_AGG_RANGES], pub to: [f64; SLG_MAX_AGG_RANGES],
+    // date_histogram: SLG_DATE_* and i64 milliseconds; filter: a registered filter id
+    pub calendar_unit: u32, pub filter: i32,
+    pub date_step: i64, pub date_offset: i64, pub date_hard_min: i64, pub date_hard_max: i64,
 }
 #[repr(C)] #[derive(Clone, Copy)] pub struct slg_agg_spec { pub n_nodes: u32, pub nodes: [slg_agg_node; SLG_MAX_AGGS] }
 #[repr(C)] #[derive(Clone, Copy, Default)] pub struct slg_agg_layout {

@@ -760,9 +760,14 @@ pub(crate) fn gpu_eligible(
   // Aggregations run on the device (slg_batch_prepare_aggs) when the tree fits what is built there: terms,
   // histogram, range, stats, cardinality, percentiles (root only) and percentile_ranks over registered columns, a
   // root or the child of a bucket root (two levels), at
-  // most ffi::SLG_MAX_AGGS nodes, no `sampling`; anything else (significant_terms, rare_terms, date_*,
-  // composite, filter, extended_stats, top_hits, pipeline aggregations as NODES — they are applied on
-  // the host to the shaped buckets —, deeper trees) keeps the request on the CPU collectors.  Not with a cursor:
+  // most ffi::SLG_MAX_AGGS nodes, no `sampling`.  The library also builds date_histogram (SLG_AGG_DATE_HISTOGRAM:
+  // fixed and calendar intervals in i64 ms, within +-2^53 and, for calendar units, years 1 .. 9999) and filter
+  // (SLG_AGG_FILTER: a node that names a REGISTERED filter id, so the filter must be compiled and registered at
+  // staging time, slg_index_add_filter_trees) as bucket roots or children, and date_range / value_count map onto
+  // range / stats nodes on the host (parse_date on the bounds; the stats count); aggs_fit_device above does not
+  // admit them yet.  Anything else (significant_terms, rare_terms, composite, extended_stats, top_hits, pipeline
+  // aggregations as NODES — they are applied on the host to the shaped buckets —, deeper trees) keeps the request
+  // on the CPU collectors.  Not with a cursor:
   // cursor batches take no aggregations.  The caller maps every segment's keyword dictionary
   // (index/fastfields.rs:711-734) to ONE dictionary per field at staging time (sorted union of the segments'
   // keys; a segment's local ordinal -> the global one) and registers the columns with

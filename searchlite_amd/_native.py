@@ -32,6 +32,8 @@ MAX_AGG_CELLS = 65536
 AGG_LDS_BYTES = 32768
 AGG_TERMS, AGG_HISTOGRAM, AGG_RANGE, AGG_STATS = 0, 1, 2, 3
 AGG_CARDINALITY, AGG_PERCENTILES, AGG_PERCENTILE_RANKS = 4, 5, 6
+AGG_DATE_HISTOGRAM, AGG_FILTER = 8, 9  # (7 is not a kind)
+DATE_FIXED, DATE_DAY, DATE_WEEK, DATE_MONTH, DATE_QUARTER, DATE_YEAR = 0, 1, 2, 3, 4, 5
 MAX_AGG_SCRATCH_WORDS = 1 << 19
 AGG_PCT_LDS_BYTES = 16384
 MAX_AGG_RANKS = 1 << 24
@@ -137,7 +139,11 @@ class AggNode(C.Structure):
     _fields_ = [("kind", C.c_int32), ("field", C.c_int32), ("parent", C.c_int32), ("has_missing", C.c_uint32),
                 ("missing", C.c_double), ("missing_ord", C.c_uint32), ("has_hard_bounds", C.c_uint32),
                 ("interval", C.c_double), ("offset", C.c_double), ("hard_min", C.c_double), ("hard_max", C.c_double),
-                ("n_ranges", C.c_uint32), ("from_", C.c_double * MAX_AGG_RANGES), ("to", C.c_double * MAX_AGG_RANGES)]
+                ("n_ranges", C.c_uint32), ("from_", C.c_double * MAX_AGG_RANGES), ("to", C.c_double * MAX_AGG_RANGES),
+                # date_histogram: DATE_* and i64 milliseconds (has_hard_bounds, has_missing / missing as above);
+                # filter: a registered filter id
+                ("calendar_unit", C.c_uint32), ("filter", C.c_int32), ("date_step", C.c_int64),
+                ("date_offset", C.c_int64), ("date_hard_min", C.c_int64), ("date_hard_max", C.c_int64)]
 
 
 class AggSpec(C.Structure):

@@ -9,14 +9,21 @@ with their key string or {"from", "to"}; stats with avg = sum / count (0.0 when 
 percentiles and percentile_ranks {"values": {key: f64}} keyed by the percent / target as Rust's `format!("{p}")`
 prints an f64 (:3245-3262), percentiles interpolated as QuantileState::percentile does (:529-537) — over ALL
 values: the device is exact at any n, where the reference switches to a t-digest estimate above 256 values.
+date_histogram keys are integers, bucket start + offset, ascending, `min_doc_count` (default 0), zero buckets walked
+from bucket_start(min) to bucket_start(max) of extended_bounds (or hard_bounds) with add_interval
+(DateHistogramCollector::finish, :1364-1403); filter {"doc_count", "aggregations"} (:2707-2726).  Two types are host
+mappings onto device kinds: date_range is a range node whose bounds and `missing` went through parse_date
+(DateRangeCollector, :1063-1122), value_count is the count of a stats node (ValueCountCollector, :1455-1476).
 
 A request is the reference's `aggs` map: name -> {"type": "terms" | "histogram" | "range" | "stats" | "cardinality"
-| "percentiles" | "percentile_ranks", "field": ..., ..., "aggs": {...children...}}.  Maps are walked in name order, as the reference's BTreeMaps.
+| "percentiles" | "percentile_ranks" | "date_histogram" | "date_range" | "filter" | "value_count", "field": ..., ...,
+"aggs": {...children...}}.  Maps are walked in name order, as the reference's BTreeMaps.
 """
 from __future__ import annotations
 
 import json
 import math
+import re
 from typing import Dict, List, Optional
 
 import numpy as np
@@ -24,8 +31,11 @@ import numpy as np
 from . import _native as N
 
 KINDS = {"terms": N.AGG_TERMS, "histogram": N.AGG_HISTOGRAM, "range": N.AGG_RANGE, "stats": N.AGG_STATS,
-         "cardinality": N.AGG_CARDINALITY, "percentiles": N.AGG_PERCENTILES, "percentile_ranks": N.AGG_PERCENTILE_RANKS}
-BUCKET_TYPES = ("terms", "histogram", "range")
+         "cardinality": N.AGG_CARDINALITY, "percentiles": N.AGG_PERCENTILES, "percentile_ranks": N.AGG_PERCENTILE_RANKS,
+         "date_histogram": N.AGG_DATE_HISTOGRAM, "filter": N.AGG_FILTER,
+         "date_range": N.AGG_RANGE, "value_count": N.AGG_STATS}  # (the last two: host mappings)
+BUCKET_TYPES = ("terms", "histogram", "range", "date_histogram", "date_range", "filter")
+FILTERS = "$filters"  # the entry of `fields` that maps a filter aggregation's `filter` body to a registered filter id
 DEFAULT_PERCENTS = [1.0, 5.0, 25.0, 50.0, 75.0, 95.0, 99.0]  # default_percentiles_list (:3376-3378)
 
 
@@ -65,12 +75,208 @@ def percentile_of(n: int, low_bits: int, high_bits: int, pct: float) -> float:
         return lo
     w = rank - float(low)
     return lo * (1.0 - w) + hi * w
+
+
+# ---- dates: parse_interval_seconds, parse_calendar_interval, parse_date, bucket_start, add_interval -------------
+I64_MIN, I64_MAX = -(1 << 63), (1 << 63) - 1
+DAY_MS = 86_400_000
+CALENDAR_UNITS = {"day": N.DATE_DAY, "1d": N.DATE_DAY, "week": N.DATE_WEEK, "1w": N.DATE_WEEK,
+                  "month": N.DATE_MONTH, "1m": N.DATE_MONTH, "quarter": N.DATE_QUARTER, "1q": N.DATE_QUARTER,
+                  "year": N.DATE_YEAR, "1y": N.DATE_YEAR}
+_INTERVAL_UNITS = {"": 1.0, "s": 1.0, "ms": 0.001, "m": 60.0, "h": 3600.0, "d": 86_400.0, "w": 604_800.0}
+_RUST_F64 = re.compile(r"[+-]?(?:(?:\d+\.?\d*|\.\d+)(?:[eE][+-]?\d+)?|(?i:inf|infinity|nan))\Z")
+_RFC3339 = re.compile(r"(\d{4})-(\d\d)-(\d\d)[Tt ](\d\d):(\d\d):(\d\d)(?:\.(\d+))?([Zz]|[+-]\d\d:\d\d)\Z")
+
+
+def rust_as_i64(x: float) -> int:
+    """`x as i64`: truncation toward zero, saturating, NaN -> 0"""
+    if math.isnan(x):
+        return 0
+    if math.isinf(x):
+        return I64_MAX if x > 0 else I64_MIN
+    return min(max(int(x), I64_MIN), I64_MAX)
+
+
+def rust_parse_f64(s: str) -> Optional[float]:
+    """`s.parse::<f64>().ok()`: no blanks, no underscores"""
+    return float(s) if isinstance(s, str) and _RUST_F64.match(s) else None
+
+
+def parse_interval_seconds(spec: str) -> Optional[float]:
+    """:3474-3498: a prefix of ASCII digits and dots, then "", s, ms, m, h, d or w"""
+    idx = 0
+    while idx < len(spec) and (spec[idx] in "0123456789."):
+        idx += 1
+    if idx == 0:
+        return None
+    value = rust_parse_f64(spec[:idx])
+    if value is None or spec[idx:] not in _INTERVAL_UNITS:
+        return None
+    return value * _INTERVAL_UNITS[spec[idx:]]
+
+
+def parse_calendar_interval(spec: str) -> Optional[int]:
+    """:3380-3389 -> DATE_DAY .. DATE_YEAR ("1m" is a month)"""
+    return CALENDAR_UNITS.get("".join(c.lower() if c.isascii() else c for c in spec))
+
+
+def days_from_civil(y: int, m: int, d: int) -> int:
+    """days since 1970-01-01 of a proleptic-Gregorian date"""
+    y -= m <= 2
+    era = y // 400
+    yoe = y - era * 400
+    doy = (153 * (m + (-3 if m > 2 else 9)) + 2) // 5 + d - 1
+    return era * 146097 + yoe * 365 + yoe // 4 - yoe // 100 + doy - 719468
+
+
+def civil_from_days(z: int):
+    """-> (y, m, d), the inverse of days_from_civil"""
+    z += 719468
+    era = z // 146097
+    doe = z - era * 146097
+    yoe = (doe - doe // 1460 + doe // 36524 - doe // 146096) // 365
+    doy = doe - (365 * yoe + yoe // 4 - yoe // 100)
+    mp = (5 * doy + 2) // 153
+    d = doy - (153 * mp + 2) // 5 + 1
+    m = mp + 3 if mp < 10 else mp - 9
+    return yoe + era * 400 + (m <= 2), m, d
+
+
+def _days_in_month(y: int, m: int) -> int:
+    return days_from_civil(y + (m == 12), m % 12 + 1, 1) - days_from_civil(y, m, 1)
+
+
+def parse_date(value) -> Optional[float]:
+    """:3467-3472: RFC 3339 -> timestamp_millis() as f64, else a plain number"""
+    if not isinstance(value, str):
+        return None
+    mt = _RFC3339.match(value)
+    if mt:
+        y, mo, d, h, mi, sec = (int(g) for g in mt.groups()[:6])
+        if 1 <= mo <= 12 and 1 <= d <= _days_in_month(y, mo) and h < 24 and mi < 60 and sec < 60:
+            ms = int((mt.group(7) or "0")[:3].ljust(3, "0"))
+            tz = mt.group(8)
+            shift = 0 if tz in "Zz" else (1 if tz[0] == "+" else -1) * (int(tz[1:3]) * 60 + int(tz[4:6])) * 60_000
+            return float((days_from_civil(y, mo, d) * 86_400 + h * 3600 + mi * 60 + sec) * 1000 + ms - shift)
+    return rust_parse_f64(value)
+
+
+def bucket_start(value: int, offset: int, unit: int, step: int) -> int:
+    """:3391-3401 with truncate_calendar (:3410-3429)"""
+    t = value - offset
+    if unit == N.DATE_FIXED:
+        bucket = rust_as_i64(float(math.ceil(float(t) / float(step))))
+        return min(max(bucket * step, I64_MIN), I64_MAX) + offset
+    day = t // DAY_MS
+    if unit == N.DATE_WEEK:
+        day -= (day + 3) % 7  # (1970-01-01 was a Thursday)
+    elif unit != N.DATE_DAY:
+        y, m, _ = civil_from_days(day)
+        m = 1 if unit == N.DATE_YEAR else (m - 1) // 3 * 3 + 1 if unit == N.DATE_QUARTER else m
+        day = days_from_civil(y, m, 1)
+    return day * DAY_MS + offset
+
+
+def bucket_key(bucket_id: int, offset: int, unit: int, step: int) -> int:
+    """the key of a device row: the start of bucket `bucket_id` (slg_date.hpp) + offset"""
+    if unit == N.DATE_FIXED:
+        return bucket_id * step + offset
+    if unit == N.DATE_DAY:
+        return bucket_id * DAY_MS + offset
+    if unit == N.DATE_WEEK:
+        return (7 * bucket_id - 3) * DAY_MS + offset
+    month = bucket_id * {N.DATE_MONTH: 1, N.DATE_QUARTER: 3, N.DATE_YEAR: 12}[unit]
+    return days_from_civil(1970 + month // 12, month % 12 + 1, 1) * DAY_MS + offset
+
+
+def add_interval(current: int, unit: int, step: int) -> Optional[int]:
+    """:3403-3465.  add_calendar re-truncates to midnight: a zero bucket behind the first loses a non-zero offset.
+    None where chrono finds no such date (with_year / with_month keep the day of the month)."""
+    if unit == N.DATE_FIXED:
+        nxt = current + step
+        return nxt if nxt <= I64_MAX else None
+    day = current // DAY_MS
+    if unit in (N.DATE_DAY, N.DATE_WEEK):
+        return (day + (1 if unit == N.DATE_DAY else 7)) * DAY_MS
+    y, m, d = civil_from_days(day)
+    y2, m2 = y, m
+    if unit == N.DATE_MONTH:
+        m2 += 1
+        if m2 > 12:
+            y2, m2 = y + 1, 1
+    elif unit == N.DATE_QUARTER:
+        m2 += 3
+        if m2 > 12:
+            y2, m2 = y + 1, m2 - 12
+    else:
+        y2, m2 = y + 1, 1
+    if d > _days_in_month(y2, m) or d > _days_in_month(y2, m2):  # with_year(y2)?.with_month(m2)?
+        return None
+    return days_from_civil(y2, m2, 1) * DAY_MS
+
+
+def date_histogram_config(name: str, body: dict) -> dict:
+    """DateHistogramCollector::new (:1264-1314) behind the request checks of validate_date_histogram_config
+    (api/reader.rs:3877-...): -> dict(unit, step, offset, extended, hard, missing), times as i64 ms"""
+    cal, fixed, off = body.get("calendar_interval"), body.get("fixed_interval"), body.get("offset")
+    if cal is None and fixed is None:
+        raise ValueError(f"date_histogram `{name}` requires `calendar_interval` or `fixed_interval`")
+    if cal is not None and parse_calendar_interval(cal) is None:
+        raise ValueError(f"date_histogram `{name}` calendar_interval `{cal}` is not supported")
+    if fixed is not None and parse_interval_seconds(fixed) is None:
+        raise ValueError(f"date_histogram `{name}` fixed_interval `{fixed}` is invalid")
+    if off is not None and parse_interval_seconds(off) is None:
+        raise ValueError(f"date_histogram `{name}` offset `{off}` is invalid")
+    bounds = {}
+    for which in ("extended_bounds", "hard_bounds"):
+        b = body.get(which)
+        if b is None:
+            bounds[which] = None
+            continue
+        lo, hi = parse_date(b["min"]), parse_date(b["max"])
+        for end, v in (("min", lo), ("max", hi)):
+            if v is None:
+                raise ValueError(f"date_histogram `{name}` {which}.{end} `{b[end]}` is not a valid date/number")
+        if lo > hi:
+            raise ValueError(f"date_histogram `{name}` {which}.min > max")
+        bounds[which] = (rust_as_i64(lo), rust_as_i64(hi))
+    if cal is not None:  # (calendar wins when both are given)
+        unit, step = parse_calendar_interval(cal), 0
+    else:
+        unit, step = N.DATE_FIXED, rust_as_i64(parse_interval_seconds(fixed) * 1000.0)
+    missing = body.get("missing")
+    if isinstance(missing, (int, float)) and not isinstance(missing, bool):
+        missing = float(missing)
+    else:
+        missing = parse_date(missing)  # (parse_date(s).or_else(|| s.parse::<f64>()): None when neither reads it)
+    return dict(unit=unit, step=step, offset=0 if off is None else rust_as_i64(parse_interval_seconds(off) * 1000.0),
+                extended=bounds["extended_bounds"], hard=bounds["hard_bounds"],
+                missing=None if missing is None else rust_as_i64(missing))
+
+
+def date_range_config(body: dict) -> dict:
+    """DateRangeCollector::new (:1064-1094): -> dict(ranges=[(key, from, to)], missing), f64 or None (a bound that
+    parse_date does not read is no bound)"""
+    as_str = lambda v: v if v is None or isinstance(v, str) else json.dumps(v)
+    ranges = [(rg.get("key"), None if rg.get("from") is None else parse_date(as_str(rg["from"])),
+               None if rg.get("to") is None else parse_date(as_str(rg["to"]))) for rg in body["ranges"]]
+    missing = body.get("missing")
+    if isinstance(missing, str):
+        missing = parse_date(missing)
+    elif isinstance(missing, (int, float)) and not isinstance(missing, bool):
+        missing = float(missing)
+    else:
+        missing = None
+    return dict(ranges=ranges, missing=missing)
+
+
 STATS_DTYPE = np.dtype([("count", np.uint64), ("min", np.float64), ("max", np.float64), ("sum", np.float64)])
 
 
 class AggPlan:
     """A request's aggregations as the device takes them: .spec (N.AggSpec) and, per node in spec order,
-    .nodes[i] = dict(name, type, body, parent, keys) for shape()."""
+    .nodes[i] = dict(name, type, body, parent, keys) for shape(); a date_histogram node also has date =
+    date_histogram_config(), a date_range node date_range = date_range_config(), a filter node filter = its id."""
 
     def __init__(self, spec: "N.AggSpec", nodes: List[dict]):
         self.spec = spec
@@ -79,9 +285,12 @@ class AggPlan:
 
 def agg_spec(aggs: Dict[str, dict], fields: Dict[str, dict]) -> AggPlan:
     """aggs: the request's `aggs` map; fields: field name -> {"id": agg field id, "keys": [dictionary strings]
-    (keyword fields)}.  Roots in name order, each followed by its children in name order.  Raises ValueError
-    for what the device does not build (other types, deeper nesting, sampling): such a request stays on the
-    CPU path."""
+    (keyword fields)}.  fields[FILTERS], when given, is a callable: the `filter` body of a filter aggregation ->
+    the id of a registered filter that stands for it (the caller compiles and registers it, searchlite_amd.filters;
+    in the spirit of compile_filter's `nested` callback); without it a filter aggregation raises ValueError.
+    Roots in name order, each followed by its children in name order.  Raises ValueError for what the device does
+    not build (other types, deeper nesting, sampling) — such a request stays on the CPU path — and for a
+    date_histogram request the reference refuses (validate_date_histogram_config)."""
     nodes: List[dict] = []
 
     def add(name, body, parent):
@@ -90,9 +299,21 @@ def agg_spec(aggs: Dict[str, dict], fields: Dict[str, dict]) -> AggPlan:
             raise ValueError(f"aggregation {name!r}: type {typ!r} is not built on the device")
         if body.get("sampling") is not None:
             raise ValueError(f"aggregation {name!r}: sampling is not built on the device")
-        if body["field"] not in fields:
-            raise ValueError(f"aggregation {name!r}: field {body['field']!r} is not registered")
-        nodes.append(dict(name=name, type=typ, body=body, parent=parent, keys=fields[body["field"]].get("keys")))
+        nd = dict(name=name, type=typ, body=body, parent=parent, keys=None)
+        if typ == "filter":
+            if not callable(fields.get(FILTERS)):
+                raise ValueError(f"aggregation {name!r}: a filter aggregation needs fields[{FILTERS!r}], the map from "
+                                 "its filter to a registered filter id")
+            nd["filter"] = int(fields[FILTERS](body["filter"]))
+        else:
+            if body["field"] not in fields or body["field"] == FILTERS:
+                raise ValueError(f"aggregation {name!r}: field {body['field']!r} is not registered")
+            nd["keys"] = fields[body["field"]].get("keys")
+        if typ == "date_histogram":
+            nd["date"] = date_histogram_config(name, body)
+        if typ == "date_range":
+            nd["date_range"] = date_range_config(body)
+        nodes.append(nd)
         me = len(nodes) - 1
         children = body.get("aggs") or {}
         if children and (parent >= 0 or typ not in BUCKET_TYPES):
@@ -106,8 +327,27 @@ def agg_spec(aggs: Dict[str, dict], fields: Dict[str, dict]) -> AggPlan:
     spec.n_nodes = len(nodes)
     for i, nd in enumerate(nodes[:N.MAX_AGGS]):  # (more are passed on as a count: the library refuses them)
         body, n = nd["body"], spec.nodes[i]
-        n.kind, n.field, n.parent = KINDS[nd["type"]], int(fields[body["field"]]["id"]), nd["parent"]
+        n.kind, n.parent = KINDS[nd["type"]], nd["parent"]
+        if nd["type"] == "filter":
+            n.filter = nd["filter"]
+            continue
+        n.field = int(fields[body["field"]]["id"])
         missing = body.get("missing")
+        if nd["type"] == "date_histogram":
+            dh, missing = nd["date"], None
+            n.calendar_unit, n.date_step, n.date_offset = dh["unit"], dh["step"], dh["offset"]
+            if dh["missing"] is not None:
+                n.has_missing, n.missing = 1, float(dh["missing"])
+            if dh["hard"] is not None:
+                n.has_hard_bounds, n.date_hard_min, n.date_hard_max = 1, dh["hard"][0], dh["hard"][1]
+        if nd["type"] == "date_range":
+            dr, missing = nd["date_range"], None
+            if dr["missing"] is not None:
+                n.has_missing, n.missing = 1, dr["missing"]
+            n.n_ranges = len(dr["ranges"])
+            for r, (_, lo, hi) in enumerate(dr["ranges"][:N.MAX_AGG_RANGES]):
+                n.from_[r] = -math.inf if lo is None else lo
+                n.to[r] = math.inf if hi is None else hi
         if nd["type"] == "terms" or (nd["type"] == "cardinality" and nd["keys"] is not None):
             if missing is not None:
                 keys = list(nd["keys"] or [])
@@ -153,6 +393,8 @@ def shape(plan: AggPlan, layout: List[dict], tables: List[np.ndarray], q: int) -
         nd, body, tab = plan.nodes[i], plan.nodes[i]["body"], tables[i][q, prow]
         if nd["type"] == "stats":
             return _stats(tab[0])
+        if nd["type"] == "value_count":  # :2685-2687
+            return {"type": "value_count", "value": int(tab[0]["count"])}
         if nd["type"] == "cardinality":  # :2688-2692
             return {"type": "cardinality", "value": int(tab[0])}
         if nd["type"] == "percentiles":  # :3245-3251 (a BTreeMap: a repeated key keeps its last value)
@@ -173,6 +415,32 @@ def shape(plan: AggPlan, layout: List[dict], tables: List[np.ndarray], q: int) -
                 b["aggregations"] = {plan.nodes[c]["name"]: node(c, row) for c in children}
             return b
 
+        if nd["type"] == "filter":  # :2707-2726: the one bucket's children are the response's
+            return {"type": "filter", "doc_count": int(tab[0]),
+                    "aggregations": {plan.nodes[c]["name"]: node(c, 0) for c in children}}
+        if nd["type"] == "date_histogram":  # DateHistogramCollector::finish, :1364-1403
+            dh = nd["date"]
+            unit, step, offset = dh["unit"], dh["step"], dh["offset"]
+            first = int(layout[i]["first_id"])
+            found = {bucket_key(first + r, offset, unit, step): (r, int(tab[r])) for r in range(len(tab)) if int(tab[r]) > 0}
+            bounds = dh["extended"] if dh["extended"] is not None else dh["hard"]
+            if bounds is not None:
+                start, end = (bucket_start(v, offset, unit, step) for v in bounds)
+                if start > end:
+                    start, end = end, start
+                current = start
+                while current is not None and current <= end:
+                    found.setdefault(current, (None, 0))
+                    current = add_interval(current, unit, step)
+            mdc = body.get("min_doc_count")
+            min_count = int(mdc) if mdc is not None else 0
+            return {"type": "date_histogram",
+                    "buckets": [bucket(key, r, c) for key, (r, c) in sorted(found.items()) if c >= min_count]}
+        if nd["type"] == "date_range":  # the inner RangeCollector's buckets under the parsed bounds
+            out = []
+            for r, (key, lo, hi) in enumerate(nd["date_range"]["ranges"]):
+                out.append(bucket(key if key is not None else {"from": lo, "to": hi}, r, int(tab[r])))
+            return {"type": "date_range", "buckets": out, "keyed": bool(body.get("keyed", False))}
         if nd["type"] == "terms":
             keys = list(nd["keys"] or [])
             min_count = int(body.get("min_doc_count", 1) if body.get("min_doc_count") is not None else 1)

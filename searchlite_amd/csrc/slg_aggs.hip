@@ -15,10 +15,19 @@ static_assert(slg::kAggTerms == SLG_AGG_TERMS && slg::kAggHistogram == SLG_AGG_H
 static_assert(slg::kAggCardinality == SLG_AGG_CARDINALITY && slg::kAggPercentiles == SLG_AGG_PERCENTILES &&
                   slg::kAggPercentileRanks == SLG_AGG_PERCENTILE_RANKS && slg::kAggPctLdsBytes == SLG_AGG_PCT_LDS_BYTES,
               "header value kinds");
+static_assert(slg::kAggDateHistogram == SLG_AGG_DATE_HISTOGRAM && slg::kAggFilter == SLG_AGG_FILTER &&
+                  slg::kDateFixed == SLG_DATE_FIXED && slg::kDateDay == SLG_DATE_DAY && slg::kDateWeek == SLG_DATE_WEEK &&
+                  slg::kDateMonth == SLG_DATE_MONTH && slg::kDateQuarter == SLG_DATE_QUARTER &&
+                  slg::kDateYear == SLG_DATE_YEAR, "header date kinds");
 static_assert(sizeof(slg::AggStatDev) == 32 && sizeof(slg_agg_stats) == 32, "stats cells are 32 bytes");
 
 namespace {
-bool is_bucket(int32_t kind) { return kind == SLG_AGG_TERMS || kind == SLG_AGG_HISTOGRAM || kind == SLG_AGG_RANGE; }
+bool is_bucket(int32_t kind) {
+  return kind == SLG_AGG_TERMS || kind == SLG_AGG_HISTOGRAM || kind == SLG_AGG_RANGE ||
+         kind == SLG_AGG_DATE_HISTOGRAM || kind == SLG_AGG_FILTER;
+}
+constexpr long long kTwo53 = 1ll << 53;  // an i64 up to here is an f64, and `as i64` / `as f64` are exact
+bool within_two53(long long v) { return v >= -kTwo53 && v <= kTwo53; }
 bool is_value(int32_t kind) {
   return kind == SLG_AGG_CARDINALITY || kind == SLG_AGG_PERCENTILES || kind == SLG_AGG_PERCENTILE_RANKS;
 }
@@ -49,11 +58,12 @@ void slghost::agg_check_spec(const slg_agg_spec *aggs) {
     if (n.parent != -1) {
       SLG_REQUIRE(n.parent >= 0 && (uint32_t)n.parent < i, node_name(i) + ": parent is not an earlier node");
       const slg_agg_node &pn = aggs->nodes[n.parent];
-      SLG_REQUIRE(is_bucket(pn.kind), node_name(i) + ": parent is not a bucket node (terms, histogram, range)");
+      SLG_REQUIRE(is_bucket(pn.kind), node_name(i) + ": parent is not a bucket node (terms, histogram, range, "
+                                                     "date_histogram, filter)");
       SLG_REQUIRE(pn.parent == -1, node_name(i) + ": parent is not a root (two levels)");
     }
     // (a cardinality node's `missing` is read for a numeric field only: checked against the index)
-    if (n.kind != SLG_AGG_TERMS && n.kind != SLG_AGG_CARDINALITY && n.has_missing)
+    if (n.kind != SLG_AGG_TERMS && n.kind != SLG_AGG_CARDINALITY && n.kind != SLG_AGG_FILTER && n.has_missing)
       SLG_REQUIRE(std::isfinite(n.missing), node_name(i) + ": missing is not finite");
     if (n.kind == SLG_AGG_PERCENTILES || n.kind == SLG_AGG_PERCENTILE_RANKS) {
       const char *what = n.kind == SLG_AGG_PERCENTILES ? "percent" : "target";
@@ -71,6 +81,12 @@ void slghost::agg_check_spec(const slg_agg_spec *aggs) {
       if (n.has_hard_bounds)
         SLG_REQUIRE(!std::isnan(n.hard_min) && !std::isnan(n.hard_max), node_name(i) + ": hard bound is NaN");
     }
+    if (n.kind == SLG_AGG_FILTER) SLG_REQUIRE(n.filter >= 0, node_name(i) + ": filter id is negative");
+    if (n.kind == SLG_AGG_DATE_HISTOGRAM) {
+      SLG_REQUIRE(n.calendar_unit <= SLG_DATE_YEAR, node_name(i) + ": unknown calendar unit");
+      if (n.calendar_unit == SLG_DATE_FIXED)
+        SLG_REQUIRE(n.date_step >= 1, node_name(i) + ": a fixed interval must be at least 1 ms");
+    }
     if (n.kind == SLG_AGG_RANGE) {
       SLG_REQUIRE(n.n_ranges >= 1, node_name(i) + ": a range node needs at least one range");
       if (n.n_ranges > SLG_MAX_AGG_RANGES)
@@ -78,6 +94,16 @@ void slghost::agg_check_spec(const slg_agg_spec *aggs) {
       for (uint32_t r = 0; r < n.n_ranges; r++)
         SLG_REQUIRE(!std::isnan(n.from[r]) && !std::isnan(n.to[r]), node_name(i) + ": range bound is NaN");
     }
+  }
+  for (uint32_t i = 0; i < aggs->n_nodes; i++) {  // (an invalid spec is reported before an unsupported one)
+    const slg_agg_node &n = aggs->nodes[i];
+    if (n.kind != SLG_AGG_DATE_HISTOGRAM) continue;
+    if (!within_two53(n.date_offset))
+      throw SlgError(SLG_ERR_UNSUPPORTED, node_name(i) + ": offset beyond +-2^53 ms (CPU path)");
+    if (n.has_missing && std::fabs(n.missing) > (double)kTwo53)
+      throw SlgError(SLG_ERR_UNSUPPORTED, node_name(i) + ": missing beyond +-2^53 ms (CPU path)");
+    if (n.has_hard_bounds && !(within_two53(n.date_hard_min) && within_two53(n.date_hard_max)))
+      throw SlgError(SLG_ERR_UNSUPPORTED, node_name(i) + ": hard bound beyond +-2^53 ms (CPU path)");
   }
 }
 
@@ -96,12 +122,18 @@ void slghost::agg_attach(slg_batch *b, const slg_agg_spec &aggs) {
   uint32_t n_value = 0, n_pct = 0, n_walk1 = 0;
   for (uint32_t i = 0; i < nn; i++) {
     const slg_agg_node &n = aggs.nodes[i];
-    const slgplan::FscoreFieldView &fd = slgplan::agg_field(fields, n.field, node_name(i) + ": ", "");
+    // (a filter node has no column: its field is not read — no_field passes the checks below — and its rows of
+    // `cols` stay null)
+    static const slgplan::FscoreFieldView no_field;
+    const bool has_col = n.kind != SLG_AGG_FILTER;
+    const slgplan::FscoreFieldView &fd =
+        has_col ? slgplan::agg_field(fields, n.field, node_name(i) + ": ", "") : no_field;
     SLG_REQUIRE((n.kind == SLG_AGG_TERMS || (n.kind == SLG_AGG_CARDINALITY && fd.keyword)) == fd.keyword,
                 node_name(i) + ": field " + std::to_string(n.field) +
                     (fd.keyword ? " is a keyword field (terms and cardinality only)"
                                 : " is a numeric field (not for terms)"));
-    std::copy_n(slgplan::agg_field_rows(fd, (uint32_t)n_segs, "", ""), n_segs, cols.begin() + (size_t)i * n_segs);
+    if (has_col)
+      std::copy_n(slgplan::agg_field_rows(fd, (uint32_t)n_segs, "", ""), n_segs, cols.begin() + (size_t)i * n_segs);
     if (!fd.keyword && fd.non_finite)
       throw SlgError(SLG_ERR_UNSUPPORTED,
                      node_name(i) + ": agg field " + std::to_string(n.field) + " holds a non-finite value (CPU path)");
@@ -145,6 +177,48 @@ void slghost::agg_attach(slg_batch *b, const slg_agg_spec &aggs) {
           throw SlgError(SLG_ERR_UNSUPPORTED, node_name(i) + ": more than SLG_MAX_AGG_CELLS histogram buckets");
         first_id = (long long)klo;
         rows = (uint64_t)((long long)khi - first_id + 1);
+      }
+    } else if (n.kind == SLG_AGG_FILTER) {
+      SLG_REQUIRE((size_t)n.filter < S.filters.size() && S.filter_usable((size_t)n.filter),
+                  node_name(i) + ": unknown filter id " + std::to_string(n.filter));
+      d.filter = (uint32_t)n.filter;
+    } else if (n.kind == SLG_AGG_DATE_HISTOGRAM) {
+      d.unit = n.calendar_unit;
+      d.step = n.calendar_unit == SLG_DATE_FIXED ? n.date_step : 1;
+      d.date_offset = n.date_offset;
+      d.has_hard = n.has_hard_bounds ? 1u : 0u;
+      d.date_hard_min = n.date_hard_min;
+      d.date_hard_max = n.date_hard_max;
+      // every collectable value within +-2^53: `as i64` and val - offset are then exact (agg_check_spec saw the
+      // offset, `missing` and the hard bounds; an _i64 column that held 2^53 + 1 recorded it as 2^53)
+      if (fd.any_value && (fd.i64_rounded || std::fabs(fd.vmin) > (double)kTwo53 || std::fabs(fd.vmax) > (double)kTwo53))
+        throw SlgError(SLG_ERR_UNSUPPORTED, node_name(i) + ": agg field " + std::to_string(n.field) +
+                                                " holds a value beyond +-2^53 (CPU path)");
+      // the dense id range, as the histogram's: date_bucket_id is monotone in the value, and so is `as i64`
+      bool any = fd.any_value;
+      long long lo = any ? (long long)fd.vmin : 0, hi = any ? (long long)fd.vmax : 0;
+      if (n.has_missing) {
+        const long long m = (long long)n.missing;
+        lo = any ? std::min(lo, m) : m;
+        hi = any ? std::max(hi, m) : m;
+        any = true;
+      }
+      if (any && n.has_hard_bounds) {
+        lo = std::max(lo, (long long)n.date_hard_min);
+        hi = std::min(hi, (long long)n.date_hard_max);
+        any = lo <= hi;
+      }
+      if (any) {
+        if (n.calendar_unit != SLG_DATE_FIXED &&
+            (lo - n.date_offset < slg::kDateMinMs || hi - n.date_offset > slg::kDateMaxMs))
+          throw SlgError(SLG_ERR_UNSUPPORTED, node_name(i) + ": a calendar instant outside 0001-01-01 .. 9999-12-31 "
+                                                             "(CPU path)");
+        const long long klo = slg::date_bucket_id(d.unit, d.step, d.date_offset, lo);
+        const long long khi = slg::date_bucket_id(d.unit, d.step, d.date_offset, hi);
+        if (khi - klo + 1 > (long long)SLG_MAX_AGG_CELLS)
+          throw SlgError(SLG_ERR_UNSUPPORTED, node_name(i) + ": more than SLG_MAX_AGG_CELLS date_histogram buckets");
+        first_id = klo;
+        rows = (uint64_t)(khi - klo + 1);
       }
     } else if (n.kind == SLG_AGG_RANGE) {
       d.n_ranges = n.n_ranges;
@@ -245,6 +319,9 @@ void slghost::agg_attach(slg_batch *b, const slg_agg_spec &aggs) {
   b->agg_value_cells = (uint32_t)value_cells;
   b->agg_card_words = (uint32_t)card_words;
   b->agg_walk1 = n_walk1 > 0;
+  b->agg_ext = false;  // the instantiations with the date_histogram and filter paths
+  for (uint32_t i = 0; i < nn; i++)
+    b->agg_ext = b->agg_ext || aggs.nodes[i].kind == SLG_AGG_DATE_HISTOGRAM || aggs.nodes[i].kind == SLG_AGG_FILTER;
   b->agg_pct_lds = n_pct ? slg::kAggPctLdsBytes : 0u;
   b->agg_x_lds = 8 * value_cells + 4 * card_words + b->agg_pct_lds <= slg::kAggLdsBytes;
   if (!b->agg_x_lds)
@@ -280,12 +357,14 @@ void slghost::agg_launch(slg_batch *b, hipStream_t st) {
     // (nothing but value nodes, and nobody to count for)
   } else if (b->agg_lds) {
     const size_t lds = (size_t)p.stats_cells * sizeof(slg::AggStatDev) + (size_t)p.count_cells * 4;
-    launch_kernel_lds(slg::agg_kernel<true>, p, dim3(b->nq), slg::kAggThreads, lds, st);
+    launch_kernel_lds(b->agg_ext ? slg::agg_kernel<true, true> : slg::agg_kernel<true, false>, p, dim3(b->nq),
+                      slg::kAggThreads, lds, st);
   } else {
     SLG_HIP(hipMemsetAsync(b->d_agg_counts.p, 0, (size_t)b->nq * std::max<size_t>(p.count_cells, 1) * 4, st));
     SLG_HIP(hipMemsetAsync(b->d_agg_stats.p, 0,
                            (size_t)b->nq * std::max<size_t>(p.stats_cells, 1) * sizeof(slg::AggStatDev), st));
-    launch_kernel_lds(slg::agg_kernel<false>, p, dim3(b->nq), slg::kAggThreads, 0, st);
+    launch_kernel_lds(b->agg_ext ? slg::agg_kernel<false, true> : slg::agg_kernel<false, false>, p, dim3(b->nq),
+                      slg::kAggThreads, 0, st);
   }
   if (b->agg_value_nodes == 0) return;
   slg::AggValueParams v{};
@@ -305,10 +384,12 @@ void slghost::agg_launch(slg_batch *b, hipStream_t st) {
   if (v.scratch_words) SLG_HIP(hipMemsetAsync(v.scratch, 0, (size_t)b->nq * v.scratch_words * 4, st));
   if (b->agg_x_lds) {
     const size_t lds = (size_t)b->agg_pct_lds + 8 * (size_t)v.value_cells + 4 * (size_t)v.card_words;
-    launch_kernel_lds(slg::agg_values_kernel<true>, v, dim3(b->nq), slg::kAggThreads, lds, st);
+    launch_kernel_lds(b->agg_ext ? slg::agg_values_kernel<true, true> : slg::agg_values_kernel<true, false>, v,
+                      dim3(b->nq), slg::kAggThreads, lds, st);
   } else {
     SLG_HIP(hipMemsetAsync(v.values, 0, (size_t)b->nq * std::max<size_t>(v.value_cells, 1) * 8, st));
-    launch_kernel_lds(slg::agg_values_kernel<false>, v, dim3(b->nq), slg::kAggThreads, b->agg_pct_lds, st);
+    launch_kernel_lds(b->agg_ext ? slg::agg_values_kernel<false, true> : slg::agg_values_kernel<false, false>, v,
+                      dim3(b->nq), slg::kAggThreads, b->agg_pct_lds, st);
   }
 }
 

@@ -1,9 +1,9 @@
-// slg_aggs.hpp — the aggregation kernel (slg_batch_prepare_aggs; query/aggs/mod.rs terms, histogram, range
-// and stats collectors).  An aggregation batch is planned as a sorted batch: its scoring kernel leaves every
-// matched doc of every sub-query in the candidate region, once.  After the batch's select kernel one
-// workgroup per query walks the query's slices as select_sorted_kernel does, applies accept() again (the
-// reject bitmap: one word per candidate, so the kernel does not depend on what the select left behind), and
-// adds every accepted doc to the query's dense tables:
+// slg_aggs.hpp — the aggregation kernel (slg_batch_prepare_aggs; query/aggs/mod.rs terms, histogram, range,
+// date_histogram, filter and stats collectors).  An aggregation batch is planned as a sorted batch: its scoring
+// kernel leaves every matched doc of every sub-query in the candidate region, once.  After the batch's select
+// kernel one workgroup per query walks the query's slices as select_sorted_kernel does, applies accept() again
+// (the reject bitmap: one word per candidate, so the kernel does not depend on what the select left behind),
+// and adds every accepted doc to the query's dense tables:
 //   counts  u32 [count_cells]   the bucket nodes' tables, node after node, each parent_rows x rows
 //   stats   AggStatDev [stats_cells]   the stats nodes' tables, each parent_rows x 1
 // A query's tables belong to one workgroup, so nothing has to be visible across workgroups.  Two homes:
@@ -22,6 +22,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "slg_date.hpp"
 #include "slg_desc.hpp"
 #include "slg_wave.hpp"
 
@@ -35,7 +36,8 @@ constexpr uint32_t kAggCoarseBits = 12;
 constexpr uint32_t kAggNoRank = 0xFFFFFFFFu;
 enum : int32_t {
   kAggTerms = 0, kAggHistogram = 1, kAggRange = 2, kAggStats = 3,
-  kAggCardinality = 4, kAggPercentiles = 5, kAggPercentileRanks = 6
+  kAggCardinality = 4, kAggPercentiles = 5, kAggPercentileRanks = 6,
+  kAggDateHistogram = 8, kAggFilter = 9
 };
 
 // min and max as u64 keys under atomicMax, so that an all-zero cell is the empty one: max_key = the value's
@@ -63,6 +65,10 @@ struct AggNodeDev {
   uint32_t shift;       // percentiles: coarse bin = rank >> shift
   uint32_t fine_lds, fine_off;  // percentiles: the fine tables lie in LDS, or at this word of the scratch slice
   const double *dict;   // percentiles: the value of every real rank
+  // date_histogram: SLG_DATE_*, then i64 milliseconds (has_hard: the two bounds are read); filter: the filter's row
+  // of reject_table
+  uint32_t unit, filter;
+  long long step, date_offset, date_hard_min, date_hard_max;
 };
 
 struct AggParams {
@@ -141,10 +147,21 @@ __device__ __forceinline__ AggDocValues agg_doc_values(const P &p, const AggNode
   return agg_doc_values(n, col, a, e);
 }
 
-// The buckets of bucket node n that one doc is counted in: emit(row) once per bucket; the doc's values in the
-// node's column are [a, e) of col.  Shared by agg_kernel (the node's own counts, and the rows its children collect
-// into) and agg_values_kernel (the rows of a value child).
-template <typename F>
+// A filter node's one bucket: the doc's bit in the reject bitmap of the node's filter is clear (a segment
+// without a bitmap rejects nothing).  A filter node has no column: nothing of `cols` is read for it.
+template <typename P>
+__device__ __forceinline__ bool agg_filter_passes(const P &p, const AggNodeDev &n, const uint32_t seg,
+                                                  const uint32_t doc) {
+  const uint32_t *rej = p.reject_table[(size_t)n.filter * p.n_segs + seg];
+  return !(rej && ((rej[doc >> 5] >> (doc & 31)) & 1u));
+}
+
+// The buckets of bucket node n (not a filter node) that one doc is counted in: emit(row) once per bucket; the
+// doc's values in the node's column are [a, e) of col.  Shared by agg_kernel (the node's own counts, and the rows
+// its children collect into) and agg_values_kernel (the rows of a value child).  EXT: the spec has a
+// date_histogram or filter node; a spec without one runs the instantiation that holds neither path (its registers
+// are what they were without them).
+template <bool EXT, typename F>
 __device__ __forceinline__ void agg_buckets(const AggNodeDev &n, const ColumnDev &col, const uint32_t a,
                                             const uint32_t e, F &&emit) {
   if (n.kind == kAggTerms) {
@@ -164,9 +181,17 @@ __device__ __forceinline__ void agg_buckets(const AggNodeDev &n, const ColumnDev
     return;
   }
   const AggDocValues d = agg_doc_values(n, col, a, e);
-  if (n.kind == kAggHistogram) {
-    // id = floor((val - offset) / interval): IEEE f64 subtraction, division and floor (no fast-math, no fma)
+  const bool date = EXT && n.kind == kAggDateHistogram;
+  if (n.kind == kAggHistogram || date) {
+    // histogram: id = floor((val - offset) / interval): IEEE f64 subtraction, division and floor (no fast-math, no
+    // fma).  date_histogram: the value `as i64` (truncated toward zero), i64 hard bounds, date_bucket_id
     auto bucket = [&](const double x, long long &id) {
+      if (date) {
+        const long long v = (long long)x;
+        if (n.has_hard && (v < n.date_hard_min || v > n.date_hard_max)) return false;
+        id = date_bucket_id(n.unit, n.step, n.date_offset, v);
+        return true;
+      }
       if (n.has_hard && (x < n.hard_min || x > n.hard_max)) return false;
       id = (long long)floor((x - n.offset) / n.interval);
       return true;
@@ -196,28 +221,38 @@ __device__ __forceinline__ void agg_buckets(const AggNodeDev &n, const ColumnDev
     if (in) emit(r);
   }
 }
-template <typename P, typename F>
+template <bool EXT, typename P, typename F>
 __device__ __forceinline__ void agg_buckets(const P &p, const AggNodeDev &n, const uint32_t seg, const uint32_t doc,
                                             F &&emit) {
+  if (EXT && n.kind == kAggFilter) {
+    if (agg_filter_passes(p, n, seg, doc)) emit(0u);
+    return;
+  }
   const ColumnDev col = p.cols[(size_t)n.col * p.n_segs + seg];
   uint32_t a, e;
   column_range(col, doc, a, e);
-  agg_buckets(n, col, a, e, emit);
+  agg_buckets<EXT>(n, col, a, e, emit);
 }
 
 
 // One node's collector for one doc; cell = the first cell of the table row the doc goes to (the node's own
 // table for a root, the parent bucket's row of it for a child).  child(b): the doc was counted in bucket b.
 // (value nodes are agg_values_kernel's)
-template <typename F>
+template <bool EXT, typename F>
 __device__ __forceinline__ void agg_collect(const AggParams &p, const AggNodeDev &n, const uint32_t seg,
                                             const uint32_t doc, const uint32_t cell, uint32_t *cnt, AggStatDev *st,
                                             F &&child) {
+  if (EXT && n.kind == kAggFilter) {  // (no column)
+    if (!agg_filter_passes(p, n, seg, doc)) return;
+    atomicAdd(&cnt[cell], 1u);
+    child(0u);
+    return;
+  }
   // (the column and the doc's range are read before the kind decides: the loads go out together)
   const ColumnDev col = p.cols[(size_t)n.col * p.n_segs + seg];
   uint32_t a, e;
   column_range(col, doc, a, e);
-  if (n.kind > kAggStats) return;
+  if (n.kind > kAggStats && !(EXT && n.kind == kAggDateHistogram)) return;
   if (n.kind == kAggStats) {
     const AggDocValues d = agg_doc_values(n, col, a, e);
     AggStatDev *s = st + cell;
@@ -231,13 +266,13 @@ __device__ __forceinline__ void agg_collect(const AggParams &p, const AggNodeDev
     }
     return;
   }
-  agg_buckets(n, col, a, e, [&](const uint32_t b) {
+  agg_buckets<EXT>(n, col, a, e, [&](const uint32_t b) {
     atomicAdd(&cnt[cell + b], 1u);
     child(b);
   });
 }
 
-template <bool LDS>
+template <bool LDS, bool EXT>
 static __global__ void __launch_bounds__(kAggThreads) agg_kernel(AggParams p) {
   extern __shared__ unsigned long long agg_lds[];  // (LDS) the stats cells, then the count cells
   __shared__ uint32_t sh_matched;
@@ -263,11 +298,11 @@ static __global__ void __launch_bounds__(kAggThreads) agg_kernel(AggParams p) {
     for (uint32_t r = 0; r < p.n_nodes; r++) {
       const AggNodeDev &root = p.nodes[r];
       if (root.parent >= 0) continue;
-      agg_collect(p, root, seg, doc, root.off, cnt, st, [&](const uint32_t b) {
+      agg_collect<EXT>(p, root, seg, doc, root.off, cnt, st, [&](const uint32_t b) {
         for (uint32_t c = r + 1; c < p.n_nodes; c++) {
           const AggNodeDev &ch = p.nodes[c];
           if (ch.parent != (int32_t)r) continue;
-          agg_collect(p, ch, seg, doc, ch.off + b * ch.rows, cnt, st, [](uint32_t) {});
+          agg_collect<EXT>(p, ch, seg, doc, ch.off + b * ch.rows, cnt, st, [](uint32_t) {});
         }
       });
     }
@@ -333,7 +368,7 @@ __device__ __forceinline__ double agg_rank_value(const AggNodeDev &n, uint32_t r
   return n.dict[r];
 }
 
-template <bool XLDS>
+template <bool XLDS, bool EXT>
 static __global__ void __launch_bounds__(kAggThreads) agg_values_kernel(AggValueParams p) {
   extern __shared__ unsigned long long av_lds[];  // the percentiles region, then (XLDS) value cells and bitmaps
   __shared__ uint32_t sh_wtot[kAggThreads / 64], sh_n, sh_nsel;
@@ -378,7 +413,7 @@ static __global__ void __launch_bounds__(kAggThreads) agg_values_kernel(AggValue
             }
           };
           if (n.parent < 0) into(0);
-          else agg_buckets(p, p.nodes[n.parent], seg, doc, into);
+          else agg_buckets<EXT>(p, p.nodes[n.parent], seg, doc, into);
         } else if (n.kind == kAggPercentileRanks) {
           const uint32_t width = 1u + n.n_ranges;
           AggDocValues d{nullptr, 0u, 0u, false, 0.0};
@@ -394,7 +429,7 @@ static __global__ void __launch_bounds__(kAggThreads) agg_values_kernel(AggValue
               if (lane == 0 && c) atomicAdd(&vals[n.off + 1 + t], (unsigned long long)c);
             }
           } else if (d.nv) {
-            agg_buckets(p, p.nodes[n.parent], seg, doc, [&](const uint32_t row) {
+            agg_buckets<EXT>(p, p.nodes[n.parent], seg, doc, [&](const uint32_t row) {
               unsigned long long *cell = vals + n.off + (size_t)row * width;
               atomicAdd(&cell[0], (unsigned long long)d.nv);
               for (uint32_t t = 0; t < n.n_ranges; t++) {

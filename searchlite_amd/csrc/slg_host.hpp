@@ -547,6 +547,7 @@ struct slg_batch {
   // value nodes (cardinality, percentiles, percentile_ranks): agg_values_kernel behind agg_kernel
   uint32_t agg_value_nodes = 0, agg_value_cells = 0, agg_card_words = 0, agg_scratch_words = 0, agg_pct_lds = 0;
   bool agg_walk1 = false, agg_x_lds = false;  // a cardinality / percentile_ranks node; cells and bitmaps fit LDS
+  bool agg_ext = false;                       // a date_histogram or filter node: the kernels that hold those paths
   DevBuf d_agg_values, d_agg_scratch;         // u64[nq * value_cells], u32[nq * scratch_words]
   // rescore batch (slg_batch_prepare_rescore): rescore_kernel runs behind the first pass's last kernel and
   // rewrites the first rows of every query in place (slg_rescore.hip)

@@ -5,6 +5,7 @@
 #include <cstring>
 #include <new>
 
+#include "slg_date.hpp"
 #include "slg_plan.hpp"
 
 extern "C" {
@@ -537,6 +538,28 @@ int slgp_plan_filter_trees(const slgp_filter_field *fields, uint32_t n_fields, c
     }
     return e.code;
   }
+}
+
+// the bucket function of a date_histogram node (slg::date_bucket_id, slg_date.hpp: what the planner's row range and
+// the aggregation kernels run) over n values: ids[i] = the bucket id of vals[i] under unit (SLG_DATE_*), step and
+// offset (i64 ms; step is read for SLG_DATE_FIXED only); ymd[3 i ..] = year, month, day of the UTC day that holds
+// vals[i] - offset (slg::date_civil).  Either output may be NULL.  0, or SLG_ERR_INVALID (an unknown unit, a fixed
+// step < 1, vals NULL with n > 0)
+int slgp_date_buckets(uint32_t unit, int64_t step, int64_t offset, const int64_t *vals, uint64_t n, int64_t *ids,
+                      int32_t *ymd) {
+  if (unit > slg::kDateYear || (unit == slg::kDateFixed && step < 1) || (n && !vals)) return SLG_ERR_INVALID;
+  for (uint64_t i = 0; i < n; i++) {
+    if (ids) ids[i] = slg::date_bucket_id(unit, step, offset, vals[i]);
+    if (ymd) {
+      long long y;
+      uint32_t m, d;
+      slg::date_civil(slg::date_floor_div(vals[i] - offset, slg::kDateDayMs), y, m, d);
+      ymd[3 * i] = (int32_t)y;
+      ymd[3 * i + 1] = (int32_t)m;
+      ymd[3 * i + 2] = (int32_t)d;
+    }
+  }
+  return SLG_OK;
 }
 
 // the host checks of slg_index_set_positions over a segment of n_postings postings.  0, or a negative error code

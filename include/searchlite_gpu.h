@@ -838,6 +838,85 @@ int slg_search_batch_agg_values(slg_index *index, const slg_query *queries, uint
                                 uint32_t *out_count, uint64_t *out_matched, uint64_t *counts, slg_agg_stats *stats,
                                 uint64_t *values);
 
+/* ---- top_hits aggregation: the best hits per bucket ---------------------------------------------------
+ * TopHitsAggregation (api/types.rs:969-980; TopHitsCollector, query/aggs/mod.rs:1870-1981): per list — the whole
+ * matched set for a root node, every bucket of its parent for a child — the limit = from + size best matched docs
+ * under the node's sort are kept and the rows [from, from + size) of them reported, best first.  The order is the
+ * field-sorted select's SortKey: parts in order, a Missing value after every value in both orders, ties by segment
+ * then doc (query/sort.rs:80-123); an empty sort is `_score` desc.  A hit's score, and the value of a `_score`
+ * part, is what the batch's rows carry for the same doc: the BM25 score in score order or under a batch sort with
+ * a `_score` part, 0.0 under a field sort without one (ScoreMode::MatchOnly).  A child sees a doc once per parent
+ * bucket the doc was counted in.  `fields` and `highlight_field` are doc-store work on the finished hits and stay
+ * with the caller: the device returns (segment, doc, score).
+ *
+ * slg_agg_node does not grow: top_hits nodes travel in a spec of their own, next to the aggregation spec.
+ * slg_batch_prepare_top_hits is slg_batch_prepare_aggs plus that spec; aggs_or_null may be NULL only when every
+ * node is a root.  Rows, matched counts and every aggregation table of such a batch are bit-identical to the same
+ * batch prepared with slg_batch_prepare_aggs (without aggs: with slg_batch_prepare_plans / _sorted), and
+ * slg_batch_matched_counts serves it.  Checked before the index is looked at (after the aggregation spec's own
+ * checks): top_hits NULL, n_nodes == 0, a parent that is neither -1 nor the index of a ROOT bucket node (terms,
+ * histogram, range, date_histogram, filter) of aggs — a parent that is itself a child, a third level, is
+ * SLG_ERR_UNSUPPORTED —, aggs NULL with a child node, an order that is neither SLG_ORDER_ASC nor _DESC, a sort
+ * field id below SLG_SORT_SCORE: SLG_ERR_INVALID; n_nodes > SLG_MAX_TOP_HITS_NODES, size == 0 (nothing to select:
+ * the total is in the tables already), from + size > SLG_MAX_TOP_HITS, more than SLG_MAX_SORT_PARTS parts:
+ * SLG_ERR_UNSUPPORTED (the CPU path; a keyword sort field cannot be registered, as for slg_batch_prepare_sorted).
+ * Against the index: an unknown sort field id or one without a column for every segment: SLG_ERR_INVALID; more
+ * than SLG_MAX_TOP_HITS_CELLS hit cells per query (the sum of lists x size: a parent's rows are known only there):
+ * SLG_ERR_UNSUPPORTED.  Nodes may come in any order; nodes of one parent that follow one another share its bucket
+ * runs, otherwise each builds them again (the same lists, more time).  Memory per batch: nq x (8 B x max_entries + 12 B x hit_cells + 4 B x list_cells), plus 4 B
+ * per row of a parent of more than 4096 rows.  Not built (the CPU path): cursor, hybrid, vector-only, scan, sharded
+ * and coalesced batches (no such entry point takes the spec; slg_batch_run_sharded* refuses the batch), a third
+ * level, from + size > 64, keyword sort parts. */
+#define SLG_MAX_TOP_HITS_NODES 4u
+#define SLG_MAX_TOP_HITS 64u              /* from + size of one node: one entry per lane */
+#define SLG_MAX_TOP_HITS_CELLS 65536u     /* hit cells of one query: sum of lists x size */
+#define SLG_MAX_TOP_HITS_ENTRIES (1u << 19) /* bucket-run entries of one query (default capacity) */
+typedef struct {
+  int32_t parent;        /* -1 = root, else the index of a ROOT bucket node of the aggs spec */
+  uint32_t from, size;
+  slg_sort_spec sort;    /* n_parts == 0: _score desc */
+} slg_top_hits_node;
+typedef struct {
+  uint32_t n_nodes;      /* 1 .. SLG_MAX_TOP_HITS_NODES */
+  uint32_t max_entries;  /* 0 = SLG_MAX_TOP_HITS_ENTRIES; smaller: less memory per query */
+  slg_top_hits_node nodes[SLG_MAX_TOP_HITS_NODES];
+} slg_top_hits_spec;
+typedef struct {
+  uint32_t lists;        /* 1 for a root, else the parent's rows */
+  uint32_t size;
+  uint32_t list_offset;  /* first list of the node in a query's count array */
+  uint32_t hit_offset;   /* first hit cell of the node in a query's hit arrays */
+} slg_top_hits_layout;
+slg_batch *slg_batch_prepare_top_hits(slg_index *index, uint32_t nq, const uint32_t *q_offsets,
+                                      const uint32_t *q_term_ids, const float *q_weights,
+                                      const slg_score_plans *plans_or_null, const int32_t *q_filter_or_null,
+                                      const slg_sort_spec *sort_or_null, const slg_agg_spec *aggs_or_null,
+                                      const slg_top_hits_spec *top_hits, uint32_t k, int strategy);
+/* One entry per top_hits node (out: n_nodes entries).  A node's hits are lists x size cells: list-major, in node
+ * order, lists in the parent's row order.  hit_cells of a query = the sum of lists x size, list_cells = the sum of
+ * lists. */
+int slg_batch_top_hits_layout(const slg_batch *batch, slg_top_hits_layout *out);
+/* The lists of the batch's last run: out_doc, out_seg, out_score [nq x hit_cells], out_count [nq x list_cells],
+ * out_status [nq] (any may be NULL); waits for the batch.  out_count[list] = min(size, max(0, collected - from))
+ * real hits, cells past it are zero.  A list's total is not returned here: it is the parent's count cell for a
+ * child (slg_batch_fetch_aggs) and the matched count for a root (slg_batch_matched_counts).  Status 0: ok; 1: the
+ * query needed more than max_entries bucket-run entries (the sum of a parent's count row): its lists are all
+ * zero and the caller takes that request to the CPU path; the batch's rows, matched counts and aggregation tables
+ * are unaffected.  Nothing here depends on scheduling: the key is a total order.  SLG_ERR_INVALID on a batch of
+ * another kind. */
+int slg_batch_fetch_top_hits(slg_batch *batch, uint32_t *out_doc, uint32_t *out_seg, float *out_score,
+                             uint32_t *out_count, uint32_t *out_status);
+/* One-shot form: slg_search_batch_agg_values with a top_hits spec (aggs_or_null as above; counts / stats / values
+ * may be NULL without cells of their kind); the th_ arrays are sized by the caller as slg_batch_top_hits_layout
+ * would tell. */
+int slg_search_batch_top_hits(slg_index *index, const slg_query *queries, uint32_t nq,
+                              const slg_score_plans *plans_or_null, const int32_t *q_filter_or_null,
+                              const slg_sort_spec *sort_or_null, const slg_agg_spec *aggs_or_null,
+                              const slg_top_hits_spec *top_hits, uint32_t k, int strategy, uint32_t *out_doc,
+                              uint32_t *out_seg, float *out_score, uint32_t *out_count, uint64_t *out_matched,
+                              uint64_t *counts, slg_agg_stats *stats, uint64_t *values, uint32_t *th_doc,
+                              uint32_t *th_seg, float *th_score, uint32_t *th_count, uint32_t *th_status);
+
 /* ---- request coalescer ------------------------------------------------------------------------------
  * searchlite has no batch API: IndexReader::search takes one request (api/reader.rs:2539) and the HTTP
  * server gives every request its own blocking thread (searchlite-http/src/lib.rs:628-652).  The

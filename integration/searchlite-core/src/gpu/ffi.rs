@@ -88,6 +88,19 @@ pub const SLG_MAX_AGG_RANKS: u32 = 1 << 24;
     pub parent_rows: u32, pub rows: u32, pub first_id: i64, pub is_stats: u32, pub offset: u64,
 }
 #[repr(C)] #[derive(Clone, Copy, Default)] pub struct slg_agg_stats { pub count: u64, pub min: f64, pub max: f64, pub sum: f64 }
+// top_hits (TopHitsAggregation): the nodes travel beside the aggregation spec; a node's lists are lists x size hit
+// cells (segment, doc, score) and `lists` counts
+pub const SLG_MAX_TOP_HITS_NODES: usize = 4;
+pub const SLG_MAX_TOP_HITS: u32 = 64;
+pub const SLG_MAX_TOP_HITS_CELLS: u32 = 65536;
+pub const SLG_MAX_TOP_HITS_ENTRIES: u32 = 1 << 19;
+#[repr(C)] pub struct slg_top_hits_node { pub parent: i32, pub from: u32, pub size: u32, pub sort: slg_sort_spec }
+#[repr(C)] pub struct slg_top_hits_spec {
+    pub n_nodes: u32, pub max_entries: u32, pub nodes: [slg_top_hits_node; SLG_MAX_TOP_HITS_NODES],
+}
+#[repr(C)] #[derive(Clone, Copy, Default)] pub struct slg_top_hits_layout {
+    pub lists: u32, pub size: u32, pub list_offset: u32, pub hit_offset: u32,
+}
 #[repr(C)] pub struct slg_bool_spec {
     pub c_offsets: *const u32, pub c_term_ids: *const u32, pub c_group: *const u32, pub g_offsets: *const u32,
     pub g_kind: *const i32, pub q_min_should: *const u32,
@@ -276,6 +289,21 @@ extern "C" {
         aggs: *const slg_agg_spec, k: u32, strategy: c_int, out_doc: *mut u32, out_seg: *mut u32,
         out_score: *mut c_float, out_count: *mut u32, out_matched: *mut u64, counts: *mut u64,
         stats: *mut slg_agg_stats, values: *mut u64) -> c_int;
+    // top_hits: slg_batch_prepare_aggs plus the spec (aggs_or_null: null only when every node is a root); the lists
+    // of the last run: doc / seg / score [nq x hit_cells], count [nq x list_cells], status [nq] (1: the CPU path)
+    pub fn slg_batch_prepare_top_hits(index: *mut slg_index, nq: u32, q_offsets: *const u32, q_term_ids: *const u32,
+        q_weights: *const c_float, plans_or_null: *const slg_score_plans, q_filter_or_null: *const i32,
+        sort_or_null: *const slg_sort_spec, aggs_or_null: *const slg_agg_spec, top_hits: *const slg_top_hits_spec,
+        k: u32, strategy: c_int) -> *mut slg_batch;
+    pub fn slg_batch_top_hits_layout(batch: *const slg_batch, out: *mut slg_top_hits_layout) -> c_int;
+    pub fn slg_batch_fetch_top_hits(batch: *mut slg_batch, out_doc: *mut u32, out_seg: *mut u32,
+        out_score: *mut c_float, out_count: *mut u32, out_status: *mut u32) -> c_int;
+    pub fn slg_search_batch_top_hits(index: *mut slg_index, queries: *const slg_query, nq: u32,
+        plans_or_null: *const slg_score_plans, q_filter_or_null: *const i32, sort_or_null: *const slg_sort_spec,
+        aggs_or_null: *const slg_agg_spec, top_hits: *const slg_top_hits_spec, k: u32, strategy: c_int,
+        out_doc: *mut u32, out_seg: *mut u32, out_score: *mut c_float, out_count: *mut u32, out_matched: *mut u64,
+        counts: *mut u64, stats: *mut slg_agg_stats, values: *mut u64, th_doc: *mut u32, th_seg: *mut u32,
+        th_score: *mut c_float, th_count: *mut u32, th_status: *mut u32) -> c_int;
     pub fn slg_batch_matched_counts(batch: *mut slg_batch, out_matched: *mut u64) -> c_int;
     pub fn slg_search_batch_sorted(index: *mut slg_index, queries: *const slg_query, nq: u32,
         plans_or_null: *const slg_score_plans, q_filter_or_null: *const i32, sort: *const slg_sort_spec, k: u32,

@@ -765,9 +765,16 @@ pub(crate) fn gpu_eligible(
   // (SLG_AGG_FILTER: a node that names a REGISTERED filter id, so the filter must be compiled and registered at
   // staging time, slg_index_add_filter_trees) as bucket roots or children, and date_range / value_count map onto
   // range / stats nodes on the host (parse_date on the bounds; the stats count); aggs_fit_device above does not
-  // admit them yet.  Anything else (significant_terms, rare_terms, composite, extended_stats, top_hits, pipeline
-  // aggregations as NODES — they are applied on the host to the shaped buckets —, deeper trees) keeps the request
-  // on the CPU collectors.  Not with a cursor:
+  // admit them yet.  top_hits is built too (ffi::slg_batch_prepare_top_hits: the nodes travel in a
+  // slg_top_hits_spec beside the aggregation spec, at the root or under a bucket root, from + size <=
+  // ffi::SLG_MAX_TOP_HITS, numeric and `_score` sort parts; the device returns (segment, doc, score) per hit and
+  // `fields` / `highlight_field` are shaped here from the doc store, as TopHitsCollector::finish does; a query with
+  // status 1 goes back to the CPU collectors) and is not admitted by aggs_fit_device yet either.  One deviation to
+  // decide on when it is: the device keeps one list over all segments and slices it at `from` once, the reference
+  // slices every segment's list and the merged list (finish, merge_top_hits), so from > 0 agrees only when one
+  // segment holds the list's hits.  Anything else (significant_terms, rare_terms, composite, extended_stats,
+  // pipeline aggregations as NODES — they are applied on the host to the shaped buckets —, deeper trees, top_hits
+  // with a keyword sort part or from + size > 64) keeps the request on the CPU collectors.  Not with a cursor:
   // cursor batches take no aggregations.  The caller maps every segment's keyword dictionary
   // (index/fastfields.rs:711-734) to ONE dictionary per field at staging time (sorted union of the segments'
   // keys; a segment's local ordinal -> the global one) and registers the columns with

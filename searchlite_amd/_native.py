@@ -37,6 +37,10 @@ DATE_FIXED, DATE_DAY, DATE_WEEK, DATE_MONTH, DATE_QUARTER, DATE_YEAR = 0, 1, 2, 
 MAX_AGG_SCRATCH_WORDS = 1 << 19
 AGG_PCT_LDS_BYTES = 16384
 MAX_AGG_RANKS = 1 << 24
+MAX_TOP_HITS_NODES = 4
+MAX_TOP_HITS = 64
+MAX_TOP_HITS_CELLS = 65536
+MAX_TOP_HITS_ENTRIES = 1 << 19
 RESCORE_TOTAL, RESCORE_MULTIPLY, RESCORE_SUM, RESCORE_MAX, RESCORE_MIN = 0, 1, 2, 3, 4
 MAX_RESCORE_WINDOW = 1024
 BOOL_MUST, BOOL_SHOULD, BOOL_MUST_NOT = 0, 1, 2
@@ -149,6 +153,23 @@ class AggNode(C.Structure):
 class AggSpec(C.Structure):
     """slg_agg_spec: the nodes of a batch's aggregations, roots and children together."""
     _fields_ = [("n_nodes", C.c_uint32), ("nodes", AggNode * MAX_AGGS)]
+
+
+class TopHitsNode(C.Structure):
+    """slg_top_hits_node: parent = -1 (the root) or a root bucket node of the aggregation spec, the rows
+    [from, from + size) of the list, the node's sort (n_parts 0: `_score` desc)."""
+    _fields_ = [("parent", C.c_int32), ("from_", C.c_uint32), ("size", C.c_uint32), ("sort", SortSpec)]
+
+
+class TopHitsSpec(C.Structure):
+    """slg_top_hits_spec: the top_hits nodes of a batch, next to its aggregation spec; max_entries 0 = the default
+    capacity of a query's bucket runs."""
+    _fields_ = [("n_nodes", C.c_uint32), ("max_entries", C.c_uint32), ("nodes", TopHitsNode * MAX_TOP_HITS_NODES)]
+
+
+class TopHitsLayout(C.Structure):
+    """slg_top_hits_layout: a node's hits are lists x size cells at hit_offset, its counts `lists` at list_offset."""
+    _fields_ = [("lists", C.c_uint32), ("size", C.c_uint32), ("list_offset", C.c_uint32), ("hit_offset", C.c_uint32)]
 
 
 class AggLayout(C.Structure):
@@ -347,6 +368,10 @@ def load():
         "slg_batch_fetch_agg_values": (i32, [vp, vp]),
         "slg_search_batch_agg_values": (i32, [vp, vp, u32, vp, vp, vp, vp, u32, i32, vp, vp, vp, vp, vp, vp, vp, vp]),
         "slg_search_batch_aggs": (i32, [vp, vp, u32, vp, vp, vp, vp, u32, i32, vp, vp, vp, vp, vp, vp, vp]),
+        "slg_batch_prepare_top_hits": (vp, [vp, u32, vp, vp, vp, vp, vp, vp, vp, vp, u32, i32]),
+        "slg_batch_top_hits_layout": (i32, [vp, vp]),
+        "slg_batch_fetch_top_hits": (i32, [vp] * 6),
+        "slg_search_batch_top_hits": (i32, [vp, vp, u32, vp, vp, vp, vp, vp, u32, i32] + [vp] * 13),
         "slg_batch_run": (i32, [vp]),
         "slg_batch_set_stream": (i32, [vp, vp]),
         "slg_batch_sync": (i32, [vp]),

@@ -18,6 +18,14 @@ mappings onto device kinds: date_range is a range node whose bounds and `missing
 A request is the reference's `aggs` map: name -> {"type": "terms" | "histogram" | "range" | "stats" | "cardinality"
 | "percentiles" | "percentile_ranks" | "date_histogram" | "date_range" | "filter" | "value_count", "field": ..., ...,
 "aggs": {...children...}}.  Maps are walked in name order, as the reference's BTreeMaps.
+
+top_hits ({"type": "top_hits", "size", "from", "sort": [{"field", "order"}]}, at the root or as a child of a root
+bucket aggregation) travels beside the aggregation spec (slg_batch_prepare_top_hits): AggPlan.top_hits.  The device
+returns (segment, doc, score) per hit; `fields` and `snippet` of the reference's TopHit are doc-store work on the
+finished hits and are left out here.  The device keeps ONE list over all segments and reports its rows [from, from +
+size); the reference slices every segment's list at `from` and the merged list again (TopHitsCollector::finish,
+merge_top_hits), so with from > 0 and hits in more than one segment it answers differently: such a request is exact
+on the device only when one segment holds the list's hits.
 """
 from __future__ import annotations
 
@@ -276,25 +284,74 @@ STATS_DTYPE = np.dtype([("count", np.uint64), ("min", np.float64), ("max", np.fl
 class AggPlan:
     """A request's aggregations as the device takes them: .spec (N.AggSpec) and, per node in spec order,
     .nodes[i] = dict(name, type, body, parent, keys) for shape(); a date_histogram node also has date =
-    date_histogram_config(), a date_range node date_range = date_range_config(), a filter node filter = its id."""
+    date_histogram_config(), a date_range node date_range = date_range_config(), a filter node filter = its id.
+    .top_hits is the N.TopHitsSpec of the request's top_hits nodes (None without one) and .top_hits_nodes[j] =
+    dict(name, parent, from, size, sort) per node in its order, parent = -1 or the index in .nodes of its bucket
+    aggregation, sort = [(sort field id or "_score", "asc" | "desc")]."""
 
-    def __init__(self, spec: "N.AggSpec", nodes: List[dict]):
+    def __init__(self, spec: "N.AggSpec", nodes: List[dict], top_hits: Optional["N.TopHitsSpec"] = None,
+                 top_hits_nodes: Optional[List[dict]] = None):
         self.spec = spec
         self.nodes = nodes
+        self.top_hits = top_hits
+        self.top_hits_nodes = top_hits_nodes or []
 
 
-def agg_spec(aggs: Dict[str, dict], fields: Dict[str, dict]) -> AggPlan:
+def _top_hits_node(name: str, body: dict, parent: int, fields: Dict[str, dict]) -> dict:
+    """one top_hits body -> dict(name, parent, from, size, sort); ValueError for what the device does not build"""
+    if body.get("aggs"):
+        raise ValueError(f"aggregation {name!r}: a top_hits aggregation has no children")
+    if body.get("size") is None:  # (TopHitsAggregation::size has no default: the reference refuses the request)
+        raise ValueError(f"aggregation {name!r}: top_hits requires `size`")
+    size, frm = int(body["size"]), int(body.get("from") or 0)
+    if size == 0:
+        raise ValueError(f"aggregation {name!r}: top_hits size 0 is not built on the device (nothing to select)")
+    if frm < 0 or size < 0 or frm + size > N.MAX_TOP_HITS:
+        raise ValueError(f"aggregation {name!r}: top_hits from + size > {N.MAX_TOP_HITS} is not built on the device")
+    sort = []
+    for part in body.get("sort") or []:
+        field, order = (part.get("field"), part.get("order")) if isinstance(part, dict) else part
+        if order is None:  # default_order_for_field (query/sort.rs:392-398)
+            order = "desc" if field == "_score" else "asc"
+        if order not in ("asc", "desc"):
+            raise ValueError(f"aggregation {name!r}: unknown sort order {order!r}")
+        if field != "_score":
+            if field not in fields or field == FILTERS:
+                raise ValueError(f"aggregation {name!r}: sort field {field!r} is not registered")
+            if fields[field].get("sort_id") is None:
+                what = "a keyword sort part" if fields[field].get("keys") is not None else "a field without a sort column"
+                raise ValueError(f"aggregation {name!r}: {what} ({field!r}) is not built on the device")
+            field = int(fields[field]["sort_id"])
+        sort.append((field, order))
+    if len(sort) > N.MAX_SORT_PARTS:
+        raise ValueError(f"aggregation {name!r}: more than {N.MAX_SORT_PARTS} sort parts are not built on the device")
+    return {"name": name, "parent": parent, "from": frm, "size": size, "sort": sort}
+
+
+def agg_spec(aggs: Dict[str, dict], fields: Dict[str, dict], top_hits_max_entries: int = 0) -> AggPlan:
     """aggs: the request's `aggs` map; fields: field name -> {"id": agg field id, "keys": [dictionary strings]
     (keyword fields)}.  fields[FILTERS], when given, is a callable: the `filter` body of a filter aggregation ->
     the id of a registered filter that stands for it (the caller compiles and registers it, searchlite_amd.filters;
     in the spirit of compile_filter's `nested` callback); without it a filter aggregation raises ValueError.
     Roots in name order, each followed by its children in name order.  Raises ValueError for what the device does
     not build (other types, deeper nesting, sampling) — such a request stays on the CPU path — and for a
-    date_histogram request the reference refuses (validate_date_histogram_config)."""
+    date_histogram request the reference refuses (validate_date_histogram_config).
+    A top_hits aggregation names its sort fields through `fields` too: fields[name]["sort_id"] is the id of the
+    registered sort field (GpuIndex.add_sort_field); a field with "keys" and no "sort_id" is a keyword sort part,
+    which the device does not build; more than N.MAX_TOP_HITS_NODES top_hits aggregations raise ValueError too.
+    top_hits_max_entries: slg_top_hits_spec.max_entries, the bucket-run slots of one query that a top_hits child of a
+    terms, histogram, range or date_histogram aggregation may fill (the sum of its parent's counts).  The batch holds
+    8 bytes per slot and query: the default 0 is the library's 2^19 slots, 4 MB per query (4 GB for 1024 queries), so
+    a caller who knows a bound on the matched docs (times the values per doc of the parent's column) passes it; a
+    query that needs more gets status 1 and goes to the CPU path."""
     nodes: List[dict] = []
+    th_nodes: List[dict] = []
 
     def add(name, body, parent):
         typ = body.get("type")
+        if typ == "top_hits":  # (beside the spec: a child only of a root bucket aggregation, which its parent checked)
+            th_nodes.append(_top_hits_node(name, body, parent, fields))
+            return
         if typ not in KINDS:
             raise ValueError(f"aggregation {name!r}: type {typ!r} is not built on the device")
         if body.get("sampling") is not None:
@@ -371,7 +428,21 @@ def agg_spec(aggs: Dict[str, dict], fields: Dict[str, dict]) -> AggPlan:
             for r, rg in enumerate(ranges[:N.MAX_AGG_RANGES]):
                 n.from_[r] = -math.inf if rg.get("from") is None else float(rg["from"])
                 n.to[r] = math.inf if rg.get("to") is None else float(rg["to"])
-    return AggPlan(spec, nodes)
+    th_spec = None
+    if len(th_nodes) > N.MAX_TOP_HITS_NODES:
+        raise ValueError(f"more than {N.MAX_TOP_HITS_NODES} top_hits aggregations are not built on the device")
+    if th_nodes:
+        th_spec = N.TopHitsSpec()
+        th_spec.n_nodes = len(th_nodes)
+        th_spec.max_entries = int(top_hits_max_entries)
+        for j, th in enumerate(th_nodes):
+            t = th_spec.nodes[j]
+            t.parent, t.from_, t.size = th["parent"], th["from"], th["size"]
+            t.sort.n_parts = len(th["sort"])
+            for i, (field, order) in enumerate(th["sort"]):
+                t.sort.field[i] = N.SORT_SCORE if field == "_score" else field
+                t.sort.order[i] = N.ORDER_ASC if order == "asc" else N.ORDER_DESC
+    return AggPlan(spec, nodes, th_spec, th_nodes)
 
 
 def _stats(cell) -> dict:
@@ -385,9 +456,28 @@ def _bucket_key_string(key) -> str:
     return key if isinstance(key, str) else json.dumps(key)
 
 
-def shape(plan: AggPlan, layout: List[dict], tables: List[np.ndarray], q: int) -> Dict[str, dict]:
+def shape(plan: AggPlan, layout: List[dict], tables: List[np.ndarray], q: int, top_hits: Optional[dict] = None,
+          matched=None) -> Dict[str, dict]:
     """The response of query q: name -> AggregationResponse as a dict ({"type": ..., "buckets": [{"key",
-    "doc_count", "aggregations"}]} / stats).  layout: PreparedBatch.agg_layout(); tables: PreparedBatch.aggs()."""
+    "doc_count", "aggregations"}]} / stats).  layout: PreparedBatch.agg_layout(); tables: PreparedBatch.aggs().
+    top_hits: PreparedBatch.top_hits() of a plan with top_hits nodes, matched: PreparedBatch.matched_counts() (a
+    root node's total): {"type": "top_hits", "total", "hits": [{"segment", "doc", "score"}]} at the root or in the
+    bucket.  `fields` and `snippet` of a hit are doc-store work and are not part of it.  ValueError for a query
+    whose bucket runs did not fit (status 1: the CPU path)."""
+    if plan.top_hits_nodes and top_hits is not None and int(top_hits["status"][q]) != 0:
+        raise ValueError(f"query {q}: the top_hits bucket runs did not fit max_entries (CPU path)")
+
+    def hits_of(j: int, row: int, total: int) -> dict:
+        arr = top_hits["nodes"][j]
+        n = int(arr["count"][q, row])
+        return {"type": "top_hits", "total": int(total),
+                "hits": [{"segment": int(arr["seg"][q, row, i]), "doc": int(arr["doc"][q, row, i]),
+                          "score": float(arr["score"][q, row, i])} for i in range(n)]}
+
+    def top_hits_under(i: int, row: int, total: int) -> dict:
+        if top_hits is None:
+            return {}
+        return {th["name"]: hits_of(j, row, total) for j, th in enumerate(plan.top_hits_nodes) if th["parent"] == i}
 
     def node(i: int, prow: int) -> dict:
         nd, body, tab = plan.nodes[i], plan.nodes[i]["body"], tables[i][q, prow]
@@ -411,13 +501,17 @@ def shape(plan: AggPlan, layout: List[dict], tables: List[np.ndarray], q: int) -
 
         def bucket(key, row: Optional[int], count: int) -> dict:
             b = {"key": key, "doc_count": int(count)}
-            if row is not None and children:
-                b["aggregations"] = {plan.nodes[c]["name"]: node(c, row) for c in children}
+            if row is not None:
+                kids = {plan.nodes[c]["name"]: node(c, row) for c in children}
+                kids.update(top_hits_under(i, row, count))
+                if kids:
+                    b["aggregations"] = kids
             return b
 
         if nd["type"] == "filter":  # :2707-2726: the one bucket's children are the response's
-            return {"type": "filter", "doc_count": int(tab[0]),
-                    "aggregations": {plan.nodes[c]["name"]: node(c, 0) for c in children}}
+            kids = {plan.nodes[c]["name"]: node(c, 0) for c in children}
+            kids.update(top_hits_under(i, 0, int(tab[0])))
+            return {"type": "filter", "doc_count": int(tab[0]), "aggregations": kids}
         if nd["type"] == "date_histogram":  # DateHistogramCollector::finish, :1364-1403
             dh = nd["date"]
             unit, step, offset = dh["unit"], dh["step"], dh["offset"]
@@ -477,4 +571,9 @@ def shape(plan: AggPlan, layout: List[dict], tables: List[np.ndarray], q: int) -
             out.append(bucket(key, r, int(tab[r])))
         return {"type": "range", "buckets": out, "keyed": bool(body.get("keyed", False))}
 
-    return {plan.nodes[i]["name"]: node(i, 0) for i in range(len(plan.nodes)) if plan.nodes[i]["parent"] < 0}
+    out = {plan.nodes[i]["name"]: node(i, 0) for i in range(len(plan.nodes)) if plan.nodes[i]["parent"] < 0}
+    if top_hits is not None and any(th["parent"] < 0 for th in plan.top_hits_nodes):
+        if matched is None:
+            raise ValueError("a root top_hits node needs `matched` (its total)")
+        out.update(top_hits_under(-1, 0, int(matched[q])))
+    return out

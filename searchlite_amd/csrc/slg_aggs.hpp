@@ -98,6 +98,8 @@ __device__ __forceinline__ unsigned long long agg_f64_key(double x) {
 // CONVERGED: f(ok, seg, doc) runs for ALL lanes of a wave together (ok false: no candidate, a dropped one, a
 // tombstone or a doc the filter rejects), so that f may use wave-wide operations; else f runs for the accepted
 // candidates only (ok is true).
+// (It has a twin: top_hits_walk in slg_tophits.hpp is the CONVERGED form with the candidate's score, slice and position
+// in the callback.  What changes here — the slices of a query, the tombstone and filter test — changes there too.)
 template <bool CONVERGED, typename P, typename F>
 __device__ __forceinline__ void agg_walk(const P &p, const QueryRef &qr, const uint32_t flt, const uint32_t wave,
                                          const uint32_t lane, F &&f) {

@@ -147,7 +147,7 @@ void slghost::release_batch_buffers(slg_batch *b, bool to_pool) {
                     &b->d_hy_keys, &b->d_hy_work, &b->d_agg_desc, &b->d_agg_counts, &b->d_agg_stats,
                     &b->d_agg_values, &b->d_agg_scratch,
                     &b->d_rs_desc, &b->d_rs_side, &b->d_bool_desc, &b->d_phrase_desc, &b->d_booltree_desc, &b->d_fscore_desc, &b->d_script_desc,
-                    &b->d_cl_desc, &b->d_cl_side};
+                    &b->d_cl_desc, &b->d_cl_side, &b->d_th_desc, &b->d_th_out, &b->d_th_entries, &b->d_th_cursors};
   for (DevBuf *d : bufs) {
     if (!to_pool) d->pool = nullptr;
     d->release();
@@ -207,6 +207,7 @@ slg_batch *slghost::prepare_impl(const PrepareRequest &r) {
       slgplan::check_script(r.script.spec, nq, script_shape);
     }
     if (r.collapse.on) slgplan::check_collapse(r.collapse.spec, k);
+    if (r.top_hits.on) slgplan::check_top_hits(r.top_hits.spec, r.aggs.spec);
     SLG_REQUIRE(ix != nullptr, "index is NULL");
     SLG_REQUIRE(!after || q_cursor != nullptr, "q_cursor is NULL");
     if (sort) {  // (checked before planning: the planner never sees a sort spec it cannot run)
@@ -243,7 +244,7 @@ slg_batch *slghost::prepare_impl(const PrepareRequest &r) {
     in.strategy = r.strategy;
     in.filter_live = filter_live.data();
     in.n_filters = filter_live.size();
-    in.sorted = sort != nullptr || after || hybrid || r.aggs.on || r.boolean.on || r.booltree.on || r.fscore.on || r.script.on;
+    in.sorted = sort != nullptr || after || hybrid || r.aggs.on || r.top_hits.on || r.boolean.on || r.booltree.on || r.fscore.on || r.script.on;
     SortBinding sorting;  // the columns of the sort parts in the batch's state
     if (sort) sorting = bind_sort(*snap, *sort, "", "part ");
     // the cursors as the key words the select kernel compares (against the same snapshot's field kinds)
@@ -368,7 +369,7 @@ slg_batch *slghost::prepare_impl(const PrepareRequest &r) {
       SLG_HIP(hipMemcpy(b->d_sort_cols.p, sorting.cols.data(), sorting.cols.size() * sizeof(slg::SortColDev),
                         hipMemcpyHostToDevice));
     }
-    if (b->sorted || b->after || r.aggs.on) b->d_matched.alloc_pooled(&ix->pool, (size_t)std::max<uint32_t>(nq, 1) * 8);
+    if (b->sorted || b->after || r.aggs.on || r.top_hits.on) b->d_matched.alloc_pooled(&ix->pool, (size_t)std::max<uint32_t>(nq, 1) * 8);
     if (b->after) {
       b->d_cursor.alloc_pooled(&ix->pool, cursor_words.size() * 4);
       SLG_HIP(hipMemcpy(b->d_cursor.p, cursor_words.data(), cursor_words.size() * 4, hipMemcpyHostToDevice));
@@ -397,6 +398,7 @@ slg_batch *slghost::prepare_impl(const PrepareRequest &r) {
     b->d_out_score = R.score(b->d_out.as<uint32_t>());
     b->d_out_count = R.count(b->d_out.as<uint32_t>());
     if (r.aggs.on) agg_attach(b, *r.aggs.spec);
+    if (r.top_hits.on) top_hits_attach(b, *r.top_hits.spec);
     if (r.rescore.on) rescore_attach(b, rescore_plan);
     if (r.phrase.on) {
       bool_attach(b, phrase_plan.bools);
@@ -580,6 +582,7 @@ int slg_batch_run(slg_batch *b) {
       SLG_HIP(hipMemsetAsync(b->d_out_count, 0, ((size_t)b->nq + 1) * 4, st));  // (k = 0, or a scan without a slice: no row)
     }
     if (b->aggs) agg_launch(b, st);  // (after the select: the tables of every accepted candidate)
+    if (b->top_hits) top_hits_launch(b, st);  // (behind agg_kernel: the parents' count rows are read)
     if (b->rescore) rescore_launch(b, st);  // (behind the rows: the first w of every query are scored again)
     if (b->collapse) collapse_launch(b, st);  // (behind the rows: they are read, never written)
   });
@@ -774,6 +777,8 @@ struct HostOut {
   float *first_score = nullptr, *rescore_score = nullptr;  // (a rescore batch)
   uint32_t *rescored = nullptr;
   void *const *collapse = nullptr;  // (a collapse batch) the 14 arrays of slg_batch_fetch_collapse, in its order
+  uint32_t *th_doc = nullptr, *th_seg = nullptr, *th_count = nullptr, *th_status = nullptr;  // (a top_hits batch)
+  float *th_score = nullptr;
 };
 // A prepared batch (null: prepare failed and set the thread's error) run to the caller's host arrays and
 // destroyed: the first error is the one reported
@@ -784,6 +789,7 @@ int run_to_host(slg_batch *b, const HostOut &o) {
   if (rc == SLG_OK && o.matched) rc = slg_batch_matched_counts(b, o.matched);
   if (rc == SLG_OK && b->aggs) rc = slg_batch_fetch_aggs(b, o.agg_counts, o.agg_stats);
   if (rc == SLG_OK && b->aggs && b->agg_value_nodes) rc = slg_batch_fetch_agg_values(b, o.agg_values);
+  if (rc == SLG_OK && b->top_hits) rc = slg_batch_fetch_top_hits(b, o.th_doc, o.th_seg, o.th_score, o.th_count, o.th_status);
   if (rc == SLG_OK && b->rescore) rc = slg_batch_fetch_rescore(b, o.first_score, o.rescore_score, o.rescored);
   if (rc == SLG_OK && o.seen) rc = slg_batch_cursor_seen(b, o.seen);
   if (rc == SLG_OK && b->collapse) {
@@ -823,7 +829,7 @@ int slg_batch_matched_counts(slg_batch *b, uint64_t *out_matched) {
   return guarded([&] {
     SLG_REQUIRE_LIVE(b);
     if (b->hybrid) throw SlgError(SLG_ERR_UNSUPPORTED, "a hybrid batch has no matched counts");
-    SLG_REQUIRE(b->sorted || b->after || b->aggs || b->scan,
+    SLG_REQUIRE(b->sorted || b->after || b->aggs || b->scan || b->top_hits,
                 "not a sorted, cursor, aggregation or scan batch (slg_batch_prepare_sorted / _after / _aggs / _scan)");
     SLG_REQUIRE(b->launched, "the batch has not run");
     SLG_REQUIRE(b->nq == 0 || out_matched != nullptr, "out_matched is NULL");
@@ -882,6 +888,38 @@ int slg_search_batch_aggs(slg_index *ix, const slg_query *queries, uint32_t nq, 
   if (rc != SLG_OK) return rc;
   return slg_search_batch_agg_values(ix, queries, nq, plans, q_filter, sort, aggs, k, strategy, out_doc, out_seg,
                                      out_score, out_count, out_matched, counts, stats, nullptr);
+}
+
+slg_batch *slg_batch_prepare_top_hits(slg_index *ix, uint32_t nq, const uint32_t *q_offsets, const uint32_t *q_term_ids,
+                                      const float *q_weights, const slg_score_plans *plans, const int32_t *q_filter,
+                                      const slg_sort_spec *sort, const slg_agg_spec *aggs,
+                                      const slg_top_hits_spec *top_hits, uint32_t k, int strategy) {
+  PrepareRequest r{ix, nq, q_offsets, q_term_ids, q_weights, plans, q_filter, k, strategy};
+  r.sort = if_given(sort);
+  r.aggs = if_given(aggs);
+  r.top_hits = {true, top_hits};
+  return prepare_impl(r);
+}
+
+int slg_search_batch_top_hits(slg_index *ix, const slg_query *queries, uint32_t nq, const slg_score_plans *plans,
+                              const int32_t *q_filter, const slg_sort_spec *sort, const slg_agg_spec *aggs,
+                              const slg_top_hits_spec *top_hits, uint32_t k, int strategy, uint32_t *out_doc,
+                              uint32_t *out_seg, float *out_score, uint32_t *out_count, uint64_t *out_matched,
+                              uint64_t *counts, slg_agg_stats *stats, uint64_t *values, uint32_t *th_doc,
+                              uint32_t *th_seg, float *th_score, uint32_t *th_count, uint32_t *th_status) {
+  FlatQueries fq;
+  const int rc = flatten_queries(ix, queries, nq, &fq);
+  if (rc != SLG_OK) return rc;
+  HostOut o{out_doc, out_seg, out_score, out_count, nullptr, out_matched, nullptr, counts, stats};
+  o.agg_values = values;
+  o.th_doc = th_doc;
+  o.th_seg = th_seg;
+  o.th_score = th_score;
+  o.th_count = th_count;
+  o.th_status = th_status;
+  return run_to_host(slg_batch_prepare_top_hits(ix, nq, fq.offs.data(), fq.tids.data(), fq.ws.data(), plans, q_filter,
+                                                sort, aggs, top_hits, k, strategy),
+                     o);
 }
 
 slg_batch *slg_batch_prepare_rescore(slg_index *ix, uint32_t nq, const uint32_t *q_offsets, const uint32_t *q_term_ids,

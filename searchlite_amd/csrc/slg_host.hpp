@@ -1,5 +1,5 @@
 // slg_host.hpp — what the host translation units of the C ABI share (slg_index.hip, slg_batch.hip,
-// slg_shard.hip, slg_rerank.hip, slg_vsearch.hip, slg_hybrid.hip, slg_aggs.hip, slg_rescore.hip, slg_bool.hip, slg_booltree.hip, slg_phrase.hip, slg_fscore.hip, slg_script.hip, slg_scan.hip, slg_collapse.hip): the error plumbing, device memory, the host
+// slg_shard.hip, slg_rerank.hip, slg_vsearch.hip, slg_hybrid.hip, slg_aggs.hip, slg_rescore.hip, slg_bool.hip, slg_booltree.hip, slg_phrase.hip, slg_fscore.hip, slg_script.hip, slg_scan.hip, slg_collapse.hip, slg_tophits.hip): the error plumbing, device memory, the host
 // structures behind the opaque handles and the small helpers several entry points use.  Private: not
 // installed, not part of include/.  No kernel header is included here — each unit includes the one
 // whose kernels it launches (slg_stage.hpp, slg_kernels.hpp, slg_rerank.hpp, slg_vsearch.hpp, slg_hybrid.hpp; the shard
@@ -603,6 +603,18 @@ struct slg_batch {
   uint32_t cl_parts = 0, cl_score_parts = 0, cl_desc_parts = 0;  // the inner sort (0 parts: the batch's own order)
   DevBuf d_cl_desc;  // slg::ColumnDev[n_segs], then slg::SortColDev[kSortMaxParts * n_segs] of the inner sort
   DevBuf d_cl_side;  // the arrays of slg_batch_fetch_collapse, back to back in its argument order
+  // top_hits batch (slg_batch_prepare_top_hits): an aggregation batch, or a plain / sorted one planned as such;
+  // top_hits_kernel runs behind agg_kernel and fills the lists from the candidates (slg_tophits.hip)
+  bool top_hits = false;
+  slg_top_hits_spec th_spec{};
+  std::vector<slg_top_hits_layout> th_layout;  // [n_nodes]
+  uint32_t th_hit_cells = 0, th_list_cells = 0;  // of one query
+  uint32_t th_max_entries = 0;                   // run slots of one query
+  uint32_t th_cursor_words = 0, th_lds_cursors = 0;  // cursors of one query in device memory / in LDS
+  bool th_ext = false;  // a date_histogram or filter parent: the instantiation that holds those paths
+  DevBuf d_th_desc;     // slg::TopHitsNodeDev[n_nodes], then slg::SortColDev[n_nodes][kSortMaxParts * n_segs]
+  DevBuf d_th_out;      // doc | seg | score [nq * hit_cells], count [nq * list_cells], status [nq], the error word
+  DevBuf d_th_entries, d_th_cursors;  // uint2[nq * max_entries], u32[nq * cursor_words]
 };
 
 namespace slghost __attribute__((visibility("hidden"))) {
@@ -726,6 +738,7 @@ struct PrepareRequest {
   Asked<slg_script_spec> script;  // slg_batch_prepare_script (with fscore: the two stages, in script_order)
   int script_order = 0;           // SLG_SCRIPT_OUTER / _INNER
   Asked<slg_collapse_spec> collapse;
+  Asked<slg_top_hits_spec> top_hits;  // slg_batch_prepare_top_hits (aggs: on when its spec is given)
 };
 // a spec that is a kind of its own only when it is given (the sort of a bool, phrase, cursor or agg batch)
 template <typename T>
@@ -848,6 +861,11 @@ void scan_launch(slg_batch *b, hipStream_t st);
 // and side arrays onto the device (throws; the batch is otherwise prepared); the launch behind the batch's rows
 void collapse_attach(slg_batch *b, const slg_collapse_spec &spec, const slg_sort_spec *batch_sort);
 void collapse_launch(slg_batch *b, hipStream_t st);
+// slg_tophits.hip: the spec against the batch's state (the nodes' sort columns, the parents' rows), the tables,
+// output arrays and run scratch onto the device (throws; the batch is otherwise prepared, agg_attach has run); the
+// launch behind agg_kernel (without an aggregation spec: behind the select)
+void top_hits_attach(slg_batch *b, const slg_top_hits_spec &spec);
+void top_hits_launch(slg_batch *b, hipStream_t st);
 
 // slg_vsearch.hip: one vector search or hybrid call, checked against one state of the index ...
 struct VsCall {

@@ -1275,6 +1275,44 @@ void check_collapse(const slg_collapse_spec *spec, uint32_t k) {
     throw SlgError(SLG_ERR_UNSUPPORTED, "more than SLG_MAX_SORT_PARTS inner sort parts");
 }
 
+// ---- top_hits ------------------------------------------------------------------------------------------
+void check_top_hits(const slg_top_hits_spec *spec, const slg_agg_spec *aggs) {
+  PLAN_REQUIRE(spec != nullptr, "top_hits spec is NULL");
+  PLAN_REQUIRE(spec->n_nodes >= 1, "a top_hits spec needs at least one node");
+  const uint32_t nn = std::min<uint32_t>(spec->n_nodes, SLG_MAX_TOP_HITS_NODES);
+  auto name = [](uint32_t i) { return "top_hits node " + std::to_string(i); };
+  for (uint32_t i = 0; i < nn; i++) {
+    const slg_top_hits_node &n = spec->nodes[i];
+    if (n.parent != -1) {
+      PLAN_REQUIRE(aggs != nullptr, name(i) + ": a child node needs an aggregation spec");
+      PLAN_REQUIRE(n.parent >= 0 && (uint32_t)n.parent < aggs->n_nodes && (uint32_t)n.parent < SLG_MAX_AGGS,
+                   name(i) + ": parent is not a node of the aggregation spec");
+      const int32_t kind = aggs->nodes[n.parent].kind;
+      PLAN_REQUIRE(kind == SLG_AGG_TERMS || kind == SLG_AGG_HISTOGRAM || kind == SLG_AGG_RANGE ||
+                       kind == SLG_AGG_DATE_HISTOGRAM || kind == SLG_AGG_FILTER,
+                   name(i) + ": parent is not a bucket node (terms, histogram, range, date_histogram, filter)");
+    }
+    for (uint32_t j = 0; j < std::min<uint32_t>(n.sort.n_parts, SLG_MAX_SORT_PARTS); j++) {
+      PLAN_REQUIRE(n.sort.order[j] == SLG_ORDER_ASC || n.sort.order[j] == SLG_ORDER_DESC,
+                   name(i) + ": unknown sort order in part " + std::to_string(j));
+      PLAN_REQUIRE(n.sort.field[j] >= 0 || n.sort.field[j] == SLG_SORT_SCORE,
+                   name(i) + ": unknown sort field id in part " + std::to_string(j));
+    }
+  }
+  if (spec->n_nodes > SLG_MAX_TOP_HITS_NODES)
+    throw SlgError(SLG_ERR_UNSUPPORTED, "more than SLG_MAX_TOP_HITS_NODES top_hits nodes");
+  for (uint32_t i = 0; i < nn; i++) {
+    const slg_top_hits_node &n = spec->nodes[i];
+    if (n.size == 0) throw SlgError(SLG_ERR_UNSUPPORTED, name(i) + ": size is 0 (nothing to select: CPU path)");
+    if ((uint64_t)n.from + n.size > SLG_MAX_TOP_HITS)
+      throw SlgError(SLG_ERR_UNSUPPORTED, name(i) + ": from + size > SLG_MAX_TOP_HITS (CPU path)");
+    if (n.sort.n_parts > SLG_MAX_SORT_PARTS)
+      throw SlgError(SLG_ERR_UNSUPPORTED, name(i) + ": more than SLG_MAX_SORT_PARTS sort parts");
+    if (n.parent != -1 && aggs->nodes[n.parent].parent != -1)
+      throw SlgError(SLG_ERR_UNSUPPORTED, name(i) + ": parent is itself a child (a third level: CPU path)");
+  }
+}
+
 void check_fscore(const slg_fscore_spec *spec, uint32_t nq) {
   PLAN_REQUIRE(spec != nullptr, "fscore spec is NULL");
   if (nq == 0) return;

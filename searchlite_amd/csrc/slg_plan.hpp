@@ -134,6 +134,13 @@ void plan_rescore(const std::vector<SegView> &segs, uint32_t nq, uint32_t k, con
 // reported first); k > SLG_MAX_COLLAPSE_ROWS, inner_from + inner_size > SLG_MAX_INNER_HITS with inner hits
 // asked for, more than SLG_MAX_SORT_PARTS inner parts (SLG_ERR_UNSUPPORTED).
 void check_collapse(const slg_collapse_spec *spec, uint32_t k);
+// The checks of a top_hits spec that need no index (slg_batch_prepare_top_hits), against the aggregation spec it
+// travels with (null: none; agg_check_spec has passed it).  Throws SlgError: spec NULL, n_nodes == 0, a parent
+// that is neither -1 nor a bucket node of aggs, aggs NULL with a child node, a part with an unknown order or a
+// negative field other than SLG_SORT_SCORE (SLG_ERR_INVALID, reported first); n_nodes > SLG_MAX_TOP_HITS_NODES,
+// size == 0, from + size > SLG_MAX_TOP_HITS, more than SLG_MAX_SORT_PARTS parts, a parent that is itself a child
+// (SLG_ERR_UNSUPPORTED).
+void check_top_hits(const slg_top_hits_spec *spec, const slg_agg_spec *aggs);
 
 // ---- boolean queries (slg_batch_prepare_bool) ----
 // The checks of a bool spec that need no index (throws SlgError): a NULL spec or array, offsets that decrease,

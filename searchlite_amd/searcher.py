@@ -458,6 +458,25 @@ class GpuIndex:
         finally:
             b.close()
 
+    def search_top_hits(self, q_offsets, q_terms, q_weights, k: int, aggs, sort=None, strategy: int = Wand,
+                        q_filter=None, top_hits=None, **plans):
+        """Batch search with top_hits aggregations (slg_batch_prepare_top_hits).  aggs: an aggs.AggPlan with
+        top_hits nodes, or an N.AggSpec / None with top_hits an N.TopHitsSpec; sort: None = score order.
+        -> (doc, seg, score, count, matched, tables, layout, hits): as search_aggs (tables and layout empty
+        without an aggregation node), and the dict of PreparedBatch.top_hits.  A child of a terms, histogram, range
+        or date_histogram aggregation costs 8 bytes x max_entries of run scratch per query, 4 MB at the default: set
+        it through aggs.agg_spec(..., top_hits_max_entries=n) or N.TopHitsSpec.max_entries.  `fields` and `snippet` of the
+        reference's hits are doc-store work and stay with the caller."""
+        b = self.prepare(q_offsets, q_terms, q_weights, k, strategy, q_filter, sort=sort, aggs=aggs,
+                         top_hits=top_hits, **plans)
+        try:
+            b.run()
+            has = b.agg_spec is not None
+            return b.fetch() + (b.matched_counts(), b.aggs() if has else [], b.agg_layout() if has else [],
+                                b.top_hits())
+        finally:
+            b.close()
+
     def search_rescore(self, q_offsets, q_terms, q_weights, k: int, rescore, strategy: int = Wand, q_filter=None,
                        **plans):
         """Batch search with a query rescore (slg_batch_prepare_rescore).  rescore: a dict with q_offsets, q_terms
@@ -595,7 +614,7 @@ class GpuIndex:
                 group_tie=None, q_node_offsets=None, node_kind=None, node_tie=None, node_parent=None,
                 q_min_match=None, sort=None, cursors=None, hybrid=False, aggs=None,
                 rescore=None, clauses=None, phrases=None, fscore=None, collapse=None,
-                clause_tree=None, script=None, script_order="outer") -> "PreparedBatch":
+                clause_tree=None, script=None, script_order="outer", top_hits=None) -> "PreparedBatch":
         """q_leaf / q_plan / q_tie / q_nleaves: score plans; leaf_group / group_plan / group_tie with
         their per-query offsets: two-level plans; q_node_offsets / node_kind / node_tie / node_parent:
         trees of any shape, node by node in pre-order (slg_batch_prepare_plans, slg_score_plans);
@@ -613,12 +632,14 @@ class GpuIndex:
         slg_batch_prepare_bool_tree (score order, or with sort); script: one script_score per query, the list of
         script.script_spec() (or its result) -> slg_batch_prepare_script (score order, or with sort), alone or with
         fscore as its second stage: script_order "outer" is script_score{query: function_score}, "inner" is
-        function_score{query: script_score}."""
+        function_score{query: script_score}; top_hits: an N.TopHitsSpec (an aggs.AggPlan passed as aggs brings its
+        own) -> slg_batch_prepare_top_hits (score order or with sort, with aggs or without;
+        PreparedBatch.top_hits)."""
         return PreparedBatch(self, q_offsets, q_terms, q_weights, k, strategy, q_filter,
                              q_leaf, q_plan, q_tie, q_nleaves, q_leaf_offsets, leaf_group,
                              q_group_offsets, group_plan, group_tie, q_node_offsets, node_kind, node_tie, node_parent,
                              q_min_match, sort, cursors, hybrid, aggs, rescore, clauses, phrases, fscore, collapse,
-                             clause_tree, script, script_order)
+                             clause_tree, script, script_order, top_hits)
 
     def search_collapse(self, q_offsets, q_terms, q_weights, k: int, collapse, sort=None, cursors=None,
                         strategy: int = Wand, q_filter=None, **plans):
@@ -1147,7 +1168,8 @@ class PreparedBatch:
                  q_leaf_offsets=None, leaf_group=None, q_group_offsets=None, group_plan=None,
                  group_tie=None, q_node_offsets=None, node_kind=None, node_tie=None, node_parent=None,
                  q_min_match=None, sort=None, cursors=None, hybrid=False, aggs=None, rescore=None, clauses=None,
-                 phrases=None, fscore=None, collapse=None, clause_tree=None, script=None, script_order="outer"):
+                 phrases=None, fscore=None, collapse=None, clause_tree=None, script=None, script_order="outer",
+                 top_hits=None):
         self.index = index
         self._lib = index._lib
         q_offsets = np.ascontiguousarray(q_offsets, dtype=np.uint32)
@@ -1187,7 +1209,23 @@ class PreparedBatch:
         self.is_collapse = collapse is not None
         self.is_bool_tree = clause_tree is not None
         self.is_script = script is not None
-        if script is not None:
+        # (an aggs.AggPlan carries its N.TopHitsSpec; a plan of top_hits roots alone has no aggregation node)
+        self.top_hits_spec = getattr(aggs, "top_hits", None) if top_hits is None else top_hits
+        if self.top_hits_spec is not None and self.agg_spec is not None and int(self.agg_spec.n_nodes) == 0:
+            self.agg_spec = None
+        if self.top_hits_spec is not None and (hybrid or cursors is not None or rescore is not None or
+                                               clauses is not None or phrases is not None or fscore is not None or
+                                               collapse is not None or clause_tree is not None or script is not None):
+            # (the library's other prepare calls take no top_hits spec: the refusal is made here with its code)
+            raise N.SlgError(N.ERR_UNSUPPORTED, "top_hits is built on plain, sorted and aggregation batches only")
+        if self.top_hits_spec is not None:
+            spec = None if sort is None else sort_spec(sort)
+            self._h = self._lib.slg_batch_prepare_top_hits(
+                index._h, self.nq, _ptr(q_offsets), _ptr(q_terms), _ptr(q_weights), C.addressof(plans),
+                opt(qf), None if spec is None else C.addressof(spec),
+                None if self.agg_spec is None else C.addressof(self.agg_spec), C.addressof(self.top_hits_spec),
+                k, strategy)
+        elif script is not None:
             # (the library's other prepare calls take no script spec: the refusal is made here with its code)
             if hybrid or cursors is not None or aggs is not None or rescore is not None or clauses is not None or \
                     phrases is not None or collapse is not None or clause_tree is not None:
@@ -1357,6 +1395,34 @@ class PreparedBatch:
             n = x["parent_rows"] * x["rows"]
             out.append(flat[:, x["offset"]:x["offset"] + n].reshape(self.nq, x["parent_rows"], x["rows"]).copy())
         return out
+
+    def top_hits_layout(self) -> list:
+        """slg_batch_top_hits_layout: per top_hits node dict(lists, size, list_offset, hit_offset)."""
+        n = int(self.top_hits_spec.n_nodes)
+        lay = (N.TopHitsLayout * n)()
+        N.check(self._lib.slg_batch_top_hits_layout(self._h, lay))
+        return [dict(lists=int(x.lists), size=int(x.size), list_offset=int(x.list_offset),
+                     hit_offset=int(x.hit_offset)) for x in lay]
+
+    def top_hits(self) -> dict:
+        """The lists of a top_hits batch's last run (slg_batch_fetch_top_hits; waits): status [nq] (1: the query's
+        bucket runs did not fit max_entries, its lists are all zero: the CPU path), and nodes = per top_hits node
+        dict(doc, seg, score [nq, lists, size], count [nq, lists]); zeros past the counts."""
+        lay = self.top_hits_layout()
+        hc = sum(x["lists"] * x["size"] for x in lay)
+        lc = sum(x["lists"] for x in lay)
+        nq = max(self.nq, 1)
+        doc, seg = np.zeros((nq, hc), dtype=np.uint32), np.zeros((nq, hc), dtype=np.uint32)
+        score, count = np.zeros((nq, hc), dtype=np.float32), np.zeros((nq, lc), dtype=np.uint32)
+        status = np.zeros(nq, dtype=np.uint32)
+        N.check(self._lib.slg_batch_fetch_top_hits(self._h, _ptr(doc), _ptr(seg), _ptr(score), _ptr(count), _ptr(status)))
+        nodes = []
+        for x in lay:
+            h0, h1 = x["hit_offset"], x["hit_offset"] + x["lists"] * x["size"]
+            cut = lambda a: a[:self.nq, h0:h1].reshape(self.nq, x["lists"], x["size"]).copy()
+            nodes.append(dict(doc=cut(doc), seg=cut(seg), score=cut(score),
+                              count=count[:self.nq, x["list_offset"]:x["list_offset"] + x["lists"]].copy()))
+        return dict(status=status[:self.nq], nodes=nodes)
 
     def rescore_details(self):
         """Per row of a rescore batch's last run (slg_batch_fetch_rescore; waits): (first_score [nq, k], the
@@ -1551,6 +1617,9 @@ class ScanBatch(PreparedBatch):
         self.after = False
         self.is_hybrid = False
         self.is_scan = True
+        if getattr(aggs, "top_hits", None) is not None:
+            # (slg_batch_prepare_scan takes no top_hits spec: refused here with the library's code, nothing dropped)
+            raise N.SlgError(N.ERR_UNSUPPORTED, "top_hits is not built on scan batches")
         self.agg_spec = getattr(aggs, "spec", aggs)  # (an aggs.AggPlan carries its N.AggSpec)
         spec = None if sort is None else sort_spec(sort)
         self._h = self._lib.slg_batch_prepare_scan(

@@ -815,7 +815,8 @@ slg_batch *slg_batch_prepare_aggs(slg_index *index, uint32_t nq, const uint32_t 
  * over the stats nodes; tables lie in node order. */
 int slg_batch_agg_layout(const slg_batch *batch, slg_agg_layout *out);
 /* The tables of the batch's last run: counts [nq x count_cells], stats [nq x stats_cells] (either may be
- * NULL when it has no cells); waits for the batch. */
+ * NULL when it has no cells); waits for the batch.  A composite batch (slg_batch_prepare_composite) has the
+ * composite's cells behind the spec's in every query's row: see slg_batch_composite_layout. */
 int slg_batch_fetch_aggs(slg_batch *batch, uint64_t *counts, slg_agg_stats *stats);
 /* The value tables of the batch's last run: values [nq x value_cells], value_cells = the sum of parent_rows * rows
  * over the value nodes (is_stats == 2), in node order; waits for the batch.  Counts, n and the percentile cells
@@ -916,6 +917,92 @@ int slg_search_batch_top_hits(slg_index *index, const slg_query *queries, uint32
                               uint32_t *out_seg, float *out_score, uint32_t *out_count, uint64_t *out_matched,
                               uint64_t *counts, slg_agg_stats *stats, uint64_t *values, uint32_t *th_doc,
                               uint32_t *th_seg, float *th_score, uint32_t *th_count, uint32_t *th_status);
+
+/* ---- composite aggregation: ordered key tuples, paged -----------------------------------------------
+ * CompositeAggregation (api/types.rs:694-718; CompositeCollector and finalize_composite, query/aggs/mod.rs:
+ * 1689-1842, 3264-3368): the bucket space is the cross product of the sources' key spaces, and a request returns
+ * the `size` smallest tuples above `after`.  A source is a keyword column (terms: the dictionary string, in UTF-8
+ * byte order) or an f64 column (histogram: floor(v / interval) * interval in IEEE f64, identity by bits, order
+ * total_cmp, so -0.0 and 0.0 are two buckets).  A doc without a value in any one source is skipped; otherwise it
+ * is counted once in every distinct tuple of its values.  Segments merge by key without truncation, so the device's
+ * all-segment counts are the reference's.
+ *
+ * Packed key: a tuple is ONE u64, source 0 in the most significant bits; part i is a slot number < slots[i] in
+ * bits[i] = ceil_log2(slots[i]) bits at `shift`.  A terms slot is ord_rank[ord].  Histogram slots run over the ids
+ * floor(vmin / interval) .. floor(vmax / interval) of the column's recorded finite minimum and maximum, with ONE
+ * extra slot for -0.0 when id 0 is in the range: zero_slot is the slot of -0.0 (= -first_id), the slot of id 0
+ * (+0.0) is zero_slot + 1, and every positive id is shifted by one.  A column without a value has one slot that is
+ * never emitted.  Integer order of the key is the reference's tuple order; key_bits <= 63, ~0 is the empty marker.
+ *
+ * slg_batch_prepare_composite is slg_batch_prepare_aggs plus the spec (aggs_or_null may be NULL).  Rows, matched
+ * counts and every table of aggs_or_null are bit-identical to the same batch without the composite.  The composite's
+ * `size` count cells, then its children's tables (parent_rows = size), lie behind the cells of aggs_or_null in the
+ * arrays of slg_batch_fetch_aggs: a query's count row is count_cells(aggs) + composite count cells wide, its stats
+ * row likewise.  Checked before the index is looked at (after the aggregation spec's own checks): spec NULL,
+ * n_sources == 0, an unknown source kind, a non-positive or non-finite interval, a child that slg_batch_prepare_aggs
+ * would reject as a root: SLG_ERR_INVALID; n_sources > SLG_MAX_COMPOSITE_SOURCES, size == 0 (the response is empty:
+ * the caller answers it), size > SLG_MAX_COMPOSITE_SIZE, n_children > SLG_MAX_AGGS, a cardinality, percentiles or
+ * percentile_ranks child: SLG_ERR_UNSUPPORTED.  Against the index: an unknown field, a field without a column for
+ * every segment, a field of the wrong kind for its source, an ord_rank that is not a permutation of [0, n_ords):
+ * SLG_ERR_INVALID; a histogram column with a non-finite value, one registered with slg_index_add_agg_field_i64 (the
+ * reference reads f64 columns only and skips every doc: the caller answers the empty response), one with an id at or
+ * beyond +-2^31, key_bits > 63, size x (1 + child cells) plus the cells of aggs_or_null over SLG_MAX_AGG_CELLS:
+ * SLG_ERR_UNSUPPORTED.  Memory per batch: nq x 8 B x (size + 1) keys, the table cells, 4 B per ordinal of a ranked
+ * terms source.  Not built (the CPU path): composite on scan, cursor, hybrid, vector-only, bool, phrase, sharded
+ * (slg_batch_run_sharded* refuses the batch) or coalesced batches; top_hits or value nodes under a composite;
+ * `sampling`; more than one composite per request; a composite below another aggregation; `missing`, `offset` or
+ * bounds on a source (the reference has none). */
+#define SLG_MAX_COMPOSITE_SOURCES 4u
+#define SLG_MAX_COMPOSITE_SIZE 1024u
+enum { SLG_COMPOSITE_TERMS = 0, SLG_COMPOSITE_HISTOGRAM = 1 };
+typedef struct {
+  uint32_t kind;   /* SLG_COMPOSITE_* */
+  int32_t field;   /* a registered aggregation column */
+  double interval; /* histogram */
+  const uint32_t *ord_rank; /* terms: [n_ords] permutation, the rank of each ordinal's key in byte order;
+                               NULL = the ordinals already are in key order */
+} slg_composite_source;
+typedef struct {
+  uint32_t n_sources, size;
+  slg_composite_source sources[SLG_MAX_COMPOSITE_SOURCES];
+  uint32_t n_children;
+  slg_agg_node children[SLG_MAX_AGGS]; /* parent is not read: every child is a child of the composite */
+} slg_composite_spec;
+typedef struct {
+  uint32_t shift, bits;
+  uint64_t slots;
+  int64_t first_id;  /* histogram: the id of slot 0 */
+  int64_t zero_slot; /* histogram: the slot of -0.0 (the slot of +0.0 follows it); -1 when id 0 is outside the range */
+} slg_composite_source_layout;
+typedef struct {
+  uint32_t n_sources, size, key_bits, n_children;
+  slg_composite_source_layout sources[SLG_MAX_COMPOSITE_SOURCES];
+  uint64_t count_offset; /* the composite's `size` count cells in a query's count row */
+  slg_agg_layout children[SLG_MAX_AGGS]; /* parent_rows = size; offsets into a query's count / stats row */
+} slg_composite_layout;
+slg_batch *slg_batch_prepare_composite(slg_index *index, uint32_t nq, const uint32_t *q_offsets,
+                                       const uint32_t *q_term_ids, const float *q_weights,
+                                       const slg_score_plans *plans_or_null, const int32_t *q_filter_or_null,
+                                       const slg_sort_spec *sort_or_null, const slg_agg_spec *aggs_or_null,
+                                       const slg_composite_spec *composite, uint32_t k, int strategy);
+int slg_batch_composite_layout(const slg_batch *batch, slg_composite_layout *out);
+/* Per query an INCLUSIVE lower bound in packed key space for the runs that follow (copied; NULL or 0: from the
+ * start; a bound >= 1 << key_bits: no bucket).  One prepared batch pages through a bucket set with set-after + run. */
+int slg_batch_set_composite_after(slg_batch *batch, const uint64_t *q_lower_or_null);
+/* The selection of the batch's last run: keys [nq x size] ascending, n_buckets [nq], has_more [nq] (any may be
+ * NULL); waits for the batch.  Row r of a query's composite count cells and of every child table belongs to
+ * keys[r]; rows past n_buckets are zero.  Keys, n_buckets, has_more and counts are exact and the same on every
+ * run; a child's sum carries the tolerance of every stats sum.  SLG_ERR_INVALID on a batch of another kind. */
+int slg_batch_fetch_composite(slg_batch *batch, uint64_t *keys, uint32_t *n_buckets, uint32_t *has_more);
+/* One-shot form for the first page (no lower bound): slg_search_batch_aggs with a composite spec; counts / stats
+ * are sized by the caller as slg_batch_agg_layout and slg_batch_composite_layout would tell. */
+int slg_search_batch_composite(slg_index *index, const slg_query *queries, uint32_t nq,
+                               const slg_score_plans *plans_or_null, const int32_t *q_filter_or_null,
+                               const slg_sort_spec *sort_or_null, const slg_agg_spec *aggs_or_null,
+                               const slg_composite_spec *composite, uint32_t k, int strategy, uint32_t *out_doc,
+                               uint32_t *out_seg, float *out_score, uint32_t *out_count, uint64_t *out_matched,
+                               uint64_t *counts, slg_agg_stats *stats, uint64_t *cp_keys, uint32_t *cp_n_buckets,
+                               uint32_t *cp_has_more);
 
 /* ---- request coalescer ------------------------------------------------------------------------------
  * searchlite has no batch API: IndexReader::search takes one request (api/reader.rs:2539) and the HTTP

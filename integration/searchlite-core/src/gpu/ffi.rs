@@ -101,6 +101,26 @@ pub const SLG_MAX_TOP_HITS_ENTRIES: u32 = 1 << 19;
 #[repr(C)] #[derive(Clone, Copy, Default)] pub struct slg_top_hits_layout {
     pub lists: u32, pub size: u32, pub list_offset: u32, pub hit_offset: u32,
 }
+// composite (CompositeAggregation): the spec travels beside the aggregation spec; a tuple is one packed u64 key (source
+// 0 in the most significant bits, a slot per source); the composite's `size` count cells and its children's tables lie
+// behind the spec's cells in the rows of slg_batch_fetch_aggs
+pub const SLG_MAX_COMPOSITE_SOURCES: usize = 4;
+pub const SLG_MAX_COMPOSITE_SIZE: u32 = 1024;
+pub const SLG_COMPOSITE_TERMS: u32 = 0;
+pub const SLG_COMPOSITE_HISTOGRAM: u32 = 1;
+#[repr(C)] pub struct slg_composite_source { pub kind: u32, pub field: i32, pub interval: f64, pub ord_rank: *const u32 }
+#[repr(C)] pub struct slg_composite_spec {
+    pub n_sources: u32, pub size: u32, pub sources: [slg_composite_source; SLG_MAX_COMPOSITE_SOURCES],
+    pub n_children: u32, pub children: [slg_agg_node; SLG_MAX_AGGS],
+}
+#[repr(C)] #[derive(Clone, Copy, Default)] pub struct slg_composite_source_layout {
+    pub shift: u32, pub bits: u32, pub slots: u64, pub first_id: i64, pub zero_slot: i64,
+}
+#[repr(C)] pub struct slg_composite_layout {
+    pub n_sources: u32, pub size: u32, pub key_bits: u32, pub n_children: u32,
+    pub sources: [slg_composite_source_layout; SLG_MAX_COMPOSITE_SOURCES], pub count_offset: u64,
+    pub children: [slg_agg_layout; SLG_MAX_AGGS],
+}
 #[repr(C)] pub struct slg_bool_spec {
     pub c_offsets: *const u32, pub c_term_ids: *const u32, pub c_group: *const u32, pub g_offsets: *const u32,
     pub g_kind: *const i32, pub q_min_should: *const u32,
@@ -304,6 +324,23 @@ extern "C" {
         out_doc: *mut u32, out_seg: *mut u32, out_score: *mut c_float, out_count: *mut u32, out_matched: *mut u64,
         counts: *mut u64, stats: *mut slg_agg_stats, values: *mut u64, th_doc: *mut u32, th_seg: *mut u32,
         th_score: *mut c_float, th_count: *mut u32, th_status: *mut u32) -> c_int;
+    // composite: slg_batch_prepare_aggs plus the spec (aggs_or_null may be null); per query an inclusive lower bound
+    // in packed key space for the runs that follow (null: from the start); the page of the last run: keys [nq x size]
+    // ascending, n_buckets [nq], has_more [nq]
+    pub fn slg_batch_prepare_composite(index: *mut slg_index, nq: u32, q_offsets: *const u32, q_term_ids: *const u32,
+        q_weights: *const c_float, plans_or_null: *const slg_score_plans, q_filter_or_null: *const i32,
+        sort_or_null: *const slg_sort_spec, aggs_or_null: *const slg_agg_spec, composite: *const slg_composite_spec,
+        k: u32, strategy: c_int) -> *mut slg_batch;
+    pub fn slg_batch_composite_layout(batch: *const slg_batch, out: *mut slg_composite_layout) -> c_int;
+    pub fn slg_batch_set_composite_after(batch: *mut slg_batch, q_lower_or_null: *const u64) -> c_int;
+    pub fn slg_batch_fetch_composite(batch: *mut slg_batch, keys: *mut u64, n_buckets: *mut u32,
+        has_more: *mut u32) -> c_int;
+    pub fn slg_search_batch_composite(index: *mut slg_index, queries: *const slg_query, nq: u32,
+        plans_or_null: *const slg_score_plans, q_filter_or_null: *const i32, sort_or_null: *const slg_sort_spec,
+        aggs_or_null: *const slg_agg_spec, composite: *const slg_composite_spec, k: u32, strategy: c_int,
+        out_doc: *mut u32, out_seg: *mut u32, out_score: *mut c_float, out_count: *mut u32, out_matched: *mut u64,
+        counts: *mut u64, stats: *mut slg_agg_stats, cp_keys: *mut u64, cp_n_buckets: *mut u32,
+        cp_has_more: *mut u32) -> c_int;
     pub fn slg_batch_matched_counts(batch: *mut slg_batch, out_matched: *mut u64) -> c_int;
     pub fn slg_search_batch_sorted(index: *mut slg_index, queries: *const slg_query, nq: u32,
         plans_or_null: *const slg_score_plans, q_filter_or_null: *const i32, sort: *const slg_sort_spec, k: u32,

@@ -772,7 +772,10 @@ pub(crate) fn gpu_eligible(
   // status 1 goes back to the CPU collectors) and is not admitted by aggs_fit_device yet either.  One deviation to
   // decide on when it is: the device keeps one list over all segments and slices it at `from` once, the reference
   // slices every segment's list and the merged list (finish, merge_top_hits), so from > 0 agrees only when one
-  // segment holds the list's hits.  Anything else (significant_terms, rare_terms, composite, extended_stats,
+  // segment holds the list's hits.  composite is built as well (ffi::slg_batch_prepare_composite: a root composite of
+  // up to four terms / histogram sources beside the aggregation spec, size <= ffi::SLG_MAX_COMPOSITE_SIZE, paged with
+  // slg_batch_set_composite_after; keys are unpacked and `after` mapped to a packed bound here) and not admitted by
+  // aggs_fit_device yet.  Anything else (significant_terms, rare_terms, extended_stats,
   // pipeline aggregations as NODES — they are applied on the host to the shaped buckets —, deeper trees, top_hits
   // with a keyword sort part or from + size > 64) keeps the request on the CPU collectors.  Not with a cursor:
   // cursor batches take no aggregations.  The caller maps every segment's keyword dictionary

@@ -26,9 +26,16 @@ finished hits and are left out here.  The device keeps ONE list over all segment
 size); the reference slices every segment's list at `from` and the merged list again (TopHitsCollector::finish,
 merge_top_hits), so with from > 0 and hits in more than one segment it answers differently: such a request is exact
 on the device only when one segment holds the list's hits.
+
+composite ({"type": "composite", "sources": [{"type": "terms" | "histogram", "name", "field", "interval"}], "size",
+"after", "aggs"}, at the root, one per request) travels beside the aggregation spec too (slg_batch_prepare_composite):
+AggPlan.composite.  The device returns the `size` smallest packed keys at or above a lower bound with their counts and
+children; composite_lower_bound maps the request's `after` object to that bound, shape_composite renders the page
+(CompositeCollector / finalize_composite, :1689-1842, :3264-3368).
 """
 from __future__ import annotations
 
+import ctypes as C
 import json
 import math
 import re
@@ -290,11 +297,80 @@ class AggPlan:
     aggregation, sort = [(sort field id or "_score", "asc" | "desc")]."""
 
     def __init__(self, spec: "N.AggSpec", nodes: List[dict], top_hits: Optional["N.TopHitsSpec"] = None,
-                 top_hits_nodes: Optional[List[dict]] = None):
+                 top_hits_nodes: Optional[List[dict]] = None, composite: Optional[dict] = None):
         self.spec = spec
         self.nodes = nodes
         self.top_hits = top_hits
         self.top_hits_nodes = top_hits_nodes or []
+        # the request's composite aggregation (None without one): dict(name, body, spec = N.CompositeSpec, size, after,
+        # sources = [dict(name, type, field, interval, keys, rank, sorted_keys)], children = the AggPlan of its `aggs`);
+        # rank[ord] is the rank of ordinal ord's key in UTF-8 byte order (None: a histogram source), sorted_keys its
+        # inverse as the key strings in that order
+        self.composite = composite
+
+
+VALUE_TYPES = ("cardinality", "percentiles", "percentile_ranks")
+
+
+def _composite_plan(name: str, body: dict, fields: Dict[str, dict]) -> dict:
+    """one composite body -> AggPlan.composite; ValueError for what the device does not build"""
+    if body.get("sampling") is not None:
+        raise ValueError(f"aggregation {name!r}: sampling is not built on the device")
+    if body.get("size") is None:
+        raise ValueError(f"aggregation {name!r}: composite requires `size`")
+    size = int(body["size"])
+    if size <= 0 or size > N.MAX_COMPOSITE_SIZE:
+        raise ValueError(f"aggregation {name!r}: composite size {size} is not built on the device "
+                         f"(1 .. {N.MAX_COMPOSITE_SIZE})")
+    srcs = body.get("sources") or []
+    if not 1 <= len(srcs) <= N.MAX_COMPOSITE_SOURCES:
+        raise ValueError(f"aggregation {name!r}: a composite of {len(srcs)} sources is not built on the device")
+    spec = N.CompositeSpec()
+    spec.n_sources, spec.size = len(srcs), size
+    sources = []
+    for i, sb in enumerate(srcs):
+        typ = sb.get("type")
+        if typ not in ("terms", "histogram"):
+            raise ValueError(f"aggregation {name!r}: composite source type {typ!r} is not built on the device")
+        if sb["field"] not in fields or sb["field"] == FILTERS:
+            raise ValueError(f"aggregation {name!r}: field {sb['field']!r} is not registered")
+        fd = fields[sb["field"]]
+        keys = fd.get("keys")
+        src = dict(name=sb["name"], type=typ, field=sb["field"], interval=None, keys=keys, rank=None, sorted_keys=None)
+        spec.sources[i].field = int(fd["id"])
+        if typ == "terms":
+            if keys is None:
+                raise ValueError(f"aggregation {name!r}: terms source {sb['name']!r} needs a keyword field")
+            raw = [k.encode("utf-8") for k in keys]
+            if len(set(raw)) != len(raw):
+                raise ValueError(f"aggregation {name!r}: the dictionary of {sb['field']!r} holds a key twice")
+            order = sorted(range(len(raw)), key=lambda o: raw[o])  # (Rust orders String by its UTF-8 bytes)
+            rank = np.zeros(len(raw), dtype=np.uint32)
+            rank[np.asarray(order, dtype=np.int64)] = np.arange(len(raw), dtype=np.uint32)
+            src["rank"], src["sorted_keys"] = rank, [keys[o] for o in order]
+            spec.sources[i].kind = N.COMPOSITE_TERMS
+            # (a dictionary registered in byte order needs no table: one dependent load less per value)
+            presorted = order == list(range(len(raw)))
+            spec.sources[i].ord_rank = None if presorted else rank.ctypes.data
+        else:
+            if keys is not None:
+                raise ValueError(f"aggregation {name!r}: histogram source {sb['name']!r} needs a numeric field")
+            src["interval"] = float(sb["interval"])
+            spec.sources[i].kind, spec.sources[i].interval = N.COMPOSITE_HISTOGRAM, src["interval"]
+        sources.append(src)
+    children = agg_spec(body.get("aggs") or {}, fields)
+    if children.top_hits_nodes or children.composite is not None:
+        raise ValueError(f"aggregation {name!r}: top_hits or composite under a composite is not built on the device")
+    for nd in children.nodes:
+        if nd["parent"] >= 0:
+            raise ValueError(f"aggregation {name!r}: only one level under a composite is built")
+        if nd["type"] in VALUE_TYPES:
+            raise ValueError(f"aggregation {name!r}: a {nd['type']} child of a composite is not built on the device")
+    spec.n_children = len(children.nodes)
+    for i in range(min(len(children.nodes), N.MAX_AGGS)):
+        C.memmove(C.addressof(spec.children[i]), C.addressof(children.spec.nodes[i]), C.sizeof(N.AggNode))
+    return dict(name=name, body=body, spec=spec, size=size, after=body.get("after"), sources=sources,
+                children=children)
 
 
 def _top_hits_node(name: str, body: dict, parent: int, fields: Dict[str, dict]) -> dict:
@@ -343,12 +419,24 @@ def agg_spec(aggs: Dict[str, dict], fields: Dict[str, dict], top_hits_max_entrie
     terms, histogram, range or date_histogram aggregation may fill (the sum of its parent's counts).  The batch holds
     8 bytes per slot and query: the default 0 is the library's 2^19 slots, 4 MB per query (4 GB for 1024 queries), so
     a caller who knows a bound on the matched docs (times the values per doc of the parent's column) passes it; a
-    query that needs more gets status 1 and goes to the CPU path."""
+    query that needs more gets status 1 and goes to the CPU path.
+    A root composite aggregation becomes AggPlan.composite (one per request; terms sources need fields[f]["keys"],
+    whose UTF-8 byte order gives the rank permutation); ValueError for a dictionary that holds a key twice, a composite
+    anywhere but the root, a second one, sampling, pipeline, top_hits or value-node children, a third level, and a
+    size of 0 or above N.MAX_COMPOSITE_SIZE."""
     nodes: List[dict] = []
     th_nodes: List[dict] = []
+    composite: List[dict] = []
 
     def add(name, body, parent):
         typ = body.get("type")
+        if typ == "composite":  # (beside the spec, as top_hits: at the root only, one per request)
+            if parent >= 0:
+                raise ValueError(f"aggregation {name!r}: a composite below another aggregation is not built on the device")
+            if composite:
+                raise ValueError(f"aggregation {name!r}: a second composite is not built on the device")
+            composite.append(_composite_plan(name, body, fields))
+            return
         if typ == "top_hits":  # (beside the spec: a child only of a root bucket aggregation, which its parent checked)
             th_nodes.append(_top_hits_node(name, body, parent, fields))
             return
@@ -442,7 +530,7 @@ def agg_spec(aggs: Dict[str, dict], fields: Dict[str, dict], top_hits_max_entrie
             for i, (field, order) in enumerate(th["sort"]):
                 t.sort.field[i] = N.SORT_SCORE if field == "_score" else field
                 t.sort.order[i] = N.ORDER_ASC if order == "asc" else N.ORDER_DESC
-    return AggPlan(spec, nodes, th_spec, th_nodes)
+    return AggPlan(spec, nodes, th_spec, th_nodes, composite[0] if composite else None)
 
 
 def _stats(cell) -> dict:
@@ -456,14 +544,107 @@ def _bucket_key_string(key) -> str:
     return key if isinstance(key, str) else json.dumps(key)
 
 
+def f64_order_key(x: float) -> int:
+    """the u64 whose integer order is f64::total_cmp (slg::agg_f64_key): -0.0 < 0.0, NaNs at the ends"""
+    b = int(np.float64(x).view(np.uint64))
+    return (~b) & 0xFFFFFFFFFFFFFFFF if b >> 63 else b | (1 << 63)
+
+
+def composite_slot_value(src_layout: dict, interval: float, slot: int) -> float:
+    """the key of a histogram source's slot: -0.0, or float(id) * interval"""
+    z = src_layout["zero_slot"]
+    if z >= 0 and slot == z:
+        return -0.0
+    return float(src_layout["first_id"] + slot - (1 if z >= 0 and slot > z else 0)) * interval
+
+
+def composite_lower_bound(layout: dict, plan: AggPlan, after) -> int:
+    """The INCLUSIVE packed lower bound of "tuple > after" (finalize_composite, :3317-3337): layout =
+    PreparedBatch.composite_layout().  Parts are walked in order; the first part that is not exactly a slot (a terms
+    string absent from the dictionary, a histogram value that is not bitwise some slot's key) turns the strict
+    comparison into "prefix equal and slot >= the first slot above it": that slot, zeros behind it.  When every part
+    is a slot the bound is packed + 1.  A part above every slot carries into the prefix by itself (the bound is an
+    integer, not a tuple); past the largest possible key the bound is 1 << key_bits (nothing follows).  An `after`
+    the reference ignores (not an object, a missing name, a non-string terms part, a non-number histogram part) is 0."""
+    cp = plan.composite
+    if after is None or not isinstance(after, dict):
+        return 0
+    lays = layout["sources"]
+    nothing = 1 << layout["key_bits"]
+    max_key = sum((L["slots"] - 1) << L["shift"] for L in lays)
+    packed = 0
+    for src, L in zip(cp["sources"], lays):
+        if src["name"] not in after:
+            return 0
+        v = after[src["name"]]
+        if src["type"] == "terms":
+            if not isinstance(v, str):
+                return 0
+            raw = v.encode("utf-8")
+            keys = src["sorted_keys"]
+            lo, hi = 0, len(keys)
+            while lo < hi:  # the first slot whose key is >= v
+                mid = (lo + hi) // 2
+                if keys[mid].encode("utf-8") < raw:
+                    lo = mid + 1
+                else:
+                    hi = mid
+            exact = lo < len(keys) and keys[lo].encode("utf-8") == raw
+        else:
+            if isinstance(v, bool) or not isinstance(v, (int, float)):
+                return 0
+            want = f64_order_key(float(v))
+            n_real = L["slots"]  # (a column without a value has one slot, never emitted: any bound is right for it)
+            lo, hi = 0, n_real
+            while lo < hi:
+                mid = (lo + hi) // 2
+                if f64_order_key(composite_slot_value(L, src["interval"], mid)) < want:
+                    lo = mid + 1
+                else:
+                    hi = mid
+            exact = lo < n_real and f64_order_key(composite_slot_value(L, src["interval"], lo)) == want
+        packed += lo << L["shift"]
+        if not exact:
+            return packed if packed <= max_key else nothing
+    packed += 1
+    return packed if packed <= max_key else nothing
+
+
+def shape_composite(plan: AggPlan, layout: dict, page: dict, q: int) -> dict:
+    """The response of query q's composite: {"type": "composite", "buckets": [{"key": {name: string | f64},
+    "doc_count", "aggregations"}], "after_key"} — buckets ascending, after_key (the last bucket's key) only when
+    there are more.  layout: PreparedBatch.composite_layout(); page: PreparedBatch.composite()."""
+    cp = plan.composite
+    lays = layout["sources"]
+    kids = cp["children"]
+    buckets = []
+    for r in range(int(page["n_buckets"][q])):
+        packed = int(page["keys"][q, r])
+        key = {}
+        for src, L in zip(cp["sources"], lays):
+            slot = (packed >> L["shift"]) & ((1 << L["bits"]) - 1)
+            key[src["name"]] = src["sorted_keys"][slot] if src["type"] == "terms" else \
+                composite_slot_value(L, src["interval"], slot)
+        b = {"key": key, "doc_count": int(page["counts"][q, r])}
+        if kids.nodes:  # (shaped by the code that shapes any bucket's children: the children as roots, at row r)
+            b["aggregations"] = shape(kids, layout["children"], page["children"], q, prow=r)
+        buckets.append(b)
+    out = {"type": "composite", "buckets": buckets}
+    if int(page["has_more"][q]) and buckets:
+        out["after_key"] = buckets[-1]["key"]
+    return out
+
+
 def shape(plan: AggPlan, layout: List[dict], tables: List[np.ndarray], q: int, top_hits: Optional[dict] = None,
-          matched=None) -> Dict[str, dict]:
+          matched=None, prow: int = 0, composite: Optional[tuple] = None) -> Dict[str, dict]:
     """The response of query q: name -> AggregationResponse as a dict ({"type": ..., "buckets": [{"key",
     "doc_count", "aggregations"}]} / stats).  layout: PreparedBatch.agg_layout(); tables: PreparedBatch.aggs().
     top_hits: PreparedBatch.top_hits() of a plan with top_hits nodes, matched: PreparedBatch.matched_counts() (a
     root node's total): {"type": "top_hits", "total", "hits": [{"segment", "doc", "score"}]} at the root or in the
     bucket.  `fields` and `snippet` of a hit are doc-store work and are not part of it.  ValueError for a query
-    whose bucket runs did not fit (status 1: the CPU path)."""
+    whose bucket runs did not fit (status 1: the CPU path).  prow: the parent row the roots are read at (0; a
+    composite's children are shaped as roots at their bucket's row).  composite: (PreparedBatch.composite_layout(),
+    PreparedBatch.composite()) of a plan with a composite: its response goes under its name (shape_composite)."""
     if plan.top_hits_nodes and top_hits is not None and int(top_hits["status"][q]) != 0:
         raise ValueError(f"query {q}: the top_hits bucket runs did not fit max_entries (CPU path)")
 
@@ -571,9 +752,11 @@ def shape(plan: AggPlan, layout: List[dict], tables: List[np.ndarray], q: int, t
             out.append(bucket(key, r, int(tab[r])))
         return {"type": "range", "buckets": out, "keyed": bool(body.get("keyed", False))}
 
-    out = {plan.nodes[i]["name"]: node(i, 0) for i in range(len(plan.nodes)) if plan.nodes[i]["parent"] < 0}
+    out = {plan.nodes[i]["name"]: node(i, prow) for i in range(len(plan.nodes)) if plan.nodes[i]["parent"] < 0}
     if top_hits is not None and any(th["parent"] < 0 for th in plan.top_hits_nodes):
         if matched is None:
             raise ValueError("a root top_hits node needs `matched` (its total)")
         out.update(top_hits_under(-1, 0, int(matched[q])))
+    if plan.composite is not None and composite is not None:
+        out[plan.composite["name"]] = shape_composite(plan, composite[0], composite[1], q)
     return out

@@ -107,18 +107,33 @@ void slghost::agg_check_spec(const slg_agg_spec *aggs) {
   }
 }
 
-// The spec against the batch's index state: fields, the tables' layout, the device descriptors and tables
-void slghost::agg_attach(slg_batch *b, const slg_agg_spec &aggs) {
-  const IndexState &S = *b->snap;
-  slg_index *ix = b->idx;
+namespace {
+// The tables of a checked spec against an index state: the device descriptors, the layout and the cell counts.
+// A root's table has root_rows parent rows (1 for an aggregation spec; a composite's children are planned as roots
+// under its `size` rows), the count table starts at cell count0 (the composite's own count row lies in front of its
+// children's), and cells_before cells of the query are taken already (they count towards SLG_MAX_AGG_CELLS).
+struct PlannedTables {
+  std::vector<slg::AggNodeDev> nodes;
+  std::vector<slg::ColumnDev> cols;
+  std::vector<const uint32_t *> rank_cols;
+  std::vector<slg_agg_layout> layout;
+  uint64_t count_cells = 0, stats_cells = 0, value_cells = 0, card_words = 0, fine_words = 0;
+  uint32_t n_value = 0, n_pct = 0, n_walk1 = 0;
+};
+void plan_tables(const IndexState &S, const slg_agg_spec &aggs, const uint64_t root_rows, const uint64_t count0,
+                 const uint64_t cells_before, PlannedTables &P) {
   const size_t n_segs = S.segs.size();
   const uint32_t nn = aggs.n_nodes;
-  std::vector<slg::AggNodeDev> nodes(nn);
-  std::vector<slg::ColumnDev> cols((size_t)nn * std::max<size_t>(n_segs, 1), slg::ColumnDev{nullptr, nullptr});
+  std::vector<slg::AggNodeDev> &nodes = P.nodes;
+  std::vector<slg::ColumnDev> &cols = P.cols;
+  std::vector<const uint32_t *> &rank_cols = P.rank_cols;
+  std::vector<slg_agg_layout> &layout = P.layout;
+  nodes.assign(nn, slg::AggNodeDev{});
+  cols.assign((size_t)nn * std::max<size_t>(n_segs, 1), slg::ColumnDev{nullptr, nullptr});
   const std::vector<slgplan::FscoreFieldView> fields = fscore_field_views(S);
-  b->agg_layout.assign(nn, slg_agg_layout{});
-  std::vector<const uint32_t *> rank_cols((size_t)nn * std::max<size_t>(n_segs, 1), nullptr);
-  uint64_t count_cells = 0, stats_cells = 0, value_cells = 0, card_words = 0, fine_words = 0, fine_total = 0;
+  layout.assign(nn, slg_agg_layout{});
+  rank_cols.assign((size_t)nn * std::max<size_t>(n_segs, 1), nullptr);
+  uint64_t count_cells = count0, stats_cells = 0, value_cells = 0, card_words = 0, fine_words = 0, fine_total = 0;
   uint32_t n_value = 0, n_pct = 0, n_walk1 = 0;
   for (uint32_t i = 0; i < nn; i++) {
     const slg_agg_node &n = aggs.nodes[i];
@@ -229,7 +244,7 @@ void slghost::agg_attach(slg_batch *b, const slg_agg_spec &aggs) {
       rows = n.n_ranges;
     }
     if (rows == 0) rows = 1;  // (a keyword field without keys and without a missing row: one cell, never counted)
-    const uint64_t parent_rows = n.parent < 0 ? 1u : b->agg_layout[n.parent].rows;
+    const uint64_t parent_rows = n.parent < 0 ? root_rows : layout[n.parent].rows;
     if (is_value(n.kind)) {
       n_value++;
       d.n_ranges = n.n_ranges;
@@ -296,12 +311,12 @@ void slghost::agg_attach(slg_batch *b, const slg_agg_spec &aggs) {
     }
     uint64_t &cells = is_value(n.kind) ? value_cells : n.kind == SLG_AGG_STATS ? stats_cells : count_cells;
     if (rows > SLG_MAX_AGG_CELLS || parent_rows * rows > SLG_MAX_AGG_CELLS ||
-        count_cells + stats_cells + value_cells + parent_rows * rows > SLG_MAX_AGG_CELLS)
+        cells_before + count_cells + stats_cells + value_cells + parent_rows * rows > SLG_MAX_AGG_CELLS)
       throw SlgError(SLG_ERR_UNSUPPORTED, "more than SLG_MAX_AGG_CELLS aggregation cells per query (at " + node_name(i) + ")");
     d.rows = (uint32_t)rows;
     d.first_id = first_id;
     d.off = (uint32_t)cells;
-    slg_agg_layout &lay = b->agg_layout[i];
+    slg_agg_layout &lay = layout[i];
     lay.parent_rows = (uint32_t)parent_rows;
     lay.rows = (uint32_t)rows;
     lay.first_id = first_id;
@@ -309,6 +324,30 @@ void slghost::agg_attach(slg_batch *b, const slg_agg_spec &aggs) {
     lay.offset = cells;
     cells += parent_rows * rows;
   }
+  P.count_cells = count_cells;
+  P.stats_cells = stats_cells;
+  P.value_cells = value_cells;
+  P.card_words = card_words;
+  P.fine_words = fine_words;
+  P.n_value = n_value;
+  P.n_pct = n_pct;
+  P.n_walk1 = n_walk1;
+}
+}  // namespace
+
+// The spec against the batch's index state: fields, the tables' layout, the device descriptors and tables
+void slghost::agg_attach(slg_batch *b, const slg_agg_spec &aggs) {
+  slg_index *ix = b->idx;
+  PlannedTables P;
+  plan_tables(*b->snap, aggs, 1, 0, 0, P);
+  std::vector<slg::AggNodeDev> &nodes = P.nodes;
+  const std::vector<slg::ColumnDev> &cols = P.cols;
+  const std::vector<const uint32_t *> &rank_cols = P.rank_cols;
+  const uint32_t nn = aggs.n_nodes;
+  const uint64_t count_cells = P.count_cells, stats_cells = P.stats_cells, value_cells = P.value_cells,
+                 card_words = P.card_words, fine_words = P.fine_words;
+  const uint32_t n_value = P.n_value, n_pct = P.n_pct, n_walk1 = P.n_walk1;
+  b->agg_layout = P.layout;
   b->aggs = true;
   b->agg_spec = aggs;
   b->agg_count_cells = (uint32_t)count_cells;
@@ -336,6 +375,28 @@ void slghost::agg_attach(slg_batch *b, const slg_agg_spec &aggs) {
   }
   b->d_agg_counts.alloc_pooled(&ix->pool, nq * std::max<size_t>(count_cells, 1) * 4);
   b->d_agg_stats.alloc_pooled(&ix->pool, nq * std::max<size_t>(stats_cells, 1) * sizeof(slg::AggStatDev));
+}
+
+CompositeChildTables slghost::agg_plan_children(const IndexState &S, const slg_composite_spec &spec,
+                                                const uint64_t cells_before) {
+  slg_agg_spec roots{};
+  roots.n_nodes = spec.n_children;
+  for (uint32_t i = 0; i < spec.n_children; i++) {
+    roots.nodes[i] = spec.children[i];
+    roots.nodes[i].parent = -1;
+  }
+  PlannedTables P;
+  plan_tables(S, roots, spec.size, spec.size, cells_before, P);
+  CompositeChildTables out;
+  const ImagePart np = image_part(P.nodes), cp = image_part(P.cols);
+  out.nodes.assign(static_cast<const unsigned char *>(np.p), static_cast<const unsigned char *>(np.p) + np.bytes);
+  out.cols.assign(static_cast<const unsigned char *>(cp.p), static_cast<const unsigned char *>(cp.p) + cp.bytes);
+  out.layout = P.layout;
+  out.count_cells = P.count_cells;
+  out.stats_cells = P.stats_cells;
+  for (uint32_t i = 0; i < spec.n_children; i++)
+    out.ext = out.ext || roots.nodes[i].kind == SLG_AGG_DATE_HISTOGRAM || roots.nodes[i].kind == SLG_AGG_FILTER;
+  return out;
 }
 
 void slghost::agg_launch(slg_batch *b, hipStream_t st) {
@@ -398,7 +459,8 @@ extern "C" {
 int slg_batch_agg_layout(const slg_batch *b, slg_agg_layout *out) {
   return guarded([&] {
     SLG_REQUIRE(b != nullptr, "batch is NULL");
-    SLG_REQUIRE(b->aggs, "not an aggregation batch (slg_batch_prepare_aggs)");
+    SLG_REQUIRE(b->aggs || b->composite, "not an aggregation batch (slg_batch_prepare_aggs)");
+    if (!b->aggs) return;  // (a composite batch without an aggregation spec: no node)
     SLG_REQUIRE(out != nullptr, "out is NULL");
     std::copy(b->agg_layout.begin(), b->agg_layout.end(), out);
   });
@@ -423,33 +485,45 @@ int slg_batch_fetch_agg_values(slg_batch *b, uint64_t *values) {
 int slg_batch_fetch_aggs(slg_batch *b, uint64_t *counts, slg_agg_stats *stats) {
   return guarded([&] {
     SLG_REQUIRE_LIVE(b);
-    SLG_REQUIRE(b->aggs, "not an aggregation batch (slg_batch_prepare_aggs)");
+    SLG_REQUIRE(b->aggs || b->composite, "not an aggregation batch (slg_batch_prepare_aggs)");
     SLG_REQUIRE(b->launched, "the batch has not run");
-    const size_t nc = (size_t)b->nq * b->agg_count_cells, ns = (size_t)b->nq * b->agg_stats_cells;
-    SLG_REQUIRE(nc == 0 || counts != nullptr, "counts is NULL");
-    SLG_REQUIRE(ns == 0 || stats != nullptr, "stats is NULL");
+    // a composite batch: the composite's cells lie behind the spec's in every query's row (tables of their own on
+    // the device: agg_kernel's tables keep their stride)
+    const size_t ac = b->aggs ? b->agg_count_cells : 0u, as = b->aggs ? b->agg_stats_cells : 0u;
+    const size_t cc = b->composite ? b->cp_count_cells : 0u, cs = b->composite ? b->cp_stats_cells : 0u;
+    const size_t nq = b->nq;
+    SLG_REQUIRE(nq * (ac + cc) == 0 || counts != nullptr, "counts is NULL");
+    SLG_REQUIRE(nq * (as + cs) == 0 || stats != nullptr, "stats is NULL");
     DeviceGuard g(b->idx->device);
     const hipStream_t st = locked_stream(b);
-    std::vector<uint32_t> hc(nc);
-    std::vector<slg::AggStatDev> hs(ns);
-    if (nc) SLG_HIP(hipMemcpyAsync(hc.data(), b->d_agg_counts.p, nc * 4, hipMemcpyDeviceToHost, st));
-    if (ns) SLG_HIP(hipMemcpyAsync(hs.data(), b->d_agg_stats.p, ns * sizeof(slg::AggStatDev), hipMemcpyDeviceToHost, st));
+    std::vector<uint32_t> hc(nq * ac), hcc(nq * cc);
+    std::vector<slg::AggStatDev> hs(nq * as), hcs(nq * cs);
+    if (!hc.empty()) SLG_HIP(hipMemcpyAsync(hc.data(), b->d_agg_counts.p, hc.size() * 4, hipMemcpyDeviceToHost, st));
+    if (!hs.empty())
+      SLG_HIP(hipMemcpyAsync(hs.data(), b->d_agg_stats.p, hs.size() * sizeof(slg::AggStatDev), hipMemcpyDeviceToHost, st));
+    if (!hcc.empty()) SLG_HIP(hipMemcpyAsync(hcc.data(), b->d_cp_counts.p, hcc.size() * 4, hipMemcpyDeviceToHost, st));
+    if (!hcs.empty())
+      SLG_HIP(hipMemcpyAsync(hcs.data(), b->d_cp_stats.p, hcs.size() * sizeof(slg::AggStatDev), hipMemcpyDeviceToHost, st));
     SLG_HIP(wait_stream(st));
-    for (size_t i = 0; i < nc; i++) counts[i] = hc[i];
     auto value = [](unsigned long long key) {  // the inverse of agg_f64_key
       const unsigned long long bits = (key >> 63) ? (key & 0x7FFFFFFFFFFFFFFFull) : ~key;
       double x;
       std::memcpy(&x, &bits, 8);
       return x;
     };
-    for (size_t i = 0; i < ns; i++) {
-      slg_agg_stats &o = stats[i];
+    auto stat = [&](const slg::AggStatDev &h, slg_agg_stats &o) {
       o = slg_agg_stats{0, 0.0, 0.0, 0.0};  // StatsState::default
-      if (hs[i].count == 0) continue;
-      o.count = hs[i].count;
-      o.min = value(~hs[i].min_key);
-      o.max = value(hs[i].max_key);
-      o.sum = hs[i].sum;
+      if (h.count == 0) return;
+      o.count = h.count;
+      o.min = value(~h.min_key);
+      o.max = value(h.max_key);
+      o.sum = h.sum;
+    };
+    for (size_t q = 0; q < nq; q++) {
+      for (size_t i = 0; i < ac; i++) counts[q * (ac + cc) + i] = hc[q * ac + i];
+      for (size_t i = 0; i < cc; i++) counts[q * (ac + cc) + ac + i] = hcc[q * cc + i];
+      for (size_t i = 0; i < as; i++) stat(hs[q * as + i], stats[q * (as + cs) + i]);
+      for (size_t i = 0; i < cs; i++) stat(hcs[q * cs + i], stats[q * (as + cs) + as + i]);
     }
   });
 }

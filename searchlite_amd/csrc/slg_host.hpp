@@ -1,5 +1,5 @@
 // slg_host.hpp — what the host translation units of the C ABI share (slg_index.hip, slg_batch.hip,
-// slg_shard.hip, slg_rerank.hip, slg_vsearch.hip, slg_hybrid.hip, slg_aggs.hip, slg_rescore.hip, slg_bool.hip, slg_booltree.hip, slg_phrase.hip, slg_fscore.hip, slg_script.hip, slg_scan.hip, slg_collapse.hip, slg_tophits.hip): the error plumbing, device memory, the host
+// slg_shard.hip, slg_rerank.hip, slg_vsearch.hip, slg_hybrid.hip, slg_aggs.hip, slg_rescore.hip, slg_bool.hip, slg_booltree.hip, slg_phrase.hip, slg_fscore.hip, slg_script.hip, slg_scan.hip, slg_collapse.hip, slg_tophits.hip, slg_composite.hip): the error plumbing, device memory, the host
 // structures behind the opaque handles and the small helpers several entry points use.  Private: not
 // installed, not part of include/.  No kernel header is included here — each unit includes the one
 // whose kernels it launches (slg_stage.hpp, slg_kernels.hpp, slg_rerank.hpp, slg_vsearch.hpp, slg_hybrid.hpp; the shard
@@ -615,6 +615,22 @@ struct slg_batch {
   DevBuf d_th_desc;     // slg::TopHitsNodeDev[n_nodes], then slg::SortColDev[n_nodes][kSortMaxParts * n_segs]
   DevBuf d_th_out;      // doc | seg | score [nq * hit_cells], count [nq * list_cells], status [nq], the error word
   DevBuf d_th_entries, d_th_cursors;  // uint2[nq * max_entries], u32[nq * cursor_words]
+  // composite batch (slg_batch_prepare_composite): an aggregation batch, or a plain / sorted one planned as such;
+  // composite_select_kernel and composite_collect_kernel run behind agg_kernel (slg_composite.hip).  The composite's
+  // tables are its own: agg_kernel's keep their stride, slg_batch_fetch_aggs puts the two side by side
+  bool composite = false;
+  slg_composite_spec cp_spec{};  // (ord_rank: not kept, the ranks are on the device)
+  slg_composite_layout cp_layout{};
+  uint32_t cp_count_cells = 0, cp_stats_cells = 0;  // of one query: `size` count cells, then the children's tables
+  uint32_t cp_cap = 0;        // entries of one wave's key set in composite_select_kernel
+  bool cp_lds = false, cp_ext = false;  // the tables fit SLG_AGG_LDS_BYTES; a date_histogram or filter child
+  size_t cp_cols_off = 0, cp_src_cols_off = 0, cp_src_off = 0;  // byte offsets into d_cp_desc
+  DevBuf d_cp_desc;    // slg::AggNodeDev[n_children], ColumnDev[n_children * n_segs], ColumnDev[n_sources * n_segs],
+                       // slg::CompositeSourceDev[n_sources]
+  DevBuf d_cp_ranks;   // u32: the ord_rank of every terms source that has one, back to back
+  DevBuf d_cp_lower;   // u64[nq] the inclusive lower bounds (slg_batch_set_composite_after)
+  DevBuf d_cp_out;     // u64 keys [nq * size], then u32 n_buckets [nq], has_more [nq], the error word
+  DevBuf d_cp_counts, d_cp_stats;  // u32[nq * cp_count_cells], slg::AggStatDev[nq * cp_stats_cells]
 };
 
 namespace slghost __attribute__((visibility("hidden"))) {
@@ -739,6 +755,7 @@ struct PrepareRequest {
   int script_order = 0;           // SLG_SCRIPT_OUTER / _INNER
   Asked<slg_collapse_spec> collapse;
   Asked<slg_top_hits_spec> top_hits;  // slg_batch_prepare_top_hits (aggs: on when its spec is given)
+  Asked<slg_composite_spec> composite;  // slg_batch_prepare_composite (aggs: on when its spec is given)
 };
 // a spec that is a kind of its own only when it is given (the sort of a bool, phrase, cursor or agg batch)
 template <typename T>
@@ -866,6 +883,23 @@ void collapse_launch(slg_batch *b, hipStream_t st);
 // launch behind agg_kernel (without an aggregation spec: behind the select)
 void top_hits_attach(slg_batch *b, const slg_top_hits_spec &spec);
 void top_hits_launch(slg_batch *b, hipStream_t st);
+// slg_composite.hip: the checks of a composite spec that need no index (throws; after agg_check_spec); the spec
+// against the batch's state (the sources' columns and key layout, the children's tables), descriptors, ranks and
+// tables onto the device (throws; the batch is otherwise prepared, agg_attach has run); the two launches behind
+// agg_kernel (without an aggregation spec: behind the select)
+void composite_check_spec(const slg_composite_spec *spec);
+void composite_attach(slg_batch *b, const slg_composite_spec &spec);
+void composite_launch(slg_batch *b, hipStream_t st);
+// slg_aggs.hip: a composite's children planned as the roots of `size` parent rows, behind the composite's own count
+// row and cells_before cells of the aggregation spec: the AggNodeDev and ColumnDev images, the layout (offsets into
+// the composite's tables) and the cells of the composite's count and stats tables
+struct CompositeChildTables {
+  std::vector<unsigned char> nodes, cols;
+  std::vector<slg_agg_layout> layout;
+  uint64_t count_cells = 0, stats_cells = 0;
+  bool ext = false;
+};
+CompositeChildTables agg_plan_children(const IndexState &S, const slg_composite_spec &spec, uint64_t cells_before);
 
 // slg_vsearch.hip: one vector search or hybrid call, checked against one state of the index ...
 struct VsCall {

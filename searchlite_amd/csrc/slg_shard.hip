@@ -152,6 +152,7 @@ int run_sharded_impl(slg_batch *b, slg_shard_group *g, bool have_seq, uint64_t s
     if (b->script) throw SlgError(SLG_ERR_UNSUPPORTED, "a script_score batch does not run sharded");
     if (b->collapse) throw SlgError(SLG_ERR_UNSUPPORTED, "a collapse batch does not run sharded");
     if (b->top_hits) throw SlgError(SLG_ERR_UNSUPPORTED, "a top_hits batch does not run sharded");
+    if (b->composite) throw SlgError(SLG_ERR_UNSUPPORTED, "a composite batch does not run sharded");
     if (b->scan) throw SlgError(SLG_ERR_UNSUPPORTED, "a scan batch does not run sharded");
   });
   if (rc != SLG_OK) return rc;
@@ -290,6 +291,7 @@ int slg_batch_fetch_sharded(slg_batch *b, uint32_t *out_doc, uint32_t *out_seg, 
     if (b->script) throw SlgError(SLG_ERR_UNSUPPORTED, "a script_score batch does not run sharded");
     if (b->collapse) throw SlgError(SLG_ERR_UNSUPPORTED, "a collapse batch does not run sharded");
     if (b->top_hits) throw SlgError(SLG_ERR_UNSUPPORTED, "a top_hits batch does not run sharded");
+    if (b->composite) throw SlgError(SLG_ERR_UNSUPPORTED, "a composite batch does not run sharded");
     if (b->scan) throw SlgError(SLG_ERR_UNSUPPORTED, "a scan batch does not run sharded");
     SLG_REQUIRE(b->nq == 0 || out_count != nullptr, "out_count is NULL");
     SLG_REQUIRE(b->nq == 0 || b->k == 0 || (out_doc && out_seg && out_score), "output array is NULL");

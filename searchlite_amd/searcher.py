@@ -614,7 +614,8 @@ class GpuIndex:
                 group_tie=None, q_node_offsets=None, node_kind=None, node_tie=None, node_parent=None,
                 q_min_match=None, sort=None, cursors=None, hybrid=False, aggs=None,
                 rescore=None, clauses=None, phrases=None, fscore=None, collapse=None,
-                clause_tree=None, script=None, script_order="outer", top_hits=None) -> "PreparedBatch":
+                clause_tree=None, script=None, script_order="outer", top_hits=None,
+                composite=None) -> "PreparedBatch":
         """q_leaf / q_plan / q_tie / q_nleaves: score plans; leaf_group / group_plan / group_tie with
         their per-query offsets: two-level plans; q_node_offsets / node_kind / node_tie / node_parent:
         trees of any shape, node by node in pre-order (slg_batch_prepare_plans, slg_score_plans);
@@ -634,12 +635,38 @@ class GpuIndex:
         fscore as its second stage: script_order "outer" is script_score{query: function_score}, "inner" is
         function_score{query: script_score}; top_hits: an N.TopHitsSpec (an aggs.AggPlan passed as aggs brings its
         own) -> slg_batch_prepare_top_hits (score order or with sort, with aggs or without;
-        PreparedBatch.top_hits)."""
+        PreparedBatch.top_hits); composite: an N.CompositeSpec (an aggs.AggPlan passed as aggs brings its own) ->
+        slg_batch_prepare_composite (score order or with sort, with aggs or without; PreparedBatch.composite)."""
         return PreparedBatch(self, q_offsets, q_terms, q_weights, k, strategy, q_filter,
                              q_leaf, q_plan, q_tie, q_nleaves, q_leaf_offsets, leaf_group,
                              q_group_offsets, group_plan, group_tie, q_node_offsets, node_kind, node_tie, node_parent,
                              q_min_match, sort, cursors, hybrid, aggs, rescore, clauses, phrases, fscore, collapse,
-                             clause_tree, script, script_order, top_hits)
+                             clause_tree, script, script_order, top_hits, composite)
+
+    def prepare_composite(self, q_offsets, q_terms, q_weights, k: int, aggs, sort=None, strategy: int = Wand,
+                          q_filter=None, composite=None, **plans) -> "PreparedBatch":
+        """A batch with a composite aggregation (slg_batch_prepare_composite).  aggs: an aggs.AggPlan with a
+        composite, or an N.AggSpec / None with composite an N.CompositeSpec.  One prepared batch pages through a
+        bucket set: set_composite_after(bounds), run(), composite(), again."""
+        return self.prepare(q_offsets, q_terms, q_weights, k, strategy, q_filter, sort=sort, aggs=aggs,
+                            composite=composite, **plans)
+
+    def search_composite(self, q_offsets, q_terms, q_weights, k: int, aggs, sort=None, strategy: int = Wand,
+                         q_filter=None, composite=None, lower=None, **plans):
+        """Batch search with a composite aggregation: one page.  lower: per query the inclusive packed lower bound
+        (aggs.composite_lower_bound), None = the first page.
+        -> (doc, seg, score, count, matched, tables, layout, page): as search_aggs (tables and layout empty
+        without an aggregation node), and the dict of PreparedBatch.composite."""
+        b = self.prepare_composite(q_offsets, q_terms, q_weights, k, aggs, sort, strategy, q_filter, composite, **plans)
+        try:
+            if lower is not None:
+                b.set_composite_after(lower)
+            b.run()
+            has = b.agg_spec is not None
+            return b.fetch() + (b.matched_counts(), b.aggs() if has else [], b.agg_layout() if has else [],
+                                b.composite())
+        finally:
+            b.close()
 
     def search_collapse(self, q_offsets, q_terms, q_weights, k: int, collapse, sort=None, cursors=None,
                         strategy: int = Wand, q_filter=None, **plans):
@@ -1169,7 +1196,7 @@ class PreparedBatch:
                  group_tie=None, q_node_offsets=None, node_kind=None, node_tie=None, node_parent=None,
                  q_min_match=None, sort=None, cursors=None, hybrid=False, aggs=None, rescore=None, clauses=None,
                  phrases=None, fscore=None, collapse=None, clause_tree=None, script=None, script_order="outer",
-                 top_hits=None):
+                 top_hits=None, composite=None):
         self.index = index
         self._lib = index._lib
         q_offsets = np.ascontiguousarray(q_offsets, dtype=np.uint32)
@@ -1218,7 +1245,25 @@ class PreparedBatch:
                                                collapse is not None or clause_tree is not None or script is not None):
             # (the library's other prepare calls take no top_hits spec: the refusal is made here with its code)
             raise N.SlgError(N.ERR_UNSUPPORTED, "top_hits is built on plain, sorted and aggregation batches only")
-        if self.top_hits_spec is not None:
+        # (an aggs.AggPlan carries its composite: a dict whose "spec" is the N.CompositeSpec)
+        cp = getattr(aggs, "composite", None) if composite is None else composite
+        self.composite_spec = cp["spec"] if isinstance(cp, dict) else cp
+        if self.composite_spec is not None and self.agg_spec is not None and int(self.agg_spec.n_nodes) == 0:
+            self.agg_spec = None
+        if self.composite_spec is not None and (
+                self.top_hits_spec is not None or hybrid or cursors is not None or rescore is not None or
+                clauses is not None or phrases is not None or fscore is not None or collapse is not None or
+                clause_tree is not None or script is not None):
+            # (the library's other prepare calls take no composite spec: the refusal is made here with its code)
+            raise N.SlgError(N.ERR_UNSUPPORTED, "composite is built on plain, sorted and aggregation batches only")
+        if self.composite_spec is not None:
+            spec = None if sort is None else sort_spec(sort)
+            self._h = self._lib.slg_batch_prepare_composite(
+                index._h, self.nq, _ptr(q_offsets), _ptr(q_terms), _ptr(q_weights), C.addressof(plans),
+                opt(qf), None if spec is None else C.addressof(spec),
+                None if self.agg_spec is None else C.addressof(self.agg_spec), C.addressof(self.composite_spec),
+                k, strategy)
+        elif self.top_hits_spec is not None:
             spec = None if sort is None else sort_spec(sort)
             self._h = self._lib.slg_batch_prepare_top_hits(
                 index._h, self.nq, _ptr(q_offsets), _ptr(q_terms), _ptr(q_weights), C.addressof(plans),
@@ -1372,15 +1417,18 @@ class PreparedBatch:
         return [dict(parent_rows=int(x.parent_rows), rows=int(x.rows), first_id=int(x.first_id),
                      is_stats=int(x.is_stats) == 1, is_values=int(x.is_stats) == 2, offset=int(x.offset)) for x in lay]
 
-    def aggs(self) -> list:
-        """The tables of the last run (slg_batch_fetch_aggs / _fetch_agg_values; waits): per node an array
-        [nq, parent_rows, rows], uint64 counts for a bucket node, aggs.STATS_DTYPE records (count, min, max, sum)
-        for a stats node, uint64 value cells for a cardinality, percentiles or percentile_ranks node."""
+    def _agg_tables(self):
+        """slg_batch_fetch_aggs / _fetch_agg_values into 2-D arrays: (layout, counts, stats, values, composite
+        layout or None).  A composite batch's rows hold the composite's cells behind the spec's."""
         from .aggs import STATS_DTYPE
-        lay = self.agg_layout()
+        lay = self.agg_layout() if self.agg_spec is not None else []
         cells = lambda pick: sum(x["parent_rows"] * x["rows"] for x in lay if pick(x))
         cc = cells(lambda x: not x["is_stats"] and not x["is_values"])
         sc, vc = cells(lambda x: x["is_stats"]), cells(lambda x: x["is_values"])
+        cl = self.composite_layout() if getattr(self, "composite_spec", None) is not None else None
+        if cl is not None:
+            cc += cl["size"] + sum(x["parent_rows"] * x["rows"] for x in cl["children"] if not x["is_stats"])
+            sc += sum(x["parent_rows"] * x["rows"] for x in cl["children"] if x["is_stats"])
         counts = np.zeros((max(self.nq, 1), max(cc, 1)), dtype=np.uint64)
         stats = np.zeros((max(self.nq, 1), max(sc, 1)), dtype=STATS_DTYPE)
         values = np.zeros((max(self.nq, 1), max(vc, 1)), dtype=np.uint64)
@@ -1388,13 +1436,55 @@ class PreparedBatch:
                                                _ptr(stats.reshape(-1)[:self.nq * sc]) if sc else None))
         if vc:
             N.check(self._lib.slg_batch_fetch_agg_values(self._h, _ptr(values.reshape(-1)[:self.nq * vc])))
-        out = []
-        for x in lay:
-            src, n_cells = (stats, sc) if x["is_stats"] else (values, vc) if x["is_values"] else (counts, cc)
-            flat = src.reshape(-1)[:self.nq * n_cells].reshape(self.nq, n_cells)
-            n = x["parent_rows"] * x["rows"]
-            out.append(flat[:, x["offset"]:x["offset"] + n].reshape(self.nq, x["parent_rows"], x["rows"]).copy())
-        return out
+        flat = lambda src, n: src.reshape(-1)[:self.nq * n].reshape(self.nq, n)
+        return lay, flat(counts, cc), flat(stats, sc), flat(values, vc), cl
+
+    @staticmethod
+    def _cut(x: dict, counts, stats, values) -> np.ndarray:
+        src = stats if x["is_stats"] else values if x["is_values"] else counts
+        n = x["parent_rows"] * x["rows"]
+        return src[:, x["offset"]:x["offset"] + n].reshape(src.shape[0], x["parent_rows"], x["rows"]).copy()
+
+    def aggs(self) -> list:
+        """The tables of the last run (slg_batch_fetch_aggs / _fetch_agg_values; waits): per node an array
+        [nq, parent_rows, rows], uint64 counts for a bucket node, aggs.STATS_DTYPE records (count, min, max, sum)
+        for a stats node, uint64 value cells for a cardinality, percentiles or percentile_ranks node."""
+        lay, counts, stats, values, _ = self._agg_tables()
+        return [self._cut(x, counts, stats, values) for x in lay]
+
+    def composite_layout(self) -> dict:
+        """slg_batch_composite_layout: dict(n_sources, size, key_bits, count_offset, sources = [dict(shift, bits, slots,
+        first_id, zero_slot)], children = [as agg_layout's entries])."""
+        lay = N.CompositeLayout()
+        N.check(self._lib.slg_batch_composite_layout(self._h, C.addressof(lay)))
+        return dict(n_sources=int(lay.n_sources), size=int(lay.size), key_bits=int(lay.key_bits),
+                    count_offset=int(lay.count_offset),
+                    sources=[dict(shift=int(x.shift), bits=int(x.bits), slots=int(x.slots), first_id=int(x.first_id),
+                                  zero_slot=int(x.zero_slot)) for x in lay.sources[:int(lay.n_sources)]],
+                    children=[dict(parent_rows=int(x.parent_rows), rows=int(x.rows), first_id=int(x.first_id),
+                                   is_stats=int(x.is_stats) == 1, is_values=False, offset=int(x.offset))
+                              for x in lay.children[:int(lay.n_children)]])
+
+    def set_composite_after(self, lower=None) -> None:
+        """slg_batch_set_composite_after: per query the INCLUSIVE lower bound in packed key space of the runs that
+        follow (aggs.composite_lower_bound); None: from the start."""
+        arr = None if lower is None else np.ascontiguousarray(lower, dtype=np.uint64)
+        assert arr is None or len(arr) == self.nq
+        N.check(self._lib.slg_batch_set_composite_after(self._h, _ptr(arr) if arr is not None and self.nq else None))
+
+    def composite(self) -> dict:
+        """The page of a composite batch's last run (slg_batch_fetch_composite and the composite's cells of
+        slg_batch_fetch_aggs; waits): keys [nq, size] uint64 ascending, n_buckets [nq], has_more [nq], counts
+        [nq, size], children = per child an array [nq, size, rows] (as aggs()); zeros past n_buckets."""
+        _, counts, stats, values, cl = self._agg_tables()
+        nq, size = max(self.nq, 1), cl["size"]
+        keys = np.zeros((nq, size), dtype=np.uint64)
+        nb, more = np.zeros(nq, dtype=np.uint32), np.zeros(nq, dtype=np.uint32)
+        N.check(self._lib.slg_batch_fetch_composite(self._h, _ptr(keys), _ptr(nb), _ptr(more)))
+        c0 = cl["count_offset"]
+        return dict(keys=keys[:self.nq], n_buckets=nb[:self.nq], has_more=more[:self.nq],
+                    counts=counts[:, c0:c0 + size].copy(),
+                    children=[self._cut(x, counts, stats, values) for x in cl["children"]])
 
     def top_hits_layout(self) -> list:
         """slg_batch_top_hits_layout: per top_hits node dict(lists, size, list_offset, hit_offset)."""
@@ -1620,6 +1710,9 @@ class ScanBatch(PreparedBatch):
         if getattr(aggs, "top_hits", None) is not None:
             # (slg_batch_prepare_scan takes no top_hits spec: refused here with the library's code, nothing dropped)
             raise N.SlgError(N.ERR_UNSUPPORTED, "top_hits is not built on scan batches")
+        if getattr(aggs, "composite", None) is not None:  # (the same for a composite)
+            raise N.SlgError(N.ERR_UNSUPPORTED, "composite is not built on scan batches")
+        self.composite_spec = None
         self.agg_spec = getattr(aggs, "spec", aggs)  # (an aggs.AggPlan carries its N.AggSpec)
         spec = None if sort is None else sort_spec(sort)
         self._h = self._lib.slg_batch_prepare_scan(

@@ -44,6 +44,10 @@
  * device into ordinary slg_query terms, keys in the reference's order; terms or patterns of up to
  * SLG_MAX_EXPAND_CHARS chars, max_expansions up to SLG_MAX_EXPANSIONS.  Regex nodes, unscored groups, a query that
  * folds to more than SLG_MAX_QUERY_TERMS terms, and expansion inside sharded or coalesced paths stay on the CPU.
+ * The completion suggester (slg_suggest_batch): SuggestRequest::Completion, plain prefix or fuzzy, against the
+ * same dictionaries and their doc frequencies; scan, merge across segments, scores and the best `size` on the
+ * device; terms of up to SLG_MAX_EXPAND_CHARS chars, a fuzzy request's size up to SLG_MAX_SUGGEST_CANDIDATES.  The
+ * analysis of the prefix, and suggest through the coalescer or shard groups, stay with the caller.
  */
 #ifndef SEARCHLITE_GPU_H
 #define SEARCHLITE_GPU_H
@@ -1999,7 +2003,8 @@ int slg_search_batch_collapse(slg_index *index, uint32_t nq, const uint32_t *q_o
  * key_bytes, key i the UTF-8 "field:term" key of term id i of the segment's CSR (n_terms = slg_segment_desc.n_terms).
  * The arrays are borrowed for the call.  The library sorts the keys by bytes (the identity for files written by
  * searchlite, whose dictionary is a BTreeMap, util/fst.rs:25-33), keeps the sorted position -> term id map and a
- * host copy, and stages sorted bytes, offsets, map and a char count per key (u8, saturating) on the device.  It
+ * host copy, and stages sorted bytes, offsets, map, a char count per key (u8, saturating) and each key's doc
+ * frequency (u32, the length of its posting list as staged; slg_suggest_batch reads it) on the device.  It
  * builds the next index state as slg_index_set_positions does: prepared batches keep theirs;
  * slg_index_update_deleted keeps the dictionaries; a segment added later has none until it is set;
  * slg_index_remove_segment drops its dictionary.  SLG_ERR_INVALID: NULL arrays, seg out of range, decreasing
@@ -2069,6 +2074,76 @@ int slg_expand_batch(slg_index *index, const slg_expand_req *reqs, uint32_t n_re
  * (uploads, both kernels, the copy back, the wait) and the host merge.  The figures are per thread, not per index:
  * `index` is only checked for NULL.  Either pointer may be NULL. */
 int slg_expand_phase_ms(slg_index *index, double *scan_ms, double *merge_ms);
+
+/* ---- completion suggester: prefix and fuzzy, scored by doc frequency (api/reader.rs:1779-1998) ----------
+ * SuggestRequest::Completion { field, prefix, size, fuzzy } -> SuggestOption { text, score, doc_freq }: the
+ * terms of a field that start with (or lie within a few edits of) what the user has typed, the most frequent
+ * first.  slg_suggest_batch answers a batch of independent requests in one call against the dictionaries of
+ * slg_index_set_terms, which also stages each key's doc frequency.  Scan AND merge run on the device; the host
+ * copies the winners' texts out of its dictionary copy and computes no score, distance or comparison.
+ *
+ * REQUESTS.  field and term are UTF-8 with byte lengths, as in slg_expand_req.  term is already analysed by the
+ * caller (completion_inputs, :1915-1939, always yields exactly one input): for a text field the last token of the
+ * analysed prefix, or the raw prefix if there is none; for a keyword field to_ascii_lowercase of the prefix.  It
+ * may be empty.  Everything is counted in Unicode scalar values.  size == 0: no options (:1948).
+ *
+ * DOC FREQUENCY.  df of a key in a segment is the length of its posting list as staged: term_offsets[t + 1] -
+ * term_offsets[t] of the slg_segment_desc (PostingsReader::len(), whatever has been deleted since).  So
+ * slg_index_update_deleted never changes an answer.
+ *
+ * PLAIN (has_fuzzy == 0; :1798-1826).  cap = clamp(size * 5, SLG_SUGGEST_MIN_SCAN, SLG_MAX_SUGGEST_CANDIDATES).
+ * Segment by segment, over the range of the term in byte order: skip the key "field:" itself; skip a key of df 0
+ * without counting it; else options[text].doc_freq += df, options[text].score += (float)df, and the visit counts.
+ * The cap is GLOBAL and counts VISITS (the same text in three segments counts three times); everything stops when
+ * it is reached.
+ *
+ * FUZZY (has_fuzzy != 0; FuzzyOptions; :1827-1874).  No options if the term has fewer than min_length chars,
+ * max_expansions == 0 or max_edits == 0; max_edits is clamped to 2 first.  cap = max(min(max_expansions,
+ * SLG_MAX_SUGGEST_CANDIDATES), size).  Over the range of the term's first min(prefix_length, chars) chars: skip
+ * the bare key, a key whose char count differs from the term's by more than max_edits, one whose Levenshtein
+ * distance d exceeds max_edits, one of df 0.  A candidate EQUAL to the term passes at distance 0 (unlike
+ * slg_expand_batch).  score += (1.0f / (d + 1.0f)) * (float)df: one f32 multiply, then one f32 add, in segment
+ * order.  The cap is global and counts visits, as above.
+ *
+ * RESULT.  Per request the options by score descending, then text ascending in byte order, cut to size;
+ * doc_freq is the u64 sum.  Scores, order and doc_freq are the reference's bit for bit, the same from run to run.
+ *
+ * OUTPUT.  out_offsets [n_reqs + 1]: request r's options are rows out_offsets[r] .. out_offsets[r + 1] - 1 of
+ * out_score (f32), out_doc_freq (u64) and out_text_offsets; option i's text is out_text[out_text_offsets[i] ..
+ * out_text_offsets[i + 1]): UTF-8 without the "field:" part, not NUL-terminated.  option_capacity = the rows
+ * out_score and out_doc_freq hold (out_text_offsets holds option_capacity + 1), text_capacity = the bytes of
+ * out_text.  The call is synchronous.
+ * SIZE QUERY: out_score, out_doc_freq, out_text_offsets and out_text all NULL.  Then out_offsets must hold
+ * n_reqs + 2 entries: [0 .. n_reqs] are filled as above and out_offsets[n_reqs + 1] receives the text bytes the
+ * batch needs; the capacities are ignored.  (A caller who knows its longest key can skip it: a request yields at
+ * most min(size, SLG_MAX_SUGGEST_CANDIDATES) options.)
+ *
+ * SLG_ERR_INVALID: index, reqs (n_reqs > 0) or out_offsets NULL; a struct_size other than
+ * sizeof(slg_suggest_req); field or term NULL with a non-zero length; field or term not valid UTF-8; a segment
+ * without a dictionary; some but not all of the four output arrays NULL; option_capacity or text_capacity too
+ * small.  SLG_ERR_UNSUPPORTED (CPU path): a term of more than SLG_MAX_EXPAND_CHARS chars; a fuzzy request whose
+ * cap exceeds SLG_MAX_SUGGEST_CANDIDATES, which means size above it (a plain request may have any size: it never
+ * yields more than SLG_MAX_SUGGEST_CANDIDATES options).  NOT BUILT: suggest through the coalescer or shard
+ * groups; analysis of the prefix. */
+#define SLG_MAX_SUGGEST_CANDIDATES 256u /* MAX_SUGGEST_CANDIDATES: the most visits of one request */
+#define SLG_SUGGEST_MIN_SCAN 64u        /* DEFAULT_SUGGEST_SCAN: a plain request's smallest cap */
+#define SLG_SUGGEST_MERGE_WORKGROUP 256u /* threads of the merge kernel: one per candidate of a request */
+typedef struct slg_suggest_req {
+  uint32_t struct_size;    /* sizeof(slg_suggest_req) */
+  const char *field;       /* UTF-8, field_len bytes */
+  const char *term;        /* UTF-8, term_len bytes: the analysed completion input */
+  uint32_t field_len, term_len;
+  uint32_t size;
+  uint32_t has_fuzzy;      /* 0: plain; else the four FuzzyOptions below hold */
+  uint32_t max_edits, prefix_length, max_expansions, min_length;
+} slg_suggest_req;
+int slg_suggest_batch(slg_index *index, const slg_suggest_req *reqs, uint32_t n_reqs, uint32_t *out_offsets,
+                      uint32_t option_capacity, float *out_score, uint64_t *out_doc_freq, uint32_t *out_text_offsets,
+                      uint32_t text_capacity, char *out_text);
+/* DIAGNOSTIC ONLY (tools/suggest_time.py): where the calling thread's last slg_suggest_batch spent its time, in
+ * ms, by the host clock: the device part (uploads, the scan's two kernels, the merge kernel, the copy back, the
+ * wait) and the host's copy of the texts.  Per thread; `index` is only checked for NULL; either may be NULL. */
+int slg_suggest_phase_ms(slg_index *index, double *device_ms, double *copy_ms);
 
 #ifdef __cplusplus
 }

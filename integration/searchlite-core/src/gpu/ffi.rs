@@ -183,6 +183,12 @@ pub const SLG_SCAN_MOD_RECIPROCAL: i32 = 4;
     pub field_len: u32, pub term_len: u32, pub max_expansions: u32,
     pub max_edits: u32, pub prefix_length: u32, pub min_length: u32,
 }
+#[repr(C)] pub struct slg_suggest_req {
+    pub struct_size: u32, pub field: *const c_char, pub term: *const c_char, pub field_len: u32, pub term_len: u32,
+    pub size: u32, pub has_fuzzy: u32, pub max_edits: u32, pub prefix_length: u32, pub max_expansions: u32,
+    pub min_length: u32,
+}
+pub const SLG_MAX_SUGGEST_CANDIDATES: u32 = 256;
 pub const SLG_EXPAND_FUZZY: i32 = 0;
 pub const SLG_EXPAND_PREFIX: i32 = 1;
 pub const SLG_EXPAND_WILDCARD: i32 = 2;
@@ -460,6 +466,11 @@ extern "C" {
         key_capacity: u32, out_term_ids: *mut u32, out_distance: *mut u8) -> c_int;
     // diagnostic only (the timing tool's split of the last call on this thread into scan and merge): not routed
     pub fn slg_expand_phase_ms(index: *mut slg_index, scan_ms: *mut f64, merge_ms: *mut f64) -> c_int;
+    // the completion suggester (SearchRequest.suggest): declared, not routed yet
+    pub fn slg_suggest_batch(index: *mut slg_index, reqs: *const slg_suggest_req, n_reqs: u32, out_offsets: *mut u32,
+        option_capacity: u32, out_score: *mut c_float, out_doc_freq: *mut u64, out_text_offsets: *mut u32,
+        text_capacity: u32, out_text: *mut c_char) -> c_int;
+    pub fn slg_suggest_phase_ms(index: *mut slg_index, device_ms: *mut f64, copy_ms: *mut f64) -> c_int;
     pub fn slg_batch_prepare_phrase(index: *mut slg_index, nq: u32, q_offsets: *const u32, q_term_ids: *const u32,
         q_weights: *const c_float, plans: *const slg_score_plans, q_filter: *const i32,
         sort: *const slg_sort_spec, bool_spec: *const slg_bool_spec, phrases: *const slg_phrase_spec, k: u32,

@@ -87,6 +87,7 @@ EXPAND_FUZZY, EXPAND_PREFIX, EXPAND_WILDCARD = 0, 1, 2
 MAX_EXPAND_CHARS = 128
 MAX_EXPANSIONS = 1024
 EXPAND_WAVE, EXPAND_WORKGROUP, EXPAND_CHUNK = 64, 256, 1024  # the scan's geometry (SLG_EXPAND_*)
+MAX_SUGGEST_CANDIDATES, SUGGEST_MIN_SCAN, SUGGEST_MERGE_WORKGROUP = 256, 64, 256  # slg_suggest_batch (SLG_*)
 
 
 class SlgError(RuntimeError):
@@ -292,6 +293,13 @@ class ExpandReq(C.Structure):
                 ("max_edits", C.c_uint32), ("prefix_length", C.c_uint32), ("min_length", C.c_uint32)]
 
 
+class SuggestReq(C.Structure):
+    """slg_suggest_req: one completion request (slg_suggest_batch)."""
+    _fields_ = [("struct_size", C.c_uint32), ("field", C.c_char_p), ("term", C.c_char_p), ("field_len", C.c_uint32),
+                ("term_len", C.c_uint32), ("size", C.c_uint32), ("has_fuzzy", C.c_uint32), ("max_edits", C.c_uint32),
+                ("prefix_length", C.c_uint32), ("max_expansions", C.c_uint32), ("min_length", C.c_uint32)]
+
+
 class Ticket(C.Structure):
     """slg_ticket (slg_coalescer_submit / _wait)."""
     _fields_ = [("batch", C.c_void_p), ("row", C.c_uint32), ("k", C.c_uint32), ("kind", C.c_uint32)]
@@ -485,6 +493,8 @@ def load():
         "slg_index_set_terms": (i32, [vp, u32, vp, vp]),
         "slg_expand_batch": (i32, [vp, vp, u32, vp, u32, vp, vp]),
         "slg_expand_phase_ms": (i32, [vp, vp, vp]),
+        "slg_suggest_batch": (i32, [vp, vp, u32, vp, u32, vp, vp, vp, u32, vp]),
+        "slg_suggest_phase_ms": (i32, [vp, vp, vp]),
     }
     for name, (res, args) in sigs.items():
         if os.environ.get("SLG_LIB_TAG") and not hasattr(L, name):

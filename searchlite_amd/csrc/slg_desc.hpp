@@ -256,6 +256,12 @@ struct ExpandSegDev {           // per segment of an index state (slg_index_set_
   const uint32_t *offs;         // [n + 1]
   const uint8_t *nchars;        // [n] chars of each key; 255: 255 or more
 };
+struct SuggestSegDev {          // the same dictionary as slg_suggest_batch reads it: with the keys' doc frequencies
+  const unsigned char *bytes;   // (ExpandSegDev's three arrays; nullptr without a dictionary)
+  const uint32_t *offs;
+  const uint8_t *nchars;
+  const uint32_t *df;           // [n] posting-list length of the key at each sorted position, as staged
+};
 struct PhraseTerm {
   uint64_t off;    // posting offset inside the segment arrays (padded layout, as BoolTerm::off)
   uint64_t ubase;  // the list's first posting in the unpadded order (= term_offsets[term]): PosSegDev::offs index

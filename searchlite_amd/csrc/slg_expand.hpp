@@ -169,7 +169,7 @@ struct ExpandParams {
   uint32_t *pair_total;        // [n_pairs] keys of the range that passed
 };
 
-#if defined(__HIPCC__)
+#if defined(__HIPCC__) && !defined(SLG_EXPAND_NO_KERNELS)  // (slg_suggest.hpp takes the pieces above, not the kernels)
 
 // the request's predicate on the key at sorted position pos (inside the range); dist: its distance (fuzzy)
 __device__ __forceinline__ bool expand_pass(const ExpandReqDev *rq, const uint32_t *cp, const ExpandSegDev &sg,
@@ -258,6 +258,6 @@ static __global__ __launch_bounds__(kExpandThreads) void expand_emit_kernel(cons
   }
 }
 
-#endif  // __HIPCC__
+#endif  // __HIPCC__ && !SLG_EXPAND_NO_KERNELS
 
 }  // namespace slg

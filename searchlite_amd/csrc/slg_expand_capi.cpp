@@ -25,7 +25,10 @@ int guarded(char *err, uint32_t err_len, F &&f) {
   }
 }
 
+}  // namespace
+
 // bounded_levenshtein, api/reader.rs:981-1018, over code points: two full rows, the row-minimum exit
+// (slg_suggest_capi.cpp's restatement of the reference's suggest loop calls it too: external linkage)
 bool ref_bounded_levenshtein(const std::vector<uint32_t> &a, const std::vector<uint32_t> &b, size_t max_edits, size_t *out) {
   const size_t a_len = a.size(), b_len = b.size();
   if ((a_len > b_len ? a_len - b_len : b_len - a_len) > max_edits) return false;
@@ -50,6 +53,8 @@ bool ref_bounded_levenshtein(const std::vector<uint32_t> &a, const std::vector<u
   *out = prev[b_len];
   return *out <= max_edits;
 }
+
+namespace {
 
 // expand_term_fuzzy / expand_prefix / expand_wildcard as the reference runs them: walk the range of every
 // segment, test every key, keep a set of the keys seen

@@ -402,7 +402,12 @@ struct PosStore {
 struct TermStore {
   slgexpand::Dict dict;
   DevBuf bytes, offs, map, nchars;  // sorted key bytes | u32[n + 1] | u32[n] sorted position -> term id | u8[n]
-  size_t device_bytes() const { return bytes.bytes + offs.bytes + map.bytes + nchars.bytes; }
+  // slg_suggest_batch: the posting-list length of the key at each sorted position (the segment's term_offsets as
+  // staged, whatever is deleted), and how many of the keys in front of each position have one above 0
+  std::vector<uint32_t> df;         // [n]
+  std::vector<uint32_t> nonzero;    // [n + 1]
+  DevBuf d_df;                      // u32[n]
+  size_t device_bytes() const { return bytes.bytes + offs.bytes + map.bytes + nchars.bytes + d_df.bytes; }
 };
 
 // One immutable state of the index (see "index updates" in searchlite_gpu.h).  Batches hold the state
@@ -425,6 +430,7 @@ struct IndexState {
   DevBuf d_pos_segs;                                          // slg::PosSegDev[n_segs]
   std::vector<std::shared_ptr<TermStore>> terms;              // [n_segs]; null = the segment has no dictionary
   DevBuf d_term_segs;                                         // slg::ExpandSegDev[n_segs]
+  DevBuf d_suggest_segs;                                      // slg::SuggestSegDev[n_segs]
   ~IndexState() {
     // kernels of already-destroyed batches, or rerank calls on the index stream, may still read the
     // tables: retiring a state is rare (one per update), so wait for the device once

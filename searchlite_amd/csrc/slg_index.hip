@@ -284,6 +284,11 @@ void finish_state(slg_index *ix, IndexState &s) {
     if (s.terms[i]) td[i] = slg::ExpandSegDev{s.terms[i]->bytes.as<unsigned char>(), s.terms[i]->offs.as<uint32_t>(), s.terms[i]->nchars.as<uint8_t>()};
   s.d_term_segs.alloc(std::max<size_t>(n_segs, 1) * sizeof(slg::ExpandSegDev), &ix->pool);
   if (n_segs) SLG_HIP(hipMemcpy(s.d_term_segs.p, td.data(), n_segs * sizeof(slg::ExpandSegDev), hipMemcpyHostToDevice));
+  std::vector<slg::SuggestSegDev> ud(n_segs, slg::SuggestSegDev{nullptr, nullptr, nullptr, nullptr});
+  for (size_t i = 0; i < n_segs; i++)
+    if (s.terms[i]) ud[i] = slg::SuggestSegDev{td[i].bytes, td[i].offs, td[i].nchars, s.terms[i]->d_df.as<uint32_t>()};
+  s.d_suggest_segs.alloc(std::max<size_t>(n_segs, 1) * sizeof(slg::SuggestSegDev), &ix->pool);
+  if (n_segs) SLG_HIP(hipMemcpy(s.d_suggest_segs.p, ud.data(), n_segs * sizeof(slg::SuggestSegDev), hipMemcpyHostToDevice));
   std::vector<uint32_t> base(n_segs + 1, 0u);
   uint64_t acc = 0;
   for (size_t i = 0; i < n_segs; i++) {
@@ -385,7 +390,7 @@ size_t state_device_bytes(const IndexState &s) {
   size_t n = s.d_segs.bytes + s.d_vsegs.bytes + s.d_reject_table.bytes + s.d_doc_base.bytes + s.d_pos_segs.bytes;
   for (auto &ps : s.positions)
     if (ps) n += ps->offs.bytes + ps->pos.bytes;
-  n += s.d_term_segs.bytes;
+  n += s.d_term_segs.bytes + s.d_suggest_segs.bytes;
   for (auto &ts : s.terms)
     if (ts) n += ts->device_bytes();
   for (auto &sh : s.segs) n += sh->device_bytes() + sh->store->device_bytes();
@@ -928,6 +933,16 @@ int slg_index_set_terms(slg_index *ix, uint32_t seg, const char *key_bytes, cons
       stage(store->offs, d.offs.data(), d.offs.size() * 4);
       stage(store->map, d.map.data(), d.map.size() * 4);
       stage(store->nchars, d.nchars.data(), d.nchars.size());
+      // the doc frequency of every key, in sorted-position order: the list lengths of the CSR as it was staged
+      // (the PostingStore keeps the original term_offsets; tombstones never change them)
+      const std::vector<uint64_t> &to = cur.segs[seg]->store->term_offsets;
+      store->df.resize(d.n());
+      store->nonzero.assign((size_t)d.n() + 1, 0u);
+      for (uint32_t pos = 0; pos < d.n(); pos++) {
+        store->df[pos] = (uint32_t)std::min<uint64_t>(to[d.map[pos] + 1] - to[d.map[pos]], 0xFFFFFFFFull);
+        store->nonzero[pos + 1] = store->nonzero[pos] + (store->df[pos] != 0u);
+      }
+      stage(store->d_df, store->df.data(), store->df.size() * 4);
       ns.terms[seg] = std::move(store);
     });
   });

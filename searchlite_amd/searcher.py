@@ -47,6 +47,7 @@ class GpuIndex:
         self.segments = list(segments)
         self.device = device
         self._batches = weakref.WeakSet()  # closed with the index
+        self._max_key_bytes = 0            # the longest key any set_terms() saw (suggest() sizes its text buffer by it)
         descs = (N.SegmentDesc * len(self.segments))()
         keep = []
         for i, s in enumerate(self.segments):
@@ -113,6 +114,7 @@ class GpuIndex:
         np.cumsum([len(r) for r in raw], out=offs[1:])
         blob = np.frombuffer(b"".join(raw) + b"\0", dtype=np.uint8)  # (one spare byte: never an empty array)
         N.check(self._lib.slg_index_set_terms(self._h, seg, _ptr(blob), _ptr(offs)))
+        self._max_key_bytes = max(self._max_key_bytes, max((len(r) for r in raw), default=0))
 
     def set_terms_from_segments(self) -> None:
         """set_terms for every segment from its host dictionary (Segment.term_dict)."""
@@ -168,6 +170,46 @@ class GpuIndex:
         (slg_expand_phase_ms)."""
         a, b = C.c_double(0), C.c_double(0)
         N.check(self._lib.slg_expand_phase_ms(self._h, C.addressof(a), C.addressof(b)))
+        return a.value, b.value
+
+    def suggest(self, requests) -> List[List[Tuple[str, float, int]]]:
+        """slg_suggest_batch: requests = suggest_request() dicts -> per request its options (text, score, doc_freq),
+        best first, as the reference's completion suggester orders them; score is an np.float32."""
+        n = len(requests)
+        reqs = (N.SuggestReq * max(n, 1))()
+        keep = []
+        for i, r in enumerate(requests):
+            f = r["field"].encode("utf-8") if isinstance(r["field"], str) else bytes(r["field"])
+            t = r["term"].encode("utf-8") if isinstance(r["term"], str) else bytes(r["term"])
+            keep += [f, t]
+            fz = r.get("fuzzy")
+            fo = dict(FUZZY_DEFAULTS, **fz) if fz is not None else dict(max_edits=0, prefix_length=0, max_expansions=0, min_length=0)
+            reqs[i] = N.SuggestReq(C.sizeof(N.SuggestReq), f, t, len(f), len(t), int(r.get("size", 5)),
+                                   0 if fz is None else 1, int(fo["max_edits"]), int(fo["prefix_length"]),
+                                   int(fo["max_expansions"]), int(fo["min_length"]))
+        offs = np.zeros(n + 2, dtype=np.uint32)
+        # the most options the requests can yield, and their texts by the longest key any set_terms() saw; the size
+        # query where that would be a large array
+        cap = max(sum(min(r.size, N.MAX_SUGGEST_CANDIDATES) for r in reqs[:n]), 1)
+        text_cap = max(cap * self._max_key_bytes, 1)
+        if text_cap > (1 << 26):
+            N.check(self._lib.slg_suggest_batch(self._h, reqs, n, _ptr(offs), 0, None, None, None, 0, None))
+            cap, text_cap = max(int(offs[n]), 1), max(int(offs[n + 1]), 1)
+        score = np.zeros(cap, dtype=np.float32)
+        df = np.zeros(cap, dtype=np.uint64)
+        toffs = np.zeros(cap + 1, dtype=np.uint32)
+        text = np.zeros(text_cap, dtype=np.uint8)
+        N.check(self._lib.slg_suggest_batch(self._h, reqs, n, _ptr(offs), cap, _ptr(score), _ptr(df), _ptr(toffs),
+                                            text_cap, _ptr(text)))
+        blob = text.tobytes()
+        return [[(blob[int(toffs[i]):int(toffs[i + 1])].decode("utf-8"), score[i], int(df[i]))
+                 for i in range(int(offs[r]), int(offs[r + 1]))] for r in range(n)]
+
+    def suggest_phase_ms(self) -> Tuple[float, float]:
+        """Diagnostic only (tools/suggest_time.py): (device part, host text copy) of this thread's last suggest(),
+        in ms (slg_suggest_phase_ms)."""
+        a, b = C.c_double(0), C.c_double(0)
+        N.check(self._lib.slg_suggest_phase_ms(self._h, C.addressof(a), C.addressof(b)))
         return a.value, b.value
 
     def expanded_queries(self, queries: Sequence[str], default_field: str, fuzzy: Optional[dict] = None,
@@ -924,6 +966,28 @@ def expand_request(kind: int, field: str, term: str, max_expansions: int, max_ed
     N.EXPAND_PREFIX (term: the prefix) or N.EXPAND_WILDCARD (term: the pattern)."""
     return dict(kind=kind, field=field, term=term, max_expansions=max_expansions, max_edits=max_edits,
                 prefix_length=prefix_length, min_length=min_length)
+
+
+FUZZY_DEFAULTS = dict(max_edits=1, prefix_length=1, max_expansions=50, min_length=3)  # FuzzyOptions::default
+
+
+def suggest_request(field: str, term: str, size: int = 5, fuzzy: Optional[dict] = None) -> dict:
+    """One request of GpuIndex.suggest() (SuggestRequest::Completion): term is the analysed completion input
+    (completion_input()); fuzzy None, or a dict of FuzzyOptions over the defaults 1 / 1 / 50 / 3 (max_edits,
+    prefix_length, max_expansions, min_length)."""
+    return dict(field=field, term=term, size=size, fuzzy=None if fuzzy is None else dict(FUZZY_DEFAULTS, **fuzzy))
+
+
+def completion_input(kind: str, prefix: str) -> str:
+    """completion_inputs (api/reader.rs:1915-1939) for what the user typed: kind "keyword" lowercases ASCII letters
+    (to_ascii_lowercase); kind "text" expects `prefix` already analysed by the caller's search analyzer and takes
+    its last whitespace token, or the prefix itself if there is none."""
+    if kind == "keyword":
+        return "".join(chr(ord(c) + 32) if "A" <= c <= "Z" else c for c in prefix)
+    if kind == "text":
+        tokens = prefix.split()
+        return tokens[-1] if tokens else prefix
+    raise ValueError("completion suggest is only supported on text / keyword fields")
 
 
 def fold_expansions(nq: int, source_query, source_key, rows, n_segs: int, boost=1.0, names=None):

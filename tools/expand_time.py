@@ -24,33 +24,11 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch  # noqa: E402
 
 from searchlite_amd import build, corpus, searcher, _native as N  # noqa: E402
+from tools.vocabulary import make_vocabulary  # noqa: E402
 
 reps = int(sys.argv[1]) if len(sys.argv) > 1 else 5
 rounds = int(sys.argv[2]) if len(sys.argv) > 2 else 3
 n_docs, vocab, nq, T = 1_000_000, 1 << 18, 1024, 3
-
-
-def make_vocabulary(n, seed=17):
-    """n distinct lowercase words, rank order: frequent words are short (2 .. 4 letters up to rank ~1000), rare
-    ones longer (up to 12), letters drawn with English-like weights"""
-    rng = np.random.default_rng(seed)
-    letters = np.array(list("etaoinshrdlcumwfgypbvkjxqz"))
-    p = np.array([12.7, 9.1, 8.2, 7.5, 7.0, 6.7, 6.3, 6.1, 6.0, 4.3, 4.0, 2.8, 2.8, 2.4, 2.4, 2.2, 2.0, 2.0, 1.9, 1.5, 1.0,
-                  0.8, 0.15, 0.15, 0.1, 0.07])
-    p /= p.sum()
-    m = 2 * n
-    mat, extra = rng.choice(26, size=(m, 12), p=p), rng.integers(0, 4, size=m)
-    words, seen = [], set()
-    for i in range(m):
-        if len(words) == n:
-            break
-        length = int(min(12, max(2, np.log2(len(words) + 4) * 0.55 + extra[i])))
-        w = "".join(letters[mat[i, :length]])
-        if w not in seen:
-            seen.add(w)
-            words.append(w)
-    assert len(words) == n
-    return words
 
 
 t0 = time.time()

@@ -1008,6 +1008,103 @@ int slg_search_batch_composite(slg_index *index, const slg_query *queries, uint3
                                uint64_t *counts, slg_agg_stats *stats, uint64_t *cp_keys, uint32_t *cp_n_buckets,
                                uint32_t *cp_has_more);
 
+/* ---- significant_terms and rare_terms: select a keyword's buckets ------------------------------------
+ * SignificantTermsAggregation and RareTermsAggregation (api/types.rs:875-901; SignificantTermsCollector,
+ * RareTermsCollector, compute_background_counts, the merge and finalize: query/aggs/mod.rs:131-359, 2110-2181,
+ * 2395-2424, 2515-2595).  Both kinds count a collected doc once per DISTINCT value of a keyword column (no
+ * `missing`) and return at most `size` buckets.
+ *   significant: buckets with doc_count >= max(min_doc_count, 1); the `size` with the highest count (count desc, key
+ *     byte order asc) are kept, scored and returned by (score desc, count desc, key asc): the set is picked by count
+ *     and ordered by score.  score = (doc_count_b / doc_count) / (bg_count_b / bg_count), three IEEE f64 divisions,
+ *     0.0 when doc_count, bg_count or bg_count_b is zero.  doc_count (the node's): collected docs with a value.
+ *     bg_count (the node's): over EVERY segment, the docs that are not deleted and pass background_filter, with a
+ *     value or without.  bg_count_b: the sum, over the segments IN WHOSE FOREGROUND THE KEY OCCURS (the query
+ *     collected a doc with that key there), of the docs of that segment that are not deleted, pass the filter and
+ *     hold the key.  It is not the key's global background count: it is what the reference's merge adds up.
+ *   rare: buckets with 1 <= doc_count <= max_doc_count, by (count asc, key asc), the first `size`.
+ * The background comes from the registered column (bg_count_kernel at prepare, once per distinct (field, filter) of
+ * the spec; the batch is pinned to its index state).
+ *
+ * Deliberate deviation (as for terms): the reference filters by the count bound and truncates to `size` per SEGMENT
+ * and again after the merge; the device counts over all segments before it filters and truncates.  The two agree
+ * whenever no segment drops or truncates a bucket that the merged answer would have needed: on one segment; for
+ * significant_terms with min_doc_count <= 1 and `size` at least each segment's bucket count; for rare_terms when no
+ * key is within max_doc_count in one segment and beyond it in the sum.  bg_count_b above is NOT part of the
+ * deviation: it is the reference's sum exactly.
+ *
+ * slg_batch_prepare_term_buckets is slg_batch_prepare_aggs plus the spec (aggs_or_null may be NULL).  Rows, matched
+ * counts and every table of aggs_or_null are bit-identical to the same batch without the spec.  A node WITH children
+ * has `size` count cells (the rows' doc counts again, as a composite's) and then its children's tables (parent_rows =
+ * size) behind the cells of aggs_or_null in the arrays of slg_batch_fetch_aggs, node after node; a node without
+ * children has none.  Row r of a child table belongs to bucket r of slg_batch_fetch_term_buckets.
+ * Checked before the index is looked at (after the aggregation spec's own checks): spec NULL, n_nodes == 0, an
+ * unknown kind, a rare node with background_filter != -1, background_filter < -1, a child that slg_batch_prepare_aggs
+ * would reject as a root: SLG_ERR_INVALID; n_nodes > SLG_MAX_TERM_BUCKET_NODES, size == 0 ("all buckets": the CPU
+ * path), size > SLG_MAX_TERM_BUCKET_SIZE, n_children > SLG_MAX_AGGS, a cardinality, percentiles or percentile_ranks
+ * child: SLG_ERR_UNSUPPORTED.  Against the index: an unknown field, a field without a column for every segment, a
+ * numeric field, an unregistered filter id, an ord_rank that is not a permutation of [0, n_ords): SLG_ERR_INVALID;
+ * more than SLG_MAX_AGG_CELLS cells of a query (per node n_ords foreground cells and n_ords background-sum cells,
+ * with children size x (1 + child cells), plus the cells of aggs_or_null), or more than SLG_MAX_AGG_SCRATCH_WORDS
+ * presence words of a query (a significant node: n_segs x ceil(n_ords / 32)): SLG_ERR_UNSUPPORTED.
+ * Memory per batch: nq x 12 B per ordinal of every node, the presence words, nq x 36 B per output row, the child
+ * cells; per distinct (field, filter): 4 B x n_segs x (n_ords + 1); 8 B per ordinal of a ranked node.
+ * Not built (the CPU path; refused, or there is no entry point): `sampling`; `size` absent; a term-bucket node below
+ * another aggregation; top_hits or value nodes below one; term buckets on scan, cursor, hybrid, vector-only, bool,
+ * phrase, sharded (slg_batch_run_sharded* refuses the batch) or coalesced batches; together with a composite or
+ * top_hits spec in one batch.  Pipeline children stay the caller's. */
+#define SLG_MAX_TERM_BUCKET_NODES 4u
+#define SLG_MAX_TERM_BUCKET_SIZE 1024u /* as SLG_MAX_COMPOSITE_SIZE */
+enum { SLG_TERMS_SIGNIFICANT = 0, SLG_TERMS_RARE = 1 };
+typedef struct {
+  uint32_t kind;              /* SLG_TERMS_* */
+  int32_t field;              /* a keyword column (slg_index_add_agg_field_ord) */
+  uint32_t size;              /* 1 .. SLG_MAX_TERM_BUCKET_SIZE */
+  uint64_t doc_count_bound;   /* significant: min_doc_count; rare: max_doc_count */
+  int32_t background_filter;  /* significant: a registered filter id, -1 = none */
+  const uint32_t *ord_rank;   /* as slg_composite_source.ord_rank; NULL = the ordinals are in key byte order */
+  uint32_t n_children;
+  slg_agg_node children[SLG_MAX_AGGS]; /* as slg_composite_spec.children */
+} slg_term_bucket_node;
+typedef struct {
+  uint32_t n_nodes;
+  slg_term_bucket_node nodes[SLG_MAX_TERM_BUCKET_NODES];
+} slg_term_bucket_spec;
+typedef struct {
+  uint32_t size, n_children;
+  uint64_t row_offset;   /* the node's first row in a query's rows of slg_batch_fetch_term_buckets */
+  uint64_t count_offset; /* with children: the node's `size` count cells in a query's count row */
+  slg_agg_layout children[SLG_MAX_AGGS]; /* parent_rows = size; offsets into a query's count / stats row */
+} slg_term_bucket_node_layout;
+typedef struct {
+  uint32_t n_nodes;
+  uint32_t rows; /* of one query: the sum of the nodes' sizes */
+  slg_term_bucket_node_layout nodes[SLG_MAX_TERM_BUCKET_NODES];
+} slg_term_bucket_layout;
+slg_batch *slg_batch_prepare_term_buckets(slg_index *index, uint32_t nq, const uint32_t *q_offsets,
+                                          const uint32_t *q_term_ids, const float *q_weights,
+                                          const slg_score_plans *plans_or_null, const int32_t *q_filter_or_null,
+                                          const slg_sort_spec *sort_or_null, const slg_agg_spec *aggs_or_null,
+                                          const slg_term_bucket_spec *spec, uint32_t k, int strategy);
+int slg_batch_term_buckets_layout(const slg_batch *batch, slg_term_bucket_layout *out);
+/* The buckets of the batch's last run, in the response's final order: ords, doc_counts, bg_counts, score_bits (the
+ * bits of the f64 score) [nq x rows], a node's rows at its row_offset; n_buckets, node_doc_count, node_bg_count
+ * [nq x n_nodes] (any may be NULL); waits for the batch.  Rows past n_buckets are zero; for a rare node bg_counts,
+ * score_bits and the two totals are zero.  Everything is exact and the same on every run.  SLG_ERR_INVALID on a
+ * batch of another kind. */
+int slg_batch_fetch_term_buckets(slg_batch *batch, uint32_t *ords, uint64_t *doc_counts, uint64_t *bg_counts,
+                                 uint64_t *score_bits, uint32_t *n_buckets, uint64_t *node_doc_count,
+                                 uint64_t *node_bg_count);
+/* One-shot form: slg_search_batch_aggs with the spec; counts / stats are sized by the caller as slg_batch_agg_layout
+ * and slg_batch_term_buckets_layout would tell. */
+int slg_search_batch_term_buckets(slg_index *index, const slg_query *queries, uint32_t nq,
+                                  const slg_score_plans *plans_or_null, const int32_t *q_filter_or_null,
+                                  const slg_sort_spec *sort_or_null, const slg_agg_spec *aggs_or_null,
+                                  const slg_term_bucket_spec *spec, uint32_t k, int strategy, uint32_t *out_doc,
+                                  uint32_t *out_seg, float *out_score, uint32_t *out_count, uint64_t *out_matched,
+                                  uint64_t *counts, slg_agg_stats *stats, uint32_t *tb_ords, uint64_t *tb_doc_counts,
+                                  uint64_t *tb_bg_counts, uint64_t *tb_score_bits, uint32_t *tb_n_buckets,
+                                  uint64_t *tb_node_doc_count, uint64_t *tb_node_bg_count);
+
 /* ---- request coalescer ------------------------------------------------------------------------------
  * searchlite has no batch API: IndexReader::search takes one request (api/reader.rs:2539) and the HTTP
  * server gives every request its own blocking thread (searchlite-http/src/lib.rs:628-652).  The

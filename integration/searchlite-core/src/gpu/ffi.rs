@@ -121,6 +121,27 @@ pub const SLG_COMPOSITE_HISTOGRAM: u32 = 1;
     pub sources: [slg_composite_source_layout; SLG_MAX_COMPOSITE_SOURCES], pub count_offset: u64,
     pub children: [slg_agg_layout; SLG_MAX_AGGS],
 }
+// significant_terms / rare_terms: the spec travels beside the aggregation spec; at most `size` rows per node come back
+// in the response's final order; a node with children has `size` count cells and its children's tables behind the
+// spec's cells in the rows of slg_batch_fetch_aggs
+pub const SLG_MAX_TERM_BUCKET_NODES: usize = 4;
+pub const SLG_MAX_TERM_BUCKET_SIZE: u32 = 1024;
+pub const SLG_TERMS_SIGNIFICANT: u32 = 0;
+pub const SLG_TERMS_RARE: u32 = 1;
+#[repr(C)] pub struct slg_term_bucket_node {
+    pub kind: u32, pub field: i32, pub size: u32, pub doc_count_bound: u64, pub background_filter: i32,
+    pub ord_rank: *const u32, pub n_children: u32, pub children: [slg_agg_node; SLG_MAX_AGGS],
+}
+#[repr(C)] pub struct slg_term_bucket_spec {
+    pub n_nodes: u32, pub nodes: [slg_term_bucket_node; SLG_MAX_TERM_BUCKET_NODES],
+}
+#[repr(C)] pub struct slg_term_bucket_node_layout {
+    pub size: u32, pub n_children: u32, pub row_offset: u64, pub count_offset: u64,
+    pub children: [slg_agg_layout; SLG_MAX_AGGS],
+}
+#[repr(C)] pub struct slg_term_bucket_layout {
+    pub n_nodes: u32, pub rows: u32, pub nodes: [slg_term_bucket_node_layout; SLG_MAX_TERM_BUCKET_NODES],
+}
 #[repr(C)] pub struct slg_bool_spec {
     pub c_offsets: *const u32, pub c_term_ids: *const u32, pub c_group: *const u32, pub g_offsets: *const u32,
     pub g_kind: *const i32, pub q_min_should: *const u32,
@@ -347,6 +368,23 @@ extern "C" {
         out_doc: *mut u32, out_seg: *mut u32, out_score: *mut c_float, out_count: *mut u32, out_matched: *mut u64,
         counts: *mut u64, stats: *mut slg_agg_stats, cp_keys: *mut u64, cp_n_buckets: *mut u32,
         cp_has_more: *mut u32) -> c_int;
+    // significant_terms / rare_terms: slg_batch_prepare_aggs plus the spec (aggs_or_null may be null); the buckets of
+    // the last run in the response's order: [nq x rows] per row array, [nq x n_nodes] per node array (any may be null)
+    pub fn slg_batch_prepare_term_buckets(index: *mut slg_index, nq: u32, q_offsets: *const u32,
+        q_term_ids: *const u32, q_weights: *const c_float, plans_or_null: *const slg_score_plans,
+        q_filter_or_null: *const i32, sort_or_null: *const slg_sort_spec, aggs_or_null: *const slg_agg_spec,
+        spec: *const slg_term_bucket_spec, k: u32, strategy: c_int) -> *mut slg_batch;
+    pub fn slg_batch_term_buckets_layout(batch: *const slg_batch, out: *mut slg_term_bucket_layout) -> c_int;
+    pub fn slg_batch_fetch_term_buckets(batch: *mut slg_batch, ords: *mut u32, doc_counts: *mut u64,
+        bg_counts: *mut u64, score_bits: *mut u64, n_buckets: *mut u32, node_doc_count: *mut u64,
+        node_bg_count: *mut u64) -> c_int;
+    pub fn slg_search_batch_term_buckets(index: *mut slg_index, queries: *const slg_query, nq: u32,
+        plans_or_null: *const slg_score_plans, q_filter_or_null: *const i32, sort_or_null: *const slg_sort_spec,
+        aggs_or_null: *const slg_agg_spec, spec: *const slg_term_bucket_spec, k: u32, strategy: c_int,
+        out_doc: *mut u32, out_seg: *mut u32, out_score: *mut c_float, out_count: *mut u32, out_matched: *mut u64,
+        counts: *mut u64, stats: *mut slg_agg_stats, tb_ords: *mut u32, tb_doc_counts: *mut u64,
+        tb_bg_counts: *mut u64, tb_score_bits: *mut u64, tb_n_buckets: *mut u32, tb_node_doc_count: *mut u64,
+        tb_node_bg_count: *mut u64) -> c_int;
     pub fn slg_batch_matched_counts(batch: *mut slg_batch, out_matched: *mut u64) -> c_int;
     pub fn slg_search_batch_sorted(index: *mut slg_index, queries: *const slg_query, nq: u32,
         plans_or_null: *const slg_score_plans, q_filter_or_null: *const i32, sort: *const slg_sort_spec, k: u32,

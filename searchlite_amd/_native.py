@@ -56,6 +56,12 @@ def composite_cap(size: int) -> int:
     return cap
 
 
+MAX_TERM_BUCKET_NODES = 4
+MAX_TERM_BUCKET_SIZE = 1024
+TERMS_SIGNIFICANT, TERMS_RARE = 0, 1
+term_bucket_cap = composite_cap  # term_bucket_select_kernel keeps composite_select_kernel's per-wave set
+
+
 RESCORE_TOTAL, RESCORE_MULTIPLY, RESCORE_SUM, RESCORE_MAX, RESCORE_MIN = 0, 1, 2, 3, 4
 MAX_RESCORE_WINDOW = 1024
 BOOL_MUST, BOOL_SHOULD, BOOL_MUST_NOT = 0, 1, 2
@@ -334,6 +340,31 @@ class CompositeLayout(C.Structure):
                 ("children", AggLayout * MAX_AGGS)]
 
 
+class TermBucketNode(C.Structure):
+    """slg_term_bucket_node: TERMS_* kind, keyword agg field id, size, min_doc_count (significant) or max_doc_count
+    (rare), the background filter id of a significant node (-1: none), the rank of every ordinal's key in byte order
+    (NULL: the ordinals are in key order), the children (parent is not read)."""
+    _fields_ = [("kind", C.c_uint32), ("field", C.c_int32), ("size", C.c_uint32), ("doc_count_bound", C.c_uint64),
+                ("background_filter", C.c_int32), ("ord_rank", C.c_void_p), ("n_children", C.c_uint32),
+                ("children", AggNode * MAX_AGGS)]
+
+
+class TermBucketSpec(C.Structure):
+    """slg_term_bucket_spec: the significant_terms / rare_terms nodes of a request."""
+    _fields_ = [("n_nodes", C.c_uint32), ("nodes", TermBucketNode * MAX_TERM_BUCKET_NODES)]
+
+
+class TermBucketNodeLayout(C.Structure):
+    """slg_term_bucket_node_layout: a node's rows in a query's output rows, its count cells and children's tables."""
+    _fields_ = [("size", C.c_uint32), ("n_children", C.c_uint32), ("row_offset", C.c_uint64),
+                ("count_offset", C.c_uint64), ("children", AggLayout * MAX_AGGS)]
+
+
+class TermBucketLayout(C.Structure):
+    """slg_term_bucket_layout: the nodes' layouts; rows = the output rows of one query."""
+    _fields_ = [("n_nodes", C.c_uint32), ("rows", C.c_uint32), ("nodes", TermBucketNodeLayout * MAX_TERM_BUCKET_NODES)]
+
+
 def load():
     """Load libsearchlite_gpu.so (built by searchlite_amd.build / __graft_entry__.build)."""
     global _lib
@@ -425,6 +456,10 @@ def load():
         "slg_batch_set_composite_after": (i32, [vp, vp]),
         "slg_batch_fetch_composite": (i32, [vp] * 4),
         "slg_search_batch_composite": (i32, [vp, vp, u32, vp, vp, vp, vp, vp, u32, i32] + [vp] * 10),
+        "slg_batch_prepare_term_buckets": (vp, [vp, u32, vp, vp, vp, vp, vp, vp, vp, vp, u32, i32]),
+        "slg_batch_term_buckets_layout": (i32, [vp, vp]),
+        "slg_batch_fetch_term_buckets": (i32, [vp] * 8),
+        "slg_search_batch_term_buckets": (i32, [vp, vp, u32, vp, vp, vp, vp, vp, u32, i32] + [vp] * 14),
         "slg_batch_run": (i32, [vp]),
         "slg_batch_set_stream": (i32, [vp, vp]),
         "slg_batch_sync": (i32, [vp]),

@@ -32,6 +32,14 @@ composite ({"type": "composite", "sources": [{"type": "terms" | "histogram", "na
 AggPlan.composite.  The device returns the `size` smallest packed keys at or above a lower bound with their counts and
 children; composite_lower_bound maps the request's `after` object to that bound, shape_composite renders the page
 (CompositeCollector / finalize_composite, :1689-1842, :3264-3368).
+
+significant_terms and rare_terms ({"type": "significant_terms", "field", "size", "min_doc_count", "background_filter",
+"aggs"} / {"type": "rare_terms", "field", "size", "max_doc_count", "aggs"}, at the root, up to four per request)
+travel beside the aggregation spec as well (slg_batch_prepare_term_buckets): AggPlan.term_buckets.  The device returns
+at most `size` rows per node in the response's order; shape_term_buckets renders them (SignificantTermsCollector,
+RareTermsCollector and finalize, :131-359, :2515-2595).  A background_filter is named through fields[FILTERS], as a
+filter aggregation's filter.  The device counts over all segments before it applies the count bound and `size`, where
+the reference does both per segment first.
 """
 from __future__ import annotations
 
@@ -297,8 +305,12 @@ class AggPlan:
     aggregation, sort = [(sort field id or "_score", "asc" | "desc")]."""
 
     def __init__(self, spec: "N.AggSpec", nodes: List[dict], top_hits: Optional["N.TopHitsSpec"] = None,
-                 top_hits_nodes: Optional[List[dict]] = None, composite: Optional[dict] = None):
+                 top_hits_nodes: Optional[List[dict]] = None, composite: Optional[dict] = None,
+                 term_buckets: Optional[dict] = None):
         self.spec = spec
+        # the request's significant_terms / rare_terms aggregations (None without one): dict(spec = N.TermBucketSpec,
+        # nodes = [dict(name, type, body, field, size, keys, rank, children = the AggPlan of its `aggs`)])
+        self.term_buckets = term_buckets
         self.nodes = nodes
         self.top_hits = top_hits
         self.top_hits_nodes = top_hits_nodes or []
@@ -373,6 +385,74 @@ def _composite_plan(name: str, body: dict, fields: Dict[str, dict]) -> dict:
                 children=children)
 
 
+TERM_BUCKET_TYPES = ("significant_terms", "rare_terms")
+
+
+def _byte_order_rank(name: str, field: str, keys: List[str]):
+    """rank[ord] = the rank of ordinal ord's key in UTF-8 byte order (Rust orders String by its bytes), or None when
+    the dictionary already is in that order (no table: one dependent load less per value)"""
+    raw = [k.encode("utf-8") for k in keys]
+    if len(set(raw)) != len(raw):
+        raise ValueError(f"aggregation {name!r}: the dictionary of {field!r} holds a key twice")
+    order = sorted(range(len(raw)), key=lambda o: raw[o])
+    if order == list(range(len(raw))):
+        return None
+    rank = np.zeros(len(raw), dtype=np.uint32)
+    rank[np.asarray(order, dtype=np.int64)] = np.arange(len(raw), dtype=np.uint32)
+    return rank
+
+
+def _term_bucket_node(name: str, body: dict, fields: Dict[str, dict], out: "N.TermBucketNode") -> dict:
+    """one significant_terms / rare_terms body -> a node of AggPlan.term_buckets, `out` filled; ValueError for what
+    the device does not build"""
+    typ = body["type"]
+    if body.get("sampling") is not None:
+        raise ValueError(f"aggregation {name!r}: sampling is not built on the device")
+    if body.get("size") is None:
+        raise ValueError(f"aggregation {name!r}: {typ} without `size` (all buckets) is not built on the device")
+    size = int(body["size"])
+    if size <= 0 or size > N.MAX_TERM_BUCKET_SIZE:
+        raise ValueError(f"aggregation {name!r}: {typ} size {size} is not built on the device "
+                         f"(1 .. {N.MAX_TERM_BUCKET_SIZE})")
+    if body["field"] not in fields or body["field"] == FILTERS:
+        raise ValueError(f"aggregation {name!r}: field {body['field']!r} is not registered")
+    fd = fields[body["field"]]
+    keys = fd.get("keys")
+    if keys is None:
+        raise ValueError(f"aggregation {name!r}: {typ} needs a keyword field")
+    rank = _byte_order_rank(name, body["field"], keys)
+    out.field, out.size = int(fd["id"]), size
+    out.ord_rank = None if rank is None else rank.ctypes.data
+    out.background_filter = -1
+    if typ == "significant_terms":
+        out.kind = N.TERMS_SIGNIFICANT
+        mdc = body.get("min_doc_count")
+        out.doc_count_bound = 1 if mdc is None else int(mdc)
+        if body.get("background_filter") is not None:
+            if not callable(fields.get(FILTERS)):
+                raise ValueError(f"aggregation {name!r}: a background_filter needs fields[{FILTERS!r}], the map from "
+                                 "a filter to a registered filter id")
+            out.background_filter = int(fields[FILTERS](body["background_filter"]))
+    else:
+        out.kind = N.TERMS_RARE
+        mdc = body.get("max_doc_count")
+        out.doc_count_bound = 1 if mdc is None else int(mdc)
+    children = agg_spec(body.get("aggs") or {}, fields)
+    if children.top_hits_nodes or children.composite is not None or children.term_buckets is not None:
+        raise ValueError(f"aggregation {name!r}: top_hits, composite, significant_terms or rare_terms under a {typ} "
+                         "is not built on the device")
+    for nd in children.nodes:
+        if nd["parent"] >= 0:
+            raise ValueError(f"aggregation {name!r}: only one level under a {typ} is built")
+        if nd["type"] in VALUE_TYPES:
+            raise ValueError(f"aggregation {name!r}: a {nd['type']} child of a {typ} is not built on the device")
+    out.n_children = len(children.nodes)
+    for i in range(min(len(children.nodes), N.MAX_AGGS)):
+        C.memmove(C.addressof(out.children[i]), C.addressof(children.spec.nodes[i]), C.sizeof(N.AggNode))
+    return dict(name=name, type=typ, body=body, field=body["field"], size=size, keys=list(keys), rank=rank,
+                children=children)
+
+
 def _top_hits_node(name: str, body: dict, parent: int, fields: Dict[str, dict]) -> dict:
     """one top_hits body -> dict(name, parent, from, size, sort); ValueError for what the device does not build"""
     if body.get("aggs"):
@@ -427,9 +507,15 @@ def agg_spec(aggs: Dict[str, dict], fields: Dict[str, dict], top_hits_max_entrie
     nodes: List[dict] = []
     th_nodes: List[dict] = []
     composite: List[dict] = []
+    term_buckets: List[tuple] = []  # (name, body) of the root significant_terms / rare_terms aggregations
 
     def add(name, body, parent):
         typ = body.get("type")
+        if typ in TERM_BUCKET_TYPES:  # (beside the spec, as a composite: at the root only)
+            if parent >= 0:
+                raise ValueError(f"aggregation {name!r}: a {typ} below another aggregation is not built on the device")
+            term_buckets.append((name, body))
+            return
         if typ == "composite":  # (beside the spec, as top_hits: at the root only, one per request)
             if parent >= 0:
                 raise ValueError(f"aggregation {name!r}: a composite below another aggregation is not built on the device")
@@ -530,7 +616,19 @@ def agg_spec(aggs: Dict[str, dict], fields: Dict[str, dict], top_hits_max_entrie
             for i, (field, order) in enumerate(th["sort"]):
                 t.sort.field[i] = N.SORT_SCORE if field == "_score" else field
                 t.sort.order[i] = N.ORDER_ASC if order == "asc" else N.ORDER_DESC
-    return AggPlan(spec, nodes, th_spec, th_nodes, composite[0] if composite else None)
+    tb = None
+    if len(term_buckets) > N.MAX_TERM_BUCKET_NODES:
+        raise ValueError(f"more than {N.MAX_TERM_BUCKET_NODES} significant_terms / rare_terms aggregations are not built "
+                         "on the device")
+    if term_buckets:
+        if composite or th_nodes:
+            raise ValueError("significant_terms / rare_terms together with a composite or top_hits aggregation is not "
+                             "built on the device")
+        tb_spec = N.TermBucketSpec()
+        tb_spec.n_nodes = len(term_buckets)
+        tb = dict(spec=tb_spec, nodes=[_term_bucket_node(name, body, fields, tb_spec.nodes[i])
+                                       for i, (name, body) in enumerate(term_buckets)])
+    return AggPlan(spec, nodes, th_spec, th_nodes, composite[0] if composite else None, tb)
 
 
 def _stats(cell) -> dict:
@@ -635,8 +733,34 @@ def shape_composite(plan: AggPlan, layout: dict, page: dict, q: int) -> dict:
     return out
 
 
+def shape_term_buckets(plan: AggPlan, layout: dict, fetched: dict, q: int) -> Dict[str, dict]:
+    """The responses of query q's significant_terms / rare_terms aggregations by name: {"type": "significant_terms",
+    "buckets": [{"key", "doc_count", "bg_count", "score", "aggregations"}], "doc_count", "bg_count"} in (score desc,
+    count desc, key asc) order and {"type": "rare_terms", "buckets": [{"key", "doc_count", "aggregations"}]} in (count
+    asc, key asc) order (finalize, :2515-2595).  layout: PreparedBatch.term_buckets_layout(); fetched:
+    PreparedBatch.term_buckets()."""
+    out = {}
+    for nd, lay, got in zip(plan.term_buckets["nodes"], layout["nodes"], fetched["nodes"]):
+        sig = nd["type"] == "significant_terms"
+        kids = nd["children"]
+        buckets = []
+        for r in range(int(got["n_buckets"][q])):
+            b = {"key": nd["keys"][int(got["ords"][q, r])], "doc_count": int(got["doc_counts"][q, r])}
+            if sig:
+                b["bg_count"], b["score"] = int(got["bg_counts"][q, r]), float(got["scores"][q, r])
+            if kids.nodes:  # (the children as roots, at row r: as a composite's)
+                b["aggregations"] = shape(kids, lay["children"], got["children"], q, prow=r)
+            buckets.append(b)
+        res = {"type": nd["type"], "buckets": buckets}
+        if sig:
+            res["doc_count"], res["bg_count"] = int(got["doc_count"][q]), int(got["bg_count"][q])
+        out[nd["name"]] = res
+    return out
+
+
 def shape(plan: AggPlan, layout: List[dict], tables: List[np.ndarray], q: int, top_hits: Optional[dict] = None,
-          matched=None, prow: int = 0, composite: Optional[tuple] = None) -> Dict[str, dict]:
+          matched=None, prow: int = 0, composite: Optional[tuple] = None,
+          term_buckets: Optional[tuple] = None) -> Dict[str, dict]:
     """The response of query q: name -> AggregationResponse as a dict ({"type": ..., "buckets": [{"key",
     "doc_count", "aggregations"}]} / stats).  layout: PreparedBatch.agg_layout(); tables: PreparedBatch.aggs().
     top_hits: PreparedBatch.top_hits() of a plan with top_hits nodes, matched: PreparedBatch.matched_counts() (a
@@ -644,7 +768,9 @@ def shape(plan: AggPlan, layout: List[dict], tables: List[np.ndarray], q: int, t
     bucket.  `fields` and `snippet` of a hit are doc-store work and are not part of it.  ValueError for a query
     whose bucket runs did not fit (status 1: the CPU path).  prow: the parent row the roots are read at (0; a
     composite's children are shaped as roots at their bucket's row).  composite: (PreparedBatch.composite_layout(),
-    PreparedBatch.composite()) of a plan with a composite: its response goes under its name (shape_composite)."""
+    PreparedBatch.composite()) of a plan with a composite: its response goes under its name (shape_composite).
+    term_buckets: (PreparedBatch.term_buckets_layout(), PreparedBatch.term_buckets()) of a plan with significant_terms
+    or rare_terms aggregations: their responses go under their names (shape_term_buckets)."""
     if plan.top_hits_nodes and top_hits is not None and int(top_hits["status"][q]) != 0:
         raise ValueError(f"query {q}: the top_hits bucket runs did not fit max_entries (CPU path)")
 
@@ -759,4 +885,6 @@ def shape(plan: AggPlan, layout: List[dict], tables: List[np.ndarray], q: int, t
         out.update(top_hits_under(-1, 0, int(matched[q])))
     if plan.composite is not None and composite is not None:
         out[plan.composite["name"]] = shape_composite(plan, composite[0], composite[1], q)
+    if plan.term_buckets is not None and term_buckets is not None:
+        out.update(shape_term_buckets(plan, term_buckets[0], term_buckets[1], q))
     return out

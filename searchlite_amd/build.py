@@ -56,7 +56,7 @@ def build_gpu(force: bool = False, verbose: bool = False, stamps: bool = False, 
     out_lib = os.path.join(LIBDIR, f"libsearchlite_gpu_{tag}.so") if tag else GPU_LIB
     os.makedirs(objdir, exist_ok=True)
     hdrs = [os.path.join(CSRC, h) for h in ("slg_desc.hpp", "slg_wave.hpp", "slg_kernels.hpp", "slg_rerank.hpp", "slg_score.hpp", "slg_score_uni4.hpp",
-                                           "slg_score_multi.hpp", "slg_plan.hpp", "slg_vsearch.hpp", "slg_hybrid.hpp", "slg_aggs.hpp", "slg_date.hpp", "slg_rescore.hpp", "slg_clause.hpp", "slg_bool.hpp", "slg_booltree.hpp", "slg_phrase.hpp", "slg_fscore.hpp", "slg_script.hpp", "slg_scan.hpp", "slg_collapse.hpp", "slg_tophits.hpp", "slg_composite.hpp", "slg_filter.hpp", "slg_host.hpp", "slg_stage.hpp", "slg_expand.hpp", "slg_expand_merge.hpp", "slg_suggest.hpp", "slg_suggest_host.hpp")]
+                                           "slg_score_multi.hpp", "slg_plan.hpp", "slg_vsearch.hpp", "slg_hybrid.hpp", "slg_aggs.hpp", "slg_date.hpp", "slg_rescore.hpp", "slg_clause.hpp", "slg_bool.hpp", "slg_booltree.hpp", "slg_phrase.hpp", "slg_fscore.hpp", "slg_script.hpp", "slg_scan.hpp", "slg_collapse.hpp", "slg_tophits.hpp", "slg_composite.hpp", "slg_cpset.hpp", "slg_termbuckets.hpp", "slg_filter.hpp", "slg_host.hpp", "slg_stage.hpp", "slg_expand.hpp", "slg_expand_merge.hpp", "slg_suggest.hpp", "slg_suggest_host.hpp")]
     hdrs.append(os.path.join(_HERE, "..", "include", "searchlite_gpu.h"))
     compile_flags = [f for f in HIPCC_FLAGS if f != "-shared"] + (["-DSLG_STAMPS"] if stamps else []) \
         + [f"-D{d}" for d in defines]
@@ -65,7 +65,7 @@ def build_gpu(force: bool = False, verbose: bool = False, stamps: bool = False, 
     jobs = [(os.path.join(CSRC, "slg_score_inst.hip"), os.path.join(objdir, f"slg_score_k{kr}.o"),
              [f"-DSLG_INST_KREGS={kr}"]) for kr in kregs]
     # the host side of the C ABI, one unit per concern (slg_host.hpp is what they share)
-    for unit in ("slg_batch", "slg_vsearch", "slg_hybrid", "slg_aggs", "slg_rescore", "slg_bool", "slg_booltree", "slg_phrase", "slg_fscore", "slg_script", "slg_scan", "slg_collapse", "slg_tophits", "slg_composite", "slg_expand", "slg_suggest", "slg_rerank", "slg_index", "slg_shard"):
+    for unit in ("slg_batch", "slg_vsearch", "slg_hybrid", "slg_aggs", "slg_rescore", "slg_bool", "slg_booltree", "slg_phrase", "slg_fscore", "slg_script", "slg_scan", "slg_collapse", "slg_tophits", "slg_composite", "slg_termbuckets", "slg_expand", "slg_suggest", "slg_rerank", "slg_index", "slg_shard"):
         jobs.append((os.path.join(CSRC, unit + ".hip"), os.path.join(objdir, unit + ".o"), []))
     # the request coalescer: host code over the public ABI
     jobs.append((os.path.join(CSRC, "slg_coalesce.hip"), os.path.join(objdir, "slg_coalesce.o"), []))

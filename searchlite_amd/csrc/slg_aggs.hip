@@ -459,8 +459,8 @@ extern "C" {
 int slg_batch_agg_layout(const slg_batch *b, slg_agg_layout *out) {
   return guarded([&] {
     SLG_REQUIRE(b != nullptr, "batch is NULL");
-    SLG_REQUIRE(b->aggs || b->composite, "not an aggregation batch (slg_batch_prepare_aggs)");
-    if (!b->aggs) return;  // (a composite batch without an aggregation spec: no node)
+    SLG_REQUIRE(b->aggs || b->composite || b->term_buckets, "not an aggregation batch (slg_batch_prepare_aggs)");
+    if (!b->aggs) return;  // (a composite or term bucket batch without an aggregation spec: no node)
     SLG_REQUIRE(out != nullptr, "out is NULL");
     std::copy(b->agg_layout.begin(), b->agg_layout.end(), out);
   });
@@ -485,12 +485,16 @@ int slg_batch_fetch_agg_values(slg_batch *b, uint64_t *values) {
 int slg_batch_fetch_aggs(slg_batch *b, uint64_t *counts, slg_agg_stats *stats) {
   return guarded([&] {
     SLG_REQUIRE_LIVE(b);
-    SLG_REQUIRE(b->aggs || b->composite, "not an aggregation batch (slg_batch_prepare_aggs)");
+    SLG_REQUIRE(b->aggs || b->composite || b->term_buckets, "not an aggregation batch (slg_batch_prepare_aggs)");
     SLG_REQUIRE(b->launched, "the batch has not run");
     // a composite batch: the composite's cells lie behind the spec's in every query's row (tables of their own on
     // the device: agg_kernel's tables keep their stride)
     const size_t ac = b->aggs ? b->agg_count_cells : 0u, as = b->aggs ? b->agg_stats_cells : 0u;
-    const size_t cc = b->composite ? b->cp_count_cells : 0u, cs = b->composite ? b->cp_stats_cells : 0u;
+    // (a term bucket batch: the same with the children's tables of its nodes; never both kinds in one batch)
+    const size_t cc = b->composite ? b->cp_count_cells : b->term_buckets ? b->tb_count_cells : 0u;
+    const size_t cs = b->composite ? b->cp_stats_cells : b->term_buckets ? b->tb_stats_cells : 0u;
+    const DevBuf &d_cc = b->term_buckets ? b->d_tb_counts : b->d_cp_counts;
+    const DevBuf &d_cs = b->term_buckets ? b->d_tb_stats : b->d_cp_stats;
     const size_t nq = b->nq;
     SLG_REQUIRE(nq * (ac + cc) == 0 || counts != nullptr, "counts is NULL");
     SLG_REQUIRE(nq * (as + cs) == 0 || stats != nullptr, "stats is NULL");
@@ -501,9 +505,9 @@ int slg_batch_fetch_aggs(slg_batch *b, uint64_t *counts, slg_agg_stats *stats) {
     if (!hc.empty()) SLG_HIP(hipMemcpyAsync(hc.data(), b->d_agg_counts.p, hc.size() * 4, hipMemcpyDeviceToHost, st));
     if (!hs.empty())
       SLG_HIP(hipMemcpyAsync(hs.data(), b->d_agg_stats.p, hs.size() * sizeof(slg::AggStatDev), hipMemcpyDeviceToHost, st));
-    if (!hcc.empty()) SLG_HIP(hipMemcpyAsync(hcc.data(), b->d_cp_counts.p, hcc.size() * 4, hipMemcpyDeviceToHost, st));
+    if (!hcc.empty()) SLG_HIP(hipMemcpyAsync(hcc.data(), d_cc.p, hcc.size() * 4, hipMemcpyDeviceToHost, st));
     if (!hcs.empty())
-      SLG_HIP(hipMemcpyAsync(hcs.data(), b->d_cp_stats.p, hcs.size() * sizeof(slg::AggStatDev), hipMemcpyDeviceToHost, st));
+      SLG_HIP(hipMemcpyAsync(hcs.data(), d_cs.p, hcs.size() * sizeof(slg::AggStatDev), hipMemcpyDeviceToHost, st));
     SLG_HIP(wait_stream(st));
     auto value = [](unsigned long long key) {  // the inverse of agg_f64_key
       const unsigned long long bits = (key >> 63) ? (key & 0x7FFFFFFFFFFFFFFFull) : ~key;

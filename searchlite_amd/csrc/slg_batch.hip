@@ -148,7 +148,9 @@ void slghost::release_batch_buffers(slg_batch *b, bool to_pool) {
                     &b->d_agg_values, &b->d_agg_scratch,
                     &b->d_rs_desc, &b->d_rs_side, &b->d_bool_desc, &b->d_phrase_desc, &b->d_booltree_desc, &b->d_fscore_desc, &b->d_script_desc,
                     &b->d_cl_desc, &b->d_cl_side, &b->d_th_desc, &b->d_th_out, &b->d_th_entries, &b->d_th_cursors,
-                    &b->d_cp_desc, &b->d_cp_ranks, &b->d_cp_lower, &b->d_cp_out, &b->d_cp_counts, &b->d_cp_stats};
+                    &b->d_cp_desc, &b->d_cp_ranks, &b->d_cp_lower, &b->d_cp_out, &b->d_cp_counts, &b->d_cp_stats,
+                    &b->d_tb_desc, &b->d_tb_ranks, &b->d_tb_bg, &b->d_tb_fg, &b->d_tb_bgsum, &b->d_tb_bits, &b->d_tb_out,
+                    &b->d_tb_sorted, &b->d_tb_counts, &b->d_tb_stats};
   for (DevBuf *d : bufs) {
     if (!to_pool) d->pool = nullptr;
     d->release();
@@ -210,6 +212,7 @@ slg_batch *slghost::prepare_impl(const PrepareRequest &r) {
     if (r.collapse.on) slgplan::check_collapse(r.collapse.spec, k);
     if (r.top_hits.on) slgplan::check_top_hits(r.top_hits.spec, r.aggs.spec);
     if (r.composite.on) composite_check_spec(r.composite.spec);
+    if (r.term_buckets.on) term_buckets_check_spec(r.term_buckets.spec);
     SLG_REQUIRE(ix != nullptr, "index is NULL");
     SLG_REQUIRE(!after || q_cursor != nullptr, "q_cursor is NULL");
     if (sort) {  // (checked before planning: the planner never sees a sort spec it cannot run)
@@ -246,7 +249,7 @@ slg_batch *slghost::prepare_impl(const PrepareRequest &r) {
     in.strategy = r.strategy;
     in.filter_live = filter_live.data();
     in.n_filters = filter_live.size();
-    in.sorted = sort != nullptr || after || hybrid || r.aggs.on || r.top_hits.on || r.composite.on || r.boolean.on || r.booltree.on || r.fscore.on || r.script.on;
+    in.sorted = sort != nullptr || after || hybrid || r.aggs.on || r.top_hits.on || r.composite.on || r.term_buckets.on || r.boolean.on || r.booltree.on || r.fscore.on || r.script.on;
     SortBinding sorting;  // the columns of the sort parts in the batch's state
     if (sort) sorting = bind_sort(*snap, *sort, "", "part ");
     // the cursors as the key words the select kernel compares (against the same snapshot's field kinds)
@@ -371,7 +374,7 @@ slg_batch *slghost::prepare_impl(const PrepareRequest &r) {
       SLG_HIP(hipMemcpy(b->d_sort_cols.p, sorting.cols.data(), sorting.cols.size() * sizeof(slg::SortColDev),
                         hipMemcpyHostToDevice));
     }
-    if (b->sorted || b->after || r.aggs.on || r.top_hits.on || r.composite.on) b->d_matched.alloc_pooled(&ix->pool, (size_t)std::max<uint32_t>(nq, 1) * 8);
+    if (b->sorted || b->after || r.aggs.on || r.top_hits.on || r.composite.on || r.term_buckets.on) b->d_matched.alloc_pooled(&ix->pool, (size_t)std::max<uint32_t>(nq, 1) * 8);
     if (b->after) {
       b->d_cursor.alloc_pooled(&ix->pool, cursor_words.size() * 4);
       SLG_HIP(hipMemcpy(b->d_cursor.p, cursor_words.data(), cursor_words.size() * 4, hipMemcpyHostToDevice));
@@ -402,6 +405,7 @@ slg_batch *slghost::prepare_impl(const PrepareRequest &r) {
     if (r.aggs.on) agg_attach(b, *r.aggs.spec);
     if (r.top_hits.on) top_hits_attach(b, *r.top_hits.spec);
     if (r.composite.on) composite_attach(b, *r.composite.spec);
+    if (r.term_buckets.on) term_buckets_attach(b, *r.term_buckets.spec);
     if (r.rescore.on) rescore_attach(b, rescore_plan);
     if (r.phrase.on) {
       bool_attach(b, phrase_plan.bools);
@@ -587,6 +591,7 @@ int slg_batch_run(slg_batch *b) {
     if (b->aggs) agg_launch(b, st);  // (after the select: the tables of every accepted candidate)
     if (b->top_hits) top_hits_launch(b, st);  // (behind agg_kernel: the parents' count rows are read)
     if (b->composite) composite_launch(b, st);  // (the select, then the collect into the selected rows)
+    if (b->term_buckets) term_buckets_launch(b, st);  // (the count walk, the select, the children's collect)
     if (b->rescore) rescore_launch(b, st);  // (behind the rows: the first w of every query are scored again)
     if (b->collapse) collapse_launch(b, st);  // (behind the rows: they are read, never written)
   });
@@ -785,6 +790,9 @@ struct HostOut {
   float *th_score = nullptr;
   uint64_t *cp_keys = nullptr;  // (a composite batch)
   uint32_t *cp_n_buckets = nullptr, *cp_has_more = nullptr;
+  uint32_t *tb_ords = nullptr, *tb_n_buckets = nullptr;  // (a term bucket batch)
+  uint64_t *tb_doc_counts = nullptr, *tb_bg_counts = nullptr, *tb_score_bits = nullptr, *tb_node_dc = nullptr,
+           *tb_node_bg = nullptr;
 };
 // A prepared batch (null: prepare failed and set the thread's error) run to the caller's host arrays and
 // destroyed: the first error is the one reported
@@ -793,8 +801,11 @@ int run_to_host(slg_batch *b, const HostOut &o) {
   int rc = slg_batch_run(b);
   if (rc == SLG_OK) rc = slg_batch_fetch(b, o.doc, o.seg, o.score, o.count, o.stats);
   if (rc == SLG_OK && o.matched) rc = slg_batch_matched_counts(b, o.matched);
-  if (rc == SLG_OK && (b->aggs || b->composite)) rc = slg_batch_fetch_aggs(b, o.agg_counts, o.agg_stats);
+  if (rc == SLG_OK && (b->aggs || b->composite || b->term_buckets)) rc = slg_batch_fetch_aggs(b, o.agg_counts, o.agg_stats);
   if (rc == SLG_OK && b->composite) rc = slg_batch_fetch_composite(b, o.cp_keys, o.cp_n_buckets, o.cp_has_more);
+  if (rc == SLG_OK && b->term_buckets)
+    rc = slg_batch_fetch_term_buckets(b, o.tb_ords, o.tb_doc_counts, o.tb_bg_counts, o.tb_score_bits, o.tb_n_buckets,
+                                      o.tb_node_dc, o.tb_node_bg);
   if (rc == SLG_OK && b->aggs && b->agg_value_nodes) rc = slg_batch_fetch_agg_values(b, o.agg_values);
   if (rc == SLG_OK && b->top_hits) rc = slg_batch_fetch_top_hits(b, o.th_doc, o.th_seg, o.th_score, o.th_count, o.th_status);
   if (rc == SLG_OK && b->rescore) rc = slg_batch_fetch_rescore(b, o.first_score, o.rescore_score, o.rescored);
@@ -836,7 +847,7 @@ int slg_batch_matched_counts(slg_batch *b, uint64_t *out_matched) {
   return guarded([&] {
     SLG_REQUIRE_LIVE(b);
     if (b->hybrid) throw SlgError(SLG_ERR_UNSUPPORTED, "a hybrid batch has no matched counts");
-    SLG_REQUIRE(b->sorted || b->after || b->aggs || b->scan || b->top_hits || b->composite,
+    SLG_REQUIRE(b->sorted || b->after || b->aggs || b->scan || b->top_hits || b->composite || b->term_buckets,
                 "not a sorted, cursor, aggregation or scan batch (slg_batch_prepare_sorted / _after / _aggs / _scan)");
     SLG_REQUIRE(b->launched, "the batch has not run");
     SLG_REQUIRE(b->nq == 0 || out_matched != nullptr, "out_matched is NULL");
@@ -955,6 +966,41 @@ int slg_search_batch_composite(slg_index *ix, const slg_query *queries, uint32_t
   o.cp_has_more = cp_has_more;
   return run_to_host(slg_batch_prepare_composite(ix, nq, fq.offs.data(), fq.tids.data(), fq.ws.data(), plans, q_filter,
                                                  sort, aggs, composite, k, strategy),
+                     o);
+}
+
+slg_batch *slg_batch_prepare_term_buckets(slg_index *ix, uint32_t nq, const uint32_t *q_offsets,
+                                          const uint32_t *q_term_ids, const float *q_weights,
+                                          const slg_score_plans *plans, const int32_t *q_filter,
+                                          const slg_sort_spec *sort, const slg_agg_spec *aggs,
+                                          const slg_term_bucket_spec *spec, uint32_t k, int strategy) {
+  PrepareRequest r{ix, nq, q_offsets, q_term_ids, q_weights, plans, q_filter, k, strategy};
+  r.sort = if_given(sort);
+  r.aggs = if_given(aggs);
+  r.term_buckets = {true, spec};
+  return prepare_impl(r);
+}
+
+int slg_search_batch_term_buckets(slg_index *ix, const slg_query *queries, uint32_t nq, const slg_score_plans *plans,
+                                  const int32_t *q_filter, const slg_sort_spec *sort, const slg_agg_spec *aggs,
+                                  const slg_term_bucket_spec *spec, uint32_t k, int strategy, uint32_t *out_doc,
+                                  uint32_t *out_seg, float *out_score, uint32_t *out_count, uint64_t *out_matched,
+                                  uint64_t *counts, slg_agg_stats *stats, uint32_t *tb_ords, uint64_t *tb_doc_counts,
+                                  uint64_t *tb_bg_counts, uint64_t *tb_score_bits, uint32_t *tb_n_buckets,
+                                  uint64_t *tb_node_doc_count, uint64_t *tb_node_bg_count) {
+  FlatQueries fq;
+  const int rc = flatten_queries(ix, queries, nq, &fq);
+  if (rc != SLG_OK) return rc;
+  HostOut o{out_doc, out_seg, out_score, out_count, nullptr, out_matched, nullptr, counts, stats};
+  o.tb_ords = tb_ords;
+  o.tb_doc_counts = tb_doc_counts;
+  o.tb_bg_counts = tb_bg_counts;
+  o.tb_score_bits = tb_score_bits;
+  o.tb_n_buckets = tb_n_buckets;
+  o.tb_node_dc = tb_node_doc_count;
+  o.tb_node_bg = tb_node_bg_count;
+  return run_to_host(slg_batch_prepare_term_buckets(ix, nq, fq.offs.data(), fq.tids.data(), fq.ws.data(), plans,
+                                                    q_filter, sort, aggs, spec, k, strategy),
                      o);
 }
 

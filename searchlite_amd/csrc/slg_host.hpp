@@ -1,5 +1,5 @@
 // slg_host.hpp — what the host translation units of the C ABI share (slg_index.hip, slg_batch.hip,
-// slg_shard.hip, slg_rerank.hip, slg_vsearch.hip, slg_hybrid.hip, slg_aggs.hip, slg_rescore.hip, slg_bool.hip, slg_booltree.hip, slg_phrase.hip, slg_fscore.hip, slg_script.hip, slg_scan.hip, slg_collapse.hip, slg_tophits.hip, slg_composite.hip): the error plumbing, device memory, the host
+// slg_shard.hip, slg_rerank.hip, slg_vsearch.hip, slg_hybrid.hip, slg_aggs.hip, slg_rescore.hip, slg_bool.hip, slg_booltree.hip, slg_phrase.hip, slg_fscore.hip, slg_script.hip, slg_scan.hip, slg_collapse.hip, slg_tophits.hip, slg_composite.hip, slg_termbuckets.hip): the error plumbing, device memory, the host
 // structures behind the opaque handles and the small helpers several entry points use.  Private: not
 // installed, not part of include/.  No kernel header is included here — each unit includes the one
 // whose kernels it launches (slg_stage.hpp, slg_kernels.hpp, slg_rerank.hpp, slg_vsearch.hpp, slg_hybrid.hpp; the shard
@@ -637,6 +637,30 @@ struct slg_batch {
   DevBuf d_cp_lower;   // u64[nq] the inclusive lower bounds (slg_batch_set_composite_after)
   DevBuf d_cp_out;     // u64 keys [nq * size], then u32 n_buckets [nq], has_more [nq], the error word
   DevBuf d_cp_counts, d_cp_stats;  // u32[nq * cp_count_cells], slg::AggStatDev[nq * cp_stats_cells]
+  // term bucket batch (slg_batch_prepare_term_buckets): an aggregation batch, or a plain / sorted one planned as
+  // such; term_bucket_count_kernel, _select_kernel and (a node with children) _collect_kernel run behind agg_kernel
+  // (slg_termbuckets.hip).  The children's cells lie behind the aggregation spec's in the arrays of
+  // slg_batch_fetch_aggs, in tables of their own on the device
+  bool term_buckets = false;
+  slg_term_bucket_spec tb_spec{};  // (ord_rank: not kept, the ranks are on the device)
+  slg_term_bucket_layout tb_layout{};
+  uint32_t tb_fg_cells = 0, tb_bits_words = 0;      // of one query: cells of fg / bgsum, presence words
+  uint32_t tb_count_cells = 0, tb_stats_cells = 0;  // of one query: the children's tables of every node
+  bool tb_lds = false;  // the count walk's fg cells (4 B each) fit SLG_AGG_LDS_BYTES
+  struct TbNodeTables {  // a node with children: its tables in a query's term bucket rows, its part of d_tb_desc
+    uint32_t cnt_off = 0, st_off = 0, count_cells = 0, stats_cells = 0;
+    size_t nodes_off = 0, cols_off = 0;
+    bool lds = false, ext = false;
+  };
+  TbNodeTables tb_tables[SLG_MAX_TERM_BUCKET_NODES];
+  size_t tb_cols_off = 0;  // byte offset of the nodes' columns in d_tb_desc
+  DevBuf d_tb_desc;   // slg::TermBucketNodeDev[n], ColumnDev[n * n_segs], per node AggNodeDev[], ColumnDev[] of its children
+  DevBuf d_tb_ranks;  // u32: ord_rank and its inverse of every ranked node, back to back
+  DevBuf d_tb_bg;     // u32 [n_segs][n_ords + 1] per distinct (field, background filter): bg_count_kernel's tables
+  DevBuf d_tb_fg, d_tb_bgsum, d_tb_bits;  // u32 / u64 [nq * tb_fg_cells], u32 [nq * tb_bits_words]
+  DevBuf d_tb_out;    // the arrays of slg_batch_fetch_term_buckets and the error word (slg_termbuckets.hip: OutBlock)
+  DevBuf d_tb_sorted; // u32 [nq * rows] the kept ordinals in ordinal order, then [nq * rows] the row of each
+  DevBuf d_tb_counts, d_tb_stats;  // u32[nq * tb_count_cells], slg::AggStatDev[nq * tb_stats_cells]
 };
 
 namespace slghost __attribute__((visibility("hidden"))) {
@@ -762,6 +786,7 @@ struct PrepareRequest {
   Asked<slg_collapse_spec> collapse;
   Asked<slg_top_hits_spec> top_hits;  // slg_batch_prepare_top_hits (aggs: on when its spec is given)
   Asked<slg_composite_spec> composite;  // slg_batch_prepare_composite (aggs: on when its spec is given)
+  Asked<slg_term_bucket_spec> term_buckets;  // slg_batch_prepare_term_buckets (aggs: on when its spec is given)
 };
 // a spec that is a kind of its own only when it is given (the sort of a bool, phrase, cursor or agg batch)
 template <typename T>
@@ -906,6 +931,13 @@ struct CompositeChildTables {
   bool ext = false;
 };
 CompositeChildTables agg_plan_children(const IndexState &S, const slg_composite_spec &spec, uint64_t cells_before);
+// slg_termbuckets.hip: the checks of a term bucket spec that need no index (throws; after agg_check_spec); the spec
+// against the batch's state (columns, filters, ranks, the background tables, the children's tables) onto the device
+// (throws; the batch is otherwise prepared, agg_attach has run); the launches behind agg_kernel (without an
+// aggregation spec: behind the select)
+void term_buckets_check_spec(const slg_term_bucket_spec *spec);
+void term_buckets_attach(slg_batch *b, const slg_term_bucket_spec &spec);
+void term_buckets_launch(slg_batch *b, hipStream_t st);
 
 // slg_vsearch.hip: one vector search or hybrid call, checked against one state of the index ...
 struct VsCall {

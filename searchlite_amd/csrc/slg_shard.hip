@@ -153,6 +153,7 @@ int run_sharded_impl(slg_batch *b, slg_shard_group *g, bool have_seq, uint64_t s
     if (b->collapse) throw SlgError(SLG_ERR_UNSUPPORTED, "a collapse batch does not run sharded");
     if (b->top_hits) throw SlgError(SLG_ERR_UNSUPPORTED, "a top_hits batch does not run sharded");
     if (b->composite) throw SlgError(SLG_ERR_UNSUPPORTED, "a composite batch does not run sharded");
+    if (b->term_buckets) throw SlgError(SLG_ERR_UNSUPPORTED, "a term bucket batch does not run sharded");
     if (b->scan) throw SlgError(SLG_ERR_UNSUPPORTED, "a scan batch does not run sharded");
   });
   if (rc != SLG_OK) return rc;
@@ -292,6 +293,7 @@ int slg_batch_fetch_sharded(slg_batch *b, uint32_t *out_doc, uint32_t *out_seg, 
     if (b->collapse) throw SlgError(SLG_ERR_UNSUPPORTED, "a collapse batch does not run sharded");
     if (b->top_hits) throw SlgError(SLG_ERR_UNSUPPORTED, "a top_hits batch does not run sharded");
     if (b->composite) throw SlgError(SLG_ERR_UNSUPPORTED, "a composite batch does not run sharded");
+    if (b->term_buckets) throw SlgError(SLG_ERR_UNSUPPORTED, "a term bucket batch does not run sharded");
     if (b->scan) throw SlgError(SLG_ERR_UNSUPPORTED, "a scan batch does not run sharded");
     SLG_REQUIRE(b->nq == 0 || out_count != nullptr, "out_count is NULL");
     SLG_REQUIRE(b->nq == 0 || b->k == 0 || (out_doc && out_seg && out_score), "output array is NULL");

@@ -657,7 +657,7 @@ class GpuIndex:
                 q_min_match=None, sort=None, cursors=None, hybrid=False, aggs=None,
                 rescore=None, clauses=None, phrases=None, fscore=None, collapse=None,
                 clause_tree=None, script=None, script_order="outer", top_hits=None,
-                composite=None) -> "PreparedBatch":
+                composite=None, term_buckets=None) -> "PreparedBatch":
         """q_leaf / q_plan / q_tie / q_nleaves: score plans; leaf_group / group_plan / group_tie with
         their per-query offsets: two-level plans; q_node_offsets / node_kind / node_tie / node_parent:
         trees of any shape, node by node in pre-order (slg_batch_prepare_plans, slg_score_plans);
@@ -678,12 +678,30 @@ class GpuIndex:
         function_score{query: script_score}; top_hits: an N.TopHitsSpec (an aggs.AggPlan passed as aggs brings its
         own) -> slg_batch_prepare_top_hits (score order or with sort, with aggs or without;
         PreparedBatch.top_hits); composite: an N.CompositeSpec (an aggs.AggPlan passed as aggs brings its own) ->
-        slg_batch_prepare_composite (score order or with sort, with aggs or without; PreparedBatch.composite)."""
+        slg_batch_prepare_composite (score order or with sort, with aggs or without; PreparedBatch.composite);
+        term_buckets: an N.TermBucketSpec (an aggs.AggPlan passed as aggs brings its own) ->
+        slg_batch_prepare_term_buckets (score order or with sort, with aggs or without; PreparedBatch.term_buckets)."""
         return PreparedBatch(self, q_offsets, q_terms, q_weights, k, strategy, q_filter,
                              q_leaf, q_plan, q_tie, q_nleaves, q_leaf_offsets, leaf_group,
                              q_group_offsets, group_plan, group_tie, q_node_offsets, node_kind, node_tie, node_parent,
                              q_min_match, sort, cursors, hybrid, aggs, rescore, clauses, phrases, fscore, collapse,
-                             clause_tree, script, script_order, top_hits, composite)
+                             clause_tree, script, script_order, top_hits, composite, term_buckets)
+
+    def search_term_buckets(self, q_offsets, q_terms, q_weights, k: int, aggs, sort=None, strategy: int = Wand,
+                            q_filter=None, term_buckets=None, **plans):
+        """Batch search with significant_terms / rare_terms aggregations (slg_batch_prepare_term_buckets).  aggs: an
+        aggs.AggPlan with such nodes, or an N.AggSpec / None with term_buckets an N.TermBucketSpec.
+        -> (doc, seg, score, count, matched, tables, layout, buckets): as search_aggs (tables and layout empty
+        without an aggregation node), and the dict of PreparedBatch.term_buckets."""
+        b = self.prepare(q_offsets, q_terms, q_weights, k, strategy, q_filter, sort=sort, aggs=aggs,
+                         term_buckets=term_buckets, **plans)
+        try:
+            b.run()
+            has = b.agg_spec is not None
+            return b.fetch() + (b.matched_counts(), b.aggs() if has else [], b.agg_layout() if has else [],
+                                b.term_buckets())
+        finally:
+            b.close()
 
     def prepare_composite(self, q_offsets, q_terms, q_weights, k: int, aggs, sort=None, strategy: int = Wand,
                           q_filter=None, composite=None, **plans) -> "PreparedBatch":
@@ -1260,7 +1278,7 @@ class PreparedBatch:
                  group_tie=None, q_node_offsets=None, node_kind=None, node_tie=None, node_parent=None,
                  q_min_match=None, sort=None, cursors=None, hybrid=False, aggs=None, rescore=None, clauses=None,
                  phrases=None, fscore=None, collapse=None, clause_tree=None, script=None, script_order="outer",
-                 top_hits=None, composite=None):
+                 top_hits=None, composite=None, term_buckets=None):
         self.index = index
         self._lib = index._lib
         q_offsets = np.ascontiguousarray(q_offsets, dtype=np.uint32)
@@ -1320,7 +1338,26 @@ class PreparedBatch:
                 clause_tree is not None or script is not None):
             # (the library's other prepare calls take no composite spec: the refusal is made here with its code)
             raise N.SlgError(N.ERR_UNSUPPORTED, "composite is built on plain, sorted and aggregation batches only")
-        if self.composite_spec is not None:
+        # (an aggs.AggPlan carries its significant_terms / rare_terms nodes: a dict whose "spec" is the N.TermBucketSpec)
+        tb = getattr(aggs, "term_buckets", None) if term_buckets is None else term_buckets
+        self.term_bucket_spec = tb["spec"] if isinstance(tb, dict) else tb
+        if self.term_bucket_spec is not None and self.agg_spec is not None and int(self.agg_spec.n_nodes) == 0:
+            self.agg_spec = None
+        if self.term_bucket_spec is not None and (
+                self.top_hits_spec is not None or self.composite_spec is not None or hybrid or cursors is not None or
+                rescore is not None or clauses is not None or phrases is not None or fscore is not None or
+                collapse is not None or clause_tree is not None or script is not None):
+            # (the library's other prepare calls take no term bucket spec: the refusal is made here with its code)
+            raise N.SlgError(N.ERR_UNSUPPORTED, "significant_terms and rare_terms are built on plain, sorted and "
+                                                "aggregation batches only")
+        if self.term_bucket_spec is not None:
+            spec = None if sort is None else sort_spec(sort)
+            self._h = self._lib.slg_batch_prepare_term_buckets(
+                index._h, self.nq, _ptr(q_offsets), _ptr(q_terms), _ptr(q_weights), C.addressof(plans),
+                opt(qf), None if spec is None else C.addressof(spec),
+                None if self.agg_spec is None else C.addressof(self.agg_spec), C.addressof(self.term_bucket_spec),
+                k, strategy)
+        elif self.composite_spec is not None:
             spec = None if sort is None else sort_spec(sort)
             self._h = self._lib.slg_batch_prepare_composite(
                 index._h, self.nq, _ptr(q_offsets), _ptr(q_terms), _ptr(q_weights), C.addressof(plans),
@@ -1493,6 +1530,11 @@ class PreparedBatch:
         if cl is not None:
             cc += cl["size"] + sum(x["parent_rows"] * x["rows"] for x in cl["children"] if not x["is_stats"])
             sc += sum(x["parent_rows"] * x["rows"] for x in cl["children"] if x["is_stats"])
+        if getattr(self, "term_bucket_spec", None) is not None:  # (the same for the nodes with children)
+            for nd in self.term_buckets_layout()["nodes"]:
+                if nd["children"]:
+                    cc += nd["size"] + sum(x["parent_rows"] * x["rows"] for x in nd["children"] if not x["is_stats"])
+                    sc += sum(x["parent_rows"] * x["rows"] for x in nd["children"] if x["is_stats"])
         counts = np.zeros((max(self.nq, 1), max(cc, 1)), dtype=np.uint64)
         stats = np.zeros((max(self.nq, 1), max(sc, 1)), dtype=STATS_DTYPE)
         values = np.zeros((max(self.nq, 1), max(vc, 1)), dtype=np.uint64)
@@ -1549,6 +1591,48 @@ class PreparedBatch:
         return dict(keys=keys[:self.nq], n_buckets=nb[:self.nq], has_more=more[:self.nq],
                     counts=counts[:, c0:c0 + size].copy(),
                     children=[self._cut(x, counts, stats, values) for x in cl["children"]])
+
+    def term_buckets_layout(self) -> dict:
+        """slg_batch_term_buckets_layout: dict(rows, nodes = [dict(size, row_offset, count_offset, children = [as
+        agg_layout's entries])])."""
+        lay = N.TermBucketLayout()
+        N.check(self._lib.slg_batch_term_buckets_layout(self._h, C.addressof(lay)))
+        return dict(rows=int(lay.rows), nodes=[
+            dict(size=int(n.size), row_offset=int(n.row_offset), count_offset=int(n.count_offset),
+                 children=[dict(parent_rows=int(x.parent_rows), rows=int(x.rows), first_id=int(x.first_id),
+                                is_stats=int(x.is_stats) == 1, is_values=False, offset=int(x.offset))
+                           for x in n.children[:int(n.n_children)]])
+            for n in lay.nodes[:int(lay.n_nodes)]])
+
+    def term_buckets(self) -> dict:
+        """The buckets of a term bucket batch's last run (slg_batch_fetch_term_buckets and the nodes' cells of
+        slg_batch_fetch_aggs; waits): nodes = per node dict(ords uint32, doc_counts, bg_counts, score_bits uint64
+        [nq, size] in the response's order, scores float64 (the bits viewed), n_buckets [nq], doc_count, bg_count [nq]
+        (the node's totals), counts [nq, size] or None, children = per child an array [nq, size, rows] (as aggs()));
+        zeros past n_buckets and for what a rare node does not return."""
+        lay = self.term_buckets_layout()
+        nq, rows, nn = max(self.nq, 1), lay["rows"], len(lay["nodes"])
+        ords = np.zeros((nq, rows), dtype=np.uint32)
+        dc, bg, sb = (np.zeros((nq, rows), dtype=np.uint64) for _ in range(3))
+        nb = np.zeros((nq, nn), dtype=np.uint32)
+        ndc, nbg = np.zeros((nq, nn), dtype=np.uint64), np.zeros((nq, nn), dtype=np.uint64)
+        N.check(self._lib.slg_batch_fetch_term_buckets(self._h, _ptr(ords), _ptr(dc), _ptr(bg), _ptr(sb), _ptr(nb),
+                                                       _ptr(ndc), _ptr(nbg)))
+        tables = self._agg_tables() if any(nd["children"] for nd in lay["nodes"]) else None
+        nodes = []
+        for i, nd in enumerate(lay["nodes"]):
+            r0, r1 = nd["row_offset"], nd["row_offset"] + nd["size"]
+            cut = lambda a: a[:self.nq, r0:r1].copy()
+            out = dict(ords=cut(ords), doc_counts=cut(dc), bg_counts=cut(bg), score_bits=cut(sb),
+                       scores=cut(sb).view(np.float64), n_buckets=nb[:self.nq, i].copy(),
+                       doc_count=ndc[:self.nq, i].copy(), bg_count=nbg[:self.nq, i].copy(), counts=None, children=[])
+            if nd["children"]:
+                _, counts, stats, values, _ = tables
+                c0 = nd["count_offset"]
+                out["counts"] = counts[:, c0:c0 + nd["size"]].copy()
+                out["children"] = [self._cut(x, counts, stats, values) for x in nd["children"]]
+            nodes.append(out)
+        return dict(nodes=nodes)
 
     def top_hits_layout(self) -> list:
         """slg_batch_top_hits_layout: per top_hits node dict(lists, size, list_offset, hit_offset)."""
@@ -1776,7 +1860,10 @@ class ScanBatch(PreparedBatch):
             raise N.SlgError(N.ERR_UNSUPPORTED, "top_hits is not built on scan batches")
         if getattr(aggs, "composite", None) is not None:  # (the same for a composite)
             raise N.SlgError(N.ERR_UNSUPPORTED, "composite is not built on scan batches")
+        if getattr(aggs, "term_buckets", None) is not None:  # (and for significant_terms / rare_terms)
+            raise N.SlgError(N.ERR_UNSUPPORTED, "significant_terms and rare_terms are not built on scan batches")
         self.composite_spec = None
+        self.term_bucket_spec = None
         self.agg_spec = getattr(aggs, "spec", aggs)  # (an aggs.AggPlan carries its N.AggSpec)
         spec = None if sort is None else sort_spec(sort)
         self._h = self._lib.slg_batch_prepare_scan(

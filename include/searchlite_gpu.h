@@ -40,9 +40,10 @@
  * keyword column over the k <= SLG_MAX_COLLAPSE_ROWS rows of a plain, sorted or cursor batch, with up to
  * SLG_MAX_INNER_HITS inner hits per group; not with aggregations, rescore, bool, phrase, function_score, hybrid or
  * vector-only batches, sharded or coalesced.  Term expansion (slg_index_set_terms, slg_expand_batch): the fuzzy
- * option of a request and Prefix / Wildcard nodes are expanded against the segments' term dictionaries on the
- * device into ordinary slg_query terms, keys in the reference's order; terms or patterns of up to
- * SLG_MAX_EXPAND_CHARS chars, max_expansions up to SLG_MAX_EXPANSIONS.  Regex nodes, unscored groups, a query that
+ * option of a request and Prefix / Wildcard / Regex nodes are expanded against the segments' term dictionaries on
+ * the device into ordinary slg_query terms, keys in the reference's order; terms or patterns of up to
+ * SLG_MAX_EXPAND_CHARS chars, max_expansions up to SLG_MAX_EXPANSIONS; a regex as a byte-level DFA of up to
+ * SLG_MAX_REGEX_STATES states (no Unicode perl classes, flags or case folding).  Unscored groups, a query that
  * folds to more than SLG_MAX_QUERY_TERMS terms, and expansion inside sharded or coalesced paths stay on the CPU.
  * The completion suggester (slg_suggest_batch): SuggestRequest::Completion, plain prefix or fuzzy, against the
  * same dictionaries and their doc frequencies; scan, merge across segments, scores and the best `size` on the
@@ -2088,12 +2089,12 @@ int slg_search_batch_collapse(slg_index *index, uint32_t nq, const uint32_t *q_o
                               uint32_t *group_seg, float *group_score, uint32_t *inner_count, uint32_t *inner_row,
                               uint32_t *inner_doc, uint32_t *inner_seg, float *inner_score);
 
-/* ---- term expansion: fuzzy, prefix and wildcard (api/reader.rs:1119-1283, 1394-1465) -----------------
+/* ---- term expansion: fuzzy, prefix, wildcard and regex (api/reader.rs:1119-1373, 1394-1465) -----------
  * A request whose terms must be expanded against the term dictionary (SearchRequest.fuzzy, QueryNode::Prefix,
- * QueryNode::Wildcard) becomes a plain batch once its terms are known: slg_expand_batch returns, per source term,
+ * QueryNode::Wildcard, QueryNode::Regex) becomes a plain batch once its terms are known: slg_expand_batch returns, per source term,
  * the keys the reference's expansion yields, in its order, as rows of per-segment term ids with their edit
- * distance; the caller weights them (fuzzy: boost * 1 / (distance + 1) in f32, distance_weight, :977-979; prefix
- * and wildcard: boost), folds equal keys of a query by summing (:2971-2983), gives all expansions of a source term
+ * distance; the caller weights them (fuzzy: boost * 1 / (distance + 1) in f32, distance_weight, :977-979; prefix,
+ * wildcard and regex: boost), folds equal keys of a query by summing (:2971-2983), gives all expansions of a source term
  * that term's plan leaf and prepares an ordinary batch.  Scoring is untouched.
  *
  * DICTIONARIES.  slg_index_set_terms attaches segment seg's dictionary: key_offsets is uint32_t[n_terms + 1] over
@@ -2128,6 +2129,45 @@ int slg_search_batch_collapse(slg_index *index, uint32_t nq, const uint32_t *q_o
  * yielded is an expansion at distance 0.  The cap is PER SEGMENT and counts only such new keys: a key past the cap
  * in segment 0 can still enter through segment 1.  max_expansions == 0: no keys.
  *
+ * REGEX (QueryNode::Regex, expand_regex :1322-1373; kind SLG_EXPAND_REGEX = 4; kind 3 is reserved and stays an
+ * unknown kind).  term is the pattern, already normalised by the caller as a wildcard pattern is; max_edits,
+ * prefix_length and min_length are ignored.  It is expand_wildcard's loop with another predicate and another
+ * prefix rule: max_expansions == 0 gives no keys; segments in order; within a segment the range of the pattern's
+ * literal prefix in byte order; the key "field:" skipped (:1347); a key passes when ^(?:pattern)$ matches the
+ * WHOLE term (util/regex.rs, is_match under the regex crate's defaults: Unicode on, case-sensitive, '.' = any
+ * scalar value but U+000A); a key of an earlier segment is skipped (:1354); the cap is PER SEGMENT and counts
+ * only new keys (:1344), so R = (seg + 1) * max_expansions as for wildcard.
+ *   The literal prefix (regex_literal_prefix, :1285-1320) works on the pattern's TEXT, not on its meaning.
+ * Outside an escape: '\' starts an escape (:1310); '^' is dropped while the prefix is still empty (:1311); any of
+ * . * + ? ( ) [ ] { } | $ ends the prefix (:1312); any other char is appended (:1313-1316).  After a '\': any of
+ * d D w W s S b B p P ends the prefix (:1299-1300); any other char is appended AS ITSELF (:1291-1306), '\\'
+ * included, and letters that are escapes in the regex too.  The consequences are the reference's answers and
+ * ours: `ab|cd` scans only the range of "ab" and never yields "cd"; `rust?` scans the range of "rust" and never
+ * yields "rus"; `ab*` never yields "a"; `\n.*` scans the range of the letter "n" (and so yields nothing).
+ *   The pattern is compiled on the host to a minimised byte-level DFA (at most SLG_MAX_REGEX_STATES states with
+ * the dead state, at most SLG_MAX_REGEX_TABLE bytes of states x byte classes) that the device walks, a lane per
+ * key.  A pattern is never mis-compiled: what is outside the language below is SLG_ERR_UNSUPPORTED (CPU path),
+ * whether or not the regex crate would accept it.  An invalid or unsupported pattern is reported whatever
+ * max_expansions is (the reference's planner compiles the pattern first, query/planner.rs:599).
+ *   Supported: literal chars of any UTF-8 width (']' and '}' alone included); '\' followed by ASCII punctuation
+ * other than '<' and '>', as that literal; \n \t \r; '.'; classes [...] and [^...] of single chars and a-z
+ * ranges, a leading ']' and a leading or trailing '-' as literals, the same escapes inside, negation over all
+ * scalar values, U+000A included; groups ( ), (?: ), (?P<name> ) and (?<name> ) with names of [A-Za-z_][A-Za-z0-9_]*;
+ * '|', empty alternatives included; the quantifiers * + ? {n} {n,} {n,m}, each optionally followed by one '?'
+ * (lazy: without meaning for a whole-term match); the anchors ^ $ \A \z anywhere in the pattern (a start anchor
+ * behind a consumed char, or an end anchor in front of one, matches nothing: `a^b` is empty, `a$|b` is {a, b}).
+ *   SLG_ERR_UNSUPPORTED, the message naming the construct and its byte offset: \d \D \w \W \s \S \p \P \b \B
+ * (their Unicode tables belong to the regex crate's Unicode version, which cannot be pinned from here); every
+ * other alphanumeric escape (\x, \u, octal, ...), '\<', '\>' and '\' before a char that is not ASCII punctuation;
+ * any flag group ((?i), (?s), (?x), (?-u), ...) or look-around; a '[' inside a class (nested classes,
+ * [:alpha:]); && -- ~~ inside a class; a '-' after a leading ']' in a class; {,m}; a quantifier applied directly
+ * to a quantifier (a**, a+*, a{2}{3}, a?+) or to an anchor (^*; a group around the anchor is taken); a repetition count above 1000, groups nested deeper than 32, an
+ * automaton of more than 8192 states before minimisation; a minimised DFA above either limit.
+ *   SLG_ERR_INVALID (the reference errors too): unbalanced '(' or ')'; an unclosed '['; a reversed range such as
+ * [z-a]; a quantifier with nothing to repeat (at the start, after '(' or after '|'); a '{' after an atom that
+ * does not complete to {n}, {n,} or {n,m}; {n,m} with n > m; a trailing lone '\'; an empty, unclosed or
+ * duplicate group name.
+ *
  * OUTPUT.  out_offsets [n_reqs + 1]: request r's keys are rows out_offsets[r] .. out_offsets[r + 1] - 1 of
  * out_term_ids ([rows x n_segs], laid out as q_term_ids: SLG_NO_TERM where the segment lacks the key) and
  * out_distance ([rows] u8).  key_capacity = the rows the two arrays hold.  Size query: out_term_ids and
@@ -2137,18 +2177,23 @@ int slg_search_batch_collapse(slg_index *index, uint32_t nq, const uint32_t *q_o
  * The device scans (slg_expand.hpp: per request and segment the first R keys of the range that pass the
  * request's predicate, in dictionary order, with their distance); the host runs the reference's sequential loop
  * over those rows (seen set, caps, term-id rows).  R = max_expansions for fuzzy and (seg + 1) * max_expansions
- * for prefix / wildcard is all the reference can consume in a segment.
+ * for prefix / wildcard / regex is all the reference can consume in a segment.
  *
  * SLG_ERR_INVALID: index, reqs (n_reqs > 0) or out_offsets NULL; a struct_size other than
  * sizeof(slg_expand_req); an unknown kind; field or term NULL with a non-zero length; field or term not valid
- * UTF-8; a segment without a dictionary; out_term_ids or out_distance NULL but not both; key_capacity too small.
+ * UTF-8; an invalid regex pattern; a segment without a dictionary; out_term_ids or out_distance NULL but not both;
+ * key_capacity too small.
  * SLG_ERR_UNSUPPORTED (CPU path): a term or pattern of more than SLG_MAX_EXPAND_CHARS chars; max_expansions above
- * SLG_MAX_EXPANSIONS.  NOT BUILT: QueryNode::Regex; unscored (score == false) groups; a query whose folded list
+ * SLG_MAX_EXPANSIONS; a regex pattern outside the supported language or above the DFA limits (REGEX above).  NOT
+ * BUILT: Unicode perl classes, case-insensitive matching and flag groups in a regex (refused, not approximated);
+ * unscored (score == false) groups; a query whose folded list
  * exceeds SLG_MAX_QUERY_TERMS (the scoring kernels' cap is untouched); expansion inside sharded or coalesced
  * paths (expand first, then submit the plain query). */
-enum { SLG_EXPAND_FUZZY = 0, SLG_EXPAND_PREFIX = 1, SLG_EXPAND_WILDCARD = 2 };
+enum { SLG_EXPAND_FUZZY = 0, SLG_EXPAND_PREFIX = 1, SLG_EXPAND_WILDCARD = 2, SLG_EXPAND_REGEX = 4 }; /* 3: reserved */
 #define SLG_MAX_EXPAND_CHARS 128u  /* chars of a term or pattern: they sit in LDS beside the scan */
 #define SLG_MAX_EXPANSIONS 1024u   /* max_expansions of a request */
+#define SLG_MAX_REGEX_STATES 256u  /* states of a pattern's minimised DFA, the dead state included: a transition is a byte */
+#define SLG_MAX_REGEX_TABLE 16384u /* states x byte classes: the bytes of its transition table in LDS */
 /* the scan's geometry (the boundaries its tests sit on): lanes of a wave = candidate keys looked at together,
  * threads of a workgroup, keys of a range one workgroup scans */
 #define SLG_EXPAND_WAVE 64u
@@ -2158,10 +2203,10 @@ typedef struct slg_expand_req {
   uint32_t struct_size;    /* sizeof(slg_expand_req) */
   int32_t kind;            /* SLG_EXPAND_* */
   const char *field;       /* UTF-8, field_len bytes */
-  const char *term;        /* UTF-8, term_len bytes: the analysed term, the prefix or the wildcard pattern */
+  const char *term;        /* UTF-8, term_len bytes: the analysed term, the prefix, the wildcard or regex pattern */
   uint32_t field_len, term_len;
   uint32_t max_expansions;
-  uint32_t max_edits, prefix_length, min_length; /* fuzzy only (FuzzyOptions) */
+  uint32_t max_edits, prefix_length, min_length; /* fuzzy only (FuzzyOptions); ignored by the other kinds */
 } slg_expand_req;
 int slg_index_set_terms(slg_index *index, uint32_t seg, const char *key_bytes, const uint32_t *key_offsets);
 int slg_expand_batch(slg_index *index, const slg_expand_req *reqs, uint32_t n_reqs, uint32_t *out_offsets,

@@ -213,6 +213,9 @@ pub const SLG_MAX_SUGGEST_CANDIDATES: u32 = 256;
 pub const SLG_EXPAND_FUZZY: i32 = 0;
 pub const SLG_EXPAND_PREFIX: i32 = 1;
 pub const SLG_EXPAND_WILDCARD: i32 = 2;
+pub const SLG_EXPAND_REGEX: i32 = 4; // (3 is reserved: an unknown kind)
+pub const SLG_MAX_REGEX_STATES: u32 = 256;
+pub const SLG_MAX_REGEX_TABLE: u32 = 16384;
 #[repr(C)] pub struct slg_stats { pub scored_docs: u64, pub candidates_examined: u64, pub postings_advanced: u64 }
 #[repr(C)] pub struct slg_query { pub n_terms: u32, pub term_ids: *const u32, pub weights: *const c_float }
 

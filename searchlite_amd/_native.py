@@ -90,6 +90,8 @@ MAX_FILTER_NODES, MAX_FILTER_DEPTH, MAX_FILTER_TREES = 64, 16, 64
 MAX_COLLAPSE_ROWS = 4096
 MAX_INNER_HITS = 64
 EXPAND_FUZZY, EXPAND_PREFIX, EXPAND_WILDCARD = 0, 1, 2
+EXPAND_REGEX = 4                                 # (3 is reserved: an unknown kind)
+MAX_REGEX_STATES, MAX_REGEX_TABLE = 256, 16384   # a pattern's minimised DFA: states, states x byte classes
 MAX_EXPAND_CHARS = 128
 MAX_EXPANSIONS = 1024
 EXPAND_WAVE, EXPAND_WORKGROUP, EXPAND_CHUNK = 64, 256, 1024  # the scan's geometry (SLG_EXPAND_*)

@@ -9,6 +9,7 @@
 
 #include "slg_expand.hpp"
 #include "slg_expand_merge.hpp"
+#include "slg_expand_regex.hpp"
 
 namespace {
 template <typename F>
@@ -56,7 +57,7 @@ bool ref_bounded_levenshtein(const std::vector<uint32_t> &a, const std::vector<u
 
 namespace {
 
-// expand_term_fuzzy / expand_prefix / expand_wildcard as the reference runs them: walk the range of every
+// expand_term_fuzzy / expand_prefix / expand_wildcard / expand_regex as the reference runs them: walk the range of every
 // segment, test every key, keep a set of the keys seen
 void ref_expand_one(const slgexpand::Request &rq, const slgexpand::Dict *const *dicts, uint32_t n_segs,
                     std::vector<uint32_t> &ids, std::vector<uint8_t> &dist) {
@@ -109,6 +110,10 @@ void ref_expand_one(const slgexpand::Request &rq, const slgexpand::Dict *const *
       if (rq.kind == SLG_EXPAND_WILDCARD &&
           !slg::glob_match(rq.cps.data(), (uint32_t)rq.cps.size(), reinterpret_cast<const unsigned char *>(key.data()) + fpl,
                            (uint32_t)(key.size() - fpl)))
+        continue;
+      if (rq.kind == SLG_EXPAND_REGEX &&  // (the host build of the device's walk: this loop serves the timing tool only)
+          !slg::regex_walk(rq.dfa.class_of, rq.dfa.table.data(), rq.dfa.accept.data(), rq.dfa.n_classes,
+                           reinterpret_cast<const unsigned char *>(key.data()) + fpl, (uint32_t)(key.size() - fpl)))
         continue;
       if (!seen.insert(std::string(key)).second) continue;
       emit(std::string(key), 0);
@@ -189,6 +194,37 @@ uint32_t slgx_banded_distance(const uint32_t *term, uint32_t n, const char *cand
 }
 int slgx_glob_match(const uint32_t *pat, uint32_t n, const char *text, uint32_t bytes) {
   return slg::glob_match(pat, n, reinterpret_cast<const unsigned char *>(text), bytes) ? 1 : 0;
+}
+
+// The regex compiler (slg_regex.cpp) on a pattern of `len` bytes -> SLG_OK with the DFA (class_of [256], table
+// [table_cap] filled if n_states x n_classes fits, accept [32]; any may be NULL), or the compiler's code with err
+int slgx_regex_compile(const char *pattern, uint32_t len, uint32_t *n_states, uint32_t *n_classes, uint8_t *class_of,
+                       uint8_t *table, uint32_t table_cap, uint8_t *accept, char *err, uint32_t err_len) {
+  return guarded(err, err_len, [&] {
+    std::vector<uint32_t> cps;
+    if (!slgexpand::utf8_decode(pattern ? pattern : "", len, &cps)) throw slgplan::SlgError(SLG_ERR_INVALID, "regex: the pattern is not valid UTF-8");
+    const slgregex::Dfa d = slgregex::compile(cps);
+    if (n_states) *n_states = d.n_states;
+    if (n_classes) *n_classes = d.n_classes;
+    if (class_of) std::memcpy(class_of, d.class_of, 256);
+    if (table && d.table.size() <= table_cap) std::memcpy(table, d.table.data(), d.table.size());
+    if (accept) std::memcpy(accept, d.accept.data(), d.accept.size());
+  });
+}
+// the device's walk (slg_expand_regex.hpp) compiled for the host, over one term -> 1 / 0
+int slgx_regex_match(const uint8_t *class_of, const uint8_t *table, const uint8_t *accept, uint32_t n_classes,
+                     const char *text, uint32_t bytes) {
+  return slg::regex_walk(class_of, table, accept, n_classes, reinterpret_cast<const unsigned char *>(text), bytes) ? 1 : 0;
+}
+// regex_literal_prefix -> its bytes into out (cap bytes), *out_len its length; -1: the pattern is not valid UTF-8
+int slgx_regex_literal_prefix(const char *pattern, uint32_t len, char *out, uint32_t cap, uint32_t *out_len) {
+  std::vector<uint32_t> cps;
+  if (!slgexpand::utf8_decode(pattern ? pattern : "", len, &cps)) return -1;
+  std::string s;
+  for (const uint32_t cp : slgregex::literal_prefix(cps)) slgregex::utf8_append(s, cp);
+  *out_len = (uint32_t)s.size();
+  std::memcpy(out, s.data(), std::min<size_t>(cap, s.size()));
+  return 0;
 }
 
 // The reference's loop on the host for n_reqs requests over n_threads threads (requests dealt round robin).

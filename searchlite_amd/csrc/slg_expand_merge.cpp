@@ -100,7 +100,7 @@ uint32_t find_key(const Dict &d, std::string_view key) {
 Request check_request(const slg_expand_req &r, uint32_t index) {
   const std::string at = "expand: request " + std::to_string(index) + ": ";
   if (r.struct_size != sizeof(slg_expand_req)) throw SlgError(SLG_ERR_INVALID, at + "struct_size is not sizeof(slg_expand_req)");
-  if (r.kind != SLG_EXPAND_FUZZY && r.kind != SLG_EXPAND_PREFIX && r.kind != SLG_EXPAND_WILDCARD)
+  if (r.kind != SLG_EXPAND_FUZZY && r.kind != SLG_EXPAND_PREFIX && r.kind != SLG_EXPAND_WILDCARD && r.kind != SLG_EXPAND_REGEX)
     throw SlgError(SLG_ERR_INVALID, at + "unknown kind " + std::to_string(r.kind));
   if (!r.field && r.field_len) throw SlgError(SLG_ERR_INVALID, at + "field is NULL");
   if (!r.term && r.term_len) throw SlgError(SLG_ERR_INVALID, at + "term is NULL");
@@ -116,7 +116,7 @@ Request check_request(const slg_expand_req &r, uint32_t index) {
   q.field_key.assign(r.field ? r.field : "", r.field_len);
   q.field_key.push_back(':');
   q.field_chars = (uint32_t)field_cps.size() + 1;
-  const std::string_view term(r.term ? r.term : "", r.term_len);
+  std::string_view term(r.term ? r.term : "", r.term_len);
   q.exact_key = q.field_key;
   q.exact_key.append(term);
   q.max_expansions = r.max_expansions;
@@ -131,8 +131,19 @@ Request check_request(const slg_expand_req &r, uint32_t index) {
       while (prefix_bytes < term.size() && (static_cast<unsigned char>(term[prefix_bytes]) & 0xC0u) == 0x80u) prefix_bytes++;
     }
   } else {
-    q.scan = r.max_expansions > 0;  // :1173, :1241
+    q.scan = r.max_expansions > 0;  // :1173, :1241, :1331
     if (r.kind == SLG_EXPAND_WILDCARD) prefix_bytes = std::min(term.find_first_of("*?"), term.size());  // :1212-1214
+  }
+  std::string regex_prefix;
+  if (r.kind == SLG_EXPAND_REGEX) {
+    try {
+      q.dfa = slgregex::compile(q.cps);
+    } catch (const SlgError &e) {
+      throw SlgError(e.code, at + e.what());
+    }
+    for (const uint32_t cp : slgregex::literal_prefix(q.cps)) slgregex::utf8_append(regex_prefix, cp);  // :1285-1320
+    term = regex_prefix;  // (not a prefix of the pattern's bytes: an escaped char stands as itself)
+    prefix_bytes = term.size();
   }
   q.range_key = q.field_key;
   q.range_key.append(term.substr(0, prefix_bytes));

@@ -1,7 +1,7 @@
 // slg_expand_merge.hpp — the host side of slg_expand_batch (slg_expand_merge.cpp): pure host code, linked into
 // libsearchlite_gpu.so and, behind a small test C ABI (slg_expand_capi.cpp), into lib/libslg_plan.so, so it is
 // unit-tested and sanitized without a GPU.  It checks and sorts a segment's dictionary, checks a request and finds
-// its range, and runs the reference's sequential loop (api/reader.rs:1164-1283, 1394-1465) over the rows the
+// its range, and runs the reference's sequential loop (api/reader.rs:1164-1283, 1322-1373, 1394-1465) over the rows the
 // device scan produced: the seen set by key bytes, the global or per-segment cap, then the row of term ids.  It
 // never computes a distance and never scans a dictionary.
 #pragma once
@@ -13,6 +13,7 @@
 
 #include "../../include/searchlite_gpu.h"
 #include "slg_plan.hpp"  // SlgError
+#include "slg_regex.hpp"
 
 namespace slgexpand {
 
@@ -53,9 +54,12 @@ struct Request {
   uint32_t field_chars = 0;    // chars of field_key
   uint32_t max_expansions = 0, max_edits = 0;
   bool scan = false;           // false: nothing to scan (fuzzy: the exact key alone; else no keys)
+  slgregex::Dfa dfa;           // regex: the compiled pattern (slg_regex.hpp)
 };
 // Throws SLG_ERR_INVALID (struct_size, kind, NULL strings, invalid UTF-8) or SLG_ERR_UNSUPPORTED (more than
-// SLG_MAX_EXPAND_CHARS chars, max_expansions above SLG_MAX_EXPANSIONS); `index`: the request's, for the message
+// SLG_MAX_EXPAND_CHARS chars, max_expansions above SLG_MAX_EXPANSIONS), and for a regex request whatever
+// slgregex::compile throws, whatever max_expansions is (the reference's planner compiles the pattern first,
+// query/planner.rs:599); `index`: the request's, for the message
 Request check_request(const slg_expand_req &r, uint32_t index);
 
 // R: the passing keys of segment seg's range the reference can consume

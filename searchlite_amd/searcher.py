@@ -240,6 +240,23 @@ class GpuIndex:
         offs, terms, w, plans = self.expanded_queries(queries, default_field, fuzzy, boost)
         return self.search_plan(offs, terms, w, k, strategy=strategy, **plans)
 
+    def search_patterns(self, nodes, k: int, strategy: int = Wand):
+        """A batch of pattern nodes, one node one query: nodes = (kind, field, value, max_expansions, boost) with kind
+        N.EXPAND_PREFIX (QueryNode::Prefix), N.EXPAND_WILDCARD (QueryNode::Wildcard) or N.EXPAND_REGEX
+        (QueryNode::Regex).  expand(), then every key of a node at weight = boost on the node's one leaf
+        (fold_expansions at distance 0), then the ordinary batch with plans -> (doc, seg, score, count).  A pattern
+        the library refuses raises SlgError (ERR_UNSUPPORTED: the CPU path)."""
+        nodes = list(nodes)
+        for kind, *_ in nodes:
+            if kind not in (N.EXPAND_PREFIX, N.EXPAND_WILDCARD, N.EXPAND_REGEX):
+                raise ValueError(f"search_patterns: kind {kind} is not a prefix, wildcard or regex node")
+        reqs = [expand_request(kind, field, value, mx) for kind, field, value, mx, _ in nodes]
+        rows = self.expand(reqs) if reqs else []
+        offs, terms, w, plans = fold_expansions(len(nodes), list(range(len(nodes))), [f"{f}:{v}" for _, f, v, _, _ in nodes],
+                                                rows, self.n_segs, [np.float32(b) for *_, b in nodes] or 1.0,
+                                                [v for _, _, v, _, _ in nodes])
+        return self.search_plan(offs, terms, w, k, strategy=strategy, **plans)
+
     @property
     def generation(self) -> int:
         return int(self._lib.slg_index_generation(self._h))
@@ -981,7 +998,7 @@ class GpuIndex:
 def expand_request(kind: int, field: str, term: str, max_expansions: int, max_edits: int = 0, prefix_length: int = 0,
                    min_length: int = 0) -> dict:
     """One request of GpuIndex.expand(): kind N.EXPAND_FUZZY (term: the analysed term; the FuzzyOptions),
-    N.EXPAND_PREFIX (term: the prefix) or N.EXPAND_WILDCARD (term: the pattern)."""
+    N.EXPAND_PREFIX (term: the prefix), N.EXPAND_WILDCARD or N.EXPAND_REGEX (term: the pattern)."""
     return dict(kind=kind, field=field, term=term, max_expansions=max_expansions, max_edits=max_edits,
                 prefix_length=prefix_length, min_length=min_length)
 

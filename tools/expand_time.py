@@ -11,7 +11,14 @@ Per batch, mean of `reps` calls after two warm-up calls, `rounds` times over so 
     slg_batch_run, and search_fuzzy (8 expansions per term, so that every query stays under the scoring kernels' 32-term
     cap) end to end through the Python layer, whose folding loop is most of that figure.
 The device's answer is compared with the restatement's before anything is timed.
-usage (GPU box): python tools/expand_time.py [reps] [rounds]"""
+
+Regex mode (`regex` as the first argument): on the same vocabulary, 1024 wildcard requests `ab*c?` (the first two
+letters of a word, any run, one of its later letters, one char; 50 expansions) and the same patterns written as
+regexes, `ab.*c.`: the same ranges and the same answers, which is asserted before anything is timed; then one pattern
+with an empty literal prefix, `.*ing` beside the wildcard `*ing`, whose range is the whole field.  Per batch the
+whole call, the device scan and the host merge as above.  `wildcard` as the first argument times the wildcard
+batches alone: the yardstick, for a library built from a commit without the regex kind (SLG_LIB_TAG).
+usage (GPU box): python tools/expand_time.py [regex | wildcard] [reps] [rounds]"""
 import ctypes as C
 import json
 import os
@@ -26,6 +33,7 @@ import torch  # noqa: E402
 from searchlite_amd import build, corpus, searcher, _native as N  # noqa: E402
 from tools.vocabulary import make_vocabulary  # noqa: E402
 
+mode = sys.argv.pop(1) if len(sys.argv) > 1 and sys.argv[1] in ("regex", "wildcard") else "fuzzy"
 reps = int(sys.argv[1]) if len(sys.argv) > 1 else 5
 rounds = int(sys.argv[2]) if len(sys.argv) > 2 else 3
 n_docs, vocab, nq, T = 1_000_000, 1 << 18, 1024, 3
@@ -104,6 +112,67 @@ def scoring_context():
     finally:
         b.close()
 
+
+def time_batch(label, reqs):
+    """`rounds` lines for one batch: the call, its scan and its merge, mean of `reps` after two warm-up calls"""
+    arr, keep = c_reqs(reqs)
+    cap = max(sum(r["max_expansions"] for r in reqs), 1)
+    o, out_ids, out_dist = np.zeros(len(reqs) + 1, np.uint32), np.zeros((cap, 1), np.uint32), np.zeros(cap, np.uint8)
+
+    def one_call():
+        N.check(ix._lib.slg_expand_batch(ix._h, arr, len(reqs), o.ctypes.data, cap, out_ids.ctypes.data, out_dist.ctypes.data))
+    one_call()
+    one_call()
+    for rnd in range(rounds):
+        call, scan, merge = [], [], []
+        for _ in range(reps):
+            t = time.perf_counter()
+            one_call()
+            call.append((time.perf_counter() - t) * 1e3)
+            sc, mg = ix.expand_phase_ms()
+            scan.append(sc)
+            merge.append(mg)
+        print(json.dumps(dict(round=rnd, batch=label, requests=len(reqs), keys=int(o[-1]),
+                              expand_call_ms=round(float(np.mean(call)), 3), device_scan_ms=round(float(np.mean(scan)), 3),
+                              host_merge_ms=round(float(np.mean(merge)), 3))), flush=True)
+
+
+if mode != "fuzzy":
+    rng = np.random.default_rng(11)
+    long_words = [x for x in words if len(x) >= 5]
+    pairs = []
+    for i in rng.choice(len(long_words), size=nq, replace=False):
+        x = long_words[int(i)]
+        pairs.append((x[:2] + "*" + x[3] + "?", x[:2] + ".*" + x[3] + "."))
+    wild = [searcher.expand_request(N.EXPAND_WILDCARD, "body", a, 50) for a, _ in pairs]
+    wild_all = [searcher.expand_request(N.EXPAND_WILDCARD, "body", "*ing", 50)]
+    if mode == "regex":
+        rx = [searcher.expand_request(N.EXPAND_REGEX, "body", b, 50) for _, b in pairs]
+        rx_all = [searcher.expand_request(N.EXPAND_REGEX, "body", ".*ing", 50)]
+        for a, b in ((wild, rx), (wild_all, rx_all)):           # the same answers before any timing
+            for i, ((ia, da), (ib, db)) in enumerate(zip(ix.expand(a), ix.expand(b))):
+                assert ia.tolist() == ib.tolist() and da.tolist() == db.tolist(), (i, a[i], b[i])
+        host = host_loop(rx, 16)[1]                             # and the C++ restatement of the loop counts as many
+        assert int(host[-1]) == sum(len(d) for _, d in ix.expand(rx))
+    first2 = np.array([x[:2] for x in words])
+    print(json.dumps(dict(mode=mode, library=os.path.basename(N.lib_path()), patterns="ab*c? / ab.*c.",
+                          mean_range_keys=round(float(np.mean([(first2 == a[:2]).sum() for a, _ in pairs])), 1),
+                          whole_field_keys=len(words))), flush=True)
+    time_batch("wildcard ab*c?", wild)
+    if mode == "regex":
+        time_batch("regex ab.*c.", rx)
+    time_batch("wildcard *ing (empty literal prefix)", wild_all)
+    if mode == "regex":
+        time_batch("regex .*ing (empty literal prefix)", rx_all)
+        t = time.perf_counter()
+        host_loop(rx, 16)
+        cpu16 = (time.perf_counter() - t) * 1e3
+        t = time.perf_counter()
+        host_loop(rx_all, 1)
+        print(json.dumps(dict(cpu_dfa_loop_16_threads_ms_ab=round(cpu16, 1),
+                              cpu_dfa_loop_1_thread_ms_ing=round((time.perf_counter() - t) * 1e3, 1),
+                              note="slgx_reference_expand with the host build of the DFA walk, not the reference's regex engine")), flush=True)
+    sys.exit(0)
 
 for prefix_length in (1, 0):
     fz = dict(max_edits=1, prefix_length=prefix_length, max_expansions=50, min_length=3)

@@ -489,7 +489,7 @@ int slg_batch_fetch_aggs(slg_batch *b, uint64_t *counts, slg_agg_stats *stats) {
     SLG_REQUIRE(b->launched, "the batch has not run");
     // a composite batch: the composite's cells lie behind the spec's in every query's row (tables of their own on
     // the device: agg_kernel's tables keep their stride)
-    const size_t ac = b->aggs ? b->agg_count_cells : 0u, as = b->aggs ? b->agg_stats_cells : 0u;
+    const size_t ac = agg_spec_cells(b).count, as = agg_spec_cells(b).stats;
     // (a term bucket batch: the same with the children's tables of its nodes; never both kinds in one batch)
     const size_t cc = b->composite ? b->cp_count_cells : b->term_buckets ? b->tb_count_cells : 0u;
     const size_t cs = b->composite ? b->cp_stats_cells : b->term_buckets ? b->tb_stats_cells : 0u;

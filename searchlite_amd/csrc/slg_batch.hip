@@ -140,21 +140,38 @@ SortBinding slghost::bind_sort(const IndexState &S, const slg_sort_spec &spec, c
   return sb;
 }
 
-void slghost::release_batch_buffers(slg_batch *b, bool to_pool) {
-  DevBuf *bufs[] = {&b->d_desc, &b->d_bounds, &b->d_rdoc, &b->d_slice_desc, &b->d_slice_tk, &b->d_slice_doc,
-                    &b->d_q_scored, &b->d_q_filter, &b->d_cand, &b->d_slice_cbeg, &b->d_slice_ccnt,
-                    &b->d_out, &b->d_stamps, &b->d_blk_skip, &b->d_gather, &b->d_merged, &b->d_q_cand,
-                    &b->d_hy_keys, &b->d_hy_work, &b->d_agg_desc, &b->d_agg_counts, &b->d_agg_stats,
-                    &b->d_agg_values, &b->d_agg_scratch,
-                    &b->d_rs_desc, &b->d_rs_side, &b->d_bool_desc, &b->d_phrase_desc, &b->d_booltree_desc, &b->d_fscore_desc, &b->d_script_desc,
-                    &b->d_cl_desc, &b->d_cl_side, &b->d_th_desc, &b->d_th_out, &b->d_th_entries, &b->d_th_cursors,
-                    &b->d_cp_desc, &b->d_cp_ranks, &b->d_cp_lower, &b->d_cp_out, &b->d_cp_counts, &b->d_cp_stats,
-                    &b->d_tb_desc, &b->d_tb_ranks, &b->d_tb_bg, &b->d_tb_fg, &b->d_tb_bgsum, &b->d_tb_bits, &b->d_tb_out,
-                    &b->d_tb_sorted, &b->d_tb_counts, &b->d_tb_stats};
-  for (DevBuf *d : bufs) {
-    if (!to_pool) d->pool = nullptr;
-    d->release();
+void slghost::release_batch_buffers(slg_batch *b) {
+  static_cast<slg_batch_buffers &>(*b) = slg_batch_buffers{};  // (each DevBuf's move assignment releases its block)
+  for (hipEvent_t &e : b->ev_shard) {
+    if (e) (void)hipEventDestroy(e);
+    e = nullptr;
   }
+}
+
+void slghost::attach_select_buffers(slg_batch *b, const std::vector<uint32_t> &q_filter, const slg_sort_spec *sort,
+                                    const SortBinding &sorting, bool counts_matched) {
+  BufPool *const pool = &b->idx->pool;
+  const uint32_t nq = b->nq;
+  if (!q_filter.empty()) {
+    b->d_q_filter.alloc_pooled(pool, (size_t)nq * 4);
+    SLG_HIP(hipMemcpy(b->d_q_filter.p, q_filter.data(), (size_t)nq * 4, hipMemcpyHostToDevice));
+  }
+  b->sorted = sort != nullptr;
+  if (b->sorted) {
+    b->n_sort_parts = sort->n_parts;
+    b->sort_score_parts = sorting.score_parts;
+    b->sort_desc_parts = sorting.desc_parts;
+    b->d_sort_cols.alloc_pooled(pool, sorting.cols.size() * sizeof(slg::SortColDev));
+    SLG_HIP(hipMemcpy(b->d_sort_cols.p, sorting.cols.data(), sorting.cols.size() * sizeof(slg::SortColDev),
+                      hipMemcpyHostToDevice));
+  }
+  if (counts_matched) b->d_matched.alloc_pooled(pool, (size_t)std::max<uint32_t>(nq, 1) * 8);
+  const ResultBlock R(nq, b->k);
+  b->d_out.alloc_pooled(pool, R.words_with_flag() * 4);
+  b->d_out_doc = R.doc(b->d_out.as<uint32_t>());
+  b->d_out_seg = R.seg(b->d_out.as<uint32_t>());
+  b->d_out_score = R.score(b->d_out.as<uint32_t>());
+  b->d_out_count = R.count(b->d_out.as<uint32_t>());
 }
 
 extern "C" {
@@ -195,8 +212,7 @@ slg_batch *slghost::prepare_impl(const PrepareRequest &r) {
   const slg_sort_spec *const sort = r.sort.spec;
   const slg_sort_cursor *const q_cursor = r.cursor.spec;
   const bool after = r.cursor.on, hybrid = r.hybrid;
-  slg_batch *b = nullptr;
-  int rc = guarded([&] {
+  return prepare_guarded([&](slg_batch *&b) {
     SLG_REQUIRE(!r.sort.on || sort != nullptr, "sort spec is NULL");
     if (r.aggs.on) agg_check_spec(r.aggs.spec);  // (what needs no index comes first, as every argument check)
     if (r.rescore.on) slgplan::check_rescore(r.rescore.spec, nq, k);
@@ -215,20 +231,12 @@ slg_batch *slghost::prepare_impl(const PrepareRequest &r) {
     if (r.term_buckets.on) term_buckets_check_spec(r.term_buckets.spec);
     SLG_REQUIRE(ix != nullptr, "index is NULL");
     SLG_REQUIRE(!after || q_cursor != nullptr, "q_cursor is NULL");
-    if (sort) {  // (checked before planning: the planner never sees a sort spec it cannot run)
-      if (sort->n_parts > SLG_MAX_SORT_PARTS)
-        throw SlgError(SLG_ERR_UNSUPPORTED, "more than SLG_MAX_SORT_PARTS sort parts");
-      SLG_REQUIRE(sort->n_parts >= 1, "a sort spec needs at least one part");
-      for (uint32_t i = 0; i < sort->n_parts; i++)
-        SLG_REQUIRE(sort->order[i] == SLG_ORDER_ASC || sort->order[i] == SLG_ORDER_DESC, "unknown sort order");
-    }
+    check_sort_spec(sort);  // (before planning: the planner never sees a sort spec it cannot run)
     // Planning (slg_plan.cpp: a pure host function) reads only the immutable state the batch binds
     // to, so host threads may prepare batches for one index concurrently, also while an update builds
     // the next state; the index mutex is held just to take the snapshot.
     const std::shared_ptr<const IndexState> snap = ix->snapshot();
-    std::vector<char> filter_live(snap->filters.size());
-    for (size_t f = 0; f < snap->filters.size(); f++)
-      filter_live[f] = snap->filter_usable(f);
+    const std::vector<char> filter_live = filter_liveness(*snap);
     std::vector<slgplan::SegView> views(snap->segs.size());
     for (size_t s = 0; s < snap->segs.size(); s++) {
       const SegHost &sh = *snap->segs[s];
@@ -249,7 +257,7 @@ slg_batch *slghost::prepare_impl(const PrepareRequest &r) {
     in.strategy = r.strategy;
     in.filter_live = filter_live.data();
     in.n_filters = filter_live.size();
-    in.sorted = sort != nullptr || after || hybrid || r.aggs.on || r.top_hits.on || r.composite.on || r.term_buckets.on || r.boolean.on || r.booltree.on || r.fscore.on || r.script.on;
+    in.sorted = r.plans_every_match();
     SortBinding sorting;  // the columns of the sort parts in the batch's state
     if (sort) sorting = bind_sort(*snap, *sort, "", "part ");
     // the cursors as the key words the select kernel compares (against the same snapshot's field kinds)
@@ -312,7 +320,6 @@ slg_batch *slghost::prepare_impl(const PrepareRequest &r) {
     b->deep = plan.deep;
     b->pruned = plan.pruned;
     b->cand_mode = plan.cand_mode;
-    b->sorted = sort != nullptr;
     b->after = after;
     b->hybrid = hybrid;
     b->score_k = slgplan::planning_k(in);
@@ -362,19 +369,7 @@ slg_batch *slghost::prepare_impl(const PrepareRequest &r) {
     // (from the pool like every per-batch buffer: a raw hipMalloc / hipFree per batch synchronises
     // the device and cost config 4's two-in-flight pipeline 60 %)
     if (b->pruned && !b->uniform && ix->tune.block_max) b->d_blk_skip.alloc_pooled(&ix->pool, ((size_t)nq + 1) * 8);
-    if (!plan.q_filter.empty()) {
-      b->d_q_filter.alloc_pooled(&ix->pool, (size_t)nq * 4);
-      SLG_HIP(hipMemcpy(b->d_q_filter.p, plan.q_filter.data(), (size_t)nq * 4, hipMemcpyHostToDevice));
-    }
-    if (b->sorted) {
-      b->n_sort_parts = sort->n_parts;
-      b->sort_score_parts = sorting.score_parts;
-      b->sort_desc_parts = sorting.desc_parts;
-      b->d_sort_cols.alloc_pooled(&ix->pool, sorting.cols.size() * sizeof(slg::SortColDev));
-      SLG_HIP(hipMemcpy(b->d_sort_cols.p, sorting.cols.data(), sorting.cols.size() * sizeof(slg::SortColDev),
-                        hipMemcpyHostToDevice));
-    }
-    if (b->sorted || b->after || r.aggs.on || r.top_hits.on || r.composite.on || r.term_buckets.on) b->d_matched.alloc_pooled(&ix->pool, (size_t)std::max<uint32_t>(nq, 1) * 8);
+    attach_select_buffers(b, plan.q_filter, sort, sorting, r.counts_matched());
     if (b->after) {
       b->d_cursor.alloc_pooled(&ix->pool, cursor_words.size() * 4);
       SLG_HIP(hipMemcpy(b->d_cursor.p, cursor_words.data(), cursor_words.size() * 4, hipMemcpyHostToDevice));
@@ -396,12 +391,6 @@ slg_batch *slghost::prepare_impl(const PrepareRequest &r) {
       b->d_q_cand.alloc_pooled(&ix->pool, b->q_cand.size() * 8);
       SLG_HIP(hipMemcpy(b->d_q_cand.p, b->q_cand.data(), b->q_cand.size() * 8, hipMemcpyHostToDevice));
     }
-    const ResultBlock R(nq, k);
-    b->d_out.alloc_pooled(&ix->pool, R.words_with_flag() * 4);
-    b->d_out_doc = R.doc(b->d_out.as<uint32_t>());
-    b->d_out_seg = R.seg(b->d_out.as<uint32_t>());
-    b->d_out_score = R.score(b->d_out.as<uint32_t>());
-    b->d_out_count = R.count(b->d_out.as<uint32_t>());
     if (r.aggs.on) agg_attach(b, *r.aggs.spec);
     if (r.top_hits.on) top_hits_attach(b, *r.top_hits.spec);
     if (r.composite.on) composite_attach(b, *r.composite.spec);
@@ -417,17 +406,7 @@ slg_batch *slghost::prepare_impl(const PrepareRequest &r) {
     if (r.fscore.on) fscore_attach(b, fscore_plan);
     if (r.script.on) script_attach(b, script_plan, r.fscore.on && r.script_order == SLG_SCRIPT_INNER);
     if (r.collapse.on) collapse_attach(b, *r.collapse.spec, sort);
-    {
-      std::lock_guard<std::mutex> lk(ix->mu);
-      ix->live.push_back(b);
-    }
   });
-  if (rc != SLG_OK) {
-    KeepLastError keep;
-    delete b;
-    return nullptr;
-  }
-  return b;
 }
 
 extern "C" {
@@ -727,7 +706,7 @@ int slg_batch_set_stream(slg_batch *b, void *hip_stream) {
 void slg_batch_destroy(slg_batch *b) {
   if (!b) return;
   slg_index *ix = b->idx;
-  if (!ix) {  // detached by slg_index_destroy: nothing left on the device
+  if (!ix) {  // detached by slg_index_destroy: nothing left on the device, the shard events gone too
     delete b;
     return;
   }
@@ -772,31 +751,9 @@ int flatten_queries(slg_index *ix, const slg_query *queries, uint32_t nq, FlatQu
   });
 }
 
-// the host arrays of a one-call search: the rows, and what the batch's kind adds to them (null: not asked for)
-struct HostOut {
-  uint32_t *doc, *seg;
-  float *score;
-  uint32_t *count;
-  slg_stats *stats = nullptr;
-  uint64_t *matched = nullptr;
-  uint8_t *seen = nullptr;
-  uint64_t *agg_counts = nullptr;  // (an aggregation batch)
-  slg_agg_stats *agg_stats = nullptr;
-  uint64_t *agg_values = nullptr;
-  float *first_score = nullptr, *rescore_score = nullptr;  // (a rescore batch)
-  uint32_t *rescored = nullptr;
-  void *const *collapse = nullptr;  // (a collapse batch) the 14 arrays of slg_batch_fetch_collapse, in its order
-  uint32_t *th_doc = nullptr, *th_seg = nullptr, *th_count = nullptr, *th_status = nullptr;  // (a top_hits batch)
-  float *th_score = nullptr;
-  uint64_t *cp_keys = nullptr;  // (a composite batch)
-  uint32_t *cp_n_buckets = nullptr, *cp_has_more = nullptr;
-  uint32_t *tb_ords = nullptr, *tb_n_buckets = nullptr;  // (a term bucket batch)
-  uint64_t *tb_doc_counts = nullptr, *tb_bg_counts = nullptr, *tb_score_bits = nullptr, *tb_node_dc = nullptr,
-           *tb_node_bg = nullptr;
-};
-// A prepared batch (null: prepare failed and set the thread's error) run to the caller's host arrays and
-// destroyed: the first error is the one reported
-int run_to_host(slg_batch *b, const HostOut &o) {
+}  // namespace
+
+int slghost::run_to_host(slg_batch *b, const HostOut &o) {
   if (!b) return last_error().code;
   int rc = slg_batch_run(b);
   if (rc == SLG_OK) rc = slg_batch_fetch(b, o.doc, o.seg, o.score, o.count, o.stats);
@@ -820,7 +777,6 @@ int run_to_host(slg_batch *b, const HostOut &o) {
   slg_batch_destroy(b);
   return rc;
 }
-}  // namespace
 
 extern "C" {
 
@@ -847,7 +803,7 @@ int slg_batch_matched_counts(slg_batch *b, uint64_t *out_matched) {
   return guarded([&] {
     SLG_REQUIRE_LIVE(b);
     if (b->hybrid) throw SlgError(SLG_ERR_UNSUPPORTED, "a hybrid batch has no matched counts");
-    SLG_REQUIRE(b->sorted || b->after || b->aggs || b->scan || b->top_hits || b->composite || b->term_buckets,
+    SLG_REQUIRE(b->d_matched.p != nullptr,
                 "not a sorted, cursor, aggregation or scan batch (slg_batch_prepare_sorted / _after / _aggs / _scan)");
     SLG_REQUIRE(b->launched, "the batch has not run");
     SLG_REQUIRE(b->nq == 0 || out_matched != nullptr, "out_matched is NULL");

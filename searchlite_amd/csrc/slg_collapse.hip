@@ -93,14 +93,10 @@ int slg_batch_fetch_collapse(slg_batch *b, uint32_t *n_groups, uint32_t *total_g
     DeviceGuard g(b->idx->device);
     const hipStream_t st = locked_stream(b);
     if (b->nq == 0) return;
-    // the arrays and the error word behind them are one block: ONE D2H copy (as slg_batch_fetch)
+    // the arrays and the error word behind them are one block
     const size_t words = side_off(b, slg::kClArrays) + 1;
-    FetchBlock host(b->idx->pool, words);
-    uint32_t *const blk = host.p;
-    SLG_HIP(hipMemcpyAsync(blk, b->d_cl_side.p, words * 4, hipMemcpyDeviceToHost, st));
-    SLG_HIP(wait_stream(st));
-    if (blk[words - 1] != 0u)  // rows a scoring wave gave up on are not collapsed into an answer
-      throw SlgError(SLG_ERR_INTERNAL, "a scoring wave gave up on a round (chunk-loop guard): results are incomplete");
+    const SideBlock host(b, b->d_cl_side, words, st);
+    const uint32_t *const blk = host.p;
     void *const dst[14] = {n_groups,  total_groups, status,      group_row, group_ord, group_size, group_doc,
                            group_seg, group_score,  inner_count, inner_row, inner_doc, inner_seg,  inner_score};
     for (uint32_t i = 0; i < slg::kClArrays; i++) {

@@ -150,12 +150,12 @@ void slghost::composite_attach(slg_batch *b, const slg_composite_spec &spec) {
     lay.sources[i].shift = below;
   }
   // the tables: behind the cells of the aggregation spec in a query's rows; `size` count cells, then the children
-  const uint64_t agg_cells =
-      b->aggs ? (uint64_t)b->agg_count_cells + b->agg_stats_cells + b->agg_value_cells : 0u;
+  const AggSpecCells spec_cells = agg_spec_cells(b);
+  const uint64_t agg_cells = spec_cells.all();
   if (agg_cells + spec.size > SLG_MAX_AGG_CELLS)
     throw SlgError(SLG_ERR_UNSUPPORTED, "more than SLG_MAX_AGG_CELLS aggregation cells per query (at the composite)");
   const CompositeChildTables ch = agg_plan_children(S, spec, agg_cells);
-  const uint32_t ac = b->aggs ? b->agg_count_cells : 0u, as = b->aggs ? b->agg_stats_cells : 0u;
+  const uint32_t ac = spec_cells.count, as = spec_cells.stats;
   lay.count_offset = ac;
   for (uint32_t i = 0; i < spec.n_children; i++) {
     lay.children[i] = ch.layout[i];
@@ -217,7 +217,7 @@ void slghost::composite_launch(slg_batch *b, hipStream_t st) {
   p.a.counts = b->d_cp_counts.as<uint32_t>();
   p.a.stats = b->d_cp_stats.as<slg::AggStatDev>();
   // a sorted batch's select counted the accepted docs, agg_kernel does in score order; without either the collect
-  p.a.out_matched = (b->sorted || b->aggs) ? nullptr : b->d_matched.as<unsigned long long>();
+  p.a.out_matched = post_select_matched(b);
   p.src_cols = reinterpret_cast<const slg::ColumnDev *>(desc + b->cp_src_cols_off);
   p.src = reinterpret_cast<const slg::CompositeSourceDev *>(desc + b->cp_src_off);
   p.n_sources = b->cp_spec.n_sources;
@@ -277,14 +277,10 @@ int slg_batch_fetch_composite(slg_batch *b, uint64_t *keys, uint32_t *n_buckets,
     DeviceGuard g(b->idx->device);
     const hipStream_t st = locked_stream(b);
     if (b->nq == 0) return;
-    // the arrays and the error word behind them are one block: ONE D2H copy (as slg_batch_fetch)
+    // the arrays and the error word behind them are one block
     const size_t words = out_words(b), nq = b->nq, kw = 2 * nq * b->cp_spec.size;
-    FetchBlock host(b->idx->pool, words);
-    uint32_t *const blk = host.p;
-    SLG_HIP(hipMemcpyAsync(blk, b->d_cp_out.p, words * 4, hipMemcpyDeviceToHost, st));
-    SLG_HIP(wait_stream(st));
-    if (blk[words - 1] != 0u)  // rows a scoring wave gave up on are not selected into an answer
-      throw SlgError(SLG_ERR_INTERNAL, "a scoring wave gave up on a round (chunk-loop guard): results are incomplete");
+    const SideBlock host(b, b->d_cp_out, words, st);
+    const uint32_t *const blk = host.p;
     if (keys) std::memcpy(keys, blk, kw * 4);
     if (n_buckets) std::memcpy(n_buckets, blk + kw, nq * 4);
     if (has_more) std::memcpy(has_more, blk + kw + nq, nq * 4);

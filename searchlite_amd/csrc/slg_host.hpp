@@ -481,8 +481,59 @@ struct slg_index {
   }
 };
 
-struct slg_batch {
+// Every device buffer of a batch, and nothing else: slg_index_destroy detaches a batch that outlives the index by
+// move-assigning a fresh one of these over it (slghost::release_batch_buffers), so a DevBuf declared here is
+// released there without being named anywhere.  The kinds they belong to are described at slg_batch's scalars.
+struct slg_batch_buffers {
   using DevBuf = slghost::DevBuf;
+  DevBuf d_desc;                     // packed descriptors
+  DevBuf d_bounds, d_rdoc, d_slice_tk, d_slice_doc, d_q_scored, d_slice_desc;
+  DevBuf d_q_filter;       // [nq] 0 = none, f + 1 (select_topk_kernel); empty when unfiltered
+  DevBuf d_cand, d_slice_cbeg, d_slice_ccnt;  // cand_mode: candidates + select_topk_kernel
+  DevBuf d_sort_cols;  // slg::SortColDev[kSortMaxParts * n_segs]
+  DevBuf d_matched;    // u64[nq] accepted docs (the batches PrepareRequest::counts_matched names, and scan batches)
+  DevBuf d_cursor;  // u32[nq * slg::kCursorStride]: has_cursor, then the key words of the select kernel
+  DevBuf d_seen;    // u32[nq] the cursor's key was seen
+  DevBuf d_out;  // the result block (slghost::ResultBlock) + the error word
+  DevBuf d_stamps;  // SLG_STAMPS diagnostic builds
+  DevBuf d_blk_skip;  // block skipping: postings of non-essential lists that were never loaded (u64)
+  // index-sharded runs (slg_batch_run_sharded): the gathered result blocks of all ranks and the merged
+  // top-k, a result block too
+  DevBuf d_gather, d_merged;
+  DevBuf d_q_cand;               // slg_batch::q_cand on the device
+  DevBuf d_hy_keys, d_hy_work;   // the gathered keys of a range of queries; clause lists, counts, sort space
+  DevBuf d_agg_desc;                 // slg::AggNodeDev[n_nodes], slg::ColumnDev[n_nodes * n_segs], then the rank columns
+  DevBuf d_agg_counts, d_agg_stats;  // u32[nq * count_cells], slg::AggStatDev[nq * stats_cells]
+  DevBuf d_agg_values, d_agg_scratch;         // u64[nq * value_cells], u32[nq * scratch_words]
+  DevBuf d_rs_desc;  // slg::RescoreQuery[nq], then slg::RescoreTerm[total x n_segs]
+  DevBuf d_rs_side;  // first-pass score | rescore score | rescored flag, [nq * k] each
+  DevBuf d_bool_desc;        // slg::BoolQuery[nq], then slg::BoolTerm rows per (query, segment)
+  DevBuf d_phrase_desc;      // slg::PhraseQuery[nq], slg::PhraseVar[phrase_vars], slg::PhraseTerm[phrase_terms]
+  DevBuf d_booltree_desc;    // slg::BoolTreeQuery[nq], BoolTreeNode[bt_nodes], BoolTerm[bt_terms], bitmap addresses
+                             // [bt_filters], then the filter rows
+  DevBuf d_fscore_desc;      // slg::FscoreQuery[nq], FscoreFn[fscore_fns], ColumnDev[fscore_cols], bitmap addresses
+  DevBuf d_script_desc;           // slg::ScriptQuery[nq], ScriptInstr[script_instrs], ColumnDev[fields][n_segs]
+  DevBuf d_cl_desc;  // slg::ColumnDev[n_segs], then slg::SortColDev[kSortMaxParts * n_segs] of the inner sort
+  DevBuf d_cl_side;  // the arrays of slg_batch_fetch_collapse, back to back in its argument order
+  DevBuf d_th_desc;     // slg::TopHitsNodeDev[n_nodes], then slg::SortColDev[n_nodes][kSortMaxParts * n_segs]
+  DevBuf d_th_out;      // doc | seg | score [nq * hit_cells], count [nq * list_cells], status [nq], the error word
+  DevBuf d_th_entries, d_th_cursors;  // uint2[nq * max_entries], u32[nq * cursor_words]
+  DevBuf d_cp_desc;    // slg::AggNodeDev[n_children], ColumnDev[n_children * n_segs], ColumnDev[n_sources * n_segs],
+                       // slg::CompositeSourceDev[n_sources]
+  DevBuf d_cp_ranks;   // u32: the ord_rank of every terms source that has one, back to back
+  DevBuf d_cp_lower;   // u64[nq] the inclusive lower bounds (slg_batch_set_composite_after)
+  DevBuf d_cp_out;     // u64 keys [nq * size], then u32 n_buckets [nq], has_more [nq], the error word
+  DevBuf d_cp_counts, d_cp_stats;  // u32[nq * cp_count_cells], slg::AggStatDev[nq * cp_stats_cells]
+  DevBuf d_tb_desc;   // slg::TermBucketNodeDev[n], ColumnDev[n * n_segs], per node AggNodeDev[], ColumnDev[] of its children
+  DevBuf d_tb_ranks;  // u32: ord_rank and its inverse of every ranked node, back to back
+  DevBuf d_tb_bg;     // u32 [n_segs][n_ords + 1] per distinct (field, background filter): bg_count_kernel's tables
+  DevBuf d_tb_fg, d_tb_bgsum, d_tb_bits;  // u32 / u64 [nq * tb_fg_cells], u32 [nq * tb_bits_words]
+  DevBuf d_tb_out;    // the arrays of slg_batch_fetch_term_buckets and the error word (slg_termbuckets.hip: OutBlock)
+  DevBuf d_tb_sorted; // u32 [nq * rows] the kept ordinals in ordinal order, then [nq * rows] the row of each
+  DevBuf d_tb_counts, d_tb_stats;  // u32[nq * tb_count_cells], slg::AggStatDev[nq * tb_stats_cells]
+};
+
+struct slg_batch : slg_batch_buffers {
   slg_index *idx = nullptr;
   std::shared_ptr<const slghost::IndexState> snap;  // the index state the batch was prepared on
   uint32_t nq = 0, k = 0;
@@ -500,7 +551,6 @@ struct slg_batch {
   bool launched = false;             // slg_batch_run was called at least once
   bool own_stream_set = false;       // slg_batch_set_stream: run on `stream` instead of the index's
   hipStream_t stream = nullptr;
-  DevBuf d_desc;                     // packed descriptors
   const slg::RoundQuery *d_sq = nullptr;
   const slg::TermRef *d_terms = nullptr;
   const uint32_t *d_slice_sq = nullptr;
@@ -508,29 +558,17 @@ struct slg_batch {
   const uint32_t *d_slice_order = nullptr;
   const slg::QueryRef *d_queries = nullptr;
   const uint32_t *d_bnd_coarse = nullptr;
-  DevBuf d_bounds, d_rdoc, d_slice_tk, d_slice_doc, d_q_scored, d_slice_desc;
-  DevBuf d_q_filter;       // [nq] 0 = none, f + 1 (select_topk_kernel); empty when unfiltered
   bool cand_mode = false;  // uniform kernel, k > 256: candidates + select_topk_kernel
-  DevBuf d_cand, d_slice_cbeg, d_slice_ccnt;
   // field-sorted batch (slg_batch_prepare_sorted): candidates of every matched doc + select_sorted_kernel
   bool sorted = false;
   uint32_t score_k = 0;  // k the scoring kernel runs with (a sorted batch: slgplan::planning_k)
   uint32_t n_sort_parts = 0, sort_score_parts = 0, sort_desc_parts = 0;
-  DevBuf d_sort_cols;  // slg::SortColDev[kSortMaxParts * n_segs]
-  DevBuf d_matched;    // u64[nq] accepted docs (sorted and cursor batches)
   // cursor batch (slg_batch_prepare_after): score order (!sorted: select_topk_kernel<true>) or a field sort
   // (select_sorted_kernel<true>)
   bool after = false;
-  DevBuf d_cursor;  // u32[nq * slg::kCursorStride]: has_cursor, then the key words of the select kernel
-  DevBuf d_seen;    // u32[nq] the cursor's key was seen
-  DevBuf d_out;  // the result block (slghost::ResultBlock) + the error word
   uint32_t *d_out_doc = nullptr, *d_out_seg = nullptr, *d_out_count = nullptr;
   float *d_out_score = nullptr;
-  DevBuf d_stamps;  // SLG_STAMPS diagnostic builds
-  DevBuf d_blk_skip;  // block skipping: postings of non-essential lists that were never loaded (u64)
-  // index-sharded runs (slg_batch_run_sharded): the gathered result blocks of all ranks and the merged
-  // top-k, a result block too
-  DevBuf d_gather, d_merged;
+  // index-sharded runs (slg_batch_run_sharded): d_gather and d_merged
   slg_shard_group *shard_group = nullptr;  // the group of the last sharded run (timing goes there)
   hipEvent_t ev_shard[4] = {nullptr, nullptr, nullptr, nullptr};  // start | local kernels done | gathered | merged
   bool shard_timed = false;
@@ -538,9 +576,7 @@ struct slg_batch {
   // hybrid text + vector batch (slg_batch_prepare_hybrid): planned as a sorted batch (candidates of every
   // matched doc), run as a score page without a cursor; slg_batch_hybrid_device then reads the candidates
   bool hybrid = false;
-  std::vector<uint64_t> q_cand;  // [nq + 1] first candidate slot of each query
-  DevBuf d_q_cand;               // the same on the device
-  DevBuf d_hy_keys, d_hy_work;   // the gathered keys of a range of queries; clause lists, counts, sort space
+  std::vector<uint64_t> q_cand;  // [nq + 1] first candidate slot of each query (d_q_cand: the same on the device)
   // aggregation batch (slg_batch_prepare_aggs): planned as a sorted batch, run in score order or under its
   // sort spec; agg_kernel then fills the tables from the candidates (slg_aggs.hip)
   bool aggs = false;
@@ -548,37 +584,28 @@ struct slg_batch {
   std::vector<slg_agg_layout> agg_layout;  // [n_nodes]
   uint32_t agg_count_cells = 0, agg_stats_cells = 0;
   bool agg_lds = false;              // the tables fit SLG_AGG_LDS_BYTES
-  DevBuf d_agg_desc;                 // slg::AggNodeDev[n_nodes], slg::ColumnDev[n_nodes * n_segs], then the rank columns
-  DevBuf d_agg_counts, d_agg_stats;  // u32[nq * count_cells], slg::AggStatDev[nq * stats_cells]
   // value nodes (cardinality, percentiles, percentile_ranks): agg_values_kernel behind agg_kernel
   uint32_t agg_value_nodes = 0, agg_value_cells = 0, agg_card_words = 0, agg_scratch_words = 0, agg_pct_lds = 0;
   bool agg_walk1 = false, agg_x_lds = false;  // a cardinality / percentile_ranks node; cells and bitmaps fit LDS
   bool agg_ext = false;                       // a date_histogram or filter node: the kernels that hold those paths
-  DevBuf d_agg_values, d_agg_scratch;         // u64[nq * value_cells], u32[nq * scratch_words]
   // rescore batch (slg_batch_prepare_rescore): rescore_kernel runs behind the first pass's last kernel and
   // rewrites the first rows of every query in place (slg_rescore.hip)
   bool rescore = false;
   uint32_t rs_lds_rows = 0, rs_max_table = 0;  // LDS rows (>= every window, even) and table entries of the launch
-  DevBuf d_rs_desc;  // slg::RescoreQuery[nq], then slg::RescoreTerm[total x n_segs]
-  DevBuf d_rs_side;  // first-pass score | rescore score | rescored flag, [nq * k] each
   // bool batch (slg_batch_prepare_bool): planned as a sorted batch, run in score order or under its sort spec;
   // bool_filter_kernel runs between the scoring kernel and the select and drops the candidates the clause
   // tables reject (slg_bool.hip)
   bool boolean = false;
   uint32_t bool_groups = 0;  // groups of all queries (0: no query has a clause table, nothing is launched)
-  DevBuf d_bool_desc;        // slg::BoolQuery[nq], then slg::BoolTerm rows per (query, segment)
   // phrase batch (slg_batch_prepare_phrase): a bool batch (boolean is set, d_bool_desc holds the term groups'
   // tables) whose clause tables also have phrase groups; phrase_filter_kernel runs in bool_filter_kernel's
   // place (slg_phrase.hip)
   bool phrase = false;
   uint32_t phrase_vars = 0, phrase_terms = 0;  // entries of the two tables behind the PhraseQuery records
-  DevBuf d_phrase_desc;      // slg::PhraseQuery[nq], slg::PhraseVar[phrase_vars], slg::PhraseTerm[phrase_terms]
   // tree batch (slg_batch_prepare_bool_tree): planned and run as a bool batch; booltree_filter_kernel runs in
   // bool_filter_kernel's place and drops the candidates the query's matcher tree rejects (slg_booltree.hip)
   bool booltree = false;
   uint32_t bt_nodes = 0, bt_terms = 0, bt_filters = 0;  // entries of the tables (bt_nodes 0: nothing is launched)
-  DevBuf d_booltree_desc;    // slg::BoolTreeQuery[nq], BoolTreeNode[bt_nodes], BoolTerm[bt_terms], bitmap addresses
-                             // [bt_filters], then the filter rows
   // function_score batch (slg_batch_prepare_fscore): planned as a sorted batch, run in score order or under its
   // sort spec; fscore_kernel runs between the scoring kernel and the select, rewrites every candidate's score and
   // drops the candidates below min_score (slg_fscore.hip)
@@ -586,7 +613,6 @@ struct slg_batch {
   uint32_t fscore_work = 0;  // queries with work (0: nothing is launched)
   bool fscore_full = false;  // some function needs ln / log1p / log2 / pow: the full instantiation
   uint32_t fscore_fns = 0, fscore_cols = 0;  // entries of the two tables behind the FscoreQuery records
-  DevBuf d_fscore_desc;      // slg::FscoreQuery[nq], FscoreFn[fscore_fns], ColumnDev[fscore_cols], bitmap addresses
   // script_score batch (slg_batch_prepare_script): planned as a function_score batch is; script_kernel runs between
   // the scoring kernel and the select — alone, in front of the fscore stage (script_first) or behind it — rewrites
   // every candidate's score and drops the candidates whose script gives none (slg_script.hip)
@@ -594,7 +620,6 @@ struct slg_batch {
   uint32_t script_work = 0;       // queries with a program (0: nothing is launched)
   uint32_t script_max_depth = 0;  // the deepest stack of the batch's programs
   uint32_t script_instrs = 0;     // entries of the instruction table behind the ScriptQuery records
-  DevBuf d_script_desc;           // slg::ScriptQuery[nq], ScriptInstr[script_instrs], ColumnDev[fields][n_segs]
   // scan batch (slg_batch_prepare_scan): no scored term, so no sub-queries, terms or rounds; scan_kernel fills the
   // candidate regions in the place of the partition and scoring kernels and counts d_q_scored and d_matched
   // (slg_scan.hip).  d_desc holds slg::ScanSlice[n_slices], ScanQuery[nq], ColumnDev[fields][n_segs], then the
@@ -607,8 +632,6 @@ struct slg_batch {
   uint32_t cl_groups = 0, cl_from = 0, cl_size = 0;  // group_limit, inner_from, inner_size
   uint32_t cl_lds_rows = 0;                          // rows the kernel's LDS arrays hold: a power of two >= k
   uint32_t cl_parts = 0, cl_score_parts = 0, cl_desc_parts = 0;  // the inner sort (0 parts: the batch's own order)
-  DevBuf d_cl_desc;  // slg::ColumnDev[n_segs], then slg::SortColDev[kSortMaxParts * n_segs] of the inner sort
-  DevBuf d_cl_side;  // the arrays of slg_batch_fetch_collapse, back to back in its argument order
   // top_hits batch (slg_batch_prepare_top_hits): an aggregation batch, or a plain / sorted one planned as such;
   // top_hits_kernel runs behind agg_kernel and fills the lists from the candidates (slg_tophits.hip)
   bool top_hits = false;
@@ -618,9 +641,6 @@ struct slg_batch {
   uint32_t th_max_entries = 0;                   // run slots of one query
   uint32_t th_cursor_words = 0, th_lds_cursors = 0;  // cursors of one query in device memory / in LDS
   bool th_ext = false;  // a date_histogram or filter parent: the instantiation that holds those paths
-  DevBuf d_th_desc;     // slg::TopHitsNodeDev[n_nodes], then slg::SortColDev[n_nodes][kSortMaxParts * n_segs]
-  DevBuf d_th_out;      // doc | seg | score [nq * hit_cells], count [nq * list_cells], status [nq], the error word
-  DevBuf d_th_entries, d_th_cursors;  // uint2[nq * max_entries], u32[nq * cursor_words]
   // composite batch (slg_batch_prepare_composite): an aggregation batch, or a plain / sorted one planned as such;
   // composite_select_kernel and composite_collect_kernel run behind agg_kernel (slg_composite.hip).  The composite's
   // tables are its own: agg_kernel's keep their stride, slg_batch_fetch_aggs puts the two side by side
@@ -631,12 +651,6 @@ struct slg_batch {
   uint32_t cp_cap = 0;        // entries of one wave's key set in composite_select_kernel
   bool cp_lds = false, cp_ext = false;  // the tables fit SLG_AGG_LDS_BYTES; a date_histogram or filter child
   size_t cp_cols_off = 0, cp_src_cols_off = 0, cp_src_off = 0;  // byte offsets into d_cp_desc
-  DevBuf d_cp_desc;    // slg::AggNodeDev[n_children], ColumnDev[n_children * n_segs], ColumnDev[n_sources * n_segs],
-                       // slg::CompositeSourceDev[n_sources]
-  DevBuf d_cp_ranks;   // u32: the ord_rank of every terms source that has one, back to back
-  DevBuf d_cp_lower;   // u64[nq] the inclusive lower bounds (slg_batch_set_composite_after)
-  DevBuf d_cp_out;     // u64 keys [nq * size], then u32 n_buckets [nq], has_more [nq], the error word
-  DevBuf d_cp_counts, d_cp_stats;  // u32[nq * cp_count_cells], slg::AggStatDev[nq * cp_stats_cells]
   // term bucket batch (slg_batch_prepare_term_buckets): an aggregation batch, or a plain / sorted one planned as
   // such; term_bucket_count_kernel, _select_kernel and (a node with children) _collect_kernel run behind agg_kernel
   // (slg_termbuckets.hip).  The children's cells lie behind the aggregation spec's in the arrays of
@@ -654,13 +668,6 @@ struct slg_batch {
   };
   TbNodeTables tb_tables[SLG_MAX_TERM_BUCKET_NODES];
   size_t tb_cols_off = 0;  // byte offset of the nodes' columns in d_tb_desc
-  DevBuf d_tb_desc;   // slg::TermBucketNodeDev[n], ColumnDev[n * n_segs], per node AggNodeDev[], ColumnDev[] of its children
-  DevBuf d_tb_ranks;  // u32: ord_rank and its inverse of every ranked node, back to back
-  DevBuf d_tb_bg;     // u32 [n_segs][n_ords + 1] per distinct (field, background filter): bg_count_kernel's tables
-  DevBuf d_tb_fg, d_tb_bgsum, d_tb_bits;  // u32 / u64 [nq * tb_fg_cells], u32 [nq * tb_bits_words]
-  DevBuf d_tb_out;    // the arrays of slg_batch_fetch_term_buckets and the error word (slg_termbuckets.hip: OutBlock)
-  DevBuf d_tb_sorted; // u32 [nq * rows] the kept ordinals in ordinal order, then [nq * rows] the row of each
-  DevBuf d_tb_counts, d_tb_stats;  // u32[nq * tb_count_cells], slg::AggStatDev[nq * tb_stats_cells]
 };
 
 namespace slghost __attribute__((visibility("hidden"))) {
@@ -750,11 +757,22 @@ struct Staging {
 };
 
 // ---- defined in one unit, used by others -------------------------------------------------------
-// slg_batch.hip: free everything a batch holds on the device; with `to_pool` false the blocks go straight
-// back to the runtime (the index and its pool are going away)
-void release_batch_buffers(slg_batch *b, bool to_pool);
+// slg_batch.hip: give back everything a batch holds on the device, its shard events included (slg_index_destroy,
+// on the index's device, its pool still alive: the blocks go there or, past its cap, to the runtime).  The
+// batch's scalar facts stay: slg_batch_info and the *_layout calls still answer
+void release_batch_buffers(slg_batch *b);
 // slg_batch.hip: the merge of several ranks' (or shards') rows
 void launch_shard_merge(const slg::ShardMergeParams &mp, hipStream_t st);
+// slg_batch.hip: a sort spec against an index state: the column table [kSortMaxParts * n_segs] (part p of segment
+// s at p * n_segs + s; null rows for `_score` parts and beyond the spec) and the bits of the `_score` and the
+// descending parts.  Throws SLG_ERR_INVALID "<prefix>unknown sort field id in <part>I" and "<prefix>sort field N
+// has no column for segment S (added after the field was registered)"
+struct SortBinding {
+  std::vector<slg::SortColDev> cols;
+  uint32_t score_parts = 0, desc_parts = 0;
+};
+SortBinding bind_sort(const IndexState &S, const slg_sort_spec &spec, const std::string &prefix, const std::string &part);
+
 // slg_batch.hip: every slg_batch_prepare* is one PrepareRequest.  The query arrays, and one member per batch
 // kind; a kind that was asked for and its spec travel together, so a kind asked for with a NULL spec still
 // reaches its check.  (hybrid and aggs plan as slg_batch_prepare_plans / _sorted with BatchIn::sorted)
@@ -787,6 +805,15 @@ struct PrepareRequest {
   Asked<slg_top_hits_spec> top_hits;  // slg_batch_prepare_top_hits (aggs: on when its spec is given)
   Asked<slg_composite_spec> composite;  // slg_batch_prepare_composite (aggs: on when its spec is given)
   Asked<slg_term_bucket_spec> term_buckets;  // slg_batch_prepare_term_buckets (aggs: on when its spec is given)
+  // the batch counts the docs its select, agg_kernel or a kernel behind them accepts (slg_batch::d_matched) ...
+  bool counts_matched() const {
+    return sort.spec != nullptr || cursor.on || aggs.on || top_hits.on || composite.on || term_buckets.on;
+  }
+  // ... and is planned with candidates of every matched doc (BatchIn::sorted): those, and the kinds whose kernels
+  // between scoring and select read or rewrite every candidate
+  bool plans_every_match() const {
+    return counts_matched() || hybrid || boolean.on || booltree.on || fscore.on || script.on;
+  }
 };
 // a spec that is a kind of its own only when it is given (the sort of a bool, phrase, cursor or agg batch)
 template <typename T>
@@ -794,6 +821,69 @@ Asked<T> if_given(const T *spec) {
   return Asked<T>{spec != nullptr, spec};
 }
 slg_batch *prepare_impl(const PrepareRequest &r);
+
+// ---- what slg_batch_prepare_scan (slg_scan.hip) shares with prepare_impl -----------------------------------------
+// the argument checks of a sort spec (null: score order), made before planning
+inline void check_sort_spec(const slg_sort_spec *sort) {
+  if (!sort) return;
+  if (sort->n_parts > SLG_MAX_SORT_PARTS) throw SlgError(SLG_ERR_UNSUPPORTED, "more than SLG_MAX_SORT_PARTS sort parts");
+  SLG_REQUIRE(sort->n_parts >= 1, "a sort spec needs at least one part");
+  for (uint32_t i = 0; i < sort->n_parts; i++)
+    SLG_REQUIRE(sort->order[i] == SLG_ORDER_ASC || sort->order[i] == SLG_ORDER_DESC, "unknown sort order");
+}
+// which filter ids of a state a query may name, as the planners read it
+inline std::vector<char> filter_liveness(const IndexState &S) {
+  std::vector<char> live(S.filters.size());
+  for (size_t f = 0; f < live.size(); f++) live[f] = S.filter_usable(f);
+  return live;
+}
+// slg_batch.hip: what the select kernels read and write, onto the device: the planned filter words (empty: no
+// query is filtered), the columns of the sort (null: score order), the matched counts if the batch has them, and
+// the result block
+void attach_select_buffers(slg_batch *b, const std::vector<uint32_t> &q_filter, const slg_sort_spec *sort,
+                           const SortBinding &sorting, bool counts_matched);
+// the frame of a prepare call: build(b) checks, plans, allocates b and fills it, throwing at the first fault; the
+// finished batch is registered with its index, a half-built one destroyed (the thread's error kept)
+template <typename F>
+slg_batch *prepare_guarded(F &&build) {
+  slg_batch *b = nullptr;
+  const int rc = guarded([&] {
+    build(b);
+    std::lock_guard<std::mutex> lk(b->idx->mu);
+    b->idx->live.push_back(b);
+  });
+  if (rc != SLG_OK) {
+    KeepLastError keep;
+    delete b;
+    return nullptr;
+  }
+  return b;
+}
+// the host arrays of a one-call search: the rows, and what the batch's kind adds to them (null: not asked for)
+struct HostOut {
+  uint32_t *doc, *seg;
+  float *score;
+  uint32_t *count;
+  slg_stats *stats = nullptr;
+  uint64_t *matched = nullptr;
+  uint8_t *seen = nullptr;
+  uint64_t *agg_counts = nullptr;  // (an aggregation batch)
+  slg_agg_stats *agg_stats = nullptr;
+  uint64_t *agg_values = nullptr;
+  float *first_score = nullptr, *rescore_score = nullptr;  // (a rescore batch)
+  uint32_t *rescored = nullptr;
+  void *const *collapse = nullptr;  // (a collapse batch) the 14 arrays of slg_batch_fetch_collapse, in its order
+  uint32_t *th_doc = nullptr, *th_seg = nullptr, *th_count = nullptr, *th_status = nullptr;  // (a top_hits batch)
+  float *th_score = nullptr;
+  uint64_t *cp_keys = nullptr;  // (a composite batch)
+  uint32_t *cp_n_buckets = nullptr, *cp_has_more = nullptr;
+  uint32_t *tb_ords = nullptr, *tb_n_buckets = nullptr;  // (a term bucket batch)
+  uint64_t *tb_doc_counts = nullptr, *tb_bg_counts = nullptr, *tb_score_bits = nullptr, *tb_node_dc = nullptr,
+           *tb_node_bg = nullptr;
+};
+// slg_batch.hip: a prepared batch (null: prepare failed and set the thread's error) run to the caller's host arrays
+// and destroyed: the first error is the one reported
+int run_to_host(slg_batch *b, const HostOut &o);
 
 // the tables of a batch kind: host arrays back to back as one image in a pooled device buffer, one copy
 struct ImagePart {
@@ -830,6 +920,33 @@ struct FetchBlock {
   }
 };
 
+// `words` words of a batch's side buffer whose last word is the error word (the arrays of a collapse, top_hits,
+// composite or term bucket batch): ONE D2H copy (as slg_batch_fetch), waited for; rows a scoring wave gave up on
+// are not made into an answer
+struct SideBlock : FetchBlock {
+  SideBlock(const slg_batch *b, const DevBuf &side, size_t words, hipStream_t st) : FetchBlock(b->idx->pool, words) {
+    SLG_HIP(hipMemcpyAsync(p, side.p, words * 4, hipMemcpyDeviceToHost, st));
+    SLG_HIP(wait_stream(st));
+    if (p[words - 1] != 0u)
+      throw SlgError(SLG_ERR_INTERNAL, "a scoring wave gave up on a round (chunk-loop guard): results are incomplete");
+  }
+};
+
+// where a kernel that walks the candidates behind the select (top_hits, composite, term buckets) adds up a query's
+// matched docs: nowhere when the sorted select or, in score order, agg_kernel has counted them
+inline unsigned long long *post_select_matched(const slg_batch *b) {
+  return (b->sorted || b->aggs) ? nullptr : b->d_matched.as<unsigned long long>();
+}
+// the cells of the aggregation spec in a query's rows (all 0 without one): what a composite's or a term bucket
+// node's own cells lie behind
+struct AggSpecCells {
+  uint32_t count = 0, stats = 0, value = 0;
+  uint64_t all() const { return (uint64_t)count + stats + value; }
+};
+inline AggSpecCells agg_spec_cells(const slg_batch *b) {
+  return b->aggs ? AggSpecCells{b->agg_count_cells, b->agg_stats_cells, b->agg_value_cells} : AggSpecCells{};
+}
+
 // what the kernels that walk a query's candidate regions share (the two selects, agg_kernel): the slices of each
 // query, their regions, and the tombstones and filters of the batch's state
 template <typename P>
@@ -845,16 +962,6 @@ void fill_candidates(P &p, const slg_batch *b) {
   p.reject_table = S.d_reject_table.as<const uint32_t *>();
   p.n_segs = (uint32_t)S.segs.size();
 }
-
-// slg_batch.hip: a sort spec against an index state: the column table [kSortMaxParts * n_segs] (part p of segment
-// s at p * n_segs + s; null rows for `_score` parts and beyond the spec) and the bits of the `_score` and the
-// descending parts.  Throws SLG_ERR_INVALID "<prefix>unknown sort field id in <part>I" and "<prefix>sort field N
-// has no column for segment S (added after the field was registered)"
-struct SortBinding {
-  std::vector<slg::SortColDev> cols;
-  uint32_t score_parts = 0, desc_parts = 0;
-};
-SortBinding bind_sort(const IndexState &S, const slg_sort_spec &spec, const std::string &prefix, const std::string &part);
 
 // what the launches of the two clause-filter kernels share (P: slg::BoolFilterParams, slg_clause.hpp): the
 // slices, the candidates and the term groups' tables of a bool or phrase batch

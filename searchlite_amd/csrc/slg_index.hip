@@ -542,7 +542,7 @@ void slg_index_destroy(slg_index *ix) {
     // slg_batch_destroy, every other call on it fails with SLG_ERR_INVALID
     std::lock_guard<std::mutex> lk(ix->mu);
     for (slg_batch *b : ix->live) {
-      release_batch_buffers(b, false);
+      release_batch_buffers(b);
       b->snap.reset();
       b->idx = nullptr;
     }

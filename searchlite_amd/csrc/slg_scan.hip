@@ -49,21 +49,13 @@ extern "C" {
 
 slg_batch *slg_batch_prepare_scan(slg_index *ix, uint32_t nq, const slg_scan_spec *spec, const int32_t *q_filter,
                                   const slg_sort_spec *sort, const slg_agg_spec *aggs, uint32_t k) {
-  slg_batch *b = nullptr;
-  const int rc = guarded([&] {
+  return prepare_guarded([&](slg_batch *&b) {
     slgplan::check_scan(spec, nq, k);  // (what needs no index comes first, as every argument check)
     if (aggs) agg_check_spec(aggs);
     SLG_REQUIRE(ix != nullptr, "index is NULL");
-    if (sort) {
-      if (sort->n_parts > SLG_MAX_SORT_PARTS)
-        throw SlgError(SLG_ERR_UNSUPPORTED, "more than SLG_MAX_SORT_PARTS sort parts");
-      SLG_REQUIRE(sort->n_parts >= 1, "a sort spec needs at least one part");
-      for (uint32_t i = 0; i < sort->n_parts; i++)
-        SLG_REQUIRE(sort->order[i] == SLG_ORDER_ASC || sort->order[i] == SLG_ORDER_DESC, "unknown sort order");
-    }
+    check_sort_spec(sort);
     const std::shared_ptr<const IndexState> snap = ix->snapshot();
-    std::vector<char> filter_live(snap->filters.size());
-    for (size_t f = 0; f < snap->filters.size(); f++) filter_live[f] = snap->filter_usable(f);
+    const std::vector<char> filter_live = filter_liveness(*snap);
     std::vector<uint32_t> seg_docs(snap->segs.size());
     for (size_t s = 0; s < snap->segs.size(); s++) seg_docs[s] = snap->segs[s]->n_docs;
     SortBinding sorting;
@@ -84,7 +76,6 @@ slg_batch *slg_batch_prepare_scan(slg_index *ix, uint32_t nq, const slg_scan_spe
     b->scan = true;
     b->scan_full = plan.full;
     b->cand_mode = true;
-    b->sorted = sort != nullptr;
     b->n_slices = (uint32_t)plan.slices.size();
     // the tables of the scan, then what the selects read of any batch (all naturally aligned in this order)
     upload_image(b->d_desc, &ix->pool,
@@ -102,37 +93,9 @@ slg_batch *slg_batch_prepare_scan(slg_index *ix, uint32_t nq, const slg_scan_spe
       SLG_HIP(hipMemcpy(b->d_slice_cbeg.p, plan.slice_cbeg.data(), (size_t)b->n_slices * 8, hipMemcpyHostToDevice));
     b->d_slice_ccnt.alloc_pooled(&ix->pool, (size_t)b->n_slices * 4);
     b->d_q_scored.alloc_pooled(&ix->pool, (size_t)nq * 4);
-    if (!plan.q_filter.empty()) {
-      b->d_q_filter.alloc_pooled(&ix->pool, (size_t)nq * 4);
-      SLG_HIP(hipMemcpy(b->d_q_filter.p, plan.q_filter.data(), (size_t)nq * 4, hipMemcpyHostToDevice));
-    }
-    if (b->sorted) {
-      b->n_sort_parts = sort->n_parts;
-      b->sort_score_parts = sorting.score_parts;
-      b->sort_desc_parts = sorting.desc_parts;
-      b->d_sort_cols.alloc_pooled(&ix->pool, sorting.cols.size() * sizeof(slg::SortColDev));
-      SLG_HIP(hipMemcpy(b->d_sort_cols.p, sorting.cols.data(), sorting.cols.size() * sizeof(slg::SortColDev),
-                        hipMemcpyHostToDevice));
-    }
-    b->d_matched.alloc_pooled(&ix->pool, (size_t)std::max<uint32_t>(nq, 1) * 8);
-    const ResultBlock R(nq, k);
-    b->d_out.alloc_pooled(&ix->pool, R.words_with_flag() * 4);
-    b->d_out_doc = R.doc(b->d_out.as<uint32_t>());
-    b->d_out_seg = R.seg(b->d_out.as<uint32_t>());
-    b->d_out_score = R.score(b->d_out.as<uint32_t>());
-    b->d_out_count = R.count(b->d_out.as<uint32_t>());
+    attach_select_buffers(b, plan.q_filter, sort, sorting, true);  // (scan_kernel counts every query's matched docs)
     if (aggs) agg_attach(b, *aggs);
-    {
-      std::lock_guard<std::mutex> lk(ix->mu);
-      ix->live.push_back(b);
-    }
   });
-  if (rc != SLG_OK) {
-    KeepLastError keep;
-    delete b;
-    return nullptr;
-  }
-  return b;
 }
 
 int slg_batch_scan_info(const slg_batch *b, uint32_t *out_variant, uint32_t *out_slices, uint32_t *out_slice_docs) {
@@ -149,16 +112,9 @@ int slg_search_batch_scan(slg_index *ix, uint32_t nq, const slg_scan_spec *spec,
                           const slg_sort_spec *sort, const slg_agg_spec *aggs, uint32_t k, uint32_t *out_doc,
                           uint32_t *out_seg, float *out_score, uint32_t *out_count, uint64_t *out_matched,
                           uint64_t *counts, slg_agg_stats *stats, uint64_t *values) {
-  slg_batch *b = slg_batch_prepare_scan(ix, nq, spec, q_filter, sort, aggs, k);
-  if (!b) return last_error().code;
-  int rc = slg_batch_run(b);
-  if (rc == SLG_OK) rc = slg_batch_fetch(b, out_doc, out_seg, out_score, out_count, nullptr);
-  if (rc == SLG_OK && out_matched) rc = slg_batch_matched_counts(b, out_matched);
-  if (rc == SLG_OK && b->aggs) rc = slg_batch_fetch_aggs(b, counts, stats);
-  if (rc == SLG_OK && b->aggs && b->agg_value_nodes) rc = slg_batch_fetch_agg_values(b, values);
-  KeepLastError keep;
-  slg_batch_destroy(b);
-  return rc;
+  HostOut o{out_doc, out_seg, out_score, out_count, nullptr, out_matched, nullptr, counts, stats};
+  o.agg_values = values;
+  return run_to_host(slg_batch_prepare_scan(ix, nq, spec, q_filter, sort, aggs, k), o);
 }
 
 }  // extern "C"

@@ -134,27 +134,32 @@ void slg_shard_group_destroy(slg_shard_group *g) {
 }
 
 namespace {
+// the kinds of batch that do not run sharded (slg_batch_run_sharded*, slg_batch_fetch_sharded)
+void require_shardable(const slg_batch *b) {
+  // (a cursor's segment_ord is index-global; the shard merge does not apply it)
+  if (b->after) throw SlgError(SLG_ERR_UNSUPPORTED, "a cursor batch does not run sharded");
+  if (b->hybrid) throw SlgError(SLG_ERR_UNSUPPORTED, "a hybrid batch does not run sharded");
+  if (b->aggs) throw SlgError(SLG_ERR_UNSUPPORTED, "an aggregation batch does not run sharded");
+  if (b->rescore) throw SlgError(SLG_ERR_UNSUPPORTED, "a rescore batch does not run sharded");
+  if (b->phrase) throw SlgError(SLG_ERR_UNSUPPORTED, "a phrase batch does not run sharded");
+  if (b->boolean) throw SlgError(SLG_ERR_UNSUPPORTED, "a bool batch does not run sharded");
+  if (b->booltree) throw SlgError(SLG_ERR_UNSUPPORTED, "a tree batch does not run sharded");
+  if (b->fscore) throw SlgError(SLG_ERR_UNSUPPORTED, "a function_score batch does not run sharded");
+  if (b->script) throw SlgError(SLG_ERR_UNSUPPORTED, "a script_score batch does not run sharded");
+  if (b->collapse) throw SlgError(SLG_ERR_UNSUPPORTED, "a collapse batch does not run sharded");
+  if (b->top_hits) throw SlgError(SLG_ERR_UNSUPPORTED, "a top_hits batch does not run sharded");
+  if (b->composite) throw SlgError(SLG_ERR_UNSUPPORTED, "a composite batch does not run sharded");
+  if (b->term_buckets) throw SlgError(SLG_ERR_UNSUPPORTED, "a term bucket batch does not run sharded");
+  if (b->scan) throw SlgError(SLG_ERR_UNSUPPORTED, "a scan batch does not run sharded");
+}
+
 int run_sharded_impl(slg_batch *b, slg_shard_group *g, bool have_seq, uint64_t seq, uint32_t *out_doc,
                      uint32_t *out_seg, float *out_score, uint32_t *out_count) {
   int rc = guarded([&] {
     SLG_REQUIRE_LIVE(b);
     SLG_REQUIRE(g != nullptr && g->idx == b->idx, "shard group is NULL or belongs to another index");
     SLG_REQUIRE(g->segs_per_rank >= b->snap->segs.size(), "the shard grew beyond the group's segs_per_rank");
-    // (a cursor's segment_ord is index-global; the shard merge does not apply it)
-    if (b->after) throw SlgError(SLG_ERR_UNSUPPORTED, "a cursor batch does not run sharded");
-    if (b->hybrid) throw SlgError(SLG_ERR_UNSUPPORTED, "a hybrid batch does not run sharded");
-    if (b->aggs) throw SlgError(SLG_ERR_UNSUPPORTED, "an aggregation batch does not run sharded");
-    if (b->rescore) throw SlgError(SLG_ERR_UNSUPPORTED, "a rescore batch does not run sharded");
-    if (b->phrase) throw SlgError(SLG_ERR_UNSUPPORTED, "a phrase batch does not run sharded");
-    if (b->boolean) throw SlgError(SLG_ERR_UNSUPPORTED, "a bool batch does not run sharded");
-    if (b->booltree) throw SlgError(SLG_ERR_UNSUPPORTED, "a tree batch does not run sharded");
-    if (b->fscore) throw SlgError(SLG_ERR_UNSUPPORTED, "a function_score batch does not run sharded");
-    if (b->script) throw SlgError(SLG_ERR_UNSUPPORTED, "a script_score batch does not run sharded");
-    if (b->collapse) throw SlgError(SLG_ERR_UNSUPPORTED, "a collapse batch does not run sharded");
-    if (b->top_hits) throw SlgError(SLG_ERR_UNSUPPORTED, "a top_hits batch does not run sharded");
-    if (b->composite) throw SlgError(SLG_ERR_UNSUPPORTED, "a composite batch does not run sharded");
-    if (b->term_buckets) throw SlgError(SLG_ERR_UNSUPPORTED, "a term bucket batch does not run sharded");
-    if (b->scan) throw SlgError(SLG_ERR_UNSUPPORTED, "a scan batch does not run sharded");
+    require_shardable(b);
   });
   if (rc != SLG_OK) return rc;
   if (!have_seq) {  // call order = the order on every rank, if one thread issues the runs
@@ -281,20 +286,7 @@ int slg_batch_fetch_sharded(slg_batch *b, uint32_t *out_doc, uint32_t *out_seg, 
                             uint32_t *out_count) {
   return guarded([&] {
     SLG_REQUIRE_LIVE(b);
-    if (b->after) throw SlgError(SLG_ERR_UNSUPPORTED, "a cursor batch does not run sharded");
-    if (b->hybrid) throw SlgError(SLG_ERR_UNSUPPORTED, "a hybrid batch does not run sharded");
-    if (b->aggs) throw SlgError(SLG_ERR_UNSUPPORTED, "an aggregation batch does not run sharded");
-    if (b->rescore) throw SlgError(SLG_ERR_UNSUPPORTED, "a rescore batch does not run sharded");
-    if (b->phrase) throw SlgError(SLG_ERR_UNSUPPORTED, "a phrase batch does not run sharded");
-    if (b->boolean) throw SlgError(SLG_ERR_UNSUPPORTED, "a bool batch does not run sharded");
-    if (b->booltree) throw SlgError(SLG_ERR_UNSUPPORTED, "a tree batch does not run sharded");
-    if (b->fscore) throw SlgError(SLG_ERR_UNSUPPORTED, "a function_score batch does not run sharded");
-    if (b->script) throw SlgError(SLG_ERR_UNSUPPORTED, "a script_score batch does not run sharded");
-    if (b->collapse) throw SlgError(SLG_ERR_UNSUPPORTED, "a collapse batch does not run sharded");
-    if (b->top_hits) throw SlgError(SLG_ERR_UNSUPPORTED, "a top_hits batch does not run sharded");
-    if (b->composite) throw SlgError(SLG_ERR_UNSUPPORTED, "a composite batch does not run sharded");
-    if (b->term_buckets) throw SlgError(SLG_ERR_UNSUPPORTED, "a term bucket batch does not run sharded");
-    if (b->scan) throw SlgError(SLG_ERR_UNSUPPORTED, "a scan batch does not run sharded");
+    require_shardable(b);
     SLG_REQUIRE(b->nq == 0 || out_count != nullptr, "out_count is NULL");
     SLG_REQUIRE(b->nq == 0 || b->k == 0 || (out_doc && out_seg && out_score), "output array is NULL");
     if (b->nq == 0) return;

@@ -129,8 +129,8 @@ void slghost::term_buckets_attach(slg_batch *b, const slg_term_bucket_spec &spec
   // the tables: per node n_ords foreground and n_ords background-sum cells, the presence words of a significant
   // node, `size` output rows; with children `size` count cells and the children's tables, behind the cells of the
   // aggregation spec in a query's rows
-  const uint64_t agg_cells =
-      b->aggs ? (uint64_t)b->agg_count_cells + b->agg_stats_cells + b->agg_value_cells : 0u;
+  const AggSpecCells spec_cells = agg_spec_cells(b);
+  const uint64_t agg_cells = spec_cells.all();
   slg_term_bucket_layout lay{};
   lay.n_nodes = nn;
   std::vector<slg::TermBucketNodeDev> nodes(nn);
@@ -164,7 +164,7 @@ void slghost::term_buckets_attach(slg_batch *b, const slg_term_bucket_spec &spec
     lay.nodes[i].row_offset = d.row_off;
   }
   lay.rows = (uint32_t)rows;
-  const uint32_t ac = b->aggs ? b->agg_count_cells : 0u, as = b->aggs ? b->agg_stats_cells : 0u;
+  const uint32_t ac = spec_cells.count, as = spec_cells.stats;
   std::vector<CompositeChildTables> ch(nn);
   uint64_t count_cells = 0, stats_cells = 0;
   for (uint32_t i = 0; i < nn; i++) {
@@ -313,7 +313,7 @@ void slghost::term_buckets_launch(slg_batch *b, hipStream_t st) {
   p.row_of = p.sorted_ords + O.nq * std::max<size_t>(O.rows, 1);
   p.flag = ResultBlock(b->nq, b->k).flag(b->d_out.as<uint32_t>());
   // a sorted batch's select counted the accepted docs, agg_kernel does in score order; without either the count walk
-  p.a.out_matched = (b->sorted || b->aggs) ? nullptr : b->d_matched.as<unsigned long long>();
+  p.a.out_matched = post_select_matched(b);
   if (p.bits_words) {  // (a significant node: the presence words and the sums they guard)
     SLG_HIP(hipMemsetAsync(p.bgsum, 0, nq * std::max<size_t>(p.fg_cells, 1) * 8, st));
     SLG_HIP(hipMemsetAsync(p.bits, 0, nq * (size_t)p.bits_words * 4, st));
@@ -380,15 +380,11 @@ int slg_batch_fetch_term_buckets(slg_batch *b, uint32_t *ords, uint64_t *doc_cou
     DeviceGuard g(b->idx->device);
     const hipStream_t st = locked_stream(b);
     if (b->nq == 0) return;
-    // the arrays and the error word behind them are one block: ONE D2H copy (as slg_batch_fetch)
+    // the arrays and the error word behind them are one block
     const OutBlock O(b);
     const size_t words = O.words(), nr = O.nq * O.rows, nn = O.nq * O.n;
-    FetchBlock host(b->idx->pool, words);
-    uint32_t *const blk = host.p;
-    SLG_HIP(hipMemcpyAsync(blk, b->d_tb_out.p, words * 4, hipMemcpyDeviceToHost, st));
-    SLG_HIP(wait_stream(st));
-    if (blk[words - 1] != 0u)  // rows a scoring wave gave up on are not selected into an answer
-      throw SlgError(SLG_ERR_INTERNAL, "a scoring wave gave up on a round (chunk-loop guard): results are incomplete");
+    const SideBlock host(b, b->d_tb_out, words, st);
+    const uint32_t *const blk = host.p;
     static_assert(sizeof(uint64_t) == sizeof(unsigned long long), "8-byte cells");
     const uint32_t *u64s = blk;
     if (doc_counts) std::memcpy(doc_counts, u64s, nr * 8);

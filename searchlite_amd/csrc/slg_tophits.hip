@@ -98,7 +98,7 @@ void slghost::top_hits_launch(slg_batch *b, hipStream_t st) {
                                                               (size_t)an * sizeof(slg::AggNodeDev))
                    : nullptr;
   p.nq = b->nq;
-  p.count_cells = b->aggs ? b->agg_count_cells : 0u;
+  p.count_cells = agg_spec_cells(b).count;
   p.counts = b->aggs ? b->d_agg_counts.as<const uint32_t>() : nullptr;
   p.n_th = b->th_spec.n_nodes;
   p.th = b->d_th_desc.as<const slg::TopHitsNodeDev>();
@@ -113,7 +113,7 @@ void slghost::top_hits_launch(slg_batch *b, hipStream_t st) {
   p.out = b->d_th_out.as<uint32_t>();
   p.flag = ResultBlock(b->nq, b->k).flag(b->d_out.as<uint32_t>());
   // a sorted batch's select counted the accepted docs, agg_kernel does in score order; without either this kernel
-  p.out_matched = (b->sorted || b->aggs) ? nullptr : b->d_matched.as<unsigned long long>();
+  p.out_matched = post_select_matched(b);
   const size_t lds = ((size_t)slg::kTopHitsMergeWords + b->th_lds_cursors) * 4;
   launch_kernel_lds(b->th_ext ? slg::top_hits_kernel<true> : slg::top_hits_kernel<false>, p, dim3(b->nq),
                     slg::kTopHitsThreads, lds, st);
@@ -139,14 +139,10 @@ int slg_batch_fetch_top_hits(slg_batch *b, uint32_t *out_doc, uint32_t *out_seg,
     DeviceGuard g(b->idx->device);
     const hipStream_t st = locked_stream(b);
     if (b->nq == 0) return;
-    // the arrays and the error word behind them are one block: ONE D2H copy (as slg_batch_fetch)
+    // the arrays and the error word behind them are one block
     const size_t words = out_off(b, 5) + 1;
-    FetchBlock host(b->idx->pool, words);
-    uint32_t *const blk = host.p;
-    SLG_HIP(hipMemcpyAsync(blk, b->d_th_out.p, words * 4, hipMemcpyDeviceToHost, st));
-    SLG_HIP(wait_stream(st));
-    if (blk[words - 1] != 0u)  // rows a scoring wave gave up on are not selected into an answer
-      throw SlgError(SLG_ERR_INTERNAL, "a scoring wave gave up on a round (chunk-loop guard): results are incomplete");
+    const SideBlock host(b, b->d_th_out, words, st);
+    const uint32_t *const blk = host.p;
     void *const dst[5] = {out_doc, out_seg, out_score, out_count, out_status};
     for (uint32_t i = 0; i < 5; i++) {
       const size_t n = out_off(b, i + 1) - out_off(b, i);

@@ -11,7 +11,7 @@ from __future__ import annotations
 import ctypes as C
 import struct
 import weakref
-from typing import List, Optional, Sequence, Tuple
+from typing import List, NamedTuple, Optional, Sequence, Tuple
 
 import numpy as np
 
@@ -1286,6 +1286,73 @@ def sort_cursor(cursor, sort=None) -> "N.SortCursor":
     return c
 
 
+def _addr(x):
+    return None if x is None else C.addressof(x)
+
+
+def _script_spec(script, nq: int):
+    from .script import script_spec
+    return script_spec(script, nq)
+
+
+# argument of PreparedBatch -> (what makes (spec, the objects it points into) of it, the attribute that keeps those).
+# The argument may be that pair already.
+_SPEC_MAKERS = {
+    "script": (_script_spec, "_script_keep"), "fscore": (fscore_spec, "_fscore_keep"),
+    "collapse": (lambda collapse, nq: collapse_spec(collapse), "_collapse_keep"),
+    "clause_tree": (bool_tree_spec, "_tree_keep"), "phrases": (phrase_spec, "_phrase_keep"),
+    "clauses": (bool_spec, "_bool_keep"), "rescore": (rescore_spec, "_rescore_keep"),
+}
+
+
+class _BatchKind(NamedTuple):
+    arg: Optional[str]  # the argument (or the spec an aggs.AggPlan carries) that asks for the kind; None: a plain batch
+    entry: str          # its prepare call
+    own: tuple          # what its pointers between q_filter and k are made from, in the call's order
+    refuses: tuple = ()  # the arguments it is not built on ...
+    message: str = ""    # ... and the ERR_UNSUPPORTED message that says so
+
+
+_FAMILY_REFUSES = ("hybrid", "cursors", "rescore", "clauses", "phrases", "fscore", "collapse", "clause_tree", "script")
+# in the precedence PreparedBatch gives them: the first kind that is asked for is the one prepared
+_BATCH_KINDS = (
+    _BatchKind("term_buckets", "slg_batch_prepare_term_buckets", ("sort", "agg_spec", "term_bucket_spec"),
+               ("top_hits", "composite") + _FAMILY_REFUSES,
+               "significant_terms and rare_terms are built on plain, sorted and aggregation batches only"),
+    _BatchKind("composite", "slg_batch_prepare_composite", ("sort", "agg_spec", "composite_spec"),
+               ("top_hits",) + _FAMILY_REFUSES, "composite is built on plain, sorted and aggregation batches only"),
+    _BatchKind("top_hits", "slg_batch_prepare_top_hits", ("sort", "agg_spec", "top_hits_spec"), _FAMILY_REFUSES,
+               "top_hits is built on plain, sorted and aggregation batches only"),
+    _BatchKind("script", "slg_batch_prepare_script", ("sort", "script", "fscore", "script_order"),
+               ("hybrid", "cursors", "aggs", "rescore", "clauses", "phrases", "collapse", "clause_tree"),
+               "script_score is not built on cursor, hybrid, aggregation, rescore, bool, phrase, collapse or matcher "
+               "tree batches"),
+    _BatchKind("clause_tree", "slg_batch_prepare_bool_tree", ("sort", "clause_tree"),
+               ("hybrid", "cursors", "aggs", "rescore", "clauses", "phrases", "fscore", "collapse"),
+               "a matcher tree is not built on cursor, hybrid, aggregation, rescore, bool, phrase, function_score or "
+               "collapse batches"),
+    _BatchKind("collapse", "slg_batch_prepare_collapse", ("sort", "cursors", "collapse"),
+               ("hybrid", "aggs", "rescore", "clauses", "phrases", "fscore"),
+               "collapse is not built on hybrid, aggregation, rescore, bool, phrase or function_score batches"),
+    _BatchKind("fscore", "slg_batch_prepare_fscore", ("sort", "fscore"),
+               ("hybrid", "cursors", "aggs", "rescore", "clauses", "phrases"),
+               "function_score is not built on cursor, hybrid, aggregation, rescore, bool or phrase batches"),
+    _BatchKind("phrases", "slg_batch_prepare_phrase", ("sort", "clauses", "phrases"),
+               ("hybrid", "cursors", "aggs", "rescore"),
+               "phrases are not built on cursor, hybrid, aggregation or rescore batches"),
+    _BatchKind("clauses", "slg_batch_prepare_bool", ("sort", "clauses"), ("hybrid", "cursors", "aggs", "rescore"),
+               "boolean clauses are not built on cursor, hybrid, aggregation or rescore batches"),
+    _BatchKind("rescore", "slg_batch_prepare_rescore", ("rescore",), ("hybrid", "cursors", "sort", "aggs"),
+               "rescore is not built on sorted, cursor, hybrid or aggregation batches"),
+    _BatchKind("aggs", "slg_batch_prepare_aggs", ("sort", "agg_spec"), ("hybrid", "cursors"),
+               "aggregations are not built on cursor or hybrid batches"),
+    _BatchKind("hybrid", "slg_batch_prepare_hybrid", ()),
+    _BatchKind("cursors", "slg_batch_prepare_after", ("sort", "cursors")),
+    _BatchKind("sort", "slg_batch_prepare_sorted", ("sort",)),
+    _BatchKind(None, "slg_batch_prepare_plans", ()),
+)
+
+
 class PreparedBatch:
     """A planned query batch with device-resident descriptors and work buffers."""
 
@@ -1327,7 +1394,6 @@ class PreparedBatch:
         self.after = cursors is not None
         self.is_hybrid = bool(hybrid)
         assert not (hybrid and (sort is not None or cursors is not None)), "a hybrid batch takes no sort or cursor"
-        self.agg_spec = getattr(aggs, "spec", aggs)  # (an aggs.AggPlan carries its N.AggSpec)
         self.is_rescore = rescore is not None
         self.is_bool = clauses is not None or phrases is not None
         self.is_phrase = phrases is not None
@@ -1335,174 +1401,54 @@ class PreparedBatch:
         self.is_collapse = collapse is not None
         self.is_bool_tree = clause_tree is not None
         self.is_script = script is not None
-        # (an aggs.AggPlan carries its N.TopHitsSpec; a plan of top_hits roots alone has no aggregation node)
-        self.top_hits_spec = getattr(aggs, "top_hits", None) if top_hits is None else top_hits
-        if self.top_hits_spec is not None and self.agg_spec is not None and int(self.agg_spec.n_nodes) == 0:
+        # an aggs.AggPlan carries its N.AggSpec, its N.TopHitsSpec and its composite and significant_terms /
+        # rare_terms nodes, the last two as dicts whose "spec" is the N.CompositeSpec / N.TermBucketSpec
+        carried = lambda name, own: getattr(aggs, name, None) if own is None else own
+        unwrap = lambda x: x["spec"] if isinstance(x, dict) else x
+        self.agg_spec = getattr(aggs, "spec", aggs)
+        self.top_hits_spec = carried("top_hits", top_hits)
+        self.composite_spec = unwrap(carried("composite", composite))
+        self.term_bucket_spec = unwrap(carried("term_buckets", term_buckets))
+        family = (self.top_hits_spec, self.composite_spec, self.term_bucket_spec)
+        # (a plan of top_hits, composite or term bucket roots alone has no aggregation node)
+        if any(x is not None for x in family) and self.agg_spec is not None and int(self.agg_spec.n_nodes) == 0:
             self.agg_spec = None
-        if self.top_hits_spec is not None and (hybrid or cursors is not None or rescore is not None or
-                                               clauses is not None or phrases is not None or fscore is not None or
-                                               collapse is not None or clause_tree is not None or script is not None):
-            # (the library's other prepare calls take no top_hits spec: the refusal is made here with its code)
-            raise N.SlgError(N.ERR_UNSUPPORTED, "top_hits is built on plain, sorted and aggregation batches only")
-        # (an aggs.AggPlan carries its composite: a dict whose "spec" is the N.CompositeSpec)
-        cp = getattr(aggs, "composite", None) if composite is None else composite
-        self.composite_spec = cp["spec"] if isinstance(cp, dict) else cp
-        if self.composite_spec is not None and self.agg_spec is not None and int(self.agg_spec.n_nodes) == 0:
-            self.agg_spec = None
-        if self.composite_spec is not None and (
-                self.top_hits_spec is not None or hybrid or cursors is not None or rescore is not None or
-                clauses is not None or phrases is not None or fscore is not None or collapse is not None or
-                clause_tree is not None or script is not None):
-            # (the library's other prepare calls take no composite spec: the refusal is made here with its code)
-            raise N.SlgError(N.ERR_UNSUPPORTED, "composite is built on plain, sorted and aggregation batches only")
-        # (an aggs.AggPlan carries its significant_terms / rare_terms nodes: a dict whose "spec" is the N.TermBucketSpec)
-        tb = getattr(aggs, "term_buckets", None) if term_buckets is None else term_buckets
-        self.term_bucket_spec = tb["spec"] if isinstance(tb, dict) else tb
-        if self.term_bucket_spec is not None and self.agg_spec is not None and int(self.agg_spec.n_nodes) == 0:
-            self.agg_spec = None
-        if self.term_bucket_spec is not None and (
-                self.top_hits_spec is not None or self.composite_spec is not None or hybrid or cursors is not None or
-                rescore is not None or clauses is not None or phrases is not None or fscore is not None or
-                collapse is not None or clause_tree is not None or script is not None):
-            # (the library's other prepare calls take no term bucket spec: the refusal is made here with its code)
-            raise N.SlgError(N.ERR_UNSUPPORTED, "significant_terms and rare_terms are built on plain, sorted and "
-                                                "aggregation batches only")
-        if self.term_bucket_spec is not None:
-            spec = None if sort is None else sort_spec(sort)
-            self._h = self._lib.slg_batch_prepare_term_buckets(
-                index._h, self.nq, _ptr(q_offsets), _ptr(q_terms), _ptr(q_weights), C.addressof(plans),
-                opt(qf), None if spec is None else C.addressof(spec),
-                None if self.agg_spec is None else C.addressof(self.agg_spec), C.addressof(self.term_bucket_spec),
-                k, strategy)
-        elif self.composite_spec is not None:
-            spec = None if sort is None else sort_spec(sort)
-            self._h = self._lib.slg_batch_prepare_composite(
-                index._h, self.nq, _ptr(q_offsets), _ptr(q_terms), _ptr(q_weights), C.addressof(plans),
-                opt(qf), None if spec is None else C.addressof(spec),
-                None if self.agg_spec is None else C.addressof(self.agg_spec), C.addressof(self.composite_spec),
-                k, strategy)
-        elif self.top_hits_spec is not None:
-            spec = None if sort is None else sort_spec(sort)
-            self._h = self._lib.slg_batch_prepare_top_hits(
-                index._h, self.nq, _ptr(q_offsets), _ptr(q_terms), _ptr(q_weights), C.addressof(plans),
-                opt(qf), None if spec is None else C.addressof(spec),
-                None if self.agg_spec is None else C.addressof(self.agg_spec), C.addressof(self.top_hits_spec),
-                k, strategy)
-        elif script is not None:
-            # (the library's other prepare calls take no script spec: the refusal is made here with its code)
-            if hybrid or cursors is not None or aggs is not None or rescore is not None or clauses is not None or \
-                    phrases is not None or collapse is not None or clause_tree is not None:
-                raise N.SlgError(N.ERR_UNSUPPORTED, "script_score is not built on cursor, hybrid, aggregation, rescore, "
-                                                    "bool, phrase, collapse or matcher tree batches")
-            from .script import script_spec
-            sspec, self._script_keep = script if isinstance(script, tuple) else script_spec(script, self.nq)
-            fspec = None
-            if fscore is not None:
-                fspec, self._fscore_keep = fscore if isinstance(fscore, tuple) else fscore_spec(fscore, self.nq)
-            order = {"outer": N.SCRIPT_OUTER, "inner": N.SCRIPT_INNER}.get(script_order, script_order)
-            spec = None if sort is None else sort_spec(sort)
-            self._h = self._lib.slg_batch_prepare_script(
-                index._h, self.nq, _ptr(q_offsets), _ptr(q_terms), _ptr(q_weights), C.addressof(plans),
-                opt(qf), None if spec is None else C.addressof(spec), C.addressof(sspec),
-                None if fspec is None else C.addressof(fspec), int(order), k, strategy)
-        elif clause_tree is not None:
-            # (the library's other prepare calls take no tree spec: the refusal is made here with its code)
-            if hybrid or cursors is not None or aggs is not None or rescore is not None or clauses is not None or \
-                    phrases is not None or fscore is not None or collapse is not None:
-                raise N.SlgError(N.ERR_UNSUPPORTED, "a matcher tree is not built on cursor, hybrid, aggregation, rescore, "
-                                                    "bool, phrase, function_score or collapse batches")
-            tspec, self._tree_keep = bool_tree_spec(clause_tree, self.nq)
-            spec = None if sort is None else sort_spec(sort)
-            self._h = self._lib.slg_batch_prepare_bool_tree(
-                index._h, self.nq, _ptr(q_offsets), _ptr(q_terms), _ptr(q_weights), C.addressof(plans),
-                opt(qf), None if spec is None else C.addressof(spec), C.addressof(tspec), k, strategy)
-        elif collapse is not None:
-            # (the library's other prepare calls take no collapse spec: the refusal is made here with its code)
-            if hybrid or aggs is not None or rescore is not None or clauses is not None or phrases is not None or \
-                    fscore is not None:
-                raise N.SlgError(N.ERR_UNSUPPORTED, "collapse is not built on hybrid, aggregation, rescore, bool, "
-                                                    "phrase or function_score batches")
-            cspec, self._collapse_keep = collapse if isinstance(collapse, tuple) else collapse_spec(collapse)
-            self.collapse_shape = (int(cspec.group_limit), int(cspec.inner_size))
-            spec = None if sort is None else sort_spec(sort)
-            cur = None
-            if cursors is not None:
+        given = dict(sort=sort, cursors=cursors, hybrid=hybrid or None, aggs=aggs, rescore=rescore, clauses=clauses,
+                     phrases=phrases, fscore=fscore, collapse=collapse, clause_tree=clause_tree, script=script,
+                     top_hits=family[0], composite=family[1], term_buckets=family[2])
+        kinds = [kd for kd in _BATCH_KINDS if kd.arg is None or given[kd.arg] is not None]
+        # The library's other prepare calls take no spec of the kind: the refusal is made here with its code.  The
+        # specs an AggPlan can carry speak before a kind is chosen, top_hits first; of the rest the chosen kind alone
+        for kd in [x for x in reversed(_BATCH_KINDS[:3]) if x in kinds] or kinds[:1]:
+            if any(given[name] is not None for name in kd.refuses):
+                raise N.SlgError(N.ERR_UNSUPPORTED, kd.message)
+        held = []  # what only the prepare call reads: alive until it has returned
+
+        def pointer(slot):
+            if slot == "script_order":
+                return int({"outer": N.SCRIPT_OUTER, "inner": N.SCRIPT_INNER}.get(script_order, script_order))
+            if slot.endswith("_spec"):
+                return _addr(getattr(self, slot))
+            if given[slot] is None:
+                return None
+            if slot == "sort":
+                obj = sort_spec(sort)
+            elif slot == "cursors":
                 assert len(cursors) == self.nq
-                cur = (N.SortCursor * max(self.nq, 1))(*[sort_cursor(c, sort) for c in cursors])
-            self._h = self._lib.slg_batch_prepare_collapse(
-                index._h, self.nq, _ptr(q_offsets), _ptr(q_terms), _ptr(q_weights), C.addressof(plans), opt(qf),
-                None if spec is None else C.addressof(spec), None if cur is None else C.addressof(cur),
-                C.addressof(cspec), k, strategy)
-        elif fscore is not None:
-            # (the library's other prepare calls take no fscore spec: the refusal is made here with its code)
-            if hybrid or cursors is not None or aggs is not None or rescore is not None or clauses is not None or \
-                    phrases is not None:
-                raise N.SlgError(N.ERR_UNSUPPORTED, "function_score is not built on cursor, hybrid, aggregation, "
-                                                    "rescore, bool or phrase batches")
-            fspec, self._fscore_keep = fscore if isinstance(fscore, tuple) else fscore_spec(fscore, self.nq)
-            spec = None if sort is None else sort_spec(sort)
-            self._h = self._lib.slg_batch_prepare_fscore(
-                index._h, self.nq, _ptr(q_offsets), _ptr(q_terms), _ptr(q_weights), C.addressof(plans),
-                opt(qf), None if spec is None else C.addressof(spec), C.addressof(fspec), k, strategy)
-        elif phrases is not None:
-            # (the library's other prepare calls take no phrase spec: the refusal is made here with its code)
-            if hybrid or cursors is not None or aggs is not None or rescore is not None:
-                raise N.SlgError(N.ERR_UNSUPPORTED, "phrases are not built on cursor, hybrid, aggregation or rescore batches")
-            pspec, self._phrase_keep = phrase_spec(phrases, self.nq)
-            bspec = None
-            if clauses is not None:
-                bspec, self._bool_keep = bool_spec(clauses, self.nq)
-            spec = None if sort is None else sort_spec(sort)
-            self._h = self._lib.slg_batch_prepare_phrase(
-                index._h, self.nq, _ptr(q_offsets), _ptr(q_terms), _ptr(q_weights), C.addressof(plans),
-                opt(qf), None if spec is None else C.addressof(spec), None if bspec is None else C.addressof(bspec),
-                C.addressof(pspec), k, strategy)
-        elif clauses is not None:
-            # (the library's other prepare calls take no bool spec: the refusal is made here with its code)
-            if hybrid or cursors is not None or aggs is not None or rescore is not None:
-                raise N.SlgError(N.ERR_UNSUPPORTED, "boolean clauses are not built on cursor, hybrid, aggregation or rescore batches")
-            bspec, self._bool_keep = bool_spec(clauses, self.nq)
-            spec = None if sort is None else sort_spec(sort)
-            self._h = self._lib.slg_batch_prepare_bool(
-                index._h, self.nq, _ptr(q_offsets), _ptr(q_terms), _ptr(q_weights), C.addressof(plans),
-                opt(qf), None if spec is None else C.addressof(spec), C.addressof(bspec), k, strategy)
-        elif rescore is not None:
-            # (the library's other prepare calls take no rescore spec: the refusal is made here with its code)
-            if hybrid or cursors is not None or sort is not None or aggs is not None:
-                raise N.SlgError(N.ERR_UNSUPPORTED, "rescore is not built on sorted, cursor, hybrid or aggregation batches")
-            spec, self._rescore_keep = rescore_spec(rescore, self.nq)
-            self._h = self._lib.slg_batch_prepare_rescore(
-                index._h, self.nq, _ptr(q_offsets), _ptr(q_terms), _ptr(q_weights), C.addressof(plans),
-                opt(qf), C.addressof(spec), k, strategy)
-        elif aggs is not None:
-            # (cursor and hybrid batches take no aggregations: the library's prepare calls for them have no
-            #  spec argument, so the refusal is made here with the library's code)
-            if hybrid or cursors is not None:
-                raise N.SlgError(N.ERR_UNSUPPORTED, "aggregations are not built on cursor or hybrid batches")
-            spec = None if sort is None else sort_spec(sort)
-            self._h = self._lib.slg_batch_prepare_aggs(
-                index._h, self.nq, _ptr(q_offsets), _ptr(q_terms), _ptr(q_weights), C.addressof(plans),
-                opt(qf), None if spec is None else C.addressof(spec), C.addressof(self.agg_spec), k, strategy)
-        elif hybrid:
-            self._h = self._lib.slg_batch_prepare_hybrid(
-                index._h, self.nq, _ptr(q_offsets), _ptr(q_terms), _ptr(q_weights), C.addressof(plans),
-                opt(qf), k, strategy)
-        elif cursors is not None:
-            assert len(cursors) == self.nq
-            cur = (N.SortCursor * max(self.nq, 1))(*[sort_cursor(c, sort) for c in cursors])
-            spec = None if sort is None else sort_spec(sort)
-            self._h = self._lib.slg_batch_prepare_after(
-                index._h, self.nq, _ptr(q_offsets), _ptr(q_terms), _ptr(q_weights), C.addressof(plans),
-                opt(qf), None if spec is None else C.addressof(spec), C.addressof(cur), k, strategy)
-        elif sort is None:
-            self._h = self._lib.slg_batch_prepare_plans(
-                index._h, self.nq, _ptr(q_offsets), _ptr(q_terms), _ptr(q_weights), C.addressof(plans),
-                opt(qf), k, strategy)
-        else:
-            spec = sort_spec(sort)
-            self._h = self._lib.slg_batch_prepare_sorted(
-                index._h, self.nq, _ptr(q_offsets), _ptr(q_terms), _ptr(q_weights), C.addressof(plans),
-                opt(qf), C.addressof(spec), k, strategy)
+                obj = (N.SortCursor * max(self.nq, 1))(*[sort_cursor(c, sort) for c in cursors])
+            else:
+                make, keep = _SPEC_MAKERS[slot]
+                made = given[slot] if isinstance(given[slot], tuple) else make(given[slot], self.nq)
+                obj = made[0]
+                setattr(self, keep, made[1])
+                if slot == "collapse":
+                    self.collapse_shape = (int(obj.group_limit), int(obj.inner_size))
+            held.append(obj)
+            return C.addressof(obj)
+
+        self._h = getattr(self._lib, kinds[0].entry)(
+            index._h, self.nq, _ptr(q_offsets), _ptr(q_terms), _ptr(q_weights), C.addressof(plans), opt(qf),
+            *[pointer(slot) for slot in kinds[0].own], k, strategy)
         if not self._h:
             raise N.SlgError(N.last_error_code() or N.ERR_INVALID, N.last_error())
         index._batches.add(self)

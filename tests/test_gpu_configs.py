@@ -286,17 +286,50 @@ def test_tie_breaker_outside_unit_interval_is_rejected(gpu):
         ix.search_plan(offs, terms, w, 5, q_plan=[gpu.PLAN_DISMAX], q_tie=[0.0])
 
 
-def test_index_closed_before_its_batches(gpu):
-    """Either destruction order is safe: a batch that outlives its index is detached (calls fail
-    with SLG_ERR_INVALID, destroy stays valid)."""
-    from searchlite_amd import _native as N
-    import ctypes as C
-    seg = random_segment(np.random.default_rng(6), 800, 20, 10)
-    offs, terms, w = random_queries(np.random.default_rng(7), 4, 2, 20)
+def _detach_world(gpu):
+    """the index of test_index_closed_before_its_batches with a sort field, a numeric and a keyword column"""
+    n = 800
+    seg = random_segment(np.random.default_rng(6), n, 20, 10)
     ix = gpu.GpuIndex([seg])
-    b = ix.prepare(offs, terms, w, 5)
+    rows = np.arange(n + 1, dtype=np.uint32)
+    sort_id = ix.add_sort_field([(rows, (np.arange(n) * 7919 % 101).astype(np.int64))], np.int64)
+    num_id = ix.add_agg_field([(rows, (np.arange(n) % 13).astype(np.float64))], np.float64)
+    kw_id = ix.add_agg_keyword_field([(rows, (np.arange(n) % 9).astype(np.uint32))], 9)
+    return seg, ix, sort_id, num_id, kw_id
+
+
+# the kinds whose batches hold d_sort_cols, d_matched, d_cursor or d_seen, a hybrid batch and a batch that ran sharded
+DETACH_KINDS = ["plain", "sorted", "cursor_score", "cursor_sorted", "aggs", "scan_sorted_aggs", "collapse_cursor",
+                "hybrid", "sharded"]
+
+
+@pytest.mark.parametrize("kind", DETACH_KINDS)
+def test_index_closed_before_its_batches(gpu, kind):
+    """Either destruction order is safe: a batch that outlives its index is detached (calls fail
+    with SLG_ERR_INVALID, its facts still answer, destroy stays valid), whatever buffers its kind holds."""
+    from searchlite_amd import _native as N
+    from searchlite_amd import aggs as AG
+    from searchlite_amd import searcher
+    seg, ix, sort_id, num_id, kw_id = _detach_world(gpu)
+    offs, terms, w = random_queries(np.random.default_rng(7), 4, 2, 20)
+    sort = [(sort_id, "desc")]
+    stats = lambda: AG.agg_spec({"a": {"type": "stats", "field": "num"}}, {"num": {"id": num_id}})
+    group = None
+    if kind == "scan_sorted_aggs":
+        b = ix.prepare_scan([{"match_all": {}}] * 4, 5, sort=sort, aggs=stats())
+    else:
+        kw = {"plain": {}, "sorted": dict(sort=sort), "cursor_score": dict(cursors=[None] * 4),
+              "cursor_sorted": dict(cursors=[None] * 4, sort=sort), "aggs": dict(aggs=stats()),
+              "collapse_cursor": dict(collapse=dict(field=kw_id, group_limit=3, inner_size=2), cursors=[None] * 4),
+              "hybrid": dict(hybrid=True), "sharded": {}}[kind]
+        b = ix.prepare(offs, terms, w, 5, **kw)
+    if kind == "sharded":
+        group = searcher.ShardGroup(ix, 0, 1, searcher.shard_unique_id(), 1)
+        b.run_sharded(group)
+        group.close()  # (a group goes before its index)
     b.run()
     b.fetch()
+    facts = b.info()
     # through the raw ABI: destroy the index first, then use and destroy the batch
     lib = N.load()
     h_ix, h_b = ix._h, b._h
@@ -305,8 +338,15 @@ def test_index_closed_before_its_batches(gpu):
     lib.slg_index_destroy(h_ix)
     assert lib.slg_batch_run(h_b) == N.ERR_INVALID
     assert lib.slg_batch_sync(h_b) == N.ERR_INVALID
+    for call in (b.fetch, b.matched_counts):
+        with pytest.raises(N.SlgError) as e:
+            call()
+        assert e.value.code == N.ERR_INVALID
+    assert b.info() == facts  # (slg_batch_info returns SLG_OK and the numbers it gave before)
     lib.slg_batch_destroy(h_b)
     b._h = None
+    if kind != "plain":
+        return
     # through the Python mirror: closing the index closes its batches
     ix2 = gpu.GpuIndex([seg])
     b2 = ix2.prepare(offs, terms, w, 5)

@@ -21,7 +21,13 @@ for src in *.hip; do
   /opt/rocm/bin/hipcc $FLAGS -c "$src" -o "${src%.hip}.o" &
   OBJS="$OBJS ${src%.hip}.o"
 done
-if [ -f slg_plan.cpp ]; then /opt/rocm/bin/hipcc $FLAGS -x c++ -c slg_plan.cpp -o plan.o & OBJS="$OBJS plan.o"; fi
+# the plain C++ units build_gpu links (searchlite_amd/build.py); slg_segfile.cpp and the *_capi.cpp files belong to
+# the host-only libraries
+for src in slg_plan.cpp slg_expand_merge.cpp slg_regex.cpp slg_suggest_host.cpp; do
+  [ -f "$src" ] || continue
+  /opt/rocm/bin/hipcc $FLAGS -x c++ -c "$src" -o "${src%.cpp}_cpp.o" &
+  OBJS="$OBJS ${src%.cpp}_cpp.o"
+done
 wait
 /opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC -o "$ROOT/searchlite_amd/lib/libsearchlite_gpu_$TAG.so" $OBJS
 rm -rf "$TMP"

@@ -49,6 +49,11 @@
  * same dictionaries and their doc frequencies; scan, merge across segments, scores and the best `size` on the
  * device; terms of up to SLG_MAX_EXPAND_CHARS chars, a fuzzy request's size up to SLG_MAX_SUGGEST_CANDIDATES.  The
  * analysis of the prefix, and suggest through the coalescer or shard groups, stay with the caller.
+ * Highlighting (slg_index_add_text_field, slg_highlight_batch, slg_batch_highlight): SearchRequest.highlight and
+ * highlight_field over stored texts registered with the index; the fragments of every (hit, field) with the tags
+ * inserted, for ASCII texts and terms / phrase words of [0-9A-Za-z_]; a text with a byte >= 0x80 is marked for the
+ * CPU per item, other words are refused.  The analysis of the terms, `fields` / return_stored and the sharded and
+ * coalesced paths stay with the caller.
  */
 #ifndef SEARCHLITE_GPU_H
 #define SEARCHLITE_GPU_H
@@ -2286,6 +2291,111 @@ int slg_suggest_batch(slg_index *index, const slg_suggest_req *reqs, uint32_t n_
  * ms, by the host clock: the device part (uploads, the scan's two kernels, the merge kernel, the copy back, the
  * wait) and the host's copy of the texts.  Per thread; `index` is only checked for NULL; either may be NULL. */
 int slg_suggest_phase_ms(slg_index *index, double *device_ms, double *copy_ms);
+
+/* ---- highlighting: fragments and tags over registered texts (index/highlight.rs:11-80; api/reader.rs:3400-3497) --
+ * materialize_hit reads each hit's stored text and runs highlight_fragments over it: for SearchRequest.highlight
+ * per configured field (HighlightOptions: pre_tag, post_tag, fragment_size, number_of_fragments), for
+ * highlight_field through make_snippet ("**", "**", 120, 1; the last fragment is the snippet).  Here the texts of
+ * a field are registered with the index and one call highlights every (hit, field) of a batch of queries on the
+ * device; out_text holds the FINISHED strings, tags inserted.  The host never touches a text.
+ *
+ * TEXT FIELDS.  slg_index_add_text_field(index, seg_offsets, seg_bytes) -> text field id (>= 0) or a negative
+ * error code.  Per segment of the current state u64 offsets[n_docs + 1] and the bytes they index: doc d's text is
+ * bytes[offsets[d] .. offsets[d + 1]).  A doc without the field, or with a value that is no string, has an empty
+ * text (the reference gives both no entry).  A segment without the field passes NULL offsets.  The call copies
+ * bytes[offsets[0] .. offsets[n_docs]) to the device, padded so that a 16-byte load at any doc's last byte stays
+ * inside the allocation, and records one bit per doc: "holds a byte >= 0x80".  The texts are part of the immutable
+ * index state and follow updates as the other registered columns do: slg_index_update_deleted leaves them alone,
+ * slg_index_remove_segment drops the segment's store and the others keep theirs under their new ordinals, a
+ * segment added later (slg_index_add_segment) has no text in the field (SLG_HL_NO_TEXT) until the field is
+ * registered again over all segments; ids are never handed out again.  slg_index_remove_text_field drops a field
+ * (batches prepared before keep it).  SLG_ERR_INVALID: NULL index or seg_offsets, offsets that decrease, NULL bytes
+ * under non-empty offsets, an unknown id; SLG_ERR_UNSUPPORTED: a doc of 2^31 bytes or more.
+ *
+ * WHAT IS COMPUTED (highlight.rs:17-64).  The pattern is `\bw1\W+w2...\b` for each phrase, then `\bterm\b` for
+ * each term, joined by `|`, case-insensitive, leftmost-first.  An empty text or no alternative: no fragments.
+ * Else offset = 0 and number_of_fragments times: m = the first match in the whole text starting at or after offset
+ * (none: stop); start = m.start - min(m.start, fragment_size / 2), end = min(len, start + fragment_size); the
+ * fragment text[start .. end) is taken as a string of its own (its edges are text edges) and every non-overlapping
+ * match in it, left to right, is wrapped in pre_tag .. post_tag; offset = m.end.  So fragments may overlap and
+ * repeat matches, fragment_size 0 yields one empty string per match, and a fragment's edge can cut a word into one
+ * that matches another term.  THE DEVICE BUILDS THE WORD-ONLY CASE: ASCII texts, terms and phrase words of one or
+ * more bytes of [0-9A-Za-z_].  Then a match is exactly a maximal run of word bytes equal to a term under ASCII case
+ * folding, a phrase match as many consecutive runs with anything else between them; at a run start the phrases
+ * are tried in order, then the terms in order.  Every string is the reference's byte for byte, the same from run
+ * to run.  A text with a byte >= 0x80 is not scanned: its items come back as SLG_HL_HOST (with Unicode, `\b` and
+ * case folding depend on the regex crate's tables).
+ *
+ * SPECS.  Every query carries a list of field specs (spec_offsets [n_queries + 1] into specs).  A spec names the
+ * text field and carries the FINAL word lists (the caller runs highlight_terms' analysis per field and
+ * normalize_phrase_terms, as it analyses the input of slg_suggest_batch): word_offsets [n_terms + n_phrase_words +
+ * 1] into word_bytes, the terms first, then the phrases' words; phrase_offsets [n_phrases + 1] counts the phrases'
+ * words from 0.  Tags are any bytes and are copied verbatim.
+ *
+ * TWO ENTRY POINTS, one implementation.  slg_highlight_batch takes host hits in CSR per query (hit_offsets
+ * [n_queries + 1] into hit_seg / hit_doc) against the index's current state.  slg_batch_highlight takes a
+ * finished batch's own device rows (doc, seg, count of slg_batch_fetch) without a round trip: query q's hits are
+ * its first count[q] rows, the state is the one the batch was prepared on, and any batch kind whose results are
+ * those rows will do (the batch must have run; its sharded results are not read).  Both are synchronous.
+ *
+ * OUTPUT (slg_hl_out).  Items are query-major, then hit, then field spec in order.  status [n_items]:
+ * SLG_HL_OK, SLG_HL_HOST (no fragments; highlight this one on the CPU), SLG_HL_NO_TEXT (the hit's segment has no
+ * store for the field; no fragments).  offsets [n_items + 1]: item i's fragments are offsets[i] .. offsets[i + 1]
+ * - 1; text_offsets [n_frags + 1] and text: fragment f is text[text_offsets[f] .. text_offsets[f + 1]), not
+ * NUL-terminated.  item_capacity / frag_capacity = the entries status / text_offsets hold less the one more that
+ * offsets / text_offsets need; text_capacity = the bytes of text.  The call fills n_items, n_frags and text_bytes.
+ * SIZE QUERY: status, offsets, text_offsets and text all NULL: only the three totals are filled (the count pass
+ * runs; nothing is emitted).
+ *
+ * SLG_ERR_INVALID: a NULL index, batch, out or array; a struct_size that is not the struct's; offsets that
+ * decrease or do not start at 0; an unknown text field id; a host hit whose seg or doc is out of range; a term or
+ * a phrase word of no bytes, a phrase of no words (the reference skips empty terms and phrases: drop them before
+ * the call); some but not all of the four output arrays NULL; a capacity too small; a batch that has not run.
+ * SLG_ERR_UNSUPPORTED (CPU path; the message names the query and the field spec): more than SLG_MAX_HL_TERMS terms,
+ * SLG_MAX_HL_PHRASES phrases, SLG_MAX_PHRASE_TERMS words in a phrase, SLG_MAX_EXPAND_CHARS bytes in a word,
+ * SLG_MAX_HL_TAG bytes in a tag, fragment_size above SLG_MAX_HL_FRAGMENT, number_of_fragments above
+ * SLG_MAX_HL_FRAGMENTS, a word with a byte outside [0-9A-Za-z_], 2^32 or more bytes of output.  Never approximated.
+ * NOT BUILT: non-ASCII texts and words (SLG_HL_HOST, or refused), analysis of the terms, `fields` /
+ * return_stored, top_hits snippets through the aggregation fetch (pass their hits to slg_highlight_batch), the
+ * sharded and coalesced paths, compressed doc-store decoding. */
+#define SLG_MAX_HL_TERMS 32u
+#define SLG_MAX_HL_PHRASES 8u
+#define SLG_MAX_HL_TAG 64u         /* bytes of pre_tag and of post_tag */
+#define SLG_MAX_HL_FRAGMENT 1024u  /* fragment_size */
+#define SLG_MAX_HL_FRAGMENTS 8u    /* number_of_fragments */
+enum { SLG_HL_OK = 0, SLG_HL_HOST = 1, SLG_HL_NO_TEXT = 2 };
+typedef struct slg_hl_spec {
+  uint32_t struct_size;            /* sizeof(slg_hl_spec) */
+  int32_t text_field;              /* slg_index_add_text_field */
+  uint32_t n_terms, n_phrases;
+  const uint32_t *phrase_offsets;  /* [n_phrases + 1] over the phrases' words, from 0; NULL with n_phrases == 0 */
+  const uint32_t *word_offsets;    /* [n_terms + phrase_offsets[n_phrases] + 1] into word_bytes, from 0 */
+  const char *word_bytes;
+  const char *pre_tag, *post_tag;
+  uint32_t pre_len, post_len;
+  uint32_t fragment_size, number_of_fragments;
+} slg_hl_spec;
+typedef struct slg_hl_out {
+  uint32_t struct_size;            /* sizeof(slg_hl_out) */
+  uint32_t item_capacity, frag_capacity;
+  uint64_t text_capacity;
+  uint8_t *status;                 /* [item_capacity] */
+  uint32_t *offsets;               /* [item_capacity + 1] */
+  uint32_t *text_offsets;          /* [frag_capacity + 1] */
+  char *text;                      /* [text_capacity] */
+  uint32_t n_items, n_frags;       /* filled by the call */
+  uint64_t text_bytes;
+} slg_hl_out;
+int slg_index_add_text_field(slg_index *index, const uint64_t *const *seg_offsets, const uint8_t *const *seg_bytes);
+int slg_index_remove_text_field(slg_index *index, int text_field_id);
+int slg_highlight_batch(slg_index *index, uint32_t n_queries, const uint32_t *hit_offsets, const uint32_t *hit_seg,
+                        const uint32_t *hit_doc, const uint32_t *spec_offsets, const slg_hl_spec *specs, slg_hl_out *out);
+int slg_batch_highlight(slg_batch *batch, const uint32_t *spec_offsets, const slg_hl_spec *specs, slg_hl_out *out);
+/* DIAGNOSTIC ONLY (tools/highlight_time.py): where the calling thread's last highlight call spent its time, in ms,
+ * by the host clock: the count part (uploads, the count and scan kernels, the totals back, the wait) and the emit
+ * part (the emit kernel, the strings back, the wait; 0 for a size query).  Per thread; `index` is only checked for
+ * NULL; either pointer may be NULL. */
+int slg_highlight_phase_ms(slg_index *index, double *count_ms, double *emit_ms);
 
 #ifdef __cplusplus
 }

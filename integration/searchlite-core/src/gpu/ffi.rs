@@ -204,6 +204,20 @@ pub const SLG_SCAN_MOD_RECIPROCAL: i32 = 4;
     pub field_len: u32, pub term_len: u32, pub max_expansions: u32,
     pub max_edits: u32, pub prefix_length: u32, pub min_length: u32,
 }
+#[repr(C)] pub struct slg_hl_spec {
+    pub struct_size: u32, pub text_field: i32, pub n_terms: u32, pub n_phrases: u32,
+    pub phrase_offsets: *const u32, pub word_offsets: *const u32, pub word_bytes: *const c_char,
+    pub pre_tag: *const c_char, pub post_tag: *const c_char, pub pre_len: u32, pub post_len: u32,
+    pub fragment_size: u32, pub number_of_fragments: u32,
+}
+#[repr(C)] pub struct slg_hl_out {
+    pub struct_size: u32, pub item_capacity: u32, pub frag_capacity: u32, pub text_capacity: u64,
+    pub status: *mut u8, pub offsets: *mut u32, pub text_offsets: *mut u32, pub text: *mut c_char,
+    pub n_items: u32, pub n_frags: u32, pub text_bytes: u64,
+}
+pub const SLG_HL_OK: u8 = 0;
+pub const SLG_HL_HOST: u8 = 1;
+pub const SLG_HL_NO_TEXT: u8 = 2;
 #[repr(C)] pub struct slg_suggest_req {
     pub struct_size: u32, pub field: *const c_char, pub term: *const c_char, pub field_len: u32, pub term_len: u32,
     pub size: u32, pub has_fuzzy: u32, pub max_edits: u32, pub prefix_length: u32, pub max_expansions: u32,
@@ -512,6 +526,16 @@ extern "C" {
         option_capacity: u32, out_score: *mut c_float, out_doc_freq: *mut u64, out_text_offsets: *mut u32,
         text_capacity: u32, out_text: *mut c_char) -> c_int;
     pub fn slg_suggest_phase_ms(index: *mut slg_index, device_ms: *mut f64, copy_ms: *mut f64) -> c_int;
+    // highlighting (SearchRequest.highlight / highlight_field) over registered texts: declared, not routed yet
+    // (INTEGRATION.md says how materialize_hit would use it)
+    pub fn slg_index_add_text_field(index: *mut slg_index, seg_offsets: *const *const u64,
+        seg_bytes: *const *const u8) -> c_int;
+    pub fn slg_index_remove_text_field(index: *mut slg_index, text_field_id: c_int) -> c_int;
+    pub fn slg_highlight_batch(index: *mut slg_index, n_queries: u32, hit_offsets: *const u32, hit_seg: *const u32,
+        hit_doc: *const u32, spec_offsets: *const u32, specs: *const slg_hl_spec, out: *mut slg_hl_out) -> c_int;
+    pub fn slg_batch_highlight(batch: *mut slg_batch, spec_offsets: *const u32, specs: *const slg_hl_spec,
+        out: *mut slg_hl_out) -> c_int;
+    pub fn slg_highlight_phase_ms(index: *mut slg_index, count_ms: *mut f64, emit_ms: *mut f64) -> c_int;
     pub fn slg_batch_prepare_phrase(index: *mut slg_index, nq: u32, q_offsets: *const u32, q_term_ids: *const u32,
         q_weights: *const c_float, plans: *const slg_score_plans, q_filter: *const i32,
         sort: *const slg_sort_spec, bool_spec: *const slg_bool_spec, phrases: *const slg_phrase_spec, k: u32,

@@ -96,6 +96,8 @@ MAX_EXPAND_CHARS = 128
 MAX_EXPANSIONS = 1024
 EXPAND_WAVE, EXPAND_WORKGROUP, EXPAND_CHUNK = 64, 256, 1024  # the scan's geometry (SLG_EXPAND_*)
 MAX_SUGGEST_CANDIDATES, SUGGEST_MIN_SCAN, SUGGEST_MERGE_WORKGROUP = 256, 64, 256  # slg_suggest_batch (SLG_*)
+MAX_HL_TERMS, MAX_HL_PHRASES, MAX_HL_TAG, MAX_HL_FRAGMENT, MAX_HL_FRAGMENTS = 32, 8, 64, 1024, 8  # highlighting (SLG_MAX_HL_*)
+HL_OK, HL_HOST, HL_NO_TEXT = 0, 1, 2
 
 
 class SlgError(RuntimeError):
@@ -306,6 +308,22 @@ class SuggestReq(C.Structure):
     _fields_ = [("struct_size", C.c_uint32), ("field", C.c_char_p), ("term", C.c_char_p), ("field_len", C.c_uint32),
                 ("term_len", C.c_uint32), ("size", C.c_uint32), ("has_fuzzy", C.c_uint32), ("max_edits", C.c_uint32),
                 ("prefix_length", C.c_uint32), ("max_expansions", C.c_uint32), ("min_length", C.c_uint32)]
+
+
+class HlSpec(C.Structure):
+    """slg_hl_spec: one field spec of one query (slg_highlight_batch / slg_batch_highlight)."""
+    _fields_ = [("struct_size", C.c_uint32), ("text_field", C.c_int32), ("n_terms", C.c_uint32), ("n_phrases", C.c_uint32),
+                ("phrase_offsets", C.c_void_p), ("word_offsets", C.c_void_p), ("word_bytes", C.c_void_p),
+                ("pre_tag", C.c_void_p), ("post_tag", C.c_void_p), ("pre_len", C.c_uint32), ("post_len", C.c_uint32),
+                ("fragment_size", C.c_uint32), ("number_of_fragments", C.c_uint32)]
+
+
+class HlOut(C.Structure):
+    """slg_hl_out: the capacities and arrays of a highlight call, and the totals it fills."""
+    _fields_ = [("struct_size", C.c_uint32), ("item_capacity", C.c_uint32), ("frag_capacity", C.c_uint32),
+                ("text_capacity", C.c_uint64), ("status", C.c_void_p), ("offsets", C.c_void_p),
+                ("text_offsets", C.c_void_p), ("text", C.c_void_p), ("n_items", C.c_uint32), ("n_frags", C.c_uint32),
+                ("text_bytes", C.c_uint64)]
 
 
 class Ticket(C.Structure):
@@ -532,6 +550,11 @@ def load():
         "slg_expand_phase_ms": (i32, [vp, vp, vp]),
         "slg_suggest_batch": (i32, [vp, vp, u32, vp, u32, vp, vp, vp, u32, vp]),
         "slg_suggest_phase_ms": (i32, [vp, vp, vp]),
+        "slg_index_add_text_field": (i32, [vp, vp, vp]),
+        "slg_index_remove_text_field": (i32, [vp, i32]),
+        "slg_highlight_batch": (i32, [vp, u32, vp, vp, vp, vp, vp, vp]),
+        "slg_batch_highlight": (i32, [vp, vp, vp, vp]),
+        "slg_highlight_phase_ms": (i32, [vp, vp, vp]),
     }
     for name, (res, args) in sigs.items():
         if os.environ.get("SLG_LIB_TAG") and not hasattr(L, name):

@@ -262,6 +262,13 @@ struct SuggestSegDev {          // the same dictionary as slg_suggest_batch read
   const uint8_t *nchars;
   const uint32_t *df;           // [n] posting-list length of the key at each sorted position, as staged
 };
+struct TextSegDev {             // per segment of a text field (slg_index_add_text_field): its docs' texts
+  const uint8_t *bytes;         // the texts back to back, 16-byte aligned and padded by 16 bytes; or nullptr
+  const uint64_t *offs;         // [n_docs + 1]
+  const uint32_t *non_ascii;    // bit d: doc d's text holds a byte >= 0x80
+  uint32_t n_docs;
+  uint32_t pad_;
+};
 struct PhraseTerm {
   uint64_t off;    // posting offset inside the segment arrays (padded layout, as BoolTerm::off)
   uint64_t ubase;  // the list's first posting in the unpadded order (= term_offsets[term]): PosSegDev::offs index

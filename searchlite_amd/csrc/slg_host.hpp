@@ -1,5 +1,5 @@
 // slg_host.hpp — what the host translation units of the C ABI share (slg_index.hip, slg_batch.hip,
-// slg_shard.hip, slg_rerank.hip, slg_vsearch.hip, slg_hybrid.hip, slg_aggs.hip, slg_rescore.hip, slg_bool.hip, slg_booltree.hip, slg_phrase.hip, slg_fscore.hip, slg_script.hip, slg_scan.hip, slg_collapse.hip, slg_tophits.hip, slg_composite.hip, slg_termbuckets.hip): the error plumbing, device memory, the host
+// slg_shard.hip, slg_rerank.hip, slg_vsearch.hip, slg_hybrid.hip, slg_aggs.hip, slg_rescore.hip, slg_bool.hip, slg_booltree.hip, slg_phrase.hip, slg_fscore.hip, slg_script.hip, slg_scan.hip, slg_collapse.hip, slg_tophits.hip, slg_composite.hip, slg_termbuckets.hip, slg_highlight.hip): the error plumbing, device memory, the host
 // structures behind the opaque handles and the small helpers several entry points use.  Private: not
 // installed, not part of include/.  No kernel header is included here — each unit includes the one
 // whose kernels it launches (slg_stage.hpp, slg_kernels.hpp, slg_rerank.hpp, slg_vsearch.hpp, slg_hybrid.hpp; the shard
@@ -410,6 +410,18 @@ struct TermStore {
   size_t device_bytes() const { return bytes.bytes + offs.bytes + map.bytes + nchars.bytes + d_df.bytes; }
 };
 
+// a registered text field (slg_index_add_text_field): per segment the docs' texts on the device, shared by the
+// states that hold them; null = the segment has no text in the field (it passed NULL, or was added later)
+struct TextSegStore {
+  DevBuf bytes, offs, non_ascii;  // the texts padded by 16 bytes | u64[n_docs + 1] | one bit per doc
+  uint32_t n_docs = 0;
+  size_t device_bytes() const { return bytes.bytes + offs.bytes + non_ascii.bytes; }
+};
+struct TextFieldHost {
+  std::vector<std::shared_ptr<TextSegStore>> per_seg;
+  DevBuf d_tsegs;  // slg::TextSegDev[n_segs] of the state this object belongs to
+};
+
 // One immutable state of the index (see "index updates" in searchlite_gpu.h).  Batches hold the state
 // they were prepared on; the index holds the current one.
 struct IndexState {
@@ -431,6 +443,7 @@ struct IndexState {
   std::vector<std::shared_ptr<TermStore>> terms;              // [n_segs]; null = the segment has no dictionary
   DevBuf d_term_segs;                                         // slg::ExpandSegDev[n_segs]
   DevBuf d_suggest_segs;                                      // slg::SuggestSegDev[n_segs]
+  std::map<int, std::shared_ptr<TextFieldHost>> text_fields;  // by id (ids are not reused); own objects, shared stores
   ~IndexState() {
     // kernels of already-destroyed batches, or rerank calls on the index stream, may still read the
     // tables: retiring a state is rare (one per update), so wait for the device once
@@ -466,6 +479,7 @@ struct slg_index {
   std::mutex update_mu;  // serialises slg_index_update_* / add_filter / add_vector_field (taken before mu)
   int next_sort_field = 0;  // (under update_mu) sort field ids are never handed out again
   int next_agg_field = 0;   // (under update_mu) the same for aggregation fields
+  int next_text_field = 0;  // (under update_mu) and for text fields
   // profiling of the scoring kernel
   bool profile = false;
   std::vector<std::pair<hipEvent_t, hipEvent_t>> prof_events;

@@ -289,6 +289,17 @@ void finish_state(slg_index *ix, IndexState &s) {
     if (s.terms[i]) ud[i] = slg::SuggestSegDev{td[i].bytes, td[i].offs, td[i].nchars, s.terms[i]->d_df.as<uint32_t>()};
   s.d_suggest_segs.alloc(std::max<size_t>(n_segs, 1) * sizeof(slg::SuggestSegDev), &ix->pool);
   if (n_segs) SLG_HIP(hipMemcpy(s.d_suggest_segs.p, ud.data(), n_segs * sizeof(slg::SuggestSegDev), hipMemcpyHostToDevice));
+  for (auto &tfp : s.text_fields) {  // (the field objects of a new state are fresh copies: see copy_state)
+    TextFieldHost &tf = *tfp.second;
+    tf.per_seg.resize(n_segs);
+    std::vector<slg::TextSegDev> tv(n_segs, slg::TextSegDev{nullptr, nullptr, nullptr, 0u, 0u});
+    for (size_t i = 0; i < n_segs; i++)
+      if (tf.per_seg[i])
+        tv[i] = slg::TextSegDev{tf.per_seg[i]->bytes.as<uint8_t>(), tf.per_seg[i]->offs.as<uint64_t>(),
+                                tf.per_seg[i]->non_ascii.as<uint32_t>(), tf.per_seg[i]->n_docs, 0u};
+    tf.d_tsegs.alloc(std::max<size_t>(n_segs, 1) * sizeof(slg::TextSegDev), &ix->pool);
+    if (n_segs) SLG_HIP(hipMemcpy(tf.d_tsegs.p, tv.data(), n_segs * sizeof(slg::TextSegDev), hipMemcpyHostToDevice));
+  }
   std::vector<uint32_t> base(n_segs + 1, 0u);
   uint64_t acc = 0;
   for (size_t i = 0; i < n_segs; i++) {
@@ -327,6 +338,11 @@ std::unique_ptr<IndexState> copy_state(const IndexState &cur) {
     c->metric = vf->metric;
     c->per_seg = vf->per_seg;
     n->vfields.push_back(std::move(c));
+  }
+  for (auto &tf : cur.text_fields) {  // the same for the text fields' d_tsegs
+    auto c = std::make_shared<TextFieldHost>();
+    c->per_seg = tf.second->per_seg;
+    n->text_fields.emplace(tf.first, std::move(c));
   }
   return n;
 }
@@ -384,6 +400,7 @@ void reshape_per_segment(IndexState &ns, Op op) {
   for (auto &vf : ns.vfields) op(vf->per_seg);  // (the field objects of a new state are fresh copies)
   op(ns.positions);  // (the state's own vector; the stores are shared)
   op(ns.terms);
+  for (auto &tf : ns.text_fields) op(tf.second->per_seg);  // (fresh copies too)
 }
 
 size_t state_device_bytes(const IndexState &s) {
@@ -393,6 +410,11 @@ size_t state_device_bytes(const IndexState &s) {
   n += s.d_term_segs.bytes + s.d_suggest_segs.bytes;
   for (auto &ts : s.terms)
     if (ts) n += ts->device_bytes();
+  for (auto &tf : s.text_fields) {
+    n += tf.second->d_tsegs.bytes;
+    for (auto &t : tf.second->per_seg)
+      if (t) n += t->device_bytes();
+  }
   for (auto &sh : s.segs) n += sh->device_bytes() + sh->store->device_bytes();
   for (auto &f : s.filters)
     if (f)
@@ -1119,6 +1141,64 @@ int slg_index_remove_agg_field(slg_index *ix, int agg_field_id) {
     update_state(ix, false, [&](const IndexState &cur, IndexState &ns) {
       SLG_REQUIRE(cur.agg_fields.count(agg_field_id) == 1, "unknown agg field id");
       ns.agg_fields.erase(agg_field_id);
+    });
+  });
+}
+
+// ---- text fields (slg_highlight_batch; index/highlight.rs, api/reader.rs:3400-3497) --------------
+int slg_index_add_text_field(slg_index *ix, const uint64_t *const *seg_offsets, const uint8_t *const *seg_bytes) {
+  int id = -1;
+  const int rc = guarded([&] {
+    SLG_REQUIRE(ix != nullptr, "index is NULL");
+    SLG_REQUIRE(seg_offsets != nullptr, "seg_offsets is NULL");
+    update_state(ix, false, [&](const IndexState &cur, IndexState &ns) {
+      const size_t n_segs = cur.segs.size();
+      auto tf = std::make_shared<TextFieldHost>();
+      tf->per_seg.resize(n_segs);
+      for (size_t s = 0; s < n_segs; s++) {
+        const uint64_t *offs = seg_offsets[s];
+        if (!offs) continue;  // the segment has no text in the field
+        const uint32_t n_docs = cur.segs[s]->n_docs;
+        const uint64_t first = offs[0], total = offs[n_docs] - offs[0];
+        for (uint32_t d = 0; d < n_docs; d++) {
+          SLG_REQUIRE(offs[d + 1] >= offs[d], "text field offsets of a segment decrease");
+          if (offs[d + 1] - offs[d] >= (1ull << 31)) throw SlgError(SLG_ERR_UNSUPPORTED, "a text of 2^31 bytes or more");
+        }
+        SLG_REQUIRE(total == 0 || (seg_bytes != nullptr && seg_bytes[s] != nullptr), "text field bytes of a segment are NULL");
+        const uint8_t *src = total ? seg_bytes[s] + first : nullptr;
+        std::vector<uint64_t> o((size_t)n_docs + 1);
+        std::vector<uint32_t> bits(((size_t)n_docs + 31) / 32 + 1, 0u);
+        for (uint32_t d = 0; d <= n_docs; d++) o[d] = offs[d] - first;
+        for (uint32_t d = 0; d < n_docs; d++)
+          for (uint64_t i = o[d]; i < o[d + 1]; i++)
+            if (src[i] >= 0x80u) {
+              bits[d >> 5] |= 1u << (d & 31u);
+              break;
+            }
+        auto store = std::make_shared<TextSegStore>();
+        store->n_docs = n_docs;
+        // padded: the 16-byte line that holds a doc's last byte lies inside the allocation (whose start is aligned)
+        store->bytes.alloc((size_t)total + 16, &ix->pool);
+        SLG_HIP(hipMemset(store->bytes.p, 0, (size_t)total + 16));
+        if (total) SLG_HIP(hipMemcpy(store->bytes.p, src, (size_t)total, hipMemcpyHostToDevice));
+        store->offs.alloc(o.size() * 8, &ix->pool);
+        SLG_HIP(hipMemcpy(store->offs.p, o.data(), o.size() * 8, hipMemcpyHostToDevice));
+        store->non_ascii.alloc(bits.size() * 4, &ix->pool);
+        SLG_HIP(hipMemcpy(store->non_ascii.p, bits.data(), bits.size() * 4, hipMemcpyHostToDevice));
+        tf->per_seg[s] = std::move(store);
+      }
+      id = ix->next_text_field++;
+      ns.text_fields.emplace(id, std::move(tf));
+    });
+  });
+  return rc == SLG_OK ? id : rc;
+}
+int slg_index_remove_text_field(slg_index *ix, int text_field_id) {
+  return guarded([&] {
+    SLG_REQUIRE(ix != nullptr, "index is NULL");
+    update_state(ix, false, [&](const IndexState &cur, IndexState &ns) {
+      SLG_REQUIRE(cur.text_fields.count(text_field_id) == 1, "unknown text field id");
+      ns.text_fields.erase(text_field_id);
     });
   });
 }

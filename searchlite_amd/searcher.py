@@ -212,6 +212,46 @@ class GpuIndex:
         N.check(self._lib.slg_suggest_phase_ms(self._h, C.addressof(a), C.addressof(b)))
         return a.value, b.value
 
+    def add_text_field(self, texts_per_segment) -> int:
+        """slg_index_add_text_field: texts_per_segment[s] = the stored text of every doc of segment s (str or bytes;
+        None or a value that is no string: an empty text), or None for a segment without the field -> the text
+        field id highlight specs name."""
+        assert len(texts_per_segment) == self.n_segs
+        offs_p = (C.c_void_p * max(self.n_segs, 1))()
+        bytes_p = (C.c_void_p * max(self.n_segs, 1))()
+        keep = []
+        for s, texts in enumerate(texts_per_segment):
+            if texts is None:
+                continue
+            assert len(texts) == self.segments[s].n_docs
+            raw = [t.encode("utf-8") if isinstance(t, str) else (bytes(t) if isinstance(t, (bytes, bytearray)) else b"")
+                   for t in texts]
+            offs = np.zeros(len(raw) + 1, dtype=np.uint64)
+            np.cumsum([len(r) for r in raw], out=offs[1:])
+            blob = np.frombuffer(b"".join(raw) + b"\0", dtype=np.uint8)  # (one spare byte: never an empty array)
+            keep += [offs, blob]
+            offs_p[s], bytes_p[s] = offs.ctypes.data, blob.ctypes.data
+        fid = self._lib.slg_index_add_text_field(self._h, offs_p, bytes_p)
+        if fid < 0:
+            raise N.SlgError(fid, N.last_error())
+        return fid
+
+    def remove_text_field(self, text_field: int) -> None:
+        N.check(self._lib.slg_index_remove_text_field(self._h, int(text_field)))
+
+    def highlight(self, hits, specs):
+        """slg_highlight_batch: hits[q] = [(seg, doc), ...], specs[q] = [highlight_spec() / snippet_spec() dicts] ->
+        result[q][hit][spec] = (status, [fragment bytes]) with the tags inserted (highlight.py)."""
+        from .highlight import highlight_hits
+        return highlight_hits(self._lib, self._h, hits, specs)
+
+    def highlight_phase_ms(self) -> Tuple[float, float]:
+        """Diagnostic only (tools/highlight_time.py): (count part, emit part) of this thread's last highlight call,
+        in ms (slg_highlight_phase_ms)."""
+        a, b = C.c_double(0), C.c_double(0)
+        N.check(self._lib.slg_highlight_phase_ms(self._h, C.addressof(a), C.addressof(b)))
+        return a.value, b.value
+
     def expanded_queries(self, queries: Sequence[str], default_field: str, fuzzy: Optional[dict] = None,
                          boost: float = 1.0):
         """The fuzzy expansion of a batch of query strings, folded into the arrays of a plain batch with plans.
@@ -1798,6 +1838,14 @@ class PreparedBatch:
         if want_stats:
             return out_doc, out_seg, out_score, out_count, stats
         return out_doc, out_seg, out_score, out_count
+
+    def highlight(self, specs):
+        """slg_batch_highlight: the batch's own device rows highlighted under specs[q] = [highlight_spec() dicts],
+        against the index state the batch was prepared on -> result[q][row][spec] = (status, [fragment bytes]) for
+        the rows in front of count[q] (highlight.py; the counts that shape the result come from fetch()).  The
+        batch must have run."""
+        from .highlight import highlight_batch
+        return highlight_batch(self._lib, self._h, self.fetch()[3], specs)
 
 
 class ScanBatch(PreparedBatch):

@@ -23,7 +23,7 @@ for src in *.hip; do
 done
 # the plain C++ units build_gpu links (searchlite_amd/build.py); slg_segfile.cpp and the *_capi.cpp files belong to
 # the host-only libraries
-for src in slg_plan.cpp slg_expand_merge.cpp slg_regex.cpp slg_suggest_host.cpp; do
+for src in slg_plan.cpp slg_expand_merge.cpp slg_regex.cpp slg_suggest_host.cpp slg_highlight_host.cpp; do
   [ -f "$src" ] || continue
   /opt/rocm/bin/hipcc $FLAGS -x c++ -c "$src" -o "${src%.cpp}_cpp.o" &
   OBJS="$OBJS ${src%.cpp}_cpp.o"

@@ -355,7 +355,8 @@ int slg_index_remove_filter(slg_index *index, int filter_id);
  *   FILTER_ID   filter_id: a registered filter of any kind.  Passes iff its reject bit is clear.  That bitmap
  *               already holds the tombstones, so NOT over this leaf passes deleted docs inside the tree; the
  *               final bitmap ORs the tombstones in again, so the result is right all the same.  This leaf is how
- *               Nested sub-filters, not-term filters and any host-made bitmap compose with the rest.
+ *               not-term filters and any host-made bitmap compose with the rest (Nested nodes are evaluated on the
+ *               device too: slg_index_add_nested_filter_trees below).
  *   AND / OR    arity children (0 and up): AND of none is true (passes_filters_at on an empty list), OR of none
  *               is false.  NOT: exactly one child.
  * A doc without a value fails every leaf over that column (NOT of the leaf then passes it); so does every doc of
@@ -393,6 +394,95 @@ typedef struct slg_filter_tree {
  * field or filter id; a field or filter without data for every segment; the wrong column kind; an ordinal out of
  * range), then SLG_ERR_UNSUPPORTED for the 2^53 rule.  Returns 0 or an error code. */
 int slg_index_add_filter_trees(slg_index *index, const slg_filter_tree *trees, uint32_t n_trees, int32_t *out_ids);
+/* ---- nested filters on the device (query/filters.rs:13-188; index/fastfields.rs:802-907) ----
+ * A Nested{path, filter} node (api/types.rs) matches a doc iff SOME object of the array of objects at `path`
+ * passes `filter` as a whole: its leaves read the values of that ONE object.  The device evaluates such trees over
+ * nested paths and nested value columns registered here, the arrays the fast-field file holds for them.
+ *
+ * A nested PATH (the reference's _nested_count:<path> and _nested_parent:<path> columns), per segment:
+ *   seg_counts[s][n_docs]            objects per doc; seg_counts == NULL or seg_counts[s] == NULL: no doc has one
+ *   seg_parent_offsets[s][n_docs+1]  CSR into seg_parents[s]: entry j of a doc is the index, within the same doc, of
+ *   seg_parents[s]                   the parent path's object that child object j belongs to; 0xFFFFFFFF: none.  A
+ *                                    list shorter than the doc's count leaves the rest unbound; NULL offsets (or a
+ *                                    NULL array of them): nothing binds.
+ * parent_path_id: the id of the path one level up (e.g. `comment` for `comment.reply`), or -1.  It is what a
+ * NESTED node inside an object scope is checked against; at the doc level no parent test is made, whatever the
+ * path.  The host builds the docs' first objects (the prefix sum of the counts) and the object -> doc table; a
+ * segment with more than 2^32 - 1 objects is SLG_ERR_UNSUPPORTED.  Returns the path id (>= 0; ids are never
+ * reused) or an error code.  Lifecycle as aggregation fields: slg_index_update_deleted keeps the tables,
+ * slg_index_remove_segment drops that segment's, slg_index_add_segment gives the new segment none (a tree naming
+ * the path is then SLG_ERR_INVALID, "nested path N has no tables for segment S", until it is registered again);
+ * batches prepared earlier keep their state.  Removing a path removes the nested fields registered under it; a
+ * path registered with it as parent stays, usable at the doc level. */
+int slg_index_add_nested_path(slg_index *index, int parent_path_id, const uint32_t *const *seg_counts,
+                              const uint32_t *const *seg_parent_offsets, const uint32_t *const *seg_parents);
+int slg_index_remove_nested_path(slg_index *index, int path_id);
+/* A nested VALUE column `<path>.<field>` (the reference's I64Nested / F64Nested / StrNested columns), per segment:
+ *   seg_doc_offsets[s][n_docs+1]     the doc's objects in seg_object_offsets[s]; NULL: the segment has no value
+ *   seg_object_offsets[s][objects+1] the object's values in seg_values[s]
+ * A doc may hold FEWER objects here than its path counts (the writer pads only up to the last object that had a
+ * value): an object beyond them has no value.  _i64 columns stay int64 on the device and are compared as
+ * integers: the +-2^53 rule of the doc-level RANGE_I64 does not apply to them.  _ord: ordinals into ONE caller-side
+ * dictionary of n_ords keys, as slg_index_add_agg_field_ord (an ordinal >= n_ords: SLG_ERR_INVALID).  Offsets that
+ * decrease, or a NULL array behind a non-empty range: SLG_ERR_INVALID.  Returns the nested field id (>= 0; ids are
+ * never reused) or an error code; lifecycle as the paths. */
+int slg_index_add_nested_field_f64(slg_index *index, int path_id, const uint32_t *const *seg_doc_offsets,
+                                   const uint32_t *const *seg_object_offsets, const double *const *seg_values);
+int slg_index_add_nested_field_i64(slg_index *index, int path_id, const uint32_t *const *seg_doc_offsets,
+                                   const uint32_t *const *seg_object_offsets, const int64_t *const *seg_values);
+int slg_index_add_nested_field_ord(slg_index *index, int path_id, const uint32_t *const *seg_doc_offsets,
+                                   const uint32_t *const *seg_object_offsets, const uint32_t *const *seg_ords,
+                                   uint32_t n_ords);
+int slg_index_remove_nested_field(slg_index *index, int nested_field_id);
+/* A nested filter tree is a list of SCOPES over one node array, children before parents; the last scope is the doc
+ * level (path -1), every other one an object scope (path: a nested path id).  A scope's nodes
+ * nodes[node_begin .. node_begin + n_nodes) are a postfix program as above.
+ *   doc level     the seven kinds above with their meaning (the 2^53 rule included), and
+ *                 NESTED  field: the index of an earlier scope of the tree.  Passes iff SOME object of that scope's
+ *                         path in the doc passes that scope's program; a doc without objects never passes (NOT of
+ *                         the leaf passes it).  No parent test is made, even for a path that has a parent.
+ *   object scope  KEYWORD_IN / RANGE_F64 / RANGE_I64  field: a NESTED FIELD id.  ANY value of the scope's object
+ *                         may satisfy the leaf; an object without a value fails it.  The kind must fit the column
+ *                         (SLG_ERR_INVALID otherwise); a field registered under ANOTHER path passes nothing (the
+ *                         reference finds no such column).  RANGE_I64 compares int64 with int64.
+ *                 AND / OR / NOT as above.
+ *                 NESTED  field: an earlier scope whose path's registered parent is THIS scope's path
+ *                         (SLG_ERR_INVALID otherwise).  Passes iff some object of that path in the doc passes its
+ *                         scope AND its entry of the parent list names this scope's object.
+ *                 FILTER_ID is SLG_ERR_INVALID here.
+ * Every scope but the last is named by exactly one NESTED node.  The Nested children of ONE And that share a path
+ * must hold for ONE object (passes_filters_at): the caller folds them into one scope whose program ANDs them; under
+ * Or and Not, and for a lone Nested, every node has a scope of its own. */
+#define SLG_FILTER_NESTED 7
+#define SLG_MAX_NESTED_SCOPES 16u  /* scopes of one tree, the doc level included */
+#define SLG_MAX_NESTED_DEPTH 4u    /* object scopes below one another */
+typedef struct slg_nested_scope {
+  int32_t path;         /* nested path id; -1: the doc level (the last scope, and only it) */
+  uint32_t node_begin;  /* into the tree's nodes */
+  uint32_t n_nodes;
+} slg_nested_scope;
+typedef struct slg_nested_filter_tree {
+  uint32_t n_scopes;
+  const slg_nested_scope *scopes;
+  uint32_t n_nodes;
+  const slg_filter_node *nodes;
+  uint32_t n_ords;
+  const uint32_t *ords;
+} slg_nested_filter_tree;
+/* Registers n_trees filters in ONE update of the index's state, all or nothing, ids as by
+ * slg_index_add_filter_trees; afterwards they are ordinary filters.  The trees are evaluated level by level, the
+ * deepest object scopes first: (nesting depth + 1) launches per segment, whatever the number of trees and scopes.
+ * Errors, in this order: SLG_ERR_INVALID before the index is looked at (NULL arrays; n_trees, n_scopes or a
+ * scope's n_nodes == 0; a scope's nodes beyond n_nodes; a last scope that is not the doc level or an earlier one
+ * that is; what slg_index_add_filter_trees refuses in a program; FILTER_ID in an object scope; a NESTED node that
+ * names no earlier scope; a scope named twice or never), then SLG_ERR_UNSUPPORTED (more than SLG_MAX_FILTER_NODES
+ * nodes over all scopes, a scope's stack deeper than SLG_MAX_FILTER_DEPTH, more than SLG_MAX_NESTED_SCOPES scopes,
+ * object scopes nested deeper than SLG_MAX_NESTED_DEPTH, more than SLG_MAX_FILTER_TREES trees), then against the
+ * index SLG_ERR_INVALID (an unknown path, nested field, agg field or filter id; one without data for every segment;
+ * the wrong column kind; an ordinal out of range; a NESTED node in an object scope whose path is not the child's
+ * registered parent), then SLG_ERR_UNSUPPORTED for the doc level's 2^53 rule.  Returns 0 or an error code. */
+int slg_index_add_nested_filter_trees(slg_index *index, const slg_nested_filter_tree *trees, uint32_t n_trees,
+                                      int32_t *out_ids);
 /* The PASS bits (~reject: the doc is alive and passes) of segment seg of any registered filter, whichever call
  * made it: ceil(n_docs / 8) bytes, bit d & 7 of byte d >> 3. */
 int slg_index_fetch_filter(slg_index *index, int filter_id, uint32_t seg, uint8_t *out_pass);

@@ -182,6 +182,13 @@ pub const SLG_SCAN_MOD_RECIPROCAL: i32 = 4;
 #[repr(C)] pub struct slg_filter_tree {
     pub n_nodes: u32, pub nodes: *const slg_filter_node, pub n_ords: u32, pub ords: *const u32,
 }
+#[repr(C)] pub struct slg_nested_scope {
+    pub path: i32, pub node_begin: u32, pub n_nodes: u32,
+}
+#[repr(C)] pub struct slg_nested_filter_tree {
+    pub n_scopes: u32, pub scopes: *const slg_nested_scope, pub n_nodes: u32, pub nodes: *const slg_filter_node,
+    pub n_ords: u32, pub ords: *const u32,
+}
 #[repr(C)] pub struct slg_phrase_spec {
     pub p_offsets: *const u32, pub p_kind: *const i32, pub p_slop: *const u32, pub v_offsets: *const u32,
     pub t_offsets: *const u32, pub t_term_ids: *const u32, pub q_min_should: *const u32,
@@ -565,6 +572,18 @@ extern "C" {
     pub fn slg_index_add_filter_trees(index: *mut slg_index, trees: *const slg_filter_tree, n_trees: u32,
         out_ids: *mut i32) -> c_int;
     pub fn slg_index_fetch_filter(index: *mut slg_index, filter_id: c_int, seg: u32, out_pass: *mut u8) -> c_int;
+    pub fn slg_index_add_nested_path(index: *mut slg_index, parent_path_id: c_int, seg_counts: *const *const u32,
+        seg_parent_offsets: *const *const u32, seg_parents: *const *const u32) -> c_int;
+    pub fn slg_index_remove_nested_path(index: *mut slg_index, path_id: c_int) -> c_int;
+    pub fn slg_index_add_nested_field_f64(index: *mut slg_index, path_id: c_int, seg_doc_offsets: *const *const u32,
+        seg_object_offsets: *const *const u32, seg_values: *const *const f64) -> c_int;
+    pub fn slg_index_add_nested_field_i64(index: *mut slg_index, path_id: c_int, seg_doc_offsets: *const *const u32,
+        seg_object_offsets: *const *const u32, seg_values: *const *const i64) -> c_int;
+    pub fn slg_index_add_nested_field_ord(index: *mut slg_index, path_id: c_int, seg_doc_offsets: *const *const u32,
+        seg_object_offsets: *const *const u32, seg_ords: *const *const u32, n_ords: u32) -> c_int;
+    pub fn slg_index_remove_nested_field(index: *mut slg_index, nested_field_id: c_int) -> c_int;
+    pub fn slg_index_add_nested_filter_trees(index: *mut slg_index, trees: *const slg_nested_filter_tree, n_trees: u32,
+        out_ids: *mut i32) -> c_int;
     // diagnostic only (the planner's champion table of a segment, [n_terms * 68]): not routed
     pub fn slg_index_fetch_champions(index: *const slg_index, seg: u32, out: *mut c_float) -> c_int;
     pub fn slg_batch_fscore_info(batch: *const slg_batch, out_variant: *mut u32, out_queries_with_work: *mut u32) -> c_int;
@@ -664,6 +683,9 @@ pub const SLG_FILTER_NOT: i32 = 6;
 pub const SLG_MAX_FILTER_NODES: u32 = 64;
 pub const SLG_MAX_FILTER_DEPTH: u32 = 16;
 pub const SLG_MAX_FILTER_TREES: u32 = 64;
+pub const SLG_FILTER_NESTED: i32 = 7;
+pub const SLG_MAX_NESTED_SCOPES: u32 = 16;
+pub const SLG_MAX_NESTED_DEPTH: u32 = 4;
 pub const SLG_RESCORE_TOTAL: i32 = 0;
 pub const SLG_RESCORE_MULTIPLY: i32 = 1;
 pub const SLG_RESCORE_SUM: i32 = 2;

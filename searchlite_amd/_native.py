@@ -87,6 +87,8 @@ SCAN_MATCH_ALL, SCAN_CONSTANT, SCAN_RANK_FEATURE = 0, 1, 2
 SCAN_MOD_NONE, SCAN_MOD_LOG, SCAN_MOD_LOG1P, SCAN_MOD_SQRT, SCAN_MOD_RECIPROCAL = 0, 1, 2, 3, 4
 FILTER_KEYWORD_IN, FILTER_RANGE_F64, FILTER_RANGE_I64, FILTER_ID, FILTER_AND, FILTER_OR, FILTER_NOT = 0, 1, 2, 3, 4, 5, 6
 MAX_FILTER_NODES, MAX_FILTER_DEPTH, MAX_FILTER_TREES = 64, 16, 64
+FILTER_NESTED = 7
+MAX_NESTED_SCOPES, MAX_NESTED_DEPTH = 16, 4
 MAX_COLLAPSE_ROWS = 4096
 MAX_INNER_HITS = 64
 EXPAND_FUZZY, EXPAND_PREFIX, EXPAND_WILDCARD = 0, 1, 2
@@ -294,6 +296,17 @@ class FilterNode(C.Structure):
 class FilterTree(C.Structure):
     """slg_filter_tree: the nodes of one tree and the ordinals its KEYWORD_IN nodes point into."""
     _fields_ = [("n_nodes", C.c_uint32), ("nodes", C.c_void_p), ("n_ords", C.c_uint32), ("ords", C.c_void_p)]
+
+
+class NestedScope(C.Structure):
+    """slg_nested_scope: one scope of a nested filter tree; path -1 is the doc level (the last scope)."""
+    _fields_ = [("path", C.c_int32), ("node_begin", C.c_uint32), ("n_nodes", C.c_uint32)]
+
+
+class NestedFilterTree(C.Structure):
+    """slg_nested_filter_tree: the scopes of one tree (children before parents), their nodes and the ordinals."""
+    _fields_ = [("n_scopes", C.c_uint32), ("scopes", C.c_void_p), ("n_nodes", C.c_uint32), ("nodes", C.c_void_p),
+                ("n_ords", C.c_uint32), ("ords", C.c_void_p)]
 
 
 class ExpandReq(C.Structure):
@@ -538,6 +551,13 @@ def load():
         "slg_search_batch_script": (i32, [vp, u32, vp, vp, vp, vp, vp, vp, vp, vp, i32, u32, i32, vp, vp, vp, vp, vp, vp]),
         "slg_index_add_filter_trees": (i32, [vp, vp, u32, vp]),
         "slg_index_fetch_filter": (i32, [vp, i32, u32, vp]),
+        "slg_index_add_nested_path": (i32, [vp, i32, vp, vp, vp]),
+        "slg_index_remove_nested_path": (i32, [vp, i32]),
+        "slg_index_add_nested_field_f64": (i32, [vp, i32, vp, vp, vp]),
+        "slg_index_add_nested_field_i64": (i32, [vp, i32, vp, vp, vp]),
+        "slg_index_add_nested_field_ord": (i32, [vp, i32, vp, vp, vp, u32]),
+        "slg_index_remove_nested_field": (i32, [vp, i32]),
+        "slg_index_add_nested_filter_trees": (i32, [vp, vp, u32, vp]),
         "slg_search_batch_fscore": (i32, [vp, u32, vp, vp, vp, vp, vp, vp, vp, u32, i32, vp, vp, vp, vp, vp, vp]),
         "slg_batch_prepare_scan": (vp, [vp, u32, vp, vp, vp, vp, u32]),
         "slg_batch_scan_info": (i32, [vp, vp, vp, vp]),

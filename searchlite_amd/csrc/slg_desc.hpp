@@ -370,6 +370,34 @@ constexpr uint32_t kFilterMaxNodes = 64, kFilterMaxDepth = 16, kFilterMaxTrees =
 constexpr uint32_t kFilterKeywordIn = 0, kFilterRangeF64 = 1, kFilterRangeI64 = 2, kFilterId = 3, kFilterAnd = 4,
                    kFilterOr = 5, kFilterNot = 6;
 
+// ---- nested filter trees (slg_index_add_nested_filter_trees; kernel: slg_nested.hpp, planner: slg_plan.cpp) ----
+// The image of one call grows the one above by scope rows and two tables.  A tree is a list of scopes: object
+// scopes (a postfix program evaluated per OBJECT of the scope's path) and, last, the doc-level scope.  The rows
+// are ordered by level: every tree's object scopes without a NESTED leaf first, then those one level up, ...,
+// then the doc-level scopes in tree order; a level is one launch per segment.  A NESTED leaf's `row` is the scope
+// row of its child; object scope r writes the pass bits of its objects to obj_bits[r * n_segs + seg].  In an
+// object scope a leaf's `row` is a row of the nested column table, RANGE_I64 keeps its bounds as int64 in the
+// bits of lo / hi, and a leaf that can pass nothing (a field of another path) is OR of nothing.
+struct NestedScopeDev {
+  uint32_t node_begin, n_nodes;
+  uint32_t path_row;  // the scope's row of the path table (doc level: unused)
+  uint32_t pad;
+};
+struct NestedPathDev {     // one registered path in one segment
+  const uint32_t *base;      // [n_docs + 1] first object of each doc (the prefix sum of the counts)
+  const uint32_t *obj_doc;   // [n_objects] the doc of each object
+  const uint32_t *par_offs;  // [n_docs + 1] into parents, or nullptr: no object binds to a parent
+  const uint32_t *parents;   // the parent object's index within the doc (0xFFFFFFFF: none)
+  uint32_t n_objects, pad;
+};
+struct NestedColDev {      // one registered nested value column in one segment
+  const uint32_t *doc_offs;  // [n_docs + 1] first object of each doc, or nullptr: the segment has no value
+  const uint32_t *obj_offs;  // [objects + 1] into vals (a doc may have fewer objects here than its path counts)
+  const void *vals;          // double[], int64_t[] or uint32_t[] (keyword ordinals)
+};
+constexpr uint32_t kFilterNested = 7;
+constexpr uint32_t kNestedMaxScopes = 16, kNestedMaxDepth = 4;  // = SLG_MAX_NESTED_*
+
 // ---- scan batches (slg_batch_prepare_scan; kernel: slg_scan.hpp, planner: slg_plan.cpp) --------------
 // A query without a scored term has no posting list: its candidates are the docs of every segment that pass the
 // bitmaps.  A (query, segment) pair is cut into slices of kScanSliceDocs consecutive docs — a multiple of 2048, so

@@ -391,6 +391,31 @@ struct AggFieldData {
   }
 };
 
+// a registered nested path (slg_index_add_nested_path): per segment the docs' first objects, the object -> doc
+// table and the parent lists on the device; null = the path predates the segment (slg_index_add_segment)
+struct NestedPathSeg {
+  DevBuf base, obj_doc;      // u32[n_docs + 1] | u32[n_objects]
+  DevBuf par_offs, parents;  // u32[n_docs + 1] | u32[]; both empty: nothing binds
+  uint32_t n_objects = 0;
+  size_t device_bytes() const { return base.bytes + obj_doc.bytes + par_offs.bytes + parents.bytes; }
+};
+struct NestedPathData {
+  int parent = -1;  // the path id one level up, or -1
+  std::vector<std::shared_ptr<NestedPathSeg>> per_seg;
+};
+// a registered nested value column (slg_index_add_nested_field_*): per segment its two offset arrays and the
+// values; null = the field predates the segment
+struct NestedColSeg {
+  DevBuf doc_offs, obj_offs, vals;  // doc_offs empty: the segment has no value (registered with NULL)
+  size_t device_bytes() const { return doc_offs.bytes + obj_offs.bytes + vals.bytes; }
+};
+struct NestedFieldData {
+  int path = 0;
+  int kind = 0;  // 1 f64, 2 i64, 3 keyword ordinals
+  uint32_t n_ords = 0;
+  std::vector<std::shared_ptr<NestedColSeg>> per_seg;
+};
+
 // the positions of a segment's postings (slg_index_set_positions): shared by the states that hold them
 struct PosStore {
   DevBuf offs;  // u32[P + 1] in the unpadded posting order
@@ -438,7 +463,9 @@ struct IndexState {
   DevBuf d_reject_table;                               // the same table on the device
   std::map<int, std::shared_ptr<SortFieldData>> sort_fields;  // by id (ids are not reused)
   std::map<int, std::shared_ptr<AggFieldData>> agg_fields;    // by id (ids are not reused)
-  std::vector<std::shared_ptr<PosStore>> positions;           // [n_segs]; null = the segment has none
+  std::map<int, std::shared_ptr<NestedPathData>> nested_paths;    // by id (ids are not reused)
+  std::map<int, std::shared_ptr<NestedFieldData>> nested_fields;  // by id (ids are not reused)
+  std::vector<std::shared_ptr<PosStore>> positions;          // [n_segs]; null = the segment has none
   DevBuf d_pos_segs;                                          // slg::PosSegDev[n_segs]
   std::vector<std::shared_ptr<TermStore>> terms;              // [n_segs]; null = the segment has no dictionary
   DevBuf d_term_segs;                                         // slg::ExpandSegDev[n_segs]
@@ -480,6 +507,7 @@ struct slg_index {
   int next_sort_field = 0;  // (under update_mu) sort field ids are never handed out again
   int next_agg_field = 0;   // (under update_mu) the same for aggregation fields
   int next_text_field = 0;  // (under update_mu) and for text fields
+  int next_nested_path = 0, next_nested_field = 0;  // (under update_mu) and for nested paths and nested fields
   // profiling of the scoring kernel
   bool profile = false;
   std::vector<std::pair<hipEvent_t, hipEvent_t>> prof_events;

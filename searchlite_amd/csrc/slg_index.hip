@@ -14,6 +14,7 @@
 #include <cstdlib>
 
 #include "slg_filter.hpp"
+#include "slg_nested.hpp"
 #include "slg_stage.hpp"
 
 slghost::LastError &slghost::last_error() {
@@ -330,6 +331,8 @@ std::unique_ptr<IndexState> copy_state(const IndexState &cur) {
   n->filters = cur.filters;
   n->sort_fields = cur.sort_fields;
   n->agg_fields = cur.agg_fields;
+  n->nested_paths = cur.nested_paths;
+  n->nested_fields = cur.nested_fields;
   n->positions = cur.positions;
   n->terms = cur.terms;
   for (auto &vf : cur.vfields) {  // the per-state table d_vsegs is rebuilt: own object, shared stores
@@ -397,6 +400,16 @@ void reshape_per_segment(IndexState &ns, Op op) {
     nf->refold();  // (a histogram's dense id range follows the minimum and maximum of the segments left)
     af.second = std::move(nf);
   }
+  for (auto &np : ns.nested_paths) {
+    auto nf = std::make_shared<NestedPathData>(*np.second);
+    op(nf->per_seg);
+    np.second = std::move(nf);
+  }
+  for (auto &nc : ns.nested_fields) {
+    auto nf = std::make_shared<NestedFieldData>(*nc.second);
+    op(nf->per_seg);
+    nc.second = std::move(nf);
+  }
   for (auto &vf : ns.vfields) op(vf->per_seg);  // (the field objects of a new state are fresh copies)
   op(ns.positions);  // (the state's own vector; the stores are shared)
   op(ns.terms);
@@ -430,6 +443,12 @@ size_t state_device_bytes(const IndexState &s) {
       if (r) n += r->bytes;
     if (af.second->dict) n += af.second->dict->vals.bytes;
   }
+  for (auto &np : s.nested_paths)
+    for (auto &c : np.second->per_seg)
+      if (c) n += c->device_bytes();
+  for (auto &nc : s.nested_fields)
+    for (auto &c : nc.second->per_seg)
+      if (c) n += c->device_bytes();
   for (auto &vf : s.vfields) {
     n += vf->d_vsegs.bytes;
     for (auto &v : vf->per_seg)
@@ -813,6 +832,294 @@ int slg_index_add_filter_trees(slg_index *ix, const slg_filter_tree *trees, uint
         p.n_docs = sh.n_docs;
         p.seg = (uint32_t)s;
         hipLaunchKernelGGL(slg::filter_tree_kernel, dim3((sh.n_docs + slg::kFilterThreads - 1) / slg::kFilterThreads, n_trees),
+                           dim3(slg::kFilterThreads), 0, st, p);
+        SLG_HIP(hipGetLastError());
+      }
+      SLG_HIP(hipStreamSynchronize(st));
+      // every filter takes the lowest free id, in the order of the trees (add_filter_impl's policy)
+      size_t slot = 0;
+      for (uint32_t t = 0; t < n_trees; t++) {
+        while (slot < ns.filters.size() && ns.filters[slot]) slot++;
+        if (slot == ns.filters.size()) ns.filters.emplace_back();
+        ns.filters[slot] = std::move(made[t]);
+        ids[t] = (int32_t)slot;
+      }
+    });
+    std::copy(ids.begin(), ids.end(), out_ids);
+  });
+}
+
+// ---- nested paths, nested value columns and the trees over them (slg_nested.hpp; planner: slg_plan.cpp) ----
+namespace {
+void stage_words(slg_index *ix, DevBuf &dst, const uint32_t *src, size_t n) {
+  dst.alloc(std::max<size_t>(n, 1) * 4, &ix->pool);
+  if (n) SLG_HIP(hipMemcpy(dst.p, src, n * 4, hipMemcpyHostToDevice));
+}
+// offs[0 .. n] must not decrease -> offs[n] - offs[0]
+size_t checked_span(const uint32_t *offs, size_t n, const char *what) {
+  for (size_t i = 0; i < n; i++) SLG_REQUIRE(offs[i + 1] >= offs[i], what);
+  return (size_t)offs[n] - offs[0];
+}
+void rebase(const uint32_t *offs, size_t n, std::vector<uint32_t> &o) {
+  o.resize(n + 1);
+  for (size_t i = 0; i <= n; i++) o[i] = offs[i] - offs[0];
+}
+
+// kind: 1 f64 values, 2 i64 values (kept as int64), 3 u32 ordinals
+int add_nested_field_impl(slg_index *ix, int kind, int path_id, const uint32_t *const *seg_doc_offsets,
+                          const uint32_t *const *seg_object_offsets, const void *const *seg_values, uint32_t n_ords) {
+  int id = -1;
+  const int rc = guarded([&] {
+    SLG_REQUIRE(ix != nullptr, "index is NULL");
+    SLG_REQUIRE(seg_doc_offsets != nullptr, "seg_doc_offsets is NULL");
+    update_state(ix, false, [&](const IndexState &cur, IndexState &ns) {
+      SLG_REQUIRE(cur.nested_paths.count(path_id) == 1, "unknown nested path id");
+      const size_t n_segs = cur.segs.size();
+      auto fd = std::make_shared<NestedFieldData>();
+      fd->path = path_id;
+      fd->kind = kind;
+      fd->n_ords = n_ords;
+      fd->per_seg.resize(n_segs);
+      const size_t width = kind == 3 ? 4 : 8;
+      for (size_t s = 0; s < n_segs; s++) {
+        const uint32_t n_docs = cur.segs[s]->n_docs;
+        auto col = std::make_shared<NestedColSeg>();
+        if (const uint32_t *doffs = seg_doc_offsets[s]) {
+          const size_t n_obj = checked_span(doffs, n_docs, "nested field doc offsets of a segment are not monotone");
+          SLG_REQUIRE(seg_object_offsets != nullptr && seg_object_offsets[s] != nullptr,
+                      "nested field object offsets of a segment are NULL");
+          const uint32_t *ooffs = seg_object_offsets[s] + doffs[0];
+          const size_t nv = checked_span(ooffs, n_obj, "nested field object offsets of a segment are not monotone");
+          SLG_REQUIRE(nv == 0 || (seg_values != nullptr && seg_values[s] != nullptr), "nested field values of a segment are NULL");
+          const unsigned char *v = nv ? static_cast<const unsigned char *>(seg_values[s]) + (size_t)ooffs[0] * width : nullptr;
+          if (kind == 3)
+            for (size_t i = 0; i < nv; i++)
+              SLG_REQUIRE(reinterpret_cast<const uint32_t *>(v)[i] < n_ords, "keyword ordinal >= n_ords");
+          std::vector<uint32_t> d, o;
+          rebase(doffs, n_docs, d);
+          rebase(ooffs, n_obj, o);
+          stage_words(ix, col->doc_offs, d.data(), d.size());
+          stage_words(ix, col->obj_offs, o.data(), o.size());
+          col->vals.alloc(std::max<size_t>(nv, 1) * width, &ix->pool);
+          if (nv) SLG_HIP(hipMemcpy(col->vals.p, v, nv * width, hipMemcpyHostToDevice));
+        }
+        fd->per_seg[s] = std::move(col);
+      }
+      id = ix->next_nested_field++;
+      ns.nested_fields.emplace(id, std::move(fd));
+    });
+  });
+  return rc == SLG_OK ? id : rc;
+}
+
+// what the planner sees of the state's nested paths and nested fields (fscore_field_views' counterpart)
+void nested_views(const IndexState &S, std::vector<slgplan::NestedPathView> &paths,
+                  std::vector<slgplan::NestedFieldView> &fields) {
+  for (const auto &kv : S.nested_paths) {
+    slgplan::NestedPathView v;
+    v.id = kv.first;
+    v.parent = kv.second->parent;
+    for (const auto &c : kv.second->per_seg) {
+      slg::NestedPathDev d{};
+      if (c) {
+        d.base = c->base.as<uint32_t>();
+        d.obj_doc = c->obj_doc.as<uint32_t>();
+        d.par_offs = c->par_offs.p ? c->par_offs.as<uint32_t>() : nullptr;
+        d.parents = c->parents.p ? c->parents.as<uint32_t>() : nullptr;
+        d.n_objects = c->n_objects;
+      }
+      v.per_seg.push_back(d);
+    }
+    paths.push_back(std::move(v));
+  }
+  for (const auto &kv : S.nested_fields) {
+    slgplan::NestedFieldView v;
+    v.id = kv.first;
+    v.path = kv.second->path;
+    v.kind = kv.second->kind;
+    v.n_ords = kv.second->n_ords;
+    for (const auto &c : kv.second->per_seg) {
+      slg::NestedColDev d{};
+      if (c && c->doc_offs.p) {
+        d.doc_offs = c->doc_offs.as<uint32_t>();
+        d.obj_offs = c->obj_offs.as<uint32_t>();
+        d.vals = c->vals.p;
+      }
+      v.per_seg.push_back(d);
+      v.has.push_back(c ? 1 : 0);
+    }
+    fields.push_back(std::move(v));
+  }
+}
+}  // namespace
+
+int slg_index_add_nested_path(slg_index *ix, int parent_path_id, const uint32_t *const *seg_counts,
+                              const uint32_t *const *seg_parent_offsets, const uint32_t *const *seg_parents) {
+  int id = -1;
+  const int rc = guarded([&] {
+    SLG_REQUIRE(ix != nullptr, "index is NULL");
+    SLG_REQUIRE(parent_path_id >= -1, "parent_path_id below -1");
+    update_state(ix, false, [&](const IndexState &cur, IndexState &ns) {
+      SLG_REQUIRE(parent_path_id == -1 || cur.nested_paths.count(parent_path_id) == 1, "unknown parent nested path id");
+      const size_t n_segs = cur.segs.size();
+      auto pd = std::make_shared<NestedPathData>();
+      pd->parent = parent_path_id;
+      pd->per_seg.resize(n_segs);
+      for (size_t s = 0; s < n_segs; s++) {
+        const uint32_t n_docs = cur.segs[s]->n_docs;
+        const uint32_t *counts = seg_counts ? seg_counts[s] : nullptr;
+        // the docs' first objects: the prefix sum of the counts (u32 on the device, as every offset of the file)
+        std::vector<uint32_t> base((size_t)n_docs + 1, 0u);
+        uint64_t total = 0;
+        for (uint32_t d = 0; d < n_docs; d++) {
+          base[d] = (uint32_t)total;
+          total += counts ? counts[d] : 0u;
+          if (total > 0xFFFFFFFFull)
+            throw SlgError(SLG_ERR_UNSUPPORTED, "a segment holds more than 2^32 - 1 objects of the nested path");
+        }
+        base[n_docs] = (uint32_t)total;
+        std::vector<uint32_t> obj_doc((size_t)total);
+        for (uint32_t d = 0; d < n_docs; d++) std::fill(obj_doc.begin() + base[d], obj_doc.begin() + base[d + 1], d);
+        auto seg = std::make_shared<NestedPathSeg>();
+        seg->n_objects = (uint32_t)total;
+        stage_words(ix, seg->base, base.data(), base.size());
+        stage_words(ix, seg->obj_doc, obj_doc.data(), obj_doc.size());
+        if (const uint32_t *poffs = seg_parent_offsets ? seg_parent_offsets[s] : nullptr) {
+          const size_t np = checked_span(poffs, n_docs, "nested parent offsets of a segment are not monotone");
+          SLG_REQUIRE(np == 0 || (seg_parents != nullptr && seg_parents[s] != nullptr), "nested parents of a segment are NULL");
+          std::vector<uint32_t> o;
+          rebase(poffs, n_docs, o);
+          stage_words(ix, seg->par_offs, o.data(), o.size());
+          stage_words(ix, seg->parents, np ? seg_parents[s] + poffs[0] : nullptr, np);
+        }
+        pd->per_seg[s] = std::move(seg);
+      }
+      id = ix->next_nested_path++;
+      ns.nested_paths.emplace(id, std::move(pd));
+    });
+  });
+  return rc == SLG_OK ? id : rc;
+}
+int slg_index_remove_nested_path(slg_index *ix, int path_id) {
+  return guarded([&] {
+    SLG_REQUIRE(ix != nullptr, "index is NULL");
+    update_state(ix, false, [&](const IndexState &cur, IndexState &ns) {
+      SLG_REQUIRE(cur.nested_paths.count(path_id) == 1, "unknown nested path id");
+      ns.nested_paths.erase(path_id);
+      for (auto it = ns.nested_fields.begin(); it != ns.nested_fields.end();)
+        it = it->second->path == path_id ? ns.nested_fields.erase(it) : std::next(it);
+    });
+  });
+}
+int slg_index_add_nested_field_f64(slg_index *ix, int path_id, const uint32_t *const *seg_doc_offsets,
+                                   const uint32_t *const *seg_object_offsets, const double *const *seg_values) {
+  return add_nested_field_impl(ix, 1, path_id, seg_doc_offsets, seg_object_offsets,
+                               reinterpret_cast<const void *const *>(seg_values), 0);
+}
+int slg_index_add_nested_field_i64(slg_index *ix, int path_id, const uint32_t *const *seg_doc_offsets,
+                                   const uint32_t *const *seg_object_offsets, const int64_t *const *seg_values) {
+  return add_nested_field_impl(ix, 2, path_id, seg_doc_offsets, seg_object_offsets,
+                               reinterpret_cast<const void *const *>(seg_values), 0);
+}
+int slg_index_add_nested_field_ord(slg_index *ix, int path_id, const uint32_t *const *seg_doc_offsets,
+                                   const uint32_t *const *seg_object_offsets, const uint32_t *const *seg_ords,
+                                   uint32_t n_ords) {
+  return add_nested_field_impl(ix, 3, path_id, seg_doc_offsets, seg_object_offsets,
+                               reinterpret_cast<const void *const *>(seg_ords), n_ords);
+}
+int slg_index_remove_nested_field(slg_index *ix, int nested_field_id) {
+  return guarded([&] {
+    SLG_REQUIRE(ix != nullptr, "index is NULL");
+    update_state(ix, false, [&](const IndexState &cur, IndexState &ns) {
+      SLG_REQUIRE(cur.nested_fields.count(nested_field_id) == 1, "unknown nested field id");
+      ns.nested_fields.erase(nested_field_id);
+    });
+  });
+}
+
+int slg_index_add_nested_filter_trees(slg_index *ix, const slg_nested_filter_tree *trees, uint32_t n_trees,
+                                      int32_t *out_ids) {
+  return guarded([&] {
+    slgplan::check_nested_filter_trees(trees, n_trees);  // (host only, before the index is looked at)
+    SLG_REQUIRE(out_ids != nullptr, "out_ids is NULL");
+    SLG_REQUIRE(ix != nullptr, "index is NULL");
+    std::vector<int32_t> ids(n_trees, -1);  // (handed out only once the state is published: all or nothing)
+    update_state(ix, false, [&](const IndexState &cur, IndexState &ns) {
+      hipStream_t st = ix->stream;
+      const size_t n_segs = cur.segs.size();
+      std::vector<char> live(cur.filters.size());
+      for (size_t f = 0; f < live.size(); f++) live[f] = cur.filter_usable(f) ? 1 : 0;
+      std::vector<slgplan::NestedPathView> paths;
+      std::vector<slgplan::NestedFieldView> nfields;
+      nested_views(cur, paths, nfields);
+      slgplan::NestedFilterPlan np;
+      slgplan::plan_nested_filter_trees(fscore_field_views(cur), cur.reject_host.data(), live.data(), live.size(), paths,
+                                        nfields, (uint32_t)n_segs, trees, n_trees, np);
+      // the new filters' bitmaps, and the object scopes' transient ones (pooled: back on return, the stream is
+      // synchronised below); their addresses are two tables of the image
+      std::vector<std::shared_ptr<FilterData>> made(n_trees);
+      std::vector<uint32_t *> outs((size_t)n_trees * n_segs);
+      for (uint32_t t = 0; t < n_trees; t++) {
+        made[t] = std::make_shared<FilterData>();
+        made[t]->per_seg.resize(n_segs);
+        for (size_t s = 0; s < n_segs; s++) {
+          const size_t words = ((size_t)cur.segs[s]->n_docs + 31) / 32;
+          made[t]->per_seg[s] = std::make_shared<DevBuf>();
+          made[t]->per_seg[s]->alloc((words ? words : 1) * 4, &ix->pool);
+          outs[(size_t)t * n_segs + s] = made[t]->per_seg[s]->as<uint32_t>();
+        }
+      }
+      const uint32_t n_obj_scopes = np.level_begin.back();
+      const auto n_objects = [&](uint32_t row, size_t s) { return np.paths[(size_t)np.scopes[row].path_row * n_segs + s].n_objects; };
+      std::vector<DevBuf> bits((size_t)n_obj_scopes * n_segs);
+      std::vector<uint32_t *> obj_bits(bits.size());
+      for (uint32_t r = 0; r < n_obj_scopes; r++)
+        for (size_t s = 0; s < n_segs; s++) {
+          DevBuf &b = bits[(size_t)r * n_segs + s];
+          b.alloc_pooled(&ix->pool, std::max<size_t>(((size_t)n_objects(r, s) + 31) / 32, 1) * 4);
+          obj_bits[(size_t)r * n_segs + s] = b.as<uint32_t>();
+        }
+      DevBuf image;
+      upload_image(image, &ix->pool, {image_part(np.scopes), image_part(np.nodes), image_part(np.cols),
+                                      image_part(np.filters), image_part(np.paths), image_part(np.ncols),
+                                      image_part(obj_bits), image_part(outs), image_part(np.words)});
+      slg::NestedFilterParams p{};
+      unsigned char *base = image.as<unsigned char>();
+      const auto take = [&base](auto *&dst, size_t bytes) {
+        dst = reinterpret_cast<std::remove_reference_t<decltype(dst)>>(base);
+        base += bytes;
+      };
+      take(p.scopes, np.scopes.size() * sizeof(slg::NestedScopeDev));
+      take(p.nodes, np.nodes.size() * sizeof(slg::FilterNodeDev));
+      take(p.cols, np.cols.size() * sizeof(slg::ColumnDev));
+      take(p.filters, np.filters.size() * sizeof(void *));
+      take(p.paths, np.paths.size() * sizeof(slg::NestedPathDev));
+      take(p.ncols, np.ncols.size() * sizeof(slg::NestedColDev));
+      take(p.obj_bits, obj_bits.size() * sizeof(void *));
+      take(p.out, outs.size() * sizeof(void *));
+      take(p.words, np.words.size() * 4);
+      p.n_segs = (uint32_t)n_segs;
+      // level by level, the deepest object scopes first: (levels + 1) launches per segment, a level's scopes of
+      // every tree on blockIdx.y
+      for (size_t s = 0; s < n_segs; s++) {
+        const SegHost &sh = *cur.segs[s];
+        if (sh.n_docs == 0) continue;
+        p.deleted = sh.d_deleted.as<uint32_t>();
+        p.n_docs = sh.n_docs;
+        p.seg = (uint32_t)s;
+        for (size_t l = 0; l + 1 < np.level_begin.size(); l++) {
+          p.first_scope = np.level_begin[l];
+          const uint32_t n_scopes = np.level_begin[l + 1] - p.first_scope;
+          uint32_t most = 0;
+          for (uint32_t r = 0; r < n_scopes; r++) most = std::max(most, n_objects(p.first_scope + r, s));
+          if (most == 0) continue;  // (no object: the bitmaps of this level are never read in this segment)
+          hipLaunchKernelGGL(slg::nested_filter_kernel<false>,
+                             dim3((uint32_t)(((uint64_t)most + slg::kFilterThreads - 1) / slg::kFilterThreads), n_scopes),
+                             dim3(slg::kFilterThreads), 0, st, p);
+          SLG_HIP(hipGetLastError());
+        }
+        p.first_scope = n_obj_scopes;
+        hipLaunchKernelGGL(slg::nested_filter_kernel<true>, dim3((sh.n_docs + slg::kFilterThreads - 1) / slg::kFilterThreads, n_trees),
                            dim3(slg::kFilterThreads), 0, st, p);
         SLG_HIP(hipGetLastError());
       }

@@ -1823,6 +1823,116 @@ static_assert(slg::kFilterKeywordIn == SLG_FILTER_KEYWORD_IN && slg::kFilterRang
                   slg::kFilterNot == SLG_FILTER_NOT, "header kinds");
 static_assert(sizeof(slg::FilterTreeDev) == 8 && sizeof(slg::FilterNodeDev) == 32, "records the kernel reads in whole words");
 
+static_assert(slg::kFilterNested == SLG_FILTER_NESTED && slg::kNestedMaxScopes == SLG_MAX_NESTED_SCOPES &&
+                  slg::kNestedMaxDepth == SLG_MAX_NESTED_DEPTH, "the nested kind and limits");
+static_assert(sizeof(slg::NestedScopeDev) == 16 && sizeof(slg::NestedPathDev) == 40 && sizeof(slg::NestedColDev) == 24,
+              "records the kernel reads in whole words");
+
+namespace {
+// The checks of one postfix program that need no index, shared by the flat trees and every scope of a nested tree
+// -> the deepest evaluation stack.  nested(n, at): what a NESTED node has to satisfy; without it the kind is unknown
+// here.  object_scope: FILTER_ID is refused.  node 0 of the program is node `first` of its tree
+template <typename Nested>
+uint64_t check_program(const slg_filter_node *nodes, uint32_t first, uint32_t n_nodes, uint32_t n_ords, bool object_scope,
+                       const std::string &in_t, const Nested *nested) {
+  uint64_t depth = 0, deepest = 0;  // the evaluation stack of the postfix program
+  for (uint32_t i = 0; i < n_nodes; i++) {
+    const slg_filter_node &n = nodes[i];
+    const std::string at = " (node " + std::to_string(first + i) + ")" + in_t;
+    PLAN_REQUIRE(n.kind >= SLG_FILTER_KEYWORD_IN && n.kind <= (nested ? SLG_FILTER_NESTED : SLG_FILTER_NOT),
+                 "unknown filter node kind" + at);
+    if (n.kind == SLG_FILTER_NOT) {
+      PLAN_REQUIRE(depth >= 1u, "NOT underflows the stack" + at);
+    } else if (n.kind == SLG_FILTER_AND || n.kind == SLG_FILTER_OR) {
+      PLAN_REQUIRE((uint64_t)n.arity <= depth, "arity larger than the stack" + at);
+      depth = depth - n.arity + 1u;
+    } else {
+      if (n.kind == SLG_FILTER_RANGE_F64)
+        PLAN_REQUIRE(!std::isnan(n.lo_f) && !std::isnan(n.hi_f), "NaN bound" + at);
+      if (n.kind == SLG_FILTER_KEYWORD_IN)
+        PLAN_REQUIRE((uint64_t)n.ord_begin + n.n_ords_in <= n_ords, "ord_begin + n_ords_in > n_ords" + at);
+      if (n.kind == SLG_FILTER_ID) PLAN_REQUIRE(!object_scope, "FILTER_ID in an object scope" + at);
+      if (n.kind == SLG_FILTER_NESTED) (*nested)(n, at);
+      depth++;
+    }
+    deepest = std::max(deepest, depth);
+  }
+  PLAN_REQUIRE(depth == 1u, "the program does not end with exactly one value" + in_t);
+  return deepest;
+}
+using NoNested = void (*)(const slg_filter_node &, const std::string &);
+
+// the ordinal bit set of a KEYWORD_IN node over a dictionary of n_ords keys, appended to words -> its first word
+uint32_t ord_bit_set(std::vector<uint32_t> &words, const slg_filter_node &n, const uint32_t *ords, uint32_t n_ords,
+                     const std::string &what, const std::string &in_t) {
+  const uint32_t bits = (uint32_t)words.size();
+  words.resize(words.size() + ((size_t)n_ords + 31u) / 32u, 0u);
+  for (uint32_t j = 0; j < n.n_ords_in; j++) {
+    const uint32_t o = ords[n.ord_begin + j];
+    PLAN_REQUIRE(o < n_ords, "ordinal " + std::to_string(o) + " >= n_ords of " + what + in_t);
+    words[bits + (o >> 5)] |= 1u << (o & 31u);
+  }
+  return bits;
+}
+
+// The doc-level nodes of filter trees against an index state's agg fields and filters: the leaf validation, the
+// i64 clamping and the two row tables that the flat trees and the doc level of nested trees share
+struct DocLevelNodes {
+  const std::vector<FscoreFieldView> &fields;
+  const char *filter_live;
+  size_t n_filters;
+  uint32_t n_segs;
+  std::vector<uint32_t> &words;
+  std::vector<int32_t> used_fields, used_filters;  // the rows of the two tables, in order of first use
+  std::string unsupported;                         // (reported behind every invalid argument)
+
+  slg::FilterNodeDev node(const slg_filter_node &n, const uint32_t *ords, const std::string &in_t) {
+    constexpr double k2p53 = 9007199254740992.0;
+    constexpr int64_t i2p53 = (int64_t)1 << 53;
+    slg::FilterNodeDev nd{};
+    nd.kind = (uint32_t)n.kind;
+    if (n.kind == SLG_FILTER_AND || n.kind == SLG_FILTER_OR) {
+      nd.arity = n.arity;
+    } else if (n.kind == SLG_FILTER_ID) {
+      const int32_t f = n.filter_id;
+      PLAN_REQUIRE(f >= 0 && (size_t)f < n_filters && filter_live[f],
+                   "unknown filter id " + std::to_string(f) + " (or one without a bitmap for every segment)" + in_t);
+      nd.row = row_of(used_filters, f);
+    } else if (n.kind != SLG_FILTER_NOT) {
+      const int32_t id = n.field;
+      const FscoreFieldView &fv = agg_field(fields, id, "", in_t);
+      agg_field_rows(fv, n_segs, "", in_t);
+      nd.row = row_of(used_fields, id);
+      if (n.kind == SLG_FILTER_KEYWORD_IN) {
+        PLAN_REQUIRE(fv.keyword, "agg field " + std::to_string(id) + " is not a keyword field" + in_t);
+        nd.bits = ord_bit_set(words, n, ords, fv.n_ords, "agg field " + std::to_string(id), in_t);
+      } else {
+        PLAN_REQUIRE(!fv.keyword, "agg field " + std::to_string(id) + " is a keyword field" + in_t);
+        if (n.kind == SLG_FILTER_RANGE_F64) {
+          nd.lo = n.lo_f;
+          nd.hi = n.hi_f;
+        } else {
+          PLAN_REQUIRE(fv.from_i64, "agg field " + std::to_string(id) + " was not registered from i64 values" + in_t);
+          if (unsupported.empty() && (fv.i64_rounded || (fv.any_value && (fv.vmin < -k2p53 || fv.vmax > k2p53))))
+            unsupported = "agg field " + std::to_string(id) + " holds an i64 value beyond +-2^53 (CPU path)" + in_t;
+          // every stored value is an integer within +-2^53: a bound on the far side of it selects what the
+          // clamped one does; a lower bound above 2^53 (an upper one below -2^53) selects nothing, which the
+          // clamped bound would not say of a value of exactly +-2^53, so it becomes the infinity
+          nd.lo = n.lo_i > i2p53 ? HUGE_VAL : (double)std::max<int64_t>(n.lo_i, -i2p53);
+          nd.hi = n.hi_i < -i2p53 ? -HUGE_VAL : (double)std::min<int64_t>(n.hi_i, i2p53);
+        }
+      }
+    }
+    return nd;
+  }
+  // behind every node: the pending SLG_ERR_UNSUPPORTED, else the two tables
+  void finish(const uint32_t *const *reject, std::vector<slg::ColumnDev> &cols, std::vector<const uint32_t *> &filters) {
+    if (!unsupported.empty()) throw SlgError(SLG_ERR_UNSUPPORTED, unsupported);
+    fill_tables(fields, used_fields, reject, used_filters, n_segs, cols, filters);
+  }
+};
+}  // namespace
+
 void check_filter_trees(const slg_filter_tree *trees, uint32_t n_trees) {
   PLAN_REQUIRE(trees != nullptr, "filter trees is NULL");
   PLAN_REQUIRE(n_trees != 0u, "n_trees is 0");
@@ -1833,26 +1943,7 @@ void check_filter_trees(const slg_filter_tree *trees, uint32_t n_trees) {
     PLAN_REQUIRE(tr.n_nodes != 0u, "n_nodes is 0" + in_t);
     PLAN_REQUIRE(tr.nodes != nullptr, "nodes is NULL" + in_t);
     PLAN_REQUIRE(tr.n_ords == 0u || tr.ords != nullptr, "ords is NULL" + in_t);
-    uint64_t depth = 0, deepest = 0;  // the evaluation stack of the postfix program
-    for (uint32_t i = 0; i < tr.n_nodes; i++) {
-      const slg_filter_node &n = tr.nodes[i];
-      const std::string at = " (node " + std::to_string(i) + ")" + in_t;
-      PLAN_REQUIRE(n.kind >= SLG_FILTER_KEYWORD_IN && n.kind <= SLG_FILTER_NOT, "unknown filter node kind" + at);
-      if (n.kind == SLG_FILTER_NOT) {
-        PLAN_REQUIRE(depth >= 1u, "NOT underflows the stack" + at);
-      } else if (n.kind == SLG_FILTER_AND || n.kind == SLG_FILTER_OR) {
-        PLAN_REQUIRE((uint64_t)n.arity <= depth, "arity larger than the stack" + at);
-        depth = depth - n.arity + 1u;
-      } else {
-        if (n.kind == SLG_FILTER_RANGE_F64)
-          PLAN_REQUIRE(!std::isnan(n.lo_f) && !std::isnan(n.hi_f), "NaN bound" + at);
-        if (n.kind == SLG_FILTER_KEYWORD_IN)
-          PLAN_REQUIRE((uint64_t)n.ord_begin + n.n_ords_in <= tr.n_ords, "ord_begin + n_ords_in > n_ords" + at);
-        depth++;
-      }
-      deepest = std::max(deepest, depth);
-    }
-    PLAN_REQUIRE(depth == 1u, "the program does not end with exactly one value" + in_t);
+    const uint64_t deepest = check_program<NoNested>(tr.nodes, 0u, tr.n_nodes, tr.n_ords, false, in_t, nullptr);
     if (unsupported.empty() && tr.n_nodes > SLG_MAX_FILTER_NODES)
       unsupported = "more than SLG_MAX_FILTER_NODES nodes" + in_t;
     if (unsupported.empty() && deepest > SLG_MAX_FILTER_DEPTH)
@@ -1867,62 +1958,203 @@ void plan_filter_trees(const std::vector<FscoreFieldView> &fields, const uint32_
                        uint32_t n_trees, FilterTreePlan &out) {
   out = FilterTreePlan{};
   out.trees.reserve(n_trees);
-  std::vector<int32_t> used_fields, used_filters;  // the rows of the two tables, in order of first use
-  std::string unsupported;                         // (reported behind every invalid argument)
-  constexpr double k2p53 = 9007199254740992.0;
-  constexpr int64_t i2p53 = (int64_t)1 << 53;
+  DocLevelNodes doc{fields, filter_live, n_filters, n_segs, out.words, {}, {}, {}};
   for (uint32_t t = 0; t < n_trees; t++) {
     const slg_filter_tree &tr = trees[t];
     const std::string in_t = " in filter tree " + std::to_string(t);
     out.trees.push_back(slg::FilterTreeDev{(uint32_t)out.nodes.size(), tr.n_nodes});
-    for (uint32_t i = 0; i < tr.n_nodes; i++) {
-      const slg_filter_node &n = tr.nodes[i];
-      slg::FilterNodeDev nd{};
-      nd.kind = (uint32_t)n.kind;
-      if (n.kind == SLG_FILTER_AND || n.kind == SLG_FILTER_OR) {
-        nd.arity = n.arity;
-      } else if (n.kind == SLG_FILTER_ID) {
-        const int32_t f = n.filter_id;
-        PLAN_REQUIRE(f >= 0 && (size_t)f < n_filters && filter_live[f],
-                     "unknown filter id " + std::to_string(f) + " (or one without a bitmap for every segment)" + in_t);
-        nd.row = row_of(used_filters, f);
-      } else if (n.kind != SLG_FILTER_NOT) {
-        const int32_t id = n.field;
-        const FscoreFieldView &fv = agg_field(fields, id, "", in_t);
-        agg_field_rows(fv, n_segs, "", in_t);
-        nd.row = row_of(used_fields, id);
-        if (n.kind == SLG_FILTER_KEYWORD_IN) {
-          PLAN_REQUIRE(fv.keyword, "agg field " + std::to_string(id) + " is not a keyword field" + in_t);
-          nd.bits = (uint32_t)out.words.size();
-          out.words.resize(out.words.size() + ((size_t)fv.n_ords + 31u) / 32u, 0u);
-          for (uint32_t j = 0; j < n.n_ords_in; j++) {
-            const uint32_t o = tr.ords[n.ord_begin + j];
-            PLAN_REQUIRE(o < fv.n_ords, "ordinal " + std::to_string(o) + " >= n_ords of agg field " +
-                                             std::to_string(id) + in_t);
-            out.words[nd.bits + (o >> 5)] |= 1u << (o & 31u);
-          }
+    for (uint32_t i = 0; i < tr.n_nodes; i++) out.nodes.push_back(doc.node(tr.nodes[i], tr.ords, in_t));
+  }
+  doc.finish(reject, out.cols, out.filters);
+}
+
+// ---- nested filter trees -------------------------------------------------------------------------------
+namespace {
+// the level of every scope of a checked tree: an object scope without a NESTED leaf is level 1, one with such
+// leaves lies one above its highest child; the doc-level scope's entry is the tree's nesting depth
+std::vector<uint32_t> scope_levels(const slg_nested_filter_tree &tr) {
+  std::vector<uint32_t> level(tr.n_scopes, 0u);
+  for (uint32_t s = 0; s < tr.n_scopes; s++) {
+    const slg_nested_scope &sc = tr.scopes[s];
+    uint32_t below = 0;
+    for (uint32_t i = 0; i < sc.n_nodes; i++) {
+      const slg_filter_node &n = tr.nodes[sc.node_begin + i];
+      if (n.kind == SLG_FILTER_NESTED) below = std::max(below, level[n.field]);
+    }
+    level[s] = s + 1u == tr.n_scopes ? below : below + 1u;
+  }
+  return level;
+}
+}  // namespace
+
+void check_nested_filter_trees(const slg_nested_filter_tree *trees, uint32_t n_trees) {
+  PLAN_REQUIRE(trees != nullptr, "nested filter trees is NULL");
+  PLAN_REQUIRE(n_trees != 0u, "n_trees is 0");
+  std::string unsupported;  // (reported behind every invalid argument)
+  for (uint32_t t = 0; t < n_trees; t++) {
+    const slg_nested_filter_tree &tr = trees[t];
+    const std::string in_t = " in nested filter tree " + std::to_string(t);
+    PLAN_REQUIRE(tr.n_scopes != 0u, "n_scopes is 0" + in_t);
+    PLAN_REQUIRE(tr.scopes != nullptr, "scopes is NULL" + in_t);
+    PLAN_REQUIRE(tr.n_nodes != 0u, "n_nodes is 0" + in_t);
+    PLAN_REQUIRE(tr.nodes != nullptr, "nodes is NULL" + in_t);
+    PLAN_REQUIRE(tr.n_ords == 0u || tr.ords != nullptr, "ords is NULL" + in_t);
+    std::vector<uint32_t> named(tr.n_scopes, 0u);  // how many NESTED nodes name each scope
+    uint64_t deepest = 0, total = 0;
+    for (uint32_t s = 0; s < tr.n_scopes; s++) {
+      const slg_nested_scope &sc = tr.scopes[s];
+      const std::string in_s = " (scope " + std::to_string(s) + ")" + in_t;
+      const bool doc_level = s + 1u == tr.n_scopes;
+      PLAN_REQUIRE(sc.path >= -1, "path below -1" + in_s);
+      PLAN_REQUIRE(doc_level == (sc.path == -1),
+                   (doc_level ? "the last scope is not the doc level" : "a scope before the last one is the doc level") + in_s);
+      PLAN_REQUIRE(sc.n_nodes != 0u, "the scope's n_nodes is 0" + in_s);
+      PLAN_REQUIRE((uint64_t)sc.node_begin + sc.n_nodes <= tr.n_nodes, "node_begin + n_nodes > the tree's n_nodes" + in_s);
+      const auto nested = [&](const slg_filter_node &n, const std::string &at) {
+        PLAN_REQUIRE(n.field >= 0 && (uint32_t)n.field < s, "a NESTED node names no earlier scope" + at);
+        named[n.field]++;
+      };
+      deepest = std::max(deepest, check_program(tr.nodes + sc.node_begin, sc.node_begin, sc.n_nodes, tr.n_ords,
+                                                !doc_level, in_s, &nested));
+      total += sc.n_nodes;
+    }
+    for (uint32_t s = 0; s + 1u < tr.n_scopes; s++)
+      PLAN_REQUIRE(named[s] == 1u, std::string(named[s] ? "a scope is named by more than one NESTED node" :
+                                                          "a scope is named by no NESTED node") +
+                                       " (scope " + std::to_string(s) + ")" + in_t);
+    if (unsupported.empty() && total > SLG_MAX_FILTER_NODES)
+      unsupported = "more than SLG_MAX_FILTER_NODES nodes over all scopes" + in_t;
+    if (unsupported.empty() && deepest > SLG_MAX_FILTER_DEPTH)
+      unsupported = "evaluation stack deeper than SLG_MAX_FILTER_DEPTH" + in_t;
+    if (unsupported.empty() && tr.n_scopes > SLG_MAX_NESTED_SCOPES)
+      unsupported = "more than SLG_MAX_NESTED_SCOPES scopes" + in_t;
+    if (unsupported.empty() && scope_levels(tr).back() > SLG_MAX_NESTED_DEPTH)
+      unsupported = "object scopes nested deeper than SLG_MAX_NESTED_DEPTH" + in_t;
+  }
+  if (unsupported.empty() && n_trees > SLG_MAX_FILTER_TREES) unsupported = "more than SLG_MAX_FILTER_TREES trees in one call";
+  if (!unsupported.empty()) throw SlgError(SLG_ERR_UNSUPPORTED, unsupported);
+}
+
+void plan_nested_filter_trees(const std::vector<FscoreFieldView> &fields, const uint32_t *const *reject,
+                              const char *filter_live, size_t n_filters, const std::vector<NestedPathView> &paths,
+                              const std::vector<NestedFieldView> &nested_fields, uint32_t n_segs,
+                              const slg_nested_filter_tree *trees, uint32_t n_trees, NestedFilterPlan &out) {
+  out = NestedFilterPlan{};
+  DocLevelNodes doc{fields, filter_live, n_filters, n_segs, out.words, {}, {}, {}};
+  std::vector<int32_t> used_paths, used_ncols;  // the rows of the two nested tables, in order of first use
+  const auto path_of = [&](int32_t id, const std::string &in_s) -> const NestedPathView & {
+    const auto it = std::find_if(paths.begin(), paths.end(), [id](const NestedPathView &v) { return v.id == id; });
+    PLAN_REQUIRE(it != paths.end(), "unknown nested path id " + std::to_string(id) + in_s);
+    for (uint32_t s = 0; s < n_segs; s++)
+      PLAN_REQUIRE(s < it->per_seg.size() && it->per_seg[s].base != nullptr,
+                   "nested path " + std::to_string(id) + " has no tables for segment " + std::to_string(s) +
+                       " (added after the path was registered)" + in_s);
+    return *it;
+  };
+  // pass 1, in the caller's order (so that the first error is the first in the trees): every scope's nodes, a
+  // NESTED node's row still the child's index in its own tree
+  struct Scope {
+    uint32_t tree, index, level, path_row;
+    std::vector<slg::FilterNodeDev> nodes;
+  };
+  std::vector<Scope> all;
+  std::vector<uint32_t> tree_first(n_trees);
+  uint32_t levels = 0;
+  for (uint32_t t = 0; t < n_trees; t++) {
+    const slg_nested_filter_tree &tr = trees[t];
+    const std::string in_t = " in nested filter tree " + std::to_string(t);
+    const std::vector<uint32_t> level = scope_levels(tr);
+    levels = std::max(levels, level.back());
+    tree_first[t] = (uint32_t)all.size();
+    for (uint32_t s = 0; s < tr.n_scopes; s++) {
+      const slg_nested_scope &sc = tr.scopes[s];
+      const std::string in_s = " (scope " + std::to_string(s) + ")" + in_t;
+      Scope scope{t, s, level[s], 0u, {}};
+      const bool doc_level = sc.path < 0;
+      const NestedPathView *own = doc_level ? nullptr : &path_of(sc.path, in_s);
+      if (own) scope.path_row = row_of(used_paths, sc.path);
+      for (uint32_t i = 0; i < sc.n_nodes; i++) {
+        const slg_filter_node &n = tr.nodes[sc.node_begin + i];
+        if (n.kind == SLG_FILTER_NESTED) {
+          const int32_t child = tr.scopes[n.field].path;
+          const NestedPathView &cp = path_of(child, in_s);
+          PLAN_REQUIRE(doc_level || cp.parent == sc.path,
+                       "nested path " + std::to_string(child) + " is not registered under path " +
+                           std::to_string(sc.path) + in_s);
+          slg::FilterNodeDev nd{};
+          nd.kind = slg::kFilterNested;
+          nd.row = (uint32_t)n.field;
+          scope.nodes.push_back(nd);
+        } else if (doc_level || n.kind >= SLG_FILTER_AND) {
+          scope.nodes.push_back(doc.node(n, tr.ords, in_s));
         } else {
-          PLAN_REQUIRE(!fv.keyword, "agg field " + std::to_string(id) + " is a keyword field" + in_t);
-          if (n.kind == SLG_FILTER_RANGE_F64) {
+          // a leaf over a nested column of this scope's path.  The column's kind must be the leaf's; a column of
+          // another path is not what the reference looks up (`path.field`): nothing passes
+          const int32_t id = n.field;
+          const auto it = std::find_if(nested_fields.begin(), nested_fields.end(),
+                                       [id](const NestedFieldView &v) { return v.id == id; });
+          PLAN_REQUIRE(it != nested_fields.end(), "unknown nested field id " + std::to_string(id) + in_s);
+          for (uint32_t g = 0; g < n_segs; g++)
+            PLAN_REQUIRE(g < it->has.size() && it->has[g],
+                         "nested field " + std::to_string(id) + " has no column for segment " + std::to_string(g) +
+                             " (added after the field was registered)" + in_s);
+          static const char *const kind_name[] = {"", "an f64", "an i64", "a keyword"};
+          const int want = n.kind == SLG_FILTER_KEYWORD_IN ? 3 : n.kind == SLG_FILTER_RANGE_F64 ? 1 : 2;
+          PLAN_REQUIRE(it->kind == want, "nested field " + std::to_string(id) + " is not " + kind_name[want] + " field" + in_s);
+          slg::FilterNodeDev nd{};
+          nd.kind = (uint32_t)n.kind;
+          if (n.kind == SLG_FILTER_KEYWORD_IN) {
+            nd.bits = ord_bit_set(out.words, n, tr.ords, it->n_ords, "nested field " + std::to_string(id), in_s);
+          } else if (n.kind == SLG_FILTER_RANGE_F64) {
             nd.lo = n.lo_f;
             nd.hi = n.hi_f;
-          } else {
-            PLAN_REQUIRE(fv.from_i64, "agg field " + std::to_string(id) + " was not registered from i64 values" + in_t);
-            if (unsupported.empty() && (fv.i64_rounded || (fv.any_value && (fv.vmin < -k2p53 || fv.vmax > k2p53))))
-              unsupported = "agg field " + std::to_string(id) + " holds an i64 value beyond +-2^53 (CPU path)" + in_t;
-            // every stored value is an integer within +-2^53: a bound on the far side of it selects what the
-            // clamped one does; a lower bound above 2^53 (an upper one below -2^53) selects nothing, which the
-            // clamped bound would not say of a value of exactly +-2^53, so it becomes the infinity
-            nd.lo = n.lo_i > i2p53 ? HUGE_VAL : (double)std::max<int64_t>(n.lo_i, -i2p53);
-            nd.hi = n.hi_i < -i2p53 ? -HUGE_VAL : (double)std::min<int64_t>(n.hi_i, i2p53);
+          } else {  // int64 against int64: the bounds travel in the bits of lo / hi
+            std::memcpy(&nd.lo, &n.lo_i, 8);
+            std::memcpy(&nd.hi, &n.hi_i, 8);
           }
+          if (it->path == sc.path) {
+            nd.row = row_of(used_ncols, id);
+          } else {
+            nd = slg::FilterNodeDev{};
+            nd.kind = slg::kFilterOr;
+          }
+          scope.nodes.push_back(nd);
         }
       }
+      all.push_back(std::move(scope));
+    }
+  }
+  doc.finish(reject, out.cols, out.filters);
+  // pass 2: the rows by level, the doc-level scopes last in tree order
+  std::vector<uint32_t> row(all.size(), 0u), order;
+  out.level_begin.push_back(0u);
+  for (uint32_t l = 1; l <= levels + 1u; l++) {
+    for (uint32_t i = 0; i < all.size(); i++) {
+      const bool doc_level = all[i].index + 1u == trees[all[i].tree].n_scopes;
+      if (l <= levels ? (!doc_level && all[i].level == l) : doc_level) {
+        row[i] = (uint32_t)order.size();
+        order.push_back(i);
+      }
+    }
+    if (l <= levels) out.level_begin.push_back((uint32_t)order.size());
+  }
+  for (const uint32_t i : order) {
+    const Scope &scope = all[i];
+    out.scopes.push_back(slg::NestedScopeDev{(uint32_t)out.nodes.size(), (uint32_t)scope.nodes.size(), scope.path_row, 0u});
+    for (slg::FilterNodeDev nd : scope.nodes) {
+      if (nd.kind == slg::kFilterNested) nd.row = row[tree_first[scope.tree] + nd.row];
       out.nodes.push_back(nd);
     }
   }
-  if (!unsupported.empty()) throw SlgError(SLG_ERR_UNSUPPORTED, unsupported);
-  fill_tables(fields, used_fields, reject, used_filters, n_segs, out.cols, out.filters);
+  for (const int32_t id : used_paths) {
+    const auto it = std::find_if(paths.begin(), paths.end(), [id](const NestedPathView &v) { return v.id == id; });
+    out.paths.insert(out.paths.end(), it->per_seg.begin(), it->per_seg.begin() + n_segs);
+  }
+  for (const int32_t id : used_ncols) {
+    const auto it = std::find_if(nested_fields.begin(), nested_fields.end(),
+                                 [id](const NestedFieldView &v) { return v.id == id; });
+    out.ncols.insert(out.ncols.end(), it->per_seg.begin(), it->per_seg.begin() + n_segs);
+  }
 }
 
 // ---- sort keys of numeric fast fields ----------------------------------------------------------

@@ -321,6 +321,45 @@ void plan_filter_trees(const std::vector<FscoreFieldView> &fields, const uint32_
                        const char *filter_live, size_t n_filters, uint32_t n_segs, const slg_filter_tree *trees,
                        uint32_t n_trees, FilterTreePlan &out);
 
+// ---- nested filter trees (slg_index_add_nested_filter_trees) ----
+// The checks of the trees that need no index (throws SlgError), in the order the header gives: SLG_ERR_INVALID
+// first (what check_filter_trees refuses in each scope's program, and the scope list itself), then
+// SLG_ERR_UNSUPPORTED for the limits.
+void check_nested_filter_trees(const slg_nested_filter_tree *trees, uint32_t n_trees);
+// What the planner sees of a registered nested path / nested value column: per segment its device arrays as
+// opaque addresses (a path without tables for a segment: base null; a column: has[s] == 0)
+struct NestedPathView {
+  int32_t id = 0, parent = -1;
+  std::vector<slg::NestedPathDev> per_seg;  // [n_segs]
+};
+struct NestedFieldView {
+  int32_t id = 0, path = 0;
+  int kind = 0;  // 1 f64, 2 i64, 3 keyword ordinals
+  uint32_t n_ords = 0;
+  std::vector<slg::NestedColDev> per_seg;  // [n_segs]
+  std::vector<char> has;                   // [n_segs] (a column's doc_offs may be null: no value in that segment)
+};
+// The device image of checked trees against an index state (fields, reject, filter_live, n_filters as
+// plan_filter_trees', whose doc-level leaves these trees share).  The scope rows are ordered by level: object
+// scopes of level l (l = 1: no NESTED leaf) are rows level_begin[l - 1] .. level_begin[l]; the doc-level scopes
+// follow from level_begin.back() on, in tree order.  Throws SLG_ERR_INVALID for an unknown id, data missing for a
+// segment, the wrong column kind, an ordinal out of range, a NESTED leaf of an object scope whose child path is
+// not registered under the scope's path; behind those SLG_ERR_UNSUPPORTED for the doc level's 2^53 rule.
+struct NestedFilterPlan {
+  std::vector<slg::NestedScopeDev> scopes;
+  std::vector<uint32_t> level_begin;        // [levels + 1]
+  std::vector<slg::FilterNodeDev> nodes;    // every scope's nodes, in row order
+  std::vector<slg::ColumnDev> cols;         // [agg fields the trees name][n_segs]
+  std::vector<const uint32_t *> filters;    // [filters the trees name][n_segs]
+  std::vector<uint32_t> words;              // the ordinal bit sets
+  std::vector<slg::NestedPathDev> paths;    // [paths the trees name][n_segs]
+  std::vector<slg::NestedColDev> ncols;     // [nested fields the trees name][n_segs]
+};
+void plan_nested_filter_trees(const std::vector<FscoreFieldView> &fields, const uint32_t *const *reject,
+                              const char *filter_live, size_t n_filters, const std::vector<NestedPathView> &paths,
+                              const std::vector<NestedFieldView> &nested_fields, uint32_t n_segs,
+                              const slg_nested_filter_tree *trees, uint32_t n_trees, NestedFilterPlan &out);
+
 // Throws SlgError (SLG_ERR_INVALID / SLG_ERR_UNSUPPORTED) on malformed input.
 void plan_batch(const std::vector<SegView> &segs, const slg_tuning &tune, const BatchIn &in, Plan &out);
 

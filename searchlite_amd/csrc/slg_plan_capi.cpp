@@ -540,6 +540,95 @@ int slgp_plan_filter_trees(const slgp_filter_field *fields, uint32_t n_fields, c
   }
 }
 
+// the host side of slg_index_add_nested_filter_trees: check_nested_filter_trees, then plan_nested_filter_trees
+// against agg fields and filters described as above and nested paths and nested fields that exist as descriptions
+// only (their arrays: made-up addresses, owner id + 1 in the high word, the segment, a tag).  scope_rows: entries
+// of 4 words (slg::NestedScopeDev); nodes: entries of 8 words; levels: level_begin; words: the ordinal bit sets.
+// Each table is filled when it fits its cap; counts: entries of scope_rows, nodes, levels, words, then the rows of
+// the path table and of the nested column table.  0, or a negative error code (err filled)
+struct slgp_nested_path {
+  int32_t id, parent;
+  const uint8_t *seg_has;
+};
+struct slgp_nested_field {
+  int32_t id, path;
+  uint32_t kind, n_ords;  // kind: 1 f64, 2 i64, 3 keyword ordinals
+  const uint8_t *seg_has;
+};
+int slgp_plan_nested_filter_trees(const slgp_filter_field *fields, uint32_t n_fields, const char *filter_live,
+                                  uint32_t n_filters, const slgp_nested_path *paths, uint32_t n_paths,
+                                  const slgp_nested_field *nested_fields, uint32_t n_nested_fields, uint32_t n_segs,
+                                  const slg_nested_filter_tree *trees, uint32_t n_trees, uint32_t *scope_rows,
+                                  uint32_t scopes_cap, uint32_t *nodes, uint32_t nodes_cap, uint32_t *levels,
+                                  uint32_t levels_cap, uint32_t *words, uint32_t words_cap, uint32_t *counts, char *err,
+                                  uint32_t err_len) {
+  try {
+    slgplan::check_nested_filter_trees(trees, n_trees);
+    std::vector<slgplan::FscoreFieldView> views(n_fields);
+    for (uint32_t i = 0; i < n_fields; i++) {
+      views[i] = described_field(fields[i], n_segs);
+      views[i].n_ords = fields[i].n_ords;
+      views[i].from_i64 = fields[i].from_i64 != 0;
+      views[i].any_value = fields[i].any_value != 0;
+      views[i].vmin = fields[i].vmin;
+      views[i].vmax = fields[i].vmax;
+    }
+    std::vector<const uint32_t *> reject((size_t)n_filters * n_segs, nullptr);
+    for (uint32_t f = 0; f < n_filters; f++)
+      for (uint32_t s = 0; s < n_segs && filter_live[f]; s++)
+        reject[(size_t)f * n_segs + s] =
+            reinterpret_cast<const uint32_t *>((uintptr_t)(((uint64_t)(f + 1) << 32) | ((uint64_t)s << 8) | 3u));
+    const auto made_up = [](int32_t owner, uint32_t s, uint32_t tag) {
+      return reinterpret_cast<const uint32_t *>((uintptr_t)(((uint64_t)(owner + 1) << 32) | ((uint64_t)s << 8) | tag));
+    };
+    std::vector<slgplan::NestedPathView> pviews(n_paths);
+    for (uint32_t i = 0; i < n_paths; i++) {
+      pviews[i].id = paths[i].id;
+      pviews[i].parent = paths[i].parent;
+      pviews[i].per_seg.assign(n_segs, slg::NestedPathDev{});
+      for (uint32_t s = 0; s < n_segs; s++)
+        if (paths[i].seg_has[s])
+          pviews[i].per_seg[s] = slg::NestedPathDev{made_up(paths[i].id, s, 4u), made_up(paths[i].id, s, 5u),
+                                                    made_up(paths[i].id, s, 6u), made_up(paths[i].id, s, 7u), 0u, 0u};
+    }
+    std::vector<slgplan::NestedFieldView> nviews(n_nested_fields);
+    for (uint32_t i = 0; i < n_nested_fields; i++) {
+      const slgp_nested_field &f = nested_fields[i];
+      nviews[i].id = f.id;
+      nviews[i].path = f.path;
+      nviews[i].kind = (int)f.kind;
+      nviews[i].n_ords = f.n_ords;
+      nviews[i].per_seg.assign(n_segs, slg::NestedColDev{});
+      nviews[i].has.assign(f.seg_has, f.seg_has + n_segs);
+      for (uint32_t s = 0; s < n_segs; s++)
+        if (f.seg_has[s]) nviews[i].per_seg[s] = slg::NestedColDev{made_up(f.id, s, 8u), made_up(f.id, s, 9u), made_up(f.id, s, 10u)};
+    }
+    slgplan::NestedFilterPlan np;
+    slgplan::plan_nested_filter_trees(views, reject.data(), filter_live, n_filters, pviews, nviews, n_segs, trees, n_trees, np);
+    static_assert(sizeof(slg::NestedScopeDev) == 16 && sizeof(slg::FilterNodeDev) == 32, "the words the caller reads");
+    if (scope_rows && np.scopes.size() <= scopes_cap)
+      std::memcpy(scope_rows, np.scopes.data(), np.scopes.size() * sizeof(slg::NestedScopeDev));
+    if (nodes && np.nodes.size() <= nodes_cap) std::memcpy(nodes, np.nodes.data(), np.nodes.size() * sizeof(slg::FilterNodeDev));
+    if (levels && np.level_begin.size() <= levels_cap) std::memcpy(levels, np.level_begin.data(), np.level_begin.size() * 4);
+    if (words && np.words.size() <= words_cap && !np.words.empty()) std::memcpy(words, np.words.data(), np.words.size() * 4);
+    if (counts) {
+      counts[0] = (uint32_t)np.scopes.size();
+      counts[1] = (uint32_t)np.nodes.size();
+      counts[2] = (uint32_t)np.level_begin.size();
+      counts[3] = (uint32_t)np.words.size();
+      counts[4] = n_segs ? (uint32_t)(np.paths.size() / n_segs) : 0u;
+      counts[5] = n_segs ? (uint32_t)(np.ncols.size() / n_segs) : 0u;
+    }
+    return SLG_OK;
+  } catch (const slgplan::SlgError &e) {
+    if (err && err_len) {
+      std::strncpy(err, e.what(), err_len - 1);
+      err[err_len - 1] = 0;
+    }
+    return e.code;
+  }
+}
+
 // the bucket function of a date_histogram node (slg::date_bucket_id, slg_date.hpp: what the planner's row range and
 // the aggregation kernels run) over n values: ids[i] = the bucket id of vals[i] under unit (SLG_DATE_*), step and
 // offset (i64 ms; step is read for SLG_DATE_FIXED only); ymd[3 i ..] = year, month, day of the UTC day that holds

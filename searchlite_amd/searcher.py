@@ -438,6 +438,105 @@ class GpuIndex:
             out.append(np.unpackbits(buf, bitorder="little")[:n].astype(bool))
         return out
 
+    # -- nested filters (query/filters.rs:13-188: same-object matching over arrays of objects) ----
+    def _u32_ptrs(self, arrays, keep):
+        """arrays[s]: an array or None -> a pointer array over contiguous u32 copies (kept alive in keep)."""
+        ptrs = []
+        for a in arrays:
+            if a is None:
+                ptrs.append(None)
+                continue
+            a = np.ascontiguousarray(a, dtype=np.uint32)
+            if a.size == 0:
+                a = np.zeros(1, np.uint32)
+            keep.append(a)
+            ptrs.append(a.ctypes.data)
+        return (C.c_void_p * self.n_segs)(*ptrs)
+
+    def add_nested_path(self, per_segment, parent: int = -1) -> int:
+        """Register a nested path (slg_index_add_nested_path).  per_segment[s]: None (no doc of the segment has an
+        object), the objects per doc (u32[n_docs]), or (counts, (parent_offsets u32[n_docs + 1], parents)) with the
+        parent lists of the reference's _nested_parent column (None: nothing binds).  parent: the id of the path
+        one level up, or -1.  Returns the path id (ids are never reused)."""
+        assert len(per_segment) == self.n_segs
+        counts, poffs, pvals = [], [], []
+        for s, v in enumerate(per_segment):
+            c, par = (v if isinstance(v, tuple) else (v, None))
+            if c is not None:
+                assert len(c) == int(self.segments[s].n_docs), "one count per doc"
+            if par is not None:
+                assert len(par[0]) == int(self.segments[s].n_docs) + 1, "one parent offset per doc + 1"
+            counts.append(c)
+            poffs.append(None if par is None else par[0])
+            pvals.append(None if par is None else par[1])
+        keep: list = []
+        rc = self._lib.slg_index_add_nested_path(self._h, int(parent), self._u32_ptrs(counts, keep),
+                                                 self._u32_ptrs(poffs, keep), self._u32_ptrs(pvals, keep))
+        if rc < 0:
+            N.check(rc)
+        return rc
+
+    def remove_nested_path(self, path_id: int) -> None:
+        """Unregister a nested path and the nested fields under it (slg_index_remove_nested_path)."""
+        N.check(self._lib.slg_index_remove_nested_path(self._h, int(path_id)))
+
+    def _add_nested_column(self, path_id, per_segment, dt, n_ords=None) -> int:
+        assert len(per_segment) == self.n_segs
+        keep: list = []
+        for s, v in enumerate(per_segment):
+            if v is not None:
+                assert len(v[0]) == int(self.segments[s].n_docs) + 1, "one doc offset per doc + 1"
+        po = self._u32_ptrs([None if v is None else v[0] for v in per_segment], keep)
+        pj = self._u32_ptrs([None if v is None else v[1] for v in per_segment], keep)
+        vals = []
+        for v in per_segment:
+            a = None if v is None else np.ascontiguousarray(v[2], dtype=dt)
+            if a is not None and a.size == 0:
+                a = np.zeros(1, dt)
+            keep.append(a)
+            vals.append(None if a is None else a.ctypes.data)
+        pv = (C.c_void_p * self.n_segs)(*vals)
+        if n_ords is not None:
+            rc = self._lib.slg_index_add_nested_field_ord(self._h, int(path_id), po, pj, pv, int(n_ords))
+        elif dt == np.int64:
+            rc = self._lib.slg_index_add_nested_field_i64(self._h, int(path_id), po, pj, pv)
+        else:
+            rc = self._lib.slg_index_add_nested_field_f64(self._h, int(path_id), po, pj, pv)
+        if rc < 0:
+            N.check(rc)
+        return rc
+
+    def add_nested_field(self, path_id: int, per_segment, dtype) -> int:
+        """Register a numeric nested value column under a path (slg_index_add_nested_field_i64 / _f64).
+        per_segment[s]: None (the segment has no value) or (doc_offsets u32[n_docs + 1], object_offsets, values),
+        the arrays of the reference's I64Nested / F64Nested column.  int64 values stay int64 on the device.
+        Returns the nested field id (ids are never reused)."""
+        dt = np.dtype(dtype)
+        if dt not in (np.dtype(np.int64), np.dtype(np.float64)):
+            raise TypeError("numeric nested fields are int64 or float64")
+        return self._add_nested_column(path_id, per_segment, dt)
+
+    def add_nested_keyword_field(self, path_id: int, per_segment_ords, n_ords: int) -> int:
+        """Register a keyword nested column (slg_index_add_nested_field_ord): per_segment_ords as add_nested_field's
+        with ordinals into ONE dictionary of n_ords keys, the caller's."""
+        return self._add_nested_column(path_id, per_segment_ords, np.dtype(np.uint32), n_ords)
+
+    def remove_nested_field(self, nested_field_id: int) -> None:
+        N.check(self._lib.slg_index_remove_nested_field(self._h, int(nested_field_id)))
+
+    def add_nested_filter_trees(self, trees) -> List[int]:
+        """Filters built on the device from filter trees with Nested nodes, all in one update of the index
+        (slg_index_add_nested_filter_trees).  trees: filters.NestedFilterProgram objects
+        (filters.compile_nested_filter) or (scopes, nodes, ords) triples.  -> the filter ids, one per tree; on an
+        error none is registered."""
+        from .filters import nested_tree_array
+        trees = list(trees)
+        arr, keep = nested_tree_array(trees)
+        ids = np.full(max(len(trees), 1), -1, dtype=np.int32)
+        N.check(self._lib.slg_index_add_nested_filter_trees(self._h, arr, len(trees), ids.ctypes.data))
+        del keep
+        return [int(i) for i in ids[:len(trees)]]
+
     # -- sort fields (query/sort.rs: `sort` on numeric fast fields) -----------------------------
     def add_sort_field(self, per_segment_values, dtype) -> int:
         """Register a numeric fast field for field-sorted search (slg_index_add_sort_field_i64 / _f64).

@@ -902,7 +902,8 @@ typedef struct {
  * SLG_MAX_AGG_CELLS cells per query (value cells count too), or more than SLG_MAX_AGG_SCRATCH_WORDS words of
  * value-node scratch per query (parent_rows x ceil(ranks / 32) per cardinality node, plus the fine tables of a
  * percentiles node: min(32, 2 * n_ranges) << max(0, ceil_log2(ranks) - 12) when that shift is > 0):
- * SLG_ERR_UNSUPPORTED.  Aggregations are not built on cursor, hybrid,
+ * SLG_ERR_UNSUPPORTED.  Aggregations behind a clause or score stage: slg_batch_prepare_request, "compound requests" below.
+ * Aggregations are not built on cursor, hybrid,
  * vector-only, sharded or coalesced batches (slg_batch_run_sharded* refuses an aggregation batch:
  * SLG_ERR_UNSUPPORTED). */
 slg_batch *slg_batch_prepare_aggs(slg_index *index, uint32_t nq, const uint32_t *q_offsets,
@@ -966,7 +967,8 @@ int slg_search_batch_agg_values(slg_index *index, const slg_query *queries, uint
  * SLG_ERR_UNSUPPORTED.  Nodes may come in any order; nodes of one parent that follow one another share its bucket
  * runs, otherwise each builds them again (the same lists, more time).  Memory per batch: nq x (8 B x max_entries + 12 B x hit_cells + 4 B x list_cells), plus 4 B
  * per row of a parent of more than 4096 rows.  Not built (the CPU path): cursor, hybrid, vector-only, scan, sharded
- * and coalesced batches (no such entry point takes the spec; slg_batch_run_sharded* refuses the batch), a third
+ * and coalesced batches (no such entry point takes the spec; behind a clause or score stage:
+ * slg_batch_prepare_request, "compound requests" below; slg_batch_run_sharded* refuses the batch), a third
  * level, from + size > 64, keyword sort parts. */
 #define SLG_MAX_TOP_HITS_NODES 4u
 #define SLG_MAX_TOP_HITS 64u              /* from + size of one node: one entry per lane */
@@ -1048,8 +1050,9 @@ int slg_search_batch_top_hits(slg_index *index, const slg_query *queries, uint32
  * reference reads f64 columns only and skips every doc: the caller answers the empty response), one with an id at or
  * beyond +-2^31, key_bits > 63, size x (1 + child cells) plus the cells of aggs_or_null over SLG_MAX_AGG_CELLS:
  * SLG_ERR_UNSUPPORTED.  Memory per batch: nq x 8 B x (size + 1) keys, the table cells, 4 B per ordinal of a ranked
- * terms source.  Not built (the CPU path): composite on scan, cursor, hybrid, vector-only, bool, phrase, sharded
- * (slg_batch_run_sharded* refuses the batch) or coalesced batches; top_hits or value nodes under a composite;
+ * terms source.  Not built (the CPU path): composite on scan, cursor, hybrid, vector-only, sharded
+ * (slg_batch_run_sharded* refuses the batch) or coalesced batches (behind a clause or score stage:
+ * slg_batch_prepare_request, "compound requests" below); top_hits or value nodes under a composite;
  * `sampling`; more than one composite per request; a composite below another aggregation; `missing`, `offset` or
  * bounds on a source (the reference has none). */
 #define SLG_MAX_COMPOSITE_SOURCES 4u
@@ -1145,8 +1148,9 @@ int slg_search_batch_composite(slg_index *index, const slg_query *queries, uint3
  * Memory per batch: nq x 12 B per ordinal of every node, the presence words, nq x 36 B per output row, the child
  * cells; per distinct (field, filter): 4 B x n_segs x (n_ords + 1); 8 B per ordinal of a ranked node.
  * Not built (the CPU path; refused, or there is no entry point): `sampling`; `size` absent; a term-bucket node below
- * another aggregation; top_hits or value nodes below one; term buckets on scan, cursor, hybrid, vector-only, bool,
- * phrase, sharded (slg_batch_run_sharded* refuses the batch) or coalesced batches; together with a composite or
+ * another aggregation; top_hits or value nodes below one; term buckets on scan, cursor, hybrid, vector-only,
+ * sharded (slg_batch_run_sharded* refuses the batch) or coalesced batches (behind a clause or score stage:
+ * slg_batch_prepare_request, "compound requests" below); together with a composite or
  * top_hits spec in one batch.  Pipeline children stay the caller's. */
 #define SLG_MAX_TERM_BUCKET_NODES 4u
 #define SLG_MAX_TERM_BUCKET_SIZE 1024u /* as SLG_MAX_COMPOSITE_SIZE */
@@ -1572,7 +1576,8 @@ int slg_search_batch_hybrid(slg_index *index, uint32_t nq, const uint32_t *q_off
  * query whose terms x segments exceed 2048 table entries: SLG_ERR_UNSUPPORTED (CPU scorer).  slg_batch_fetch_rescore on a batch without rescore, or one that has not
  * run: SLG_ERR_INVALID.  slg_batch_run_sharded* and slg_batch_fetch_sharded refuse a rescore batch with
  * SLG_ERR_UNSUPPORTED.  Not built: rescore on sorted, cursor, hybrid, vector-only and aggregation batches,
- * and in the coalescer (none of their prepare calls takes a rescore spec).
+ * and in the coalescer (none of their prepare calls takes a rescore spec; behind a clause stage:
+ * slg_batch_prepare_request, "compound requests" below).
  */
 enum { SLG_RESCORE_TOTAL = 0, SLG_RESCORE_MULTIPLY = 1, SLG_RESCORE_SUM = 2, SLG_RESCORE_MAX = 3, SLG_RESCORE_MIN = 4 };
 #define SLG_MAX_RESCORE_WINDOW 1024u
@@ -1647,8 +1652,8 @@ int slg_search_batch_rescore(slg_index *index, uint32_t nq, const uint32_t *q_of
  * SLG_MAX_BOOL_GROUPS groups or SLG_MAX_BOOL_TERMS clause terms in a query.  slg_batch_run_sharded* and
  * slg_batch_fetch_sharded refuse a bool batch with SLG_ERR_UNSUPPORTED.  Nested matchers (a bool, dis_max or
  * query string as a child of bool) and a bool's own filter list: slg_batch_prepare_bool_tree below.  Not built
- * (CPU scorer): clause tables on cursor, hybrid, aggregation, rescore, sharded and coalesced batches (none of
- * their prepare calls takes a bool spec).  Phrase children of a bool and the query string's quoted phrases:
+ * (CPU scorer): clause tables on hybrid, sharded and coalesced batches (with a cursor, a score stage,
+ * aggregations, rescore or collapse: slg_batch_prepare_request, "compound requests" below).  Phrase children of a bool and the query string's quoted phrases:
  * slg_batch_prepare_phrase below.
  * --------------------------------------------------------------------------------------------------------- */
 #define SLG_BOOL_MUST 0
@@ -1736,9 +1741,9 @@ int slg_search_batch_bool(slg_index *index, uint32_t nq, const uint32_t *q_offse
  * the plans.  SLG_ERR_UNSUPPORTED (CPU scorer): more than SLG_MAX_BOOL_TREE_LEAVES leaves, SLG_MAX_BOOL_TREE_NODES
  * nodes or SLG_MAX_BOOL_TERMS clause terms in a query; the same child twice in one node (the reference would
  * count it twice, a mask cannot).  slg_batch_run_sharded* and slg_batch_fetch_sharded refuse the batch with
- * SLG_ERR_UNSUPPORTED.  Not built (CPU scorer): phrase leaves in a tree, and trees on cursor, hybrid,
- * aggregation, rescore, collapse, function_score, sharded and coalesced batches (none of their prepare calls
- * takes a tree spec).
+ * SLG_ERR_UNSUPPORTED.  Not built (CPU scorer): phrase leaves in a tree, and trees on hybrid,
+ * sharded and coalesced batches (with a cursor, a score stage, aggregations, rescore or collapse:
+ * slg_batch_prepare_request, "compound requests" below).
  * --------------------------------------------------------------------------------------------------------- */
 #define SLG_MAX_BOOL_TREE_LEAVES 32u  /* term groups + filter leaves of one query (bits 0-31 of the kernel's masks) */
 #define SLG_MAX_BOOL_TREE_NODES 32u   /* nodes of one query (bits 32-63) */
@@ -1830,7 +1835,8 @@ int slg_search_batch_bool_tree(slg_index *index, uint32_t nq, const uint32_t *q_
  * SLG_MAX_PHRASE_QUERY_TERMS variant terms in a query, a slop above SLG_MAX_PHRASE_SLOP, too many groups.
  * slg_batch_run_sharded* and slg_batch_fetch_sharded refuse a phrase batch with SLG_ERR_UNSUPPORTED.  Not built
  * (CPU scorer): phrases in rescore queries, position alternatives, nested matchers, and phrase batches on
- * cursor, hybrid, aggregation, rescore, sharded and coalesced paths.
+ * hybrid, sharded and coalesced paths (with a cursor, a score stage, aggregations, rescore or collapse:
+ * slg_batch_prepare_request, "compound requests" below).
  * --------------------------------------------------------------------------------------------------------- */
 int slg_index_set_positions(slg_index *index, uint32_t seg, const uint64_t *pos_offsets, const uint32_t *positions);
 
@@ -1918,8 +1924,9 @@ int slg_search_batch_phrase(slg_index *index, uint32_t nq, const uint32_t *q_off
  * (slg_batch_prepare_script, below).  Not built (CPU scorer): function_score below the root or over any other
  * inner query (rank_feature and constant_score at the root are scan batches, below), deeper nesting, explain,
  * function filters other than registered
- * filter ids, and specs on bool, phrase, cursor, hybrid, aggregation, rescore, sharded and coalesced batches
- * (none of their prepare calls takes the spec).
+ * filter ids, and specs on hybrid, rescore, sharded and coalesced batches
+ * (behind bool, phrase or tree clauses, with a cursor, aggregations or collapse:
+ * slg_batch_prepare_request, "compound requests" below).
  * --------------------------------------------------------------------------------------------------------- */
 #define SLG_MAX_FSCORE_FUNCS 8u /* functions of one query */
 enum { SLG_FSCORE_WEIGHT = 0, SLG_FSCORE_FIELD_VALUE_FACTOR = 1, SLG_FSCORE_DECAY = 2 };
@@ -2014,7 +2021,9 @@ int slg_search_batch_fscore(slg_index *index, uint32_t nq, const uint32_t *q_off
  * with no hit (e.g. "1 2") — and a column that holds a non-finite value (the rule of aggregations).
  * slg_batch_run_sharded* and slg_batch_fetch_sharded refuse a script batch with SLG_ERR_UNSUPPORTED.
  * Not built (CPU scorer): script_score below the root or over any other inner query, more than the two stages,
- * explain, and specs on any other batch kind (rank_feature and constant_score at the root are scan batches, below).
+ * explain, and specs on hybrid, rescore, sharded and coalesced batches (rank_feature and constant_score at the root are
+ * scan batches, below; behind bool, phrase or tree clauses, with a cursor, aggregations or collapse:
+ * slg_batch_prepare_request, "compound requests" below).
  * --------------------------------------------------------------------------------------------------------- */
 #define SLG_MAX_SCRIPT_INSTRS 64u /* instructions of one query */
 #define SLG_MAX_SCRIPT_DEPTH 8u   /* stack slots */
@@ -2150,8 +2159,9 @@ int slg_search_batch_scan(slg_index *index, uint32_t nq, const slg_scan_spec *sp
  * field id, a numeric agg field, a field without a column for every segment, an unknown inner sort field.
  * SLG_ERR_UNSUPPORTED (CPU path): k > SLG_MAX_COLLAPSE_ROWS; inner_size > 0 and inner_from + inner_size >
  * SLG_MAX_INNER_HITS; more than SLG_MAX_SORT_PARTS inner parts.  slg_batch_fetch_collapse on another kind
- * of batch or before the batch has run: SLG_ERR_INVALID.  NOT BUILT: collapse together with aggregations,
- * rescore, bool, phrase, function_score, hybrid or vector-only batches, in the coalescer or sharded
+ * of batch or before the batch has run: SLG_ERR_INVALID.  NOT BUILT: collapse together with
+ * rescore, hybrid or vector-only batches (behind clause and score stages and beside aggregations:
+ * slg_batch_prepare_request, "compound requests" below), in the coalescer or sharded
  * (slg_batch_run_sharded* and slg_batch_fetch_sharded refuse a collapse batch: SLG_ERR_UNSUPPORTED);
  * k > SLG_MAX_COLLAPSE_ROWS; inner_hits beyond SLG_MAX_INNER_HITS (an unlimited inner size included). */
 #define SLG_MAX_COLLAPSE_ROWS 4096u /* k of a collapse batch: the rows of a query are collapsed in LDS */
@@ -2183,6 +2193,88 @@ int slg_search_batch_collapse(slg_index *index, uint32_t nq, const uint32_t *q_o
                               uint32_t *group_row, uint32_t *group_ord, uint32_t *group_size, uint32_t *group_doc,
                               uint32_t *group_seg, float *group_score, uint32_t *inner_count, uint32_t *inner_row,
                               uint32_t *inner_doc, uint32_t *inner_seg, float *inner_score);
+
+/* ---- compound requests: several batch kinds in one batch ------------------------------------------------
+ * A SearchRequest is rarely one feature: a filtered bool query with facets, a function_score around a bool,
+ * a bool under a sort with search_after, collapse over a phrase query.  slg_batch_prepare_request takes the
+ * query arrays of slg_batch_prepare_plans and one nullable pointer per kind; a kind is asked for when its
+ * pointer is non-NULL (script_order is read only with script_spec).  Every slg_batch_prepare_<kind> is this
+ * call with that kind's pointers set: a request that asks for one kind gives that kind's batch, byte for byte.
+ * The batch is an ordinary slg_batch: slg_batch_run / _fetch / _matched_counts / _cursor_seen, and the fetches
+ * of every kind it was asked for (slg_batch_fetch_aggs, _agg_values, _top_hits, _composite with
+ * slg_batch_set_composite_after, _term_buckets, _rescore, _collapse, slg_batch_highlight).  There is no
+ * one-call form.
+ *
+ * ORDER OF THE STAGES (one run; each stage is the kernel of its kind, unchanged).  Per candidate the reference
+ * runs score_adjust (which may drop the doc), then accept (tombstones, matcher, root filter, cursor, matched
+ * count), then collector.collect (query/wand.rs:506-517; the collectors are fed from accept's survivors,
+ * api/reader.rs:3020-3028).  The device runs: scoring; the clause stage (drops the candidates the matcher
+ * rejects); the score stage (function_score / script_score, in script_order: rewrites every surviving
+ * candidate's score, drops those below min_score or without a script value); the select in score order or
+ * under the sort, with the cursor; the collectors over the surviving candidates; rescore or collapse over the
+ * rows.  The matcher never reads a score and the score stage never reads the matcher, so clause-then-score
+ * keeps exactly the docs score_adjust-then-matcher keeps.
+ *
+ * THE MATCHED SET of a compound batch is the docs that pass tombstones, q_filter, the clause stage and the
+ * score stage's min_score.  slg_batch_matched_counts, the aggregation tables, top_hits, composite,
+ * term buckets and collapse's total_groups (over the rows) see exactly that set; top_hits and a `_score` sort
+ * part see the rewritten score; the rows equal those of the same request without collectors / collapse, bit
+ * for bit.  slg_stats.scored_docs is the plain batch's count minus the clause stage's rejects minus the score
+ * stage's drops (each stage takes its own off the same counter, over the candidates the stage before left).
+ *
+ * LEGAL COMBINATIONS.
+ *   clause stage   at most one of bool_spec, phrase_spec (with its optional bool_spec: the term groups of a
+ *                  phrase batch, as slg_batch_prepare_phrase) and bool_tree_spec
+ *   score stage    fscore_spec, script_spec, or both in script_order; alone or behind a clause stage
+ *                  (function_score{query: bool{..}} / script_score{query: bool{..}} at the root)
+ *   order          score order or sort, q_cursor on either; behind any clause and / or score stage
+ *   collectors     aggs, alone or with ONE of top_hits / composite / term_buckets (each of the three also
+ *                  without aggs), behind any clause and / or score stage, in score order or under a sort
+ *   collapse       k <= SLG_MAX_COLLAPSE_ROWS, SLG_MAX_INNER_HITS inner hits; behind any clause and / or score
+ *                  stage, beside collectors, and with a cursor when there are no collectors
+ *   rescore        score order, no cursor; alone or behind a clause stage
+ * REFUSED, SLG_ERR_UNSUPPORTED (CPU path), the message naming the pair, before the index is looked at and after
+ * every kind's own argument checks (an invalid argument is reported before an unsupported combination):
+ *   bool_tree_spec with bool_spec or phrase_spec (two clause kinds);
+ *   two of top_hits / composite / term_buckets;
+ *   q_cursor with aggs, top_hits, composite or term_buckets: the reference collects only the docs behind the
+ *     cursor (accept returns false before collector.collect) and the collectors' walks do not test the cursor;
+ *   rescore with sort, q_cursor, fscore_spec, script_spec, aggs, top_hits, composite, term_buckets or collapse.
+ * Hybrid, vector-only and scan batches are not requests of this form: they keep their own entry points
+ * (slg_batch_prepare_hybrid, slg_vector_search_batch*, slg_batch_prepare_scan) and the struct cannot ask for
+ * them.  The coalescer takes plain requests only, and slg_batch_run_sharded* / slg_batch_fetch_sharded refuse
+ * a compound batch by the first of its kinds they do not run (SLG_ERR_UNSUPPORTED).
+ *
+ * SLG_ERR_INVALID: req NULL; struct_size other than sizeof(slg_request) (the struct may grow: always set it
+ * from sizeof); reserved other than 0; index NULL; and whatever each kind's own prepare call reports for its spec, with the same
+ * message.  Each kind's limits (SLG_MAX_*) hold as in its own section. */
+typedef struct slg_request {
+  uint32_t struct_size; /* = sizeof(slg_request) */
+  uint32_t nq;
+  const uint32_t *q_offsets;  /* the query arrays of slg_batch_prepare_plans */
+  const uint32_t *q_term_ids;
+  const float *q_weights;
+  const slg_score_plans *plans; /* NULL: every query is a flat sum */
+  const int32_t *q_filter;      /* NULL: no query is filtered */
+  uint32_t k;
+  int32_t strategy;
+  const slg_sort_spec *sort;                /* NULL: score order */
+  const slg_sort_cursor *q_cursor;          /* [nq]; NULL: no cursor */
+  const slg_bool_spec *bool_spec;           /* clause stage: bool (with phrase_spec: its term groups) */
+  const slg_phrase_spec *phrase_spec;       /* clause stage: phrase */
+  const slg_bool_tree_spec *bool_tree_spec; /* clause stage: matcher tree */
+  const slg_fscore_spec *fscore_spec;       /* score stage: function_score */
+  const slg_script_spec *script_spec;       /* score stage: script_score */
+  int32_t script_order;                     /* SLG_SCRIPT_OUTER / _INNER; read only with script_spec */
+  uint32_t reserved;                        /* must be 0 */
+  const slg_agg_spec *aggs;
+  const slg_top_hits_spec *top_hits;
+  const slg_composite_spec *composite;
+  const slg_term_bucket_spec *term_buckets;
+  const slg_rescore_spec *rescore;
+  const slg_collapse_spec *collapse;
+} slg_request;
+slg_batch *slg_batch_prepare_request(slg_index *index, const slg_request *req);
 
 /* ---- term expansion: fuzzy, prefix, wildcard and regex (api/reader.rs:1119-1373, 1394-1465) -----------
  * A request whose terms must be expanded against the term dictionary (SearchRequest.fuzzy, QueryNode::Prefix,

@@ -204,6 +204,19 @@ pub const SLG_SCAN_MOD_RECIPROCAL: i32 = 4;
     pub field: i32, pub group_limit: u32, pub inner_from: u32, pub inner_size: u32,
     pub inner_sort: *const slg_sort_spec,
 }
+// a compound request (slg_batch_prepare_request): the query arrays and one nullable pointer per batch kind; a
+// kind is asked for when its pointer is non-null; struct_size = size_of::<slg_request>()
+#[repr(C)] pub struct slg_request {
+    pub struct_size: u32, pub nq: u32, pub q_offsets: *const u32, pub q_term_ids: *const u32,
+    pub q_weights: *const c_float, pub plans: *const slg_score_plans, pub q_filter: *const i32, pub k: u32,
+    pub strategy: i32, pub sort: *const slg_sort_spec, pub q_cursor: *const slg_sort_cursor,
+    pub bool_spec: *const slg_bool_spec, pub phrase_spec: *const slg_phrase_spec,
+    pub bool_tree_spec: *const slg_bool_tree_spec, pub fscore_spec: *const slg_fscore_spec,
+    pub script_spec: *const slg_script_spec, pub script_order: i32, pub reserved: u32,
+    pub aggs: *const slg_agg_spec, pub top_hits: *const slg_top_hits_spec, pub composite: *const slg_composite_spec,
+    pub term_buckets: *const slg_term_bucket_spec, pub rescore: *const slg_rescore_spec,
+    pub collapse: *const slg_collapse_spec,
+}
 // term expansion (SearchRequest::fuzzy, QueryNode::Prefix / ::Wildcard): one source term, prefix or pattern;
 // field and term are UTF-8 with byte lengths, max_edits / prefix_length / min_length are FuzzyOptions
 #[repr(C)] pub struct slg_expand_req {
@@ -621,6 +634,7 @@ extern "C" {
         group_size: *mut u32, group_doc: *mut u32, group_seg: *mut u32, group_score: *mut c_float,
         inner_count: *mut u32, inner_row: *mut u32, inner_doc: *mut u32, inner_seg: *mut u32,
         inner_score: *mut c_float) -> c_int;
+    pub fn slg_batch_prepare_request(index: *mut slg_index, req: *const slg_request) -> *mut slg_batch;
 }
 pub const SLG_MAX_COLLAPSE_ROWS: u32 = 4096;
 pub const SLG_MAX_INNER_HITS: u32 = 64;

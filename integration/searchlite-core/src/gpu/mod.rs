@@ -754,6 +754,19 @@ pub(crate) fn gpu_eligible(
   // no collector: agg_ref stays None only without aggregations (api/reader.rs:2694-2699).  A cursor (the next
   // page) runs on the device in score order and in every field sort above (slg_batch_prepare_after); with a
   // vector query it stays on the CPU
+  // Compound shapes (ffi::slg_batch_prepare_request: one slg_request with a pointer per kind).  The library now runs,
+  // in ONE batch: a clause stage (a flat bool, a phrase query, or a nested matcher tree: at most one of the three),
+  // then a score stage (function_score and / or script_score at the root: `needs_score_hook` with a flat function
+  // list or an arithmetic script over registered columns), then score order or a field sort with or without a cursor,
+  // then aggregations (alone or with one of top_hits / composite / significant_terms / rare_terms) and collapse; or,
+  // in score order without a cursor, a clause stage and a rescore.  What this predicate may route once the shim builds
+  // the specs (it does not yet: the struct and the call are bound in ffi.rs, nothing below constructs a slg_request):
+  //   bool / phrase / matcher + aggs [+ sort]; + function_score / script_score at the root; + a cursor WITHOUT aggs;
+  //   + collapse (with aggs, or with a cursor, not with both); bool / phrase / matcher + rescore in score order.
+  // What stays on the CPU scorer, and what the library refuses with SLG_ERR_UNSUPPORTED naming the pair: a cursor
+  // together with any aggregation (the reference collects only the docs behind the cursor, query/wand.rs:506-517);
+  // rescore with a sort, a cursor, a score stage, aggregations or collapse; two clause kinds (a phrase leaf inside a
+  // matcher tree); two of top_hits / composite / term buckets; hybrid, vector-only and scan requests; `explain`.
   if req.explain || needs_score_hook {
     return None;
   }

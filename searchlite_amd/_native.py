@@ -286,6 +286,18 @@ class CollapseSpec(C.Structure):
                 ("inner_size", C.c_uint32), ("inner_sort", C.c_void_p)]
 
 
+class Request(C.Structure):
+    """slg_request: the query arrays and one nullable pointer per batch kind (slg_batch_prepare_request); a kind
+    is asked for when its pointer is set.  struct_size = sizeof."""
+    _fields_ = [("struct_size", C.c_uint32), ("nq", C.c_uint32), ("q_offsets", C.c_void_p), ("q_term_ids", C.c_void_p),
+                ("q_weights", C.c_void_p), ("plans", C.c_void_p), ("q_filter", C.c_void_p), ("k", C.c_uint32),
+                ("strategy", C.c_int32), ("sort", C.c_void_p), ("q_cursor", C.c_void_p), ("bool_spec", C.c_void_p),
+                ("phrase_spec", C.c_void_p), ("bool_tree_spec", C.c_void_p), ("fscore_spec", C.c_void_p),
+                ("script_spec", C.c_void_p), ("script_order", C.c_int32), ("reserved", C.c_uint32),
+                ("aggs", C.c_void_p), ("top_hits", C.c_void_p), ("composite", C.c_void_p),
+                ("term_buckets", C.c_void_p), ("rescore", C.c_void_p), ("collapse", C.c_void_p)]
+
+
 class FilterNode(C.Structure):
     """slg_filter_node: one node of a filter tree's postfix program (slg_index_add_filter_trees)."""
     _fields_ = [("kind", C.c_int32), ("field", C.c_int32), ("filter_id", C.c_int32), ("arity", C.c_uint32),
@@ -565,6 +577,7 @@ def load():
         "slg_batch_prepare_collapse": (vp, [vp, u32, vp, vp, vp, vp, vp, vp, vp, vp, u32, i32]),
         "slg_batch_fetch_collapse": (i32, [vp] * 15),
         "slg_search_batch_collapse": (i32, [vp, u32, vp, vp, vp, vp, vp, vp, vp, vp, u32, i32] + [vp] * 18),
+        "slg_batch_prepare_request": (vp, [vp, vp]),
         "slg_index_set_terms": (i32, [vp, u32, vp, vp]),
         "slg_expand_batch": (i32, [vp, vp, u32, vp, u32, vp, vp]),
         "slg_expand_phase_ms": (i32, [vp, vp, vp]),

@@ -204,6 +204,37 @@ slg_batch *slg_batch_prepare_plan(slg_index *ix, uint32_t nq, const uint32_t *q_
 
 }  // extern "C"
 
+// The kinds one batch may hold together (searchlite_gpu.h, "compound requests").  Only
+// slg_batch_prepare_request can ask for a pair this refuses: each legacy entry sets one legal combination.
+// Needs no index; the message names the pair.
+static void check_request(const PrepareRequest &r) {
+  auto refuse = [](const char *a, const char *b, const char *why) {
+    throw SlgError(SLG_ERR_UNSUPPORTED, std::string(a) + " with " + b + ": " + why);
+  };
+  // (a phrase batch's bool spec is its own term groups: boolean.on beside phrase.on is one clause kind)
+  const char *const clause = r.phrase.on ? "phrase_spec" : r.boolean.on ? "bool_spec" : nullptr;
+  if (r.booltree.on && clause) refuse("bool_tree_spec", clause, "one clause stage per request");
+  struct Named {
+    bool on;
+    const char *name;
+  };
+  const Named family[3] = {{r.top_hits.on, "top_hits"}, {r.composite.on, "composite"}, {r.term_buckets.on, "term_buckets"}};
+  const Named collectors[4] = {{r.aggs.on, "aggs"}, family[0], family[1], family[2]};
+  for (int i = 0; i < 3; i++)
+    for (int j = i + 1; j < 3; j++)
+      if (family[i].on && family[j].on) refuse(family[i].name, family[j].name, "one of the three beside aggs");
+  if (r.cursor.on)
+    for (const Named &c : collectors)
+      if (c.on) refuse("q_cursor", c.name, "the collectors do not test the cursor");
+  if (r.rescore.on) {
+    const Named others[] = {{r.sort.on, "sort"},   {r.cursor.on, "q_cursor"}, {r.fscore.on, "fscore_spec"},
+                            {r.script.on, "script_spec"}, collectors[0], collectors[1], collectors[2], collectors[3],
+                            {r.collapse.on, "collapse"}};
+    for (const Named &o : others)
+      if (o.on) refuse("rescore", o.name, "rescore runs in score order behind at most a clause stage");
+  }
+}
+
 // every slg_batch_prepare*: the kinds the request asks for decide what is checked, planned and attached
 slg_batch *slghost::prepare_impl(const PrepareRequest &r) {
   slg_index *const ix = r.ix;
@@ -229,6 +260,7 @@ slg_batch *slghost::prepare_impl(const PrepareRequest &r) {
     if (r.top_hits.on) slgplan::check_top_hits(r.top_hits.spec, r.aggs.spec);
     if (r.composite.on) composite_check_spec(r.composite.spec);
     if (r.term_buckets.on) term_buckets_check_spec(r.term_buckets.spec);
+    check_request(r);  // (behind every kind's own checks: an invalid argument comes before an unsupported pair)
     SLG_REQUIRE(ix != nullptr, "index is NULL");
     SLG_REQUIRE(!after || q_cursor != nullptr, "q_cursor is NULL");
     check_sort_spec(sort);  // (before planning: the planner never sees a sort spec it cannot run)
@@ -434,6 +466,33 @@ slg_batch *slg_batch_prepare_after(slg_index *ix, uint32_t nq, const uint32_t *q
   PrepareRequest r{ix, nq, q_offsets, q_term_ids, q_weights, plans, q_filter, k, strategy};
   r.sort = if_given(sort);
   r.cursor = {true, q_cursor};
+  return prepare_impl(r);
+}
+
+// a compound request: every kind whose pointer is given, through the one path of the calls above and below
+slg_batch *slg_batch_prepare_request(slg_index *ix, const slg_request *req) {
+  const int rc = guarded([&] {
+    SLG_REQUIRE(req != nullptr, "req is NULL");
+    SLG_REQUIRE(req->struct_size == sizeof(slg_request), "slg_request.struct_size is not sizeof(slg_request)");
+    SLG_REQUIRE(req->reserved == 0u, "slg_request.reserved is not 0");
+  });
+  if (rc != SLG_OK) return nullptr;
+  PrepareRequest r{ix, req->nq, req->q_offsets, req->q_term_ids, req->q_weights, req->plans, req->q_filter, req->k,
+                   req->strategy};
+  r.sort = if_given(req->sort);
+  r.cursor = if_given(req->q_cursor);
+  r.phrase = if_given(req->phrase_spec);
+  r.boolean = {req->bool_spec != nullptr || req->phrase_spec != nullptr, req->bool_spec};  // (as slg_batch_prepare_phrase)
+  r.booltree = if_given(req->bool_tree_spec);
+  r.fscore = if_given(req->fscore_spec);
+  r.script = if_given(req->script_spec);
+  r.script_order = req->script_spec ? req->script_order : SLG_SCRIPT_OUTER;
+  r.aggs = if_given(req->aggs);
+  r.top_hits = if_given(req->top_hits);
+  r.composite = if_given(req->composite);
+  r.term_buckets = if_given(req->term_buckets);
+  r.rescore = if_given(req->rescore);
+  r.collapse = if_given(req->collapse);
   return prepare_impl(r);
 }
 

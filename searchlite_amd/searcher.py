@@ -843,6 +843,49 @@ class GpuIndex:
                              q_min_match, sort, cursors, hybrid, aggs, rescore, clauses, phrases, fscore, collapse,
                              clause_tree, script, script_order, top_hits, composite, term_buckets)
 
+    def prepare_request(self, q_offsets, q_terms, q_weights, k: int, strategy: int = Wand, q_filter=None,
+                        **kinds) -> "PreparedBatch":
+        """A compound request (slg_batch_prepare_request): several batch kinds in one batch.  **kinds: the keyword
+        arguments of prepare() — sort, cursors, clauses, phrases, clause_tree, fscore, script, script_order, aggs,
+        top_hits, composite, term_buckets, rescore, collapse and the score plan arrays — every one that is given
+        is asked for, and the library refuses the combinations that are not built (ERR_UNSUPPORTED, the message
+        naming the pair).  The batch has the fetch methods of every kind asked for: fetch, matched_counts,
+        cursor_seen, aggs, top_hits, composite, term_buckets, rescore_details, collapse_groups, highlight."""
+        if "hybrid" in kinds or "request" in kinds:
+            raise N.SlgError(N.ERR_UNSUPPORTED, "prepare_request takes no `hybrid` or `request` argument (a hybrid batch "
+                                                "keeps its own entry point: prepare(hybrid=True))")
+        return PreparedBatch(self, q_offsets, q_terms, q_weights, k, strategy, q_filter, request=True, **kinds)
+
+    def search_request(self, q_offsets, q_terms, q_weights, k: int, strategy: int = Wand, q_filter=None,
+                       want_stats: bool = False, **kinds) -> dict:
+        """prepare_request, one run and everything the request asked for, as a dict: doc, seg, score, count[, stats];
+        matched (a sort, a cursor or a collector); seen (cursors); aggs and agg_layout; top_hits; composite;
+        term_buckets; rescore (first_score, rescore_score, rescored); collapse."""
+        b = self.prepare_request(q_offsets, q_terms, q_weights, k, strategy, q_filter, **kinds)
+        try:
+            b.run()
+            out = dict(zip(("doc", "seg", "score", "count", "stats"), b.fetch(want_stats)))
+            collectors = [x is not None for x in (b.agg_spec, b.top_hits_spec, b.composite_spec, b.term_bucket_spec)]
+            if b.sorted or b.after or any(collectors):
+                out["matched"] = b.matched_counts()
+            if b.after:
+                out["seen"] = b.cursor_seen()
+            if collectors[0]:
+                out["aggs"], out["agg_layout"] = b.aggs(), b.agg_layout()
+            if collectors[1]:
+                out["top_hits"] = b.top_hits()
+            if collectors[2]:
+                out["composite"] = b.composite()
+            if collectors[3]:
+                out["term_buckets"] = b.term_buckets()
+            if b.is_rescore:
+                out["rescore"] = b.rescore_details()
+            if b.is_collapse:
+                out["collapse"] = b.collapse_groups()
+            return out
+        finally:
+            b.close()
+
     def search_term_buckets(self, q_offsets, q_terms, q_weights, k: int, aggs, sort=None, strategy: int = Wand,
                             q_filter=None, term_buckets=None, **plans):
         """Batch search with significant_terms / rare_terms aggregations (slg_batch_prepare_term_buckets).  aggs: an
@@ -1501,7 +1544,7 @@ class PreparedBatch:
                  group_tie=None, q_node_offsets=None, node_kind=None, node_tie=None, node_parent=None,
                  q_min_match=None, sort=None, cursors=None, hybrid=False, aggs=None, rescore=None, clauses=None,
                  phrases=None, fscore=None, collapse=None, clause_tree=None, script=None, script_order="outer",
-                 top_hits=None, composite=None, term_buckets=None):
+                 top_hits=None, composite=None, term_buckets=None, request=False):
         self.index = index
         self._lib = index._lib
         q_offsets = np.ascontiguousarray(q_offsets, dtype=np.uint32)
@@ -1558,7 +1601,8 @@ class PreparedBatch:
         kinds = [kd for kd in _BATCH_KINDS if kd.arg is None or given[kd.arg] is not None]
         # The library's other prepare calls take no spec of the kind: the refusal is made here with its code.  The
         # specs an AggPlan can carry speak before a kind is chosen, top_hits first; of the rest the chosen kind alone
-        for kd in [x for x in reversed(_BATCH_KINDS[:3]) if x in kinds] or kinds[:1]:
+        # (a compound request goes to the library as it is: slg_batch_prepare_request refuses what is not built)
+        for kd in () if request else [x for x in reversed(_BATCH_KINDS[:3]) if x in kinds] or kinds[:1]:
             if any(given[name] is not None for name in kd.refuses):
                 raise N.SlgError(N.ERR_UNSUPPORTED, kd.message)
         held = []  # what only the prepare call reads: alive until it has returned
@@ -1585,9 +1629,20 @@ class PreparedBatch:
             held.append(obj)
             return C.addressof(obj)
 
-        self._h = getattr(self._lib, kinds[0].entry)(
-            index._h, self.nq, _ptr(q_offsets), _ptr(q_terms), _ptr(q_weights), C.addressof(plans), opt(qf),
-            *[pointer(slot) for slot in kinds[0].own], k, strategy)
+        if request:
+            if hybrid:
+                raise N.SlgError(N.ERR_UNSUPPORTED, "a hybrid batch is not a compound request (slg_batch_prepare_hybrid)")
+            req = N.Request(C.sizeof(N.Request), self.nq, _ptr(q_offsets), _ptr(q_terms), _ptr(q_weights),
+                            C.addressof(plans), opt(qf), k, strategy,
+                            *[pointer(slot) for slot in ("sort", "cursors", "clauses", "phrases", "clause_tree", "fscore",
+                                                         "script", "script_order")], 0,
+                            *[pointer(slot) for slot in ("agg_spec", "top_hits_spec", "composite_spec",
+                                                         "term_bucket_spec", "rescore", "collapse")])
+            self._h = self._lib.slg_batch_prepare_request(index._h, C.addressof(req))
+        else:
+            self._h = getattr(self._lib, kinds[0].entry)(
+                index._h, self.nq, _ptr(q_offsets), _ptr(q_terms), _ptr(q_weights), C.addressof(plans), opt(qf),
+                *[pointer(slot) for slot in kinds[0].own], k, strategy)
         if not self._h:
             raise N.SlgError(N.last_error_code() or N.ERR_INVALID, N.last_error())
         index._batches.add(self)

@@ -15,13 +15,23 @@ lists, one entry per segment:
            the tree filter)
     si/sf  the i64 and the f64 sort field, value lists per doc
     xvec   the store of the extra vector field, (metric, offsets, values) or None
+    text   the stored texts of the text field, ASCII bytes per doc (built from tok; a few empty), or None: the
+           segment has no text at all (add_text_field with NULL offsets)
+    npath  the nested paths c and c.r (c.r bound to c): {"counts": {path: objects per doc}, "parents": {"c.r": the
+           parent index of every reply, or None}}, as tests/nested_ref.py takes them (add_nested_path)
+    ncol   the nested value columns c.author (keyword) and c.r.n (i64): values per object per doc (add_nested_*field)
+    ts     the i64 timestamp column of the date aggregations, 0 - 2 values per doc around the epoch
 The term filter (add_filter_terms) reads the posting lists of TERM_FILTER, the tree filter (add_filter_trees) the kw and
-num columns: their bitmaps derive from lists above.
+num columns, the nested tree (add_nested_filter_trees: NESTED_FILTER) npath, ncol and kw: their bitmaps derive from the
+lists above.  The suggester's doc frequencies derive from segs and keys; `numf`, the f64 column the composite's
+histogram source reads, is the num list registered a second time.
 
 delete / add / remove are list operations.  expect(model, kind) gives the expected result of ONE small request of a
 kind, from the CPU oracle and the existing restatements only (bool_ref, booltree_ref, phrase_ref, fscore_ref,
-script_ref, scan_ref, agg_ref, agg_values_ref, collapse_ref, rescore_ref, expand_ref, hybrid_ref, filter_ref, and the
-sort / cursor key helpers and the vector reference of the sort, cursor and vector-search tests).  request(model, kind,
+script_ref, scan_ref, agg_ref, agg_values_ref, collapse_ref, rescore_ref, expand_ref, hybrid_ref, filter_ref,
+agg_date_ref, top_hits_ref, composite_ref, term_buckets_ref, request_ref, nested_ref, regex_ref, suggest_ref,
+highlight_ref, and the sort / cursor key helpers and the vector reference of the sort, cursor and vector-search
+tests).  request(model, kind,
 ids) is the same request as the device takes it, with the ids a live index handed out.
 
 Sizes: 65, 300, 33 and 200 docs put 32 / 33, 64 / 65 and a non-multiple of 32 on the word edges of the tombstone and
@@ -40,11 +50,19 @@ from searchlite_amd import booltree as BT
 from searchlite_amd.script import compile_script
 from tests import agg_ref, agg_values_ref as V
 from tests import bool_ref as B
+from tests import agg_date_ref as D
 from tests import booltree_ref, collapse_ref, filter_ref, fscore_ref, hybrid_ref, rescore_ref, scan_ref, script_ref
+from tests import composite_ref, highlight_ref, nested_ref, request_ref, term_buckets_ref
+from tests import top_hits_ref as T
+from tests import top_hits_world as TW
+from tests import nested_world as NW
+from tests import regex_util as X
+from tests import suggest_worlds as SW
 from tests import collapse_world as CW
 from tests import expand_util as U
 from tests import phrase_ref as P
 from tests.expand_worlds import word
+from tests.test_gpu_composite import want_page as want_composite_page
 from tests.test_gpu_cursor import cursor_of, key_of, ordered_rows
 from tests.test_gpu_phrase import specs_of
 from tests.test_gpu_sort import expected_rows
@@ -72,14 +90,19 @@ CAND, K_OUT = 20, 11
 # the first seed from 20270 on whose world passes tests/test_lifecycle_world.py: with four queries, a hit of every kind
 # in every segment that a step touches and the vector kinds' near-tie gaps are what most seeds miss
 SEED = 20296
-RESOURCES = ("keys", "mask", "rcol", "num", "kw", "si", "sf", "xvec", "positions", "f_terms", "f_tree")
+RESOURCES = ("keys", "mask", "rcol", "num", "kw", "si", "sf", "xvec", "positions", "f_terms", "f_tree",
+             "text", "npath", "ncol", "ts", "f_nested")
 # canonical ids: what a fresh index hands out when everything is registered in the order of
 # tests/test_gpu_lifecycle.py: Live.register
-CANON = dict(num=0, kw=1, f_mask=0, f_range=1, f_terms=2, f_tree=3, si=0, sf=1, xvec=1)
-KINDS = ("plain", "sorted", "cursor", "bool", "tree", "phrase", "fscore", "script", "scan", "aggs", "collapse",
-         "rescore", "expand", "vector", "hybrid", "rerank")
+CANON = dict(num=0, kw=1, f_mask=0, f_range=1, f_terms=2, f_tree=3, si=0, sf=1, xvec=1,
+             ts=2, numf=3, text=0, p_c=0, p_cr=1, n_author=0, n_n=1, f_nested=4)
+# the kinds the suite was written with: the tombstone sets are drawn from THEIR hits, so they stay what they were
+OLD_KINDS = ("plain", "sorted", "cursor", "bool", "tree", "phrase", "fscore", "script", "scan", "aggs", "collapse",
+             "rescore", "expand", "vector", "hybrid", "rerank")
+KINDS = OLD_KINDS + ("date_aggs", "top_hits", "composite", "term_buckets", "request", "nested", "regex", "suggest",
+                    "highlight", "highlight_batch")
 PREPARED = ("plain", "sorted", "cursor", "bool", "tree", "phrase", "fscore", "script", "scan", "aggs", "collapse",
-            "rescore")
+            "rescore", "date_aggs", "top_hits", "composite", "term_buckets", "request")
 # what a kind reads of the registered resources (the segments themselves are read by all)
 READS = {
     "plain": (), "rescore": (),
@@ -93,15 +116,23 @@ READS = {
     "collapse": ("kw", "si"),
     "expand": ("keys",),
     "vector": ("xvec",), "hybrid": ("xvec",), "rerank": ("xvec",),
+    "date_aggs": ("ts", "num", "f_tree"),
+    "top_hits": ("kw", "si"), "composite": ("kw", "num"), "term_buckets": ("kw", "mask"),
+    "request": ("num", "mask", "kw", "si", "sf"),
+    "nested": ("npath", "ncol", "kw", "f_nested"),
+    "regex": ("keys",), "suggest": ("keys",),
+    "highlight": ("text",), "highlight_batch": ("text",),
 }
-# tombstones change no dictionary, and a rerank scores the candidates it is handed, deleted or not
-SAME_UNDER_DELETE = ("expand", "rerank")
+# tombstones change no dictionary, and a rerank scores the candidates it is handed, deleted or not; the header says
+# the same of the regex expansion ("slg_index_update_deleted keeps the dictionaries"), of the suggester
+# ("slg_index_update_deleted never changes an answer") and of the texts ("leaves them alone": host hits name their docs)
+SAME_UNDER_DELETE = ("expand", "rerank", "regex", "suggest", "highlight")
 EDGE_DOCS = (0, 31, 32, 63, 64)
 
 
 # ---- the model -------------------------------------------------------------------------------------------------
 class Model:
-    LISTS = ("segs", "tok", "keys", "mask", "rcol", "num", "kw", "si", "sf", "xvec")
+    LISTS = ("segs", "tok", "keys", "mask", "rcol", "num", "kw", "si", "sf", "xvec", "text", "npath", "ncol", "ts")
 
     def __init__(self, queries, **lists):
         self.q = queries           # what the requests are made of: the same for every state of the index
@@ -171,6 +202,7 @@ class Model:
         by_id = {CANON["kw"]: dict(kind="keyword", keys=KEYS, docs=self.kw, id=CANON["kw"]),
                  CANON["num"]: dict(kind="i64", keys=None, docs=self.num, id=CANON["num"])}
         out["f_tree"] = [filter_ref.eval_program(nodes, ords, by_id, {}, s, seg.n_docs) for s, seg in enumerate(self.segs)]
+        out["f_nested"] = [np.array(nested_ref.mask(nested_world(self, s), NESTED_FILTER), bool) for s in range(self.n_segs)]
         for name, masks in self.stale.items():  # (a bitmap list a wrong library left unshifted)
             if name in out:
                 out[name] = [fit(m, seg.n_docs) for m, seg in zip(masks, self.segs)]
@@ -179,7 +211,7 @@ class Model:
 
     def filters_by_id(self, ids=CANON):
         fm = self.filter_masks()
-        return {ids[name]: fm[name] for name in ("f_mask", "f_range", "f_terms", "f_tree")}
+        return {ids[name]: fm[name] for name in ("f_mask", "f_range", "f_terms", "f_tree", "f_nested")}
 
     def vector_fields(self):
         """[embedded store per segment, extra field per segment] as (metric, offsets, values) or None"""
@@ -217,8 +249,13 @@ def unshifted(before, seg, resource):
             np.cumsum(cnt, out=offs[1:])
             s.pos_offsets, s.positions = offs, np.resize(ps, int(offs[-1])).astype(np.uint32)
             m.segs[i] = s
-    elif resource in ("f_terms", "f_tree"):
+    elif resource in ("f_terms", "f_tree", "f_nested"):
         m.stale[resource] = keep(before.filter_masks()[resource])
+    elif resource == "npath":
+        m.npath = [{part: {p: fit(v, sg.n_docs) for p, v in old[part].items()} for part in ("counts", "parents")}
+                   for old, sg in zip(keep(before.npath), m.segs)]
+    elif resource == "ncol":
+        m.ncol = [{name: fit(v, sg.n_docs) for name, v in old.items()} for old, sg in zip(keep(before.ncol), m.segs)]
     elif resource == "keys":
         m.keys = keep(before.keys)
     elif resource == "xvec":
@@ -283,6 +320,87 @@ def make_entry(rng, n, key_words, qv, shuffle_keys=False, extra_vectors=True):
         xvec=_store(rng, n, qv[:, DIM:] if n < 100 else None, p_missing=0.3) if extra_vectors else None)
 
 
+# ---- the lists of the resources added since: a random stream of their own, so that every draw above stays what it was
+MORE_SEED = 20261020
+DAY = 86_400_000
+AUTHORS = ["a0", "a1", "a2"]
+NESTED_KEY = 5                       # the doc-level leaf of the nested tree: kw == KEYS[NESTED_KEY]
+N_LO, N_HI = -1, 2                   # ... and its innermost leaf: a reply's n in [N_LO, N_HI]
+NESTED_FILTER = NW.AND(NW.nest("c", NW.keq("author", "a0")), NW.nest("c", NW.nest("r", NW.i64("n", N_LO, N_HI))),
+                       NW.keq("kw", KEYS[NESTED_KEY]))
+NESTED_KINDS = {"kw": "keyword", "c.author": "keyword", "c.r.n": "i64"}
+TEXTLESS = 3                         # the segment whose text field has no text at all (NULL offsets)
+SEPARATORS = (" ", " ", ", ", " - ", ". ")
+
+
+def tword(t):
+    """the word a token id stands for in the stored texts (one vocabulary for every segment)"""
+    return word(int(t))
+
+
+def text_of(rng, tokens):
+    """a doc's stored text: its token sequence as words, some capitalised (the match folds ASCII case), with mixed
+    separators between them"""
+    words = [tword(t).capitalize() if rng.random() < 0.2 else tword(t) for t in tokens]
+    out = words[0]
+    for w in words[1:]:
+        out += SEPARATORS[int(rng.integers(0, len(SEPARATORS)))] + w
+    return out.encode("ascii")
+
+
+def crosses_a_word(counts):
+    """the docs whose object range [first, first + count) lies in two 32-bit words of the object bitmap"""
+    first = np.concatenate([[0], np.cumsum(counts)[:-1]])
+    return [d for d, (f, c) in enumerate(zip(first, counts)) if c and f // 32 != (f + c - 1) // 32]
+
+
+def make_more(rng, n, tok, kw, textless=False):
+    """the lists of one segment for the text field, the two nested paths (c, and c.r bound to it), the two nested
+    columns (c.author keyword, c.r.n i64) and the timestamp column.  Object counts per doc come from {0, 1, 2, 5}; in
+    a segment of 64 docs or more some doc's objects cross a 32-bit word.  The docs whose kw is KEYS[NESTED_KEY] mostly
+    hold an object that passes the nested leaves (a0, with a reply bound to it whose n is in range): the tree then
+    passes a few docs of every segment, and every other doc fails it"""
+    pick = lambda: int((0, 1, 2, 5)[int(rng.integers(0, 4))])
+    while True:
+        c = [pick() for _ in range(n)]
+        if n < 64 or crosses_a_word(c):
+            break
+    r = [pick() for _ in range(n)]
+    parents, author, nn = [], [], []
+    for d in range(n):
+        row = [None if rng.random() < 0.1 or c[d] == 0 else int(rng.integers(0, c[d])) for _ in range(r[d])]
+        a = [[AUTHORS[int(rng.integers(0, len(AUTHORS)))]] if rng.random() < 0.8 else [] for _ in range(c[d])]
+        v = [[int(rng.integers(-4, 5))] if rng.random() < 0.8 else [] for _ in range(r[d])]
+        if kw[d] == [NESTED_KEY] and (rng.random() < 0.9 or d in EDGE_DOCS):
+            c[d], r[d] = max(c[d], 1), max(r[d], 1)
+            a, row, v = (a or [[]]), (row or [None]), (v or [[]])
+            o = int(rng.integers(0, c[d]))
+            a += [[] for _ in range(c[d] - len(a))]
+            a[o], row[-1], v[-1] = ["a0"], o, [int(rng.integers(N_LO, N_HI + 1))]
+        for objs in (a, v):                               # padded only up to the last object that had a value
+            while objs and not objs[-1]:
+                objs.pop()
+        parents.append(row)
+        author.append(a)
+        nn.append(v)
+    if n >= 64 and not crosses_a_word(c):                 # (the forced objects moved the ranges: draw again)
+        return make_more(rng, n, tok, kw, textless)
+    ts = []
+    for d in range(n):
+        u = rng.random()
+        ts.append([] if u < 0.1 else [int(x) for x in rng.integers(-40 * DAY, 40 * DAY, 2 if u < 0.2 else 1)])
+    ts[1], ts[2] = [-1], [0, 31 * DAY]                    # the last ms of 1969 and the first of 1970 and of its February
+    text = None if textless else [b"" if d % 13 == 5 else text_of(rng, tok[d]) for d in range(n)]
+    return dict(text=text, ts=ts, npath=dict(counts={"c": c, "c.r": r}, parents={"c.r": parents}),
+                ncol={"c.author": author, "c.r.n": nn})
+
+
+def nested_world(m, s):
+    """segment s as tests/nested_ref.py takes it"""
+    return {"n_docs": int(m.segs[s].n_docs), "kinds": NESTED_KINDS, "doc": {"kw": [[KEYS[o] for o in d] for d in m.kw[s]]},
+            "counts": m.npath[s]["counts"], "parents": m.npath[s]["parents"], "nested": m.ncol[s]}
+
+
 def merge_entries(a, b):
     """the segment a compaction writes for a and b: the docs of a, then the docs of b, tombstones gone (every
     per-doc resource concatenated; the postings keep the token ids, so the dictionary is a's, key by term id)"""
@@ -303,7 +421,13 @@ def merge_entries(a, b):
         return (x or y)[0], np.concatenate([xo, yo]), np.concatenate([xv, yv]).astype(F32)
 
     nb = b["segs"].n_docs
+    texts = lambda e, n: [b""] * n if e["text"] is None else e["text"]
+    more = dict(
+        text=None if a["text"] is None and b["text"] is None else texts(a, na) + texts(b, nb), ts=a["ts"] + b["ts"],
+        npath={part: {p: a["npath"][part][p] + b["npath"][part][p] for p in a["npath"][part]} for part in ("counts", "parents")},
+        ncol={name: a["ncol"][name] + b["ncol"][name] for name in a["ncol"]})
     return dict(
+        more,
         segs=segment_of(tok, cat_store(ea, eb, nb)), tok=tok,
         keys=list(a["keys"]),
         mask=np.concatenate([a["mask"], b["mask"]]), rcol=np.concatenate([a["rcol"], b["rcol"]]),
@@ -346,6 +470,9 @@ def build(seed=SEED):
         entries = [make_entry(rng, n, pools[i], queries["qv"], shuffle_keys=i == 1, extra_vectors=i != 1)
                    for i, n in enumerate(SIZES)]
         fifth = make_entry(rng, FIFTH, pools[-1], queries["qv"])
+        more = np.random.default_rng(MORE_SEED)   # (the new lists draw from a stream of their own)
+        for i, e in enumerate(entries + [fifth]):
+            e.update(make_more(more, e["segs"].n_docs, e["tok"], e["kw"], textless=i == TEXTLESS))
         # the first and the last segment each hold an end of the numeric column's value range alone: removing one
         # shrinks the dense id range of a histogram over the column (what the field records of its values must follow)
         entries[0]["num"][5], entries[3]["num"][7] = [90], [-90]
@@ -362,7 +489,7 @@ def _with_hits(m, seg, docs, oracle):
     """docs plus, for every kind a delete must show in, the first doc of segment `seg` among the rows its device
     check compares: the tombstones then remove a current hit of every kind"""
     out = set(docs)
-    for kind in KINDS:
+    for kind in OLD_KINDS:   # (the kinds added since show a delete through these docs: tests/test_lifecycle_world.py)
         if kind in SAME_UNDER_DELETE:
             continue
         hit = [d for s, d in hit_docs(m, kind, oracle) if s == seg]
@@ -546,9 +673,175 @@ def rerank_fields(m):
             for metric, stores in zip((0, 0), m.vector_fields())]
 
 
+# a calendar-month date_histogram with a stats child, a date_range whose bounds are the epoch and the first of
+# February 1970, and a filter aggregation over the registered tree filter
+DATE_AGGS = {"h": {"type": "date_histogram", "field": "ts", "calendar_interval": "month",
+                   "aggs": {"s": {"type": "stats", "field": "num"}}},
+             "r": {"type": "date_range", "field": "ts",
+                   "ranges": [{"to": "1970-01-01T00:00:00Z"}, {"from": "0", "to": "1970-02-01T00:00:00Z"},
+                              {"from": "1970-02-01T00:00:00Z"}]},
+             "f": {"type": "filter", "filter": {"name": "f_tree"}}}
+
+
+def date_plan(ids, request=DATE_AGGS):
+    return A.agg_spec(request, {"ts": {"id": ids["ts"]}, "num": {"id": ids["num"]},
+                                  A.FILTERS: lambda body: ids[body["name"]]})
+
+
+def date_columns(m):
+    return {"ts": m.ts, "num": m.num}
+
+
+def nested_program(ids):
+    """the nested tree as slg_index_add_nested_filter_trees takes it, compiled against the ids of a live index"""
+    from searchlite_amd.filters import compile_nested_filter
+    fields = {"kw": {"id": ids["kw"], "kind": "keyword", "keys": KEYS}}
+    nested = {"paths": {"c": {"id": ids["p_c"]}, "c.r": {"id": ids["p_cr"]}},
+              "fields": {"c.author": {"id": ids["n_author"], "path": "c", "kind": "keyword", "keys": AUTHORS},
+                         "c.r.n": {"id": ids["n_n"], "path": "c.r", "kind": "i64", "keys": None}}}
+    return compile_nested_filter(NESTED_FILTER, fields, nested)
+
+
+def nested_arrays(m):
+    """what add_nested_path (c, then c.r) and add_nested_keyword_field / add_nested_field take, per segment"""
+    worlds = [nested_world(m, s) for s in range(m.n_segs)]
+    for w in worlds:   # (top-level objects carry no parent list: the path is registered with counts alone)
+        assert "c" not in w["parents"]
+    return dict(c=[NW.path_arrays(w, "c") for w in worlds], cr=[NW.path_arrays(w, "c.r") for w in worlds],
+                author=[NW.column_arrays(w, "c.author", AUTHORS) for w in worlds],
+                n=[NW.column_arrays(w, "c.r.n") for w in worlds])
+
+
+def regex_requests(m):
+    """one regex per query over the dictionaries: a class after a literal prefix, one of the expansion's own words
+    with its last letter open, a suffix (no literal prefix: the whole field is scanned) and an alternation"""
+    w0, _ = m.q["x_words"]
+    return [X.regex("body", "aa[a-b].*", 50), X.regex("body", w0[:3] + ".", 50), X.regex("body", ".*b", 7),
+            X.regex("body", "aab[a-m]|aac.+", 50)]
+
+
+def suggest_requests(m):
+    """a plain prefix and a fuzzy completion: their scores are sums of per-segment doc frequencies"""
+    from searchlite_amd.searcher import suggest_request
+    return [suggest_request("body", "aab", 5), suggest_request("body", m.q["x_words"][0], 5, {})]
+
+
+def suggest_segments(m):
+    """per segment [(key, doc frequency)] in term-id order, as tests/suggest_worlds.py: World takes them"""
+    return [[(k, int(seg.df(t))) for t, k in enumerate(keys)] for seg, keys in zip(m.segs, m.keys)]
+
+
+def highlight_specs(m, field):
+    """per query one spec: the query's third term as a word (of the three positions the one with which every state
+    of every scenario has a fragment among the plain batch's rows of each touched segment: the 65-doc segment is down
+    to ONE such row after the delete scenario's second step) and its phrase pair as a two-word phrase"""
+    from searchlite_amd.highlight import highlight_spec
+    q = m.q
+    return [[highlight_spec(field, [tword(hl_term(m, i))], [[tword(a), tword(b)]], pre_tag="<b>",
+                            post_tag="</b>", fragment_size=24, number_of_fragments=2)]
+            for i, (a, b) in enumerate(q["p_terms"])]
+
+
+def hl_term(m, i):
+    return int(m.q["terms"][int(m.q["offs"][i]) + 2])
+
+
+def highlight_hits(m):
+    """host hits that no tombstone moves: per query and segment, in the order of the rerank kind's permutation, the
+    first 4 docs whose tokens hold the spec's term and the first 2 that do not"""
+    out = []
+    for i in range(NQ):
+        t, hits = hl_term(m, i), []
+        for s, n in enumerate(m.n_docs()):
+            docs = [int(x) for x in m.q["cand_perm"][i] if x < n]
+            hits += [(s, d) for d in [d for d in docs if t in m.tok[s][d]][:4] + [d for d in docs if t not in m.tok[s][d]][:2]]
+        out.append(hits)
+    return out
+
+
+def highlight_items(m, hits, specs):
+    """result[q][hit][spec] of tests/highlight_ref.py; a segment without the field's store: SLG_HL_NO_TEXT"""
+    return [[[(N.HL_NO_TEXT, []) if m.text[s] is None else (N.HL_OK, highlight_ref.highlight_spec_ref(m.text[s][d], sp))
+              for sp in specs[q]] for s, d in hq] for q, hq in enumerate(hits)]
+
+
+# top_hits: a root node, and a node under a terms parent on kw (a list per key: the many-lists path) sorted by si
+TOP_HITS = {"root": {"type": "top_hits", "size": 3, "from": 0, "sort": []},
+            "by_kw": {"type": "terms", "field": "kw",
+                      "aggs": {"best": {"type": "top_hits", "size": 2, "from": 0, "sort": [{"field": "si", "order": "asc"}]}}}}
+# composite: a terms source on kw and a histogram source on num, fewer buckets a page than there are tuples.  The
+# header refuses a histogram source over a column registered as i64 ("the reference reads f64 columns only"), so the
+# source reads `numf`: the num list registered a second time, as f64 (num_as_f64)
+COMPOSITE = {"type": "composite", "size": 4,
+             "sources": [{"type": "terms", "name": "kw", "field": "kw"},
+                         {"type": "histogram", "name": "num", "field": "numf", "interval": 40}]}
+# significant_terms with f_mask as the background filter, and rare_terms.  size = the number of keys and a
+# max_doc_count no key exceeds: nothing is truncated or dropped per segment, so term_buckets_ref's per-segment mode
+# (the reference, literally) and its all-segment mode (the device's counting) give the same buckets; the background
+# counts are in both the sums over the segments in whose foreground the key occurs, of docs that are alive and pass
+TERM_BUCKETS = {"sig": {"type": "significant_terms", "field": "kw", "size": len(KEYS), "background_filter": {"name": "f_mask"}},
+                "rare": {"type": "rare_terms", "field": "kw", "size": len(KEYS), "max_doc_count": 100000}}
+
+
+def collector_fields(ids):
+    """the `fields` of aggs.agg_spec for the collectors' requests"""
+    return {"kw": {"id": ids["kw"], "keys": KEYS}, "num": {"id": ids["num"]}, "numf": {"id": ids["numf"]}, "si": {"sort_id": ids["si"]},
+            A.FILTERS: lambda body: ids[body["name"]]}
+
+
+def num_as_f64(m):
+    return [[[float(v) for v in d] for d in seg] for seg in m.num]
+
+
+def top_hits_plan(ids):
+    return A.agg_spec(TOP_HITS, collector_fields(ids))
+
+
+def composite_plan(ids):
+    return A.agg_spec({"cmp": COMPOSITE}, collector_fields(ids))
+
+
+def term_buckets_plan(ids):
+    return A.agg_spec(TERM_BUCKETS, collector_fields(ids))
+
+
+# the compound request: the bool clause, function_score, the field sort, a terms aggregation and collapse
+REQUEST_AGGS = {"t": {"type": "terms", "field": "kw", "aggs": {"s": {"type": "stats", "field": "num"}}}}
+
+
+def compound_request(m, ids):
+    return dict(clauses=B.clauses_of(bool_queries(), m.n_segs), fscore=fscore_functions(ids), sort=sort_ids(SORT, ids),
+                aggs=A.agg_spec(REQUEST_AGGS, collector_fields(ids)),
+                collapse=dict(COLLAPSE, field=ids["kw"], inner_sort=sort_ids(INNER_SORT, ids)))
+
+
 def request(m, kind, ids=CANON):
     """the request of `kind` as the device takes it -> dict of keyword arguments (see tests/test_gpu_lifecycle.py)"""
     Q = text_queries(m)
+    if kind == "top_hits":
+        return dict(q=Q, k=K, aggs=top_hits_plan(ids))
+    if kind == "composite":
+        return dict(q=Q, k=K, aggs=composite_plan(ids))
+    if kind == "term_buckets":
+        return dict(q=Q, k=K, aggs=term_buckets_plan(ids))
+    if kind == "request":
+        return dict(compound_request(m, ids), q=Q, k=K)
+    if kind == "date_aggs":
+        return dict(q=Q, k=K, aggs=date_plan(ids))
+    if kind == "nested":
+        qs, _ = scan_queries(ids)
+        return dict(filter=ids["f_nested"],
+                    bool=dict(q=Q, k=K, clauses=B.clauses_of(bool_queries(), m.n_segs),
+                              q_filter=np.full(NQ, ids["f_nested"], np.int32)),
+                    scan=dict(queries=qs, k=K, q_filter=np.full(len(qs), ids["f_nested"], np.int32)))
+    if kind == "regex":
+        return dict(requests=regex_requests(m))
+    if kind == "suggest":
+        return dict(requests=suggest_requests(m))
+    if kind == "highlight":
+        return dict(hits=highlight_hits(m), specs=highlight_specs(m, ids["text"]))
+    if kind == "highlight_batch":
+        return dict(q=Q, k=K_PLAIN, specs=highlight_specs(m, ids["text"]))
     if kind == "plain":
         return dict(q=Q, k=K_PLAIN)
     if kind == "sorted":
@@ -626,13 +919,14 @@ def alive_filters(m, ids=CANON):
 
 def without_registration(m, seg):
     """the model as the device sees segment `seg` between slg_index_add_segment and the second registration, for
-    the kinds the header gives an answer (not a refusal) there: no positions (no phrase holds a doc of it) and no
-    vectors in the extra field"""
+    the kinds the header gives an answer (not a refusal) there: no positions (no phrase holds a doc of it), no
+    vectors in the extra field and no store in the text field"""
     out = m.clone()
     s = copy.copy(out.segs[seg])
     s.pos_offsets = s.positions = None
     out.segs[seg] = s
     out.xvec[seg] = None
+    out.text[seg] = None          # (and no text: SLG_HL_NO_TEXT for its hits)
     return out
 
 
@@ -644,7 +938,85 @@ def expect(m, kind, oracle=None):
     return m._memo[kind]
 
 
+def _expect_more(m, kind, oracle):
+    """the kinds added since, from agg_date_ref, nested_ref (through filter_masks), regex_ref, suggest_ref and
+    highlight_ref"""
+    Q = text_queries(m)
+    segs = m.segs
+    if kind == "date_aggs":
+        plan, cols = date_plan(CANON), date_columns(m)
+        doc, seg, _, count = all_hits(m, oracle)
+        docs = [[(int(seg[q, i]), int(doc[q, i])) for i in range(int(count[q]))] for q in range(len(count))]
+        layout = D.ref_layout(plan.nodes, cols, KEYS_OF)
+        states = [D.run(DATE_AGGS, cols, m.filter_masks(), d) for d in docs]
+        per_q = [D.dense(plan.nodes, layout, st, KEYS_OF) for st in states]
+        tables = [np.stack([t[i] for t in per_q]) for i in range(len(plan.nodes))]
+        return dict(want=(layout, tables, {q: D.respond(DATE_AGGS, st) for q, st in enumerate(states)}), docs=docs,
+                    rows=oracle.search_batch(segs, *Q, K, strategy=oracle.BM25))
+    if kind == "nested":
+        r = request(m, kind)
+        filters = m.filters_by_id()
+        world = dict(n_docs=m.n_docs(), deleted=[None if s.deleted is None else m.dead(i) for i, s in enumerate(segs)],
+                     filters=filters, fields={CANON["num"]: m.num})
+        assert not scan_ref.unsafe_docs(r["scan"]["queries"], world)
+        rows, matched, _ = scan_ref.search(r["scan"]["queries"], world, K, r["scan"]["q_filter"])
+        return dict(bitmaps=alive_filters(m)[CANON["f_nested"]],
+                    bool=B.reference(oracle, segs, *Q, K, r["bool"]["clauses"], q_filter=r["bool"]["q_filter"], filters=filters),
+                    scan=dict(rows=rows, matched=matched))
+    if kind in ("top_hits", "composite", "term_buckets"):
+        cols = agg_columns(m)
+        hits = TW.hits_of(all_hits(m, oracle))
+        docs = [[(s, d) for s, d, _ in h] for h in hits]
+        out = dict(matched=[len(h) for h in hits], rows=oracle.search_batch(segs, *Q, K, strategy=oracle.BM25))
+        if kind == "top_hits":
+            plan = top_hits_plan(CANON)
+            layout = D.ref_layout(plan.nodes, cols, KEYS_OF)
+            lists, totals = T.expected(TW.ref_nodes(TOP_HITS, plan, layout), layout, hits, cols, m.filter_masks(), KEYS_OF,
+                                       sort_fields(m))
+            return dict(out, lists=lists, totals=totals)
+        if kind == "composite":
+            world = dict(cols=dict(cols, numf=num_as_f64(m)), masks={})
+            buckets = [composite_ref.collect(COMPOSITE["sources"], world["cols"], ("numf",), d) for d in docs]
+            first = [want_composite_page(world, COMPOSITE, b, None) for b in buckets]
+            afters = [p.get("after_key") for p in first]
+            second = [{"type": "composite", "buckets": []} if a is None else want_composite_page(world, COMPOSITE, b, a)
+                      for b, a in zip(buckets, afters)]
+            return dict(out, pages=[first, second], afters=afters, tuples=[len(b) for b in buckets])
+        dead = [None if s.deleted is None else set(int(d) for d in np.nonzero(m.dead(i))[0]) for i, s in enumerate(segs)]
+        return dict(out, cols=cols, masks=m.filter_masks(),
+                    nodes={name: [term_buckets_ref.respond(body, cols, m.n_docs(), dead, m.filter_masks(), d, True) for d in docs]
+                           for name, body in TERM_BUCKETS.items()})
+    if kind == "request":
+        cands = fscore_ref.all_candidates(oracle, segs, *Q)
+        cols = fscore_ref.Columns(segs, {CANON["num"]: (m.num, np.dtype(np.int64))}, m.filters_by_id())
+        r = compound_request(m, CANON)
+        ms = request_ref.matched_sets(cands, segs, NQ, ("bool", r["clauses"]),
+                                      request_ref.chains_of(NQ, fscore_functions(CANON)), cols)
+        rows = request_ref.ordered(ms["rows"], SORT, sort_fields(m))
+        page = request_ref.as_arrays(rows, K)
+        return dict(page=page, matched=ms["matched"], sets=ms["rows"],
+                    aggs=request_ref.agg_tables(REQUEST_AGGS, r["aggs"].nodes, agg_columns(m), m.filter_masks(), KEYS_OF, ms["rows"]),
+                    collapse=request_ref.collapse_arrays(page, m.kw, dict(COLLAPSE, inner_sort=INNER_SORT), SORT, sort_fields(m)))
+    if kind == "regex":
+        world = X.World(m.keys)
+        return [world.want(r) for r in regex_requests(m)]
+    if kind == "suggest":
+        world = SW.World(suggest_segments(m))
+        return [world.want(r) for r in suggest_requests(m)]
+    if kind == "highlight":
+        hits = highlight_hits(m)
+        return highlight_items(m, hits, highlight_specs(m, CANON["text"]))
+    if kind == "highlight_batch":
+        rows = oracle.search_batch(segs, *Q, K_PLAIN, strategy=oracle.BM25)
+        doc, seg, _, count = rows
+        hits = [[(int(seg[q, i]), int(doc[q, i])) for i in range(int(count[q]))] for q in range(len(count))]
+        return dict(rows=rows, items=highlight_items(m, hits, highlight_specs(m, CANON["text"])))
+    raise ValueError(kind)
+
+
 def _expect(m, kind, oracle):
+    if kind not in OLD_KINDS:
+        return _expect_more(m, kind, oracle)
     Q = text_queries(m)
     segs = m.segs
     if kind == "plain":
@@ -769,6 +1141,13 @@ def checked_part(m, kind, want):
         return [(w["rows"], w["total"]) for w in want]
     if kind == "rerank":
         return want["rows"]
+    if kind == "date_aggs":
+        return dict(want=want["want"], rows=want["rows"], matched=[len(d) for d in want["docs"]])
+    if kind == "term_buckets":
+        return dict(nodes={n: [term_buckets_ref.strip(r) for r in rs] for n, rs in want["nodes"].items()},
+                    rows=want["rows"], matched=want["matched"])
+    if kind == "request":
+        return {n: v for n, v in want.items() if n != "sets"}
     return want
 
 

@@ -287,10 +287,15 @@ def test_tie_breaker_outside_unit_interval_is_rejected(gpu):
 
 
 def _detach_world(gpu):
-    """the index of test_index_closed_before_its_batches with a sort field, a numeric and a keyword column"""
+    """the index of test_index_closed_before_its_batches with a sort field, a numeric and a keyword column, positions
+    (every posting's occurrences at 0 .. tf - 1) and a text field"""
     n = 800
     seg = random_segment(np.random.default_rng(6), n, 20, 10)
     ix = gpu.GpuIndex([seg])
+    pos_offsets = np.zeros(len(seg.tfs) + 1, np.uint64)
+    np.cumsum(seg.tfs, out=pos_offsets[1:])
+    ix.set_positions(0, pos_offsets, np.concatenate([np.arange(t, dtype=np.uint32) for t in seg.tfs]))
+    ix.add_text_field([[b"one two three two one" if d % 5 else b"" for d in range(n)]])   # (text field 0)
     rows = np.arange(n + 1, dtype=np.uint32)
     sort_id = ix.add_sort_field([(rows, (np.arange(n) * 7919 % 101).astype(np.int64))], np.int64)
     num_id = ix.add_agg_field([(rows, (np.arange(n) % 13).astype(np.float64))], np.float64)
@@ -298,9 +303,56 @@ def _detach_world(gpu):
     return seg, ix, sort_id, num_id, kw_id
 
 
-# the kinds whose batches hold d_sort_cols, d_matched, d_cursor or d_seen, a hybrid batch and a batch that ran sharded
+# the kinds whose batches hold d_sort_cols, d_matched, d_cursor or d_seen, a hybrid batch and a batch that ran sharded;
+# then one batch of every other kind that holds buffers of its own (clause tables, phrase specs, function and script
+# programs, the rescore queries, the collectors' tables), a compound request, and a plain batch that highlighted its rows
 DETACH_KINDS = ["plain", "sorted", "cursor_score", "cursor_sorted", "aggs", "scan_sorted_aggs", "collapse_cursor",
-                "hybrid", "sharded"]
+                "hybrid", "sharded", "phrase", "bool", "tree", "fscore", "script", "rescore", "top_hits", "composite",
+                "term_buckets", "request", "highlight"]
+
+
+def _detach_more(kind, offs, terms, w, sort, stats, num_id, kw_id):
+    """the keyword arguments of prepare() / prepare_request() for the kinds added to DETACH_KINDS"""
+    from searchlite_amd import aggs as AG
+    from searchlite_amd import booltree
+    from searchlite_amd.script import compile_script
+    from tests import bool_ref as B
+    from tests import phrase_ref as P
+    from tests.test_gpu_phrase import specs_of
+    nq = len(offs) - 1
+    keys = {"kw": {"id": kw_id, "keys": [f"k{i}" for i in range(9)]}}
+    clauses = lambda: B.clauses_of([([(B.MUST, [q % 4]), (B.SHOULD, [4 + q % 3]), (B.MUST_NOT, [8 + q % 2])], 0)
+                                    for q in range(nq)], 1)
+    if kind == "phrase":
+        cl, ph = specs_of([([], [(P.MUST, 2, [[q % 5, (q + 1) % 5]])], 0) for q in range(nq)], 1)
+        return dict(clauses=cl, phrases=ph)
+    if kind == "bool":
+        return dict(clauses=clauses())
+    if kind == "tree":
+        return dict(clause_tree=booltree.compile_matchers(
+            [{"bool": {"must": [{"term": [q % 3]}], "should": [{"term": [4]}, {"dis_max": [{"term": [6]}, {"term": [7]}]}]}}
+             for q in range(nq)], 1))
+    if kind == "fscore":
+        fvf = dict(kind="field_value_factor", field=num_id, modifier="sqrt", factor=0.5, missing=2.0)
+        return dict(fscore=[dict(functions=[fvf, dict(kind="weight", weight=1.5)], score_mode="sum", boost_mode="sum")] * nq)
+    if kind == "script":
+        return dict(script=[dict(program=compile_script("_score * 2 + num / 4", None, {"num": num_id}), boost=1.0)] * nq)
+    if kind == "rescore":
+        return dict(rescore=dict(q_offsets=offs, q_terms=terms, q_weights=w, window=np.full(nq, 7, np.uint32),
+                                 mode=np.zeros(nq, np.int32)))
+    if kind == "top_hits":
+        return dict(aggs=AG.agg_spec({"root": {"type": "top_hits", "size": 3, "from": 0, "sort": []},
+                                      "t": {"type": "terms", "field": "kw", "aggs": {"best": {"type": "top_hits", "size": 2}}}}, keys))
+    if kind == "composite":
+        return dict(aggs=AG.agg_spec({"cmp": {"type": "composite", "size": 4,
+                                              "sources": [{"type": "terms", "name": "kw", "field": "kw"}]}}, keys))
+    if kind == "term_buckets":
+        return dict(aggs=AG.agg_spec({"sig": {"type": "significant_terms", "field": "kw", "size": 4},
+                                      "rare": {"type": "rare_terms", "field": "kw", "size": 3, "max_doc_count": 1000}}, keys))
+    if kind == "request":
+        return dict(clauses=clauses(), sort=sort, aggs=stats(), collapse=dict(field=kw_id, group_limit=3, inner_size=2))
+    assert kind == "highlight"
+    return {}
 
 
 @pytest.mark.parametrize("kind", DETACH_KINDS)
@@ -317,6 +369,9 @@ def test_index_closed_before_its_batches(gpu, kind):
     group = None
     if kind == "scan_sorted_aggs":
         b = ix.prepare_scan([{"match_all": {}}] * 4, 5, sort=sort, aggs=stats())
+    elif kind in DETACH_KINDS[9:]:
+        more = _detach_more(kind, offs, terms, w, sort, stats, num_id, kw_id)
+        b = (ix.prepare_request if kind == "request" else ix.prepare)(offs, terms, w, 5, **more)
     else:
         kw = {"plain": {}, "sorted": dict(sort=sort), "cursor_score": dict(cursors=[None] * 4),
               "cursor_sorted": dict(cursors=[None] * 4, sort=sort), "aggs": dict(aggs=stats()),
@@ -329,6 +384,10 @@ def test_index_closed_before_its_batches(gpu, kind):
         group.close()  # (a group goes before its index)
     b.run()
     b.fetch()
+    if kind == "highlight":   # (slg_batch_highlight from the batch's device rows: what it allocates is the batch's to free)
+        from searchlite_amd.highlight import highlight_spec
+        got = b.highlight([[highlight_spec(0, ["two"], [["one", "two"]])]] * 4)
+        assert any(frags for q in got for item in q for _, frags in item)
     facts = b.info()
     # through the raw ABI: destroy the index first, then use and destroy the batch
     lib = N.load()

@@ -4,13 +4,16 @@ reshape_per_segment, finish_state, slg_index_update_deleted / _add_segment / _re
 Every scenario starts from a fresh four-segment index (tuning updatable = 1) with everything of
 tests/lifecycle_world.py registered: positions and a dictionary per segment, a ranked numeric column, a keyword column,
 one filter from each of the four constructors, an i64 and an f64 sort field, the embedded vector store and an extra
-vector field.  The steps go to the live index and to the model together, and at each checkpoint EVERY kind of request
+vector field, and what was added since: a text field (one segment without text), two nested paths (two levels), a
+nested keyword and a nested i64 column, a nested filter tree, a timestamp column.  The steps go to the live index and to the model together, and at each checkpoint EVERY kind of request
 is checked two ways:
 
   (a) against lifecycle_world.expect(model, kind) with the comparison helper of the kind's own test module, at that
       module's bar: integers and f32 bit patterns exactly (plain, sorted, cursor, bool, tree, phrase, fscore, script,
-      scan, aggs, collapse, rescore, expand), test_gpu_vector_search.check / test_gpu_hybrid.check /
-      tests.util.check_rerank_result for the vector kinds.  No tolerance is introduced here;
+      scan, aggs, collapse, rescore, expand; date_aggs, top_hits, composite page one and two, term_buckets, the compound
+      request, the nested tree as bitmap / q_filter / scan filter, regex, suggest, highlight from host hits and from a
+      batch), test_gpu_vector_search.check / test_gpu_hybrid.check / tests.util.check_rerank_result for the vector
+      kinds.  No tolerance is introduced here;
   (b) bit for bit against a TWIN: a new GpuIndex over the model's current segment list with every resource
       registered from scratch — the header's contract ("bit-identical to a fresh slg_index_create on the updated
       descriptor").
@@ -25,7 +28,16 @@ Where to find what (resource x step -> test):
   batches keep their state  test_prepared_batches_keep_their_state[remove|add]
 and every checkpoint of every test runs all kinds, so each resource (filters of the four constructors, sort columns,
 numeric column and ranks, keyword column, positions, dictionaries, extra vector field, embedded store, d_doc_base,
-deleted) has a consumer at each of them: lifecycle_world.READS."""
+deleted) has a consumer at each of them: lifecycle_world.READS.  The resources added since, and who reads them:
+  text field (TextFieldHost::per_seg, d_tsegs)      highlight, highlight_batch; NO_TEXT after add: test_add; a retired
+                                                    state's texts and rows: test_prepared_batches_keep_their_state
+  nested paths and columns, the nested tree         nested (check_filters: its bitmap takes new tombstones with no
+                                                    second registration); refusals after add: test_add
+  timestamp column                                  date_aggs (with num under it and the tree filter as a source)
+  suggest table (d_suggest_segs), dictionaries      suggest, regex; refused after add until set_terms: test_add
+  keyword / numeric / sort columns, bitmap filter   top_hits, composite (after-key kept across an update:
+                                                    test_prepared...), term_buckets (background counted at prepare:
+                                                    test_prepared...[remove]), request"""
 import copy
 
 import numpy as np
@@ -33,6 +45,12 @@ import pytest
 
 from tests import collapse_ref
 from tests import lifecycle_world as W
+from tests import suggest_ref
+from tests import top_hits_ref
+from tests.test_gpu_composite import assert_same_response as same_composite, check_raw as check_composite_raw
+from tests.test_gpu_request import check_aggs as check_request_aggs
+from tests.test_gpu_term_buckets import check_node as check_term_bucket_node
+from tests.test_gpu_agg_date import check as check_date_tables
 from tests.test_gpu_agg_values import check_value_tables
 from tests.test_gpu_bool import same
 from tests.test_gpu_collapse import same_rows
@@ -87,9 +105,35 @@ class Live:
         ids["si"] = ix.add_sort_field(m.si, np.int64)
         ids["sf"] = ix.add_sort_field(m.sf, np.float64)
         ids["xvec"] = ix.add_vector_field(m.xvec)
+        # the resources added since, behind the others: the ids above keep their values
+        ids["ts"] = ix.add_agg_field(m.ts, np.int64)
+        ids["numf"] = ix.add_agg_field(W.num_as_f64(m), np.float64)   # (the composite's histogram source reads f64)
+        ids["text"] = ix.add_text_field(m.text)
+        self.register_nested(m, ("p_c", "p_cr"), ("n_author", "n_n"))
+        ids["f_nested"], = ix.add_nested_filter_trees([W.nested_program(ids)])
+
+    def register_nested(self, m, paths, fields):
+        """the nested paths (c, then c.r under it) and the nested columns, any part of them"""
+        ix, ids, arrays = self.ix, self.ids, W.nested_arrays(m)
+        if "p_c" in paths:
+            ids["p_c"] = ix.add_nested_path(arrays["c"])
+        if "p_cr" in paths:
+            ids["p_cr"] = ix.add_nested_path(arrays["cr"], ids["p_c"])
+        if "n_author" in fields:
+            ids["n_author"] = ix.add_nested_keyword_field(ids["p_c"], arrays["author"], len(W.AUTHORS))
+        if "n_n" in fields:
+            ids["n_n"] = ix.add_nested_field(ids["p_cr"], arrays["n"], np.int64)
 
     def unregister(self):
         """(a vector field has no removal: the second registration adds a new one)"""
+        self.ix.remove_filter(self.ids["f_nested"])
+        for name in ("n_author", "n_n"):
+            self.ix.remove_nested_field(self.ids[name])
+        for name in ("p_cr", "p_c"):
+            self.ix.remove_nested_path(self.ids[name])
+        self.ix.remove_text_field(self.ids["text"])
+        for name in ("ts", "numf"):
+            self.ix.remove_agg_field(self.ids[name])
         for name in FILTERS:
             self.ix.remove_filter(self.ids[name])
         for name in ("si", "sf"):
@@ -122,6 +166,8 @@ class Live:
 def prepare(ix, kind, req):
     if kind == "scan":
         return ix.prepare_scan(req["queries"], req["k"], q_filter=req["q_filter"])
+    if kind == "request":
+        return ix.prepare_request(*req["q"], req["k"], **{n: v for n, v in req.items() if n not in ("q", "k")})
     return ix.prepare(*req["q"], req["k"], **{n: v for n, v in req.items() if n not in ("q", "k")})
 
 
@@ -131,13 +177,48 @@ def collect(kind, b):
         out += (b.matched_counts(),)
     elif kind == "cursor":
         out += (b.matched_counts(), b.cursor_seen())
-    elif kind == "aggs":
+    elif kind in ("aggs", "date_aggs"):
         out += (b.matched_counts(), b.aggs(), b.agg_layout())
+    elif kind == "top_hits":
+        out += (b.matched_counts(), b.top_hits(), b.aggs(), b.top_hits_layout())
+    elif kind == "composite":
+        out += (b.matched_counts(),) + composite_pages(b)
+    elif kind == "term_buckets":
+        out += (b.matched_counts(), b.term_buckets(), b.term_buckets_layout())
+    elif kind == "request":
+        out += (b.matched_counts(), b.aggs(), b.agg_layout(), b.collapse_groups())
     elif kind == "collapse":
         out += (b.collapse_groups(),)
     elif kind == "rescore":
         out += b.rescore_details()
     return out
+
+
+def shaped_pages(b):
+    """(shaping reads the plan's names, keys and intervals, no id: the canonical plan serves every index)"""
+    from searchlite_amd import aggs as A
+    lay, page = b.composite_layout(), b.composite()
+    check_composite_raw(page, lay, "composite")
+    return page, [A.shape_composite(W.composite_plan(W.CANON), lay, page, q) for q in range(W.NQ)]
+
+
+def set_after(b, afters):
+    """page two starts behind page one's after-key; a query whose page one was its last is parked above every key"""
+    from searchlite_amd import aggs as A
+    lay = b.composite_layout()
+    b.set_composite_after([1 << lay["key_bits"] if a is None else A.composite_lower_bound(lay, W.composite_plan(W.CANON), a)
+                           for a in afters])
+
+
+def composite_pages(b):
+    """of a batch that has just run from the start: page one, then page two from page one's after-key (a second run);
+    the batch is left as it was, at the start -> (raw pages, shaped pages)"""
+    raw1, one = shaped_pages(b)
+    set_after(b, [p.get("after_key") for p in one])
+    b.run()
+    raw2, two = shaped_pages(b)
+    b.set_composite_after(None)
+    return [raw1, raw2], [one, two]
 
 
 def request(m, kind, ids, oracle):
@@ -149,8 +230,25 @@ def run(ix, kind, req):
         with prepare(ix, kind, req) as b:
             b.run()
             return collect(kind, b)
-    if kind == "expand":
+    if kind in ("expand", "regex"):
         return ix.expand(req["requests"])
+    if kind == "suggest":
+        return [suggest_ref.bits(o) for o in ix.suggest(req["requests"])]
+    if kind == "highlight":
+        return ix.highlight(req["hits"], req["specs"])
+    if kind == "highlight_batch":
+        with ix.prepare(*req["q"], req["k"]) as b:
+            b.run()
+            return b.fetch(), b.highlight(req["specs"])
+    if kind == "nested":
+        out = dict(bitmaps=ix.fetch_filter(req["filter"]))
+        with prepare(ix, "bool", req["bool"]) as b:
+            b.run()
+            out["bool"] = b.fetch()
+        with prepare(ix, "scan", req["scan"]) as b:
+            b.run()
+            out["scan"] = collect("scan", b)
+        return out
     if kind == "vector":
         return ix.vector_search(req["clause_field"], req["qvecs"], req["alpha"], req["cand"], req["k_out"], boost=req["boost"])
     if kind == "hybrid":
@@ -186,7 +284,55 @@ def check(kind, got, want, m, what):
         collapse_ref.assert_same_arrays(got[4], want["groups"], what)
     elif kind == "rescore":
         same_rescore(got, want, what)
-    elif kind == "expand":
+    elif kind == "date_aggs":
+        same(got[:4], want["rows"], what)   # (the rows of an aggregation batch are those of the plain batch)
+        assert got[4].tolist() == [len(d) for d in want["docs"]], f"{what}: matched"
+        check_date_tables(W.date_plan(W.CANON), got[5], got[6], want["want"], what)
+    elif kind == "top_hits":
+        same(got[:4], want["rows"], what)
+        assert got[4].tolist() == want["matched"], f"{what}: matched"
+        th, tables, lay = got[5], got[6], got[7]
+        assert not th["status"].any() and [x["lists"] for x in lay] == [w_["count"].shape[1] for w_ in want["lists"]], what
+        top_hits_ref.assert_same_lists(th["nodes"], want["lists"], what)
+        for nd, tot in zip(W.top_hits_plan(W.CANON).top_hits_nodes, want["totals"]):
+            if nd["parent"] < 0:
+                assert tot[:, 0].tolist() == got[4].tolist(), f"{what}: a root's total is the matched count"
+            else:
+                assert np.array_equal(tot, tables[nd["parent"]][:, 0, :]), f"{what}: a child's total is the parent's count cell"
+    elif kind == "composite":
+        same(got[:4], want["rows"], what)
+        assert got[4].tolist() == want["matched"], f"{what}: matched"
+        for page in (0, 1):
+            for q in range(W.NQ):
+                same_composite(got[6][page][q], want["pages"][page][q], f"{what}: page {page + 1} of query {q}")
+    elif kind == "term_buckets":
+        same(got[:4], want["rows"], what)
+        assert got[4].tolist() == want["matched"], f"{what}: matched"
+        plan = W.term_buckets_plan(W.CANON)
+        for nd, nlay, ngot in zip(plan.term_buckets["nodes"], got[6]["nodes"], got[5]["nodes"]):
+            check_term_bucket_node(want, W.TERM_BUCKETS[nd["name"]], nd, nlay, ngot, want["nodes"][nd["name"]], f"{what}: {nd['name']}")
+    elif kind == "request":
+        same(got[:4], want["page"], what)
+        assert got[4].tolist() == want["matched"].tolist(), f"{what}: matched"
+        world = dict(cols=W.agg_columns(m), masks=m.filter_masks(), keys_of=W.KEYS_OF, nq=W.NQ)
+        check_request_aggs(world, W.compound_request(m, W.CANON)["aggs"], W.REQUEST_AGGS, want["sets"], got[5], got[6], what)
+        collapse_ref.assert_same_arrays(got[7], want["collapse"], what)
+    elif kind == "nested":
+        assert len(got["bitmaps"]) == m.n_segs
+        for s in range(m.n_segs):
+            assert np.array_equal(got["bitmaps"][s], want["bitmaps"][s]), f"{what}: bitmap of segment {s}"
+        same(got["bool"], want["bool"], f"{what} as q_filter")
+        same(got["scan"][:4], want["scan"]["rows"], f"{what} as a scan's filter")
+        assert got["scan"][4].tolist() == want["scan"]["matched"].tolist(), f"{what}: matched"
+    elif kind == "suggest":
+        assert got == want, what                          # texts, order, doc_freq and the scores' f32 bits
+    elif kind == "highlight":
+        assert got == want, what                          # status and the bytes of every fragment
+    elif kind == "highlight_batch":
+        assert_same_hits(got[0], want["rows"], 0.0, what)
+        same(got[0], want["rows"], what)
+        assert got[1] == want["items"], what
+    elif kind in ("expand", "regex"):
         assert len(got) == len(want)
         for r, ((ids, dist), (want_ids, want_dist)) in enumerate(zip(got, want)):
             assert ids.shape == want_ids.shape and ids.shape[1] == m.n_segs, f"{what} request {r}: {ids.shape}"
@@ -217,9 +363,9 @@ def checkpoint(live, m, oracle, what, kinds=W.KINDS):
 
 
 def check_filters(live, m, what):
-    """the four registered bitmaps against the model: alive and passing, segment by segment"""
+    """the five registered bitmaps (the nested tree's too) against the model: alive and passing, segment by segment"""
     masks = m.filter_masks()
-    for name in FILTERS:
+    for name in FILTERS + ("f_nested",):
         got = live.ix.fetch_filter(live.ids[name])
         assert len(got) == m.n_segs
         for s in range(m.n_segs):
@@ -270,7 +416,7 @@ def test_remove(sa, oracle, which):
             live.apply(m, op)
         assert live.ix.generation == 1 and live.ix.info()["n_segs"] == 3 and live.ids == ids
         got = checkpoint(live, m, oracle, f"remove {which}")
-        assert all(rows.shape[1] == 3 for rows, _ in got["expand"])
+        assert all(rows.shape[1] == 3 for rows, _ in got["expand"] + got["regex"])
         check_filters(live, m, f"remove {which}")
         refused(sa, lambda: live.ix.remove_segment(3), "no such segment")
 
@@ -320,6 +466,41 @@ def test_add(sa, oracle):
         assert any(s == 4 for mp in lists for s, _ in mp[0]) and not any(s == 4 for mp in lists for s, _ in mp[1])
         for kind in ("plain", "rescore"):                   # and what reads the segments alone is complete already
             check(kind, run(ix, kind, request(m, kind, old, oracle)), W.expect(m, kind, oracle), m, "after add_segment")
+        # the resources added since, one by one, as include/searchlite_gpu.h has them
+        # an aggregation field ("gives the new segment none"): the date aggregations are refused
+        # (its filter source is refused "as it is in q_filter": "unknown filter id"; without it, the column shows)
+        refused(sa, lambda: run(ix, "date_aggs", request(m, "date_aggs", old, oracle)), "unknown filter id")
+        dates = {n: body for n, body in W.DATE_AGGS.items() if body["type"] != "filter"}
+        refused(sa, lambda: ix.search_aggs(*Q, W.K, W.date_plan(old, dates)), "no column for segment 4")
+        for kind in ("top_hits", "composite", "term_buckets"):   # ("a batch that names the field then fails with
+            refused(sa, lambda: run(ix, kind, request(m, kind, old, oracle)))   # SLG_ERR_INVALID", whichever it names first)
+        refused(sa, lambda: run(ix, "request", request(m, "request", old, oracle)))
+        # a text field: "a segment added later has no text in the field (SLG_HL_NO_TEXT) until the field is registered
+        # again over all segments": an answer, in both forms
+        assert bare.text[4] is None and m.text[4] is not None
+        for kind in ("highlight", "highlight_batch"):
+            got = run(ix, kind, request(m, kind, old, oracle))
+            check(kind, got, W.expect(bare, kind, oracle), bare, "the text field without segment 4")
+        hits, items = W.highlight_hits(m), run(ix, "highlight", request(m, "highlight", old, oracle))
+        there = [it[0] for hq, iq in zip(hits, items) for (s, _), it in zip(hq, iq) if s == 4]
+        assert len(there) >= 2 * W.NQ and all(x == (W.N.HL_NO_TEXT, []) for x in there)
+        # the nested tree's filter is an ordinary filter: refused as the four above
+        refused(sa, lambda: ix.search_batch(*Q, W.K, q_filter=np.full(W.NQ, old["f_nested"], np.int32)), "unknown filter id")
+        refused(sa, lambda: ix.prepare_scan(W.scan_queries(old)[0], W.K, q_filter=np.full(8, old["f_nested"], np.int32)),
+                "unknown filter id")
+        # a nested path: "a tree naming the path is then SLG_ERR_INVALID, "nested path N has no tables for segment S""
+        # (the deepest scope is looked at first: the path named is c.r)
+        refused(sa, lambda: ix.add_nested_filter_trees([W.nested_program(old)]), "nested path", "has no tables for segment 4")
+        # ... and a nested column ("lifecycle as the paths"): under paths registered again, the old columns are refused
+        live.register_nested(m, ("p_c", "p_cr"), ())
+        refused(sa, lambda: ix.add_nested_filter_trees([W.nested_program(live.ids)]), "nested field", "segment 4")
+        for name in ("p_cr", "p_c"):
+            ix.remove_nested_path(live.ids[name])
+            live.ids[name] = old[name]
+        # the dictionaries: the suggester and the regex expansion are refused until set_terms
+        refused(sa, lambda: run(ix, "suggest", request(m, "suggest", old, oracle)), "segment 4 has no term dictionary")
+        refused(sa, lambda: run(ix, "regex", request(m, "regex", old, oracle)), "segment 4")
+        assert ix.generation == 1
         # registered again
         live.unregister()
         live.set_text(m, [4])
@@ -365,22 +546,48 @@ def test_prepared_batches_keep_their_state(sa, oracle, step):
     live = Live(sa, m)
     try:
         want = {kind: W.expect(old, kind, oracle) for kind in W.PREPARED}
+        hl_specs = request(old, "highlight_batch", live.ids, oracle)["specs"]
+        hl_items = W.expect(old, "highlight_batch", oracle)["items"]     # (over the rows of the `plain` batch)
         reqs = {kind: request(old, kind, live.ids, oracle) for kind in W.PREPARED}   # (kept: a batch borrows its specs)
         batches = {kind: prepare(live.ix, kind, reqs[kind]) for kind in W.PREPARED}
         ran = prepare(live.ix, "plain", reqs["plain"])
         ran.run()                                           # in flight during the update
+        batches["composite"].run()                          # page one, and the after-key set: page two comes after the update
+        set_after(batches["composite"], want["composite"]["afters"])
         live.apply(m, ("remove", 1) if step == "remove" else ("add", fifth))
+        batches["composite"].run()
+        for q, page in enumerate(shaped_pages(batches["composite"])[1]):
+            same_composite(page, want["composite"]["pages"][1][q], f"the after-key set before {step}: page two of query {q}")
+        batches["composite"].set_composite_after(None)
         for kind, b in batches.items():
             b.run()
             check(kind, collect(kind, b), want[kind], old, f"prepared before {step}, run after")
         check("plain", collect("plain", ran), want["plain"], old, f"run before {step}, fetched after")
+        # slg_batch_highlight: "the state is the one the batch was prepared on", its texts and its rows
+        assert batches["plain"].highlight(hl_specs) == hl_items and ran.highlight(hl_specs) == hl_items
         # two further updates: the state the batches hold is two generations behind the current one
+        mid = m.clone()
+        if step == "remove":   # (nothing was added yet: the registrations still cover every segment)
+            mid_req = request(mid, "term_buckets", live.ids, oracle)
+            mid_batch = prepare(live.ix, "term_buckets", mid_req)   # prepared before the tombstones below
         live.apply(m, ("delete", 0, [0, 31, 32, 63, 64]))
+        if step == "remove":
+            # the background tables are counted from the tombstones of the batch's state at prepare: a batch prepared
+            # before update_deleted on a segment that holds foreground keys reports the old counts, a fresh one the new
+            before, new = W.expect(mid, "term_buckets", oracle), W.expect(m, "term_buckets", oracle)
+            bg = lambda x: [[(b["key"], b["bg_count"]) for b in r["buckets"]] for r in x["nodes"]["sig"]]
+            assert bg(before) != bg(new) and any(s == 0 for h in W.TW.hits_of(W.all_hits(mid, oracle)) for s, _, _ in h)
+            mid_batch.run()
+            check("term_buckets", collect("term_buckets", mid_batch), before, mid, "prepared before the tombstones: the old background")
+            mid_batch.close()
+            check("term_buckets", run(live.ix, "term_buckets", request(m, "term_buckets", live.ids, oracle)), new, m,
+                  "prepared after the tombstones: the new background")
         live.apply(m, ("remove", 0) if step == "add" else ("add", fifth))
         assert live.ix.generation == 3
         for kind, b in batches.items():
             b.run()
             check(kind, collect(kind, b), want[kind], old, f"prepared before {step}, run two updates later")
+        assert batches["plain"].highlight(hl_specs) == hl_items and ran.highlight(hl_specs) == hl_items
         # and new batches see the new state (what reads the segments alone needs no second registration)
         check("plain", run(live.ix, "plain", request(m, "plain", live.ids, oracle)), W.expect(m, "plain", oracle), m,
               "the current state")

@@ -157,7 +157,7 @@ def check_node(W, body, nd, lay, got, want, what):
     sig = body["type"] == "significant_terms"
     keys = nd["keys"]
     kids = body.get("aggs") or {}
-    for q in range(NQ):
+    for q in range(len(want)):   # (NQ here; tests/test_gpu_lifecycle.py brings its own queries)
         wq, n = want[q], int(got["n_buckets"][q])
         at = f"{what}: query {q}"
         assert n == len(wq["buckets"]), f"{at}: {n} buckets, want {len(wq['buckets'])}"

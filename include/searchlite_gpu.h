@@ -1922,8 +1922,8 @@ int slg_search_batch_phrase(slg_index *index, uint32_t nq, const uint32_t *q_off
  * slg_batch_run_sharded* and slg_batch_fetch_sharded refuse a function_score batch with SLG_ERR_UNSUPPORTED.
  * Built beside it: script_score at the root, and the two nodes nested one inside the other
  * (slg_batch_prepare_script, below).  Not built (CPU scorer): function_score below the root or over any other
- * inner query (rank_feature and constant_score at the root are scan batches, below), deeper nesting, explain,
- * function filters other than registered
+ * inner query (rank_feature and constant_score at the root are scan batches, below), deeper nesting,
+ * (explain is built: slg_batch_explain, at the end of this header), function filters other than registered
  * filter ids, and specs on hybrid, rescore, sharded and coalesced batches
  * (behind bool, phrase or tree clauses, with a cursor, aggregations or collapse:
  * slg_batch_prepare_request, "compound requests" below).
@@ -2021,7 +2021,8 @@ int slg_search_batch_fscore(slg_index *index, uint32_t nq, const uint32_t *q_off
  * with no hit (e.g. "1 2") — and a column that holds a non-finite value (the rule of aggregations).
  * slg_batch_run_sharded* and slg_batch_fetch_sharded refuse a script batch with SLG_ERR_UNSUPPORTED.
  * Not built (CPU scorer): script_score below the root or over any other inner query, more than the two stages,
- * explain, and specs on hybrid, rescore, sharded and coalesced batches (rank_feature and constant_score at the root are
+ * and specs on hybrid, rescore, sharded and coalesced batches (explain is built: slg_batch_explain, at the end of
+ * this header; rank_feature and constant_score at the root are
  * scan batches, below; behind bool, phrase or tree clauses, with a cursor, aggregations or collapse:
  * slg_batch_prepare_request, "compound requests" below).
  * --------------------------------------------------------------------------------------------------------- */
@@ -2578,6 +2579,71 @@ int slg_batch_highlight(slg_batch *batch, const uint32_t *spec_offsets, const sl
  * part (the emit kernel, the strings back, the wait; 0 for a size query).  Per thread; `index` is only checked for
  * NULL; either pointer may be NULL. */
 int slg_highlight_phase_ms(slg_index *index, double *count_ms, double *emit_ms);
+
+/* ---------------------------------------------------------------------------------------------------------
+ * explain (SearchRequest.explain): per returned hit the first-pass score, the value of every score function that
+ * gave the doc one, the rescore part and the final score — HitExplanation (api/reader.rs:90-97), from
+ * evaluate_compiled_score (:418-613), describe_function (:389-416), the score hook (:3038-3127), rescore_hits
+ * (:3365-3383) and the final pass (:2803-2816).  A post-pass over a batch that has run, as slg_batch_highlight is:
+ * no batch kind of its own, and a batch that is never explained runs what it runs without this call.
+ *
+ * slg_batch_explain explains the first min(rows, count[q]) rows of every query.  It is queued behind the batch's
+ * last kernel on the batch's stream, works against the index state the batch was prepared on, and returns when the
+ * caller's arrays are filled.  The arrays of slg_explain_out are the caller's, with a fixed stride of `rows` per
+ * query (row r of query q at q * rows + r; entry e of that row at (q * rows + r) * SLG_MAX_EXPLAIN_FUNCS + e).
+ * Rows at or beyond a query's count, and the entries behind a row's n_functions, are zero-filled.
+ *
+ * BASE SCORE.  base_score = ScorePlan::evaluate(leaves): the first-pass score of the row's doc before any score
+ * stage.  The stages rewrite the candidates' scores in place, so it is computed again: the doc is looked up in every
+ * posting list of the (query, row's segment) sub-query, with the batch's own term table (folded weights, leaves).
+ * The arithmetic is the scoring kernels' for flat plans, every operation f32 and rounded on its own: impact *
+ * weight per term; a leaf's terms added in query-term order from +0.0; Sum: the leaves added in leaf order from
+ * -0.0; DisMax: max + tie * (sum - max), the sum from +0.0 over every leaf, the max from 0.0 when a leaf of the plan
+ * has no term in the segment (else from -inf), a leaf without a posting of the doc counting as 0.0.
+ *
+ * FUNCTIONS.  The score stages run in the batch's order over that base, with the device functions the stages
+ * themselves run.  A function_score appends, in request order, one entry per function that gives the doc a value:
+ * a function whose filter rejects the doc appends nothing, neither does a decay without a value of the column, nor
+ * a field_value_factor whose product or result is not finite.  fn_type is SLG_EXPLAIN_*, fn_field the agg field
+ * id the caller named in f_field (-1 for a weight and for a script), fn_value the function's value as f32.  A
+ * script_score appends one entry SLG_EXPLAIN_SCRIPT_SCORE with value script * boost.  Nesting follows
+ * evaluate_compiled_score's recursion, inner entries first: SLG_SCRIPT_OUTER gives the function entries, then the
+ * script entry; SLG_SCRIPT_INNER the script entry, then the function entries.  The substitution of 1.0 for a base
+ * score within f32::EPSILON of 0 changes final_score, never the reported base_score.  A query without work in a
+ * stage appends nothing for it.
+ *
+ * FINAL SCORE.  final_score is the end of the chain, computed again.  For every explained row of a batch without
+ * rescore it is bit for bit the row's score as slg_batch_fetch returns it.
+ *
+ * RESCORE BATCH (legal only without score stages: n_functions is 0).  base_score is the first-pass score computed
+ * again — first_score of slg_batch_fetch_rescore, bit for bit; rescored, rescore_score and combined_score are the
+ * batch's own (rescored 0: the two scores are 0.0); final_score is the row's score: the combined score of a matched
+ * row, the first-pass score of an unmatched row and of a row behind the window.  The three arrays are read only
+ * for a rescore batch and must be given there; otherwise they may be NULL and are left alone.
+ *
+ * Errors.  SLG_ERR_INVALID, before any device work: a NULL batch, `out` or required array, rows == 0, a batch
+ * that has not run, a batch whose index was destroyed.  SLG_ERR_UNSUPPORTED (CPU scorer), the reason named: rows >
+ * SLG_MAX_EXPLAIN_ROWS, a scan batch, a hybrid batch, a batch with a two-level or deeper score plan, a query whose
+ * term rows of all segments exceed 2048 entries (the kernel's LDS table), a batch whose last run was sharded.
+ * Not built (CPU scorer): the inner hits of collapse, the hits of top_hits, scan batches (rank_feature entries),
+ * vector-only results, the coalescer, and `profile`.
+ * --------------------------------------------------------------------------------------------------------- */
+#define SLG_MAX_EXPLAIN_ROWS 1024u /* rows of one query: 256 threads x 4 rows, as the rescore window */
+#define SLG_MAX_EXPLAIN_FUNCS 9u   /* SLG_MAX_FSCORE_FUNCS + the script_score entry */
+enum { SLG_EXPLAIN_WEIGHT = 0, SLG_EXPLAIN_FIELD_VALUE_FACTOR = 1, SLG_EXPLAIN_DECAY_EXP = 2,
+       SLG_EXPLAIN_DECAY_GAUSS = 3, SLG_EXPLAIN_DECAY_LINEAR = 4, SLG_EXPLAIN_SCRIPT_SCORE = 5 };
+typedef struct slg_explain_out {
+  float *base_score;      /* [nq * rows] */
+  float *final_score;     /* [nq * rows] */
+  uint32_t *n_functions;  /* [nq * rows] entries of the row, <= SLG_MAX_EXPLAIN_FUNCS */
+  uint32_t *fn_type;      /* [nq * rows * SLG_MAX_EXPLAIN_FUNCS] SLG_EXPLAIN_* */
+  int32_t *fn_field;      /* [nq * rows * SLG_MAX_EXPLAIN_FUNCS] agg field id, or -1 */
+  float *fn_value;        /* [nq * rows * SLG_MAX_EXPLAIN_FUNCS] */
+  uint32_t *rescored;     /* [nq * rows]; a rescore batch only, else NULL or left alone */
+  float *rescore_score;   /* [nq * rows]; as rescored */
+  float *combined_score;  /* [nq * rows]; as rescored */
+} slg_explain_out;
+int slg_batch_explain(slg_batch *batch, uint32_t rows, const slg_explain_out *out);
 
 #ifdef __cplusplus
 }

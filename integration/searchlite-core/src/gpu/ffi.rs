@@ -235,6 +235,21 @@ pub const SLG_SCAN_MOD_RECIPROCAL: i32 = 4;
     pub status: *mut u8, pub offsets: *mut u32, pub text_offsets: *mut u32, pub text: *mut c_char,
     pub n_items: u32, pub n_frags: u32, pub text_bytes: u64,
 }
+// slg_batch_explain (SearchRequest.explain): caller-owned arrays with a stride of `rows` per query; the last three
+// are read only for a rescore batch
+#[repr(C)] pub struct slg_explain_out {
+    pub base_score: *mut c_float, pub final_score: *mut c_float, pub n_functions: *mut u32,
+    pub fn_type: *mut u32, pub fn_field: *mut i32, pub fn_value: *mut c_float,
+    pub rescored: *mut u32, pub rescore_score: *mut c_float, pub combined_score: *mut c_float,
+}
+pub const SLG_MAX_EXPLAIN_ROWS: u32 = 1024;
+pub const SLG_MAX_EXPLAIN_FUNCS: u32 = 9;
+pub const SLG_EXPLAIN_WEIGHT: u32 = 0;
+pub const SLG_EXPLAIN_FIELD_VALUE_FACTOR: u32 = 1;
+pub const SLG_EXPLAIN_DECAY_EXP: u32 = 2;
+pub const SLG_EXPLAIN_DECAY_GAUSS: u32 = 3;
+pub const SLG_EXPLAIN_DECAY_LINEAR: u32 = 4;
+pub const SLG_EXPLAIN_SCRIPT_SCORE: u32 = 5;
 pub const SLG_HL_OK: u8 = 0;
 pub const SLG_HL_HOST: u8 = 1;
 pub const SLG_HL_NO_TEXT: u8 = 2;
@@ -556,6 +571,9 @@ extern "C" {
     pub fn slg_batch_highlight(batch: *mut slg_batch, spec_offsets: *const u32, specs: *const slg_hl_spec,
         out: *mut slg_hl_out) -> c_int;
     pub fn slg_highlight_phase_ms(index: *mut slg_index, count_ms: *mut f64, emit_ms: *mut f64) -> c_int;
+    // explain (SearchRequest.explain) behind a batch that has run: declared, not routed yet (INTEGRATION.md says
+    // how the request path would use it)
+    pub fn slg_batch_explain(batch: *mut slg_batch, rows: u32, out: *const slg_explain_out) -> c_int;
     pub fn slg_batch_prepare_phrase(index: *mut slg_index, nq: u32, q_offsets: *const u32, q_term_ids: *const u32,
         q_weights: *const c_float, plans: *const slg_score_plans, q_filter: *const i32,
         sort: *const slg_sort_spec, bool_spec: *const slg_bool_spec, phrases: *const slg_phrase_spec, k: u32,

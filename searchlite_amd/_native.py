@@ -351,6 +351,18 @@ class HlOut(C.Structure):
                 ("text_bytes", C.c_uint64)]
 
 
+MAX_EXPLAIN_ROWS, MAX_EXPLAIN_FUNCS = 1024, 9  # SLG_MAX_EXPLAIN_*
+(EXPLAIN_WEIGHT, EXPLAIN_FIELD_VALUE_FACTOR, EXPLAIN_DECAY_EXP, EXPLAIN_DECAY_GAUSS, EXPLAIN_DECAY_LINEAR,
+ EXPLAIN_SCRIPT_SCORE) = range(6)
+
+
+class ExplainOut(C.Structure):
+    """slg_explain_out: the caller's arrays of slg_batch_explain, a stride of `rows` per query."""
+    _fields_ = [("base_score", C.c_void_p), ("final_score", C.c_void_p), ("n_functions", C.c_void_p),
+                ("fn_type", C.c_void_p), ("fn_field", C.c_void_p), ("fn_value", C.c_void_p),
+                ("rescored", C.c_void_p), ("rescore_score", C.c_void_p), ("combined_score", C.c_void_p)]
+
+
 class Ticket(C.Structure):
     """slg_ticket (slg_coalescer_submit / _wait)."""
     _fields_ = [("batch", C.c_void_p), ("row", C.c_uint32), ("k", C.c_uint32), ("kind", C.c_uint32)]
@@ -588,6 +600,7 @@ def load():
         "slg_highlight_batch": (i32, [vp, u32, vp, vp, vp, vp, vp, vp]),
         "slg_batch_highlight": (i32, [vp, vp, vp, vp]),
         "slg_highlight_phase_ms": (i32, [vp, vp, vp]),
+        "slg_batch_explain": (i32, [vp, u32, vp]),
     }
     for name, (res, args) in sigs.items():
         if os.environ.get("SLG_LIB_TAG") and not hasattr(L, name):

@@ -359,6 +359,18 @@ slg_batch *slghost::prepare_impl(const PrepareRequest &r) {
     b->n_terms = (uint32_t)plan.terms.size();
     b->n_slices = (uint32_t)plan.slice_sq.size();
     b->n_boundaries = (uint32_t)plan.n_bnd;
+    {  // what slg_batch_explain looks a row's lists up with: the sub-query of every (query, segment) pair
+      const size_t n_segs = snap->segs.size();
+      b->ex_q_seg_sq.assign((size_t)nq * n_segs, 0xFFFFFFFFu);
+      std::vector<uint32_t> q_rows(nq, 0u);
+      for (size_t i = 0; i < plan.sqs.size(); i++) {
+        const slg::RoundQuery &sq = plan.sqs[i];
+        if (sq.q >= nq || sq.seg >= n_segs) throw SlgError(SLG_ERR_INTERNAL, "a sub-query of no query or segment");
+        b->ex_q_seg_sq[(size_t)sq.q * n_segs + sq.seg] = (uint32_t)i;
+        q_rows[sq.q] += sq.n_terms;
+        b->ex_max_table = std::max(b->ex_max_table, q_rows[sq.q]);
+      }
+    }
 
     // ---- the descriptor image: one H2D copy the caller waits for, outside any lock, on an upload
     // stream of its own.  (Measured against an image copied asynchronously on the batch's stream in
@@ -505,6 +517,7 @@ int slg_batch_run(slg_batch *b) {
     DeviceGuard g(ix->device);
     hipStream_t st = batch_stream(b);
     b->launched = true;
+    b->last_sharded = false;  // (slg_batch_run_sharded* sets it behind this call)
     if (b->nq == 0) return;
     if (b->scan) {
       scan_launch(b, st);  // (no scored term: the candidates come from a scan over the segments' docs)

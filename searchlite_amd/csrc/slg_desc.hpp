@@ -326,7 +326,9 @@ struct FscoreFn {
   uint32_t filter;     // 0: none; r + 1: row r of the batch's filter table
   float weight;        // weight, or field_value_factor's factor
   double missing, origin, scale, offset, decay;
-  uint32_t pad[2];
+  int32_t field;       // the agg field id the caller named, -1 for a weight (what an explanation reports; no kernel
+                       // between scoring and select reads it)
+  uint32_t pad;
 };
 constexpr uint32_t kFscoreMaxFuncs = 8;  // = SLG_MAX_FSCORE_FUNCS
 

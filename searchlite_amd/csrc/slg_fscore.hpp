@@ -68,6 +68,103 @@ __device__ __forceinline__ double fscore_modifier(double x, uint32_t mod) {
   return x;
 }
 
+// A value that is wave-uniform where one wave works on one segment (UNI: the kernels between scoring and select, which
+// keep it in scalar registers), and per lane where a lane's rows lie in any segment (explain_kernel, slg_explain.hpp)
+template <bool UNI>
+__device__ __forceinline__ uint32_t fscore_u32(uint32_t v) {
+  if constexpr (UNI) return rfl(v);
+  else return v;
+}
+template <bool UNI>
+__device__ __forceinline__ uint64_t fscore_u64(uint64_t v) {
+  if constexpr (UNI) return uniform64(v);
+  else return v;
+}
+
+// One candidate through the functions of its query: the new score (boost applied) and, in `accept`, whether the doc
+// stays (live, and not below min_score).  row: the query's functions; n_fns, score_mode, boost_mode, flags: the
+// query's, wave-uniform.  emit(kinds, field id, value) is called, in request order, for every function that gives the
+// doc a value (the entries of an explanation; fscore_kernel passes a callable that does nothing).
+template <bool FULL, bool UNI, typename Emit>
+__device__ __forceinline__ float fscore_candidate(const FscoreQuery &fq, const FscoreFn *const row, const uint32_t n_fns,
+                                                  const uint32_t score_mode, const uint32_t boost_mode, const uint32_t flags,
+                                                  const ColumnDev *const cols, const uint32_t *const *const filters,
+                                                  const uint32_t n_segs, const uint32_t seg, const uint32_t doc,
+                                                  const bool live, const float base_score, bool &accept, Emit emit) {
+  float fs = 0.0f;
+  uint32_t present = 0u;
+  for (uint32_t f = 0; f < n_fns; f++) {
+    const FscoreFn fn = load_const(row + f);
+    const uint32_t kinds = rfl(fn.kinds);
+    const uint32_t kind = kinds & 0xFFu;
+    bool has = live;
+    const uint32_t flt = rfl(fn.filter);
+    if (flt != 0u) {
+      typedef const __attribute__((address_space(1))) uint32_t *gu32_t;
+      const uint64_t a = fscore_u64<UNI>((uint64_t)(uintptr_t)load_const(filters + ((size_t)(flt - 1u) * n_segs + seg)));
+      uint32_t w = 0u;
+      if (has && a != 0ull) w = ((gu32_t)(uintptr_t)a)[doc >> 5];  // (a live doc is below the segment's n_docs)
+      has = has && ((w >> (doc & 31u)) & 1u) == 0u;
+    }
+    double v = 0.0;
+    if (kind != kFsWeight) {  // the doc's first value of the column
+      typedef const __attribute__((address_space(1))) uint32_t *gu32_t;
+      typedef const __attribute__((address_space(1))) double *gf64_t;
+      const ColumnDev col = load_const(cols + ((size_t)rfl(fn.col) * n_segs + seg));
+      const uint64_t offs = fscore_u64<UNI>((uint64_t)(uintptr_t)col.offs), vals = fscore_u64<UNI>((uint64_t)(uintptr_t)col.vals);
+      uint32_t first = doc, end = doc + 1u;
+      if (offs != 0ull && has) {
+        first = ((gu32_t)(uintptr_t)offs)[doc];
+        end = ((gu32_t)(uintptr_t)offs)[doc + 1u];
+      }
+      const bool valued = has && first < end;
+      if (valued) v = ((gf64_t)(uintptr_t)vals)[first];
+      if (kind == kFsFieldValue) {
+        const double raw = valued ? v : fn.missing;
+        const double scaled = raw * (double)fn.weight;
+        v = fscore_modifier<FULL>(scaled, (kinds >> 8) & 0xFFu);
+        has = has && isfinite(scaled) && isfinite(v);
+      } else {
+        const double distance = fabs(v - fn.origin) - fn.offset;
+        const double norm = fmax(distance, 0.0) / fn.scale;
+        const uint32_t dfn = (kinds >> 16) & 0xFFu;
+        if (dfn == kFsDecayLinear) {
+          v = fmax((1.0 - norm) * (1.0 - fn.decay) + fn.decay, 0.0);
+        } else {
+          if constexpr (FULL) v = pow(fn.decay, dfn == kFsDecayGauss ? norm * norm : norm);
+        }
+        has = valued && isfinite(v);
+      }
+    }
+    const float val = kind == kFsWeight ? fn.weight : (float)v;
+    if (has) {
+      float next;
+      if (score_mode == kFsMultiply) next = fs * val;
+      else if (score_mode == kFsMax) next = fmaxf(fs, val);
+      else if (score_mode == kFsMin) next = fminf(fs, val);
+      else next = fs + val;
+      fs = present == 0u ? val : next;
+      present++;
+      emit(kinds, fn.field, val);
+    }
+  }
+  float eff = base_score;
+  if (present != 0u && fabsf(base_score) <= 1.1920929e-7f) eff = 1.0f;  // (f32::EPSILON)
+  float combined = eff;
+  if (present != 0u) {
+    if (score_mode == kFsAvg) fs = fs / (float)present;
+    if (boost_mode == kFsBoostMultiply) combined = eff * fs;
+    else if (boost_mode == kFsBoostSum) combined = eff + fs;
+    else if (boost_mode == kFsBoostReplace) combined = fs;
+    else if (boost_mode == kFsBoostMax) combined = fmaxf(eff, fs);
+    else combined = fminf(eff, fs);
+  }
+  if (flags & kFsHasMaxBoost) combined = fminf(combined, fq.max_boost);
+  accept = live && !((flags & kFsHasMinScore) != 0u && combined < fq.min_score);
+  combined *= fq.boost;
+  return combined;
+}
+
 template <bool FULL>
 static __global__ void __launch_bounds__(kFscoreThreads) fscore_kernel(FscoreParams p) {
   const uint32_t lane = threadIdx.x & 63u;
@@ -91,77 +188,10 @@ static __global__ void __launch_bounds__(kFscoreThreads) fscore_kernel(FscorePar
     const uint2 c = clause_candidate(sl, base + lane);
     const bool live = c.y != 0xFFFFFFFFu;  // (a dropped entry stays dropped)
     const uint32_t doc = c.y;
-    const float base_score = fscore_base(c.x);
-    float fs = 0.0f;
-    uint32_t present = 0u;
-    for (uint32_t f = 0; f < n_fns; f++) {
-      const FscoreFn fn = load_const(row + f);
-      const uint32_t kinds = rfl(fn.kinds);
-      const uint32_t kind = kinds & 0xFFu;
-      bool has = live;
-      const uint32_t flt = rfl(fn.filter);
-      if (flt != 0u) {
-        typedef const __attribute__((address_space(1))) uint32_t *gu32_t;
-        const uint64_t a = uniform64((uint64_t)(uintptr_t)load_const(p.filters + ((size_t)(flt - 1u) * p.c.n_segs + sl.seg)));
-        uint32_t w = 0u;
-        if (has && a != 0ull) w = ((gu32_t)(uintptr_t)a)[doc >> 5];  // (a live doc is below the segment's n_docs)
-        has = has && ((w >> (doc & 31u)) & 1u) == 0u;
-      }
-      double v = 0.0;
-      if (kind != kFsWeight) {  // the doc's first value of the column
-        typedef const __attribute__((address_space(1))) uint32_t *gu32_t;
-        typedef const __attribute__((address_space(1))) double *gf64_t;
-        const ColumnDev col = load_const(p.cols + ((size_t)rfl(fn.col) * p.c.n_segs + sl.seg));
-        const uint64_t offs = uniform64((uint64_t)(uintptr_t)col.offs), vals = uniform64((uint64_t)(uintptr_t)col.vals);
-        uint32_t first = doc, end = doc + 1u;
-        if (offs != 0ull && has) {
-          first = ((gu32_t)(uintptr_t)offs)[doc];
-          end = ((gu32_t)(uintptr_t)offs)[doc + 1u];
-        }
-        const bool valued = has && first < end;
-        if (valued) v = ((gf64_t)(uintptr_t)vals)[first];
-        if (kind == kFsFieldValue) {
-          const double raw = valued ? v : fn.missing;
-          const double scaled = raw * (double)fn.weight;
-          v = fscore_modifier<FULL>(scaled, (kinds >> 8) & 0xFFu);
-          has = has && isfinite(scaled) && isfinite(v);
-        } else {
-          const double distance = fabs(v - fn.origin) - fn.offset;
-          const double norm = fmax(distance, 0.0) / fn.scale;
-          const uint32_t dfn = (kinds >> 16) & 0xFFu;
-          if (dfn == kFsDecayLinear) {
-            v = fmax((1.0 - norm) * (1.0 - fn.decay) + fn.decay, 0.0);
-          } else {
-            if constexpr (FULL) v = pow(fn.decay, dfn == kFsDecayGauss ? norm * norm : norm);
-          }
-          has = valued && isfinite(v);
-        }
-      }
-      const float val = kind == kFsWeight ? fn.weight : (float)v;
-      if (has) {
-        float next;
-        if (score_mode == kFsMultiply) next = fs * val;
-        else if (score_mode == kFsMax) next = fmaxf(fs, val);
-        else if (score_mode == kFsMin) next = fminf(fs, val);
-        else next = fs + val;
-        fs = present == 0u ? val : next;
-        present++;
-      }
-    }
-    float eff = base_score;
-    if (present != 0u && fabsf(base_score) <= 1.1920929e-7f) eff = 1.0f;  // (f32::EPSILON)
-    float combined = eff;
-    if (present != 0u) {
-      if (score_mode == kFsAvg) fs = fs / (float)present;
-      if (boost_mode == kFsBoostMultiply) combined = eff * fs;
-      else if (boost_mode == kFsBoostSum) combined = eff + fs;
-      else if (boost_mode == kFsBoostReplace) combined = fs;
-      else if (boost_mode == kFsBoostMax) combined = fmaxf(eff, fs);
-      else combined = fminf(eff, fs);
-    }
-    if (flags & kFsHasMaxBoost) combined = fminf(combined, fq.max_boost);
-    const bool accept = live && !((flags & kFsHasMinScore) != 0u && combined < fq.min_score);
-    combined *= fq.boost;
+    bool accept;
+    const float combined = fscore_candidate<FULL, true>(fq, row, n_fns, score_mode, boost_mode, flags, p.cols, p.filters,
+                                                        p.c.n_segs, sl.seg, doc, live, fscore_base(c.x), accept,
+                                                        [](uint32_t, int32_t, float) {});
     clause_keep(sl, make_uint2(ordered_score(combined), doc), live, accept);
   }
   clause_finish(p.c, s, sl, lane);

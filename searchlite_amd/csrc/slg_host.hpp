@@ -1,5 +1,5 @@
 // slg_host.hpp — what the host translation units of the C ABI share (slg_index.hip, slg_batch.hip,
-// slg_shard.hip, slg_rerank.hip, slg_vsearch.hip, slg_hybrid.hip, slg_aggs.hip, slg_rescore.hip, slg_bool.hip, slg_booltree.hip, slg_phrase.hip, slg_fscore.hip, slg_script.hip, slg_scan.hip, slg_collapse.hip, slg_tophits.hip, slg_composite.hip, slg_termbuckets.hip, slg_highlight.hip): the error plumbing, device memory, the host
+// slg_shard.hip, slg_rerank.hip, slg_vsearch.hip, slg_hybrid.hip, slg_aggs.hip, slg_rescore.hip, slg_bool.hip, slg_booltree.hip, slg_phrase.hip, slg_fscore.hip, slg_script.hip, slg_scan.hip, slg_collapse.hip, slg_tophits.hip, slg_composite.hip, slg_termbuckets.hip, slg_highlight.hip, slg_explain.hip): the error plumbing, device memory, the host
 // structures behind the opaque handles and the small helpers several entry points use.  Private: not
 // installed, not part of include/.  No kernel header is included here — each unit includes the one
 // whose kernels it launches (slg_stage.hpp, slg_kernels.hpp, slg_rerank.hpp, slg_vsearch.hpp, slg_hybrid.hpp; the shard
@@ -591,6 +591,11 @@ struct slg_batch : slg_batch_buffers {
   uint64_t n_postings = 0, n_postings_essential = 0, n_rounds = 0;
   std::vector<uint64_t> q_postings;  // per query (stats.postings_advanced)
   bool launched = false;             // slg_batch_run was called at least once
+  bool last_sharded = false;         // the last run was slg_batch_run_sharded*: the rows a caller holds are the merged ones
+  // slg_batch_explain (slg_explain.hip): the sub-query of every (query, segment) pair, [nq * n_segs], 0xFFFFFFFF where
+  // the pair has none; the most term rows (all segments) of one query.  From the plan, at prepare
+  std::vector<uint32_t> ex_q_seg_sq;
+  uint32_t ex_max_table = 0;
   bool own_stream_set = false;       // slg_batch_set_stream: run on `stream` instead of the index's
   hipStream_t stream = nullptr;
   const slg::RoundQuery *d_sq = nullptr;

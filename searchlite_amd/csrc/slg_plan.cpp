@@ -1423,6 +1423,7 @@ void plan_fscore(const std::vector<FscoreFieldView> &fields, const uint32_t *con
       const int32_t kind = spec.f_kind[f];
       fn.kinds = (uint32_t)kind;
       fn.weight = spec.f_weight[f];
+      fn.field = kind != SLG_FSCORE_WEIGHT ? spec.f_field[f] : -1;
       if (spec.f_filter[f] >= 0) {
         PLAN_REQUIRE((size_t)spec.f_filter[f] < n_filters && filter_live[spec.f_filter[f]],
                      "unknown filter id " + std::to_string(spec.f_filter[f]) + in_q);

@@ -65,7 +65,8 @@ __device__ __forceinline__ double script_pick(uint32_t at, double r0, double r1,
 }
 
 // the doc's first value of the column of row `row` of the column table (wave-uniform), 0.0 without one; not loaded
-// at all when the query has no such field (`used`, wave-uniform)
+// at all when the query has no such field (`used`, wave-uniform).  UNI: the segment is wave-uniform (fscore_u64)
+template <bool UNI>
 __device__ __forceinline__ double script_field(const ColumnDev *cols, uint32_t n_segs, uint32_t seg, uint32_t row, bool used,
                                                uint32_t doc, bool live) {
   typedef const __attribute__((address_space(1))) uint32_t *gu32_t;
@@ -73,7 +74,7 @@ __device__ __forceinline__ double script_field(const ColumnDev *cols, uint32_t n
   double v = 0.0;
   if (used) {
     const ColumnDev col = load_const(cols + ((size_t)rfl(row) * n_segs + seg));
-    const uint64_t offs = uniform64((uint64_t)(uintptr_t)col.offs), vals = uniform64((uint64_t)(uintptr_t)col.vals);
+    const uint64_t offs = fscore_u64<UNI>((uint64_t)(uintptr_t)col.offs), vals = fscore_u64<UNI>((uint64_t)(uintptr_t)col.vals);
     uint32_t first = doc, end = doc + 1u;
     if (offs != 0ull && live) {  // (a live doc is below the segment's n_docs: offsets has n_docs + 1 entries)
       first = ((gu32_t)(uintptr_t)offs)[doc];
@@ -84,6 +85,75 @@ __device__ __forceinline__ double script_field(const ColumnDev *cols, uint32_t n
   return v;
 }
 
+// One candidate through the program of its query: script * boost, and in `none` whether the script gives the doc no
+// score (the doc is dropped).  prog: the query's instructions; n_instrs, n_fields: the query's, wave-uniform
+template <bool UNI>
+__device__ __forceinline__ float script_candidate(const ScriptQuery &sq, const ScriptInstr *const prog, const uint32_t n_instrs,
+                                                  const uint32_t n_fields, const ColumnDev *const cols, const uint32_t n_segs,
+                                                  const uint32_t seg, const uint32_t doc, const bool live,
+                                                  const float base_f32, bool &none_out) {
+  const double base_score = (double)base_f32;
+  // the doc's first value of every distinct field of the query, 0.0 without one
+  const double f0 = script_field<UNI>(cols, n_segs, seg, sq.col[0], n_fields > 0u, doc, live);
+  const double f1 = script_field<UNI>(cols, n_segs, seg, sq.col[1], n_fields > 1u, doc, live);
+  const double f2 = script_field<UNI>(cols, n_segs, seg, sq.col[2], n_fields > 2u, doc, live);
+  const double f3 = script_field<UNI>(cols, n_segs, seg, sq.col[3], n_fields > 3u, doc, live);
+  const double f4 = script_field<UNI>(cols, n_segs, seg, sq.col[4], n_fields > 4u, doc, live);
+  const double f5 = script_field<UNI>(cols, n_segs, seg, sq.col[5], n_fields > 5u, doc, live);
+  const double f6 = script_field<UNI>(cols, n_segs, seg, sq.col[6], n_fields > 6u, doc, live);
+  const double f7 = script_field<UNI>(cols, n_segs, seg, sq.col[7], n_fields > 7u, doc, live);
+  // The stack: `top` is its highest live slot, s0 .. s6 the slots below it (slot 7 can only ever be the top).  An
+  // instruction's result is the new top: a push at slot `at` first puts the old top, slot at - 1, away; an operator
+  // at slot `at` reads a = slot at from the registers and b = slot at + 1 = the top; NEG works on the top alone.
+  double top = 0.0, s0 = 0.0, s1 = 0.0, s2 = 0.0, s3 = 0.0, s4 = 0.0, s5 = 0.0, s6 = 0.0;
+  bool none = false;
+  for (uint32_t i = 0; i < n_instrs; i++) {
+    const ScriptInstr in = load_const(prog + i);
+    const uint32_t code = rfl(in.code);
+    const uint32_t op = code & 0xFFu, at = (code >> 8) & 0xFFu;
+    double r;
+    if (op <= kScPushScore) {
+      const uint32_t below = at - 1u;  // (at 0: no slot)
+      s0 = below == 0u ? top : s0;
+      s1 = below == 1u ? top : s1;
+      s2 = below == 2u ? top : s2;
+      s3 = below == 3u ? top : s3;
+      s4 = below == 4u ? top : s4;
+      s5 = below == 5u ? top : s5;
+      s6 = below == 6u ? top : s6;
+      if (op == kScPushConst) r = in.value;
+      else if (op == kScPushField) r = script_pick((code >> 16) & 0xFFu, f0, f1, f2, f3, f4, f5, f6, f7);
+      else r = base_score;
+      // (a push is not checked, as in the reference: `1 / _score` of an infinite base score is 0.0, not NONE)
+    } else {
+      if (op == kScNeg) {
+        r = -top;
+      } else {
+        const double a = script_pick(at, s0, s1, s2, s3, s4, s5, s6, s6), b = top;
+        if (op == kScAdd) {
+          r = a + b;
+        } else if (op == kScSub) {
+          r = a - b;
+        } else if (op == kScMul) {
+          r = a * b;
+        } else {
+          none = none || b == 0.0;
+          r = a / b;
+        }
+      }
+      none = none || !isfinite(r);
+    }
+    top = r;
+  }
+  const float v = (float)top;  // (a well-formed program ends with one value)
+  none = none || !isfinite(v);
+  const float score = v * sq.boost;
+  none = none || !isfinite(score);
+  none_out = none;
+  return score;
+}
+
+#ifndef SLG_SCRIPT_DEVICE_FUNCTIONS_ONLY  // (a unit that calls script_candidate alone, slg_explain.hip, compiles no second script_kernel)
 static __global__ void __launch_bounds__(kScriptThreads) script_kernel(ScriptParams p) {
   const uint32_t lane = threadIdx.x & 63u;
   const uint32_t s = rfl(blockIdx.x * (kScriptThreads / 64) + (threadIdx.x >> 6));
@@ -106,66 +176,13 @@ static __global__ void __launch_bounds__(kScriptThreads) script_kernel(ScriptPar
     const uint2 c = clause_candidate(sl, base + lane);
     const bool live = c.y != 0xFFFFFFFFu;  // (a dropped entry stays dropped)
     const uint32_t doc = c.y;
-    const double base_score = (double)fscore_base(c.x);
-    // the doc's first value of every distinct field of the query, 0.0 without one
-    const double f0 = script_field(p.cols, p.c.n_segs, sl.seg, sq.col[0], n_fields > 0u, doc, live);
-    const double f1 = script_field(p.cols, p.c.n_segs, sl.seg, sq.col[1], n_fields > 1u, doc, live);
-    const double f2 = script_field(p.cols, p.c.n_segs, sl.seg, sq.col[2], n_fields > 2u, doc, live);
-    const double f3 = script_field(p.cols, p.c.n_segs, sl.seg, sq.col[3], n_fields > 3u, doc, live);
-    const double f4 = script_field(p.cols, p.c.n_segs, sl.seg, sq.col[4], n_fields > 4u, doc, live);
-    const double f5 = script_field(p.cols, p.c.n_segs, sl.seg, sq.col[5], n_fields > 5u, doc, live);
-    const double f6 = script_field(p.cols, p.c.n_segs, sl.seg, sq.col[6], n_fields > 6u, doc, live);
-    const double f7 = script_field(p.cols, p.c.n_segs, sl.seg, sq.col[7], n_fields > 7u, doc, live);
-    // The stack: `top` is its highest live slot, s0 .. s6 the slots below it (slot 7 can only ever be the top).  An
-    // instruction's result is the new top: a push at slot `at` first puts the old top, slot at - 1, away; an operator
-    // at slot `at` reads a = slot at from the registers and b = slot at + 1 = the top; NEG works on the top alone.
-    double top = 0.0, s0 = 0.0, s1 = 0.0, s2 = 0.0, s3 = 0.0, s4 = 0.0, s5 = 0.0, s6 = 0.0;
-    bool none = false;
-    for (uint32_t i = 0; i < n_instrs; i++) {
-      const ScriptInstr in = load_const(prog + i);
-      const uint32_t code = rfl(in.code);
-      const uint32_t op = code & 0xFFu, at = (code >> 8) & 0xFFu;
-      double r;
-      if (op <= kScPushScore) {
-        const uint32_t below = at - 1u;  // (at 0: no slot)
-        s0 = below == 0u ? top : s0;
-        s1 = below == 1u ? top : s1;
-        s2 = below == 2u ? top : s2;
-        s3 = below == 3u ? top : s3;
-        s4 = below == 4u ? top : s4;
-        s5 = below == 5u ? top : s5;
-        s6 = below == 6u ? top : s6;
-        if (op == kScPushConst) r = in.value;
-        else if (op == kScPushField) r = script_pick((code >> 16) & 0xFFu, f0, f1, f2, f3, f4, f5, f6, f7);
-        else r = base_score;
-        // (a push is not checked, as in the reference: `1 / _score` of an infinite base score is 0.0, not NONE)
-      } else {
-        if (op == kScNeg) {
-          r = -top;
-        } else {
-          const double a = script_pick(at, s0, s1, s2, s3, s4, s5, s6, s6), b = top;
-          if (op == kScAdd) {
-            r = a + b;
-          } else if (op == kScSub) {
-            r = a - b;
-          } else if (op == kScMul) {
-            r = a * b;
-          } else {
-            none = none || b == 0.0;
-            r = a / b;
-          }
-        }
-        none = none || !isfinite(r);
-      }
-      top = r;
-    }
-    const float v = (float)top;  // (a well-formed program ends with one value)
-    none = none || !isfinite(v);
-    const float score = v * sq.boost;
-    none = none || !isfinite(score);
+    bool none;
+    const float score = script_candidate<true>(sq, prog, n_instrs, n_fields, p.cols, p.c.n_segs, sl.seg, doc, live,
+                                               fscore_base(c.x), none);
     clause_keep(sl, make_uint2(ordered_score(score), doc), live, live && !none);
   }
   clause_finish(p.c, s, sl, lane);
 }
+#endif
 
 }  // namespace slg

@@ -239,6 +239,7 @@ int run_sharded_impl(slg_batch *b, slg_shard_group *g, bool have_seq, uint64_t s
       if (timed) SLG_HIP(hipEventRecord(b->ev_shard[3], st));
       b->shard_group = g;
       b->shard_timed = timed;
+      b->last_sharded = true;
     }
   });
   if (rc == SLG_OK) rc = rc2;

@@ -2001,6 +2001,24 @@ class PreparedBatch:
         from .highlight import highlight_batch
         return highlight_batch(self._lib, self._h, self.fetch()[3], specs)
 
+    def explain(self, rows: int) -> dict:
+        """slg_batch_explain: the first min(rows, count[q]) rows of every query explained, against the index state
+        the batch was prepared on -> the raw arrays, by the names of slg_explain_out: base_score, final_score,
+        n_functions [nq, rows]; fn_type, fn_field, fn_value [nq, rows, MAX_EXPLAIN_FUNCS]; a rescore batch also
+        rescored, rescore_score, combined_score [nq, rows].  Rows at or beyond a query's count are zero.  The batch
+        must have run; explain.shape() turns the arrays into the reference's JSON form."""
+        nq, nf = self.nq, N.MAX_EXPLAIN_FUNCS
+        r = max(int(rows), 1)  # (rows 0 is refused by the library: the arrays only have to exist)
+        out = dict(base_score=np.zeros((nq, r), np.float32), final_score=np.zeros((nq, r), np.float32),
+                   n_functions=np.zeros((nq, r), np.uint32), fn_type=np.zeros((nq, r, nf), np.uint32),
+                   fn_field=np.zeros((nq, r, nf), np.int32), fn_value=np.zeros((nq, r, nf), np.float32))
+        if getattr(self, "is_rescore", False):  # (a ScanBatch has no such kind: the library refuses it by name)
+            out.update(rescored=np.zeros((nq, r), np.uint32), rescore_score=np.zeros((nq, r), np.float32),
+                       combined_score=np.zeros((nq, r), np.float32))
+        arg = N.ExplainOut(**{name: a.ctypes.data for name, a in out.items()})
+        N.check(self._lib.slg_batch_explain(self._h, int(rows), C.addressof(arg)))
+        return out
+
 
 class ScanBatch(PreparedBatch):
     """A planned batch of unscored root queries — match_all, constant_score, rank_feature — whose candidates come

@@ -1478,6 +1478,54 @@ int slg_vector_search_batch_device(slg_index *index, uint32_t nq, uint32_t n_cla
                                    float *d_out_vec_score, uint32_t *d_out_count, uint64_t *d_out_total);
 
 /*
+ * Two-pass vector search over a reduced-precision copy of the store.
+ *
+ * slg_index_quantize_vector_field builds, on the device, a bf16 copy of every segment's store of vector field
+ * `field` (0 = the field of the segment descriptors, else an id of slg_index_add_vector_field): each f32 value
+ * rounded to nearest even (a NaN stays a NaN, +-inf stays +-inf, an f32 denormal rounds like any other value),
+ * rows in the store's order and shared vec_offsets, each row padded with zeros, and beside each row its f32
+ * squared norm, summed left to right over the f32 row.  The copy is part of the index state: it costs half the
+ * store's bytes again, slg_index_update_deleted leaves it alone, slg_index_remove_segment drops that segment's,
+ * and slg_index_add_segment quantises the new segment's field-0 store when field 0 has a copy (other fields hold
+ * no vectors for a new segment).  Calling it again for the same field does nothing and returns 0; a field id that
+ * does not exist: SLG_ERR_INVALID.
+ *
+ * slg_index_fetch_vector_copy reads a segment's copy back: up to rows_cap rows of vec_dim bf16 bit patterns each
+ * (unpadded, row-major) into out_u16 and as many norms into out_norm; it returns the number of rows the copy
+ * holds (0: the segment has no vectors in the field; the arrays may be NULL when rows_cap is 0), or a negative
+ * error code (SLG_ERR_INVALID: the field has no copy, or no such segment).
+ *
+ * slg_vector_search_batch_approx[_device]: the arguments, outputs and checks of slg_vector_search_batch[_device],
+ * plus refine.  Per clause, a first pass scores every doc from the bf16 copy (queries rounded to bf16, products
+ * on v_mfma_f32_16x16x32_bf16 with f32 accumulation; L2 as |x|^2 + |q|^2 - 2 x.q from the f32 norms) and keeps the
+ * best `refine`; a second pass scores those again from the f32 store in the exact scan's own arithmetic and keeps
+ * the best cand_size; union, blend and top k_out follow as in the exact call.
+ *   - Every returned score (out_score, out_vec_score) is bit for bit the exact call's score of that doc against
+ *     the same clause lists; only the choice of the docs that reach the second pass is approximate.
+ *   - A doc of the exact call's clause list can be missing from the list only if its exact score lies within the
+ *     first pass's error of the score at the `refine` boundary (cosine of unit vectors: below 2^-7 * |boost|).
+ *   - refine >= the number of live docs with a vector in the field makes the call identical to the exact one.
+ * refine outside cand_size..SLG_MAX_VECTOR_CANDIDATES: SLG_ERR_UNSUPPORTED (checked first); a clause whose field
+ * has no copy: SLG_ERR_INVALID, the message names the field; all before any device work.  The _device form is
+ * asynchronous on the index stream and makes no host round trip between the passes.  out_total is the union size
+ * of the refined cand_size lists.
+ */
+int slg_index_quantize_vector_field(slg_index *index, uint32_t field);
+int slg_index_fetch_vector_copy(slg_index *index, uint32_t field, uint32_t seg, uint16_t *out_u16, float *out_norm,
+                                uint32_t rows_cap);
+int slg_vector_search_batch_approx(slg_index *index, uint32_t nq, uint32_t n_clauses, const uint32_t *clause_field,
+                                   const float *qvecs, const float *alpha, const float *boost,
+                                   const int32_t *q_filter, uint32_t cand_size, uint32_t refine, uint32_t k_out,
+                                   uint32_t *out_doc, uint32_t *out_seg, float *out_score, float *out_vec_score,
+                                   uint32_t *out_count, uint64_t *out_total);
+int slg_vector_search_batch_approx_device(slg_index *index, uint32_t nq, uint32_t n_clauses,
+                                          const uint32_t *clause_field, const float *d_qvecs, const float *d_alpha,
+                                          const float *d_boost, const int32_t *d_q_filter, uint32_t cand_size,
+                                          uint32_t refine, uint32_t k_out, uint32_t *d_out_doc, uint32_t *d_out_seg,
+                                          float *d_out_score, float *d_out_vec_score, uint32_t *d_out_count,
+                                          uint64_t *d_out_total);
+
+/*
  * Hybrid text + vector search: one request with a text query and vector clauses (api/reader.rs:2754-2775:
  * collect_vector_maps with require_text_match = true, then merge_vector_hits, :2474-2537).  Per query:
  *   1. the matched set M = every doc the text query matches that is not deleted and passes q_filter (and

@@ -505,6 +505,19 @@ extern "C" {
         d_qvecs: *const c_float, d_alpha: *const c_float, d_boost: *const c_float, d_q_filter: *const i32,
         cand_size: u32, k_out: u32, d_out_doc: *mut u32, d_out_seg: *mut u32, d_out_score: *mut c_float,
         d_out_vec_score: *mut c_float, d_out_count: *mut u32, d_out_total: *mut u64) -> c_int;
+    // two-pass vector search: a bf16 copy of a field's stores, a first pass over it, exact scores for `refine` docs
+    pub fn slg_index_quantize_vector_field(index: *mut slg_index, field: u32) -> c_int;
+    pub fn slg_index_fetch_vector_copy(index: *mut slg_index, field: u32, seg: u32, out_u16: *mut u16,
+        out_norm: *mut c_float, rows_cap: u32) -> c_int;
+    pub fn slg_vector_search_batch_approx(index: *mut slg_index, nq: u32, n_clauses: u32, clause_field: *const u32,
+        qvecs: *const c_float, alpha: *const c_float, boost: *const c_float, q_filter: *const i32, cand_size: u32,
+        refine: u32, k_out: u32, out_doc: *mut u32, out_seg: *mut u32, out_score: *mut c_float,
+        out_vec_score: *mut c_float, out_count: *mut u32, out_total: *mut u64) -> c_int;
+    pub fn slg_vector_search_batch_approx_device(index: *mut slg_index, nq: u32, n_clauses: u32,
+        clause_field: *const u32, d_qvecs: *const c_float, d_alpha: *const c_float, d_boost: *const c_float,
+        d_q_filter: *const i32, cand_size: u32, refine: u32, k_out: u32, d_out_doc: *mut u32, d_out_seg: *mut u32,
+        d_out_score: *mut c_float, d_out_vec_score: *mut c_float, d_out_count: *mut u32,
+        d_out_total: *mut u64) -> c_int;
     // hybrid text + vector search (merge_vector_hits): prepare, run (slg_batch_run), then the vector side
     pub fn slg_batch_prepare_hybrid(index: *mut slg_index, nq: u32, q_offsets: *const u32, q_term_ids: *const u32,
         q_weights: *const c_float, plans: *const slg_score_plans, q_filter: *const i32, k: u32,

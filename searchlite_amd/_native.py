@@ -554,6 +554,12 @@ def load():
         "slg_vector_search_batch": (i32, [vp, u32, u32, vp, vp, vp, vp, vp, u32, u32, vp, vp, vp, vp, vp, vp]),
         "slg_vector_search_batch_device": (i32, [vp, u32, u32, vp, vp, vp, vp, vp, u32, u32, vp, vp, vp, vp,
                                                  vp, vp]),
+        "slg_index_quantize_vector_field": (i32, [vp, u32]),
+        "slg_index_fetch_vector_copy": (i32, [vp, u32, u32, vp, vp, u32]),
+        "slg_vector_search_batch_approx": (i32, [vp, u32, u32, vp, vp, vp, vp, vp, u32, u32, u32, vp, vp, vp, vp,
+                                                 vp, vp]),
+        "slg_vector_search_batch_approx_device": (i32, [vp, u32, u32, vp, vp, vp, vp, vp, u32, u32, u32, vp, vp, vp,
+                                                        vp, vp, vp]),
         "slg_batch_prepare_hybrid": (vp, [vp, u32, vp, vp, vp, vp, vp, u32, i32]),
         "slg_batch_hybrid_device": (i32, [vp, u32, vp, vp, vp, vp, u32, u32, vp, vp, vp, vp, vp, vp]),
         "slg_search_batch_hybrid": (i32, [vp, u32, vp, vp, vp, vp, vp, u32, i32, u32, vp, vp, vp, vp, u32, u32,

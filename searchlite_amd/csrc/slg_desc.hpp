@@ -145,6 +145,15 @@ struct VecSegDev {
   int32_t metric;  // 0 cosine, 1 l2
   uint32_t pad;
 };
+// The bf16 copy of a segment's store (slg_index_quantize_vector_field; slg_vsearch_approx.hpp): the rows of
+// VecSegDev::values in the same order, rounded to nearest even, each padded with zeros to dim_pad values, and
+// the f32 squared norm of each f32 row.  rows == nullptr: the segment has no vectors in the field.
+struct VecCopyDev {
+  const uint16_t *rows;  // [rows * dim_pad] bf16 bit patterns
+  const float *norms;    // [rows]
+  uint32_t dim_pad;
+  uint32_t pad;
+};
 
 // ---- query rescore (slg_batch_prepare_rescore; kernel: slg_rescore.hpp, planner: slg_plan.cpp) -------
 // The rescore terms of query q are terms[(term_begin + i) * n_segs + s], i = 0 .. n_terms - 1, for

@@ -314,13 +314,24 @@ struct SegHost {
 // shared stores (null: the segment has no vectors in the field)
 struct VecSegStore {
   DevBuf offsets, values;
-  uint32_t dim = 0;
+  uint32_t dim = 0, n_rows = 0;
 };
 struct VecFieldHost {
   uint32_t dim = 0;
   int32_t metric = 0;
   std::vector<std::shared_ptr<VecSegStore>> per_seg;
   DevBuf d_vsegs;  // slg::VecSegDev[n_segs] of the state this object belongs to
+};
+
+// the bf16 copy of a vector field (slg_index_quantize_vector_field; field 0 too): per segment the shared copy of
+// its store (null: the segment has no vectors in the field), in the store's row order
+struct VecCopySeg {
+  DevBuf rows, norms;  // u16[n_rows * dim_pad] bf16, zero-padded rows | f32[n_rows] squared norms of the f32 rows
+  uint32_t n_rows = 0, dim = 0, dim_pad = 0;
+};
+struct VecCopyField {
+  std::vector<std::shared_ptr<VecCopySeg>> per_seg;
+  DevBuf d_csegs;  // slg::VecCopyDev[n_segs] of the state this object belongs to
 };
 
 // a registered doc filter: per segment a reject bitmap (deleted | ~filter); null = the filter predates
@@ -458,6 +469,7 @@ struct IndexState {
   DevBuf d_doc_base;  // u32[n_segs + 1]: first flat doc of each segment (slg_vector_search_batch*)
   uint64_t total_docs = 0;
   std::vector<std::shared_ptr<VecFieldHost>> vfields;  // field id f >= 1 is vfields[f - 1]
+  std::map<uint32_t, std::shared_ptr<VecCopyField>> vcopies;  // by field id (0 too); own objects, shared copies
   std::vector<std::shared_ptr<FilterData>> filters;    // slot = filter id; null = free
   std::vector<const uint32_t *> reject_host;           // flattened [filter * n_segs + seg] device pointers
   DevBuf d_reject_table;                               // the same table on the device
@@ -1100,6 +1112,7 @@ struct VsCall {
   uint32_t dim[SLG_MAX_VECTOR_CLAUSES] = {}, coff[SLG_MAX_VECTOR_CLAUSES] = {};
   int32_t metric[SLG_MAX_VECTOR_CLAUSES] = {};
   const slg::VecSegDev *vsegs[SLG_MAX_VECTOR_CLAUSES] = {};
+  const slg::VecCopyDev *csegs[SLG_MAX_VECTOR_CLAUSES] = {};  // (slg_vector_search_batch_approx*) the fields' bf16 copies
   uint32_t q_floats = 0;
 };
 // ... and its arrays (host or device memory, as the entry says)
@@ -1116,6 +1129,9 @@ struct VsArgs {
 bool vs_prepare(slg_index *ix, uint32_t nq, uint32_t n_clauses, const uint32_t *clause_field, uint32_t cand_size,
                 uint32_t k_out, const VsArgs &a, bool host_filter, VsCall *vc,
                 std::shared_ptr<const IndexState> state = nullptr);
+// slg_vsearch.hip: the bf16 copy of one store of n_rows x dim f32 values on the device (vs_quantize_kernel on the
+// index stream, waited for); the caller holds the index's device
+std::shared_ptr<VecCopySeg> vs_quantize_store(slg_index *ix, const float *d_values, uint32_t n_rows, uint32_t dim);
 // slg_vsearch.hip: the steps a hybrid call (slg_hybrid.hip) shares with the vector search, whose kernels they
 // run.  HyWork: the clause lists and sort space of one call, laid out over one block (base null: the size only);
 // cnt = run_cnt [clause][nq] then key_cnt [clause][nq], zeroed by the caller

@@ -273,6 +273,17 @@ void finish_state(slg_index *ix, IndexState &s) {
     vf.d_vsegs.alloc(std::max<size_t>(n_segs, 1) * sizeof(slg::VecSegDev), &ix->pool);
     if (n_segs) SLG_HIP(hipMemcpy(vf.d_vsegs.p, fv.data(), n_segs * sizeof(slg::VecSegDev), hipMemcpyHostToDevice));
   }
+  for (auto &vcp : s.vcopies) {  // (fresh copies too)
+    VecCopyField &vc = *vcp.second;
+    vc.per_seg.resize(n_segs);
+    std::vector<slg::VecCopyDev> cv(n_segs, slg::VecCopyDev{nullptr, nullptr, 0u, 0u});
+    for (size_t i = 0; i < n_segs; i++)
+      if (vc.per_seg[i])
+        cv[i] = slg::VecCopyDev{vc.per_seg[i]->rows.as<uint16_t>(), vc.per_seg[i]->norms.as<float>(),
+                                vc.per_seg[i]->dim_pad, 0u};
+    vc.d_csegs.alloc(std::max<size_t>(n_segs, 1) * sizeof(slg::VecCopyDev), &ix->pool);
+    if (n_segs) SLG_HIP(hipMemcpy(vc.d_csegs.p, cv.data(), n_segs * sizeof(slg::VecCopyDev), hipMemcpyHostToDevice));
+  }
   s.positions.resize(n_segs);  // (a new state of a new segment list: no positions where none were set)
   std::vector<slg::PosSegDev> pd(n_segs);
   for (size_t i = 0; i < n_segs; i++)
@@ -341,6 +352,11 @@ std::unique_ptr<IndexState> copy_state(const IndexState &cur) {
     c->metric = vf->metric;
     c->per_seg = vf->per_seg;
     n->vfields.push_back(std::move(c));
+  }
+  for (auto &vc : cur.vcopies) {  // the same for the bf16 copies' d_csegs
+    auto c = std::make_shared<VecCopyField>();
+    c->per_seg = vc.second->per_seg;
+    n->vcopies.emplace(vc.first, std::move(c));
   }
   for (auto &tf : cur.text_fields) {  // the same for the text fields' d_tsegs
     auto c = std::make_shared<TextFieldHost>();
@@ -411,6 +427,7 @@ void reshape_per_segment(IndexState &ns, Op op) {
     nc.second = std::move(nf);
   }
   for (auto &vf : ns.vfields) op(vf->per_seg);  // (the field objects of a new state are fresh copies)
+  for (auto &vc : ns.vcopies) op(vc.second->per_seg);  // (fresh copies too)
   op(ns.positions);  // (the state's own vector; the stores are shared)
   op(ns.terms);
   for (auto &tf : ns.text_fields) op(tf.second->per_seg);  // (fresh copies too)
@@ -453,6 +470,11 @@ size_t state_device_bytes(const IndexState &s) {
     n += vf->d_vsegs.bytes;
     for (auto &v : vf->per_seg)
       if (v) n += v->offsets.bytes + v->values.bytes;
+  }
+  for (auto &vc : s.vcopies) {
+    n += vc.second->d_csegs.bytes;
+    for (auto &c : vc.second->per_seg)
+      if (c) n += c->rows.bytes + c->norms.bytes;
   }
   return n;
 }
@@ -1556,6 +1578,11 @@ int slg_index_add_segment(slg_index *ix, const slg_segment_desc *seg) {
       // unusable until it is registered again
       const size_t n_segs = ns.segs.size();
       reshape_per_segment(ns, [n_segs](auto &per_seg) { per_seg.resize(n_segs); });
+      // ... but the new segment's own store (field 0) is quantised here when field 0 has a bf16 copy
+      const PostingStore &ps = *ns.segs.back()->store;
+      const auto c0 = ns.vcopies.find(0u);
+      if (c0 != ns.vcopies.end() && ps.vec_dim)
+        c0->second->per_seg[n_segs - 1] = vs_quantize_store(ix, ps.d_vec_values.as<float>(), ps.vec_rows, ps.vec_dim);
       ord = (int)n_segs - 1;
     });
   });
@@ -1648,6 +1675,7 @@ int slg_index_add_vector_field(slg_index *ix, const slg_vector_field_desc *per_s
         vs->values.alloc(vb, &ix->pool);
         if (vb) SLG_HIP(hipMemcpy(vs->values.p, d.vec_values, vb, hipMemcpyHostToDevice));
         vs->dim = d.vec_dim;
+        vs->n_rows = d.vec_rows;
         vf->per_seg[s] = std::move(vs);
       }
       ns.vfields.push_back(std::move(vf));
@@ -1655,6 +1683,63 @@ int slg_index_add_vector_field(slg_index *ix, const slg_vector_field_desc *per_s
     });
   });
   return rc == SLG_OK ? id : rc;
+}
+
+int slg_index_quantize_vector_field(slg_index *ix, uint32_t field) {
+  return guarded([&] {
+    SLG_REQUIRE(ix != nullptr, "index is NULL");
+    {
+      const auto cur = ix->snapshot();
+      SLG_REQUIRE(field <= cur->vfields.size(), "unknown vector field id");
+      if (cur->vcopies.count(field)) return;  // (copies follow the index's updates: nothing to redo)
+    }
+    update_state(ix, false, [&](const IndexState &cur, IndexState &ns) {
+      SLG_REQUIRE(field <= cur.vfields.size(), "unknown vector field id");
+      if (cur.vcopies.count(field)) return;
+      const size_t n_segs = cur.segs.size();
+      auto vc = std::make_shared<VecCopyField>();
+      vc->per_seg.resize(n_segs);
+      for (size_t s = 0; s < n_segs; s++) {
+        if (field == 0) {
+          const PostingStore &ps = *cur.segs[s]->store;
+          if (ps.vec_dim)
+            vc->per_seg[s] = vs_quantize_store(ix, ps.d_vec_values.as<float>(), ps.vec_rows, ps.vec_dim);
+        } else {
+          const VecFieldHost &vf = *cur.vfields[field - 1];
+          if (s < vf.per_seg.size() && vf.per_seg[s]) {
+            const VecSegStore &st = *vf.per_seg[s];
+            vc->per_seg[s] = vs_quantize_store(ix, st.values.as<float>(), st.n_rows, st.dim);
+          }
+        }
+      }
+      ns.vcopies[field] = std::move(vc);
+    });
+  });
+}
+
+int slg_index_fetch_vector_copy(slg_index *ix, uint32_t field, uint32_t seg, uint16_t *out_u16, float *out_norm,
+                                uint32_t rows_cap) {
+  int rows = 0;
+  const int rc = guarded([&] {
+    SLG_REQUIRE(ix != nullptr, "index is NULL");
+    const auto st = ix->snapshot();
+    const auto it = st->vcopies.find(field);
+    SLG_REQUIRE(it != st->vcopies.end(), "vector field " + std::to_string(field) + " has no bf16 copy");
+    SLG_REQUIRE(seg < st->segs.size(), "no such segment");
+    const VecCopyField &vc = *it->second;
+    if (seg >= vc.per_seg.size() || !vc.per_seg[seg]) return;  // (no vectors of the field in this segment)
+    const VecCopySeg &c = *vc.per_seg[seg];
+    SLG_REQUIRE(c.n_rows <= 0x7FFFFFFFu, "more than 2^31 - 1 rows");
+    rows = (int)c.n_rows;
+    const uint32_t n = std::min(c.n_rows, rows_cap);
+    if (n == 0) return;
+    SLG_REQUIRE(out_u16 != nullptr && out_norm != nullptr, "output arrays are NULL");
+    DeviceGuard g(ix->device);
+    SLG_HIP(hipMemcpy2D(out_u16, (size_t)c.dim * 2, c.rows.p, (size_t)c.dim_pad * 2, (size_t)c.dim * 2, n,
+                        hipMemcpyDeviceToHost));
+    SLG_HIP(hipMemcpy(out_norm, c.norms.p, (size_t)n * 4, hipMemcpyDeviceToHost));
+  });
+  return rc == SLG_OK ? rows : rc;
 }
 
 }  // extern "C"

@@ -106,6 +106,113 @@ inline size_t vs_scan_lds_bytes(bool topk, uint32_t cap) {
   return (size_t)(kVsTileDocs + kVsTileQ) * kVsRow * 4 + kVsTileDocs * 8 + (topk ? (size_t)kVsTileQ * cap * 8 : 0);
 }
 
+// ---- the epilogue of a scan tile, shared by vs_scan_kernel and the bf16 first pass of the two-pass search
+//      (slg_vsearch_approx.hpp): both leave the scores of a 64 x 128 tile in the C/D layout of the 16x16 MFMAs ----
+// what a lane carries from tile to tile: its query (16w + qc of the workgroup's 64), the query's boost and
+// filter, and (top-k form) the entries its query's LDS buffer holds and the threshold key
+struct VsEpilogue {
+  uint32_t lane, w, qc, g;
+  uint32_t myq;
+  float bst;
+  int32_t flt;
+  uint32_t cap;
+  uint64_t *s_buf, *my_buf;   // [64][cap] of the workgroup; this lane's query's row
+  uint32_t cnt, th_hi, th_lo;
+};
+// is (seg, doc) deleted, or rejected by filter flt (< 0: none)?  Keeps the lane's reject bitmap of the segment at hand
+struct VsReject {
+  const uint32_t *rej = nullptr;
+  uint32_t rej_seg = 0xFFFFFFFFu;
+  bool rej_all = false;
+  __device__ __forceinline__ bool operator()(const VsScanParams &p, const int32_t flt, uint32_t seg, uint32_t doc) {
+    if (seg != rej_seg) {
+      rej_seg = seg;
+      rej_all = false;
+      if (flt < 0) {
+        rej = p.segs[seg].deleted;
+      } else if ((uint32_t)flt < p.n_filters) {
+        rej = p.reject_table[(size_t)flt * p.n_segs + seg];
+        rej_all = rej == nullptr;  // (a filter without a bitmap for this segment matches nothing)
+      } else {
+        rej = nullptr;
+        rej_all = true;  // (no such filter: matches nothing)
+      }
+    }
+    return rej_all || (rej && ((rej[doc >> 5] >> (doc & 31)) & 1u));
+  }
+};
+// the fused top-k epilogue of one tile of 128 docs from flat doc `base`: sim(acc[ti][r], i) is the similarity of this
+// lane's query and doc i = 16 ti + 4 g + r of the tile (s_seg[i] = its segment or ~0: no vector, s_doc[i] = the doc
+// in it).  Times the boost it becomes a key, and the keys that beat the threshold go to the query's buffer.
+// (The store form stays inline in each scan kernel: as a function it costs vs_scan_kernel<1, false> two more
+// AGPR copies.)
+template <typename Sim>
+__device__ __forceinline__ void vs_tile_topk(const VsScanParams &p, VsEpilogue &e, const uint32_t base,
+                                             const uint32_t *s_seg, const uint32_t *s_doc, const f32x4_t (&acc)[8],
+                                             Sim &&sim) {
+  const uint32_t lane = e.lane, w = e.w, qc = e.qc, g = e.g, cap = e.cap;
+  const bool q_ok = e.myq < p.nq;
+  const int32_t flt = e.flt;
+  const float bst = e.bst;
+  uint32_t cnt = e.cnt, th_hi = e.th_hi, th_lo = e.th_lo;
+  VsReject rejected;
+#pragma unroll
+  for (int ti = 0; ti < 8; ti++) {
+#pragma unroll
+    for (int r = 0; r < 4; r++) {
+      const uint32_t i = 16 * ti + 4 * g + r;
+      float s = sim(acc[ti][r], i);
+      s = s * bst;
+      const uint32_t seg = s_seg[i];
+      const uint32_t hi = ordered_score(s), lo = ~(base + i);
+      auto beats = [&]() { return hi > th_hi || (hi == th_hi && lo > th_lo); };
+      bool pass = q_ok && seg != 0xFFFFFFFFu && beats();
+      if (__ballot(pass) == 0ull) continue;
+      pass = pass && !rejected(p, flt, seg, s_doc[i]);
+      // room for 4 more entries of every query of this wave
+      uint64_t need = __ballot(g == 0 && cnt + 4 > cap);
+      while (need) {
+        const uint32_t j = (uint32_t)__builtin_ctzll(need);
+        need &= need - 1;
+        const uint32_t n = rl(cnt, j);
+        uint64_t *b = e.s_buf + (size_t)(16 * w + j) * cap;
+        const uint32_t kept = vs_compact(b, n, p.k, lane);
+        if (qc == j) {
+          cnt = kept;
+          if (n >= p.k) {
+            const uint64_t kth = b[p.k - 1];
+            th_hi = (uint32_t)(kth >> 32);
+            th_lo = (uint32_t)kth;
+          }
+        }
+      }
+      pass = pass && beats();
+      const uint64_t m = __ballot(pass);
+      const uint32_t b0 = (uint32_t)(m >> qc) & 1u, b1 = (uint32_t)(m >> (16 + qc)) & 1u,
+                     b2 = (uint32_t)(m >> (32 + qc)) & 1u, b3 = (uint32_t)(m >> (48 + qc)) & 1u;
+      const uint32_t pre = (g > 0 ? b0 : 0u) + (g > 1 ? b1 : 0u) + (g > 2 ? b2 : 0u);
+      wave_fence();
+      if (pass) e.my_buf[cnt + pre] = ((uint64_t)hi << 32) | lo;
+      wave_fence();
+      cnt += b0 + b1 + b2 + b3;
+    }
+  }
+  e.cnt = cnt;
+  e.th_hi = th_hi;
+  e.th_lo = th_lo;
+}
+
+// (top-k form, after the last tile) the chunk's partial list of each query: its k best, sorted
+__device__ __forceinline__ void vs_write_partials(const VsScanParams &p, const VsEpilogue &e, const uint32_t q0) {
+  for (uint32_t j = 0; j < 16; j++) {
+    const uint32_t q = q0 + 16 * e.w + j;
+    if (q >= p.nq) break;
+    uint64_t *b = e.s_buf + (size_t)(16 * e.w + j) * e.cap;
+    const uint32_t kept = vs_compact(b, rl(e.cnt, j), p.k, e.lane);
+    p.out[((size_t)q * p.n_chunks + blockIdx.y) * kVsSmallK + e.lane] = e.lane < kept ? b[e.lane] : 0ull;
+  }
+}
+
 // METRIC 0: cosine on the matrix cores; 1: L2 on the VALU.  TOPK: fused top-k (else: store keys).
 // Lane l of wave w holds, per tile t of 16 docs, the scores of query 16w + (l & 15) and docs
 // 16t + 4(l >> 4) + r, r < 4 (the D layout of v_mfma_f32_16x16x4_f32 with A = docs, B = queries).
@@ -127,9 +234,8 @@ __global__ void __launch_bounds__(256) vs_scan_kernel(VsScanParams p) {
   const bool q_ok = myq < p.nq;
   const float bst = q_ok && p.boost ? p.boost[(size_t)myq * p.n_clauses + p.clause] : 1.0f;
   const int32_t flt = q_ok && p.q_filter ? p.q_filter[myq] : -1;
-  uint32_t cnt = 0, th_hi = 0, th_lo = 0;  // (TOPK) buffered entries, threshold key
   const uint32_t cap = p.cap;
-  uint64_t *my_buf = s_buf + (size_t)(16 * w + qc) * cap;
+  VsEpilogue e{lane, w, qc, g, myq, bst, flt, cap, s_buf, s_buf + (size_t)(16 * w + qc) * cap, 0, 0, 0};
   // this thread's query rows for the staging loads: rows (t >> 3) + 32 j
   const float *qrow[2];
 #pragma unroll
@@ -225,84 +331,29 @@ __global__ void __launch_bounds__(256) vs_scan_kernel(VsScanParams p) {
       }
     }
     // ---- epilogue: metric_similarity (vectors/mod.rs:107-120), * boost (api/reader.rs:2421) ----
-    const uint32_t *rej = nullptr;  // this lane's reject bitmap for the segment at hand
-    uint32_t rej_seg = 0xFFFFFFFFu;
-    bool rej_all = false;
-    auto rejected = [&](uint32_t seg, uint32_t doc) -> bool {
-      if (seg != rej_seg) {
-        rej_seg = seg;
-        rej_all = false;
-        if (flt < 0) {
-          rej = p.segs[seg].deleted;
-        } else if ((uint32_t)flt < p.n_filters) {
-          rej = p.reject_table[(size_t)flt * p.n_segs + seg];
-          rej_all = rej == nullptr;  // (a filter without a bitmap for this segment matches nothing)
-        } else {
-          rej = nullptr;
-          rej_all = true;  // (no such filter: matches nothing)
-        }
-      }
-      return rej_all || (rej && ((rej[doc >> 5] >> (doc & 31)) & 1u));
-    };
+    const auto sim = [](float s, uint32_t) { return METRIC == 0 ? (s != s ? 0.0f : s) : -sqrtf(s); };
+    if constexpr (TOPK) {
+      vs_tile_topk(p, e, base, s_seg, s_doc, acc, sim);
+    } else {
+      VsReject rejected;
 #pragma unroll
-    for (int ti = 0; ti < 8; ti++) {
+      for (int ti = 0; ti < 8; ti++) {
 #pragma unroll
-      for (int r = 0; r < 4; r++) {
-        const uint32_t i = 16 * ti + 4 * g + r;
-        float s = acc[ti][r];
-        s = METRIC == 0 ? (s != s ? 0.0f : s) : -sqrtf(s);
-        s = s * bst;
-        const uint32_t seg = s_seg[i];
-        const uint32_t hi = ordered_score(s), lo = ~(base + i);
-        if (!TOPK) {
-          const bool ok = q_ok && seg != 0xFFFFFFFFu && !rejected(seg, s_doc[i]);
+        for (int r = 0; r < 4; r++) {
+          const uint32_t i = 16 * ti + 4 * g + r;
+          const float s = sim(acc[ti][r], i) * bst;
+          const uint32_t seg = s_seg[i];
+          const uint32_t hi = ordered_score(s), lo = ~(base + i);
+          const bool ok = q_ok && seg != 0xFFFFFFFFu && !rejected(p, flt, seg, s_doc[i]);
           if (q_ok) p.out[(size_t)myq * p.out_stride + (base + i - p.tile_begin * kVsTileDocs)] =
               ok ? (((uint64_t)hi << 32) | lo) : 0ull;
-          continue;
         }
-        auto beats = [&]() { return hi > th_hi || (hi == th_hi && lo > th_lo); };
-        bool pass = q_ok && seg != 0xFFFFFFFFu && beats();
-        if (__ballot(pass) == 0ull) continue;
-        pass = pass && !rejected(seg, s_doc[i]);
-        // room for 4 more entries of every query of this wave
-        uint64_t need = __ballot(g == 0 && cnt + 4 > cap);
-        while (need) {
-          const uint32_t j = (uint32_t)__builtin_ctzll(need);
-          need &= need - 1;
-          const uint32_t n = rl(cnt, j);
-          uint64_t *b = s_buf + (size_t)(16 * w + j) * cap;
-          const uint32_t kept = vs_compact(b, n, p.k, lane);
-          if (qc == j) {
-            cnt = kept;
-            if (n >= p.k) {
-              const uint64_t kth = b[p.k - 1];
-              th_hi = (uint32_t)(kth >> 32);
-              th_lo = (uint32_t)kth;
-            }
-          }
-        }
-        pass = pass && beats();
-        const uint64_t m = __ballot(pass);
-        const uint32_t b0 = (uint32_t)(m >> qc) & 1u, b1 = (uint32_t)(m >> (16 + qc)) & 1u,
-                       b2 = (uint32_t)(m >> (32 + qc)) & 1u, b3 = (uint32_t)(m >> (48 + qc)) & 1u;
-        const uint32_t pre = (g > 0 ? b0 : 0u) + (g > 1 ? b1 : 0u) + (g > 2 ? b2 : 0u);
-        wave_fence();
-        if (pass) my_buf[cnt + pre] = ((uint64_t)hi << 32) | lo;
-        wave_fence();
-        cnt += b0 + b1 + b2 + b3;
       }
     }
     __syncthreads();  // s_seg / s_doc of the next tile
   }
   if (!TOPK) return;
-  // ---- the chunk's partial list of each query: its k best, sorted ----
-  for (uint32_t j = 0; j < 16; j++) {
-    const uint32_t q = q0 + 16 * w + j;
-    if (q >= p.nq) break;
-    uint64_t *b = s_buf + (size_t)(16 * w + j) * cap;
-    const uint32_t kept = vs_compact(b, rl(cnt, j), p.k, lane);
-    p.out[((size_t)q * p.n_chunks + blockIdx.y) * kVsSmallK + lane] = lane < kept ? b[lane] : 0ull;
-  }
+  vs_write_partials(p, e, q0);
 }
 
 // block-wide bitonic sort, descending, of P (a power of two) keys at a (LDS or global memory)

@@ -1114,6 +1114,60 @@ class GpuIndex:
             _ptr(doc), _ptr(seg), _ptr(score), _ptr(vec), _ptr(count), _ptr(total)))
         return doc, seg, score, vec, count, total
 
+    def quantize_vector_field(self, field: int = 0) -> None:
+        """Build the bf16 copy of vector field `field` on the device (slg_index_quantize_vector_field): what
+        vector_search_approx scans.  A second call for the same field does nothing."""
+        N.check(self._lib.slg_index_quantize_vector_field(self._h, int(field)))
+
+    def fetch_vector_copy(self, field: int, seg: int, dim: int):
+        """The bf16 copy of segment `seg`'s store of `field` (slg_index_fetch_vector_copy): (bf16 bit patterns
+        u16 [rows, dim], f32 squared norms [rows]), or None when the segment has no vectors in the field.  dim:
+        the field's dimension in that segment."""
+        rows = self._lib.slg_index_fetch_vector_copy(self._h, int(field), int(seg), None, None, 0)
+        if rows < 0:
+            N.check(rows)
+        if rows == 0:
+            return None
+        bits = np.zeros((rows, int(dim)), np.uint16)
+        norms = np.zeros(rows, np.float32)
+        rc = self._lib.slg_index_fetch_vector_copy(self._h, int(field), int(seg), _ptr(bits), _ptr(norms), rows)
+        if rc < 0:
+            N.check(rc)
+        return bits, norms
+
+    def vector_search_approx(self, clause_field, qvecs, alpha, cand_size: int, refine: int, k_out: int, boost=None,
+                             q_filter=None):
+        """Two-pass vector search (slg_vector_search_batch_approx): per clause the best `refine` docs of a scan of
+        the field's bf16 copy (quantize_vector_field) are scored again from the f32 store, and the best cand_size
+        of those form the clause's list.  Arguments and result as vector_search(); every returned score is the
+        exact call's, and refine >= the live docs with a vector makes the whole result the exact call's."""
+        cf = np.ascontiguousarray(clause_field, dtype=np.uint32)
+        nc = len(cf)
+        qvecs = np.ascontiguousarray(qvecs, dtype=np.float32)
+        nq = qvecs.shape[0]
+        alpha, bst = _f32(alpha, (nq, nc)), _f32(boost, (nq, nc))
+        flt = None if q_filter is None else np.ascontiguousarray(q_filter, dtype=np.int32)
+        doc = np.zeros((nq, k_out), np.uint32)
+        seg = np.zeros((nq, k_out), np.uint32)
+        score = np.zeros((nq, k_out), np.float32)
+        vec = np.zeros((nq, k_out), np.float32)
+        count = np.zeros(nq, np.uint32)
+        total = np.zeros(nq, np.uint64)
+        N.check(self._lib.slg_vector_search_batch_approx(
+            self._h, nq, nc, _ptr(cf), _ptr(qvecs), _ptr(alpha), _ptr(bst), _ptr(flt), int(cand_size), int(refine),
+            int(k_out), _ptr(doc), _ptr(seg), _ptr(score), _ptr(vec), _ptr(count), _ptr(total)))
+        return doc, seg, score, vec, count, total
+
+    def vector_search_approx_device(self, nq, clause_field, d_qvecs, d_alpha, d_boost, d_q_filter, cand_size, refine,
+                                    k_out, d_out_doc, d_out_seg, d_out_score, d_out_vec, d_out_count,
+                                    d_out_total) -> None:
+        """Device-pointer form of vector_search_approx (ints; d_boost / d_q_filter may be None; clause_field
+        stays a host array), asynchronous on the index stream."""
+        cf = np.ascontiguousarray(clause_field, dtype=np.uint32)
+        N.check(self._lib.slg_vector_search_batch_approx_device(
+            self._h, nq, len(cf), _ptr(cf), d_qvecs, d_alpha, d_boost, d_q_filter, int(cand_size), int(refine),
+            int(k_out), d_out_doc, d_out_seg, d_out_score, d_out_vec, d_out_count, d_out_total))
+
     def search_hybrid(self, q_offsets, q_terms, q_weights, k: int, clause_field, qvecs, alpha, cand_size: int,
                       k_out: int, boost=None, strategy: int = Wand, q_filter=None, **plans):
         """Hybrid text + vector search (merge_vector_hits, api/reader.rs:2474-2537) in one call: the BM25 top k

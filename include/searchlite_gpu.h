@@ -1526,6 +1526,75 @@ int slg_vector_search_batch_approx_device(slg_index *index, uint32_t nq, uint32_
                                           uint64_t *d_out_total);
 
 /*
+ * Vector search over an inverted-file (IVF) index of a vector field: probe the nearest lists, exact scores.
+ *
+ * slg_index_cluster_vector_field groups the docs of every segment that have a vector in `field` (0 = the field of
+ * the segment descriptors, else an id of slg_index_add_vector_field) into n_lists lists around the caller's
+ * centroids, used as given.  A doc goes to the centroid with the greatest metric_similarity(row, centroid) in the
+ * exact scan's own arithmetic (cosine: the fmaf chain with NaN -> 0; L2: -sqrt(sum (x - y)^2)); equal scores go to
+ * the lowest list id; deleted docs are assigned too (tombstones apply at search time); inside a list the docs
+ * ascend; an empty list is legal.  Assignment (an exact scan of the centroids with the store's rows as queries and
+ * a top-1) and list build (count, exclusive scan, ordered fill) run on the device and are deterministic.  The lists
+ * and the centroid tables are part of the index state: 4 bytes per doc with a vector plus the tables, no second
+ * copy of the store.  slg_index_update_deleted leaves them alone, slg_index_remove_segment drops that segment's,
+ * and a segment added by slg_index_add_segment is unclustered in every field.  Calling the function again builds
+ * a new state: n_lists 0 leaves (or makes) a segment unclustered, SLG_KEEP_VECTOR_LISTS keeps what the segment
+ * has (nothing to keep: it stays unclustered).  SLG_ERR_INVALID: no such field, n_segs other than the index's
+ * segment count, n_lists > 0 with NULL centroids or on a segment without vectors in the field;
+ * SLG_ERR_UNSUPPORTED: n_lists > SLG_MAX_VECTOR_LISTS; all before any device work.
+ *
+ * slg_index_fetch_vector_lists reads a segment's lists back: it returns n_lists (0: unclustered, or no vectors in
+ * the field) or a negative code (SLG_ERR_INVALID: no such field or segment), and writes, up to the caps,
+ * min(n_lists, lists_cap) + 1 entries of out_list_begin, the docs list after list into out_docs (docs_cap of them at
+ * most) and min(n_lists, lists_cap) rows of the centroid table as stored into out_centroids.  The arrays may be NULL
+ * when their caps are 0.
+ *
+ * slg_vector_search_batch_ivf[_device]: the arguments, outputs and checks of slg_vector_search_batch[_device], plus
+ * nprobe.  Per query q and clause c (field f):
+ *   1. the lists of all clustered segments of f form one list space ordered by (segment asc, list asc); a list's
+ *      key is metric_similarity(query, centroid) * boost[q][c] in the exact scan's arithmetic, and the best
+ *      min(nprobe, lists of f) by (key desc, segment asc, list asc) are probed (a negative boost probes the
+ *      farthest lists, where its best docs are);
+ *   2. the candidates are the docs of the probed lists and every doc of the unclustered segments of f, which are
+ *      scanned whole and do not count against nprobe;
+ *   3. of those, the docs that are live and pass q_filter[q] are scored as in the exact call, and the best
+ *      cand_size by (score desc, segment asc, doc asc) are the clause list;
+ *   4. union, blend, top k_out, out_count and out_total are the exact call's.
+ * Guarantees:
+ *   - every out_score / out_vec_score is bit for bit the exact call's score of that doc against the same clause
+ *     lists;
+ *   - with one clause the call is byte-identical to slg_vector_search_batch under a filter that is the query's
+ *     filter AND "the doc is in a probed list or an unclustered segment";
+ *   - nprobe >= the number of lists of every clause's field makes it byte-identical to the exact call.
+ * nprobe outside 1..SLG_MAX_VECTOR_PROBES: SLG_ERR_UNSUPPORTED (checked first); cand_size > 64:
+ * SLG_ERR_UNSUPPORTED (only the fused top-k form of the scan is built: use the exact or the two-pass call); a clause
+ * whose field has no clustered segment: SLG_ERR_INVALID, the message names the field; all before any device work.
+ * The _device form is asynchronous on the index stream and makes no host round trip between its steps.
+ */
+#define SLG_MAX_VECTOR_LISTS  65536u       /* lists of one segment of one field */
+#define SLG_MAX_VECTOR_PROBES 256u
+#define SLG_KEEP_VECTOR_LISTS 0xFFFFFFFFu  /* n_lists: leave this segment's lists as they are */
+typedef struct {
+  uint32_t n_lists;        /* 0: the segment is (or becomes) unclustered; SLG_KEEP_VECTOR_LISTS: unchanged */
+  const float *centroids;  /* [n_lists * vec_dim] row-major host array, used as given */
+} slg_vector_lists_desc;
+int slg_index_cluster_vector_field(slg_index *index, uint32_t field, const slg_vector_lists_desc *per_segment,
+                                   uint32_t n_segs);
+int slg_index_fetch_vector_lists(slg_index *index, uint32_t field, uint32_t seg, uint32_t *out_list_begin,
+                                 uint32_t *out_docs, float *out_centroids, uint32_t lists_cap, uint32_t docs_cap);
+int slg_vector_search_batch_ivf(slg_index *index, uint32_t nq, uint32_t n_clauses, const uint32_t *clause_field,
+                                const float *qvecs, const float *alpha, const float *boost, const int32_t *q_filter,
+                                uint32_t cand_size, uint32_t nprobe, uint32_t k_out, uint32_t *out_doc,
+                                uint32_t *out_seg, float *out_score, float *out_vec_score, uint32_t *out_count,
+                                uint64_t *out_total);
+int slg_vector_search_batch_ivf_device(slg_index *index, uint32_t nq, uint32_t n_clauses,
+                                       const uint32_t *clause_field, const float *d_qvecs, const float *d_alpha,
+                                       const float *d_boost, const int32_t *d_q_filter, uint32_t cand_size,
+                                       uint32_t nprobe, uint32_t k_out, uint32_t *d_out_doc, uint32_t *d_out_seg,
+                                       float *d_out_score, float *d_out_vec_score, uint32_t *d_out_count,
+                                       uint64_t *d_out_total);
+
+/*
  * Hybrid text + vector search: one request with a text query and vector clauses (api/reader.rs:2754-2775:
  * collect_vector_maps with require_text_match = true, then merge_vector_hits, :2474-2537).  Per query:
  *   1. the matched set M = every doc the text query matches that is not deleted and passes q_filter (and

@@ -36,6 +36,10 @@ pub struct slg_tuning {
 #[repr(C)] pub struct slg_vector_field_desc {
     pub vec_dim: u32, pub vec_metric: i32, pub vec_offsets: *const u32, pub vec_values: *const c_float, pub vec_rows: u32,
 }
+pub const SLG_MAX_VECTOR_LISTS: u32 = 65536;
+pub const SLG_MAX_VECTOR_PROBES: u32 = 256;
+pub const SLG_KEEP_VECTOR_LISTS: u32 = 0xFFFF_FFFF;
+#[repr(C)] pub struct slg_vector_lists_desc { pub n_lists: u32, pub centroids: *const c_float }
 #[repr(C)] pub struct slg_score_plans {
     pub q_leaf: *const u32, pub q_plan: *const i32, pub q_tie: *const c_float, pub q_nleaves: *const u32,
     pub q_leaf_offsets: *const u32, pub leaf_group: *const u32, pub q_group_offsets: *const u32,
@@ -516,6 +520,20 @@ extern "C" {
     pub fn slg_vector_search_batch_approx_device(index: *mut slg_index, nq: u32, n_clauses: u32,
         clause_field: *const u32, d_qvecs: *const c_float, d_alpha: *const c_float, d_boost: *const c_float,
         d_q_filter: *const i32, cand_size: u32, refine: u32, k_out: u32, d_out_doc: *mut u32, d_out_seg: *mut u32,
+        d_out_score: *mut c_float, d_out_vec_score: *mut c_float, d_out_count: *mut u32,
+        d_out_total: *mut u64) -> c_int;
+    // IVF vector search: lists around caller-supplied centroids per (field, segment), the nprobe nearest are scanned
+    pub fn slg_index_cluster_vector_field(index: *mut slg_index, field: u32,
+        per_segment: *const slg_vector_lists_desc, n_segs: u32) -> c_int;
+    pub fn slg_index_fetch_vector_lists(index: *mut slg_index, field: u32, seg: u32, out_list_begin: *mut u32,
+        out_docs: *mut u32, out_centroids: *mut c_float, lists_cap: u32, docs_cap: u32) -> c_int;
+    pub fn slg_vector_search_batch_ivf(index: *mut slg_index, nq: u32, n_clauses: u32, clause_field: *const u32,
+        qvecs: *const c_float, alpha: *const c_float, boost: *const c_float, q_filter: *const i32, cand_size: u32,
+        nprobe: u32, k_out: u32, out_doc: *mut u32, out_seg: *mut u32, out_score: *mut c_float,
+        out_vec_score: *mut c_float, out_count: *mut u32, out_total: *mut u64) -> c_int;
+    pub fn slg_vector_search_batch_ivf_device(index: *mut slg_index, nq: u32, n_clauses: u32,
+        clause_field: *const u32, d_qvecs: *const c_float, d_alpha: *const c_float, d_boost: *const c_float,
+        d_q_filter: *const i32, cand_size: u32, nprobe: u32, k_out: u32, d_out_doc: *mut u32, d_out_seg: *mut u32,
         d_out_score: *mut c_float, d_out_vec_score: *mut c_float, d_out_count: *mut u32,
         d_out_total: *mut u64) -> c_int;
     // hybrid text + vector search (merge_vector_hits): prepare, run (slg_batch_run), then the vector side

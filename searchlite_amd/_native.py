@@ -17,6 +17,9 @@ MAX_K = 20001
 MAX_RERANK_K = 1024
 MAX_VECTOR_CLAUSES = 8
 MAX_VECTOR_CANDIDATES = 10000
+MAX_VECTOR_LISTS = 65536
+MAX_VECTOR_PROBES = 256
+KEEP_VECTOR_LISTS = 0xFFFFFFFF
 SHARD_UNIQUE_ID_BYTES = 128
 
 OK, ERR_INVALID, ERR_DEVICE, ERR_OOM, ERR_UNSUPPORTED, ERR_INTERNAL = 0, -1, -2, -3, -4, -5
@@ -124,6 +127,10 @@ class SegmentDesc(C.Structure):
 class VectorFieldDesc(C.Structure):
     _fields_ = [("vec_dim", C.c_uint32), ("vec_metric", C.c_int32), ("vec_offsets", C.c_void_p),
                 ("vec_values", C.c_void_p), ("vec_rows", C.c_uint32)]
+
+
+class VectorListsDesc(C.Structure):
+    _fields_ = [("n_lists", C.c_uint32), ("centroids", C.c_void_p)]
 
 
 class Stats(C.Structure):
@@ -560,6 +567,12 @@ def load():
                                                  vp, vp]),
         "slg_vector_search_batch_approx_device": (i32, [vp, u32, u32, vp, vp, vp, vp, vp, u32, u32, u32, vp, vp, vp,
                                                         vp, vp, vp]),
+        "slg_index_cluster_vector_field": (i32, [vp, u32, vp, u32]),
+        "slg_index_fetch_vector_lists": (i32, [vp, u32, u32, vp, vp, vp, u32, u32]),
+        "slg_vector_search_batch_ivf": (i32, [vp, u32, u32, vp, vp, vp, vp, vp, u32, u32, u32, vp, vp, vp, vp,
+                                              vp, vp]),
+        "slg_vector_search_batch_ivf_device": (i32, [vp, u32, u32, vp, vp, vp, vp, vp, u32, u32, u32, vp, vp, vp,
+                                                     vp, vp, vp]),
         "slg_batch_prepare_hybrid": (vp, [vp, u32, vp, vp, vp, vp, vp, u32, i32]),
         "slg_batch_hybrid_device": (i32, [vp, u32, vp, vp, vp, vp, u32, u32, vp, vp, vp, vp, vp, vp]),
         "slg_search_batch_hybrid": (i32, [vp, u32, vp, vp, vp, vp, vp, u32, i32, u32, vp, vp, vp, vp, u32, u32,

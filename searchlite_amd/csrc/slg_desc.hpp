@@ -154,6 +154,21 @@ struct VecCopyDev {
   uint32_t dim_pad;
   uint32_t pad;
 };
+// The inverted-file lists of a segment's store (slg_index_cluster_vector_field; slg_vsearch_ivf.hpp): list l holds
+// docs[list_begin[l] .. list_begin[l + 1]), ascending.  list_begin == nullptr: the segment is unclustered.
+struct VecListDev {
+  const uint32_t *list_begin;  // [n_lists + 1]
+  const uint32_t *docs;
+  uint32_t n_lists;
+  uint32_t pad;
+};
+// an unclustered segment with vectors in a clustered field: every query scans it whole, as a list behind the field's own
+constexpr uint32_t kIvfUnclChunks = 32;  // doc chunks of an unclustered segment, at most
+struct IvfUncl {
+  uint32_t seg, n_docs;
+  uint32_t chunk_docs;  // docs of a chunk (a multiple of the scan tile's 128)
+  uint32_t slot;        // the first of its partial slots among the unclustered segments' (one per chunk)
+};
 
 // ---- query rescore (slg_batch_prepare_rescore; kernel: slg_rescore.hpp, planner: slg_plan.cpp) -------
 // The rescore terms of query q are terms[(term_begin + i) * n_segs + s], i = 0 .. n_terms - 1, for

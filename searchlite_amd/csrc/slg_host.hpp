@@ -334,6 +334,20 @@ struct VecCopyField {
   DevBuf d_csegs;  // slg::VecCopyDev[n_segs] of the state this object belongs to
 };
 
+// the inverted-file lists of a vector field (slg_index_cluster_vector_field; field 0 too): per segment the shared
+// lists of its store (null: the segment is unclustered, or has no vectors in the field)
+struct VecListSeg {
+  DevBuf list_begin, docs, centroids, iota;  // u32[n_lists + 1] | u32[n_listed] | f32[n_lists * dim] | u32[n_lists] 0, 1, ..
+  uint32_t n_lists = 0, dim = 0, n_listed = 0, max_len = 0;
+};
+struct VecListField {
+  std::vector<std::shared_ptr<VecListSeg>> per_seg;
+  // the tables of the state this object belongs to: the lists, the centroid tables as pseudo-segments of the exact
+  // scan (a "doc" = a list) with their tombstone-free segment descriptors and flat list bases, the unclustered segments
+  DevBuf d_lsegs, d_csegs, d_psegs, d_list_base, d_uncl;
+  uint32_t total_lists = 0, max_len = 0, n_uncl = 0, uncl_slots = 0;
+};
+
 // a registered doc filter: per segment a reject bitmap (deleted | ~filter); null = the filter predates
 // the segment (slg_index_add_segment) and cannot be used until it is registered again
 struct FilterData {
@@ -470,6 +484,7 @@ struct IndexState {
   uint64_t total_docs = 0;
   std::vector<std::shared_ptr<VecFieldHost>> vfields;  // field id f >= 1 is vfields[f - 1]
   std::map<uint32_t, std::shared_ptr<VecCopyField>> vcopies;  // by field id (0 too); own objects, shared copies
+  std::map<uint32_t, std::shared_ptr<VecListField>> vlists;   // the same for the inverted-file lists
   std::vector<std::shared_ptr<FilterData>> filters;    // slot = filter id; null = free
   std::vector<const uint32_t *> reject_host;           // flattened [filter * n_segs + seg] device pointers
   DevBuf d_reject_table;                               // the same table on the device
@@ -1113,6 +1128,7 @@ struct VsCall {
   int32_t metric[SLG_MAX_VECTOR_CLAUSES] = {};
   const slg::VecSegDev *vsegs[SLG_MAX_VECTOR_CLAUSES] = {};
   const slg::VecCopyDev *csegs[SLG_MAX_VECTOR_CLAUSES] = {};  // (slg_vector_search_batch_approx*) the fields' bf16 copies
+  const VecListField *lists[SLG_MAX_VECTOR_CLAUSES] = {};     // (slg_vector_search_batch_ivf*) the fields' lists
   uint32_t q_floats = 0;
 };
 // ... and its arrays (host or device memory, as the entry says)
@@ -1132,6 +1148,12 @@ bool vs_prepare(slg_index *ix, uint32_t nq, uint32_t n_clauses, const uint32_t *
 // slg_vsearch.hip: the bf16 copy of one store of n_rows x dim f32 values on the device (vs_quantize_kernel on the
 // index stream, waited for); the caller holds the index's device
 std::shared_ptr<VecCopySeg> vs_quantize_store(slg_index *ix, const float *d_values, uint32_t n_rows, uint32_t dim);
+// slg_vsearch.hip: the lists of one store around n_lists host centroids (the assignment is an exact scan of the
+// centroids with the store's rows as queries; count, scan and ordered fill on the index stream, waited for); the
+// caller holds the index's device
+std::shared_ptr<VecListSeg> vs_cluster_store(slg_index *ix, const uint32_t *d_offsets, const float *d_values,
+                                             uint32_t n_docs, uint32_t n_rows, uint32_t dim, int32_t metric,
+                                             const float *centroids, uint32_t n_lists);
 // slg_vsearch.hip: the steps a hybrid call (slg_hybrid.hip) shares with the vector search, whose kernels they
 // run.  HyWork: the clause lists and sort space of one call, laid out over one block (base null: the size only);
 // cnt = run_cnt [clause][nq] then key_cnt [clause][nq], zeroed by the caller

@@ -284,6 +284,53 @@ void finish_state(slg_index *ix, IndexState &s) {
     vc.d_csegs.alloc(std::max<size_t>(n_segs, 1) * sizeof(slg::VecCopyDev), &ix->pool);
     if (n_segs) SLG_HIP(hipMemcpy(vc.d_csegs.p, cv.data(), n_segs * sizeof(slg::VecCopyDev), hipMemcpyHostToDevice));
   }
+  for (auto &vlp : s.vlists) {  // (fresh copies too) the inverted-file lists' tables
+    VecListField &vl = *vlp.second;
+    const uint32_t f = vlp.first;
+    vl.per_seg.resize(n_segs);
+    std::vector<slg::VecListDev> lv(n_segs, slg::VecListDev{nullptr, nullptr, 0u, 0u});
+    std::vector<slg::VecSegDev> cv(n_segs);
+    std::vector<slg::SegDev> pv(n_segs, slg::SegDev{});
+    std::vector<uint32_t> lbase(n_segs + 1, 0u);
+    std::vector<slg::IvfUncl> uv;
+    const int32_t metric = f == 0 ? field_metric : (f <= s.vfields.size() ? s.vfields[f - 1]->metric : 0);
+    vl.total_lists = vl.max_len = vl.uncl_slots = 0;
+    for (size_t i = 0; i < n_segs; i++) {
+      lbase[i] = vl.total_lists;
+      cv[i] = slg::VecSegDev{nullptr, nullptr, 0u, 0u, metric, 0u};
+      const bool has_vectors = f == 0 ? s.segs[i]->store->vec_dim != 0
+                                      : (f <= s.vfields.size() && i < s.vfields[f - 1]->per_seg.size() &&
+                                         s.vfields[f - 1]->per_seg[i]);
+      if (vl.per_seg[i] && vl.per_seg[i]->n_lists) {
+        const VecListSeg &ls = *vl.per_seg[i];
+        lv[i] = slg::VecListDev{ls.list_begin.as<uint32_t>(), ls.docs.as<uint32_t>(), ls.n_lists, 0u};
+        cv[i] = slg::VecSegDev{ls.iota.as<uint32_t>(), ls.centroids.as<float>(), ls.n_lists, ls.dim, metric, 0u};
+        pv[i].n_docs = ls.n_lists;
+        vl.total_lists += ls.n_lists;
+        vl.max_len = std::max(vl.max_len, ls.max_len);
+      } else if (has_vectors && s.segs[i]->n_docs) {
+        // chunks of whole scan tiles (128 docs), at most kIvfUnclChunks of them
+        const uint32_t nd = s.segs[i]->n_docs, tiles = (nd + 127u) / 128u;
+        const uint32_t want = std::min<uint32_t>(tiles, slg::kIvfUnclChunks), chunk = ((tiles + want - 1) / want) * 128u;
+        uv.push_back(slg::IvfUncl{(uint32_t)i, nd, chunk, vl.uncl_slots});
+        vl.uncl_slots += (nd + chunk - 1) / chunk;
+      }
+    }
+    lbase[n_segs] = vl.total_lists;
+    vl.n_uncl = (uint32_t)uv.size();
+    vl.d_lsegs.alloc(std::max<size_t>(n_segs, 1) * sizeof(slg::VecListDev), &ix->pool);
+    vl.d_csegs.alloc(std::max<size_t>(n_segs, 1) * sizeof(slg::VecSegDev), &ix->pool);
+    vl.d_psegs.alloc(std::max<size_t>(n_segs, 1) * sizeof(slg::SegDev), &ix->pool);
+    vl.d_list_base.alloc(lbase.size() * 4, &ix->pool);
+    vl.d_uncl.alloc(std::max<size_t>(uv.size(), 1) * sizeof(slg::IvfUncl), &ix->pool);
+    if (n_segs) {
+      SLG_HIP(hipMemcpy(vl.d_lsegs.p, lv.data(), n_segs * sizeof(slg::VecListDev), hipMemcpyHostToDevice));
+      SLG_HIP(hipMemcpy(vl.d_csegs.p, cv.data(), n_segs * sizeof(slg::VecSegDev), hipMemcpyHostToDevice));
+      SLG_HIP(hipMemcpy(vl.d_psegs.p, pv.data(), n_segs * sizeof(slg::SegDev), hipMemcpyHostToDevice));
+    }
+    SLG_HIP(hipMemcpy(vl.d_list_base.p, lbase.data(), lbase.size() * 4, hipMemcpyHostToDevice));
+    if (!uv.empty()) SLG_HIP(hipMemcpy(vl.d_uncl.p, uv.data(), uv.size() * sizeof(slg::IvfUncl), hipMemcpyHostToDevice));
+  }
   s.positions.resize(n_segs);  // (a new state of a new segment list: no positions where none were set)
   std::vector<slg::PosSegDev> pd(n_segs);
   for (size_t i = 0; i < n_segs; i++)
@@ -358,6 +405,11 @@ std::unique_ptr<IndexState> copy_state(const IndexState &cur) {
     c->per_seg = vc.second->per_seg;
     n->vcopies.emplace(vc.first, std::move(c));
   }
+  for (auto &vl : cur.vlists) {  // the same for the inverted-file lists' tables
+    auto c = std::make_shared<VecListField>();
+    c->per_seg = vl.second->per_seg;
+    n->vlists.emplace(vl.first, std::move(c));
+  }
   for (auto &tf : cur.text_fields) {  // the same for the text fields' d_tsegs
     auto c = std::make_shared<TextFieldHost>();
     c->per_seg = tf.second->per_seg;
@@ -428,6 +480,7 @@ void reshape_per_segment(IndexState &ns, Op op) {
   }
   for (auto &vf : ns.vfields) op(vf->per_seg);  // (the field objects of a new state are fresh copies)
   for (auto &vc : ns.vcopies) op(vc.second->per_seg);  // (fresh copies too)
+  for (auto &vl : ns.vlists) op(vl.second->per_seg);  // (fresh copies too)
   op(ns.positions);  // (the state's own vector; the stores are shared)
   op(ns.terms);
   for (auto &tf : ns.text_fields) op(tf.second->per_seg);  // (fresh copies too)
@@ -475,6 +528,12 @@ size_t state_device_bytes(const IndexState &s) {
     n += vc.second->d_csegs.bytes;
     for (auto &c : vc.second->per_seg)
       if (c) n += c->rows.bytes + c->norms.bytes;
+  }
+  for (auto &vl : s.vlists) {
+    const VecListField &f = *vl.second;
+    n += f.d_lsegs.bytes + f.d_csegs.bytes + f.d_psegs.bytes + f.d_list_base.bytes + f.d_uncl.bytes;
+    for (auto &l : f.per_seg)
+      if (l) n += l->list_begin.bytes + l->docs.bytes + l->centroids.bytes + l->iota.bytes;
   }
   return n;
 }
@@ -1740,6 +1799,100 @@ int slg_index_fetch_vector_copy(slg_index *ix, uint32_t field, uint32_t seg, uin
     SLG_HIP(hipMemcpy(out_norm, c.norms.p, (size_t)n * 4, hipMemcpyDeviceToHost));
   });
   return rc == SLG_OK ? rows : rc;
+}
+
+int slg_index_cluster_vector_field(slg_index *ix, uint32_t field, const slg_vector_lists_desc *per_segment,
+                                   uint32_t n_segs) {
+  return guarded([&] {
+    SLG_REQUIRE(ix != nullptr, "index is NULL");
+    update_state(ix, false, [&](const IndexState &cur, IndexState &ns) {
+      // every check before any device work
+      SLG_REQUIRE(field <= cur.vfields.size(), "unknown vector field id");
+      SLG_REQUIRE(n_segs == cur.segs.size(), "n_segs is not the index's segment count");
+      SLG_REQUIRE(per_segment != nullptr || n_segs == 0, "per_segment is NULL");
+      auto store_of = [&](size_t s, const uint32_t **offs, const float **vals, uint32_t *rows, uint32_t *dim,
+                          int32_t *metric) {
+        *dim = 0;
+        if (field == 0) {
+          const PostingStore &ps = *cur.segs[s]->store;
+          if (!ps.vec_dim) return;
+          *offs = ps.d_vec_offsets.as<uint32_t>();
+          *vals = ps.d_vec_values.as<float>();
+          *rows = ps.vec_rows;
+          *dim = ps.vec_dim;
+          *metric = ps.vec_metric;
+        } else {
+          const VecFieldHost &vf = *cur.vfields[field - 1];
+          if (s >= vf.per_seg.size() || !vf.per_seg[s]) return;
+          const VecSegStore &st = *vf.per_seg[s];
+          *offs = st.offsets.as<uint32_t>();
+          *vals = st.values.as<float>();
+          *rows = st.n_rows;
+          *dim = st.dim;
+          *metric = vf.metric;
+        }
+      };
+      for (uint32_t s = 0; s < n_segs; s++) {
+        const slg_vector_lists_desc &d = per_segment[s];
+        if (d.n_lists == 0 || d.n_lists == SLG_KEEP_VECTOR_LISTS) continue;
+        if (d.n_lists > SLG_MAX_VECTOR_LISTS) throw SlgError(SLG_ERR_UNSUPPORTED, "n_lists > SLG_MAX_VECTOR_LISTS");
+        SLG_REQUIRE(d.centroids != nullptr, "centroids is NULL with n_lists > 0");
+        const uint32_t *offs = nullptr;
+        const float *vals = nullptr;
+        uint32_t rows = 0, dim = 0;
+        int32_t metric = 0;
+        store_of(s, &offs, &vals, &rows, &dim, &metric);
+        SLG_REQUIRE(dim != 0, "n_lists > 0 on segment " + std::to_string(s) + ", which has no vectors in the field");
+      }
+      auto vl = std::make_shared<VecListField>();
+      const auto old = cur.vlists.find(field);
+      vl->per_seg.resize(n_segs);
+      for (uint32_t s = 0; s < n_segs; s++) {
+        const slg_vector_lists_desc &d = per_segment[s];
+        if (d.n_lists == SLG_KEEP_VECTOR_LISTS) {
+          if (old != cur.vlists.end() && s < old->second->per_seg.size()) vl->per_seg[s] = old->second->per_seg[s];
+          continue;
+        }
+        if (d.n_lists == 0) continue;
+        const uint32_t *offs = nullptr;
+        const float *vals = nullptr;
+        uint32_t rows = 0, dim = 0;
+        int32_t metric = 0;
+        store_of(s, &offs, &vals, &rows, &dim, &metric);
+        vl->per_seg[s] = vs_cluster_store(ix, offs, vals, cur.segs[s]->n_docs, rows, dim, metric, d.centroids, d.n_lists);
+      }
+      ns.vlists[field] = std::move(vl);
+    });
+  });
+}
+
+int slg_index_fetch_vector_lists(slg_index *ix, uint32_t field, uint32_t seg, uint32_t *out_list_begin,
+                                 uint32_t *out_docs, float *out_centroids, uint32_t lists_cap, uint32_t docs_cap) {
+  int lists = 0;
+  const int rc = guarded([&] {
+    SLG_REQUIRE(ix != nullptr, "index is NULL");
+    const auto st = ix->snapshot();
+    SLG_REQUIRE(field <= st->vfields.size(), "unknown vector field id");
+    SLG_REQUIRE(seg < st->segs.size(), "no such segment");
+    const auto it = st->vlists.find(field);
+    if (it == st->vlists.end()) return;  // (never clustered)
+    const VecListField &vl = *it->second;
+    if (seg >= vl.per_seg.size() || !vl.per_seg[seg]) return;  // (unclustered, or no vectors of the field)
+    const VecListSeg &ls = *vl.per_seg[seg];
+    lists = (int)ls.n_lists;
+    DeviceGuard g(ix->device);
+    const uint32_t nl = std::min(ls.n_lists, lists_cap), nd = std::min(ls.n_listed, docs_cap);
+    if (nl) {
+      SLG_REQUIRE(out_list_begin != nullptr && out_centroids != nullptr, "output arrays are NULL");
+      SLG_HIP(hipMemcpy(out_list_begin, ls.list_begin.p, ((size_t)nl + 1) * 4, hipMemcpyDeviceToHost));
+      SLG_HIP(hipMemcpy(out_centroids, ls.centroids.p, (size_t)nl * ls.dim * 4, hipMemcpyDeviceToHost));
+    }
+    if (nd) {
+      SLG_REQUIRE(out_docs != nullptr, "out_docs is NULL");
+      SLG_HIP(hipMemcpy(out_docs, ls.docs.p, (size_t)nd * 4, hipMemcpyDeviceToHost));
+    }
+  });
+  return rc == SLG_OK ? lists : rc;
 }
 
 }  // extern "C"

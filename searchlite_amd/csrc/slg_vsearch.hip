@@ -1,9 +1,11 @@
 // slg_vsearch.hip — exact vector-only search (slg_vector_search_batch*; kernels: slg_vsearch.hpp) and the two-pass
-// search over a bf16 copy of the store (slg_vector_search_batch_approx*; kernels: slg_vsearch_approx.hpp).
+// search over a bf16 copy of the store (slg_vector_search_batch_approx*; kernels: slg_vsearch_approx.hpp) and the
+// search over the inverted-file lists of a field (slg_vector_search_batch_ivf*; kernels: slg_vsearch_ivf.hpp).
 #include "slg_host.hpp"
 
 #include "slg_vsearch.hpp"
 #include "slg_vsearch_approx.hpp"
+#include "slg_vsearch_ivf.hpp"
 
 using namespace slghost;
 
@@ -56,6 +58,124 @@ std::shared_ptr<VecCopySeg> slghost::vs_quantize_store(slg_index *ix, const floa
     SLG_HIP(hipStreamSynchronize(ix->stream));
   }
   return c;
+}
+
+namespace {
+// workgroups of one round of a scan with lds bytes of LDS each: as many as the LDS of a CU holds, at most by_vgprs
+// (3: the VGPR bound of vs_scan_kernel)
+uint32_t vs_resident_groups(slg_index *ix, size_t lds, uint32_t by_vgprs = 3u) {
+  int n_cu = 0;
+  SLG_HIP(hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, ix->device));
+  const uint32_t per_cu = std::min<uint32_t>(by_vgprs, (uint32_t)((160u << 10) / lds));
+  return std::max<uint32_t>((uint32_t)n_cu, 1u) * std::max<uint32_t>(per_cu, 1u);
+}
+}  // namespace
+
+std::shared_ptr<VecListSeg> slghost::vs_cluster_store(slg_index *ix, const uint32_t *d_offsets, const float *d_values,
+                                                      uint32_t n_docs, uint32_t n_rows, uint32_t dim, int32_t metric,
+                                                      const float *centroids, uint32_t n_lists) {
+  const hipStream_t st = ix->stream;
+  auto ls = std::make_shared<VecListSeg>();
+  ls->n_lists = n_lists;
+  ls->dim = dim;
+  ls->list_begin.alloc(((size_t)n_lists + 1) * 4, &ix->pool);
+  ls->centroids.alloc((size_t)n_lists * dim * 4, &ix->pool);
+  ls->iota.alloc((size_t)n_lists * 4, &ix->pool);
+  SLG_HIP(hipMemcpy(ls->centroids.p, centroids, (size_t)n_lists * dim * 4, hipMemcpyHostToDevice));
+  {
+    std::vector<uint32_t> iota(n_lists);
+    for (uint32_t i = 0; i < n_lists; i++) iota[i] = i;
+    SLG_HIP(hipMemcpy(ls->iota.p, iota.data(), (size_t)n_lists * 4, hipMemcpyHostToDevice));
+  }
+  // ---- the list of every row: an exact scan with the rows as queries, the centroids as the docs of one
+  //      pseudo-segment without tombstones, and a top-1 ----
+  const slg::VecSegDev cseg{ls->iota.as<uint32_t>(), ls->centroids.as<float>(), n_lists, dim, metric, 0u};
+  const slg::SegDev pseg{};
+  const uint32_t cbase[2] = {0u, n_lists};
+  DevBuf d_cseg, d_pseg, d_cbase, row_list, doc_list, table, lens, partials;
+  d_cseg.alloc(sizeof(cseg), &ix->pool);
+  d_pseg.alloc(sizeof(pseg), &ix->pool);
+  d_cbase.alloc(sizeof(cbase), &ix->pool);
+  SLG_HIP(hipMemcpy(d_cseg.p, &cseg, sizeof(cseg), hipMemcpyHostToDevice));
+  SLG_HIP(hipMemcpy(d_pseg.p, &pseg, sizeof(pseg), hipMemcpyHostToDevice));
+  SLG_HIP(hipMemcpy(d_cbase.p, cbase, sizeof(cbase), hipMemcpyHostToDevice));
+  row_list.alloc(std::max<size_t>(n_rows, 1) * 4, &ix->pool);
+  const uint32_t n_tiles = (n_lists + slg::kVsTileDocs - 1) / slg::kVsTileDocs;
+  const size_t lds = slg::vs_scan_lds_bytes(true, slg::kVsBufCapNarrow);
+  const uint32_t target = vs_resident_groups(ix, lds);
+  const uint32_t batch = 65536;  // rows of one scan
+  if (n_rows) {
+    const uint32_t b_rows = std::min(batch, n_rows), qtiles = (b_rows + slg::kVsTileQ - 1) / slg::kVsTileQ;
+    uint32_t n_chunks = std::min<uint32_t>(std::max<uint32_t>((target + qtiles - 1) / qtiles, 1u), n_tiles);
+    const uint32_t tpb = (n_tiles + n_chunks - 1) / n_chunks;
+    n_chunks = (n_tiles + tpb - 1) / tpb;
+    partials.alloc((size_t)b_rows * n_chunks * slg::kVsSmallK * 8, &ix->pool);
+    slg::VsScanParams sp{};
+    sp.vsegs = d_cseg.as<slg::VecSegDev>();
+    sp.segs = d_pseg.as<slg::SegDev>();
+    sp.doc_base = d_cbase.as<uint32_t>();
+    sp.n_segs = 1;
+    sp.dim = dim;
+    sp.q_stride = dim;
+    sp.qvec4 = dim % 4 == 0 ? 1u : 0u;  // (device allocations are aligned)
+    sp.n_clauses = 1;
+    sp.tile_end = n_tiles;
+    sp.tiles_per_block = tpb;
+    sp.n_chunks = n_chunks;
+    sp.out = partials.as<uint64_t>();
+    sp.k = 1;
+    sp.cap = slg::kVsBufCapNarrow;
+    for (uint32_t r0 = 0; r0 < n_rows; r0 += batch) {
+      const uint32_t nr = std::min(batch, n_rows - r0);
+      sp.nq = nr;
+      sp.qvecs = d_values + (size_t)r0 * dim;
+      const dim3 grid((nr + slg::kVsTileQ - 1) / slg::kVsTileQ, n_chunks);
+      if (metric == 0)
+        launch_kernel_lds(slg::vs_scan_kernel<0, true>, sp, grid, 256, lds, st);
+      else
+        launch_kernel_lds(slg::vs_scan_kernel<1, true>, sp, grid, 256, lds, st);
+      slg::IvfBestParams bp{partials.as<uint64_t>(), nr, n_chunks, row_list.as<uint32_t>() + r0};
+      hipLaunchKernelGGL(slg::vs_ivf_best_kernel, dim3((nr + 255) / 256), dim3(256), 0, st, bp);
+      SLG_HIP(hipGetLastError());
+    }
+  }
+  // ---- the lists: count per (list, doc range), prefix per list, exclusive scan of the lengths, ordered fill ----
+  const uint32_t max_ranges = std::max<uint32_t>(std::min<uint32_t>(slg::kIvfMaxRanges, (16u << 20) / n_lists), 1u);
+  uint32_t range_docs = std::max<uint32_t>(slg::kIvfRangeDocs, (n_docs + max_ranges - 1) / max_ranges);
+  range_docs = (range_docs + 63u) / 64u * 64u;
+  const uint32_t n_ranges = std::max<uint32_t>((n_docs + range_docs - 1) / range_docs, 1u);
+  doc_list.alloc(std::max<size_t>(n_docs, 1) * 4, &ix->pool);
+  table.alloc((size_t)n_lists * n_ranges * 4, &ix->pool);
+  lens.alloc((size_t)n_lists * 4, &ix->pool);
+  SLG_HIP(hipMemsetAsync(table.p, 0, (size_t)n_lists * n_ranges * 4, st));
+  slg::IvfBuildParams bp{};
+  bp.offsets = d_offsets;
+  bp.row_list = row_list.as<uint32_t>();
+  bp.doc_list = doc_list.as<uint32_t>();
+  bp.table = table.as<uint32_t>();
+  bp.lens = lens.as<uint32_t>();
+  bp.list_begin = ls->list_begin.as<uint32_t>();
+  bp.n_docs = n_docs;
+  bp.n_lists = n_lists;
+  bp.n_ranges = n_ranges;
+  bp.range_docs = range_docs;
+  if (n_docs) hipLaunchKernelGGL(slg::vs_ivf_count_kernel, dim3((n_docs + 255) / 256), dim3(256), 0, st, bp);
+  hipLaunchKernelGGL(slg::vs_ivf_prefix_kernel, dim3((n_lists + 255) / 256), dim3(256), 0, st, bp);
+  slg::IvfScanParams xp{lens.as<uint32_t>(), ls->list_begin.as<uint32_t>(), n_lists};
+  hipLaunchKernelGGL(slg::vs_ivf_exscan_kernel, dim3(1), dim3(slg::kIvfScanThreads), 0, st, xp);
+  SLG_HIP(hipGetLastError());
+  std::vector<uint32_t> lb((size_t)n_lists + 1);
+  SLG_HIP(hipMemcpyAsync(lb.data(), ls->list_begin.p, lb.size() * 4, hipMemcpyDeviceToHost, st));
+  SLG_HIP(hipStreamSynchronize(st));
+  ls->n_listed = lb[n_lists];
+  SLG_REQUIRE(ls->n_listed <= n_docs, "the lists hold more docs than the segment");
+  for (uint32_t l = 0; l < n_lists; l++) ls->max_len = std::max(ls->max_len, lb[l + 1] - lb[l]);
+  ls->docs.alloc(std::max<size_t>(ls->n_listed, 1) * 4, &ix->pool);
+  bp.docs = ls->docs.as<uint32_t>();
+  if (n_docs) hipLaunchKernelGGL(slg::vs_ivf_fill_kernel, dim3(n_ranges), dim3(64), 0, st, bp);
+  SLG_HIP(hipGetLastError());
+  SLG_HIP(hipStreamSynchronize(st));
+  return ls;
 }
 
 namespace {
@@ -215,9 +335,188 @@ void vs_blend(const VsCall &vc, const VsArgs &a, const uint64_t *dlist, const ui
                    P > slg::kVsSortCap ? 0 : (size_t)P * 8, st);
 }
 
+// (slg_vector_search_batch_ivf*) what one clause's steps need of vs_scratch, from what the host knows: nq, the
+// probes of a query, the field's lists, its longest list and its unclustered segments
+struct IvfPlan {
+  uint32_t P = 0;            // probes of a query: min(nprobe, lists of the field)
+  uint32_t list_chunks = 0, list_chunk_docs = 0, slots_q = 0, n_ext = 0, items_cap = 0;
+  uint32_t coarse_docs = 0;  // lists of one coarse scan + select step
+  size_t n_probe_keys = 0, n_coarse = 0, n_partial = 0, n_u32 = 0;
+  // probes | coarse keys | partial lists | items | pairs (8 bytes each) | the counters and offsets
+  size_t bytes() const {
+    return (n_probe_keys + n_coarse + n_partial + n_probe_keys) * 8 + (size_t)items_cap * sizeof(slg::IvfItem) + n_u32 * 4;
+  }
+};
+IvfPlan ivf_plan(const VsCall &vc, uint32_t c, uint32_t nprobe) {
+  const VecListField &vl = *vc.lists[c];
+  IvfPlan pl;
+  pl.P = std::min(nprobe, vl.total_lists);
+  pl.list_chunks = std::max<uint32_t>(std::min<uint32_t>(slg::kIvfListChunks, (vl.max_len + 1023u) / 1024u), 1u);
+  pl.list_chunk_docs = std::max<uint32_t>(((vl.max_len + pl.list_chunks - 1) / pl.list_chunks + slg::kVsTileDocs - 1) /
+                                              slg::kVsTileDocs * slg::kVsTileDocs, slg::kVsTileDocs);
+  pl.slots_q = pl.P * pl.list_chunks + vl.uncl_slots;
+  pl.n_ext = vl.total_lists + vl.n_uncl;
+  const uint32_t qtiles = (vc.nq + slg::kVsTileQ - 1) / slg::kVsTileQ;
+  // a list's items: its query tiles x its chunks; all lists: at most the probes / 64 + one tile per probed list
+  const uint64_t pairs = (uint64_t)vc.nq * pl.P;
+  const uint64_t items = (pairs / slg::kVsTileQ + std::min<uint64_t>(vl.total_lists, pairs)) * pl.list_chunks +
+                         (uint64_t)qtiles * vl.uncl_slots;
+  SLG_REQUIRE(pairs < 0x7FFFFFFFull && items < 0x7FFFFFFFull, "too many (query, probed list) pairs in one call");
+  pl.items_cap = (uint32_t)items;
+  pl.coarse_docs = std::min<uint32_t>(((slg::kVsSortCap - pl.P) / slg::kVsTileDocs) * slg::kVsTileDocs,
+                                      (vl.total_lists + slg::kVsTileDocs - 1) / slg::kVsTileDocs * slg::kVsTileDocs);
+  pl.n_probe_keys = pairs;
+  pl.n_coarse = (size_t)vc.nq * pl.coarse_docs;
+  pl.n_partial = (size_t)vc.nq * pl.slots_q * slg::kVsSmallK;
+  pl.n_u32 = 4 * (size_t)pl.n_ext + 3 + vc.nq + 1;  // cnt, cursor, goff, ioff, n_items, the coarse select's counts
+  return pl;
+}
+
+// the clause lists of one IVF call on st (run / run_cnt zeroed by the caller; work: the clause-by-clause work area)
+void vs_lists_ivf(slg_index *ix, const VsCall &vc, const VsArgs &a, uint32_t nprobe, uint64_t *run, uint32_t *run_cnt,
+                  uint64_t *dlist, void *work, hipStream_t st) {
+  const IndexState &S = *vc.S;
+  const uint32_t nq = vc.nq, NC = vc.n_clauses, K = vc.cand;
+  const uint32_t cap = K <= slg::kVsSmallK / 2 ? slg::kVsBufCapNarrow : slg::kVsBufCap;
+  const size_t scan_lds = slg::vs_ivf_scan_lds_bytes(cap);
+  const uint32_t qtiles = (nq + slg::kVsTileQ - 1) / slg::kVsTileQ;
+  for (uint32_t c = 0; c < NC; c++) {
+    const VecListField &vl = *vc.lists[c];
+    const IvfPlan pl = ivf_plan(vc, c, nprobe);
+    uint64_t *probes = static_cast<uint64_t *>(work), *coarse = probes + pl.n_probe_keys;
+    uint64_t *partials = coarse + pl.n_coarse;
+    slg::IvfItem *items = reinterpret_cast<slg::IvfItem *>(partials + pl.n_partial);
+    uint2 *pairs = reinterpret_cast<uint2 *>(items + pl.items_cap);
+    uint32_t *cnt = reinterpret_cast<uint32_t *>(pairs + pl.n_probe_keys), *cursor = cnt + pl.n_ext;
+    uint32_t *goff = cursor + pl.n_ext, *ioff = goff + pl.n_ext + 1, *n_items = ioff + pl.n_ext + 1;
+    uint32_t *probe_cnt = n_items + 1;  // [nq] the coarse select's counts
+    const uint32_t qvec4 = (vc.q_floats % 4 == 0 && vc.coff[c] % 4 == 0 && ((uintptr_t)a.qvecs & 15) == 0) ? 1u : 0u;
+    // every counter of the steps, and the partial slots no item writes
+    SLG_HIP(hipMemsetAsync(cnt, 0, (2 * (size_t)pl.n_ext) * 4, st));
+    SLG_HIP(hipMemsetAsync(n_items, 0, 4, st));
+    SLG_HIP(hipMemsetAsync(partials, 0, pl.n_partial * 8, st));
+    SLG_HIP(hipMemsetAsync(probes, 0, pl.n_probe_keys * 8, st));
+    // ---- coarse step: the exact scan's store form over the centroid tables, the best P lists of each query ----
+    slg::VsScanParams sp{};
+    sp.vsegs = vl.d_csegs.as<slg::VecSegDev>();
+    sp.segs = vl.d_psegs.as<slg::SegDev>();
+    sp.doc_base = vl.d_list_base.as<uint32_t>();
+    sp.n_segs = (uint32_t)S.segs.size();
+    sp.dim = vc.dim[c];
+    sp.nq = nq;
+    sp.qvecs = a.qvecs;
+    sp.q_stride = vc.q_floats;
+    sp.q_off = vc.coff[c];
+    sp.qvec4 = qvec4;
+    sp.boost = a.boost;
+    sp.n_clauses = NC;
+    sp.clause = c;
+    sp.tiles_per_block = 1;
+    sp.out = coarse;
+    sp.out_stride = pl.coarse_docs;
+    const uint32_t n_tiles = (vl.total_lists + slg::kVsTileDocs - 1) / slg::kVsTileDocs;
+    const uint32_t step_tiles = pl.coarse_docs / slg::kVsTileDocs;
+    SLG_HIP(hipMemsetAsync(probe_cnt, 0, (size_t)nq * 4, st));
+    for (uint32_t t0 = 0; t0 < n_tiles; t0 += step_tiles) {
+      const uint32_t t1 = std::min(t0 + step_tiles, n_tiles);
+      sp.tile_begin = t0;
+      sp.tile_end = t1;
+      const size_t lds = slg::vs_scan_lds_bytes(false, 0);
+      if (vc.metric[c] == 0)
+        launch_kernel_lds(slg::vs_scan_kernel<0, false>, sp, dim3(qtiles, t1 - t0), 256, lds, st);
+      else
+        launch_kernel_lds(slg::vs_scan_kernel<1, false>, sp, dim3(qtiles, t1 - t0), 256, lds, st);
+      vs_select(probes, probe_cnt, nullptr, coarse, nq, pl.P, 0, 1, (t1 - t0) * slg::kVsTileDocs, pl.coarse_docs, false,
+                st);
+    }
+    // ---- inversion: the probes as per-list query groups, and the work table ----
+    slg::IvfPlanParams ip{};
+    ip.probes = probes;
+    ip.lsegs = vl.d_lsegs.as<slg::VecListDev>();
+    ip.list_base = vl.d_list_base.as<uint32_t>();
+    ip.uncl = vl.d_uncl.as<slg::IvfUncl>();
+    ip.n_segs = (uint32_t)S.segs.size();
+    ip.n_lists = vl.total_lists;
+    ip.n_uncl = vl.n_uncl;
+    ip.nq = nq;
+    ip.n_probe = pl.P;
+    ip.list_chunk_docs = pl.list_chunk_docs;
+    ip.list_chunks = pl.list_chunks;
+    ip.cnt = cnt;
+    ip.cursor = cursor;
+    ip.goff = goff;
+    ip.ioff = ioff;
+    ip.n_items = n_items;
+    ip.pairs = pairs;
+    ip.items = items;
+    ip.items_cap = pl.items_cap;
+    const uint32_t n_pairs = nq * pl.P;
+    hipLaunchKernelGGL(slg::vs_ivf_probe_count_kernel, dim3((n_pairs + 255) / 256), dim3(256), 0, st, ip);
+    hipLaunchKernelGGL(slg::vs_ivf_plan_kernel, dim3(1), dim3(slg::kIvfScanThreads), 0, st, ip);
+    hipLaunchKernelGGL(slg::vs_ivf_items_kernel, dim3((std::max(n_pairs, pl.n_ext) + 255) / 256), dim3(256), 0, st, ip);
+    SLG_HIP(hipGetLastError());
+    // ---- the scan of the work table by one round of resident workgroups ----
+    slg::VsIvfScanParams xp{};
+    slg::VsScanParams &xs = xp.s;
+    xs.vsegs = vc.vsegs[c];
+    xs.segs = S.d_segs.as<slg::SegDev>();
+    xs.reject_table = S.d_reject_table.as<const uint32_t *>();
+    xs.doc_base = S.d_doc_base.as<uint32_t>();
+    xs.n_segs = (uint32_t)S.segs.size();
+    xs.n_filters = (uint32_t)S.filters.size();
+    xs.dim = vc.dim[c];
+    xs.nq = nq;
+    xs.qvecs = a.qvecs;
+    xs.q_stride = vc.q_floats;
+    xs.q_off = vc.coff[c];
+    xs.qvec4 = qvec4;
+    xs.boost = a.boost;
+    xs.n_clauses = NC;
+    xs.clause = c;
+    xs.q_filter = a.q_filter;
+    xs.out = partials;
+    xs.k = K;
+    xs.cap = cap;
+    xp.lsegs = ip.lsegs;
+    xp.items = items;
+    xp.n_items = n_items;
+    xp.pairs = pairs;
+    xp.slots_q = pl.slots_q;
+    // (profiles/vsearch_ivf_resource_usage.txt: the cosine form's registers leave two waves per SIMD, the L2 form's one)
+    const uint32_t groups = vs_resident_groups(ix, scan_lds, vc.metric[c] == 0 ? 2u : 1u);
+    const dim3 grid(std::min<uint32_t>(groups, std::max<uint32_t>(pl.items_cap, 1u)));
+    if (vc.metric[c] == 0)
+      launch_kernel_lds(slg::vs_ivf_scan_kernel<0, true>, xp, grid, 256, scan_lds, st);
+    else
+      launch_kernel_lds(slg::vs_ivf_scan_kernel<1, true>, xp, grid, 256, scan_lds, st);
+    // ---- a query's partials fold into its clause list in passes that sort in LDS with the running list ----
+    const uint32_t n_in = pl.slots_q * slg::kVsSmallK, fold_n = slg::kVsSortCap - K;
+    const size_t qc0 = (size_t)c * nq;
+    for (uint32_t o = 0; o < n_in; o += fold_n)
+      vs_select(run + qc0 * K, run_cnt + qc0, dlist + qc0 * K, partials + o, nq, K, 0, 1, std::min(fold_n, n_in - o),
+                n_in, o + fold_n >= n_in, st);
+  }
+}
+
 // the kernels of one call on st, device arrays in a (the caller holds ix->mu and the device).  refine 0: the exact
-// search; else the two-pass one: lists of `refine` keys from the bf16 copies, their exact scores, the best cand_size
-void vs_run(slg_index *ix, const VsCall &vc, const VsArgs &a, uint32_t refine, hipStream_t st) {
+// search; else the two-pass one: lists of `refine` keys from the bf16 copies, their exact scores, the best cand_size.
+// nprobe != 0 (refine 0): the search over the fields' inverted-file lists
+void vs_run(slg_index *ix, const VsCall &vc, const VsArgs &a, uint32_t refine, uint32_t nprobe, hipStream_t st) {
+  if (nprobe) {
+    const uint32_t nq = vc.nq, NC = vc.n_clauses, K = vc.cand;
+    const size_t n_run = (size_t)NC * nq * K, n_cnt = (size_t)NC * nq;
+    const uint32_t P = slg::vs_pow2(NC * K);  // (K <= kVsSmallK: the union sorts in LDS)
+    size_t work = 0;
+    for (uint32_t c = 0; c < NC; c++) work = std::max(work, ivf_plan(vc, c, nprobe).bytes());
+    const size_t bytes = 2 * n_run * 8 + work + n_cnt * 4 + 256;
+    if (ix->vs_scratch.bytes < bytes) ix->vs_scratch.alloc(bytes + bytes / 4, &ix->pool);
+    uint64_t *run = ix->vs_scratch.as<uint64_t>(), *dlist = run + n_run, *wk = dlist + n_run;
+    uint32_t *run_cnt = reinterpret_cast<uint32_t *>(reinterpret_cast<unsigned char *>(wk) + (work + 7) / 8 * 8);
+    SLG_HIP(hipMemsetAsync(run_cnt, 0, n_cnt * 4, st));
+    vs_lists_ivf(ix, vc, a, nprobe, run, run_cnt, dlist, wk, st);
+    vs_blend(vc, a, dlist, run_cnt, K, nullptr, P, st);
+    return;
+  }
   const uint32_t nq = vc.nq, NC = vc.n_clauses, K = vc.cand, R = refine ? refine : K;
   const VsPlan pl = vs_plan(ix, vc, R, refine != 0);
   const size_t n_run = (size_t)NC * nq * K, n_first = refine ? (size_t)NC * nq * R : 0, n_cnt = (size_t)NC * nq;
@@ -275,29 +574,48 @@ void vs_prepare_approx(uint32_t n_clauses, const uint32_t *clause_field, VsCall 
     vc->csegs[c] = it->second->d_csegs.as<slg::VecCopyDev>();
   }
 }
+// (slg_vector_search_batch_ivf*) nprobe and cand_size, checked first; then the lists of every clause's field
+void vs_check_ivf(uint32_t cand_size, uint32_t nprobe) {
+  if (nprobe < 1 || nprobe > SLG_MAX_VECTOR_PROBES)
+    throw SlgError(SLG_ERR_UNSUPPORTED, "nprobe outside 1..SLG_MAX_VECTOR_PROBES");
+  if (cand_size > slg::kVsSmallK)
+    throw SlgError(SLG_ERR_UNSUPPORTED, "cand_size > 64 is not built for the IVF search: use slg_vector_search_batch "
+                                        "or slg_vector_search_batch_approx");
+}
+void vs_prepare_ivf(uint32_t n_clauses, const uint32_t *clause_field, VsCall *vc) {
+  const IndexState &S = *vc->S;
+  for (uint32_t c = 0; c < n_clauses; c++) {
+    const auto it = S.vlists.find(clause_field[c]);
+    SLG_REQUIRE(it != S.vlists.end() && it->second->total_lists != 0,
+                "vector field " + std::to_string(clause_field[c]) + " has no lists (slg_index_cluster_vector_field)");
+    vc->lists[c] = it->second.get();
+  }
+}
 void vs_check_refine(uint32_t cand_size, uint32_t refine) {
   if (refine < cand_size || refine > SLG_MAX_VECTOR_CANDIDATES)
     throw SlgError(SLG_ERR_UNSUPPORTED, "refine outside cand_size..SLG_MAX_VECTOR_CANDIDATES");
 }
 
-// refine 0: the exact search (both forms)
+// refine 0 and nprobe 0: the exact search (both forms)
 void vs_device(slg_index *ix, uint32_t nq, uint32_t n_clauses, const uint32_t *clause_field, uint32_t cand_size,
-               uint32_t refine, uint32_t k_out, const VsArgs &d) {
+               uint32_t refine, uint32_t nprobe, uint32_t k_out, const VsArgs &d) {
   VsCall vc;
   if (!vs_prepare(ix, nq, n_clauses, clause_field, cand_size, k_out, d, false, &vc)) return;
   if (refine) vs_prepare_approx(n_clauses, clause_field, &vc);
+  if (nprobe) vs_prepare_ivf(n_clauses, clause_field, &vc);
   std::lock_guard<std::mutex> lk(ix->mu);
   DeviceGuard g(ix->device);
-  vs_run(ix, vc, d, refine, ix->stream);
+  vs_run(ix, vc, d, refine, nprobe, ix->stream);
 }
 
 // host arrays: checks, pooled device buffers, H2D, the kernels, D2H and a wait, all on the index stream
 // (Staging: slg_host.hpp)
 void vs_staged(slg_index *ix, uint32_t nq, uint32_t n_clauses, const uint32_t *clause_field, uint32_t cand_size,
-               uint32_t refine, uint32_t k_out, const VsArgs &h) {
+               uint32_t refine, uint32_t nprobe, uint32_t k_out, const VsArgs &h) {
   VsCall vc;
   if (!vs_prepare(ix, nq, n_clauses, clause_field, cand_size, k_out, h, true, &vc)) return;
   if (refine) vs_prepare_approx(n_clauses, clause_field, &vc);
+  if (nprobe) vs_prepare_ivf(n_clauses, clause_field, &vc);
   const size_t nqc = (size_t)nq * n_clauses, no = (size_t)nq * k_out;
   DeviceGuard g(ix->device);
   const hipStream_t st = ix->stream;
@@ -315,7 +633,7 @@ void vs_staged(slg_index *ix, uint32_t nq, uint32_t n_clauses, const uint32_t *c
   d.out_total = sg.up<uint64_t>(nullptr, nq);
   {
     std::lock_guard<std::mutex> lk(ix->mu);
-    vs_run(ix, vc, d, refine, st);
+    vs_run(ix, vc, d, refine, nprobe, st);
   }
   sg.down(h.out_doc, d.out_doc, no);
   sg.down(h.out_seg, d.out_seg, no);
@@ -413,7 +731,7 @@ int slg_vector_search_batch(slg_index *ix, uint32_t nq, uint32_t n_clauses, cons
                             uint32_t cand_size, uint32_t k_out, uint32_t *out_doc, uint32_t *out_seg,
                             float *out_score, float *out_vec_score, uint32_t *out_count, uint64_t *out_total) {
   return guarded([&] {
-    vs_staged(ix, nq, n_clauses, clause_field, cand_size, 0, k_out,
+    vs_staged(ix, nq, n_clauses, clause_field, cand_size, 0, 0, k_out,
               {qvecs, alpha, boost, q_filter, out_doc, out_seg, out_score, out_vec_score, out_count, out_total});
   });
 }
@@ -424,7 +742,7 @@ int slg_vector_search_batch_device(slg_index *ix, uint32_t nq, uint32_t n_clause
                                    uint32_t *d_out_doc, uint32_t *d_out_seg, float *d_out_score,
                                    float *d_out_vec_score, uint32_t *d_out_count, uint64_t *d_out_total) {
   return guarded([&] {
-    vs_device(ix, nq, n_clauses, clause_field, cand_size, 0, k_out,
+    vs_device(ix, nq, n_clauses, clause_field, cand_size, 0, 0, k_out,
               {d_qvecs, d_alpha, d_boost, d_q_filter, d_out_doc, d_out_seg, d_out_score, d_out_vec_score,
                d_out_count, d_out_total});
   });
@@ -437,7 +755,7 @@ int slg_vector_search_batch_approx(slg_index *ix, uint32_t nq, uint32_t n_clause
                                    uint64_t *out_total) {
   return guarded([&] {
     vs_check_refine(cand_size, refine);
-    vs_staged(ix, nq, n_clauses, clause_field, cand_size, refine, k_out,
+    vs_staged(ix, nq, n_clauses, clause_field, cand_size, refine, 0, k_out,
               {qvecs, alpha, boost, q_filter, out_doc, out_seg, out_score, out_vec_score, out_count, out_total});
   });
 }
@@ -450,7 +768,32 @@ int slg_vector_search_batch_approx_device(slg_index *ix, uint32_t nq, uint32_t n
                                           uint64_t *d_out_total) {
   return guarded([&] {
     vs_check_refine(cand_size, refine);
-    vs_device(ix, nq, n_clauses, clause_field, cand_size, refine, k_out,
+    vs_device(ix, nq, n_clauses, clause_field, cand_size, refine, 0, k_out,
+              {d_qvecs, d_alpha, d_boost, d_q_filter, d_out_doc, d_out_seg, d_out_score, d_out_vec_score,
+               d_out_count, d_out_total});
+  });
+}
+
+int slg_vector_search_batch_ivf(slg_index *ix, uint32_t nq, uint32_t n_clauses, const uint32_t *clause_field,
+                                const float *qvecs, const float *alpha, const float *boost, const int32_t *q_filter,
+                                uint32_t cand_size, uint32_t nprobe, uint32_t k_out, uint32_t *out_doc,
+                                uint32_t *out_seg, float *out_score, float *out_vec_score, uint32_t *out_count,
+                                uint64_t *out_total) {
+  return guarded([&] {
+    vs_check_ivf(cand_size, nprobe);
+    vs_staged(ix, nq, n_clauses, clause_field, cand_size, 0, nprobe, k_out,
+              {qvecs, alpha, boost, q_filter, out_doc, out_seg, out_score, out_vec_score, out_count, out_total});
+  });
+}
+
+int slg_vector_search_batch_ivf_device(slg_index *ix, uint32_t nq, uint32_t n_clauses, const uint32_t *clause_field,
+                                       const float *d_qvecs, const float *d_alpha, const float *d_boost,
+                                       const int32_t *d_q_filter, uint32_t cand_size, uint32_t nprobe, uint32_t k_out,
+                                       uint32_t *d_out_doc, uint32_t *d_out_seg, float *d_out_score,
+                                       float *d_out_vec_score, uint32_t *d_out_count, uint64_t *d_out_total) {
+  return guarded([&] {
+    vs_check_ivf(cand_size, nprobe);
+    vs_device(ix, nq, n_clauses, clause_field, cand_size, 0, nprobe, k_out,
               {d_qvecs, d_alpha, d_boost, d_q_filter, d_out_doc, d_out_seg, d_out_score, d_out_vec_score,
                d_out_count, d_out_total});
   });

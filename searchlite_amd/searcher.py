@@ -1168,6 +1168,79 @@ class GpuIndex:
             self._h, nq, len(cf), _ptr(cf), d_qvecs, d_alpha, d_boost, d_q_filter, int(cand_size), int(refine),
             int(k_out), d_out_doc, d_out_seg, d_out_score, d_out_vec, d_out_count, d_out_total))
 
+    def cluster_vector_field(self, field: int, per_segment) -> None:
+        """Build the inverted-file lists of vector field `field` on the device (slg_index_cluster_vector_field):
+        what vector_search_ivf probes.  per_segment[s] = the segment's centroids f32 [n_lists, dim], None (the
+        segment is or becomes unclustered) or N.KEEP_VECTOR_LISTS (its lists stay as they are)."""
+        descs = (N.VectorListsDesc * max(len(per_segment), 1))()
+        keep = []
+        for s, c in enumerate(per_segment):
+            if c is None:
+                descs[s].n_lists, descs[s].centroids = 0, None
+            elif isinstance(c, int):
+                descs[s].n_lists, descs[s].centroids = int(c), None
+            else:
+                c = np.ascontiguousarray(c, dtype=np.float32)
+                keep.append(c)
+                descs[s].n_lists, descs[s].centroids = c.shape[0], c.ctypes.data
+        N.check(self._lib.slg_index_cluster_vector_field(self._h, int(field), C.addressof(descs), len(per_segment)))
+
+    def fetch_vector_lists(self, field: int, seg: int, dim: int):
+        """The lists of segment `seg` in `field` (slg_index_fetch_vector_lists): (list_begin u32 [n_lists + 1],
+        docs u32 [list_begin[-1]], centroids f32 [n_lists, dim]), or None when the segment is unclustered or has
+        no vectors in the field.  dim: the field's dimension."""
+        n = self._lib.slg_index_fetch_vector_lists(self._h, int(field), int(seg), None, None, None, 0, 0)
+        if n < 0:
+            N.check(n)
+        if n == 0:
+            return None
+        begin = np.zeros(n + 1, np.uint32)
+        cents = np.zeros((n, int(dim)), np.float32)
+        rc = self._lib.slg_index_fetch_vector_lists(self._h, int(field), int(seg), _ptr(begin), None, _ptr(cents), n, 0)
+        if rc < 0:
+            N.check(rc)
+        docs = np.zeros(int(begin[-1]), np.uint32)
+        if len(docs):
+            rc = self._lib.slg_index_fetch_vector_lists(self._h, int(field), int(seg), _ptr(begin), _ptr(docs),
+                                                        _ptr(cents), n, len(docs))
+            if rc < 0:
+                N.check(rc)
+        return begin, docs, cents
+
+    def vector_search_ivf(self, clause_field, qvecs, alpha, cand_size: int, nprobe: int, k_out: int, boost=None,
+                          q_filter=None):
+        """Vector search over the fields' inverted-file lists (slg_vector_search_batch_ivf): per clause the docs
+        of the `nprobe` lists nearest the query (cluster_vector_field) and of the unclustered segments are scored
+        from the f32 store, and the best cand_size form the clause's list.  Arguments and result as
+        vector_search(); every returned score is the exact call's, and nprobe >= the lists of every clause's
+        field makes the whole result the exact call's.  cand_size <= 64."""
+        cf = np.ascontiguousarray(clause_field, dtype=np.uint32)
+        nc = len(cf)
+        qvecs = np.ascontiguousarray(qvecs, dtype=np.float32)
+        nq = qvecs.shape[0]
+        alpha, bst = _f32(alpha, (nq, nc)), _f32(boost, (nq, nc))
+        flt = None if q_filter is None else np.ascontiguousarray(q_filter, dtype=np.int32)
+        doc = np.zeros((nq, k_out), np.uint32)
+        seg = np.zeros((nq, k_out), np.uint32)
+        score = np.zeros((nq, k_out), np.float32)
+        vec = np.zeros((nq, k_out), np.float32)
+        count = np.zeros(nq, np.uint32)
+        total = np.zeros(nq, np.uint64)
+        N.check(self._lib.slg_vector_search_batch_ivf(
+            self._h, nq, nc, _ptr(cf), _ptr(qvecs), _ptr(alpha), _ptr(bst), _ptr(flt), int(cand_size), int(nprobe),
+            int(k_out), _ptr(doc), _ptr(seg), _ptr(score), _ptr(vec), _ptr(count), _ptr(total)))
+        return doc, seg, score, vec, count, total
+
+    def vector_search_ivf_device(self, nq, clause_field, d_qvecs, d_alpha, d_boost, d_q_filter, cand_size, nprobe,
+                                 k_out, d_out_doc, d_out_seg, d_out_score, d_out_vec, d_out_count,
+                                 d_out_total) -> None:
+        """Device-pointer form of vector_search_ivf (ints; d_boost / d_q_filter may be None; clause_field stays a
+        host array), asynchronous on the index stream."""
+        cf = np.ascontiguousarray(clause_field, dtype=np.uint32)
+        N.check(self._lib.slg_vector_search_batch_ivf_device(
+            self._h, nq, len(cf), _ptr(cf), d_qvecs, d_alpha, d_boost, d_q_filter, int(cand_size), int(nprobe),
+            int(k_out), d_out_doc, d_out_seg, d_out_score, d_out_vec, d_out_count, d_out_total))
+
     def search_hybrid(self, q_offsets, q_terms, q_weights, k: int, clause_field, qvecs, alpha, cand_size: int,
                       k_out: int, boost=None, strategy: int = Wand, q_filter=None, **plans):
         """Hybrid text + vector search (merge_vector_hits, api/reader.rs:2474-2537) in one call: the BM25 top k

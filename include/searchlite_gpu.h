@@ -1595,6 +1595,60 @@ int slg_vector_search_batch_ivf_device(slg_index *index, uint32_t nq, uint32_t n
                                        uint64_t *d_out_total);
 
 /*
+ * Training the centroids of an IVF index on the device: Lloyd steps over the f32 store.
+ *
+ * slg_index_train_vector_field computes, for every segment s with per_segment[s].n_lists in
+ * 1..SLG_MAX_VECTOR_LISTS, centroids on the device from the segment's own store and builds the segment's lists
+ * around them in a new index state.  The lifecycle is slg_index_cluster_vector_field's: n_lists 0 leaves (or makes)
+ * the segment unclustered, SLG_KEEP_VECTOR_LISTS keeps the segment's list object by reference, earlier states keep
+ * theirs, and slg_index_fetch_vector_lists returns the trained centroids.  The algorithm, in the order of its
+ * floating-point operations (R = the rows of the segment's value array, dim = the field's dimension):
+ *   start   C_0 = init when it is given, used as given.  Otherwise centroid i is row floor(i * R / n_lists) of the
+ *           value array (u64 arithmetic), copied on the device as stored.
+ *   assign  A_t = assign(C_{t-1}), t = 1 .. iters, is the assignment of slg_index_cluster_vector_field for those
+ *           centroids: the exact scan's arithmetic, ties to the lowest list, deleted docs assigned (and summed:
+ *           tombstones apply at search time only), docs without a vector in no list, docs ascending in a list.
+ *   stop    moved_t = the rows (of the value array) whose list differs from the one in A_{t-1}; moved_1 = R.  If
+ *           t > 1 and moved_t == 0, training stops with C_{t-1}.  That is a fixed point, because the update depends
+ *           only on the assignment and an empty list keeps its centroid: the early stop never changes the result.
+ *   update  C_t = update(A_t, C_{t-1}), per list l with its n docs ascending:
+ *             sum[d]: the docs are cut into consecutive chunks of SLG_VECTOR_TRAIN_CHUNK; per chunk an f64 sum of
+ *               (double)row[d] in doc order from +0.0; the chunk sums added in chunk order from +0.0;
+ *             m[d] = (float)(sum[d] / (double)n);
+ *             s = sum over d ascending of (double)m[d] * (double)m[d], from +0.0;
+ *             the list adopts a new centroid iff n > 0, s is finite and (cosine only) s > 0; otherwise
+ *               C_t[l] = C_{t-1}[l] bit for bit;
+ *             the new centroid is m (L2) or (float)((double)m[d] / sqrt(s)) (cosine).
+ *           Division, square root and the f64 -> f32 conversions are IEEE round-to-nearest-even, correctly rounded;
+ *           nothing is contracted.  No floating-point atomics: the bytes do not depend on the device's schedule.
+ *   finish  the state's lists are assign(final centroids): A_t after an early stop, one more assignment after the
+ *           last step, assign(C_0) with iters 0.
+ * Guarantee: the resulting state is byte-identical to slg_index_cluster_vector_field called with the centroids
+ * slg_index_fetch_vector_lists returns.
+ * out_stats (NULL, or [n_segs]), per trained segment: iters_run = the updates applied; moved = moved_t of the last
+ * assignment made by a step t <= iters (0 after an early stop; 0 with iters 0: the finishing assignment is not a
+ * step); empty_lists and max_len of the final lists.  Untrained segments get zeros.  Nothing is written on error.
+ * Errors, all before any device work: SLG_ERR_UNSUPPORTED: iters > SLG_MAX_VECTOR_TRAIN_ITERS on a trained segment
+ * (checked first, before the index is looked at), n_lists > SLG_MAX_VECTOR_LISTS; SLG_ERR_INVALID: NULL index, no
+ * such field, n_segs other than the index's segment count, n_lists > 0 on a segment without vectors in the field,
+ * init NULL with n_lists greater than R.
+ * The loop runs on the index stream with scratch released before the call returns (two list ids per row, the
+ * partial sums: 8 bytes x dim per (list, chunk)); per step the host reads back moved and the list lengths.
+ * Not built: training on a sample; k-means++ or seeded starts on the device (pass init); re-seeding of empty
+ * lists; training across segments; training over the bf16 copy.
+ */
+#define SLG_MAX_VECTOR_TRAIN_ITERS 256u
+#define SLG_VECTOR_TRAIN_CHUNK     256u   /* docs of one partial sum, see "update" */
+typedef struct {
+  uint32_t n_lists;     /* 0: the segment is (or becomes) unclustered; SLG_KEEP_VECTOR_LISTS: unchanged; else train */
+  uint32_t iters;       /* Lloyd steps at most, 0 .. SLG_MAX_VECTOR_TRAIN_ITERS */
+  const float *init;    /* [n_lists * vec_dim] host array, used as given; NULL: rows of the store, see "start" */
+} slg_vector_train_desc;                 /* 16 bytes */
+typedef struct { uint32_t iters_run, moved, empty_lists, max_len; } slg_vector_train_stats;
+int slg_index_train_vector_field(slg_index *index, uint32_t field, const slg_vector_train_desc *per_segment,
+                                 uint32_t n_segs, slg_vector_train_stats *out_stats /* [n_segs] or NULL */);
+
+/*
  * Hybrid text + vector search: one request with a text query and vector clauses (api/reader.rs:2754-2775:
  * collect_vector_maps with require_text_match = true, then merge_vector_hits, :2474-2537).  Per query:
  *   1. the matched set M = every doc the text query matches that is not deleted and passes q_filter (and

@@ -40,6 +40,10 @@ pub const SLG_MAX_VECTOR_LISTS: u32 = 65536;
 pub const SLG_MAX_VECTOR_PROBES: u32 = 256;
 pub const SLG_KEEP_VECTOR_LISTS: u32 = 0xFFFF_FFFF;
 #[repr(C)] pub struct slg_vector_lists_desc { pub n_lists: u32, pub centroids: *const c_float }
+pub const SLG_MAX_VECTOR_TRAIN_ITERS: u32 = 256;
+pub const SLG_VECTOR_TRAIN_CHUNK: u32 = 256;
+#[repr(C)] pub struct slg_vector_train_desc { pub n_lists: u32, pub iters: u32, pub init: *const c_float }
+#[repr(C)] pub struct slg_vector_train_stats { pub iters_run: u32, pub moved: u32, pub empty_lists: u32, pub max_len: u32 }
 #[repr(C)] pub struct slg_score_plans {
     pub q_leaf: *const u32, pub q_plan: *const i32, pub q_tie: *const c_float, pub q_nleaves: *const u32,
     pub q_leaf_offsets: *const u32, pub leaf_group: *const u32, pub q_group_offsets: *const u32,
@@ -527,6 +531,9 @@ extern "C" {
         per_segment: *const slg_vector_lists_desc, n_segs: u32) -> c_int;
     pub fn slg_index_fetch_vector_lists(index: *mut slg_index, field: u32, seg: u32, out_list_begin: *mut u32,
         out_docs: *mut u32, out_centroids: *mut c_float, lists_cap: u32, docs_cap: u32) -> c_int;
+    // Lloyd steps over the f32 store on the device, then the lists of the trained centroids (out_stats may be null)
+    pub fn slg_index_train_vector_field(index: *mut slg_index, field: u32,
+        per_segment: *const slg_vector_train_desc, n_segs: u32, out_stats: *mut slg_vector_train_stats) -> c_int;
     pub fn slg_vector_search_batch_ivf(index: *mut slg_index, nq: u32, n_clauses: u32, clause_field: *const u32,
         qvecs: *const c_float, alpha: *const c_float, boost: *const c_float, q_filter: *const i32, cand_size: u32,
         nprobe: u32, k_out: u32, out_doc: *mut u32, out_seg: *mut u32, out_score: *mut c_float,

@@ -20,6 +20,8 @@ MAX_VECTOR_CANDIDATES = 10000
 MAX_VECTOR_LISTS = 65536
 MAX_VECTOR_PROBES = 256
 KEEP_VECTOR_LISTS = 0xFFFFFFFF
+MAX_VECTOR_TRAIN_ITERS = 256
+VECTOR_TRAIN_CHUNK = 256
 SHARD_UNIQUE_ID_BYTES = 128
 
 OK, ERR_INVALID, ERR_DEVICE, ERR_OOM, ERR_UNSUPPORTED, ERR_INTERNAL = 0, -1, -2, -3, -4, -5
@@ -131,6 +133,15 @@ class VectorFieldDesc(C.Structure):
 
 class VectorListsDesc(C.Structure):
     _fields_ = [("n_lists", C.c_uint32), ("centroids", C.c_void_p)]
+
+
+class VectorTrainDesc(C.Structure):
+    _fields_ = [("n_lists", C.c_uint32), ("iters", C.c_uint32), ("init", C.c_void_p)]
+
+
+class VectorTrainStats(C.Structure):
+    _fields_ = [("iters_run", C.c_uint32), ("moved", C.c_uint32), ("empty_lists", C.c_uint32),
+                ("max_len", C.c_uint32)]
 
 
 class Stats(C.Structure):
@@ -569,6 +580,7 @@ def load():
                                                         vp, vp, vp]),
         "slg_index_cluster_vector_field": (i32, [vp, u32, vp, u32]),
         "slg_index_fetch_vector_lists": (i32, [vp, u32, u32, vp, vp, vp, u32, u32]),
+        "slg_index_train_vector_field": (i32, [vp, u32, vp, u32, vp]),
         "slg_vector_search_batch_ivf": (i32, [vp, u32, u32, vp, vp, vp, vp, vp, u32, u32, u32, vp, vp, vp, vp,
                                               vp, vp]),
         "slg_vector_search_batch_ivf_device": (i32, [vp, u32, u32, vp, vp, vp, vp, vp, u32, u32, u32, vp, vp, vp,

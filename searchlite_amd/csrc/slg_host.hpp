@@ -1154,6 +1154,12 @@ std::shared_ptr<VecCopySeg> vs_quantize_store(slg_index *ix, const float *d_valu
 std::shared_ptr<VecListSeg> vs_cluster_store(slg_index *ix, const uint32_t *d_offsets, const float *d_values,
                                              uint32_t n_docs, uint32_t n_rows, uint32_t dim, int32_t metric,
                                              const float *centroids, uint32_t n_lists);
+// slg_vsearch.hip: at most iters Lloyd steps from init (null: rows of the store) on the index stream, then the
+// lists of the final centroids (slg_index_train_vector_field); its scratch is gone when it returns
+std::shared_ptr<VecListSeg> vs_train_store(slg_index *ix, const uint32_t *d_offsets, const float *d_values,
+                                           uint32_t n_docs, uint32_t n_rows, uint32_t dim, int32_t metric,
+                                           const float *init, uint32_t n_lists, uint32_t iters,
+                                           slg_vector_train_stats *stats);
 // slg_vsearch.hip: the steps a hybrid call (slg_hybrid.hip) shares with the vector search, whose kernels they
 // run.  HyWork: the clause lists and sort space of one call, laid out over one block (base null: the size only);
 // cnt = run_cnt [clause][nq] then key_cnt [clause][nq], zeroed by the caller

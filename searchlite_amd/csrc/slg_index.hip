@@ -540,6 +540,32 @@ size_t state_device_bytes(const IndexState &s) {
 
 }  // namespace
 
+namespace {
+// the store of segment s in vector field `field` of a state (*dim 0: the segment has no vectors in the field)
+void vec_store_of(const IndexState &cur, uint32_t field, size_t s, const uint32_t **offs, const float **vals,
+                  uint32_t *rows, uint32_t *dim, int32_t *metric) {
+  *dim = 0;
+  if (field == 0) {
+    const PostingStore &ps = *cur.segs[s]->store;
+    if (!ps.vec_dim) return;
+    *offs = ps.d_vec_offsets.as<uint32_t>();
+    *vals = ps.d_vec_values.as<float>();
+    *rows = ps.vec_rows;
+    *dim = ps.vec_dim;
+    *metric = ps.vec_metric;
+  } else {
+    const VecFieldHost &vf = *cur.vfields[field - 1];
+    if (s >= vf.per_seg.size() || !vf.per_seg[s]) return;
+    const VecSegStore &st = *vf.per_seg[s];
+    *offs = st.offsets.as<uint32_t>();
+    *vals = st.values.as<float>();
+    *rows = st.n_rows;
+    *dim = st.dim;
+    *metric = vf.metric;
+  }
+}
+}  // namespace
+
 extern "C" {
 
 uint32_t slg_abi_version(void) { return SLG_ABI_VERSION; }
@@ -1811,27 +1837,7 @@ int slg_index_cluster_vector_field(slg_index *ix, uint32_t field, const slg_vect
       SLG_REQUIRE(n_segs == cur.segs.size(), "n_segs is not the index's segment count");
       SLG_REQUIRE(per_segment != nullptr || n_segs == 0, "per_segment is NULL");
       auto store_of = [&](size_t s, const uint32_t **offs, const float **vals, uint32_t *rows, uint32_t *dim,
-                          int32_t *metric) {
-        *dim = 0;
-        if (field == 0) {
-          const PostingStore &ps = *cur.segs[s]->store;
-          if (!ps.vec_dim) return;
-          *offs = ps.d_vec_offsets.as<uint32_t>();
-          *vals = ps.d_vec_values.as<float>();
-          *rows = ps.vec_rows;
-          *dim = ps.vec_dim;
-          *metric = ps.vec_metric;
-        } else {
-          const VecFieldHost &vf = *cur.vfields[field - 1];
-          if (s >= vf.per_seg.size() || !vf.per_seg[s]) return;
-          const VecSegStore &st = *vf.per_seg[s];
-          *offs = st.offsets.as<uint32_t>();
-          *vals = st.values.as<float>();
-          *rows = st.n_rows;
-          *dim = st.dim;
-          *metric = vf.metric;
-        }
-      };
+                          int32_t *metric) { vec_store_of(cur, field, s, offs, vals, rows, dim, metric); };
       for (uint32_t s = 0; s < n_segs; s++) {
         const slg_vector_lists_desc &d = per_segment[s];
         if (d.n_lists == 0 || d.n_lists == SLG_KEEP_VECTOR_LISTS) continue;
@@ -1863,6 +1869,61 @@ int slg_index_cluster_vector_field(slg_index *ix, uint32_t field, const slg_vect
       }
       ns.vlists[field] = std::move(vl);
     });
+  });
+}
+
+int slg_index_train_vector_field(slg_index *ix, uint32_t field, const slg_vector_train_desc *per_segment,
+                                 uint32_t n_segs, slg_vector_train_stats *out_stats) {
+  return guarded([&] {
+    auto trained = [](const slg_vector_train_desc &d) { return d.n_lists != 0 && d.n_lists != SLG_KEEP_VECTOR_LISTS; };
+    if (per_segment)  // the iters check comes first, before the index is looked at
+      for (uint32_t s = 0; s < n_segs; s++)
+        if (trained(per_segment[s]) && per_segment[s].iters > SLG_MAX_VECTOR_TRAIN_ITERS)
+          throw SlgError(SLG_ERR_UNSUPPORTED, "iters > SLG_MAX_VECTOR_TRAIN_ITERS");
+    SLG_REQUIRE(ix != nullptr, "index is NULL");
+    std::vector<slg_vector_train_stats> stats;  // (sized once n_segs is known to be the index's)
+    update_state(ix, false, [&](const IndexState &cur, IndexState &ns) {
+      // every check before any device work
+      SLG_REQUIRE(field <= cur.vfields.size(), "unknown vector field id");
+      SLG_REQUIRE(n_segs == cur.segs.size(), "n_segs is not the index's segment count");
+      SLG_REQUIRE(per_segment != nullptr || n_segs == 0, "per_segment is NULL");
+      stats.assign(n_segs, slg_vector_train_stats{0u, 0u, 0u, 0u});
+      for (uint32_t s = 0; s < n_segs; s++) {
+        const slg_vector_train_desc &d = per_segment[s];
+        if (!trained(d)) continue;
+        if (d.n_lists > SLG_MAX_VECTOR_LISTS) throw SlgError(SLG_ERR_UNSUPPORTED, "n_lists > SLG_MAX_VECTOR_LISTS");
+        const uint32_t *offs = nullptr;
+        const float *vals = nullptr;
+        uint32_t rows = 0, dim = 0;
+        int32_t metric = 0;
+        vec_store_of(cur, field, s, &offs, &vals, &rows, &dim, &metric);
+        SLG_REQUIRE(dim != 0, "n_lists > 0 on segment " + std::to_string(s) + ", which has no vectors in the field");
+        SLG_REQUIRE(d.init != nullptr || d.n_lists <= rows,
+                    "init is NULL and n_lists exceeds the " + std::to_string(rows) + " rows of segment " +
+                        std::to_string(s) + "'s store");
+      }
+      auto vl = std::make_shared<VecListField>();
+      const auto old = cur.vlists.find(field);
+      vl->per_seg.resize(n_segs);
+      for (uint32_t s = 0; s < n_segs; s++) {
+        const slg_vector_train_desc &d = per_segment[s];
+        if (d.n_lists == SLG_KEEP_VECTOR_LISTS) {
+          if (old != cur.vlists.end() && s < old->second->per_seg.size()) vl->per_seg[s] = old->second->per_seg[s];
+          continue;
+        }
+        if (d.n_lists == 0) continue;
+        const uint32_t *offs = nullptr;
+        const float *vals = nullptr;
+        uint32_t rows = 0, dim = 0;
+        int32_t metric = 0;
+        vec_store_of(cur, field, s, &offs, &vals, &rows, &dim, &metric);
+        vl->per_seg[s] = vs_train_store(ix, offs, vals, cur.segs[s]->n_docs, rows, dim, metric, d.init, d.n_lists,
+                                        d.iters, &stats[s]);
+      }
+      ns.vlists[field] = std::move(vl);
+    });
+    if (out_stats)
+      for (uint32_t s = 0; s < n_segs; s++) out_stats[s] = stats[s];
   });
 }
 

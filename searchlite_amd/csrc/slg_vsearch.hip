@@ -6,8 +6,11 @@
 #include "slg_vsearch.hpp"
 #include "slg_vsearch_approx.hpp"
 #include "slg_vsearch_ivf.hpp"
+#include "slg_vsearch_train.hpp"
 
 using namespace slghost;
+
+static_assert(slg::kIvfTrainChunk == SLG_VECTOR_TRAIN_CHUNK, "the chunk of a partial sum is part of the ABI");
 
 bool slghost::vs_prepare(slg_index *ix, uint32_t nq, uint32_t n_clauses, const uint32_t *clause_field,
                          uint32_t cand_size, uint32_t k_out, const VsArgs &a, bool host_filter, VsCall *vc,
@@ -69,48 +72,54 @@ uint32_t vs_resident_groups(slg_index *ix, size_t lds, uint32_t by_vgprs = 3u) {
   const uint32_t per_cu = std::min<uint32_t>(by_vgprs, (uint32_t)((160u << 10) / lds));
   return std::max<uint32_t>((uint32_t)n_cu, 1u) * std::max<uint32_t>(per_cu, 1u);
 }
-}  // namespace
 
-std::shared_ptr<VecListSeg> slghost::vs_cluster_store(slg_index *ix, const uint32_t *d_offsets, const float *d_values,
-                                                      uint32_t n_docs, uint32_t n_rows, uint32_t dim, int32_t metric,
-                                                      const float *centroids, uint32_t n_lists) {
-  const hipStream_t st = ix->stream;
+// a segment's list object with its tables allocated: the centroid table (not yet filled), the list ids 0, 1, ..
+std::shared_ptr<VecListSeg> vs_new_lists(slg_index *ix, uint32_t n_lists, uint32_t dim) {
   auto ls = std::make_shared<VecListSeg>();
   ls->n_lists = n_lists;
   ls->dim = dim;
   ls->list_begin.alloc(((size_t)n_lists + 1) * 4, &ix->pool);
   ls->centroids.alloc((size_t)n_lists * dim * 4, &ix->pool);
   ls->iota.alloc((size_t)n_lists * 4, &ix->pool);
-  SLG_HIP(hipMemcpy(ls->centroids.p, centroids, (size_t)n_lists * dim * 4, hipMemcpyHostToDevice));
-  {
-    std::vector<uint32_t> iota(n_lists);
-    for (uint32_t i = 0; i < n_lists; i++) iota[i] = i;
-    SLG_HIP(hipMemcpy(ls->iota.p, iota.data(), (size_t)n_lists * 4, hipMemcpyHostToDevice));
-  }
-  // ---- the list of every row: an exact scan with the rows as queries, the centroids as the docs of one
-  //      pseudo-segment without tombstones, and a top-1 ----
-  const slg::VecSegDev cseg{ls->iota.as<uint32_t>(), ls->centroids.as<float>(), n_lists, dim, metric, 0u};
-  const slg::SegDev pseg{};
-  const uint32_t cbase[2] = {0u, n_lists};
-  DevBuf d_cseg, d_pseg, d_cbase, row_list, doc_list, table, lens, partials;
-  d_cseg.alloc(sizeof(cseg), &ix->pool);
-  d_pseg.alloc(sizeof(pseg), &ix->pool);
-  d_cbase.alloc(sizeof(cbase), &ix->pool);
-  SLG_HIP(hipMemcpy(d_cseg.p, &cseg, sizeof(cseg), hipMemcpyHostToDevice));
-  SLG_HIP(hipMemcpy(d_pseg.p, &pseg, sizeof(pseg), hipMemcpyHostToDevice));
-  SLG_HIP(hipMemcpy(d_cbase.p, cbase, sizeof(cbase), hipMemcpyHostToDevice));
-  row_list.alloc(std::max<size_t>(n_rows, 1) * 4, &ix->pool);
-  const uint32_t n_tiles = (n_lists + slg::kVsTileDocs - 1) / slg::kVsTileDocs;
-  const size_t lds = slg::vs_scan_lds_bytes(true, slg::kVsBufCapNarrow);
-  const uint32_t target = vs_resident_groups(ix, lds);
-  const uint32_t batch = 65536;  // rows of one scan
-  if (n_rows) {
+  std::vector<uint32_t> iota(n_lists);
+  for (uint32_t i = 0; i < n_lists; i++) iota[i] = i;
+  SLG_HIP(hipMemcpy(ls->iota.p, iota.data(), (size_t)n_lists * 4, hipMemcpyHostToDevice));
+  return ls;
+}
+
+// ---- the list of every row: an exact scan with the rows as queries, the centroids as the docs of one
+//      pseudo-segment without tombstones, and a top-1 ----
+// (the tables point at ls's centroid table: run() assigns to whatever it holds at that point of the stream)
+struct IvfAssign {
+  DevBuf d_cseg, d_pseg, d_cbase, partials;
+  slg::VsScanParams sp{};
+  const float *d_values = nullptr;
+  uint32_t n_rows = 0, n_chunks = 0;
+  int32_t metric = 0;
+  size_t lds = 0;
+  static constexpr uint32_t batch = 65536;  // rows of one scan
+
+  IvfAssign(slg_index *ix, const VecListSeg &ls, const float *values, uint32_t rows, int32_t metric_)
+      : d_values(values), n_rows(rows), metric(metric_) {
+    const uint32_t n_lists = ls.n_lists, dim = ls.dim;
+    const slg::VecSegDev cseg{ls.iota.as<uint32_t>(), ls.centroids.as<float>(), n_lists, dim, metric, 0u};
+    const slg::SegDev pseg{};
+    const uint32_t cbase[2] = {0u, n_lists};
+    d_cseg.alloc(sizeof(cseg), &ix->pool);
+    d_pseg.alloc(sizeof(pseg), &ix->pool);
+    d_cbase.alloc(sizeof(cbase), &ix->pool);
+    SLG_HIP(hipMemcpy(d_cseg.p, &cseg, sizeof(cseg), hipMemcpyHostToDevice));
+    SLG_HIP(hipMemcpy(d_pseg.p, &pseg, sizeof(pseg), hipMemcpyHostToDevice));
+    SLG_HIP(hipMemcpy(d_cbase.p, cbase, sizeof(cbase), hipMemcpyHostToDevice));
+    const uint32_t n_tiles = (n_lists + slg::kVsTileDocs - 1) / slg::kVsTileDocs;
+    lds = slg::vs_scan_lds_bytes(true, slg::kVsBufCapNarrow);
+    const uint32_t target = vs_resident_groups(ix, lds);
+    if (!n_rows) return;
     const uint32_t b_rows = std::min(batch, n_rows), qtiles = (b_rows + slg::kVsTileQ - 1) / slg::kVsTileQ;
-    uint32_t n_chunks = std::min<uint32_t>(std::max<uint32_t>((target + qtiles - 1) / qtiles, 1u), n_tiles);
+    n_chunks = std::min<uint32_t>(std::max<uint32_t>((target + qtiles - 1) / qtiles, 1u), n_tiles);
     const uint32_t tpb = (n_tiles + n_chunks - 1) / n_chunks;
     n_chunks = (n_tiles + tpb - 1) / tpb;
     partials.alloc((size_t)b_rows * n_chunks * slg::kVsSmallK * 8, &ix->pool);
-    slg::VsScanParams sp{};
     sp.vsegs = d_cseg.as<slg::VecSegDev>();
     sp.segs = d_pseg.as<slg::SegDev>();
     sp.doc_base = d_cbase.as<uint32_t>();
@@ -125,21 +134,32 @@ std::shared_ptr<VecListSeg> slghost::vs_cluster_store(slg_index *ix, const uint3
     sp.out = partials.as<uint64_t>();
     sp.k = 1;
     sp.cap = slg::kVsBufCapNarrow;
+  }
+
+  void run(uint32_t *row_list, hipStream_t st) {
     for (uint32_t r0 = 0; r0 < n_rows; r0 += batch) {
       const uint32_t nr = std::min(batch, n_rows - r0);
       sp.nq = nr;
-      sp.qvecs = d_values + (size_t)r0 * dim;
+      sp.qvecs = d_values + (size_t)r0 * sp.dim;
       const dim3 grid((nr + slg::kVsTileQ - 1) / slg::kVsTileQ, n_chunks);
       if (metric == 0)
         launch_kernel_lds(slg::vs_scan_kernel<0, true>, sp, grid, 256, lds, st);
       else
         launch_kernel_lds(slg::vs_scan_kernel<1, true>, sp, grid, 256, lds, st);
-      slg::IvfBestParams bp{partials.as<uint64_t>(), nr, n_chunks, row_list.as<uint32_t>() + r0};
+      slg::IvfBestParams bp{partials.as<uint64_t>(), nr, n_chunks, row_list + r0};
       hipLaunchKernelGGL(slg::vs_ivf_best_kernel, dim3((nr + 255) / 256), dim3(256), 0, st, bp);
       SLG_HIP(hipGetLastError());
     }
   }
-  // ---- the lists: count per (list, doc range), prefix per list, exclusive scan of the lengths, ordered fill ----
+};
+
+// ---- the lists of an assignment: count per (list, doc range), prefix per list, exclusive scan of the lengths,
+//      ordered fill.  lb: list_begin as read back ----
+void vs_build_lists(slg_index *ix, const uint32_t *d_offsets, uint32_t n_docs, const uint32_t *row_list,
+                    VecListSeg *ls, std::vector<uint32_t> *lb_out) {
+  const hipStream_t st = ix->stream;
+  const uint32_t n_lists = ls->n_lists;
+  DevBuf doc_list, table, lens;
   const uint32_t max_ranges = std::max<uint32_t>(std::min<uint32_t>(slg::kIvfMaxRanges, (16u << 20) / n_lists), 1u);
   uint32_t range_docs = std::max<uint32_t>(slg::kIvfRangeDocs, (n_docs + max_ranges - 1) / max_ranges);
   range_docs = (range_docs + 63u) / 64u * 64u;
@@ -150,7 +170,7 @@ std::shared_ptr<VecListSeg> slghost::vs_cluster_store(slg_index *ix, const uint3
   SLG_HIP(hipMemsetAsync(table.p, 0, (size_t)n_lists * n_ranges * 4, st));
   slg::IvfBuildParams bp{};
   bp.offsets = d_offsets;
-  bp.row_list = row_list.as<uint32_t>();
+  bp.row_list = row_list;
   bp.doc_list = doc_list.as<uint32_t>();
   bp.table = table.as<uint32_t>();
   bp.lens = lens.as<uint32_t>();
@@ -164,17 +184,122 @@ std::shared_ptr<VecListSeg> slghost::vs_cluster_store(slg_index *ix, const uint3
   slg::IvfScanParams xp{lens.as<uint32_t>(), ls->list_begin.as<uint32_t>(), n_lists};
   hipLaunchKernelGGL(slg::vs_ivf_exscan_kernel, dim3(1), dim3(slg::kIvfScanThreads), 0, st, xp);
   SLG_HIP(hipGetLastError());
-  std::vector<uint32_t> lb((size_t)n_lists + 1);
+  std::vector<uint32_t> &lb = *lb_out;
+  lb.assign((size_t)n_lists + 1, 0u);
   SLG_HIP(hipMemcpyAsync(lb.data(), ls->list_begin.p, lb.size() * 4, hipMemcpyDeviceToHost, st));
   SLG_HIP(hipStreamSynchronize(st));
   ls->n_listed = lb[n_lists];
   SLG_REQUIRE(ls->n_listed <= n_docs, "the lists hold more docs than the segment");
+  ls->max_len = 0;
   for (uint32_t l = 0; l < n_lists; l++) ls->max_len = std::max(ls->max_len, lb[l + 1] - lb[l]);
-  ls->docs.alloc(std::max<size_t>(ls->n_listed, 1) * 4, &ix->pool);
+  const size_t docs_bytes = std::max<size_t>(ls->n_listed, 1) * 4;
+  if (ls->docs.bytes != docs_bytes) ls->docs.alloc(docs_bytes, &ix->pool);
   bp.docs = ls->docs.as<uint32_t>();
   if (n_docs) hipLaunchKernelGGL(slg::vs_ivf_fill_kernel, dim3(n_ranges), dim3(64), 0, st, bp);
   SLG_HIP(hipGetLastError());
   SLG_HIP(hipStreamSynchronize(st));
+}
+
+}  // namespace
+
+std::shared_ptr<VecListSeg> slghost::vs_cluster_store(slg_index *ix, const uint32_t *d_offsets, const float *d_values,
+                                                      uint32_t n_docs, uint32_t n_rows, uint32_t dim, int32_t metric,
+                                                      const float *centroids, uint32_t n_lists) {
+  auto ls = vs_new_lists(ix, n_lists, dim);
+  SLG_HIP(hipMemcpy(ls->centroids.p, centroids, (size_t)n_lists * dim * 4, hipMemcpyHostToDevice));
+  DevBuf row_list;
+  row_list.alloc(std::max<size_t>(n_rows, 1) * 4, &ix->pool);
+  IvfAssign assign(ix, *ls, d_values, n_rows, metric);
+  assign.run(row_list.as<uint32_t>(), ix->stream);
+  std::vector<uint32_t> lb;
+  vs_build_lists(ix, d_offsets, n_docs, row_list.as<uint32_t>(), ls.get(), &lb);
+  return ls;
+}
+
+std::shared_ptr<VecListSeg> slghost::vs_train_store(slg_index *ix, const uint32_t *d_offsets, const float *d_values,
+                                                    uint32_t n_docs, uint32_t n_rows, uint32_t dim, int32_t metric,
+                                                    const float *init, uint32_t n_lists, uint32_t iters,
+                                                    slg_vector_train_stats *stats) {
+  const hipStream_t st = ix->stream;
+  auto ls = vs_new_lists(ix, n_lists, dim);
+  const size_t c_bytes = (size_t)n_lists * dim * 4;
+  if (init) {
+    SLG_HIP(hipMemcpy(ls->centroids.p, init, c_bytes, hipMemcpyHostToDevice));
+  } else {
+    slg::IvfStartParams sp{d_values, ls->centroids.as<float>(), n_rows, n_lists, dim};
+    const uint64_t n = (uint64_t)n_lists * dim;
+    hipLaunchKernelGGL(slg::vs_ivf_start_kernel, dim3((uint32_t)((n + 255) / 256)), dim3(256), 0, st, sp);
+    SLG_HIP(hipGetLastError());
+  }
+  // the scratch of the loop: all of it is released when the call returns
+  DevBuf rl[2], d_moved, next, d_items, d_item_begin, partial;
+  rl[0].alloc(std::max<size_t>(n_rows, 1) * 4, &ix->pool);
+  rl[1].alloc(std::max<size_t>(n_rows, 1) * 4, &ix->pool);
+  d_moved.alloc(4, &ix->pool);
+  next.alloc(c_bytes, &ix->pool);
+  d_item_begin.alloc(((size_t)n_lists + 1) * 4, &ix->pool);
+  IvfAssign assign(ix, *ls, d_values, n_rows, metric);
+  std::vector<uint32_t> lb, item_begin((size_t)n_lists + 1);
+  std::vector<slg::IvfSumItem> items;
+  uint32_t cur = 0, iters_run = 0, moved_last = 0;
+  bool stopped = false;
+  for (uint32_t t = 1; t <= iters; t++) {
+    assign.run(rl[cur].as<uint32_t>(), st);
+    uint32_t moved = n_rows;
+    if (t > 1) {
+      SLG_HIP(hipMemsetAsync(d_moved.p, 0, 4, st));
+      slg::IvfMovedParams mp{rl[cur].as<uint32_t>(), rl[cur ^ 1].as<uint32_t>(), n_rows, d_moved.as<uint32_t>()};
+      if (n_rows) hipLaunchKernelGGL(slg::vs_ivf_moved_kernel, dim3((n_rows + 255) / 256), dim3(256), 0, st, mp);
+      SLG_HIP(hipGetLastError());
+      SLG_HIP(hipMemcpyAsync(&moved, d_moved.p, 4, hipMemcpyDeviceToHost, st));
+      SLG_HIP(hipStreamSynchronize(st));
+    }
+    moved_last = moved;
+    if (t > 1 && moved == 0) {  // a fixed point: the lists of the previous step are those of these centroids
+      stopped = true;
+      break;
+    }
+    vs_build_lists(ix, d_offsets, n_docs, rl[cur].as<uint32_t>(), ls.get(), &lb);
+    // the work table: one item per (list, chunk of its docs)
+    items.clear();
+    for (uint32_t l = 0; l < n_lists; l++) {
+      item_begin[l] = (uint32_t)items.size();
+      for (uint32_t d = lb[l]; d < lb[l + 1]; d += slg::kIvfTrainChunk)
+        items.push_back(slg::IvfSumItem{d, std::min(d + slg::kIvfTrainChunk, lb[l + 1])});
+    }
+    const uint32_t n_items = (uint32_t)items.size();
+    item_begin[n_lists] = n_items;
+    SLG_HIP(hipMemcpy(d_item_begin.p, item_begin.data(), item_begin.size() * 4, hipMemcpyHostToDevice));
+    if (n_items) {
+      if (d_items.bytes < (size_t)n_items * sizeof(slg::IvfSumItem))
+        d_items.alloc((size_t)n_items * sizeof(slg::IvfSumItem) * 5 / 4, &ix->pool);
+      if (partial.bytes < (size_t)n_items * dim * 8) partial.alloc((size_t)n_items * dim * 8 * 5 / 4, &ix->pool);
+      SLG_HIP(hipMemcpy(d_items.p, items.data(), (size_t)n_items * sizeof(slg::IvfSumItem), hipMemcpyHostToDevice));
+      slg::IvfSumParams sp{d_items.as<slg::IvfSumItem>(), ls->docs.as<uint32_t>(), d_offsets, d_values,
+                           partial.as<double>(), n_items, n_docs, n_rows, dim};
+      hipLaunchKernelGGL(slg::vs_ivf_sum_kernel, dim3(std::min<uint32_t>(n_items, 1u << 20)),
+                         dim3(slg::kIvfTrainThreads), 0, st, sp);
+    }
+    slg::IvfCentroidParams cp{partial.as<double>(), d_item_begin.as<uint32_t>(), ls->list_begin.as<uint32_t>(),
+                              ls->centroids.as<float>(), next.as<float>(), n_lists, dim, metric};
+    hipLaunchKernelGGL(slg::vs_ivf_centroid_kernel, dim3(n_lists), dim3(slg::kIvfTrainThreads), 0, st, cp);
+    SLG_HIP(hipGetLastError());
+    SLG_HIP(hipMemcpyAsync(ls->centroids.p, next.p, c_bytes, hipMemcpyDeviceToDevice, st));
+    iters_run++;
+    cur ^= 1;
+  }
+  if (!stopped) {  // the lists of the final centroids
+    assign.run(rl[cur].as<uint32_t>(), st);
+    vs_build_lists(ix, d_offsets, n_docs, rl[cur].as<uint32_t>(), ls.get(), &lb);
+  }
+  SLG_HIP(hipStreamSynchronize(st));
+  if (stats) {
+    stats->iters_run = iters_run;
+    stats->moved = iters ? moved_last : 0u;
+    stats->empty_lists = 0;
+    for (uint32_t l = 0; l < n_lists; l++) stats->empty_lists += lb[l + 1] == lb[l] ? 1u : 0u;
+    stats->max_len = ls->max_len;
+  }
   return ls;
 }
 

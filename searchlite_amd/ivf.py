@@ -1,5 +1,8 @@
 """Centroids for GpuIndex.cluster_vector_field: a plain seeded Lloyd k-means in numpy on the host.  The index takes
-whatever centroids the caller supplies; this is the helper for callers that have none."""
+whatever centroids the caller supplies; this is the helper for callers that have none and hold the vectors on the
+host.  GpuIndex.train_vector_field (slg_index_train_vector_field) trains on the device instead, over the store the
+index already holds, and needs neither numpy nor the vectors; its centroids can start from this helper's through
+`init`."""
 from __future__ import annotations
 
 from typing import Optional

@@ -1185,6 +1185,43 @@ class GpuIndex:
                 descs[s].n_lists, descs[s].centroids = c.shape[0], c.ctypes.data
         N.check(self._lib.slg_index_cluster_vector_field(self._h, int(field), C.addressof(descs), len(per_segment)))
 
+    def train_vector_field(self, field: int, per_segment, dim=None):
+        """Train the centroids of vector field `field` on the device and build its lists around them
+        (slg_index_train_vector_field): Lloyd steps over each segment's own f32 store.  per_segment[s] = None (the
+        segment is or becomes unclustered), N.KEEP_VECTOR_LISTS (its lists stay as they are), (n_lists, iters) (the
+        start is rows of the store) or (n_lists, iters, init f32 [n_lists, dim]).  The library reads n_lists * dim
+        floats of an init, so its width must be the field's dimension: it is checked against `dim` when that is
+        given, and for field 0 against the segment's own vec_dim.
+        -> per segment dict(iters_run, moved, empty_lists, max_len); zeros for a segment that was not trained."""
+        import numbers
+        n = len(per_segment)
+        descs = (N.VectorTrainDesc * max(n, 1))()
+        stats = (N.VectorTrainStats * max(n, 1))()
+        keep = []
+        for s, c in enumerate(per_segment):
+            if c is None:
+                descs[s].n_lists, descs[s].iters, descs[s].init = 0, 0, None
+            elif isinstance(c, numbers.Integral):
+                descs[s].n_lists, descs[s].iters, descs[s].init = int(c), 0, None
+            else:
+                descs[s].n_lists, descs[s].iters, descs[s].init = int(c[0]), int(c[1]), None
+                if len(c) > 2 and c[2] is not None:
+                    init = np.ascontiguousarray(c[2], dtype=np.float32)
+                    if init.ndim != 2 or init.shape[0] != int(c[0]):
+                        raise ValueError("init must be f32 [n_lists, dim]")
+                    want = dim
+                    if want is None and int(field) == 0 and s < len(self.segments):
+                        want = getattr(self.segments[s], "vec_dim", 0) or None
+                    if want is not None and init.shape[1] != int(want):
+                        raise ValueError(f"init of segment {s} has {init.shape[1]} columns, the field's dimension "
+                                         f"is {int(want)}")
+                    keep.append(init)
+                    descs[s].init = init.ctypes.data
+        N.check(self._lib.slg_index_train_vector_field(self._h, int(field), C.addressof(descs), n,
+                                                       C.addressof(stats)))
+        return [dict(iters_run=int(st.iters_run), moved=int(st.moved), empty_lists=int(st.empty_lists),
+                     max_len=int(st.max_len)) for st in stats[:n]]
+
     def fetch_vector_lists(self, field: int, seg: int, dim: int):
         """The lists of segment `seg` in `field` (slg_index_fetch_vector_lists): (list_begin u32 [n_lists + 1],
         docs u32 [list_begin[-1]], centroids f32 [n_lists, dim]), or None when the segment is unclustered or has

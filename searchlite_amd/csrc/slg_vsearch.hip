@@ -73,6 +73,71 @@ uint32_t vs_resident_groups(slg_index *ix, size_t lds, uint32_t by_vgprs = 3u) {
   return std::max<uint32_t>((uint32_t)n_cu, 1u) * std::max<uint32_t>(per_cu, 1u);
 }
 
+// the doc chunks of a top-k scan whose workgroups (qtiles x chunks) fill one round of `target` resident ones: at
+// most max_chunks (1 .. n_tiles), each of tpb of the n_tiles tiles
+struct VsChunks {
+  uint32_t n_chunks, tpb;
+};
+VsChunks vs_round_chunks(uint32_t target, uint32_t qtiles, uint32_t n_tiles, uint32_t max_chunks) {
+  const uint32_t want = std::max<uint32_t>((target + qtiles - 1) / qtiles, 1u);
+  const uint32_t n = std::min<uint32_t>(want, max_chunks);
+  const uint32_t tpb = (n_tiles + n - 1) / n;
+  return VsChunks{(n_tiles + tpb - 1) / tpb, tpb};
+}
+
+// are 16-byte loads of clause c's query vectors aligned?
+uint32_t vs_qvec4(const VsCall &vc, const VsArgs &a, uint32_t c) {
+  return (vc.q_floats % 4 == 0 && vc.coff[c] % 4 == 0 && ((uintptr_t)a.qvecs & 15) == 0) ? 1u : 0u;
+}
+
+// what every scan of clause c of a call shares: the index's stores, tombstones and filters (a scan over
+// pseudo-segments, or a call without a state, sets its own tables) and the clause's queries, boost and filter ids.
+// The caller adds the tiles, the output and k / cap
+slg::VsScanParams vs_scan_base(const VsCall &vc, const VsArgs &a, uint32_t c) {
+  slg::VsScanParams sp{};
+  if (vc.S) {
+    const IndexState &S = *vc.S;
+    sp.segs = S.d_segs.as<slg::SegDev>();
+    sp.reject_table = S.d_reject_table.as<const uint32_t *>();
+    sp.doc_base = S.d_doc_base.as<uint32_t>();
+    sp.n_segs = (uint32_t)S.segs.size();
+    sp.n_filters = (uint32_t)S.filters.size();
+  }
+  sp.vsegs = vc.vsegs[c];
+  sp.dim = vc.dim[c];
+  sp.nq = vc.nq;
+  sp.qvecs = a.qvecs;
+  sp.q_stride = vc.q_floats;
+  sp.q_off = vc.coff[c];
+  sp.qvec4 = vs_qvec4(vc, a, c);
+  sp.boost = a.boost;
+  sp.n_clauses = vc.n_clauses;
+  sp.clause = c;
+  sp.q_filter = a.q_filter;
+  return sp;
+}
+
+// the one place that names the scan kernels' instantiations.  The parameter type picks the kernel: VsScanParams the
+// f32 scan, VsScanBf16Params the bf16 first pass, VsIvfScanParams the scan of the IVF work table (top-k form only)
+template <int METRIC, bool TOPK, typename P>
+void vs_launch_scan_as(const P &p, dim3 grid, size_t lds, hipStream_t st) {
+  if constexpr (std::is_same<P, slg::VsScanParams>::value)
+    launch_kernel_lds(slg::vs_scan_kernel<METRIC, TOPK>, p, grid, 256, lds, st);
+  else if constexpr (std::is_same<P, slg::VsScanBf16Params>::value)
+    launch_kernel_lds(slg::vs_scan_bf16_kernel<METRIC, TOPK>, p, grid, 256, lds, st);
+  else if constexpr (TOPK)
+    launch_kernel_lds(slg::vs_ivf_scan_kernel<METRIC, true>, p, grid, 256, lds, st);
+  else
+    throw SlgError(SLG_ERR_UNSUPPORTED, "the store form of the IVF scan is not built");
+}
+template <typename P>
+void vs_launch_scan(int32_t metric, bool topk, const P &p, dim3 grid, size_t lds, hipStream_t st) {
+  if (metric == 0)
+    topk ? vs_launch_scan_as<0, true>(p, grid, lds, st) : vs_launch_scan_as<0, false>(p, grid, lds, st);
+  else
+    topk ? vs_launch_scan_as<1, true>(p, grid, lds, st) : vs_launch_scan_as<1, false>(p, grid, lds, st);
+}
+
 // a segment's list object with its tables allocated: the centroid table (not yet filled), the list ids 0, 1, ..
 std::shared_ptr<VecListSeg> vs_new_lists(slg_index *ix, uint32_t n_lists, uint32_t dim) {
   auto ls = std::make_shared<VecListSeg>();
@@ -113,23 +178,24 @@ struct IvfAssign {
     SLG_HIP(hipMemcpy(d_cbase.p, cbase, sizeof(cbase), hipMemcpyHostToDevice));
     const uint32_t n_tiles = (n_lists + slg::kVsTileDocs - 1) / slg::kVsTileDocs;
     lds = slg::vs_scan_lds_bytes(true, slg::kVsBufCapNarrow);
-    const uint32_t target = vs_resident_groups(ix, lds);
     if (!n_rows) return;
     const uint32_t b_rows = std::min(batch, n_rows), qtiles = (b_rows + slg::kVsTileQ - 1) / slg::kVsTileQ;
-    n_chunks = std::min<uint32_t>(std::max<uint32_t>((target + qtiles - 1) / qtiles, 1u), n_tiles);
-    const uint32_t tpb = (n_tiles + n_chunks - 1) / n_chunks;
-    n_chunks = (n_tiles + tpb - 1) / tpb;
+    const VsChunks ch = vs_round_chunks(vs_resident_groups(ix, lds), qtiles, n_tiles, n_tiles);
+    n_chunks = ch.n_chunks;
     partials.alloc((size_t)b_rows * n_chunks * slg::kVsSmallK * 8, &ix->pool);
-    sp.vsegs = d_cseg.as<slg::VecSegDev>();
+    // the rows are the query vectors of a one-clause call without an index state: the tables are the pseudo-segment's
+    VsCall vc;
+    vc.n_clauses = 1;
+    vc.dim[0] = vc.q_floats = dim;
+    vc.vsegs[0] = d_cseg.as<slg::VecSegDev>();
+    VsArgs a{};
+    a.qvecs = d_values;
+    sp = vs_scan_base(vc, a, 0);
     sp.segs = d_pseg.as<slg::SegDev>();
     sp.doc_base = d_cbase.as<uint32_t>();
     sp.n_segs = 1;
-    sp.dim = dim;
-    sp.q_stride = dim;
-    sp.qvec4 = dim % 4 == 0 ? 1u : 0u;  // (device allocations are aligned)
-    sp.n_clauses = 1;
     sp.tile_end = n_tiles;
-    sp.tiles_per_block = tpb;
+    sp.tiles_per_block = ch.tpb;
     sp.n_chunks = n_chunks;
     sp.out = partials.as<uint64_t>();
     sp.k = 1;
@@ -141,11 +207,7 @@ struct IvfAssign {
       const uint32_t nr = std::min(batch, n_rows - r0);
       sp.nq = nr;
       sp.qvecs = d_values + (size_t)r0 * sp.dim;
-      const dim3 grid((nr + slg::kVsTileQ - 1) / slg::kVsTileQ, n_chunks);
-      if (metric == 0)
-        launch_kernel_lds(slg::vs_scan_kernel<0, true>, sp, grid, 256, lds, st);
-      else
-        launch_kernel_lds(slg::vs_scan_kernel<1, true>, sp, grid, 256, lds, st);
+      vs_launch_scan(metric, true, sp, dim3((nr + slg::kVsTileQ - 1) / slg::kVsTileQ, n_chunks), lds, st);
       slg::IvfBestParams bp{partials.as<uint64_t>(), nr, n_chunks, row_list + r0};
       hipLaunchKernelGGL(slg::vs_ivf_best_kernel, dim3((nr + 255) / 256), dim3(256), 0, st, bp);
       SLG_HIP(hipGetLastError());
@@ -305,6 +367,27 @@ std::shared_ptr<VecListSeg> slghost::vs_train_store(slg_index *ix, const uint32_
 
 namespace {
 
+// one block of scratch as a list of arrays.  A layout takes its arrays from a Carver in order: over no block it only
+// counts, over the block it binds the pointers, so a block's size and its pointers come from one list.  Every array
+// starts 8-byte aligned; bytes() adds a slack of 256
+struct Carver {
+  unsigned char *base;  // null: count only
+  size_t off = 0;
+  explicit Carver(void *block) : base(static_cast<unsigned char *>(block)) {}
+  template <typename T>
+  T *take(size_t n) {
+    T *p = base ? reinterpret_cast<T *>(base + off) : nullptr;
+    off += (n * sizeof(T) + 7) / 8 * 8;
+    return p;
+  }
+  size_t bytes() const { return off + 256; }
+};
+// the index's vs_scratch, grown by a quarter beyond what a call needs
+void *vs_scratch(slg_index *ix, size_t bytes) {
+  if (ix->vs_scratch.bytes < bytes) ix->vs_scratch.alloc(bytes + bytes / 4, &ix->pool);
+  return ix->vs_scratch.p;
+}
+
 // how the scans of one call cut the flat doc space for lists of K keys: K <= kVsSmallK = the fused top-k epilogue
 // over n_chunks doc chunks of one round of resident workgroups, else chunks of chunk_docs docs + select
 struct VsPlan {
@@ -324,16 +407,13 @@ VsPlan vs_plan(slg_index *ix, const VsCall &vc, uint32_t K, bool bf16) {
   pl.small = K <= slg::kVsSmallK;
   pl.cap = K <= slg::kVsSmallK / 2 ? slg::kVsBufCapNarrow : slg::kVsBufCap;
   if (pl.small && pl.n_tiles) {
-    // one round of resident workgroups: as many as the LDS of a CU holds (at most 3, the VGPR bound; 2 for
-    // vs_scan_bf16_kernel, whose 197 registers leave two waves per SIMD)
-    int n_cu = 0;
-    SLG_HIP(hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, ix->device));
-    const uint32_t per_cu = std::min<uint32_t>(bf16 ? 2u : 3u, (uint32_t)((160u << 10) / pl.lds(true)));
-    const uint32_t target = std::max<uint32_t>((uint32_t)n_cu, 1u) * std::max<uint32_t>(per_cu, 1u);
-    pl.n_chunks = std::min<uint32_t>(std::max<uint32_t>((target + pl.qtiles - 1) / pl.qtiles, 1u),
-                                     std::min<uint32_t>(n_tiles, (slg::kVsSortCap - slg::kVsSmallK) / slg::kVsSmallK));
-    pl.tpb = (pl.n_tiles + pl.n_chunks - 1) / pl.n_chunks;
-    pl.n_chunks = (pl.n_tiles + pl.tpb - 1) / pl.tpb;
+    // (by_vgprs 2 for vs_scan_bf16_kernel, whose 197 registers leave two waves per SIMD); the partial lists of a
+    // query sort in LDS with its running list
+    const VsChunks ch =
+        vs_round_chunks(vs_resident_groups(ix, pl.lds(true), bf16 ? 2u : 3u), pl.qtiles, n_tiles,
+                        std::min<uint32_t>(n_tiles, (slg::kVsSortCap - slg::kVsSmallK) / slg::kVsSmallK));
+    pl.n_chunks = ch.n_chunks;
+    pl.tpb = ch.tpb;
   } else if (!pl.small) {
     pl.chunk_docs = ((slg::kVsSortCap - K) / slg::kVsTileDocs) * slg::kVsTileDocs;
   }
@@ -341,8 +421,14 @@ VsPlan vs_plan(slg_index *ix, const VsCall &vc, uint32_t K, bool bf16) {
   return pl;
 }
 
-void vs_select(uint64_t *run, uint32_t *run_cnt, uint64_t *dlist, const uint64_t *in, uint32_t nq, uint32_t K,
-               uint32_t c0, uint32_t n_cl, uint32_t n_in_q, uint32_t stride, bool final_, hipStream_t st) {
+// one launch of vs_select_kernel over (nq, n_cl) lists: sel without its pass (n_in keys per query, final_)
+void vs_select_pass(slg::VsSelectParams sel, uint32_t n_in, uint32_t sort_n, bool final_, dim3 grid, hipStream_t st) {
+  sel.n_in = n_in;
+  sel.final_ = final_ ? 1u : 0u;
+  launch_kernel_lds(slg::vs_select_kernel, sel, grid, slg::kVsSortThreads, (size_t)slg::vs_pow2(sel.k + sort_n) * 8, st);
+}
+slg::VsSelectParams vs_select_params(uint64_t *run, uint32_t *run_cnt, uint64_t *dlist, const uint64_t *in, uint32_t nq,
+                                     uint32_t K, uint32_t c0, uint32_t stride) {
   slg::VsSelectParams sel{};
   sel.run = run;
   sel.run_cnt = run_cnt;
@@ -351,64 +437,60 @@ void vs_select(uint64_t *run, uint32_t *run_cnt, uint64_t *dlist, const uint64_t
   sel.k = K;
   sel.in = in;
   sel.c0 = c0;
-  sel.n_in = n_in_q;
   sel.in_stride = stride;
-  sel.final_ = final_ ? 1u : 0u;
-  const size_t lds = (size_t)slg::vs_pow2(K + n_in_q) * 8;
-  launch_kernel_lds(slg::vs_select_kernel, sel, dim3(nq, n_cl), slg::kVsSortThreads, lds, st);
+  return sel;
+}
+void vs_select(uint64_t *run, uint32_t *run_cnt, uint64_t *dlist, const uint64_t *in, uint32_t nq, uint32_t K,
+               uint32_t c0, uint32_t n_cl, uint32_t n_in_q, uint32_t stride, bool final_, hipStream_t st) {
+  vs_select_pass(vs_select_params(run, run_cnt, dlist, in, nq, K, c0, stride), n_in_q, n_in_q, final_, dim3(nq, n_cl),
+                 st);
+}
+// `total` keys per query fold into the running lists in passes of kVsSortCap - k keys, which sort in LDS with the
+// running list; the last pass is final.  sel.in_off (the hybrid call's keys): the kernel cuts every query's pass from
+// its own count, and every pass has the LDS of the first
+void vs_fold(slg::VsSelectParams sel, uint64_t total, dim3 grid, hipStream_t st) {
+  const uint32_t fold_n = slg::kVsSortCap - sel.k;
+  const uint64_t passes = std::max<uint64_t>((total + fold_n - 1) / fold_n, 1);
+  const uint64_t *in = sel.in;
+  for (uint64_t t = 0; t < passes; t++) {
+    const uint64_t o = t * fold_n;
+    const bool final_ = t + 1 == passes;
+    if (sel.in_off) {
+      sel.in_skip = (uint32_t)o;
+      vs_select_pass(sel, fold_n, (uint32_t)std::min<uint64_t>(total, fold_n), final_, grid, st);
+    } else {
+      const uint32_t n = (uint32_t)std::min<uint64_t>(fold_n, total - o);
+      sel.in = in + o;
+      vs_select_pass(sel, n, n, final_, grid, st);
+    }
+  }
 }
 
 // the clause lists of one call on st: per (clause, query) the best K keys in run (best first, run_cnt of them;
 // zeroed by the caller) and, final_, sorted by doc in dlist.  The exact scan, or (pl.bf16) the scan of the bf16 copies
 void vs_lists(const VsCall &vc, const VsArgs &a, const VsPlan &pl, uint32_t K, uint64_t *run, uint32_t *run_cnt,
               uint64_t *dlist, uint64_t *in, bool final_, hipStream_t st) {
-  const IndexState &S = *vc.S;
   const uint32_t nq = vc.nq, NC = vc.n_clauses;
-  slg::VsScanBf16Params bp{};
-  slg::VsScanParams &sp = bp.s;
-  sp.segs = S.d_segs.as<slg::SegDev>();
-  sp.reject_table = S.d_reject_table.as<const uint32_t *>();
-  sp.doc_base = S.d_doc_base.as<uint32_t>();
-  sp.n_segs = (uint32_t)S.segs.size();
-  sp.n_filters = (uint32_t)S.filters.size();
-  sp.nq = nq;
-  sp.qvecs = a.qvecs;
-  sp.q_stride = vc.q_floats;
-  sp.boost = a.boost;
-  sp.n_clauses = NC;
-  sp.q_filter = a.q_filter;
-  sp.k = K;
-  sp.cap = pl.cap;
+  slg::VsScanBf16Params bp[SLG_MAX_VECTOR_CLAUSES];
+  for (uint32_t c = 0; c < NC; c++) {
+    bp[c].s = vs_scan_base(vc, a, c);
+    bp[c].s.k = K;
+    bp[c].s.cap = pl.cap;
+    bp[c].csegs = vc.csegs[c];
+  }
   auto scan = [&](uint32_t c, bool topk, dim3 grid) {
-    sp.vsegs = vc.vsegs[c];
-    bp.csegs = vc.csegs[c];
-    sp.dim = vc.dim[c];
-    sp.q_off = vc.coff[c];
-    sp.clause = c;
-    sp.qvec4 = (vc.q_floats % 4 == 0 && vc.coff[c] % 4 == 0 && ((uintptr_t)a.qvecs & 15) == 0) ? 1u : 0u;
-    const size_t lds = pl.lds(topk);
-    const bool cosine = vc.metric[c] == 0;
-    if (pl.bf16) {
-      if (cosine)
-        topk ? launch_kernel_lds(slg::vs_scan_bf16_kernel<0, true>, bp, grid, 256, lds, st)
-             : launch_kernel_lds(slg::vs_scan_bf16_kernel<0, false>, bp, grid, 256, lds, st);
-      else
-        topk ? launch_kernel_lds(slg::vs_scan_bf16_kernel<1, true>, bp, grid, 256, lds, st)
-             : launch_kernel_lds(slg::vs_scan_bf16_kernel<1, false>, bp, grid, 256, lds, st);
-    } else if (cosine) {
-      topk ? launch_kernel_lds(slg::vs_scan_kernel<0, true>, sp, grid, 256, lds, st)
-           : launch_kernel_lds(slg::vs_scan_kernel<0, false>, sp, grid, 256, lds, st);
-    } else {
-      topk ? launch_kernel_lds(slg::vs_scan_kernel<1, true>, sp, grid, 256, lds, st)
-           : launch_kernel_lds(slg::vs_scan_kernel<1, false>, sp, grid, 256, lds, st);
-    }
+    if (pl.bf16)
+      vs_launch_scan(vc.metric[c], topk, bp[c], grid, pl.lds(topk), st);
+    else
+      vs_launch_scan(vc.metric[c], topk, bp[c].s, grid, pl.lds(topk), st);
   };
   if (pl.small) {
-    sp.tile_begin = 0;
-    sp.tile_end = pl.n_tiles;
-    sp.tiles_per_block = pl.tpb;
-    sp.n_chunks = pl.n_chunks;
     for (uint32_t c = 0; c < NC && pl.n_chunks; c++) {
+      slg::VsScanParams &sp = bp[c].s;
+      sp.tile_begin = 0;
+      sp.tile_end = pl.n_tiles;
+      sp.tiles_per_block = pl.tpb;
+      sp.n_chunks = pl.n_chunks;
       sp.out = in + (size_t)c * nq * pl.n_chunks * slg::kVsSmallK;
       scan(c, true, dim3(pl.qtiles, pl.n_chunks));
     }
@@ -416,15 +498,16 @@ void vs_lists(const VsCall &vc, const VsArgs &a, const VsPlan &pl, uint32_t K, u
               final_, st);
   } else {
     const uint32_t tiles_per_chunk = pl.chunk_docs / slg::kVsTileDocs;
-    sp.out = in;
-    sp.out_stride = pl.chunk_docs;
-    sp.tiles_per_block = 1;
     const uint32_t steps = std::max<uint32_t>((pl.n_tiles + tiles_per_chunk - 1) / tiles_per_chunk, 1u);
     for (uint32_t s = 0; s < steps; s++) {
       const uint32_t t0 = s * tiles_per_chunk, t1 = std::min<uint32_t>(t0 + tiles_per_chunk, pl.n_tiles);
-      sp.tile_begin = t0;
-      sp.tile_end = t1;
       for (uint32_t c = 0; c < NC; c++) {
+        slg::VsScanParams &sp = bp[c].s;
+        sp.out = in;
+        sp.out_stride = pl.chunk_docs;
+        sp.tiles_per_block = 1;
+        sp.tile_begin = t0;
+        sp.tile_end = t1;
         if (t1 > t0) scan(c, false, dim3(pl.qtiles, t1 - t0));
         vs_select(run, run_cnt, dlist, in, nq, K, c, 1, (t1 > t0 ? t1 - t0 : 0) * slg::kVsTileDocs, pl.chunk_docs,
                   final_ && s + 1 == steps, st);
@@ -433,9 +516,10 @@ void vs_lists(const VsCall &vc, const VsArgs &a, const VsPlan &pl, uint32_t K, u
   }
 }
 
-// union of the clause lists (K keys each, sorted by doc), blend, top k_out
-void vs_blend(const VsCall &vc, const VsArgs &a, const uint64_t *dlist, const uint32_t *run_cnt, uint32_t K,
-              uint64_t *ukeys, uint32_t P, hipStream_t st) {
+// the fields vs_blend_kernel reads in both of its forms: the clause lists (K keys each, sorted by doc), the sort
+// space of the union (P keys a query; ukeys when they do not fit LDS) and the outputs
+slg::VsBlendParams vs_blend_params(const VsCall &vc, const VsArgs &a, const uint64_t *dlist, const uint32_t *run_cnt,
+                                   uint32_t K, uint64_t *ukeys, uint32_t P) {
   const IndexState &S = *vc.S;
   slg::VsBlendParams bp{};
   bp.dlist = dlist;
@@ -456,25 +540,29 @@ void vs_blend(const VsCall &vc, const VsArgs &a, const uint64_t *dlist, const ui
   bp.out_vec = a.out_vec;
   bp.out_count = a.out_count;
   bp.out_total = a.out_total;
-  launch_kernel_lds(slg::vs_blend_kernel<false>, bp, dim3(vc.nq), slg::kVsSortThreads,
-                   P > slg::kVsSortCap ? 0 : (size_t)P * 8, st);
+  return bp;
+}
+// union of the clause lists, blend, top k_out
+void vs_blend(const VsCall &vc, const VsArgs &a, const uint64_t *dlist, const uint32_t *run_cnt, uint32_t K,
+              uint64_t *ukeys, uint32_t P, hipStream_t st) {
+  launch_kernel_lds(slg::vs_blend_kernel<false>, vs_blend_params(vc, a, dlist, run_cnt, K, ukeys, P), dim3(vc.nq),
+                    slg::kVsSortThreads, P > slg::kVsSortCap ? 0 : (size_t)P * 8, st);
 }
 
 // (slg_vector_search_batch_ivf*) what one clause's steps need of vs_scratch, from what the host knows: nq, the
 // probes of a query, the field's lists, its longest list and its unclustered segments
 struct IvfPlan {
+  uint32_t nq = 0;
   uint32_t P = 0;            // probes of a query: min(nprobe, lists of the field)
   uint32_t list_chunks = 0, list_chunk_docs = 0, slots_q = 0, n_ext = 0, items_cap = 0;
   uint32_t coarse_docs = 0;  // lists of one coarse scan + select step
-  size_t n_probe_keys = 0, n_coarse = 0, n_partial = 0, n_u32 = 0;
-  // probes | coarse keys | partial lists | items | pairs (8 bytes each) | the counters and offsets
-  size_t bytes() const {
-    return (n_probe_keys + n_coarse + n_partial + n_probe_keys) * 8 + (size_t)items_cap * sizeof(slg::IvfItem) + n_u32 * 4;
-  }
+  size_t n_probe_keys = 0, n_coarse = 0, n_partial = 0;
+  size_t bytes() const;      // of its work area (IvfWork)
 };
 IvfPlan ivf_plan(const VsCall &vc, uint32_t c, uint32_t nprobe) {
   const VecListField &vl = *vc.lists[c];
   IvfPlan pl;
+  pl.nq = vc.nq;
   pl.P = std::min(nprobe, vl.total_lists);
   pl.list_chunks = std::max<uint32_t>(std::min<uint32_t>(slg::kIvfListChunks, (vl.max_len + 1023u) / 1024u), 1u);
   pl.list_chunk_docs = std::max<uint32_t>(((vl.max_len + pl.list_chunks - 1) / pl.list_chunks + slg::kVsTileDocs - 1) /
@@ -493,9 +581,32 @@ IvfPlan ivf_plan(const VsCall &vc, uint32_t c, uint32_t nprobe) {
   pl.n_probe_keys = pairs;
   pl.n_coarse = (size_t)vc.nq * pl.coarse_docs;
   pl.n_partial = (size_t)vc.nq * pl.slots_q * slg::kVsSmallK;
-  pl.n_u32 = 4 * (size_t)pl.n_ext + 3 + vc.nq + 1;  // cnt, cursor, goff, ioff, n_items, the coarse select's counts
   return pl;
 }
+// the work area of one clause's steps
+struct IvfWork {
+  uint64_t *probes, *coarse, *partials;
+  slg::IvfItem *items;
+  uint2 *pairs;
+  uint32_t *cnt;  // [n_ext] the lists' query counts, then [n_ext] the fill cursors: zeroed together
+  uint32_t *goff, *ioff, *n_items;
+  uint32_t *probe_cnt;  // [nq] the coarse select's counts
+  size_t lay(const IvfPlan &pl, void *block) {
+    Carver c(block);
+    probes = c.take<uint64_t>(pl.n_probe_keys);
+    coarse = c.take<uint64_t>(pl.n_coarse);
+    partials = c.take<uint64_t>(pl.n_partial);
+    items = c.take<slg::IvfItem>(pl.items_cap);
+    pairs = c.take<uint2>(pl.n_probe_keys);
+    cnt = c.take<uint32_t>(2 * (size_t)pl.n_ext);
+    goff = c.take<uint32_t>((size_t)pl.n_ext + 1);
+    ioff = c.take<uint32_t>((size_t)pl.n_ext + 1);
+    n_items = c.take<uint32_t>(1);
+    probe_cnt = c.take<uint32_t>(pl.nq);
+    return c.off;
+  }
+};
+size_t IvfPlan::bytes() const { return IvfWork().lay(*this, nullptr); }
 
 // the clause lists of one IVF call on st (run / run_cnt zeroed by the caller; work: the clause-by-clause work area)
 void vs_lists_ivf(slg_index *ix, const VsCall &vc, const VsArgs &a, uint32_t nprobe, uint64_t *run, uint32_t *run_cnt,
@@ -508,73 +619,41 @@ void vs_lists_ivf(slg_index *ix, const VsCall &vc, const VsArgs &a, uint32_t npr
   for (uint32_t c = 0; c < NC; c++) {
     const VecListField &vl = *vc.lists[c];
     const IvfPlan pl = ivf_plan(vc, c, nprobe);
-    uint64_t *probes = static_cast<uint64_t *>(work), *coarse = probes + pl.n_probe_keys;
-    uint64_t *partials = coarse + pl.n_coarse;
-    slg::IvfItem *items = reinterpret_cast<slg::IvfItem *>(partials + pl.n_partial);
-    uint2 *pairs = reinterpret_cast<uint2 *>(items + pl.items_cap);
-    uint32_t *cnt = reinterpret_cast<uint32_t *>(pairs + pl.n_probe_keys), *cursor = cnt + pl.n_ext;
-    uint32_t *goff = cursor + pl.n_ext, *ioff = goff + pl.n_ext + 1, *n_items = ioff + pl.n_ext + 1;
-    uint32_t *probe_cnt = n_items + 1;  // [nq] the coarse select's counts
-    const uint32_t qvec4 = (vc.q_floats % 4 == 0 && vc.coff[c] % 4 == 0 && ((uintptr_t)a.qvecs & 15) == 0) ? 1u : 0u;
+    IvfWork w;
+    w.lay(pl, work);
     // every counter of the steps, and the partial slots no item writes
-    SLG_HIP(hipMemsetAsync(cnt, 0, (2 * (size_t)pl.n_ext) * 4, st));
-    SLG_HIP(hipMemsetAsync(n_items, 0, 4, st));
-    SLG_HIP(hipMemsetAsync(partials, 0, pl.n_partial * 8, st));
-    SLG_HIP(hipMemsetAsync(probes, 0, pl.n_probe_keys * 8, st));
-    // ---- coarse step: the exact scan's store form over the centroid tables, the best P lists of each query ----
-    slg::VsScanParams sp{};
+    SLG_HIP(hipMemsetAsync(w.cnt, 0, (2 * (size_t)pl.n_ext) * 4, st));
+    SLG_HIP(hipMemsetAsync(w.n_items, 0, 4, st));
+    SLG_HIP(hipMemsetAsync(w.partials, 0, pl.n_partial * 8, st));
+    SLG_HIP(hipMemsetAsync(w.probes, 0, pl.n_probe_keys * 8, st));
+    // ---- coarse step: the exact scan's store form over the centroid tables (pseudo-segments without tombstones
+    //      or filters), the best P lists of each query ----
+    slg::VsScanParams sp = vs_scan_base(vc, a, c);
     sp.vsegs = vl.d_csegs.as<slg::VecSegDev>();
     sp.segs = vl.d_psegs.as<slg::SegDev>();
     sp.doc_base = vl.d_list_base.as<uint32_t>();
-    sp.n_segs = (uint32_t)S.segs.size();
-    sp.dim = vc.dim[c];
-    sp.nq = nq;
-    sp.qvecs = a.qvecs;
-    sp.q_stride = vc.q_floats;
-    sp.q_off = vc.coff[c];
-    sp.qvec4 = qvec4;
-    sp.boost = a.boost;
-    sp.n_clauses = NC;
-    sp.clause = c;
+    sp.reject_table = nullptr;
+    sp.n_filters = 0;
+    sp.q_filter = nullptr;
     sp.tiles_per_block = 1;
-    sp.out = coarse;
+    sp.out = w.coarse;
     sp.out_stride = pl.coarse_docs;
     const uint32_t n_tiles = (vl.total_lists + slg::kVsTileDocs - 1) / slg::kVsTileDocs;
     const uint32_t step_tiles = pl.coarse_docs / slg::kVsTileDocs;
-    SLG_HIP(hipMemsetAsync(probe_cnt, 0, (size_t)nq * 4, st));
+    SLG_HIP(hipMemsetAsync(w.probe_cnt, 0, (size_t)nq * 4, st));
     for (uint32_t t0 = 0; t0 < n_tiles; t0 += step_tiles) {
       const uint32_t t1 = std::min(t0 + step_tiles, n_tiles);
       sp.tile_begin = t0;
       sp.tile_end = t1;
-      const size_t lds = slg::vs_scan_lds_bytes(false, 0);
-      if (vc.metric[c] == 0)
-        launch_kernel_lds(slg::vs_scan_kernel<0, false>, sp, dim3(qtiles, t1 - t0), 256, lds, st);
-      else
-        launch_kernel_lds(slg::vs_scan_kernel<1, false>, sp, dim3(qtiles, t1 - t0), 256, lds, st);
-      vs_select(probes, probe_cnt, nullptr, coarse, nq, pl.P, 0, 1, (t1 - t0) * slg::kVsTileDocs, pl.coarse_docs, false,
-                st);
+      vs_launch_scan(vc.metric[c], false, sp, dim3(qtiles, t1 - t0), slg::vs_scan_lds_bytes(false, 0), st);
+      vs_select(w.probes, w.probe_cnt, nullptr, w.coarse, nq, pl.P, 0, 1, (t1 - t0) * slg::kVsTileDocs, pl.coarse_docs,
+                false, st);
     }
     // ---- inversion: the probes as per-list query groups, and the work table ----
-    slg::IvfPlanParams ip{};
-    ip.probes = probes;
-    ip.lsegs = vl.d_lsegs.as<slg::VecListDev>();
-    ip.list_base = vl.d_list_base.as<uint32_t>();
-    ip.uncl = vl.d_uncl.as<slg::IvfUncl>();
-    ip.n_segs = (uint32_t)S.segs.size();
-    ip.n_lists = vl.total_lists;
-    ip.n_uncl = vl.n_uncl;
-    ip.nq = nq;
-    ip.n_probe = pl.P;
-    ip.list_chunk_docs = pl.list_chunk_docs;
-    ip.list_chunks = pl.list_chunks;
-    ip.cnt = cnt;
-    ip.cursor = cursor;
-    ip.goff = goff;
-    ip.ioff = ioff;
-    ip.n_items = n_items;
-    ip.pairs = pairs;
-    ip.items = items;
-    ip.items_cap = pl.items_cap;
+    const slg::IvfPlanParams ip{w.probes, vl.d_lsegs.as<slg::VecListDev>(), vl.d_list_base.as<uint32_t>(),
+                                vl.d_uncl.as<slg::IvfUncl>(), (uint32_t)S.segs.size(), vl.total_lists, vl.n_uncl, nq,
+                                pl.P, pl.list_chunk_docs, pl.list_chunks, w.cnt, w.cnt + pl.n_ext, w.goff, w.ioff,
+                                w.n_items, w.pairs, w.items, pl.items_cap};
     const uint32_t n_pairs = nq * pl.P;
     hipLaunchKernelGGL(slg::vs_ivf_probe_count_kernel, dim3((n_pairs + 255) / 256), dim3(256), 0, st, ip);
     hipLaunchKernelGGL(slg::vs_ivf_plan_kernel, dim3(1), dim3(slg::kIvfScanThreads), 0, st, ip);
@@ -582,76 +661,72 @@ void vs_lists_ivf(slg_index *ix, const VsCall &vc, const VsArgs &a, uint32_t npr
     SLG_HIP(hipGetLastError());
     // ---- the scan of the work table by one round of resident workgroups ----
     slg::VsIvfScanParams xp{};
-    slg::VsScanParams &xs = xp.s;
-    xs.vsegs = vc.vsegs[c];
-    xs.segs = S.d_segs.as<slg::SegDev>();
-    xs.reject_table = S.d_reject_table.as<const uint32_t *>();
-    xs.doc_base = S.d_doc_base.as<uint32_t>();
-    xs.n_segs = (uint32_t)S.segs.size();
-    xs.n_filters = (uint32_t)S.filters.size();
-    xs.dim = vc.dim[c];
-    xs.nq = nq;
-    xs.qvecs = a.qvecs;
-    xs.q_stride = vc.q_floats;
-    xs.q_off = vc.coff[c];
-    xs.qvec4 = qvec4;
-    xs.boost = a.boost;
-    xs.n_clauses = NC;
-    xs.clause = c;
-    xs.q_filter = a.q_filter;
-    xs.out = partials;
-    xs.k = K;
-    xs.cap = cap;
+    xp.s = vs_scan_base(vc, a, c);
+    xp.s.out = w.partials;
+    xp.s.k = K;
+    xp.s.cap = cap;
     xp.lsegs = ip.lsegs;
-    xp.items = items;
-    xp.n_items = n_items;
-    xp.pairs = pairs;
+    xp.items = w.items;
+    xp.n_items = w.n_items;
+    xp.pairs = w.pairs;
     xp.slots_q = pl.slots_q;
     // (profiles/vsearch_ivf_resource_usage.txt: the cosine form's registers leave two waves per SIMD, the L2 form's one)
     const uint32_t groups = vs_resident_groups(ix, scan_lds, vc.metric[c] == 0 ? 2u : 1u);
-    const dim3 grid(std::min<uint32_t>(groups, std::max<uint32_t>(pl.items_cap, 1u)));
-    if (vc.metric[c] == 0)
-      launch_kernel_lds(slg::vs_ivf_scan_kernel<0, true>, xp, grid, 256, scan_lds, st);
-    else
-      launch_kernel_lds(slg::vs_ivf_scan_kernel<1, true>, xp, grid, 256, scan_lds, st);
-    // ---- a query's partials fold into its clause list in passes that sort in LDS with the running list ----
-    const uint32_t n_in = pl.slots_q * slg::kVsSmallK, fold_n = slg::kVsSortCap - K;
+    vs_launch_scan(vc.metric[c], true, xp, dim3(std::min<uint32_t>(groups, std::max<uint32_t>(pl.items_cap, 1u))),
+                   scan_lds, st);
+    // ---- a query's partials fold into its clause list ----
+    const uint32_t n_in = pl.slots_q * slg::kVsSmallK;
     const size_t qc0 = (size_t)c * nq;
-    for (uint32_t o = 0; o < n_in; o += fold_n)
-      vs_select(run + qc0 * K, run_cnt + qc0, dlist + qc0 * K, partials + o, nq, K, 0, 1, std::min(fold_n, n_in - o),
-                n_in, o + fold_n >= n_in, st);
+    vs_fold(vs_select_params(run + qc0 * K, run_cnt + qc0, dlist + qc0 * K, w.partials, nq, K, 0, n_in), n_in,
+            dim3(nq, 1), st);
   }
 }
 
-// the kernels of one call on st, device arrays in a (the caller holds ix->mu and the device).  refine 0: the exact
-// search; else the two-pass one: lists of `refine` keys from the bf16 copies, their exact scores, the best cand_size.
-// nprobe != 0 (refine 0): the search over the fields' inverted-file lists
-void vs_run(slg_index *ix, const VsCall &vc, const VsArgs &a, uint32_t refine, uint32_t nprobe, hipStream_t st) {
-  if (nprobe) {
-    const uint32_t nq = vc.nq, NC = vc.n_clauses, K = vc.cand;
-    const size_t n_run = (size_t)NC * nq * K, n_cnt = (size_t)NC * nq;
-    const uint32_t P = slg::vs_pow2(NC * K);  // (K <= kVsSmallK: the union sorts in LDS)
-    size_t work = 0;
-    for (uint32_t c = 0; c < NC; c++) work = std::max(work, ivf_plan(vc, c, nprobe).bytes());
-    const size_t bytes = 2 * n_run * 8 + work + n_cnt * 4 + 256;
-    if (ix->vs_scratch.bytes < bytes) ix->vs_scratch.alloc(bytes + bytes / 4, &ix->pool);
-    uint64_t *run = ix->vs_scratch.as<uint64_t>(), *dlist = run + n_run, *wk = dlist + n_run;
-    uint32_t *run_cnt = reinterpret_cast<uint32_t *>(reinterpret_cast<unsigned char *>(wk) + (work + 7) / 8 * 8);
-    SLG_HIP(hipMemsetAsync(run_cnt, 0, n_cnt * 4, st));
-    vs_lists_ivf(ix, vc, a, nprobe, run, run_cnt, dlist, wk, st);
-    vs_blend(vc, a, dlist, run_cnt, K, nullptr, P, st);
-    return;
-  }
+// the kernels of one IVF call on st: per clause the coarse step, the scan of the probed lists and the fold; blend
+void vs_run_ivf(slg_index *ix, const VsCall &vc, const VsArgs &a, uint32_t nprobe, hipStream_t st) {
+  const uint32_t nq = vc.nq, NC = vc.n_clauses, K = vc.cand;
+  const size_t n_run = (size_t)NC * nq * K, n_cnt = (size_t)NC * nq;
+  const uint32_t P = slg::vs_pow2(NC * K);  // (K <= kVsSmallK: the union sorts in LDS)
+  size_t work = 0;
+  for (uint32_t c = 0; c < NC; c++) work = std::max(work, ivf_plan(vc, c, nprobe).bytes());
+  uint64_t *run = nullptr, *dlist = nullptr;
+  unsigned char *wk = nullptr;
+  uint32_t *run_cnt = nullptr;
+  auto lay = [&](void *block) {
+    Carver c(block);
+    run = c.take<uint64_t>(n_run);
+    dlist = c.take<uint64_t>(n_run);
+    wk = c.take<unsigned char>(work);
+    run_cnt = c.take<uint32_t>(n_cnt);
+    return c.bytes();
+  };
+  lay(vs_scratch(ix, lay(nullptr)));
+  SLG_HIP(hipMemsetAsync(run_cnt, 0, n_cnt * 4, st));
+  vs_lists_ivf(ix, vc, a, nprobe, run, run_cnt, dlist, wk, st);
+  vs_blend(vc, a, dlist, run_cnt, K, nullptr, P, st);
+}
+
+// the kernels of one scan call on st.  refine 0: the exact search; else the two-pass one: lists of `refine` keys from
+// the bf16 copies, their exact scores, the best cand_size
+void vs_run_scan(slg_index *ix, const VsCall &vc, const VsArgs &a, uint32_t refine, hipStream_t st) {
   const uint32_t nq = vc.nq, NC = vc.n_clauses, K = vc.cand, R = refine ? refine : K;
   const VsPlan pl = vs_plan(ix, vc, R, refine != 0);
   const size_t n_run = (size_t)NC * nq * K, n_first = refine ? (size_t)NC * nq * R : 0, n_cnt = (size_t)NC * nq;
   const uint32_t P = slg::vs_pow2(NC * K);
-  const size_t n_u = P > slg::kVsSortCap ? (size_t)nq * P : 0;
-  const size_t bytes = (2 * n_run + n_first + std::max<size_t>(pl.n_in, 1) + n_u) * 8 + 2 * n_cnt * 4 + 256;
-  if (ix->vs_scratch.bytes < bytes) ix->vs_scratch.alloc(bytes + bytes / 4, &ix->pool);
-  uint64_t *run = ix->vs_scratch.as<uint64_t>(), *dlist = run + n_run, *first = dlist + n_run;
-  uint64_t *in = first + n_first, *ukeys = in + std::max<size_t>(pl.n_in, 1);
-  uint32_t *run_cnt = reinterpret_cast<uint32_t *>(ukeys + n_u), *first_cnt = run_cnt + n_cnt;
+  uint64_t *run = nullptr, *dlist = nullptr, *first = nullptr, *in = nullptr, *ukeys = nullptr;
+  uint32_t *run_cnt = nullptr;  // [n_cnt], then the first pass's counts: zeroed together
+  auto lay = [&](void *block) {
+    Carver c(block);
+    run = c.take<uint64_t>(n_run);
+    dlist = c.take<uint64_t>(n_run);
+    first = c.take<uint64_t>(n_first);
+    in = c.take<uint64_t>(std::max<size_t>(pl.n_in, 1));
+    ukeys = c.take<uint64_t>(P > slg::kVsSortCap ? (size_t)nq * P : 0);
+    run_cnt = c.take<uint32_t>(2 * n_cnt);
+    return c.bytes();
+  };
+  lay(vs_scratch(ix, lay(nullptr)));
+  uint32_t *first_cnt = run_cnt + n_cnt;
   SLG_HIP(hipMemsetAsync(run_cnt, 0, 2 * n_cnt * 4, st));
   if (!refine) {
     vs_lists(vc, a, pl, K, run, run_cnt, dlist, in, true, st);
@@ -673,7 +748,7 @@ void vs_run(slg_index *ix, const VsCall &vc, const VsArgs &a, uint32_t refine, u
       rp.vsegs = vc.vsegs[c];
       rp.dim = vc.dim[c];
       rp.q_off = vc.coff[c];
-      rp.qvec4 = (vc.q_floats % 4 == 0 && vc.coff[c] % 4 == 0 && ((uintptr_t)a.qvecs & 15) == 0) ? 1u : 0u;
+      rp.qvec4 = vs_qvec4(vc, a, c);
       rp.clause = c;
       if (vc.metric[c] == 0)
         hipLaunchKernelGGL(slg::vs_refine_kernel<0>, dim3(nq), dim3(256), 0, st, rp);
@@ -681,12 +756,19 @@ void vs_run(slg_index *ix, const VsCall &vc, const VsArgs &a, uint32_t refine, u
         hipLaunchKernelGGL(slg::vs_refine_kernel<1>, dim3(nq), dim3(256), 0, st, rp);
       SLG_HIP(hipGetLastError());
     }
-    // the refined keys fold into the final lists in passes that sort in LDS with the running list
-    const uint32_t fold_n = slg::kVsSortCap - K;
-    for (uint32_t o = 0; o < R; o += fold_n)
-      vs_select(run, run_cnt, dlist, first + o, nq, K, 0, NC, std::min(fold_n, R - o), R, o + fold_n >= R, st);
+    // the refined keys fold into the final lists
+    vs_fold(vs_select_params(run, run_cnt, dlist, first, nq, K, 0, R), R, dim3(nq, NC), st);
   }
   vs_blend(vc, a, dlist, run_cnt, K, ukeys, P, st);
+}
+
+// the kernels of one call on st, device arrays in a (the caller holds ix->mu and the device).  nprobe != 0: the search
+// over the fields' inverted-file lists; else the scans of the flat space, exact (refine 0) or two-pass
+void vs_run(slg_index *ix, const VsCall &vc, const VsArgs &a, uint32_t refine, uint32_t nprobe, hipStream_t st) {
+  if (nprobe)
+    vs_run_ivf(ix, vc, a, nprobe, st);
+  else
+    vs_run_scan(ix, vc, a, refine, st);
 }
 
 // (slg_vector_search_batch_approx*) a bf16 copy of every clause's field; refine against cand_size
@@ -721,122 +803,88 @@ void vs_check_refine(uint32_t cand_size, uint32_t refine) {
     throw SlgError(SLG_ERR_UNSUPPORTED, "refine outside cand_size..SLG_MAX_VECTOR_CANDIDATES");
 }
 
-// refine 0 and nprobe 0: the exact search (both forms)
-void vs_device(slg_index *ix, uint32_t nq, uint32_t n_clauses, const uint32_t *clause_field, uint32_t cand_size,
-               uint32_t refine, uint32_t nprobe, uint32_t k_out, const VsArgs &d) {
-  VsCall vc;
-  if (!vs_prepare(ix, nq, n_clauses, clause_field, cand_size, k_out, d, false, &vc)) return;
-  if (refine) vs_prepare_approx(n_clauses, clause_field, &vc);
-  if (nprobe) vs_prepare_ivf(n_clauses, clause_field, &vc);
-  std::lock_guard<std::mutex> lk(ix->mu);
-  DeviceGuard g(ix->device);
-  vs_run(ix, vc, d, refine, nprobe, ix->stream);
-}
+// which of the three searches an entry point runs; `extra` is its own integer: none, refine, nprobe
+enum class VsKind { Exact, Approx, Ivf };
 
-// host arrays: checks, pooled device buffers, H2D, the kernels, D2H and a wait, all on the index stream
+// one entry point of the family.  device: the arrays of a are device memory and the call is asynchronous on the index
+// stream; else host arrays: checks, pooled device buffers, H2D, the kernels, D2H and a wait, all on the index stream
 // (Staging: slg_host.hpp)
-void vs_staged(slg_index *ix, uint32_t nq, uint32_t n_clauses, const uint32_t *clause_field, uint32_t cand_size,
-               uint32_t refine, uint32_t nprobe, uint32_t k_out, const VsArgs &h) {
-  VsCall vc;
-  if (!vs_prepare(ix, nq, n_clauses, clause_field, cand_size, k_out, h, true, &vc)) return;
-  if (refine) vs_prepare_approx(n_clauses, clause_field, &vc);
-  if (nprobe) vs_prepare_ivf(n_clauses, clause_field, &vc);
-  const size_t nqc = (size_t)nq * n_clauses, no = (size_t)nq * k_out;
-  DeviceGuard g(ix->device);
-  const hipStream_t st = ix->stream;
-  Staging sg(&ix->pool, st);
-  VsArgs d{};
-  d.qvecs = sg.up(h.qvecs, (size_t)nq * vc.q_floats);
-  d.alpha = sg.up(h.alpha, nqc);
-  if (h.boost) d.boost = sg.up(h.boost, nqc);
-  if (h.q_filter) d.q_filter = sg.up(h.q_filter, nq);
-  d.out_doc = sg.up<uint32_t>(nullptr, no);
-  d.out_seg = sg.up<uint32_t>(nullptr, no);
-  d.out_score = sg.up<float>(nullptr, no);
-  d.out_vec = sg.up<float>(nullptr, no);
-  d.out_count = sg.up<uint32_t>(nullptr, nq);
-  d.out_total = sg.up<uint64_t>(nullptr, nq);
-  {
-    std::lock_guard<std::mutex> lk(ix->mu);
-    vs_run(ix, vc, d, refine, nprobe, st);
-  }
-  sg.down(h.out_doc, d.out_doc, no);
-  sg.down(h.out_seg, d.out_seg, no);
-  sg.down(h.out_score, d.out_score, no);
-  sg.down(h.out_vec, d.out_vec, no);
-  sg.down(h.out_count, d.out_count, nq);
-  sg.down(h.out_total, d.out_total, nq);
-  SLG_HIP(hipStreamSynchronize(st));
+int vs_entry(VsKind kind, bool device, slg_index *ix, uint32_t nq, uint32_t n_clauses, const uint32_t *clause_field,
+             uint32_t cand_size, uint32_t extra, uint32_t k_out, const VsArgs &a) {
+  return guarded([&] {
+    if (kind == VsKind::Approx) vs_check_refine(cand_size, extra);
+    if (kind == VsKind::Ivf) vs_check_ivf(cand_size, extra);
+    const uint32_t refine = kind == VsKind::Approx ? extra : 0u, nprobe = kind == VsKind::Ivf ? extra : 0u;
+    VsCall vc;
+    if (!vs_prepare(ix, nq, n_clauses, clause_field, cand_size, k_out, a, !device, &vc)) return;
+    if (refine) vs_prepare_approx(n_clauses, clause_field, &vc);
+    if (nprobe) vs_prepare_ivf(n_clauses, clause_field, &vc);
+    const hipStream_t st = ix->stream;
+    if (device) {
+      std::lock_guard<std::mutex> lk(ix->mu);
+      DeviceGuard g(ix->device);
+      vs_run(ix, vc, a, refine, nprobe, st);
+      return;
+    }
+    DeviceGuard g(ix->device);
+    const size_t nqc = (size_t)nq * n_clauses, no = (size_t)nq * k_out;
+    Staging sg(&ix->pool, st);
+    VsArgs d{};
+    d.qvecs = sg.up(a.qvecs, (size_t)nq * vc.q_floats);
+    d.alpha = sg.up(a.alpha, nqc);
+    if (a.boost) d.boost = sg.up(a.boost, nqc);
+    if (a.q_filter) d.q_filter = sg.up(a.q_filter, nq);
+    d.out_doc = sg.up<uint32_t>(nullptr, no);
+    d.out_seg = sg.up<uint32_t>(nullptr, no);
+    d.out_score = sg.up<float>(nullptr, no);
+    d.out_vec = sg.up<float>(nullptr, no);
+    d.out_count = sg.up<uint32_t>(nullptr, nq);
+    d.out_total = sg.up<uint64_t>(nullptr, nq);
+    {
+      std::lock_guard<std::mutex> lk(ix->mu);
+      vs_run(ix, vc, d, refine, nprobe, st);
+    }
+    sg.down(a.out_doc, d.out_doc, no);
+    sg.down(a.out_seg, d.out_seg, no);
+    sg.down(a.out_score, d.out_score, no);
+    sg.down(a.out_vec, d.out_vec, no);
+    sg.down(a.out_count, d.out_count, nq);
+    sg.down(a.out_total, d.out_total, nq);
+    SLG_HIP(hipStreamSynchronize(st));
+  });
 }
 }  // namespace
 
 size_t slghost::hy_work_layout(const VsCall &vc, uint32_t bm_k, void *base, HyWork *w) {
   const size_t n_run = (size_t)vc.n_clauses * vc.nq * vc.cand, n_cnt = (size_t)vc.n_clauses * vc.nq;
   const uint32_t P = slg::vs_pow2(vc.n_clauses * vc.cand + bm_k), Pb = slg::vs_pow2(std::max<uint32_t>(bm_k, 1u));
+  HyWork lw{};
+  Carver c(w ? base : nullptr);
+  lw.run = c.take<uint64_t>(n_run);
+  lw.dlist = c.take<uint64_t>(n_run);
   // the union keys sort in LDS while they fit, and the BM25 hits behind them while both do
-  const size_t n_u = P > slg::kVsSortCap ? (size_t)vc.nq * P : 0;
-  const size_t n_b = P + Pb > slg::kVsSortCap ? (size_t)vc.nq * Pb : 0;
-  if (w) {
-    uint64_t *p = static_cast<uint64_t *>(base);
-    w->run = p;
-    w->dlist = w->run + n_run;
-    w->ukeys = w->dlist + n_run;
-    w->bkeys = w->ukeys + n_u;
-    w->cnt = reinterpret_cast<uint32_t *>(w->bkeys + n_b);
-    w->P = P;
-    w->Pb = Pb;
-  }
-  return (2 * n_run + n_u + n_b) * 8 + 2 * n_cnt * 4 + 256;
+  lw.ukeys = c.take<uint64_t>(P > slg::kVsSortCap ? (size_t)vc.nq * P : 0);
+  lw.bkeys = c.take<uint64_t>(P + Pb > slg::kVsSortCap ? (size_t)vc.nq * Pb : 0);
+  lw.cnt = c.take<uint32_t>(2 * n_cnt);  // (hy_fold reads the key counts right behind the run counts)
+  lw.P = P;
+  lw.Pb = Pb;
+  if (w) *w = lw;
+  return c.bytes();
 }
 
 void slghost::hy_fold(const VsCall &vc, const HyWork &w, const HyKeys &k, hipStream_t st) {
-  const uint32_t K = vc.cand, NC = vc.n_clauses;
-  const uint32_t fold_n = slg::kVsSortCap - K;  // keys of a pass: with the running list they sort in LDS
-  slg::VsSelectParams sel{};
-  sel.run = w.run;
-  sel.run_cnt = w.cnt;
-  sel.dlist = w.dlist;
-  sel.nq = vc.nq;
-  sel.k = K;
-  sel.in = k.keys;
-  sel.in_stride = (uint32_t)k.stride;
+  slg::VsSelectParams sel = vs_select_params(w.run, w.cnt, w.dlist, k.keys, vc.nq, vc.cand, 0, (uint32_t)k.stride);
   sel.in_off = k.q_cand;
-  sel.in_cnt = w.cnt + (size_t)NC * vc.nq;
+  sel.in_cnt = w.cnt + (size_t)vc.n_clauses * vc.nq;
   sel.in_base = k.slot_lo;
   sel.q0 = k.q_lo;
-  sel.n_in = fold_n;
-  const uint64_t passes = std::max<uint64_t>((k.max_cap + fold_n - 1) / fold_n, 1);
-  const size_t lds = (size_t)slg::vs_pow2((uint32_t)std::min<uint64_t>(K + k.max_cap, slg::kVsSortCap)) * 8;
-  for (uint64_t t = 0; t < passes; t++) {
-    sel.in_skip = (uint32_t)(t * fold_n);
-    sel.final_ = t + 1 == passes ? 1u : 0u;
-    launch_kernel_lds(slg::vs_select_kernel, sel, dim3(k.q_hi - k.q_lo, NC), slg::kVsSortThreads, lds, st);
-  }
+  vs_fold(sel, k.max_cap, dim3(k.q_hi - k.q_lo, vc.n_clauses), st);
 }
 
 void slghost::hy_blend(const VsCall &vc, const VsArgs &a, const HyWork &w, const uint32_t *bm_doc,
                        const uint32_t *bm_seg, const float *bm_score, const uint32_t *bm_count, uint32_t bm_k,
                        hipStream_t st) {
-  const IndexState &S = *vc.S;
-  slg::VsBlendParams bp{};
-  bp.dlist = w.dlist;
-  bp.run_cnt = w.cnt;
-  bp.nq = vc.nq;
-  bp.k = vc.cand;
-  bp.n_clauses = vc.n_clauses;
-  bp.alpha = a.alpha;
-  for (uint32_t c = 0; c < vc.n_clauses; c++) bp.metric[c] = vc.metric[c];
-  bp.doc_base = S.d_doc_base.as<uint32_t>();
-  bp.n_segs = (uint32_t)S.segs.size();
-  bp.ukeys = w.ukeys;
-  bp.P = w.P;
-  bp.k_out = vc.k_out;
-  bp.out_doc = a.out_doc;
-  bp.out_seg = a.out_seg;
-  bp.out_score = a.out_score;
-  bp.out_vec = a.out_vec;
-  bp.out_count = a.out_count;
-  bp.out_total = a.out_total;
+  slg::VsBlendParams bp = vs_blend_params(vc, a, w.dlist, w.cnt, vc.cand, w.ukeys, w.P);
   bp.bm_doc = bm_doc;
   bp.bm_seg = bm_seg;
   bp.bm_score = bm_score;
@@ -855,10 +903,8 @@ int slg_vector_search_batch(slg_index *ix, uint32_t nq, uint32_t n_clauses, cons
                             const float *qvecs, const float *alpha, const float *boost, const int32_t *q_filter,
                             uint32_t cand_size, uint32_t k_out, uint32_t *out_doc, uint32_t *out_seg,
                             float *out_score, float *out_vec_score, uint32_t *out_count, uint64_t *out_total) {
-  return guarded([&] {
-    vs_staged(ix, nq, n_clauses, clause_field, cand_size, 0, 0, k_out,
-              {qvecs, alpha, boost, q_filter, out_doc, out_seg, out_score, out_vec_score, out_count, out_total});
-  });
+  return vs_entry(VsKind::Exact, false, ix, nq, n_clauses, clause_field, cand_size, 0, k_out,
+                  {qvecs, alpha, boost, q_filter, out_doc, out_seg, out_score, out_vec_score, out_count, out_total});
 }
 
 int slg_vector_search_batch_device(slg_index *ix, uint32_t nq, uint32_t n_clauses, const uint32_t *clause_field,
@@ -866,11 +912,9 @@ int slg_vector_search_batch_device(slg_index *ix, uint32_t nq, uint32_t n_clause
                                    const int32_t *d_q_filter, uint32_t cand_size, uint32_t k_out,
                                    uint32_t *d_out_doc, uint32_t *d_out_seg, float *d_out_score,
                                    float *d_out_vec_score, uint32_t *d_out_count, uint64_t *d_out_total) {
-  return guarded([&] {
-    vs_device(ix, nq, n_clauses, clause_field, cand_size, 0, 0, k_out,
-              {d_qvecs, d_alpha, d_boost, d_q_filter, d_out_doc, d_out_seg, d_out_score, d_out_vec_score,
-               d_out_count, d_out_total});
-  });
+  return vs_entry(VsKind::Exact, true, ix, nq, n_clauses, clause_field, cand_size, 0, k_out,
+                  {d_qvecs, d_alpha, d_boost, d_q_filter, d_out_doc, d_out_seg, d_out_score, d_out_vec_score,
+                   d_out_count, d_out_total});
 }
 
 int slg_vector_search_batch_approx(slg_index *ix, uint32_t nq, uint32_t n_clauses, const uint32_t *clause_field,
@@ -878,11 +922,8 @@ int slg_vector_search_batch_approx(slg_index *ix, uint32_t nq, uint32_t n_clause
                                    uint32_t cand_size, uint32_t refine, uint32_t k_out, uint32_t *out_doc,
                                    uint32_t *out_seg, float *out_score, float *out_vec_score, uint32_t *out_count,
                                    uint64_t *out_total) {
-  return guarded([&] {
-    vs_check_refine(cand_size, refine);
-    vs_staged(ix, nq, n_clauses, clause_field, cand_size, refine, 0, k_out,
-              {qvecs, alpha, boost, q_filter, out_doc, out_seg, out_score, out_vec_score, out_count, out_total});
-  });
+  return vs_entry(VsKind::Approx, false, ix, nq, n_clauses, clause_field, cand_size, refine, k_out,
+                  {qvecs, alpha, boost, q_filter, out_doc, out_seg, out_score, out_vec_score, out_count, out_total});
 }
 
 int slg_vector_search_batch_approx_device(slg_index *ix, uint32_t nq, uint32_t n_clauses, const uint32_t *clause_field,
@@ -891,12 +932,9 @@ int slg_vector_search_batch_approx_device(slg_index *ix, uint32_t nq, uint32_t n
                                           uint32_t k_out, uint32_t *d_out_doc, uint32_t *d_out_seg,
                                           float *d_out_score, float *d_out_vec_score, uint32_t *d_out_count,
                                           uint64_t *d_out_total) {
-  return guarded([&] {
-    vs_check_refine(cand_size, refine);
-    vs_device(ix, nq, n_clauses, clause_field, cand_size, refine, 0, k_out,
-              {d_qvecs, d_alpha, d_boost, d_q_filter, d_out_doc, d_out_seg, d_out_score, d_out_vec_score,
-               d_out_count, d_out_total});
-  });
+  return vs_entry(VsKind::Approx, true, ix, nq, n_clauses, clause_field, cand_size, refine, k_out,
+                  {d_qvecs, d_alpha, d_boost, d_q_filter, d_out_doc, d_out_seg, d_out_score, d_out_vec_score,
+                   d_out_count, d_out_total});
 }
 
 int slg_vector_search_batch_ivf(slg_index *ix, uint32_t nq, uint32_t n_clauses, const uint32_t *clause_field,
@@ -904,11 +942,8 @@ int slg_vector_search_batch_ivf(slg_index *ix, uint32_t nq, uint32_t n_clauses, 
                                 uint32_t cand_size, uint32_t nprobe, uint32_t k_out, uint32_t *out_doc,
                                 uint32_t *out_seg, float *out_score, float *out_vec_score, uint32_t *out_count,
                                 uint64_t *out_total) {
-  return guarded([&] {
-    vs_check_ivf(cand_size, nprobe);
-    vs_staged(ix, nq, n_clauses, clause_field, cand_size, 0, nprobe, k_out,
-              {qvecs, alpha, boost, q_filter, out_doc, out_seg, out_score, out_vec_score, out_count, out_total});
-  });
+  return vs_entry(VsKind::Ivf, false, ix, nq, n_clauses, clause_field, cand_size, nprobe, k_out,
+                  {qvecs, alpha, boost, q_filter, out_doc, out_seg, out_score, out_vec_score, out_count, out_total});
 }
 
 int slg_vector_search_batch_ivf_device(slg_index *ix, uint32_t nq, uint32_t n_clauses, const uint32_t *clause_field,
@@ -916,12 +951,9 @@ int slg_vector_search_batch_ivf_device(slg_index *ix, uint32_t nq, uint32_t n_cl
                                        const int32_t *d_q_filter, uint32_t cand_size, uint32_t nprobe, uint32_t k_out,
                                        uint32_t *d_out_doc, uint32_t *d_out_seg, float *d_out_score,
                                        float *d_out_vec_score, uint32_t *d_out_count, uint64_t *d_out_total) {
-  return guarded([&] {
-    vs_check_ivf(cand_size, nprobe);
-    vs_device(ix, nq, n_clauses, clause_field, cand_size, 0, nprobe, k_out,
-              {d_qvecs, d_alpha, d_boost, d_q_filter, d_out_doc, d_out_seg, d_out_score, d_out_vec_score,
-               d_out_count, d_out_total});
-  });
+  return vs_entry(VsKind::Ivf, true, ix, nq, n_clauses, clause_field, cand_size, nprobe, k_out,
+                  {d_qvecs, d_alpha, d_boost, d_q_filter, d_out_doc, d_out_seg, d_out_score, d_out_vec_score,
+                   d_out_count, d_out_total});
 }
 
 }  // extern "C"

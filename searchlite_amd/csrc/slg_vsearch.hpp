@@ -18,6 +18,10 @@
 // union of the clause lists, applies compute_hybrid_score at bm25 = 0 (:225-254) and sorts the union.
 // Hybrid text + vector search (slg_hybrid.hpp) gathers its keys from a batch's matched docs and shares the
 // last two steps: vs_select_kernel folds them, vs_blend_kernel<true> adds the BM25 hits to the union.
+//
+// What the scans of the family share lives here: vs_tile_scores (the f32 tile body of vs_scan_kernel and of the
+// cosine IVF scan), VsEpilogue / vs_tile_topk / vs_write_partials (the fused top-k epilogue of those two and of the bf16 first
+// pass; the flat id of a tile row and the slot of a partial list are functors) and VsReject.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -106,8 +110,9 @@ inline size_t vs_scan_lds_bytes(bool topk, uint32_t cap) {
   return (size_t)(kVsTileDocs + kVsTileQ) * kVsRow * 4 + kVsTileDocs * 8 + (topk ? (size_t)kVsTileQ * cap * 8 : 0);
 }
 
-// ---- the epilogue of a scan tile, shared by vs_scan_kernel and the bf16 first pass of the two-pass search
-//      (slg_vsearch_approx.hpp): both leave the scores of a 64 x 128 tile in the C/D layout of the 16x16 MFMAs ----
+// ---- the epilogue of a scan tile, shared by vs_scan_kernel, the bf16 first pass of the two-pass search
+//      (slg_vsearch_approx.hpp) and the IVF scan (slg_vsearch_ivf.hpp): all three leave the scores of a 64 x 128
+//      tile in the C/D layout of the 16x16 MFMAs ----
 // what a lane carries from tile to tile: its query (16w + qc of the workgroup's 64), the query's boost and
 // filter, and (top-k form) the entries its query's LDS buffer holds and the threshold key
 struct VsEpilogue {
@@ -141,13 +146,14 @@ struct VsReject {
     return rej_all || (rej && ((rej[doc >> 5] >> (doc & 31)) & 1u));
   }
 };
-// the fused top-k epilogue of one tile of 128 docs from flat doc `base`: sim(acc[ti][r], i) is the similarity of this
-// lane's query and doc i = 16 ti + 4 g + r of the tile (s_seg[i] = its segment or ~0: no vector, s_doc[i] = the doc
-// in it).  Times the boost it becomes a key, and the keys that beat the threshold go to the query's buffer.
+// the fused top-k epilogue of one tile of 128 docs: sim(acc[ti][r], i) is the similarity of this lane's query and
+// doc i = 16 ti + 4 g + r of the tile (s_seg[i] = its segment or ~0: no vector, s_doc[i] = the doc in it, flat(i) =
+// its flat id: base + i in the scans of the flat space, a table in the IVF scan).  Times the boost it becomes a
+// key, and the keys that beat the threshold go to the query's buffer.
 // (The store form stays inline in each scan kernel: as a function it costs vs_scan_kernel<1, false> two more
 // AGPR copies.)
-template <typename Sim>
-__device__ __forceinline__ void vs_tile_topk(const VsScanParams &p, VsEpilogue &e, const uint32_t base,
+template <typename Flat, typename Sim>
+__device__ __forceinline__ void vs_tile_topk(const VsScanParams &p, VsEpilogue &e, Flat &&flat,
                                              const uint32_t *s_seg, const uint32_t *s_doc, const f32x4_t (&acc)[8],
                                              Sim &&sim) {
   const uint32_t lane = e.lane, w = e.w, qc = e.qc, g = e.g, cap = e.cap;
@@ -164,7 +170,7 @@ __device__ __forceinline__ void vs_tile_topk(const VsScanParams &p, VsEpilogue &
       float s = sim(acc[ti][r], i);
       s = s * bst;
       const uint32_t seg = s_seg[i];
-      const uint32_t hi = ordered_score(s), lo = ~(base + i);
+      const uint32_t hi = ordered_score(s), lo = ~flat(i);
       auto beats = [&]() { return hi > th_hi || (hi == th_hi && lo > th_lo); };
       bool pass = q_ok && seg != 0xFFFFFFFFu && beats();
       if (__ballot(pass) == 0ull) continue;
@@ -202,16 +208,98 @@ __device__ __forceinline__ void vs_tile_topk(const VsScanParams &p, VsEpilogue &
   e.th_lo = th_lo;
 }
 
-// (top-k form, after the last tile) the chunk's partial list of each query: its k best, sorted
-__device__ __forceinline__ void vs_write_partials(const VsScanParams &p, const VsEpilogue &e, const uint32_t q0) {
+// (top-k form, after the last tile) the partial list of each query of the wave: its k best, sorted, at slot *o of
+// p.out, as slot(j, &o) says for the wave's query j: write it, skip this query, or stop (no later query has a slot).
+// The scans of the flat space write the slot of (query, chunk), the IVF scan that of (query, probe rank, chunk)
+enum VsSlot { kVsSlotWrite, kVsSlotSkip, kVsSlotStop };
+template <typename Slot>
+__device__ __forceinline__ void vs_write_partials(const VsScanParams &p, const VsEpilogue &e, Slot &&slot) {
   for (uint32_t j = 0; j < 16; j++) {
-    const uint32_t q = q0 + 16 * e.w + j;
-    if (q >= p.nq) break;
+    size_t o = 0;
+    const VsSlot s = slot(j, &o);
+    if (s == kVsSlotStop) break;
+    if (s == kVsSlotSkip) continue;
     uint64_t *b = e.s_buf + (size_t)(16 * e.w + j) * e.cap;
     const uint32_t kept = vs_compact(b, rl(e.cnt, j), p.k, e.lane);
-    p.out[((size_t)q * p.n_chunks + blockIdx.y) * kVsSmallK + e.lane] = e.lane < kept ? b[e.lane] : 0ull;
+    p.out[o * kVsSmallK + e.lane] = e.lane < kept ? b[e.lane] : 0ull;
   }
 }
+
+// ---- the f32 tile body, shared by vs_scan_kernel and the cosine IVF scan (slg_vsearch_ivf.hpp): the raw scores of the
+//      workgroup's 64 queries (rows qrow, null = none) x 128 docs (rows drow) into acc, through the LDS tiles sA
+//      [128][kVsRow] / sB [64][kVsRow], kVsKc dimensions at a time, the next step's rows in flight under this one's
+//      products.  METRIC 0: dot products on the matrix cores; 1: sum (q - x)^2 on the VALU.  The order of the
+//      floating-point operations is part of the result: both searches return the same bits ----
+template <int METRIC>
+__device__ __forceinline__ void vs_tile_scores(float *sA, float *sB, const float *(&drow)[4],
+                                               const float *(&qrow)[2], const uint32_t dim, const bool vec4,
+                                               const bool qvec4, f32x4_t (&acc)[8]) {
+  const uint32_t t = threadIdx.x, lane = t & 63, w = t >> 6;
+  const uint32_t qc = lane & 15u, g = lane >> 4;
+  const uint32_t col = 4 * (t & 7u);
+#pragma unroll
+  for (int i = 0; i < 8; i++) acc[i] = (f32x4_t){0.f, 0.f, 0.f, 0.f};
+  f32x4_t ra[4], rb[2];
+#pragma unroll
+  for (int i = 0; i < 4; i++) ra[i] = vs_ld4(drow[i], col, dim, vec4);
+#pragma unroll
+  for (int j = 0; j < 2; j++) rb[j] = vs_ld4(qrow[j], col, dim, qvec4);
+  for (uint32_t k0 = 0; k0 < dim; k0 += kVsKc) {
+    __syncthreads();  // the previous step's reads are done
+#pragma unroll
+    for (int i = 0; i < 4; i++) *reinterpret_cast<f32x4_t *>(sA + ((t >> 3) + 32 * i) * kVsRow + col) = ra[i];
+#pragma unroll
+    for (int j = 0; j < 2; j++) *reinterpret_cast<f32x4_t *>(sB + ((t >> 3) + 32 * j) * kVsRow + col) = rb[j];
+    __syncthreads();
+    if (k0 + kVsKc < dim) {  // the next step's rows, in flight under this step's products
+#pragma unroll
+      for (int i = 0; i < 4; i++) ra[i] = vs_ld4(drow[i], k0 + kVsKc + col, dim, vec4);
+#pragma unroll
+      for (int j = 0; j < 2; j++) rb[j] = vs_ld4(qrow[j], k0 + kVsKc + col, dim, qvec4);
+    }
+    if (METRIC == 0) {
+      // lane group g feeds k = 4g + c of each 16-wide half (component c = one MFMA): the same k
+      // permutation on both operands
+#pragma unroll
+      for (int h = 0; h < 2; h++) {
+        const f32x4_t b = *reinterpret_cast<const f32x4_t *>(sB + (16 * w + qc) * kVsRow + 16 * h + 4 * g);
+#pragma unroll
+        for (int ti = 0; ti < 8; ti++) {
+          const f32x4_t a = *reinterpret_cast<const f32x4_t *>(sA + (16 * ti + qc) * kVsRow + 16 * h + 4 * g);
+          acc[ti] = __builtin_amdgcn_mfma_f32_16x16x4f32(a.x, b.x, acc[ti], 0, 0, 0);
+          acc[ti] = __builtin_amdgcn_mfma_f32_16x16x4f32(a.y, b.y, acc[ti], 0, 0, 0);
+          acc[ti] = __builtin_amdgcn_mfma_f32_16x16x4f32(a.z, b.z, acc[ti], 0, 0, 0);
+          acc[ti] = __builtin_amdgcn_mfma_f32_16x16x4f32(a.w, b.w, acc[ti], 0, 0, 0);
+        }
+      }
+    } else {
+      for (uint32_t kk = 0; kk < kVsKc; kk += 4) {
+        const f32x4_t b = *reinterpret_cast<const f32x4_t *>(sB + (16 * w + qc) * kVsRow + kk);
+#pragma unroll
+        for (int ti = 0; ti < 8; ti++) {
+#pragma unroll
+          for (int r = 0; r < 4; r++) {
+            const f32x4_t a = *reinterpret_cast<const f32x4_t *>(sA + (16 * ti + 4 * g + r) * kVsRow + kk);
+            const float d0 = b.x - a.x, d1 = b.y - a.y, d2 = b.z - a.z, d3 = b.w - a.w;
+            float s = acc[ti][r];
+            s += d0 * d0;
+            s += d1 * d1;
+            s += d2 * d2;
+            s += d3 * d3;
+            acc[ti][r] = s;
+          }
+        }
+      }
+    }
+  }
+}
+// metric_similarity (vectors/mod.rs:107-120) of a raw score of vs_tile_scores
+template <int METRIC>
+struct VsExactSim {
+  __device__ __forceinline__ float operator()(float s, uint32_t) const {
+    return METRIC == 0 ? (s != s ? 0.0f : s) : -sqrtf(s);
+  }
+};
 
 // METRIC 0: cosine on the matrix cores; 1: L2 on the VALU.  TOPK: fused top-k (else: store keys).
 // Lane l of wave w holds, per tile t of 16 docs, the scores of query 16w + (l & 15) and docs
@@ -243,7 +331,6 @@ __global__ void __launch_bounds__(256) vs_scan_kernel(VsScanParams p) {
     const uint32_t q = q0 + (t >> 3) + 32 * j;
     qrow[j] = q < p.nq ? p.qvecs + (size_t)q * p.q_stride + p.q_off : nullptr;
   }
-  const uint32_t col = 4 * (t & 7u);
   const uint32_t total = p.doc_base[p.n_segs];
 
   const uint32_t tb = p.tile_begin + blockIdx.y * p.tiles_per_block;
@@ -275,65 +362,11 @@ __global__ void __launch_bounds__(256) vs_scan_kernel(VsScanParams p) {
       }
     }
     f32x4_t acc[8];
-#pragma unroll
-    for (int i = 0; i < 8; i++) acc[i] = (f32x4_t){0.f, 0.f, 0.f, 0.f};
-    f32x4_t ra[4], rb[2];
-#pragma unroll
-    for (int i = 0; i < 4; i++) ra[i] = vs_ld4(drow[i], col, dim, vec4);
-#pragma unroll
-    for (int j = 0; j < 2; j++) rb[j] = vs_ld4(qrow[j], col, dim, vec4 && p.qvec4);
-    for (uint32_t k0 = 0; k0 < dim; k0 += kVsKc) {
-      __syncthreads();  // the previous step's reads are done
-#pragma unroll
-      for (int i = 0; i < 4; i++) *reinterpret_cast<f32x4_t *>(sA + ((t >> 3) + 32 * i) * kVsRow + col) = ra[i];
-#pragma unroll
-      for (int j = 0; j < 2; j++) *reinterpret_cast<f32x4_t *>(sB + ((t >> 3) + 32 * j) * kVsRow + col) = rb[j];
-      __syncthreads();
-      if (k0 + kVsKc < dim) {  // the next step's rows, in flight under this step's products
-#pragma unroll
-        for (int i = 0; i < 4; i++) ra[i] = vs_ld4(drow[i], k0 + kVsKc + col, dim, vec4);
-#pragma unroll
-        for (int j = 0; j < 2; j++) rb[j] = vs_ld4(qrow[j], k0 + kVsKc + col, dim, vec4 && p.qvec4);
-      }
-      if (METRIC == 0) {
-        // lane group g feeds k = 4g + c of each 16-wide half (component c = one MFMA): the same k
-        // permutation on both operands
-#pragma unroll
-        for (int h = 0; h < 2; h++) {
-          const f32x4_t b = *reinterpret_cast<const f32x4_t *>(sB + (16 * w + qc) * kVsRow + 16 * h + 4 * g);
-#pragma unroll
-          for (int ti = 0; ti < 8; ti++) {
-            const f32x4_t a = *reinterpret_cast<const f32x4_t *>(sA + (16 * ti + qc) * kVsRow + 16 * h + 4 * g);
-            acc[ti] = __builtin_amdgcn_mfma_f32_16x16x4f32(a.x, b.x, acc[ti], 0, 0, 0);
-            acc[ti] = __builtin_amdgcn_mfma_f32_16x16x4f32(a.y, b.y, acc[ti], 0, 0, 0);
-            acc[ti] = __builtin_amdgcn_mfma_f32_16x16x4f32(a.z, b.z, acc[ti], 0, 0, 0);
-            acc[ti] = __builtin_amdgcn_mfma_f32_16x16x4f32(a.w, b.w, acc[ti], 0, 0, 0);
-          }
-        }
-      } else {
-        for (uint32_t kk = 0; kk < kVsKc; kk += 4) {
-          const f32x4_t b = *reinterpret_cast<const f32x4_t *>(sB + (16 * w + qc) * kVsRow + kk);
-#pragma unroll
-          for (int ti = 0; ti < 8; ti++) {
-#pragma unroll
-            for (int r = 0; r < 4; r++) {
-              const f32x4_t a = *reinterpret_cast<const f32x4_t *>(sA + (16 * ti + 4 * g + r) * kVsRow + kk);
-              const float d0 = b.x - a.x, d1 = b.y - a.y, d2 = b.z - a.z, d3 = b.w - a.w;
-              float s = acc[ti][r];
-              s += d0 * d0;
-              s += d1 * d1;
-              s += d2 * d2;
-              s += d3 * d3;
-              acc[ti][r] = s;
-            }
-          }
-        }
-      }
-    }
+    vs_tile_scores<METRIC>(sA, sB, drow, qrow, dim, vec4, vec4 && p.qvec4, acc);
     // ---- epilogue: metric_similarity (vectors/mod.rs:107-120), * boost (api/reader.rs:2421) ----
-    const auto sim = [](float s, uint32_t) { return METRIC == 0 ? (s != s ? 0.0f : s) : -sqrtf(s); };
+    const VsExactSim<METRIC> sim;
     if constexpr (TOPK) {
-      vs_tile_topk(p, e, base, s_seg, s_doc, acc, sim);
+      vs_tile_topk(p, e, [&](uint32_t i) { return base + i; }, s_seg, s_doc, acc, sim);
     } else {
       VsReject rejected;
 #pragma unroll
@@ -353,7 +386,11 @@ __global__ void __launch_bounds__(256) vs_scan_kernel(VsScanParams p) {
     __syncthreads();  // s_seg / s_doc of the next tile
   }
   if (!TOPK) return;
-  vs_write_partials(p, e, q0);
+  vs_write_partials(p, e, [&](uint32_t j, size_t *o) {
+    const uint32_t q = q0 + 16 * w + j;
+    *o = (size_t)q * p.n_chunks + blockIdx.y;
+    return q < p.nq ? kVsSlotWrite : kVsSlotStop;
+  });
 }
 
 // block-wide bitonic sort, descending, of P (a power of two) keys at a (LDS or global memory)

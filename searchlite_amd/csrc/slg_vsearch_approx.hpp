@@ -194,7 +194,7 @@ __global__ void __launch_bounds__(256) vs_scan_bf16_kernel(VsScanBf16Params pp) 
       return -sqrtf(fmaxf((s_nrm[i] + qn) - 2.0f * s, 0.0f));
     };
     if constexpr (TOPK) {
-      vs_tile_topk(p, e, base, s_seg, s_doc, acc, sim);
+      vs_tile_topk(p, e, [&](uint32_t i) { return base + i; }, s_seg, s_doc, acc, sim);
     } else {
       VsReject rejected;
 #pragma unroll
@@ -214,7 +214,11 @@ __global__ void __launch_bounds__(256) vs_scan_bf16_kernel(VsScanBf16Params pp) 
     __syncthreads();  // s_seg / s_doc / s_nrm of the next tile
   }
   if (!TOPK) return;
-  vs_write_partials(p, e, q0);
+  vs_write_partials(p, e, [&](uint32_t j, size_t *o) {
+    const uint32_t q = q0 + 16 * w + j;
+    *o = (size_t)q * p.n_chunks + blockIdx.y;
+    return q < p.nq ? kVsSlotWrite : kVsSlotStop;
+  });
 }
 
 // ---- pass 2: the exact score of every first-pass candidate ----

@@ -10,6 +10,9 @@
 //     vs_select_kernel's top nprobe; (2) the probes are inverted into per-list query groups (count, exclusive scan,
 //     fill) and a work table of (list, 64 of its queries, chunk of its docs) items; (3) vs_ivf_scan_kernel walks the
 //     table and leaves one partial top-k list per (query, probe rank, chunk); vs_select_kernel folds them.
+//     The scan owns how an item finds its queries and docs; the tile body (vs_tile_scores; the L2 form keeps a copy
+//     of the L2 body, which is faster there) and the top-k epilogue (vs_tile_topk, vs_write_partials) are the exact
+//     scan's functions.
 #pragma once
 
 #include "slg_vsearch.hpp"
@@ -210,6 +213,19 @@ __global__ void __launch_bounds__(kIvfScanThreads) vs_ivf_plan_kernel(IvfPlanPar
     *p.n_items = ibase < p.items_cap ? ibase : p.items_cap;
   }
 }
+// the items of one list at items[at .. end): tiles of 64 of its n_queries queries (from g0) x chunks of chunk_docs of
+// its len docs (from begin of the segment's array); an item's slot = slot0 + its chunk
+__device__ __forceinline__ void ivf_emit_items(const IvfPlanParams &p, uint32_t at, const uint32_t end, uint32_t seg,
+                                               uint32_t begin, uint32_t len, uint32_t chunk_docs, uint32_t g0,
+                                               uint32_t n_queries, uint32_t slot0, uint32_t uncl) {
+  for (uint32_t q0 = 0; q0 < n_queries; q0 += kVsTileQ)
+    for (uint32_t d = 0, ch = 0; d < len; d += chunk_docs, ch++) {
+      if (at >= end) return;
+      const uint32_t de = d + chunk_docs < len ? d + chunk_docs : len;
+      p.items[at++] = IvfItem{seg, begin + d, begin + de, g0 + q0, n_queries - q0 < kVsTileQ ? n_queries - q0 : kVsTileQ,
+                              slot0 + ch, uncl, 0u};
+    }
+}
 // thread i: pair i = (query, probe rank) goes to its list's group; list i's items go to the work table
 __global__ void __launch_bounds__(256) vs_ivf_items_kernel(IvfPlanParams p) {
   const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -227,22 +243,11 @@ __global__ void __launch_bounds__(256) vs_ivf_items_kernel(IvfPlanParams p) {
   const uint32_t end = p.ioff[i + 1] < p.items_cap ? p.ioff[i + 1] : p.items_cap;
   if (i < p.n_lists) {
     uint32_t seg, begin;
-    const uint32_t len = ivf_list_len(p, i, &seg, &begin), c = p.cnt[i], g0 = p.goff[i];
-    for (uint32_t q0 = 0; q0 < c; q0 += kVsTileQ)
-      for (uint32_t d = 0, ch = 0; d < len; d += p.list_chunk_docs, ch++) {
-        if (at >= end) return;
-        const uint32_t de = d + p.list_chunk_docs < len ? d + p.list_chunk_docs : len;
-        p.items[at++] = IvfItem{seg, begin + d, begin + de, g0 + q0, c - q0 < kVsTileQ ? c - q0 : kVsTileQ, ch, 0u, 0u};
-      }
+    const uint32_t len = ivf_list_len(p, i, &seg, &begin);
+    ivf_emit_items(p, at, end, seg, begin, len, p.list_chunk_docs, p.goff[i], p.cnt[i], 0u, 0u);
   } else {
     const IvfUncl u = p.uncl[i - p.n_lists];
-    for (uint32_t q0 = 0; q0 < p.nq; q0 += kVsTileQ)
-      for (uint32_t d = 0, ch = 0; d < u.n_docs; d += u.chunk_docs, ch++) {
-        if (at >= end) return;
-        const uint32_t de = d + u.chunk_docs < u.n_docs ? d + u.chunk_docs : u.n_docs;
-        p.items[at++] = IvfItem{u.seg, d, de, q0, p.nq - q0 < kVsTileQ ? p.nq - q0 : kVsTileQ,
-                                p.n_probe * p.list_chunks + u.slot + ch, 1u, 0u};
-      }
+    ivf_emit_items(p, at, end, u.seg, 0u, u.n_docs, u.chunk_docs, 0u, p.nq, p.n_probe * p.list_chunks + u.slot, 1u);
   }
 }
 
@@ -261,8 +266,9 @@ inline size_t vs_ivf_scan_lds_bytes(uint32_t cap) {
   return vs_scan_lds_bytes(true, cap) + kVsTileDocs * 4 + kVsTileQ * 8;
 }
 
-// vs_scan_kernel's tile over the docs of a list and the queries of its group; the epilogue is vs_tile_topk's with the
-// doc's flat id per tile row (its own copy: the exact scans keep their registers).  TOPK: the only form built.
+// vs_scan_kernel's tile over the docs of a list and the queries of its group: the tile body is vs_tile_scores (cosine)
+// and the epilogue vs_tile_topk / vs_write_partials (slg_vsearch.hpp), with the docs' flat ids from a table and one
+// VsEpilogue per item.  TOPK: the only form built.
 template <int METRIC, bool TOPK>
 __global__ void __launch_bounds__(256) vs_ivf_scan_kernel(VsIvfScanParams ip) {
   static_assert(TOPK, "the store form of the IVF scan is not built");
@@ -280,8 +286,6 @@ __global__ void __launch_bounds__(256) vs_ivf_scan_kernel(VsIvfScanParams ip) {
   const uint32_t qc = lane & 15u, g = lane >> 4;
   const uint32_t dim = p.dim, cap = p.cap;
   const bool vec4 = (dim & 3u) == 0;
-  const uint32_t col = 4 * (t & 7u);
-  uint64_t *my_buf = s_buf + (size_t)(16 * w + qc) * cap;
   const uint32_t n_items = *ip.n_items;
 
   for (uint32_t it = blockIdx.x; it < n_items; it += gridDim.x) {
@@ -303,12 +307,12 @@ __global__ void __launch_bounds__(256) vs_ivf_scan_kernel(VsIvfScanParams ip) {
       s_slot[t] = slot;
     }
     __syncthreads();
-    // this lane's query in the epilogue
+    // this lane's query in the epilogue (~0, which no nq exceeds: none)
     const uint32_t myq = s_q[16 * w + qc];
     const bool q_ok = myq != 0xFFFFFFFFu;
     const float bst = q_ok && p.boost ? p.boost[(size_t)myq * p.n_clauses + p.clause] : 1.0f;
     const int32_t flt = q_ok && p.q_filter ? p.q_filter[myq] : -1;
-    uint32_t cnt = 0, th_hi = 0, th_lo = 0;
+    VsEpilogue e{lane, w, qc, g, myq, bst, flt, cap, s_buf, s_buf + (size_t)(16 * w + qc) * cap, 0, 0, 0};
     const float *qrow[2];
 #pragma unroll
     for (int j = 0; j < 2; j++) {
@@ -343,40 +347,33 @@ __global__ void __launch_bounds__(256) vs_ivf_scan_kernel(VsIvfScanParams ip) {
         }
       }
       f32x4_t acc[8];
+      if constexpr (METRIC == 0) {
+        vs_tile_scores<0>(sA, sB, drow, qrow, dim, vec4, vec4 && p.qvec4, acc);
+      } else {
+        // the L2 tile body of vs_tile_scores, written out: through the function this kernel takes 165 registers
+        // for 284 and, on the one workgroup per CU its grid has, the call at nprobe 1 / 64 took 7.623 / 19.109 ms
+        // for 6.326 / 16.126 (profiles/vsearch_fold_time.txt)
+        const uint32_t col = 4 * (t & 7u);
 #pragma unroll
-      for (int i = 0; i < 8; i++) acc[i] = (f32x4_t){0.f, 0.f, 0.f, 0.f};
-      f32x4_t ra[4], rb[2];
+        for (int i = 0; i < 8; i++) acc[i] = (f32x4_t){0.f, 0.f, 0.f, 0.f};
+        f32x4_t ra[4], rb[2];
 #pragma unroll
-      for (int i = 0; i < 4; i++) ra[i] = vs_ld4(drow[i], col, dim, vec4);
+        for (int i = 0; i < 4; i++) ra[i] = vs_ld4(drow[i], col, dim, vec4);
 #pragma unroll
-      for (int j = 0; j < 2; j++) rb[j] = vs_ld4(qrow[j], col, dim, vec4 && p.qvec4);
-      for (uint32_t k0 = 0; k0 < dim; k0 += kVsKc) {
-        __syncthreads();  // the previous step's reads are done
+        for (int j = 0; j < 2; j++) rb[j] = vs_ld4(qrow[j], col, dim, vec4 && p.qvec4);
+        for (uint32_t k0 = 0; k0 < dim; k0 += kVsKc) {
+          __syncthreads();  // the previous step's reads are done
 #pragma unroll
-        for (int i = 0; i < 4; i++) *reinterpret_cast<f32x4_t *>(sA + ((t >> 3) + 32 * i) * kVsRow + col) = ra[i];
+          for (int i = 0; i < 4; i++) *reinterpret_cast<f32x4_t *>(sA + ((t >> 3) + 32 * i) * kVsRow + col) = ra[i];
 #pragma unroll
-        for (int j = 0; j < 2; j++) *reinterpret_cast<f32x4_t *>(sB + ((t >> 3) + 32 * j) * kVsRow + col) = rb[j];
-        __syncthreads();
-        if (k0 + kVsKc < dim) {  // the next step's rows, in flight under this step's products
+          for (int j = 0; j < 2; j++) *reinterpret_cast<f32x4_t *>(sB + ((t >> 3) + 32 * j) * kVsRow + col) = rb[j];
+          __syncthreads();
+          if (k0 + kVsKc < dim) {  // the next step's rows, in flight under this step's sums
 #pragma unroll
-          for (int i = 0; i < 4; i++) ra[i] = vs_ld4(drow[i], k0 + kVsKc + col, dim, vec4);
+            for (int i = 0; i < 4; i++) ra[i] = vs_ld4(drow[i], k0 + kVsKc + col, dim, vec4);
 #pragma unroll
-          for (int j = 0; j < 2; j++) rb[j] = vs_ld4(qrow[j], k0 + kVsKc + col, dim, vec4 && p.qvec4);
-        }
-        if (METRIC == 0) {
-#pragma unroll
-          for (int h = 0; h < 2; h++) {
-            const f32x4_t b = *reinterpret_cast<const f32x4_t *>(sB + (16 * w + qc) * kVsRow + 16 * h + 4 * g);
-#pragma unroll
-            for (int ti = 0; ti < 8; ti++) {
-              const f32x4_t a = *reinterpret_cast<const f32x4_t *>(sA + (16 * ti + qc) * kVsRow + 16 * h + 4 * g);
-              acc[ti] = __builtin_amdgcn_mfma_f32_16x16x4f32(a.x, b.x, acc[ti], 0, 0, 0);
-              acc[ti] = __builtin_amdgcn_mfma_f32_16x16x4f32(a.y, b.y, acc[ti], 0, 0, 0);
-              acc[ti] = __builtin_amdgcn_mfma_f32_16x16x4f32(a.z, b.z, acc[ti], 0, 0, 0);
-              acc[ti] = __builtin_amdgcn_mfma_f32_16x16x4f32(a.w, b.w, acc[ti], 0, 0, 0);
-            }
+            for (int j = 0; j < 2; j++) rb[j] = vs_ld4(qrow[j], k0 + kVsKc + col, dim, vec4 && p.qvec4);
           }
-        } else {
           for (uint32_t kk = 0; kk < kVsKc; kk += 4) {
             const f32x4_t b = *reinterpret_cast<const f32x4_t *>(sB + (16 * w + qc) * kVsRow + kk);
 #pragma unroll
@@ -396,58 +393,15 @@ __global__ void __launch_bounds__(256) vs_ivf_scan_kernel(VsIvfScanParams ip) {
           }
         }
       }
-      // ---- epilogue: vs_tile_topk with s_flat[i] for base + i ----
-      VsReject rejected;
-#pragma unroll
-      for (int ti = 0; ti < 8; ti++) {
-#pragma unroll
-        for (int r = 0; r < 4; r++) {
-          const uint32_t i = 16 * ti + 4 * g + r;
-          float s = METRIC == 0 ? (acc[ti][r] != acc[ti][r] ? 0.0f : acc[ti][r]) : -sqrtf(acc[ti][r]);
-          s = s * bst;
-          const uint32_t seg = s_seg[i];
-          const uint32_t hi = ordered_score(s), lo = ~s_flat[i];
-          auto beats = [&]() { return hi > th_hi || (hi == th_hi && lo > th_lo); };
-          bool pass = q_ok && seg != 0xFFFFFFFFu && beats();
-          if (__ballot(pass) == 0ull) continue;
-          pass = pass && !rejected(p, flt, seg, s_doc[i]);
-          uint64_t need = __ballot(g == 0 && cnt + 4 > cap);
-          while (need) {
-            const uint32_t j = (uint32_t)__builtin_ctzll(need);
-            need &= need - 1;
-            const uint32_t n = rl(cnt, j);
-            uint64_t *b = s_buf + (size_t)(16 * w + j) * cap;
-            const uint32_t kept = vs_compact(b, n, p.k, lane);
-            if (qc == j) {
-              cnt = kept;
-              if (n >= p.k) {
-                const uint64_t kth = b[p.k - 1];
-                th_hi = (uint32_t)(kth >> 32);
-                th_lo = (uint32_t)kth;
-              }
-            }
-          }
-          pass = pass && beats();
-          const uint64_t m = __ballot(pass);
-          const uint32_t b0 = (uint32_t)(m >> qc) & 1u, b1 = (uint32_t)(m >> (16 + qc)) & 1u,
-                         b2 = (uint32_t)(m >> (32 + qc)) & 1u, b3 = (uint32_t)(m >> (48 + qc)) & 1u;
-          const uint32_t pre = (g > 0 ? b0 : 0u) + (g > 1 ? b1 : 0u) + (g > 2 ? b2 : 0u);
-          wave_fence();
-          if (pass) my_buf[cnt + pre] = ((uint64_t)hi << 32) | lo;
-          wave_fence();
-          cnt += b0 + b1 + b2 + b3;
-        }
-      }
+      vs_tile_topk(p, e, [&](uint32_t i) { return s_flat[i]; }, s_seg, s_doc, acc, VsExactSim<METRIC>());
       __syncthreads();  // s_seg / s_doc / s_flat of the next tile
     }
-    // the item's partial list of each of its queries: the k best, sorted, in the slot of (query, probe rank, chunk)
-    for (uint32_t j = 0; j < 16; j++) {
-      const uint32_t q = s_q[16 * w + j];
-      if (q == 0xFFFFFFFFu || s_slot[16 * w + j] >= ip.slots_q) continue;
-      uint64_t *b = s_buf + (size_t)(16 * w + j) * cap;
-      const uint32_t kept = vs_compact(b, rl(cnt, j), p.k, lane);
-      p.out[((size_t)q * ip.slots_q + s_slot[16 * w + j]) * kVsSmallK + lane] = lane < kept ? b[lane] : 0ull;
-    }
+    // the item's partial list of each of its queries, in the slot of (query, probe rank, chunk)
+    vs_write_partials(p, e, [&](uint32_t j, size_t *o) {
+      const uint32_t q = s_q[16 * w + j], slot = s_slot[16 * w + j];
+      *o = (size_t)q * ip.slots_q + slot;
+      return q != 0xFFFFFFFFu && slot < ip.slots_q ? kVsSlotWrite : kVsSlotSkip;
+    });
   }
 }
 

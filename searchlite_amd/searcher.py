@@ -1097,22 +1097,39 @@ class GpuIndex:
         vector.  clause_field [n_clauses] field ids; qvecs [nq, sum of the clause dims] (a query's
         clause vectors one after another); alpha / boost [nq, n_clauses]; q_filter [nq] filter ids
         (< 0: none).  -> (doc, seg, score, vec_score) [nq, k_out], count [nq], total [nq] (union size)."""
+        return self._vector_call(self._lib.slg_vector_search_batch, clause_field, qvecs, alpha, boost, q_filter,
+                                 (cand_size,), k_out)
+
+    def _vector_call(self, fn, clause_field, qvecs, alpha, boost, q_filter, ints, k_out, text=None):
+        """One host-array call of the vector search family: stage the clause arrays and the filter ids, allocate
+        the six outputs and call fn with `ints` (cand_size and the call's own integer) before k_out.  text: the
+        hybrid call's (q_offsets, q_terms, q_weights, k, strategy), which fn takes ahead of the clause arrays."""
         cf = np.ascontiguousarray(clause_field, dtype=np.uint32)
         nc = len(cf)
         qvecs = np.ascontiguousarray(qvecs, dtype=np.float32)
-        nq = qvecs.shape[0]
+        nq = qvecs.shape[0] if text is None else len(text[0]) - 1
         alpha, bst = _f32(alpha, (nq, nc)), _f32(boost, (nq, nc))
         flt = None if q_filter is None else np.ascontiguousarray(q_filter, dtype=np.int32)
+        clause = (nc, _ptr(cf), _ptr(qvecs), _ptr(alpha), _ptr(bst))
+        if text is None:
+            head = clause + (_ptr(flt),)
+        else:
+            head = tuple(_ptr(x) for x in text[:3]) + (None, _ptr(flt), int(text[3]), int(text[4])) + clause
         doc = np.zeros((nq, k_out), np.uint32)
         seg = np.zeros((nq, k_out), np.uint32)
         score = np.zeros((nq, k_out), np.float32)
         vec = np.zeros((nq, k_out), np.float32)
         count = np.zeros(nq, np.uint32)
         total = np.zeros(nq, np.uint64)
-        N.check(self._lib.slg_vector_search_batch(
-            self._h, nq, nc, _ptr(cf), _ptr(qvecs), _ptr(alpha), _ptr(bst), _ptr(flt), int(cand_size), int(k_out),
-            _ptr(doc), _ptr(seg), _ptr(score), _ptr(vec), _ptr(count), _ptr(total)))
+        N.check(fn(self._h, nq, *head, *(int(i) for i in ints), int(k_out),
+                   _ptr(doc), _ptr(seg), _ptr(score), _ptr(vec), _ptr(count), _ptr(total)))
         return doc, seg, score, vec, count, total
+
+    def _vector_call_device(self, fn, nq, clause_field, d_in, ints, k_out, d_out) -> None:
+        """One device-pointer call of the family: d_in = (d_qvecs, d_alpha, d_boost, d_q_filter), d_out the six
+        output pointers; clause_field stays a host array."""
+        cf = np.ascontiguousarray(clause_field, dtype=np.uint32)
+        N.check(fn(self._h, nq, len(cf), _ptr(cf), *d_in, *(int(i) for i in ints), int(k_out), *d_out))
 
     def quantize_vector_field(self, field: int = 0) -> None:
         """Build the bf16 copy of vector field `field` on the device (slg_index_quantize_vector_field): what
@@ -1141,32 +1158,17 @@ class GpuIndex:
         the field's bf16 copy (quantize_vector_field) are scored again from the f32 store, and the best cand_size
         of those form the clause's list.  Arguments and result as vector_search(); every returned score is the
         exact call's, and refine >= the live docs with a vector makes the whole result the exact call's."""
-        cf = np.ascontiguousarray(clause_field, dtype=np.uint32)
-        nc = len(cf)
-        qvecs = np.ascontiguousarray(qvecs, dtype=np.float32)
-        nq = qvecs.shape[0]
-        alpha, bst = _f32(alpha, (nq, nc)), _f32(boost, (nq, nc))
-        flt = None if q_filter is None else np.ascontiguousarray(q_filter, dtype=np.int32)
-        doc = np.zeros((nq, k_out), np.uint32)
-        seg = np.zeros((nq, k_out), np.uint32)
-        score = np.zeros((nq, k_out), np.float32)
-        vec = np.zeros((nq, k_out), np.float32)
-        count = np.zeros(nq, np.uint32)
-        total = np.zeros(nq, np.uint64)
-        N.check(self._lib.slg_vector_search_batch_approx(
-            self._h, nq, nc, _ptr(cf), _ptr(qvecs), _ptr(alpha), _ptr(bst), _ptr(flt), int(cand_size), int(refine),
-            int(k_out), _ptr(doc), _ptr(seg), _ptr(score), _ptr(vec), _ptr(count), _ptr(total)))
-        return doc, seg, score, vec, count, total
+        return self._vector_call(self._lib.slg_vector_search_batch_approx, clause_field, qvecs, alpha, boost, q_filter,
+                                 (cand_size, refine), k_out)
 
     def vector_search_approx_device(self, nq, clause_field, d_qvecs, d_alpha, d_boost, d_q_filter, cand_size, refine,
                                     k_out, d_out_doc, d_out_seg, d_out_score, d_out_vec, d_out_count,
                                     d_out_total) -> None:
         """Device-pointer form of vector_search_approx (ints; d_boost / d_q_filter may be None; clause_field
         stays a host array), asynchronous on the index stream."""
-        cf = np.ascontiguousarray(clause_field, dtype=np.uint32)
-        N.check(self._lib.slg_vector_search_batch_approx_device(
-            self._h, nq, len(cf), _ptr(cf), d_qvecs, d_alpha, d_boost, d_q_filter, int(cand_size), int(refine),
-            int(k_out), d_out_doc, d_out_seg, d_out_score, d_out_vec, d_out_count, d_out_total))
+        self._vector_call_device(self._lib.slg_vector_search_batch_approx_device, nq, clause_field,
+                                 (d_qvecs, d_alpha, d_boost, d_q_filter), (cand_size, refine), k_out,
+                                 (d_out_doc, d_out_seg, d_out_score, d_out_vec, d_out_count, d_out_total))
 
     def cluster_vector_field(self, field: int, per_segment) -> None:
         """Build the inverted-file lists of vector field `field` on the device (slg_index_cluster_vector_field):
@@ -1251,32 +1253,17 @@ class GpuIndex:
         from the f32 store, and the best cand_size form the clause's list.  Arguments and result as
         vector_search(); every returned score is the exact call's, and nprobe >= the lists of every clause's
         field makes the whole result the exact call's.  cand_size <= 64."""
-        cf = np.ascontiguousarray(clause_field, dtype=np.uint32)
-        nc = len(cf)
-        qvecs = np.ascontiguousarray(qvecs, dtype=np.float32)
-        nq = qvecs.shape[0]
-        alpha, bst = _f32(alpha, (nq, nc)), _f32(boost, (nq, nc))
-        flt = None if q_filter is None else np.ascontiguousarray(q_filter, dtype=np.int32)
-        doc = np.zeros((nq, k_out), np.uint32)
-        seg = np.zeros((nq, k_out), np.uint32)
-        score = np.zeros((nq, k_out), np.float32)
-        vec = np.zeros((nq, k_out), np.float32)
-        count = np.zeros(nq, np.uint32)
-        total = np.zeros(nq, np.uint64)
-        N.check(self._lib.slg_vector_search_batch_ivf(
-            self._h, nq, nc, _ptr(cf), _ptr(qvecs), _ptr(alpha), _ptr(bst), _ptr(flt), int(cand_size), int(nprobe),
-            int(k_out), _ptr(doc), _ptr(seg), _ptr(score), _ptr(vec), _ptr(count), _ptr(total)))
-        return doc, seg, score, vec, count, total
+        return self._vector_call(self._lib.slg_vector_search_batch_ivf, clause_field, qvecs, alpha, boost, q_filter,
+                                 (cand_size, nprobe), k_out)
 
     def vector_search_ivf_device(self, nq, clause_field, d_qvecs, d_alpha, d_boost, d_q_filter, cand_size, nprobe,
                                  k_out, d_out_doc, d_out_seg, d_out_score, d_out_vec, d_out_count,
                                  d_out_total) -> None:
         """Device-pointer form of vector_search_ivf (ints; d_boost / d_q_filter may be None; clause_field stays a
         host array), asynchronous on the index stream."""
-        cf = np.ascontiguousarray(clause_field, dtype=np.uint32)
-        N.check(self._lib.slg_vector_search_batch_ivf_device(
-            self._h, nq, len(cf), _ptr(cf), d_qvecs, d_alpha, d_boost, d_q_filter, int(cand_size), int(nprobe),
-            int(k_out), d_out_doc, d_out_seg, d_out_score, d_out_vec, d_out_count, d_out_total))
+        self._vector_call_device(self._lib.slg_vector_search_batch_ivf_device, nq, clause_field,
+                                 (d_qvecs, d_alpha, d_boost, d_q_filter), (cand_size, nprobe), k_out,
+                                 (d_out_doc, d_out_seg, d_out_score, d_out_vec, d_out_count, d_out_total))
 
     def search_hybrid(self, q_offsets, q_terms, q_weights, k: int, clause_field, qvecs, alpha, cand_size: int,
                       k_out: int, boost=None, strategy: int = Wand, q_filter=None, **plans):
@@ -1290,32 +1277,16 @@ class GpuIndex:
         q_offsets = np.ascontiguousarray(q_offsets, dtype=np.uint32)
         q_terms = np.ascontiguousarray(q_terms, dtype=np.uint32)
         q_weights = np.ascontiguousarray(q_weights, dtype=np.float32)
-        nq = len(q_offsets) - 1
-        cf = np.ascontiguousarray(clause_field, dtype=np.uint32)
-        nc = len(cf)
-        qvecs = np.ascontiguousarray(qvecs, dtype=np.float32)
-        alpha, bst = _f32(alpha, (nq, nc)), _f32(boost, (nq, nc))
-        flt = None if q_filter is None else np.ascontiguousarray(q_filter, dtype=np.int32)
-        doc = np.zeros((nq, k_out), np.uint32)
-        seg = np.zeros((nq, k_out), np.uint32)
-        score = np.zeros((nq, k_out), np.float32)
-        vec = np.zeros((nq, k_out), np.float32)
-        count = np.zeros(nq, np.uint32)
-        total = np.zeros(nq, np.uint64)
-        N.check(self._lib.slg_search_batch_hybrid(
-            self._h, nq, _ptr(q_offsets), _ptr(q_terms), _ptr(q_weights), None, _ptr(flt), int(k), int(strategy),
-            nc, _ptr(cf), _ptr(qvecs), _ptr(alpha), _ptr(bst), int(cand_size), int(k_out),
-            _ptr(doc), _ptr(seg), _ptr(score), _ptr(vec), _ptr(count), _ptr(total)))
-        return doc, seg, score, vec, count, total
+        return self._vector_call(self._lib.slg_search_batch_hybrid, clause_field, qvecs, alpha, boost, q_filter,
+                                 (cand_size,), k_out, text=(q_offsets, q_terms, q_weights, k, strategy))
 
     def vector_search_device(self, nq, clause_field, d_qvecs, d_alpha, d_boost, d_q_filter, cand_size, k_out,
                              d_out_doc, d_out_seg, d_out_score, d_out_vec, d_out_count, d_out_total) -> None:
         """Device-pointer form of vector_search (ints; d_boost / d_q_filter may be None; clause_field
         stays a host array), asynchronous on the index stream."""
-        cf = np.ascontiguousarray(clause_field, dtype=np.uint32)
-        N.check(self._lib.slg_vector_search_batch_device(
-            self._h, nq, len(cf), _ptr(cf), d_qvecs, d_alpha, d_boost, d_q_filter, int(cand_size), int(k_out),
-            d_out_doc, d_out_seg, d_out_score, d_out_vec, d_out_count, d_out_total))
+        self._vector_call_device(self._lib.slg_vector_search_batch_device, nq, clause_field,
+                                 (d_qvecs, d_alpha, d_boost, d_q_filter), (cand_size,), k_out,
+                                 (d_out_doc, d_out_seg, d_out_score, d_out_vec, d_out_count, d_out_total))
 
     def rerank_batch_device(self, nq, d_qvecs, d_alpha, d_cand_doc, d_cand_seg, d_cand_bm25,
                             d_cand_count, max_cand, k_out, d_out_doc, d_out_seg, d_out_score,

@@ -11,7 +11,9 @@ clustering time of each store.
 Kernel times: run the script under `rocprofv3 --kernel-trace --output-format csv -d DIR -- python
 tools/vector_ivf_time.py --schedule DIR/schedule.json`, then `python tools/vector_ivf_time.py --parse DIR`: every
 call ends with one vs_blend_kernel, so the trace splits into calls, and the schedule names each call.
-usage (GPU box): python tools/vector_ivf_time.py [--reps N] [--rows N] [--no-uniform] [--schedule FILE] | --parse DIR"""
+--metric 1: the same rows as an L2 store (vec_metric 1).
+usage (GPU box): python tools/vector_ivf_time.py [--reps N] [--rows N] [--no-uniform] [--metric 0|1] [--schedule FILE] |
+--parse DIR"""
 import argparse
 import csv
 import glob
@@ -28,6 +30,7 @@ ap = argparse.ArgumentParser()
 ap.add_argument("--reps", type=int, default=10)
 ap.add_argument("--rows", type=int, default=1_000_000)
 ap.add_argument("--lists", type=int, default=1024)
+ap.add_argument("--metric", type=int, choices=(0, 1), default=0)
 ap.add_argument("--no-uniform", action="store_true", help="skip the uniformly random store")
 ap.add_argument("--schedule", default=None, help="write the label of every call, in order, to this file")
 ap.add_argument("--parse", default=None, help="a rocprofv3 output directory holding schedule.json")
@@ -87,7 +90,8 @@ def clustered_rows(count, centres, seed, sigma=0.02):
 def index_of(vals):
     seg = Segment(n_docs=len(vals), term_offsets=[0, 1], doc_ids=[0], tfs=[1],
                   field_doc_len=[np.ones(len(vals), np.float32)], field_avgdl=[1.0], docs=float(len(vals)),
-                  vec_dim=dim, vec_metric=0, vec_offsets=np.arange(len(vals), dtype=np.uint32), vec_values=vals)
+                  vec_dim=dim, vec_metric=args.metric, vec_offsets=np.arange(len(vals), dtype=np.uint32),
+                  vec_values=vals)
     ix = searcher.GpuIndex([seg])
     ix.set_stream(torch.cuda.current_stream().cuda_stream)
     return ix

@@ -2,7 +2,8 @@
 Headline: config 5's store (1M x 768 f32, cosine), 1024 queries, one clause, cand_size 20, k_out 11.
 Large path: cand_size 1000 over two clauses (the 768-d field and a 256-d field), k_out 1001.
 Scan-kernel time comes from a rocprofv3 --kernel-trace --stats run of this script (vs_scan_kernel rows).
-usage (GPU box): python tools/vector_search_time.py [--shape headline|large|both] [--iters N]"""
+--metric 1: the same rows as an L2 store (vec_metric 1).
+usage (GPU box): python tools/vector_search_time.py [--shape headline|large|both] [--iters N] [--metric 0|1]"""
 import argparse
 import os
 import sys
@@ -19,12 +20,13 @@ PEAK_F32_MFMA_TF = 157.3
 ap = argparse.ArgumentParser()
 ap.add_argument("--shape", default="both")
 ap.add_argument("--iters", type=int, default=5)
+ap.add_argument("--metric", type=int, choices=(0, 1), default=0)
 args = ap.parse_args()
 
 n, dim, nq = 1_000_000, 768, 1024
 vals = corpus.unit_vectors(n, dim, seed=11)
 seg = Segment(n_docs=n, term_offsets=[0, 1], doc_ids=[0], tfs=[1], field_doc_len=[np.ones(n, np.float32)],
-              field_avgdl=[1.0], docs=float(n), vec_dim=dim, vec_metric=0,
+              field_avgdl=[1.0], docs=float(n), vec_dim=dim, vec_metric=args.metric,
               vec_offsets=np.arange(n, dtype=np.uint32), vec_values=vals)
 ix = searcher.GpuIndex([seg])
 L = N.load()
@@ -68,7 +70,7 @@ if args.shape in ("headline", "both"):
     qv = torch.from_numpy(corpus.unit_vectors(nq, dim, seed=12)).to(dev)
     timed("headline 1M x 768 cosine, 1 clause, cand 20, k_out 11", [0], qv, 20, 11)
 if args.shape in ("large", "both"):
-    f1 = ix.add_vector_field([(0, np.arange(n, dtype=np.uint32), corpus.unit_vectors(n, 256, seed=31))])
+    f1 = ix.add_vector_field([(args.metric, np.arange(n, dtype=np.uint32), corpus.unit_vectors(n, 256, seed=31))])
     qv = torch.from_numpy(np.concatenate([corpus.unit_vectors(nq, dim, seed=12), corpus.unit_vectors(nq, 256, seed=13)],
                                          axis=1)).to(dev)
     timed("large path 2 clauses (768-d + 256-d), cand 1000, k_out 1001", [0, f1], qv, 1000, 1001)
